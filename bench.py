@@ -14,11 +14,20 @@ N > 1: `python bench.py --gpus N` re-executes itself under torch.distributed.run
 windows are sharded by id (w mod N), no data-path collective (independent windows); RCCL carries the
 barrier, the max-over-ranks time and the all-gather of the per-window result records (every id must come back exactly once).
 
-Output contract: the LAST stdout line is ONE compact JSON object (< 4 KB: the driver keeps an 8 KB tail) -- the contract keys, `config`,
-`roofline` (dominant kernel), `cpu_baseline`, `parity`, `device_resident_solves_per_s`, a few headline scalars and `details_file`.  Everything
-else (per-kernel rooflines, configs 3 / 5 / tumrs, small batches, host-side figures) goes to that file: gpurun_out/bench_details_n<N>.json.
+Output contract: the LAST stdout line is ONE compact JSON object (< 4 KB: the driver keeps an 8 KB tail) -- the contract keys and `config`.
+A plain run does only what that headline needs: set up, warm up, time --steps steps, write the outputs (--dump-outputs DIR) and print the
+line (`details_file` null).
 
-Objects (compact line: roofline, parity, cpu_baseline; the rest in the details file):
+--full adds every side measurement below: `roofline` (dominant kernel), `cpu_baseline`, `parity`, `device_resident_solves_per_s` and a few
+headline scalars in the line, `details_file` names the side file with everything else (per-kernel rooflines, configs 3 / 5 / tumrs, small
+batches, host-side figures), and at N > 1 the all-gather of the per-window records is checked.
+
+--dump-outputs DIR: after the timed steps every rank writes what the timed path handed its caller in the LAST step -- the solved states
+(quat, pos, bias, rho, line_delay) of its windows, concatenated in window order, and their global ids (window_id) -- as float64
+DIR/<name>.npy (rank<r>_<name>.npy at N > 1); above 64 MB in all, a fixed seeded sample of the windows.  The inputs are seeded: the same
+arguments give the same windows in every run.
+
+Objects (--full; compact line: roofline, parity, cpu_baseline; the rest in the details file):
   roofline       dominant kernel of a profiled solve of one handle (HIP events on the solver's stream, other handles idle):
                  achieved = algorithmic bytes or flops per launch / average launch duration, against 8 TB/s HBM
                  or 78.6 TFLOP/s fp64 -- whichever roof the kernel is closer to; both fractions, the PMC traffic and the issue counters
@@ -409,6 +418,41 @@ def write_details(out, world):
         return None
 
 
+DUMP_LIMIT = 64 << 20    # bytes of --dump-outputs, all ranks together
+
+
+def dump_outputs(dirname, outs, wins, ids, rank, world):
+    """--dump-outputs: the states of the last timed step (outs[si] = the quat / pos / bias / rho / line-delay arrays handle si's batch came
+    back in, wins[si] its windows) as float64 .npy files, windows in local order with their global ids; a fixed seeded sample of the windows
+    when all of them would exceed this rank's share of DUMP_LIMIT."""
+    import numpy as np
+    names = ("quat", "pos", "bias", "rho", "line_delay")
+    per_win = []                                        # (handle, index in the handle's batch, offsets of its K / F / L rows)
+    for si, wl in enumerate(wins):
+        k0 = f0 = l0 = 0
+        for j, w in enumerate(wl):
+            per_win.append((si, j, k0, f0, l0, w))
+            k0 += w.K; f0 += w.F; l0 += w.L
+    nbytes = lambda w: 8 * (7 * w.K + 6 * w.F + w.L + 2)
+    sel = np.arange(len(per_win))
+    budget = DUMP_LIMIT // max(world, 1)
+    if sum(nbytes(w) for *_, w in per_win) > budget:
+        m = max(1, budget // max(nbytes(w) for *_, w in per_win))
+        sel = np.sort(np.random.default_rng(12345).choice(len(per_win), size=min(m, len(per_win)), replace=False))
+    parts = {n: [] for n in names}
+    for i in sel:
+        si, j, k0, f0, l0, w = per_win[i]
+        q, p, b, r, ld = outs[si]
+        parts["quat"].append(q[k0:k0 + w.K]); parts["pos"].append(p[k0:k0 + w.K]); parts["bias"].append(b[f0:f0 + w.F])
+        parts["rho"].append(r[l0:l0 + w.L]); parts["line_delay"].append(ld[j:j + 1])
+    arrays = {n: np.concatenate(parts[n]) for n in names}
+    arrays["window_id"] = np.asarray(ids, dtype=np.float64)[sel]
+    os.makedirs(dirname, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, prefix + n + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def mixed_batch(cv, torch, config, nwin, ndist, iters, device, steps=3):
     """`nwin` windows per launch made of `ndist` DISTINCT windows (seeds 5000 ..: generated by tools/make_windows.py on a process pool in a
     fresh interpreter) against the same launch made of the headline's 64 distinct ones: the 64-periodic batch terminates in lock-step, a mixed
@@ -469,9 +513,13 @@ def main():
     ap.add_argument("--gpu-slots", type=int, default=0, help="handles allowed inside ctvio_solve at once (0: half of the streams, at least 1)")
     ap.add_argument("--host-threads", type=int, default=0, help="packing threads per handle (0: cores / streams, at most 16)")
     ap.add_argument("--device-resident-only", action="store_true", help="time the device-resident solve instead (diagnostics)")
-    ap.add_argument("--quick", action="store_true", help="skip the side measurements (single window, configs 3 / 5, tumrs, 8-rank host share)")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip the side measurements (single window, configs 3 / 5, tumrs, 8-rank host share)")
     ap.add_argument("--shared-caller-buffers", action="store_true",
                     help="replicas of a distinct window share its caller buffers (rounds 1-4: the packer then reads 11 MB out of the host's L3 instead of streaming 1.5 GB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (device-resident rate, rooflines, parity, CPU baselines, other configs, details file)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solved states of the last timed step to DIR/<name>.npy (float64, <= 64 MB: a seeded sample beyond)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -527,7 +575,8 @@ def main():
             wc = w if args.shared_caller_buffers else w.copy()
             keep.append(wc)                                   # (the C window points into the copy's arrays)
             arr[j] = cv.capi.to_cwindow(wc, keep)
-            arr_sh[j] = cv.capi.to_cwindow(w, keep)
+            if args.full:                                     # (the shared-buffer side measurement only)
+                arr_sh[j] = cv.capi.to_cwindow(w, keep)
             wl.append(w)
         cbatches_shared.append(arr_sh)
         K = sum(w.K for w in wl); F = sum(w.F for w in wl); L = sum(w.L for w in wl)
@@ -603,6 +652,11 @@ def main():
         prepare_resident()
     steps(args.warmup, resident_headline)
     t_total = timed(args.steps, resident_headline)
+    if args.dump_outputs:
+        if resident_headline:   # the timed solves left their states on the device: read them back as the end-to-end path would
+            for si in range(nstream):
+                cv.capi.check(lib.ctvio_get_batch_state(solvers[si]._h, *[cv.capi._p(a) for a in outs[si]]))
+        dump_outputs(args.dump_outputs, outs, [wl for _, wl in keeps], my_ids, rank, world)
     per_rank_rate = [args.windows * args.steps / t for t in rank_times]
     n_solved = args.windows * world * args.steps
     fp_bytes = 8 if args.precision == "fp64" else 4
@@ -625,6 +679,13 @@ def main():
     if args.windows <= 64:   # BASELINE configs[3] as written (64 windows over 8 GPUs = 8 per rank) is launch-latency territory: say what a step took
         out["small_batch_latency"] = {"windows_per_rank": args.windows, "end_to_end_ms_per_step_by_rank": [1e3 * t / args.steps for t in rank_times],
                                       "note": "one step = set_batch + solve + get_batch_state of this many windows on every rank, concurrently"}
+    if not args.full:        # a plain run: the headline only
+        if rank == 0:
+            print(compact_line(out, None), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- device-resident rate next to it (no packing, no PCIe: ctvio_restore_state on the device between solves)
     if not resident_headline:
         prepare_resident()

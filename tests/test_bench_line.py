@@ -55,3 +55,38 @@ def test_traffic_is_tied_to_the_kernel_sources():
     assert len(h) == 64 and h == bench.csrc_sha256()
     pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
     assert "_source" in pmc      # (whether the hashes agree depends on the last profile run: the bench prints null when they do not)
+
+
+def test_dump_outputs_writes_float64_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: every window's state in window order with its global id; past the size limit a fixed seeded sample of windows whose
+    rows still line up with their ids."""
+    import types
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(0)
+    wins, outs = [], []
+    for si in range(2):                                  # two handles of 5 windows, of different sizes
+        wl = [types.SimpleNamespace(K=4 + j, F=3, L=2 * j) for j in range(5)]
+        K, F, L = sum(w.K for w in wl), sum(w.F for w in wl), sum(w.L for w in wl)
+        outs.append((rng.random((K, 4)), rng.random((K, 3)), rng.random((F, 6)), rng.random(max(L, 1)), rng.random(5)))
+        wins.append(wl)
+    ids = [3 * i for i in range(10)]
+    bench.dump_outputs(str(tmp_path / "all"), outs, wins, ids, 0, 1)
+    d = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("quat", "pos", "bias", "rho", "line_delay", "window_id")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    np.testing.assert_array_equal(d["window_id"], ids)
+    np.testing.assert_array_equal(d["quat"], np.concatenate([outs[0][0], outs[1][0]]))
+    np.testing.assert_array_equal(d["rho"], np.concatenate([outs[0][3][:20], outs[1][3][:20]]))
+    np.testing.assert_array_equal(d["line_delay"], np.concatenate([outs[0][4], outs[1][4]]))
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2 * 8 * (7 * 8 + 6 * 3 + 8 + 2))     # room for two of the largest windows
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs, wins, ids, 1, 2)             # rank 1 of 2: half the room, its own file names
+    a = {n: np.load(tmp_path / "a" / ("rank1_" + n + ".npy")) for n in ("quat", "line_delay", "window_id")}
+    b = {n: np.load(tmp_path / "b" / ("rank1_" + n + ".npy")) for n in ("quat", "line_delay", "window_id")}
+    assert len(a["window_id"]) == 1 and all(np.array_equal(a[n], b[n]) for n in a)  # the same sample every run
+    i = ids.index(int(a["window_id"][0]))
+    si, j = divmod(i, 5)
+    k0 = sum(w.K for w in wins[si][:j])
+    np.testing.assert_array_equal(a["quat"], outs[si][0][k0:k0 + wins[si][j].K])
+    assert a["line_delay"][0] == outs[si][4][j]

@@ -1,6 +1,6 @@
 """GPU: the N > 1 paths, exercised on ONE device so that the first run on an 8-GPU node is not the first run at all.
 
-* `bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one process per rank): both ranks map to device 0
+* `bench.py --gpus 2 --full` exactly as the driver launches it (torch.distributed.run, one process per rank): both ranks map to device 0
   (rank -> local % device_count; the collectives go over gloo when ranks share a device, over RCCL otherwise), windows shard by id,
   barrier + max-over-ranks timing + all-gather of the per-window records run, and rank 0 prints the contract's JSON line.
 * `ctvio_solve_sharded` with two shards on one device (TEST-ONLY switch CTVIO_SHARD_OVERSUBSCRIBE=1): two host threads, two solver
@@ -38,7 +38,7 @@ def _bench_line(args, timeout=900):
 
 
 def test_bench_two_ranks_on_one_device():
-    d = _bench_line(["--gpus", "2", "--quick", "--windows", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = _bench_line(["--gpus", "2", "--full", "--quick", "--windows", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["value"] > 0 and d["unit"] == "solves/s" and d["higher_is_better"] is True
     assert d["ms_per_step"] > 0 and abs(d["value"] - 2 * 128 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]   # whole-job aggregate
@@ -52,7 +52,7 @@ def test_bench_eight_ranks_on_one_device_config4_shape():
     """BASELINE configs[3] as literally written: 64 windows over 8 ranks = 8 per rank, launched as the driver launches an 8-GPU run (all eight
     ranks share device 0 here; collectives over gloo).  The contract line must say n_gpus 8, carry every window id exactly once, one rate per
     rank (the first real SCALE run shows imbalance directly) and the per-step latency of the 8-per-rank shape."""
-    d = _bench_line(["--gpus", "8", "--quick", "--windows", "8", "--streams", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], timeout=1500)
+    d = _bench_line(["--gpus", "8", "--full", "--quick", "--windows", "8", "--streams", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], timeout=1500)
     assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["steps"] == 2
     assert abs(d["value"] - 8 * 8 / (d["ms_per_step"] / 1e3)) < 1e-6 * d["value"]          # whole-job aggregate over the 8 ranks
     ss = d["solve_summary"]
@@ -62,6 +62,35 @@ def test_bench_eight_ranks_on_one_device_config4_shape():
     lat = d["small_batch_latency"]
     assert lat["windows_per_rank"] == 8 and len(lat["end_to_end_ms_per_step_by_rank"]) == 8 and max(lat["end_to_end_ms_per_step_by_rank"]) == pytest.approx(d["ms_per_step"], rel=1e-9)
     assert "mod 8" in d["config"]["sharding"]
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(cv, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints only the headline and, with --dump-outputs, writes the states the timed
+    end-to-end path handed back in its last step: window j of the 16 is seed 1000 + j, solved as a lone Solver solves it."""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--windows", "16", "--unique", "16", "--streams", "2", "--steps", "3",
+           "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["details_file"] is None
+    assert abs(line["value"] - 16 / (line["ms_per_step"] / 1e3)) < 1e-4 * line["value"]
+    assert "roofline" not in line and line["parity"] is None and line["cpu_baseline"] is None
+    d = {n: np.load(tmp_path / (n + ".npy")) for n in ("quat", "pos", "bias", "rho", "line_delay", "window_id")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    np.testing.assert_array_equal(d["window_id"], np.arange(16))
+    ref = [cv.synth.make_window("config2", seed=1000 + j) for j in range(16)]
+    with cv.Solver() as s:
+        s.set_windows(ref)
+        s.solve(15)
+    k0 = f0 = l0 = 0
+    for j, w in enumerate(ref):
+        got = w.copy()
+        got.quat[:] = d["quat"][k0:k0 + w.K]; got.pos[:] = d["pos"][k0:k0 + w.K]; got.bias[:] = d["bias"][f0:f0 + w.F]
+        got.rho[:] = d["rho"][l0:l0 + w.L]; got.ld = float(d["line_delay"][j])
+        assert cv.rel_state_error(got, w)["state"] < 1e-6, j
+        k0 += w.K; f0 += w.F; l0 += w.L
+    assert (k0, f0, l0) == (len(d["quat"]), len(d["bias"]), len(d["rho"]))
 
 
 def test_sharded_entry_two_shards_on_one_device(cv):

@@ -4,7 +4,7 @@
 #   spread x 512 and of the native TUM-RSVI shape x 2048, and the full bench line.
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof6; mkdir -p $O; export TMPDIR=/tmp; cd /tmp
-B1="env CTVIO_SPLIT_LINEARIZE=1 python $R/bench.py --no-cpu-baseline --quick --steps 1 --warmup 1 --device-resident-only --streams 1 --windows 2048"
+B1="env CTVIO_SPLIT_LINEARIZE=1 python $R/bench.py --full --no-cpu-baseline --quick --steps 1 --warmup 1 --device-resident-only --streams 1 --windows 2048"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- $B1 > /dev/null 2> $O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- $B1 > /dev/null 2> $O/pmc_write.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_issue -o m -- $B1 > /dev/null 2> $O/pmc_issue.err
@@ -16,7 +16,7 @@ python tools/prof_summary.py counters $O/pmc_issue.json $(find $O/pmc_issue -nam
 python tools/prof_summary.py counters $O/pmc_lds.json $(find $O/pmc_lds -name "*counter_collection.csv") > $O/pmc_lds_table_2048.txt; head -30 $O/pmc_lds_table_2048.txt
 trace() {  # name, bench args...
   name=$1; shift
-  cd /tmp; rocprofv3 --kernel-trace --stats -d $O/kt_$name -o kt -- env CTVIO_SPLIT_LINEARIZE=1 python $R/bench.py --no-cpu-baseline --quick --streams 1 --device-resident-only "$@" > $O/bench_$name.json 2> $O/err_$name.txt
+  cd $TMPDIR; rocprofv3 --kernel-trace --stats -d $O/kt_$name -o kt -- env CTVIO_SPLIT_LINEARIZE=1 python $R/bench.py --full --no-cpu-baseline --quick --streams 1 --device-resident-only "$@" > $O/bench_$name.json 2> $O/err_$name.txt
   cd $R; python tools/prof_summary.py stats $(find $O/kt_$name -name "*.db") > $O/kernel_stats_$name.txt; find $O/kt_$name -name "*.db" -delete; head -14 $O/kernel_stats_$name.txt
 }
 trace 1x2048 --steps 1 --warmup 1 --windows 2048
@@ -25,9 +25,10 @@ trace config5_x512 --config config5 --windows 512 --unique 8 --steps 2 --warmup 
 trace config5_spread_x512 --config config5_spread --windows 512 --unique 8 --steps 2 --warmup 1
 trace tumrs_x2048 --config tumrs --windows 2048 --unique 16 --steps 1 --warmup 1
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python $R/bench.py --no-cpu-baseline --quick --steps 3 --warmup 1 > $O/kt_bench.json 2> $O/kt.err
+rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python $R/bench.py --full --no-cpu-baseline --quick --steps 3 --warmup 1 > $O/kt_bench.json 2> $O/kt.err
 cd $R; python tools/prof_summary.py stats $(find $O/kt -name "*.db") > $O/kernel_stats_default_4x2048.txt
 cp $O/pmc_traffic.json $O/pmc_issue.json $O/pmc_lds.json $R/profiles/   # (the bench record below prints roofline.traffic from THIS run's counters)
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 300 $O/bench_n1.err; cp gpurun_out/bench_details_n1.json $O/bench_details_n1.json
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 300 $O/bench_n1.err
+cp "$(tail -1 $O/bench_n1.json | python -c 'import json, sys; print(json.load(sys.stdin)["details_file"])')" $O/bench_details_n1.json
 python tools/imu_isa_count.py > $O/imu_isa_count.txt 2>&1
 find $O -name "*.db" -delete; find $O -name "*.csv" -size +4M -delete

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r5s; mkdir -p $O; cd $R
 for cfg in "4 2 16" "4 2 8" "4 3 16" "6 2 16" "6 3 8" "8 4 8" "8 3 4"; do
   set -- $cfg
-  python bench.py --quick --no-cpu-baseline --steps 6 --warmup 2 --streams $1 --gpu-slots $2 --host-threads $3 > $O/b_$1_$2_$3.json 2>/dev/null
+  python bench.py --full --quick --no-cpu-baseline --steps 6 --warmup 2 --streams $1 --gpu-slots $2 --host-threads $3 > $O/b_$1_$2_$3.json 2>/dev/null
   python - <<PY
 import json
 d=json.loads(open('$O/b_$1_$2_$3.json').read().strip().splitlines()[-1])

@@ -6,9 +6,9 @@ if [ "$1" = "none" ]; then :
 elif [ -n "$1" ]; then timeout 1500 python -m pytest tests -m gpu -q -x -k "$1" 2>&1 | tail -25 | tee $O/pytest.txt
 else timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | tail -25 | tee $O/pytest.txt; fi
 if [ "$2" = "skipbench" ]; then exit 0; fi
-if [ "$2" = "full" ]; then timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err
-elif [ "$2" = "quick" ]; then timeout 900 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --quick > $O/bench.json 2> $O/bench.err
-else timeout 900 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; fi
+if [ "$2" = "full" ]; then timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err
+elif [ "$2" = "quick" ]; then timeout 900 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --quick > $O/bench.json 2> $O/bench.err
+else timeout 900 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; fi
 tail -3 $O/bench.err
 python - <<PY
 import json

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3ab2; mkdir -p $O; cd $R
 [ -n "$PYTEST_K" ] && env $B_ENV timeout 900 python -m pytest tests -m gpu -q -x -k "$PYTEST_K" 2>&1 | tail -4
 for v in "$A_ENV" "$B_ENV" "$A_ENV" "$B_ENV"; do
-  env $v timeout 300 python bench.py --windows 2048 --streams 1 --device-resident-only --steps 3 --warmup 1 --no-cpu-baseline > $O/x.json 2> $O/x.err
+  env $v timeout 300 python bench.py --full --windows 2048 --streams 1 --device-resident-only --steps 3 --warmup 1 --no-cpu-baseline > $O/x.json 2> $O/x.err
   python - <<PY
 import json
 try:

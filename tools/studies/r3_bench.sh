@@ -1,7 +1,7 @@
 # default bench line as the driver runs it (N = 1), timed
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3b; mkdir -p $O; cd $R
 [ -n "$PYTEST_K" ] && timeout 900 python -m pytest tests -m gpu -q -x -k "$PYTEST_K" 2>&1 | tail -6
-T0=$(date +%s.%N); timeout 900 python bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err; T1=$(date +%s.%N); echo "bench wall $(echo "$T1 - $T0" | bc) s"; tail -c 600 $O/bench.err | tail -5
+T0=$(date +%s.%N); timeout 900 python bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err; T1=$(date +%s.%N); echo "bench wall $(echo "$T1 - $T0" | bc) s"; tail -c 600 $O/bench.err | tail -5
 python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

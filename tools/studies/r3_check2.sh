@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3c2; mkdir -p $O; export TMPDIR=/tmp; cd $R
 timeout 1500 python -m pytest tests -m gpu -q -x 2>&1 | tail -25 > $O/pytest.txt; cat $O/pytest.txt
 run() {  # name, env, args
-  env $2 timeout 300 python bench.py $3 --no-cpu-baseline > $O/$1.json 2> $O/$1.err
+  env $2 timeout 300 python bench.py --full $3 --no-cpu-baseline > $O/$1.json 2> $O/$1.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3q; mkdir -p $O; export TMPDIR=/tmp; cd $R
 timeout 900 python -m pytest tests -m gpu -q -x -k "${PYTEST_K:-product_parity or lm_step or linearize or edge or ragged or config5 or large_batch}" 2>&1 | tail -8
 run() {
-  env $2 timeout 300 python bench.py $3 --no-cpu-baseline > $O/$1.json 2> $O/$1.err
+  env $2 timeout 300 python bench.py --full $3 --no-cpu-baseline > $O/$1.json 2> $O/$1.err
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3sw; mkdir -p $O; cd $R
 for cfg in "4 2" "4 3" "4 4" "6 3" "8 4" "8 8"; do
   set -- $cfg
-  timeout 300 python bench.py --quick --no-cpu-baseline --steps 6 --warmup 1 --streams $1 --gpu-slots $2 --windows ${WINDOWS:-8192} > $O/s$1_g$2.json 2> $O/s$1_g$2.err
+  timeout 300 python bench.py --full --quick --no-cpu-baseline --steps 6 --warmup 1 --streams $1 --gpu-slots $2 --windows ${WINDOWS:-8192} > $O/s$1_g$2.json 2> $O/s$1_g$2.err
   python - <<PY
 import json
 try:

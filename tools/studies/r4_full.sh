@@ -2,7 +2,7 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4full; mkdir -p $O; export TMPDIR=/tmp; cd $R
 timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | tail -8 > $O/pytest.txt; cat $O/pytest.txt
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; tail -5 $O/bench.err
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -5 $O/bench.err
 python -c "
 import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
 print(d['metric'], d['value'], d['device_resident_solves_per_s'], d['ms_per_step'])
