@@ -636,16 +636,18 @@ class SolverImpl : public SolverBase {
     const Dev &d = dev_;
     const int nw = d.nwin;
     const bool merged = merge_linearize();
+    // (the merged launch carries the prior gradient + cost share only while dx fits its LDS next to the reduction cells)
+    const bool misc_in_pre = merged && d.maxPn <= PRE_LIN_MAX_PN;
     ph_begin(PH_ASM_REST);
     if (!store_path()) { if (!imu_zero_mode()) hipLaunchKernelGGL(k_zero_normal, dim3(64, nw), dim3(256), 0, stream_, d, vis_parts() == 1 ? 1 : 0, mode); }
-    else if (!merged) hipLaunchKernelGGL(k_misc, dim3(nw), dim3(256), std::max(d.maxPn, 1) * sizeof(double), stream_, d, mode, 1, 0);   // prior gradient + cost share
+    else if (!misc_in_pre) hipLaunchKernelGGL(k_misc, dim3(nw), dim3(256), std::max(d.maxPn, 1) * sizeof(double), stream_, d, mode, 1, 0);   // prior gradient + cost share
     ph_end();
     if (merged) {
       // Small batches: TWO launches for the whole linearisation.  k_pre_linearize: the anchors' records, the IMU groups the specialised body
       // leaves out and (store-semantics path) the prior gradient + cost share -- three launches of 5 - 7 us each until round 5; then
       // k_linearize_f64: both evaluations (independent work: their latencies overlap on batches smaller than the chip).  A profiled
       // solve (and CTVIO_SPLIT_LINEARIZE=1, for rocprofv3 runs) keeps everything apart so that each kernel gets its own timing.
-      const int nab = nblk(d.Atot, 64), with_misc = store_path() ? 1 : 0;
+      const int nab = nblk(d.Atot, 64), with_misc = store_path() && misc_in_pre ? 1 : 0;
       hipLaunchKernelGGL(k_pre_linearize, dim3(nab + nw + (with_misc ? nw : 0)), dim3(64), 0, stream_, d, mode, imu_general_only(), imu_zero_mode(), nab, with_misc);
       hipLaunchKernelGGL(k_linearize_f64, dim3(d.Gtot + nblk(d.Vtot, 64)), dim3(64), 0, stream_, d, mode, imu_general_only(), imu_zero_mode());
       return;

@@ -161,13 +161,17 @@ inline bool validate_window(const ctvio_window *w, std::string &err) {
     if (w->bc_i[b] < 0 || w->bc_i[b] >= w->F || w->bc_j[b] < 0 || w->bc_j[b] >= w->F) return bad("bias chain index out of range");
   if (w->pn > 0) {
     if (!w->pJ0 || !w->pr0 || !w->p_x0 || !w->p_kind || !w->p_index || !w->p_off) return bad("null prior pointer");
-    // the kept blocks must tile the prior's columns exactly once (a hole would leave an unmapped column)
-    std::vector<uint8_t> cover((size_t)w->pn, 0);
+    // the kept blocks must tile the prior's columns exactly once (a hole would leave an unmapped column), and name each parameter block
+    // at most once (Ceres refuses duplicate parameter blocks in one residual block; the store-semantics tail maps each unknown to ONE
+    // prior column) -- so pn <= P
+    std::vector<uint8_t> cover((size_t)w->pn, 0), seen((size_t)2 * w->K + 2 * w->F + 1, 0);
     for (int b = 0; b < w->pnb; ++b) {
       const int kind = w->p_kind[b], idx = w->p_index[b];
       const int lim = (kind <= CTVIO_PK_POS) ? w->K : (kind <= CTVIO_PK_BA ? w->F : 1);
       if (kind < 0 || kind > CTVIO_PK_LD || idx < 0 || idx >= lim || w->p_off[b] < 0 || w->p_off[b] + prior_block_size(kind) > w->pn)
         return bad("prior block out of range");
+      const size_t slot = kind <= CTVIO_PK_POS ? (size_t)2 * idx + kind : (kind <= CTVIO_PK_BA ? (size_t)2 * w->K + 2 * idx + (kind - CTVIO_PK_BG) : seen.size() - 1);
+      if (seen[slot]++) return bad("duplicate prior block (the same kind and index kept twice)");
       for (int k = 0; k < prior_block_size(kind); ++k)
         if (cover[w->p_off[b] + k]++) return bad("prior blocks overlap");
     }

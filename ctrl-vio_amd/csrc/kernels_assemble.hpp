@@ -547,8 +547,18 @@ __device__ __forceinline__ const double *prior_block_ptr(const WinMeta &m, int k
 // store != 0 (store-semantics assembly tail): nothing is added here -- the prior's gradient J0^T r0 + (J0^T J0) dx goes to Dev::pgrad,
 // and the assembly looks the prior and the chain up when it writes each entry.
 // with_imu != 0: the window's IMU group tiles are scattered first (assemble_imu_window: the accumulate path's k_assemble_imu, fused).
-// NT threads per workgroup: 256 (k_misc), or 64 when the store-semantics part (prior gradient + cost share, with_imu = 0) rides in k_pre_linearize
-template <int NT> __device__ __forceinline__ void misc_body(const Dev &d, int mode, int store, int with_imu, int w, double *smd /* LDS [pn (+ band)] */, double *red /* LDS [NT] */) {
+// NT threads per workgroup: 256 (k_misc), or 64 when the store-semantics part (prior gradient + cost share, with_imu = 0) rides in k_pre_linearize.
+// The cost share comes out bit-for-bit the same for both NT (the deterministic mode promises equal bits whichever launch shape a batch
+// takes -- profiling and CTVIO_SPLIT_LINEARIZE=1 select k_misc): term e of each list (bias-chain entries, then prior rows) belongs to
+// virtual lane e % MISC_LANES, a lane adds its terms in list order, and the MISC_LANES partial sums go through one fixed tree.  Thread
+// tid of an NT-wide workgroup runs the virtual lanes tid, tid + NT, ...
+constexpr int MISC_LANES = 256;
+// The largest prior dimension whose dx fits k_pre_linearize's LDS in front of the reduction cells.  A valid window has pn <= P (duplicate
+// blocks are refused) and P <= ~590 (the single-workgroup Cholesky); the host launches k_misc instead for a batch beyond this.
+constexpr int PRE_LIN_MAX_PN = 600;
+template <int NT> __device__ __forceinline__ void misc_body(const Dev &d, int mode, int store, int with_imu, int w, double *smd /* LDS [pn (+ band)] */, double *red /* LDS [MISC_LANES] */) {
+  static_assert(MISC_LANES % NT == 0, "every thread runs the same number of virtual lanes");
+  constexpr int R = MISC_LANES / NT;
   // with_imu == 2: the launch carries 144 maxK doubles of LDS behind the prior's dx for the band of the IMU knot blocks (windows with K > 24)
   if (with_imu) { assemble_imu_window(d, mode, w, with_imu == 2 ? smd + ((max(d.maxPn, 1) + 1) & ~1) : nullptr); __syncthreads(); }
   const Lm &lm = d.lm[w];
@@ -561,21 +571,29 @@ template <int NT> __device__ __forceinline__ void misc_body(const Dev &d, int mo
   double *Hpp = d.HppS[tg] + m.H0, *g = d.gS[tg] + m.u0;
   double *dx = smd;                 // [pn]
   const int tid = threadIdx.x;
-  double cost = 0.0;
-  for (int e = tid; e < m.NB * 6; e += NT) {
-    const int b = e / 6, k = e % 6;
-    const int bi = d.bc_i[m.bc0 + b], bj = d.bc_j[m.bc0 + b];
-    const double wv = d.bc_w[(size_t)(m.bc0 + b) * 6 + k];
-    const double r = wv * (bias[6 * (m.bias0 + bj) + k] - bias[6 * (m.bias0 + bi) + k]);
-    cost += 0.5 * r * r;
-    if (LIN) {
-      const int ii = 6 * m.K + 6 * bi + k, jj = 6 * m.K + 6 * bj + k;
-      atomicAdd(&g[ii], -wv * r);
-      atomicAdd(&g[jj], wv * r);
-      atomicAdd(&Hpp[(long long)ii * m.ldh + ii], wv * wv);
-      atomicAdd(&Hpp[(long long)jj * m.ldh + jj], wv * wv);
-      const int hi = max(ii, jj), lo = min(ii, jj);
-      atomicAdd(&Hpp[(long long)hi * m.ldh + lo], -wv * wv);
+  double cost[R];   // [q]: virtual lane q NT + tid
+#pragma unroll
+  for (int q = 0; q < R; ++q) cost[q] = 0.0;
+  const int nbc = m.NB * 6;
+  for (int e0 = 0; e0 < nbc; e0 += MISC_LANES) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      const int e = e0 + q * NT + tid;
+      if (e >= nbc) continue;
+      const int b = e / 6, k = e % 6;
+      const int bi = d.bc_i[m.bc0 + b], bj = d.bc_j[m.bc0 + b];
+      const double wv = d.bc_w[(size_t)(m.bc0 + b) * 6 + k];
+      const double r = wv * (bias[6 * (m.bias0 + bj) + k] - bias[6 * (m.bias0 + bi) + k]);
+      cost[q] += 0.5 * r * r;
+      if (LIN) {
+        const int ii = 6 * m.K + 6 * bi + k, jj = 6 * m.K + 6 * bj + k;
+        atomicAdd(&g[ii], -wv * r);
+        atomicAdd(&g[jj], wv * r);
+        atomicAdd(&Hpp[(long long)ii * m.ldh + ii], wv * wv);
+        atomicAdd(&Hpp[(long long)jj * m.ldh + jj], wv * wv);
+        const int hi = max(ii, jj), lo = min(ii, jj);
+        atomicAdd(&Hpp[(long long)hi * m.ldh + lo], -wv * wv);
+      }
     }
   }
   const int n = m.pn;
@@ -598,14 +616,19 @@ template <int NT> __device__ __forceinline__ void misc_body(const Dev &d, int mo
     __syncthreads();
     const double *pH = d.pH + m.pH0, *b0 = d.pb0 + m.pv0;
     const int *pcol = d.pcol + m.pv0;
-    for (int i = tid; i < n; i += NT) {
-      double hd = 0.0;
-      for (int j = 0; j < n; ++j) hd += pH[(size_t)j * n + i] * dx[j];   // (J0^T J0 is symmetric: column i, coalesced over the threads)
-      cost += dx[i] * (b0[i] + 0.5 * hd);
-      if (store) d.pgrad[m.pv0 + i] = b0[i] + hd;
-      if (LIN && pcol[i] >= 0) atomicAdd(&g[pcol[i]], b0[i] + hd);
+    for (int i0 = 0; i0 < n; i0 += MISC_LANES) {
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        const int i = i0 + q * NT + tid;
+        if (i >= n) continue;
+        double hd = 0.0;
+        for (int j = 0; j < n; ++j) hd += pH[(size_t)j * n + i] * dx[j];   // (J0^T J0 is symmetric: column i, coalesced over the threads)
+        cost[q] += dx[i] * (b0[i] + 0.5 * hd);
+        if (store) d.pgrad[m.pv0 + i] = b0[i] + hd;
+        if (LIN && pcol[i] >= 0) atomicAdd(&g[pcol[i]], b0[i] + hd);
+      }
     }
-    if (tid == 0) cost += 0.5 * d.pc0[w];
+    if (tid == 0) cost[0] += 0.5 * d.pc0[w];
     if (LIN) {
       for (int e = tid; e < n * n; e += NT) {
         const int i = e / n, j = e % n;
@@ -614,9 +637,13 @@ template <int NT> __device__ __forceinline__ void misc_body(const Dev &d, int mo
       }
     }
   }
-  red[tid] = cost;
+#pragma unroll
+  for (int q = 0; q < R; ++q) red[q * NT + tid] = cost[q];
   __syncthreads();
-  for (int st = NT / 2; st > 0; st >>= 1) { if (tid < st) red[tid] += red[tid + st]; __syncthreads(); }
+  for (int st = MISC_LANES / 2; st > 0; st >>= 1) {
+    for (int c = tid; c < st; c += NT) red[c] += red[c + st];
+    __syncthreads();
+  }
   if (tid == 0) {
     d.misc_cost[w] = red[0];
     if (store && !lin_cost_only(lm, mode, d.prm)) {   // (the generic path resets these in k_zero_normal)
@@ -626,7 +653,7 @@ template <int NT> __device__ __forceinline__ void misc_body(const Dev &d, int mo
 }
 __global__ __launch_bounds__(256) void k_misc(Dev d, int mode, int store, int with_imu) {
   extern __shared__ __attribute__((aligned(16))) double smd[];
-  __shared__ double red[256];
+  __shared__ double red[MISC_LANES];
   misc_body<256>(d, mode, store, with_imu, blockIdx.x, smd, red);
 }
 // Small batches (the merged linearisation, <= 128 windows): everything that must precede k_linearize_f64 or is independent of it in ONE launch of
@@ -638,10 +665,12 @@ __global__ __launch_bounds__(256) void k_misc(Dev d, int mode, int store, int wi
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_pre_linearize(Dev d, int mode, int general_only, int zero_mode, int n_anchor_blocks, int with_misc) {
   __shared__ __attribute__((aligned(32))) double srec[64 * AREC_LD];
   static_assert(64 * AREC_LD >= 64 * 33, "the general IMU body's row buffer uses the anchor records' staging area");
+  static_assert(PRE_LIN_MAX_PN + MISC_LANES <= 64 * AREC_LD, "the misc share's dx and reduction cells share the staging area");
   const int b = blockIdx.x;
   if (b < n_anchor_blocks) { vis_anchor_body(d, mode, srec, b); return; }
   if (b < n_anchor_blocks + d.nwin) { imu_rest_body(d, mode, general_only, zero_mode, reinterpret_cast<unsigned char *>(srec), b - n_anchor_blocks); return; }
-  if (with_misc) misc_body<64>(d, mode, 1, 0, b - n_anchor_blocks - d.nwin, srec, srec + 64 * AREC_LD - 64);   // (dx: pn <= ~600 doubles, far below the reduction cells)
+  // (dx: d.maxPn <= PRE_LIN_MAX_PN doubles -- the host passes with_misc = 0 otherwise -- in front of the reduction cells at the end)
+  if (with_misc) misc_body<64>(d, mode, 1, 0, b - n_anchor_blocks - d.nwin, srec, srec + 64 * AREC_LD - MISC_LANES);
 }
 
 // Jacobi scaling (computed once, at iteration 0: Ceres jacobi_scaling), gradient max-norm of

@@ -67,7 +67,8 @@ typedef struct ctvio_options {
   double min_lm_diagonal, max_lm_diagonal; /* 1e-6, 1e32 */
   int32_t max_consecutive_invalid_steps;   /* 5 */
   int32_t deterministic;        /* 1: order-fixed accumulation everywhere (no floating-point atomics): two runs of the same batch
-                                   are bitwise equal.  It exists for batches whose every window has K <= 25 (packed Hessian in LDS):
+                                   are bitwise equal, also when profiling (ctvio_set_profiling) splits the launches differently.
+                                   It exists for batches whose every window has K <= 25 (packed Hessian in LDS):
                                    ctvio_upload / ctvio_set_batch return CTVIO_ERR_INVALID for any other batch
                                    instead of silently accumulating with atomics.  -1 (default): on for batches of <= 64 windows
                                    where it applies, the atomic path (run-to-run differences ~1e-13 in the state) otherwise; 0: off */
@@ -106,7 +107,10 @@ typedef struct ctvio_window {
   /* AddMarginalizationFactor (trajectory_estimator.h:146-148): r = r0 + J0*dx over the kept blocks */
   const double *pJ0;            /* pn*pn COLUMN-major (Eigen default of linearized_jacobians) */
   const double *pr0;            /* pn */
-  const int32_t *p_kind, *p_index, *p_off; /* pnb: block kind, knot/frame index, column offset (keep_block_idx - m) */
+  const int32_t *p_kind, *p_index, *p_off; /* pnb: block kind, knot/frame index, column offset (keep_block_idx - m).  The blocks
+                                   tile [0, pn) without overlap, and each (kind, index) appears at most once -- a duplicate block
+                                   is refused with CTVIO_ERR_INVALID, as Ceres refuses a parameter block listed twice in one
+                                   residual block; hence pn <= P */
   const double *p_x0;           /* pnb*4: keep_block_data (quaternion x,y,z,w or 3-vector / scalar, zero padded) */
   /* per residual block: the reference creates one loss per AddImageFeatureDelayAnalytic call, CauchyLoss(marg_this_feature ?
    * 1 : 2) (trajectory_estimator.cpp:320-323).  V entries (<= 0: no loss for that block) or NULL: cauchy_a for every block. */
