@@ -26,6 +26,7 @@
 #include "kernels.hpp"
 #include "marginalize.hpp"
 #include "marg_device.hpp"
+#include "marg_blocked.hpp"
 #include "host_pack.hpp"
 
 namespace ctv {
@@ -57,6 +58,7 @@ struct DebugSwitches {
   int schur_tile2 = -1;      // CTVIO_SCHUR_TILE2=0/1    one wave per tile / per 2 x 2 tiles
   int marg_debug = 0;        // CTVIO_MARG_DEBUG=1       sweep trace of the device eigen-solver on stderr
   int marg_host = 0;         // CTVIO_MARG_HOST=1        ctvio_marginalize on the host factorisation
+  int marg_blocked = 0;      // CTVIO_MARG_BLOCKED=1     ctvio_marginalize_batch: every window through the blocked path (csrc/marg_blocked.hpp)
   int shard_oversubscribe = 0;   // CTVIO_SHARD_OVERSUBSCRIBE=1  TEST ONLY: more shards than devices (ctvio_shards_used)
 };
 static DebugSwitches read_debug_switches() {
@@ -67,7 +69,7 @@ static DebugSwitches read_debug_switches() {
       {"CTVIO_IMU_WAVES", &g.imu_waves}, {"CTVIO_IMU_GENERAL", &g.imu_general}, {"CTVIO_SCHUR_TILES", &g.schur_tiles},
       {"CTVIO_SCHUR_COPY_PLAIN", &g.schur_copy_plain}, {"CTVIO_CHOL_TILES", &g.chol_tiles}, {"CTVIO_DENSE", &g.dense},
       {"CTVIO_SCHUR_TILE2", &g.schur_tile2}, {"CTVIO_MARG_DEBUG", &g.marg_debug}, {"CTVIO_MARG_HOST", &g.marg_host},
-      {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}};
+      {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}};
   for (const auto &t : tab)
     if (const char *e = std::getenv(t.name)) *t.dst = (e[0] == '\0') ? 1 : std::atoi(e);   // (set but empty counts as 1)
   g.imu_waves = std::max(1, g.imu_waves);
@@ -1054,13 +1056,15 @@ class SolverImpl : public SolverBase {
   // workgroup per window eliminates the marginalised unknowns and factors the rest (csrc/marg_device.hpp: parallel Jacobi
   // in LDS).  role: concatenated per window (sum N entries, window i at its unknown offset); `only` >= 0 restricts the work
   // to that window.  Outputs: n_keep[nwin]; kept at the window's unknown offset; J0 / r0 packed tightly in window order.
+  // allow_blocked: windows with m or n in (MARG_MAXD, MARG_MAXD_BLOCKED] take the blocked path (csrc/marg_blocked.hpp, one window
+  // after the other, after the in-LDS launch of the small ones); without it they are reported too large.
   int marg_device(const int8_t *role_all, int only, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0, bool *too_large,
-                  int *stalled = nullptr) {
+                  int *stalled = nullptr, bool allow_blocked = false) {
     if (stalled) *stalled = -1;
     Dev &d = dev_;
     const int nw = d.nwin, wb = nblk(nw, 64);
     *too_large = false;
-    std::vector<MargMeta> metas((size_t)nw);
+    std::vector<MargMeta> metas((size_t)nw), bmeta;   // bmeta: the blocked windows (k_marginalize sees them with m = n = 0)
     std::vector<int32_t> iscr;
     size_t scr = 0, outd = 0;
     for (int w = 0; w < nw; ++w) {
@@ -1074,7 +1078,16 @@ class SolverImpl : public SolverBase {
       for (int i = 0; i < m.N; ++i) if (role[i] == 1) { iscr.push_back(i); mm.m++; }
       for (int i = 0; i < m.N; ++i) if (role[i] == 0) { iscr.push_back(i); kept[m.u0 + mm.n] = i; mm.n++; }
       n_keep[w] = mm.n;
-      if (mm.m > MARG_MAXD || mm.n > MARG_MAXD) { *too_large = true; return CTVIO_OK; }
+      const bool big = mm.m > MARG_MAXD || mm.n > MARG_MAXD;
+      if (mm.m > MARG_MAXD_BLOCKED || mm.n > MARG_MAXD_BLOCKED || (big && !allow_blocked)) { *too_large = true; return CTVIO_OK; }
+      if (allow_blocked && mm.n > 0 && (big || dbg_.marg_blocked)) {
+        mm.J0 = (int64_t)outd; outd += (size_t)mm.n * mm.n;
+        mm.r0 = (int64_t)outd; outd += (size_t)mm.n;
+        mm.sweeps_m = w;                // (the window index, while the copy waits in bmeta)
+        bmeta.push_back(mm);
+        mm.m = mm.n = 0;
+        continue;
+      }
       const int np = std::max(mm.m, mm.n) + (std::max(mm.m, mm.n) & 1);
       mm.A0 = (int64_t)scr; scr += (size_t)m.N * m.N;
       mm.V0 = (int64_t)scr; scr += (size_t)mm.m * mm.m;
@@ -1095,11 +1108,20 @@ class SolverImpl : public SolverBase {
     HIPCHK(mg_out_.alloc(outd));
     constexpr size_t lds = ((size_t)MARG_MAXD * (MARG_MAXD + 1) / 2 + 4 * MARG_MAXD + 512) * sizeof(double) + 2 * MARG_MAXD * sizeof(int);
     if (!marg_attr_set_) { HIPCHK(hipFuncSetAttribute((const void *)k_marginalize, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); marg_attr_set_ = true; }
-    hipLaunchKernelGGL(k_marginalize, dim3(nw), dim3(256), lds, stream_, d, mg_meta_.p, mg_idx_.p, mg_scr_.p, mg_out_.p, eps);
+    if (bmeta.size() < (size_t)nw)
+      hipLaunchKernelGGL(k_marginalize, dim3(nw), dim3(256), lds, stream_, d, mg_meta_.p, mg_idx_.p, mg_scr_.p, mg_out_.p, eps);
+    for (MargMeta &bm : bmeta) {
+      const int w = bm.sweeps_m;
+      const int rc = marg_blocked(w, bm, eps);
+      if (rc != CTVIO_OK) return rc;
+      metas[w] = bm;
+    }
     std::vector<double> outh(std::max<size_t>(outd, 1));
     HIPCHK(hipMemcpyAsync(outh.data(), mg_out_.p, sizeof(double) * std::max<size_t>(outd, 1), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(metas.data(), mg_meta_.p, sizeof(MargMeta) * nw, hipMemcpyDeviceToHost, stream_));
+    std::vector<MargMeta> small((size_t)nw);
+    HIPCHK(hipMemcpyAsync(small.data(), mg_meta_.p, sizeof(MargMeta) * nw, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
+    for (int w = 0; w < nw; ++w) if (small[w].n > 0) metas[w] = small[w];
     HIPCHK(hipGetLastError());
     if (const int rc = check_span_violation()) return rc;
     size_t oj = 0, orr = 0;
@@ -1118,6 +1140,74 @@ class SolverImpl : public SolverBase {
     }
     return CTVIO_OK;
   }
+  // Block two-sided Jacobi (csrc/marg_blocked.hpp) on B (D x D, nd real rows / columns) and V, one launch per phase; the host reads the
+  // per-block mass after every sweep and applies jacobi_packed's rule.  *sweeps: the sweeps done, or -1; off / diagonal mass per sweep in trace.
+  int mb_jacobi(double *B, double *V, int D, int nd, double *Q, double *trace, int32_t *sweeps) {
+    const int nb = D / MB_BLK, npair = nb / 2;
+    std::vector<double> part((size_t)2 * nb);
+    double prev_off = 1e300;
+    *sweeps = -1;
+    for (int sweep = 0; sweep < MB_MAX_SWEEPS; ++sweep) {
+      hipLaunchKernelGGL(k_mb_mass, dim3(nb), dim3(256), 0, stream_, B, D, mb_part_.p);
+      HIPCHK(hipMemcpyAsync(part.data(), mb_part_.p, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      double off = 0.0, d2 = 0.0;
+      for (int b = 0; b < nb; ++b) { off += part[2 * b]; d2 += part[2 * b + 1]; }
+      if (sweep < 26) trace[sweep] = off / d2;
+      const double floor_rel = std::max(1e-28, 4.0 * (double)nd * (double)nd * 4.93e-32);
+      if (off <= 1e-60 || off <= 1e-32 * d2 || (sweep >= 12 && off <= floor_rel * d2 && off > 0.25 * prev_off)) { *sweeps = sweep; return CTVIO_OK; }
+      prev_off = off;
+      for (int s = 0; s < nb - 1; ++s) {
+        hipLaunchKernelGGL(k_mb_pair, dim3(npair), dim3(256), 0, stream_, B, D, s, Q);
+        hipLaunchKernelGGL(k_mb_update, dim3(npair * (npair - 1) / 2 + (D / 64) * npair), dim3(256), 0, stream_, B, V, D, s, Q);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    return CTVIO_OK;
+  }
+  // one window through the blocked path; J0 / r0 to mg_out_ at bm's offsets, status and sweeps into bm
+  int marg_blocked(int w, MargMeta &bm, double eps) {
+    const int m = bm.m, n = bm.n, dm = m > 0 ? mb_padded(m) : 0, dn = mb_padded(n), D = std::max(dm, dn);
+    const size_t mn1 = (size_t)m * (n + 1);
+    const size_t need = 2 * (size_t)dm * dm + 2 * (size_t)dn * dn + 3 * mn1 + (size_t)n + (size_t)(D / 64) * 64 * 64;
+    HIPCHK(hipStreamSynchronize(stream_));   // (the scratch of the previous window may still be in use)
+    HIPCHK(mb_scr_.alloc(need));
+    HIPCHK(mb_part_.alloc((size_t)2 * D / MB_BLK));
+    HIPCHK(mb_rank_.alloc((size_t)n));
+    MbWin b;
+    b.w = w; b.m = m; b.n = n; b.dm = dm; b.dn = dn;
+    b.im = mg_idx_.p + bm.idx0; b.ik = b.im + m;
+    double *p = mb_scr_.p;
+    b.Bm = p; p += (size_t)dm * dm;
+    b.Vm = p; p += (size_t)dm * dm;
+    b.Bn = p; p += (size_t)dn * dn;
+    b.Vn = p; p += (size_t)dn * dn;
+    b.G = p; p += mn1;
+    b.Y = p; p += mn1;
+    b.X = p; p += mn1;
+    b.bp = p; p += n;
+    double *Q = p;
+    b.J0 = mg_out_.p + bm.J0; b.r0 = mg_out_.p + bm.r0; b.rank = mb_rank_.p;
+    auto grid = [](long long cnt) { return dim3((unsigned)std::max<long long>(1, (cnt + 255) / 256)); };
+    const long long gat = std::max<long long>((long long)dm * dm, std::max<long long>((long long)mn1, (long long)dn * dn));
+    hipLaunchKernelGGL(k_mb_gather, dim3((unsigned)std::min<long long>(2048, (gat + 255) / 256)), dim3(256), 0, stream_, dev_, b);
+    int status = 0;
+    bm.sweeps_m = 0;
+    if (m > 0) {
+      if (const int rc = mb_jacobi(b.Bm, b.Vm, dm, m, Q, bm.trace, &bm.sweeps_m)) return rc;
+      if (bm.sweeps_m < 0) status = 1;
+      hipLaunchKernelGGL(k_mb_y, grid((long long)mn1), dim3(256), 0, stream_, b, eps);
+      hipLaunchKernelGGL(k_mb_x, grid((long long)mn1), dim3(256), 0, stream_, b);
+    }
+    hipLaunchKernelGGL(k_mb_reduce, grid((long long)dn * dn + n), dim3(256), 0, stream_, dev_, b);
+    if (const int rc = mb_jacobi(b.Bn, b.Vn, dn, n, Q, bm.trace + 26, &bm.sweeps_n)) return rc;
+    if (bm.sweeps_n < 0) status = 1;
+    hipLaunchKernelGGL(k_mb_rank, grid(n), dim3(256), 0, stream_, b, eps);
+    hipLaunchKernelGGL(k_mb_j0, grid((long long)n * n), dim3(256), 0, stream_, b, eps);
+    HIPCHK(hipGetLastError());
+    bm.status = status;
+    return CTVIO_OK;
+  }
   int marginalize_batch(const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) override {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (!role || !n_keep || !kept || !J0 || !r0 || !(eps >= 0)) return fail(CTVIO_ERR_INVALID, "bad arguments");
@@ -1125,11 +1215,11 @@ class SolverImpl : public SolverBase {
     bool too_large = false;
     int stalled = -1;
     marg_ran_on_host_ = 0;
-    const int rc = marg_device(role, -1, eps, n_keep, kept, J0, r0, &too_large, &stalled);
+    const int rc = marg_device(role, -1, eps, n_keep, kept, J0, r0, &too_large, &stalled, true);
     if (rc != CTVIO_OK && stalled >= 0)
       return fail(CTVIO_ERR_HIP, "device eigen-solver did not converge for window " + std::to_string(stalled) + ": call ctvio_marginalize for it (host factorisation)");
     if (rc != CTVIO_OK) return rc;
-    if (too_large) return fail(CTVIO_ERR_INVALID, "a window has more than " + std::to_string(MARG_MAXD) + " marginalised or kept unknowns: use ctvio_marginalize");
+    if (too_large) return fail(CTVIO_ERR_INVALID, "a window has more than " + std::to_string(MARG_MAXD_BLOCKED) + " marginalised or kept unknowns");
     return CTVIO_OK;
   }
   // one window; windows beyond the device eigen-solver's size (m or n > MARG_MAXD) take the host path (csrc/marginalize.hpp)
@@ -1339,6 +1429,8 @@ class SolverImpl : public SolverBase {
   DBuf<MargMeta> mg_meta_;   // device marginalisation: descriptors, index lists, scratch, outputs
   DBuf<int32_t> mg_idx_;
   DBuf<double> mg_scr_, mg_out_;
+  DBuf<double> mb_scr_, mb_part_;   // blocked marginalisation (csrc/marg_blocked.hpp): scratch of one window, per-block sweep mass
+  DBuf<int32_t> mb_rank_;
   bool marg_attr_set_ = false;
   double *snap_ = nullptr;   // state snapshot (inside work_)
   Lm *lm_host_ = nullptr; size_t lm_host_cap_ = 0;

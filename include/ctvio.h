@@ -222,15 +222,18 @@ int32_t ctvio_sensor_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_t 
  * the prior has to match an fp64 reference tightly: the elimination amplifies the fp32 noise of the default path. */
 int32_t ctvio_marginalize(ctvio_solver *s, int32_t id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0);
 
-/* The same for EVERY window of the batch in one launch (one workgroup per window: Schur elimination + two parallel-Jacobi
- * eigendecompositions in LDS).  role: the windows' role arrays concatenated (sum of N_i entries, window order); outputs:
- * n_keep[n_windows]; kept: window i's kept unknowns at offset sum_{k<i} N_k; J0 / r0 packed tightly in window order
- * (offsets sum_{k<i} n_keep_k^2 / sum_{k<i} n_keep_k).  Every window needs <= 180 marginalised and <= 180 kept unknowns
- * (ctvio_marginalize falls back to a host factorisation beyond that). */
+/* The same for EVERY window of the batch, all on the device.  Windows with <= 180 marginalised and <= 180 kept unknowns share one
+ * launch (one workgroup per window: Schur elimination + two parallel-Jacobi eigendecompositions in LDS); larger windows, up to 1024
+ * marginalised and 1024 kept unknowns, take the blocked path one after the other (csrc/marg_blocked.hpp: block two-sided Jacobi, the
+ * same convergence rule, deterministic).  Both may share a batch.  role: the windows' role arrays concatenated (sum of N_i entries,
+ * window order); outputs: n_keep[n_windows]; kept: window i's kept unknowns at offset sum_{k<i} N_k; J0 / r0 packed tightly in window
+ * order (offsets sum_{k<i} n_keep_k^2 / sum_{k<i} n_keep_k).  A window beyond 1024 is refused with CTVIO_ERR_INVALID (the handle stays
+ * usable). */
 int32_t ctvio_marginalize_batch(ctvio_solver *s, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0);
 /* Where the LAST ctvio_marginalize / ctvio_marginalize_batch call of this handle factored: 0 = on the device (the product path), 1 = the
  * eigen-decompositions ran on the HOST cores (csrc/marginalize.hpp: a window with more than 180 marginalised or kept unknowns, or one whose
- * in-LDS Jacobi sweeps stalled; ctvio_marginalize only -- the batch entry fails instead).  The normal equations come from the device kernels
+ * in-LDS Jacobi sweeps stalled; ctvio_marginalize only -- the batch entry factors such windows on the device (blocked path) and never
+ * sets it).  The normal equations come from the device kernels
  * either way.  Reference counterpart of the host leg: MarginalizationInfo::marginalize, marginalization_factor.cpp:178-265. */
 int32_t ctvio_marginalize_ran_on_host(const ctvio_solver *s);
 
@@ -282,6 +285,7 @@ int32_t ctvio_graph_captures(const ctvio_solver *s);
  *   CTVIO_DENSE=1 (dense sparsity plan)   CTVIO_CHOL_TILES=0|1|3   CTVIO_SCHUR_TILE2=0|1   CTVIO_SCHUR_TILES=1   CTVIO_SCHUR_COPY_PLAIN=1
  *   CTVIO_STORE_PATH=0|1   CTVIO_SPLIT_LINEARIZE=1   CTVIO_MERGE_LINEARIZE=0|1   CTVIO_ZERO_KERNEL=1   CTVIO_NO_IMU_BAND=1   CTVIO_IMU_WAVES=n
  *   CTVIO_IMU_GENERAL=1   CTVIO_MARG_HOST=1   CTVIO_MARG_DEBUG=1   CTVIO_DEBUG_STAMPS=1
+ *   CTVIO_MARG_BLOCKED=1 (ctvio_marginalize_batch: small windows through the blocked path too)
  *   CTVIO_SHARD_OVERSUBSCRIBE=1 (test only; read by ctvio_shards_used / ctvio_solve_sharded at call time) */
 
 #ifdef __cplusplus

@@ -1,0 +1,189 @@
+"""GPU: ctvio_marginalize_batch beyond the in-LDS eigen-solver (m or n > 180, up to MARG_MAXD_BLOCKED = 1024): the blocked path
+(csrc/marg_blocked.hpp: gathered Amm / Amr, block two-sided Jacobi with explicit Q, multi-workgroup elimination and factor) against the
+oracle's cyclic Jacobi, a NumPy eigh restatement and the chained Gauss-Newton step; mixed batches, determinism, the refusal beyond the
+bound, and its speed against the host leg."""
+import os
+import sys
+import time
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+import marg_blocked_helpers as mb  # noqa: E402
+
+
+def check_vs_oracle(kept, J0, r0, ko, Jo, ro, what, scaled=1e-8):
+    eH, eg, eS = mb.prior_errors(J0, r0, Jo, ro)
+    print(f"{what}: J0'J0 {eH:.2e}, J0'r0 {eg:.2e}, scaled {eS:.2e}, rank {mb.rank(J0)} / oracle {mb.rank(Jo)}")
+    assert np.array_equal(kept, ko)
+    assert eH <= 1e-7 and eg <= 1e-7, (eH, eg)
+    assert eS <= scaled and mb.rank(J0) == mb.rank(Jo), (eS, mb.rank(J0), mb.rank(Jo), mb.near_eps(J0), mb.near_eps(Jo))
+
+
+def slide_case():
+    import slide_helpers as sh
+    world = sh.make_world()
+    st = sh.State(world)
+    w, info = sh.window_of(world, st, 0, sh.initial_prior(world))
+    return sh.marg_window_of(world, st, 0, w, info)
+
+
+def config1_case(cv):
+    w = cv.synth.make_window("config1", seed=1000)
+    w.cauchy_a = 1.0
+    role = np.zeros(w.N, np.int8)                     # test_marginalize_prior_construction's drop set: m 43 / n 218
+    role[:12] = 1
+    role[6 * w.K:6 * w.K + 6] = 1
+    role[w.P:w.P + w.L // 2] = 1
+    return w, role
+
+
+@pytest.fixture(scope="module")
+def c5(oracle):
+    w = mb.config5_window(1500)
+    role = mb.drop_roles(w, [0, 1])
+    t0 = time.perf_counter()
+    ko, Jo, ro = oracle.OracleWindow(w.copy()).marginalize(role, 1e-8)
+    return w, role, (ko, Jo, ro), time.perf_counter() - t0
+
+
+def test_config5_drop_set_against_oracle(cv, c5):
+    w, role, ref, _ = c5
+    assert (role == 1).sum() == 268 and (role == 0).sum() == 553
+    with cv.Solver() as s:
+        s.set_windows([w.copy()])
+        (kept, J0, r0), = s.marginalize_batch([role])
+        assert not s.marginalize_ran_on_host()
+    assert mb.rank(ref[1]) == 547
+    check_vs_oracle(kept, J0, r0, *ref, "config-5 drop set (m 268 / n 553)")
+
+
+def test_chain_exactness_config5(cv):
+    """test_prior_chain_on_device through the batch entry on config 5: m 500 / n 187."""
+    from chain_helpers import chain_case, prior_arrays
+    w, wD, wR, mapR = chain_case("config5", 1500)
+    with cv.Solver(precision="fp64") as s:
+        s.set_windows([wD.copy()])
+        Hpp = s.linearize(0)[0]
+        role = np.where(np.arange(wD.N) >= wD.P, 1, np.where(np.concatenate([np.diag(Hpp), np.ones(wD.L)]) > 0, 0, -1)).astype(np.int8)
+        assert (role == 1).sum() > 180
+        (kept, J0, r0), = s.marginalize_batch([role])
+        assert not s.marginalize_ran_on_host()
+    wR.pJ0, wR.pr0, wR.p_kind, wR.p_index, wR.p_off, wR.p_x0 = prior_arrays(wR, kept, J0, r0)
+    wR.normalize()
+    w.fixed_upto = 3
+    wR.fixed_upto = 3
+    with cv.Solver(precision="fp64") as s:
+        s.set_windows([w.copy(), wR.copy()])
+        d_full, _ = s.lm_step(0, 1e16)
+        d_red, _ = s.lm_step(1, 1e16)
+    P = w.P
+    assert np.abs(d_red[:P] - d_full[:P]).max() < 1e-6 * np.abs(d_full[:P]).max()
+    assert np.abs(d_red[P:] - d_full[P + mapR]).max() < 1e-6 * np.abs(d_full[P:]).max()
+
+
+def test_near_the_bound_and_beyond(cv, oracle):
+    """m 518 / n 928 against the oracle: kept set, rank, 1e-7 relative to the largest entry (measured 1e-11 / 2e-10).  NumPy's eigh
+    restatement is printed but is not the yardstick: on this window it is itself 1.5e-7 (J0^T J0) and 1.9e-6 (J0^T r0) from the oracle,
+    rank 925 against 922.  The diagonally scaled error is only bounded loosely here (measured 1.2e-3; NumPy: 1.0): a few kept unknowns have
+    a prior diagonal near eps, where the scaled yardstick compares eps-level noise of the two Jacobi solvers."""
+    from test_marginalize_host import numpy_marginalize
+    w = mb.config5_window(1500)
+    role = mb.drop_roles(w, [0, 1, 2, 3], keep_frames=[4, 5, 6])
+    m, n = int((role == 1).sum()), int((role == 0).sum())
+    assert 500 <= m <= 1024 and 900 <= n <= 1024, (m, n)
+    H, g, _ = oracle.OracleWindow(w.copy()).build_normal()
+    ko, Jo, ro = oracle.OracleWindow(w.copy()).marginalize(role, 1e-8)
+    big = mb.drop_roles(w, [0, 1], keep_frames=[2, 3, 4, 5, 6, 7])
+    assert (big == 0).sum() > 1024
+    small = np.full(w.N, -1, np.int8)
+    small[:12] = 1                                    # knots 0-1 out, knots 2-3 kept: m 12 / n 12
+    small[12:24] = 0
+    with cv.Solver() as s:
+        s.set_windows([w.copy()])
+        (kept, J0, r0), = s.marginalize_batch([role])
+        with pytest.raises(cv.capi.CtvioError, match="1024"):
+            s.marginalize_batch([big])
+        (ks, Js, rs), = s.marginalize_batch([small])
+    ik, Jn, rn = numpy_marginalize(H, g, role, 1e-8)
+    eH, eg, eS = mb.prior_errors(J0, r0, Jn, rn)
+    print(f"near the bound (m {m} / n {n}) vs numpy eigh: J0'J0 {eH:.2e}, J0'r0 {eg:.2e}, scaled {eS:.2e}, rank {mb.rank(Jn)}")
+    check_vs_oracle(kept, J0, r0, ko, Jo, ro, f"near the bound (m {m} / n {n})", scaled=1e-2)
+    iks, Jsn, rsn = numpy_marginalize(H, g, small, 1e-8)
+    assert np.array_equal(ks, iks)
+    e2 = mb.prior_errors(Js, rs, Jsn, rsn)
+    assert e2[0] <= 1e-7 and e2[1] <= 1e-7, e2
+
+
+def test_mixed_batch_and_determinism(cv, oracle):
+    mw, mrole = slide_case()
+    w1, r1 = config1_case(cv)
+    assert (mrole == 1).sum() <= 180 and (mrole == 0).sum() <= 180
+    assert (r1 == 0).sum() > 180
+    wins, roles = [mw, w1, w1], [mrole, r1, r1]
+    with cv.Solver() as s:
+        s.set_windows([x.copy() for x in wins])
+        res = s.marginalize_batch(roles)
+        again = s.marginalize_batch(roles)
+    for a, b in zip(res, again):
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y)
+    for x, y in zip(res[1], res[2]):
+        assert np.array_equal(x, y)
+    for i, (x, rl) in enumerate(zip(wins, roles)):
+        with cv.Solver() as s1:
+            s1.set_windows([x.copy()])
+            one, = s1.marginalize_batch([rl])
+        assert np.array_equal(one[0], res[i][0])
+        for a, b in zip(one[1:], res[i][1:]):
+            assert np.abs(a - b).max() <= 1e-12 * np.abs(b).max()
+        print(f"member {i}: bitwise equal to its one-window batch: {all(np.array_equal(a, b) for a, b in zip(one, res[i]))}")
+    ko, Jo, ro = oracle.OracleWindow(w1.copy()).marginalize(r1, 1e-8)
+    # (scaled yardstick measured 7.2e-7, not 1e-8: this window has kept unknowns whose prior diagonal is near eps, where the scaled error
+    #  compares eps-level noise of two Jacobi solvers; relative to the largest entry the two agree to 6e-14, with the same rank)
+    check_vs_oracle(*res[1], ko, Jo, ro, "config-1 case (m 43 / n 218)", scaled=1e-5)
+
+
+def test_blocked_path_agrees_with_lds_path(cv, monkeypatch):
+    """CTVIO_MARG_BLOCKED=1 sends the slide drop set (m 26 / n 91) through the blocked path: the prior must not change character at 180."""
+    mw, mrole = slide_case()
+    with cv.Solver() as s:
+        s.set_windows([mw.copy()])
+        (kl, Jl, rl), = s.marginalize_batch([mrole])
+    monkeypatch.setenv("CTVIO_MARG_BLOCKED", "1")
+    with cv.Solver() as s:
+        s.set_windows([mw.copy()])
+        (kb, Jb, rb), = s.marginalize_batch([mrole])
+    assert np.array_equal(kb, kl)
+    eH, eg, eS = mb.prior_errors(Jb, rb, Jl, rl)
+    print(f"blocked vs in-LDS path: J0'J0 {eH:.2e}, J0'r0 {eg:.2e}, scaled {eS:.2e}")
+    assert eH <= 1e-9 and eg <= 1e-9                  # measured 9e-13 / 3e-14
+    assert eS <= 1e-6                                 # measured 2.8e-8: unknowns with a prior diagonal near eps (see the mixed-batch test)
+
+
+def test_blocked_faster_than_host_leg(cv, c5):
+    w, role, _, t_oracle = c5
+    with cv.Solver() as s:
+        s.set_windows([w.copy()])
+        s.marginalize_batch([role])                   # warm-up (allocations, kernel load)
+        t0 = time.perf_counter()
+        s.marginalize_batch([role])
+        t_dev = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        s.marginalize(0, role)
+        t_host = time.perf_counter() - t0
+        assert s.marginalize_ran_on_host()
+    nb = 16
+    with cv.Solver() as s:
+        s.set_windows([w.copy() for _ in range(nb)])
+        s.marginalize_batch([role] * nb)
+        t0 = time.perf_counter()
+        s.marginalize_batch([role] * nb)
+        t16 = time.perf_counter() - t0
+    print(f"config-5 drop set: device {1e3 * t_dev:.1f} ms, host leg {1e3 * t_host:.1f} ms, oracle {t_oracle:.1f} s; "
+          f"batch of {nb}: {1e3 * t16 / nb:.1f} ms per window")
+    assert t_dev < t_host
