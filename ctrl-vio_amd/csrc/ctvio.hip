@@ -60,6 +60,8 @@ struct DebugSwitches {
   int marg_host = 0;         // CTVIO_MARG_HOST=1        ctvio_marginalize on the host factorisation
   int marg_blocked = 0;      // CTVIO_MARG_BLOCKED=1     ctvio_marginalize_batch: every window through the blocked path (csrc/marg_blocked.hpp)
   int shard_oversubscribe = 0;   // CTVIO_SHARD_OVERSUBSCRIBE=1  TEST ONLY: more shards than devices (ctvio_shards_used)
+  int poison = 0;            // CTVIO_POISON=1/2         TEST ONLY: reused double scratch starts as quiet NaN / 2.6e151 at every use; the
+                             //                          upload checks that the packer writes every staged byte (SolverImpl::poison)
 };
 static DebugSwitches read_debug_switches() {
   DebugSwitches g;
@@ -69,7 +71,7 @@ static DebugSwitches read_debug_switches() {
       {"CTVIO_IMU_WAVES", &g.imu_waves}, {"CTVIO_IMU_GENERAL", &g.imu_general}, {"CTVIO_SCHUR_TILES", &g.schur_tiles},
       {"CTVIO_SCHUR_COPY_PLAIN", &g.schur_copy_plain}, {"CTVIO_CHOL_TILES", &g.chol_tiles}, {"CTVIO_DENSE", &g.dense},
       {"CTVIO_SCHUR_TILE2", &g.schur_tile2}, {"CTVIO_MARG_DEBUG", &g.marg_debug}, {"CTVIO_MARG_HOST", &g.marg_host},
-      {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}};
+      {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}, {"CTVIO_POISON", &g.poison}};
   for (const auto &t : tab)
     if (const char *e = std::getenv(t.name)) *t.dst = (e[0] == '\0') ? 1 : std::atoi(e);   // (set but empty counts as 1)
   g.imu_waves = std::max(1, g.imu_waves);
@@ -92,6 +94,12 @@ template <class U> struct DBuf {
     if (e != hipSuccess || h.empty()) return e;
     return hipMemcpyAsync(p, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice, st);
   }
+};
+
+// One segment of an arena layout: name, byte offset, the bytes a batch fills (CTVIO_POISON checks and poisons these extents).
+struct ArenaSeg {
+  const char *name;
+  size_t off, bytes;
 };
 
 // Owning host copy of one window (ctvio_add_window: the caller's buffers are only read inside that call).
@@ -306,25 +314,31 @@ class SolverImpl : public SolverBase {
     Mtot_ = M0; Vtot_ = V0;
     // ---- input arena layout (host mirror + device)
     size_t off = 0;
-    auto seg = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_meta = seg(sizeof(WinMeta) * nw);
-    const size_t o_state = seg(sizeof(double) * ((size_t)7 * K0 + 6 * F0 + L0 + nw));   // quat | pos | bias | rho | ld, contiguous
-    const size_t o_knot_win = seg(4 * (size_t)K0), o_bias_win = seg(4 * (size_t)F0), o_lm_win = seg(4 * (size_t)L0);
-    const size_t o_groups = seg(sizeof(ImuGroup) * (size_t)G0), o_imu_grp = seg(4 * Mt);
-    const size_t o_imu_u = seg(sizeof(double) * Mt), o_imu_meas = seg(sizeof(double) * 6 * Mt);
-    const size_t o_v_win = seg(4 * Vt), o_v_lm = seg(4 * Vt), o_v_anc = seg(4 * Vt), o_v_rowj = seg(4 * Vt);
-    const size_t o_v_tj = seg(8 * Vt), o_v_obs = seg(sizeof(double) * 2 * Vt);
-    const size_t o_v_cauchy = seg(8 * Vt), o_vb_win = seg(4 * (Vt / 64 + 1));
-    const size_t o_a_win = seg(4 * At), o_a_lm = seg(4 * At), o_a_row = seg(4 * At), o_a_t = seg(8 * At), o_a_obs = seg(8 * 2 * At);
-    const size_t o_vitems = seg(sizeof(VisItem) * (size_t)std::max(I0, 1)), o_vblk = seg(4 * Vt), o_vblk_anc = seg(4 * Vt);
-    const size_t o_bc_win = seg(4 * (size_t)B0), o_bc_i = seg(4 * (size_t)B0), o_bc_j = seg(4 * (size_t)B0), o_bc_w = seg(8 * 6 * (size_t)B0);
-    const size_t o_pJ0 = seg(8 * (size_t)pH0), o_pr0 = seg(8 * (size_t)pv0);
-    const size_t o_pH = seg(8 * (size_t)pH0), o_pb0 = seg(8 * (size_t)pv0), o_pc0 = seg(8 * (size_t)nw), o_p_x0 = seg(8 * 4 * (size_t)pb);
-    const size_t o_pcol = seg(4 * (size_t)pv0), o_p_kind = seg(4 * (size_t)pb), o_p_index = seg(4 * (size_t)pb), o_p_off = seg(4 * (size_t)pb);
-    const size_t o_pinv = seg(4 * (size_t)Pp0), o_bgl_off = seg(4 * ((size_t)F0 + nw)), o_bgl = seg(4 * (size_t)std::max(G0, 1));
-    const size_t o_active = seg((size_t)U0);
-    const size_t o_lm_pos = seg(4 * (size_t)L0), o_lm_at = seg(4 * (size_t)L0), o_lm_klo = seg(4 * (size_t)L0), o_lm_khi = seg(4 * (size_t)L0);
-    const size_t o_tl_beg = seg(4 * (size_t)TR0), o_tl_end = seg(4 * (size_t)TR0), o_env_first = seg(4 * (size_t)TR0), o_env_tile = seg(4 * (size_t)TR0);
+    std::vector<ArenaSeg> segs;   // (CTVIO_POISON: the extents of the segments, named, without their alignment tails)
+    auto seg = [&](const char *name, size_t bytes, size_t used = SIZE_MAX) {   // used: the bytes the batch fills (an empty set keeps one entry)
+      const size_t o = off;
+      off += (bytes + 255) & ~(size_t)255;
+      if (dbg_.poison) segs.push_back(ArenaSeg{name, o, std::min(bytes, used)});
+      return o;
+    };
+    const size_t o_meta = seg("meta", sizeof(WinMeta) * nw);
+    const size_t o_state = seg("state", sizeof(double) * ((size_t)7 * K0 + 6 * F0 + L0 + nw));   // quat | pos | bias | rho | ld, contiguous
+    const size_t o_knot_win = seg("knot_win", 4 * (size_t)K0), o_bias_win = seg("bias_win", 4 * (size_t)F0), o_lm_win = seg("lm_win", 4 * (size_t)L0);
+    const size_t o_groups = seg("groups", sizeof(ImuGroup) * (size_t)G0), o_imu_grp = seg("imu_grp", 4 * Mt, 4 * (size_t)M0);
+    const size_t o_imu_u = seg("imu_u", sizeof(double) * Mt, sizeof(double) * (size_t)M0), o_imu_meas = seg("imu_meas", sizeof(double) * 6 * Mt, sizeof(double) * 6 * (size_t)M0);
+    const size_t o_v_win = seg("v_win", 4 * Vt, 4 * (size_t)V0), o_v_lm = seg("v_lm", 4 * Vt, 4 * (size_t)V0), o_v_anc = seg("v_anc", 4 * Vt, 4 * (size_t)V0), o_v_rowj = seg("v_rowj", 4 * Vt, 4 * (size_t)V0);
+    const size_t o_v_tj = seg("v_tj", 8 * Vt, 8 * (size_t)V0), o_v_obs = seg("v_obs", sizeof(double) * 2 * Vt, sizeof(double) * 2 * (size_t)V0);
+    const size_t o_v_cauchy = seg("v_cauchy", 8 * Vt, 8 * (size_t)V0), o_vb_win = seg("vb_win", 4 * (Vt / 64 + 1), 4 * ((size_t)V0 / 64));
+    const size_t o_a_win = seg("a_win", 4 * At, 4 * (size_t)A0), o_a_lm = seg("a_lm", 4 * At, 4 * (size_t)A0), o_a_row = seg("a_row", 4 * At, 4 * (size_t)A0), o_a_t = seg("a_t", 8 * At, 8 * (size_t)A0), o_a_obs = seg("a_obs", 8 * 2 * At, 8 * 2 * (size_t)A0);
+    const size_t o_vitems = seg("vitems", sizeof(VisItem) * (size_t)std::max(I0, 1), sizeof(VisItem) * (size_t)I0), o_vblk = seg("vblk", 4 * Vt, 4 * (size_t)V0), o_vblk_anc = seg("vblk_anc", 4 * Vt, 4 * (size_t)V0);
+    const size_t o_bc_win = seg("bc_win", 4 * (size_t)B0), o_bc_i = seg("bc_i", 4 * (size_t)B0), o_bc_j = seg("bc_j", 4 * (size_t)B0), o_bc_w = seg("bc_w", 8 * 6 * (size_t)B0);
+    const size_t o_pJ0 = seg("pJ0", 8 * (size_t)pH0), o_pr0 = seg("pr0", 8 * (size_t)pv0);
+    const size_t o_pH = seg("pH", 8 * (size_t)pH0), o_pb0 = seg("pb0", 8 * (size_t)pv0), o_pc0 = seg("pc0", 8 * (size_t)nw), o_p_x0 = seg("p_x0", 8 * 4 * (size_t)pb);
+    const size_t o_pcol = seg("pcol", 4 * (size_t)pv0), o_p_kind = seg("p_kind", 4 * (size_t)pb), o_p_index = seg("p_index", 4 * (size_t)pb), o_p_off = seg("p_off", 4 * (size_t)pb);
+    const size_t o_pinv = seg("pinv", 4 * (size_t)Pp0), o_bgl_off = seg("bgl_off", 4 * ((size_t)F0 + nw)), o_bgl = seg("bgl", 4 * (size_t)std::max(G0, 1), 4 * (size_t)G0);
+    const size_t o_active = seg("active", (size_t)U0);
+    const size_t o_lm_pos = seg("lm_pos", 4 * (size_t)L0), o_lm_at = seg("lm_at", 4 * (size_t)L0), o_lm_klo = seg("lm_klo", 4 * (size_t)L0), o_lm_khi = seg("lm_khi", 4 * (size_t)L0);
+    const size_t o_tl_beg = seg("tl_beg", 4 * (size_t)TR0), o_tl_end = seg("tl_end", 4 * (size_t)TR0), o_env_first = seg("env_first", 4 * (size_t)TR0), o_env_tile = seg("env_tile", 4 * (size_t)TR0);
     const size_t in_bytes = off;
     bool grew = false;
     HIPCHK(hipStreamSynchronize(stream_));   // the previous batch may still be reading the staging arena (H2D in flight)
@@ -332,7 +346,6 @@ class SolverImpl : public SolverBase {
     char *hb = in_.host, *db = in_.dev;
 #define CTV_H(type, o) reinterpret_cast<type *>(hb + (o))
 #define CTV_D(type, o) reinterpret_cast<type *>(db + (o))
-    std::memcpy(CTV_H(WinMeta, o_meta), meta_.data(), sizeof(WinMeta) * nw);
     double *h_quat = CTV_H(double, o_state), *h_pos = h_quat + (size_t)4 * K0, *h_bias = h_pos + (size_t)3 * K0, *h_rho = h_bias + (size_t)6 * F0,
            *h_ld = h_rho + L0;
     int32_t *h_knot_win = CTV_H(int32_t, o_knot_win), *h_bias_win = CTV_H(int32_t, o_bias_win), *h_lm_win = CTV_H(int32_t, o_lm_win);
@@ -359,7 +372,7 @@ class SolverImpl : public SolverBase {
     int32_t *h_tl_beg = CTV_H(int32_t, o_tl_beg), *h_tl_end = CTV_H(int32_t, o_tl_end), *h_env_first = CTV_H(int32_t, o_env_first), *h_env_tile = CTV_H(int32_t, o_env_tile);
     h_lm_pos_ = h_lm_pos; h_ld_ = h_ld;
     // ---- second pass: every window fills its own slices
-    pool_.run(nw, nth, [&](int wi) {
+    auto fill_window = [&](int wi) {
       const ctvio_window &w = *wins[wi];
       const WinMeta &m = meta_[wi];
       const PackTmp &t = tmp[wi];
@@ -481,7 +494,17 @@ class SolverImpl : public SolverBase {
         for (int gi = 0; gi < m.ngrp; ++gi) h_bgl[m.grp0 + fill[h_groups[m.grp0 + gi].bias]++] = m.grp0 + gi;
         for (int f = 0; f <= w.F; ++f) off[f] += m.grp0;   // absolute positions in bgl
       }
-    });
+    };
+    auto pack = [&]() {
+      std::memcpy(CTV_H(WinMeta, o_meta), meta_.data(), sizeof(WinMeta) * nw);
+      pool_.run(nw, nth, fill_window);
+    };
+    if (dbg_.poison) {   // every byte of every segment must come from the batch: the packs over 0x00 and over 0xFF agree
+      const int rc = check_staging(segs, in_bytes, pack);
+      if (rc != CTVIO_OK) return rc;
+    } else {
+      pack();
+    }
     // ---- device pointers of the input arena
     Dev &d = dev_;
     std::memset(&d, 0, sizeof d);
@@ -529,29 +552,34 @@ class SolverImpl : public SolverBase {
     // ---- work arena (device only)
     state_doubles_ = (size_t)7 * K0 + 6 * F0 + L0 + nw;
     off = 0;
-    const size_t o_cstate = seg(8 * state_doubles_), o_snap = seg(8 * state_doubles_);
-    const size_t o_lkd = seg(8 * 3 * (size_t)K0), o_kjri = seg(sizeof(double) * 9 * (size_t)K0);
-    const size_t o_tiles = seg(sizeof(double) * 1024 * (size_t)G0);
-    const size_t o_imu_cost = seg(8 * (size_t)std::max(G0, 1)), o_vis_cost = seg(8 * ((Vt + 63) / 64)), o_misc_cost = seg(8 * (size_t)nw);
+    segs.clear();
+    const size_t o_cstate = seg("cstate", 8 * state_doubles_), o_snap = seg("snap", 8 * state_doubles_);
+    const size_t o_lkd = seg("lkd", 8 * 3 * (size_t)K0), o_kjri = seg("kjri", sizeof(double) * 9 * (size_t)K0);
+    const size_t o_tiles = seg("tiles", sizeof(double) * 1024 * (size_t)G0);
+    const size_t o_imu_cost = seg("imu_cost", 8 * (size_t)std::max(G0, 1)), o_vis_cost = seg("vis_cost", 8 * ((Vt + 63) / 64)), o_misc_cost = seg("misc_cost", 8 * (size_t)nw);
     // packed partial Hessians of the multi-part store-semantics assembly (knot triangle + line-delay row + gradient per part)
     const size_t part_stride = ((size_t)6 * maxK * (6 * maxK + 1) / 2 + 2 * (6 * (size_t)maxK + 1) + 7) & ~(size_t)7;
     const int nparts_alloc = store_path() ? vis_parts() : 1;
-    const size_t o_pgrad = seg(8 * (size_t)std::max(pv0, 1)), o_Hpart = seg(nparts_alloc > 1 ? 8 * part_stride * nparts_alloc * (size_t)nw : 8);
-    const size_t o_Jt = seg(sizeof(double) * VT_ROWS * 64 * ((Vt + 63) / 64)), o_vsj = seg(4 * Vt);
-    const size_t o_arec = seg(8 * (size_t)AREC * At), o_a_s = seg(4 * At);
+    const size_t o_pgrad = seg("pgrad", 8 * (size_t)std::max(pv0, 1)), o_Hpart = seg("Hpart", nparts_alloc > 1 ? 8 * part_stride * nparts_alloc * (size_t)nw : 8);
+    const size_t o_Jt = seg("Jt", sizeof(double) * VT_ROWS * 64 * ((Vt + 63) / 64)), o_vsj = seg("vsj", 4 * Vt);
+    const size_t o_arec = seg("arec", 8 * (size_t)AREC * At), o_a_s = seg("a_s", 4 * At);
     // two normal-equation sets (current linearisation / speculative linearisation at the candidate, Lm::cur)
-    const size_t o_Hpp = seg(8 * (size_t)H0), o_Hpp1 = seg(8 * (size_t)H0), o_S = seg(8 * (size_t)H0);
+    const size_t o_Hpp = seg("Hpp", 8 * (size_t)H0), o_Hpp1 = seg("Hpp1", 8 * (size_t)H0), o_S = seg("S", 8 * (size_t)H0);
     const size_t o_zero0 = off;   // ---- zeroed at every upload from here ...
-    const size_t o_W = seg(sizeof(double) * (size_t)W0), o_W1 = seg(sizeof(double) * (size_t)W0), o_Hll = seg(8 * (size_t)L0), o_Hll1 = seg(8 * (size_t)L0),
-                 o_g = seg(8 * (size_t)U0), o_g1 = seg(8 * (size_t)U0), o_delta = seg(8 * (size_t)U0),
-                 o_cscale = seg(8 * (size_t)U0), o_lm = seg(sizeof(Lm) * (size_t)nw), o_nact = seg(16), o_dbg = seg(8 * 128);
+    const size_t o_W = seg("W", sizeof(double) * (size_t)W0), o_W1 = seg("W1", sizeof(double) * (size_t)W0), o_Hll = seg("Hll", 8 * (size_t)L0), o_Hll1 = seg("Hll1", 8 * (size_t)L0),
+                 o_g = seg("g", 8 * (size_t)U0), o_g1 = seg("g1", 8 * (size_t)U0), o_delta = seg("delta", 8 * (size_t)U0),
+                 o_cscale = seg("cscale", 8 * (size_t)U0), o_lm = seg("lm", sizeof(Lm) * (size_t)nw), o_nact = seg("nact", 16), o_dbg = seg("dbg", 8 * 128);
     const size_t o_zero1 = off;   // ---- ... to here
-    const size_t o_rhs = seg(8 * (size_t)Pp0), o_dd = seg(8 * (size_t)U0), o_dinv = seg(8 * (size_t)L0), o_grs = seg(8 * (size_t)L0);
+    const size_t o_rhs = seg("rhs", 8 * (size_t)Pp0), o_dd = seg("dd", 8 * (size_t)U0), o_dinv = seg("dinv", 8 * (size_t)L0), o_grs = seg("grs", 8 * (size_t)L0);
     d.chol_nblk = (maxP + 31) / 32;
     d.line_search = opt_.line_search ? 1 : 0;
-    const size_t o_chol_inv = seg(8 * (size_t)nw * d.chol_nblk * 1024);
+    const size_t o_chol_inv = seg("chol_inv", 8 * (size_t)nw * d.chol_nblk * 1024);
     HIPCHK(work_.reserve(off, false, &grew));
-    if (grew) HIPCHK(hipMemsetAsync(work_.dev, 0, work_.cap, stream_));   // fresh memory may hold NaN patterns (0 * NaN in masked products)
+    if (grew || dbg_.poison) HIPCHK(hipMemsetAsync(work_.dev, 0, work_.cap, stream_));   // fresh memory may hold NaN patterns (0 * NaN in masked products)
+    if (dbg_.poison)   // every double segment outside the per-upload zero region starts as the pattern (the integer ones never: they feed addresses)
+      for (const ArenaSeg &sg : segs)
+        if ((sg.off < o_zero0 || sg.off >= o_zero1) && std::strcmp(sg.name, "vsj") != 0 && std::strcmp(sg.name, "a_s") != 0)
+          HIPCHK(poison(work_.dev + sg.off, sg.bytes));
     char *wb = work_.dev;
 #define CTV_W(type, o) reinterpret_cast<type *>(wb + (o))
     d.cquat = CTV_W(double, o_cstate); d.cpos = d.cquat + (size_t)4 * K0; d.cbias = d.cpos + (size_t)3 * K0; d.crho = d.cbias + (size_t)6 * F0; d.cld = d.crho + L0;
@@ -569,10 +597,10 @@ class SolverImpl : public SolverBase {
 #undef CTV_W
     HIPCHK(hipMemsetAsync(wb + o_zero0, 0, o_zero1 - o_zero0, stream_));
     // pinned landing areas of the results
-    if ((size_t)nw > lm_host_cap_) {
+    if ((size_t)nw > lm_host_cap_) {   // (lm_host_cap_ records for the windows, one more as scratch: lm_scratch)
       if (lm_host_) (void)hipHostFree(lm_host_);
       lm_host_cap_ = (size_t)nw + nw / 8 + 16;
-      HIPCHK(hipHostMalloc((void **)&lm_host_, sizeof(Lm) * lm_host_cap_, hipHostMallocDefault));
+      HIPCHK(hipHostMalloc((void **)&lm_host_, sizeof(Lm) * (lm_host_cap_ + 1), hipHostMallocDefault));
     }
     chol_lds_ = chol_lds;
     snap_valid_ = false;
@@ -837,7 +865,7 @@ class SolverImpl : public SolverBase {
   // row of W was written into a neighbour's columns.  Every entry point that launches the kernel ends with this check; the counter is cleared
   // again so that a later call on the same batch (after ctvio_set_state / ctvio_restore_state) starts clean.  The stream must be idle.
   int check_span_violation() {
-    int32_t *viol = reinterpret_cast<int32_t *>(lm_host_ + lm_host_cap_ - 1) + 2;   // (pinned scratch record, beside the "still running" word)
+    int32_t *viol = lm_scratch() + 2;   // (beside the "still running" word)
     HIPCHK(hipMemcpyAsync(viol, dev_.span_viol, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     if (*viol == 0) return CTVIO_OK;
@@ -872,7 +900,7 @@ class SolverImpl : public SolverBase {
       ++it;
       if (it >= pass_cap) break;
       if (it >= max_iters || it % check == 0) {
-        int32_t *na = reinterpret_cast<int32_t *>(lm_host_ + lm_host_cap_ - 1);   // pinned scratch word
+        int32_t *na = lm_scratch();
         HIPCHK(hipMemcpyAsync(na, d.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
         if (*na == 0) break;
@@ -1106,6 +1134,8 @@ class SolverImpl : public SolverBase {
     HIPCHK(mg_idx_.upload(iscr, stream_));
     HIPCHK(mg_scr_.alloc(scr));
     HIPCHK(mg_out_.alloc(outd));
+    HIPCHK(poison(mg_scr_.p, sizeof(double) * scr));
+    HIPCHK(poison(mg_out_.p, sizeof(double) * outd));
     constexpr size_t lds = ((size_t)MARG_MAXD * (MARG_MAXD + 1) / 2 + 4 * MARG_MAXD + 512) * sizeof(double) + 2 * MARG_MAXD * sizeof(int);
     if (!marg_attr_set_) { HIPCHK(hipFuncSetAttribute((const void *)k_marginalize, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); marg_attr_set_ = true; }
     if (bmeta.size() < (size_t)nw)
@@ -1174,6 +1204,8 @@ class SolverImpl : public SolverBase {
     HIPCHK(mb_scr_.alloc(need));
     HIPCHK(mb_part_.alloc((size_t)2 * D / MB_BLK));
     HIPCHK(mb_rank_.alloc((size_t)n));
+    HIPCHK(poison(mb_scr_.p, sizeof(double) * need));
+    HIPCHK(poison(mb_part_.p, sizeof(double) * 2 * D / MB_BLK));
     MbWin b;
     b.w = w; b.m = m; b.n = n; b.dm = dm; b.dn = dn;
     b.im = mg_idx_.p + bm.idx0; b.ik = b.im + m;
@@ -1276,6 +1308,7 @@ class SolverImpl : public SolverBase {
     const int n = 14 + m.pn;
     DBuf<double> out;
     HIPCHK(out.alloc(n));
+    HIPCHK(poison(out.p, sizeof(double) * n));
     hipLaunchKernelGGL(k_residual_summary, dim3(1), dim3(256), (size_t)(14 + 2 * m.pn) * sizeof(double), stream_, dev_, id, out.p);
     HIPCHK(hipMemcpyAsync(sums, out.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
@@ -1328,6 +1361,7 @@ class SolverImpl : public SolverBase {
     for (int i = 0; i < n; ++i) rel[i] = (long long)(t_ns[i] - t0_[id]);
     *reinterpret_cast<int *>(hs + o_err) = 0;
     HIPCHK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, stream_));
+    HIPCHK(poison(ds + o_out, nd * sizeof(double)));
     double *dp = reinterpret_cast<double *>(ds + o_out), *dv = dp + (pose7 ? (size_t)7 * n : 0), *dw = dv + (vel3 ? (size_t)3 * n : 0),
            *da = dw + (omega3 ? (size_t)3 * n : 0);
     hipLaunchKernelGGL(k_spline_eval, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, id, (const int32_t *)nullptr, n, reinterpret_cast<const long long *>(ds),
@@ -1366,6 +1400,7 @@ class SolverImpl : public SolverBase {
     }
     *reinterpret_cast<int *>(hs + o_err) = 0;
     HIPCHK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, stream_));
+    HIPCHK(poison(ds + o_out, nd * sizeof(double)));
     double *dp = reinterpret_cast<double *>(ds + o_out), *dv = dp + (pose7 ? (size_t)7 * n : 0), *dw = dv + (vel3 ? (size_t)3 * n : 0),
            *da = dw + (omega3 ? (size_t)3 * n : 0);
     if (kernel_ms) HIPCHK(hipEventRecord(ev_[10], stream_));
@@ -1417,6 +1452,34 @@ class SolverImpl : public SolverBase {
   // scratch of the small per-call entries (spline query, gauge restore): grow-only device buffer + pinned host mirror
   DBuf<char> call_dev_;
   char *call_host_ = nullptr; size_t call_host_cap_ = 0;
+  // CTVIO_POISON: a reused handle's scratch holds the numbers of earlier calls in another layout, a fresh one zeros.  A kernel that reads
+  // an entry it never wrote and masks it by a product instead of a select is right on zeros only; with the switch every double buffer
+  // the next call reuses starts as a quiet NaN (1) or as a large finite value (2, caught where fmax / fmin or a comparison would drop a
+  // NaN).  Integer buffers are never poisoned.  With the switch off: nothing (one branch per call).
+  hipError_t poison(void *p, size_t bytes) {
+    if (!dbg_.poison || bytes < 4) return hipSuccess;
+    const uint32_t pattern = dbg_.poison == 2 ? 0x5F5F5F5Fu : 0x7FF8DEADu;
+    return hipMemsetD32Async((hipDeviceptr_t)p, (int)pattern, bytes / 4, stream_);
+  }
+  // The upload's staging arena mirrors the device arena byte for byte and is reused: a byte the packer does not write carries the
+  // previous batch to the device.  Packs the batch over 0x00 and over 0xFF and compares every segment's filled extent.
+  template <class Pack> int check_staging(const std::vector<ArenaSeg> &segs, size_t bytes, Pack &&pack) {
+    std::memset(in_.host, 0x00, bytes);
+    pack();
+    const std::vector<char> first(in_.host, in_.host + bytes);
+    std::memset(in_.host, 0xFF, bytes);
+    pack();
+    for (const ArenaSeg &sg : segs) {
+      if (std::memcmp(first.data() + sg.off, in_.host + sg.off, sg.bytes) == 0) continue;
+      size_t i = 0;
+      while (first[sg.off + i] == in_.host[sg.off + i]) ++i;
+      return fail(CTVIO_ERR_INTERNAL, std::string("staging segment ") + sg.name + ": byte " + std::to_string(i) + " of " +
+                                          std::to_string(sg.bytes) + " is not written by the packer");
+    }
+    return CTVIO_OK;
+  }
+  // a pinned word pair for the "still running" and span-violation polls: the record after the lm_host_cap_ window records
+  int32_t *lm_scratch() { return reinterpret_cast<int32_t *>(lm_host_ + lm_host_cap_); }
   int call_scratch(size_t bytes) {
     HIPCHK(call_dev_.alloc(bytes));
     if (bytes > call_host_cap_) {

@@ -286,7 +286,9 @@ int32_t ctvio_graph_captures(const ctvio_solver *s);
  *   CTVIO_STORE_PATH=0|1   CTVIO_SPLIT_LINEARIZE=1   CTVIO_MERGE_LINEARIZE=0|1   CTVIO_ZERO_KERNEL=1   CTVIO_NO_IMU_BAND=1   CTVIO_IMU_WAVES=n
  *   CTVIO_IMU_GENERAL=1   CTVIO_MARG_HOST=1   CTVIO_MARG_DEBUG=1   CTVIO_DEBUG_STAMPS=1
  *   CTVIO_MARG_BLOCKED=1 (ctvio_marginalize_batch: small windows through the blocked path too)
- *   CTVIO_SHARD_OVERSUBSCRIBE=1 (test only; read by ctvio_shards_used / ctvio_solve_sharded at call time) */
+ *   CTVIO_SHARD_OVERSUBSCRIBE=1 (test only; read by ctvio_shards_used / ctvio_solve_sharded at call time)
+ *   CTVIO_POISON=1|2 (test only: reused double scratch starts as quiet NaN / 2.6e151 at every upload and call, and ctvio_upload /
+ *     ctvio_set_batch fail with CTVIO_ERR_INTERNAL if the packer leaves a staged input byte unwritten) */
 
 #ifdef __cplusplus
 }
