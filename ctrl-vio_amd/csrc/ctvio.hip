@@ -31,6 +31,9 @@
 
 namespace ctv {
 
+// A prior built by ctvio_marginalize_batch lives on the next window's trajectory unknowns: every prior it can build must be solvable.
+static_assert(CHOL_MAX_P == MARG_MAXD_BLOCKED, "the batch solve's bound on P and the blocked marginalisation's bound must meet");
+
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
@@ -54,6 +57,8 @@ struct DebugSwitches {
   int schur_tiles = 0;       // CTVIO_SCHUR_TILES=1      tile Schur kernels also for large batches of small windows
   int schur_copy_plain = 0;  // CTVIO_SCHUR_COPY_PLAIN=1 the per-window Schur kernel copies product-free tiles to S
   int chol_tiles = -1;       // CTVIO_CHOL_TILES=0/1/3   P <= 223: panel kernel / k_cholesky_tiles (round 5: barriers) / k_cholesky_flow (default)
+  int chol_compact = 0;      // CTVIO_CHOL_COMPACT=1/n   TEST ONLY: the panel kernel's slot-indexed variant for every batch it would run (1: as many
+                             //                          slots as the batch needs; n >= 2: at most n slots, the rest overflows to S)
   int dense = 0;             // CTVIO_DENSE=1            the sparsity plan degenerates to the dense one
   int schur_tile2 = -1;      // CTVIO_SCHUR_TILE2=0/1    one wave per tile / per 2 x 2 tiles
   int marg_debug = 0;        // CTVIO_MARG_DEBUG=1       sweep trace of the device eigen-solver on stderr
@@ -69,7 +74,7 @@ static DebugSwitches read_debug_switches() {
       {"CTVIO_DEBUG_STAMPS", &g.stamps}, {"CTVIO_STORE_PATH", &g.store_path}, {"CTVIO_SPLIT_LINEARIZE", &g.split_linearize},
       {"CTVIO_MERGE_LINEARIZE", &g.merge_linearize}, {"CTVIO_NO_IMU_BAND", &g.no_imu_band}, {"CTVIO_ZERO_KERNEL", &g.zero_kernel},
       {"CTVIO_IMU_WAVES", &g.imu_waves}, {"CTVIO_IMU_GENERAL", &g.imu_general}, {"CTVIO_SCHUR_TILES", &g.schur_tiles},
-      {"CTVIO_SCHUR_COPY_PLAIN", &g.schur_copy_plain}, {"CTVIO_CHOL_TILES", &g.chol_tiles}, {"CTVIO_DENSE", &g.dense},
+      {"CTVIO_SCHUR_COPY_PLAIN", &g.schur_copy_plain}, {"CTVIO_CHOL_TILES", &g.chol_tiles}, {"CTVIO_CHOL_COMPACT", &g.chol_compact}, {"CTVIO_DENSE", &g.dense},
       {"CTVIO_SCHUR_TILE2", &g.schur_tile2}, {"CTVIO_MARG_DEBUG", &g.marg_debug}, {"CTVIO_MARG_HOST", &g.marg_host},
       {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}, {"CTVIO_POISON", &g.poison}};
   for (const auto &t : tab)
@@ -186,6 +191,8 @@ class SolverImpl : public SolverBase {
     // kernels that need more than 64 KiB of dynamic LDS
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_tiles<16, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_flow, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -243,6 +250,8 @@ class SolverImpl : public SolverBase {
     // envelope); otherwise the panel kernel, which works inside every window's envelope.  (Sizes alone decide: known before planning.)
     int maxP_pre = 0;
     for (int wi = 0; wi < nw; ++wi) if (wins[wi]) maxP_pre = std::max(maxP_pre, 6 * wins[wi]->K + 6 * wins[wi]->F + 1);
+    if (maxP_pre > CHOL_MAX_P)
+      return fail(CTVIO_ERR_INVALID, "window too large for the single-workgroup Cholesky (P = 6K + 6F + 1 > " + std::to_string(CHOL_MAX_P) + ")");
     chol_tiles_ = chol_tiles_for(maxP_pre);   // (decided here, once per batch: launch_step and the Schur launch use the member)
     const bool dense_env = chol_tiles_ != 0 || sparsity_off();
     pool_.run(nw, nth, [&](int wi) {
@@ -264,7 +273,8 @@ class SolverImpl : public SolverBase {
     t0_.resize(nw);
     int64_t H0 = 0, W0 = 0, pH0 = 0;
     int K0 = 0, F0 = 0, L0 = 0, M0 = 0, V0 = 0, B0 = 0, U0 = 0, Pp0 = 0, pv0 = 0, pb = 0, G0 = 0, I0 = 0, A0 = 0, TR0 = 0, maxSpan = 1;
-    int maxN = 0, maxP = 0, maxPn = 0, maxL = 0, maxLdw = 0, maxK = 0, maxSchurTiles = 0;
+    int maxN = 0, maxP = 0, maxPn = 0, maxL = 0, maxLdw = 0, maxK = 0, maxSchurTiles = 0, maxSlots = 0;
+    const bool slots_needed = chol_tiles_ == 0 && (chol_panel_lds(maxP_pre) > 160 * 1024 || dbg_.chol_compact > 0);   // (the variant's choice below)
     size_t vis_lds_bytes = vis_stage_bytes(), vis_glb_bytes = vis_stage_bytes();
     for (int wi = 0; wi < nw; ++wi) {
       const ctvio_window &w = *wins[wi];
@@ -296,6 +306,7 @@ class SolverImpl : public SolverBase {
       H0 += (int64_t)m.P * m.ldh; W0 += (int64_t)m.Lpad * m.ldw; pH0 += (int64_t)w.pn * w.pn;
       maxN = std::max(maxN, m.N); maxP = std::max(maxP, m.P); maxPn = std::max(maxPn, w.pn);
       maxL = std::max(maxL, m.L); maxLdw = std::max(maxLdw, m.ldw); maxK = std::max(maxK, m.K);
+      if (slots_needed) maxSlots = std::max(maxSlots, chol_panel_slots(tmp[wi].env_first.data(), m.P));
       {   // 16 x 16 tiles of the reduced system that receive Schur products (k_schur_window_f64): knot columns, line delay, rhs row
         const int ntl = m.ldw / 16, K6 = 6 * m.K;
         int cnt = 0;
@@ -308,8 +319,19 @@ class SolverImpl : public SolverBase {
         maxSchurTiles = std::max(maxSchurTiles, cnt);
       }
     }
-    const size_t chol_lds = (size_t)(2 * 32 * 34 + 32 + 34 + 32 + (size_t)((std::max(maxP - 32, 0) + 1 + 15) / 16 * 16) * 32) * sizeof(double);
-    if (chol_lds > 160 * 1024) return fail(CTVIO_ERR_INVALID, "window too large for the single-workgroup Cholesky (P > ~600)");
+    // The panel kernel's LDS: a fixed part and the panel, 32 columns x the full trailing height (P <= 591 fits 160 KB).  Batches beyond that
+    // (or CTVIO_CHOL_COMPACT) take the slot-indexed variant: 32 x 16 doubles per slot, as many slots as the batch's panels need or fit; the
+    // back-substitution reuses the panel as xs[P].
+    size_t chol_lds = chol_panel_lds(maxP);
+    chol_compact_ = slots_needed;
+    int chol_slots = 0;
+    if (chol_compact_) {
+      const int fit = (int)((160 * 1024 / sizeof(double) - chol_lds_fixed) / (32 * 16));
+      chol_slots = std::min(maxSlots, fit);
+      if (dbg_.chol_compact >= 2) chol_slots = std::min(chol_slots, dbg_.chol_compact);
+      chol_slots = std::max(chol_slots, 2);   // (local tiles 0 and 1, the next diagonal block, take part in every panel)
+      chol_lds = (chol_lds_fixed + std::max((size_t)32 * 16 * chol_slots, (size_t)maxP)) * sizeof(double);
+    }
     const size_t Mt = (size_t)std::max(M0, 1), Vt = (size_t)std::max(V0, 1), At = (size_t)std::max(A0, 1);
     Mtot_ = M0; Vtot_ = V0;
     // ---- input arena layout (host mirror + device)
@@ -572,6 +594,7 @@ class SolverImpl : public SolverBase {
     const size_t o_zero1 = off;   // ---- ... to here
     const size_t o_rhs = seg("rhs", 8 * (size_t)Pp0), o_dd = seg("dd", 8 * (size_t)U0), o_dinv = seg("dinv", 8 * (size_t)L0), o_grs = seg("grs", 8 * (size_t)L0);
     d.chol_nblk = (maxP + 31) / 32;
+    d.chol_slots = chol_slots;
     d.line_search = opt_.line_search ? 1 : 0;
     const size_t o_chol_inv = seg("chol_inv", 8 * (size_t)nw * d.chol_nblk * 1024);
     HIPCHK(work_.reserve(off, false, &grew));
@@ -753,6 +776,11 @@ class SolverImpl : public SolverBase {
     }
     // (8 waves also when the panel's LDS footprint allows one workgroup per CU anyway -- P = 571: 157 KB -- where 4 waves left three quarters
     //  of the CU's wave slots empty)
+    // (windows beyond 591 unknowns: the slot-indexed variant, same wave-count rule)
+    else if (chol_compact_) {
+      if (nw <= 192 || chol_lds_ > 80 * 1024) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(nw), dim3(512), chol_lds_, stream_, d);
+      else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(nw), dim3(256), chol_lds_, stream_, d);
+    }
     else if (nw <= 192 || chol_lds_ > 80 * 1024) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(nw), dim3(512), chol_lds_, stream_, d);
     else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(nw), dim3(256), chol_lds_, stream_, d);
     ph_end();
@@ -803,6 +831,9 @@ class SolverImpl : public SolverBase {
     return 3;   // (register-resident tiles as a data-flow of waves: k_cholesky_flow; 1 = round 5's k_cholesky_tiles, the barrier-per-panel form)
   }
   int chol_tiles() const { return chol_tiles_; }   // the batch's choice, taken in pack_and_upload
+  // k_cholesky_solve's LDS in doubles: Lb, LiT, dinvs, yb, flags, plist (fixed) + the panel, 32 columns x the trailing height of the first panel
+  static constexpr size_t chol_lds_fixed = 2 * 32 * 34 + 32 + 34 + 32;
+  static size_t chol_panel_lds(int maxP) { return (chol_lds_fixed + (size_t)((std::max(maxP - 32, 0) + 1 + 15) / 16 * 16) * 32) * sizeof(double); }
   // CTVIO_DENSE=1: the sparsity plan degenerates to the dense one (every row range = all landmarks, envelope = the whole triangle) -- the
   // A/B switch of the sparsity-aware kernels and the cross-check of tests/test_gpu_sparsity.py
   bool sparsity_off() const { return dbg_.dense == 1; }
@@ -1432,6 +1463,7 @@ class SolverImpl : public SolverBase {
   ctvio_options opt_;
   const DebugSwitches dbg_;   // environment switches as they were when the handle was created
   int chol_tiles_ = 3;        // the uploaded batch's factorisation kernel (0 panel kernel, 1 / 3 register tiles): pack_and_upload
+  bool chol_compact_ = false; // panel kernel: its slot-indexed variant (Dev::chol_slots), for windows beyond 591 unknowns: pack_and_upload
   int marg_ran_on_host_ = 0;  // the last ctvio_marginalize(_batch) call: 1 if the factorisation ran on the host
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -161,6 +161,7 @@ struct Dev {
   double *S, *rhs;       // Schur complement (lower) and its right-hand side [sum P]
   double *chol_inv;      // [nwin][chol_nblk][32][32] inverses of the diagonal blocks of the Cholesky factor (row-major)
   int32_t chol_nblk;
+  int32_t chol_slots;    // k_cholesky_solve<NW, true>: 16-row tiles its slot-indexed LDS panel holds (host_pack.hpp: chol_panel_slots)
   double *dd, *dinv;     // LM damping per unknown [Utot]; 1/(Hll + dd) [Ltot] by ROW of W (sorted landmark order)
   double *cscale;        // Jacobi scaling [Utot]
   double *delta;         // step [Utot]

@@ -376,6 +376,20 @@ inline void plan_sparsity(const ctvio_window *w, bool dense, bool full_ranges, P
   }
 }
 
+// The most 16-row tiles that take part in one 32-column panel of k_cholesky_solve, by the kernel's own rule (tile R0 + l below panel jb takes
+// part iff env_first[R0 + l] <= jb / 16 + 1): the LDS slots its slot-indexed variant needs to stage every panel of the window without overflow.
+// ef: plan_sparsity's env_first (P / 16 + 1 entries).  Python mirror: packer.chol_panel_slots.
+inline int chol_panel_slots(const int32_t *ef, int P) {
+  int best = 0;
+  for (int jb = 0; jb < P; jb += 32) {
+    const int r0 = std::min(jb + 32, P), ntile = (P - r0 + 1 + 15) / 16, R0 = r0 / 16;
+    int n = 0;
+    for (int l = 0; l < ntile; ++l) n += ef[std::min(R0 + l, P / 16)] <= jb / 16 + 1 ? 1 : 0;
+    best = std::max(best, n);
+  }
+  return best;
+}
+
 // Unknowns of Ceres' reduced program: referenced by some residual block and not constant
 // (trajectory_estimator.cpp:114-141, 236-245, 311-318).
 inline void active_mask(const ctvio_window *w, const PackTmp &t, int P, const int32_t *pcol, uint8_t *act) {

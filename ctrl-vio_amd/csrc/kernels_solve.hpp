@@ -596,7 +596,15 @@ __device__ __forceinline__ void chol_diag_all(double (&v)[32], int &bad) {
 // A 16-row tile R below panel jb TAKES PART in it iff env_first[R] <= jb / 16 + 1; only those tiles are staged, solved against L11 and updated,
 // and a trailing tile (Ri, Rj) is touched only when both rows take part.  Config 5 (K = 64, P = 571): 1.9 k of 7.8 k tile products.  The host
 // aligns the envelope to the 32-column panels and makes the next diagonal block take part in every panel (its look-ahead below).
-template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_cholesky_solve(Dev d) {
+// COMPACT (windows whose full-height panel does not fit the LDS: 591 < P <= CHOL_MAX_P): the panel is SLOT-INDEXED -- the it-th tile that takes
+// part (plist[it]) is staged at slot it, not at its local tile, so the LDS holds Dev::chol_slots tiles, the most that take part in any panel of
+// the batch (host_pack.hpp: chol_panel_slots).  Tiles beyond the slots (a dense envelope: CTVIO_DENSE=1, a window with a prior, whose kept
+// blocks couple mutually) OVERFLOW: they are not staged, the L21 step reads A21 from S / y and stores L21 there as always, and the trailing
+// update reads these operands back from S / y (columns jb .. jb + nb, below r0: nothing writes them in the update).  Same MFMA sequence and
+// summation order as the LDS path: both give the same bits.
+constexpr int CHOL_MAX_P = 1024;   // largest P of the batch solve (ctvio.h); equal to MARG_MAXD_BLOCKED (ctvio.hip)
+static_assert((CHOL_MAX_P - 32 + 1 + 15) / 16 <= 64, "the tiles below the first panel must fit one 64-lane ballot and plist[64]");
+template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_cholesky_solve(Dev d) {
   constexpr int NT = 64 * NW;
   const int w = blockIdx.x;
   Lm &lm = d.lm[w];
@@ -611,7 +619,8 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
   int &s_fail = *reinterpret_cast<int *>(yb + 32);
   int &s_trip = reinterpret_cast<int *>(yb + 32)[1];   // next unclaimed tile of the trailing update
   int *plist = reinterpret_cast<int *>(yb + 34);       // [64] the local 16-row tiles that take part in the current panel, ascending
-  double *LpT = yb + 34 + 32;       // [32][RS] panel (+ rhs row) k-major: LpT[k][r]
+  double *LpT = yb + 34 + 32;       // [32][RS] panel (+ rhs row) k-major: LpT[k][r]  (COMPACT: [32][16 chol_slots], LpT[k][16 slot + r % 16])
+  const int slots = COMPACT ? d.chol_slots : 64;
   double *S = d.S + m.H0;
   double *y = d.rhs + m.p0;         // augmented row; becomes L^-1 rhs
   double *x = d.delta + m.u0;
@@ -660,7 +669,8 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
   for (int jb = 0; jb < P; jb += 32) {
     const int nb = min(32, P - jb), r0 = jb + nb, nt = P - r0, ntr = nt + 1;  // ntr: trailing rows incl. the rhs row
     const int RS = (ntr + 15) & ~15, ntile = RS >> 4;
-    // ---- the tiles that take part (every wave forms the same mask: one ballot; <= 36 local tiles).  The last wave lists them in LDS.
+    const int PS = COMPACT ? 16 * slots : RS;   // the panel's row stride
+    // ---- the tiles that take part (every wave forms the same mask: one ballot; <= 36 local tiles, COMPACT <= 64).  The last wave lists them in LDS.
     const int R0 = r0 >> 4;
     const bool mine = lane < ntile && ef[min(R0 + lane, P / 16)] <= (jb >> 4) + 1;
     const unsigned long long pmask = __ballot(mine);
@@ -673,13 +683,19 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
       if (jb == 0 && wave == 0) diag_block(0);
       for (int r = tid - first; r >= 0 && r < RS; r += nthr) {
         if (!((pmask >> (r >> 4)) & 1ull)) continue;   // a tile outside the panel's envelope: nothing of it is read below
+        int pr = r;                                     // the row's place in the panel
+        if constexpr (COMPACT) {
+          const int it = __popcll(pmask & ((1ull << (r >> 4)) - 1ull));
+          if (it >= slots) continue;                    // overflow: the L21 step reads the row from S / y
+          pr = 16 * it + (r & 15);
+        }
         const double *src = (r < nt) ? S + (long long)(r0 + r) * ldh + jb : y + jb;
         double tmp[32];
 #pragma unroll
         for (int k = 0; k < 32; ++k) tmp[k] = src[min(k, nb - 1)];   // unconditional: 32 loads in flight
         const bool live = r < ntr;
 #pragma unroll
-        for (int k = 0; k < 32; ++k) LpT[k * RS + r] = (live && k < nb) ? tmp[k] : 0.0;
+        for (int k = 0; k < 32; ++k) LpT[k * PS + pr] = (live && k < nb) ? tmp[k] : 0.0;
       }
     }
     if (tid == 0) s_trip = 4;   // wave 0 starts with tiles 0-3 (they hold the next diagonal block)
@@ -691,20 +707,27 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
     // ---- L21 = A21 L11^-T, in place: Linv is lower triangular, so output columns 0..15 need k < 16 only
     for (int it = wave; it < np; it += NW) {
       const int tr = plist[it];
+      const bool staged = !COMPACT || it < slots;      // (uniform over the wave)
+      const int pt = COMPACT ? 16 * it : 16 * tr;       // the tile's first row in the panel
       f64x4 c0 = {0.0, 0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0, 0.0};
-      const double *pa = LpT + 16 * tr + l15;
+      const double *pa = LpT + pt + l15;
+      const int arow = 16 * tr + l15;
+      const double *asrc = (arow < nt) ? S + (long long)(r0 + arow) * ldh + jb : y + jb;   // overflow: A21 as the staging would have read it
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk) {
         const int k = 4 * kk + q4;
-        const double av = pa[k * RS];
+        const double av = staged ? pa[k * PS] : ((arow < ntr && k < nb) ? asrc[k] : 0.0);
         if (kk < 4) c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, LiT[k * 34 + l15], c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, LiT[k * 34 + 16 + l15], c1, 0, 0, 0);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 16 * tr + q4 + 4 * r;
-        LpT[l15 * RS + row] = c0[r];
-        LpT[(16 + l15) * RS + row] = c1[r];
+        const int prow = COMPACT ? pt + q4 + 4 * r : row;
+        if (staged) {
+          LpT[l15 * PS + prow] = c0[r];
+          LpT[(16 + l15) * PS + prow] = c1[r];
+        }
         if (row < ntr) {
           double *dst = (row < nt) ? S + (long long)(r0 + row) * ldh + jb : y + jb;
           if (l15 < nb) dst[l15] = c0[r];
@@ -727,12 +750,13 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
       else tb = __builtin_amdgcn_readfirstlane(lane == 0 ? atomicAdd(&s_trip, 4) : 0);
       if (tb >= ntt) break;
       double sv[4][4];
-      int ti4[4], tj4[4];
+      int ti4[4], tj4[4], si4[4], sj4[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         int pa_, pb_;
         tile_decode(min(tb + u, ntt - 1), pa_, pb_);
         ti4[u] = plist[pa_]; tj4[u] = plist[pb_];
+        si4[u] = pa_; sj4[u] = pb_;
         const int col = 16 * tj4[u] + l15;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -744,11 +768,31 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         f64x4 c = {0.0, 0.0, 0.0, 0.0};
-        const double *pa = LpT + 16 * ti4[u] + l15, *pb = LpT + 16 * tj4[u] + l15;
+        if constexpr (!COMPACT) {
+          const double *pa = LpT + 16 * ti4[u] + l15, *pb = LpT + 16 * tj4[u] + l15;
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-          const int k = 4 * kk + q4;
-          c = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[k * RS], pb[k * RS], c, 0, 0, 0);
+          for (int kk = 0; kk < 8; ++kk) {
+            const int k = 4 * kk + q4;
+            c = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[k * RS], pb[k * RS], c, 0, 0, 0);
+          }
+        } else {
+          // an operand tile: its slot in LDS, or (overflow) the L21 rows the L21 step stored into S / y, columns >= nb masked to zero
+          auto opnd = [&](int s, int t, double (&o)[8]) {
+            if (s < slots) {
+#pragma unroll
+              for (int kk = 0; kk < 8; ++kk) o[kk] = LpT[(4 * kk + q4) * PS + 16 * s + l15];
+            } else {
+              const int row = 16 * t + l15;
+              const double *src = (row < nt) ? S + (long long)(r0 + row) * ldh + jb : y + jb;
+#pragma unroll
+              for (int kk = 0; kk < 8; ++kk) o[kk] = (row < ntr && 4 * kk + q4 < nb) ? src[4 * kk + q4] : 0.0;
+            }
+          };
+          double oa[8], ob[8];
+          opnd(si4[u], ti4[u], oa);
+          opnd(sj4[u], tj4[u], ob);
+#pragma unroll
+          for (int kk = 0; kk < 8; ++kk) c = __builtin_amdgcn_mfma_f64_16x16x4f64(oa[kk], ob[kk], c, 0, 0, 0);
         }
         const int col = 16 * tj4[u] + l15;
 #pragma unroll
@@ -775,7 +819,7 @@ template <int NW> __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_wa
   //      for the rows above.  x lives in LDS; per block the loads of Linv_b (wave 0) and of the panel rows (everyone) do
   //      not depend on x and are issued together, before the block solve.  Block row b reaches back to column 16 env_first only: the two
   //      16-row tiles of the block have their own starts (ca <= cb or cb <= ca), columns before a tile's start are not stored at all.
-  double *xs = LpT;   // the panel is no longer needed
+  double *xs = LpT;   // the panel is no longer needed (COMPACT: the host sizes it to at least P doubles)
   for (int i = tid; i < P; i += NT) xs[i] = y[i];
   __syncthreads();
   const int nblk = (P + 31) / 32;

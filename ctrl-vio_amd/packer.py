@@ -175,6 +175,18 @@ def reduced_system_envelope(w, align_panels=True):
     return env
 
 
+def chol_panel_slots(P, env):
+    """Mirror of host_pack.hpp: chol_panel_slots -- the most 16-row tiles that take part in one 32-column panel of the panel Cholesky (tile
+    R0 + l below panel jb takes part iff env[R0 + l] <= jb // 16 + 1): the LDS slots its slot-indexed variant needs to stage every panel."""
+    best = 0
+    for jb in range(0, P, 32):
+        r0 = min(jb + 32, P)
+        ntile = (P - r0 + 1 + 15) // 16
+        R0 = r0 // 16
+        best = max(best, sum(1 for l in range(ntile) if env[min(R0 + l, P // 16)] <= jb // 16 + 1))
+    return best
+
+
 def envelope_entries(w, dense=False):
     """Entries of the lower triangle of S inside the envelope (what a factorisation must read at least once); dense: P (P + 1) / 2."""
     P = w.P

@@ -147,7 +147,7 @@ int32_t ctvio_add_window(ctvio_solver *s, const ctvio_window *w, int32_t *id);
 /* Pack (sort IMU samples into (segment,bias) groups, visual blocks landmark by landmark, prior J0^T J0, ...), PLAN THE SPARSITY of the
  * reduced system -- what the reference leaves to Ceres' SPARSE_NORMAL_CHOLESKY (trajectory_estimator.cpp:371-384): every landmark's knot span
  * over the box [ld_lo, ld_hi] of the line delay, the row order of Hpl, the envelope of the Schur complement -- and copy to HBM.
- * Checked here (CTVIO_ERR_INVALID otherwise): P = 6K + 6F + 1 <= ~600; at most 64 visual blocks per landmark; finite observations and line
+ * Checked here (CTVIO_ERR_INVALID otherwise): P = 6K + 6F + 1 <= 1024; at most 64 visual blocks per landmark; finite observations and line
  * delay; ld_lo <= ld_hi for a free line delay; every row time t + row * ld inside the spline for ld at both ends of the box. */
 int32_t ctvio_upload(ctvio_solver *s);
 /* ctvio_clear + n x ctvio_add_window + ctvio_upload in one call, without the intermediate host copy: the n windows are
@@ -288,7 +288,9 @@ int32_t ctvio_graph_captures(const ctvio_solver *s);
  *   CTVIO_MARG_BLOCKED=1 (ctvio_marginalize_batch: small windows through the blocked path too)
  *   CTVIO_SHARD_OVERSUBSCRIBE=1 (test only; read by ctvio_shards_used / ctvio_solve_sharded at call time)
  *   CTVIO_POISON=1|2 (test only: reused double scratch starts as quiet NaN / 2.6e151 at every upload and call, and ctvio_upload /
- *     ctvio_set_batch fail with CTVIO_ERR_INTERNAL if the packer leaves a staged input byte unwritten) */
+ *     ctvio_set_batch fail with CTVIO_ERR_INTERNAL if the packer leaves a staged input byte unwritten)
+ *   CTVIO_CHOL_COMPACT=1|n (test only: every batch the panel Cholesky factors takes its slot-indexed variant, which otherwise runs only for
+ *     windows beyond 591 unknowns; 1 = as many LDS slots as the batch needs, n >= 2 = at most n, the tiles beyond overflow to S) */
 
 #ifdef __cplusplus
 }
