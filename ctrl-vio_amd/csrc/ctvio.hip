@@ -273,7 +273,8 @@ class SolverImpl : public SolverBase {
     t0_.resize(nw);
     int64_t H0 = 0, W0 = 0, pH0 = 0;
     int K0 = 0, F0 = 0, L0 = 0, M0 = 0, V0 = 0, B0 = 0, U0 = 0, Pp0 = 0, pv0 = 0, pb = 0, G0 = 0, I0 = 0, A0 = 0, TR0 = 0, maxSpan = 1;
-    int maxN = 0, maxP = 0, maxPn = 0, maxL = 0, maxLdw = 0, maxK = 0, maxSchurTiles = 0, maxSlots = 0;
+    int maxN = 0, maxP = 0, maxPn = 0, maxL = 0, maxLdw = 0, maxK = 0, maxSchurTiles = 0, maxSlots = 0, maxK_lds = 0;
+    bool any_wide = false;
     const bool slots_needed = chol_tiles_ == 0 && (chol_panel_lds(maxP_pre) > 160 * 1024 || dbg_.chol_compact > 0);   // (the variant's choice below)
     size_t vis_lds_bytes = vis_stage_bytes(), vis_glb_bytes = vis_stage_bytes();
     for (int wi = 0; wi < nw; ++wi) {
@@ -298,6 +299,7 @@ class SolverImpl : public SolverBase {
         const size_t need = ((nH + 3) & ~(size_t)3) * sizeof(double) + 32 + vis_stage_bytes();   // fp64 accumulators in LDS
         const size_t need_glb = ((nG + 3) & ~(size_t)3) * sizeof(double) + 16 + vis_stage_bytes();
         m.vis_lds = need <= 160 * 1024 ? 1 : 0;
+        if (m.vis_lds) maxK_lds = std::max(maxK_lds, w.K); else any_wide = true;
         vis_lds_bytes = std::max(vis_lds_bytes, m.vis_lds ? need : need_glb);
         vis_glb_bytes = std::max(vis_glb_bytes, need_glb);
       }
@@ -361,6 +363,9 @@ class SolverImpl : public SolverBase {
     const size_t o_active = seg("active", (size_t)U0);
     const size_t o_lm_pos = seg("lm_pos", 4 * (size_t)L0), o_lm_at = seg("lm_at", 4 * (size_t)L0), o_lm_klo = seg("lm_klo", 4 * (size_t)L0), o_lm_khi = seg("lm_khi", 4 * (size_t)L0);
     const size_t o_tl_beg = seg("tl_beg", 4 * (size_t)TR0), o_tl_end = seg("tl_end", 4 * (size_t)TR0), o_env_first = seg("env_first", 4 * (size_t)TR0), o_env_tile = seg("env_tile", 4 * (size_t)TR0);
+    // the walk of the order-fixed wide-window assembly (deterministic = 2 with a window beyond the LDS-resident Hessian; else not uploaded)
+    const bool walk = opt_.deterministic == 2 && any_wide;
+    const size_t o_vrow = seg("vrow", walk ? 4 * Vt : 4, walk ? 4 * (size_t)V0 : 0), o_vrow_off = seg("vrow_off", walk ? 4 * ((size_t)L0 + nw) : 4, walk ? 4 * ((size_t)L0 + nw) : 0);
     const size_t in_bytes = off;
     bool grew = false;
     HIPCHK(hipStreamSynchronize(stream_));   // the previous batch may still be reading the staging arena (H2D in flight)
@@ -392,6 +397,7 @@ class SolverImpl : public SolverBase {
     int32_t *h_pinv = CTV_H(int32_t, o_pinv), *h_bgl_off = CTV_H(int32_t, o_bgl_off), *h_bgl = CTV_H(int32_t, o_bgl);
     int32_t *h_lm_pos = CTV_H(int32_t, o_lm_pos), *h_lm_at = CTV_H(int32_t, o_lm_at), *h_lm_klo = CTV_H(int32_t, o_lm_klo), *h_lm_khi = CTV_H(int32_t, o_lm_khi);
     int32_t *h_tl_beg = CTV_H(int32_t, o_tl_beg), *h_tl_end = CTV_H(int32_t, o_tl_end), *h_env_first = CTV_H(int32_t, o_env_first), *h_env_tile = CTV_H(int32_t, o_env_tile);
+    int32_t *h_vrow = CTV_H(int32_t, o_vrow), *h_vrow_off = CTV_H(int32_t, o_vrow_off);
     h_lm_pos_ = h_lm_pos; h_ld_ = h_ld;
     // ---- second pass: every window fills its own slices
     auto fill_window = [&](int wi) {
@@ -412,6 +418,10 @@ class SolverImpl : public SolverBase {
       }
       std::memcpy(h_tl_beg + m.tr0, t.tl_beg.data(), 4 * (size_t)m.ntr); std::memcpy(h_tl_end + m.tr0, t.tl_end.data(), 4 * (size_t)m.ntr);
       std::memcpy(h_env_first + m.tr0, t.env_first.data(), 4 * (size_t)m.ntr); std::memcpy(h_env_tile + m.tr0, t.env_tile.data(), 4 * (size_t)m.ntr);
+      if (walk) {
+        plan_row_walk(&w, t, h_vrow + m.vis0, h_vrow_off + m.lm0 + wi);
+        std::fill(h_vrow + m.vis0 + w.V, h_vrow + m.vis0 + m.Vp, 0);   // (unused tail of the window's list)
+      }
       // IMU samples in (segment, bias) order; groups = runs of equal (segment, bias)
       int g = m.grp0 - 1;
       for (int i = 0; i < w.M; ++i) {
@@ -551,6 +561,7 @@ class SolverImpl : public SolverBase {
     d.lm_pos = CTV_D(int32_t, o_lm_pos); d.lm_at = CTV_D(int32_t, o_lm_at); d.lm_klo = CTV_D(int32_t, o_lm_klo); d.lm_khi = CTV_D(int32_t, o_lm_khi);
     d.tl_beg = CTV_D(int32_t, o_tl_beg); d.tl_end = CTV_D(int32_t, o_tl_end); d.env_first = CTV_D(int32_t, o_env_first); d.env_tile = CTV_D(int32_t, o_env_tile);
     d.max_span6 = 6 * maxSpan;
+    d.vrow = walk ? CTV_D(int32_t, o_vrow) : nullptr; d.vrow_off = walk ? CTV_D(int32_t, o_vrow_off) : nullptr;
 #undef CTV_H
 #undef CTV_D
     HIPCHK(hipMemcpyAsync(in_.dev, in_.host, in_bytes, hipMemcpyHostToDevice, stream_));
@@ -565,9 +576,11 @@ class SolverImpl : public SolverBase {
     // (the member goes into the launch signature and selects kernels: it must say what RUNS -- the default falls back to the accumulate path
     //  for batches the order-fixed assembly cannot cover, and then it is off)
     if (!any_vis_lds_ || any_vis_glb_) { if (opt_.deterministic <= 0) deterministic_ = false; }
-    // The order-fixed accumulation exists for batches whose every window keeps its packed Hessian in LDS, on the matrix-core kernels.
-    // An explicit request that cannot be honoured is an error; the default (-1) falls back to the accumulate path for such batches.
-    if (opt_.deterministic > 0 && (!any_vis_lds_ || any_vis_glb_))
+    // deterministic = 1: the order-fixed accumulation of the batches whose every window keeps its packed Hessian in LDS, on the matrix-core
+    // kernels.  An explicit request that cannot be honoured is an error; the default (-1) falls back to the accumulate path for such batches.
+    // deterministic = 2: every batch -- the other windows take the order-fixed wide-window assembly (k_assemble_wide).
+    wide_fixed_ = deterministic_ && opt_.deterministic == 2 && any_vis_glb_;
+    if (opt_.deterministic > 0 && opt_.deterministic != 2 && (!any_vis_lds_ || any_vis_glb_))
       return fail(CTVIO_ERR_INVALID, "deterministic = 1 needs every window's packed Hessian in LDS (K <= 25): this batch would "
                                      "fall back to floating-point atomics");
     maxK_ = maxK;
@@ -580,11 +593,14 @@ class SolverImpl : public SolverBase {
     const size_t o_tiles = seg("tiles", sizeof(double) * 1024 * (size_t)G0);
     const size_t o_imu_cost = seg("imu_cost", 8 * (size_t)std::max(G0, 1)), o_vis_cost = seg("vis_cost", 8 * ((Vt + 63) / 64)), o_misc_cost = seg("misc_cost", 8 * (size_t)nw);
     // packed partial Hessians of the multi-part store-semantics assembly (knot triangle + line-delay row + gradient per part)
-    const size_t part_stride = ((size_t)6 * maxK * (6 * maxK + 1) / 2 + 2 * (6 * (size_t)maxK + 1) + 7) & ~(size_t)7;
-    const int nparts_alloc = store_path() ? vis_parts() : 1;
+    // (only the LDS-resident windows have parts: with deterministic = 2 a batch may hold wider ones)
+    const int kpart = wide_fixed_ ? maxK_lds : maxK;
+    const size_t part_stride = ((size_t)6 * kpart * (6 * kpart + 1) / 2 + 2 * (6 * (size_t)kpart + 1) + 7) & ~(size_t)7;
+    const int nparts_alloc = store_path() && kpart > 0 ? vis_parts() : 1;
     const size_t o_pgrad = seg("pgrad", 8 * (size_t)std::max(pv0, 1)), o_Hpart = seg("Hpart", nparts_alloc > 1 ? 8 * part_stride * nparts_alloc * (size_t)nw : 8);
     const size_t o_Jt = seg("Jt", sizeof(double) * VT_ROWS * 64 * ((Vt + 63) / 64)), o_vsj = seg("vsj", 4 * Vt);
     const size_t o_arec = seg("arec", 8 * (size_t)AREC * At), o_a_s = seg("a_s", 4 * At);
+    const size_t o_vexp = seg("vexp", wide_fixed_ ? sizeof(double) * VX_LD * Vt : 8);   // expanded block records of the wide windows (k_vis_expand)
     // two normal-equation sets (current linearisation / speculative linearisation at the candidate, Lm::cur)
     const size_t o_Hpp = seg("Hpp", 8 * (size_t)H0), o_Hpp1 = seg("Hpp1", 8 * (size_t)H0), o_S = seg("S", 8 * (size_t)H0);
     const size_t o_zero0 = off;   // ---- zeroed at every upload from here ...
@@ -611,6 +627,7 @@ class SolverImpl : public SolverBase {
     d.imu_cost = CTV_W(double, o_imu_cost); d.vis_cost = CTV_W(double, o_vis_cost); d.misc_cost = CTV_W(double, o_misc_cost);
     d.pgrad = CTV_W(double, o_pgrad); d.Hpart = CTV_W(double, o_Hpart); d.npart_stride = (int32_t)part_stride;
     d.Jt = CTV_W(double, o_Jt); d.vsj = CTV_W(int32_t, o_vsj); d.arec = CTV_W(double, o_arec); d.a_s = CTV_W(int32_t, o_a_s);
+    d.vexp = wide_fixed_ ? CTV_W(double, o_vexp) : nullptr;
     d.HppS[0] = CTV_W(double, o_Hpp); d.HppS[1] = CTV_W(double, o_Hpp1); d.S = CTV_W(double, o_S);
     d.WS[0] = CTV_W(double, o_W); d.WS[1] = CTV_W(double, o_W1); d.HllS[0] = CTV_W(double, o_Hll); d.HllS[1] = CTV_W(double, o_Hll1);
     d.gS[0] = CTV_W(double, o_g); d.gS[1] = CTV_W(double, o_g1);
@@ -646,7 +663,10 @@ class SolverImpl : public SolverBase {
   // Store-semantics assembly tail (kernels.hpp: bias_rows_store; every entry written once, no atomics): the deterministic mode, when
   // every window's packed Hessian is LDS resident.  (CTVIO_STORE_PATH=1 forces it for the throughput mode too: measured slower there,
   // the bias-row gather costs more than the zeroing + atomic passes it replaces -- 14.5 vs 13.4 ms per 2048-window solve.)
+  // With deterministic = 2 and a window beyond the LDS-resident Hessian the choice is per window: the LDS-resident ones take this tail, the
+  // others k_assemble_wide -- both store every entry once, so the batch has no zeroing pass and no atomic assembly at all.
   bool store_path() const {
+    if (wide_fixed_) return true;
     if (!any_vis_lds_ || any_vis_glb_) return false;
     if (dbg_.store_path >= 0) return dbg_.store_path == 1;
     return deterministic_;
@@ -729,9 +749,12 @@ class SolverImpl : public SolverBase {
     if (store_path()) {
       // every entry of Hpp / g is written once, completely, with a plain store: no zeroing pass, no k_assemble_imu, no atomics
       ph_begin(PH_ASM_VIS);
-      launch_assemble_vis_store(parts, mode);
-      if (parts > 1) hipLaunchKernelGGL(k_reduce_finalize, dim3(deterministic_ ? 48 : 24, nw), dim3(256), 0, stream_, d, mode, parts);
-      else hipLaunchKernelGGL(k_bias_rows, dim3(8, nw), dim3(256), 0, stream_, d, mode);
+      if (!wide_fixed_ || any_vis_lds_) {
+        launch_assemble_vis_store(parts, mode);
+        if (parts > 1) hipLaunchKernelGGL(k_reduce_finalize, dim3(deterministic_ ? 48 : 24, nw), dim3(256), 0, stream_, d, mode, parts);
+        else hipLaunchKernelGGL(k_bias_rows, dim3(8, nw), dim3(256), 0, stream_, d, mode);
+      }
+      if (wide_fixed_) launch_assemble_wide(mode);
       ph_end();
       if (mode != LIN_SPEC) {   // (the candidate's gradient norm: k_pass_end)
         ph_begin(PH_ASM_REST);
@@ -806,6 +829,15 @@ class SolverImpl : public SolverBase {
   int imu_general_only() const { return (dbg_.imu_general || opt_.use_mfma == 2) ? 1 : 0; }
   void launch_assemble_vis_lds(int parts, int mode);
   void launch_assemble_vis_glb(int parts, int mode);
+  // The windows beyond the LDS-resident Hessian under deterministic = 2: the expanded block records, one workgroup per 16 x 16 tile of the knot
+  // block + line-delay row + gradient (augmented: 6K + 2 unknowns), the bias rows by gather.
+  void launch_assemble_wide(int mode) {
+    const Dev &d = dev_;
+    const int nt = (6 * maxK_ + 2 + 15) / 16;
+    if (d.Vtot) hipLaunchKernelGGL(k_vis_expand, dim3(nblk((long long)d.Vtot * (VX_COLS + 1), 256)), dim3(256), 0, stream_, d, mode);
+    hipLaunchKernelGGL(k_assemble_wide, dim3(nt * (nt + 1) / 2, d.nwin), dim3(64 * WIDE_NW), 0, stream_, d, mode);
+    hipLaunchKernelGGL(k_bias_rows_wide, dim3(32, d.nwin), dim3(256), 0, stream_, d, mode);
+  }
   void launch_assemble_vis_store(int parts, int mode) {
     const Dev &d = dev_;
     if (deterministic_) hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, true, 1, true>), dim3(d.nwin, parts), dim3(64), vis_lds_, stream_, d, mode);
@@ -873,7 +905,7 @@ class SolverImpl : public SolverBase {
   std::vector<long long> launch_signature() const {
     return {(long long)vis_lds_, (long long)vis_glb_, (long long)any_vis_lds_, (long long)any_vis_glb_, (long long)maxK_, (long long)max_schur_tiles_,
             (long long)chol_lds_, (long long)opt_.use_mfma, (long long)vis_parts(), (long long)deterministic_, (long long)chol_tiles(), (long long)imu_zero_mode(), (long long)merge_linearize(), (long long)dev_.nwin,
-            (long long)dbg_.schur_tile2};
+            (long long)dbg_.schur_tile2, (long long)wide_fixed_};
   }
   int ensure_graph() {
     const std::vector<long long> sig = launch_signature();
@@ -1534,6 +1566,7 @@ class SolverImpl : public SolverBase {
   Dev graph_dev_;
   std::vector<long long> graph_sig_;
   bool deterministic_ = false;   // order-fixed accumulation for this batch (ctvio_options.deterministic)
+  bool wide_fixed_ = false;      // ... and deterministic = 2 with windows beyond the LDS-resident Hessian: k_assemble_wide
   double *state_host_ = nullptr; size_t state_host_cap_ = 0;
   bool snap_valid_ = false, any_vis_lds_ = false, any_vis_glb_ = false, all_windows_have_imu_ = false;
   int maxK_ = 0, max_schur_tiles_ = 0;

@@ -171,6 +171,12 @@ struct Dev {
   long long *dbg;        // optional clock64() stamps (profiling aid), may be null
   int32_t line_search;   // 1: restate Ceres' projected line search (all-fp64 product path)
   LmParams prm;
+  // order-fixed assembly of the windows whose packed Hessian is not LDS resident (k_assemble_wide; deterministic = 2, else null).  The walk
+  // of the upload plan (host_pack.hpp: plan_row_walk): vrow [Vtot], window w's V blocks from vis0 on, as window-relative slots, landmark rows
+  // in sorted order and a landmark's blocks in slot order; vrow_off [Ltot + nwin], window w's L + 1 offsets from lm0 + w on: row r's blocks
+  // are vrow[vis0 + vrow_off[r] .. vis0 + vrow_off[r + 1]).  vexp [Vtot][102]: the expanded block records, in walk order (k_vis_expand).
+  const int32_t *vrow, *vrow_off;
+  double *vexp;
 };
 
 }  // namespace ctv

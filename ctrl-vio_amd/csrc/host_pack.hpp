@@ -376,6 +376,21 @@ inline void plan_sparsity(const ctvio_window *w, bool dense, bool full_ranges, P
   }
 }
 
+// The walk of the order-fixed wide-window assembly (kernels_assemble.hpp: k_assemble_wide), after plan_window and plan_sparsity: the window's
+// blocks as slots (window-relative), landmark rows in sorted order (t.lm_at), a landmark's blocks in slot order -- vrow[V]; row r's blocks are
+// vrow[off[r] .. off[r + 1]), off[L + 1].  A tile walks the rows [tl_beg, tl_end) of both its row and its column tile: a contiguous stretch.
+// Python mirror: packer.row_walk.
+inline void plan_row_walk(const ctvio_window *w, const PackTmp &t, int32_t *vrow, int32_t *off) {
+  const int L = w->L;
+  std::vector<int32_t> next((size_t)L + 1, 0);
+  for (int s = 0; s < t.Vp; ++s)
+    if (t.lord[s] >= 0) next[t.lm_pos[w->v_lm[t.lord[s]]] + 1]++;
+  for (int r = 0; r < L; ++r) next[r + 1] += next[r];
+  for (int r = 0; r <= L; ++r) off[r] = next[r];
+  for (int s = 0; s < t.Vp; ++s)      // (counting sort by row: slot order inside a row)
+    if (t.lord[s] >= 0) vrow[next[t.lm_pos[w->v_lm[t.lord[s]]]]++] = s;
+}
+
 // The most 16-row tiles that take part in one 32-column panel of k_cholesky_solve, by the kernel's own rule (tile R0 + l below panel jb takes
 // part iff env_first[R0 + l] <= jb / 16 + 1): the LDS slots its slot-indexed variant needs to stage every panel of the window without overflow.
 // ef: plan_sparsity's env_first (P / 16 + 1 entries).  Python mirror: packer.chol_panel_slots.

@@ -529,6 +529,195 @@ __global__ __launch_bounds__(256) void k_reduce_finalize(Dev d, int mode, int np
   bias_rows_store(d, m, tg, mode == LIN_SPEC ? d.cbias : d.bias, first, stride);
 }
 
+// ---- order-fixed assembly of the windows whose packed Hessian is not LDS resident (vis_lds = 0; ctvio_options.deterministic = 2).  Every
+// entry of the knot x knot block, the line-delay row and the pose gradient is owned by ONE workgroup (a 16 x 16 tile of the augmented pose
+// block: unknowns 0 .. 6K - 1 the knots, 6K the line delay, 6K + 1 the residual, whose row is the gradient), formed completely and written
+// with a plain store.  Its visual share is the sum over the blocks of the tile's walk, in the order of the upload plan (Dev::vrow: landmark
+// rows in sorted order, a landmark's blocks in slot order), two blocks per v_mfma_f64_16x16x4f64 (K = 2 blocks x 2 residual rows, the
+// operand layout of k_assemble_vis_mfma), the walk's chunks of 64 blocks dealt round-robin to the waves and their sums added in wave order;
+// then the IMU group tiles that touch it, in group order; then the prior; then the store.  The bias rows
+// come from k_bias_rows_wide (bias_rows_store), the prior gradient and the cost share from k_misc (store = 1).  No floating-point atomics.
+//
+// k_vis_expand: the compressed block records of k_vis_eval (Dev::Jt, the anchor records) expanded once per linearisation, in WALK order
+// (entry vis0 + i = the i-th block of the window's walk, Dev::vrow), into the 48 pose columns (vis_col order), the line-delay column and
+// the residual per residual row, and the two ends' first knots: [vis0 + i][2 x VX_COLS + 2].  The tiles visit a block ~15 times; the
+// expansion is one pass, and the tiles' walks read consecutive records with no lookup chain in front of them.
+constexpr int VX_COLS = 50, VX_LD = 2 * VX_COLS + 2;
+__global__ __launch_bounds__(256) void k_vis_expand(Dev d, int mode) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (walk position, column): both residual rows
+  if (e >= (long long)d.Vtot * (VX_COLS + 1)) return;
+  const int pos = (int)(e / (VX_COLS + 1)), c = (int)(e - (long long)pos * (VX_COLS + 1));
+  const int w = d.vb_win[pos / 64];
+  const WinMeta &m = d.wins[w];
+  if (pos - m.vis0 >= m.V) return;   // (the unused tail of the window's range: never walked)
+  if (!lin_run(d.lm[w], mode) || lin_cost_only(d.lm[w], mode, d.prm) || m.vis_lds) return;
+  const int slot = m.vis0 + d.vrow[pos];
+  double *out = d.vexp + (size_t)pos * VX_LD;
+  if (c == VX_COLS) { out[2 * VX_COLS] = (double)d.a_s[d.v_anc[slot]]; out[2 * VX_COLS + 1] = (double)d.vsj[slot]; return; }
+  const double *J = d.Jt + (size_t)slot * VT_ROWS;
+#pragma unroll
+  for (int rr = 0; rr < 2; ++rr) {
+    double v;
+    if (c < 12) {          // anchor end, rotation: A~[rr] . GR[c]
+      const double *gr = d.arec + (size_t)d.v_anc[slot] * AREC + AR_GR + 3 * c;
+      v = J[VB_AT + rr] * gr[0] + J[VB_AT + 2 + rr] * gr[1] + J[VB_AT + 4 + rr] * gr[2];
+    } else if (c < 24) {   // anchor end, position: cp0[k] A~[rr][b]
+      const int k = (c - 12) / 3, b = (c - 12) % 3;
+      v = d.arec[(size_t)d.v_anc[slot] * AREC + AR_CP0 + k] * J[VB_AT + 2 * b + rr];
+    } else if (c < 36) {   // j end, rotation
+      v = J[VB_JROT + 2 * (c - 24) + rr];
+    } else if (c < 48) {   // j end, position: -cp1[k] A~[rr][b]
+      const int k = (c - 36) / 3, b = (c - 36) % 3;
+      v = -(J[VB_CP1 + k] * J[VB_AT + 2 * b + rr]);
+    } else {
+      v = J[(c == 48 ? VB_LD : VB_RES) + rr];
+    }
+    out[VX_COLS * rr + c] = v;
+  }
+}
+// Value of augmented unknown u in residual row rr of an expanded block whose ends start at knots si, sj (ends that share a knot add up).
+__device__ __forceinline__ double vx_value(const double *X, int si, int sj, int u, int K6) {
+  if (u >= K6) return u == K6 ? X[48] : (u == K6 + 1 ? X[49] : 0.0);
+  const int k = u / 6, c = u - 6 * k, ki = k - si, kj = k - sj;
+  double v = 0.0;
+  if (ki >= 0 && ki < 4) v += X[c < 3 ? 3 * ki + c : 9 + 3 * ki + c];
+  if (kj >= 0 && kj < 4) v += X[c < 3 ? 24 + 3 * kj + c : 33 + 3 * kj + c];
+  return v;
+}
+// a block (ends at knots si, sj) reaches augmented columns [t0, t0 + 16)
+__device__ __forceinline__ bool vx_reaches(int si, int sj, int t0, int K6) {
+  return t0 + 15 >= K6 || (6 * si <= t0 + 15 && 6 * si + 23 >= t0) || (6 * sj <= t0 + 15 && 6 * sj + 23 >= t0);
+}
+// the sorted rows of W whose landmark can reach augmented tile T (the line-delay / residual tile: every observed landmark)
+__device__ __forceinline__ void wide_rows(const Dev &d, const WinMeta &m, int T, int &b, int &e) {
+  if (16 * T + 15 < 6 * m.K) { b = d.tl_beg[m.tr0 + T]; e = d.tl_end[m.tr0 + T]; }
+  else { b = 0; e = m.Lobs; }
+}
+// Grid (tiles, windows): one workgroup of WIDE_NW waves per tile, the tiles of the last row (line delay, gradient: every block reaches them)
+// first.  Wave v walks the chunks v, v + WIDE_NW, ... of 64 blocks of the tile's walk; wave 0 adds the other waves' sums in wave order.
+constexpr int WIDE_NW = 4;
+__global__ __launch_bounds__(64 * WIDE_NW) void k_assemble_wide(Dev d, int mode) {
+  const int w = blockIdx.y;
+  if (!lin_run(d.lm[w], mode) || lin_cost_only(d.lm[w], mode, d.prm)) return;
+  const WinMeta &m = d.wins[w];
+  if (m.vis_lds) return;
+  const int K6 = 6 * m.K, na = K6 + 2, nt = (na + 15) / 16, P = m.P, ldh = m.ldh;
+  if ((int)blockIdx.x >= nt * (nt + 1) / 2) return;     // (uniform over the workgroup)
+  const int tile = nt * (nt + 1) / 2 - 1 - (int)blockIdx.x, wave = threadIdx.x >> 6;
+  __shared__ double part[WIDE_NW - 1][4][64];
+  int R = (int)((sqrtf(8.0f * (float)tile + 1.0f) - 1.0f) * 0.5f);
+  R += ((R + 1) * (R + 2) / 2 <= tile) ? 1 : 0;
+  R -= (R * (R + 1) / 2 > tile) ? 1 : 0;
+  const int C = tile - R * (R + 1) / 2, r0 = 16 * R, c0 = 16 * C;
+  const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4, bsel = kq >> 1, rr = kq & 1;
+  const int ua = r0 + l15, ub = c0 + l15;     // the unknowns of this lane's A (tile row) and B (tile column) operand
+  f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+  // ---- visual blocks: the rows of W that can reach both the tile's rows and its columns, their blocks in plan order
+  int bR, eR, bC, eC;
+  wide_rows(d, m, R, bR, eR);
+  wide_rows(d, m, C, bC, eC);
+  const int lo = max(bR, bC), hi = min(eR, eC);
+  if (hi > lo) {
+    const int32_t *off = d.vrow_off + m.lm0 + w;      // (window w's L + 1 offsets start at lm0 + w)
+    const int i0 = m.vis0 + off[lo], i1 = m.vis0 + off[hi];
+    // 64 blocks of the walk per trip: lane q reads the ends of block base + q (the next trip's are requested before this trip's products);
+    // the blocks that reach both ranges at the CURRENT line delay are taken in walk order, up to 2 NPR per round (NPR products with all
+    // their operand loads in flight)
+    constexpr int NPR = 8;
+    auto ends = [&](int base, int &si, int &sj) {
+      const size_t p = (size_t)min(base + lane, max(i1 - 1, 0)) * VX_LD + 2 * VX_COLS;
+      si = (int)d.vexp[p]; sj = (int)d.vexp[p + 1];
+    };
+    int nsi = 0, nsj = 0;
+    if (i0 + 64 * wave < i1) ends(i0 + 64 * wave, nsi, nsj);
+    for (int base = i0 + 64 * wave; base < i1; base += 64 * WIDE_NW) {
+      const int si = nsi, sj = nsj;
+      if (base + 64 * WIDE_NW < i1) ends(base + 64 * WIDE_NW, nsi, nsj);
+      const bool use = base + lane < i1 && vx_reaches(si, sj, r0, K6) && vx_reaches(si, sj, c0, K6);
+      unsigned long long mask = __ballot(use);
+      while (mask) {
+        double av[NPR], bv[NPR];
+#pragma unroll
+        for (int p = 0; p < NPR; ++p) {
+          int b0 = -1, b1 = -1;
+          if (mask) { b0 = __ffsll((long long)mask) - 1; mask &= mask - 1; }
+          if (mask) { b1 = __ffsll((long long)mask) - 1; mask &= mask - 1; }
+          const int s = bsel ? b1 : b0;
+          const int ssi = __shfl(si, max(s, 0)), ssj = __shfl(sj, max(s, 0));
+          const double *X = d.vexp + (size_t)(base + max(s, 0)) * VX_LD + VX_COLS * rr;
+          av[p] = s >= 0 ? vx_value(X, ssi, ssj, ua, K6) : 0.0;
+          bv[p] = s >= 0 ? vx_value(X, ssi, ssj, ub, K6) : 0.0;
+        }
+#pragma unroll
+        for (int p = 0; p < NPR; ++p) acc = mfma16(av[p], bv[p], acc);
+      }
+    }
+  }
+  // D register j of lane l = D[(l / 16) + 4 j][l % 16]: entries (r0 + kq + 4 j, ub)
+  if (wave > 0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[wave - 1][j][lane] = acc[j];
+  }
+  __syncthreads();
+  if (wave > 0) return;
+  double h[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    h[j] = acc[j];
+#pragma unroll
+    for (int v = 0; v < WIDE_NW - 1; ++v) h[j] += part[v][j][lane];
+  }
+  // ---- IMU group tiles (knots s .. s + 3, in group order; the groups are sorted by segment) that touch the tile's rows and columns
+  const bool grad_rows = r0 + 15 >= K6 + 1;
+  for (int base = 0; base < m.ngrp; base += 64) {
+    const int gi = base + lane;
+    int s = 0;
+    bool use = false;
+    if (gi < m.ngrp) {
+      s = d.groups[m.grp0 + gi].s;
+      const bool row_hit = (6 * s <= r0 + 15 && 6 * s + 23 >= r0) || grad_rows, col_hit = 6 * s <= c0 + 15 && 6 * s + 23 >= c0;
+      use = row_hit && col_hit;
+    }
+    unsigned long long mask = __ballot(use);
+    while (mask) {
+      const int q = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const int sg = __shfl(s, q);
+      const double *tl = d.imu_tiles + (size_t)(m.grp0 + base + q) * 1024;
+      const int kb = ub / 6 - sg, cb = ub - 6 * (ub / 6);
+      const int ib = (ub < K6 && kb >= 0 && kb < 4) ? (cb < 3 ? 3 * kb + cb : 9 + 3 * kb + cb) : -1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int ua2 = r0 + kq + 4 * j;
+        if (ib < 0 || ua2 > K6 + 1 || ua2 == K6) continue;
+        if (ua2 == K6 + 1) { h[j] += tl[ib * 32 + 30]; continue; }
+        const int ka = ua2 / 6 - sg, ca = ua2 - 6 * (ua2 / 6);
+        if (ka >= 0 && ka < 4) h[j] += tl[(ca < 3 ? 3 * ka + ca : 9 + 3 * ka + ca) * 32 + ib];
+      }
+    }
+  }
+  // ---- prior, then the store: augmented unknown 6K = the line delay (P - 1), row 6K + 1 = the gradient
+  const int tg = lin_target(d.lm[w], mode);
+  double *Hg = d.HppS[tg] + m.H0, *g = d.gS[tg] + m.u0;
+  const int gb = ub < K6 ? ub : P - 1;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int ua2 = r0 + kq + 4 * j;
+    if (ua2 >= na || ub > ua2 || ub > K6) continue;
+    if (ua2 == K6 + 1) { g[gb] = h[j] + prior_g(d, m, gb); continue; }
+    const int ga = ua2 < K6 ? ua2 : P - 1;
+    Hg[(long long)ga * ldh + gb] = h[j] + prior_H(d, m, ga, gb);
+  }
+}
+// Bias rows of the wide windows (the same gather as k_bias_rows): grid (blocks, windows).
+__global__ __launch_bounds__(256) void k_bias_rows_wide(Dev d, int mode) {
+  const int w = blockIdx.y;
+  if (!lin_run(d.lm[w], mode) || lin_cost_only(d.lm[w], mode, d.prm)) return;
+  const WinMeta &m = d.wins[w];
+  if (m.vis_lds) return;
+  bias_rows_store(d, m, lin_target(d.lm[w], mode), mode == LIN_SPEC ? d.cbias : d.bias, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
 // ------------------------------------------------------------------------------------------------ bias chain + prior
 __device__ __forceinline__ const double *prior_block_ptr(const WinMeta &m, int kind, int idx, const double *quat, const double *pos,
                                                          const double *bias, const double *ldp, int w) {

@@ -175,6 +175,20 @@ def reduced_system_envelope(w, align_panels=True):
     return env
 
 
+def row_walk(lord, v_lm, lm_pos):
+    """Mirror of host_pack.hpp: plan_row_walk -- the walk of the order-fixed wide-window assembly (csrc/kernels_assemble.hpp: k_assemble_wide):
+    the window's block slots grouped by the sorted row of their landmark (lm_pos), slot order inside a row.  lord[slot] = block or -1
+    (padding).  Returns (vrow, off): row r's slots are vrow[off[r]:off[r + 1]]."""
+    lord = np.asarray(lord)
+    L = len(lm_pos)
+    slots = np.nonzero(lord >= 0)[0]
+    rows = np.asarray(lm_pos)[np.asarray(v_lm)[lord[slots]]]
+    order = np.argsort(rows, kind="stable")
+    off = np.zeros(L + 1, np.int64)
+    np.add.at(off, rows + 1, 1)
+    return slots[order].astype(np.int32), np.cumsum(off).astype(np.int32)
+
+
 def chol_panel_slots(P, env):
     """Mirror of host_pack.hpp: chol_panel_slots -- the most 16-row tiles that take part in one 32-column panel of the panel Cholesky (tile
     R0 + l below panel jb takes part iff env[R0 + l] <= jb // 16 + 1): the LDS slots its slot-indexed variant needs to stage every panel."""

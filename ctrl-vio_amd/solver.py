@@ -21,7 +21,9 @@ class Solver:
                  deterministic: int = -1, host_threads: int = 0, use_graph: bool = True, line_search: bool = True,
                  **tolerances):
         """All-fp64, like the reference (`precision` is kept for call compatibility: only "fp64" exists).  deterministic: 1 = order-fixed
-        accumulation (bitwise reproducible), 0 = off, -1 = on for batches of <= 64 windows."""
+        accumulation (bitwise reproducible) for batches whose every window has K <= 25 (others are refused), 2 = order-fixed accumulation
+        for every batch the solver accepts (windows up to P = 1024; the K <= 25 windows run exactly as under 1), 0 = off, -1 = on for batches
+        of <= 64 windows where 1 applies."""
         if precision not in ("fp64", capi.FP64):
             raise ValueError("only precision='fp64' exists (the mixed fp32 mode was removed: it missed the 1e-4 contract)")
         self._lib = capi.load_library()

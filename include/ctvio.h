@@ -71,7 +71,11 @@ typedef struct ctvio_options {
                                    It exists for batches whose every window has K <= 25 (packed Hessian in LDS):
                                    ctvio_upload / ctvio_set_batch return CTVIO_ERR_INVALID for any other batch
                                    instead of silently accumulating with atomics.  -1 (default): on for batches of <= 64 windows
-                                   where it applies, the atomic path (run-to-run differences ~1e-13 in the state) otherwise; 0: off */
+                                   where it applies, the atomic path (run-to-run differences ~1e-13 in the state) otherwise; 0: off.
+                                   2: order-fixed accumulation for EVERY batch the solver accepts (windows up to P = 1024, mixed
+                                   batches, IMU-only long splines): the windows with K <= 25 run exactly as under 1 (same bits),
+                                   the others assemble their pose block with one owner per entry and a summation order fixed by
+                                   the upload plan.  Two runs of the same batch are bitwise equal. */
   int32_t host_threads;         /* host threads that validate / pack a batch (ctvio_set_batch, ctvio_upload); 0 = min(cores, 16) */
   int32_t use_graph;            /* 1 (default): the launch sequence of one LM pass is captured into a hipGraph and replayed */
   int32_t line_search;          /* 1 (default): Ceres' projected Armijo line search of bounds-constrained problems
