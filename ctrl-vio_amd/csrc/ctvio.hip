@@ -47,14 +47,7 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 // change of the environment cannot make upload and solve disagree about a kernel choice.  None of them is needed in production.
 struct DebugSwitches {
   int stamps = 0;            // CTVIO_DEBUG_STAMPS=1     clock64 stamps of a few kernels, printed by ctvio_solve (disables the hipGraph)
-  int store_path = -1;       // CTVIO_STORE_PATH=0/1     force the store-semantics assembly tail off / on
   int split_linearize = 0;   // CTVIO_SPLIT_LINEARIZE=1  IMU and visual evaluation as separate launches also for small batches (rocprofv3 runs)
-  int merge_linearize = -1;  // CTVIO_MERGE_LINEARIZE=0/1 force the merged launch off / on
-  int no_imu_band = 0;       // CTVIO_NO_IMU_BAND=1      k_misc adds the IMU knot blocks to Hpp without the LDS band
-  int zero_kernel = 0;       // CTVIO_ZERO_KERNEL=1      k_zero_normal instead of the IMU kernel's zeroing share
-  int imu_waves = 2048;      // CTVIO_IMU_WAVES=n        walking waves of k_imu_linearize_f64
-  int imu_general = 0;       // CTVIO_IMU_GENERAL=1      every IMU group through the general body (same as use_mfma = 2)
-  int schur_tiles = 0;       // CTVIO_SCHUR_TILES=1      tile Schur kernels also for large batches of small windows
   int schur_copy_plain = 0;  // CTVIO_SCHUR_COPY_PLAIN=1 the per-window Schur kernel copies product-free tiles to S
   int chol_tiles = -1;       // CTVIO_CHOL_TILES=0/1/3   P <= 223: panel kernel / k_cholesky_tiles (round 5: barriers) / k_cholesky_flow (default)
   int chol_compact = 0;      // CTVIO_CHOL_COMPACT=1/n   TEST ONLY: the panel kernel's slot-indexed variant for every batch it would run (1: as many
@@ -66,20 +59,17 @@ struct DebugSwitches {
   int marg_blocked = 0;      // CTVIO_MARG_BLOCKED=1     ctvio_marginalize_batch: every window through the blocked path (csrc/marg_blocked.hpp)
   int shard_oversubscribe = 0;   // CTVIO_SHARD_OVERSUBSCRIBE=1  TEST ONLY: more shards than devices (ctvio_shards_used)
   int poison = 0;            // CTVIO_POISON=1/2         TEST ONLY: reused double scratch starts as quiet NaN / 2.6e151 at every use; the
-                             //                          upload checks that the packer writes every staged byte (SolverImpl::poison)
+                             //                          upload checks that the packer writes every staged byte (host_pack.hpp: check_staging)
 };
 static DebugSwitches read_debug_switches() {
   DebugSwitches g;
   struct { const char *name; int *dst; } const tab[] = {
-      {"CTVIO_DEBUG_STAMPS", &g.stamps}, {"CTVIO_STORE_PATH", &g.store_path}, {"CTVIO_SPLIT_LINEARIZE", &g.split_linearize},
-      {"CTVIO_MERGE_LINEARIZE", &g.merge_linearize}, {"CTVIO_NO_IMU_BAND", &g.no_imu_band}, {"CTVIO_ZERO_KERNEL", &g.zero_kernel},
-      {"CTVIO_IMU_WAVES", &g.imu_waves}, {"CTVIO_IMU_GENERAL", &g.imu_general}, {"CTVIO_SCHUR_TILES", &g.schur_tiles},
+      {"CTVIO_DEBUG_STAMPS", &g.stamps}, {"CTVIO_SPLIT_LINEARIZE", &g.split_linearize},
       {"CTVIO_SCHUR_COPY_PLAIN", &g.schur_copy_plain}, {"CTVIO_CHOL_TILES", &g.chol_tiles}, {"CTVIO_CHOL_COMPACT", &g.chol_compact}, {"CTVIO_DENSE", &g.dense},
       {"CTVIO_SCHUR_TILE2", &g.schur_tile2}, {"CTVIO_MARG_DEBUG", &g.marg_debug}, {"CTVIO_MARG_HOST", &g.marg_host},
       {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}, {"CTVIO_POISON", &g.poison}};
   for (const auto &t : tab)
     if (const char *e = std::getenv(t.name)) *t.dst = (e[0] == '\0') ? 1 : std::atoi(e);   // (set but empty counts as 1)
-  g.imu_waves = std::max(1, g.imu_waves);
   return g;
 }
 
@@ -99,12 +89,6 @@ template <class U> struct DBuf {
     if (e != hipSuccess || h.empty()) return e;
     return hipMemcpyAsync(p, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice, st);
   }
-};
-
-// One segment of an arena layout: name, byte offset, the bytes a batch fills (CTVIO_POISON checks and poisons these extents).
-struct ArenaSeg {
-  const char *name;
-  size_t off, bytes;
 };
 
 // Owning host copy of one window (ctvio_add_window: the caller's buffers are only read inside that call).
@@ -137,45 +121,14 @@ struct HostWindow {
   HostWindow &operator=(const HostWindow &) = delete;
 };
 
-struct SolverBase {
-  virtual ~SolverBase() {}
-  virtual int clear() = 0;
-  virtual int add_window(const ctvio_window *w, int32_t *id) = 0;
-  virtual int upload() = 0;
-  virtual int set_batch(int n, const ctvio_window *wins) = 0;
-  virtual int num_windows() const = 0;
-  virtual int solve(int max_iters, ctvio_summary *out) = 0;
-  virtual int get_state(int id, double *quat, double *pos, double *bias, double *rho, double *ld) = 0;
-  virtual int get_batch_state(double *quat, double *pos, double *bias, double *rho, double *ld) = 0;
-  virtual int set_state(int id, const double *quat, const double *pos, const double *bias, const double *rho, double ld) = 0;
-  virtual int linearize(int id, double *Hpp, double *W, double *Hll, double *g, double *cost) = 0;
-  virtual int cost(int id, double *cost) = 0;
-  virtual int lm_step(int id, double mu, double *delta, double *mc) = 0;
-  virtual int spline_eval(int id, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
-                          const double *q_SI = nullptr, const double *p_SI = nullptr) = 0;
-  virtual int spline_eval_batch(int64_t n, const int32_t *win, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
-                                double *kernel_ms) = 0;
-  virtual int gauge_restore(int n, const int32_t *ids, const int32_t *knot, const double *q0, const double *t0) = 0;
-  virtual int marginalize(int id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) = 0;
-  virtual int marginalize_batch(const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) = 0;
-  virtual int residual_summary(int id, double *sums, int32_t *counts4) = 0;
-  virtual int bind() = 0;   // make the solver's device current on the calling thread (every ABI entry: callers use threads)
-  virtual int snapshot(int restore) = 0;
-  virtual int last_timing(double *ms8, int32_t *n8) = 0;
-  virtual int set_profiling(int on) = 0;
-  virtual void *stream() = 0;
-  virtual int graph_captures() const = 0;
-  virtual int marg_ran_on_host() const = 0;
-};
-
-class SolverImpl : public SolverBase {
+class SolverImpl {
  public:
   // visual blocks per work item (k_assemble_vis_mfma): eight per-wave staging areas must fit beside the fp64 LDS Hessian -- sized by the
   // constexpr the kernel itself lays its LDS out with (kernels_assemble.hpp: vis_stage_bytes)
   static constexpr int VCH = 8;
   static constexpr size_t vis_stage_bytes() { return ctv::vis_stage_bytes(8, VCH); }
   explicit SolverImpl(const ctvio_options &o) : opt_(o), dbg_(read_debug_switches()) {}
-  ~SolverImpl() override {
+  ~SolverImpl() {
     if (stream_) (void)hipStreamDestroy(stream_);
     for (auto &e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto &e : pev_) (void)hipEventDestroy(e);
@@ -197,7 +150,6 @@ class SolverImpl : public SolverBase {
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_flow, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, true, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<7, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -205,14 +157,14 @@ class SolverImpl : public SolverBase {
     HIPCHK(hipFuncSetAttribute((const void *)k_misc, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));   // (+ 2 KB of static LDS)
     return CTVIO_OK;
   }
-  int bind() override { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
-  int clear() override { own_.clear(); uploaded_ = false; return CTVIO_OK; }
-  int num_windows() const override { return uploaded_ ? (int)meta_.size() : (int)own_.size(); }
-  void *stream() override { return (void *)stream_; }
-  int graph_captures() const override { return graph_captures_; }
-  int marg_ran_on_host() const override { return marg_ran_on_host_; }
+  int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
+  int clear() { own_.clear(); uploaded_ = false; return CTVIO_OK; }
+  int num_windows() const { return uploaded_ ? (int)meta_.size() : (int)own_.size(); }
+  void *stream() { return (void *)stream_; }
+  int graph_captures() const { return graph_captures_; }
+  int marg_ran_on_host() const { return marg_ran_on_host_; }
 
-  int add_window(const ctvio_window *w, int32_t *id) override {
+  int add_window(const ctvio_window *w, int32_t *id) {
     std::string err;
     if (!validate_window(w, err)) return fail(CTVIO_ERR_INVALID, err);
     own_.emplace_back(new HostWindow(*w));
@@ -220,14 +172,14 @@ class SolverImpl : public SolverBase {
     uploaded_ = false;
     return CTVIO_OK;
   }
-  int upload() override {
+  int upload() {
     if (own_.empty()) return fail(CTVIO_ERR_STATE, "no windows");
     std::vector<const ctvio_window *> ptr(own_.size());
     for (size_t i = 0; i < own_.size(); ++i) ptr[i] = &own_[i]->w;
     return pack_and_upload(ptr, false);
   }
   // ctvio_set_batch: the windows are read straight from the caller's buffers (no intermediate copy)
-  int set_batch(int n, const ctvio_window *wins) override {
+  int set_batch(int n, const ctvio_window *wins) {
     if (n <= 0 || !wins) return fail(CTVIO_ERR_INVALID, "empty batch");
     own_.clear();
     uploaded_ = false;
@@ -240,7 +192,7 @@ class SolverImpl : public SolverBase {
   // Two passes over the windows, both spread over host threads: (1) validate, sort, count; (2) fill the pinned staging
   // arena, which mirrors the device input arena byte for byte -- one hipMemcpyAsync carries the batch to HBM.  Work
   // buffers live in a second, device-only arena.  Both arenas only ever grow, so a stream of equally sized batches
-  // allocates nothing after the first one.
+  // allocates nothing after the first one.  The host-only steps (plan, offsets, layout, fill) are csrc/host_pack.hpp's.
   int pack_and_upload(const std::vector<const ctvio_window *> &wins, bool validate) {
     const int nw = (int)wins.size();
     const int nth = host_threads(opt_.host_threads);
@@ -252,8 +204,9 @@ class SolverImpl : public SolverBase {
     for (int wi = 0; wi < nw; ++wi) if (wins[wi]) maxP_pre = std::max(maxP_pre, 6 * wins[wi]->K + 6 * wins[wi]->F + 1);
     if (maxP_pre > CHOL_MAX_P)
       return fail(CTVIO_ERR_INVALID, "window too large for the single-workgroup Cholesky (P = 6K + 6F + 1 > " + std::to_string(CHOL_MAX_P) + ")");
-    chol_tiles_ = chol_tiles_for(maxP_pre);   // (decided here, once per batch: launch_step and the Schur launch use the member)
-    const bool dense_env = chol_tiles_ != 0 || sparsity_off();
+    const int chol_tiles = chol_tiles_for(maxP_pre);
+    const bool dense_env = chol_tiles != 0 || sparsity_off();
+    // ---- plan (threads)
     pool_.run(nw, nth, [&](int wi) {
       if (validate && !validate_window(wins[wi], tmp[wi].err)) {
         int cur = first_bad.load();
@@ -268,409 +221,250 @@ class SolverImpl : public SolverBase {
       }
     });
     if (first_bad.load() < nw) return fail(CTVIO_ERR_INVALID, "window " + std::to_string(first_bad.load()) + ": " + tmp[first_bad.load()].err);
-    // ---- offsets (serial prefix sums)
-    meta_.assign(nw, WinMeta());
-    t0_.resize(nw);
-    int64_t H0 = 0, W0 = 0, pH0 = 0;
-    int K0 = 0, F0 = 0, L0 = 0, M0 = 0, V0 = 0, B0 = 0, U0 = 0, Pp0 = 0, pv0 = 0, pb = 0, G0 = 0, I0 = 0, A0 = 0, TR0 = 0, maxSpan = 1;
-    int maxN = 0, maxP = 0, maxPn = 0, maxL = 0, maxLdw = 0, maxK = 0, maxSchurTiles = 0, maxSlots = 0, maxK_lds = 0;
-    bool any_wide = false;
-    const bool slots_needed = chol_tiles_ == 0 && (chol_panel_lds(maxP_pre) > 160 * 1024 || dbg_.chol_compact > 0);   // (the variant's choice below)
-    size_t vis_lds_bytes = vis_stage_bytes(), vis_glb_bytes = vis_stage_bytes();
-    for (int wi = 0; wi < nw; ++wi) {
-      const ctvio_window &w = *wins[wi];
-      WinMeta &m = meta_[wi];
-      t0_[wi] = w.t0_ns;
-      m.K = w.K; m.F = w.F; m.L = w.L; m.M = w.M; m.NB = w.NB; m.V = w.V;
-      m.P = 6 * w.K + 6 * w.F + 1; m.N = m.P + w.L; m.pn = w.pn; m.pnb = w.pnb;
-      m.knot0 = K0; m.bias0 = F0; m.lm0 = L0; m.imu0 = M0; m.vis0 = V0; m.bc0 = B0; m.u0 = U0; m.p0 = Pp0;
-      m.grp0 = G0; m.ngrp = tmp[wi].ngrp; m.vitem0 = I0; m.nvitem = tmp[wi].nvitem; m.Vp = tmp[wi].Vp;
-      m.anc0 = A0; m.A = tmp[wi].A;
-      m.tr0 = TR0; m.ntr = tmp[wi].ntr; m.Lobs = tmp[wi].Lobs; TR0 += tmp[wi].ntr; maxSpan = std::max(maxSpan, tmp[wi].max_span);
-      m.ldw = (m.P + 1 + 31) / 32 * 32; m.Lpad = std::max(2, (w.L + 1) / 2 * 2);
-      m.pv0 = pv0; m.pblk0 = pb; m.fix_ld = w.fix_ld; m.lock_bg = w.lock_bg; m.lock_ba = w.lock_ba; m.fixed_upto = w.fixed_upto;
-      m.H0 = H0; m.W0 = W0; m.pH0 = pH0; m.ldh = (m.P + 15) / 16 * 16; m.dt_ns = w.dt_ns; m.inv_dt = 1e9 / (double)w.dt_ns;
-      for (int i = 0; i < 4; ++i) m.q_CI[i] = w.q_CI[i];
-      for (int i = 0; i < 3; ++i) { m.p_CI[i] = w.p_CI[i]; m.gravity[i] = w.gravity[i]; }
-      for (int i = 0; i < 6; ++i) m.imu_w[i] = w.imu_w[i];
-      m.img_w = w.img_w; m.cauchy_a = w.cauchy_a; m.ld_lo = w.ld_lo; m.ld_hi = w.ld_hi;
-      {
-        const size_t K6 = 6 * (size_t)w.K, nG = K6 + 1, nH = K6 * (K6 + 1) / 2 + K6 + 1 + nG;
-        const size_t need = ((nH + 3) & ~(size_t)3) * sizeof(double) + 32 + vis_stage_bytes();   // fp64 accumulators in LDS
-        const size_t need_glb = ((nG + 3) & ~(size_t)3) * sizeof(double) + 16 + vis_stage_bytes();
-        m.vis_lds = need <= 160 * 1024 ? 1 : 0;
-        if (m.vis_lds) maxK_lds = std::max(maxK_lds, w.K); else any_wide = true;
-        vis_lds_bytes = std::max(vis_lds_bytes, m.vis_lds ? need : need_glb);
-        vis_glb_bytes = std::max(vis_glb_bytes, need_glb);
-      }
-      K0 += w.K; F0 += w.F; L0 += w.L; M0 += w.M; V0 += m.Vp; B0 += w.NB; U0 += m.N; Pp0 += m.P; pv0 += w.pn; pb += w.pnb;
-      G0 += m.ngrp; I0 += m.nvitem; A0 += m.A;
-      H0 += (int64_t)m.P * m.ldh; W0 += (int64_t)m.Lpad * m.ldw; pH0 += (int64_t)w.pn * w.pn;
-      maxN = std::max(maxN, m.N); maxP = std::max(maxP, m.P); maxPn = std::max(maxPn, w.pn);
-      maxL = std::max(maxL, m.L); maxLdw = std::max(maxLdw, m.ldw); maxK = std::max(maxK, m.K);
-      if (slots_needed) maxSlots = std::max(maxSlots, chol_panel_slots(tmp[wi].env_first.data(), m.P));
-      {   // 16 x 16 tiles of the reduced system that receive Schur products (k_schur_window_f64): knot columns, line delay, rhs row
-        const int ntl = m.ldw / 16, K6 = 6 * m.K;
-        int cnt = 0;
-        for (int ti = 0; ti < ntl; ++ti)
-          for (int tj = 0; tj <= ti; ++tj) {
-            const bool nzr = (16 * ti < K6) || (m.P >= 16 * ti && m.P - 1 < 16 * ti + 16);
-            const bool nzc = (16 * tj < K6) || (m.P - 1 >= 16 * tj && m.P - 1 < 16 * tj + 16);
-            cnt += (nzr && nzc) ? 1 : 0;
-          }
-        maxSchurTiles = std::max(maxSchurTiles, cnt);
-      }
-    }
+    // ---- lay out: offsets (serial prefix sums), then the input arena (host mirror + device)
     // The panel kernel's LDS: a fixed part and the panel, 32 columns x the full trailing height (P <= 591 fits 160 KB).  Batches beyond that
     // (or CTVIO_CHOL_COMPACT) take the slot-indexed variant: 32 x 16 doubles per slot, as many slots as the batch's panels need or fit; the
     // back-substitution reuses the panel as xs[P].
-    size_t chol_lds = chol_panel_lds(maxP);
-    chol_compact_ = slots_needed;
+    const bool chol_compact = chol_tiles == 0 && (chol_panel_lds(maxP_pre) > 160 * 1024 || dbg_.chol_compact > 0);
+    BatchFacts &b = facts_;
+    b = batch_offsets(wins, tmp, chol_compact, vis_stage_bytes(), opt_.deterministic == 2, meta_, t0_);
+    b.chol_tiles = chol_tiles; b.chol_compact = chol_compact; b.chol_lds = chol_panel_lds(b.maxP);
     int chol_slots = 0;
-    if (chol_compact_) {
+    if (chol_compact) {
       const int fit = (int)((160 * 1024 / sizeof(double) - chol_lds_fixed) / (32 * 16));
-      chol_slots = std::min(maxSlots, fit);
+      chol_slots = std::min(b.maxSlots, fit);
       if (dbg_.chol_compact >= 2) chol_slots = std::min(chol_slots, dbg_.chol_compact);
       chol_slots = std::max(chol_slots, 2);   // (local tiles 0 and 1, the next diagonal block, take part in every panel)
-      chol_lds = (chol_lds_fixed + std::max((size_t)32 * 16 * chol_slots, (size_t)maxP)) * sizeof(double);
+      b.chol_lds = (chol_lds_fixed + std::max((size_t)32 * 16 * chol_slots, (size_t)b.maxP)) * sizeof(double);
     }
-    const size_t Mt = (size_t)std::max(M0, 1), Vt = (size_t)std::max(V0, 1), At = (size_t)std::max(A0, 1);
-    Mtot_ = M0; Vtot_ = V0;
-    // ---- input arena layout (host mirror + device)
-    size_t off = 0;
-    std::vector<ArenaSeg> segs;   // (CTVIO_POISON: the extents of the segments, named, without their alignment tails)
-    auto seg = [&](const char *name, size_t bytes, size_t used = SIZE_MAX) {   // used: the bytes the batch fills (an empty set keeps one entry)
-      const size_t o = off;
-      off += (bytes + 255) & ~(size_t)255;
-      if (dbg_.poison) segs.push_back(ArenaSeg{name, o, std::min(bytes, used)});
-      return o;
-    };
-    const size_t o_meta = seg("meta", sizeof(WinMeta) * nw);
-    const size_t o_state = seg("state", sizeof(double) * ((size_t)7 * K0 + 6 * F0 + L0 + nw));   // quat | pos | bias | rho | ld, contiguous
-    const size_t o_knot_win = seg("knot_win", 4 * (size_t)K0), o_bias_win = seg("bias_win", 4 * (size_t)F0), o_lm_win = seg("lm_win", 4 * (size_t)L0);
-    const size_t o_groups = seg("groups", sizeof(ImuGroup) * (size_t)G0), o_imu_grp = seg("imu_grp", 4 * Mt, 4 * (size_t)M0);
-    const size_t o_imu_u = seg("imu_u", sizeof(double) * Mt, sizeof(double) * (size_t)M0), o_imu_meas = seg("imu_meas", sizeof(double) * 6 * Mt, sizeof(double) * 6 * (size_t)M0);
-    const size_t o_v_win = seg("v_win", 4 * Vt, 4 * (size_t)V0), o_v_lm = seg("v_lm", 4 * Vt, 4 * (size_t)V0), o_v_anc = seg("v_anc", 4 * Vt, 4 * (size_t)V0), o_v_rowj = seg("v_rowj", 4 * Vt, 4 * (size_t)V0);
-    const size_t o_v_tj = seg("v_tj", 8 * Vt, 8 * (size_t)V0), o_v_obs = seg("v_obs", sizeof(double) * 2 * Vt, sizeof(double) * 2 * (size_t)V0);
-    const size_t o_v_cauchy = seg("v_cauchy", 8 * Vt, 8 * (size_t)V0), o_vb_win = seg("vb_win", 4 * (Vt / 64 + 1), 4 * ((size_t)V0 / 64));
-    const size_t o_a_win = seg("a_win", 4 * At, 4 * (size_t)A0), o_a_lm = seg("a_lm", 4 * At, 4 * (size_t)A0), o_a_row = seg("a_row", 4 * At, 4 * (size_t)A0), o_a_t = seg("a_t", 8 * At, 8 * (size_t)A0), o_a_obs = seg("a_obs", 8 * 2 * At, 8 * 2 * (size_t)A0);
-    const size_t o_vitems = seg("vitems", sizeof(VisItem) * (size_t)std::max(I0, 1), sizeof(VisItem) * (size_t)I0), o_vblk = seg("vblk", 4 * Vt, 4 * (size_t)V0), o_vblk_anc = seg("vblk_anc", 4 * Vt, 4 * (size_t)V0);
-    const size_t o_bc_win = seg("bc_win", 4 * (size_t)B0), o_bc_i = seg("bc_i", 4 * (size_t)B0), o_bc_j = seg("bc_j", 4 * (size_t)B0), o_bc_w = seg("bc_w", 8 * 6 * (size_t)B0);
-    const size_t o_pJ0 = seg("pJ0", 8 * (size_t)pH0), o_pr0 = seg("pr0", 8 * (size_t)pv0);
-    const size_t o_pH = seg("pH", 8 * (size_t)pH0), o_pb0 = seg("pb0", 8 * (size_t)pv0), o_pc0 = seg("pc0", 8 * (size_t)nw), o_p_x0 = seg("p_x0", 8 * 4 * (size_t)pb);
-    const size_t o_pcol = seg("pcol", 4 * (size_t)pv0), o_p_kind = seg("p_kind", 4 * (size_t)pb), o_p_index = seg("p_index", 4 * (size_t)pb), o_p_off = seg("p_off", 4 * (size_t)pb);
-    const size_t o_pinv = seg("pinv", 4 * (size_t)Pp0), o_bgl_off = seg("bgl_off", 4 * ((size_t)F0 + nw)), o_bgl = seg("bgl", 4 * (size_t)std::max(G0, 1), 4 * (size_t)G0);
-    const size_t o_active = seg("active", (size_t)U0);
-    const size_t o_lm_pos = seg("lm_pos", 4 * (size_t)L0), o_lm_at = seg("lm_at", 4 * (size_t)L0), o_lm_klo = seg("lm_klo", 4 * (size_t)L0), o_lm_khi = seg("lm_khi", 4 * (size_t)L0);
-    const size_t o_tl_beg = seg("tl_beg", 4 * (size_t)TR0), o_tl_end = seg("tl_end", 4 * (size_t)TR0), o_env_first = seg("env_first", 4 * (size_t)TR0), o_env_tile = seg("env_tile", 4 * (size_t)TR0);
-    // the walk of the order-fixed wide-window assembly (deterministic = 2 with a window beyond the LDS-resident Hessian; else not uploaded)
-    const bool walk = opt_.deterministic == 2 && any_wide;
-    const size_t o_vrow = seg("vrow", walk ? 4 * Vt : 4, walk ? 4 * (size_t)V0 : 0), o_vrow_off = seg("vrow_off", walk ? 4 * ((size_t)L0 + nw) : 4, walk ? 4 * ((size_t)L0 + nw) : 0);
-    const size_t in_bytes = off;
-    bool grew = false;
+    const InputLayout lay = layout_input(b);
+    // ---- reserve
     HIPCHK(hipStreamSynchronize(stream_));   // the previous batch may still be reading the staging arena (H2D in flight)
-    HIPCHK(in_.reserve(in_bytes, true, &grew));
-    char *hb = in_.host, *db = in_.dev;
-#define CTV_H(type, o) reinterpret_cast<type *>(hb + (o))
-#define CTV_D(type, o) reinterpret_cast<type *>(db + (o))
-    double *h_quat = CTV_H(double, o_state), *h_pos = h_quat + (size_t)4 * K0, *h_bias = h_pos + (size_t)3 * K0, *h_rho = h_bias + (size_t)6 * F0,
-           *h_ld = h_rho + L0;
-    int32_t *h_knot_win = CTV_H(int32_t, o_knot_win), *h_bias_win = CTV_H(int32_t, o_bias_win), *h_lm_win = CTV_H(int32_t, o_lm_win);
-    ImuGroup *h_groups = CTV_H(ImuGroup, o_groups);
-    int32_t *h_imu_grp = CTV_H(int32_t, o_imu_grp);
-    double *h_imu_u = CTV_H(double, o_imu_u), *h_imu_meas = CTV_H(double, o_imu_meas), *h_v_obs = CTV_H(double, o_v_obs);
-    double *h_v_cauchy = CTV_H(double, o_v_cauchy);
-    int32_t *h_vb_win = CTV_H(int32_t, o_vb_win);
-    int32_t *h_v_win = CTV_H(int32_t, o_v_win), *h_v_lm = CTV_H(int32_t, o_v_lm), *h_v_anc = CTV_H(int32_t, o_v_anc), *h_v_rowj = CTV_H(int32_t, o_v_rowj);
-    int64_t *h_v_tj = CTV_H(int64_t, o_v_tj);
-    int32_t *h_a_win = CTV_H(int32_t, o_a_win), *h_a_lm = CTV_H(int32_t, o_a_lm), *h_a_row = CTV_H(int32_t, o_a_row);
-    int64_t *h_a_t = CTV_H(int64_t, o_a_t);
-    double *h_a_obs = CTV_H(double, o_a_obs);
-    VisItem *h_vitems = CTV_H(VisItem, o_vitems);
-    int32_t *h_vblk = CTV_H(int32_t, o_vblk), *h_vblk_anc = CTV_H(int32_t, o_vblk_anc);
-    int32_t *h_bc_win = CTV_H(int32_t, o_bc_win), *h_bc_i = CTV_H(int32_t, o_bc_i), *h_bc_j = CTV_H(int32_t, o_bc_j);
-    double *h_pJ0 = CTV_H(double, o_pJ0), *h_pr0 = CTV_H(double, o_pr0);
-    double *h_bc_w = CTV_H(double, o_bc_w), *h_pH = CTV_H(double, o_pH), *h_pb0 = CTV_H(double, o_pb0), *h_pc0 = CTV_H(double, o_pc0),
-           *h_p_x0 = CTV_H(double, o_p_x0);
-    int32_t *h_pcol = CTV_H(int32_t, o_pcol), *h_p_kind = CTV_H(int32_t, o_p_kind), *h_p_index = CTV_H(int32_t, o_p_index), *h_p_off = CTV_H(int32_t, o_p_off);
-    uint8_t *h_active = CTV_H(uint8_t, o_active);
-    int32_t *h_pinv = CTV_H(int32_t, o_pinv), *h_bgl_off = CTV_H(int32_t, o_bgl_off), *h_bgl = CTV_H(int32_t, o_bgl);
-    int32_t *h_lm_pos = CTV_H(int32_t, o_lm_pos), *h_lm_at = CTV_H(int32_t, o_lm_at), *h_lm_klo = CTV_H(int32_t, o_lm_klo), *h_lm_khi = CTV_H(int32_t, o_lm_khi);
-    int32_t *h_tl_beg = CTV_H(int32_t, o_tl_beg), *h_tl_end = CTV_H(int32_t, o_tl_end), *h_env_first = CTV_H(int32_t, o_env_first), *h_env_tile = CTV_H(int32_t, o_env_tile);
-    int32_t *h_vrow = CTV_H(int32_t, o_vrow), *h_vrow_off = CTV_H(int32_t, o_vrow_off);
-    h_lm_pos_ = h_lm_pos; h_ld_ = h_ld;
-    // ---- second pass: every window fills its own slices
-    auto fill_window = [&](int wi) {
-      const ctvio_window &w = *wins[wi];
-      const WinMeta &m = meta_[wi];
-      const PackTmp &t = tmp[wi];
-      std::memcpy(h_quat + (size_t)4 * m.knot0, w.quat, sizeof(double) * 4 * w.K);
-      std::memcpy(h_pos + (size_t)3 * m.knot0, w.pos, sizeof(double) * 3 * w.K);
-      std::memcpy(h_bias + (size_t)6 * m.bias0, w.bias, sizeof(double) * 6 * w.F);
-      if (w.L) std::memcpy(h_rho + m.lm0, w.rho, sizeof(double) * w.L);
-      h_ld[wi] = w.fix_ld ? w.ld : std::min(std::max(w.ld, w.ld_lo), w.ld_hi);   // Ceres IterationZero: project on the feasible set
-      std::fill(h_knot_win + m.knot0, h_knot_win + m.knot0 + w.K, wi);
-      std::fill(h_bias_win + m.bias0, h_bias_win + m.bias0 + w.F, wi);
-      std::fill(h_lm_win + m.lm0, h_lm_win + m.lm0 + w.L, wi);
-      if (w.L) {   // sparsity plan: rows of W in sorted landmark order and their knot spans
-        std::memcpy(h_lm_pos + m.lm0, t.lm_pos.data(), 4 * (size_t)w.L); std::memcpy(h_lm_at + m.lm0, t.lm_at.data(), 4 * (size_t)w.L);
-        std::memcpy(h_lm_klo + m.lm0, t.row_klo.data(), 4 * (size_t)w.L); std::memcpy(h_lm_khi + m.lm0, t.row_khi.data(), 4 * (size_t)w.L);
-      }
-      std::memcpy(h_tl_beg + m.tr0, t.tl_beg.data(), 4 * (size_t)m.ntr); std::memcpy(h_tl_end + m.tr0, t.tl_end.data(), 4 * (size_t)m.ntr);
-      std::memcpy(h_env_first + m.tr0, t.env_first.data(), 4 * (size_t)m.ntr); std::memcpy(h_env_tile + m.tr0, t.env_tile.data(), 4 * (size_t)m.ntr);
-      if (walk) {
-        plan_row_walk(&w, t, h_vrow + m.vis0, h_vrow_off + m.lm0 + wi);
-        std::fill(h_vrow + m.vis0 + w.V, h_vrow + m.vis0 + m.Vp, 0);   // (unused tail of the window's list)
-      }
-      // IMU samples in (segment, bias) order; groups = runs of equal (segment, bias)
-      int g = m.grp0 - 1;
-      for (int i = 0; i < w.M; ++i) {
-        const int src = t.iorder[i];
-        if (i == 0 || t.iseg[src] != t.iseg[t.iorder[i - 1]] || w.imu_bias[src] != w.imu_bias[t.iorder[i - 1]])
-          h_groups[++g] = ImuGroup{wi, t.iseg[src], w.imu_bias[src], i, 0, m.knot0 + t.iseg[src], m.bias0 + w.imu_bias[src], m.imu0 + i};
-        h_groups[g].count++;
-        const size_t e = (size_t)m.imu0 + i;
-        h_imu_grp[e] = g;
-        const int64_t st = w.imu_t[src] - w.t0_ns;
-        const double uu = (double)(st % w.dt_ns) / (double)w.dt_ns;
-        h_imu_u[e] = (double)uu;
-        for (int c = 0; c < 3; ++c) {
-          h_imu_meas[(size_t)c * Mt + e] = (double)w.imu_gyro[3 * src + c];
-          h_imu_meas[(size_t)(3 + c) * Mt + e] = (double)w.imu_acc[3 * src + c];
-        }
-      }
-      // anchors (the i ends, landmark-major) and visual blocks: evaluation slots in landmark-major order (padding slots: window -1,
-      // harmless values)
-      for (int a = 0; a < m.A; ++a) {
-        const int v = t.anc_rep[a];
-        const size_t e = (size_t)m.anc0 + a;
-        h_a_win[e] = wi; h_a_lm[e] = w.v_lm[v]; h_a_row[e] = w.v_rowi[v]; h_a_t[e] = w.v_ti[v] - w.t0_ns;
-        h_a_obs[e] = w.v_pi[2 * v]; h_a_obs[At + e] = w.v_pi[2 * v + 1];
-      }
-      std::fill(h_vb_win + m.vis0 / 64, h_vb_win + (m.vis0 + m.Vp) / 64, wi);
-      for (int i = 0; i < m.Vp; ++i) {
-        const int v = t.lord[i];
-        const size_t e = (size_t)m.vis0 + i;
-        if (v < 0) {
-          h_v_win[e] = -1; h_v_lm[e] = 0; h_v_anc[e] = m.anc0; h_v_tj[e] = 0; h_v_rowj[e] = 0; h_v_cauchy[e] = 0.0;
-          for (int c = 0; c < 2; ++c) h_v_obs[(size_t)c * Vt + e] = 0.0;
-          continue;
-        }
-        h_v_win[e] = wi; h_v_lm[e] = w.v_lm[v]; h_v_anc[e] = m.anc0 + t.anc_of[v];
-        h_v_tj[e] = w.v_tj[v] - w.t0_ns;
-        h_v_rowj[e] = w.v_rowj[v];
-        h_v_obs[e] = (double)w.v_pj[2 * v]; h_v_obs[Vt + e] = (double)w.v_pj[2 * v + 1];
-        h_v_cauchy[e] = w.v_cauchy ? w.v_cauchy[v] : w.cauchy_a;
-      }
-      // the assembly's items: <= VCH blocks of one frame pair, frame-pair order, as lists of slots (vblk)
-      int it = m.vitem0 - 1;
-      for (int i = 0; i < w.V; ++i) {
-        const int v = t.vord[i];
-        const bool fresh = (i == 0) || w.v_ti[v] != w.v_ti[t.vord[i - 1]] || w.v_tj[v] != w.v_tj[t.vord[i - 1]] || h_vitems[it].count >= VCH;
-        if (fresh) h_vitems[++it] = VisItem{m.vis0 + i, 0};
-        h_vitems[it].count++;
-        h_vblk[(size_t)m.vis0 + i] = m.vis0 + t.vpos[v];
-        h_vblk_anc[(size_t)m.vis0 + i] = m.anc0 + t.anc_of[v];
-      }
-      for (int i = w.V; i < m.Vp; ++i) { h_vblk[(size_t)m.vis0 + i] = m.vis0; h_vblk_anc[(size_t)m.vis0 + i] = m.anc0; }   // (unused tail of the window's list)
-      for (int b = 0; b < w.NB; ++b) { h_bc_win[m.bc0 + b] = wi; h_bc_i[m.bc0 + b] = w.bc_i[b]; h_bc_j[m.bc0 + b] = w.bc_j[b]; }
-      if (w.NB) std::memcpy(h_bc_w + (size_t)6 * m.bc0, w.bc_w, sizeof(double) * 6 * w.NB);
-      // prior: J0^T J0 (row-major n*n), J0^T r0, r0^T r0 in fp64; J0 is column-major (Eigen)
-      const int n = w.pn;
-      h_pc0[wi] = 0.0;
-      int32_t *col = h_pcol + m.pv0;
-      if (n > 0) {
-        for (int b = 0; b < w.pnb; ++b) {
-          const int kind = w.p_kind[b], idx = w.p_index[b];
-          int u0 = 0;
-          switch (kind) {
-            case CTVIO_PK_ROT: u0 = 6 * idx; break;
-            case CTVIO_PK_POS: u0 = 6 * idx + 3; break;
-            case CTVIO_PK_BG: u0 = 6 * w.K + 6 * idx; break;
-            case CTVIO_PK_BA: u0 = 6 * w.K + 6 * idx + 3; break;
-            default: u0 = m.P - 1;
-          }
-          for (int k = 0; k < prior_block_size(kind); ++k) col[w.p_off[b] + k] = u0 + k;
-        }
-        double *pH = h_pH + m.pH0, *pb0 = h_pb0 + m.pv0;
-        std::memcpy(h_pJ0 + m.pH0, w.pJ0, sizeof(double) * (size_t)n * n);
-        std::memcpy(h_pr0 + m.pv0, w.pr0, sizeof(double) * (size_t)n);
-        for (int i = 0; i < n; ++i) {
-          const double *Ji = w.pJ0 + (size_t)i * n;
-          double bi = 0;
-          for (int r = 0; r < n; ++r) bi += Ji[r] * w.pr0[r];
-          pb0[i] = bi;
-          for (int j = 0; j <= i; ++j) {
-            const double *Jj = w.pJ0 + (size_t)j * n;
-            double s = 0;
-            for (int r = 0; r < n; ++r) s += Ji[r] * Jj[r];
-            pH[(size_t)i * n + j] = s; pH[(size_t)j * n + i] = s;
-          }
-        }
-        double c0 = 0;
-        for (int r = 0; r < n; ++r) c0 += w.pr0[r] * w.pr0[r];
-        h_pc0[wi] = c0;
-        std::memcpy(h_p_kind + m.pblk0, w.p_kind, 4 * (size_t)w.pnb); std::memcpy(h_p_index + m.pblk0, w.p_index, 4 * (size_t)w.pnb);
-        std::memcpy(h_p_off + m.pblk0, w.p_off, 4 * (size_t)w.pnb); std::memcpy(h_p_x0 + (size_t)4 * m.pblk0, w.p_x0, 8 * 4 * (size_t)w.pnb);
-      }
-      active_mask(&w, t, m.P, col, h_active + m.u0);
-      // inverse column map of the prior, and the IMU groups of every bias state (group order) -- read by the store-semantics assembly
-      std::fill(h_pinv + m.p0, h_pinv + m.p0 + m.P, -1);
-      for (int i = 0; i < n; ++i) h_pinv[m.p0 + col[i]] = i;
-      {
-        int32_t *off = h_bgl_off + m.bias0 + wi;
-        std::fill(off, off + w.F + 1, 0);
-        for (int gi = 0; gi < m.ngrp; ++gi) off[h_groups[m.grp0 + gi].bias + 1]++;
-        for (int f = 0; f < w.F; ++f) off[f + 1] += off[f];
-        std::vector<int32_t> fill(off, off + w.F);
-        for (int gi = 0; gi < m.ngrp; ++gi) h_bgl[m.grp0 + fill[h_groups[m.grp0 + gi].bias]++] = m.grp0 + gi;
-        for (int f = 0; f <= w.F; ++f) off[f] += m.grp0;   // absolute positions in bgl
-      }
-    };
-    auto pack = [&]() {
-      std::memcpy(CTV_H(WinMeta, o_meta), meta_.data(), sizeof(WinMeta) * nw);
-      pool_.run(nw, nth, fill_window);
-    };
+    HIPCHK(in_.reserve(lay.bytes, true, nullptr));
+    // ---- fill (threads)
+    auto pack = [&]() { pack_input(wins, tmp, meta_, b, lay, in_.host, VCH, pool_, nth); };
     if (dbg_.poison) {   // every byte of every segment must come from the batch: the packs over 0x00 and over 0xFF agree
-      const int rc = check_staging(segs, in_bytes, pack);
-      if (rc != CTVIO_OK) return rc;
+      const std::string err = check_staging(lay, in_.host, pack);
+      if (!err.empty()) return fail(CTVIO_ERR_INTERNAL, err);
     } else {
       pack();
     }
+    const InputPtrs hp = lay.at(in_.host), dp = lay.at(in_.dev);
+    h_lm_pos_ = hp.lm_pos; h_ld_ = StatePtrs(hp.state, b).ld;
     // ---- device pointers of the input arena
     Dev &d = dev_;
     std::memset(&d, 0, sizeof d);
-    d.nwin = nw; d.Ktot = K0; d.Ftot = F0; d.Ltot = L0; d.Mtot = M0; d.Gtot = G0; d.Vtot = V0; d.Atot = A0;
-    d.NBtot = B0; d.Utot = U0; d.maxN = maxN; d.maxP = maxP; d.maxPn = maxPn; d.maxL = maxL; d.maxLdw = maxLdw; maxK_ = maxK; max_schur_tiles_ = maxSchurTiles;
-    d.wins = CTV_D(WinMeta, o_meta);
-    d.quat = CTV_D(double, o_state); d.pos = d.quat + (size_t)4 * K0; d.bias = d.pos + (size_t)3 * K0; d.rho = d.bias + (size_t)6 * F0; d.ld = d.rho + L0;
-    d.knot_win = CTV_D(int32_t, o_knot_win); d.bias_win = CTV_D(int32_t, o_bias_win); d.lm_win = CTV_D(int32_t, o_lm_win);
-    d.groups = CTV_D(ImuGroup, o_groups); d.imu_grp = CTV_D(int32_t, o_imu_grp); d.imu_u = CTV_D(double, o_imu_u); d.imu_meas = CTV_D(double, o_imu_meas);
-    d.v_cauchy = CTV_D(double, o_v_cauchy); d.vb_win = CTV_D(int32_t, o_vb_win);
-    d.v_win = CTV_D(int32_t, o_v_win); d.v_lm = CTV_D(int32_t, o_v_lm); d.v_anc = CTV_D(int32_t, o_v_anc); d.v_rowj = CTV_D(int32_t, o_v_rowj);
-    d.v_tj = CTV_D(int64_t, o_v_tj); d.v_obs = CTV_D(double, o_v_obs);
-    d.a_win = CTV_D(int32_t, o_a_win); d.a_lm = CTV_D(int32_t, o_a_lm); d.a_row = CTV_D(int32_t, o_a_row); d.a_t = CTV_D(int64_t, o_a_t);
-    d.a_obs = CTV_D(double, o_a_obs);
-    d.vitems = CTV_D(VisItem, o_vitems); d.vblk = CTV_D(int32_t, o_vblk); d.vblk_anc = CTV_D(int32_t, o_vblk_anc);
-    d.bc_win = CTV_D(int32_t, o_bc_win); d.bc_i = CTV_D(int32_t, o_bc_i); d.bc_j = CTV_D(int32_t, o_bc_j); d.bc_w = CTV_D(double, o_bc_w);
-    d.pJ0 = CTV_D(double, o_pJ0); d.pr0 = CTV_D(double, o_pr0);
-    d.pH = CTV_D(double, o_pH); d.pb0 = CTV_D(double, o_pb0); d.pc0 = CTV_D(double, o_pc0); d.p_x0 = CTV_D(double, o_p_x0);
-    d.pcol = CTV_D(int32_t, o_pcol); d.p_kind = CTV_D(int32_t, o_p_kind); d.p_index = CTV_D(int32_t, o_p_index); d.p_off = CTV_D(int32_t, o_p_off);
-    d.active = CTV_D(uint8_t, o_active);
-    d.pinv = CTV_D(int32_t, o_pinv); d.bgl_off = CTV_D(int32_t, o_bgl_off); d.bgl = CTV_D(int32_t, o_bgl);
-    d.lm_pos = CTV_D(int32_t, o_lm_pos); d.lm_at = CTV_D(int32_t, o_lm_at); d.lm_klo = CTV_D(int32_t, o_lm_klo); d.lm_khi = CTV_D(int32_t, o_lm_khi);
-    d.tl_beg = CTV_D(int32_t, o_tl_beg); d.tl_end = CTV_D(int32_t, o_tl_end); d.env_first = CTV_D(int32_t, o_env_first); d.env_tile = CTV_D(int32_t, o_env_tile);
-    d.max_span6 = 6 * maxSpan;
-    d.vrow = walk ? CTV_D(int32_t, o_vrow) : nullptr; d.vrow_off = walk ? CTV_D(int32_t, o_vrow_off) : nullptr;
-#undef CTV_H
-#undef CTV_D
-    HIPCHK(hipMemcpyAsync(in_.dev, in_.host, in_bytes, hipMemcpyHostToDevice, stream_));
-    in_bytes_ = in_bytes;
-    any_vis_lds_ = any_vis_glb_ = false;
-    // (a window whose packed Hessian does not fit in LDS counts as "global" even without visual blocks -- e.g. an IMU-only predict of a
-    // long spline: the store-semantics tail only finishes LDS-resident windows, so such a batch must take the accumulate path)
-    for (const auto &mm : meta_) { if (mm.vis_lds) any_vis_lds_ = true; else any_vis_glb_ = true; }
-    all_windows_have_imu_ = !meta_.empty();
-    for (const auto &mm : meta_) if (mm.ngrp == 0) all_windows_have_imu_ = false;
-    deterministic_ = opt_.deterministic > 0 || (opt_.deterministic < 0 && nw <= 64);
-    // (the member goes into the launch signature and selects kernels: it must say what RUNS -- the default falls back to the accumulate path
-    //  for batches the order-fixed assembly cannot cover, and then it is off)
-    if (!any_vis_lds_ || any_vis_glb_) { if (opt_.deterministic <= 0) deterministic_ = false; }
+    d.nwin = nw; d.Ktot = b.K0; d.Ftot = b.F0; d.Ltot = b.L0; d.Mtot = b.M0; d.Gtot = b.G0; d.Vtot = b.V0; d.Atot = b.A0;
+    d.NBtot = b.B0; d.Utot = b.U0; d.maxN = b.maxN; d.maxP = b.maxP; d.maxPn = b.maxPn; d.maxL = b.maxL; d.maxLdw = b.maxLdw;
+#define CTV_X(type, name, member, alloc, used) d.member = dp.name;
+    CTV_INPUT_SEGMENTS(CTV_X)
+#undef CTV_X
+    { const StatePtrs st(dp.state, b); d.pos = st.pos; d.bias = st.bias; d.rho = st.rho; d.ld = st.ld; }   // (d.quat: the head of the block)
+    if (!b.walk) d.vrow = d.vrow_off = nullptr;
+    d.max_span6 = 6 * b.maxSpan;
+    // ---- one copy
+    HIPCHK(hipMemcpyAsync(in_.dev, in_.host, lay.bytes, hipMemcpyHostToDevice, stream_));
+    // ---- launch plan (before the work arena: the partial Hessians are sized by its parts)
     // deterministic = 1: the order-fixed accumulation of the batches whose every window keeps its packed Hessian in LDS, on the matrix-core
     // kernels.  An explicit request that cannot be honoured is an error; the default (-1) falls back to the accumulate path for such batches.
     // deterministic = 2: every batch -- the other windows take the order-fixed wide-window assembly (k_assemble_wide).
-    wide_fixed_ = deterministic_ && opt_.deterministic == 2 && any_vis_glb_;
-    if (opt_.deterministic > 0 && opt_.deterministic != 2 && (!any_vis_lds_ || any_vis_glb_))
+    if (opt_.deterministic > 0 && opt_.deterministic != 2 && (!b.any_vis_lds || b.any_vis_glb))
       return fail(CTVIO_ERR_INVALID, "deterministic = 1 needs every window's packed Hessian in LDS (K <= 25): this batch would "
                                      "fall back to floating-point atomics");
-    maxK_ = maxK;
-    // ---- work arena (device only)
-    state_doubles_ = (size_t)7 * K0 + 6 * F0 + L0 + nw;
-    off = 0;
-    segs.clear();
-    const size_t o_cstate = seg("cstate", 8 * state_doubles_), o_snap = seg("snap", 8 * state_doubles_);
-    const size_t o_lkd = seg("lkd", 8 * 3 * (size_t)K0), o_kjri = seg("kjri", sizeof(double) * 9 * (size_t)K0);
-    const size_t o_tiles = seg("tiles", sizeof(double) * 1024 * (size_t)G0);
-    const size_t o_imu_cost = seg("imu_cost", 8 * (size_t)std::max(G0, 1)), o_vis_cost = seg("vis_cost", 8 * ((Vt + 63) / 64)), o_misc_cost = seg("misc_cost", 8 * (size_t)nw);
-    // packed partial Hessians of the multi-part store-semantics assembly (knot triangle + line-delay row + gradient per part)
-    // (only the LDS-resident windows have parts: with deterministic = 2 a batch may hold wider ones)
-    const int kpart = wide_fixed_ ? maxK_lds : maxK;
-    const size_t part_stride = ((size_t)6 * kpart * (6 * kpart + 1) / 2 + 2 * (6 * (size_t)kpart + 1) + 7) & ~(size_t)7;
-    const int nparts_alloc = store_path() && kpart > 0 ? vis_parts() : 1;
-    const size_t o_pgrad = seg("pgrad", 8 * (size_t)std::max(pv0, 1)), o_Hpart = seg("Hpart", nparts_alloc > 1 ? 8 * part_stride * nparts_alloc * (size_t)nw : 8);
-    const size_t o_Jt = seg("Jt", sizeof(double) * VT_ROWS * 64 * ((Vt + 63) / 64)), o_vsj = seg("vsj", 4 * Vt);
-    const size_t o_arec = seg("arec", 8 * (size_t)AREC * At), o_a_s = seg("a_s", 4 * At);
-    const size_t o_vexp = seg("vexp", wide_fixed_ ? sizeof(double) * VX_LD * Vt : 8);   // expanded block records of the wide windows (k_vis_expand)
-    // two normal-equation sets (current linearisation / speculative linearisation at the candidate, Lm::cur)
-    const size_t o_Hpp = seg("Hpp", 8 * (size_t)H0), o_Hpp1 = seg("Hpp1", 8 * (size_t)H0), o_S = seg("S", 8 * (size_t)H0);
-    const size_t o_zero0 = off;   // ---- zeroed at every upload from here ...
-    const size_t o_W = seg("W", sizeof(double) * (size_t)W0), o_W1 = seg("W1", sizeof(double) * (size_t)W0), o_Hll = seg("Hll", 8 * (size_t)L0), o_Hll1 = seg("Hll1", 8 * (size_t)L0),
-                 o_g = seg("g", 8 * (size_t)U0), o_g1 = seg("g1", 8 * (size_t)U0), o_delta = seg("delta", 8 * (size_t)U0),
-                 o_cscale = seg("cscale", 8 * (size_t)U0), o_lm = seg("lm", sizeof(Lm) * (size_t)nw), o_nact = seg("nact", 16), o_dbg = seg("dbg", 8 * 128);
-    const size_t o_zero1 = off;   // ---- ... to here
-    const size_t o_rhs = seg("rhs", 8 * (size_t)Pp0), o_dd = seg("dd", 8 * (size_t)U0), o_dinv = seg("dinv", 8 * (size_t)L0), o_grs = seg("grs", 8 * (size_t)L0);
-    d.chol_nblk = (maxP + 31) / 32;
+    plan_ = make_plan(false);
+    d.schur_plain_in_H = plan_.schur_plain_in_H;
+    d.chol_nblk = (b.maxP + 31) / 32;
     d.chol_slots = chol_slots;
     d.line_search = opt_.line_search ? 1 : 0;
-    const size_t o_chol_inv = seg("chol_inv", 8 * (size_t)nw * d.chol_nblk * 1024);
-    HIPCHK(work_.reserve(off, false, &grew));
-    if (grew || dbg_.poison) HIPCHK(hipMemsetAsync(work_.dev, 0, work_.cap, stream_));   // fresh memory may hold NaN patterns (0 * NaN in masked products)
-    if (dbg_.poison)   // every double segment outside the per-upload zero region starts as the pattern (the integer ones never: they feed addresses)
-      for (const ArenaSeg &sg : segs)
-        if ((sg.off < o_zero0 || sg.off >= o_zero1) && std::strcmp(sg.name, "vsj") != 0 && std::strcmp(sg.name, "a_s") != 0)
-          HIPCHK(poison(work_.dev + sg.off, sg.bytes));
-    char *wb = work_.dev;
-#define CTV_W(type, o) reinterpret_cast<type *>(wb + (o))
-    d.cquat = CTV_W(double, o_cstate); d.cpos = d.cquat + (size_t)4 * K0; d.cbias = d.cpos + (size_t)3 * K0; d.crho = d.cbias + (size_t)6 * F0; d.cld = d.crho + L0;
-    snap_ = CTV_W(double, o_snap);
-    d.lkd = CTV_W(double, o_lkd); d.kjri = CTV_W(double, o_kjri); d.imu_tiles = CTV_W(double, o_tiles);
-    d.imu_cost = CTV_W(double, o_imu_cost); d.vis_cost = CTV_W(double, o_vis_cost); d.misc_cost = CTV_W(double, o_misc_cost);
-    d.pgrad = CTV_W(double, o_pgrad); d.Hpart = CTV_W(double, o_Hpart); d.npart_stride = (int32_t)part_stride;
-    d.Jt = CTV_W(double, o_Jt); d.vsj = CTV_W(int32_t, o_vsj); d.arec = CTV_W(double, o_arec); d.a_s = CTV_W(int32_t, o_a_s);
-    d.vexp = wide_fixed_ ? CTV_W(double, o_vexp) : nullptr;
-    d.HppS[0] = CTV_W(double, o_Hpp); d.HppS[1] = CTV_W(double, o_Hpp1); d.S = CTV_W(double, o_S);
-    d.WS[0] = CTV_W(double, o_W); d.WS[1] = CTV_W(double, o_W1); d.HllS[0] = CTV_W(double, o_Hll); d.HllS[1] = CTV_W(double, o_Hll1);
-    d.gS[0] = CTV_W(double, o_g); d.gS[1] = CTV_W(double, o_g1);
-    d.delta = CTV_W(double, o_delta); d.cscale = CTV_W(double, o_cscale); d.lm = CTV_W(Lm, o_lm); d.n_active = CTV_W(int32_t, o_nact); d.span_viol = d.n_active + 1;
-    d.dbg = dbg_.stamps ? CTV_W(long long, o_dbg) : nullptr;
-    d.rhs = CTV_W(double, o_rhs); d.dd = CTV_W(double, o_dd); d.dinv = CTV_W(double, o_dinv); d.grs = CTV_W(double, o_grs); d.chol_inv = CTV_W(double, o_chol_inv);
-#undef CTV_W
-    HIPCHK(hipMemsetAsync(wb + o_zero0, 0, o_zero1 - o_zero0, stream_));
+    // ---- work arena (device only)
+    if (const int rc = layout_work()) return rc;
     // pinned landing areas of the results
     if ((size_t)nw > lm_host_cap_) {   // (lm_host_cap_ records for the windows, one more as scratch: lm_scratch)
       if (lm_host_) (void)hipHostFree(lm_host_);
       lm_host_cap_ = (size_t)nw + nw / 8 + 16;
       HIPCHK(hipHostMalloc((void **)&lm_host_, sizeof(Lm) * (lm_host_cap_ + 1), hipHostMallocDefault));
     }
-    chol_lds_ = chol_lds;
     snap_valid_ = false;
-    vis_lds_ = vis_lds_bytes;
-    vis_glb_ = vis_glb_bytes;
-    d.schur_plain_in_H = schur_plain_in_H_for_batch();
     uploaded_ = true;
     return CTVIO_OK;
   }
 
+  // The work arena (device only), every segment ONCE: X(element type, the pointer it becomes, name, count, doubles that CTVIO_POISON
+  // may poison -- the integer segments never are: they feed addresses).  Three stretches: the middle one is zeroed at every upload.
+  // Irregular: cstate and snap are contiguous state blocks like the input's (StatePtrs); Hpart holds one entry unless the store tail runs
+  // with several parts; vexp one entry unless the order-fixed wide assembly runs (Dev gets null); Hpp / W / Hll / g come as two
+  // normal-equation sets (current linearisation / speculative linearisation at the candidate, Lm::cur); nact is n_active and span_viol
+  // (+ two spare words); dbg reaches Dev only with CTVIO_DEBUG_STAMPS.
+#define CTV_WORK_HEAD(X)                                                                                                  \
+  X(double, d.cquat, "cstate", state_doubles_, true) X(double, snap_, "snap", state_doubles_, true)                      \
+  X(double, d.lkd, "lkd", 3 * K0, true) X(double, d.kjri, "kjri", 9 * K0, true) X(double, d.imu_tiles, "tiles", 1024 * G0, true) \
+  X(double, d.imu_cost, "imu_cost", std::max<size_t>(G0, 1), true) X(double, d.vis_cost, "vis_cost", (Vt + 63) / 64, true) \
+  X(double, d.misc_cost, "misc_cost", nw, true)                                                                          \
+  X(double, d.pgrad, "pgrad", std::max<size_t>(b.pv0, 1), true)                                                          \
+  /* packed partial Hessians of the multi-part store-semantics assembly (knot triangle + line-delay row + gradient per part) */ \
+  X(double, d.Hpart, "Hpart", nparts_alloc > 1 ? part_stride * nparts_alloc * nw : 1, true)                              \
+  X(double, d.Jt, "Jt", (size_t)VT_ROWS * 64 * ((Vt + 63) / 64), true) X(int32_t, d.vsj, "vsj", Vt, false)                \
+  X(double, d.arec, "arec", (size_t)AREC * At, true) X(int32_t, d.a_s, "a_s", At, false)                                  \
+  /* expanded block records of the wide windows (k_vis_expand) */                                                        \
+  X(double, d.vexp, "vexp", wide ? (size_t)VX_LD * Vt : 1, true)                                                          \
+  X(double, d.HppS[0], "Hpp", H0, true) X(double, d.HppS[1], "Hpp1", H0, true) X(double, d.S, "S", H0, true)
+#define CTV_WORK_ZEROED(X)                                                                                                \
+  X(double, d.WS[0], "W", W0, true) X(double, d.WS[1], "W1", W0, true) X(double, d.HllS[0], "Hll", L0, true) X(double, d.HllS[1], "Hll1", L0, true) \
+  X(double, d.gS[0], "g", U0, true) X(double, d.gS[1], "g1", U0, true) X(double, d.delta, "delta", U0, true)              \
+  X(double, d.cscale, "cscale", U0, true) X(Lm, d.lm, "lm", nw, false) X(int32_t, d.n_active, "nact", 4, false) X(long long, d.dbg, "dbg", 128, false)
+#define CTV_WORK_TAIL(X)                                                                                                  \
+  X(double, d.rhs, "rhs", b.Pp0, true) X(double, d.dd, "dd", U0, true) X(double, d.dinv, "dinv", L0, true) X(double, d.grs, "grs", L0, true) \
+  X(double, d.chol_inv, "chol_inv", nw * d.chol_nblk * 1024, true)
+  int layout_work() {
+    Dev &d = dev_;
+    const BatchFacts &b = facts_;
+    const size_t nw = b.nw, K0 = b.K0, L0 = b.L0, G0 = b.G0, U0 = b.U0, H0 = (size_t)b.H0, W0 = (size_t)b.W0;
+    const size_t Vt = (size_t)std::max(b.V0, 1), At = (size_t)std::max(b.A0, 1);
+    state_doubles_ = (size_t)7 * b.K0 + 6 * b.F0 + b.L0 + nw;
+    // (only the LDS-resident windows have parts: with deterministic = 2 a batch may hold wider ones)
+    const bool wide = plan_.tail == TAIL_STORE_WIDE;
+    const int kpart = wide ? b.maxK_lds : b.maxK;
+    const size_t part_stride = ((size_t)6 * kpart * (6 * kpart + 1) / 2 + 2 * (6 * (size_t)kpart + 1) + 7) & ~(size_t)7;
+    const size_t nparts_alloc = plan_.tail != TAIL_ACCUMULATE && kpart > 0 ? plan_.parts : 1;
+    d.npart_stride = (int32_t)part_stride;
+    size_t off = 0;
+#define CTV_X(type, ptr, name, count, dbl) off += arena_align(sizeof(type) * (size_t)(count));
+    CTV_WORK_HEAD(CTV_X)
+    const size_t o_zero0 = off;   // ---- zeroed at every upload from here ...
+    CTV_WORK_ZEROED(CTV_X)
+    const size_t o_zero1 = off;   // ---- ... to here
+    CTV_WORK_TAIL(CTV_X)
+#undef CTV_X
+    bool grew = false;
+    HIPCHK(work_.reserve(off, false, &grew));
+    if (grew || dbg_.poison) HIPCHK(hipMemsetAsync(work_.dev, 0, work_.cap, stream_));   // fresh memory may hold NaN patterns (0 * NaN in masked products)
+    // (CTVIO_POISON: every double segment outside the per-upload zero region starts as the pattern)
+    char *p = work_.dev;
+#define CTV_X(type, ptr, name, count, dbl)                                                                                               \
+  ptr = reinterpret_cast<type *>(p);                                                                                                     \
+  if (dbl && !zeroed && poison(p, sizeof(type) * (size_t)(count)) != hipSuccess) return fail(CTVIO_ERR_HIP, "CTVIO_POISON: work segment " name); \
+  p += arena_align(sizeof(type) * (size_t)(count));
+    bool zeroed = false;
+    CTV_WORK_HEAD(CTV_X)
+    zeroed = true;
+    CTV_WORK_ZEROED(CTV_X)
+    zeroed = false;
+    CTV_WORK_TAIL(CTV_X)
+#undef CTV_X
+    { const StatePtrs st(d.cquat, b); d.cpos = st.pos; d.cbias = st.bias; d.crho = st.rho; d.cld = st.ld; }
+    if (!wide) d.vexp = nullptr;
+    d.span_viol = d.n_active + 1;
+    if (!dbg_.stamps) d.dbg = nullptr;
+    HIPCHK(hipMemsetAsync(work_.dev + o_zero0, 0, o_zero1 - o_zero0, stream_));
+    return CTVIO_OK;
+  }
+
+  // ---------------------------------------------------------------------------------------- launch plan
+  // Every resolved decision of the launch list, and nothing else: built by make_plan, the only place that turns a switch or an option into a
+  // kernel choice; the launch_* functions read dev_ and this.  Built zero-filled, like Dev: the captured graph is valid while both compare equal.
+  enum { TAIL_ACCUMULATE = 0, TAIL_STORE, TAIL_STORE_WIDE };                                        // LaunchPlan::tail
+  enum { SCHUR_WINDOW_5_7 = 0, SCHUR_WINDOW_5_14, SCHUR_WINDOW_7_14, SCHUR_TILE, SCHUR_TILE2 };     // LaunchPlan::schur
+  enum { CHOL_FLOW = 0, CHOL_TILES, CHOL_PANEL, CHOL_PANEL_SLOTS };                                 // LaunchPlan::chol
+  struct LaunchPlan {
+    int32_t tail;                    // assembly tail: atomics into zeroed Hpp / g; every entry stored once; stored once + k_assemble_wide for the wide windows
+    int32_t parts;                   // workgroups per window of the visual assembly
+    int32_t lds_windows, glb_windows;   // the batch has windows with / without the LDS-resident packed Hessian
+    int32_t merged, misc_in_pre;     // linearisation in two launches (else split); the prior gradient + cost share rides in k_pre_linearize
+    int32_t imu_zero, imu_general;   // kernels_imu.hpp: imu_zero_share mode; every IMU group through the general body
+    int32_t misc_imu;                // k_misc's IMU share on the accumulate path: 0 none, 1 straight to Hpp, 2 through the LDS band
+    int32_t schur, schur_tiles;      // the Schur kernel; tile kernels: 16 x 16 tiles (or 32 x 32 blocks) per window
+    int32_t schur_plain_in_H;        // Dev::schur_plain_in_H
+    int32_t chol, chol_waves;        // the Cholesky kernel; the panel kernels' waves
+    int32_t finish_waves;            // k_step_finish
+    int32_t wide_tiles;              // k_assemble_wide: tile rows of the augmented knot block
+    size_t vis_lds, vis_glb, misc_lds, schur_lds, chol_lds;   // dynamic LDS bytes
+  };
+  // Runs once per upload, and again around a profiled solve (which keeps every kernel apart); never per pass.
+  LaunchPlan make_plan(bool profiling) const {
+    const BatchFacts &b = facts_;
+    const int nw = b.nw;
+    LaunchPlan p;
+    std::memset(&p, 0, sizeof p);
+    p.lds_windows = b.any_vis_lds; p.glb_windows = b.any_vis_glb;
+    // Store-semantics assembly tail (kernels.hpp: bias_rows_store; every entry written once, no atomics): the deterministic mode, when
+    // every window's packed Hessian is LDS resident.  (The throughput mode does not take it: measured slower there, the bias-row gather
+    // costs more than the zeroing + atomic passes it replaces -- 14.5 vs 13.4 ms per 2048-window solve.)
+    // With deterministic = 2 and a window beyond the LDS-resident Hessian the choice is per window: the LDS-resident ones take this tail, the
+    // others k_assemble_wide -- both store every entry once, so the batch has no zeroing pass and no atomic assembly at all.
+    // (the default falls back to the accumulate path for batches the order-fixed assembly cannot cover; deterministic = 1 on such a batch
+    //  was refused by the upload)
+    const bool mixed = !b.any_vis_lds || b.any_vis_glb;
+    const bool deterministic = mixed ? opt_.deterministic > 0 : (opt_.deterministic > 0 || (opt_.deterministic < 0 && nw <= 64));
+    p.tail = !deterministic ? TAIL_ACCUMULATE : (opt_.deterministic == 2 && b.any_vis_glb) ? TAIL_STORE_WIDE : TAIL_STORE;
+    const bool store = p.tail != TAIL_ACCUMULATE;
+    // Workgroups per window of the visual assembly: batches smaller than the chip split a window's items over several parts.  In the
+    // deterministic mode a part is ONE wave (its LDS additions happen in program order) and there are more of them.
+    p.parts = store ? std::min(32, std::max(1, 512 / std::max(nw, 1))) : std::min(8, std::max(1, 256 / std::max(nw, 1)));
+    // The merged launch runs the visual body with the IMU body's register allocation (one wave per SIMD): only for batches smaller than
+    // the chip, where the single-wave latencies of the two evaluations overlap instead of adding up.
+    p.merged = b.G0 && b.V0 && !profiling && !dbg_.split_linearize && nw <= 128;
+    // (the merged launch carries the prior gradient + cost share only while dx fits its LDS next to the reduction cells)
+    p.misc_in_pre = p.merged && b.maxPn <= PRE_LIN_MAX_PN;
+    // The IMU linearisation kernels clear the accumulated parts of the normal equations on the side (kernels.hpp: imu_zero_share) when every
+    // window has IMU groups: 1 = bias rows only (one visual-assembly part stores the knot x knot block), 2 = everything; 0 = k_zero_normal.
+    p.imu_zero = (store || !b.all_imu) ? 0 : (p.parts == 1 ? 1 : 2);
+    // use_mfma = 2: every IMU group through the general body (k_imu_linearize_rest) -- the cross-check of the specialised one and the
+    // tests' way into the path that large knot-to-knot rotations / anisotropic accelerometer weights take
+    p.imu_general = opt_.use_mfma == 2 ? 1 : 0;
+    p.vis_lds = b.vis_lds_bytes; p.vis_glb = b.vis_glb_bytes;
+    {
+      // (windows without the LDS-resident Hessian: the IMU knot blocks are summed in an LDS band before they go to Hpp -- when it fits)
+      const size_t dxb = (size_t)((std::max(b.maxPn, 1) + 1) & ~1) * sizeof(double), bandb = (size_t)144 * b.maxK * sizeof(double);
+      const bool band = b.any_vis_glb && b.G0 && dxb + bandb <= 150 * 1024;
+      p.misc_lds = band ? dxb + bandb : dxb;
+      p.misc_imu = b.G0 ? (band ? 2 : 1) : 0;
+    }
+    {
+      // Large batches of small windows take the per-window Schur kernel (one workgroup per window, W staged through LDS once); everything else
+      // the tile kernels: one wave per 16 x 16 tile (shorter latency, W re-read per tile).  Every variant also produces the reduced
+      // right-hand side (g_rho rides as column P).
+      const int nt = (b.maxLdw + 15) / 16, ntile = nt * (nt + 1) / 2;
+      const size_t lds = ((size_t)2 * 16 * (b.maxLdw + 16) + 3 * b.maxLdw + 32 + 64) * sizeof(double);   // + column vectors + the list of tiles with products
+      const int nc = 6 * b.maxK + 2;   // compact columns of W per landmark: knots, line delay, g_rho
+      const int nt2 = b.maxP / 16 + 1, ntile2 = nt2 * (nt2 + 1) / 2;   // tile rows up to index P (the rhs row)
+      const int nb2 = (nt2 + 1) / 2, nblk2 = nb2 * (nb2 + 1) / 2;      // 32 x 32 blocks of the lower triangle
+      if (nw >= 192 && b.maxLdw <= 224 && ntile <= 112 && lds <= 160 * 1024 && nc <= 224) {
+        p.schur = (16 * nc <= 5 * 512 && b.maxSchurTiles <= 56) ? SCHUR_WINDOW_5_7 : (16 * nc <= 5 * 512) ? SCHUR_WINDOW_5_14 : SCHUR_WINDOW_7_14;
+        p.schur_lds = lds;
+      }
+      // enough tiles to fill the chip several times over (config 5: 666 per window): one wave per 2 x 2 tiles, half the operand loads
+      // per product; otherwise one wave per tile (more waves in flight).  CTVIO_SCHUR_TILE2 = 0 / 1 forces the choice (A/B).
+      else if (dbg_.schur_tile2 >= 0 ? dbg_.schur_tile2 != 0 : (long long)nw * ntile2 >= 16384) { p.schur = SCHUR_TILE2; p.schur_tiles = nblk2; }
+      else { p.schur = SCHUR_TILE; p.schur_tiles = ntile2; }
+    }
+    // P <= 223: the register-resident tile kernel (S read once, nothing written back; 16 waves per window) for batches smaller than
+    // the chip, where latency counts; large batches: the panel kernel with 4 waves, two windows per CU (throughput); windows beyond
+    // 223 unknowns: the panel kernel, with 8 waves when there are fewer windows than CUs
+    if (b.chol_tiles) {
+      const int ntr = b.maxP / 16 + 1;
+      p.chol = b.chol_tiles == 1 ? CHOL_TILES : CHOL_FLOW;   // (CTVIO_CHOL_TILES=1: round 5's kernel)
+      p.chol_lds = b.chol_tiles == 1 ? (size_t)(272 + 2 * ntr * 272 + 32 * ntr + 4 + 768) * sizeof(double)   // identity + panel + inverses + vectors + parked tiles
+                                     : (size_t)(272 + 5 * ntr * 272 + 32 * ntr + 48) * sizeof(double);      // identity + inverses + sub-diagonal tiles + three panels + vectors + flags
+    } else {
+      // (8 waves also when the panel's LDS footprint allows one workgroup per CU anyway -- P = 571: 157 KB -- where 4 waves left three quarters
+      //  of the CU's wave slots empty)
+      // (windows beyond 591 unknowns: the slot-indexed variant, same wave-count rule)
+      p.chol = b.chol_compact ? CHOL_PANEL_SLOTS : CHOL_PANEL;
+      p.chol_lds = b.chol_lds;
+      p.chol_waves = (nw <= 192 || b.chol_lds > 80 * 1024) ? 8 : 4;
+    }
+    // Dev::schur_plain_in_H is part of the Dev struct the captured graph is keyed on: decided once per upload, never inside a launch
+    // (launch_schur used to set it, so every upload -- which clears Dev -- invalidated the cached hipGraph of the headline configuration).
+    p.schur_plain_in_H = (p.schur <= SCHUR_WINDOW_7_14 && b.chol_tiles != 0 && !dbg_.schur_copy_plain) ? 1 : 0;
+    // (fewer windows than CUs: 8 waves per window shorten the landmark back-substitution; 16 waves -- a 128-register cap -- spilled 18
+    //  registers to scratch and were measured slower: 3.15 vs 3.09 ms per single-window solve)
+    p.finish_waves = nw <= 192 ? 8 : 4;
+    p.wide_tiles = (6 * b.maxK + 2 + 15) / 16;
+    return p;
+  }
+
   // ---------------------------------------------------------------------------------------- launches
   static int nblk(long long n, int b) { return (int)std::max<long long>((n + b - 1) / b, 1); }
-  // Workgroups per window of the visual assembly: batches smaller than the chip split a window's items over several parts.  In the
-  // deterministic mode a part is ONE wave (its LDS additions happen in program order) and there are more of them.
-  int vis_parts() const {
-    const int nw = std::max((int)meta_.size(), 1);
-    if (store_path()) return std::min(32, std::max(1, 512 / nw));
-    return std::min(8, std::max(1, 256 / nw));
-  }
-  // Store-semantics assembly tail (kernels.hpp: bias_rows_store; every entry written once, no atomics): the deterministic mode, when
-  // every window's packed Hessian is LDS resident.  (CTVIO_STORE_PATH=1 forces it for the throughput mode too: measured slower there,
-  // the bias-row gather costs more than the zeroing + atomic passes it replaces -- 14.5 vs 13.4 ms per 2048-window solve.)
-  // With deterministic = 2 and a window beyond the LDS-resident Hessian the choice is per window: the LDS-resident ones take this tail, the
-  // others k_assemble_wide -- both store every entry once, so the batch has no zeroing pass and no atomic assembly at all.
-  bool store_path() const {
-    if (wide_fixed_) return true;
-    if (!any_vis_lds_ || any_vis_glb_) return false;
-    if (dbg_.store_path >= 0) return dbg_.store_path == 1;
-    return deterministic_;
-  }
   void set_params(int max_iters) {
     LmParams &p = dev_.prm;
     p.ftol = opt_.function_tolerance; p.gtol = opt_.gradient_tolerance; p.ptol = opt_.parameter_tolerance;
@@ -707,54 +501,54 @@ class SolverImpl : public SolverBase {
   // the cost partials of the evaluated state come out on the way.
   void launch_linearize(int mode) {
     const Dev &d = dev_;
+    const LaunchPlan &p = plan_;
     const int nw = d.nwin;
-    const bool merged = merge_linearize();
-    // (the merged launch carries the prior gradient + cost share only while dx fits its LDS next to the reduction cells)
-    const bool misc_in_pre = merged && d.maxPn <= PRE_LIN_MAX_PN;
     ph_begin(PH_ASM_REST);
-    if (!store_path()) { if (!imu_zero_mode()) hipLaunchKernelGGL(k_zero_normal, dim3(64, nw), dim3(256), 0, stream_, d, vis_parts() == 1 ? 1 : 0, mode); }
-    else if (!misc_in_pre) hipLaunchKernelGGL(k_misc, dim3(nw), dim3(256), std::max(d.maxPn, 1) * sizeof(double), stream_, d, mode, 1, 0);   // prior gradient + cost share
+    if (p.tail == TAIL_ACCUMULATE) { if (!p.imu_zero) hipLaunchKernelGGL(k_zero_normal, dim3(64, nw), dim3(256), 0, stream_, d, p.parts == 1 ? 1 : 0, mode); }
+    else if (!p.misc_in_pre) hipLaunchKernelGGL(k_misc, dim3(nw), dim3(256), std::max(d.maxPn, 1) * sizeof(double), stream_, d, mode, 1, 0);   // prior gradient + cost share
     ph_end();
-    if (merged) {
+    if (p.merged) {
       // Small batches: TWO launches for the whole linearisation.  k_pre_linearize: the anchors' records, the IMU groups the specialised body
       // leaves out and (store-semantics path) the prior gradient + cost share -- three launches of 5 - 7 us each until round 5; then
       // k_linearize_f64: both evaluations (independent work: their latencies overlap on batches smaller than the chip).  A profiled
       // solve (and CTVIO_SPLIT_LINEARIZE=1, for rocprofv3 runs) keeps everything apart so that each kernel gets its own timing.
-      const int nab = nblk(d.Atot, 64), with_misc = store_path() && misc_in_pre ? 1 : 0;
-      hipLaunchKernelGGL(k_pre_linearize, dim3(nab + nw + (with_misc ? nw : 0)), dim3(64), 0, stream_, d, mode, imu_general_only(), imu_zero_mode(), nab, with_misc);
-      hipLaunchKernelGGL(k_linearize_f64, dim3(d.Gtot + nblk(d.Vtot, 64)), dim3(64), 0, stream_, d, mode, imu_general_only(), imu_zero_mode());
+      const int nab = nblk(d.Atot, 64), with_misc = p.tail != TAIL_ACCUMULATE && p.misc_in_pre ? 1 : 0;
+      hipLaunchKernelGGL(k_pre_linearize, dim3(nab + nw + (with_misc ? nw : 0)), dim3(64), 0, stream_, d, mode, p.imu_general, p.imu_zero, nab, with_misc);
+      hipLaunchKernelGGL(k_linearize_f64, dim3(d.Gtot + nblk(d.Vtot, 64)), dim3(64), 0, stream_, d, mode, p.imu_general, p.imu_zero);
       return;
     }
+    launch_evaluate(mode);
+  }
+  // The evaluations as separate launches (the split linearisation, and ctvio_cost): IMU groups, anchors, visual blocks.
+  static constexpr int IMU_WALK_WAVES = 2048;   // walking waves of k_imu_linearize_f64
+  void launch_evaluate(int mode) {
+    const Dev &d = dev_;
     ph_begin(PH_IMU_LIN);
-    if (d.Gtot) launch_imu_linearize(mode);
+    if (d.Gtot) {
+      // (at most 2048 waves -- two rounds of one wave per SIMD -- each walking its share of the groups with the next group's data in flight)
+      hipLaunchKernelGGL(k_imu_linearize_f64, dim3(std::min(d.Gtot, IMU_WALK_WAVES)), dim3(64), (size_t)(72 * 33 + 64) * sizeof(double), stream_, d, mode, plan_.imu_general, plan_.imu_zero);
+      hipLaunchKernelGGL(k_imu_linearize_rest, dim3(d.nwin), dim3(64), (size_t)64 * 33 * sizeof(double), stream_, d, mode, plan_.imu_general, plan_.imu_zero);
+    }
     ph_end();
     ph_begin(PH_VIS_LIN);   // (one timed group: the anchors' records, then the blocks)
     if (d.Atot) hipLaunchKernelGGL(k_vis_anchor, dim3(nblk(d.Atot, 64)), dim3(64), 0, stream_, d, mode);   // the i ends, once per anchor
     if (d.Vtot) hipLaunchKernelGGL(k_vis_eval, dim3(nblk(d.Vtot, 64)), dim3(64), 0, stream_, d, mode);
     ph_end();
   }
-  // The merged launch runs the visual body with the IMU body's register allocation (one wave per SIMD): only for batches smaller than
-  // the chip, where the single-wave latencies of the two evaluations overlap instead of adding up.  CTVIO_MERGE_LINEARIZE = 0 / 1 forces
-  // the choice (A/B measurements).
-  bool merge_linearize() const {
-    const Dev &d = dev_;
-    if (!(d.Gtot && d.Vtot && !profiling_ && !dbg_.split_linearize)) return false;
-    if (dbg_.merge_linearize >= 0) return dbg_.merge_linearize == 1;
-    return d.nwin <= 128;
-  }
   void launch_assemble(int mode) {
     const Dev &d = dev_;
+    const LaunchPlan &p = plan_;
     const int nw = d.nwin;
-    const int parts = vis_parts();   // few windows: split each window's items over several workgroups to fill the chip
-    if (store_path()) {
+    const int parts = p.parts;   // few windows: split each window's items over several workgroups to fill the chip
+    if (p.tail != TAIL_ACCUMULATE) {
       // every entry of Hpp / g is written once, completely, with a plain store: no zeroing pass, no k_assemble_imu, no atomics
       ph_begin(PH_ASM_VIS);
-      if (!wide_fixed_ || any_vis_lds_) {
-        launch_assemble_vis_store(parts, mode);
-        if (parts > 1) hipLaunchKernelGGL(k_reduce_finalize, dim3(deterministic_ ? 48 : 24, nw), dim3(256), 0, stream_, d, mode, parts);
+      if (p.lds_windows) {   // (the store tail always runs in the deterministic mode: a part is ONE wave)
+        hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, true, 1, true>), dim3(nw, parts), dim3(64), p.vis_lds, stream_, d, mode);
+        if (parts > 1) hipLaunchKernelGGL(k_reduce_finalize, dim3(48, nw), dim3(256), 0, stream_, d, mode, parts);
         else hipLaunchKernelGGL(k_bias_rows, dim3(8, nw), dim3(256), 0, stream_, d, mode);
       }
-      if (wide_fixed_) launch_assemble_wide(mode);
+      if (p.tail == TAIL_STORE_WIDE) launch_assemble_wide(mode);
       ph_end();
       if (mode != LIN_SPEC) {   // (the candidate's gradient norm: k_pass_end)
         ph_begin(PH_ASM_REST);
@@ -764,17 +558,13 @@ class SolverImpl : public SolverBase {
       return;
     }
     ph_begin(PH_ASM_VIS);
-    if (any_vis_lds_) launch_assemble_vis_lds(parts, mode);
-    if (any_vis_glb_) launch_assemble_vis_glb(parts, mode);
+    if (p.lds_windows) hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, true>), dim3(nw, parts), dim3(512), p.vis_lds, stream_, d, mode);
+    // windows whose packed Hessian does not fit in LDS (K > 25): run products on the MFMA units, added to Hpp with global atomics
+    if (p.glb_windows) hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, false>), dim3(nw, parts), dim3(512), p.vis_glb, stream_, d, mode);
     ph_end();
     ph_begin(PH_ASM_REST);
     // (the IMU tiles' bias rows, the bias chain and the prior in ONE launch: k_misc with assemble_imu_window in front)
-    {
-      // (windows without the LDS-resident Hessian: the IMU knot blocks are summed in an LDS band before they go to Hpp -- when it fits)
-      const size_t dxb = (size_t)((std::max(d.maxPn, 1) + 1) & ~1) * sizeof(double), bandb = (size_t)144 * maxK_ * sizeof(double);
-      const bool band = any_vis_glb_ && d.Gtot && dxb + bandb <= 150 * 1024 && !dbg_.no_imu_band;
-      hipLaunchKernelGGL(k_misc, dim3(nw), dim3(256), band ? dxb + bandb : dxb, stream_, d, mode, 0, d.Gtot ? (band ? 2 : 1) : 0);
-    }
+    hipLaunchKernelGGL(k_misc, dim3(nw), dim3(256), p.misc_lds, stream_, d, mode, 0, p.misc_imu);
     if (mode != LIN_SPEC) hipLaunchKernelGGL(k_post_linearize, dim3(nblk(d.maxN, 256), nw), dim3(256), 0, stream_, d, mode);
     ph_end();
   }
@@ -782,94 +572,62 @@ class SolverImpl : public SolverBase {
   // candidate x (+) alpha delta of every window with a valid step (also those inside the line search: new alpha, same delta).
   void launch_step() {
     const Dev &d = dev_;
+    const LaunchPlan &p = plan_;
     const int nw = d.nwin;
     ph_begin(PH_SCHUR);
     launch_schur();
     ph_end();
     ph_begin(PH_CHOL);
-    // P <= 223: the register-resident tile kernel (S read once, nothing written back; 16 waves per window) for batches smaller than
-    // the chip, where latency counts; large batches: the panel kernel with 4 waves, two windows per CU (throughput); windows beyond
-    // 223 unknowns: the panel kernel, with 8 waves when there are fewer windows than CUs
-    if (chol_tiles()) {
-      const int ntr = d.maxP / 16 + 1;
-      const size_t lds = (size_t)(272 + 2 * ntr * 272 + 32 * ntr + 4 + 768) * sizeof(double);   // identity + panel + inverses + vectors + parked tiles
-      const size_t lds_flow = (size_t)(272 + 5 * ntr * 272 + 32 * ntr + 48) * sizeof(double);   // identity + inverses + sub-diagonal tiles + three panels + vectors + flags
-      if (chol_tiles() == 1) hipLaunchKernelGGL((k_cholesky_tiles<16, 7>), dim3(nw), dim3(1024), lds, stream_, d);   // (A/B: round 5's kernel)
-      else hipLaunchKernelGGL(k_cholesky_flow, dim3(nw), dim3(1024), lds_flow, stream_, d);
+    switch (p.chol) {
+      case CHOL_TILES: hipLaunchKernelGGL((k_cholesky_tiles<16, 7>), dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
+      case CHOL_FLOW: hipLaunchKernelGGL(k_cholesky_flow, dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
+      case CHOL_PANEL_SLOTS:
+        if (p.chol_waves == 8) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(nw), dim3(512), p.chol_lds, stream_, d);
+        else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(nw), dim3(256), p.chol_lds, stream_, d);
+        break;
+      default:
+        if (p.chol_waves == 8) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(nw), dim3(512), p.chol_lds, stream_, d);
+        else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(nw), dim3(256), p.chol_lds, stream_, d);
     }
-    // (8 waves also when the panel's LDS footprint allows one workgroup per CU anyway -- P = 571: 157 KB -- where 4 waves left three quarters
-    //  of the CU's wave slots empty)
-    // (windows beyond 591 unknowns: the slot-indexed variant, same wave-count rule)
-    else if (chol_compact_) {
-      if (nw <= 192 || chol_lds_ > 80 * 1024) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(nw), dim3(512), chol_lds_, stream_, d);
-      else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(nw), dim3(256), chol_lds_, stream_, d);
-    }
-    else if (nw <= 192 || chol_lds_ > 80 * 1024) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(nw), dim3(512), chol_lds_, stream_, d);
-    else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(nw), dim3(256), chol_lds_, stream_, d);
     ph_end();
     ph_begin(PH_REST);
-    // (fewer windows than CUs: 16 waves per window shorten the landmark back-substitution from 7 trips to 2)
-    // (fewer windows than CUs: 8 waves per window shorten the landmark back-substitution; 16 waves -- a 128-register cap -- spilled 18
-    //  registers to scratch and were measured slower: 3.15 vs 3.09 ms per single-window solve)
-    if (nw <= 192) hipLaunchKernelGGL((k_step_finish<8>), dim3(nw), dim3(512), (size_t)d.maxP * sizeof(double), stream_, d);
+    if (p.finish_waves == 8) hipLaunchKernelGGL((k_step_finish<8>), dim3(nw), dim3(512), (size_t)d.maxP * sizeof(double), stream_, d);
     else hipLaunchKernelGGL((k_step_finish<4>), dim3(nw), dim3(256), (size_t)d.maxP * sizeof(double), stream_, d);
     ph_end();
   }
-  void launch_schur();
-  void launch_imu_linearize(int mode);
-  // use_mfma = 2 (or CTVIO_IMU_GENERAL=1): every IMU group through the general body (k_imu_linearize_rest) -- the cross-check of the
-  // specialised one and the tests' way into the path that large knot-to-knot rotations / anisotropic accelerometer weights take
-  // The IMU linearisation kernels clear the accumulated parts of the normal equations on the side (kernels.hpp: imu_zero_share) when every
-  // window has IMU groups: 1 = bias rows only (one visual-assembly part stores the knot x knot block), 2 = everything; 0 = k_zero_normal.
-  int imu_zero_mode() const {
-    if (store_path() || !all_windows_have_imu_ || dbg_.zero_kernel) return 0;
-    return vis_parts() == 1 ? 1 : 2;
+  void launch_schur() {
+    const Dev &d = dev_;
+    const LaunchPlan &p = plan_;
+    const int ngrid = p.schur_tiles * 8 * ((d.nwin + 7) / 8);   // (the tile kernels)
+    switch (p.schur) {
+      case SCHUR_WINDOW_5_7: hipLaunchKernelGGL((k_schur_window_f64<5, 7>), dim3(d.nwin), dim3(512), p.schur_lds, stream_, d); break;
+      case SCHUR_WINDOW_5_14: hipLaunchKernelGGL((k_schur_window_f64<5, 14>), dim3(d.nwin), dim3(512), p.schur_lds, stream_, d); break;
+      case SCHUR_WINDOW_7_14: hipLaunchKernelGGL((k_schur_window_f64<7, 14>), dim3(d.nwin), dim3(512), p.schur_lds, stream_, d); break;
+      case SCHUR_TILE2: hipLaunchKernelGGL(k_schur_tile2_f64, dim3(ngrid), dim3(64), 0, stream_, d, p.schur_tiles); break;
+      default: hipLaunchKernelGGL(k_schur_tile_f64, dim3(ngrid), dim3(64), 0, stream_, d, p.schur_tiles);
+    }
   }
-  int imu_walk_waves() const { return dbg_.imu_waves; }
-  int imu_general_only() const { return (dbg_.imu_general || opt_.use_mfma == 2) ? 1 : 0; }
-  void launch_assemble_vis_lds(int parts, int mode);
-  void launch_assemble_vis_glb(int parts, int mode);
   // The windows beyond the LDS-resident Hessian under deterministic = 2: the expanded block records, one workgroup per 16 x 16 tile of the knot
   // block + line-delay row + gradient (augmented: 6K + 2 unknowns), the bias rows by gather.
   void launch_assemble_wide(int mode) {
     const Dev &d = dev_;
-    const int nt = (6 * maxK_ + 2 + 15) / 16;
+    const int nt = plan_.wide_tiles;
     if (d.Vtot) hipLaunchKernelGGL(k_vis_expand, dim3(nblk((long long)d.Vtot * (VX_COLS + 1), 256)), dim3(256), 0, stream_, d, mode);
     hipLaunchKernelGGL(k_assemble_wide, dim3(nt * (nt + 1) / 2, d.nwin), dim3(64 * WIDE_NW), 0, stream_, d, mode);
     hipLaunchKernelGGL(k_bias_rows_wide, dim3(32, d.nwin), dim3(256), 0, stream_, d, mode);
   }
-  void launch_assemble_vis_store(int parts, int mode) {
-    const Dev &d = dev_;
-    if (deterministic_) hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, true, 1, true>), dim3(d.nwin, parts), dim3(64), vis_lds_, stream_, d, mode);
-    else hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, true, 8, true>), dim3(d.nwin, parts), dim3(512), vis_lds_, stream_, d, mode);
-  }
-  // Large batches of small windows take the per-window Schur kernel (W staged through LDS once); everything else the tile kernels.
-  bool schur_window_path() const {
-    const Dev &d = dev_;
-    const int nt = (d.maxLdw + 15) / 16, ntile = nt * (nt + 1) / 2;
-    const size_t lds = schur_window_lds();
-    const bool small = d.nwin < 192 || dbg_.schur_tiles;
-    const int nc = 6 * maxK_ + 2;   // compact columns of W per landmark: knots, line delay, g_rho
-    return !small && d.maxLdw <= 224 && ntile <= 112 && lds <= 160 * 1024 && nc <= 224;
-  }
-  size_t schur_window_lds() const { return ((size_t)2 * 16 * (dev_.maxLdw + 16) + 3 * dev_.maxLdw + 32 + 64) * sizeof(double); }   // + column vectors + the list of tiles with products
-  // Dev::schur_plain_in_H is part of the Dev struct the captured graph is keyed on: decided once per upload, never inside a launch
-  // (launch_schur used to set it, so every upload -- which clears Dev -- invalidated the cached hipGraph of the headline configuration).
-  int schur_plain_in_H_for_batch() const { return (schur_window_path() && chol_tiles() != 0 && !dbg_.schur_copy_plain) ? 1 : 0; }
   // CTVIO_CHOL_TILES = 0 / 1 / 3 forces the choice (A/B measurements: panel kernel / k_cholesky_tiles / k_cholesky_flow)
   int chol_tiles_for(int maxP) const {
     if (maxP > 223) return 0;
     if (dbg_.chol_tiles >= 0) return dbg_.chol_tiles;
     return 3;   // (register-resident tiles as a data-flow of waves: k_cholesky_flow; 1 = round 5's k_cholesky_tiles, the barrier-per-panel form)
   }
-  int chol_tiles() const { return chol_tiles_; }   // the batch's choice, taken in pack_and_upload
   // k_cholesky_solve's LDS in doubles: Lb, LiT, dinvs, yb, flags, plist (fixed) + the panel, 32 columns x the trailing height of the first panel
   static constexpr size_t chol_lds_fixed = 2 * 32 * 34 + 32 + 34 + 32;
   static size_t chol_panel_lds(int maxP) { return (chol_lds_fixed + (size_t)((std::max(maxP - 32, 0) + 1 + 15) / 16 * 16) * 32) * sizeof(double); }
   // CTVIO_DENSE=1: the sparsity plan degenerates to the dense one (every row range = all landmarks, envelope = the whole triangle) -- the
   // A/B switch of the sparsity-aware kernels and the cross-check of tests/test_gpu_sparsity.py
   bool sparsity_off() const { return dbg_.dense == 1; }
-  int n_state() const { return dev_.Ktot + dev_.Ftot + dev_.Ltot + dev_.nwin; }
 
   // One PASS of the device-resident LM: every running window advances by one phase -- a new trust-region iteration (damp, Schur,
   // Cholesky, back-substitute, candidate) or, inside Ceres' projected line search, one trial step (candidate at the new alpha) --
@@ -878,7 +636,7 @@ class SolverImpl : public SolverBase {
   // (continuation tests, LM diagonal).  The launch list is fixed: kernels skip windows that are not in the matching phase.
   void launch_pass() {
     Dev &d = dev_;
-    const int nw = d.nwin, wb = nblk(nw, 64);
+    const int nw = d.nwin;
     launch_step();
     launch_linearize(LIN_SPEC);
     launch_assemble(LIN_SPEC);
@@ -899,17 +657,11 @@ class SolverImpl : public SolverBase {
     hipLaunchKernelGGL(k_initial_cost, dim3(nw), dim3(64), 0, stream_, d, 0);
   }
   // The pass as a hipGraph (captured once per batch shape: the kernel arguments are the Dev struct, so equal shapes in the
-  // grow-only arenas give identical graphs), replayed instead of ~25 launches.
-  // Everything the launch list depends on besides the Dev struct: dynamic LDS sizes, kernel choices (template arguments, which
-  // assembly variants run).  Two batches with identical totals can differ in these (e.g. the same sum K split differently).
-  std::vector<long long> launch_signature() const {
-    return {(long long)vis_lds_, (long long)vis_glb_, (long long)any_vis_lds_, (long long)any_vis_glb_, (long long)maxK_, (long long)max_schur_tiles_,
-            (long long)chol_lds_, (long long)opt_.use_mfma, (long long)vis_parts(), (long long)deterministic_, (long long)chol_tiles(), (long long)imu_zero_mode(), (long long)merge_linearize(), (long long)dev_.nwin,
-            (long long)dbg_.schur_tile2, (long long)wide_fixed_};
-  }
+  // grow-only arenas give identical graphs), replayed instead of ~25 launches.  Everything else the launch list depends on -- dynamic
+  // LDS sizes, kernel choices (template arguments, which assembly variants run) -- is the launch plan: two batches with identical totals
+  // can differ in these (e.g. the same sum K split differently).
   int ensure_graph() {
-    const std::vector<long long> sig = launch_signature();
-    if (graph_exec_ && std::memcmp(&graph_dev_, &dev_, sizeof dev_) == 0 && sig == graph_sig_) return CTVIO_OK;
+    if (graph_exec_ && std::memcmp(&graph_dev_, &dev_, sizeof dev_) == 0 && std::memcmp(&graph_plan_, &plan_, sizeof plan_) == 0) return CTVIO_OK;
     if (graph_exec_) { (void)hipGraphExecDestroy(graph_exec_); graph_exec_ = nullptr; }
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
@@ -919,7 +671,7 @@ class SolverImpl : public SolverBase {
     (void)hipGraphDestroy(g);
     if (e != hipSuccess) { graph_exec_ = nullptr; return fail(CTVIO_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
     graph_dev_ = dev_;
-    graph_sig_ = sig;
+    graph_plan_ = plan_;
     ++graph_captures_;
     return CTVIO_OK;
   }
@@ -939,13 +691,14 @@ class SolverImpl : public SolverBase {
                                     "the normal equations of this call are not to be trusted");
   }
 
-  int solve(int max_iters, ctvio_summary *out) override {
+  int solve(int max_iters, ctvio_summary *out) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (max_iters < 0) return fail(CTVIO_ERR_INVALID, "max_iterations < 0");
     Dev &d = dev_;
-    const int nw = d.nwin, wb = nblk(nw, 64);
+    const int nw = d.nwin;
     set_params(max_iters);
     profiling_ = profiling_requested_;
+    if (profiling_) plan_ = make_plan(true);   // (every kernel apart; the upload's plan comes back below)
     pev_phase_.clear(); pev_used_ = 0;
     const bool graph = opt_.use_graph && !profiling_ && !d.dbg;
     if (graph) { const int rc = ensure_graph(); if (rc != CTVIO_OK) return rc; }
@@ -978,6 +731,7 @@ class SolverImpl : public SolverBase {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev_[8], ev_[9]));
     if (profiling_) ph_collect(); else { std::fill(ph_ms_, ph_ms_ + 8, 0.0); std::fill(ph_n_, ph_n_ + 8, 0); }
+    if (profiling_) plan_ = make_plan(false);
     profiling_ = false;
     std::copy(ph_ms_, ph_ms_ + 7, timing_);
     timing_[7] = ms;
@@ -1009,7 +763,7 @@ class SolverImpl : public SolverBase {
     return CTVIO_OK;
   }
 
-  int get_state(int id, double *quat, double *pos, double *bias, double *rho, double *ld) override {
+  int get_state(int id, double *quat, double *pos, double *bias, double *rho, double *ld) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
     const WinMeta &m = meta_[id];
@@ -1021,7 +775,7 @@ class SolverImpl : public SolverBase {
     HIPCHK(hipStreamSynchronize(stream_));
     return CTVIO_OK;
   }
-  int set_state(int id, const double *quat, const double *pos, const double *bias, const double *rho, double ld) override {
+  int set_state(int id, const double *quat, const double *pos, const double *bias, const double *rho, double ld) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
     const WinMeta &m = meta_[id];
@@ -1037,7 +791,7 @@ class SolverImpl : public SolverBase {
   }
 
   // device-side copy of the whole batch state (restore != 0: copy back); the state is one contiguous block
-  int snapshot(int restore) override {
+  int snapshot(int restore) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (restore && !snap_valid_) return fail(CTVIO_ERR_STATE, "no snapshot taken");
     HIPCHK(hipMemcpyAsync(restore ? dev_.quat : snap_, restore ? snap_ : dev_.quat, state_doubles_ * sizeof(double), hipMemcpyDeviceToDevice, stream_));
@@ -1045,7 +799,7 @@ class SolverImpl : public SolverBase {
     return CTVIO_OK;
   }
   // every window's state in one device-to-host copy (concatenated in window order, like the device arrays)
-  int get_batch_state(double *quat, double *pos, double *bias, double *rho, double *ld) override {
+  int get_batch_state(double *quat, double *pos, double *bias, double *rho, double *ld) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     const Dev &d = dev_;
     if (state_doubles_ > state_host_cap_) {
@@ -1068,11 +822,10 @@ class SolverImpl : public SolverBase {
     return CTVIO_OK;
   }
 
-  int linearize(int id, double *Hpp, double *W, double *Hll, double *g, double *cost) override {
+  int linearize(int id, double *Hpp, double *W, double *Hll, double *g, double *cost) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
     Dev &d = dev_;
-    const int nw = d.nwin, wb = nblk(nw, 64);
     set_params(1);
     launch_initial(opt_.initial_radius, 0);
     const WinMeta &m = meta_[id];
@@ -1102,7 +855,7 @@ class SolverImpl : public SolverBase {
     if (cost) *cost = lm.cost;
     return CTVIO_OK;
   }
-  int cost(int id, double *cost) override {
+  int cost(int id, double *cost) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
     Dev &d = dev_;
@@ -1110,9 +863,7 @@ class SolverImpl : public SolverBase {
     set_params(1);
     hipLaunchKernelGGL(k_lm_init, dim3(wb), dim3(64), 0, stream_, d, opt_.initial_radius, 1);
     hipLaunchKernelGGL(k_knot_prep, dim3(nblk(d.Ktot, 256)), dim3(256), 0, stream_, d);
-    if (d.Gtot) launch_imu_linearize(COST_AT_X);
-    if (d.Atot) hipLaunchKernelGGL(k_vis_anchor, dim3(nblk(d.Atot, 64)), dim3(64), 0, stream_, d, (int)COST_AT_X);
-    if (d.Vtot) hipLaunchKernelGGL(k_vis_eval, dim3(nblk(d.Vtot, 64)), dim3(64), 0, stream_, d, (int)COST_AT_X);
+    launch_evaluate(COST_AT_X);
     hipLaunchKernelGGL(k_misc, dim3(d.nwin), dim3(256), std::max(d.maxPn, 1) * sizeof(double), stream_, d, (int)COST_AT_X, 0, 0);
     hipLaunchKernelGGL(k_initial_cost, dim3(d.nwin), dim3(64), 0, stream_, d, 1);
     Lm lm;
@@ -1123,11 +874,10 @@ class SolverImpl : public SolverBase {
     if (cost) *cost = lm.cand_cost;
     return CTVIO_OK;
   }
-  int lm_step(int id, double mu, double *delta, double *mc) override {
+  int lm_step(int id, double mu, double *delta, double *mc) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
     Dev &d = dev_;
-    const int wb = nblk(d.nwin, 64);
     set_params(1);
     launch_initial(mu, 0);
     HIPCHK(hipMemsetAsync(d.n_active, 0, sizeof(int32_t), stream_));
@@ -1153,7 +903,7 @@ class SolverImpl : public SolverBase {
                   int *stalled = nullptr, bool allow_blocked = false) {
     if (stalled) *stalled = -1;
     Dev &d = dev_;
-    const int nw = d.nwin, wb = nblk(nw, 64);
+    const int nw = d.nwin;
     *too_large = false;
     std::vector<MargMeta> metas((size_t)nw), bmeta;   // bmeta: the blocked windows (k_marginalize sees them with m = n = 0)
     std::vector<int32_t> iscr;
@@ -1303,7 +1053,7 @@ class SolverImpl : public SolverBase {
     bm.status = status;
     return CTVIO_OK;
   }
-  int marginalize_batch(const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) override {
+  int marginalize_batch(const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (!role || !n_keep || !kept || !J0 || !r0 || !(eps >= 0)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     for (int i = 0; i < dev_.Utot; ++i) if (role[i] < -1 || role[i] > 1) return fail(CTVIO_ERR_INVALID, "role must be -1, 0 or 1");
@@ -1318,7 +1068,7 @@ class SolverImpl : public SolverBase {
     return CTVIO_OK;
   }
   // one window; windows beyond the device eigen-solver's size (m or n > MARG_MAXD) take the host path (csrc/marginalize.hpp)
-  int marginalize(int id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) override {
+  int marginalize(int id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
     if (!role || !n_keep || !kept || !J0 || !r0 || !(eps >= 0)) return fail(CTVIO_ERR_INVALID, "bad arguments");
@@ -1364,7 +1114,7 @@ class SolverImpl : public SolverBase {
     return CTVIO_OK;
   }
   // ResidualSummary (reference trajectory_estimator.h:37-59): per-type sums of |r_i| at the current state
-  int residual_summary(int id, double *sums, int32_t *counts4) override {
+  int residual_summary(int id, double *sums, int32_t *counts4) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin || !sums) return fail(CTVIO_ERR_INVALID, "bad arguments");
     const WinMeta &m = meta_[id];
@@ -1379,7 +1129,7 @@ class SolverImpl : public SolverBase {
     if (counts4) { counts4[0] = m.M; counts4[1] = m.NB; counts4[2] = m.V; counts4[3] = m.pn > 0 ? 1 : 0; }
     return CTVIO_OK;
   }
-  int gauge_restore(int n, const int32_t *ids, const int32_t *knot, const double *q0, const double *t0) override {
+  int gauge_restore(int n, const int32_t *ids, const int32_t *knot, const double *q0, const double *t0) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (n < 0 || (n && (!ids || !knot || !q0 || !t0))) return fail(CTVIO_ERR_INVALID, "bad arguments");
     for (int i = 0; i < n; ++i) {
@@ -1402,8 +1152,8 @@ class SolverImpl : public SolverBase {
     HIPCHK(hipGetLastError());
     return CTVIO_OK;
   }
-  int spline_eval(int id, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3, const double *q_SI,
-                  const double *p_SI) override {
+  int spline_eval(int id, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3, const double *q_SI = nullptr,
+                  const double *p_SI = nullptr) {
     SensorExt ext{};
     if (q_SI && p_SI) {
       const double nq = std::sqrt(q_SI[0] * q_SI[0] + q_SI[1] * q_SI[1] + q_SI[2] * q_SI[2] + q_SI[3] * q_SI[3]);
@@ -1414,52 +1164,31 @@ class SolverImpl : public SolverBase {
     }
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (id < 0 || id >= dev_.nwin || n < 0 || (n && !t_ns)) return fail(CTVIO_ERR_INVALID, "bad arguments");
-    if (n == 0) return CTVIO_OK;
-    // grow-only scratch (pinned host mirror): [t_rel n x i64 | err | pose 7n | vel 3n | omega 3n | acc 3n]
-    const size_t o_err = sizeof(long long) * (size_t)n, o_out = o_err + 16;
-    const size_t nd = (size_t)n * ((pose7 ? 7 : 0) + (vel3 ? 3 : 0) + (omega3 ? 3 : 0) + (acc3 ? 3 : 0));
-    if (const int rc = call_scratch(o_out + nd * sizeof(double))) return rc;
-    char *hs = call_host_, *ds = call_dev_.p;
-    long long *rel = reinterpret_cast<long long *>(hs);
-    for (int i = 0; i < n; ++i) rel[i] = (long long)(t_ns[i] - t0_[id]);
-    *reinterpret_cast<int *>(hs + o_err) = 0;
-    HIPCHK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, stream_));
-    HIPCHK(poison(ds + o_out, nd * sizeof(double)));
-    double *dp = reinterpret_cast<double *>(ds + o_out), *dv = dp + (pose7 ? (size_t)7 * n : 0), *dw = dv + (vel3 ? (size_t)3 * n : 0),
-           *da = dw + (omega3 ? (size_t)3 * n : 0);
-    hipLaunchKernelGGL(k_spline_eval, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, id, (const int32_t *)nullptr, n, reinterpret_cast<const long long *>(ds),
-                       pose7 ? dp : nullptr, vel3 ? dv : nullptr, omega3 ? dw : nullptr, acc3 ? da : nullptr, reinterpret_cast<int *>(ds + o_err), ext);
-    HIPCHK(hipMemcpyAsync(hs + o_err, ds + o_err, 16 + nd * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    const int err = *reinterpret_cast<int *>(hs + o_err);
-    const double *ho = reinterpret_cast<const double *>(hs + o_out);
-    if (pose7) { std::memcpy(pose7, ho, sizeof(double) * 7 * n); ho += (size_t)7 * n; }
-    if (vel3) { std::memcpy(vel3, ho, sizeof(double) * 3 * n); ho += (size_t)3 * n; }
-    if (omega3) { std::memcpy(omega3, ho, sizeof(double) * 3 * n); ho += (size_t)3 * n; }
-    if (acc3) std::memcpy(acc3, ho, sizeof(double) * 3 * n);
-    if (err) return fail(CTVIO_ERR_INVALID, "query time outside the spline");
-    return CTVIO_OK;
+    return spline_query(id, nullptr, n, t_ns, pose7, vel3, omega3, acc3, ext, nullptr);
   }
   // Queries of any windows of the batch in ONE launch (query i: window win[i], absolute time t_ns[i]).
   int spline_eval_batch(int64_t n64, const int32_t *win, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
-                        double *kernel_ms) override {
+                        double *kernel_ms) {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || !win))) return fail(CTVIO_ERR_INVALID, "bad arguments");
-    const int n = (int)n64;
     if (kernel_ms) *kernel_ms = 0.0;
+    return spline_query(0, win, (int)n64, t_ns, pose7, vel3, omega3, acc3, SensorExt{}, kernel_ms);
+  }
+  // n queries of window `id` (win == null, as the kernel takes it) or of the windows win[i]
+  int spline_query(int id, const int32_t *win, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
+                   const SensorExt &ext, double *kernel_ms) {
     if (n == 0) return CTVIO_OK;
-    // grow-only scratch (pinned host mirror): [t_rel n x i64 | window n x i32 | err | pose 7n | vel 3n | omega 3n | acc 3n]
-    const size_t o_win = sizeof(long long) * (size_t)n, o_err = (o_win + sizeof(int32_t) * (size_t)n + 15) & ~(size_t)15, o_out = o_err + 16;
+    // grow-only scratch (pinned host mirror): [t_rel n x i64 | window n x i32 (with a window list) | err | pose 7n | vel 3n | omega 3n | acc 3n]
+    const size_t o_win = sizeof(long long) * (size_t)n, o_err = win ? (o_win + sizeof(int32_t) * (size_t)n + 15) & ~(size_t)15 : o_win, o_out = o_err + 16;
     const size_t nd = (size_t)n * ((pose7 ? 7 : 0) + (vel3 ? 3 : 0) + (omega3 ? 3 : 0) + (acc3 ? 3 : 0));
     if (const int rc = call_scratch(o_out + nd * sizeof(double))) return rc;
     char *hs = call_host_, *ds = call_dev_.p;
     long long *rel = reinterpret_cast<long long *>(hs);
     int32_t *hw = reinterpret_cast<int32_t *>(hs + o_win);
     for (int i = 0; i < n; ++i) {
-      if (win[i] < 0 || win[i] >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
-      hw[i] = win[i];
-      rel[i] = (long long)(t_ns[i] - t0_[win[i]]);
+      if (win && (win[i] < 0 || win[i] >= dev_.nwin)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+      if (win) hw[i] = win[i];
+      rel[i] = (long long)(t_ns[i] - t0_[win ? win[i] : id]);
     }
     *reinterpret_cast<int *>(hs + o_err) = 0;
     HIPCHK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, stream_));
@@ -1467,9 +1196,9 @@ class SolverImpl : public SolverBase {
     double *dp = reinterpret_cast<double *>(ds + o_out), *dv = dp + (pose7 ? (size_t)7 * n : 0), *dw = dv + (vel3 ? (size_t)3 * n : 0),
            *da = dw + (omega3 ? (size_t)3 * n : 0);
     if (kernel_ms) HIPCHK(hipEventRecord(ev_[10], stream_));
-    hipLaunchKernelGGL(k_spline_eval, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, 0, reinterpret_cast<const int32_t *>(ds + o_win), n,
+    hipLaunchKernelGGL(k_spline_eval, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, id, win ? reinterpret_cast<const int32_t *>(ds + o_win) : nullptr, n,
                        reinterpret_cast<const long long *>(ds), pose7 ? dp : nullptr, vel3 ? dv : nullptr, omega3 ? dw : nullptr, acc3 ? da : nullptr,
-                       reinterpret_cast<int *>(ds + o_err), SensorExt{});
+                       reinterpret_cast<int *>(ds + o_err), ext);
     if (kernel_ms) HIPCHK(hipEventRecord(ev_[11], stream_));
     HIPCHK(hipMemcpyAsync(hs + o_err, ds + o_err, 16 + nd * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
@@ -1484,18 +1213,16 @@ class SolverImpl : public SolverBase {
     if (err) return fail(CTVIO_ERR_INVALID, "query time outside the spline");
     return CTVIO_OK;
   }
-  int last_timing(double *ms8, int32_t *n8) override {
+  int last_timing(double *ms8, int32_t *n8) {
     if (ms8) std::copy(timing_, timing_ + 8, ms8);
     if (n8) { std::copy(ph_n_, ph_n_ + 7, n8); n8[7] = last_iters_; }
     return CTVIO_OK;
   }
-  int set_profiling(int on) override { profiling_requested_ = on != 0; return CTVIO_OK; }
+  int set_profiling(int on) { profiling_requested_ = on != 0; return CTVIO_OK; }
 
  private:
   ctvio_options opt_;
   const DebugSwitches dbg_;   // environment switches as they were when the handle was created
-  int chol_tiles_ = 3;        // the uploaded batch's factorisation kernel (0 panel kernel, 1 / 3 register tiles): pack_and_upload
-  bool chol_compact_ = false; // panel kernel: its slot-indexed variant (Dev::chol_slots), for windows beyond 591 unknowns: pack_and_upload
   int marg_ran_on_host_ = 0;  // the last ctvio_marginalize(_batch) call: 1 if the factorisation ran on the host
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1509,8 +1236,9 @@ class SolverImpl : public SolverBase {
   std::vector<WinMeta> meta_;
   std::vector<int64_t> t0_;
   Dev dev_;
-  int Mtot_ = 0, Vtot_ = 0;
-  size_t chol_lds_ = 0, vis_lds_ = 0, vis_glb_ = 0, in_bytes_ = 0, state_doubles_ = 0;
+  BatchFacts facts_;         // the uploaded batch as the offset pass saw it (+ its factorisation): what make_plan reads
+  LaunchPlan plan_;          // the launch list of the uploaded batch
+  size_t state_doubles_ = 0;
   Arena in_, work_;          // uploaded inputs (pinned mirror) / device-only work buffers
   WorkerPool pool_;          // the handle's packing threads (created on first use, kept)
   // scratch of the small per-call entries (spline query, gauge restore): grow-only device buffer + pinned host mirror
@@ -1524,23 +1252,6 @@ class SolverImpl : public SolverBase {
     if (!dbg_.poison || bytes < 4) return hipSuccess;
     const uint32_t pattern = dbg_.poison == 2 ? 0x5F5F5F5Fu : 0x7FF8DEADu;
     return hipMemsetD32Async((hipDeviceptr_t)p, (int)pattern, bytes / 4, stream_);
-  }
-  // The upload's staging arena mirrors the device arena byte for byte and is reused: a byte the packer does not write carries the
-  // previous batch to the device.  Packs the batch over 0x00 and over 0xFF and compares every segment's filled extent.
-  template <class Pack> int check_staging(const std::vector<ArenaSeg> &segs, size_t bytes, Pack &&pack) {
-    std::memset(in_.host, 0x00, bytes);
-    pack();
-    const std::vector<char> first(in_.host, in_.host + bytes);
-    std::memset(in_.host, 0xFF, bytes);
-    pack();
-    for (const ArenaSeg &sg : segs) {
-      if (std::memcmp(first.data() + sg.off, in_.host + sg.off, sg.bytes) == 0) continue;
-      size_t i = 0;
-      while (first[sg.off + i] == in_.host[sg.off + i]) ++i;
-      return fail(CTVIO_ERR_INTERNAL, std::string("staging segment ") + sg.name + ": byte " + std::to_string(i) + " of " +
-                                          std::to_string(sg.bytes) + " is not written by the packer");
-    }
-    return CTVIO_OK;
   }
   // a pinned word pair for the "still running" and span-violation polls: the record after the lm_host_cap_ window records
   int32_t *lm_scratch() { return reinterpret_cast<int32_t *>(lm_host_ + lm_host_cap_); }
@@ -1562,59 +1273,21 @@ class SolverImpl : public SolverBase {
   double *snap_ = nullptr;   // state snapshot (inside work_)
   Lm *lm_host_ = nullptr; size_t lm_host_cap_ = 0;
   int graph_captures_ = 0;                // how many times the pass was captured (ctvio_graph_captures: a stream of equal batches captures once)
-  hipGraphExec_t graph_exec_ = nullptr;   // one LM pass (launch_pass) as a graph, valid while dev_ == graph_dev_
+  hipGraphExec_t graph_exec_ = nullptr;   // one LM pass (launch_pass) as a graph, valid while dev_ == graph_dev_ and plan_ == graph_plan_
   Dev graph_dev_;
-  std::vector<long long> graph_sig_;
-  bool deterministic_ = false;   // order-fixed accumulation for this batch (ctvio_options.deterministic)
-  bool wide_fixed_ = false;      // ... and deterministic = 2 with windows beyond the LDS-resident Hessian: k_assemble_wide
+  LaunchPlan graph_plan_;
   double *state_host_ = nullptr; size_t state_host_cap_ = 0;
-  bool snap_valid_ = false, any_vis_lds_ = false, any_vis_glb_ = false, all_windows_have_imu_ = false;
-  int maxK_ = 0, max_schur_tiles_ = 0;
+  bool snap_valid_ = false;
   const double *h_ld_ = nullptr;        // the line delays as uploaded (same arena)
   const int32_t *h_lm_pos_ = nullptr;   // host mirror of Dev::lm_pos (inside in_.host: valid while the batch is uploaded)
 };
 
-void SolverImpl::launch_imu_linearize(int mode) {
-  const Dev &d = dev_;
-  // (at most 2048 waves -- two rounds of one wave per SIMD -- each walking its share of the groups with the next group's data in flight)
-  hipLaunchKernelGGL(k_imu_linearize_f64, dim3(std::min(d.Gtot, imu_walk_waves())), dim3(64), (size_t)(72 * 33 + 64) * sizeof(double), stream_, d, mode, imu_general_only(), imu_zero_mode());
-  hipLaunchKernelGGL(k_imu_linearize_rest, dim3(d.nwin), dim3(64), (size_t)64 * 33 * sizeof(double), stream_, d, mode, imu_general_only(), imu_zero_mode());
-}
-void SolverImpl::launch_assemble_vis_lds(int parts, int mode) {
-  const Dev &d = dev_;
-  hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, true>), dim3(d.nwin, parts), dim3(512), vis_lds_, stream_, d, mode);
-}
-// windows whose packed Hessian does not fit in LDS (K > 25): run products on the MFMA units, added to Hpp with global atomics
-void SolverImpl::launch_assemble_vis_glb(int parts, int mode) {
-  const Dev &d = dev_;
-  hipLaunchKernelGGL((k_assemble_vis_mfma<VCH, false>), dim3(d.nwin, parts), dim3(512), vis_glb_, stream_, d, mode);
-}
-void SolverImpl::launch_schur() {
-  const Dev &d = dev_;
-  // large batches: one workgroup per window, W staged through LDS once; small batches: one wave per 16 x 16 tile (shorter latency, W re-read
-  // per tile).  Every variant also produces the reduced right-hand side (g_rho rides as column P).
-  const int nc = 6 * maxK_ + 2;   // compact columns of W per landmark: knots, line delay, g_rho
-  if (schur_window_path()) {
-    const size_t lds = schur_window_lds();
-    if (16 * nc <= 5 * 512 && max_schur_tiles_ <= 56) hipLaunchKernelGGL((k_schur_window_f64<5, 7>), dim3(d.nwin), dim3(512), lds, stream_, d);
-    else if (16 * nc <= 5 * 512) hipLaunchKernelGGL((k_schur_window_f64<5, 14>), dim3(d.nwin), dim3(512), lds, stream_, d);
-    else hipLaunchKernelGGL((k_schur_window_f64<7, 14>), dim3(d.nwin), dim3(512), lds, stream_, d);
-    return;
-  }
-  const int nt2 = d.maxP / 16 + 1, ntile2 = nt2 * (nt2 + 1) / 2;   // tile rows up to index P (the rhs row)
-  const int nb2 = (nt2 + 1) / 2, nblk2 = nb2 * (nb2 + 1) / 2;      // 32 x 32 blocks of the lower triangle
-  // enough tiles to fill the chip several times over (config 5: 666 per window): one wave per 2 x 2 tiles, half the operand loads
-  // per product; otherwise one wave per tile (more waves in flight).  DebugSwitches::schur_tile2 = 0 / 1 forces the choice (A/B).
-  const int force2 = dbg_.schur_tile2;
-  const bool tile2 = force2 >= 0 ? force2 != 0 : (long long)d.nwin * ntile2 >= 16384;
-  if (tile2) hipLaunchKernelGGL(k_schur_tile2_f64, dim3(nblk2 * 8 * ((d.nwin + 7) / 8)), dim3(64), 0, stream_, d, nblk2);
-  else hipLaunchKernelGGL(k_schur_tile_f64, dim3(ntile2 * 8 * ((d.nwin + 7) / 8)), dim3(64), 0, stream_, d, ntile2);
-}
-
 }  // namespace ctv
 
 // ================================================================================================ C ABI
-struct ctvio_solver { std::unique_ptr<ctv::SolverBase> impl; };
+struct ctvio_solver {
+  ctv::SolverImpl impl;
+};
 
 extern "C" {
 
@@ -1652,62 +1325,60 @@ int32_t ctvio_create(const ctvio_options *opt, ctvio_solver **out) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return ctv::fail(CTVIO_ERR_NO_DEVICE, "hipGetDeviceCount found no device");
   if (o.device < 0 || o.device >= n) return ctv::fail(CTVIO_ERR_INVALID, "device ordinal out of range");
-  std::unique_ptr<ctvio_solver> s(new ctvio_solver);
-  int rc;
   if (o.precision != CTVIO_FP64) return ctv::fail(CTVIO_ERR_INVALID, "precision: only CTVIO_FP64 exists (the mixed fp32 mode was removed: it missed the 1e-4 contract)");
   if (o.use_mfma != 1 && o.use_mfma != 2) return ctv::fail(CTVIO_ERR_INVALID, "use_mfma: 1 or 2 (the vector-ALU cross-check kernels of use_mfma = 0 were removed: the oracle is the cross-check)");
-  { auto *p = new ctv::SolverImpl(o); s->impl.reset(p); rc = p->init(); }
-  if (rc != CTVIO_OK) return rc;
+  std::unique_ptr<ctvio_solver> s(new ctvio_solver{ctv::SolverImpl(o)});
+  if (const int rc = s->impl.init()) return rc;
   *out = s.release();
   return CTVIO_OK;
 }
 void ctvio_destroy(ctvio_solver *s) { delete s; }
 // every entry point: null check, then the solver's device becomes current on this thread -- HIP's current device is per thread
 // (default 0), and a multi-GPU rank that drives several solver handles from worker threads would otherwise launch on device 0
-#define CHK_S if (!s) return ctv::fail(CTVIO_ERR_INVALID, "null solver"); if (int rc_bind_ = s->impl->bind()) return rc_bind_
-int32_t ctvio_clear(ctvio_solver *s) { CHK_S; return s->impl->clear(); }
-int32_t ctvio_add_window(ctvio_solver *s, const ctvio_window *w, int32_t *id) { CHK_S; return s->impl->add_window(w, id); }
-int32_t ctvio_upload(ctvio_solver *s) { CHK_S; return s->impl->upload(); }
-int32_t ctvio_set_batch(ctvio_solver *s, int32_t n, const ctvio_window *wins) { CHK_S; return s->impl->set_batch(n, wins); }
-int32_t ctvio_num_windows(const ctvio_solver *s) { return s ? s->impl->num_windows() : 0; }
-int32_t ctvio_solve(ctvio_solver *s, int32_t max_iterations, ctvio_summary *out) { CHK_S; return s->impl->solve(max_iterations, out); }
+#define CHK_S if (!s) return ctv::fail(CTVIO_ERR_INVALID, "null solver"); if (int rc_bind_ = s->impl.bind()) return rc_bind_
+int32_t ctvio_clear(ctvio_solver *s) { CHK_S; return s->impl.clear(); }
+int32_t ctvio_add_window(ctvio_solver *s, const ctvio_window *w, int32_t *id) { CHK_S; return s->impl.add_window(w, id); }
+int32_t ctvio_upload(ctvio_solver *s) { CHK_S; return s->impl.upload(); }
+int32_t ctvio_set_batch(ctvio_solver *s, int32_t n, const ctvio_window *wins) { CHK_S; return s->impl.set_batch(n, wins); }
+int32_t ctvio_num_windows(const ctvio_solver *s) { return s ? s->impl.num_windows() : 0; }
+int32_t ctvio_solve(ctvio_solver *s, int32_t max_iterations, ctvio_summary *out) { CHK_S; return s->impl.solve(max_iterations, out); }
 int32_t ctvio_get_state(ctvio_solver *s, int32_t id, double *quat, double *pos, double *bias, double *rho, double *ld) {
-  CHK_S; return s->impl->get_state(id, quat, pos, bias, rho, ld);
+  CHK_S; return s->impl.get_state(id, quat, pos, bias, rho, ld);
 }
 int32_t ctvio_get_batch_state(ctvio_solver *s, double *quat, double *pos, double *bias, double *rho, double *ld) {
-  CHK_S; return s->impl->get_batch_state(quat, pos, bias, rho, ld);
+  CHK_S; return s->impl.get_batch_state(quat, pos, bias, rho, ld);
 }
 int32_t ctvio_set_state(ctvio_solver *s, int32_t id, const double *quat, const double *pos, const double *bias, const double *rho, double ld) {
-  CHK_S; return s->impl->set_state(id, quat, pos, bias, rho, ld);
+  CHK_S; return s->impl.set_state(id, quat, pos, bias, rho, ld);
 }
 int32_t ctvio_linearize(ctvio_solver *s, int32_t id, double *Hpp, double *W, double *Hll, double *g, double *cost) {
-  CHK_S; return s->impl->linearize(id, Hpp, W, Hll, g, cost);
+  CHK_S; return s->impl.linearize(id, Hpp, W, Hll, g, cost);
 }
-int32_t ctvio_cost(ctvio_solver *s, int32_t id, double *cost) { CHK_S; return s->impl->cost(id, cost); }
+int32_t ctvio_cost(ctvio_solver *s, int32_t id, double *cost) { CHK_S; return s->impl.cost(id, cost); }
 int32_t ctvio_lm_step(ctvio_solver *s, int32_t id, double mu, double *delta, double *model_cost_change) {
-  CHK_S; return s->impl->lm_step(id, mu, delta, model_cost_change);
+  CHK_S; return s->impl.lm_step(id, mu, delta, model_cost_change);
 }
 int32_t ctvio_marginalize(ctvio_solver *s, int32_t id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
-  CHK_S; return s->impl->marginalize(id, role, eps, n_keep, kept, J0, r0);
+  CHK_S; return s->impl.marginalize(id, role, eps, n_keep, kept, J0, r0);
 }
-int32_t ctvio_residual_summary(ctvio_solver *s, int32_t id, double *sums, int32_t *counts4) { CHK_S; return s->impl->residual_summary(id, sums, counts4); }
+int32_t ctvio_residual_summary(ctvio_solver *s, int32_t id, double *sums, int32_t *counts4) { CHK_S; return s->impl.residual_summary(id, sums, counts4); }
 int32_t ctvio_marginalize_batch(ctvio_solver *s, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
-  CHK_S; return s->impl->marginalize_batch(role, eps, n_keep, kept, J0, r0);
+  CHK_S; return s->impl.marginalize_batch(role, eps, n_keep, kept, J0, r0);
 }
 int32_t ctvio_gauge_restore(ctvio_solver *s, int32_t n, const int32_t *ids, const int32_t *knot, const double *q0, const double *t0) {
-  CHK_S; return s->impl->gauge_restore(n, ids, knot, q0, t0);
+  CHK_S; return s->impl.gauge_restore(n, ids, knot, q0, t0);
 }
 int32_t ctvio_spline_eval(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3) {
-  CHK_S; return s->impl->spline_eval(id, n, t_ns, pose7, vel3, omega3, acc3);
+  CHK_S; return s->impl.spline_eval(id, n, t_ns, pose7, vel3, omega3, acc3);
 }
 int32_t ctvio_spline_eval_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, double *pose7, double *vel3, double *omega3,
                                 double *acc3, double *kernel_ms) {
-  CHK_S; return s->impl->spline_eval_batch(n, win, t_ns, pose7, vel3, omega3, acc3, kernel_ms);
+  CHK_S; return s->impl.spline_eval_batch(n, win, t_ns, pose7, vel3, omega3, acc3, kernel_ms);
 }
 int32_t ctvio_sensor_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *pose7) {
   CHK_S;
   if (!q_SI || !p_SI || (n && !pose7)) return ctv::fail(CTVIO_ERR_INVALID, "ctvio_sensor_pose: null argument");
-  return s->impl->spline_eval(id, n, t_ns, pose7, nullptr, nullptr, nullptr, q_SI, p_SI);
+  return s->impl.spline_eval(id, n, t_ns, pose7, nullptr, nullptr, nullptr, q_SI, p_SI);
 }
 // ---- multi-device host entry: w mod G, one host thread + solver handle per device
 int32_t ctvio_shard_of(int32_t window_id, int32_t n_devices) { return n_devices > 0 ? window_id % n_devices : 0; }
@@ -1857,12 +1528,12 @@ int32_t ctvio_solve_sharded(const ctvio_options *opt, int32_t n_devices, int32_t
   return CTVIO_OK;
 }
 
-int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8) { CHK_S; return s->impl->last_timing(ms8, launches8); }
-int32_t ctvio_snapshot_state(ctvio_solver *s) { CHK_S; return s->impl->snapshot(0); }
-int32_t ctvio_restore_state(ctvio_solver *s) { CHK_S; return s->impl->snapshot(1); }
-int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on) { CHK_S; return s->impl->set_profiling(on); }
-void *ctvio_stream(ctvio_solver *s) { return s ? s->impl->stream() : nullptr; }
-int32_t ctvio_graph_captures(const ctvio_solver *s) { return s ? s->impl->graph_captures() : 0; }
-int32_t ctvio_marginalize_ran_on_host(const ctvio_solver *s) { return s ? s->impl->marg_ran_on_host() : 0; }
+int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8) { CHK_S; return s->impl.last_timing(ms8, launches8); }
+int32_t ctvio_snapshot_state(ctvio_solver *s) { CHK_S; return s->impl.snapshot(0); }
+int32_t ctvio_restore_state(ctvio_solver *s) { CHK_S; return s->impl.snapshot(1); }
+int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on) { CHK_S; return s->impl.set_profiling(on); }
+void *ctvio_stream(ctvio_solver *s) { return s ? s->impl.stream() : nullptr; }
+int32_t ctvio_graph_captures(const ctvio_solver *s) { return s ? s->impl.graph_captures() : 0; }
+int32_t ctvio_marginalize_ran_on_host(const ctvio_solver *s) { return s ? s->impl.marg_ran_on_host() : 0; }
 
 }  // extern "C"

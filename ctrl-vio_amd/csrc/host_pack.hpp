@@ -436,4 +436,318 @@ inline void active_mask(const ctvio_window *w, const PackTmp &t, int P, const in
   if (w->fix_ld) act[P - 1] = 0;
 }
 
+// ---------------------------------------------------------------------------------------- the batch: offsets, input arena, fill
+// What the serial offset pass gathers about a batch: the totals the arenas are sized by and the maxima the launch list is chosen by.
+struct BatchFacts {
+  int32_t nw, K0, F0, L0, M0, V0, B0, U0, Pp0, pv0, pb, G0, I0, A0, TR0;   // sums over the windows (V0: block slots incl. padding)
+  int64_t H0, W0, pH0;
+  int32_t maxN, maxP, maxPn, maxL, maxLdw, maxK, maxK_lds, maxSpan, maxSchurTiles, maxSlots;   // maxK_lds: over the LDS-resident windows
+  // (a window whose packed Hessian does not fit in LDS counts as "global" even without visual blocks -- e.g. an IMU-only predict of a
+  // long spline: the store-semantics tail only finishes LDS-resident windows, so such a batch must take the accumulate path)
+  bool any_vis_lds, any_vis_glb, all_imu;
+  bool walk;                               // the row walk of the order-fixed wide-window assembly is uploaded (vrow, vrow_off)
+  size_t vis_lds_bytes, vis_glb_bytes;     // dynamic LDS of the visual assembly kernels
+  // the factorisation of the batch, set by the upload (the choice steers the planning: dense envelope, slot count)
+  int32_t chol_tiles;
+  bool chol_compact;
+  size_t chol_lds;
+};
+
+// One segment of an arena layout: name, byte offset, the bytes a batch fills (CTVIO_POISON checks and poisons these extents); dbl: the
+// segment holds doubles that may be poisoned (integer segments never are: they feed addresses).
+struct ArenaSeg {
+  const char *name;
+  size_t off, bytes;
+  bool dbl;
+};
+inline size_t arena_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// The input arena (pinned host mirror + device), every segment ONCE: X(element type, segment, Dev member, allocated count, filled count).
+// An empty set keeps one entry allocated.  The names stand for BatchFacts members (layout_input).  Irregular: `state` is the contiguous
+// block quat | pos | bias | rho | ld (StatePtrs); vrow / vrow_off hold one unused entry unless the row walk is uploaded, and Dev gets null.
+#define CTV_INPUT_SEGMENTS(X)                                                                          \
+  X(WinMeta, meta, wins, nw, nw)                                                                       \
+  X(double, state, quat, 7 * K0 + 6 * F0 + L0 + nw, 7 * K0 + 6 * F0 + L0 + nw)                         \
+  X(int32_t, knot_win, knot_win, K0, K0) X(int32_t, bias_win, bias_win, F0, F0) X(int32_t, lm_win, lm_win, L0, L0) \
+  X(ImuGroup, groups, groups, G0, G0) X(int32_t, imu_grp, imu_grp, Mt, M0)                             \
+  X(double, imu_u, imu_u, Mt, M0) X(double, imu_meas, imu_meas, 6 * Mt, 6 * M0)                        \
+  X(int32_t, v_win, v_win, Vt, V0) X(int32_t, v_lm, v_lm, Vt, V0) X(int32_t, v_anc, v_anc, Vt, V0) X(int32_t, v_rowj, v_rowj, Vt, V0) \
+  X(int64_t, v_tj, v_tj, Vt, V0) X(double, v_obs, v_obs, 2 * Vt, 2 * V0)                               \
+  X(double, v_cauchy, v_cauchy, Vt, V0) X(int32_t, vb_win, vb_win, Vt / 64 + 1, V0 / 64)               \
+  X(int32_t, a_win, a_win, At, A0) X(int32_t, a_lm, a_lm, At, A0) X(int32_t, a_row, a_row, At, A0)     \
+  X(int64_t, a_t, a_t, At, A0) X(double, a_obs, a_obs, 2 * At, 2 * A0)                                 \
+  X(VisItem, vitems, vitems, std::max<size_t>(I0, 1), I0) X(int32_t, vblk, vblk, Vt, V0) X(int32_t, vblk_anc, vblk_anc, Vt, V0) \
+  X(int32_t, bc_win, bc_win, B0, B0) X(int32_t, bc_i, bc_i, B0, B0) X(int32_t, bc_j, bc_j, B0, B0) X(double, bc_w, bc_w, 6 * B0, 6 * B0) \
+  X(double, pJ0, pJ0, pH0, pH0) X(double, pr0, pr0, pv0, pv0)                                          \
+  X(double, pH, pH, pH0, pH0) X(double, pb0, pb0, pv0, pv0) X(double, pc0, pc0, nw, nw) X(double, p_x0, p_x0, 4 * pb, 4 * pb) \
+  X(int32_t, pcol, pcol, pv0, pv0) X(int32_t, p_kind, p_kind, pb, pb) X(int32_t, p_index, p_index, pb, pb) X(int32_t, p_off, p_off, pb, pb) \
+  X(int32_t, pinv, pinv, Pp0, Pp0) X(int32_t, bgl_off, bgl_off, F0 + nw, F0 + nw) X(int32_t, bgl, bgl, std::max<size_t>(G0, 1), G0) \
+  X(uint8_t, active, active, U0, U0)                                                                   \
+  X(int32_t, lm_pos, lm_pos, L0, L0) X(int32_t, lm_at, lm_at, L0, L0) X(int32_t, lm_klo, lm_klo, L0, L0) X(int32_t, lm_khi, lm_khi, L0, L0) \
+  X(int32_t, tl_beg, tl_beg, TR0, TR0) X(int32_t, tl_end, tl_end, TR0, TR0) X(int32_t, env_first, env_first, TR0, TR0) X(int32_t, env_tile, env_tile, TR0, TR0) \
+  /* the walk of the order-fixed wide-window assembly (deterministic = 2 with a window beyond the LDS-resident Hessian; else not uploaded) */ \
+  X(int32_t, vrow, vrow, walk ? Vt : 1, walk ? V0 : 0) X(int32_t, vrow_off, vrow_off, walk ? L0 + nw : 1, walk ? L0 + nw : 0)
+
+#define CTV_X(type, name, member, alloc, used) +1
+constexpr int INPUT_NSEG = 0 CTV_INPUT_SEGMENTS(CTV_X);
+#undef CTV_X
+
+// One typed pointer per input segment: into the host mirror (the packer fills these) or into the device arena (Dev gets these).
+struct InputPtrs {
+#define CTV_X(type, name, member, alloc, used) type *name;
+  CTV_INPUT_SEGMENTS(CTV_X)
+#undef CTV_X
+};
+// The contiguous state block quat | pos | bias | rho | ld of a batch (the input segment `state`; cstate and snap in the work arena).
+struct StatePtrs {
+  double *quat, *pos, *bias, *rho, *ld;
+  StatePtrs(double *p, const BatchFacts &b) : quat(p), pos(quat + (size_t)4 * b.K0), bias(pos + (size_t)3 * b.K0), rho(bias + (size_t)6 * b.F0), ld(rho + b.L0) {}
+};
+
+struct InputLayout {
+  ArenaSeg segs[INPUT_NSEG];   // in list order (the extents of the segments, named, without their alignment tails)
+  size_t bytes;
+  InputPtrs at(char *base) const {
+    InputPtrs p;
+    int i = 0;
+#define CTV_X(type, name, member, alloc, used) p.name = reinterpret_cast<type *>(base + segs[i++].off);
+    CTV_INPUT_SEGMENTS(CTV_X)
+#undef CTV_X
+    return p;
+  }
+};
+inline InputLayout layout_input(const BatchFacts &b) {
+  const size_t nw = b.nw, K0 = b.K0, F0 = b.F0, L0 = b.L0, M0 = b.M0, V0 = b.V0, B0 = b.B0, U0 = b.U0, Pp0 = b.Pp0, pv0 = b.pv0, pb = b.pb, G0 = b.G0,
+               I0 = b.I0, A0 = b.A0, TR0 = b.TR0, pH0 = (size_t)b.pH0;
+  const size_t Mt = std::max<size_t>(M0, 1), Vt = std::max<size_t>(V0, 1), At = std::max<size_t>(A0, 1);
+  const bool walk = b.walk;
+  InputLayout l;
+  size_t off = 0;
+  int i = 0;
+#define CTV_X(type, name, member, alloc, used)                                    \
+  l.segs[i++] = ArenaSeg{#name, off, sizeof(type) * (size_t)(used), false};       \
+  off += arena_align(sizeof(type) * (size_t)(alloc));
+  CTV_INPUT_SEGMENTS(CTV_X)
+#undef CTV_X
+  l.bytes = off;
+  return l;
+}
+
+// The serial offset pass (prefix sums) after the planning: every window's WinMeta and relative time origin, and the batch's facts.
+// need_slots: the batch takes the slot-indexed panel Cholesky (its slot count is gathered); vis_stage: the staging bytes of the visual
+// assembly beside its LDS Hessian (kernels_assemble.hpp: vis_stage_bytes); wide_walk: deterministic = 2 (a batch with a window beyond
+// the LDS-resident Hessian then uploads the row walk).
+inline BatchFacts batch_offsets(const std::vector<const ctvio_window *> &wins, const std::vector<PackTmp> &tmp, bool need_slots, size_t vis_stage,
+                                bool wide_walk, std::vector<WinMeta> &meta, std::vector<int64_t> &t0) {
+  const int nw = (int)wins.size();
+  meta.assign(nw, WinMeta());
+  t0.resize(nw);
+  BatchFacts b;
+  std::memset(&b, 0, sizeof b);
+  b.nw = nw; b.maxSpan = 1;
+  b.vis_lds_bytes = b.vis_glb_bytes = vis_stage;
+  b.all_imu = nw > 0;
+  for (int wi = 0; wi < nw; ++wi) {
+    const ctvio_window &w = *wins[wi];
+    WinMeta &m = meta[wi];
+    t0[wi] = w.t0_ns;
+    m.K = w.K; m.F = w.F; m.L = w.L; m.M = w.M; m.NB = w.NB; m.V = w.V;
+    m.P = 6 * w.K + 6 * w.F + 1; m.N = m.P + w.L; m.pn = w.pn; m.pnb = w.pnb;
+    m.knot0 = b.K0; m.bias0 = b.F0; m.lm0 = b.L0; m.imu0 = b.M0; m.vis0 = b.V0; m.bc0 = b.B0; m.u0 = b.U0; m.p0 = b.Pp0;
+    m.grp0 = b.G0; m.ngrp = tmp[wi].ngrp; m.vitem0 = b.I0; m.nvitem = tmp[wi].nvitem; m.Vp = tmp[wi].Vp;
+    m.anc0 = b.A0; m.A = tmp[wi].A;
+    m.tr0 = b.TR0; m.ntr = tmp[wi].ntr; m.Lobs = tmp[wi].Lobs; b.TR0 += tmp[wi].ntr; b.maxSpan = std::max(b.maxSpan, tmp[wi].max_span);
+    m.ldw = (m.P + 1 + 31) / 32 * 32; m.Lpad = std::max(2, (w.L + 1) / 2 * 2);
+    m.pv0 = b.pv0; m.pblk0 = b.pb; m.fix_ld = w.fix_ld; m.lock_bg = w.lock_bg; m.lock_ba = w.lock_ba; m.fixed_upto = w.fixed_upto;
+    m.H0 = b.H0; m.W0 = b.W0; m.pH0 = b.pH0; m.ldh = (m.P + 15) / 16 * 16; m.dt_ns = w.dt_ns; m.inv_dt = 1e9 / (double)w.dt_ns;
+    for (int i = 0; i < 4; ++i) m.q_CI[i] = w.q_CI[i];
+    for (int i = 0; i < 3; ++i) { m.p_CI[i] = w.p_CI[i]; m.gravity[i] = w.gravity[i]; }
+    for (int i = 0; i < 6; ++i) m.imu_w[i] = w.imu_w[i];
+    m.img_w = w.img_w; m.cauchy_a = w.cauchy_a; m.ld_lo = w.ld_lo; m.ld_hi = w.ld_hi;
+    {
+      const size_t K6 = 6 * (size_t)w.K, nG = K6 + 1, nH = K6 * (K6 + 1) / 2 + K6 + 1 + nG;
+      const size_t need = ((nH + 3) & ~(size_t)3) * sizeof(double) + 32 + vis_stage;   // fp64 accumulators in LDS
+      const size_t need_glb = ((nG + 3) & ~(size_t)3) * sizeof(double) + 16 + vis_stage;
+      m.vis_lds = need <= 160 * 1024 ? 1 : 0;
+      if (m.vis_lds) { b.any_vis_lds = true; b.maxK_lds = std::max(b.maxK_lds, w.K); } else b.any_vis_glb = true;
+      b.vis_lds_bytes = std::max(b.vis_lds_bytes, m.vis_lds ? need : need_glb);
+      b.vis_glb_bytes = std::max(b.vis_glb_bytes, need_glb);
+    }
+    if (m.ngrp == 0) b.all_imu = false;
+    b.K0 += w.K; b.F0 += w.F; b.L0 += w.L; b.M0 += w.M; b.V0 += m.Vp; b.B0 += w.NB; b.U0 += m.N; b.Pp0 += m.P; b.pv0 += w.pn; b.pb += w.pnb;
+    b.G0 += m.ngrp; b.I0 += m.nvitem; b.A0 += m.A;
+    b.H0 += (int64_t)m.P * m.ldh; b.W0 += (int64_t)m.Lpad * m.ldw; b.pH0 += (int64_t)w.pn * w.pn;
+    b.maxN = std::max(b.maxN, m.N); b.maxP = std::max(b.maxP, m.P); b.maxPn = std::max(b.maxPn, w.pn);
+    b.maxL = std::max(b.maxL, m.L); b.maxLdw = std::max(b.maxLdw, m.ldw); b.maxK = std::max(b.maxK, m.K);
+    if (need_slots) b.maxSlots = std::max(b.maxSlots, chol_panel_slots(tmp[wi].env_first.data(), m.P));
+    {   // 16 x 16 tiles of the reduced system that receive Schur products (k_schur_window_f64): knot columns, line delay, rhs row
+      const int ntl = m.ldw / 16, K6 = 6 * m.K;
+      int cnt = 0;
+      for (int ti = 0; ti < ntl; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
+          const bool nzr = (16 * ti < K6) || (m.P >= 16 * ti && m.P - 1 < 16 * ti + 16);
+          const bool nzc = (16 * tj < K6) || (m.P - 1 >= 16 * tj && m.P - 1 < 16 * tj + 16);
+          cnt += (nzr && nzc) ? 1 : 0;
+        }
+      b.maxSchurTiles = std::max(b.maxSchurTiles, cnt);
+    }
+  }
+  b.walk = wide_walk && b.any_vis_glb;
+  return b;
+}
+
+// Second pass: window wi fills its own slices of every input segment (h: the host mirror's pointers).
+inline void fill_window(const ctvio_window &w, int wi, const WinMeta &m, const PackTmp &t, const BatchFacts &b, const InputPtrs &h, int vch) {
+  const size_t Mt = (size_t)std::max(b.M0, 1), Vt = (size_t)std::max(b.V0, 1), At = (size_t)std::max(b.A0, 1);
+  const StatePtrs st(h.state, b);
+  std::memcpy(st.quat + (size_t)4 * m.knot0, w.quat, sizeof(double) * 4 * w.K);
+  std::memcpy(st.pos + (size_t)3 * m.knot0, w.pos, sizeof(double) * 3 * w.K);
+  std::memcpy(st.bias + (size_t)6 * m.bias0, w.bias, sizeof(double) * 6 * w.F);
+  if (w.L) std::memcpy(st.rho + m.lm0, w.rho, sizeof(double) * w.L);
+  st.ld[wi] = w.fix_ld ? w.ld : std::min(std::max(w.ld, w.ld_lo), w.ld_hi);   // Ceres IterationZero: project on the feasible set
+  std::fill(h.knot_win + m.knot0, h.knot_win + m.knot0 + w.K, wi);
+  std::fill(h.bias_win + m.bias0, h.bias_win + m.bias0 + w.F, wi);
+  std::fill(h.lm_win + m.lm0, h.lm_win + m.lm0 + w.L, wi);
+  if (w.L) {   // sparsity plan: rows of W in sorted landmark order and their knot spans
+    std::memcpy(h.lm_pos + m.lm0, t.lm_pos.data(), 4 * (size_t)w.L); std::memcpy(h.lm_at + m.lm0, t.lm_at.data(), 4 * (size_t)w.L);
+    std::memcpy(h.lm_klo + m.lm0, t.row_klo.data(), 4 * (size_t)w.L); std::memcpy(h.lm_khi + m.lm0, t.row_khi.data(), 4 * (size_t)w.L);
+  }
+  std::memcpy(h.tl_beg + m.tr0, t.tl_beg.data(), 4 * (size_t)m.ntr); std::memcpy(h.tl_end + m.tr0, t.tl_end.data(), 4 * (size_t)m.ntr);
+  std::memcpy(h.env_first + m.tr0, t.env_first.data(), 4 * (size_t)m.ntr); std::memcpy(h.env_tile + m.tr0, t.env_tile.data(), 4 * (size_t)m.ntr);
+  if (b.walk) {
+    plan_row_walk(&w, t, h.vrow + m.vis0, h.vrow_off + m.lm0 + wi);
+    std::fill(h.vrow + m.vis0 + w.V, h.vrow + m.vis0 + m.Vp, 0);   // (unused tail of the window's list)
+  }
+  // IMU samples in (segment, bias) order; groups = runs of equal (segment, bias)
+  int g = m.grp0 - 1;
+  for (int i = 0; i < w.M; ++i) {
+    const int src = t.iorder[i];
+    if (i == 0 || t.iseg[src] != t.iseg[t.iorder[i - 1]] || w.imu_bias[src] != w.imu_bias[t.iorder[i - 1]])
+      h.groups[++g] = ImuGroup{wi, t.iseg[src], w.imu_bias[src], i, 0, m.knot0 + t.iseg[src], m.bias0 + w.imu_bias[src], m.imu0 + i};
+    h.groups[g].count++;
+    const size_t e = (size_t)m.imu0 + i;
+    h.imu_grp[e] = g;
+    const int64_t st_ns = w.imu_t[src] - w.t0_ns;
+    const double uu = (double)(st_ns % w.dt_ns) / (double)w.dt_ns;
+    h.imu_u[e] = (double)uu;
+    for (int c = 0; c < 3; ++c) {
+      h.imu_meas[(size_t)c * Mt + e] = (double)w.imu_gyro[3 * src + c];
+      h.imu_meas[(size_t)(3 + c) * Mt + e] = (double)w.imu_acc[3 * src + c];
+    }
+  }
+  // anchors (the i ends, landmark-major) and visual blocks: evaluation slots in landmark-major order (padding slots: window -1,
+  // harmless values)
+  for (int a = 0; a < m.A; ++a) {
+    const int v = t.anc_rep[a];
+    const size_t e = (size_t)m.anc0 + a;
+    h.a_win[e] = wi; h.a_lm[e] = w.v_lm[v]; h.a_row[e] = w.v_rowi[v]; h.a_t[e] = w.v_ti[v] - w.t0_ns;
+    h.a_obs[e] = w.v_pi[2 * v]; h.a_obs[At + e] = w.v_pi[2 * v + 1];
+  }
+  std::fill(h.vb_win + m.vis0 / 64, h.vb_win + (m.vis0 + m.Vp) / 64, wi);
+  for (int i = 0; i < m.Vp; ++i) {
+    const int v = t.lord[i];
+    const size_t e = (size_t)m.vis0 + i;
+    if (v < 0) {
+      h.v_win[e] = -1; h.v_lm[e] = 0; h.v_anc[e] = m.anc0; h.v_tj[e] = 0; h.v_rowj[e] = 0; h.v_cauchy[e] = 0.0;
+      for (int c = 0; c < 2; ++c) h.v_obs[(size_t)c * Vt + e] = 0.0;
+      continue;
+    }
+    h.v_win[e] = wi; h.v_lm[e] = w.v_lm[v]; h.v_anc[e] = m.anc0 + t.anc_of[v];
+    h.v_tj[e] = w.v_tj[v] - w.t0_ns;
+    h.v_rowj[e] = w.v_rowj[v];
+    h.v_obs[e] = (double)w.v_pj[2 * v]; h.v_obs[Vt + e] = (double)w.v_pj[2 * v + 1];
+    h.v_cauchy[e] = w.v_cauchy ? w.v_cauchy[v] : w.cauchy_a;
+  }
+  // the assembly's items: <= vch blocks of one frame pair, frame-pair order, as lists of slots (vblk)
+  int it = m.vitem0 - 1;
+  for (int i = 0; i < w.V; ++i) {
+    const int v = t.vord[i];
+    const bool fresh = (i == 0) || w.v_ti[v] != w.v_ti[t.vord[i - 1]] || w.v_tj[v] != w.v_tj[t.vord[i - 1]] || h.vitems[it].count >= vch;
+    if (fresh) h.vitems[++it] = VisItem{m.vis0 + i, 0};
+    h.vitems[it].count++;
+    h.vblk[(size_t)m.vis0 + i] = m.vis0 + t.vpos[v];
+    h.vblk_anc[(size_t)m.vis0 + i] = m.anc0 + t.anc_of[v];
+  }
+  for (int i = w.V; i < m.Vp; ++i) { h.vblk[(size_t)m.vis0 + i] = m.vis0; h.vblk_anc[(size_t)m.vis0 + i] = m.anc0; }   // (unused tail of the window's list)
+  for (int k = 0; k < w.NB; ++k) { h.bc_win[m.bc0 + k] = wi; h.bc_i[m.bc0 + k] = w.bc_i[k]; h.bc_j[m.bc0 + k] = w.bc_j[k]; }
+  if (w.NB) std::memcpy(h.bc_w + (size_t)6 * m.bc0, w.bc_w, sizeof(double) * 6 * w.NB);
+  // prior: J0^T J0 (row-major n*n), J0^T r0, r0^T r0 in fp64; J0 is column-major (Eigen)
+  const int n = w.pn;
+  h.pc0[wi] = 0.0;
+  int32_t *col = h.pcol + m.pv0;
+  if (n > 0) {
+    for (int k = 0; k < w.pnb; ++k) {
+      const int kind = w.p_kind[k], idx = w.p_index[k];
+      int u0 = 0;
+      switch (kind) {
+        case CTVIO_PK_ROT: u0 = 6 * idx; break;
+        case CTVIO_PK_POS: u0 = 6 * idx + 3; break;
+        case CTVIO_PK_BG: u0 = 6 * w.K + 6 * idx; break;
+        case CTVIO_PK_BA: u0 = 6 * w.K + 6 * idx + 3; break;
+        default: u0 = m.P - 1;
+      }
+      for (int c = 0; c < prior_block_size(kind); ++c) col[w.p_off[k] + c] = u0 + c;
+    }
+    double *pH = h.pH + m.pH0, *pb0 = h.pb0 + m.pv0;
+    std::memcpy(h.pJ0 + m.pH0, w.pJ0, sizeof(double) * (size_t)n * n);
+    std::memcpy(h.pr0 + m.pv0, w.pr0, sizeof(double) * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+      const double *Ji = w.pJ0 + (size_t)i * n;
+      double bi = 0;
+      for (int r = 0; r < n; ++r) bi += Ji[r] * w.pr0[r];
+      pb0[i] = bi;
+      for (int j = 0; j <= i; ++j) {
+        const double *Jj = w.pJ0 + (size_t)j * n;
+        double s = 0;
+        for (int r = 0; r < n; ++r) s += Ji[r] * Jj[r];
+        pH[(size_t)i * n + j] = s; pH[(size_t)j * n + i] = s;
+      }
+    }
+    double c0 = 0;
+    for (int r = 0; r < n; ++r) c0 += w.pr0[r] * w.pr0[r];
+    h.pc0[wi] = c0;
+    std::memcpy(h.p_kind + m.pblk0, w.p_kind, 4 * (size_t)w.pnb); std::memcpy(h.p_index + m.pblk0, w.p_index, 4 * (size_t)w.pnb);
+    std::memcpy(h.p_off + m.pblk0, w.p_off, 4 * (size_t)w.pnb); std::memcpy(h.p_x0 + (size_t)4 * m.pblk0, w.p_x0, 8 * 4 * (size_t)w.pnb);
+  }
+  active_mask(&w, t, m.P, col, h.active + m.u0);
+  // inverse column map of the prior, and the IMU groups of every bias state (group order) -- read by the store-semantics assembly
+  std::fill(h.pinv + m.p0, h.pinv + m.p0 + m.P, -1);
+  for (int i = 0; i < n; ++i) h.pinv[m.p0 + col[i]] = i;
+  {
+    int32_t *off = h.bgl_off + m.bias0 + wi;
+    std::fill(off, off + w.F + 1, 0);
+    for (int gi = 0; gi < m.ngrp; ++gi) off[h.groups[m.grp0 + gi].bias + 1]++;
+    for (int f = 0; f < w.F; ++f) off[f + 1] += off[f];
+    std::vector<int32_t> fill(off, off + w.F);
+    for (int gi = 0; gi < m.ngrp; ++gi) h.bgl[m.grp0 + fill[h.groups[m.grp0 + gi].bias]++] = m.grp0 + gi;
+    for (int f = 0; f <= w.F; ++f) off[f] += m.grp0;   // absolute positions in bgl
+  }
+}
+
+// The whole batch into the mirror at `base` (laid out by layout_input): the window records, then every window's slices over the pool.
+inline void pack_input(const std::vector<const ctvio_window *> &wins, const std::vector<PackTmp> &tmp, const std::vector<WinMeta> &meta, const BatchFacts &b,
+                       const InputLayout &lay, char *base, int vch, WorkerPool &pool, int nthreads) {
+  const InputPtrs h = lay.at(base);
+  std::memcpy(h.meta, meta.data(), sizeof(WinMeta) * meta.size());
+  pool.run((int)wins.size(), nthreads, [&](int wi) { fill_window(*wins[wi], wi, meta[wi], tmp[wi], b, h, vch); });
+}
+
+// The staging arena mirrors the device arena byte for byte and is reused: a byte the packer does not write carries the previous batch
+// to the device.  Packs the batch over 0x00 and over 0xFF (pack() fills `base`) and compares every segment's filled extent; returns the
+// complaint, empty when every byte of every segment comes from the batch.
+template <class Pack> inline std::string check_staging(const InputLayout &lay, char *base, Pack &&pack) {
+  std::memset(base, 0x00, lay.bytes);
+  pack();
+  const std::vector<char> first(base, base + lay.bytes);
+  std::memset(base, 0xFF, lay.bytes);
+  pack();
+  for (const ArenaSeg &sg : lay.segs) {
+    if (std::memcmp(first.data() + sg.off, base + sg.off, sg.bytes) == 0) continue;
+    size_t i = 0;
+    while (first[sg.off + i] == base[sg.off + i]) ++i;
+    return std::string("staging segment ") + sg.name + ": byte " + std::to_string(i) + " of " + std::to_string(sg.bytes) + " is not written by the packer";
+  }
+  return std::string();
+}
+
 }  // namespace ctv

@@ -500,7 +500,7 @@ __device__ __forceinline__ bool imu_group_fast(const Dev &d, int gidx) {
 // The groups the fast body leaves out are picked up by k_imu_linearize_rest (one wave per WINDOW: its lanes look at the window's groups,
 // the wave then takes the flagged ones in turn -- 12 us per launch when there is nothing to do, which is the rule): the two bodies in
 // one kernel cost the fast one registers.
-// (general_only: every group through the general body -- ctvio_options.use_mfma = 2 / CTVIO_IMU_GENERAL=1, the tests' way into it)
+// (general_only: every group through the general body -- ctvio_options.use_mfma = 2, the tests' way into it)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_imu_linearize_f64(Dev d, int mode, int general_only, int zero_mode) {
   extern __shared__ __attribute__((aligned(32))) unsigned char smraw[];
   if (!general_only) imu_linearize_f64_fast(d, mode, reinterpret_cast<double *>(smraw), blockIdx.x, gridDim.x, zero_mode);   // (skips the groups that are not its own)
