@@ -78,7 +78,7 @@ struct LmParams {
 // Device pointers of one batch (all arithmetic is fp64, like the reference's).
 struct Dev {
   int32_t nwin, Ktot, Ftot, Ltot, Mtot, Gtot, Vtot, NBtot, Utot, maxN, maxP, maxPn;
-  int32_t schur_plain_in_H;   // k_schur_window_f64 left the 16 x 16 tiles without Schur products unwritten: k_cholesky_tiles forms them from Hpp + D itself
+  int32_t schur_plain_in_H;   // k_schur_window_f64 left the 16 x 16 tiles without Schur products unwritten: the tile Cholesky (k_cholesky_flow) forms them from Hpp + D itself (kernels_solve.hpp: SchurTiles)
   const WinMeta *wins;
   // state, fp64 master copies: current and candidate
   double *quat, *pos, *bias, *rho, *ld;
@@ -135,7 +135,7 @@ struct Dev {
   // tiles: empty), and env_first: the first tile column of tile row c inside the ENVELOPE of the reduced system S (and of its Cholesky factor:
   // fill stays inside the row envelope) -- tiles (r, c < env_first[r]) are structurally zero: not formed, not stored, not multiplied.
   const int32_t *tl_beg, *tl_end, *env_first;
-  const int32_t *env_tile;         // the raw (unaligned) tile envelope, also for batches whose env_first is the whole triangle: k_cholesky_tiles skips empty tiles' products
+  const int32_t *env_tile;         // the raw (unaligned) tile envelope, also for batches whose env_first is the whole triangle: k_cholesky_flow skips empty tiles' products
   double *grs;                     // [Ltot] g_rho by ROW (written with dinv by begin_iteration): the Schur kernels stream rows, not landmarks
   int32_t *span_viol;              // device counter: an evaluation fell outside its landmark's planned span (never, unless the plan is wrong)
   int32_t max_span6, pad_ms;       // 6 x the widest landmark span of the batch (knot columns): LDS row width of k_vis_eval

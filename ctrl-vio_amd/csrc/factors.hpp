@@ -32,7 +32,7 @@ struct SegConstLazy {
   CTV_DI M3 jri(int i) const {
     M3 J;
 #pragma unroll
-    for (int e = 0; e < 9; ++e) J.m[e] = (double)tab[9 * i + e];
+    for (int e = 0; e < 9; ++e) J.m[e] = tab[9 * i + e];
     return J;
   }
 };
@@ -45,7 +45,7 @@ struct SegConstS {
 };
 CTV_DI void seg_const_lazy(const double *kd, const double *kjri, SegConstLazy &sc) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) sc.d[i] = mk((double)kd[3 * i], (double)kd[3 * i + 1], (double)kd[3 * i + 2]);
+  for (int i = 0; i < 3; ++i) sc.d[i] = mk(kd[3 * i], kd[3 * i + 1], kd[3 * i + 2]);
   sc.tab = kjri;
 }
 CTV_DI void seg_const(const Knots4 &k, SegConst &sc, bool want_jac) {
@@ -71,10 +71,10 @@ CTV_DI void knot_pair_const(const double *qa, const double *qb, double *d3, doub
 CTV_DI void seg_const_load(const double *kd, const double *kjri, SegConst &sc, bool want_jac) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    sc.d[i] = mk((double)kd[3 * i], (double)kd[3 * i + 1], (double)kd[3 * i + 2]);
+    sc.d[i] = mk(kd[3 * i], kd[3 * i + 1], kd[3 * i + 2]);
     if (want_jac) {
 #pragma unroll
-      for (int e = 0; e < 9; ++e) sc.JrI[i].m[e] = (double)kjri[9 * i + e];
+      for (int e = 0; e < 9; ++e) sc.JrI[i].m[e] = kjri[9 * i + e];
     }
   }
 }

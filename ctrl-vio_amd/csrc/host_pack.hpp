@@ -291,7 +291,7 @@ inline int vis_segment(const ctvio_window *w, int64_t t, int row, double ld) {
 //     state), a bias-chain link, the prior (all its columns mutually), or a landmark (its span's knots mutually, and each with the line delay);
 //     Cholesky fill stays inside the row envelope, so tiles (r, c < env_first[r]) are never formed, stored or multiplied.  dense = true (batches
 //     whose factorisation keeps the whole triangle in registers: P <= 223) sets env_first = 0 -- every tile is formed and loaded -- and leaves
-//     the raw tile envelope in env_tile, by which k_cholesky_tiles skips the PRODUCTS of empty tiles; full_ranges widens every non-empty row
+//     the raw tile envelope in env_tile, by which k_cholesky_flow skips the PRODUCTS of empty tiles; full_ranges widens every non-empty row
 //     range to all observed rows and drops the envelope (the dense cross-check).
 inline void plan_sparsity(const ctvio_window *w, bool dense, bool full_ranges, PackTmp &t) {
   const int K = w->K, F = w->F, L = w->L, V = w->V, K6 = 6 * K, P = K6 + 6 * F + 1;
@@ -370,7 +370,7 @@ inline void plan_sparsity(const ctvio_window *w, bool dense, bool full_ranges, P
     // tile row reaches at least the panel before its own 32-row block (so that the next diagonal block always takes part in a panel's
     // trailing update: its look-ahead relies on that).  The tiles this adds hold zeros.
     int ft = f / 16;
-    t.env_tile[r] = ft;                                        // the envelope as it is (k_cholesky_tiles skips the products of empty tiles)
+    t.env_tile[r] = ft;                                        // the envelope as it is (k_cholesky_flow skips the products of empty tiles)
     if (r >= 2) ft = std::min(ft, 2 * (r / 2) - 2);
     t.env_first[r] = (dense || r < 2) ? 0 : (ft & ~1);
   }
@@ -629,10 +629,10 @@ inline void fill_window(const ctvio_window &w, int wi, const WinMeta &m, const P
     h.imu_grp[e] = g;
     const int64_t st_ns = w.imu_t[src] - w.t0_ns;
     const double uu = (double)(st_ns % w.dt_ns) / (double)w.dt_ns;
-    h.imu_u[e] = (double)uu;
+    h.imu_u[e] = uu;
     for (int c = 0; c < 3; ++c) {
-      h.imu_meas[(size_t)c * Mt + e] = (double)w.imu_gyro[3 * src + c];
-      h.imu_meas[(size_t)(3 + c) * Mt + e] = (double)w.imu_acc[3 * src + c];
+      h.imu_meas[(size_t)c * Mt + e] = w.imu_gyro[3 * src + c];
+      h.imu_meas[(size_t)(3 + c) * Mt + e] = w.imu_acc[3 * src + c];
     }
   }
   // anchors (the i ends, landmark-major) and visual blocks: evaluation slots in landmark-major order (padding slots: window -1,
@@ -655,7 +655,7 @@ inline void fill_window(const ctvio_window &w, int wi, const WinMeta &m, const P
     h.v_win[e] = wi; h.v_lm[e] = w.v_lm[v]; h.v_anc[e] = m.anc0 + t.anc_of[v];
     h.v_tj[e] = w.v_tj[v] - w.t0_ns;
     h.v_rowj[e] = w.v_rowj[v];
-    h.v_obs[e] = (double)w.v_pj[2 * v]; h.v_obs[Vt + e] = (double)w.v_pj[2 * v + 1];
+    h.v_obs[e] = w.v_pj[2 * v]; h.v_obs[Vt + e] = w.v_pj[2 * v + 1];
     h.v_cauchy[e] = w.v_cauchy ? w.v_cauchy[v] : w.cauchy_a;
   }
   // the assembly's items: <= vch blocks of one frame pair, frame-pair order, as lists of slots (vblk)

@@ -1,5 +1,6 @@
 // kernels.hpp -- gfx950 kernels of the sliding-window solve (all fp64).  One launch covers a whole batch of windows.  This header holds
-// what the kernels share (linearisation modes, column maps, knot loading) and includes the sections in order:
+// what the kernels share (linearisation modes, the LDS sync / clock-stamp / opaque-zero idioms, column maps, knot loading) and includes the
+// sections in order:
 //
 //   kernels_control.hpp   k_lm_init, k_initial_cost, k_pass_end (gradient norm, cost, Ceres 1.14 accept / reject / terminate / Armijo, set
 //                         swap, next iteration's damping), k_zero_normal (only for batches with an IMU-less window), k_knot_prep (d =
@@ -11,9 +12,11 @@
 //                         g_rho formed in the same kernel), k_linearize_f64 (IMU + visual in one launch for small batches)
 //   kernels_assemble.hpp  k_assemble_vis_mfma (MFMA + fp64 LDS Hessian, or global atomics for K > 25; STORE = the order-fixed tail of the
 //                         deterministic mode with k_reduce_finalize / k_bias_rows), k_misc
-//                         (IMU tiles' bias rows + bias chain + prior), k_post_linearize (first linearisation only)
-//   kernels_solve.hpp     k_begin_iter, k_schur_window_f64 (large batches) / k_schur_tile_f64 (small; both also produce the reduced rhs),
-//                         k_cholesky_tiles (register-resident 16 x 16 tiles; k_cholesky_solve =
+//                         (IMU tiles' bias rows + bias chain + prior), k_post_linearize (first linearisation only); for the windows whose
+//                         packed Hessian is not LDS resident under deterministic = 2: k_vis_expand, k_assemble_wide, k_bias_rows_wide
+//   kernels_solve.hpp     k_begin_iter, k_schur_window_f64 (large batches) / k_schur_tile_f64, k_schur_tile2_f64 (small; all also produce the
+//                         reduced rhs), k_cholesky_flow (P <= 223: register-resident 16 x 16 tiles as a data-flow of waves; k_cholesky_tiles =
+//                         its barrier-per-panel form, kept as the timing-independent twin the tests compare it with; k_cholesky_solve =
 //                         panel kernel for P > 223), k_step_finish (back-substitution, candidate x (+) alpha delta, its knot-pair table)
 //   kernels_query.hpp     k_gauge_restore (double2vector), k_residual_summary, k_spline_eval (trajectory queries)
 #pragma once
@@ -51,6 +54,37 @@ __device__ __forceinline__ double readlane_d(double x, int lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// A wave-uniform zero the compiler cannot see through (an SGPR written by an opaque s_mov): added to an index or an address, it makes
+// the result depend on this point of the program, so that it is recomputed here instead of being hoisted and kept live -- or spilled --
+// across a loop or a phase.  Each use says what it keeps from being hoisted.
+__device__ __forceinline__ int opaque_zero() {
+  int z;
+  asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+  return z;
+}
+
+// LDS hand-over between lanes: wait for this wave's LDS traffic, then meet the other lanes.  The s_waitcnt immediate used here (and
+// by the few waits without a barrier) is the gfx9 encoding of lgkmcnt (bits 11:8) = 0 with vmcnt (15:14, 3:0) and expcnt (6:4) at their
+// maxima: "every LDS and scalar-memory operation of this wave has completed; outstanding global loads and stores are not waited for" --
+// the wait for those is what __syncthreads() would add.
+__device__ __forceinline__ void lds_wave_sync() {    // the lanes of one wave (the barrier only pins the compiler's ordering)
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ void lds_block_sync() {   // the waves of one workgroup
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_s_barrier();
+}
+
+// CTVIO_DEBUG_STAMPS (Dev::dbg, null otherwise): the lane that satisfies `lane_cond` writes clock64() to stamps[idx++], at most `cap`
+// slots per kernel.  An optional fifth argument is a double the stamp is made to depend on (x * 0.0 is not folded without fast-math),
+// so that the clock is read after the value is complete and not wherever the scheduler finds room.
+#define CTV_STAMP(stamps, idx, cap, lane_cond, ...)                                                        \
+  do {                                                                                                     \
+    if ((stamps) && (lane_cond) && (idx) < (cap))                                                          \
+      (stamps)[(idx)++] = clock64() __VA_OPT__(+ (long long)((__VA_ARGS__) * 0.0));                        \
+  } while (0)
+
 // local column -> unknown index maps
 __device__ __forceinline__ int imu_col(int c, int s, int K, int bias) {
   if (c < 12) return 6 * (s + c / 3) + c % 3;
@@ -71,12 +105,12 @@ __device__ __forceinline__ void load_knots(const double *quat, const double *pos
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const double *q = quat + 4 * (k0 + i), *p = pos + 3 * (k0 + i);
-    k.q[i] = qmk((double)q[0], (double)q[1], (double)q[2], (double)q[3]);
-    k.p[i] = mk((double)(p[0] - origin[0]), (double)(p[1] - origin[1]), (double)(p[2] - origin[2]));
+    k.q[i] = qmk(q[0], q[1], q[2], q[3]);
+    k.p[i] = mk(p[0] - origin[0], p[1] - origin[1], p[2] - origin[2]);
   }
 }
 
-// Knots k0..k0+3 in the local frame of the reference knot `kref` (fp64 arithmetic, then cast):
+// Knots k0..k0+3 in the local frame of the reference knot `kref`:
 //   q'_k = q_ref^-1 q_k (near identity), p'_k = R_ref^T (p_k - p_ref).
 struct LocalFrame {
   Q4 qref_inv;
@@ -96,22 +130,12 @@ struct LocalFrame {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const double *q = quat + 4 * (k0 + i), *p = pos + 3 * (k0 + i);
-      const Q4 ql = qmul_raw(qref_inv, qmk(q[0], q[1], q[2], q[3]));   // unit x unit: no renormalisation in fp64
-      const V3 pl = mul(RT, mk(p[0] - o[0], p[1] - o[1], p[2] - o[2]));
-      k.q[i] = qmk((double)ql.x, (double)ql.y, (double)ql.z, (double)ql.w);
-      k.p[i] = mk((double)pl.x, (double)pl.y, (double)pl.z);
+      k.q[i] = qmul_raw(qref_inv, qmk(q[0], q[1], q[2], q[3]));   // unit x unit: no renormalisation in fp64
+      k.p[i] = mul(RT, mk(p[0] - o[0], p[1] - o[1], p[2] - o[2]));
     }
   }
-  __device__ __forceinline__ V3 rotate(const double *v) const {  // R_ref^T v
-    const V3 r = mul(RT, mk(v[0], v[1], v[2]));
-    return mk((double)r.x, (double)r.y, (double)r.z);
-  }
-  __device__ __forceinline__ M3 RrefT() const {
-    M3 r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.m[i] = (double)RT.m[i];
-    return r;
-  }
+  __device__ __forceinline__ V3 rotate(const double *v) const { return mul(RT, mk(v[0], v[1], v[2])); }  // R_ref^T v
+  __device__ __forceinline__ M3 RrefT() const { return RT; }
 };
 
 }  // namespace ctv

@@ -179,9 +179,9 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
       for (int q = 0; q < 9; ++q) {
         const int e = lane + 64 * q, a = e / 24, b = e % 24;
         const int ga = imu_col(a, gs_[u], K, gb_[u]), gb = imu_col(b, gs_[u], K, gb_[u]);
-        if (ga >= gb) atomicAdd(&Hs[ga * (ga + 1) / 2 + gb], (double)tv[u][q]);
+        if (ga >= gb) atomicAdd(&Hs[ga * (ga + 1) / 2 + gb], tv[u][q]);
       }
-      if (STORE && lane < 24) atomicAdd(&Hs[nHh + imu_col(lane, gs_[u], K, gb_[u])], (double)tgv[u]);   // (gs = Hs + nHh)
+      if (STORE && lane < 24) atomicAdd(&Hs[nHh + imu_col(lane, gs_[u], K, gb_[u])], tgv[u]);   // (gs = Hs + nHh)
     }
   }
   double *Js = stage + wave * SROWS * CHP;
@@ -196,9 +196,8 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
   const int sc = lane % CH, srr = lane / CH;                               // staging: column (block) and row parity of this lane
   long long *dbg = (d.dbg && w == (d.nwin > 1000 ? 1000 : 0) && part == 0) ? d.dbg + 48 : nullptr;
   int dbi = 0;
-#define CTV_STAMP() do { if (dbg && tid == 0 && dbi < 15) dbg[dbi++] = clock64(); } while (0)
   if (dbg && tid == 0) dbg[dbi++] = t_begin;
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 15, tid == 0);
   // MFMA operand row offsets of this lane: tile row I -> knot column 16 I + l15, at k = q4 (block bsel of the pair, residual
   // row rr).  The line-delay column (staged rows 98, 99) and the residual (rows 100, 101) ride on the same operand
   // values with plain FMAs: every lane multiplies its three J entries by J_ld[k] and r[k] of its own k; the four k
@@ -311,22 +310,22 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
           double hv = acc[q][rg];
           if (gA == gB && ca != cb) hv *= 2.0;
           const bool ge = gA >= gB;
-          if (LDSH) atomicAdd(&Hs[(ge ? trow[I][rg] : tcol[J]) + (ge ? gB : gA)], (double)hv);
-          else atomicAdd(&Hg[(long long)(ge ? gA : gB) * ldh + (ge ? gB : gA)], (double)hv);
+          if (LDSH) atomicAdd(&Hs[(ge ? trow[I][rg] : tcol[J]) + (ge ? gB : gA)], hv);
+          else atomicAdd(&Hg[(long long)(ge ? gA : gB) * ldh + (ge ? gB : gA)], hv);
         }
       }
     // line-delay row of the Hessian and the pose gradient (every k group holds the totals; group q4 = 0 adds them)
     if (q4 == 0) {
 #pragma unroll
       for (int J = 0; J < 3; ++J) {
-        if (LDSH) atomicAdd(&Hs[tri + gcol[J]], (double)pl[J]);
-        else atomicAdd(&Hg[(long long)(P - 1) * ldh + gcol[J]], (double)pl[J]);
-        atomicAdd(&gs[gcol[J]], (double)pr[J]);
+        if (LDSH) atomicAdd(&Hs[tri + gcol[J]], pl[J]);
+        else atomicAdd(&Hg[(long long)(P - 1) * ldh + gcol[J]], pl[J]);
+        atomicAdd(&gs[gcol[J]], pr[J]);
       }
       if (l15 == 0) {   // (ld, ld) and r . J_ld
-        if (LDSH) atomicAdd(&Hs[tri + K6], (double)pll);
-        else atomicAdd(&Hg[(long long)(P - 1) * ldh + (P - 1)], (double)pll);
-        atomicAdd(&gs[K6], (double)prl);
+        if (LDSH) atomicAdd(&Hs[tri + K6], pll);
+        else atomicAdd(&Hg[(long long)(P - 1) * ldh + (P - 1)], pll);
+        atomicAdd(&gs[K6], prl);
       }
     }
   };
@@ -361,7 +360,7 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
       Js[(24 + 48 * side + rem) * CHP + sc] = side ? -(cv * pv) : cv * pv;
     }
     __builtin_amdgcn_wave_barrier();
-    if (r < 2) CTV_STAMP();
+    if (r < 2) CTV_STAMP(dbg, dbi, 15, tid == 0);
     fetch(r + 1);
     int start = 0;
     while (start < ncur) {
@@ -412,14 +411,14 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
           prl += rv[s] * ldv[s];
         }
       }
-      if (r < 2) CTV_STAMP();
+      if (r < 2) CTV_STAMP(dbg, dbi, 15, tid == 0);
       start = end;
     }
-    if (r < 2) CTV_STAMP();
+    if (r < 2) CTV_STAMP(dbg, dbi, 15, tid == 0);
   }
   if (asi >= 0) scatter(asi, asj);
   __syncthreads();
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 15, tid == 0);
   // IMU group tiles: the knot x knot part (24 x 24 per group, overlapping between consecutive segments); without the LDS
   // Hessian k_assemble_imu adds them
   for (int gi = part * NW + wave + NGI * per_round; LDSH && gi < ngrp; gi += per_round) {   // groups beyond the prefetched ones
@@ -432,12 +431,12 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
     for (int u = 0; u < 9; ++u) {
       const int e = lane + 64 * u, a = e / 24, b = e % 24;
       const int ga = imu_col(a, grp.s, K, grp.bias), gb = imu_col(b, grp.s, K, grp.bias);
-      if (ga >= gb) atomicAdd(&Hs[ga * (ga + 1) / 2 + gb], (double)tv[u]);
+      if (ga >= gb) atomicAdd(&Hs[ga * (ga + 1) / 2 + gb], tv[u]);
     }
-    if (STORE && lane < 24) atomicAdd(&gs[imu_col(lane, grp.s, K, grp.bias)], (double)tile[lane * 32 + 30]);
+    if (STORE && lane < 24) atomicAdd(&gs[imu_col(lane, grp.s, K, grp.bias)], tile[lane * 32 + 30]);
   }
   __syncthreads();
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 15, tid == 0);
   if constexpr (STORE) {
     if (nparts > 1) {   // this part's packed Hessian + gradient: summed with the others, in part order, by k_reduce_finalize
       double *dst = d.Hpart + ((size_t)w * nparts + part) * d.npart_stride;
@@ -476,13 +475,12 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
       else Hg[(long long)ga * ldh + gb] = hv;  // first writer after k_zero_normal; later kernels add atomically
     }
   }
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 15, tid == 0);
   for (int i = tid; i < K6 + 1; i += NT) {
     const double gv = gs[i];
     if (gv != 0.0) atomicAdd(&d.gS[tgset][u0 + (i < K6 ? i : P - 1)], gv);
   }
-  CTV_STAMP();
-#undef CTV_STAMP
+  CTV_STAMP(dbg, dbi, 15, tid == 0);
 }
 
 // Bias rows of the single-part store-semantics assembly: grid (blocks, windows).

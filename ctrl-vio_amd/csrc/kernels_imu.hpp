@@ -108,8 +108,7 @@ __device__ __forceinline__ void imu_linearize_f64_body(const Dev &d, int mode, d
       __builtin_amdgcn_wave_barrier();   // the previous phase's operand reads are complete (consumed by its MFMAs)
 #pragma unroll
       for (int c = 0; c < 32; ++c) A[lane * 33 + c] = row[c];
-      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the rows are in LDS
-      __builtin_amdgcn_wave_barrier();
+      lds_wave_sync();   // the rows are in LDS
       for (int k0 = 0; k0 < kmax; k0 += 4) {
         const double lo = A[(k0 + q4) * 33 + l15], hi = A[(k0 + q4) * 33 + 16 + l15];
         acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(lo, lo, acc00, 0, 0, 0);
@@ -125,8 +124,7 @@ __device__ __forceinline__ void imu_linearize_f64_body(const Dev &d, int mode, d
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int c = 0; c < 16; ++c) A[lane * 17 + c] = row[c];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
+      lds_wave_sync();
       for (int k0 = 0; k0 < kmax; k0 += 4) {
         const double v = A[(k0 + q4) * 17 + l15];
         gacc = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, gacc, 0, 0, 0);
@@ -147,8 +145,7 @@ __device__ __forceinline__ void imu_linearize_f64_body(const Dev &d, int mode, d
     A[(16 + row) * 32 + col] = acc10[r];
     A[col * 32 + 16 + row] = acc10[r];     // mirror of the off-diagonal tile
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();
   {
     const int tc = l15 < 12 ? l15 : (l15 < 15 ? l15 + 12 : 30);
 #pragma unroll
@@ -158,8 +155,7 @@ __device__ __forceinline__ void imu_linearize_f64_body(const Dev &d, int mode, d
       A[tr * 32 + tc] += gacc[r];
     }
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();
   double *tile = d.imu_tiles + (size_t)gidx * 1024;
 #pragma unroll
   for (int i = 0; i < 16; ++i) tile[i * 64 + lane] = A[i * 64 + lane];
@@ -300,8 +296,7 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
   }
   long long *dbg = (d.dbg && gidx == 5000 && jac) ? d.dbg + 64 : nullptr;   // CTVIO_DEBUG_STAMPS: clock64 of lane 0 at the phase boundaries
   int dbi = 0;
-#define CTV_ISTAMP(x) do { if (dbg && lane == 0 && dbi < 16) dbg[dbi++] = clock64() + (long long)((x) * 0.0); } while (0)
-  CTV_ISTAMP(0.0);
+  CTV_STAMP(dbg, dbi, 16, lane == 0);
   double *gc = A + 72 * 33;   // (8 spare rows behind the 64: the chains' last prefetch)
   {
     double gcv = cur.kq;      // lanes 21..35: gravity, bias, weights as requested
@@ -315,8 +310,7 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     }
     __builtin_amdgcn_wave_barrier();
     if (lane < 36) gc[lane] = gcv;
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
+    lds_wave_sync();
   }
   const double idt = readlane_d(cur.kq, 36);
   double csum = 0.0;
@@ -342,7 +336,7 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
   f64x4 acc00 = {0.0, 0.0, 0.0, 0.0}, acc10 = {0.0, 0.0, 0.0, 0.0}, gacc = {0.0, 0.0, 0.0, 0.0};
   double spp[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int c0 = 0; c0 < grp.count; c0 += 64) {
-    CTV_ISTAMP(csum);
+    CTV_STAMP(dbg, dbi, 16, lane == 0, csum);
     const int nval = min(64, grp.count - c0);
     const bool live = lane < nval;
     double gy[3], ac[3], r[6];
@@ -367,11 +361,11 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     imu_eval_values3(gc, sc, u, idt, gy, ac, wl, r, md);
 #pragma unroll
     for (int i = 0; i < 6; ++i) csum += 0.5 * r[i] * r[i];   // (dead lanes: zero weights, zero residual)
-    CTV_ISTAMP(csum);
+    CTV_STAMP(dbg, dbi, 16, lane == 0, csum);
     {
       M3 Jw[4];
       imu_jac_gyro3(md, sc, Jw);
-      CTV_ISTAMP(Jw[3].m[8]);
+      CTV_STAMP(dbg, dbi, 16, lane == 0, Jw[3].m[8]);
 #pragma unroll
       for (int a = 0; a < 3; ++a) {   // unrolled: the row index must be static
         double row[16];
@@ -379,16 +373,15 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
         __builtin_amdgcn_wave_barrier();   // the previous phase's operand reads are complete (consumed by its MFMAs)
 #pragma unroll
         for (int c = 0; c < 16; ++c) A[lane * 17 + c] = row[c];
-        __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the rows are in LDS
-        __builtin_amdgcn_wave_barrier();
+        lds_wave_sync();   // the rows are in LDS
         imu_chain_gyro(A, q4, l15, kmax, gacc);
       }
     }
-    CTV_ISTAMP(gacc[0]);
+    CTV_STAMP(dbg, dbi, 16, lane == 0, gacc[0]);
     {
       M3 Ja[4], Rinv_g;
       imu_jac_accel3(md, sc, gc, Ja, Rinv_g);
-      CTV_ISTAMP(Ja[3].m[8] + Rinv_g.m[8]);
+      CTV_STAMP(dbg, dbi, 16, lane == 0, Ja[3].m[8] + Rinv_g.m[8]);
       {
         double la[4];
 #pragma unroll
@@ -406,13 +399,12 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int c = 0; c < 28; ++c) A[lane * 33 + c] = row[c];   // (columns 28..31 feed accumulator rows nobody reads)
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
+        lds_wave_sync();
         imu_chain_accel(A, q4, l15, kmax, acc00, acc10);
       }
     }
   }
-  CTV_ISTAMP(acc00[0] + acc10[0]);
+  CTV_STAMP(dbg, dbi, 16, lane == 0, acc00[0] + acc10[0]);
   // ---- combine in LDS into the full symmetric 32 x 32 tile in the local column order [rot 12 | pos 12 | bg 3 | ba 3 | r | -]
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -425,8 +417,7 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
 #pragma unroll
     for (int e = 0; e < 10; ++e) S[e * 64 + lane] = spp[e];
     S[10 * 64 + lane] = csum;
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
+    lds_wave_sync();
     const int e = min(lane >> 2, 10), part = lane & 3;
     double t = 0.0;
 #pragma unroll
@@ -437,8 +428,7 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     if (lane < 40 && part == 0) S[704 + e] = t;
     if (lane == 40) d.imu_cost[gidx] = t;
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();
   {
     // T0 (accelerometer rows: rot 12 | ba 3 | r) and the gyro tile (rot 12 | bg 3 | r) share the accumulator layout: where neither index
     // is a bias one the two land on the same entry and are added in registers; a bias index sends them to the ba / bg columns
@@ -459,21 +449,18 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     const int hi = max(ka, kb), lo = min(ka, kb);
     if (lane < 48) A[(12 + 3 * ka + b) * 32 + 12 + 3 * kb + b] = A[1024 + 704 + hi * (hi + 1) / 2 + lo];
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();
   double *tile = d.imu_tiles + (size_t)gidx * 1024;
 #pragma unroll
   for (int i = 0; i < 8; ++i)   // 16 bytes per lane: 8 stores of 1 KiB (under load a store costs ~100 cycles whatever its width)
     *reinterpret_cast<double2 *>(tile + i * 128 + 2 * lane) = *reinterpret_cast<const double2 *>(A + i * 128 + 2 * lane);
   // (last: the memory counter is in-order, a load issued after these stores would wait for their acknowledgement)
   imu_zero_share(d, mode, grp, gidx, zero_mode);
-  CTV_ISTAMP(0.0);
-#undef CTV_ISTAMP
+  CTV_STAMP(dbg, dbi, 16, lane == 0);
   } while (false);
   // ---- on to the wave's next group
   if (!has_next) break;
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();          // (the tile copy-out has read the LDS buffer before the next group writes its constants)
+  lds_wave_sync();   // (the tile copy-out has read the LDS buffer before the next group writes its constants)
   if (!nmeas) {                             // this group left early: the next one's first pass has not been asked for yet
     const int idx = grpn.iabs + min(lane, grpn.count - 1);
 #pragma unroll
@@ -515,8 +502,7 @@ __device__ __forceinline__ void imu_rest_body(const Dev &d, int mode, int genera
       const int b = __ffsll((long long)todo) - 1;
       todo &= todo - 1;
       imu_linearize_f64_body(d, mode, reinterpret_cast<double *>(smraw), m.grp0 + g0 + b, zero_mode);
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
+      lds_wave_sync();
     }
   }
 }
@@ -550,7 +536,7 @@ __device__ __forceinline__ void assemble_imu_window(const Dev &d, int mode, int 
       } else { a = t - 165; b = 30; }
       // (the tile is symmetric: the gradient column is read as row 30, next to the bias rows -- 7 consecutive rows of the tile instead of a
       //  cache line of every row)
-      const double v = (double)(b == 30 ? tile[30 * 32 + a] : tile[a * 32 + b]);
+      const double v = b == 30 ? tile[30 * 32 + a] : tile[a * 32 + b];
       const int ga = imu_col(a, grp.s, K, grp.bias);
       if (b == 30) { atomicAdd(&g[ga], v); continue; }
       const int gb = imu_col(b, grp.s, K, grp.bias);
@@ -598,7 +584,7 @@ __device__ __forceinline__ void assemble_imu_window(const Dev &d, int mode, int 
         const int r = q < 1 ? 0 : q < 3 ? 1 : q < 6 ? 2 : q < 10 ? 3 : q < 15 ? 4 : 5;
         a = 24 + r; b = 24 + q - r * (r + 1) / 2;
       } else { a = t - 165; b = 30; }
-      const double v = (double)(b == 30 ? tile[30 * 32 + a] : tile[a * 32 + b]);
+      const double v = b == 30 ? tile[30 * 32 + a] : tile[a * 32 + b];
       const int ga = imu_col(a, grp.s, K, grp.bias);
       if (b == 30) { atomicAdd(&g[ga], v); continue; }
       const int gb = imu_col(b, grp.s, K, grp.bias);
@@ -611,7 +597,7 @@ __device__ __forceinline__ void assemble_imu_window(const Dev &d, int mode, int 
     const ImuGroup grp = d.groups[m.grp0 + gi];
     const double *tile = d.imu_tiles + (size_t)(m.grp0 + gi) * 1024;
     const int b = e / 30, a = e % 30;  // a < 30 : unknown row; b <= 30
-    const double v = (double)tile[a * 32 + b];
+    const double v = tile[a * 32 + b];
     const int ga = imu_col(a, grp.s, K, grp.bias);
     if (b == 30) { atomicAdd(&g[ga], v); continue; }
     const int gb = imu_col(b, grp.s, K, grp.bias);

@@ -86,9 +86,9 @@ __global__ __launch_bounds__(256) void k_residual_summary(Dev d, int w, double *
     double b[6], wgt[6], gy[3], ac[3], r[6];
     const double *bp = d.bias + 6 * (m.bias0 + grp.bias);
     for (int c = 0; c < 6; ++c) { b[c] = bp[c]; wgt[c] = m.imu_w[c]; }
-    for (int c = 0; c < 3; ++c) { gy[c] = (double)d.imu_meas[(size_t)c * d.Mtot + idx]; ac[c] = (double)d.imu_meas[(size_t)(3 + c) * d.Mtot + idx]; }
+    for (int c = 0; c < 3; ++c) { gy[c] = d.imu_meas[(size_t)c * d.Mtot + idx]; ac[c] = d.imu_meas[(size_t)(3 + c) * d.Mtot + idx]; }
     ImuJac J;
-    imu_eval_core(k, sc, (double)d.imu_u[idx], m.inv_dt, lf.rotate(m.gravity), b, gy, ac, wgt, lf.RrefT(), r, false, J);
+    imu_eval_core(k, sc, d.imu_u[idx], m.inv_dt, lf.rotate(m.gravity), b, gy, ac, wgt, lf.RrefT(), r, false, J);
     for (int c = 0; c < 6; ++c) atomicAdd(&sums[c], fabs(r[c]));
   }
   for (int e = tid; e < m.NB * 6; e += 256) {
@@ -126,8 +126,8 @@ __global__ __launch_bounds__(256) void k_residual_summary(Dev d, int w, double *
     vis_anchor_eval<false>(gi.q[0], gi.p, sci, ui, m.inv_dt, q_CI, p_CI, d.a_obs[a], d.a_obs[(size_t)d.Atot + a], (double)rowi,
                            d.rho[m.lm0 + d.v_lm[v]], false, rec);
     VisNullSink sink;
-    vis_block_eval<false>(rec, gj.q[0], gj.p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, -1.0 /* raw residual */, (double)d.v_obs[v],
-                          (double)d.v_obs[(size_t)d.Vtot + v], (double)rowj, r, false, sink);
+    vis_block_eval<false>(rec, gj.q[0], gj.p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, -1.0 /* raw residual */, d.v_obs[v],
+                          d.v_obs[(size_t)d.Vtot + v], (double)rowj, r, false, sink);
     atomicAdd(&sums[12], fabs(r[0]));
     atomicAdd(&sums[13], fabs(r[1]));
   }

@@ -1,5 +1,6 @@
 // kernels_solve.hpp -- The step: begin_iteration / k_begin_iter, Schur complement (k_schur_window_f64, k_schur_tile_f64, k_schur_tile2_f64), Cholesky
-// (k_cholesky_tiles register-resident, k_cholesky_solve panel kernel), k_step_finish (back-substitution, candidate, its pair table).
+// (k_cholesky_flow register-resident tiles, k_cholesky_tiles its barrier-per-panel twin, k_cholesky_solve panel kernel), k_step_finish
+// (back-substitution, candidate, its pair table).
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 #pragma once
 
@@ -59,6 +60,18 @@ __device__ __forceinline__ void tile_decode(int t, int &bi, int &bj) {  // t -> 
   bj = t - bi * (bi + 1) / 2;
 }
 
+// WHICH 16 x 16 TILES OF THE REDUCED SYSTEM HAVE SCHUR PRODUCTS.  W is non-zero only in the knot columns [0, 6K) and the line-delay column P - 1,
+// and the appended g_rho column P makes the tile row that holds index P produce the reduced rhs: tile (ti, tj) has products when its row tile
+// and its column tile both hold such a column: nz_row(ti) && nz_col(tj).  This one predicate is a contract between two kernels: with Dev::schur_plain_in_H,
+// k_schur_window_f64 leaves every tile WITHOUT products unwritten in S, and the tile Cholesky kernels (k_cholesky_flow, k_cholesky_tiles) form
+// exactly those tiles from Hpp + D themselves.  A classification that differed between the two would make the Cholesky read memory nobody wrote.
+struct SchurTiles {
+  const int &K6, &P;   // 6 K and P of the window, by reference like the closures this replaces: held by value, or as free functions, the
+                       // same text compiled to other code in five kernels (tools/isa_diff.py)
+  __device__ bool nz_row(int b) const { return (16 * b < K6) || (P >= 16 * b && P - 1 < 16 * b + 16); }
+  __device__ bool nz_col(int b) const { return (16 * b < K6) || (P - 1 >= 16 * b && P - 1 < 16 * b + 16); }
+};
+
 // Rows of W (sorted landmark order) that can be non-zero in BOTH the columns of tile row bi and those of tile column bj: the intersection of the
 // host's per-tile ranges (host_pack.hpp: plan_sparsity); the tile row that holds index P carries g_rho on its A side for EVERY observed row.
 // Tiles over bias-only columns come out empty.
@@ -104,13 +117,12 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
   // W is non-zero only in the knot columns [0, 6K) and the line-delay column P - 1 (plus the rhs row P): a tile has products
   // when its row tile and its column tile both hold such a column.  Those tiles (55 of 105 at K = 24) are listed and dealt to
   // the waves; the others only need the epilogue (S = Hpp + D).
-  auto nz_row = [&](int b) { return (16 * b < K6) || (P >= 16 * b && P - 1 < 16 * b + 16); };
-  auto nz_col = [&](int b) { return (16 * b < K6) || (P - 1 >= 16 * b && P - 1 < 16 * b + 16); };
+  const SchurTiles tiles{K6, P};
   __syncthreads();   // tcount
   for (int t = tid; t < ntile; t += 512) {
     int ti, tj;
     tile_decode(t, ti, tj);
-    if (nz_row(ti) && nz_col(tj)) { const int pos = atomicAdd(&tcount, 1); if (pos < 8 * NTQ) tlist[pos] = (ti << 8) | tj; }
+    if (tiles.nz_row(ti) && tiles.nz_col(tj)) { const int pos = atomicAdd(&tcount, 1); if (pos < 8 * NTQ) tlist[pos] = (ti << 8) | tj; }
   }
   // Only the knot columns [0, 6K), the line-delay column P - 1 and the appended g_rho column P are fetched and staged (NC
   // compact columns per landmark); every other column of the two LDS buffers is zeroed once and stays zero.
@@ -153,8 +165,7 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
   const int nact = min(tcount, 8 * NTQ);
   long long *dbg = (d.dbg && w == (d.nwin > 1000 ? 1000 : 0)) ? d.dbg + 96 : nullptr;   // CTVIO_DEBUG_STAMPS: clock64 of thread 0 at the phase boundaries
   int dbi = 0;
-#define CTV_STAMP() do { if (dbg && tid == 0 && dbi < 30) dbg[dbi++] = clock64(); } while (0)
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   // this wave's tiles: slot q holds list entry wave + 8 q; slots past the end repeat the wave's first tile (products computed,
   // result dropped) so that the tile loop below has no branches and the operand reads of a tile overlap the previous products
   int tij[NTQ];
@@ -174,8 +185,7 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
   // instead of costing the epilogue a global round trip per tile, and S = -(acc) + D needs no second operand there.
   const double *H = d.HppS[d.lm[w].cur] + m.H0;
   f64x4 acc[NTQ];
-  int opq;   // (a zero the compiler cannot see through: otherwise the row / column indices computed here are kept -- spilled -- for the epilogue)
-  asm volatile("s_mov_b32 %0, 0" : "=s"(opq));
+  const int opq = opaque_zero();   // (otherwise the row / column indices computed here are kept -- spilled -- for the epilogue)
 #pragma unroll
   for (int q = 0; q < NTQ; ++q) {
     const int tq = (tij[q] & 0xffff) + opq, jc = min(16 * (tq & 255) + l15, P - 1);
@@ -188,7 +198,7 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
   }
   if (nchunk > 0) { fetch(0); stash(0, 0); }
   __syncthreads();
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   for (int ch = 0; ch < nchunk && nact > 0; ++ch) {
     const int buf = ch & 1;
     if (ch + 1 < nchunk) fetch(ch + 1);
@@ -216,7 +226,7 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
     if (ch + 1 < nchunk) stash(ch + 1, buf ^ 1);
     __syncthreads();
   }
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   // epilogue: S = Hpp - W^T Hll^-1 W + D on the active lower triangle, identity rows for fixed unknowns; rhs row.  The per-column vectors
   // come from LDS, read before any branch (pin) so that the compiler does not sink each read into a branch of its own.
   double *S = d.S + m.H0, *rhs = d.rhs + m.p0;
@@ -250,20 +260,20 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
     for (int r = 0; r < 4; ++r) { hs[r] = -acc[q][r]; bs[r] = acc[q][r]; }
     store_tile((tij[q] >> 8) & 255, tij[q] & 255, hs, bs);
   }
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   // tiles without products (S = Hpp + D): this wave's list first (scalar), then the Hpp entries of four tiles requested together -- every tile used
   // to be a global round trip of its own
   auto next_plain = [&](int t) {   // the next tile without products of this wave at or after t (wave-uniform)
     for (; t < ntile; t += 8) {
       int ti, tj;
       tile_decode(t, ti, tj);
-      if (!(nz_row(ti) && nz_col(tj))) break;
+      if (!(tiles.nz_row(ti) && tiles.nz_col(tj))) break;
     }
     return t;
   };
   if (d.schur_plain_in_H) {   // the Cholesky kernel reads Hpp itself (half of this kernel's Hpp reads and S writes were copies); only the
     for (int c = tid; c < P; c += 512)   // rhs entries of the columns that no product tile covers are left to do
-      if (!nz_col(c >> 4)) rhs[c] = acts[c] != 0.0 ? -gv[c] : 0.0;
+      if (!tiles.nz_col(c >> 4)) rhs[c] = acts[c] != 0.0 ? -gv[c] : 0.0;
   } else
   for (int tp = next_plain(wave); tp < ntile;) {
     int pi[4], pj[4];   // (-1: none)
@@ -287,8 +297,7 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
     for (int u = 0; u < 4; ++u)
       if (pi[u] >= 0) store_tile(pi[u], pj[u], hv[u], zero);
   }
-  CTV_STAMP();
-#undef CTV_STAMP
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
 }
 
 // fp64 path: the same SYRK on the fp64 matrix cores, one wave per 16 x 16 tile of the lower triangle
@@ -633,8 +642,7 @@ template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __
   __syncthreads();
   long long *dbg = (d.dbg && w == 0) ? d.dbg : nullptr;
   int dbi = 0;
-#define CTV_STAMP() do { if (dbg && tid == 0 && dbi < 30) dbg[dbi++] = clock64(); } while (0)
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   const int q4 = lane >> 4, l15 = lane & 15;
   // ---- diagonal block at column jb (one wave): lanes 0-31 the rows (lanes >= nb of the last, partial block carry identity
   //      rows), lanes 32-63 the columns of the inverse (identity).  The block is in LDS (Lb): the first one staged above, the
@@ -701,9 +709,8 @@ template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __
     if (tid == 0) s_trip = 4;   // wave 0 starts with tiles 0-3 (they hold the next diagonal block)
     // LDS-only barrier: what the next phase reads (LiT, LpT, plist) is in LDS; wave 0's global stores of the block inverse may
     // stay in flight (a full __syncthreads would wait for them; they are read after later full barriers only)
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    CTV_STAMP();
+    lds_block_sync();
+    CTV_STAMP(dbg, dbi, 30, tid == 0);
     // ---- L21 = A21 L11^-T, in place: Linv is lower triangular, so output columns 0..15 need k < 16 only
     for (int it = wave; it < np; it += NW) {
       const int tr = plist[it];
@@ -736,7 +743,7 @@ template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __
       }
     }
     __syncthreads();
-    CTV_STAMP();
+    CTV_STAMP(dbg, dbi, 30, tid == 0);
     // ---- trailing update A22 -= L21 L21^T on the lower triangle (16 x 16 tiles) and the rhs row, over the PAIRS of tiles that take part.
     //      Trips of 4 consecutive pairs are claimed from an LDS counter.  Wave 0 takes pairs 0-3 first -- (0,0), (1,0), (1,1) are the next
     //      diagonal block (local tiles 0 and 1 always take part), left in Lb -- then factors that block (LOOK-AHEAD: 21 k cycles on one wave
@@ -813,7 +820,7 @@ template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __
       }
     }
     __syncthreads();
-    CTV_STAMP();
+    CTV_STAMP(dbg, dbi, 30, tid == 0);
   }
   // ---- block back-substitution L^T x = y with the stored block inverses: x_b = Linv_b^T t_b, then t_j -= L[b][j]^T x_b
   //      for the rows above.  x lives in LDS; per block the loads of Linv_b (wave 0) and of the panel rows (everyone) do
@@ -862,9 +869,8 @@ template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __
     __syncthreads();
   }
   for (int i = tid; i < P; i += NT) x[i] = xs[i];
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   if (tid == 0) lm.chol_fail = s_fail;
-#undef CTV_STAMP
 }
 
 // ---- Register-resident tile Cholesky (windows with P <= 223): the whole lower triangle of the reduced system lives in the
@@ -882,29 +888,7 @@ template <int NW, bool COMPACT = false> __global__ __launch_bounds__(64 * NW) __
 // owner of tile (b, j) -- no atomics anywhere, the summation order is fixed (bitwise reproducible); one barrier per block.
 // With Dev::schur_plain_in_H the tiles without Schur products are read from Hpp (damping and fixed unknowns applied here), the others from S.
 // Pivots with index >= P (the rhs row, padding rows) are forced to 1 and never flagged.
-template <int J, int C> __device__ __forceinline__ void chol16_row_updates(double (&v)[16], int lo, int hi) {
-  if constexpr (C + 3 <= 15) {
-    chol_bcast_update4<C>(v[C], v[C + 1], v[C + 2], v[C + 3], v[J], lo, hi);
-    chol16_row_updates<J, C + 4>(v, lo, hi);
-  } else if constexpr (C <= 15) {
-    chol_bcast_update<C>(v[C], v[J], lo, hi);
-    chol16_row_updates<J, C + 1>(v, lo, hi);
-  }
-}
-template <int J> __device__ __forceinline__ void chol16_from(double (&v)[16], double di, int nreal, int &bad) {
-  v[J] *= di;
-  const int lo = __double2loint(v[J]), hi = __double2hiint(v[J]);
-  if constexpr (J < 15) {
-    chol_bcast_update_first<J + 1>(v[J + 1], v[J], lo, hi);
-    double di_next = 1.0;
-    if (J + 1 < nreal) di_next = chol_pivot_rsqrt(readlane_d(v[J + 1], J + 1), bad);   // (uniform branch; without it -- the 16 pivots as one
-    // basic block, so that the scheduler may put the row updates of pivot J into the bubbles of pivot J + 1's rsq / Newton chain -- the
-    // diagonal tile took 8.2 k cycles instead of 7.6 k: measured, not kept)
-    if constexpr (J < 14) chol16_row_updates<J, J + 2>(v, lo, hi);
-    chol16_from<J + 1>(v, di_next, nreal, bad);
-  }
-}
-// ---- The same diagonal tile with the broadcasts done by the data-parallel path of the fp64 ALU (v_fmac_f64_dpp row_newbcast:C: every lane of
+// ---- The diagonal tile, with the broadcasts done by the data-parallel path of the fp64 ALU (v_fmac_f64_dpp row_newbcast:C: every lane of
 // a 16-lane row reads lane C of ITS row; gfx90a+ allows exactly this DPP control on 64-bit operations) -- ONE instruction per column update instead
 // of two v_readlane and an FMA.  A lone wave issues one vector instruction per ~5.3 clocks whether or not it depends on the one before
 // (tools/fp64_latency_probe.hip), so the tile's time is its instruction count and nothing else.  Even rows of the wave (lanes 0-15, 32-47) hold
@@ -979,7 +963,7 @@ template <int K> __device__ __forceinline__ void dpp_dot16(double &acc, double t
 }
 __device__ __forceinline__ double f64x4_get(const f64x4 &a, int r) { return r == 0 ? a[0] : (r == 1 ? a[1] : (r == 2 ? a[2] : a[3])); }
 
-// (History of the diagonal tile.  With v_readlane broadcasts -- chol16_from above, still the cross-check in tools/chol16_probe.hip -- a BLOCKED
+// (History of the diagonal tile.  With v_readlane broadcasts -- chol16_from, kept in tools/chol16_probe.hip as the cross-check -- a BLOCKED
 //  variant (four blocks of four pivots, rank-4 updates as two v_mfma_f64_16x16x4) and a reciprocal-based pivot chain were built early in round 4
 //  and found no faster: 8.7 k / 9.0 k vs 8.3 k cycles per tile.  The explanation given then -- "300 dependent cycles per pivot" -- was wrong: a
 //  lone wave issues one fp64 instruction per ~5.3 clocks whether it depends on the previous one or not (tools/fp64_latency_probe.hip), the tile
@@ -1006,9 +990,7 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
   const double *Hc = d.HppS[lm.cur] + m.H0;
   const bool from_h = d.schur_plain_in_H != 0;
   const int K6 = 6 * m.K;
-  // (the same tile classification as k_schur_window_f64: W is non-zero in the knot columns, the line-delay column and the rhs row)
-  auto nz_row = [&](int b) { return (16 * b < K6) || (P >= 16 * b && P - 1 < 16 * b + 16); };
-  auto nz_col = [&](int b) { return (16 * b < K6) || (P - 1 >= 16 * b && P - 1 < 16 * b + 16); };
+  const SchurTiles tiles{K6, P};
   if (tid == 0) s_fail = 0;
   for (int i = tid; i < 16 * NTR; i += NT) tv[i] = 0.0;
   // activity of the unknowns as four 64-bit masks in SGPRs (each wave builds its own: four byte loads per lane, no LDS, no barrier)
@@ -1040,7 +1022,7 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
     tj[q] = __builtin_amdgcn_readfirstlane(t < ntiles ? b : 1 << 20);   // (never equal to a panel, never a trailing tile: ti < tj)
     ek[q] = __builtin_amdgcn_readfirstlane(max(d.env_tile[m.tr0 + a], d.env_tile[m.tr0 + b]));
     // unconditional loads on clamped addresses straight into the tile registers; fixed up below
-    const bool plain = from_h && !(nz_row(a) && nz_col(b));   // (wave-uniform)
+    const bool plain = from_h && !(tiles.nz_row(a) && tiles.nz_col(b));   // (wave-uniform)
     const double *src = plain ? Hc : S;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1052,7 +1034,7 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
   for (int q = 0; q < NS; ++q) {
     if (ti[q] < 0) continue;
     const int col = 16 * tj[q] + l15;
-    if (from_h && !(nz_row(ti[q]) && nz_col(tj[q]))) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
+    if (from_h && !(tiles.nz_row(ti[q]) && tiles.nz_col(tj[q]))) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
       const int a_j = active_bit(col);
       double ddiag = 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window; one L2 round trip for its wave)
       if (ti[q] == tj[q]) ddiag = d.dd[m.u0 + min(col, P - 1)];
@@ -1078,11 +1060,11 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
   __syncthreads();
   long long *dbg = (d.dbg && w == 0) ? d.dbg : nullptr;   // CTVIO_DEBUG_STAMPS: clock64 of thread 0 at the phase boundaries
   int dbi = 0;
-#define CTV_STAMP() do { if (dbg && tid == 0 && dbi < 30) dbg[dbi++] = clock64(); } while (0)
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   for (int k = 0; k < NTR; ++k) {
-    int opq;   // (a zero the compiler cannot see through: the per-slot LDS addresses of steps C and E are recomputed each panel -- one add each --
-    asm volatile("s_mov_b32 %0, 0" : "=s"(opq));   // instead of being kept as 14 loop-invariant registers, which no longer fit beside the tile)
+    // (the per-slot LDS addresses of steps C and E are recomputed each panel -- one add each -- instead of being kept as 14 loop-invariant
+    // registers, which no longer fit beside the tile)
+    const int opq = opaque_zero();
     double *Pnk = Pn + opq;
     // ---- A. diagonal tile (k, k)
     const int td = k * (k + 1) / 2 + k, od = td % NW, sd = td / NW;
@@ -1100,19 +1082,18 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
 #pragma unroll
         for (int r = 0; r < 4; ++r) { park[(3 * r) * 64 + lane] = acc[0][r]; park[(3 * r + 1) * 64 + lane] = acc[1][r]; park[(3 * r + 2) * 64 + lane] = acc[2][r]; }
       }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
+      lds_wave_sync();
       double v[16];
-      int opaque0;   // a zero the compiler cannot see through: without it the 16 identity columns below are hoisted out of the panel
-      asm volatile("s_mov_b32 %0, 0" : "=s"(opaque0));   // loop as loop invariants and, for lack of registers, kept in scratch
+      // without the opaque zero the 16 identity columns below are hoisted out of the panel loop as loop invariants and, for lack of registers,
+      // kept in scratch
+      const int opaque0 = opaque_zero();
       // even rows of the wave: the tile's rows (whole rows: the factorisation never reads the upper half); odd rows: the identity, from LDS as
       // well.  (With selects -- lane < 16 ? (c <= lane ? a : 0) : (c == lane) -- the compiler sank each of the 16 LDS reads into its own branch
       // with its own s_waitcnt: 2.2 k clocks per tile for the load alone, tools/chol16_probe.hip.)
       const double *src = ((lane & 16) ? Id : Dg) + (l15 + opaque0) * 17;
 #pragma unroll
       for (int c = 0; c < 16; ++c) v[c] = src[c];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();      // every lane has read its row before the block is overwritten with the inverse
+      lds_wave_sync();   // every lane has read its row before the block is overwritten with the inverse
       const int nreal = P - 16 * k;         // pivots below this are real; the rhs row and the padding rows are not factored
       int bad = 0;
       chol16_dpp(v, nreal, bad);
@@ -1130,10 +1111,9 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
         for (int r = 0; r < 4; ++r) { acc[0][r] = park[(3 * r) * 64 + lane]; acc[1][r] = park[(3 * r + 1) * 64 + lane]; acc[2][r] = park[(3 * r + 2) * 64 + lane]; }
       }
     }
-    if (k < 4) CTV_STAMP();
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    if (k < 4) CTV_STAMP();
+    if (k < 4) CTV_STAMP(dbg, dbi, 30, tid == 0);
+    lds_block_sync();
+    if (k < 4) CTV_STAMP(dbg, dbi, 30, tid == 0);
     // ---- C. L_ik = A_ik L_kk^-T for the tiles below the diagonal one
     const double *Lk = Li + k * TS;
 #pragma unroll
@@ -1142,13 +1122,11 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
       double *blk = Pnk + ti[q] * TS;
 #pragma unroll
       for (int r = 0; r < 4; ++r) blk[(q4 + 4 * r) * 17 + l15] = acc[q][r];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();
+      lds_wave_sync();
       double a[4], b[4];
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) { a[s4] = blk[l15 * 17 + 4 * s4 + q4]; b[s4] = Lk[l15 * 17 + 4 * s4 + q4]; }
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();          // operands are in registers before the slice is overwritten
+      lds_wave_sync();   // operands are in registers before the slice is overwritten
       f64x4 c = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], c, 0, 0, 0);
@@ -1157,10 +1135,9 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
       for (int r = 0; r < 4; ++r) blk[(q4 + 4 * r) * 17 + l15] = c[r];
       if (ti[q] == ip && q4 == (rp & 3)) tv[16 * k + l15] = f64x4_get(c, rp >> 2);   // y: row P of L
     }
-    if (k < 4) CTV_STAMP();
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
-    if (k < 4) CTV_STAMP();
+    if (k < 4) CTV_STAMP(dbg, dbi, 30, tid == 0);
+    lds_block_sync();
+    if (k < 4) CTV_STAMP(dbg, dbi, 30, tid == 0);
     // ---- E. trailing tiles (i, j), j > k: A_ij -= L_ik L_jk^T
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
@@ -1184,11 +1161,11 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
     //  panels by A -> L_(k+1,k) -> update of (k+1,k+1) -> A with the two middle steps serial in one wave (6.9 k cycles per panel against
     //  ~5.7 k here): profiles/r06_chol_chain_experiment.txt.)
     // (the next panel's step C overwrites the LDS panel only after the barrier that follows its step A)
-    if (k < 4) CTV_STAMP();
+    if (k < 4) CTV_STAMP(dbg, dbi, 30, tid == 0);
   }
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   __syncthreads();
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   // ---- back-substitution L^T x = y over the tiles in registers: ONE barrier per block.  After x_b is known, the only contribution t_{b-1}
   // still lacks is that of tile (b, b - 1): its owner finishes t_{b-1} in registers and forms x_{b-1} = L_{b-1,b-1}^-T t_{b-1} at once (the sixteen
   // t[k] read across the 16-lane rows by v_fmac_f64_dpp row_newbcast, the sum over the four row groups by v_permlane16/32_swap -- no LDS round
@@ -1204,8 +1181,7 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
     xa += __shfl_xor(xa, 32);
     if (q4 == 0) xs[16 * bl + l15] = xa;
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_s_barrier();
+  lds_block_sync();
   for (int b = NTR - 1; b >= 1; --b) {
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
@@ -1235,14 +1211,12 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
         if (q4 == 0) tv[16 * tj[q] + l15] -= part;
       }
     }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_s_barrier();
+    lds_block_sync();
   }
-  CTV_STAMP();
+  CTV_STAMP(dbg, dbi, 30, tid == 0);
   double *x = d.delta + m.u0;
   for (int i = tid; i < P; i += NT) x[i] = xs[i];
   if (tid == 0) lm.chol_fail = s_fail;
-#undef CTV_STAMP
 }
 
 // ---- The same factorisation as a DATA-FLOW of waves (round 6): the critical path of a tile Cholesky is
@@ -1310,14 +1284,12 @@ __device__ __forceinline__ void chol_wait(volatile int *f, int target, int &fail
 // everything this wave wrote to LDS is there; then the flag
 __device__ __forceinline__ void chol_post(volatile int *f, int value, int lane) {
   asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();
   if (lane == 0) *f = value;
 }
 __device__ __forceinline__ void chol_count(int *f, int lane) {
   asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();
   if (lane == 0) atomicAdd(f, 1);
 }
 
@@ -1345,23 +1317,20 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   volatile int *F_inv = fl + 16, *F_row = fl + 32;
   int *F_park = fl + 48, *done_E = fl + 64;
   long long *dbg = (d.dbg && w == 0) ? d.dbg : nullptr;   // CTVIO_DEBUG_STAMPS: clock64 of the chain wave at its steps
-#define CTV_BAR() do { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_s_barrier(); } while (0)
   if (chain) {
     // ================================================================ the chain wave
     int dbi = 0, fail = 0;
-#define CTV_STAMP() do { if (dbg && lane == 0 && dbi < 30) dbg[dbi++] = clock64(); } while (0)
     for (int i = lane; i < 80; i += 64) fl[i] = 0;
     for (int i = lane; i < TS; i += 64) Id[i] = (i / 17 == i % 17) ? 1.0 : 0.0;
     for (int i = lane; i < 16 * NTR; i += 64) tv[i] = 0.0;
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    CTV_BAR();                                   // tile (0, 0) is in LDS, the flags are clear
-    CTV_STAMP();
+    lds_wave_sync();
+    lds_block_sync();   // tile (0, 0) is in LDS, the flags are clear
+    CTV_STAMP(dbg, dbi, 30, lane == 0);
     for (int k = 0; k < NTR; ++k) {
       double *Dg = Li + k * TS;
       if (k > 0) {
         chol_wait(reinterpret_cast<volatile int *>(F_park + k), 2, fail);
-        if (k < 4) CTV_STAMP();
+        if (k < 4) CTV_STAMP(dbg, dbi, 30, lane == 0);
         // ---- L_(k,k-1) = A_(k,k-1) L_(k-1,k-1)^-T: both operands are in LDS in row-major form (no accumulator -> operand round trip)
         double *blk = Ls + k * TS;
         const double *Lk = Li + (k - 1) * TS;
@@ -1371,8 +1340,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         f64x4 acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = Dg[(q4 + 4 * r) * 17 + l15];     // tile (k, k), requested with the operands
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
+        lds_wave_sync();
         f64x4 c = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) c = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], c, 0, 0, 0);
@@ -1389,19 +1357,16 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], acc, 0, 0, 0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Dg[(q4 + 4 * r) * 17 + l15] = acc[r];
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
-        if (k < 4) CTV_STAMP();
+        lds_wave_sync();
+        if (k < 4) CTV_STAMP(dbg, dbi, 30, lane == 0);
       }
       double v[16];
-      int opaque0;   // a zero the compiler cannot see through (the 16 identity columns would be hoisted out of the panel loop otherwise)
-      asm volatile("s_mov_b32 %0, 0" : "=s"(opaque0));
+      const int opaque0 = opaque_zero();   // (the 16 identity columns would be hoisted out of the panel loop otherwise)
       // even rows of the wave: the tile's rows (whole rows: the factorisation never reads the upper half); odd rows: the identity, from LDS too
       const double *src = ((lane & 16) ? Id : Dg) + (l15 + opaque0) * 17;
 #pragma unroll
       for (int cc = 0; cc < 16; ++cc) v[cc] = src[cc];
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      __builtin_amdgcn_wave_barrier();          // every lane has read its row before the block is overwritten with the inverse
+      lds_wave_sync();   // every lane has read its row before the block is overwritten with the inverse
       const int nreal = P - 16 * k;             // pivots below this are real; the rhs row and the padding rows are not factored
       int bad = 0;
       chol16_dpp(v, nreal, bad);
@@ -1415,7 +1380,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
       }
       if (bad) fail = 1;
       chol_post(F_inv + k, 1, lane);
-      CTV_STAMP();
+      CTV_STAMP(dbg, dbi, 30, lane == 0);
     }
     if (lane == 0 && fail) s_fail = 1;
     // back-substitution: x of the last block, x_b[j] = sum_k Linv[k][j] t[k]: lane (q4, j = l15) sums k = 4 q4 .. 4 q4 + 3
@@ -1429,10 +1394,9 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
       xa += __shfl_xor(xa, 32);
       if (q4 == 0) xs[16 * bl + l15] = xa;
     }
-    CTV_STAMP();
-    CTV_BAR();                                   // the factorisation is complete (the update waves arrive here when they are through)
+    CTV_STAMP(dbg, dbi, 30, lane == 0);
+    lds_block_sync();   // the factorisation is complete (the update waves arrive here when they are through)
     return;                                      // (the update waves finish the back-substitution among themselves)
-#undef CTV_STAMP
   }
   // ================================================================== update waves
   const int utid = 64 * uw + lane;
@@ -1441,9 +1405,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   const double *Hc = d.HppS[lm.cur] + m.H0;
   const bool from_h = d.schur_plain_in_H != 0;
   const int K6 = 6 * m.K;
-  // (the same tile classification as k_schur_window_f64: W is non-zero in the knot columns, the line-delay column and the rhs row)
-  auto nz_row = [&](int b) { return (16 * b < K6) || (P >= 16 * b && P - 1 < 16 * b + 16); };
-  auto nz_col = [&](int b) { return (16 * b < K6) || (P - 1 >= 16 * b && P - 1 < 16 * b + 16); };
+  const SchurTiles tiles{K6, P};
   // activity of the unknowns as four 64-bit masks in SGPRs (each wave builds its own: four byte loads per lane, no LDS, no barrier)
   unsigned long long amask[4] = {0ull, 0ull, 0ull, 0ull};
   if (from_h) {
@@ -1470,7 +1432,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
     tj[q] = __builtin_amdgcn_readfirstlane(a0 >= 0 ? b0 : 1 << 20);   // (never equal to a panel, never a trailing tile: ti < tj)
     ek[q] = __builtin_amdgcn_readfirstlane(max(d.env_tile[m.tr0 + a], d.env_tile[m.tr0 + b]));
     // unconditional loads on clamped addresses straight into the tile registers; fixed up below
-    const bool plain = from_h && !(nz_row(a) && nz_col(b));   // (wave-uniform)
+    const bool plain = from_h && !(tiles.nz_row(a) && tiles.nz_col(b));   // (wave-uniform)
     const double *src = plain ? Hc : S;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1482,7 +1444,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   for (int q = 0; q < NS; ++q) {
     if (ti[q] < 0) continue;
     const int col = 16 * tj[q] + l15;
-    if (from_h && !(nz_row(ti[q]) && nz_col(tj[q]))) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
+    if (from_h && !(tiles.nz_row(ti[q]) && tiles.nz_col(tj[q]))) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
       const int a_j = active_bit(col);
       double ddiag = 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window; one L2 round trip for its wave)
       if (ti[q] == tj[q]) ddiag = d.dd[m.u0 + min(col, P - 1)];
@@ -1510,13 +1472,13 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
       for (int r = 0; r < 4; ++r) dst[(q4 + 4 * r) * 17 + l15] = acc[q][r];
     }
   }
-  CTV_BAR();
+  lds_block_sync();
   // Iteration c of an update wave: panel c - 1 applied to its NEAR trailing tiles (columns c and c + 1: the tiles whose L_ic the next panel needs, and
   // the two tiles of row c + 1 that go to the chain wave), then -- as soon as the chain wave has L_cc^-1 -- the L_ic of its tiles of column c, and
   // panel c - 1 applied to the rest, which fills the wait for L_cc^-1 when that is not there yet.
   for (int c = 0; c < NTR; ++c) {
-    int opq;   // (a zero the compiler cannot see through: the per-slot LDS addresses are recomputed each panel -- one add each -- instead of
-    asm volatile("s_mov_b32 %0, 0" : "=s"(opq));   // being kept as loop-invariant registers beside the tiles)
+    // (the per-slot LDS addresses are recomputed each panel -- one add each -- instead of being kept as loop-invariant registers beside the tiles)
+    const int opq = opaque_zero();
     double *Pnc = Pn + (c % NPB) * NTR * TS + opq;                      // panel c: written here
     const double *Pnp = Pn + ((c + NPB - 1) % NPB) * NTR * TS + opq;    // panel c - 1: applied here
     unsigned seen = 0;     // rows whose L_(i,c-1) this wave has already found published
@@ -1559,13 +1521,11 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         double *blk = Pnc + ti[q] * TS;
 #pragma unroll
         for (int r = 0; r < 4; ++r) blk[(q4 + 4 * r) * 17 + l15] = acc[q][r];
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
+        lds_wave_sync();
         double a[4], b[4];
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) { a[s4] = blk[l15 * 17 + 4 * s4 + q4]; b[s4] = Lc[l15 * 17 + 4 * s4 + q4]; }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();          // operands are in registers before the slice is overwritten
+        lds_wave_sync();   // operands are in registers before the slice is overwritten
         f64x4 cc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) cc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], cc, 0, 0, 0);
@@ -1593,7 +1553,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
     if (c > 0) chol_count(done_E + (c - 1), lane);   // this wave is through with panel c - 1
   }
   if (lane == 0 && fail) s_fail = 1;
-  CTV_BAR();                                      // the factorisation is complete; x of the last block (chain wave)
+  lds_block_sync();   // the factorisation is complete; x of the last block (chain wave)
   // the tiles (b, b - 1) come back from the chain wave as L_(b,b-1)
 #pragma unroll
   for (int q = 0; q < NS; ++q) {
@@ -1635,12 +1595,11 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         if (q4 == 0) tv[16 * tj[q] + l15] -= part;
       }
     }
-    CTV_BAR();
+    lds_block_sync();
   }
   double *x = d.delta + m.u0;
   for (int i = utid; i < P; i += NTU) x[i] = xs[i];
   if (utid == 0) lm.chol_fail = s_fail;
-#undef CTV_BAR
 }
 
 // (Fusing this kernel into k_cholesky_tiles -- same workgroup, the pose step straight from LDS -- was built and measured: no gain for
@@ -1712,7 +1671,7 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
       for (int k = 0; k < 2; ++k) {
         const double xi = (i0 + lane + 64 * k < NCB) ? xs[col[k]] : 0.0;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) acc8[u] += (double)wv[u][k] * xi;
+        for (int u = 0; u < 8; ++u) acc8[u] += wv[u][k] * xi;
       }
     }
     // 8 row sums over 64 lanes with 10 shuffles: each butterfly step halves the rows a lane carries (bit 5 of the lane

@@ -6,21 +6,6 @@
 namespace ctv {
 
 // ------------------------------------------------------------------------------------------------ visual
-// Entry (row = 2 * local column + residual row, < 100; 100 / 101 = the residual) of the robust-corrected 2 x 50 Jacobian of the block
-// in slot v with anchor `anc`, rebuilt from the block record and the anchor record (factors.hpp): the cross-check assembly's input.
-__device__ __forceinline__ double vis_J_entry(const Dev &d, int row, unsigned v, unsigned anc) {
-  const double *J = d.Jt + (size_t)v * VT_ROWS;
-  if (row >= 100) return J[VB_RES + row - 100];
-  const int col = row >> 1, rr = row & 1;
-  if (col >= 48) return J[(col == 48 ? VB_RHO : VB_LD) + rr];
-  const double *rec = d.arec + (size_t)anc * AREC;
-  if (col < 12) return J[VB_AT + rr] * rec[AR_GR + 3 * col] + J[VB_AT + 2 + rr] * rec[AR_GR + 3 * col + 1] + J[VB_AT + 4 + rr] * rec[AR_GR + 3 * col + 2];
-  if (col < 24) { const int c = col - 12; return rec[AR_CP0 + c / 3] * J[VB_AT + 2 * (c % 3) + rr]; }
-  if (col < 36) return J[VB_JROT + 2 * (col - 24) + rr];
-  const int c = col - 36;
-  return -(J[VB_CP1 + c / 3] * J[VB_AT + 2 * (c % 3) + rr]);
-}
-
 // time -> (first active knot, u) in integer ns (reference spline_segment.h:83-85); the line delay is
 // truncated to integer ns exactly as image_feature_factor.h:72.
 __device__ __forceinline__ void vis_times(const WinMeta &m, long long t_rel, int row, double ld, int &s, double &u) {
@@ -75,8 +60,7 @@ __device__ __forceinline__ void vis_anchor_body(const Dev &d, int mode, double *
   else vis_anchor_eval<false>(q0, p, sc, ui, m.inv_dt, q_CI, p_CI, pix, piy, (double)rowi, d_inv, jac, rec);
   d.a_s[a] = si;
   }
-  __builtin_amdgcn_s_waitcnt(0xc07f);          // (one wave per workgroup: the wave's own LDS writes have completed)
-  __builtin_amdgcn_wave_barrier();
+  lds_wave_sync();   // (one wave per workgroup: the wave's own LDS writes have completed)
   {
     const int lane = threadIdx.x;
     double *dst = d.arec + (size_t)(block * 64) * AREC;
@@ -198,10 +182,9 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
     double *Hllset = d.HllS[tgw], *gset = d.gS[tgw];
     // One wave per workgroup: LDS hand-overs only need the wave's own LDS operations to have completed.  (__syncthreads() also
     // waits for vmcnt(0), i.e. for the J~ and W stores in flight to be acknowledged -- ~5 us per barrier here, measured.)
-#define LDS_SYNC() do { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); } while (0)
     long long *dbg = (d.dbg && vblock == 1000) ? d.dbg + 32 : nullptr;   // (profiling aid: clock stamps of one wave)
     if (dbg && lane == 0) { dbg[-1] = t_entry; dbg[0] = clock64() + (long long)(c * 0); }
-    LDS_SYNC();
+    lds_wave_sync();
     // ---- this lane's contributions to its landmark's row of W.  With jr = J~_rho (2) and n3 = A~^T jr (3): the columns of the block's own
     //      (j) end are jr^T J~_rot and -cp1[k] n3; the anchor end's are (sum over the anchor's blocks of n3)^T [GR | cp0 (x) I] -- formed
     //      once per anchor from the record; line delay, Hll, g_rho ride with that sum.
@@ -294,11 +277,11 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
     int ri = ksi - my_klo, rj = ksj - my_klo;
     if (on && (rj < 0 || ksj + 3 > my_khi || (head_a && (ri < 0 || ksi + 3 > my_khi)))) atomicAdd(d.span_viol, 1);
     ri = max(0, min(ri, SPW / 6 - 4)); rj = max(0, min(rj, SPW / 6 - 4));
-    LDS_SYNC();   // every lane has read its record, the copy-out has read them all
+    lds_wave_sync();   // every lane has read its record, the copy-out has read them all
     for (int c0 = 0; c0 < nlm; c0 += NR) {
       const int nr = min(NR, nlm - c0);
       for (int i = 2 * lane; i < nr * RS; i += 128) *reinterpret_cast<VecN<double, 2> *>(rows + i) = VecN<double, 2>{{0.0, 0.0}};   // (NR RS + 1 doubles fit)
-      LDS_SYNC();
+      lds_wave_sync();
       if (on && ord >= c0 && ord < c0 + nr) {
         double *row = rows + (size_t)(ord - c0) * RS;
         if (head_a) {
@@ -321,7 +304,7 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
             atomicAdd(&row[6 * (rj + k) + 3 + b], wj[12 + 3 * k + b]);
           }
       }
-      LDS_SYNC();
+      lds_wave_sync();
       if (dbg && lane == 0) dbg[3 + 2 * (c0 / NR)] = clock64();
       // write-out: a row's span columns as 16-byte column pairs (a span starts on a 48-byte boundary of a 256-byte aligned row), four rows
       // per store instruction -- one row per 16-lane group
@@ -347,10 +330,9 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
           gset[u0 + P + l] = row[SPW + 2];
         }
       }
-      LDS_SYNC();
+      lds_wave_sync();
       if (dbg && lane == 0) { dbg[4 + 2 * (c0 / NR)] = clock64(); dbg[10] = nlm * 1000000ll; dbg[11] = NR * 1000; }
     }
-#undef LDS_SYNC
   }
 }
 

@@ -43,7 +43,7 @@ __device__ __forceinline__ double mb_elem(const Dev &d, const WinMeta &wm, int c
   const int P = wm.P;
   if (i < P && j < P) return d.HppS[cset][wm.H0 + (long long)max(i, j) * wm.ldh + min(i, j)];
   if (i >= P && j >= P) return (i == j) ? d.HllS[cset][wm.lm0 + i - P] : 0.0;
-  return (double)d.WS[cset][wm.W0 + (long long)d.lm_pos[wm.lm0 + max(i, j) - P] * wm.ldw + min(i, j)];
+  return d.WS[cset][wm.W0 + (long long)d.lm_pos[wm.lm0 + max(i, j) - P] * wm.ldw + min(i, j)];
 }
 
 __global__ __launch_bounds__(256) void k_mb_gather(Dev d, MbWin b) {

@@ -1,5 +1,6 @@
-// chol16_probe.hip -- the 16 x 16 diagonal tile of k_cholesky_tiles on its own: the v_readlane variant (chol16_from) against the DPP variant
-// (chol16_dpp), one wave, checked against a host Cholesky + inverse and timed with s_memtime over REP tiles.
+// chol16_probe.hip -- the 16 x 16 diagonal tile of the tile Cholesky (k_cholesky_flow / k_cholesky_tiles) on its own: the v_readlane variant
+// (chol16_from, below: the kernels' diagonal tile until the DPP one replaced it) against the DPP variant (chol16_dpp), one wave, checked
+// against a host Cholesky + inverse and timed with s_memtime over REP tiles.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ctrl-vio_amd/csrc tools/chol16_probe.hip -o /tmp/chol16_probe && /tmp/chol16_probe
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,30 @@
 
 using namespace ctv;
 
+// The v_readlane diagonal tile: the 16-pivot form of chol_diag_step / chol_row_updates of k_cholesky_solve (kernels_solve.hpp).
+template <int J, int C> __device__ __forceinline__ void chol16_row_updates(double (&v)[16], int lo, int hi) {
+  if constexpr (C + 3 <= 15) {
+    chol_bcast_update4<C>(v[C], v[C + 1], v[C + 2], v[C + 3], v[J], lo, hi);
+    chol16_row_updates<J, C + 4>(v, lo, hi);
+  } else if constexpr (C <= 15) {
+    chol_bcast_update<C>(v[C], v[J], lo, hi);
+    chol16_row_updates<J, C + 1>(v, lo, hi);
+  }
+}
+template <int J> __device__ __forceinline__ void chol16_from(double (&v)[16], double di, int nreal, int &bad) {
+  v[J] *= di;
+  const int lo = __double2loint(v[J]), hi = __double2hiint(v[J]);
+  if constexpr (J < 15) {
+    chol_bcast_update_first<J + 1>(v[J + 1], v[J], lo, hi);
+    double di_next = 1.0;
+    if (J + 1 < nreal) di_next = chol_pivot_rsqrt(readlane_d(v[J + 1], J + 1), bad);   // (uniform branch; without it -- the 16 pivots as one
+    // basic block, so that the scheduler may put the row updates of pivot J into the bubbles of pivot J + 1's rsq / Newton chain -- the
+    // diagonal tile took 8.2 k cycles instead of 7.6 k: measured, not kept)
+    if constexpr (J < 14) chol16_row_updates<J, J + 2>(v, lo, hi);
+    chol16_from<J + 1>(v, di_next, nreal, bad);
+  }
+}
+
 template <int VARIANT> __global__ __launch_bounds__(1024) void k_probe(const double *tiles, double *out, long long *cycles, int rep, int nreal) {
   __shared__ double Dg[16 * 17], Id[16 * 17];
   for (int i = threadIdx.x; i < 16 * 17; i += blockDim.x) Id[i] = (i / 17 == i % 17) ? 1.0 : 0.0;
@@ -23,13 +48,10 @@ template <int VARIANT> __global__ __launch_bounds__(1024) void k_probe(const dou
   for (int it = 0; it < rep; ++it) {
     const double *A = tiles + 256 * it;
     for (int i = lane; i < 256; i += 64) Dg[(i / 16) * 17 + i % 16] = A[i];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
+    lds_wave_sync();
     t0 = clock64();
     double v[16];
-    int opaque0;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(opaque0));
-    const int lz = l15 + opaque0;
+    const int lz = l15 + opaque_zero();
     if (VARIANT == 0) {
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
@@ -41,8 +63,7 @@ template <int VARIANT> __global__ __launch_bounds__(1024) void k_probe(const dou
 #pragma unroll
       for (int c = 0; c < 16; ++c) v[c] = src[c];
     }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
+    lds_wave_sync();
     const long long t1 = clock64();
     if (VARIANT == 0) {
       double di0 = 1.0;
@@ -56,8 +77,7 @@ template <int VARIANT> __global__ __launch_bounds__(1024) void k_probe(const dou
 #pragma unroll
       for (int i = 0; i < 16; ++i) Dg[i * 17 + l15] = v[i];
     }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
+    lds_wave_sync();
     acc += clock64() - t0; accl += t1 - t0; accf += t2 - t1;
     // out: [it][0..255] = L (row-major, lower), [it][256..511] = Linv (row-major)
     if (lane < 16) {
@@ -65,8 +85,7 @@ template <int VARIANT> __global__ __launch_bounds__(1024) void k_probe(const dou
       for (int c = 0; c < 16; ++c) out[512 * it + 16 * lane + c] = v[c];
     }
     for (int i = lane; i < 256; i += 64) out[512 * it + 256 + i] = Dg[(i / 16) * 17 + i % 16];
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
+    lds_wave_sync();
   }
   if (lane == 0) { cycles[0] = acc; cycles[1] = bad; cycles[2] = accl; cycles[3] = accf; }
 }

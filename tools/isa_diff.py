@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""Per-kernel comparison of two device assembly files (the `*-gfx950.s` that `hipcc -save-temps` leaves):
+    isa_diff.py <parent.s> <branch.s>
+A kernel runs from its `_Z...:` label to its `.Lfunc_end`; comment text after `;`, empty lines and the `.loc` / `.file` /
+`.cfi` / `.p2align` lines are dropped, the remaining lines are compared.  Exit status 1 if any kernel differs."""
+import re
+import sys
+
+DROP = re.compile(r"\s*\.(loc|file|cfi\w*|p2align)\b")
+
+
+def kernels(path):
+    out, name, funcs = {}, None, set()
+    for line in open(path):
+        f = re.match(r"\s*\.type\s+(_Z\w+),@function", line)
+        if f:
+            funcs.add(f.group(1))
+        m = re.match(r"(_Z\w+):", line)
+        if m and name is None and m.group(1) in funcs:
+            name, out[m.group(1)] = m.group(1), []
+            continue
+        if name is None:
+            continue
+        if line.startswith(".Lfunc_end"):
+            name = None
+            continue
+        line = line.split(";", 1)[0].strip()
+        if line and not DROP.match(line):
+            out[name].append(line)
+    return out
+
+
+def main(parent, branch):
+    a, b = kernels(parent), kernels(branch)
+    changed = [k for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
+    for k in changed:
+        print(f"DIFF  {k}: {len(a.get(k, []))} -> {len(b.get(k, []))} lines" if k in a and k in b
+              else f"{'GONE' if k in a else 'NEW '}  {k}")
+    print(f"{len(set(a) & set(b)) - sum(k in a and k in b for k in changed)} of {len(a)} kernels identical")
+    return 1 if changed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(*sys.argv[1:3]))
