@@ -899,20 +899,24 @@ class SolverImpl {
   // to that window.  Outputs: n_keep[nwin]; kept at the window's unknown offset; J0 / r0 packed tightly in window order.
   // allow_blocked: windows with m or n in (MARG_MAXD, MARG_MAXD_BLOCKED] take the blocked path (csrc/marg_blocked.hpp, one window
   // after the other, after the in-LDS launch of the small ones); without it they are reported too large.
-  int marg_device(const int8_t *role_all, int only, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0, bool *too_large,
-                  int *stalled = nullptr, bool allow_blocked = false) {
-    if (stalled) *stalled = -1;
+  struct MargResult {   // too_large: a window is beyond what the call may take (rc is CTVIO_OK, nothing computed); stalled: the window
+    int rc; bool too_large = false; int stalled = -1;   // whose eigen-solver did not converge (rc is an error then), or -1
+    MargResult(int rc_ = CTVIO_OK) : rc(rc_) {}
+  };
+  struct BlockedMeta { int w; MargMeta mm; };
+  MargResult marg_device(const int8_t *role_all, int only, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0, bool allow_blocked) {
+    MargResult res;
     Dev &d = dev_;
     const int nw = d.nwin;
-    *too_large = false;
-    std::vector<MargMeta> metas((size_t)nw), bmeta;   // bmeta: the blocked windows (k_marginalize sees them with m = n = 0)
+    std::vector<MargMeta> metas((size_t)nw);
+    std::vector<BlockedMeta> bmeta;   // the blocked windows (k_marginalize sees them with m = n = 0)
     std::vector<int32_t> iscr;
     size_t scr = 0, outd = 0;
     for (int w = 0; w < nw; ++w) {
       const WinMeta &m = meta_[w];
       MargMeta &mm = metas[w];
       std::memset(&mm, 0, sizeof mm);
-      mm.N = m.N; mm.P = m.P;
+      mm.N = m.N;
       if (only >= 0 && w != only) { n_keep[w] = 0; continue; }
       const int8_t *role = role_all + m.u0;
       mm.idx0 = (int32_t)iscr.size();
@@ -920,12 +924,11 @@ class SolverImpl {
       for (int i = 0; i < m.N; ++i) if (role[i] == 0) { iscr.push_back(i); kept[m.u0 + mm.n] = i; mm.n++; }
       n_keep[w] = mm.n;
       const bool big = mm.m > MARG_MAXD || mm.n > MARG_MAXD;
-      if (mm.m > MARG_MAXD_BLOCKED || mm.n > MARG_MAXD_BLOCKED || (big && !allow_blocked)) { *too_large = true; return CTVIO_OK; }
+      if (mm.m > MARG_MAXD_BLOCKED || mm.n > MARG_MAXD_BLOCKED || (big && !allow_blocked)) { res.too_large = true; return res; }
+      mm.J0 = (int64_t)outd; outd += (size_t)mm.n * mm.n;
+      mm.r0 = (int64_t)outd; outd += (size_t)mm.n;
       if (allow_blocked && mm.n > 0 && (big || dbg_.marg_blocked)) {
-        mm.J0 = (int64_t)outd; outd += (size_t)mm.n * mm.n;
-        mm.r0 = (int64_t)outd; outd += (size_t)mm.n;
-        mm.sweeps_m = w;                // (the window index, while the copy waits in bmeta)
-        bmeta.push_back(mm);
+        bmeta.push_back({w, mm});
         mm.m = mm.n = 0;
         continue;
       }
@@ -936,8 +939,6 @@ class SolverImpl {
       mm.Y0 = (int64_t)scr; scr += (size_t)mm.m * (mm.n + 1);
       mm.rot0 = (int64_t)scr; scr += (size_t)MARG_MAX_SWEEPS * std::max(np - 1, 1) * (np / 2) * 2;
       mm.b0 = (int64_t)scr; scr += (size_t)mm.n;
-      mm.J0 = (int64_t)outd; outd += (size_t)mm.n * mm.n;
-      mm.r0 = (int64_t)outd; outd += (size_t)mm.n;
     }
     // normal equations of every window at its current state
     set_params(1);
@@ -949,15 +950,13 @@ class SolverImpl {
     HIPCHK(mg_out_.alloc(outd));
     HIPCHK(poison(mg_scr_.p, sizeof(double) * scr));
     HIPCHK(poison(mg_out_.p, sizeof(double) * outd));
-    constexpr size_t lds = ((size_t)MARG_MAXD * (MARG_MAXD + 1) / 2 + 4 * MARG_MAXD + 512) * sizeof(double) + 2 * MARG_MAXD * sizeof(int);
-    if (!marg_attr_set_) { HIPCHK(hipFuncSetAttribute((const void *)k_marginalize, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); marg_attr_set_ = true; }
+    if (!marg_attr_set_) { HIPCHK(hipFuncSetAttribute((const void *)k_marginalize, hipFuncAttributeMaxDynamicSharedMemorySize, MARG_LDS_LIMIT)); marg_attr_set_ = true; }
     if (bmeta.size() < (size_t)nw)
-      hipLaunchKernelGGL(k_marginalize, dim3(nw), dim3(256), lds, stream_, d, mg_meta_.p, mg_idx_.p, mg_scr_.p, mg_out_.p, eps);
-    for (MargMeta &bm : bmeta) {
-      const int w = bm.sweeps_m;
-      const int rc = marg_blocked(w, bm, eps);
+      hipLaunchKernelGGL(k_marginalize, dim3(nw), dim3(256), MargLds::BYTES, stream_, d, mg_meta_.p, mg_idx_.p, mg_scr_.p, mg_out_.p, eps);
+    for (BlockedMeta &b : bmeta) {
+      const int rc = marg_blocked(b.w, b.mm, eps);
       if (rc != CTVIO_OK) return rc;
-      metas[w] = bm;
+      metas[b.w] = b.mm;
     }
     std::vector<double> outh(std::max<size_t>(outd, 1));
     HIPCHK(hipMemcpyAsync(outh.data(), mg_out_.p, sizeof(double) * std::max<size_t>(outd, 1), hipMemcpyDeviceToHost, stream_));
@@ -973,18 +972,18 @@ class SolverImpl {
       if (mm.n <= 0) continue;
       if (dbg_.marg_debug && w == (only >= 0 ? only : 0)) {
         std::fprintf(stderr, "[ctvio] marg window %d: m %d n %d sweeps %d / %d; off/dia per sweep (A'):", w, mm.m, mm.n, mm.sweeps_m, mm.sweeps_n);
-        for (int i = 0; i < 26 && i <= std::max(mm.sweeps_n, 0) + 1; ++i) std::fprintf(stderr, " %.2e", mm.trace[26 + i]);
+        for (int i = 0; i < JACOBI_TRACE && i <= std::max(mm.sweeps_n, 0) + 1; ++i) std::fprintf(stderr, " %.2e", mm.trace[JACOBI_TRACE + i]);
         std::fprintf(stderr, "\n");
       }
-      if (mm.status) { if (stalled) *stalled = w; return fail(CTVIO_ERR_HIP, "device eigen-solver did not converge (window " + std::to_string(w) + ")"); }
+      if (mm.status) { res.stalled = w; res.rc = fail(CTVIO_ERR_HIP, "device eigen-solver did not converge (window " + std::to_string(w) + ")"); return res; }
       std::memcpy(J0 + oj, outh.data() + mm.J0, sizeof(double) * (size_t)mm.n * mm.n);
       std::memcpy(r0 + orr, outh.data() + mm.r0, sizeof(double) * (size_t)mm.n);
       oj += (size_t)mm.n * mm.n; orr += (size_t)mm.n;
     }
-    return CTVIO_OK;
+    return res;
   }
   // Block two-sided Jacobi (csrc/marg_blocked.hpp) on B (D x D, nd real rows / columns) and V, one launch per phase; the host reads the
-  // per-block mass after every sweep and applies jacobi_packed's rule.  *sweeps: the sweeps done, or -1; off / diagonal mass per sweep in trace.
+  // per-block mass after every sweep and applies jacobi_converged (csrc/jacobi_core.hpp).  *sweeps: the sweeps done, or -1; off / diagonal mass per sweep in trace.
   int mb_jacobi(double *B, double *V, int D, int nd, double *Q, double *trace, int32_t *sweeps) {
     const int nb = D / MB_BLK, npair = nb / 2;
     std::vector<double> part((size_t)2 * nb);
@@ -996,9 +995,8 @@ class SolverImpl {
       HIPCHK(hipStreamSynchronize(stream_));
       double off = 0.0, d2 = 0.0;
       for (int b = 0; b < nb; ++b) { off += part[2 * b]; d2 += part[2 * b + 1]; }
-      if (sweep < 26) trace[sweep] = off / d2;
-      const double floor_rel = std::max(1e-28, 4.0 * (double)nd * (double)nd * 4.93e-32);
-      if (off <= 1e-60 || off <= 1e-32 * d2 || (sweep >= 12 && off <= floor_rel * d2 && off > 0.25 * prev_off)) { *sweeps = sweep; return CTVIO_OK; }
+      if (sweep < JACOBI_TRACE) trace[sweep] = off / d2;
+      if (jacobi_converged(off, d2, nd, sweep, prev_off)) { *sweeps = sweep; return CTVIO_OK; }
       prev_off = off;
       for (int s = 0; s < nb - 1; ++s) {
         hipLaunchKernelGGL(k_mb_pair, dim3(npair), dim3(256), 0, stream_, B, D, s, Q);
@@ -1008,30 +1006,32 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // The scratch of one blocked window (b.m, b.n, b.dm, b.dn set), every segment once: points b and *Q (the Q of a step's block pairs)
+  // into base and returns the doubles used; base = nullptr gives the size alone.
+  static size_t mb_scratch(MbWin &b, double *base, double **Q) {
+    const size_t dm2 = (size_t)b.dm * b.dm, dn2 = (size_t)b.dn * b.dn, mn1 = (size_t)b.m * (b.n + 1);
+    const std::pair<double **, size_t> segs[] = {{&b.Bm, dm2}, {&b.Vm, dm2}, {&b.Bn, dn2}, {&b.Vn, dn2}, {&b.G, mn1}, {&b.Y, mn1}, {&b.X, mn1},
+                                                 {&b.bp, (size_t)b.n}, {Q, (size_t)(std::max(b.dm, b.dn) / 64) * 64 * 64}};
+    size_t off = 0;
+    for (const auto &sg : segs) { *sg.first = base ? base + off : nullptr; off += sg.second; }
+    return off;
+  }
   // one window through the blocked path; J0 / r0 to mg_out_ at bm's offsets, status and sweeps into bm
   int marg_blocked(int w, MargMeta &bm, double eps) {
     const int m = bm.m, n = bm.n, dm = m > 0 ? mb_padded(m) : 0, dn = mb_padded(n), D = std::max(dm, dn);
     const size_t mn1 = (size_t)m * (n + 1);
-    const size_t need = 2 * (size_t)dm * dm + 2 * (size_t)dn * dn + 3 * mn1 + (size_t)n + (size_t)(D / 64) * 64 * 64;
+    MbWin b;
+    b.w = w; b.m = m; b.n = n; b.dm = dm; b.dn = dn;
+    double *Q;
+    const size_t need = mb_scratch(b, nullptr, &Q);
     HIPCHK(hipStreamSynchronize(stream_));   // (the scratch of the previous window may still be in use)
     HIPCHK(mb_scr_.alloc(need));
     HIPCHK(mb_part_.alloc((size_t)2 * D / MB_BLK));
     HIPCHK(mb_rank_.alloc((size_t)n));
     HIPCHK(poison(mb_scr_.p, sizeof(double) * need));
     HIPCHK(poison(mb_part_.p, sizeof(double) * 2 * D / MB_BLK));
-    MbWin b;
-    b.w = w; b.m = m; b.n = n; b.dm = dm; b.dn = dn;
+    mb_scratch(b, mb_scr_.p, &Q);
     b.im = mg_idx_.p + bm.idx0; b.ik = b.im + m;
-    double *p = mb_scr_.p;
-    b.Bm = p; p += (size_t)dm * dm;
-    b.Vm = p; p += (size_t)dm * dm;
-    b.Bn = p; p += (size_t)dn * dn;
-    b.Vn = p; p += (size_t)dn * dn;
-    b.G = p; p += mn1;
-    b.Y = p; p += mn1;
-    b.X = p; p += mn1;
-    b.bp = p; p += n;
-    double *Q = p;
     b.J0 = mg_out_.p + bm.J0; b.r0 = mg_out_.p + bm.r0; b.rank = mb_rank_.p;
     auto grid = [](long long cnt) { return dim3((unsigned)std::max<long long>(1, (cnt + 255) / 256)); };
     const long long gat = std::max<long long>((long long)dm * dm, std::max<long long>((long long)mn1, (long long)dn * dn));
@@ -1045,7 +1045,7 @@ class SolverImpl {
       hipLaunchKernelGGL(k_mb_x, grid((long long)mn1), dim3(256), 0, stream_, b);
     }
     hipLaunchKernelGGL(k_mb_reduce, grid((long long)dn * dn + n), dim3(256), 0, stream_, dev_, b);
-    if (const int rc = mb_jacobi(b.Bn, b.Vn, dn, n, Q, bm.trace + 26, &bm.sweeps_n)) return rc;
+    if (const int rc = mb_jacobi(b.Bn, b.Vn, dn, n, Q, bm.trace + JACOBI_TRACE, &bm.sweeps_n)) return rc;
     if (bm.sweeps_n < 0) status = 1;
     hipLaunchKernelGGL(k_mb_rank, grid(n), dim3(256), 0, stream_, b, eps);
     hipLaunchKernelGGL(k_mb_j0, grid((long long)n * n), dim3(256), 0, stream_, b, eps);
@@ -1057,14 +1057,12 @@ class SolverImpl {
     if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
     if (!role || !n_keep || !kept || !J0 || !r0 || !(eps >= 0)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     for (int i = 0; i < dev_.Utot; ++i) if (role[i] < -1 || role[i] > 1) return fail(CTVIO_ERR_INVALID, "role must be -1, 0 or 1");
-    bool too_large = false;
-    int stalled = -1;
     marg_ran_on_host_ = 0;
-    const int rc = marg_device(role, -1, eps, n_keep, kept, J0, r0, &too_large, &stalled, true);
-    if (rc != CTVIO_OK && stalled >= 0)
-      return fail(CTVIO_ERR_HIP, "device eigen-solver did not converge for window " + std::to_string(stalled) + ": call ctvio_marginalize for it (host factorisation)");
-    if (rc != CTVIO_OK) return rc;
-    if (too_large) return fail(CTVIO_ERR_INVALID, "a window has more than " + std::to_string(MARG_MAXD_BLOCKED) + " marginalised or kept unknowns");
+    const MargResult r = marg_device(role, -1, eps, n_keep, kept, J0, r0, true);
+    if (r.stalled >= 0)
+      return fail(CTVIO_ERR_HIP, "device eigen-solver did not converge for window " + std::to_string(r.stalled) + ": call ctvio_marginalize for it (host factorisation)");
+    if (r.rc != CTVIO_OK) return r.rc;
+    if (r.too_large) return fail(CTVIO_ERR_INVALID, "a window has more than " + std::to_string(MARG_MAXD_BLOCKED) + " marginalised or kept unknowns");
     return CTVIO_OK;
   }
   // one window; windows beyond the device eigen-solver's size (m or n > MARG_MAXD) take the host path (csrc/marginalize.hpp)
@@ -1080,12 +1078,10 @@ class SolverImpl {
       std::vector<int8_t> role_all((size_t)dev_.Utot, (int8_t)-1);
       std::copy(role, role + N, role_all.begin() + m.u0);
       std::vector<int32_t> nk((size_t)dev_.nwin), kv((size_t)dev_.Utot);
-      bool too_large = false;
-      int stalled = -1;
-      const int rc = marg_device(role_all.data(), id, eps, nk.data(), kv.data(), J0, r0, &too_large, &stalled);
-      if (rc != CTVIO_OK && stalled < 0) return rc;
+      const MargResult r = marg_device(role_all.data(), id, eps, nk.data(), kv.data(), J0, r0, false);
+      if (r.rc != CTVIO_OK && r.stalled < 0) return r.rc;
       // the in-LDS Jacobi sweep stalled above its (tight) off-diagonal bound: the host Householder / QL path below takes over
-      if (rc == CTVIO_OK && !too_large) {
+      if (r.rc == CTVIO_OK && !r.too_large) {
         *n_keep = nk[id];
         std::copy(kv.begin() + m.u0, kv.begin() + m.u0 + nk[id], kept);
         return CTVIO_OK;

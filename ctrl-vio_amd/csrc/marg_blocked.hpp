@@ -11,13 +11,14 @@
 //
 // BLOCK TWO-SIDED JACOBI.  The matrix (dimension nd) is padded to D = 64 * ceil(nd / 64) with decoupled zero rows and columns and
 // split into D / 32 column blocks.  One sweep is a round-robin tournament over the blocks (rr_pair): per step, every block pair
-// (p, q) is a 64 x 64 sub-problem; k_mb_pair loads it into LDS, runs one parallel cyclic Jacobi sweep on it (the rotation rule of
-// jacobi_packed) and forms its rotation Q explicitly; k_mb_update then applies A <- Q^T A Q to every off-diagonal 64 x 64 tile of the
-// step's pairs (one workgroup per tile: the tile depends only on itself and two Q, so the update is in place) and V <- V Q.  The
-// diagonal tiles keep the rotated matrix of the LDS sweep.  A padded column meets only zero entries, so its rotations are the
-// identity: it stays an exact zero eigenpair at its own index and is dropped.  After every sweep k_mb_mass sums the off-diagonal
-// and diagonal mass per column block; the host adds the partials in block order and applies jacobi_packed's (the oracle's)
-// convergence rule.  No floating-point atomics and no cross-workgroup synchronisation: equal inputs give equal bits.
+// (p, q) is a 64 x 64 sub-problem; k_mb_pair loads it into LDS, runs one parallel cyclic Jacobi sweep on it (jacobi_core.hpp: the
+// tournament, rotation rule and 2 x 2-block updates of jacobi_packed) and forms its rotation Q explicitly; k_mb_update then applies
+// A <- Q^T A Q to every off-diagonal 64 x 64 tile of the step's pairs (one workgroup per tile: the tile depends only on itself and
+// two Q, so the update is in place) and V <- V Q.  The diagonal tiles keep the rotated matrix of the LDS sweep.  A padded column meets
+// only zero entries, so its rotations are the identity: it stays an exact zero eigenpair at its own index and is dropped.  After every
+// sweep k_mb_mass sums the off-diagonal and diagonal mass per column block; the host adds the partials in block order and applies
+// jacobi_converged (jacobi_core.hpp), as jacobi_packed does.  No floating-point atomics and no cross-workgroup synchronisation: equal
+// inputs give equal bits.
 #pragma once
 #include "marg_device.hpp"
 
@@ -38,14 +39,6 @@ struct MbWin {
   int32_t *rank;
 };
 
-// entry (i, j) of the window's normal equations [Hpp W^T; W diag(Hll)] (k_marginalize's dense build, one entry)
-__device__ __forceinline__ double mb_elem(const Dev &d, const WinMeta &wm, int cset, int i, int j) {
-  const int P = wm.P;
-  if (i < P && j < P) return d.HppS[cset][wm.H0 + (long long)max(i, j) * wm.ldh + min(i, j)];
-  if (i >= P && j >= P) return (i == j) ? d.HllS[cset][wm.lm0 + i - P] : 0.0;
-  return d.WS[cset][wm.W0 + (long long)d.lm_pos[wm.lm0 + max(i, j) - P] * wm.ldw + min(i, j)];
-}
-
 __global__ __launch_bounds__(256) void k_mb_gather(Dev d, MbWin b) {
   const WinMeta &wm = d.wins[b.w];
   const int cset = d.lm[b.w].cur;
@@ -54,12 +47,12 @@ __global__ __launch_bounds__(256) void k_mb_gather(Dev d, MbWin b) {
   const int m = b.m, n = b.n;
   for (long long e = t0; e < (long long)b.dm * b.dm; e += stride) {
     const int i = (int)(e / b.dm), j = (int)(e % b.dm);
-    b.Bm[e] = (i < m && j < m) ? mb_elem(d, wm, cset, b.im[i], b.im[j]) : 0.0;
+    b.Bm[e] = (i < m && j < m) ? normal_eq_entry(d, wm, cset, b.im[i], b.im[j]) : 0.0;
     b.Vm[e] = (i == j) ? 1.0 : 0.0;
   }
   for (long long e = t0; e < (long long)m * (n + 1); e += stride) {
     const int i = (int)(e / (n + 1)), c = (int)(e % (n + 1));
-    b.G[e] = c < n ? mb_elem(d, wm, cset, b.im[i], b.ik[c]) : g[b.im[i]];
+    b.G[e] = c < n ? normal_eq_entry(d, wm, cset, b.im[i], b.ik[c]) : g[b.im[i]];
   }
   for (long long e = t0; e < (long long)b.dn * b.dn; e += stride) b.Vn[e] = (e / b.dn == e % b.dn) ? 1.0 : 0.0;
 }
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(256) void k_mb_mass(const double *B, int D, double 
 }
 
 // one workgroup per block pair of step s: one parallel cyclic Jacobi sweep on the 64 x 64 sub-problem in LDS (packed lower triangle,
-// jacobi_packed's rotation rule and 2 x 2-block update), Q accumulated explicitly; the rotated sub-problem goes back to B, Q to Qs
+// one sweep of jacobi_packed without its dummy player), Q accumulated explicitly; the rotated sub-problem goes back to B, Q to Qs
 __global__ __launch_bounds__(256) void k_mb_pair(double *B, int D, int s, double *Qs) {
   constexpr int W = 2 * MB_BLK, NPK = W * (W + 1) / 2, HALF = W / 2, NBLK = HALF * (HALF + 1) / 2;
   __shared__ double Apk[NPK];
@@ -95,10 +88,8 @@ __global__ __launch_bounds__(256) void k_mb_pair(double *B, int D, int s, double
   int bp, bq;
   mb_group(D / MB_BLK, s, blockIdx.x, bp, bq);
   for (int e = tid; e < NPK; e += 256) {
-    int i = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-    while ((i + 1) * (i + 2) / 2 <= e) ++i;
-    while (i * (i + 1) / 2 > e) --i;
-    const int j = e - i * (i + 1) / 2;
+    int i, j;
+    tri_decode(e, i, j);
     Apk[e] = B[(long long)mb_gl(bp, bq, i) * D + mb_gl(bp, bq, j)];
   }
   for (int e = tid; e < W * W; e += 256) Q[e] = (e / W == e % W) ? 1.0 : 0.0;
@@ -107,47 +98,22 @@ __global__ __launch_bounds__(256) void k_mb_pair(double *B, int D, int s, double
     if (tid < HALF) {
       int p, q;
       rr_pair(W, st, tid, p, q);
-      double c = 1.0, sn = 0.0;
-      const double apq = Apk[pk_idx(q, p)];
-      if (apq != 0.0) {
-        const double app = Apk[pk_idx(p, p)], aqq = Apk[pk_idx(q, q)];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        c = 1.0 / sqrt(tt * tt + 1.0); sn = tt * c;
-      }
+      double c, sn;
+      jacobi_cs(Apk, p, q, c, sn);
       cs[2 * tid] = c; cs[2 * tid + 1] = sn; pq[2 * tid] = p; pq[2 * tid + 1] = q;
     }
     __syncthreads();
     for (int e = tid; e < NBLK; e += 256) {
-      int I = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-      while ((I + 1) * (I + 2) / 2 <= e) ++I;
-      while (I * (I + 1) / 2 > e) --I;
-      const int J = e - I * (I + 1) / 2;
+      int I, J;
+      tri_decode(e, I, J);
       const int p1 = pq[2 * I], q1 = pq[2 * I + 1], p2 = pq[2 * J], q2 = pq[2 * J + 1];
       const double c1 = cs[2 * I], s1 = cs[2 * I + 1], c2 = cs[2 * J], s2 = cs[2 * J + 1];
-      if (I == J) {
-        const double app = Apk[pk_idx(p1, p1)], aqq = Apk[pk_idx(q1, q1)], apq = Apk[pk_idx(q1, p1)];
-        Apk[pk_idx(p1, p1)] = c1 * c1 * app - 2.0 * c1 * s1 * apq + s1 * s1 * aqq;
-        Apk[pk_idx(q1, q1)] = s1 * s1 * app + 2.0 * c1 * s1 * apq + c1 * c1 * aqq;
-        Apk[pk_idx(q1, p1)] = 0.0;
-        continue;
-      }
-      const double a_pp = Apk[pk_idx(p1, p2)], a_pq = Apk[pk_idx(p1, q2)];
-      const double a_qp = Apk[pk_idx(q1, p2)], a_qq = Apk[pk_idx(q1, q2)];
-      const double t_pp = c2 * a_pp - s2 * a_pq, t_pq = s2 * a_pp + c2 * a_pq;   // columns (pair J)
-      const double t_qp = c2 * a_qp - s2 * a_qq, t_qq = s2 * a_qp + c2 * a_qq;
-      Apk[pk_idx(p1, p2)] = c1 * t_pp - s1 * t_qp;                                // rows (pair I)
-      Apk[pk_idx(p1, q2)] = c1 * t_pq - s1 * t_qq;
-      Apk[pk_idx(q1, p2)] = s1 * t_pp + c1 * t_qp;
-      Apk[pk_idx(q1, q2)] = s1 * t_pq + c1 * t_qq;
+      if (I != J) jacobi_block_update<false>(Apk, W, p1, q1, p2, q2, c1, s1, c2, s2);
+      else jacobi_diag_update(Apk, p1, q1, c1, s1);
     }
     for (int e = tid; e < W * HALF; e += 256) {   // Q <- Q R (columns p, q of every row)
       const int row = e / HALF, i = e % HALF;
-      const int p = pq[2 * i], q = pq[2 * i + 1];
-      const double c = cs[2 * i], sn = cs[2 * i + 1];
-      const double vp = Q[row * W + p], vq = Q[row * W + q];
-      Q[row * W + p] = c * vp - sn * vq;
-      Q[row * W + q] = sn * vp + c * vq;
+      rotate_cols(Q, row * W + pq[2 * i], row * W + pq[2 * i + 1], cs[2 * i], cs[2 * i + 1]);
     }
     __syncthreads();
   }
@@ -170,10 +136,8 @@ __global__ __launch_bounds__(256) void k_mb_update(double *B, double *V, int D, 
   double *M;
   const double *Ql, *Qr = nullptr;
   if (it < noff) {
-    int k = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)it)) * 0.5f);
-    while (k * (k - 1) / 2 > it) --k;
-    while ((k + 1) * k / 2 <= it) ++k;
-    const int l = it - k * (k - 1) / 2;
+    int k, l;
+    tri_decode_strict(it, k, l);
     mb_group(nb, s, k, rp, rq);
     mb_group(nb, s, l, cp, cq);
     M = B; Qr = Qs + (size_t)k * W * W; Ql = Qs + (size_t)l * W * W;
@@ -256,7 +220,7 @@ __global__ __launch_bounds__(256) void k_mb_reduce(Dev d, MbWin b) {
     const int r = (int)(e / dn), c = (int)(e % dn);
     double v = 0.0;
     if (r < n && c < n) {
-      double s1 = mb_elem(d, wm, cset, b.ik[r], b.ik[c]), s2 = mb_elem(d, wm, cset, b.ik[c], b.ik[r]);
+      double s1 = normal_eq_entry(d, wm, cset, b.ik[r], b.ik[c]), s2 = normal_eq_entry(d, wm, cset, b.ik[c], b.ik[r]);
       for (int i = 0; i < b.m; ++i) {
         s1 -= b.G[(long long)i * n1 + r] * b.X[(long long)i * n1 + c];
         s2 -= b.G[(long long)i * n1 + c] * b.X[(long long)i * n1 + r];

@@ -9,8 +9,10 @@
 // round-robin tournament are rotated at once -- every 2 x 2 block (pair I, pair J) of the matrix is owned by one thread,
 // so no entry is touched twice in a step.  The rotation angles are recorded in HBM scratch; the eigenvectors are then
 // rebuilt by replaying them on row slabs of the identity that fit in the same LDS (V itself would not: 180 KB).
+// Tournament, rotation rule, 2 x 2-block updates and convergence rule: jacobi_core.hpp, shared with the blocked path (marg_blocked.hpp).
 #pragma once
 #include "device_types.hpp"
+#include "jacobi_core.hpp"
 
 namespace ctv {
 
@@ -18,24 +20,32 @@ constexpr int MARG_MAXD = 180;        // largest eigen-problem: packed lower tri
 constexpr int MARG_MAX_SWEEPS = 24;   // cyclic Jacobi converges quadratically; 8-11 sweeps are typical at n = 150
 
 struct MargMeta {
-  int32_t N, P, m, n;                 // unknowns, pose unknowns, marginalised, kept
+  int32_t N, m, n;                    // unknowns, marginalised, kept
   int32_t idx0;                       // offset of [im (m) | ik (n)] in the int scratch
   int32_t status;                     // out: 0 ok, 1 = Jacobi did not converge
   int64_t A0, V0, X0, Y0, rot0, b0;   // offsets (doubles) into the scratch: A full N x N | Vm m x m | X, Y m x (n+1) | rotations | b' n
   int64_t J0, r0;                     // offsets (doubles) into the outputs
   int32_t sweeps_m, sweeps_n;         // out: Jacobi sweeps of the two eigen-problems
-  double trace[2 * 26];               // out: off / diagonal mass before every sweep (diagnostics)
+  double trace[2 * JACOBI_TRACE];     // out: off / diagonal mass before every sweep (diagnostics): Amm, then A'
 };
 
-__device__ __forceinline__ int pk_idx(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+// LDS of k_marginalize: offsets in doubles (the two int arrays last), and the bytes a launch asks for
+struct MargLds {
+  static constexpr int NPK = MARG_MAXD * (MARG_MAXD + 1) / 2;
+  static constexpr int APK = 0, EV = APK + NPK;                     // [NPK] packed matrix / eigenvector slab; [MARG_MAXD] eigenvalues
+  static constexpr int CS = EV + MARG_MAXD, RED = CS + MARG_MAXD;   // [MARG_MAXD] (c, s) of the current step; [512] mass reduction
+  static constexpr int RACC = RED + 512, PQ = RACC + MARG_MAXD;     // [MARG_MAXD] r0 accumulators; int pq[MARG_MAXD], rank[MARG_MAXD]
+  static constexpr size_t BYTES = (PQ + MARG_MAXD) * sizeof(double) + 2 * MARG_MAXD * sizeof(int);   // (with the MARG_MAXD spare doubles
+};                                                                                                   //  every launch has asked for)
+constexpr int MARG_LDS_LIMIT = 160 * 1024;   // hipFuncAttributeMaxDynamicSharedMemorySize of k_marginalize: the LDS of a gfx950 CU
+static_assert(MargLds::BYTES <= MARG_LDS_LIMIT, "k_marginalize's LDS layout exceeds a CU");
 
-// round-robin tournament over np players (np even), step s in [0, np-1), pair i in [0, np/2): (p < q)
-__device__ __forceinline__ void rr_pair(int np, int s, int i, int &p, int &q) {
-  const int r = np - 1;
-  int a, b;
-  if (i == 0) { a = r; b = s; }
-  else { a = (s + i) % r; b = (s + r - i) % r; }
-  p = min(a, b); q = max(a, b);
+// entry (i, j) of a window's normal equations [Hpp W^T; W diag(Hll)] in set cset (rows of W: sorted landmark order)
+__device__ __forceinline__ double normal_eq_entry(const Dev &d, const WinMeta &wm, int cset, int i, int j) {
+  const int P = wm.P;
+  if (i < P && j < P) return d.HppS[cset][wm.H0 + (long long)max(i, j) * wm.ldh + min(i, j)];
+  if (i >= P && j >= P) return (i == j) ? d.HllS[cset][wm.lm0 + i - P] : 0.0;
+  return d.WS[cset][wm.W0 + (long long)d.lm_pos[wm.lm0 + max(i, j) - P] * wm.ldw + min(i, j)];
 }
 
 // Cyclic parallel Jacobi on the packed symmetric matrix Apk (dimension nd) in LDS; (c, s) of every rotation goes to rot
@@ -56,57 +66,28 @@ __device__ inline int jacobi_packed(double *Apk, int nd, double *rot, double *cs
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) { if (tid < st) { red[tid] += red[tid + st]; red[256 + tid] += red[256 + tid + st]; } __syncthreads(); }
     const double off = red[0], d2 = red[256];
-    if (tid == 0 && sweep < 26) trace[sweep] = off / d2;
+    if (tid == 0 && sweep < JACOBI_TRACE) trace[sweep] = off / d2;
     __syncthreads();
-    // converged: the oracle's test (one full sweep beyond ~1e-29 is what resolves the noise-level eigenvalues of a rank-deficient
-    // A', which decide what falls under eps); stagnation just above it after many sweeps is accepted as the rounding floor
-    // (the floor of the off-diagonal mass is ~ n^2 eps^2 d2: at n = 180 that is 1.6e-27 d2, above a fixed 1e-28)
-    const double floor_rel = fmax(1e-28, 4.0 * (double)nd * (double)nd * 4.93e-32);
-    if (off <= 1e-60 || off <= 1e-32 * d2 || (sweep >= 12 && off <= floor_rel * d2 && off > 0.25 * prev_off)) return sweep;
+    if (jacobi_converged(off, d2, nd, sweep, prev_off)) return sweep;
     prev_off = off;
     for (int s = 0; s < steps; ++s) {
       if (tid < half) {
         int p, q;
         rr_pair(np, s, tid, p, q);
         double c = 1.0, sn = 0.0;
-        if (q < nd) {
-          const double apq = Apk[pk_idx(q, p)];
-          if (apq != 0.0) {
-            const double app = Apk[pk_idx(p, p)], aqq = Apk[pk_idx(q, q)];
-            const double theta = (aqq - app) / (2.0 * apq);
-            const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            c = 1.0 / sqrt(tt * tt + 1.0); sn = tt * c;
-          }
-        }
+        if (q < nd) jacobi_cs(Apk, p, q, c, sn);
         cs[2 * tid] = c; cs[2 * tid + 1] = sn; pq[2 * tid] = p; pq[2 * tid + 1] = q;
         rot[((size_t)sweep * steps + s) * half * 2 + 2 * tid] = c;
         rot[((size_t)sweep * steps + s) * half * 2 + 2 * tid + 1] = sn;
       }
       __syncthreads();
       for (int e = tid; e < nblk; e += 256) {
-        int I = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-        while ((I + 1) * (I + 2) / 2 <= e) ++I;
-        while (I * (I + 1) / 2 > e) --I;
-        const int J = e - I * (I + 1) / 2;
+        int I, J;
+        tri_decode(e, I, J);
         const int p1 = pq[2 * I], q1 = pq[2 * I + 1], p2 = pq[2 * J], q2 = pq[2 * J + 1];
         const double c1 = cs[2 * I], s1 = cs[2 * I + 1], c2 = cs[2 * J], s2 = cs[2 * J + 1];
-        if (I == J) {
-          if (q1 >= nd) continue;
-          const double app = Apk[pk_idx(p1, p1)], aqq = Apk[pk_idx(q1, q1)], apq = Apk[pk_idx(q1, p1)];
-          Apk[pk_idx(p1, p1)] = c1 * c1 * app - 2.0 * c1 * s1 * apq + s1 * s1 * aqq;
-          Apk[pk_idx(q1, q1)] = s1 * s1 * app + 2.0 * c1 * s1 * apq + c1 * c1 * aqq;
-          Apk[pk_idx(q1, p1)] = 0.0;
-          continue;
-        }
-        const bool vq1 = q1 < nd, vq2 = q2 < nd;   // a dummy player (odd nd) has no row / column
-        const double a_pp = Apk[pk_idx(p1, p2)], a_pq = vq2 ? Apk[pk_idx(p1, q2)] : 0.0;
-        const double a_qp = vq1 ? Apk[pk_idx(q1, p2)] : 0.0, a_qq = (vq1 && vq2) ? Apk[pk_idx(q1, q2)] : 0.0;
-        const double t_pp = c2 * a_pp - s2 * a_pq, t_pq = s2 * a_pp + c2 * a_pq;   // columns (pair J)
-        const double t_qp = c2 * a_qp - s2 * a_qq, t_qq = s2 * a_qp + c2 * a_qq;
-        Apk[pk_idx(p1, p2)] = c1 * t_pp - s1 * t_qp;                                // rows (pair I)
-        if (vq2) Apk[pk_idx(p1, q2)] = c1 * t_pq - s1 * t_qq;
-        if (vq1) Apk[pk_idx(q1, p2)] = s1 * t_pp + c1 * t_qp;
-        if (vq1 && vq2) Apk[pk_idx(q1, q2)] = s1 * t_pq + c1 * t_qq;
+        if (I != J) jacobi_block_update<true>(Apk, nd, p1, q1, p2, q2, c1, s1, c2, s2);
+        else if (q1 < nd) jacobi_diag_update(Apk, p1, q1, c1, s1);
       }
       __syncthreads();
     }
@@ -132,10 +113,7 @@ __device__ inline void jacobi_replay(double *slab, int nd, int r0, int nr, const
       int p, q;
       rr_pair(np, s, i, p, q);
       if (q >= nd) continue;
-      const double c = cs[2 * i], sn = cs[2 * i + 1];
-      const double vp = slab[row * nd + p], vq = slab[row * nd + q];
-      slab[row * nd + p] = c * vp - sn * vq;
-      slab[row * nd + q] = sn * vp + c * vq;
+      rotate_cols(slab, row * nd + p, row * nd + q, cs[2 * i], cs[2 * i + 1]);
     }
     __syncthreads();
   }
@@ -145,43 +123,25 @@ __global__ __launch_bounds__(256) void k_marginalize(Dev d, MargMeta *metas, con
   const int w = blockIdx.x, tid = threadIdx.x;
   MargMeta &mm = metas[w];
   const WinMeta &wm = d.wins[w];
-  const int N = mm.N, P = mm.P, m = mm.m, n = mm.n;
+  const int N = mm.N, m = mm.m, n = mm.n;
   if (n <= 0) return;
   extern __shared__ __attribute__((aligned(16))) double sml[];
-  constexpr int NPK = MARG_MAXD * (MARG_MAXD + 1) / 2;
-  double *Apk = sml;                   // packed matrix / eigenvector slab
-  double *ev = Apk + NPK;              // [MARG_MAXD] eigenvalues
-  double *cs = ev + MARG_MAXD;         // [MARG_MAXD] (c, s) of the current step
-  double *red = cs + MARG_MAXD;        // [512]
-  double *racc = red + 512;            // [MARG_MAXD] r0 accumulators
-  int *pq = reinterpret_cast<int *>(racc + MARG_MAXD);   // [MARG_MAXD]
-  int *rank = pq + MARG_MAXD;          // [MARG_MAXD]
+  constexpr int NPK = MargLds::NPK;
+  double *Apk = sml + MargLds::APK, *ev = sml + MargLds::EV, *cs = sml + MargLds::CS, *red = sml + MargLds::RED, *racc = sml + MargLds::RACC;
+  int *pq = reinterpret_cast<int *>(sml + MargLds::PQ), *rank = pq + MARG_MAXD;
   const int32_t *im = iscr + mm.idx0, *ik = im + m;
   double *A = scr + mm.A0, *Vm = scr + mm.V0, *X = scr + mm.X0, *Y = scr + mm.Y0, *rot = scr + mm.rot0, *bp = scr + mm.b0;
   const int cset = d.lm[blockIdx.x].cur;   // the normal-equation set that holds the linearisation at the current state
   const double *g = d.gS[cset] + wm.u0;
   // ---- dense symmetric A (N x N) from the structured normal equations: [Hpp W^T; W diag(Hll)]
-  {
-    const double *H = d.HppS[cset] + wm.H0;
-    const double *Wp = d.WS[cset] + wm.W0;
-    for (long long e = tid; e < (long long)N * N; e += 256) {
-      const int i = (int)(e / N), j = (int)(e % N);
-      double v;
-      if (i < P && j < P) v = H[(long long)max(i, j) * wm.ldh + min(i, j)];
-      else if (i >= P && j >= P) v = (i == j) ? d.HllS[cset][wm.lm0 + i - P] : 0.0;
-      else v = Wp[(long long)d.lm_pos[wm.lm0 + max(i, j) - P] * wm.ldw + min(i, j)];   // (rows of W: sorted landmark order)
-      A[e] = v;
-    }
-  }
+  for (long long e = tid; e < (long long)N * N; e += 256) A[e] = normal_eq_entry(d, wm, cset, (int)(e / N), (int)(e % N));
   __syncthreads();
   int status = 0;
   // ---- Amm = Vm diag(em) Vm^T
   if (m > 0) {
     for (int e = tid; e < m * (m + 1) / 2; e += 256) {
-      int i = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-      while ((i + 1) * (i + 2) / 2 <= e) ++i;
-      while (i * (i + 1) / 2 > e) --i;
-      const int j = e - i * (i + 1) / 2;
+      int i, j;
+      tri_decode(e, i, j);
       Apk[e] = A[(long long)im[i] * N + im[j]];
     }
     __syncthreads();
@@ -220,10 +180,8 @@ __global__ __launch_bounds__(256) void k_marginalize(Dev d, MargMeta *metas, con
   }
   // ---- A' = Arr - Arm X (symmetrised, packed into LDS), b' = br - Arm x_b
   for (int e = tid; e < n * (n + 1) / 2; e += 256) {
-    int r = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
-    while ((r + 1) * (r + 2) / 2 <= e) ++r;
-    while (r * (r + 1) / 2 > e) --r;
-    const int c = e - r * (r + 1) / 2;
+    int r, c;
+    tri_decode(e, r, c);
     double s1 = A[(long long)ik[r] * N + ik[c]], s2 = A[(long long)ik[c] * N + ik[r]];
     for (int i = 0; i < m; ++i) {
       s1 -= A[(long long)ik[r] * N + im[i]] * X[(long long)i * (n + 1) + c];
@@ -239,7 +197,7 @@ __global__ __launch_bounds__(256) void k_marginalize(Dev d, MargMeta *metas, con
   __threadfence_block();
   __syncthreads();
   // ---- A' = V S V^T
-  const int sweeps = jacobi_packed(Apk, n, rot, cs, pq, red, mm.trace + 26);
+  const int sweeps = jacobi_packed(Apk, n, rot, cs, pq, red, mm.trace + JACOBI_TRACE);
   if (tid == 0) mm.sweeps_n = sweeps;
   if (sweeps < 0) status = 1;
   for (int i = tid; i < n; i += 256) { ev[i] = Apk[i * (i + 3) / 2]; racc[i] = 0.0; }

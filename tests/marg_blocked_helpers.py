@@ -1,5 +1,7 @@
 """Helpers of the blocked marginalisation tests (csrc/marg_blocked.hpp): the config-5 drop sets of the issue's windows, a NumPy
-model of the device's block two-sided Jacobi schedule, and the yardsticks a prior is compared with."""
+model of the device's block two-sided Jacobi schedule, and the yardsticks a prior is compared with.  The model restates what
+csrc/jacobi_core.hpp holds for both device paths (rr_pair, jacobi_cs, jacobi_converged) independently: it does not call the C++, and
+tests/test_jacobi_core_host.py compares the two."""
 import importlib
 
 import numpy as np
@@ -42,7 +44,7 @@ def config5_window(seed=1500):
 # ---------------------------------------------------------------- model of the device schedule
 
 def rr_pair(np_, s, i):
-    """marg_device.hpp rr_pair: round-robin tournament over np_ players, step s, pair i -> (p < q)."""
+    """jacobi_core.hpp rr_pair: round-robin tournament over np_ players, step s, pair i -> (p < q)."""
     r = np_ - 1
     if i == 0:
         a, b = r, s
@@ -51,21 +53,27 @@ def rr_pair(np_, s, i):
     return min(a, b), max(a, b)
 
 
+def jacobi_cs(app, aqq, apq):
+    """jacobi_core.hpp jacobi_cs on arrays of pivots: (c, s) of the rotation that annihilates apq; the identity where apq = 0."""
+    c = np.ones(apq.shape); sn = np.zeros(apq.shape)
+    nz = apq != 0.0
+    theta = (aqq[nz] - app[nz]) / (2.0 * apq[nz])
+    with np.errstate(over="ignore"):               # theta^2 = inf gives tt = 0, as on the device
+        tt = np.where(theta >= 0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+    c[nz] = 1.0 / np.sqrt(tt * tt + 1.0); sn[nz] = tt * c[nz]
+    return c, sn
+
+
 def inner_sweep(T):
-    """One parallel cyclic Jacobi sweep on the 64 x 64 sub-problem T (in place), the rotation rule of jacobi_packed.  Returns Q with
-    T_out = Q^T T_in Q."""
+    """One parallel cyclic Jacobi sweep on the 64 x 64 sub-problem T (in place): k_mb_pair, i.e. one sweep of jacobi_packed (jacobi_cs,
+    jacobi_diag_update, jacobi_block_update, rotate_cols of jacobi_core.hpp).  Returns Q with T_out = Q^T T_in Q."""
     d = T.shape[0]
     Q = np.eye(d)
     pairs = [np.array([rr_pair(d, s, i) for i in range(d // 2)]) for s in range(d - 1)]
     for pq in pairs:
         p, q = pq[:, 0], pq[:, 1]
         apq, app, aqq = T[q, p], T[p, p], T[q, q]
-        c = np.ones(d // 2); sn = np.zeros(d // 2)
-        nz = apq != 0.0
-        theta = (aqq[nz] - app[nz]) / (2.0 * apq[nz])
-        with np.errstate(over="ignore"):           # theta^2 = inf gives tt = 0, as on the device
-            tt = np.where(theta >= 0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
-        c[nz] = 1.0 / np.sqrt(tt * tt + 1.0); sn[nz] = tt * c[nz]
+        c, sn = jacobi_cs(app, aqq, apq)
         dpp = c * c * app - 2.0 * c * sn * apq + sn * sn * aqq
         dqq = sn * sn * app + 2.0 * c * sn * apq + c * c * aqq
         for M in (T,):
@@ -80,7 +88,7 @@ def inner_sweep(T):
 
 
 def converged(off, d2, nd, sweep, prev_off):
-    """jacobi_packed's (the oracle's) rule, with its rounding-floor clause."""
+    """jacobi_core.hpp jacobi_converged (the oracle's rule, with its rounding-floor clause), restated."""
     floor_rel = max(1e-28, 4.0 * nd * nd * 4.93e-32)
     return off <= 1e-60 or off <= 1e-32 * d2 or (sweep >= 12 and off <= floor_rel * d2 and off > 0.25 * prev_off)
 

@@ -165,6 +165,31 @@ def test_blocked_path_agrees_with_lds_path(cv, monkeypatch):
     assert eS <= 1e-6                                 # measured 2.8e-8: unknowns with a prior diagonal near eps (see the mixed-batch test)
 
 
+@pytest.mark.parametrize("m,n", [(7, 5), (0, 9), (1, 1), (12, 12)])
+def test_small_dimensions_on_both_paths(cv, oracle, monkeypatch, m, n):
+    """The smallest shapes at which what the two paths share (csrc/jacobi_core.hpp) can go wrong, each through the in-LDS path and, with
+    CTVIO_MARG_BLOCKED=1, through the blocked path (D = 64: one block pair, no off-diagonal tile, k_mb_update on V only).  m 7 / n 5: both
+    dimensions odd (the dummy player); m 0 / n 9: no elimination; m 1 / n 1: one tournament step, half = 1; m 12 / n 12: even.  The oracle,
+    NumPy's eigh restatement and the block-Jacobi model agree on all four to 1.2e-14 at full rank: the bounds leave seven orders."""
+    w = cv.synth.make_window("tiny", seed=7)
+    w.cauchy_a = 1.0
+    assert w.N == 115
+    role = np.full(w.N, -1, np.int8)
+    role[:m] = 1
+    role[m:m + n] = 0
+    ref = oracle.OracleWindow(w.copy()).marginalize(role, 1e-8)
+    kept = {}
+    for path in ("in-LDS", "blocked"):
+        if path == "blocked":
+            monkeypatch.setenv("CTVIO_MARG_BLOCKED", "1")
+        with cv.Solver() as s:
+            s.set_windows([w.copy()])
+            (kept[path], J0, r0), = s.marginalize_batch([role])
+            assert not s.marginalize_ran_on_host()
+        check_vs_oracle(kept[path], J0, r0, *ref, f"tiny m {m} / n {n}, {path} path")
+    assert np.array_equal(kept["in-LDS"], kept["blocked"])
+
+
 def test_blocked_faster_than_host_leg(cv, c5):
     w, role, _, t_oracle = c5
     with cv.Solver() as s:
