@@ -155,6 +155,7 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_misc, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));   // (+ 2 KB of static LDS)
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     return CTVIO_OK;
   }
   int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
@@ -575,7 +576,7 @@ class SolverImpl {
     const LaunchPlan &p = plan_;
     const int nw = d.nwin;
     ph_begin(PH_SCHUR);
-    launch_schur();
+    launch_schur(d);
     ph_end();
     ph_begin(PH_CHOL);
     switch (p.chol) {
@@ -595,8 +596,7 @@ class SolverImpl {
     else hipLaunchKernelGGL((k_step_finish<4>), dim3(nw), dim3(256), (size_t)d.maxP * sizeof(double), stream_, d);
     ph_end();
   }
-  void launch_schur() {
-    const Dev &d = dev_;
+  void launch_schur(const Dev &d) {   // (d: dev_, or the covariance's copy of it)
     const LaunchPlan &p = plan_;
     const int ngrid = p.schur_tiles * 8 * ((d.nwin + 7) / 8);   // (the tile kernels)
     switch (p.schur) {
@@ -1209,6 +1209,132 @@ class SolverImpl {
     if (err) return fail(CTVIO_ERR_INVALID, "query time outside the spline");
     return CTVIO_OK;
   }
+  // ---------------------------------------------------------------------------------------- marginal covariances
+  // ctvio_covariance_batch / ctvio_covariance (only >= 0: that window alone, n_sel / sel / outputs are its own).  The normal equations of the
+  // current state (as ctvio_linearize forms them), then Schur complement and panel Cholesky on a COPY of Dev -- per-call activity mask, zero
+  // damping, every tile of S written -- and the kernels of csrc/kernels_cov.hpp.  dev_, plan_ and the captured graph are not touched; the scratch
+  // is a grow-only buffer of its own (its size follows the call's selections, not the upload).
+  static constexpr int COV_MAX_SEL = 64;
+  int covariance(int only, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
+    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    const int nw = dev_.nwin;
+    if (only >= nw) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (!n_sel) return fail(CTVIO_ERR_INVALID, "null n_sel");
+    const int wbeg = only >= 0 ? only : 0, wend = only >= 0 ? only + 1 : nw;
+    // ---- the call's tiles: selections first, then (with var_rho) every 16 consecutive sorted rows of W
+    std::vector<CovTile> tiles;
+    std::vector<CovWin> cwins;
+    size_t nsel_tot = 0, ycount = 0, ncov = 0;
+    {
+      std::vector<uint8_t> seen;
+      for (int w = wbeg; w < wend; ++w) {
+        const WinMeta &m = meta_[w];
+        const int ns = n_sel[w - wbeg];
+        if (ns < 0 || ns > COV_MAX_SEL) return fail(CTVIO_ERR_INVALID, "window " + std::to_string(w) + ": n_sel outside [0, " + std::to_string(COV_MAX_SEL) + "]");
+        if (ns && (!sel || !cov)) return fail(CTVIO_ERR_INVALID, "null sel / cov with a non-empty selection");
+        seen.assign((size_t)m.P, 0);
+        for (int i = 0; i < ns; ++i) {
+          const int j = sel[nsel_tot + i];
+          if (j < 0 || j >= m.P) return fail(CTVIO_ERR_INVALID, "window " + std::to_string(w) + ": selected unknown outside [0, P)");
+          if (seen[j]) return fail(CTVIO_ERR_INVALID, "window " + std::to_string(w) + ": unknown " + std::to_string(j) + " selected twice");
+          seen[j] = 1;
+        }
+        if (ns) {
+          CovWin cw{w, ns, (int32_t)nsel_tot, 0, (long long)ycount, (long long)ncov};
+          cwins.push_back(cw);
+          for (int t = 0; 16 * t < ns; ++t) {
+            tiles.push_back(CovTile{w, 0, (int32_t)nsel_tot + 16 * t, std::min(16, ns - 16 * t), (long long)ycount});
+            ycount += (size_t)16 * m.P;
+          }
+        }
+        if (var_rho)
+          for (int r = 0; r < m.L; r += 16) tiles.push_back(CovTile{w, 1, r, std::min(16, m.L - r), 0});
+        nsel_tot += (size_t)ns; ncov += (size_t)ns * ns;
+      }
+    }
+    // ---- scratch: [mask Utot | excl Utot | sel | tiles | windows | Y | cov | var_rho (Ltot, batch order)]
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_excl = up((size_t)dev_.Utot), o_sel = 2 * o_excl, o_tiles = o_sel + up(sizeof(int32_t) * nsel_tot), o_wins = o_tiles + up(sizeof(CovTile) * tiles.size());
+    const size_t o_y = o_wins + up(sizeof(CovWin) * cwins.size()), o_cov = o_y + up(sizeof(double) * ycount), o_var = o_cov + up(sizeof(double) * ncov);
+    const size_t nvar = var_rho ? (size_t)dev_.Ltot : 0, total = o_var + up(sizeof(double) * nvar);
+    HIPCHK(hipStreamSynchronize(stream_));
+    HIPCHK(cov_dev_.alloc(total));
+    char *ds = cov_dev_.p;
+    uint8_t *mask = reinterpret_cast<uint8_t *>(ds), *excl = mask + o_excl;
+    const int32_t *dsel = reinterpret_cast<const int32_t *>(ds + o_sel);
+    const CovTile *dtiles = reinterpret_cast<const CovTile *>(ds + o_tiles);
+    const CovWin *dwins = reinterpret_cast<const CovWin *>(ds + o_wins);
+    double *dy = reinterpret_cast<double *>(ds + o_y), *dcov = reinterpret_cast<double *>(ds + o_cov), *dvar = reinterpret_cast<double *>(ds + o_var);
+    if (nsel_tot) HIPCHK(hipMemcpyAsync(ds + o_sel, sel, sizeof(int32_t) * nsel_tot, hipMemcpyHostToDevice, stream_));
+    if (!tiles.empty()) HIPCHK(hipMemcpyAsync(ds + o_tiles, tiles.data(), sizeof(CovTile) * tiles.size(), hipMemcpyHostToDevice, stream_));
+    if (!cwins.empty()) HIPCHK(hipMemcpyAsync(ds + o_wins, cwins.data(), sizeof(CovWin) * cwins.size(), hipMemcpyHostToDevice, stream_));
+    HIPCHK(poison(ds + o_y, total - o_y));
+    // ---- normal equations at the current state, then the factor of the undamped reduced system
+    set_params(1);
+    HIPCHK(hipEventRecord(ev_[8], stream_));
+    launch_initial(opt_.initial_radius, 0);
+    Dev c = dev_;
+    c.schur_plain_in_H = 0;
+    c.active = mask;
+    HIPCHK(hipEventRecord(ev_[12], stream_));
+    hipLaunchKernelGGL(k_cov_prepare, dim3(nw), dim3(256), 0, stream_, dev_, mask, excl);
+    HIPCHK(hipEventRecord(ev_[13], stream_));
+    launch_schur(c);
+    {
+      const BatchFacts &b = facts_;
+      const bool w8 = nw <= 192 || b.chol_lds > 80 * 1024;
+      if (b.chol_compact) {
+        if (w8) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(nw), dim3(512), b.chol_lds, stream_, c);
+        else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(nw), dim3(256), b.chol_lds, stream_, c);
+      } else {
+        if (w8) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(nw), dim3(512), b.chol_lds, stream_, c);
+        else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(nw), dim3(256), b.chol_lds, stream_, c);
+      }
+    }
+    HIPCHK(hipEventRecord(ev_[14], stream_));
+    if (!tiles.empty()) {
+      const size_t lds = ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double);
+      hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), lds, stream_, c, dtiles, dsel, dy, dvar);
+    }
+    HIPCHK(hipEventRecord(ev_[15], stream_));
+    if (!cwins.empty())
+      hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
+    HIPCHK(hipEventRecord(ev_[9], stream_));
+    // ---- results
+    std::vector<double> vh(nvar);
+    if (ncov) HIPCHK(hipMemcpyAsync(cov, dcov, sizeof(double) * ncov, hipMemcpyDeviceToHost, stream_));
+    if (nvar) HIPCHK(hipMemcpyAsync(vh.data(), dvar, sizeof(double) * nvar, hipMemcpyDeviceToHost, stream_));
+    Lm *lm = lm_host_;
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipStreamSynchronize(stream_));
+    HIPCHK(hipGetLastError());
+    if (const int rc = check_span_violation()) return rc;
+    {   // device times of this call, for ctvio_last_timing: the three covariance kernels and the whole call
+      const int pair[4][2] = {{12, 13}, {14, 15}, {15, 9}, {8, 9}};
+      float ms[4] = {0, 0, 0, 0};
+      for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(&ms[i], ev_[pair[i][0]], ev_[pair[i][1]]));
+      std::fill(timing_, timing_ + 8, 0.0); std::fill(ph_n_, ph_n_ + 8, 0);
+      timing_[0] = ms[0]; timing_[1] = ms[1]; timing_[2] = ms[2]; timing_[7] = ms[3];
+      ph_n_[0] = 1; ph_n_[1] = tiles.empty() ? 0 : 1; ph_n_[2] = cwins.empty() ? 0 : 1;
+      last_iters_ = 0;
+    }
+    // (a window whose factorisation met a non-positive or non-finite pivot: its outputs are NaN)
+    const double nan = std::nan("");
+    size_t oc = 0, ov = 0;
+    for (int w = wbeg; w < wend; ++w) {
+      const WinMeta &m = meta_[w];
+      const size_t ns = (size_t)n_sel[w - wbeg];
+      const bool bad = lm[w].chol_fail != 0;
+      if (singular) singular[w - wbeg] = bad ? 1 : 0;
+      if (bad) std::fill(cov + oc, cov + oc + ns * ns, nan);
+      if (var_rho) {
+        for (int l = 0; l < m.L; ++l) var_rho[ov + l] = bad ? nan : vh[(size_t)m.lm0 + l];
+        ov += (size_t)m.L;
+      }
+      oc += ns * ns;
+    }
+    return CTVIO_OK;
+  }
   int last_timing(double *ms8, int32_t *n8) {
     if (ms8) std::copy(timing_, timing_ + 8, ms8);
     if (n8) { std::copy(ph_n_, ph_n_ + 7, n8); n8[7] = last_iters_; }
@@ -1221,7 +1347,7 @@ class SolverImpl {
   const DebugSwitches dbg_;   // environment switches as they were when the handle was created
   int marg_ran_on_host_ = 0;  // the last ctvio_marginalize(_batch) call: 1 if the factorisation ran on the host
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool uploaded_ = false, profiling_ = false, profiling_requested_ = false;
   double timing_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_ms_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int32_t ph_n_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_iters_ = 0;
@@ -1260,6 +1386,7 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  DBuf<char> cov_dev_;       // ctvio_covariance(_batch): mask, selections, tiles, Y, outputs (grow-only)
   DBuf<MargMeta> mg_meta_;   // device marginalisation: descriptors, index lists, scratch, outputs
   DBuf<int32_t> mg_idx_;
   DBuf<double> mg_scr_, mg_out_;
@@ -1356,6 +1483,14 @@ int32_t ctvio_lm_step(ctvio_solver *s, int32_t id, double mu, double *delta, dou
 }
 int32_t ctvio_marginalize(ctvio_solver *s, int32_t id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
   CHK_S; return s->impl.marginalize(id, role, eps, n_keep, kept, J0, r0);
+}
+int32_t ctvio_covariance_batch(ctvio_solver *s, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
+  CHK_S; return s->impl.covariance(-1, n_sel, sel, cov, var_rho, singular);
+}
+int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.covariance(id, &n_sel, sel, cov, var_rho, singular);
 }
 int32_t ctvio_residual_summary(ctvio_solver *s, int32_t id, double *sums, int32_t *counts4) { CHK_S; return s->impl.residual_summary(id, sums, counts4); }
 int32_t ctvio_marginalize_batch(ctvio_solver *s, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {

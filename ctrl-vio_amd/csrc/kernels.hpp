@@ -19,6 +19,7 @@
 //                         its barrier-per-panel form, kept as the timing-independent twin the tests compare it with; k_cholesky_solve =
 //                         panel kernel for P > 223), k_step_finish (back-substitution, candidate x (+) alpha delta, its knot-pair table)
 //   kernels_query.hpp     k_gauge_restore (double2vector), k_residual_summary, k_spline_eval (trajectory queries)
+//   kernels_cov.hpp       k_cov_prepare, k_cov_solve, k_cov_gram (marginal covariances from the factor of the reduced system)
 #pragma once
 #include <utility>
 
@@ -146,3 +147,4 @@ struct LocalFrame {
 #include "kernels_assemble.hpp"
 #include "kernels_solve.hpp"
 #include "kernels_query.hpp"
+#include "kernels_cov.hpp"

@@ -1,0 +1,197 @@
+// kernels_cov.hpp -- marginal covariances from the reduced system (ctvio_covariance_batch): k_cov_prepare (per-call activity mask, zero damping),
+// k_cov_solve (block forward substitution against 16 right-hand sides per workgroup), k_cov_gram (selected block of the covariance).
+// Part of kernels.hpp (included from there, in order; not a stand-alone header).
+//
+// With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
+// touches (H_jj == 0) -- removed, the reduced system S = Hpp - W Hll^-1 W^T = L L^T is factored by the panel kernel (k_cholesky_solve: L21 in S,
+// the inverses of the 32 x 32 diagonal blocks in Dev::chol_inv).  Then
+//   Sigma[i][j]     = (L^-1 e_i)^T (L^-1 e_j)                    for trajectory unknowns i, j,
+//   Sigma[P+l][P+l] = 1 / Hll_l + | L^-1 (w_l / Hll_l) |^2        for the inverse depth of landmark l (w_l: its row of W),
+// so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
+#pragma once
+
+namespace ctv {
+
+// One right-hand-side tile: 16 columns of one window.
+struct CovTile {
+  int32_t win;
+  int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll
+  int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1: first row of W (window-local)
+  int32_t count;    // columns in use (<= 16)
+  long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
+};
+// One window with a selection (k_cov_gram).
+struct CovWin {
+  int32_t win, nsel, sel0, pad;   // sel0: offset of its selection in the concatenated list
+  long long y0, cov0;             // its first Y tile (tile t at y0 + 16 P t); its n_sel^2 block of the output
+};
+
+// Why a trajectory unknown is left out of the covariance's system (k_cov_prepare -> k_cov_gram).  Dev::active is 0 both for constant unknowns
+// and for those no factor touches (host_pack.hpp: active_mask), so the two are told apart here: constant by the window's flags (fixed_upto,
+// lock_bg / lock_ba, fix_ld), or inactive with H_jj != 0 (a per-knot constant that factors touch); untouched: H_jj == 0 exactly.
+enum { COV_IN = 0, COV_CONSTANT = 1, COV_UNTOUCHED = 2 };
+
+// Per call: the activity mask of the covariance (mask[j] = 1: unknown j is in the system) and the reason of every exclusion, zero damping,
+// 1 / Hll by row of W.
+__global__ __launch_bounds__(256) void k_cov_prepare(Dev d, uint8_t *mask, uint8_t *excl) {
+  const int w = blockIdx.x;
+  const WinMeta &m = d.wins[w];
+  const int cur = d.lm[w].cur, K6 = 6 * m.K;
+  const double *Hd = d.HppS[cur] + m.H0, *Hl = d.HllS[cur] + m.lm0;
+  for (int j = threadIdx.x; j < m.N; j += blockDim.x) {
+    const bool act = d.active[m.u0 + j] != 0;
+    const double h = (j < m.P) ? Hd[(long long)j * m.ldh + j] : Hl[j - m.P];
+    int why = COV_IN;
+    if (j < m.P) {
+      const bool flagged = j < K6 ? j / 6 <= m.fixed_upto : (j == m.P - 1 ? m.fix_ld != 0 : ((j - K6) % 6 < 3 ? m.lock_bg != 0 : m.lock_ba != 0));
+      why = flagged ? COV_CONSTANT : (h == 0.0 ? COV_UNTOUCHED : (act ? COV_IN : COV_CONSTANT));
+    }
+    mask[m.u0 + j] = why == COV_IN ? 1 : 0;
+    excl[m.u0 + j] = (uint8_t)why;
+    d.dd[m.u0 + j] = 0.0;
+    if (j >= m.P) {
+      const int row = m.lm0 + d.lm_pos[m.lm0 + j - m.P];
+      d.dinv[row] = h > 0.0 ? 1.0 / h : 0.0;   // (a landmark without observations: Hll = 0, its row of W is zero)
+      d.grs[row] = 0.0;   // (the reduced right-hand side rides through the factorisation; nothing here reads it)
+    }
+  }
+}
+
+// Y = L^-1 B for one tile of 16 right-hand sides.  d is the covariance's copy of Dev (d.active = the per-call mask).  Four waves: wave (h, kp)
+// owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of a half are added
+// in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row, as the back-substitution of the panel
+// kernel reads it); L_bb^-1 from Dev::chol_inv.  The substitution starts at the first block in which the tile is non-zero.
+constexpr int COV_NT = 256;
+__global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho) {
+  const CovTile t = tiles[blockIdx.x];
+  const int w = t.win;
+  const WinMeta &m = d.wins[w];
+  const int P = m.P, ldh = m.ldh, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int q4 = lane >> 4, l15 = lane & 15;
+  const int nblk = (P + 31) / 32, PP = 32 * nblk;
+  const int cur = d.lm[w].cur;
+  extern __shared__ __attribute__((aligned(16))) double smcov[];
+  double *Ys = smcov;              // [PP][16] the right-hand sides, block by block replaced by Y
+  double *part = Ys + 16 * PP;   // [512] partial sums handed between waves
+  __shared__ int s_first;
+  for (int e = tid; e < 16 * PP; e += COV_NT) Ys[e] = 0.0;
+  if (tid == 0) s_first = PP;
+  __syncthreads();
+  if (t.kind == 0) {
+    if (tid < t.count) {
+      const int j = sel[t.first + tid];
+      if (d.active[m.u0 + j]) { Ys[j * 16 + tid] = 1.0; atomicMin(&s_first, j); }   // (an excluded unknown: a zero column, finished by k_cov_gram)
+    }
+  } else {
+    const int col = tid >> 4, sub = tid & 15;
+    if (col < t.count) {
+      const int row = m.lm0 + t.first + col, klo = d.lm_klo[row], khi = d.lm_khi[row];
+      const double dv = d.dinv[row];
+      const double *Wr = d.WS[cur] + m.W0 + (long long)(t.first + col) * m.ldw;
+      if (khi >= klo && dv != 0.0) {   // the row's planned span, then the line-delay column
+        const int cend = min(6 * khi + 6, P);
+        for (int c = 6 * klo + sub; c < cend; c += 16)
+          if (d.active[m.u0 + c]) Ys[c * 16 + col] = Wr[c] * dv;
+        if (sub == 0) {
+          if (cend <= P - 1 && d.active[m.u0 + P - 1]) Ys[(P - 1) * 16 + col] = Wr[P - 1] * dv;
+          atomicMin(&s_first, 6 * klo);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int b0 = s_first / 32;   // (PP / 32 = nblk for a tile of zero columns: nothing to substitute)
+  const double *S = d.S + m.H0;
+  const int32_t *ef = d.env_first + m.tr0;
+  const int h = wave & 1, kp = wave >> 1;
+  for (int b = b0; b < nblk; ++b) {
+    double li[8];
+    if (kp == 0) {   // L_bb^-1, rows of this wave's half (row-major; rows beyond the last unknown are identity rows)
+      const double *gi = d.chol_inv + ((size_t)w * d.chol_nblk + b) * 1024 + (16 * h + l15) * 32;
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) li[kk] = (kk < 4 * (h + 1)) ? gi[4 * kk + q4] : 0.0;
+    }
+    // ---- products with the blocks left of the diagonal: rows 16 R .. 16 R + 15, columns [kbeg, 32 b)
+    const int R = 2 * b + h, rrow = 16 * R + l15;
+    const bool rlive = rrow < P;
+    const double *arow = S + (long long)min(rrow, P - 1) * ldh;
+    const int kbeg = max(16 * ef[min(R, P / 16)], 32 * b0);
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    if (16 * R < P) {
+      for (int kt = kbeg / 16 + kp; 16 * kt < 32 * b; kt += 2) {
+        double av[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) av[kk] = rlive ? arow[16 * kt + 4 * kk + q4] : 0.0;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], Ys[(16 * kt + 4 * kk + q4) * 16 + l15], acc, 0, 0, 0);
+      }
+    }
+    if (kp == 1) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) part[h * 256 + r * 64 + lane] = acc[r];
+    }
+    __syncthreads();
+    if (kp == 0) {   // T_b = B_b - (sum of the two partial products), in place
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double *y = Ys + (32 * b + 16 * h + q4 + 4 * r) * 16 + l15;
+        *y = *y - (acc[r] + part[h * 256 + r * 64 + lane]);
+      }
+    }
+    __syncthreads();
+    f64x4 yv = {0.0, 0.0, 0.0, 0.0};
+    if (kp == 0) {   // Y_b = L_bb^-1 T_b (lower triangular: the upper half needs k < 16 only)
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk)
+        if (kk < 4 * (h + 1)) yv = __builtin_amdgcn_mfma_f64_16x16x4f64(li[kk], Ys[(32 * b + 4 * kk + q4) * 16 + l15], yv, 0, 0, 0);
+    }
+    __syncthreads();
+    if (kp == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Ys[(32 * b + 16 * h + q4 + 4 * r) * 16 + l15] = yv[r];
+    }
+    __syncthreads();
+  }
+  if (t.kind == 0) {   // a selection tile: Y to the scratch, for k_cov_gram
+    double *yo = yscr + t.yoff;
+    for (int e = tid; e < 16 * P; e += COV_NT) yo[e] = Ys[e];
+    return;
+  }
+  // ---- a landmark tile: column sums of squares in a fixed order (16 strided partial sums per column, then added in sequence)
+  {
+    const int col = tid & 15, p = tid >> 4;
+    double s = 0.0;
+    for (int k = min(32 * b0, P) + p; k < P; k += 16) { const double v = Ys[k * 16 + col]; s += v * v; }
+    part[p * 16 + col] = s;
+  }
+  __syncthreads();
+  if (tid < t.count) {
+    double tot = 0.0;
+    for (int p = 0; p < 16; ++p) tot += part[p * 16 + tid];
+    const int row = m.lm0 + t.first + tid, l = d.lm_at[row];
+    const double dv = d.dinv[row];
+    var_rho[m.lm0 + l] = dv == 0.0 ? __builtin_inf() : dv + tot;   // (Hll = 0: no information)
+  }
+}
+
+// cov[i][j] = Y_i^T Y_j over the pairs of selection tiles of a window (grid: pair, window with a selection); one entry per thread, summed over
+// the rows in sequence.  A constant selected unknown gives a zero row and column, an untouched one +inf on its diagonal and 0 elsewhere.
+__global__ __launch_bounds__(256) void k_cov_gram(Dev d, const CovWin *wins, const int32_t *sel, const uint8_t *excl, const double *yscr, double *cov) {
+  const CovWin cw = wins[blockIdx.y];
+  int ti, tj;
+  tile_decode(blockIdx.x, ti, tj);
+  if (16 * ti >= cw.nsel) return;
+  const WinMeta &m = d.wins[cw.win];
+  const int P = m.P, i = threadIdx.x >> 4, j = threadIdx.x & 15, si = 16 * ti + i, sj = 16 * tj + j;
+  if (si >= cw.nsel || sj >= cw.nsel) return;
+  const int ui = sel[cw.sel0 + si], uj = sel[cw.sel0 + sj];
+  const double *yi = yscr + cw.y0 + (long long)16 * P * ti + i, *yj = yscr + cw.y0 + (long long)16 * P * tj + j;
+  double s = 0.0;
+  for (int k = 0; k < P; ++k) s += yi[16 * k] * yj[16 * k];
+  if (excl[m.u0 + ui] != COV_IN || excl[m.u0 + uj] != COV_IN) s = (si == sj && excl[m.u0 + ui] == COV_UNTOUCHED) ? __builtin_inf() : 0.0;
+  double *c = cov + cw.cov0;
+  c[(long long)si * cw.nsel + sj] = s;
+  if (ti != tj) c[(long long)sj * cw.nsel + si] = s;
+}
+
+}  // namespace ctv

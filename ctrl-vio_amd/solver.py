@@ -237,6 +237,36 @@ class Solver:
             u += N; oj += n * n; orr += n
         return out
 
+    def covariance_batch(self, sels, rho: bool = False):
+        """ctvio_covariance_batch: marginal covariances of every window at its current state.  sels = one index list per window
+        (trajectory unknowns in [0, P), at most 64, may be empty).  Returns (list of n x n arrays in the order of each selection,
+        list of per-landmark inverse-depth variances or None, singular flags (n windows))."""
+        assert len(sels) == len(self.windows)
+        sels = [np.ascontiguousarray(s, np.int32).reshape(-1) for s in sels]
+        ns = np.array([s.shape[0] for s in sels], np.int32)
+        sel = np.ascontiguousarray(np.concatenate(sels) if len(sels) else np.zeros(0, np.int32), np.int32)
+        cov = np.zeros(max(int((ns.astype(np.int64) ** 2).sum()), 1))
+        Ls = [w.L for w in self.windows]
+        var = np.zeros(max(sum(Ls), 1)) if rho else None
+        sing = np.zeros(len(sels), np.int32)
+        capi.check(self._lib.ctvio_covariance_batch(self._h, capi._p(ns), capi._p(sel), capi._p(cov), capi._p(var) if rho else None, capi._p(sing)))
+        covs, vars_, oc, ov = [], [], 0, 0
+        for n, L in zip(ns, Ls):
+            n = int(n)
+            covs.append(cov[oc:oc + n * n].reshape(n, n).copy()); oc += n * n
+            if rho:
+                vars_.append(var[ov:ov + L].copy()); ov += L
+        return covs, (vars_ if rho else None), sing
+
+    def covariance(self, wid: int, sel, rho: bool = False):
+        """ctvio_covariance: the same for window wid alone (same bits as the batch entry).  Returns (n x n array, inverse-depth
+        variances (L,) or None, singular flag)."""
+        sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+        n, L = int(sel.shape[0]), self.windows[wid].L
+        cov = np.zeros(max(n * n, 1)); var = np.zeros(max(L, 1)) if rho else None; sing = np.zeros(1, np.int32)
+        capi.check(self._lib.ctvio_covariance(self._h, int(wid), n, capi._p(sel), capi._p(cov), capi._p(var) if rho else None, capi._p(sing)))
+        return cov[:n * n].reshape(n, n).copy(), (var[:L].copy() if rho else None), int(sing[0])
+
     def gauge_restore(self, wids, knots, q0, t0):
         """4-DoF gauge restore (reference double2vector): windows `wids`, reference knot index per window, its pre-solve
         quaternion (n,4) (x,y,z,w) and position (n,3).  Acts on the device state; read it back with get_state."""

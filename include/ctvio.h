@@ -195,6 +195,25 @@ int32_t ctvio_residual_summary(ctvio_solver *s, int32_t id, double *sums, int32_
  * model cost change; the state is not modified. */
 int32_t ctvio_lm_step(ctvio_solver *s, int32_t id, double mu, double *delta, double *model_cost_change);
 
+/* Marginal covariances of window estimates, from the reduced system of the CURRENT state (the reference includes ceres/covariance.h at its
+ * estimator boundary, src/estimator/trajectory_estimator.h:23; Ceres' Covariance::Compute + GetCovarianceBlockInTangentSpace are the
+ * counterpart).  H = the normal matrix sum J~^T J~ that the linearise entry returns (prior, bias chain and robust corrector included, NO LM
+ * damping).  An unknown is EXCLUDED if it is constant or if no factor touches it (H_jj == 0 exactly, e.g. the spline's last padding knot);
+ * Sigma = (H restricted to the other unknowns)^-1; rotations in the tangent space of the Jacobians (q <- q exp(delta)).
+ *   n_sel[w] (0 .. 64): trajectory unknowns selected in window w; sel: the selections concatenated, each an index in [0, P_w) in the unknown
+ *   order above (any order inside a window, no duplicates); cov: window w owns n_sel[w]^2 doubles, row-major in the order of sel, packed in
+ *   window order (may be NULL if every n_sel is 0): cov[i][j] = Sigma[sel_i][sel_j]; a constant selected unknown gives a zero row and
+ *   column, an untouched one +inf on its diagonal and 0 elsewhere.  var_rho (sum L doubles, window order, the caller's landmark order; or
+ *   NULL): the marginal variance of every inverse depth, +inf for a landmark without information (Hll == 0).  singular (n windows, or NULL):
+ *   1 if the window's factorisation met a non-positive or non-finite pivot -- its outputs are NaN then; the call still returns CTVIO_OK.
+ * CTVIO_ERR_INVALID: an entry outside [0, P), a duplicate, n_sel > 64; CTVIO_ERR_STATE before the upload; the handle stays usable.  The state,
+ * the launch plan and the captured graph of the solve are left as they were; the kernels of the covariance use no atomics: where the linearisation
+ * is order-fixed (opt.deterministic) two calls give the same bits, and the single-window entry
+ * (n_sel, sel, cov, var_rho (L doubles), singular (1) of window id alone) gives the bits of the batch entry.  Pose-landmark cross terms are
+ * not computed. */
+int32_t ctvio_covariance_batch(ctvio_solver *s, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
+int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
+
 /* Batched trajectory query on the device: Se3Spline::poseNs / transVelWorld / rotVelBody / transAccelWorld
  * (se3_spline.h:361-399).  pose7 = (px,py,pz,qx,qy,qz,qw).  Any output may be NULL. */
 int32_t ctvio_spline_eval(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, double *pose7, double *vel3,
@@ -275,7 +294,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  *   0 k_imu_linearize  1 k_vis_eval (linearise)  2 k_assemble_vis  3 zero + k_assemble_imu + k_misc + k_post_linearize
  *   4 Schur SYRK (k_schur_window / k_schur_mfma)  5 k_cholesky_solve  6 everything else (damping, rhs, backsub, update, cost, control)
  *   7 whole solve (always measured).  launches8: number of launches of each group, [7] = LM passes launched.
- * Groups 0..6 are zero unless profiling was on. */
+ * Groups 0..6 are zero unless profiling was on.
+ * After a covariance call instead: ms8[0..2] = device time of k_cov_prepare, k_cov_solve, k_cov_gram, ms8[7] = the whole call on the device
+ * (linearisation, Schur complement and Cholesky included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);
 /* The HIP stream every kernel of this solver is launched on (hipStream_t), for external event timing. */
 void *ctvio_stream(ctvio_solver *s);

@@ -455,6 +455,60 @@ class TrajectoryEstimator {
     return r;
   }
 
+  // ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for the given parameter blocks (the reference includes ceres/covariance.h at
+  // this boundary, trajectory_estimator.h:23), at the CURRENT parameter values, from the factors of Solve (ctvio_covariance).  blocks: parameter
+  // pointers as the Add* calls took them -- a knot's quaternion gives 3 tangent columns (q <- q exp(delta)), a knot's position 3, a gyro / accel
+  // bias 3 each, the line delay 1 -- at most 64 columns, no block twice; cov: row-major over the concatenated tangent.  A constant block gives
+  // zero rows and columns, one no factor touches +inf on its diagonal.  Inverse-depth pointers are accepted in a list of their own: their
+  // variances on the diagonal, the entries between two depths NaN (not computed); mixing them with trajectory blocks throws, the cross terms
+  // between a depth and anything else are not computed.  Returns false if the window's reduced system is singular (cov is NaN then).
+  bool GetCovarianceInTangentSpace(const std::vector<const double *> &blocks, std::vector<double> &cov) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const int K = pk.w.K, F = pk.w.F, L = pk.w.L;
+    std::vector<int32_t> sel;
+    std::vector<int> lms;
+    for (const double *p : blocks) {
+      auto kt = knot_of_.find(p);
+      auto bt = bias_of_.find(p);
+      auto lt = lm_of_.find(p);
+      if (p == &traj_->line_delay) sel.push_back(6 * K + 6 * F);
+      else if (kt != knot_of_.end()) {
+        const int k = kt->second - pk.kmin;
+        if (k < 0 || k >= K) throw std::invalid_argument("covariance block: a knot no factor of this estimator touches");
+        const int u = 6 * k + (p == traj_->so3_[kt->second].data() ? 0 : 3);
+        for (int c = 0; c < 3; ++c) sel.push_back(u + c);
+      } else if (bt != bias_of_.end()) {
+        const int f = pk.bias_map[bt->second];
+        if (f < 0) throw std::invalid_argument("covariance block: a bias state that is not part of the solve");
+        const int u = 6 * K + 6 * f + (bias_ptr_[bt->second].first == p ? 0 : 3);
+        for (int c = 0; c < 3; ++c) sel.push_back(u + c);
+      } else if (lt != lm_of_.end()) {
+        if (pk.lm_map[lt->second] < 0) throw std::invalid_argument("covariance block: a landmark that is not part of the solve");
+        lms.push_back(pk.lm_map[lt->second]);
+      } else {
+        throw std::invalid_argument("covariance block is not a knot / bias / line delay / inverse depth of this estimator");
+      }
+    }
+    if (!lms.empty() && !sel.empty())
+      throw std::invalid_argument("covariance between an inverse depth and a trajectory block is not computed: ask for the depths in a list of their own");
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    int32_t singular = 0;
+    if (!lms.empty()) {
+      std::vector<double> var((size_t)L);
+      check(ctvio_covariance(s, 0, 0, nullptr, nullptr, var.data(), &singular));
+      const size_t n = lms.size();
+      cov.assign(n * n, std::nan(""));
+      for (size_t i = 0; i < n; ++i) cov[i * n + i] = var[(size_t)lms[i]];
+    } else {
+      const size_t n = sel.size();
+      cov.assign(n * n, 0.0);
+      check(ctvio_covariance(s, 0, (int32_t)n, sel.data(), cov.data(), nullptr, &singular));
+    }
+    return singular == 0;
+  }
+
  private:
   // One packed window: only the knots the factors touch (the reference registers exactly those with Ceres,
   // trajectory_estimator.cpp:114-141; the trajectory itself keeps growing), biases / landmarks that are referenced.
