@@ -73,24 +73,6 @@ static DebugSwitches read_debug_switches() {
   return g;
 }
 
-template <class U> struct DBuf {
-  U *p = nullptr;
-  size_t n = 0;
-  ~DBuf() { release(); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-  hipError_t alloc(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    release();
-    n = std::max<size_t>(count, 1);
-    return hipMalloc((void **)&p, n * sizeof(U));
-  }
-  hipError_t upload(const std::vector<U> &h, hipStream_t st) {
-    hipError_t e = alloc(h.size());
-    if (e != hipSuccess || h.empty()) return e;
-    return hipMemcpyAsync(p, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice, st);
-  }
-};
-
 // Owning host copy of one window (ctvio_add_window: the caller's buffers are only read inside that call).
 struct HostWindow {
   ctvio_window w;  // scalars + pointers into the vectors below
@@ -132,10 +114,7 @@ class SolverImpl {
     if (stream_) (void)hipStreamDestroy(stream_);
     for (auto &e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto &e : pev_) (void)hipEventDestroy(e);
-    if (lm_host_) (void)hipHostFree(lm_host_);
-    if (state_host_) (void)hipHostFree(state_host_);
     if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
-    if (call_host_) (void)hipHostFree(call_host_);
   }
   int init() {
     HIPCHK(hipSetDevice(opt_.device));
@@ -279,12 +258,9 @@ class SolverImpl {
     d.line_search = opt_.line_search ? 1 : 0;
     // ---- work arena (device only)
     if (const int rc = layout_work()) return rc;
-    // pinned landing areas of the results
-    if ((size_t)nw > lm_host_cap_) {   // (lm_host_cap_ records for the windows, one more as scratch: lm_scratch)
-      if (lm_host_) (void)hipHostFree(lm_host_);
-      lm_host_cap_ = (size_t)nw + nw / 8 + 16;
-      HIPCHK(hipHostMalloc((void **)&lm_host_, sizeof(Lm) * (lm_host_cap_ + 1), hipHostMallocDefault));
-    }
+    // ---- the fixed head of call_io_ (HEAD_*): the pinned landing areas of the results; every call reserves head + its own tail (reserve_call)
+    head_ = CallLayout();
+    head_.add("lm", sizeof(Lm), (size_t)nw, false); head_.add("poll", sizeof(int32_t), 4, false); head_.add("state", sizeof(double), state_doubles_, false);
     snap_valid_ = false;
     uploaded_ = true;
     return CTVIO_OK;
@@ -365,7 +341,7 @@ class SolverImpl {
   // kernel choice; the launch_* functions read dev_ and this.  Built zero-filled, like Dev: the captured graph is valid while both compare equal.
   enum { TAIL_ACCUMULATE = 0, TAIL_STORE, TAIL_STORE_WIDE };                                        // LaunchPlan::tail
   enum { SCHUR_WINDOW_5_7 = 0, SCHUR_WINDOW_5_14, SCHUR_WINDOW_7_14, SCHUR_TILE, SCHUR_TILE2 };     // LaunchPlan::schur
-  enum { CHOL_FLOW = 0, CHOL_TILES, CHOL_PANEL, CHOL_PANEL_SLOTS };                                 // LaunchPlan::chol
+  enum { CHOL_FLOW = 0, CHOL_TILES, CHOL_PANEL };                                                   // LaunchPlan::chol
   struct LaunchPlan {
     int32_t tail;                    // assembly tail: atomics into zeroed Hpp / g; every entry stored once; stored once + k_assemble_wide for the wide windows
     int32_t parts;                   // workgroups per window of the visual assembly
@@ -375,10 +351,11 @@ class SolverImpl {
     int32_t misc_imu;                // k_misc's IMU share on the accumulate path: 0 none, 1 straight to Hpp, 2 through the LDS band
     int32_t schur, schur_tiles;      // the Schur kernel; tile kernels: 16 x 16 tiles (or 32 x 32 blocks) per window
     int32_t schur_plain_in_H;        // Dev::schur_plain_in_H
-    int32_t chol, chol_waves;        // the Cholesky kernel; the panel kernels' waves
+    int32_t chol;                    // the solve's Cholesky kernel
+    int32_t panel_slots, panel_waves;   // the panel kernel (launch_chol_panel: the solve's CHOL_PANEL, the covariance's for every batch): slot-indexed variant; waves
     int32_t finish_waves;            // k_step_finish
     int32_t wide_tiles;              // k_assemble_wide: tile rows of the augmented knot block
-    size_t vis_lds, vis_glb, misc_lds, schur_lds, chol_lds;   // dynamic LDS bytes
+    size_t vis_lds, vis_glb, misc_lds, schur_lds, chol_lds, panel_lds;   // dynamic LDS bytes (chol_lds: the tile kernels')
   };
   // Runs once per upload, and again around a profiled solve (which keeps every kernel apart); never per pass.
   LaunchPlan make_plan(bool profiling) const {
@@ -447,13 +424,15 @@ class SolverImpl {
       p.chol_lds = b.chol_tiles == 1 ? (size_t)(272 + 2 * ntr * 272 + 32 * ntr + 4 + 768) * sizeof(double)   // identity + panel + inverses + vectors + parked tiles
                                      : (size_t)(272 + 5 * ntr * 272 + 32 * ntr + 48) * sizeof(double);      // identity + inverses + sub-diagonal tiles + three panels + vectors + flags
     } else {
-      // (8 waves also when the panel's LDS footprint allows one workgroup per CU anyway -- P = 571: 157 KB -- where 4 waves left three quarters
-      //  of the CU's wave slots empty)
-      // (windows beyond 591 unknowns: the slot-indexed variant, same wave-count rule)
-      p.chol = b.chol_compact ? CHOL_PANEL_SLOTS : CHOL_PANEL;
-      p.chol_lds = b.chol_lds;
-      p.chol_waves = (nw <= 192 || b.chol_lds > 80 * 1024) ? 8 : 4;
+      p.chol = CHOL_PANEL;
     }
+    // The panel kernel of the batch, whichever kernel the solve takes (a pure function of the sizes that also key the graph):
+    // (8 waves also when the panel's LDS footprint allows one workgroup per CU anyway -- P = 571: 157 KB -- where 4 waves left three quarters
+    //  of the CU's wave slots empty)
+    // (windows beyond 591 unknowns: the slot-indexed variant, same wave-count rule)
+    p.panel_slots = b.chol_compact ? 1 : 0;
+    p.panel_lds = b.chol_lds;
+    p.panel_waves = (nw <= 192 || b.chol_lds > 80 * 1024) ? 8 : 4;
     // Dev::schur_plain_in_H is part of the Dev struct the captured graph is keyed on: decided once per upload, never inside a launch
     // (launch_schur used to set it, so every upload -- which clears Dev -- invalidated the cached hipGraph of the headline configuration).
     p.schur_plain_in_H = (p.schur <= SCHUR_WINDOW_7_14 && b.chol_tiles != 0 && !dbg_.schur_copy_plain) ? 1 : 0;
@@ -473,6 +452,14 @@ class SolverImpl {
     p.min_diag = opt_.min_lm_diagonal; p.max_diag = opt_.max_lm_diagonal; p.max_invalid = opt_.max_consecutive_invalid_steps;
     p.max_iters = max_iters;
   }
+  // ctvio_last_timing's record: ms[0..6] per phase of a profiled solve (or the covariance's three kernels), ms[7] the whole call on the
+  // device; n[0..6] the launches behind each figure, n[7] the passes of the solve.  A call clears its own copy, fills it and publishes it.
+  struct Timing {
+    double ms[8];
+    int32_t n[8];
+    void clear() { *this = Timing{}; }
+  };
+  enum Ev { EV_CALL_BEGIN = 0, EV_CALL_END, EV_QUERY_BEGIN, EV_QUERY_END, EV_COV_PREPARE, EV_COV_FACTOR, EV_COV_SOLVE, EV_COV_GRAM, EV_COUNT };
   // Per-phase timing with HIP events on the solver's stream (only when profiling is switched on).
   enum { PH_IMU_LIN = 0, PH_VIS_LIN, PH_ASM_VIS, PH_ASM_REST, PH_SCHUR, PH_CHOL, PH_REST, PH_COUNT };
   void ph_begin(int ph) {
@@ -488,12 +475,10 @@ class SolverImpl {
     if (!profiling_) return;
     (void)hipEventRecord(pev_[pev_used_ - 1], stream_);
   }
-  void ph_collect() {
-    std::fill(ph_ms_, ph_ms_ + 8, 0.0);
-    std::fill(ph_n_, ph_n_ + 8, 0);
+  void ph_collect(Timing &t) {
     for (size_t i = 0; i < pev_phase_.size(); ++i) {
       float ms = 0;
-      if (hipEventElapsedTime(&ms, pev_[2 * i], pev_[2 * i + 1]) == hipSuccess) { ph_ms_[pev_phase_[i]] += ms; ph_n_[pev_phase_[i]] += 1; }
+      if (hipEventElapsedTime(&ms, pev_[2 * i], pev_[2 * i + 1]) == hipSuccess) { t.ms[pev_phase_[i]] += ms; t.n[pev_phase_[i]] += 1; }
     }
     pev_phase_.clear();
     pev_used_ = 0;
@@ -582,19 +567,23 @@ class SolverImpl {
     switch (p.chol) {
       case CHOL_TILES: hipLaunchKernelGGL((k_cholesky_tiles<16, 7>), dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
       case CHOL_FLOW: hipLaunchKernelGGL(k_cholesky_flow, dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
-      case CHOL_PANEL_SLOTS:
-        if (p.chol_waves == 8) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(nw), dim3(512), p.chol_lds, stream_, d);
-        else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(nw), dim3(256), p.chol_lds, stream_, d);
-        break;
-      default:
-        if (p.chol_waves == 8) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(nw), dim3(512), p.chol_lds, stream_, d);
-        else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(nw), dim3(256), p.chol_lds, stream_, d);
+      default: launch_chol_panel(d);
     }
     ph_end();
     ph_begin(PH_REST);
     if (p.finish_waves == 8) hipLaunchKernelGGL((k_step_finish<8>), dim3(nw), dim3(512), (size_t)d.maxP * sizeof(double), stream_, d);
     else hipLaunchKernelGGL((k_step_finish<4>), dim3(nw), dim3(256), (size_t)d.maxP * sizeof(double), stream_, d);
     ph_end();
+  }
+  void launch_chol_panel(const Dev &d) {   // (d: dev_, or the covariance's copy of it)
+    const LaunchPlan &p = plan_;
+    if (p.panel_slots) {
+      if (p.panel_waves == 8) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(d.nwin), dim3(512), p.panel_lds, stream_, d);
+      else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(d.nwin), dim3(256), p.panel_lds, stream_, d);
+    } else {
+      if (p.panel_waves == 8) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(d.nwin), dim3(512), p.panel_lds, stream_, d);
+      else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(d.nwin), dim3(256), p.panel_lds, stream_, d);
+    }
   }
   void launch_schur(const Dev &d) {   // (d: dev_, or the covariance's copy of it)
     const LaunchPlan &p = plan_;
@@ -647,14 +636,17 @@ class SolverImpl {
   }
   // The first linearisation of a solve (and of the diagnostic entries): knot-pair constants, normal equations and cost of the
   // current state in set 0, Jacobi scaling.
-  void launch_initial(double mu, int keep_scale) {
-    Dev &d = dev_;
-    const int nw = d.nwin, wb = nblk(nw, 64);
-    hipLaunchKernelGGL(k_lm_init, dim3(wb), dim3(64), 0, stream_, d, mu, keep_scale);
-    hipLaunchKernelGGL(k_knot_prep, dim3(nblk(d.Ktot, 256)), dim3(256), 0, stream_, d);
+  void launch_initial(double mu) {
+    launch_prepare(mu, 0);
     launch_linearize(LIN_AT_X);
     launch_assemble(LIN_AT_X);
-    hipLaunchKernelGGL(k_initial_cost, dim3(nw), dim3(64), 0, stream_, d, 0);
+    hipLaunchKernelGGL(k_initial_cost, dim3(dev_.nwin), dim3(64), 0, stream_, dev_, 0);
+  }
+  // what every evaluation of the current state starts with (launch_initial, ctvio_cost): the LM records, the knot-pair constants
+  void launch_prepare(double mu, int keep_scale) {
+    const Dev &d = dev_;
+    hipLaunchKernelGGL(k_lm_init, dim3(nblk(d.nwin, 64)), dim3(64), 0, stream_, d, mu, keep_scale);
+    hipLaunchKernelGGL(k_knot_prep, dim3(nblk(d.Ktot, 256)), dim3(256), 0, stream_, d);
   }
   // The pass as a hipGraph (captured once per batch shape: the kernel arguments are the Dev struct, so equal shapes in the
   // grow-only arenas give identical graphs), replayed instead of ~25 launches.  Everything else the launch list depends on -- dynamic
@@ -676,13 +668,45 @@ class SolverImpl {
     return CTVIO_OK;
   }
 
-  // k_vis_eval counts evaluations that fall outside the knot span the packer planned for their landmark (host_pack.hpp: plan_sparsity): such a
-  // row of W was written into a neighbour's columns.  Every entry point that launches the kernel ends with this check; the counter is cleared
-  // again so that a later call on the same batch (after ctvio_set_state / ctvio_restore_state) starts clean.  The stream must be idle.
-  int check_span_violation() {
-    int32_t *viol = lm_scratch() + 2;   // (beside the "still running" word)
-    HIPCHK(hipMemcpyAsync(viol, dev_.span_viol, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  // ---------------------------------------------------------------------------------------- per-call entries
+  // Every entry below starts with guard() and lays its scratch out ONCE (host_pack.hpp: CallLayout) in two arenas: call_io_, mirrored by
+  // pinned host memory, holds what is copied in or out -- every asynchronous copy to the host lands in its mirror and reaches the caller's
+  // buffer after the synchronise --, call_scr_ (device only) everything else.  io starts as a copy of head_, the result areas
+  // pack_and_upload laid out (HEAD_*: the LM records, the poll words -- a segment of their own, so they alias no record at any nwin --, the
+  // batch state); segments after io.landing() have no device twin (their sources lie in the input / work arena).  Irregular: the head is
+  // such a landing area too, but stays in front, so its device twin is unused.  reserve_call comes before the first launch or copy that
+  // takes a pointer into either arena.  CTVIO_POISON: every segment declared dbl -- doubles the call reads after a kernel wrote them --
+  // starts as the pattern at every call; integer segments and staged inputs never do.
+  enum { HEAD_LM = 0, HEAD_POLL, HEAD_STATE };
+  int guard() const { return uploaded_ ? CTVIO_OK : fail(CTVIO_ERR_STATE, "ctvio_upload not called"); }
+  int guard(int id, const char *msg = "window id out of range") const {
+    if (const int rc = guard()) return rc;
+    return id >= 0 && id < dev_.nwin ? CTVIO_OK : fail(CTVIO_ERR_INVALID, msg);
+  }
+  int reserve_call(CallLayout &io, CallLayout *scr = nullptr) {
+    HIPCHK(call_io_.reserve(io.dev_bytes(), true, nullptr, io.bytes() - io.dev_bytes()));
+    io.reserved();
+    if (scr) { HIPCHK(call_scr_.reserve(scr->bytes(), false, nullptr, 0, false)); scr->reserved(); }
+    if (!dbg_.poison) return CTVIO_OK;
+    for (const ArenaSeg &sg : io.segs()) if (sg.dbl) HIPCHK(poison(call_io_.dev + sg.off, sg.bytes));
+    if (scr) for (const ArenaSeg &sg : scr->segs()) if (sg.dbl) HIPCHK(poison(call_scr_.dev + sg.off, sg.bytes));
+    return CTVIO_OK;
+  }
+  template <class U> U *io_host(const CallLayout &io, int seg) { return io.at<U>(call_io_.host, seg); }
+  template <class U> U *io_dev(const CallLayout &io, int seg) { return io.at<U>(call_io_.dev, seg); }
+  int sync_call() {
     HIPCHK(hipStreamSynchronize(stream_));
+    HIPCHK(hipGetLastError());
+    return CTVIO_OK;
+  }
+  // The end of every entry that launches k_vis_eval, in ONE blocking round trip with the entry's own copies.  The kernel counts evaluations
+  // that fall outside the knot span the packer planned for their landmark (host_pack.hpp: plan_sparsity): such a row of W was written into
+  // a neighbour's columns.  The counter is cleared again so that a later call on the same batch (after ctvio_set_state /
+  // ctvio_restore_state) starts clean.
+  int finish_call(const CallLayout &io) {
+    int32_t *viol = io_host<int32_t>(io, HEAD_POLL) + 1;   // (beside the "still running" word)
+    HIPCHK(hipMemcpyAsync(viol, dev_.span_viol, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    if (const int rc = sync_call()) return rc;
     if (*viol == 0) return CTVIO_OK;
     const int n = *viol;
     HIPCHK(hipMemsetAsync(dev_.span_viol, 0, sizeof(int32_t), stream_));
@@ -690,20 +714,31 @@ class SolverImpl {
     return fail(CTVIO_ERR_INTERNAL, std::to_string(n) + " evaluation(s) fell outside the planned knot span of their landmark (host_pack.hpp: plan_sparsity): "
                                     "the normal equations of this call are not to be trusted");
   }
+  int publish_timing(Timing &t, int passes) {   // (the stream is idle)
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev_[EV_CALL_BEGIN], ev_[EV_CALL_END]));
+    t.ms[7] = ms; t.n[7] = passes;
+    timing_ = t;
+    return CTVIO_OK;
+  }
 
   int solve(int max_iters, ctvio_summary *out) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     if (max_iters < 0) return fail(CTVIO_ERR_INVALID, "max_iterations < 0");
     Dev &d = dev_;
     const int nw = d.nwin;
+    CallLayout io = head_;
+    if (const int rc = reserve_call(io)) return rc;
+    Lm *lm = io_host<Lm>(io, HEAD_LM);   // pinned: the copy does not stage through a runtime bounce buffer
+    int32_t *na = io_host<int32_t>(io, HEAD_POLL);
     set_params(max_iters);
     profiling_ = profiling_requested_;
     if (profiling_) plan_ = make_plan(true);   // (every kernel apart; the upload's plan comes back below)
     pev_phase_.clear(); pev_used_ = 0;
     const bool graph = opt_.use_graph && !profiling_ && !d.dbg;
     if (graph) { const int rc = ensure_graph(); if (rc != CTVIO_OK) return rc; }
-    HIPCHK(hipEventRecord(ev_[8], stream_));
-    launch_initial(opt_.initial_radius, 0);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+    launch_initial(opt_.initial_radius);
     HIPCHK(hipMemsetAsync(d.n_active, 0, sizeof(int32_t), stream_));
     hipLaunchKernelGGL(k_begin_iter, dim3(nw), dim3(256), 0, stream_, d);   // the first iteration; later ones start in k_pass_end
     // max_iters passes finish every window that never enters the line search; the host looks at the "windows that start another
@@ -716,26 +751,19 @@ class SolverImpl {
       ++it;
       if (it >= pass_cap) break;
       if (it >= max_iters || it % check == 0) {
-        int32_t *na = lm_scratch();
         HIPCHK(hipMemcpyAsync(na, d.n_active, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
         HIPCHK(hipStreamSynchronize(stream_));
         if (*na == 0) break;
       }
     }
-    HIPCHK(hipEventRecord(ev_[9], stream_));
-    Lm *lm = lm_host_;   // pinned: the copy does not stage through a runtime bounce buffer
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
     HIPCHK(hipMemcpyAsync(lm, d.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    if (const int rc = check_span_violation()) return rc;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev_[8], ev_[9]));
-    if (profiling_) ph_collect(); else { std::fill(ph_ms_, ph_ms_ + 8, 0.0); std::fill(ph_n_, ph_n_ + 8, 0); }
-    if (profiling_) plan_ = make_plan(false);
+    if (const int rc = finish_call(io)) return rc;
+    Timing t;
+    t.clear();
+    if (profiling_) { ph_collect(t); plan_ = make_plan(false); }
     profiling_ = false;
-    std::copy(ph_ms_, ph_ms_ + 7, timing_);
-    timing_[7] = ms;
-    last_iters_ = it;
+    if (const int rc = publish_timing(t, it)) return rc;
     if (d.dbg) {
       long long st[128];
       HIPCHK(hipMemcpy(st, d.dbg, sizeof st, hipMemcpyDeviceToHost));
@@ -764,8 +792,7 @@ class SolverImpl {
   }
 
   int get_state(int id, double *quat, double *pos, double *bias, double *rho, double *ld) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (const int rc = guard(id)) return rc;
     const WinMeta &m = meta_[id];
     if (quat) HIPCHK(hipMemcpyAsync(quat, dev_.quat + 4 * (size_t)m.knot0, sizeof(double) * 4 * m.K, hipMemcpyDeviceToHost, stream_));
     if (pos) HIPCHK(hipMemcpyAsync(pos, dev_.pos + 3 * (size_t)m.knot0, sizeof(double) * 3 * m.K, hipMemcpyDeviceToHost, stream_));
@@ -776,8 +803,7 @@ class SolverImpl {
     return CTVIO_OK;
   }
   int set_state(int id, const double *quat, const double *pos, const double *bias, const double *rho, double ld) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (const int rc = guard(id)) return rc;
     const WinMeta &m = meta_[id];
     if (!m.fix_ld) ld = std::min(std::max(ld, m.ld_lo), m.ld_hi);
     else if (ld != h_ld_[id]) return fail(CTVIO_ERR_INVALID, "the line delay of a fix_ld window cannot change after the upload: the knot spans of its landmarks were planned for it");
@@ -792,7 +818,7 @@ class SolverImpl {
 
   // device-side copy of the whole batch state (restore != 0: copy back); the state is one contiguous block
   int snapshot(int restore) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     if (restore && !snap_valid_) return fail(CTVIO_ERR_STATE, "no snapshot taken");
     HIPCHK(hipMemcpyAsync(restore ? dev_.quat : snap_, restore ? snap_ : dev_.quat, state_doubles_ * sizeof(double), hipMemcpyDeviceToDevice, stream_));
     if (!restore) { HIPCHK(hipStreamSynchronize(stream_)); snap_valid_ = true; }
@@ -800,97 +826,86 @@ class SolverImpl {
   }
   // every window's state in one device-to-host copy (concatenated in window order, like the device arrays)
   int get_batch_state(double *quat, double *pos, double *bias, double *rho, double *ld) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     const Dev &d = dev_;
-    if (state_doubles_ > state_host_cap_) {
-      if (state_host_) (void)hipHostFree(state_host_);
-      state_host_cap_ = state_doubles_ + state_doubles_ / 8;
-      HIPCHK(hipHostMalloc((void **)&state_host_, sizeof(double) * state_host_cap_, hipHostMallocDefault));
-    }
-    HIPCHK(hipMemcpyAsync(state_host_, d.quat, state_doubles_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
+    CallLayout io = head_;
+    if (const int rc = reserve_call(io)) return rc;
+    double *p = io_host<double>(io, HEAD_STATE);
+    HIPCHK(hipMemcpyAsync(p, d.quat, state_doubles_ * sizeof(double), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
-    const double *p = state_host_;
-    if (quat) std::memcpy(quat, p, sizeof(double) * 4 * d.Ktot);
-    p += (size_t)4 * d.Ktot;
-    if (pos) std::memcpy(pos, p, sizeof(double) * 3 * d.Ktot);
-    p += (size_t)3 * d.Ktot;
-    if (bias) std::memcpy(bias, p, sizeof(double) * 6 * d.Ftot);
-    p += (size_t)6 * d.Ftot;
-    if (rho && d.Ltot) std::memcpy(rho, p, sizeof(double) * d.Ltot);
-    p += d.Ltot;
-    if (ld) std::memcpy(ld, p, sizeof(double) * d.nwin);
+    const std::pair<double *, size_t> dst[] = {{quat, (size_t)4 * d.Ktot}, {pos, (size_t)3 * d.Ktot}, {bias, (size_t)6 * d.Ftot}, {rho, (size_t)d.Ltot}, {ld, (size_t)d.nwin}};
+    for (const auto &x : dst) { if (x.first && x.second) std::memcpy(x.first, p, sizeof(double) * x.second); p += x.second; }
     return CTVIO_OK;
   }
 
   int linearize(int id, double *Hpp, double *W, double *Hll, double *g, double *cost) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (const int rc = guard(id)) return rc;
     Dev &d = dev_;
-    set_params(1);
-    launch_initial(opt_.initial_radius, 0);
     const WinMeta &m = meta_[id];
-    const int P = m.P;
+    const size_t P = (size_t)m.P, L = (size_t)m.L, nW = W ? (size_t)m.Lpad * m.ldw : 0;
+    CallLayout io = head_;
+    io.landing();   // (W comes as the device keeps it: Lpad sorted rows of ldw)
+    const int s_h = io.add("Hpp", sizeof(double), Hpp ? P * P : 0, false), s_w = io.add("W", sizeof(double), L ? nW : 0, false),
+              s_l = io.add("Hll", sizeof(double), Hll ? L : 0, false), s_g = io.add("g", sizeof(double), g ? (size_t)m.N : 0, false);
+    if (const int rc = reserve_call(io)) return rc;
+    double *hH = io_host<double>(io, s_h), *hW = io_host<double>(io, s_w), *hL = io_host<double>(io, s_l), *hg = io_host<double>(io, s_g);
+    Lm *lm = io_host<Lm>(io, HEAD_LM) + id;
+    set_params(1);
+    launch_initial(opt_.initial_radius);
     if (Hpp) {
-      HIPCHK(hipMemcpy2DAsync(Hpp, sizeof(double) * (size_t)P, d.HppS[0] + m.H0, sizeof(double) * (size_t)m.ldh, sizeof(double) * (size_t)P, (size_t)P,
-                              hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipMemcpy2DAsync(hH, sizeof(double) * P, d.HppS[0] + m.H0, sizeof(double) * (size_t)m.ldh, sizeof(double) * P, P, hipMemcpyDeviceToHost, stream_));
     }
-    std::vector<double> Wh;
-    if (W && m.L) {
-      Wh.resize((size_t)m.Lpad * m.ldw);
-      HIPCHK(hipMemcpyAsync(Wh.data(), d.WS[0] + m.W0, sizeof(double) * Wh.size(), hipMemcpyDeviceToHost, stream_));
-    }
-    if (Hll && m.L) HIPCHK(hipMemcpyAsync(Hll, d.HllS[0] + m.lm0, sizeof(double) * m.L, hipMemcpyDeviceToHost, stream_));
-    if (g) HIPCHK(hipMemcpyAsync(g, d.gS[0] + m.u0, sizeof(double) * m.N, hipMemcpyDeviceToHost, stream_));
-    Lm lm;
-    HIPCHK(hipMemcpyAsync(&lm, d.lm + id, sizeof(Lm), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    if (const int rc = check_span_violation()) return rc;
-    if (Hpp)
-      for (int i = 0; i < P; ++i)
-        for (int j = i + 1; j < P; ++j) Hpp[(size_t)i * P + j] = Hpp[(size_t)j * P + i];
-    if (W && m.L)
-      for (int i = 0; i < P; ++i)
-        for (int l = 0; l < m.L; ++l) W[(size_t)i * m.L + l] = (double)Wh[(size_t)h_lm_pos_[m.lm0 + l] * m.ldw + i];   // (rows of W: sorted landmark order)
-    if (cost) *cost = lm.cost;
+    if (W && L) HIPCHK(hipMemcpyAsync(hW, d.WS[0] + m.W0, sizeof(double) * nW, hipMemcpyDeviceToHost, stream_));
+    if (Hll && L) HIPCHK(hipMemcpyAsync(hL, d.HllS[0] + m.lm0, sizeof(double) * L, hipMemcpyDeviceToHost, stream_));
+    if (g) HIPCHK(hipMemcpyAsync(hg, d.gS[0] + m.u0, sizeof(double) * m.N, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(lm, d.lm + id, sizeof(Lm), hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    if (Hpp)   // (the device keeps the lower triangle)
+      for (size_t i = 0; i < P; ++i)
+        for (size_t j = 0; j < P; ++j) Hpp[i * P + j] = j <= i ? hH[i * P + j] : hH[j * P + i];
+    if (W && L)
+      for (size_t i = 0; i < P; ++i)
+        for (size_t l = 0; l < L; ++l) W[i * L + l] = hW[(size_t)h_lm_pos_[m.lm0 + l] * m.ldw + i];   // (rows of W: sorted landmark order)
+    if (Hll && L) std::memcpy(Hll, hL, sizeof(double) * L);
+    if (g) std::memcpy(g, hg, sizeof(double) * m.N);
+    if (cost) *cost = lm->cost;
     return CTVIO_OK;
   }
   int cost(int id, double *cost) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (const int rc = guard(id)) return rc;
     Dev &d = dev_;
-    const int wb = nblk(d.nwin, 64);
+    CallLayout io = head_;
+    if (const int rc = reserve_call(io)) return rc;
+    Lm *lm = io_host<Lm>(io, HEAD_LM) + id;
     set_params(1);
-    hipLaunchKernelGGL(k_lm_init, dim3(wb), dim3(64), 0, stream_, d, opt_.initial_radius, 1);
-    hipLaunchKernelGGL(k_knot_prep, dim3(nblk(d.Ktot, 256)), dim3(256), 0, stream_, d);
+    launch_prepare(opt_.initial_radius, 1);
     launch_evaluate(COST_AT_X);
     hipLaunchKernelGGL(k_misc, dim3(d.nwin), dim3(256), std::max(d.maxPn, 1) * sizeof(double), stream_, d, (int)COST_AT_X, 0, 0);
     hipLaunchKernelGGL(k_initial_cost, dim3(d.nwin), dim3(64), 0, stream_, d, 1);
-    Lm lm;
-    HIPCHK(hipMemcpyAsync(&lm, d.lm + id, sizeof(Lm), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    if (const int rc = check_span_violation()) return rc;
-    if (cost) *cost = lm.cand_cost;
+    HIPCHK(hipMemcpyAsync(lm, d.lm + id, sizeof(Lm), hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    if (cost) *cost = lm->cand_cost;
     return CTVIO_OK;
   }
   int lm_step(int id, double mu, double *delta, double *mc) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (const int rc = guard(id)) return rc;
     Dev &d = dev_;
+    const WinMeta &m = meta_[id];
+    CallLayout io = head_;
+    io.landing();
+    const int s_d = io.add("delta", sizeof(double), delta ? (size_t)m.N : 0, false);
+    if (const int rc = reserve_call(io)) return rc;
+    Lm *lm = io_host<Lm>(io, HEAD_LM) + id;
     set_params(1);
-    launch_initial(mu, 0);
+    launch_initial(mu);
     HIPCHK(hipMemsetAsync(d.n_active, 0, sizeof(int32_t), stream_));
     hipLaunchKernelGGL(k_begin_iter, dim3(d.nwin), dim3(256), 0, stream_, d);
     launch_step();
-    const WinMeta &m = meta_[id];
-    Lm lm;
-    if (delta) HIPCHK(hipMemcpyAsync(delta, d.delta + m.u0, sizeof(double) * m.N, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(&lm, d.lm + id, sizeof(Lm), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    if (const int rc = check_span_violation()) return rc;
-    if (mc) *mc = lm.step_valid ? lm.model_change : -1.0;
+    if (delta) HIPCHK(hipMemcpyAsync(io_host<double>(io, s_d), d.delta + m.u0, sizeof(double) * m.N, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(lm, d.lm + id, sizeof(Lm), hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    if (delta) std::memcpy(delta, io_host<double>(io, s_d), sizeof(double) * m.N);
+    if (mc) *mc = lm->step_valid ? lm->model_change : -1.0;
     return CTVIO_OK;
   }
   // Prior construction, all on the device: A, b of every window's factors by the linearise kernels, then one
@@ -904,6 +919,9 @@ class SolverImpl {
     MargResult(int rc_ = CTVIO_OK) : rc(rc_) {}
   };
   struct BlockedMeta { int w; MargMeta mm; };
+  struct MbBase {   // where the blocked path works: one window's scratch at a time (mb_scratch), the per-block sweep mass and its mirror, the call's lists
+    char *scr; double *mass, *mass_host; int32_t *rank; const int32_t *idx; double *out;
+  };
   MargResult marg_device(const int8_t *role_all, int only, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0, bool allow_blocked) {
     MargResult res;
     Dev &d = dev_;
@@ -911,7 +929,12 @@ class SolverImpl {
     std::vector<MargMeta> metas((size_t)nw);
     std::vector<BlockedMeta> bmeta;   // the blocked windows (k_marginalize sees them with m = n = 0)
     std::vector<int32_t> iscr;
-    size_t scr = 0, outd = 0;
+    // scr: A / V / X / Y / rot / b of every in-LDS window (MargMeta keeps their offsets in doubles), then the blocked path's scratch, sized for
+    // its largest window, and rank vector.  io: descriptors and index lists (in), J0 | r0 of every window packed as the caller gets them,
+    // and the blocked path's per-block mass (out: the host reads it after every sweep).
+    CallLayout io = head_, scr;
+    size_t outd = 0, mb_bytes = 0;
+    int mb_D = 0, mb_n = 0;
     for (int w = 0; w < nw; ++w) {
       const WinMeta &m = meta_[w];
       MargMeta &mm = metas[w];
@@ -929,43 +952,45 @@ class SolverImpl {
       mm.r0 = (int64_t)outd; outd += (size_t)mm.n;
       if (allow_blocked && mm.n > 0 && (big || dbg_.marg_blocked)) {
         bmeta.push_back({w, mm});
+        MbWin b = mb_window(w, mm);
+        mb_bytes = std::max(mb_bytes, mb_scratch(b, nullptr, nullptr));
+        mb_D = std::max(mb_D, std::max(b.dm, b.dn)); mb_n = std::max(mb_n, b.n);
         mm.m = mm.n = 0;
         continue;
       }
       const int np = std::max(mm.m, mm.n) + (std::max(mm.m, mm.n) & 1);
-      mm.A0 = (int64_t)scr; scr += (size_t)m.N * m.N;
-      mm.V0 = (int64_t)scr; scr += (size_t)mm.m * mm.m;
-      mm.X0 = (int64_t)scr; scr += (size_t)mm.m * (mm.n + 1);
-      mm.Y0 = (int64_t)scr; scr += (size_t)mm.m * (mm.n + 1);
-      mm.rot0 = (int64_t)scr; scr += (size_t)MARG_MAX_SWEEPS * std::max(np - 1, 1) * (np / 2) * 2;
-      mm.b0 = (int64_t)scr; scr += (size_t)mm.n;
+      const size_t mn1 = (size_t)mm.m * (mm.n + 1);
+      const std::pair<int64_t *, size_t> segs[] = {{&mm.A0, (size_t)m.N * m.N}, {&mm.V0, (size_t)mm.m * mm.m}, {&mm.X0, mn1}, {&mm.Y0, mn1},
+                                                   {&mm.rot0, (size_t)MARG_MAX_SWEEPS * std::max(np - 1, 1) * (np / 2) * 2}, {&mm.b0, (size_t)mm.n}};
+      for (const auto &sg : segs) *sg.first = (int64_t)(scr.off(scr.add("marg", sizeof(double), sg.second, true)) / sizeof(double));
     }
+    if (iscr.empty()) iscr.push_back(0);
+    const int s_mb = scr.add("mb", 1, mb_bytes, true), s_rank = scr.add("rank", sizeof(int32_t), (size_t)mb_n, false);
+    const int s_meta = io.add("meta", sizeof(MargMeta), (size_t)nw, false), s_idx = io.add("idx", sizeof(int32_t), iscr.size(), false),
+              s_out = io.add("out", sizeof(double), outd, true), s_mass = io.add("mass", sizeof(double), (size_t)2 * mb_D / MB_BLK, true);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    MargMeta *hmeta = io_host<MargMeta>(io, s_meta), *dmeta = io_dev<MargMeta>(io, s_meta);
+    const MbBase mb{scr.at<char>(call_scr_.dev, s_mb), io_dev<double>(io, s_mass), io_host<double>(io, s_mass), scr.at<int32_t>(call_scr_.dev, s_rank),
+                    io_dev<int32_t>(io, s_idx), io_dev<double>(io, s_out)};
     // normal equations of every window at its current state
     set_params(1);
-    launch_initial(opt_.initial_radius, 0);
-    HIPCHK(mg_meta_.upload(metas, stream_));
-    if (iscr.empty()) iscr.push_back(0);
-    HIPCHK(mg_idx_.upload(iscr, stream_));
-    HIPCHK(mg_scr_.alloc(scr));
-    HIPCHK(mg_out_.alloc(outd));
-    HIPCHK(poison(mg_scr_.p, sizeof(double) * scr));
-    HIPCHK(poison(mg_out_.p, sizeof(double) * outd));
+    launch_initial(opt_.initial_radius);
+    std::memcpy(hmeta, metas.data(), sizeof(MargMeta) * nw);
+    std::memcpy(io_host<int32_t>(io, s_idx), iscr.data(), sizeof(int32_t) * iscr.size());
+    HIPCHK(hipMemcpyAsync(dmeta, hmeta, io.off(s_out) - io.off(s_meta), hipMemcpyHostToDevice, stream_));   // (meta | idx)
     if (!marg_attr_set_) { HIPCHK(hipFuncSetAttribute((const void *)k_marginalize, hipFuncAttributeMaxDynamicSharedMemorySize, MARG_LDS_LIMIT)); marg_attr_set_ = true; }
     if (bmeta.size() < (size_t)nw)
-      hipLaunchKernelGGL(k_marginalize, dim3(nw), dim3(256), MargLds::BYTES, stream_, d, mg_meta_.p, mg_idx_.p, mg_scr_.p, mg_out_.p, eps);
+      hipLaunchKernelGGL(k_marginalize, dim3(nw), dim3(256), MargLds::BYTES, stream_, d, dmeta, mb.idx, reinterpret_cast<double *>(call_scr_.dev), mb.out, eps);
     for (BlockedMeta &b : bmeta) {
-      const int rc = marg_blocked(b.w, b.mm, eps);
+      const int rc = marg_blocked(b.w, b.mm, eps, mb);
       if (rc != CTVIO_OK) return rc;
       metas[b.w] = b.mm;
     }
-    std::vector<double> outh(std::max<size_t>(outd, 1));
-    HIPCHK(hipMemcpyAsync(outh.data(), mg_out_.p, sizeof(double) * std::max<size_t>(outd, 1), hipMemcpyDeviceToHost, stream_));
-    std::vector<MargMeta> small((size_t)nw);
-    HIPCHK(hipMemcpyAsync(small.data(), mg_meta_.p, sizeof(MargMeta) * nw, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    for (int w = 0; w < nw; ++w) if (small[w].n > 0) metas[w] = small[w];
-    HIPCHK(hipGetLastError());
-    if (const int rc = check_span_violation()) return rc;
+    const double *outh = io_host<double>(io, s_out);
+    if (outd) HIPCHK(hipMemcpyAsync((void *)outh, mb.out, sizeof(double) * outd, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(hmeta, dmeta, sizeof(MargMeta) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    for (int w = 0; w < nw; ++w) if (hmeta[w].n > 0) metas[w] = hmeta[w];
     size_t oj = 0, orr = 0;
     for (int w = 0; w < nw; ++w) {
       const MargMeta &mm = metas[w];
@@ -976,22 +1001,22 @@ class SolverImpl {
         std::fprintf(stderr, "\n");
       }
       if (mm.status) { res.stalled = w; res.rc = fail(CTVIO_ERR_HIP, "device eigen-solver did not converge (window " + std::to_string(w) + ")"); return res; }
-      std::memcpy(J0 + oj, outh.data() + mm.J0, sizeof(double) * (size_t)mm.n * mm.n);
-      std::memcpy(r0 + orr, outh.data() + mm.r0, sizeof(double) * (size_t)mm.n);
+      std::memcpy(J0 + oj, outh + mm.J0, sizeof(double) * (size_t)mm.n * mm.n);
+      std::memcpy(r0 + orr, outh + mm.r0, sizeof(double) * (size_t)mm.n);
       oj += (size_t)mm.n * mm.n; orr += (size_t)mm.n;
     }
     return res;
   }
   // Block two-sided Jacobi (csrc/marg_blocked.hpp) on B (D x D, nd real rows / columns) and V, one launch per phase; the host reads the
   // per-block mass after every sweep and applies jacobi_converged (csrc/jacobi_core.hpp).  *sweeps: the sweeps done, or -1; off / diagonal mass per sweep in trace.
-  int mb_jacobi(double *B, double *V, int D, int nd, double *Q, double *trace, int32_t *sweeps) {
+  int mb_jacobi(double *B, double *V, int D, int nd, double *Q, const MbBase &mb, double *trace, int32_t *sweeps) {
     const int nb = D / MB_BLK, npair = nb / 2;
-    std::vector<double> part((size_t)2 * nb);
+    const double *part = mb.mass_host;
     double prev_off = 1e300;
     *sweeps = -1;
     for (int sweep = 0; sweep < MB_MAX_SWEEPS; ++sweep) {
-      hipLaunchKernelGGL(k_mb_mass, dim3(nb), dim3(256), 0, stream_, B, D, mb_part_.p);
-      HIPCHK(hipMemcpyAsync(part.data(), mb_part_.p, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, stream_));
+      hipLaunchKernelGGL(k_mb_mass, dim3(nb), dim3(256), 0, stream_, B, D, mb.mass);
+      HIPCHK(hipMemcpyAsync(mb.mass_host, mb.mass, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, stream_));
       HIPCHK(hipStreamSynchronize(stream_));
       double off = 0.0, d2 = 0.0;
       for (int b = 0; b < nb; ++b) { off += part[2 * b]; d2 += part[2 * b + 1]; }
@@ -1006,46 +1031,50 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
-  // The scratch of one blocked window (b.m, b.n, b.dm, b.dn set), every segment once: points b and *Q (the Q of a step's block pairs)
-  // into base and returns the doubles used; base = nullptr gives the size alone.
-  static size_t mb_scratch(MbWin &b, double *base, double **Q) {
+  static MbWin mb_window(int w, const MargMeta &bm) {
+    MbWin b{};
+    b.w = w; b.m = bm.m; b.n = bm.n; b.dm = bm.m > 0 ? mb_padded(bm.m) : 0; b.dn = mb_padded(bm.n);
+    return b;
+  }
+  // The scratch of one blocked window, every segment once -- a layout of its own inside the call's "mb" segment: points b and *Q (the Q of a
+  // step's block pairs) into base and returns the bytes used; base = nullptr gives the size alone.
+  static size_t mb_scratch(MbWin &b, char *base, double **Q) {
     const size_t dm2 = (size_t)b.dm * b.dm, dn2 = (size_t)b.dn * b.dn, mn1 = (size_t)b.m * (b.n + 1);
     const std::pair<double **, size_t> segs[] = {{&b.Bm, dm2}, {&b.Vm, dm2}, {&b.Bn, dn2}, {&b.Vn, dn2}, {&b.G, mn1}, {&b.Y, mn1}, {&b.X, mn1},
                                                  {&b.bp, (size_t)b.n}, {Q, (size_t)(std::max(b.dm, b.dn) / 64) * 64 * 64}};
-    size_t off = 0;
-    for (const auto &sg : segs) { *sg.first = base ? base + off : nullptr; off += sg.second; }
-    return off;
+    CallLayout l;
+    for (const auto &sg : segs) l.add("mb", sizeof(double), sg.second, true);
+    if (base) {
+      l.reserved();
+      for (size_t k = 0; k < sizeof segs / sizeof segs[0]; ++k) *segs[k].first = l.at<double>(base, (int)k);
+    }
+    return l.bytes();
   }
-  // one window through the blocked path; J0 / r0 to mg_out_ at bm's offsets, status and sweeps into bm
-  int marg_blocked(int w, MargMeta &bm, double eps) {
-    const int m = bm.m, n = bm.n, dm = m > 0 ? mb_padded(m) : 0, dn = mb_padded(n), D = std::max(dm, dn);
+  // one window through the blocked path, in the call's reservation; J0 / r0 to mb.out at bm's offsets, status and sweeps into bm
+  int marg_blocked(int w, MargMeta &bm, double eps, const MbBase &mb) {
+    MbWin b = mb_window(w, bm);
+    const int m = b.m, n = b.n, dm = b.dm, dn = b.dn;
     const size_t mn1 = (size_t)m * (n + 1);
-    MbWin b;
-    b.w = w; b.m = m; b.n = n; b.dm = dm; b.dn = dn;
     double *Q;
-    const size_t need = mb_scratch(b, nullptr, &Q);
-    HIPCHK(hipStreamSynchronize(stream_));   // (the scratch of the previous window may still be in use)
-    HIPCHK(mb_scr_.alloc(need));
-    HIPCHK(mb_part_.alloc((size_t)2 * D / MB_BLK));
-    HIPCHK(mb_rank_.alloc((size_t)n));
-    HIPCHK(poison(mb_scr_.p, sizeof(double) * need));
-    HIPCHK(poison(mb_part_.p, sizeof(double) * 2 * D / MB_BLK));
-    mb_scratch(b, mb_scr_.p, &Q);
-    b.im = mg_idx_.p + bm.idx0; b.ik = b.im + m;
-    b.J0 = mg_out_.p + bm.J0; b.r0 = mg_out_.p + bm.r0; b.rank = mb_rank_.p;
+    const size_t need = mb_scratch(b, mb.scr, &Q);
+    // (CTVIO_POISON: every window starts on the pattern, not on the previous window's numbers)
+    HIPCHK(poison(mb.scr, need));
+    HIPCHK(poison(mb.mass, sizeof(double) * 2 * std::max(dm, dn) / MB_BLK));
+    b.im = mb.idx + bm.idx0; b.ik = b.im + m;
+    b.J0 = mb.out + bm.J0; b.r0 = mb.out + bm.r0; b.rank = mb.rank;
     auto grid = [](long long cnt) { return dim3((unsigned)std::max<long long>(1, (cnt + 255) / 256)); };
     const long long gat = std::max<long long>((long long)dm * dm, std::max<long long>((long long)mn1, (long long)dn * dn));
     hipLaunchKernelGGL(k_mb_gather, dim3((unsigned)std::min<long long>(2048, (gat + 255) / 256)), dim3(256), 0, stream_, dev_, b);
     int status = 0;
     bm.sweeps_m = 0;
     if (m > 0) {
-      if (const int rc = mb_jacobi(b.Bm, b.Vm, dm, m, Q, bm.trace, &bm.sweeps_m)) return rc;
+      if (const int rc = mb_jacobi(b.Bm, b.Vm, dm, m, Q, mb, bm.trace, &bm.sweeps_m)) return rc;
       if (bm.sweeps_m < 0) status = 1;
       hipLaunchKernelGGL(k_mb_y, grid((long long)mn1), dim3(256), 0, stream_, b, eps);
       hipLaunchKernelGGL(k_mb_x, grid((long long)mn1), dim3(256), 0, stream_, b);
     }
     hipLaunchKernelGGL(k_mb_reduce, grid((long long)dn * dn + n), dim3(256), 0, stream_, dev_, b);
-    if (const int rc = mb_jacobi(b.Bn, b.Vn, dn, n, Q, bm.trace + JACOBI_TRACE, &bm.sweeps_n)) return rc;
+    if (const int rc = mb_jacobi(b.Bn, b.Vn, dn, n, Q, mb, bm.trace + JACOBI_TRACE, &bm.sweeps_n)) return rc;
     if (bm.sweeps_n < 0) status = 1;
     hipLaunchKernelGGL(k_mb_rank, grid(n), dim3(256), 0, stream_, b, eps);
     hipLaunchKernelGGL(k_mb_j0, grid((long long)n * n), dim3(256), 0, stream_, b, eps);
@@ -1054,7 +1083,7 @@ class SolverImpl {
     return CTVIO_OK;
   }
   int marginalize_batch(const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     if (!role || !n_keep || !kept || !J0 || !r0 || !(eps >= 0)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     for (int i = 0; i < dev_.Utot; ++i) if (role[i] < -1 || role[i] > 1) return fail(CTVIO_ERR_INVALID, "role must be -1, 0 or 1");
     marg_ran_on_host_ = 0;
@@ -1067,8 +1096,7 @@ class SolverImpl {
   }
   // one window; windows beyond the device eigen-solver's size (m or n > MARG_MAXD) take the host path (csrc/marginalize.hpp)
   int marginalize(int id, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
+    if (const int rc = guard(id)) return rc;
     if (!role || !n_keep || !kept || !J0 || !r0 || !(eps >= 0)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     const WinMeta &m = meta_[id];
     const int N = m.N, P = m.P, L = m.L;
@@ -1111,22 +1139,22 @@ class SolverImpl {
   }
   // ResidualSummary (reference trajectory_estimator.h:37-59): per-type sums of |r_i| at the current state
   int residual_summary(int id, double *sums, int32_t *counts4) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin || !sums) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (const int rc = guard(id, "bad arguments")) return rc;
+    if (!sums) return fail(CTVIO_ERR_INVALID, "bad arguments");
     const WinMeta &m = meta_[id];
-    const int n = 14 + m.pn;
-    DBuf<double> out;
-    HIPCHK(out.alloc(n));
-    HIPCHK(poison(out.p, sizeof(double) * n));
-    hipLaunchKernelGGL(k_residual_summary, dim3(1), dim3(256), (size_t)(14 + 2 * m.pn) * sizeof(double), stream_, dev_, id, out.p);
-    HIPCHK(hipMemcpyAsync(sums, out.p, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
+    const size_t n = (size_t)14 + m.pn;
+    CallLayout io = head_;
+    const int s_out = io.add("sums", sizeof(double), n, true);
+    if (const int rc = reserve_call(io)) return rc;
+    hipLaunchKernelGGL(k_residual_summary, dim3(1), dim3(256), (size_t)(14 + 2 * m.pn) * sizeof(double), stream_, dev_, id, io_dev<double>(io, s_out));
+    HIPCHK(hipMemcpyAsync(io_host<double>(io, s_out), io_dev<double>(io, s_out), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = sync_call()) return rc;
+    std::memcpy(sums, io_host<double>(io, s_out), sizeof(double) * n);
     if (counts4) { counts4[0] = m.M; counts4[1] = m.NB; counts4[2] = m.V; counts4[3] = m.pn > 0 ? 1 : 0; }
     return CTVIO_OK;
   }
   int gauge_restore(int n, const int32_t *ids, const int32_t *knot, const double *q0, const double *t0) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     if (n < 0 || (n && (!ids || !knot || !q0 || !t0))) return fail(CTVIO_ERR_INVALID, "bad arguments");
     for (int i = 0; i < n; ++i) {
       if (ids[i] < 0 || ids[i] >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "window id out of range");
@@ -1134,19 +1162,18 @@ class SolverImpl {
       for (int j = 0; j < i; ++j) if (ids[j] == ids[i]) return fail(CTVIO_ERR_INVALID, "window listed twice");
     }
     if (n == 0) return CTVIO_OK;
-    // one grow-only scratch buffer and one staged copy: [ids | knot] as int32, then [q0 | t0] as doubles
-    const size_t nbytes = (((size_t)2 * n * sizeof(int32_t) + 15) & ~(size_t)15) + (size_t)7 * n * sizeof(double);
-    if (const int rc = call_scratch(nbytes)) return rc;
-    char *hs = call_host_, *ds = call_dev_.p;
-    const size_t ioff = ((size_t)2 * n * sizeof(int32_t) + 15) & ~(size_t)15;
-    std::memcpy(hs, ids, sizeof(int32_t) * n); std::memcpy(hs + sizeof(int32_t) * n, knot, sizeof(int32_t) * n);
-    std::memcpy(hs + ioff, q0, sizeof(double) * 4 * n); std::memcpy(hs + ioff + sizeof(double) * 4 * n, t0, sizeof(double) * 3 * n);
-    HIPCHK(hipMemcpyAsync(ds, hs, nbytes, hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL(k_gauge_restore, dim3(n), dim3(64), 0, stream_, dev_, n, reinterpret_cast<const int32_t *>(ds),
-                       reinterpret_cast<const int32_t *>(ds) + n, reinterpret_cast<const double *>(ds + ioff), reinterpret_cast<const double *>(ds + ioff) + 4 * (size_t)n);
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    return CTVIO_OK;
+    // one staged copy: [ids | knot], then [q0 | t0]
+    const size_t nn = (size_t)n;
+    CallLayout io = head_;
+    const int s_i = io.add("ids_knot", sizeof(int32_t), 2 * nn, false), s_p = io.add("q0_t0", sizeof(double), 7 * nn, false);
+    if (const int rc = reserve_call(io)) return rc;
+    int32_t *hi = io_host<int32_t>(io, s_i), *di = io_dev<int32_t>(io, s_i);
+    double *hp = io_host<double>(io, s_p), *dp = io_dev<double>(io, s_p);
+    std::memcpy(hi, ids, sizeof(int32_t) * nn); std::memcpy(hi + nn, knot, sizeof(int32_t) * nn);
+    std::memcpy(hp, q0, sizeof(double) * 4 * nn); std::memcpy(hp + 4 * nn, t0, sizeof(double) * 3 * nn);
+    HIPCHK(hipMemcpyAsync(di, hi, io.bytes() - io.off(s_i), hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(k_gauge_restore, dim3(n), dim3(64), 0, stream_, dev_, n, di, di + nn, dp, dp + 4 * nn);
+    return sync_call();
   }
   int spline_eval(int id, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3, const double *q_SI = nullptr,
                   const double *p_SI = nullptr) {
@@ -1158,14 +1185,14 @@ class SolverImpl {
       for (int i = 0; i < 3; ++i) ext.p[i] = p_SI[i];
       ext.on = 1;
     }
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
-    if (id < 0 || id >= dev_.nwin || n < 0 || (n && !t_ns)) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (const int rc = guard(id, "bad arguments")) return rc;
+    if (n < 0 || (n && !t_ns)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     return spline_query(id, nullptr, n, t_ns, pose7, vel3, omega3, acc3, ext, nullptr);
   }
   // Queries of any windows of the batch in ONE launch (query i: window win[i], absolute time t_ns[i]).
   int spline_eval_batch(int64_t n64, const int32_t *win, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
                         double *kernel_ms) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || !win))) return fail(CTVIO_ERR_INVALID, "bad arguments");
     if (kernel_ms) *kernel_ms = 0.0;
     return spline_query(0, win, (int)n64, t_ns, pose7, vel3, omega3, acc3, SensorExt{}, kernel_ms);
@@ -1174,49 +1201,47 @@ class SolverImpl {
   int spline_query(int id, const int32_t *win, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
                    const SensorExt &ext, double *kernel_ms) {
     if (n == 0) return CTVIO_OK;
-    // grow-only scratch (pinned host mirror): [t_rel n x i64 | window n x i32 (with a window list) | err | pose 7n | vel 3n | omega 3n | acc 3n]
-    const size_t o_win = sizeof(long long) * (size_t)n, o_err = win ? (o_win + sizeof(int32_t) * (size_t)n + 15) & ~(size_t)15 : o_win, o_out = o_err + 16;
-    const size_t nd = (size_t)n * ((pose7 ? 7 : 0) + (vel3 ? 3 : 0) + (omega3 ? 3 : 0) + (acc3 ? 3 : 0));
-    if (const int rc = call_scratch(o_out + nd * sizeof(double))) return rc;
-    char *hs = call_host_, *ds = call_dev_.p;
-    long long *rel = reinterpret_cast<long long *>(hs);
-    int32_t *hw = reinterpret_cast<int32_t *>(hs + o_win);
+    // in: relative times, windows (with a window list), the error word; out: the error word again and the outputs the caller asked for
+    const size_t nn = (size_t)n;
+    double *const out[4] = {pose7, vel3, omega3, acc3};
+    const size_t width[4] = {7, 3, 3, 3};
+    CallLayout io = head_;
+    const int s_rel = io.add("t_rel", sizeof(long long), nn, false), s_win = io.add("win", sizeof(int32_t), win ? nn : 0, false),
+              s_err = io.add("err", sizeof(int32_t), 4, false);
+    int s_out[4];
+    for (int k = 0; k < 4; ++k) s_out[k] = io.add("query_out", sizeof(double), out[k] ? width[k] * nn : 0, true);
+    if (const int rc = reserve_call(io)) return rc;
+    long long *rel = io_host<long long>(io, s_rel);
+    int32_t *hw = io_host<int32_t>(io, s_win);
+    int *herr = io_host<int>(io, s_err), *derr = io_dev<int>(io, s_err);
     for (int i = 0; i < n; ++i) {
       if (win && (win[i] < 0 || win[i] >= dev_.nwin)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
       if (win) hw[i] = win[i];
       rel[i] = (long long)(t_ns[i] - t0_[win ? win[i] : id]);
     }
-    *reinterpret_cast<int *>(hs + o_err) = 0;
-    HIPCHK(hipMemcpyAsync(ds, hs, o_out, hipMemcpyHostToDevice, stream_));
-    HIPCHK(poison(ds + o_out, nd * sizeof(double)));
-    double *dp = reinterpret_cast<double *>(ds + o_out), *dv = dp + (pose7 ? (size_t)7 * n : 0), *dw = dv + (vel3 ? (size_t)3 * n : 0),
-           *da = dw + (omega3 ? (size_t)3 * n : 0);
-    if (kernel_ms) HIPCHK(hipEventRecord(ev_[10], stream_));
-    hipLaunchKernelGGL(k_spline_eval, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, id, win ? reinterpret_cast<const int32_t *>(ds + o_win) : nullptr, n,
-                       reinterpret_cast<const long long *>(ds), pose7 ? dp : nullptr, vel3 ? dv : nullptr, omega3 ? dw : nullptr, acc3 ? da : nullptr,
-                       reinterpret_cast<int *>(ds + o_err), ext);
-    if (kernel_ms) HIPCHK(hipEventRecord(ev_[11], stream_));
-    HIPCHK(hipMemcpyAsync(hs + o_err, ds + o_err, 16 + nd * sizeof(double), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev_[10], ev_[11])); *kernel_ms = ms; }
-    const int err = *reinterpret_cast<int *>(hs + o_err);
-    const double *ho = reinterpret_cast<const double *>(hs + o_out);
-    if (pose7) { std::memcpy(pose7, ho, sizeof(double) * 7 * n); ho += (size_t)7 * n; }
-    if (vel3) { std::memcpy(vel3, ho, sizeof(double) * 3 * n); ho += (size_t)3 * n; }
-    if (omega3) { std::memcpy(omega3, ho, sizeof(double) * 3 * n); ho += (size_t)3 * n; }
-    if (acc3) std::memcpy(acc3, ho, sizeof(double) * 3 * n);
-    if (err) return fail(CTVIO_ERR_INVALID, "query time outside the spline");
+    *herr = 0;
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_rel), rel, io.off(s_out[0]) - io.off(s_rel), hipMemcpyHostToDevice, stream_));
+    double *dv[4];
+    for (int k = 0; k < 4; ++k) dv[k] = out[k] ? io_dev<double>(io, s_out[k]) : nullptr;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+    hipLaunchKernelGGL(k_spline_eval, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, id, win ? io_dev<int32_t>(io, s_win) : nullptr, n,
+                       io_dev<long long>(io, s_rel), dv[0], dv[1], dv[2], dv[3], derr, ext);
+    if (kernel_ms) HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+    HIPCHK(hipMemcpyAsync(herr, derr, io.bytes() - io.off(s_err), hipMemcpyDeviceToHost, stream_));   // (err | outputs)
+    if (const int rc = sync_call()) return rc;
+    if (kernel_ms) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END])); *kernel_ms = ms; }
+    for (int k = 0; k < 4; ++k) if (out[k]) std::memcpy(out[k], io_host<double>(io, s_out[k]), sizeof(double) * width[k] * nn);
+    if (*herr) return fail(CTVIO_ERR_INVALID, "query time outside the spline");
     return CTVIO_OK;
   }
   // ---------------------------------------------------------------------------------------- marginal covariances
   // ctvio_covariance_batch / ctvio_covariance (only >= 0: that window alone, n_sel / sel / outputs are its own).  The normal equations of the
   // current state (as ctvio_linearize forms them), then Schur complement and panel Cholesky on a COPY of Dev -- per-call activity mask, zero
-  // damping, every tile of S written -- and the kernels of csrc/kernels_cov.hpp.  dev_, plan_ and the captured graph are not touched; the scratch
-  // is a grow-only buffer of its own (its size follows the call's selections, not the upload).
+  // damping, every tile of S written -- and the kernels of csrc/kernels_cov.hpp.  dev_, plan_ and the captured graph are not touched; the panel
+  // kernel launches from the plan like the solve's (launch_chol_panel).  The scratch follows the call's selections, not the upload.
   static constexpr int COV_MAX_SEL = 64;
   int covariance(int only, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
-    if (!uploaded_) return fail(CTVIO_ERR_STATE, "ctvio_upload not called");
+    if (const int rc = guard()) return rc;
     const int nw = dev_.nwin;
     if (only >= nw) return fail(CTVIO_ERR_INVALID, "window id out of range");
     if (!n_sel) return fail(CTVIO_ERR_INVALID, "null n_sel");
@@ -1252,71 +1277,63 @@ class SolverImpl {
         nsel_tot += (size_t)ns; ncov += (size_t)ns * ns;
       }
     }
-    // ---- scratch: [mask Utot | excl Utot | sel | tiles | windows | Y | cov | var_rho (Ltot, batch order)]
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_excl = up((size_t)dev_.Utot), o_sel = 2 * o_excl, o_tiles = o_sel + up(sizeof(int32_t) * nsel_tot), o_wins = o_tiles + up(sizeof(CovTile) * tiles.size());
-    const size_t o_y = o_wins + up(sizeof(CovWin) * cwins.size()), o_cov = o_y + up(sizeof(double) * ycount), o_var = o_cov + up(sizeof(double) * ncov);
-    const size_t nvar = var_rho ? (size_t)dev_.Ltot : 0, total = o_var + up(sizeof(double) * nvar);
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(cov_dev_.alloc(total));
-    char *ds = cov_dev_.p;
-    uint8_t *mask = reinterpret_cast<uint8_t *>(ds), *excl = mask + o_excl;
-    const int32_t *dsel = reinterpret_cast<const int32_t *>(ds + o_sel);
-    const CovTile *dtiles = reinterpret_cast<const CovTile *>(ds + o_tiles);
-    const CovWin *dwins = reinterpret_cast<const CovWin *>(ds + o_wins);
-    double *dy = reinterpret_cast<double *>(ds + o_y), *dcov = reinterpret_cast<double *>(ds + o_cov), *dvar = reinterpret_cast<double *>(ds + o_var);
-    if (nsel_tot) HIPCHK(hipMemcpyAsync(ds + o_sel, sel, sizeof(int32_t) * nsel_tot, hipMemcpyHostToDevice, stream_));
-    if (!tiles.empty()) HIPCHK(hipMemcpyAsync(ds + o_tiles, tiles.data(), sizeof(CovTile) * tiles.size(), hipMemcpyHostToDevice, stream_));
-    if (!cwins.empty()) HIPCHK(hipMemcpyAsync(ds + o_wins, cwins.data(), sizeof(CovWin) * cwins.size(), hipMemcpyHostToDevice, stream_));
-    HIPCHK(poison(ds + o_y, total - o_y));
+    // ---- scratch.  io: selections, tiles, windows (in, one staged copy); cov | var_rho (Ltot, batch order) (out, one copy).  scr: mask, exclusions, Y
+    const size_t nvar = var_rho ? (size_t)dev_.Ltot : 0;
+    CallLayout io = head_, scr;
+    const int s_sel = io.add("sel", sizeof(int32_t), nsel_tot, false), s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
+              s_wins = io.add("wins", sizeof(CovWin), cwins.size(), false), s_cov = io.add("cov", sizeof(double), ncov, true),
+              s_var = io.add("var_rho", sizeof(double), nvar, true);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_y = scr.add("Y", sizeof(double), ycount, true);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    double *dy = scr.at<double>(call_scr_.dev, s_y), *dcov = io_dev<double>(io, s_cov), *dvar = io_dev<double>(io, s_var);
+    const int32_t *dsel = io_dev<int32_t>(io, s_sel);
+    const CovTile *dtiles = io_dev<CovTile>(io, s_tiles);
+    const CovWin *dwins = io_dev<CovWin>(io, s_wins);
+    const double *hcov = io_host<double>(io, s_cov), *vh = io_host<double>(io, s_var);
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    if (nsel_tot) std::memcpy(io_host<int32_t>(io, s_sel), sel, sizeof(int32_t) * nsel_tot);
+    if (!tiles.empty()) std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+    if (!cwins.empty()) std::memcpy(io_host<CovWin>(io, s_wins), cwins.data(), sizeof(CovWin) * cwins.size());
+    if (io.off(s_cov) > io.off(s_sel))
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_sel), io_host<char>(io, s_sel), io.off(s_cov) - io.off(s_sel), hipMemcpyHostToDevice, stream_));
     // ---- normal equations at the current state, then the factor of the undamped reduced system
     set_params(1);
-    HIPCHK(hipEventRecord(ev_[8], stream_));
-    launch_initial(opt_.initial_radius, 0);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+    launch_initial(opt_.initial_radius);
     Dev c = dev_;
     c.schur_plain_in_H = 0;
     c.active = mask;
-    HIPCHK(hipEventRecord(ev_[12], stream_));
+    HIPCHK(hipEventRecord(ev_[EV_COV_PREPARE], stream_));
     hipLaunchKernelGGL(k_cov_prepare, dim3(nw), dim3(256), 0, stream_, dev_, mask, excl);
-    HIPCHK(hipEventRecord(ev_[13], stream_));
+    HIPCHK(hipEventRecord(ev_[EV_COV_FACTOR], stream_));
     launch_schur(c);
-    {
-      const BatchFacts &b = facts_;
-      const bool w8 = nw <= 192 || b.chol_lds > 80 * 1024;
-      if (b.chol_compact) {
-        if (w8) hipLaunchKernelGGL((k_cholesky_solve<8, true>), dim3(nw), dim3(512), b.chol_lds, stream_, c);
-        else hipLaunchKernelGGL((k_cholesky_solve<4, true>), dim3(nw), dim3(256), b.chol_lds, stream_, c);
-      } else {
-        if (w8) hipLaunchKernelGGL((k_cholesky_solve<8>), dim3(nw), dim3(512), b.chol_lds, stream_, c);
-        else hipLaunchKernelGGL((k_cholesky_solve<4>), dim3(nw), dim3(256), b.chol_lds, stream_, c);
-      }
-    }
-    HIPCHK(hipEventRecord(ev_[14], stream_));
+    launch_chol_panel(c);
+    HIPCHK(hipEventRecord(ev_[EV_COV_SOLVE], stream_));
     if (!tiles.empty()) {
       const size_t lds = ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double);
       hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), lds, stream_, c, dtiles, dsel, dy, dvar);
     }
-    HIPCHK(hipEventRecord(ev_[15], stream_));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     if (!cwins.empty())
       hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
-    HIPCHK(hipEventRecord(ev_[9], stream_));
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
     // ---- results
-    std::vector<double> vh(nvar);
-    if (ncov) HIPCHK(hipMemcpyAsync(cov, dcov, sizeof(double) * ncov, hipMemcpyDeviceToHost, stream_));
-    if (nvar) HIPCHK(hipMemcpyAsync(vh.data(), dvar, sizeof(double) * nvar, hipMemcpyDeviceToHost, stream_));
-    Lm *lm = lm_host_;
+    if (ncov + nvar) HIPCHK(hipMemcpyAsync((void *)hcov, dcov, io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipStreamSynchronize(stream_));
-    HIPCHK(hipGetLastError());
-    if (const int rc = check_span_violation()) return rc;
+    if (const int rc = finish_call(io)) return rc;
     {   // device times of this call, for ctvio_last_timing: the three covariance kernels and the whole call
-      const int pair[4][2] = {{12, 13}, {14, 15}, {15, 9}, {8, 9}};
-      float ms[4] = {0, 0, 0, 0};
-      for (int i = 0; i < 4; ++i) HIPCHK(hipEventElapsedTime(&ms[i], ev_[pair[i][0]], ev_[pair[i][1]]));
-      std::fill(timing_, timing_ + 8, 0.0); std::fill(ph_n_, ph_n_ + 8, 0);
-      timing_[0] = ms[0]; timing_[1] = ms[1]; timing_[2] = ms[2]; timing_[7] = ms[3];
-      ph_n_[0] = 1; ph_n_[1] = tiles.empty() ? 0 : 1; ph_n_[2] = cwins.empty() ? 0 : 1;
-      last_iters_ = 0;
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_SOLVE, EV_COV_GRAM}, {EV_COV_GRAM, EV_CALL_END}};
+      const bool ran[3] = {true, !tiles.empty(), !cwins.empty()};
+      Timing t;
+      t.clear();
+      for (int i = 0; i < 3; ++i) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev_[pair[i][0]], ev_[pair[i][1]]));
+        t.ms[i] = ms; t.n[i] = ran[i] ? 1 : 0;
+      }
+      if (const int rc = publish_timing(t, 0)) return rc;
     }
     // (a window whose factorisation met a non-positive or non-finite pivot: its outputs are NaN)
     const double nan = std::nan("");
@@ -1326,7 +1343,7 @@ class SolverImpl {
       const size_t ns = (size_t)n_sel[w - wbeg];
       const bool bad = lm[w].chol_fail != 0;
       if (singular) singular[w - wbeg] = bad ? 1 : 0;
-      if (bad) std::fill(cov + oc, cov + oc + ns * ns, nan);
+      if (ns) { if (bad) std::fill(cov + oc, cov + oc + ns * ns, nan); else std::memcpy(cov + oc, hcov + oc, sizeof(double) * ns * ns); }
       if (var_rho) {
         for (int l = 0; l < m.L; ++l) var_rho[ov + l] = bad ? nan : vh[(size_t)m.lm0 + l];
         ov += (size_t)m.L;
@@ -1336,8 +1353,8 @@ class SolverImpl {
     return CTVIO_OK;
   }
   int last_timing(double *ms8, int32_t *n8) {
-    if (ms8) std::copy(timing_, timing_ + 8, ms8);
-    if (n8) { std::copy(ph_n_, ph_n_ + 7, n8); n8[7] = last_iters_; }
+    if (ms8) std::copy(timing_.ms, timing_.ms + 8, ms8);
+    if (n8) std::copy(timing_.n, timing_.n + 8, n8);
     return CTVIO_OK;
   }
   int set_profiling(int on) { profiling_requested_ = on != 0; return CTVIO_OK; }
@@ -1347,10 +1364,9 @@ class SolverImpl {
   const DebugSwitches dbg_;   // environment switches as they were when the handle was created
   int marg_ran_on_host_ = 0;  // the last ctvio_marginalize(_batch) call: 1 if the factorisation ran on the host
   hipStream_t stream_ = nullptr;
-  hipEvent_t ev_[16] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev_[EV_COUNT] = {};
   bool uploaded_ = false, profiling_ = false, profiling_requested_ = false;
-  double timing_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ph_ms_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t ph_n_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_iters_ = 0;
+  Timing timing_{};          // what ctvio_last_timing reports: the last solve or covariance call
   std::vector<hipEvent_t> pev_;
   std::vector<int> pev_phase_;
   size_t pev_used_ = 0;
@@ -1363,9 +1379,8 @@ class SolverImpl {
   size_t state_doubles_ = 0;
   Arena in_, work_;          // uploaded inputs (pinned mirror) / device-only work buffers
   WorkerPool pool_;          // the handle's packing threads (created on first use, kept)
-  // scratch of the small per-call entries (spline query, gauge restore): grow-only device buffer + pinned host mirror
-  DBuf<char> call_dev_;
-  char *call_host_ = nullptr; size_t call_host_cap_ = 0;
+  Arena call_io_, call_scr_;   // scratch of the per-call entries: copied in or out (pinned mirror) / device only
+  CallLayout head_;            // the fixed head of call_io_ (HEAD_*), laid out by the upload
   // CTVIO_POISON: a reused handle's scratch holds the numbers of earlier calls in another layout, a fresh one zeros.  A kernel that reads
   // an entry it never wrote and masks it by a product instead of a select is right on zeros only; with the switch every double buffer
   // the next call reuses starts as a quiet NaN (1) or as a large finite value (2, caught where fmax / fmin or a comparison would drop a
@@ -1375,31 +1390,12 @@ class SolverImpl {
     const uint32_t pattern = dbg_.poison == 2 ? 0x5F5F5F5Fu : 0x7FF8DEADu;
     return hipMemsetD32Async((hipDeviceptr_t)p, (int)pattern, bytes / 4, stream_);
   }
-  // a pinned word pair for the "still running" and span-violation polls: the record after the lm_host_cap_ window records
-  int32_t *lm_scratch() { return reinterpret_cast<int32_t *>(lm_host_ + lm_host_cap_); }
-  int call_scratch(size_t bytes) {
-    HIPCHK(call_dev_.alloc(bytes));
-    if (bytes > call_host_cap_) {
-      if (call_host_) (void)hipHostFree(call_host_);
-      call_host_cap_ = bytes + bytes / 4 + 4096;
-      HIPCHK(hipHostMalloc((void **)&call_host_, call_host_cap_, hipHostMallocDefault));
-    }
-    return CTVIO_OK;
-  }
-  DBuf<char> cov_dev_;       // ctvio_covariance(_batch): mask, selections, tiles, Y, outputs (grow-only)
-  DBuf<MargMeta> mg_meta_;   // device marginalisation: descriptors, index lists, scratch, outputs
-  DBuf<int32_t> mg_idx_;
-  DBuf<double> mg_scr_, mg_out_;
-  DBuf<double> mb_scr_, mb_part_;   // blocked marginalisation (csrc/marg_blocked.hpp): scratch of one window, per-block sweep mass
-  DBuf<int32_t> mb_rank_;
   bool marg_attr_set_ = false;
   double *snap_ = nullptr;   // state snapshot (inside work_)
-  Lm *lm_host_ = nullptr; size_t lm_host_cap_ = 0;
   int graph_captures_ = 0;                // how many times the pass was captured (ctvio_graph_captures: a stream of equal batches captures once)
   hipGraphExec_t graph_exec_ = nullptr;   // one LM pass (launch_pass) as a graph, valid while dev_ == graph_dev_ and plan_ == graph_plan_
   Dev graph_dev_;
   LaunchPlan graph_plan_;
-  double *state_host_ = nullptr; size_t state_host_cap_ = 0;
   bool snap_valid_ = false;
   const double *h_ld_ = nullptr;        // the line delays as uploaded (same arena)
   const int32_t *h_lm_pos_ = nullptr;   // host mirror of Dev::lm_pos (inside in_.host: valid while the batch is uploaded)

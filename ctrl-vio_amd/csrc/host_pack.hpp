@@ -83,30 +83,33 @@ class WorkerPool {
   bool quit_ = false;
 };
 
-// Grow-only device buffer, optionally mirrored by pinned host memory of the same size.
+// Grow-only device buffer, optionally mirrored by pinned host memory.  The mirror may run `landing` bytes past the device block: landing
+// areas of copies whose source lies elsewhere on the device, which need no device twin.
 struct Arena {
   char *dev = nullptr, *host = nullptr;
-  size_t cap = 0;
-  bool mirrored = false;
+  size_t cap = 0, hcap = 0;
   ~Arena() { release(); }
   void release() {
     if (dev) (void)hipFree(dev);
     if (host) (void)hipHostFree(host);
-    dev = host = nullptr; cap = 0;
+    dev = host = nullptr; cap = hcap = 0;
   }
-  // returns hipSuccess; *grew tells the caller that the contents (and every pointer into the arena) are gone
-  hipError_t reserve(size_t bytes, bool mirror, bool *grew) {
+  // returns hipSuccess; *grew tells the caller that the contents (and every pointer into the arena) are gone.  headroom: a slightly larger
+  // next batch does not reallocate (not for device-only scratch of tens of MB).
+  hipError_t reserve(size_t bytes, bool mirror, bool *grew, size_t landing = 0, bool headroom = true) {
+    const size_t hbytes = mirror ? bytes + landing : 0;
     if (grew) *grew = false;
-    if (bytes <= cap && dev && (!mirror || host)) return hipSuccess;
+    if (bytes <= cap && dev && hbytes <= hcap && (!mirror || host)) return hipSuccess;
+    auto grown = [&](size_t need, size_t have) { return std::max(std::max<size_t>(need + (headroom ? need / 8 : 0), 4096), have); };
+    const size_t want = grown(bytes, cap), hwant = mirror ? grown(hbytes, hcap) : 0;
     release();
-    const size_t want = std::max<size_t>(bytes + bytes / 8, 4096);   // headroom: a slightly larger next batch does not reallocate
     hipError_t e = hipMalloc((void **)&dev, want);
     if (e != hipSuccess) { dev = nullptr; return e; }
     if (mirror) {
-      e = hipHostMalloc((void **)&host, want, hipHostMallocDefault);
+      e = hipHostMalloc((void **)&host, hwant, hipHostMallocDefault);
       if (e != hipSuccess) { host = nullptr; release(); return e; }
     }
-    cap = want; mirrored = mirror;
+    cap = want; hcap = hwant;
     if (grew) *grew = true;
     return hipSuccess;
   }
@@ -461,6 +464,36 @@ struct ArenaSeg {
   bool dbl;
 };
 inline size_t arena_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// The layout of one per-call entry's scratch (ctvio.hip: call_io_ / call_scr_).  The call names every segment ONCE, in order: add(name,
+// element size, count, dbl) gives 256-byte aligned offsets and bytes(), the total.  One reservation per call: after reserved() -- the
+// caller's arena holds bytes() -- at<T>(base, segment) gives typed pointers and add() is refused (-1), as at() is before it (null): a grow
+// frees the old block, and a pointer taken before it would be stale inside an already queued kernel.  A segment without elements costs
+// nothing (it shares its offset with the next one).  Segments added after landing() exist in the pinned mirror only: dev_bytes() ends before them.
+class CallLayout {
+ public:
+  int add(const char *name, size_t elem, size_t count, bool dbl) {
+    if (reserved_) return -1;
+    segs_.push_back(ArenaSeg{name, bytes_, elem * count, dbl});
+    bytes_ += arena_align(elem * count);
+    if (!landing_) dev_bytes_ = bytes_;
+    return (int)segs_.size() - 1;
+  }
+  void landing() { landing_ = true; }
+  void reserved() { reserved_ = true; }
+  size_t bytes() const { return bytes_; }
+  size_t dev_bytes() const { return dev_bytes_; }
+  const std::vector<ArenaSeg> &segs() const { return segs_; }
+  size_t off(int seg) const { return segs_[(size_t)seg].off; }
+  template <class T> T *at(char *base, int seg) const {
+    return reserved_ && base && seg >= 0 && seg < (int)segs_.size() ? reinterpret_cast<T *>(base + segs_[(size_t)seg].off) : nullptr;
+  }
+
+ private:
+  std::vector<ArenaSeg> segs_;
+  size_t bytes_ = 0, dev_bytes_ = 0;
+  bool landing_ = false, reserved_ = false;
+};
 
 // The input arena (pinned host mirror + device), every segment ONCE: X(element type, segment, Dev member, allocated count, filled count).
 // An empty set keeps one entry allocated.  The names stand for BatchFacts members (layout_input).  Irregular: `state` is the contiguous

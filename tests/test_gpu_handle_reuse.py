@@ -161,6 +161,22 @@ def _run_marg(cv, s, ws, roles, single=None, form=False):
     return out
 
 
+def _cov_windows(cv):
+    """`tiny` (P = 103) and `config1` (P = 211) with selections of 20 and 17 unknowns, none of them on the two newest knots (an
+    unknown that no factor touches has an infinite variance, and the comparison asks for finite numbers)."""
+    ws = [cv.synth.make_window("tiny", seed=7), cv.synth.make_window("config1", seed=1000)]
+    rng = np.random.default_rng(11)
+    sels = [[int(x) for x in rng.permutation(np.r_[0:6 * (w.K - 2), 6 * w.K:w.P])[:n]] for w, n in zip(ws, (20, 17))]
+    return ws, sels
+
+
+def _run_cov(cv, s, ws, sels):
+    """covariance_batch with the landmark variances, then the single-window entry alone."""
+    s.set_windows([w.copy() for w in ws])
+    covs, var, sing = s.covariance_batch(sels, rho=True)
+    return {"cov": covs, "var": var, "singular": sing, "one": s.covariance(1, sels[1], rho=True)}
+
+
 def _spline_windows(cv):
     ws = [cv.synth.make_window("tiny", seed=21), cv.synth.make_window("config1", seed=1004), cv.synth.make_window("config3", seed=1005)]
     ws[1].t0_ns = 1_000_000_007
@@ -242,6 +258,7 @@ def _build_table(cv):
     sw = _spline_windows(cv)
     sm, srole = _slide_marg()
     c5m, c5role = _c5_marg()
+    cw, csel = _cov_windows(cv)
     W = _run_windows
     return {
         "ragged7": ({}, 1, lambda s: W(cv, s, r7, lin_ids=range(7)), None, ()),
@@ -262,6 +279,7 @@ def _build_table(cv):
         "marg_blocked": ({"CTVIO_MARG_BLOCKED": 1}, None, lambda s: _run_marg(cv, s, [sm] * 2, [srole] * 2), None, ()),
         "marg_c5_blocked": ({}, None, lambda s: _run_marg(cv, s, [c5m], [c5role], form=True), 1e-7, ()),
         "marg_host": ({"CTVIO_MARG_HOST": 1}, None, lambda s: _run_marg(cv, s, [sm], [srole], single=0), None, ()),
+        "covariance": ({}, 1, lambda s: _run_cov(cv, s, cw, csel), None, ()),
     }
 
 
@@ -280,7 +298,7 @@ def _run_case(cv, name, poison):
 
 CASES = ["ragged7", "ragged7_n200", "ragged7_chol0", "ragged7_chol1", "sizes26", "p301", "p301_tile2", "config5", "prior_merged_store",
          "prior_split_store", "prior_accumulate", "prior_accumulate_band", "imu_only_mixed", "queries", "marg_lds", "marg_blocked",
-         "marg_c5_blocked", "marg_host"]
+         "marg_c5_blocked", "marg_host", "covariance"]
 
 
 @pytest.mark.parametrize("pattern", [1, 2])
@@ -299,15 +317,19 @@ def test_poison_changes_nothing(cv, case, pattern):
 
 def test_history_does_not_matter(cv):
     """One handle, one sequence of batches that shrinks and grows both arenas and reallocates them; every step equals the same batch on a fresh
-    handle, and the three runs of the seven-window batch are bitwise equal to each other.  The batch of 241 windows is exactly the capacity
-    of the pinned result records after the 200-window batch (200 + 200 / 8 + 16): the records of all its windows come back intact, and the
-    arenas grow under it, so the cached hipGraph of the LM pass must be captured again, not replayed with stale pointers."""
+    handle, and the three runs of the seven-window batch are bitwise equal to each other.  The batch of 241 windows outgrows the pinned result
+    areas reserved under the 200-window batch (the head of the per-call arena: one record per window, the poll words in a segment of their
+    own, the batch state; an eighth of headroom): the records of all its windows come back intact, and the arenas grow under it, so the
+    cached hipGraph of the LM pass must be captured again, not replayed with stale pointers.  Every per-call entry lays its scratch out in
+    the same two arenas, so the covariance and the queries that follow the config-5 marginalisation run over its numbers in another layout."""
     r7 = _ragged7(cv)
     c2 = [cv.synth.make_window("config2", seed=1002 + i % 64) for i in range(241)]
     c5 = [cv.synth.make_window("config5", seed=1011)]
     tiny = [cv.synth.make_window("tiny", seed=7)]
     qw = _query_window(cv)
     c5m, c5role = _c5_marg()
+    cw, csel = _cov_windows(cv)
+    sw = _spline_windows(cv)
     tq = np.linspace(qw.t0_ns, qw.max_time_ns() - 1, 97).astype(np.int64)
 
     def query(s):
@@ -320,6 +342,8 @@ def test_history_does_not_matter(cv):
              ("ragged7", lambda s: _run_windows(cv, s, r7, lin_ids=range(7)), None),
              ("query", query, None),
              ("marg_c5", lambda s: _run_marg(cv, s, [c5m], [c5role], form=True), 1e-7),
+             ("covariance", lambda s: _run_cov(cv, s, cw, csel), None),
+             ("queries", lambda s: _run_queries(cv, s, sw), None),
              ("ragged7", lambda s: _run_windows(cv, s, r7, lin_ids=range(7)), None),
              ("c2x241", lambda s: _run_windows(cv, s, c2, lin_ids=(0, 200, 240), steps=False), 1e-7),
              ("ragged7", lambda s: _run_windows(cv, s, r7, lin_ids=range(7)), None)]
