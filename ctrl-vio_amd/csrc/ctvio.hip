@@ -125,8 +125,8 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_solve<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_tiles<16, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_flow, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, CHOL_LDS_LIMIT));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cholesky_flow, hipFuncAttributeMaxDynamicSharedMemorySize, CHOL_LDS_LIMIT));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_assemble_vis_mfma<VCH, true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -421,8 +421,7 @@ class SolverImpl {
     if (b.chol_tiles) {
       const int ntr = b.maxP / 16 + 1;
       p.chol = b.chol_tiles == 1 ? CHOL_TILES : CHOL_FLOW;   // (CTVIO_CHOL_TILES=1: round 5's kernel)
-      p.chol_lds = b.chol_tiles == 1 ? (size_t)(272 + 2 * ntr * 272 + 32 * ntr + 4 + 768) * sizeof(double)   // identity + panel + inverses + vectors + parked tiles
-                                     : (size_t)(272 + 5 * ntr * 272 + 32 * ntr + 48) * sizeof(double);      // identity + inverses + sub-diagonal tiles + three panels + vectors + flags
+      p.chol_lds = b.chol_tiles == 1 ? CholTilesLds(ntr).bytes : CholFlowLds(ntr).bytes;
     } else {
       p.chol = CHOL_PANEL;
     }
@@ -565,7 +564,7 @@ class SolverImpl {
     ph_end();
     ph_begin(PH_CHOL);
     switch (p.chol) {
-      case CHOL_TILES: hipLaunchKernelGGL((k_cholesky_tiles<16, 7>), dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
+      case CHOL_TILES: hipLaunchKernelGGL(k_cholesky_tiles, dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
       case CHOL_FLOW: hipLaunchKernelGGL(k_cholesky_flow, dim3(nw), dim3(1024), p.chol_lds, stream_, d); break;
       default: launch_chol_panel(d);
     }

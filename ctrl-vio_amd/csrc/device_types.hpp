@@ -4,6 +4,7 @@
 // recorded in WinMeta; kernels are launched over (element, window) grids and exit early for windows
 // whose LM loop has terminated (Lm::status != 0) -- the LM control flow never returns to the host.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace ctv {
@@ -178,5 +179,39 @@ struct Dev {
   const int32_t *vrow, *vrow_off;
   double *vexp;
 };
+
+// LDS of the two register-resident tile Cholesky kernels (kernels_solve.hpp) for ntr = P / 16 + 1 tile rows: the offset of every segment in
+// doubles, and the bytes a launch asks for.  A 16 x 16 block takes CHOL_TS doubles (row stride 17).  The spare doubles behind the last
+// segment are what every launch has asked for: the bytes decide how many workgroups share a CU.
+constexpr int CHOL_TS = 16 * 17;
+constexpr int CHOL_LDS_LIMIT = 160 * 1024;   // hipFuncAttributeMaxDynamicSharedMemorySize of both kernels: the LDS of a gfx950 CU
+struct CholTilesLds {                        // k_cholesky_tiles (a barrier per panel)
+  int Id, Li, Pn, tv, xs, flags, park;
+  size_t bytes;
+  constexpr explicit CholTilesLds(int ntr)
+      : Id(0),                        // [TS] a 16 x 16 identity: the diagonal tile's inverse lanes start from it
+        Li(Id + CHOL_TS),             // [ntr][TS] inverses of the diagonal blocks, Li[b][j * 17 + k] = Linv_b[j][k]
+        Pn(Li + ntr * CHOL_TS),       // [ntr][TS] panel: Pn[i][m * 17 + c] = L_ik[m][c] of the current panel
+        tv(Pn + ntr * CHOL_TS),       // [16 ntr] y, then the running right-hand side of the back-substitution
+        xs(tv + 16 * ntr),            // [16 ntr] solution
+        flags(xs + 16 * ntr),         // int[4]: the window's failure flag
+        park(flags + 2),              // [12][64] three tiles of the wave that factors a diagonal tile wait here meanwhile
+        bytes((size_t)(park + 12 * 64 + 2) * sizeof(double)) {}
+};
+struct CholFlowLds {                         // k_cholesky_flow (flags, three panel buffers)
+  static constexpr int NPB = 3, NFLAG = 80;  // panel buffers; ints of flags: fail, F_inv, F_row, F_park, done_E at 16 each
+  int Id, Li, Ls, Pn, tv, xs, flags;
+  size_t bytes;
+  constexpr explicit CholFlowLds(int ntr)
+      : Id(0),                            // [TS] the identity, as above
+        Li(Id + CHOL_TS),                 // [ntr][TS] diagonal blocks on their way to the chain wave, then their inverses: Li[b][j * 17 + k] = Linv_b[j][k]
+        Ls(Li + ntr * CHOL_TS),           // [ntr][TS] tile (b, b - 1) on its way to the chain wave, then L_(b,b-1) (row major) for the back-substitution
+        Pn(Ls + ntr * CHOL_TS),           // [NPB][ntr][TS] panels: Pn[c % NPB][i][m * 17 + cc] = L_ic[m][cc]
+        tv(Pn + NPB * ntr * CHOL_TS),     // [16 ntr] y, then the running right-hand side of the back-substitution
+        xs(tv + 16 * ntr),                // [16 ntr] solution
+        flags(xs + 16 * ntr),             // int[NFLAG]
+        bytes((size_t)(flags + NFLAG / 2 + 8) * sizeof(double)) {}
+};
+static_assert(CholTilesLds(14).bytes <= CHOL_LDS_LIMIT && CholFlowLds(14).bytes <= CHOL_LDS_LIMIT, "P = 223 (14 tile rows) must fit the LDS of a CU");
 
 }  // namespace ctv

@@ -16,7 +16,8 @@
 //                         packed Hessian is not LDS resident under deterministic = 2: k_vis_expand, k_assemble_wide, k_bias_rows_wide
 //   kernels_solve.hpp     k_begin_iter, k_schur_window_f64 (large batches) / k_schur_tile_f64, k_schur_tile2_f64 (small; all also produce the
 //                         reduced rhs), k_cholesky_flow (P <= 223: register-resident 16 x 16 tiles as a data-flow of waves; k_cholesky_tiles =
-//                         its barrier-per-panel form, kept as the timing-independent twin the tests compare it with; k_cholesky_solve =
+//                         its barrier-per-panel form, kept as the timing-independent twin the tests compare it with: it shares the tile steps
+//                         (chol_*) with the flow form and differs only in scheduling; k_cholesky_solve =
 //                         panel kernel for P > 223), k_step_finish (back-substitution, candidate x (+) alpha delta, its knot-pair table)
 //   kernels_query.hpp     k_gauge_restore (double2vector), k_residual_summary, k_spline_eval (trajectory queries)
 //   kernels_cov.hpp       k_cov_prepare, k_cov_solve, k_cov_gram (marginal covariances from the factor of the reduced system)

@@ -963,54 +963,204 @@ template <int K> __device__ __forceinline__ void dpp_dot16(double &acc, double t
 }
 __device__ __forceinline__ double f64x4_get(const f64x4 &a, int r) { return r == 0 ? a[0] : (r == 1 ? a[1] : (r == 2 ? a[2] : a[3])); }
 
+// ---- THE STEPS OF THE REGISTER-RESIDENT TILE CHOLESKY, written once for its two schedules: k_cholesky_flow (a data-flow of waves, the default) and
+// k_cholesky_tiles (a barrier per panel).  The kernels differ in who owns which tile and in how a step learns that its inputs are there; what a
+// step computes is here.  Lane (q4, l15) = (lane >> 4, lane & 15) holds rows q4 + 4 r, r = 0 .. 3, of column l15 of a tile (the accumulator layout
+// of v_mfma_f64_16x16x4_f64); a 16 x 16 block in LDS has row stride 17 (CHOL_TS doubles).
+constexpr int CHOL_NS = 7;   // tile slots per wave (105 tiles at P = 211)
+
+// activity of the unknowns as four 64-bit masks in SGPRs (each wave builds its own: four byte loads per lane, no LDS, no barrier)
+struct CholActive {
+  unsigned long long w[4];
+  __device__ __forceinline__ int bit(int i) const {   // (i < 256; lane-variant)
+    const unsigned long long wlo = (i & 128) ? w[2] : w[0], whi = (i & 128) ? w[3] : w[1];
+    return (int)((((i & 64) ? whi : wlo) >> (i & 63)) & 1ull);
+  }
+};
+// What a wave reads a window's tiles from: S -- or, with Dev::schur_plain_in_H, Hpp for the tiles without Schur products (SchurTiles) -- and the
+// rhs, which rides along as row P (tile row ip = P / 16, local row rp = P % 16).
+struct CholWindow {
+  const double *S, *Hc, *y, *dd;   // reduced system, Hpp of the current set, reduced rhs, damping: all at the window's offset
+  int P, ldh, K6;
+  bool from_h;
+  CholActive act;
+  __device__ __forceinline__ bool plain(int a, int b) const {   // (wave-uniform) tile (a, b) comes straight from Hpp
+    const SchurTiles tiles{K6, P};
+    return from_h && !(tiles.nz_row(a) && tiles.nz_col(b));
+  }
+};
+__device__ __forceinline__ CholWindow chol_window(const Dev &d, const WinMeta &m, const Lm &lm, int lane) {
+  CholWindow cw = {d.S + m.H0, d.HppS[lm.cur] + m.H0, d.rhs + m.p0, d.dd + m.u0, m.P, m.ldh, 6 * m.K, d.schur_plain_in_H != 0, {{0ull, 0ull, 0ull, 0ull}}};
+  if (cw.from_h) {
+    unsigned char ab[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ab[k] = d.active[m.u0 + min(lane + 64 * k, cw.P - 1)];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cw.act.w[k] = __ballot(lane + 64 * k < cw.P && ab[k] != 0);
+  }
+  return cw;
+}
+// SPARSITY: tile (i, c) of the factor is empty for c < env_tile[i] (host_pack.hpp: plan_sparsity; fill stays inside the row envelope), so
+// panel k neither solves nor updates with a tile whose row starts after it: the first panel either row of tile (a, b) takes part in.
+// (The tiles themselves are all resident -- the empty ones hold exact zeros -- so loads, layout and the back-substitution do not change.)
+__device__ __forceinline__ int chol_first_panel(const Dev &d, const WinMeta &m, int a, int b) {
+  return __builtin_amdgcn_readfirstlane(max(d.env_tile[m.tr0 + a], d.env_tile[m.tr0 + b]));
+}
+// tile (a, b): unconditional loads on clamped addresses straight into the tile registers; chol_tile_fixup completes it
+__device__ __forceinline__ void chol_tile_fetch(f64x4 &t, const CholWindow &cw, int a, int b, int q4, int l15) {
+  const double *S = cw.S, *Hc = cw.Hc;   // (copies: a select between the two MEMBERS is a select of their addresses, and the struct goes to scratch)
+  const double *src = cw.plain(a, b) ? Hc : S;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int rc = min(16 * a + q4 + 4 * r, cw.P - 1);
+    t[r] = src[(long long)rc * cw.ldh + min(16 * b + l15, rc)];
+  }
+}
+__device__ __forceinline__ void chol_tile_fixup(f64x4 &t, const CholWindow &cw, int a, int b, int q4, int l15) {
+  const int P = cw.P, ip = P / 16, col = 16 * b + l15;
+  if (cw.plain(a, b)) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
+    const int a_j = cw.act.bit(col);
+    double ddiag = 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window; one L2 round trip for its wave)
+    if (a == b) ddiag = cw.dd[min(col, P - 1)];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * a + q4 + 4 * r;
+      t[r] = (cw.act.bit(row) & a_j) ? t[r] + (row == col ? ddiag : 0.0) : (row == col ? 1.0 : 0.0);
+    }
+  }
+  if (a == b) {             // diagonal tile: the upper half is not stored in S
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[r] = (col <= 16 * a + q4 + 4 * r) ? t[r] : 0.0;
+  }
+  if (a == ip) {            // tile row of the rhs row P; identity beyond it
+    const double yv = cw.y[min(col, P - 1)];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * ip + q4 + 4 * r;
+      t[r] = row < P ? t[r] : (row == P ? (col < P ? yv : 0.0) : (row == col ? 1.0 : 0.0));
+    }
+  }
+}
+__device__ __forceinline__ void chol_tile_to_lds(double *blk, const f64x4 &t, int q4, int l15) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) blk[(q4 + 4 * r) * 17 + l15] = t[r];
+}
+// The diagonal tile (k, k), in Dg in LDS: factored by one wave, L_kk^-1 left in its place; returns whether a pivot was bad.
+__device__ __forceinline__ int chol_diag_tile(double *Dg, const double *Id, int k, int P, int ip, int rp, double *tv, int lane) {
+  const int l15 = lane & 15;
+  double v[16];
+  // without the opaque zero the 16 identity columns below are hoisted out of the panel loop as loop invariants and, for lack of registers,
+  // kept in scratch
+  const int opaque0 = opaque_zero();
+  // even rows of the wave: the tile's rows (whole rows: the factorisation never reads the upper half); odd rows: the identity, from LDS as
+  // well.  (With selects -- lane < 16 ? (c <= lane ? a : 0) : (c == lane) -- the compiler sank each of the 16 LDS reads into its own branch
+  // with its own s_waitcnt: 2.2 k clocks per tile for the load alone, tools/chol16_probe.hip.)
+  const double *src = ((lane & 16) ? Id : Dg) + (l15 + opaque0) * 17;
+#pragma unroll
+  for (int c = 0; c < 16; ++c) v[c] = src[c];
+  lds_wave_sync();   // every lane has read its row before the block is overwritten with the inverse
+  const int nreal = P - 16 * k;         // pivots below this are real; the rhs row and the padding rows are not factored
+  int bad = 0;
+  chol16_dpp(v, nreal, bad);
+  if (lane >= 16 && lane < 32) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) Dg[i * 17 + l15] = v[i];   // Linv[i][column l15]
+  }
+  if (k == ip && lane == rp) {          // the part of y inside the last diagonal tile: L[P][16 ip + c], c < rp
+#pragma unroll
+    for (int c = 0; c < 16; ++c) if (c < rp) tv[16 * ip + c] = v[c];
+  }
+  return bad;
+}
+// (The step between the two, L_ik = A_ik L_kk^-T, is NOT here: it stays written out in both kernels.  As a function -- tile by reference, by value
+//  and returned, the wave's tiles and a slot, the y row inside or at the call site -- k_cholesky_flow came out at 97 or 98 VGPRs instead of the 96
+//  that leave it five waves per SIMD; the scope a call puts around the step's temporaries is enough: a pair of braces around the written-out
+//  text does the same (tools/isa_diff.py and the .s metadata, twenty forms).)
+// trailing tile (i, j): A_ij -= L_ik L_jk^T, operands from the slices of rows i and j of the LDS panel
+__device__ __forceinline__ void chol_trailing(f64x4 &t, const double *Lik, const double *Ljk, int q4, int l15) {
+  const double *pa = Lik + l15 * 17 + q4, *pb = Ljk + l15 * 17 + q4;
+  double a[4], b[4];
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) { a[s4] = -pa[4 * s4]; b[s4] = pb[4 * s4]; }
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) t = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], t, 0, 0, 0);
+}
+// x of the last block bl, by one wave: x_b[j] = sum_k Linv[k][j] t[k]: lane (q4, j = l15) sums k = 4 q4 .. 4 q4 + 3
+__device__ __forceinline__ void chol_last_block_x(const double *Li, const double *tv, double *xs, int bl, int q4, int l15) {
+  const double *Lb = Li + bl * CHOL_TS;
+  double xa = 0.0;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) xa += Lb[(4 * q4 + kk) * 17 + l15] * tv[16 * bl + 4 * q4 + kk];
+  xa += __shfl_xor(xa, 16);
+  xa += __shfl_xor(xa, 32);
+  if (q4 == 0) xs[16 * bl + l15] = xa;
+}
+// ---- back-substitution L^T x = y over the tiles in registers, x of the last block known: ONE barrier per block.  After x_b is known, the only
+// contribution t_{b-1} still lacks is that of tile (b, b - 1): its owner finishes t_{b-1} in registers and forms x_{b-1} = L_{b-1,b-1}^-T t_{b-1} at
+// once (the sixteen t[k] read across the 16-lane rows by v_fmac_f64_dpp row_newbcast, the sum over the four row groups by v_permlane16/32_swap --
+// no LDS round trip on the chain); the owners of the other tiles (b, j) subtract their parts from t_j in LDS meanwhile.  Every tile has a single
+// owner -- no atomics anywhere, the summation order is fixed.  (x_b by one wave, barrier, the updates, barrier: 19.7 k of a factorisation's
+// 143 k cycles.)  Every wave of the workgroup that is still running calls this.
+__device__ __forceinline__ void chol_back_substitute(const f64x4 (&acc)[CHOL_NS], const int (&ti)[CHOL_NS], const int (&tj)[CHOL_NS], const double *Li,
+                                                     double *tv, double *xs, int NTR, int q4, int l15) {
+  for (int b = NTR - 1; b >= 1; --b) {
+#pragma unroll
+    for (int q = 0; q < CHOL_NS; ++q) {
+      if (ti[q] != b || tj[q] >= b) continue;   // tiles (b, j), j < b: t_j -= L_bj^T x_b
+      double xb[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xb[r] = xs[16 * b + q4 + 4 * r];
+      if (tj[q] == b - 1) {                     // (uniform) the chain
+        const double *Lb = Li + (b - 1) * CHOL_TS;
+        double lk[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk) lk[kk] = Lb[kk * 17 + l15];
+        const double tb = tv[16 * (b - 1) + l15];
+        double part = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
+        const double t = tb - rowgroup_sum(part);   // t_{b-1}[l15], in every row group
+        double xa = 0.0;
+        dpp_dot16<0>(xa, t, lk);
+        if (q4 == 0) xs[16 * (b - 1) + l15] = xa;
+      } else {
+        double part = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        if (q4 == 0) tv[16 * tj[q] + l15] -= part;
+      }
+    }
+    lds_block_sync();
+  }
+}
+
 // (History of the diagonal tile.  With v_readlane broadcasts -- chol16_from, kept in tools/chol16_probe.hip as the cross-check -- a BLOCKED
 //  variant (four blocks of four pivots, rank-4 updates as two v_mfma_f64_16x16x4) and a reciprocal-based pivot chain were built early in round 4
 //  and found no faster: 8.7 k / 9.0 k vs 8.3 k cycles per tile.  The explanation given then -- "300 dependent cycles per pivot" -- was wrong: a
 //  lone wave issues one fp64 instruction per ~5.3 clocks whether it depends on the previous one or not (tools/fp64_latency_probe.hip), the tile
 //  was 760 instructions, and 2.2 k of its clocks were the tile's LOAD, compiled into 16 branches with a ds_read and an s_waitcnt each.
 //  chol16_dpp + the branch-free load: 3.2 k clocks per tile.)
-template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_tiles(Dev d) {
-  constexpr int NT = 64 * NW, TS = 16 * 17;    // a 16 x 16 block in LDS: row stride 17
+constexpr int CHOL_NW = 16;   // waves of k_cholesky_tiles: tile t = i (i + 1) / 2 + j belongs to wave t % CHOL_NW, slot t / CHOL_NW
+__global__ __launch_bounds__(64 * CHOL_NW) void k_cholesky_tiles(Dev d) {
+  constexpr int NW = CHOL_NW, NS = CHOL_NS, NT = 64 * NW, TS = CHOL_TS;
   const int w = blockIdx.x;
   Lm &lm = d.lm[w];
   if (lm.status || lm.ls_active) return;
   const WinMeta &m = d.wins[w];
-  const int P = m.P, ldh = m.ldh, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int P = m.P, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int q4 = lane >> 4, l15 = lane & 15;
   const int NTR = P / 16 + 1, ntiles = NTR * (NTR + 1) / 2, ip = P / 16, rp = P % 16;   // the rhs row P sits in tile row ip, local row rp
   extern __shared__ __attribute__((aligned(16))) double smt[];
-  double *Id = smt;                    // [TS] a 16 x 16 identity: the diagonal tile's inverse lanes start from it
-  double *Li = Id + TS;                // [NTR][TS] inverses of the diagonal blocks, Li[b][j * 17 + k] = Linv_b[j][k]
-  double *Pn = Li + NTR * TS;          // [NTR][TS] panel: Pn[i][m * 17 + c] = L_ik[m][c] of the current panel
-  double *tv = Pn + NTR * TS;          // [16 NTR] y, then the running right-hand side of the back-substitution
-  double *xs = tv + 16 * NTR;          // [16 NTR] solution
-  int &s_fail = *reinterpret_cast<int *>(xs + 16 * NTR);
-  double *park = xs + 16 * NTR + 2;    // [12][64] three tiles of the wave that factors a diagonal tile wait here meanwhile (see step A)
-  const double *S = d.S + m.H0, *y = d.rhs + m.p0;
-  const double *Hc = d.HppS[lm.cur] + m.H0;
-  const bool from_h = d.schur_plain_in_H != 0;
-  const int K6 = 6 * m.K;
-  const SchurTiles tiles{K6, P};
+  const CholTilesLds lds(NTR);
+  double *Id = smt + lds.Id, *Li = smt + lds.Li, *Pn = smt + lds.Pn, *tv = smt + lds.tv, *xs = smt + lds.xs, *park = smt + lds.park;
+  int &s_fail = *reinterpret_cast<int *>(smt + lds.flags);
   if (tid == 0) s_fail = 0;
   for (int i = tid; i < 16 * NTR; i += NT) tv[i] = 0.0;
-  // activity of the unknowns as four 64-bit masks in SGPRs (each wave builds its own: four byte loads per lane, no LDS, no barrier)
-  unsigned long long amask[4] = {0ull, 0ull, 0ull, 0ull};
-  if (from_h) {
-    unsigned char ab[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ab[k] = d.active[m.u0 + min(lane + 64 * k, P - 1)];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) amask[k] = __ballot(lane + 64 * k < P && ab[k] != 0);
-  }
-  auto active_bit = [&](int i) {   // (i < 256; lane-variant)
-    const unsigned long long wlo = (i & 128) ? amask[2] : amask[0], whi = (i & 128) ? amask[3] : amask[1];
-    return (int)((((i & 64) ? whi : wlo) >> (i & 63)) & 1ull);
-  };
+  const CholWindow cw = chol_window(d, m, lm, lane);
   for (int i = tid; i < TS; i += NT) Id[i] = (i / 17 == i % 17) ? 1.0 : 0.0;
   // ---- this wave's tiles (SGPRs) and their contents
-  // SPARSITY: tile (i, c) of the factor is empty for c < env_tile[i] (host_pack.hpp: plan_sparsity; fill stays inside the row envelope), so
-  // panel k neither solves nor updates with a tile whose row starts after it: ek = the first panel either row of the tile takes part in.
-  // (The tiles themselves are all resident -- the empty ones hold exact zeros -- so loads, layout and the back-substitution do not change.)
   int ti[NS], tj[NS], ek[NS];
   f64x4 acc[NS];
 #pragma unroll
@@ -1020,43 +1170,12 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
     tile_decode(min(t, ntiles - 1), a, b);
     ti[q] = __builtin_amdgcn_readfirstlane(t < ntiles ? a : -1);
     tj[q] = __builtin_amdgcn_readfirstlane(t < ntiles ? b : 1 << 20);   // (never equal to a panel, never a trailing tile: ti < tj)
-    ek[q] = __builtin_amdgcn_readfirstlane(max(d.env_tile[m.tr0 + a], d.env_tile[m.tr0 + b]));
-    // unconditional loads on clamped addresses straight into the tile registers; fixed up below
-    const bool plain = from_h && !(tiles.nz_row(a) && tiles.nz_col(b));   // (wave-uniform)
-    const double *src = plain ? Hc : S;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rc = min(16 * a + q4 + 4 * r, P - 1);
-      acc[q][r] = src[(long long)rc * ldh + min(16 * b + l15, rc)];
-    }
+    ek[q] = chol_first_panel(d, m, a, b);
+    chol_tile_fetch(acc[q], cw, a, b, q4, l15);
   }
 #pragma unroll
-  for (int q = 0; q < NS; ++q) {
-    if (ti[q] < 0) continue;
-    const int col = 16 * tj[q] + l15;
-    if (from_h && !(tiles.nz_row(ti[q]) && tiles.nz_col(tj[q]))) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
-      const int a_j = active_bit(col);
-      double ddiag = 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window; one L2 round trip for its wave)
-      if (ti[q] == tj[q]) ddiag = d.dd[m.u0 + min(col, P - 1)];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * ti[q] + q4 + 4 * r;
-        acc[q][r] = (active_bit(row) & a_j) ? acc[q][r] + (row == col ? ddiag : 0.0) : (row == col ? 1.0 : 0.0);
-      }
-    }
-    if (ti[q] == tj[q]) {             // diagonal tile: the upper half is not stored in S
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[q][r] = (col <= 16 * ti[q] + q4 + 4 * r) ? acc[q][r] : 0.0;
-    }
-    if (ti[q] == ip) {                // tile row of the rhs row P; identity beyond it
-      const double yv = y[min(col, P - 1)];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * ip + q4 + 4 * r;
-        acc[q][r] = row < P ? acc[q][r] : (row == P ? (col < P ? yv : 0.0) : (row == col ? 1.0 : 0.0));
-      }
-    }
-  }
+  for (int q = 0; q < NS; ++q)
+    if (ti[q] >= 0) chol_tile_fixup(acc[q], cw, ti[q], tj[q], q4, l15);
   __syncthreads();
   long long *dbg = (d.dbg && w == 0) ? d.dbg : nullptr;   // CTVIO_DEBUG_STAMPS: clock64 of thread 0 at the phase boundaries
   int dbi = 0;
@@ -1072,44 +1191,16 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
       double *Dg = Li + k * TS;
 #pragma unroll
       for (int q = 0; q < NS; ++q)
-        if (q == sd) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) Dg[(q4 + 4 * r) * 17 + l15] = acc[q][r];
-        }
+        if (q == sd) chol_tile_to_lds(Dg, acc[q], q4, l15);
       // The tile's 16 columns, the multipliers and the pivot chain do not fit beside seven resident tiles in 128 registers: three tiles wait in
       // LDS meanwhile (left to the compiler they went to scratch: a dozen scratch round trips per panel on the critical path).
-      if constexpr (NS >= 3) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { park[(3 * r) * 64 + lane] = acc[0][r]; park[(3 * r + 1) * 64 + lane] = acc[1][r]; park[(3 * r + 2) * 64 + lane] = acc[2][r]; }
-      }
+      for (int r = 0; r < 4; ++r) { park[(3 * r) * 64 + lane] = acc[0][r]; park[(3 * r + 1) * 64 + lane] = acc[1][r]; park[(3 * r + 2) * 64 + lane] = acc[2][r]; }
       lds_wave_sync();
-      double v[16];
-      // without the opaque zero the 16 identity columns below are hoisted out of the panel loop as loop invariants and, for lack of registers,
-      // kept in scratch
-      const int opaque0 = opaque_zero();
-      // even rows of the wave: the tile's rows (whole rows: the factorisation never reads the upper half); odd rows: the identity, from LDS as
-      // well.  (With selects -- lane < 16 ? (c <= lane ? a : 0) : (c == lane) -- the compiler sank each of the 16 LDS reads into its own branch
-      // with its own s_waitcnt: 2.2 k clocks per tile for the load alone, tools/chol16_probe.hip.)
-      const double *src = ((lane & 16) ? Id : Dg) + (l15 + opaque0) * 17;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) v[c] = src[c];
-      lds_wave_sync();   // every lane has read its row before the block is overwritten with the inverse
-      const int nreal = P - 16 * k;         // pivots below this are real; the rhs row and the padding rows are not factored
-      int bad = 0;
-      chol16_dpp(v, nreal, bad);
-      if (lane >= 16 && lane < 32) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) Dg[i * 17 + l15] = v[i];   // Linv[i][column l15]
-      }
-      if (k == ip && lane == rp) {          // the part of y inside the last diagonal tile: L[P][16 ip + c], c < rp
-#pragma unroll
-        for (int c = 0; c < 16; ++c) if (c < rp) tv[16 * ip + c] = v[c];
-      }
+      const int bad = chol_diag_tile(Dg, Id, k, P, ip, rp, tv, lane);
       if (lane == 0 && bad) s_fail = 1;
-      if constexpr (NS >= 3) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { acc[0][r] = park[(3 * r) * 64 + lane]; acc[1][r] = park[(3 * r + 1) * 64 + lane]; acc[2][r] = park[(3 * r + 2) * 64 + lane]; }
-      }
+      for (int r = 0; r < 4; ++r) { acc[0][r] = park[(3 * r) * 64 + lane]; acc[1][r] = park[(3 * r + 1) * 64 + lane]; acc[2][r] = park[(3 * r + 2) * 64 + lane]; }
     }
     if (k < 4) CTV_STAMP(dbg, dbi, 30, tid == 0);
     lds_block_sync();
@@ -1142,12 +1233,7 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
 #pragma unroll
     for (int q = 0; q < NS; ++q) {
       if (ti[q] < 0 || tj[q] <= k || tj[q] >= (1 << 20) || k < ek[q]) continue;   // (uniform; L_ik or L_jk is empty)
-      const double *pa = Pnk + ti[q] * TS + l15 * 17 + q4, *pb = Pnk + tj[q] * TS + l15 * 17 + q4;
-      double a[4], b[4];
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) { a[s4] = -pa[4 * s4]; b[s4] = pb[4 * s4]; }
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], acc[q], 0, 0, 0);
+      chol_trailing(acc[q], Pnk + ti[q] * TS, Pnk + tj[q] * TS, q4, l15);
     }
     // (K-step outermost, so that consecutive MFMAs go to different tiles, was measured slower: 5.7 k cycles for the first panel's
     //  updates either way, and the diagonal tiles waited longer.  LOOK-AHEAD -- the owner of tile (k + 1, k + 1) updates that tile
@@ -1166,53 +1252,10 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
   CTV_STAMP(dbg, dbi, 30, tid == 0);
   __syncthreads();
   CTV_STAMP(dbg, dbi, 30, tid == 0);
-  // ---- back-substitution L^T x = y over the tiles in registers: ONE barrier per block.  After x_b is known, the only contribution t_{b-1}
-  // still lacks is that of tile (b, b - 1): its owner finishes t_{b-1} in registers and forms x_{b-1} = L_{b-1,b-1}^-T t_{b-1} at once (the sixteen
-  // t[k] read across the 16-lane rows by v_fmac_f64_dpp row_newbcast, the sum over the four row groups by v_permlane16/32_swap -- no LDS round
-  // trip on the chain); the owners of the other tiles (b, j) subtract their parts from t_j in LDS meanwhile.  (x_b by one wave, barrier, the
-  // updates, barrier: 19.7 k of a factorisation's 143 k cycles.)
-  if (wave == ((NTR - 1) % NW)) {   // x_b[j] = sum_k Linv[k][j] t[k] of the last block: lane (q4, j = l15) sums k = 4 q4 .. 4 q4 + 3
-    const int bl = NTR - 1;
-    const double *Lb = Li + bl * TS;
-    double xa = 0.0;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) xa += Lb[(4 * q4 + kk) * 17 + l15] * tv[16 * bl + 4 * q4 + kk];
-    xa += __shfl_xor(xa, 16);
-    xa += __shfl_xor(xa, 32);
-    if (q4 == 0) xs[16 * bl + l15] = xa;
-  }
+  // ---- back-substitution (chol_back_substitute): x of the last block by the wave that factored its diagonal tile
+  if (wave == ((NTR - 1) % NW)) chol_last_block_x(Li, tv, xs, NTR - 1, q4, l15);
   lds_block_sync();
-  for (int b = NTR - 1; b >= 1; --b) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-      if (ti[q] != b || tj[q] >= b) continue;   // tiles (b, j), j < b: t_j -= L_bj^T x_b
-      double xb[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xb[r] = xs[16 * b + q4 + 4 * r];
-      if (tj[q] == b - 1) {                     // (uniform) the chain
-        const double *Lb = Li + (b - 1) * TS;
-        double lk[16];
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) lk[kk] = Lb[kk * 17 + l15];
-        const double tb = tv[16 * (b - 1) + l15];
-        double part = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
-        const double t = tb - rowgroup_sum(part);   // t_{b-1}[l15], in every row group
-        double xa = 0.0;
-        dpp_dot16<0>(xa, t, lk);
-        if (q4 == 0) xs[16 * (b - 1) + l15] = xa;
-      } else {
-        double part = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
-        part += __shfl_xor(part, 16);
-        part += __shfl_xor(part, 32);
-        if (q4 == 0) tv[16 * tj[q] + l15] -= part;
-      }
-    }
-    lds_block_sync();
-  }
+  chol_back_substitute(acc, ti, tj, Li, tv, xs, NTR, q4, l15);
   CTV_STAMP(dbg, dbi, 30, tid == 0);
   double *x = d.delta + m.u0;
   for (int i = tid; i < P; i += NT) x[i] = xs[i];
@@ -1242,7 +1285,7 @@ template <int NW, int NS> __global__ __launch_bounds__(64 * NW) void k_cholesky_
 // chain overlapped (profiles/r06_chol_chain_experiment.txt): 69 - 71 us.
 // Also tried: the three tiles (r, r - 2), (r, r - 1), (r, r) of a row with ONE owner who applies panel r - 2 to the last two AHEAD of its other work
 // and parks them at once (the chain never waited in panels 1 - 3, and 5 - 6 k cycles in every later one: 84 us per factorisation).
-constexpr int CHOL_NU = 15, CHOL_NS = 7;   // update waves, tile slots per wave (105 tiles at P = 211)
+constexpr int CHOL_NU = 15;   // update waves of k_cholesky_flow (CHOL_NS tile slots each)
 struct CholMap { signed char ti[15][CHOL_NU][CHOL_NS], tj[15][CHOL_NU][CHOL_NS]; };   // [tile rows NTR][update wave][slot]: tile (ti, tj), -1 = empty slot
 constexpr CholMap make_chol_map() {
   CholMap mp{};
@@ -1294,7 +1337,7 @@ __device__ __forceinline__ void chol_count(int *f, int lane) {
 }
 
 __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
-  constexpr int NU = CHOL_NU, NS = CHOL_NS, NTU = 64 * NU, TS = 16 * 17, NPB = 3;    // update waves, tile slots per wave; a 16 x 16 block in LDS: row stride 17
+  constexpr int NU = CHOL_NU, NS = CHOL_NS, NTU = 64 * NU, TS = CHOL_TS, NPB = CholFlowLds::NPB;
   const int w = blockIdx.x;
   Lm &lm = d.lm[w];
   if (lm.status || lm.ls_active) return;
@@ -1302,17 +1345,13 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   const bool chain = wave == 0;
   const int uw = wave - 1;                      // update wave index 0 .. 14
   const WinMeta &m = d.wins[w];
-  const int P = m.P, ldh = m.ldh;
+  const int P = m.P;
   const int q4 = lane >> 4, l15 = lane & 15;
   const int NTR = P / 16 + 1, ip = P / 16, rp = P % 16;   // the rhs row P sits in tile row ip, local row rp
   extern __shared__ __attribute__((aligned(16))) double smt[];
-  double *Id = smt;                    // [TS] a 16 x 16 identity: the diagonal tile's inverse lanes start from it
-  double *Li = Id + TS;                // [NTR][TS] diagonal blocks on their way to the chain wave, then their inverses: Li[b][j * 17 + k] = Linv_b[j][k]
-  double *Ls = Li + NTR * TS;          // [NTR][TS] tile (b, b - 1) on its way to the chain wave, then L_(b,b-1) (row major) for the back-substitution
-  double *Pn = Ls + NTR * TS;          // [NPB][NTR][TS] panels: Pn[c % NPB][i][m * 17 + cc] = L_ic[m][cc]
-  double *tv = Pn + NPB * NTR * TS;      // [16 NTR] y, then the running right-hand side of the back-substitution
-  double *xs = tv + 16 * NTR;          // [16 NTR] solution
-  int *fl = reinterpret_cast<int *>(xs + 16 * NTR);
+  const CholFlowLds lds(NTR);
+  double *Id = smt + lds.Id, *Li = smt + lds.Li, *Ls = smt + lds.Ls, *Pn = smt + lds.Pn, *tv = smt + lds.tv, *xs = smt + lds.xs;
+  int *fl = reinterpret_cast<int *>(smt + lds.flags);
   int &s_fail = fl[0];
   volatile int *F_inv = fl + 16, *F_row = fl + 32;
   int *F_park = fl + 48, *done_E = fl + 64;
@@ -1320,7 +1359,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   if (chain) {
     // ================================================================ the chain wave
     int dbi = 0, fail = 0;
-    for (int i = lane; i < 80; i += 64) fl[i] = 0;
+    for (int i = lane; i < CholFlowLds::NFLAG; i += 64) fl[i] = 0;
     for (int i = lane; i < TS; i += 64) Id[i] = (i / 17 == i % 17) ? 1.0 : 0.0;
     for (int i = lane; i < 16 * NTR; i += 64) tv[i] = 0.0;
     lds_wave_sync();
@@ -1360,40 +1399,12 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         lds_wave_sync();
         if (k < 4) CTV_STAMP(dbg, dbi, 30, lane == 0);
       }
-      double v[16];
-      const int opaque0 = opaque_zero();   // (the 16 identity columns would be hoisted out of the panel loop otherwise)
-      // even rows of the wave: the tile's rows (whole rows: the factorisation never reads the upper half); odd rows: the identity, from LDS too
-      const double *src = ((lane & 16) ? Id : Dg) + (l15 + opaque0) * 17;
-#pragma unroll
-      for (int cc = 0; cc < 16; ++cc) v[cc] = src[cc];
-      lds_wave_sync();   // every lane has read its row before the block is overwritten with the inverse
-      const int nreal = P - 16 * k;             // pivots below this are real; the rhs row and the padding rows are not factored
-      int bad = 0;
-      chol16_dpp(v, nreal, bad);
-      if (lane >= 16 && lane < 32) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) Dg[i * 17 + l15] = v[i];   // Linv[i][column l15]
-      }
-      if (k == ip && lane == rp) {              // the part of y inside the last diagonal tile: L[P][16 ip + c], c < rp
-#pragma unroll
-        for (int cc = 0; cc < 16; ++cc) if (cc < rp) tv[16 * ip + cc] = v[cc];
-      }
-      if (bad) fail = 1;
+      if (chol_diag_tile(Dg, Id, k, P, ip, rp, tv, lane)) fail = 1;
       chol_post(F_inv + k, 1, lane);
       CTV_STAMP(dbg, dbi, 30, lane == 0);
     }
     if (lane == 0 && fail) s_fail = 1;
-    // back-substitution: x of the last block, x_b[j] = sum_k Linv[k][j] t[k]: lane (q4, j = l15) sums k = 4 q4 .. 4 q4 + 3
-    {
-      const int bl = NTR - 1;
-      const double *Lb = Li + bl * TS;
-      double xa = 0.0;
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) xa += Lb[(4 * q4 + kk) * 17 + l15] * tv[16 * bl + 4 * q4 + kk];
-      xa += __shfl_xor(xa, 16);
-      xa += __shfl_xor(xa, 32);
-      if (q4 == 0) xs[16 * bl + l15] = xa;
-    }
+    chol_last_block_x(Li, tv, xs, NTR - 1, q4, l15);   // the back-substitution starts here
     CTV_STAMP(dbg, dbi, 30, lane == 0);
     lds_block_sync();   // the factorisation is complete (the update waves arrive here when they are through)
     return;                                      // (the update waves finish the back-substitution among themselves)
@@ -1401,27 +1412,8 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   // ================================================================== update waves
   const int utid = 64 * uw + lane;
   int fail = 0;
-  const double *S = d.S + m.H0, *y = d.rhs + m.p0;
-  const double *Hc = d.HppS[lm.cur] + m.H0;
-  const bool from_h = d.schur_plain_in_H != 0;
-  const int K6 = 6 * m.K;
-  const SchurTiles tiles{K6, P};
-  // activity of the unknowns as four 64-bit masks in SGPRs (each wave builds its own: four byte loads per lane, no LDS, no barrier)
-  unsigned long long amask[4] = {0ull, 0ull, 0ull, 0ull};
-  if (from_h) {
-    unsigned char ab[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ab[k] = d.active[m.u0 + min(lane + 64 * k, P - 1)];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) amask[k] = __ballot(lane + 64 * k < P && ab[k] != 0);
-  }
-  auto active_bit = [&](int i) {   // (i < 256; lane-variant)
-    const unsigned long long wlo = (i & 128) ? amask[2] : amask[0], whi = (i & 128) ? amask[3] : amask[1];
-    return (int)((((i & 64) ? whi : wlo) >> (i & 63)) & 1ull);
-  };
-  // ---- this wave's tiles (SGPRs) and their contents.  SPARSITY: tile (i, c) of the factor is empty for c < env_tile[i] (host_pack.hpp:
-  // plan_sparsity; fill stays inside the row envelope), so panel k neither solves nor updates with a tile whose row starts after it: ek = the
-  // first panel either row of the tile takes part in.  (The tiles are all resident -- the empty ones hold exact zeros.)
+  const CholWindow cw = chol_window(d, m, lm, lane);
+  // ---- this wave's tiles (SGPRs) and their contents
   int ti[NS], tj[NS], ek[NS];
   f64x4 acc[NS];
 #pragma unroll
@@ -1430,47 +1422,14 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
     const int a = max(a0, 0), b = max(b0, 0);
     ti[q] = __builtin_amdgcn_readfirstlane(a0);
     tj[q] = __builtin_amdgcn_readfirstlane(a0 >= 0 ? b0 : 1 << 20);   // (never equal to a panel, never a trailing tile: ti < tj)
-    ek[q] = __builtin_amdgcn_readfirstlane(max(d.env_tile[m.tr0 + a], d.env_tile[m.tr0 + b]));
-    // unconditional loads on clamped addresses straight into the tile registers; fixed up below
-    const bool plain = from_h && !(tiles.nz_row(a) && tiles.nz_col(b));   // (wave-uniform)
-    const double *src = plain ? Hc : S;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rc = min(16 * a + q4 + 4 * r, P - 1);
-      acc[q][r] = src[(long long)rc * ldh + min(16 * b + l15, rc)];
-    }
+    ek[q] = chol_first_panel(d, m, a, b);
+    chol_tile_fetch(acc[q], cw, a, b, q4, l15);
   }
 #pragma unroll
   for (int q = 0; q < NS; ++q) {
     if (ti[q] < 0) continue;
-    const int col = 16 * tj[q] + l15;
-    if (from_h && !(tiles.nz_row(ti[q]) && tiles.nz_col(tj[q]))) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
-      const int a_j = active_bit(col);
-      double ddiag = 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window; one L2 round trip for its wave)
-      if (ti[q] == tj[q]) ddiag = d.dd[m.u0 + min(col, P - 1)];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * ti[q] + q4 + 4 * r;
-        acc[q][r] = (active_bit(row) & a_j) ? acc[q][r] + (row == col ? ddiag : 0.0) : (row == col ? 1.0 : 0.0);
-      }
-    }
-    if (ti[q] == tj[q]) {             // diagonal tile: the upper half is not stored in S
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[q][r] = (col <= 16 * ti[q] + q4 + 4 * r) ? acc[q][r] : 0.0;
-    }
-    if (ti[q] == ip) {                // tile row of the rhs row P; identity beyond it
-      const double yv = y[min(col, P - 1)];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * ip + q4 + 4 * r;
-        acc[q][r] = row < P ? acc[q][r] : (row == P ? (col < P ? yv : 0.0) : (row == col ? 1.0 : 0.0));
-      }
-    }
-    if (ti[q] == 0) {                 // tile (0, 0): to the chain wave as it is (row 1 follows in iteration 0 of the loop below)
-      double *dst = Li;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dst[(q4 + 4 * r) * 17 + l15] = acc[q][r];
-    }
+    chol_tile_fixup(acc[q], cw, ti[q], tj[q], q4, l15);
+    if (ti[q] == 0) chol_tile_to_lds(Li, acc[q], q4, l15);   // tile (0, 0): to the chain wave as it is (row 1 follows in iteration 0 of the loop below)
   }
   lds_block_sync();
   // Iteration c of an update wave: panel c - 1 applied to its NEAR trailing tiles (columns c and c + 1: the tiles whose L_ic the next panel needs, and
@@ -1492,17 +1451,10 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         if (c - 1 >= ek[q]) {
           if (!((seen >> ti[q]) & 1u)) { chol_wait(F_row + ti[q], c, fail); seen |= 1u << ti[q]; }
           if (!((seen >> tj[q]) & 1u)) { chol_wait(F_row + tj[q], c, fail); seen |= 1u << tj[q]; }
-          const double *pa = Pnp + ti[q] * TS + l15 * 17 + q4, *pb = Pnp + tj[q] * TS + l15 * 17 + q4;
-          double a[4], b[4];
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) { a[s4] = -pa[4 * s4]; b[s4] = pb[4 * s4]; }
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s4], b[s4], acc[q], 0, 0, 0);
+          chol_trailing(acc[q], Pnp + ti[q] * TS, Pnp + tj[q] * TS, q4, l15);
         }
         if (ti[q] == c + 1) {   // (uniform) tiles (c + 1, c) and (c + 1, c + 1): every update up to panel c - 1 is in; to the chain wave
-          double *dst = (tj[q] == c + 1 ? Li : Ls) + (c + 1) * TS;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dst[(q4 + 4 * r) * 17 + l15] = acc[q][r];
+          chol_tile_to_lds((tj[q] == c + 1 ? Li : Ls) + (c + 1) * TS, acc[q], q4, l15);
           chol_count(F_park + c + 1, lane);
         }
       }
@@ -1562,41 +1514,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[q][r] = src[(q4 + 4 * r) * 17 + l15];
   }
-  // ---- back-substitution L^T x = y over the tiles in registers: ONE barrier per block.  After x_b is known, the only contribution t_{b-1}
-  // still lacks is that of tile (b, b - 1): its owner finishes t_{b-1} in registers and forms x_{b-1} = L_{b-1,b-1}^-T t_{b-1} at once (the sixteen
-  // t[k] read across the 16-lane rows by v_fmac_f64_dpp row_newbcast, the sum over the four row groups by v_permlane16/32_swap -- no LDS round
-  // trip on the chain); the owners of the other tiles (b, j) subtract their parts from t_j in LDS meanwhile.
-  for (int b = NTR - 1; b >= 1; --b) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q) {
-      if (ti[q] != b || tj[q] >= b) continue;   // tiles (b, j), j < b: t_j -= L_bj^T x_b
-      double xb[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xb[r] = xs[16 * b + q4 + 4 * r];
-      if (tj[q] == b - 1) {                     // (uniform) the chain
-        const double *Lb = Li + (b - 1) * TS;
-        double lk[16];
-#pragma unroll
-        for (int kk = 0; kk < 16; ++kk) lk[kk] = Lb[kk * 17 + l15];
-        const double tb = tv[16 * (b - 1) + l15];
-        double part = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
-        const double t = tb - rowgroup_sum(part);   // t_{b-1}[l15], in every row group
-        double xa = 0.0;
-        dpp_dot16<0>(xa, t, lk);
-        if (q4 == 0) xs[16 * (b - 1) + l15] = xa;
-      } else {
-        double part = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
-        part += __shfl_xor(part, 16);
-        part += __shfl_xor(part, 32);
-        if (q4 == 0) tv[16 * tj[q] + l15] -= part;
-      }
-    }
-    lds_block_sync();
-  }
+  chol_back_substitute(acc, ti, tj, Li, tv, xs, NTR, q4, l15);
   double *x = d.delta + m.u0;
   for (int i = utid; i < P; i += NTU) x[i] = xs[i];
   if (utid == 0) lm.chol_fail = s_fail;

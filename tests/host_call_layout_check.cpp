@@ -143,6 +143,25 @@ int cl_layout(int c, int which, int cap, const char **name, uint64_t *off, uint6
 }
 int cl_refusals(int c, int which) { return refusals(g_cases[(size_t)c], which); }
 int cl_fill_and_read(int c, int which) { return fill_and_read(g_cases[(size_t)c], which); }
+// the LDS of the tile Cholesky kernels for ntr tile rows (device_types.hpp: CholTilesLds, flow = 0; CholFlowLds, flow = 1): every segment's
+// name, offset and the extent the kernel uses, in bytes; *total = the bytes a launch asks for
+int cl_chol_lds(int flow, int ntr, const char **name, uint64_t *off, uint64_t *bytes, uint64_t *total) {
+  const uint64_t ts = ctv::CHOL_TS, n = (uint64_t)ntr;
+  int ns = 0;
+  auto seg = [&](const char *nm, int off_d, uint64_t doubles) { name[ns] = nm; off[ns] = (uint64_t)off_d * D; bytes[ns] = doubles * D; ++ns; };
+  if (flow) {
+    const ctv::CholFlowLds l(ntr);
+    seg("Id", l.Id, ts); seg("Li", l.Li, n * ts); seg("Ls", l.Ls, n * ts); seg("Pn", l.Pn, ctv::CholFlowLds::NPB * n * ts);
+    seg("tv", l.tv, 16 * n); seg("xs", l.xs, 16 * n); seg("flags", l.flags, ctv::CholFlowLds::NFLAG / 2);
+    *total = l.bytes;
+  } else {
+    const ctv::CholTilesLds l(ntr);
+    seg("Id", l.Id, ts); seg("Li", l.Li, n * ts); seg("Pn", l.Pn, n * ts); seg("tv", l.tv, 16 * n); seg("xs", l.xs, 16 * n);
+    seg("flags", l.flags, 1); seg("park", l.park, 12 * 64);
+    *total = l.bytes;
+  }
+  return ns;
+}
 }
 
 #ifdef CALL_LAYOUT_MAIN

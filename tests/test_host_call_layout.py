@@ -2,6 +2,7 @@
 (tests/host_call_layout_check.cpp).  Every entry of ctvio.hip names the segments of its scratch once and gets aligned offsets, a total and,
 after the one reservation of the call, typed pointers.  The cases are the entries' segment lists at the smallest interesting sizes and the
 degenerate ones (no queries, no selection with var_rho, nothing marginalised, a batch with no blocked window, a batch of only blocked ones).
+The shim also reads out the LDS layouts of the two tile Cholesky kernels (csrc/device_types.hpp: CholTilesLds, CholFlowLds).
 The same file is also built as a stand-alone program under AddressSanitizer + UBSan, which fills every segment of every case through its
 pointer over buffers of exactly the reserved sizes."""
 import ctypes as C
@@ -32,6 +33,7 @@ def cl():
     lib = C.CDLL(_build(os.path.join(HERE, "_build", "libhostcalllayout.so"), ["-fPIC", "-shared"]))
     lib.cl_case_name.restype = C.c_char_p
     lib.cl_layout.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.cl_chol_lds.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4
     return lib
 
 
@@ -92,6 +94,29 @@ def test_degenerate_cases_cost_what_they_should(cl):
     assert m[7][1] == m[8][1] == m[9][1] == m[10][1]
     b = layout(cl, NAMES.index("marg_only_blocked"), 1)
     assert [s[0] for s in b[0]] == ["mb", "rank"] and b[0][0][2] == layout(cl, NAMES.index("mb_window_268_553"), 1)[1]
+
+
+@pytest.mark.parametrize("flow", [0, 1], ids=["barrier", "flow"])
+@pytest.mark.parametrize("ntr", range(1, 15))
+def test_tile_cholesky_lds_layout(cl, flow, ntr):
+    """device_types.hpp: CholTilesLds / CholFlowLds, the LDS of k_cholesky_tiles / k_cholesky_flow for every tile-row count a window with
+    P <= 223 can have.  The launch bytes are the values the launch plan computed before the layout was stated (they decide how many
+    workgroups share a CU, so they must not move)."""
+    name = (C.c_char_p * 8)(); off = np.zeros(8, np.uint64); nb = np.zeros(8, np.uint64); tot = np.zeros(1, np.uint64)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    n = cl.cl_chol_lds(flow, ntr, C.cast(name, C.c_void_p), p(off), p(nb), p(tot))
+    segs = [(name[i].decode(), int(off[i]), int(nb[i])) for i in range(n)]
+    assert [s[0] for s in segs] == (["Id", "Li", "Ls", "Pn", "tv", "xs", "flags"] if flow else ["Id", "Li", "Pn", "tv", "xs", "flags", "park"])
+    end = 0
+    for nm, o, b in segs:
+        assert o >= end and b > 0, nm                # in order, disjoint
+        end = o + b
+    assert end <= int(tot[0])
+    assert all(o % 8 == 0 for nm, o, _ in segs if nm in ("flags", "park"))
+    recorded = (272 + 5 * ntr * 272 + 32 * ntr + 48) * 8 if flow else (272 + 2 * ntr * 272 + 32 * ntr + 4 + 768) * 8
+    assert int(tot[0]) == recorded
+    if ntr == 14:
+        assert int(tot[0]) <= 160 * 1024
 
 
 def test_stand_alone_program_under_sanitizers(tmp_path):

@@ -2,11 +2,13 @@
 """Per-kernel comparison of two device assembly files (the `*-gfx950.s` that `hipcc -save-temps` leaves):
     isa_diff.py <parent.s> <branch.s>
 A kernel runs from its `_Z...:` label to its `.Lfunc_end`; comment text after `;`, empty lines and the `.loc` / `.file` /
-`.cfi` / `.p2align` lines are dropped, the remaining lines are compared.  Exit status 1 if any kernel differs."""
+`.cfi` / `.p2align` lines are dropped, and the function's index in its local labels (`.LBB34_10`: it shifts when a kernel elsewhere in the file
+changes its name or place) is taken out; the remaining lines are compared.  Exit status 1 if any kernel differs."""
 import re
 import sys
 
 DROP = re.compile(r"\s*\.(loc|file|cfi\w*|p2align)\b")
+LABEL = re.compile(r"\.L([A-Za-z]+)\d+_")
 
 
 def kernels(path):
@@ -24,7 +26,7 @@ def kernels(path):
         if line.startswith(".Lfunc_end"):
             name = None
             continue
-        line = line.split(";", 1)[0].strip()
+        line = LABEL.sub(r".L\1_", line.split(";", 1)[0].strip())
         if line and not DROP.match(line):
             out[name].append(line)
     return out
