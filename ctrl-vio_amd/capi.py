@@ -74,13 +74,18 @@ class Summary(C.Structure):
                     num_line_search_steps=self.num_line_search_steps, num_line_search_reduced=self.num_line_search_reduced)
 
 
+class TriangulateOptions(C.Structure):
+    _fields_ = [("row_times", C.c_int32), ("only_unset", C.c_int32), ("apply", C.c_int32), ("min_depth", C.c_double), ("init_depth", C.c_double)]
+
+
 # every symbol include/ctvio.h declares (tests check the .so exports all of them)
 SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "ctvio_device_count", "ctvio_create",
            "ctvio_destroy", "ctvio_clear", "ctvio_add_window", "ctvio_upload", "ctvio_set_batch", "ctvio_num_windows", "ctvio_solve",
            "ctvio_get_state", "ctvio_get_batch_state", "ctvio_set_state", "ctvio_snapshot_state", "ctvio_restore_state", "ctvio_linearize", "ctvio_cost", "ctvio_lm_step", "ctvio_spline_eval", "ctvio_sensor_pose", "ctvio_gauge_restore", "ctvio_marginalize", "ctvio_marginalize_batch", "ctvio_residual_summary",
            "ctvio_last_timing", "ctvio_set_profiling", "ctvio_stream", "ctvio_solve_sharded", "ctvio_sharded_release", "ctvio_shard_of",
            "ctvio_shard_count", "ctvio_shards_used", "ctvio_spline_eval_batch", "ctvio_graph_captures", "ctvio_marginalize_ran_on_host",
-           "ctvio_covariance_batch", "ctvio_covariance"]
+           "ctvio_covariance_batch", "ctvio_covariance",
+           "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
 _lib = None
 
@@ -126,6 +131,11 @@ def load_library():
         lib.ctvio_spline_eval_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 7
         lib.ctvio_covariance_batch.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         lib.ctvio_covariance.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
+        lib.ctvio_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
+        lib.ctvio_default_triangulate_options.restype = None
+        lib.ctvio_triangulate_batch.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p]
+        lib.ctvio_triangulate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p]
+        lib.ctvio_shift_anchor_batch.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.c_int64] + [C.c_void_p] * 6
         _lib = lib
     return _lib
 

@@ -1351,6 +1351,76 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // ---------------------------------------------------------------------------------------- landmark depths
+  // ctvio_triangulate_batch / ctvio_triangulate (single: window `only` alone) and ctvio_shift_anchor_batch: one kernel each
+  // (csrc/kernels_tri.hpp) on the current state.  dev_, plan_ and the captured graph are not touched.
+  static TriOpts tri_opts(const ctvio_triangulate_options &o) {
+    return TriOpts{o.row_times != 0, o.only_unset != 0, o.apply != 0, 0, o.min_depth, o.init_depth};
+  }
+  int tri_timing() {   // (the stream is idle) ms[0]: the kernel between the query events, ms[7]: the whole call
+    Timing t;
+    t.clear();
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
+    t.ms[0] = ms; t.n[0] = 1;
+    return publish_timing(t, 0);
+  }
+  int triangulate(bool single, int only, const ctvio_triangulate_options *o, double *depth, int32_t *flag) {
+    if (const int rc = single ? guard(only) : guard()) return rc;
+    if (!o) return fail(CTVIO_ERR_INVALID, "null options");
+    const int l0 = single ? meta_[only].lm0 : 0, n = single ? meta_[only].L : dev_.Ltot;
+    CallLayout io = head_;
+    const int s_dep = io.add("depth", sizeof(double), (size_t)n, true), s_flag = io.add("flag", sizeof(int32_t), (size_t)n, false);
+    if (const int rc = reserve_call(io)) return rc;
+    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+    HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+    if (n) hipLaunchKernelGGL(k_triangulate, dim3(nblk(n, 4)), dim3(256), 0, stream_, dev_, l0, n, tri_opts(*o), io_dev<double>(io, s_dep), io_dev<int32_t>(io, s_flag));
+    HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+    if (n) HIPCHK(hipMemcpyAsync(io_host<char>(io, s_dep), io_dev<char>(io, s_dep), io.bytes() - io.off(s_dep), hipMemcpyDeviceToHost, stream_));   // (depth | flag)
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    if (const int rc = sync_call()) return rc;
+    if (const int rc = tri_timing()) return rc;
+    if (depth && n) std::memcpy(depth, io_host<double>(io, s_dep), sizeof(double) * (size_t)n);
+    if (flag && n) std::memcpy(flag, io_host<int32_t>(io, s_flag), sizeof(int32_t) * (size_t)n);
+    return CTVIO_OK;
+  }
+  int shift_anchor(const ctvio_triangulate_options *o, int64_t n64, const int32_t *win, const int32_t *lm, const int64_t *t_new, const int32_t *row_new,
+                   double *depth_new, int32_t *flag) {
+    if (const int rc = guard()) return rc;
+    if (!o) return fail(CTVIO_ERR_INVALID, "null options");
+    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!win || !lm || !t_new))) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (!row_new && o->row_times) return fail(CTVIO_ERR_INVALID, "row_new may be null only with row_times = 0");
+    const int n = (int)n64;
+    const size_t nn = (size_t)n;
+    for (int i = 0; i < n; ++i) {
+      if (win[i] < 0 || win[i] >= dev_.nwin) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+      if (lm[i] < 0 || lm[i] >= meta_[win[i]].L) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": landmark index out of range");
+    }
+    if (n == 0) return CTVIO_OK;
+    // in: relative times | windows, landmarks, rows (one staged copy); out: depth | flag (one copy)
+    CallLayout io = head_;
+    const int s_rel = io.add("t_rel", sizeof(long long), nn, false), s_q = io.add("win_lm_row", sizeof(int32_t), 3 * nn, false),
+              s_dep = io.add("depth_new", sizeof(double), nn, true), s_flag = io.add("flag", sizeof(int32_t), nn, false);
+    if (const int rc = reserve_call(io)) return rc;
+    long long *rel = io_host<long long>(io, s_rel);
+    int32_t *hq = io_host<int32_t>(io, s_q), *dq = io_dev<int32_t>(io, s_q);
+    for (int i = 0; i < n; ++i) rel[i] = (long long)(t_new[i] - t0_[win[i]]);
+    std::memcpy(hq, win, sizeof(int32_t) * nn); std::memcpy(hq + nn, lm, sizeof(int32_t) * nn);
+    if (row_new) std::memcpy(hq + 2 * nn, row_new, sizeof(int32_t) * nn); else std::memset(hq + 2 * nn, 0, sizeof(int32_t) * nn);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_rel), rel, io.off(s_dep) - io.off(s_rel), hipMemcpyHostToDevice, stream_));
+    HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+    hipLaunchKernelGGL(k_shift_anchor, dim3(nblk(n, 256)), dim3(256), 0, stream_, dev_, n, dq, dq + nn, io_dev<long long>(io, s_rel), dq + 2 * nn, tri_opts(*o),
+                       io_dev<double>(io, s_dep), io_dev<int32_t>(io, s_flag));
+    HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_dep), io_dev<char>(io, s_dep), io.bytes() - io.off(s_dep), hipMemcpyDeviceToHost, stream_));   // (depth | flag)
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    if (const int rc = sync_call()) return rc;
+    if (const int rc = tri_timing()) return rc;
+    if (depth_new) std::memcpy(depth_new, io_host<double>(io, s_dep), sizeof(double) * nn);
+    if (flag) std::memcpy(flag, io_host<int32_t>(io, s_flag), sizeof(int32_t) * nn);
+    return CTVIO_OK;
+  }
   int last_timing(double *ms8, int32_t *n8) {
     if (ms8) std::copy(timing_.ms, timing_.ms + 8, ms8);
     if (n8) std::copy(timing_.n, timing_.n + 8, n8);
@@ -1365,7 +1435,7 @@ class SolverImpl {
   hipStream_t stream_ = nullptr;
   hipEvent_t ev_[EV_COUNT] = {};
   bool uploaded_ = false, profiling_ = false, profiling_requested_ = false;
-  Timing timing_{};          // what ctvio_last_timing reports: the last solve or covariance call
+  Timing timing_{};          // what ctvio_last_timing reports: the last solve, covariance, triangulation or anchor-shift call
   std::vector<hipEvent_t> pev_;
   std::vector<int> pev_phase_;
   size_t pev_used_ = 0;
@@ -1486,6 +1556,22 @@ int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.covariance(id, &n_sel, sel, cov, var_rho, singular);
+}
+void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
+  if (!o) return;
+  o->row_times = 1; o->only_unset = 1; o->apply = 1;
+  o->min_depth = 0.1;    // feature_manager.cpp:218
+  o->init_depth = 5.0;   // parameters.cpp:44 INIT_DEPTH
+}
+int32_t ctvio_triangulate_batch(ctvio_solver *s, const ctvio_triangulate_options *o, double *depth, int32_t *flag) {
+  CHK_S; return s->impl.triangulate(false, 0, o, depth, flag);
+}
+int32_t ctvio_triangulate(ctvio_solver *s, int32_t id, const ctvio_triangulate_options *o, double *depth, int32_t *flag) {
+  CHK_S; return s->impl.triangulate(true, id, o, depth, flag);
+}
+int32_t ctvio_shift_anchor_batch(ctvio_solver *s, const ctvio_triangulate_options *o, int64_t n, const int32_t *win, const int32_t *lm,
+                                 const int64_t *t_new, const int32_t *row_new, double *depth_new, int32_t *flag) {
+  CHK_S; return s->impl.shift_anchor(o, n, win, lm, t_new, row_new, depth_new, flag);
 }
 int32_t ctvio_residual_summary(ctvio_solver *s, int32_t id, double *sums, int32_t *counts4) { CHK_S; return s->impl.residual_summary(id, sums, counts4); }
 int32_t ctvio_marginalize_batch(ctvio_solver *s, const int8_t *role, double eps, int32_t *n_keep, int32_t *kept, double *J0, double *r0) {

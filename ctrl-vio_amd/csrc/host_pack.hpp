@@ -123,6 +123,7 @@ struct PackTmp {
   std::vector<int32_t> vord;            // visual blocks: order by (ti, tj, rowi, rowj)  (frame-pair order: the assembly's items)
   std::vector<int32_t> lord, vpos;      // landmark-major slots: lord[slot] = block or -1 (padding), vpos[block] = slot
   std::vector<int32_t> anc_of, anc_rep; // anchors (distinct i ends), numbered landmark-major: anchor of every block / a block that carries it
+  std::vector<int32_t> lm_slot, lm_cnt; // per landmark: its first slot (window-relative) and its block count
   int32_t ngrp = 0, nvitem = 0, Vp = 0; // Vp: slots incl. padding, a multiple of 64
   int32_t A = 0;                        // number of anchors
   // sparsity plan (plan_sparsity): rows of W in sorted landmark order, their knot spans, per-tile row ranges, envelope of the reduced system
@@ -253,10 +254,12 @@ inline void plan_window(const ctvio_window *w, int vch, PackTmp &t) {
   t.A = (int)rep.size();
   t.anc_rep.resize((size_t)t.A);
   std::vector<int32_t> newid((size_t)t.A), astart((size_t)t.A);
+  t.lm_slot.resize((size_t)L); t.lm_cnt.resize((size_t)L);
   int pos = 0, na = 0;
   for (int l = 0; l < L; ++l) {
     const int c = lcount[l];
     if ((pos & 63) + c > 64) pos = (pos + 63) & ~63;
+    t.lm_slot[l] = pos; t.lm_cnt[l] = c;
     for (int a = first[l]; a >= 0; a = next[a]) {
       newid[a] = na; t.anc_rep[na] = rep[a]; astart[na] = pos;
       pos += acount[a];
@@ -517,6 +520,7 @@ class CallLayout {
   X(int32_t, pinv, pinv, Pp0, Pp0) X(int32_t, bgl_off, bgl_off, F0 + nw, F0 + nw) X(int32_t, bgl, bgl, std::max<size_t>(G0, 1), G0) \
   X(uint8_t, active, active, U0, U0)                                                                   \
   X(int32_t, lm_pos, lm_pos, L0, L0) X(int32_t, lm_at, lm_at, L0, L0) X(int32_t, lm_klo, lm_klo, L0, L0) X(int32_t, lm_khi, lm_khi, L0, L0) \
+  X(int32_t, lm_vfirst, lm_vfirst, L0, L0) X(int32_t, lm_vcnt, lm_vcnt, L0, L0)                        \
   X(int32_t, tl_beg, tl_beg, TR0, TR0) X(int32_t, tl_end, tl_end, TR0, TR0) X(int32_t, env_first, env_first, TR0, TR0) X(int32_t, env_tile, env_tile, TR0, TR0) \
   /* the walk of the order-fixed wide-window assembly (deterministic = 2 with a window beyond the LDS-resident Hessian; else not uploaded) */ \
   X(int32_t, vrow, vrow, walk ? Vt : 1, walk ? V0 : 0) X(int32_t, vrow_off, vrow_off, walk ? L0 + nw : 1, walk ? L0 + nw : 0)
@@ -644,6 +648,7 @@ inline void fill_window(const ctvio_window &w, int wi, const WinMeta &m, const P
   if (w.L) {   // sparsity plan: rows of W in sorted landmark order and their knot spans
     std::memcpy(h.lm_pos + m.lm0, t.lm_pos.data(), 4 * (size_t)w.L); std::memcpy(h.lm_at + m.lm0, t.lm_at.data(), 4 * (size_t)w.L);
     std::memcpy(h.lm_klo + m.lm0, t.row_klo.data(), 4 * (size_t)w.L); std::memcpy(h.lm_khi + m.lm0, t.row_khi.data(), 4 * (size_t)w.L);
+    for (int l = 0; l < w.L; ++l) { h.lm_vfirst[m.lm0 + l] = m.vis0 + t.lm_slot[l]; h.lm_vcnt[m.lm0 + l] = t.lm_cnt[l]; }
   }
   std::memcpy(h.tl_beg + m.tr0, t.tl_beg.data(), 4 * (size_t)m.ntr); std::memcpy(h.tl_end + m.tr0, t.tl_end.data(), 4 * (size_t)m.ntr);
   std::memcpy(h.env_first + m.tr0, t.env_first.data(), 4 * (size_t)m.ntr); std::memcpy(h.env_tile + m.tr0, t.env_tile.data(), 4 * (size_t)m.ntr);

@@ -267,6 +267,50 @@ class Solver:
         capi.check(self._lib.ctvio_covariance(self._h, int(wid), n, capi._p(sel), capi._p(cov), capi._p(var) if rho else None, capi._p(sing)))
         return cov[:n * n].reshape(n, n).copy(), (var[:L].copy() if rho else None), int(sing[0])
 
+    def _tri_options(self, opts):
+        o = capi.TriangulateOptions()
+        self._lib.ctvio_default_triangulate_options(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("row_times", "only_unset", "apply", "min_depth", "init_depth"):
+                raise TypeError(f"unknown triangulation option {k}")
+            setattr(o, k, float(v) if k.endswith("depth") else int(v))
+        return o
+
+    def triangulate_batch(self, **opts):
+        """ctvio_triangulate_batch: landmark depths of every window at the current device state (options: the fields of
+        ctvio_triangulate_options; defaults row_times=1, only_unset=1, apply=1, min_depth=0.1, init_depth=5.0).  Returns (list of depth
+        arrays, list of flag arrays), one per window, in the caller's landmark order."""
+        o = self._tri_options(opts)
+        Ls = [w.L for w in self.windows]
+        depth = np.zeros(max(sum(Ls), 1)); flag = np.zeros(max(sum(Ls), 1), np.int32)
+        capi.check(self._lib.ctvio_triangulate_batch(self._h, C.byref(o), capi._p(depth), capi._p(flag)))
+        cut = np.cumsum([0] + Ls)
+        return [depth[a:b].copy() for a, b in zip(cut[:-1], cut[1:])], [flag[a:b].copy() for a, b in zip(cut[:-1], cut[1:])]
+
+    def triangulate(self, wid: int, **opts):
+        """ctvio_triangulate: the same for window wid alone (same bits as the batch entry).  Returns (depth (L,), flag (L,))."""
+        o = self._tri_options(opts)
+        L = self.windows[wid].L
+        depth = np.zeros(max(L, 1)); flag = np.zeros(max(L, 1), np.int32)
+        capi.check(self._lib.ctvio_triangulate(self._h, int(wid), C.byref(o), capi._p(depth), capi._p(flag)))
+        return depth[:L].copy(), flag[:L].copy()
+
+    def shift_anchor(self, win, lm, t_new, row_new=None, **opts):
+        """ctvio_shift_anchor_batch: the depth of landmark lm[i] of window win[i] in the frame of a new anchor observation at absolute time
+        t_new[i], row row_new[i] (None: frame times, row_times=0).  Returns (depth_new (n,), flag (n,)); the state is not modified."""
+        if row_new is None:
+            opts.setdefault("row_times", 0)
+        o = self._tri_options(opts)
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1); li = np.ascontiguousarray(lm, np.int32).reshape(-1)
+        t = np.ascontiguousarray(t_new, np.int64).reshape(-1)
+        r = np.ascontiguousarray(row_new, np.int32).reshape(-1) if row_new is not None else None
+        n = int(wi.shape[0])
+        assert li.shape[0] == n and t.shape[0] == n and (r is None or r.shape[0] == n)
+        depth = np.zeros(max(n, 1)); flag = np.zeros(max(n, 1), np.int32)
+        capi.check(self._lib.ctvio_shift_anchor_batch(self._h, C.byref(o), C.c_int64(n), capi._p(wi), capi._p(li), capi._p(t),
+                                                      capi._p(r) if r is not None else None, capi._p(depth), capi._p(flag)))
+        return depth[:n].copy(), flag[:n].copy()
+
     def gauge_restore(self, wids, knots, q0, t0):
         """4-DoF gauge restore (reference double2vector): windows `wids`, reference knot index per window, its pre-solve
         quaternion (n,4) (x,y,z,w) and position (n,3).  Acts on the device state; read it back with get_state."""

@@ -214,6 +214,45 @@ int32_t ctvio_lm_step(ctvio_solver *s, int32_t id, double mu, double *delta, dou
 int32_t ctvio_covariance_batch(ctvio_solver *s, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
 int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
 
+/* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
+ * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
+ * a slide (feature_manager.cpp:341-381, visual_odometry.cpp:299-308). */
+typedef struct ctvio_triangulate_options {
+  int32_t row_times;   /* 1 (default): every observation at t + row * line delay of the CURRENT state, the time computed exactly as the factors
+                          compute it (truncated integer-ns line delay) -- the reference's triangulateRS (feature_manager.cpp:276-339, `#if 0`
+                          there: per-row poses are expensive on the host); 0: at its frame time t -- the reference's live triangulate(Ps, Rs) */
+  int32_t only_unset;  /* 1 (default): only landmarks whose current rho <= 0 (reference: `if (estimated_depth > 0) continue`); 0: every landmark */
+  int32_t apply;       /* 1 (default): rho = 1 / depth is written into the device state for every landmark flagged 1 or 2 (triangulation only) */
+  double min_depth;    /* 0.1 (feature_manager.cpp:218) */
+  double init_depth;   /* 5.0 (parameters.cpp:44 INIT_DEPTH) */
+} ctvio_triangulate_options;
+void ctvio_default_triangulate_options(ctvio_triangulate_options *o);
+/* Triangulation of every landmark of the batch / of window id.  Observation 0 of a landmark is the anchor (t_i, row_i, p_i) of its visual
+ * blocks, observations 1..n the (t_j, row_j, p_j) of the blocks (n <= 64).  Camera pose of an observation: the spline pose times (q_CI, p_CI)
+ * (Trajectory::GetSensorPose); relative to the anchor camera R = R0^T Rk, t = R0^T (tk - t0), P = [R^T | -R^T t], f = (x, y, 1) / |.|; every
+ * observation, the anchor included, gives the rows f0 P.row(2) - f2 P.row(0) and f1 P.row(2) - f2 P.row(1); depth = v[2] / v[3] for the right
+ * singular vector v of the smallest singular value of that 2 (n + 1) x 4 matrix (feature_manager.cpp:236-266).  The singular vector comes from
+ * one-sided Jacobi on the matrix itself (not from its normal matrix), rows summed in a fixed order: two calls give the same bits, and the
+ * single-window entry the bits of the batch entry.  The blocks enter in the library's packed order, not the caller's: v does not depend on
+ * the order of the rows beyond rounding.
+ *   depth, flag: sum L entries (batch) / L entries (window id), window order, the caller's landmark order; either may be NULL.
+ *   flag 0: skipped by only_unset, depth = 1 / rho;  1: triangulated;  2: the depth came out below min_depth or non-finite and init_depth is
+ *   returned (the reference's `depth < 0.1` lets NaN through: a stated difference);  3: not triangulable -- no block, blocks that name more
+ *   than one anchor observation, or an observation time outside the spline -- depth = 1 / rho, never applied.
+ * CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID for a bad id or NULL options (the handle stays usable).  The launch plan and the captured
+ * graph of the solve are untouched; with apply = 0 the state is bitwise unchanged.  A window may be uploaded with rho <= 0 on its new landmarks
+ * for this purpose; solving such a state is the caller's error. */
+int32_t ctvio_triangulate_batch(ctvio_solver *s, const ctvio_triangulate_options *o, double *depth, int32_t *flag);
+int32_t ctvio_triangulate(ctvio_solver *s, int32_t id, const ctvio_triangulate_options *o, double *depth, int32_t *flag);
+/* Depths in the frame of a new anchor observation: query i is landmark lm[i] of window win[i]; with p_i its current anchor point and camera
+ * poses (row_times as above), depth_new[i] = z(R_new^T (R_old (p_i / rho) + P_old - P_new)) for the new anchor observation at absolute time
+ * t_new[i], row row_new[i] (row_new may be NULL when row_times = 0) -- removeBackShiftDepth (feature_manager.cpp:370-377).
+ *   flag 1: shifted;  2: the result was <= 0 and init_depth is returned;  3: not computable (rho <= 0, no single anchor, a time outside the
+ *   spline), depth_new = NaN.  depth_new, flag: n entries, either may be NULL.  The state is never modified (only row_times and init_depth of the
+ *   options are read).  CTVIO_ERR_INVALID for a window id or landmark index out of range, NULL options, NULL row_new with row_times = 1. */
+int32_t ctvio_shift_anchor_batch(ctvio_solver *s, const ctvio_triangulate_options *o, int64_t n, const int32_t *win, const int32_t *lm,
+                                 const int64_t *t_new, const int32_t *row_new, double *depth_new, int32_t *flag);
+
 /* Batched trajectory query on the device: Se3Spline::poseNs / transVelWorld / rotVelBody / transAccelWorld
  * (se3_spline.h:361-399).  pose7 = (px,py,pz,qx,qy,qz,qw).  Any output may be NULL. */
 int32_t ctvio_spline_eval(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, double *pose7, double *vel3,
@@ -296,7 +335,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  *   7 whole solve (always measured).  launches8: number of launches of each group, [7] = LM passes launched.
  * Groups 0..6 are zero unless profiling was on.
  * After a covariance call instead: ms8[0..2] = device time of k_cov_prepare, k_cov_solve, k_cov_gram, ms8[7] = the whole call on the device
- * (linearisation, Schur complement and Cholesky included), the rest zero. */
+ * (linearisation, Schur complement and Cholesky included), the rest zero.
+ * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
+ * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);
 /* The HIP stream every kernel of this solver is launched on (hipStream_t), for external event timing. */
 void *ctvio_stream(ctvio_solver *s);

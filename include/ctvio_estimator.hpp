@@ -509,6 +509,33 @@ class TrajectoryEstimator {
     return singular == 0;
   }
 
+  // FeatureManager::triangulate (feature_manager.cpp:226-274; row_times: its triangulateRS, :276-339) for the landmarks of the image factors
+  // added so far, at the CURRENT parameter values (ctvio_triangulate): every inverse-depth parameter that is <= 0 (only_unset) or every one
+  // receives 1 / depth in place, as the reference writes estimated_depth.  flags (optional): one ctvio_triangulate flag per inverse-depth
+  // pointer, in the order the pointers were first passed to AddImageFeatureDelayAnalytic (3 for a landmark without a factor).  Returns how
+  // many were written.
+  int TriangulateDepths(bool row_times = true, bool only_unset = true, std::vector<int32_t> *flags = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_triangulate_options o;
+    ctvio_default_triangulate_options(&o);
+    o.row_times = row_times ? 1 : 0; o.only_unset = only_unset ? 1 : 0; o.apply = 0;
+    std::vector<double> depth((size_t)pk.w.L);
+    std::vector<int32_t> fl((size_t)pk.w.L);
+    check(ctvio_triangulate(s, 0, &o, depth.data(), fl.data()));
+    if (flags) flags->assign(lm_ptr_.size(), 3);
+    int written = 0;
+    for (size_t l = 0; l < lm_ptr_.size(); ++l) {
+      const int j = pk.lm_map[l];
+      if (j < 0) continue;
+      if (flags) (*flags)[l] = fl[(size_t)j];
+      if (fl[(size_t)j] == 1 || fl[(size_t)j] == 2) { *lm_ptr_[l] = 1.0 / depth[(size_t)j]; ++written; }
+    }
+    return written;
+  }
+
  private:
   // One packed window: only the knots the factors touch (the reference registers exactly those with Ceres,
   // trajectory_estimator.cpp:114-141; the trajectory itself keeps growing), biases / landmarks that are referenced.
