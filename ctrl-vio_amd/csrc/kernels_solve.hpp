@@ -127,7 +127,7 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
   // Only the knot columns [0, 6K), the line-delay column P - 1 and the appended g_rho column P are fetched and staged (NC
   // compact columns per landmark); every other column of the two LDS buffers is zeroed once and stays zero.
   // SPARSITY: the rows of W are sorted by knot span (host_pack.hpp: plan_sparsity); rows past Lobs are zero, and a tile multiplies only the
-  // chunks that overlap the row range of its two column tiles (cbeg / cend below).
+  // K-steps that overlap the row range of its two column tiles (kb / ke below).
   const int nchunk = (m.Lobs + 15) >> 4, nel = 16 * ldl, NC = K6 + 2, nelc = 16 * NC;
   for (int e = tid; e < 2 * nel; e += 512) Wb[e] = 0.0;
   double pre[NPRE];
@@ -171,15 +171,15 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
   int tij[NTQ];
 #pragma unroll
   for (int q = 0; q < NTQ; ++q) tij[q] = __builtin_amdgcn_readfirstlane(tlist[(wave + 8 * q < nact) ? wave + 8 * q : min(wave, max(nact - 1, 0))]);   // SGPRs
-  // the chunks a tile has products with ride in bits 16-23 (first) and 24-31 (end; 255 = no upper limit) of its SGPR -- separate registers
-  // sent the kernel's scalar file over the edge
+  // the K-steps (one v_mfma: 4 sorted landmark rows) a tile has products with ride in bits 16-23 (first) and 24-31 (end; 255 = no upper limit)
+  // of its SGPR -- separate registers sent the kernel's scalar file over the edge.  (A clamped value only widens the range.)
 #pragma unroll
   for (int q = 0; q < NTQ; ++q) {
     int lb, le;
     schur_row_range(d, m, tij[q] >> 8, tij[q] & 255, lb, le);
     const bool real = wave + 8 * q < nact && le > lb;   // (a slot past the end of the list repeats the wave's first tile: no products for it)
-    const int cb = real ? min(lb >> 4, 254) : 0, ce = real ? min((le + 15) >> 4, 255) : 0;
-    tij[q] = __builtin_amdgcn_readfirstlane(tij[q] | (cb << 16) | (ce << 24));
+    const int kb = real ? min(lb >> 2, 254) : 0, ke = real ? min((le + 3) >> 2, 255) : 0;
+    tij[q] = __builtin_amdgcn_readfirstlane(tij[q] | (kb << 16) | (ke << 24));
   }
   // The accumulators start at -Hpp (rows beyond the unknowns -- the rhs row -- at 0): the tile's Hpp entries arrive with the first chunk of W
   // instead of costing the epilogue a global round trip per tile, and S = -(acc) + D needs no second operand there.
@@ -209,9 +209,13 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
     // The eight operand reads of a tile are issued together, and the scheduler may not move anything across the fences: left to itself it
     // issued every ds_read right before the v_mfma that consumes it -- 28 serial LDS round trips per chunk and wave (5.5 k - 13 k clocks
     // against 0.9 k of matrix-core time).  One round trip per tile is hidden by the other three waves of the SIMD.
+    // Of the first and the last chunk of a tile's row range only the K-steps inside the range are multiplied (in order: S is what it was);
+    // the matrix instruction is 64 cycles of the datapath the vector instructions share, a skipped one a scalar branch.
 #pragma unroll
     for (int q = 0; q < NTQ; ++q) {
-      { const int cb = (tij[q] >> 16) & 255, ce = (tij[q] >> 24) & 255; if (ch < cb || (ch >= ce && ce != 255)) continue; }   // (uniform) no row of this chunk reaches both column tiles
+      const int kb = (tij[q] >> 16) & 255, ke = (tij[q] >> 24) & 255;
+      const int s0 = max(kb - 4 * ch, 0), s1 = ke == 255 ? 4 : min(ke - 4 * ch, 4);
+      if (s0 >= s1) continue;   // (uniform) no row of this chunk reaches both column tiles
       double a[4], b[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
@@ -220,7 +224,8 @@ template <int NPRE, int NTQ> __global__ __launch_bounds__(512, NTQ <= 7 ? 4 : 2)
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s] * dl[s], acc[q], 0, 0, 0);
+      for (int s = 0; s < 4; ++s)
+        if (s >= s0 && s < s1) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b[s] * dl[s], acc[q], 0, 0, 0);   // (uniform)
       __builtin_amdgcn_sched_barrier(0);
     }
     if (ch + 1 < nchunk) stash(ch + 1, buf ^ 1);

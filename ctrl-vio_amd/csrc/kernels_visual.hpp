@@ -80,12 +80,15 @@ __global__ __launch_bounds__(64) void k_vis_anchor(Dev d, int mode) {
   vis_anchor_body(d, mode, srec, blockIdx.x);
 }
 
-// k_vis_eval<LIN> stages the records of its 64 blocks in LDS, block-major like the copy in HBM ([64][VT_LD]: this lane's block starts
-// at J[0]; the odd stride spreads the lanes over the banks) and forms the landmark rows from it after the evaluation.
-constexpr int VT_LD = VT_ROWS + 1;
+// k_vis_eval<LIN> stages the records of its 64 blocks in LDS, block-major like the copy in HBM ([64][VT_ROWS]) and forms the landmark rows
+// from it after the evaluation.  The stride of 40 doubles alone would put the 32 lanes of a ds_write_b64 on four banks (40 l = 8 l mod 32):
+// entry e of block l lives at e ^ ((l >> 2) & 7) instead -- the eight blocks that share l & 3 take the eight places of e's group of eight,
+// the four values of l & 3 the four groups of banks: conflict-free like the odd stride 41 was, in exactly 64 x 40 doubles.
+__device__ __forceinline__ int vt_at(int l, int e) { return VT_ROWS * l + (e ^ ((l >> 2) & 7)); }
 struct VisRecSink {
-  double *J;
-  __device__ __forceinline__ void put(int e, double v) { J[e] = v; }
+  double *wcs;
+  int l;
+  __device__ __forceinline__ void put(int e, double v) { wcs[vt_at(l, e)] = v; }
 };
 struct VisNullSink {
   __device__ __forceinline__ void put(int, double) {}
@@ -95,11 +98,14 @@ struct VisNullSink {
 // (robust-corrected), materialised block-major -- and form the rows of W, Hll, g_rho of the wave's landmarks into the normal-equation
 // set the mode selects.  The wave's share of the cost goes to Dev::vis_cost (a window's block slots start on a wave boundary: one window
 // per wave).  A window on its last allowed iteration is only costed (residuals, no Jacobians, nothing else written).
-constexpr int VIS_LDS_BYTES = 64 * VT_LD * 8;   // the records of a wave's 64 blocks, afterwards the fp64 rows of W of the wave's landmarks
-__device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned char *smt, long long *rowoff, int *rlm, int *rspan, int vblock) {
+constexpr int VIS_LDS_BYTES = 64 * VT_ROWS * 8;   // the records of a wave's 64 blocks, afterwards the fp64 rows of W of the wave's landmarks and
+constexpr int VIS_ROW_BYTES = VIS_LDS_BYTES - 64 * 16;   // (at the buffer's end) their rowoff / rlm / rspan: 20 480 bytes, eight workgroups per CU
+__device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned char *smt, int vblock) {
   const int v = vblock * 64 + threadIdx.x;
   const long long t_entry = d.dbg ? clock64() : 0ll;
-  constexpr int LDS_BYTES = VIS_LDS_BYTES;
+  constexpr int LDS_BYTES = VIS_ROW_BYTES;
+  long long *rowoff = reinterpret_cast<long long *>(smt + VIS_ROW_BYTES);   // [64]  } of the wave's landmarks: first written after the records
+  int *rlm = reinterpret_cast<int *>(rowoff + 64), *rspan = rlm + 64;       // [64]  } have left the buffer
   double *wcs = reinterpret_cast<double *>(smt);
   const bool at_cand = mode == LIN_SPEC;
   const double *quat = at_cand ? d.cquat : d.quat, *pos = at_cand ? d.cpos : d.pos, *ldp = at_cand ? d.cld : d.ld;
@@ -149,13 +155,13 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
       const double pjx = d.v_obs[v], pjy = d.v_obs[(size_t)d.Vtot + v], ca = d.v_cauchy[v];
       double r[2];
       if (jac) {
-        VisRecSink sink{wcs + VT_LD * threadIdx.x};
+        VisRecSink sink{wcs, (int)threadIdx.x};
         on = true;
         my_lm = d.v_lm[v];
         my_anc = anc;
         if (small) c = vis_block_eval<true>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, true, sink);
         else c = vis_block_eval<false>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, true, sink);
-        sink.J[VB_RES] = r[0]; sink.J[VB_RES + 1] = r[1];
+        sink.put(VB_RES, r[0]); sink.put(VB_RES + 1, r[1]);
         d.vsj[v] = sj;
         ksj = sj;
       } else {
@@ -190,21 +196,21 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
     //      once per anchor from the record; line delay, Hll, g_rho ride with that sum.
     double wj[24], s6[6];
     {
-      const double *Jl = wcs + VT_LD * lane;
-      const double jr0 = Jl[VB_RHO], jr1 = Jl[VB_RHO + 1];
+      auto Jl = [&](int e) { return wcs[vt_at(lane, e)]; };
+      const double jr0 = Jl(VB_RHO), jr1 = Jl(VB_RHO + 1);
 #pragma unroll
-      for (int cc = 0; cc < 12; ++cc) wj[cc] = jr0 * Jl[VB_JROT + 2 * cc] + jr1 * Jl[VB_JROT + 2 * cc + 1];
+      for (int cc = 0; cc < 12; ++cc) wj[cc] = jr0 * Jl(VB_JROT + 2 * cc) + jr1 * Jl(VB_JROT + 2 * cc + 1);
 #pragma unroll
-      for (int b = 0; b < 3; ++b) s6[b] = jr0 * Jl[VB_AT + 2 * b] + jr1 * Jl[VB_AT + 2 * b + 1];
+      for (int b = 0; b < 3; ++b) s6[b] = jr0 * Jl(VB_AT + 2 * b) + jr1 * Jl(VB_AT + 2 * b + 1);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const double cp1 = Jl[VB_CP1 + k];
+        const double cp1 = Jl(VB_CP1 + k);
 #pragma unroll
         for (int b = 0; b < 3; ++b) wj[12 + 3 * k + b] = -(cp1 * s6[b]);
       }
-      s6[3] = jr0 * Jl[VB_LD] + jr1 * Jl[VB_LD + 1];
+      s6[3] = jr0 * Jl(VB_LD) + jr1 * Jl(VB_LD + 1);
       s6[4] = jr0 * jr0 + jr1 * jr1;
-      s6[5] = jr0 * Jl[VB_RES] + jr1 * Jl[VB_RES + 1];
+      s6[5] = jr0 * Jl(VB_RES) + jr1 * Jl(VB_RES + 1);
     }
     // the anchor record's GR and cp0 again (every lane asks for its own anchor's: same lines as during the evaluation; only the head
     // lane of an anchor uses them) -- requested here, consumed after the copy-out below, which hides the round trip
@@ -246,9 +252,11 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
 #pragma unroll 4
       for (int k = 0; k < HP; ++k) {             // 64 * HP pairs, 64 per store
         const int i = k * 64 + lane, bl = i / HP, r = 2 * (i - bl * HP);
+        const int sw = (bl >> 2) & 7;              // (a pair of entries stays an aligned pair under the swizzle, swapped where sw is odd)
+        const VecN<double, 2> pp = *reinterpret_cast<const VecN<double, 2> *>(wcs + VT_ROWS * bl + (r ^ (sw & 6)));
         VecN<double, 2> pr;
-        pr.v[0] = wcs[VT_LD * bl + r];
-        pr.v[1] = wcs[VT_LD * bl + r + 1];
+        pr.v[0] = (sw & 1) ? pp.v[1] : pp.v[0];
+        pr.v[1] = (sw & 1) ? pp.v[0] : pp.v[1];
         if ((on_mask >> bl) & 1ull) *reinterpret_cast<VecN<double, 2> *>(dst + (size_t)bl * VT_ROWS + r) = pr;
       }
     }
@@ -272,12 +280,12 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
     const int SPW = d.max_span6;
     const int RS = SPW + 3;                                            // odd row stride (SPW is even)
     const int NR = max(1, min(nlm, ((int)(LDS_BYTES / 8) - 1) / RS));
-    if (head) { rowoff[ord] = W0 + (long long)my_row * ldw; rlm[ord] = my_lm; rspan[ord] = (my_klo << 16) | max(my_khi - my_klo + 1, 0); }
     // an end outside the planned span would corrupt a neighbour's row: counted (ctvio_solve fails loudly) and clamped
     int ri = ksi - my_klo, rj = ksj - my_klo;
     if (on && (rj < 0 || ksj + 3 > my_khi || (head_a && (ri < 0 || ksi + 3 > my_khi)))) atomicAdd(d.span_viol, 1);
     ri = max(0, min(ri, SPW / 6 - 4)); rj = max(0, min(rj, SPW / 6 - 4));
     lds_wave_sync();   // every lane has read its record, the copy-out has read them all
+    if (head) { rowoff[ord] = W0 + (long long)my_row * ldw; rlm[ord] = my_lm; rspan[ord] = (my_klo << 16) | max(my_khi - my_klo + 1, 0); }   // (read after the sweep's own fences)
     for (int c0 = 0; c0 < nlm; c0 += NR) {
       const int nr = min(NR, nlm - c0);
       for (int i = 2 * lane; i < nr * RS; i += 128) *reinterpret_cast<VecN<double, 2> *>(rows + i) = VecN<double, 2>{{0.0, 0.0}};   // (NR RS + 1 doubles fit)
@@ -338,9 +346,7 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_vis_eval(Dev d, int mode) {
   __shared__ __attribute__((aligned(16))) unsigned char smt[VIS_LDS_BYTES];
-  __shared__ long long rowoff[64];
-  __shared__ int rlm[64], rspan[64];
-  vis_eval_body(d, mode, smt, rowoff, rlm, rspan, blockIdx.x);
+  vis_eval_body(d, mode, smt, blockIdx.x);
 }
 
 // Both evaluations in ONE launch: workgroups [0, Gtot) take an IMU group each, the others a wave of 64 visual block slots.  The two are
@@ -349,11 +355,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_linearize_f64(Dev d, int mode, int general_only, int zero_mode) {
   static_assert(VIS_LDS_BYTES >= (72 * 33 + 64) * 8, "the IMU rows use the head of the visual body's LDS buffer");
   __shared__ __attribute__((aligned(32))) unsigned char smt[VIS_LDS_BYTES];
-  __shared__ long long rowoff[64];
-  __shared__ int rlm[64], rspan[64];
   if ((int)blockIdx.x < d.Gtot) {
     if (!general_only) imu_linearize_f64_fast(d, mode, reinterpret_cast<double *>(smt), blockIdx.x, d.Gtot, zero_mode);   // (one group per wave here)
-  } else vis_eval_body(d, mode, smt, rowoff, rlm, rspan, blockIdx.x - d.Gtot);
+  } else vis_eval_body(d, mode, smt, blockIdx.x - d.Gtot);
 }
 
 }  // namespace ctv
