@@ -15,6 +15,7 @@
 #include <cstring>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -1174,16 +1175,20 @@ class SolverImpl {
     hipLaunchKernelGGL(k_gauge_restore, dim3(n), dim3(64), 0, stream_, dev_, n, di, di + nn, dp, dp + 4 * nn);
     return sync_call();
   }
+  // the sensor-to-IMU extrinsic as the kernels take it: the quaternion normalised
+  static int sensor_ext(const double *q_SI, const double *p_SI, SensorExt &ext) {
+    const double nq = std::sqrt(q_SI[0] * q_SI[0] + q_SI[1] * q_SI[1] + q_SI[2] * q_SI[2] + q_SI[3] * q_SI[3]);
+    if (!(nq > 0.0) || !std::isfinite(nq)) return fail(CTVIO_ERR_INVALID, "sensor extrinsic: quaternion must be non-zero and finite");
+    for (int i = 0; i < 4; ++i) ext.q[i] = q_SI[i] / nq;
+    for (int i = 0; i < 3; ++i) ext.p[i] = p_SI[i];
+    ext.on = 1;
+    return CTVIO_OK;
+  }
   int spline_eval(int id, int n, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3, const double *q_SI = nullptr,
                   const double *p_SI = nullptr) {
     SensorExt ext{};
-    if (q_SI && p_SI) {
-      const double nq = std::sqrt(q_SI[0] * q_SI[0] + q_SI[1] * q_SI[1] + q_SI[2] * q_SI[2] + q_SI[3] * q_SI[3]);
-      if (!(nq > 0.0) || !std::isfinite(nq)) return fail(CTVIO_ERR_INVALID, "sensor extrinsic: quaternion must be non-zero and finite");
-      for (int i = 0; i < 4; ++i) ext.q[i] = q_SI[i] / nq;
-      for (int i = 0; i < 3; ++i) ext.p[i] = p_SI[i];
-      ext.on = 1;
-    }
+    if (q_SI && p_SI)
+      if (const int rc = sensor_ext(q_SI, p_SI, ext)) return rc;
     if (const int rc = guard(id, "bad arguments")) return rc;
     if (n < 0 || (n && !t_ns)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     return spline_query(id, nullptr, n, t_ns, pose7, vel3, omega3, acc3, ext, nullptr);
@@ -1239,6 +1244,35 @@ class SolverImpl {
   // damping, every tile of S written -- and the kernels of csrc/kernels_cov.hpp.  dev_, plan_ and the captured graph are not touched; the panel
   // kernel launches from the plan like the solve's (launch_chol_panel).  The scratch follows the call's selections, not the upload.
   static constexpr int COV_MAX_SEL = 64;
+  // The shared middle of covariance() and pose_covariance(): the normal equations at the current state, then the factor of the undamped
+  // reduced system on c, the call's copy of Dev.  Records EV_CALL_BEGIN .. EV_COV_SOLVE; the stream is left ready for k_cov_solve.
+  int cov_factor(Dev &c, uint8_t *mask, uint8_t *excl) {
+    set_params(1);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+    launch_initial(opt_.initial_radius);
+    c = dev_;
+    c.schur_plain_in_H = 0;
+    c.active = mask;
+    HIPCHK(hipEventRecord(ev_[EV_COV_PREPARE], stream_));
+    hipLaunchKernelGGL(k_cov_prepare, dim3(dev_.nwin), dim3(256), 0, stream_, dev_, mask, excl);
+    HIPCHK(hipEventRecord(ev_[EV_COV_FACTOR], stream_));
+    launch_schur(c);
+    launch_chol_panel(c);
+    HIPCHK(hipEventRecord(ev_[EV_COV_SOLVE], stream_));
+    return CTVIO_OK;
+  }
+  size_t cov_solve_lds() const { return ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double); }   // Ys | part (k_cov_solve)
+  // the three kernel times of a covariance call (the stream is idle): ms[i] between the events pair[i], where the kernel ran
+  int cov_timing(const Ev (&pair)[3][2], const bool (&ran)[3]) {
+    Timing t;
+    t.clear();
+    for (int i = 0; i < 3; ++i) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, ev_[pair[i][0]], ev_[pair[i][1]]));
+      t.ms[i] = ms; t.n[i] = ran[i] ? 1 : 0;
+    }
+    return publish_timing(t, 0);
+  }
   int covariance(int only, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
     if (const int rc = guard()) return rc;
     const int nw = dev_.nwin;
@@ -1297,23 +1331,11 @@ class SolverImpl {
     if (!cwins.empty()) std::memcpy(io_host<CovWin>(io, s_wins), cwins.data(), sizeof(CovWin) * cwins.size());
     if (io.off(s_cov) > io.off(s_sel))
       HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_sel), io_host<char>(io, s_sel), io.off(s_cov) - io.off(s_sel), hipMemcpyHostToDevice, stream_));
-    // ---- normal equations at the current state, then the factor of the undamped reduced system
-    set_params(1);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-    launch_initial(opt_.initial_radius);
-    Dev c = dev_;
-    c.schur_plain_in_H = 0;
-    c.active = mask;
-    HIPCHK(hipEventRecord(ev_[EV_COV_PREPARE], stream_));
-    hipLaunchKernelGGL(k_cov_prepare, dim3(nw), dim3(256), 0, stream_, dev_, mask, excl);
-    HIPCHK(hipEventRecord(ev_[EV_COV_FACTOR], stream_));
-    launch_schur(c);
-    launch_chol_panel(c);
-    HIPCHK(hipEventRecord(ev_[EV_COV_SOLVE], stream_));
-    if (!tiles.empty()) {
-      const size_t lds = ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double);
-      hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), lds, stream_, c, dtiles, dsel, dy, dvar);
-    }
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    if (!tiles.empty())
+      hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, dtiles, dsel, dy, dvar, (const PoseRec *)nullptr,
+                         (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     if (!cwins.empty())
       hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
@@ -1325,14 +1347,7 @@ class SolverImpl {
     {   // device times of this call, for ctvio_last_timing: the three covariance kernels and the whole call
       const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_SOLVE, EV_COV_GRAM}, {EV_COV_GRAM, EV_CALL_END}};
       const bool ran[3] = {true, !tiles.empty(), !cwins.empty()};
-      Timing t;
-      t.clear();
-      for (int i = 0; i < 3; ++i) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev_[pair[i][0]], ev_[pair[i][1]]));
-        t.ms[i] = ms; t.n[i] = ran[i] ? 1 : 0;
-      }
-      if (const int rc = publish_timing(t, 0)) return rc;
+      if (const int rc = cov_timing(pair, ran)) return rc;
     }
     // (a window whose factorisation met a non-positive or non-finite pivot: its outputs are NaN)
     const double nan = std::nan("");
@@ -1348,6 +1363,82 @@ class SolverImpl {
         ov += (size_t)m.L;
       }
       oc += ns * ns;
+    }
+    return CTVIO_OK;
+  }
+  // ctvio_pose_covariance_batch / ctvio_pose_covariance (only >= 0: every query belongs to that window, win is not read): J Sigma J^T of the
+  // pose at n query times.  The queries are grouped by window (stable: a window's queries keep the caller's order) and paired into tiles of
+  // kind 2; k_cov_pose_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 6 x 6 blocks into the
+  // caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are not touched.
+  int pose_covariance(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *cov36,
+                      int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || !cov36 || (only < 0 && !win)))) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if ((q_SI == nullptr) != (p_SI == nullptr)) return fail(CTVIO_ERR_INVALID, "sensor extrinsic: q_SI and p_SI come together (both null: the body pose)");
+    SensorExt ext{};
+    if (q_SI)
+      if (const int rc = sensor_ext(q_SI, p_SI, ext)) return rc;
+    const int n = (int)n64, nw = dev_.nwin;
+    const size_t nn = (size_t)n;
+    if (only < 0)
+      for (int i = 0; i < n; ++i)
+        if (win[i] < 0 || win[i] >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+    if (n == 0) return CTVIO_OK;
+    // ---- queries by window, two per tile; slot[r]: the caller's index of sorted query r
+    std::vector<int32_t> slot(nn);
+    for (int i = 0; i < n; ++i) slot[i] = i;
+    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
+    std::vector<CovTile> tiles;
+    for (int r = 0; r < n;) {
+      const int cnt = (r + 1 < n && win_of(r + 1) == win_of(r)) ? 2 : 1;
+      tiles.push_back(CovTile{win_of(r), 2, r, cnt, 0});
+      r += cnt;
+    }
+    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); cov36 | status (out, one copy).  scr: mask, exclusions, records
+    CallLayout io = head_, scr;
+    const int s_q = io.add("queries", sizeof(PoseQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov36", sizeof(double), 36 * nn, true),
+              s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_rec = scr.add("records", sizeof(PoseRec), nn, false);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    PoseRec *drec = scr.at<PoseRec>(call_scr_.dev, s_rec);
+    PoseQuery *hq = io_host<PoseQuery>(io, s_q);
+    for (int r = 0; r < n; ++r) hq[r] = PoseQuery{win_of(r), 0, (long long)(t_ns[slot[(size_t)r]] - t0_[win_of(r)])};
+    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_cov) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, drec, io_dev<int32_t>(io, s_stat));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+                       io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, drec, io_dev<double>(io, s_cov));
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // ---- results: the blocks as the kernel left them, the statuses in sorted order
+    int32_t *hstat = io_host<int32_t>(io, s_stat);
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov36 | status)
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_pose_jac and the whole call
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
+      const bool ran[3] = {true, true, true};
+      if (const int rc = cov_timing(pair, ran)) return rc;
+    }
+    // (time outside the spline: NaN; an untouched knot: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN)
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    const double *hcov = io_host<double>(io, s_cov);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      int st = hstat[r];
+      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
+      double *o = cov36 + 36 * i;
+      if (st == POSE_OK) std::memcpy(o, hcov + 36 * i, sizeof(double) * 36);
+      else for (int e = 0; e < 36; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 7 == 0 ? inf : 0.0) : nan;
+      if (status) status[i] = st;
     }
     return CTVIO_OK;
   }
@@ -1556,6 +1647,16 @@ int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.covariance(id, &n_sel, sel, cov, var_rho, singular);
+}
+int32_t ctvio_pose_covariance_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, const double *q_SI, const double *p_SI,
+                                    double *cov36, int32_t *status) {
+  CHK_S; return s->impl.pose_covariance(-1, n, win, t_ns, q_SI, p_SI, cov36, status);
+}
+int32_t ctvio_pose_covariance(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *cov36,
+                              int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.pose_covariance(id, n, nullptr, t_ns, q_SI, p_SI, cov36, status);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

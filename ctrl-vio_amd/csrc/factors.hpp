@@ -401,6 +401,35 @@ template <class SC> CTV_DI Q4 eval_R(const Q4 q[4], const SC &sc, double u) {
   return res;
 }
 
+// Jacobian of the pose at u against the tangents of its four knots (ctvio_pose_covariance), TRANSPOSED: jt[(6 k + c) * 6 + a] =
+// d(output a) / d(unknown c of knot k), unknowns (rot 0..2, pos 3..5) under R_k <- R_k exp(delta_k), p_k <- p_k + dp_k, outputs
+// (dtheta 0..2, dp 3..5) under R(t) <- R(t) exp(dtheta), p(t) <- p(t) + dp.  Body pose: d(dtheta) / d(delta_k) = J^Rp_k (eval_Rp),
+// d(dp) / d(dp_k) = c_k I with c the blending coefficients of the position spline, cross blocks zero.  With a sensor extrinsic (q_SI, p_SI) the
+// pose is T_I(t) T_SI: dtheta_S = R_SI^T dtheta_I, dp_S = dp_I - R_I(t) hat(p_SI) dtheta_I.  All 144 entries are written, each once.
+// At u = 0 the last knot's blocks are exact zeros (c_3 = u^3 / 6 in both bases).
+template <class SC> CTV_DI void pose_jac_T(const Q4 q[4], const SC &sc, double u, bool ext_on, Q4 q_SI, V3 p_SI, double *jt) {
+  M3 J[4];
+  const Q4 R = eval_Rp<SC>(q, sc, u, J, true);
+  double c[4];
+  basis<false, 0>(u, 1.0, c);
+  M3 RSI = m3_id(), X = m3_zero();   // X = -R_I(t) hat(p_SI)
+  if (ext_on) { RSI = q2R(q_SI); X = scale(mul_hat(q2R(R), p_SI), -1.0); }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const M3 B = mul(X, J[k]);
+#pragma unroll
+    for (int cc = 0; cc < 3; ++cc)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        // rotation unknown cc of knot k: (R_SI^T J_k)[a][cc], then the lever arm
+        jt[(6 * k + cc) * 6 + a] = ext_on ? RSI.m[a] * J[k].m[cc] + RSI.m[3 + a] * J[k].m[3 + cc] + RSI.m[6 + a] * J[k].m[6 + cc] : J[k].m[3 * a + cc];
+        jt[(6 * k + cc) * 6 + 3 + a] = ext_on ? B.m[3 * a + cc] : 0.0;
+        jt[(6 * k + 3 + cc) * 6 + a] = 0.0;
+        jt[(6 * k + 3 + cc) * 6 + 3 + a] = a == cc ? c[k] : 0.0;
+      }
+  }
+}
+
 // Streaming forms of the two views: the per-knot partial Jacobians are handed to `f(knot, J)` one at a time, as soon as they
 // are final, instead of being returned as four 3 x 3 matrices -- the same operations in the same order (bit-identical
 // values), but only ~5 matrices are live at any time (the array forms keep 11, i.e. ~200 fp64 registers for both ends).

@@ -1,5 +1,6 @@
 // kernels_cov.hpp -- marginal covariances from the reduced system (ctvio_covariance_batch): k_cov_prepare (per-call activity mask, zero damping),
-// k_cov_solve (block forward substitution against 16 right-hand sides per workgroup), k_cov_gram (selected block of the covariance).
+// k_cov_solve (block forward substitution against 16 right-hand sides per workgroup), k_cov_gram (selected block of the covariance); pose
+// covariances at query times (ctvio_pose_covariance_batch): k_cov_pose_jac (one record per query), then k_cov_solve on tiles of kind 2.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -7,6 +8,7 @@
 // the inverses of the 32 x 32 diagonal blocks in Dev::chol_inv).  Then
 //   Sigma[i][j]     = (L^-1 e_i)^T (L^-1 e_j)                    for trajectory unknowns i, j,
 //   Sigma[P+l][P+l] = 1 / Hll_l + | L^-1 (w_l / Hll_l) |^2        for the inverse depth of landmark l (w_l: its row of W),
+//   Sigma_pose(t)   = J Sigma J^T = (L^-1 J^T)^T (L^-1 J^T)        for the 6 x P Jacobian J of the pose at time t (factors.hpp: pose_jac_T),
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -15,9 +17,11 @@ namespace ctv {
 // One right-hand-side tile: 16 columns of one window.
 struct CovTile {
   int32_t win;
-  int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll
-  int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1: first row of W (window-local)
-  int32_t count;    // columns in use (<= 16)
+  int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll; 2: the six columns of
+                    // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5)
+  int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1: first row of W (window-local);
+                    // kind 2: the tile's first query record
+  int32_t count;    // columns in use (<= 16); kind 2: queries (1 or 2)
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -57,12 +61,56 @@ __global__ __launch_bounds__(256) void k_cov_prepare(Dev d, uint8_t *mask, uint8
   }
 }
 
+// One pose query (ctvio_pose_covariance_batch), grouped by window on the host, and what k_cov_pose_jac makes of it.
+enum { POSE_OK = 0, POSE_SINGULAR = 1, POSE_UNTOUCHED = 2, POSE_OUTSIDE = 3 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
+struct PoseQuery {
+  int32_t win, pad;
+  long long t_rel;   // relative to the window's t0
+};
+struct PoseRec {
+  int32_t status, s, nk, pad;   // first knot; knots the pose depends on: 3 at u = 0 (the last blending weights are u^3 / 6), else 4
+  double jt[144];               // J^T, rows of knots s .. s + 3 (pose_jac_T; written for POSE_OK only)
+};
+
+// One lane per query: segment and u by the integer-ns rule of k_spline_eval, the status, and J^T at the current state.  A knot the pose
+// depends on that no factor touches (k_cov_prepare: COV_UNTOUCHED on any of its six unknowns) gives POSE_UNTOUCHED: decided on the
+// exclusion flags and on u > 0, never on a Jacobian entry.
+__global__ __launch_bounds__(64) void k_cov_pose_jac(Dev d, int n, const PoseQuery *qs, const uint8_t *excl, SensorExt ext, PoseRec *recs, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PoseQuery q = qs[i];
+  const WinMeta &m = d.wins[q.win];
+  const long long sl = q.t_rel / m.dt_ns;
+  const bool outside = q.t_rel < 0 || sl + 3 >= m.K;
+  const int s = outside ? 0 : (int)sl;
+  const double u = (double)(q.t_rel % m.dt_ns) / (double)m.dt_ns;
+  const int nk = u > 0.0 ? 4 : 3;
+  int status = outside ? POSE_OUTSIDE : POSE_OK;
+  if (!outside)
+    for (int j = 6 * s; j < 6 * (s + nk); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+  PoseRec &r = recs[i];
+  r.status = status; r.s = s; r.nk = nk; r.pad = 0;
+  status_out[i] = status;
+  if (status != POSE_OK) return;
+  const double zero3[3] = {0, 0, 0};
+  Knots4 k;
+  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  SegConst sc;
+  seg_const(k, sc, true);
+  pose_jac_T(k.q, sc, u, ext.on != 0, qmk(ext.q[0], ext.q[1], ext.q[2], ext.q[3]), mk(ext.p[0], ext.p[1], ext.p[2]), r.jt);
+}
+
 // Y = L^-1 B for one tile of 16 right-hand sides.  d is the covariance's copy of Dev (d.active = the per-call mask).  Four waves: wave (h, kp)
 // owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of a half are added
 // in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row, as the back-substitution of the panel
-// kernel reads it); L_bb^-1 from Dev::chol_inv.  The substitution starts at the first block in which the tile is non-zero.
+// kernel reads it); L_bb^-1 from Dev::chol_inv.  The substitution starts at the first block in which the tile is non-zero; the 16-column
+// tiles of the products go to the two partial sums by their parity, so where the tile starts moves no product from one sum to the other:
+// a column's bits do not depend on the columns it shares the tile with.
+// Kind 2: sel = the caller's slot of every query record, prec = the records, pose_cov = the caller-ordered 6 x 6 blocks.
 constexpr int COV_NT = 256;
-__global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho) {
+__global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
+                                                      const PoseRec *prec, double *pose_cov) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
   const WinMeta &m = d.wins[w];
@@ -82,6 +130,15 @@ __global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tile
       const int j = sel[t.first + tid];
       if (d.active[m.u0 + j]) { Ys[j * 16 + tid] = 1.0; atomicMin(&s_first, j); }   // (an excluded unknown: a zero column, finished by k_cov_gram)
     }
+  } else if (t.kind == 2) {   // rows 6 s .. 6 (s + nk) - 1 of every query's six columns, where the unknown is in the system
+    for (int e = tid; e < 144 * t.count; e += COV_NT) {
+      const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
+      const PoseRec &pr = prec[t.first + qi];
+      if (pr.status == POSE_OK && r < 6 * pr.nk && d.active[m.u0 + 6 * pr.s + r]) Ys[(6 * pr.s + r) * 16 + 6 * qi + a] = pr.jt[6 * r + a];
+    }
+    if (tid == 0)
+      for (int qi = 0; qi < t.count; ++qi)
+        if (prec[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * prec[t.first + qi].s);
   } else {
     const int col = tid >> 4, sub = tid & 15;
     if (col < t.count) {
@@ -118,7 +175,7 @@ __global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tile
     const int kbeg = max(16 * ef[min(R, P / 16)], 32 * b0);
     f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     if (16 * R < P) {
-      for (int kt = kbeg / 16 + kp; 16 * kt < 32 * b; kt += 2) {
+      for (int kt = kbeg / 16 + ((kbeg / 16 + kp) & 1); 16 * kt < 32 * b; kt += 2) {   // (tiles kt = kp mod 2)
         double av[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) av[kk] = rlive ? arow[16 * kt + 4 * kk + q4] : 0.0;
@@ -155,6 +212,18 @@ __global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tile
   if (t.kind == 0) {   // a selection tile: Y to the scratch, for k_cov_gram
     double *yo = yscr + t.yoff;
     for (int e = tid; e < 16 * P; e += COV_NT) yo[e] = Ys[e];
+    return;
+  }
+  if (t.kind == 2) {   // pose tiles: the two 6 x 6 Gram blocks straight from Ys; every entry three partial sums over the rows k = p mod 3, added in sequence
+    const int k0 = min(32 * b0, P) / 3 * 3;
+    if (tid < 216) {
+      const int p = tid / 72, e = tid % 72, ci = 6 * (e / 36) + (e % 36) / 6, cj = 6 * (e / 36) + e % 6;
+      double s = 0.0;
+      for (int k = k0 + p; k < P; k += 3) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+      part[p * 72 + e] = s;
+    }
+    __syncthreads();
+    if (tid < 36 * t.count) pose_cov[(long long)36 * sel[t.first + tid / 36] + tid % 36] = (part[tid] + part[72 + tid]) + part[144 + tid];
     return;
   }
   // ---- a landmark tile: column sums of squares in a fixed order (16 strided partial sums per column, then added in sequence)

@@ -267,6 +267,35 @@ class Solver:
         capi.check(self._lib.ctvio_covariance(self._h, int(wid), n, capi._p(sel), capi._p(cov), capi._p(var) if rho else None, capi._p(sing)))
         return cov[:n * n].reshape(n, n).copy(), (var[:L].copy() if rho else None), int(sing[0])
 
+    @staticmethod
+    def _extrinsic(q_SI, p_SI):
+        if (q_SI is None) != (p_SI is None):
+            raise ValueError("q_SI and p_SI come together (both None: the body pose)")
+        if q_SI is None:
+            return None, None
+        return np.ascontiguousarray(q_SI, np.float64).reshape(4), np.ascontiguousarray(p_SI, np.float64).reshape(3)
+
+    def pose_covariance_batch(self, win, t_ns, q_SI=None, p_SI=None):
+        """ctvio_pose_covariance_batch: the 6 x 6 covariance of the pose at absolute time t_ns[i] of window win[i], at the current state, in the
+        tangent (theta, p) of R(t) <- R(t) exp(dtheta), p(t) <- p(t) + dp.  q_SI = (x,y,z,w), p_SI: a sensor extrinsic (None: the body pose).
+        Returns (cov (n, 6, 6), status (n,)): 0 ok, 1 singular window (NaN), 2 an untouched knot (+inf diagonal), 3 time outside the spline (NaN)."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1); t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        n = int(t.shape[0])
+        assert wi.shape[0] == n
+        q, p = self._extrinsic(q_SI, p_SI)
+        cov = np.zeros((max(n, 1), 6, 6)); st = np.zeros(max(n, 1), np.int32)
+        capi.check(self._lib.ctvio_pose_covariance_batch(self._h, C.c_int64(n), capi._p(wi), capi._p(t), capi._p(q), capi._p(p), capi._p(cov), capi._p(st)))
+        return cov[:n].copy(), st[:n].copy()
+
+    def pose_covariance(self, wid: int, t_ns, q_SI=None, p_SI=None):
+        """ctvio_pose_covariance: the same for the times t_ns of window wid alone (same bits as the batch entry)."""
+        t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        n = int(t.shape[0])
+        q, p = self._extrinsic(q_SI, p_SI)
+        cov = np.zeros((max(n, 1), 6, 6)); st = np.zeros(max(n, 1), np.int32)
+        capi.check(self._lib.ctvio_pose_covariance(self._h, int(wid), n, capi._p(t), capi._p(q), capi._p(p), capi._p(cov), capi._p(st)))
+        return cov[:n].copy(), st[:n].copy()
+
     def _tri_options(self, opts):
         o = capi.TriangulateOptions()
         self._lib.ctvio_default_triangulate_options(C.byref(o))

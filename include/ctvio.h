@@ -214,6 +214,30 @@ int32_t ctvio_lm_step(ctvio_solver *s, int32_t id, double mu, double *delta, dou
 int32_t ctvio_covariance_batch(ctvio_solver *s, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
 int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
 
+/* The 6 x 6 covariance of the POSE at a time -- what an odometry message, a gate or a downstream fuser takes -- from the same reduced system:
+ * Sigma_pose(t) = J Sigma J^T, with H, the exclusions and Sigma exactly those of ctvio_covariance_batch (no damping) and J the Jacobian of the
+ * pose at t against the spline unknowns, evaluated on the device (the cumulative-B-spline rotation Jacobian of the visual factors, reference
+ * so3_spline_view.h:136-198).  Query i = (window win[i], absolute time t_ns[i]) at the CURRENT state; any number of queries per window, in any
+ * order, from any windows -- no 64-unknown limit.  Segment and u by the integer-ns rule of ctvio_spline_eval; the time must lie in
+ * [t0, t0 + (K - 3) dt).  The pose depends on knots s, s + 1, s + 2, and on s + 3 iff u > 0.
+ *   Tangent of the result: R(t) <- R(t) exp(dtheta), p(t) <- p(t) + dp, ordered (theta0..2, p0..2) -- rotation first, as in the unknown order;
+ *   the knots under the library's own retraction (R_k <- R_k exp(delta_k), p_k <- p_k + dp_k).
+ *   q_SI = (x,y,z,w), p_SI (the arguments of ctvio_sensor_pose; both NULL: the body pose): the pose is T_I(t) T_SI, dtheta_S = R_SI^T dtheta_I,
+ *   dp_S = dp_I - R_I(t) [p_SI]x dtheta_I.
+ *   cov36: n x 36 doubles, row-major 6 x 6 per query, symmetric to the bit.  status (n entries, or NULL) per query:
+ *     0 ok;  1 the window's factorisation met a non-positive or non-finite pivot: NaN;  2 a knot the pose depends on is touched by no factor:
+ *     +inf on the diagonal, 0 elsewhere;  3 time outside the spline: NaN.
+ *   Constant unknowns contribute nothing: a pose that depends on constant knots alone has the exact zero matrix and status 0.
+ * The call returns CTVIO_OK for every status.  n == 0 returns CTVIO_OK and launches nothing.  CTVIO_ERR_STATE before the upload;
+ * CTVIO_ERR_INVALID for a window id out of range, n < 0, a NULL win / t_ns / cov36 with n > 0, exactly one of q_SI / p_SI NULL (or a zero
+ * quaternion); the handle stays usable.  The state, the launch plan and the captured graph of the solve are left as they were; no atomics:
+ * where the linearisation is order-fixed (opt.deterministic) the bits of a query's result depend on its window and time alone -- not on the
+ * entry (batch or single-window: win is window id for every query), the order of the queries, or which other query shares its tile. */
+int32_t ctvio_pose_covariance_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, const double *q_SI, const double *p_SI,
+                                    double *cov36, int32_t *status);
+int32_t ctvio_pose_covariance(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *cov36,
+                              int32_t *status);
+
 /* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
  * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
  * a slide (feature_manager.cpp:341-381, visual_odometry.cpp:299-308). */
@@ -336,6 +360,8 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * Groups 0..6 are zero unless profiling was on.
  * After a covariance call instead: ms8[0..2] = device time of k_cov_prepare, k_cov_solve, k_cov_gram, ms8[7] = the whole call on the device
  * (linearisation, Schur complement and Cholesky included), the rest zero.
+ * After a pose-covariance call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution and the 6 x 6 blocks), k_cov_pose_jac,
+ * ms8[7] = the whole call on the device, the rest zero.
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

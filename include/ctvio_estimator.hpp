@@ -508,6 +508,22 @@ class TrajectoryEstimator {
     }
     return singular == 0;
   }
+  // The 6 x 6 covariance of the pose at the times t_ns (absolute, inside the solved knots), at the CURRENT parameter values, from the factors
+  // of Solve (ctvio_pose_covariance): cov36 = t_ns.size() x 36, row-major per time, in the tangent (theta0..2, p0..2) of R(t) <- R(t) exp(dtheta),
+  // p(t) <- p(t) + dp.  q_SI = (x,y,z,w), p_SI: a sensor extrinsic (e.g. traj.q_CI / p_CI for the camera pose; both null: the body pose).
+  // Returns false if any status is not 0 (ctvio.h: a singular window or a time outside the spline give NaN, a knot no factor touches +inf).
+  bool GetPoseCovariance(const std::vector<int64_t> &t_ns, std::vector<double> &cov36, const double *q_SI = nullptr, const double *p_SI = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    const size_t n = t_ns.size();
+    cov36.assign(36 * n, 0.0);
+    std::vector<int32_t> status(n, 0);
+    check(ctvio_pose_covariance(s, 0, (int32_t)n, t_ns.data(), q_SI, p_SI, cov36.data(), status.data()));
+    for (int32_t st : status) if (st != 0) return false;
+    return true;
+  }
 
   // FeatureManager::triangulate (feature_manager.cpp:226-274; row_times: its triangulateRS, :276-339) for the landmarks of the image factors
   // added so far, at the CURRENT parameter values (ctvio_triangulate): every inverse-depth parameter that is <= 0 (only_unset) or every one
