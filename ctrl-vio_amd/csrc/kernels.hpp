@@ -58,6 +58,18 @@ __device__ __forceinline__ double readlane_d(double x, int lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// the sum of a value over the four 16-lane row groups of the wave, in every lane (the tree of two __shfl_xor steps, without the LDS crossbar)
+__device__ __forceinline__ double rowgroup_sum(double p) {
+  unsigned lo = (unsigned)__double2loint(p), hi = (unsigned)__double2hiint(p);
+  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);   // [0] = {g0, g0, g2, g2}, [1] = {g1, g1, g3, g3}
+  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  const double s = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
+  lo = (unsigned)__double2loint(s); hi = (unsigned)__double2hiint(s);
+  const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);   // [0] = {lower half, lower half}, [1] = {upper, upper}
+  const auto e = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __hiloint2double((int)e[0], (int)c[0]) + __hiloint2double((int)e[1], (int)c[1]);
+}
+
 // A wave-uniform zero the compiler cannot see through (an SGPR written by an opaque s_mov): added to an index or an address, it makes
 // the result depend on this point of the program, so that it is recomputed here instead of being hoisted and kept live -- or spilled --
 // across a loop or a phase.  Each use says what it keeps from being hoisted.
@@ -95,7 +107,7 @@ __device__ __forceinline__ int imu_col(int c, int s, int K, int bias) {
   if (c < 24) return 6 * (s + (c - 12) / 3) + 3 + (c - 12) % 3;
   return 6 * K + 6 * bias + (c - 24);
 }
-__device__ __forceinline__ int vis_col(int c, int si, int sj, int P) {
+constexpr __device__ __forceinline__ int vis_col(int c, int si, int sj, int P) {
   if (c < 12) return 6 * (si + c / 3) + c % 3;
   if (c < 24) return 6 * (si + (c - 12) / 3) + 3 + (c - 12) % 3;
   if (c < 36) return 6 * (sj + (c - 24) / 3) + (c - 24) % 3;
@@ -103,6 +115,26 @@ __device__ __forceinline__ int vis_col(int c, int si, int sj, int P) {
   if (c == 48) return -1;  // inverse depth: landmark block
   return P - 1;            // line delay
 }
+// The visual assembly multiplies the 48 pose columns of a run in KNOT-MAJOR order: [i end: knot 0 (dtheta 3, dp 3) .. knot 3][j end: the
+// same], so that local column c is unknown 6 si + c (c < 24) or 6 sj + c - 24: contiguous per end, no division in the scatter.  The staged
+// rows keep vis_col's order (rotations of the four knots, then positions); vis_knot_major_to_col(c) is the vis_col column behind c.
+constexpr __device__ __forceinline__ int vis_knot_major_to_col(int c) {
+  const int end = c / 24, r = c % 24, k = r / 6, cc = r % 6;
+  return 24 * end + (cc < 3 ? 3 * k + cc : 12 + 3 * k + (cc - 3));
+}
+constexpr bool vis_knot_major_complete() {   // a bijection of 0 .. 47 that vis_col maps onto the contiguous formula
+  bool seen[48] = {};
+  for (int c = 0; c < 48; ++c) {
+    const int o = vis_knot_major_to_col(c);
+    if (o < 0 || o >= 48 || seen[o]) return false;
+    seen[o] = true;
+    for (int si = 0; si < 3; ++si)
+      for (int sj = 0; sj < 9; sj += 4)
+        if (vis_col(o, si, sj, 1000) != (c < 24 ? 6 * si + c : 6 * sj + c - 24)) return false;
+  }
+  return true;
+}
+static_assert(vis_knot_major_complete(), "vis_knot_major_to_col must permute the 48 pose columns into [end][knot][6]");
 
 __device__ __forceinline__ void load_knots(const double *quat, const double *pos, int k0, const double *origin,
                                                             Knots4 &k) {

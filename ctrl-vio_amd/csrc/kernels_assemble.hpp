@@ -113,6 +113,20 @@ constexpr int VIS_SROWS = 116;
 constexpr int vis_stage_stride(int ch) { return ch + 1; }
 constexpr size_t vis_stage_bytes(int nw, int ch) { return (size_t)nw * VIS_SROWS * vis_stage_stride(ch) * sizeof(double) + (size_t)nw * 2 * ch * sizeof(int); }
 __device__ __forceinline__ f64x4 mfma16(double a, double b, f64x4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+// Knot x knot part of an IMU group tile (24 x 24, imu_col order) in the packed Hessian: both ends of an entry lie in the group's knots
+// s .. s + 3, so entry e = 24 a + b goes to unknowns (B + oa, B + ob) with B = 6 s and oa, ob constants of e.  Its packed index is
+// B (B + 1) / 2 + B (oa + 1) + oa (oa + 1) / 2 + ob: imu_tile_const(e) = (oa + 1) << 16 | oa (oa + 1) / 2 + ob, or -1 for the
+// upper triangle (oa < ob).  A lane holds the constants of its nine entries e = lane + 64 q; per group only B changes.
+__device__ __forceinline__ int imu_tile_const(int e) {
+  const int oa = imu_col(e / 24, 0, 0, 0), ob = imu_col(e % 24, 0, 0, 0);
+  return oa >= ob ? ((oa + 1) << 16) | (oa * (oa + 1) / 2 + ob) : -1;
+}
+__device__ __forceinline__ void imu_tile_add(double *Hs, int s, const int (&tc)[9], const double (&tv)[9]) {
+  const int B = 6 * s, tB = B * (B + 1) / 2;
+#pragma unroll
+  for (int q = 0; q < 9; ++q)
+    if (tc[q] >= 0) atomicAdd(&Hs[tB + (int)__umul24((unsigned)B, (unsigned)tc[q] >> 16) + (tc[q] & 0xffff)], tv[q]);
+}
 // NW = waves per workgroup: 8, or 1 in the deterministic mode (all LDS additions of a partial Hessian then come from one wave, in program
 // order).  STORE (LDS-resident windows of the product path): store-semantics tail -- with one part the workgroup finishes the window
 // itself (prior added on the way out, bias rows gathered); with several parts every part writes its packed partial Hessian to
@@ -149,20 +163,21 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
   double *gs = Hs + nHh;
   double *stage = reinterpret_cast<double *>(Hs + ((nH + 3) & ~3));     // [NW][SROWS][CHP]
   int *keys = reinterpret_cast<int *>(stage + NW * SROWS * CHP);        // [NW][2][CH]
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  // (the wave index read into a scalar register: the item walk -- ranges, descriptors, staging base, loop counters -- is then scalar code)
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int per_round = NW * nparts;
   // IMU group tiles (knot x knot part, 24 x 24 per group, overlapping between consecutive segments): the loads of this wave's
   // first NGI groups are issued before the LDS Hessian is zeroed and added right after -- at the end of the kernel they
   // were three exposed memory round trips (24 k of 243 k cycles, measured)
   constexpr int NGI = 3;
   double tv[NGI][9], tgv[NGI];   // tgv: the group's gradient entries of the knot rows (tile column 30), store-semantics tail only
-  int gs_[NGI], gb_[NGI];
+  int gs_[NGI];
   if (LDSH) {
 #pragma unroll
     for (int u = 0; u < NGI; ++u) {
       const int gi = min(part * NW + wave + u * per_round, max(ngrp - 1, 0));
       const ImuGroup grp = d.groups[grp0 + gi];
-      gs_[u] = grp.s; gb_[u] = grp.bias;
+      gs_[u] = grp.s;
       const double *tile = d.imu_tiles + (size_t)(grp0 + gi) * 1024;
 #pragma unroll
       for (int q = 0; q < 9; ++q) { const int e = lane + 64 * q; tv[u][q] = ngrp > 0 ? tile[(e / 24) * 32 + e % 24] : 0.0; }
@@ -172,16 +187,16 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
   for (int i = 2 * tid; i < ((nH + 3) & ~3); i += 2 * NT) *reinterpret_cast<double2 *>(Hs + i) = double2{0.0, 0.0};
   __syncthreads();
   if (LDSH) {
+    int tc[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) tc[q] = imu_tile_const(lane + 64 * q);
+    const int tcg = imu_col(min(lane, 23), 0, 0, 0);
 #pragma unroll
     for (int u = 0; u < NGI; ++u) {
       if (part * NW + wave + u * per_round >= ngrp) continue;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) {
-        const int e = lane + 64 * q, a = e / 24, b = e % 24;
-        const int ga = imu_col(a, gs_[u], K, gb_[u]), gb = imu_col(b, gs_[u], K, gb_[u]);
-        if (ga >= gb) atomicAdd(&Hs[ga * (ga + 1) / 2 + gb], tv[u][q]);
-      }
-      if (STORE && lane < 24) atomicAdd(&Hs[nHh + imu_col(lane, gs_[u], K, gb_[u])], tgv[u]);   // (gs = Hs + nHh)
+      const int sg = __builtin_amdgcn_readfirstlane(gs_[u]);   // (one group per wave: uniform; read here, so that the requests above stay in flight together)
+      imu_tile_add(Hs, sg, tc, tv[u]);
+      if (STORE && lane < 24) atomicAdd(&Hs[nHh + 6 * sg + tcg], tgv[u]);   // (gs = Hs + nHh)
     }
   }
   double *Js = stage + wave * SROWS * CHP;
@@ -202,9 +217,11 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
   // row rr).  The line-delay column (staged rows 98, 99) and the residual (rows 100, 101) ride on the same operand
   // values with plain FMAs: every lane multiplies its three J entries by J_ld[k] and r[k] of its own k; the four k
   // groups (lanes l15 + 16 q4) are summed with two shuffles per value at the end of the run.
+  // The tiles run over the columns in knot-major order (vis_knot_major_to_col): tile column 16 I + l15 reads the staged row of the vis_col
+  // column behind it -- the only place the order shows before the scatter; every product is the same sum in the same K order.
   int orow[3];
 #pragma unroll
-  for (int I = 0; I < 3; ++I) orow[I] = (2 * (16 * I + l15) + rr) * CHP;
+  for (int I = 0; I < 3; ++I) orow[I] = (2 * vis_knot_major_to_col(16 * I + l15) + rr) * CHP;
   const int ldrow = (98 + rr) * CHP, rrow = (100 + rr) * CHP;
   double tj[5], tg9[9], tc0 = 0.0;
   int n = 0, v0 = 0, key_i = 0, key_j = 0;
@@ -218,7 +235,7 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
     my_count = (lane < rounds && it < nvitem) ? I.count : 0;
   }
   auto item_desc = [&](int r, int &istart, int &icount) {
-    if (r < 64) { istart = __shfl(my_start, r); icount = __shfl(my_count, r); }
+    if (r < 64) { istart = __builtin_amdgcn_readlane(my_start, r); icount = __builtin_amdgcn_readlane(my_count, r); }   // (r is wave-uniform)
     else {
       const int it = it0 + r;
       const VisItem I = d.vitems[vitem0 + min(it, nvitem - 1)];
@@ -275,45 +292,62 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
     for (int I = 0; I < 3; ++I) { pl[I] = 0.0; pr[I] = 0.0; }
     pll = 0.0; prl = 0.0;
   };
-  // ---- scatter: local column -> unknown, each unordered local pair once; pairs of different local columns that map
-  //      to the same unknown (ends sharing a knot) count twice on the diagonal
+  // ---- scatter: local column c (knot-major) -> unknown 6 si + c (c < 24) or 6 sj + c - 24; each unordered local pair once, placed at
+  //      (max, min); pairs of different local columns that map to the same unknown (ends sharing a knot) count twice on the diagonal.
+  //      A run whose j end lies wholly after its i end (sj >= si + 4, wave-uniform) needs none of the per-element decisions: within an end
+  //      and from the j end's rows to the i end's columns the local order is the order of the unknowns, and no two columns meet.
   auto scatter = [&](int si, int sj) {
 #pragma unroll
+    for (int I = 0; I < 3; ++I) { pl[I] = rowgroup_sum(pl[I]); pr[I] = rowgroup_sum(pr[I]); }
+    pll = rowgroup_sum(pll); prl = rowgroup_sum(prl);
+    // unknown index and triangular row offset g (g + 1) / 2 of this lane's 3 tile columns and 12 tile rows, once per run: tile 0 lies in
+    // the i end, tile 2 in the j end, tile 1 changes ends at its local column 8 (row groups rg < 2 | rg >= 2)
+    const int bi = 6 * si, bj = 6 * sj - 24;
+    int gcol[3], grow[3][4], trow[3][4];
+    gcol[0] = bi + l15; gcol[1] = 16 + l15 + (l15 < 8 ? bi : bj); gcol[2] = bj + 32 + l15;
+#pragma unroll
     for (int I = 0; I < 3; ++I) {
-      pl[I] += __shfl_xor(pl[I], 16); pl[I] += __shfl_xor(pl[I], 32);
-      pr[I] += __shfl_xor(pr[I], 16); pr[I] += __shfl_xor(pr[I], 32);
+      const int g0 = 16 * I + q4 + (I == 0 ? bi : bj), g1 = 16 * I + q4 + (I == 2 ? bj : bi);   // rows rg = 2, 3 | rg = 0, 1
+      grow[I][0] = g1; grow[I][1] = g1 + 4; grow[I][2] = g0 + 8; grow[I][3] = g0 + 12;
+      trow[I][0] = g1 * (g1 + 1) / 2; trow[I][1] = trow[I][0] + 4 * g1 + 10;                    // t(g + 4) = t(g) + 4 g + 10
+      trow[I][2] = I == 1 ? (g0 + 8) * (g0 + 9) / 2 : trow[I][1] + 4 * g1 + 26;
+      trow[I][3] = trow[I][2] + 4 * g0 + 42;
     }
-    pll += __shfl_xor(pll, 16); pll += __shfl_xor(pll, 32);
-    prl += __shfl_xor(prl, 16); prl += __shfl_xor(prl, 32);
-    // unknown index and triangular row offset g (g + 1) / 2 of this lane's 3 tile columns and 12 tile rows, once per run
-    int gcol[3], tcol[3], grow[3][4], trow[3][4];
+    if (sj - si >= 4) {
+      int q = 0;
 #pragma unroll
-    for (int J = 0; J < 3; ++J) {
-      gcol[J] = vis_col(16 * J + l15, si, sj, P);
-      tcol[J] = gcol[J] * (gcol[J] + 1) / 2;
+      for (int I = 0; I < 3; ++I)
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        grow[J][rg] = vis_col(16 * J + (q4 + 4 * rg), si, sj, P);
-        trow[J][rg] = grow[J][rg] * (grow[J][rg] + 1) / 2;
-      }
-    }
-    int q = 0;
+        for (int J = 0; J <= I; ++J, ++q) {
 #pragma unroll
-    for (int I = 0; I < 3; ++I)
-#pragma unroll
-      for (int J = 0; J <= I; ++J, ++q) {
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int ca = 16 * I + (q4 + 4 * rg), cb = 16 * J + l15;
-          if (I == J && ca < cb) continue;
-          const int gA = grow[I][rg], gB = gcol[J];
-          double hv = acc[q][rg];
-          if (gA == gB && ca != cb) hv *= 2.0;
-          const bool ge = gA >= gB;
-          if (LDSH) atomicAdd(&Hs[(ge ? trow[I][rg] : tcol[J]) + (ge ? gB : gA)], hv);
-          else atomicAdd(&Hg[(long long)(ge ? gA : gB) * ldh + (ge ? gB : gA)], hv);
+          for (int rg = 0; rg < 4; ++rg) {
+            if (I == J && q4 + 4 * rg < l15) continue;
+            if (LDSH) atomicAdd(&Hs[trow[I][rg] + gcol[J]], acc[q][rg]);
+            else atomicAdd(&Hg[(long long)grow[I][rg] * ldh + gcol[J]], acc[q][rg]);
+          }
         }
-      }
+    } else {
+      int tcol[3];
+#pragma unroll
+      for (int J = 0; J < 3; ++J) tcol[J] = gcol[J] * (gcol[J] + 1) / 2;
+      int q = 0;
+#pragma unroll
+      for (int I = 0; I < 3; ++I)
+#pragma unroll
+        for (int J = 0; J <= I; ++J, ++q) {
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            const int ca = 16 * I + (q4 + 4 * rg), cb = 16 * J + l15;
+            if (I == J && ca < cb) continue;
+            const int gA = grow[I][rg], gB = gcol[J];
+            double hv = acc[q][rg];
+            if (gA == gB && ca != cb) hv *= 2.0;
+            const bool ge = gA >= gB;
+            if (LDSH) atomicAdd(&Hs[(ge ? trow[I][rg] : tcol[J]) + (ge ? gB : gA)], hv);
+            else atomicAdd(&Hg[(long long)(ge ? gA : gB) * ldh + (ge ? gB : gA)], hv);
+          }
+        }
+    }
     // line-delay row of the Hessian and the pose gradient (every k group holds the totals; group q4 = 0 adds them)
     if (q4 == 0) {
 #pragma unroll
@@ -344,20 +378,28 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
     if (lane < CH) { ks[lane] = key_i; ks[CH + lane] = key_j; }
     __builtin_amdgcn_wave_barrier();
     // anchor end's rotation rows: entry e = srr + 8 i (= 2 * column + residual row) = A~[rr][0..2] . GR[column][0..2]
+    // position rows: column 12 + 3 k + b (i end) = cp0[k] P~[b], column 36 + 3 k + b (j end) = -cp1[k] P~[b]
+    // All LDS reads of both expansions (rows 102..115) come before the first write (rows 0..95): the compiler keeps LDS reads behind
+    // earlier LDS writes, and read-multiply-write per row put eight LDS round trips in a row into every item.
     {
       const int rr2 = srr & 1;
       const double a0 = Js[(102 + rr2) * CHP + sc], a1 = Js[(104 + rr2) * CHP + sc], a2 = Js[(106 + rr2) * CHP + sc];   // (zero for sc >= ncur)
+      constexpr int HALF = 24 / RPP;
+      double pv[HALF], cv[2][HALF];
+#pragma unroll
+      for (int h = 0; h < HALF; ++h) {
+        const int rem = h * RPP + srr, pc = rem >> 1, kk = pc / 3, b = pc - 3 * kk;    // rem = 2 * (3 k + b) + residual row
+        pv[h] = Js[(102 + 2 * b + (rem & 1)) * CHP + sc];
+        cv[0][h] = Js[(108 + kk) * CHP + sc];
+        cv[1][h] = Js[(112 + kk) * CHP + sc];
+      }
 #pragma unroll
       for (int i = 0; i < 3; ++i) Js[(srr + 8 * i) * CHP + sc] = a0 * tg9[3 * i] + a1 * tg9[3 * i + 1] + a2 * tg9[3 * i + 2];
-    }
-    // position rows: column 12 + 3 k + b (i end) = cp0[k] P~[b], column 36 + 3 k + b (j end) = -cp1[k] P~[b]
 #pragma unroll
-    for (int e = 0; e < NEXP; ++e) {
-      constexpr int HALF = 24 / RPP;
-      const int side = e / HALF, rem = (e % HALF) * RPP + srr;    // rem = 2 * (3 k + b) + residual row
-      const int pc = rem >> 1, kk = pc / 3, b = pc - 3 * kk;
-      const double pv = Js[(102 + 2 * b + (rem & 1)) * CHP + sc], cv = Js[(108 + 4 * side + kk) * CHP + sc];
-      Js[(24 + 48 * side + rem) * CHP + sc] = side ? -(cv * pv) : cv * pv;
+      for (int e = 0; e < NEXP; ++e) {
+        const int side = e / HALF, h = e % HALF;
+        Js[(24 + 48 * side + h * RPP + srr) * CHP + sc] = side ? -(cv[1][h] * pv[h]) : cv[0][h] * pv[h];
+      }
     }
     __builtin_amdgcn_wave_barrier();
     if (r < 2) CTV_STAMP(dbg, dbi, 15, tid == 0);
@@ -421,19 +463,23 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
   CTV_STAMP(dbg, dbi, 15, tid == 0);
   // IMU group tiles: the knot x knot part (24 x 24 per group, overlapping between consecutive segments); without the LDS
   // Hessian k_assemble_imu adds them
-  for (int gi = part * NW + wave + NGI * per_round; LDSH && gi < ngrp; gi += per_round) {   // groups beyond the prefetched ones
-    const ImuGroup grp = d.groups[grp0 + gi];
-    const double *tile = d.imu_tiles + (size_t)(grp0 + gi) * 1024;
-    double tv[9];   // 24 x 24 = 9 x 64 entries: all loads in flight together
+  if (LDSH && part * NW + wave + NGI * per_round < ngrp) {   // groups beyond the prefetched ones
+    // (the entry constants are formed again here, from a lane index the compiler cannot trace back: nine registers that would otherwise
+    // stay live across the item loop)
+    const int ln = lane + opaque_zero();
+    int tc[9];
 #pragma unroll
-    for (int u = 0; u < 9; ++u) { const int e = lane + 64 * u; tv[u] = tile[(e / 24) * 32 + e % 24]; }
+    for (int q = 0; q < 9; ++q) tc[q] = imu_tile_const(ln + 64 * q);
+    const int tcg = imu_col(min(ln, 23), 0, 0, 0);
+    for (int gi = part * NW + wave + NGI * per_round; gi < ngrp; gi += per_round) {
+      const int s = __builtin_amdgcn_readfirstlane(d.groups[grp0 + gi].s);
+      const double *tile = d.imu_tiles + (size_t)(grp0 + gi) * 1024;
+      double tv[9];   // 24 x 24 = 9 x 64 entries: all loads in flight together
 #pragma unroll
-    for (int u = 0; u < 9; ++u) {
-      const int e = lane + 64 * u, a = e / 24, b = e % 24;
-      const int ga = imu_col(a, grp.s, K, grp.bias), gb = imu_col(b, grp.s, K, grp.bias);
-      if (ga >= gb) atomicAdd(&Hs[ga * (ga + 1) / 2 + gb], tv[u]);
+      for (int u = 0; u < 9; ++u) { const int e = lane + 64 * u; tv[u] = tile[(e / 24) * 32 + e % 24]; }
+      imu_tile_add(Hs, s, tc, tv);
+      if (STORE && lane < 24) atomicAdd(&gs[6 * s + tcg], tile[lane * 32 + 30]);
     }
-    if (STORE && lane < 24) atomicAdd(&gs[imu_col(lane, grp.s, K, grp.bias)], tile[lane * 32 + 30]);
   }
   __syncthreads();
   CTV_STAMP(dbg, dbi, 15, tid == 0);
@@ -444,36 +490,21 @@ template <int CH, bool LDSH, int NW = 8, bool STORE = false> __global__ __launch
       return;
     }
     double *gq = d.gS[tgset] + u0;
-    for (int i0 = tid; i0 < nHh; i0 += 4 * NT) {     // 4 entries per trip: the LDS reads first, then decode + prior + store
-      double hv4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) hv4[u] = Hs[min(i0 + NT * u, nHh - 1)];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + NT * u;
-        if (i >= nHh) continue;
-        int ga, gb;
-        packed_decode(i, tri, K6, P, ga, gb);
-        Hg[(long long)ga * ldh + gb] = hv4[u] + prior_H(d, m, ga, gb);
-      }
-    }
+    // the packed triangle by rows (wave -> rows, lane -> columns), then the line-delay row
+    for (int ga = wave; ga < K6; ga += NW)
+      for (int gb = lane; gb <= ga; gb += 64) Hg[(long long)ga * ldh + gb] = Hs[ga * (ga + 1) / 2 + gb] + prior_H(d, m, ga, gb);
+    for (int i = tid; i < K6 + 1; i += NT) { const int gb = i < K6 ? i : P - 1; Hg[(long long)(P - 1) * ldh + gb] = Hs[tri + i] + prior_H(d, m, P - 1, gb); }
     for (int i = tid; i < K6 + 1; i += NT) { const int uu = i < K6 ? i : P - 1; gq[uu] = gs[i] + prior_g(d, m, uu); }
     return;   // (the bias rows: k_bias_rows -- a gather with dependent loads wants more waves per CU than this kernel's LDS allows)
   }
-  for (int i0 = tid; LDSH && i0 < nHh; i0 += 4 * NT) {     // 4 entries per trip: the LDS reads first, then decode + store
-    double hv4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) hv4[u] = Hs[min(i0 + NT * u, nHh - 1)];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + NT * u;
-      const double hv = hv4[u];
-      if (i >= nHh || (nparts > 1 && hv == 0.0)) continue;
-      int ga, gb;
-      packed_decode(i, tri, K6, P, ga, gb);
-      if (nparts > 1) atomicAdd(&Hg[(long long)ga * ldh + gb], hv);
+  if (LDSH) {   // the packed triangle by rows (wave -> rows, lane -> columns), then the line-delay row
+    auto flush = [&](int ga, int gb, double hv) {
+      if (nparts > 1) { if (hv != 0.0) atomicAdd(&Hg[(long long)ga * ldh + gb], hv); }
       else Hg[(long long)ga * ldh + gb] = hv;  // first writer after k_zero_normal; later kernels add atomically
-    }
+    };
+    for (int ga = wave; ga < K6; ga += NW)
+      for (int gb = lane; gb <= ga; gb += 64) flush(ga, gb, Hs[ga * (ga + 1) / 2 + gb]);
+    for (int i = tid; i < K6 + 1; i += NT) flush(P - 1, i < K6 ? i : P - 1, Hs[tri + i]);
   }
   CTV_STAMP(dbg, dbi, 15, tid == 0);
   for (int i = tid; i < K6 + 1; i += NT) {

@@ -948,17 +948,6 @@ __device__ __forceinline__ void chol16_dpp(double (&v)[16], int nreal, int &bad)
   if (!(last - last == 0.0)) bad = 1;
 }
 
-// the sum of a value over the four 16-lane row groups of the wave, in every lane (the tree of two __shfl_xor steps, without the LDS crossbar)
-__device__ __forceinline__ double rowgroup_sum(double p) {
-  unsigned lo = (unsigned)__double2loint(p), hi = (unsigned)__double2hiint(p);
-  const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);   // [0] = {g0, g0, g2, g2}, [1] = {g1, g1, g3, g3}
-  const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  const double s = __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
-  lo = (unsigned)__double2loint(s); hi = (unsigned)__double2hiint(s);
-  const auto c = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);   // [0] = {lower half, lower half}, [1] = {upper, upper}
-  const auto e = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double((int)e[0], (int)c[0]) + __hiloint2double((int)e[1], (int)c[1]);
-}
 // acc += sum_k t[lane k of this lane's row] * lk[k], k = K .. 15
 template <int K> __device__ __forceinline__ void dpp_dot16(double &acc, double t, const double (&lk)[16]) {
   if constexpr (K < 16) {
