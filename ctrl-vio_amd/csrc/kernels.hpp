@@ -48,6 +48,9 @@ __device__ __forceinline__ int lin_target(const Lm &lm, int mode) { return mode 
 
 // (defined with the Schur / step kernels, used by k_pass_end)
 __device__ __forceinline__ double grad_norm_entry(const Dev &d, const WinMeta &m, int w, int j, const double *g, bool at_cand);
+__device__ __forceinline__ double grad_norm_rot(const Dev &d, const WinMeta &m, int k, const double *g, bool at_cand);
+__device__ __forceinline__ bool grad_norm_is_rot(const WinMeta &m, int j);
+__device__ __forceinline__ double grad_norm_other(const Dev &d, const WinMeta &m, int w, int j, const double *g, bool at_cand);
 __device__ __forceinline__ void begin_iteration(const Dev &d, int w, int *s_go);
 
 // a lane's double as a wave-uniform value (two v_readlane_b32)

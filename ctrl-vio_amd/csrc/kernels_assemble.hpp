@@ -894,26 +894,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 // Jacobi scaling (computed once, at iteration 0: Ceres jacobi_scaling), gradient max-norm of
 // x - Plus(x, -g) (Ceres gradient_max_norm) and |x|^2 of the reduced program.
 // |x - Plus(x, -g)| of unknown j (Ceres gradient_max_norm: ambient difference for a rotation block, the box of the line delay)
-__device__ __forceinline__ double grad_norm_entry(const Dev &d, const WinMeta &m, int w, int j, const double *g, bool at_cand) {
-  const double *squat = at_cand ? d.cquat : d.quat, *sld = at_cand ? d.cld : d.ld;
-  const int K6 = 6 * m.K;
-  if (j < K6) {
-    const int k = j / 6, c = j % 6;
-    if (c == 0) {  // rotation block: ambient difference q - q*exp(-g)
-      const double *q = squat + 4 * (m.knot0 + k);
-      const Q4 q0 = qmk(q[0], q[1], q[2], q[3]);
-      const Q4 q1 = qmul(q0, so3_exp(mk(-g[j], -g[j + 1], -g[j + 2])));
-      return fmax(fmax(fabs(q0.x - q1.x), fabs(q0.y - q1.y)), fmax(fabs(q0.z - q1.z), fabs(q0.w - q1.w)));
-    }
-    return c >= 3 ? fabs(g[j]) : 0.0;
-  }
+// (in two parts, so that a kernel that walks the unknowns in a loop can take the rotation blocks -- the quaternion product and its series -- outside it)
+__device__ __forceinline__ double grad_norm_rot(const Dev &d, const WinMeta &m, int k, const double *g, bool at_cand) {
+  // rotation block of knot k (unknown 6 k): ambient difference q - q*exp(-g)
+  const double *q = (at_cand ? d.cquat : d.quat) + 4 * (m.knot0 + k);
+  const int j = 6 * k;
+  const Q4 q0 = qmk(q[0], q[1], q[2], q[3]);
+  const Q4 q1 = qmul(q0, so3_exp(mk(-g[j], -g[j + 1], -g[j + 2])));
+  return fmax(fmax(fabs(q0.x - q1.x), fabs(q0.y - q1.y)), fmax(fabs(q0.z - q1.z), fabs(q0.w - q1.w)));
+}
+__device__ __forceinline__ bool grad_norm_is_rot(const WinMeta &m, int j) { return j < 6 * m.K && j % 6 == 0; }
+__device__ __forceinline__ double grad_norm_other(const Dev &d, const WinMeta &m, int w, int j, const double *g, bool at_cand) {   // (every unknown but a rotation block's first)
+  if (j < 6 * m.K) return j % 6 >= 3 ? fabs(g[j]) : 0.0;
   if (j == m.P - 1) {
-    const double ld = sld[w];
+    const double ld = (at_cand ? d.cld : d.ld)[w];
     double nl = ld - g[j];
     if (!m.fix_ld) nl = fmin(fmax(nl, m.ld_lo), m.ld_hi);
     return fabs(ld - nl);
   }
   return fabs(g[j]);
+}
+__device__ __forceinline__ double grad_norm_entry(const Dev &d, const WinMeta &m, int w, int j, const double *g, bool at_cand) {
+  return grad_norm_is_rot(m, j) ? grad_norm_rot(d, m, j / 6, g, at_cand) : grad_norm_other(d, m, w, j, g, at_cand);
 }
 
 // After the first linearisation of a solve (LIN_AT_X): Jacobi scaling (computed once, at iteration 0: Ceres jacobi_scaling) and the

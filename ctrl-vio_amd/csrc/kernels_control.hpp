@@ -26,6 +26,13 @@ __global__ void k_lm_init(Dev d, double mu, int keep_scale) {
 
 // ---- interpolation of the next trial step (Ceres polynomial.cc: FindInterpolatingPolynomial / MinimizePolynomial)
 struct LsSample { double x, v, g; };
+// The arrays of the interpolation, used by ONE lane of k_pass_end: kept in LDS (632 B per workgroup).  As private arrays they were thread 0's
+// 384 B of scratch and 72 B x 256 threads of compiler-promoted LDS, and set the register count of a kernel whose other 255 threads only reduce and copy.
+struct LsWork {
+  double A[6][7], coef[6], der[5], roots[4];   // ls_minimize_interpolating
+  double q[5], zr[4], zi[4];                   // ls_root_real_parts
+  LsSample sp[3];                              // lm_decide
+};
 __device__ inline double ls_poly_eval(const double *p, int n, double x) {
   double v = 0;
   for (int i = 0; i < n; ++i) v = v * x + p[i];
@@ -33,7 +40,7 @@ __device__ inline double ls_poly_eval(const double *p, int n, double x) {
 }
 __device__ inline double ls_ipow(double x, int e) { double r = 1.0; for (int i = 0; i < e; ++i) r *= x; return r; }
 // real parts of all (complex) roots of a polynomial of degree <= 4, coefficients highest power first
-__device__ inline int ls_root_real_parts(const double *p_in, int n, double *re) {
+__device__ __forceinline__ int ls_root_real_parts(const double *p_in, int n, double *re, LsWork &ws) {
   while (n > 0 && p_in[0] == 0.0) { ++p_in; --n; }
   const int deg = n - 1;
   if (deg <= 0) return 0;
@@ -46,12 +53,15 @@ __device__ inline int ls_root_real_parts(const double *p_in, int n, double *re) 
     } else { re[0] = re[1] = -b / (2.0 * a); }
     return 2;
   }
-  double q[5], zr[4], zi[4];
+  double *q = ws.q, *zr = ws.zr, *zi = ws.zi;
   for (int i = 0; i <= deg; ++i) q[i] = p_in[i] / p_in[0];
   double rad = 0;
   for (int i = 1; i <= deg; ++i) rad = fmax(rad, fabs(q[i]));
   rad = 1.0 + rad;
-  for (int k = 0; k < deg; ++k) { const double ang = 2.0 * 3.14159265358979323846 * k / deg + 0.4; zr[k] = 0.5 * rad * cos(ang); zi[k] = 0.5 * rad * sin(ang); }
+  // (deg is 3 or 4 here.  Unrolled: as a loop, the literals of the sine and cosine are hoisted out of it and spilled across it)
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < deg) { const double ang = 2.0 * 3.14159265358979323846 * k / deg + 0.4; zr[k] = 0.5 * rad * cos(ang); zi[k] = 0.5 * rad * sin(ang); }
   for (int it = 0; it < 500; ++it) {   // Durand-Kerner
     double change = 0;
     for (int k = 0; k < deg; ++k) {
@@ -74,9 +84,9 @@ __device__ inline int ls_root_real_parts(const double *p_in, int n, double *re) 
   for (int k = 0; k < deg; ++k) re[k] = zr[k];
   return deg;
 }
-__device__ inline double ls_minimize_interpolating(const LsSample *s, int ns, double x_min, double x_max) {
+__device__ __forceinline__ double ls_minimize_interpolating(const LsSample *s, int ns, double x_min, double x_max, LsWork &ws) {
   const int nc = 2 * ns, deg = nc - 1;
-  double A[6][7], coef[6], der[5], roots[4];
+  double (*A)[7] = ws.A, *coef = ws.coef, *der = ws.der, *roots = ws.roots;
   for (int i = 0; i < ns; ++i) {
     for (int j = 0; j <= deg; ++j) A[2 * i][j] = ls_ipow(s[i].x, deg - j);
     A[2 * i][nc] = s[i].v;
@@ -100,7 +110,7 @@ __device__ inline double ls_minimize_interpolating(const LsSample *s, int ns, do
   v = ls_poly_eval(coef, nc, x_min); if (v < best) { best = v; best_x = x_min; }
   v = ls_poly_eval(coef, nc, x_max); if (v < best) { best = v; best_x = x_max; }
   for (int i = 0; i < nc - 1; ++i) der[i] = (nc - 1 - i) * coef[i];
-  const int nr = ls_root_real_parts(der, nc - 1, roots);
+  const int nr = ls_root_real_parts(der, nc - 1, roots, ws);
   for (int i = 0; i < nr; ++i) {
     if (roots[i] < x_min || roots[i] > x_max) continue;
     v = ls_poly_eval(coef, nc, roots[i]);
@@ -157,7 +167,7 @@ __global__ __launch_bounds__(64) void k_initial_cost(Dev d, int as_candidate) {
 }
 
 // Decision of one window after its candidate has been evaluated (lane 0 of k_lm_control): returns 1 when the candidate is accepted.
-__device__ inline int lm_decide(const Dev &d, Lm &lm, double cand_cost, double gd, bool have_grad) {
+__device__ __forceinline__ int lm_decide(const Dev &d, Lm &lm, double cand_cost, double gd, bool have_grad, LsWork &ws) {
   lm.cand_cost = cand_cost;
   lm.cand_gd = gd;
   lm.have_grad = have_grad ? 1 : 0;
@@ -175,12 +185,12 @@ __device__ inline int lm_decide(const Dev &d, Lm &lm, double cand_cost, double g
       if (!valid) {
         step = fmin(fmax(lm.ls_cur_x * 0.5, lo), hi);
       } else {
-        LsSample sp[3];
+        LsSample *sp = ws.sp;
         int ns = 0;
         sp[ns++] = LsSample{0.0, lm.cost, lm.ls_gd0};
         sp[ns++] = LsSample{lm.ls_cur_x, lm.ls_cur_v, lm.ls_cur_g};
         if (lm.ls_prev_valid) sp[ns++] = LsSample{lm.ls_prev_x, lm.ls_prev_v, lm.ls_prev_g};
-        step = ls_minimize_interpolating(sp, ns, lo, hi);
+        step = ls_minimize_interpolating(sp, ns, lo, hi, ws);
       }
       if (step * lm.ls_dmax < 1e-9) { lm.ls_active = 2; lm.alpha = 1.0; lm.nls_steps += lm.ls_iters; return 0; }   // min_line_search_step_size
       lm.ls_prev_x = lm.ls_cur_x; lm.ls_prev_v = lm.ls_cur_v; lm.ls_prev_g = lm.ls_cur_g; lm.ls_prev_valid = valid ? 1 : 0;
@@ -221,12 +231,13 @@ __device__ inline int lm_decide(const Dev &d, Lm &lm, double cand_cost, double g
 //     contracted into [1e-3, 0.6] x alpha, and the window stays in the search (ls_active = 1);
 //   * ParameterToleranceReached / FunctionToleranceReached / IsStepSuccessful / LM radius update; on acceptance the speculative
 //     normal equations become the current ones (cur ^= 1).
-__global__ __launch_bounds__(256) void k_pass_end(Dev d) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_pass_end(Dev d) {
   const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   Lm &lm = d.lm[w];
   __shared__ double s_red[4];
   __shared__ unsigned long long s_gmax[4];
   __shared__ int s_acc, s_go;
+  __shared__ LsWork s_ls;
   const WinMeta &m = d.wins[w];
   if (!lm.status && lm.step_valid) {   // (uniform: the window evaluated a candidate this pass)
     const bool have_grad = !lin_cost_only(lm, LIN_SPEC, d.prm);
@@ -234,9 +245,13 @@ __global__ __launch_bounds__(256) void k_pass_end(Dev d) {
     const double *gc = d.gS[tg] + m.u0, *dl = d.delta + m.u0;
     // gradient max-norm at the candidate and g(candidate) . delta: block reductions in a fixed order (max is exact in any order)
     double gd = 0.0, gm = 0.0;
-    if (have_grad)
+    if (have_grad) {
       for (int j = tid; j < m.N; j += 256)
-        if (d.active[m.u0 + j]) { gd += gc[j] * dl[j]; gm = fmax(gm, grad_norm_entry(d, m, w, j, gc, true)); }
+        if (d.active[m.u0 + j]) { gd += gc[j] * dl[j]; if (!grad_norm_is_rot(m, j)) gm = fmax(gm, grad_norm_other(d, m, w, j, gc, true)); }
+      // the rotation blocks OUTSIDE the loop, one knot per thread (K <= 170: P = 6 K + 6 F + 1 <= 1024, ctvio.h): inside it the compiler hoists the
+      // literals of the series out of the loop and spills them across it
+      if (tid < m.K && d.active[m.u0 + 6 * tid]) gm = fmax(gm, grad_norm_rot(d, m, tid, gc, true));
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) { gd += __shfl_xor(gd, off); gm = fmax(gm, __shfl_xor(gm, off)); }
     if (lane == 0) { s_red[wave] = gd; s_gmax[wave] = (unsigned long long)__double_as_longlong(gm); }
@@ -246,15 +261,16 @@ __global__ __launch_bounds__(256) void k_pass_end(Dev d) {
       if (lane == 0) {
         const double gdt = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
         lm.cand_gmax_bits = max(max(s_gmax[0], s_gmax[1]), max(s_gmax[2], s_gmax[3]));   // (non-negative doubles order like their bit patterns)
-        s_acc = lm_decide(d, lm, cand_cost, lm.ls_on ? gdt : 0.0, have_grad);
+        s_acc = lm_decide(d, lm, cand_cost, lm.ls_on ? gdt : 0.0, have_grad, s_ls);
       }
     }
     __syncthreads();
     if (s_acc) {   // the accepted candidate becomes the current state (the reference: Ceres writes through the parameter pointers)
-      for (int t = tid; t < 4 * m.K; t += 256) d.quat[4 * m.knot0 + t] = d.cquat[4 * m.knot0 + t];
-      for (int t = tid; t < 3 * m.K; t += 256) d.pos[3 * m.knot0 + t] = d.cpos[3 * m.knot0 + t];
-      for (int t = tid; t < 6 * m.F; t += 256) d.bias[6 * m.bias0 + t] = d.cbias[6 * m.bias0 + t];
-      for (int t = tid; t < m.L; t += 256) d.rho[m.lm0 + t] = d.crho[m.lm0 + t];
+      const int t0 = tid + opaque_zero();   // (keeps the copy's addresses from being formed before the decision and held, spilled, across it)
+      for (int t = t0; t < 4 * m.K; t += 256) d.quat[4 * m.knot0 + t] = d.cquat[4 * m.knot0 + t];
+      for (int t = t0; t < 3 * m.K; t += 256) d.pos[3 * m.knot0 + t] = d.cpos[3 * m.knot0 + t];
+      for (int t = t0; t < 6 * m.F; t += 256) d.bias[6 * m.bias0 + t] = d.cbias[6 * m.bias0 + t];
+      for (int t = t0; t < m.L; t += 256) d.rho[m.lm0 + t] = d.crho[m.lm0 + t];
       if (tid == 0) d.ld[w] = d.cld[w];
     }
     __syncthreads();

@@ -1524,8 +1524,11 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
 // ceres_local_param.h:137-145; additive elsewhere; the line delay projected on its box, trajectory_estimator.cpp:316-317), |step|^2 and
 // |x|^2 of the reduced program (fixed-order block reductions, no atomics) and the knot-pair constants of the candidate for the
 // linearisation that follows.  Windows inside the line search skip the solve part: their step is the same, only alpha changed.
-template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev d) {
+// <4> (one 256-thread workgroup per window, the large batches' shape) is held to 64 registers: eight waves per SIMD, so that 2048 windows are
+// resident at once -- the kernel is a chain of dependent round trips (metadata -> W -> reduce -> store) that only other waves can fill.
+template <int NWV> __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(NWV == 4 ? 8 : 4))) void k_step_finish(Dev d) {
   constexpr int NT = 64 * NWV;
+  constexpr int STEP_NC = 1;   // columns per lane and trip of the W loop (2: the 8 x 2 values and their sums do not fit 64 registers)
   const int w = blockIdx.x;
   // the pass's "windows that start another pass" counter (k_pass_end adds to it, several launches later): cleared here instead of by a
   // memset node of its own
@@ -1533,7 +1536,11 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
   Lm &lm = d.lm[w];
   if (lm.status) return;
   const WinMeta &m = d.wins[w];
-  const int P = m.P, L = m.L, N = m.N, u0 = m.u0, lm0 = m.lm0, ldw = m.ldw;
+  // (window constants through v_readfirstlane: the store above keeps the compiler from reading them with scalar loads, and as per-lane copies
+  //  they are live across the whole kernel)
+  auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+  const int P = uni(m.P), L = uni(m.L), N = uni(m.N), u0 = uni(m.u0), lm0 = uni(m.lm0), ldw = uni(m.ldw);
+  const int K = uni(m.K), F = uni(m.F), knot0 = uni(m.knot0), bias0 = uni(m.bias0), cur = uni(lm.cur);
   extern __shared__ __attribute__((aligned(16))) double xs[];   // [P] pose step
   __shared__ double red[NWV], red_gd[NWV], red_dm[NWV];
   __shared__ int bad, s_go;
@@ -1542,16 +1549,18 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
     if (tid == 0) s_go = lm.step_valid;
   } else {
   double *x = d.delta + u0;
-  const double *g = d.gS[d.lm[w].cur] + u0, *dd = d.dd + u0;
-  const double *Wp = d.WS[d.lm[w].cur] + m.W0;
+  const double *g = d.gS[cur] + u0, *dd = d.dd + u0;
+  const double *Wp = d.WS[cur] + m.W0;
   for (int i = tid; i < P; i += NT) xs[i] = x[i];
   if (tid == 0) bad = 0;
   __syncthreads();
   // delta_rho = -(g_rho + W_r . delta_p) / (Hll + D) of the landmark of row r: a wave takes 8 ROWS of W per pass.  The rows are sorted by knot
-  // span (host_pack.hpp: plan_sparsity), so the 8 rows of a pass share most of their columns: only the union of their spans' knot columns and the
-  // line-delay column are read (config 2: ~100 of 145 columns; K = 64: ~110 of 385) -- the rest of a row is zero and never touched.
+  // span (host_pack.hpp: plan_sparsity), so the 8 rows of a pass share most of their columns: the pass walks the union of their spans' knot
+  // columns and the line-delay column (config 2: ~100 of 145 columns; K = 64: ~110 of 385), and each row is READ over its own span only: a column
+  // outside it is clamped into it (a duplicate address: no extra sector) and its product masked -- the rest of a row is zero and never touched.
+  // The row bases and spans are wave-uniform (scalar registers); a lane's address is a 32-bit byte offset from its row's base.
   const int32_t *klo = d.lm_klo + lm0, *khi = d.lm_khi + lm0, *lat = d.lm_at + lm0;
-  for (int l0 = 8 * wave; l0 < L; l0 += 8 * NWV) {
+  for (int l0 = 8 * __builtin_amdgcn_readfirstlane(wave); l0 < L; l0 += 8 * NWV) {
     double acc8[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc8[u] = 0.0;
@@ -1560,45 +1569,59 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
     const int lmk = lat[lrow];
     const double g_l = g[P + lmk], dinv_l = d.dinv[lm0 + lrow];
     const bool act_l = d.active[u0 + P + lmk] != 0;
-    int kmin = klo[lrow], kmax = khi[lrow];      // (a row without observations: klo = K, khi = -1 -- it widens nothing)
+    const int kmin = klo[lrow], kmax = khi[lrow];
+    int lo[8], hi[8], c_lo = 6 * K, c_hi = 0;  // row u's columns [lo, hi); their union (a row without observations: klo = K, khi = -1 -- it widens nothing)
 #pragma unroll
-    for (int off = 8; off < 64; off <<= 1) { kmin = min(kmin, __shfl_xor(kmin, off)); kmax = max(kmax, __shfl_xor(kmax, off)); }
-    const int c_lo = __builtin_amdgcn_readfirstlane(6 * kmin), nkc = __builtin_amdgcn_readfirstlane(max(6 * (kmax + 1) - 6 * kmin, 0));
+    for (int u = 0; u < 8; ++u) {
+      const int a = 6 * __builtin_amdgcn_readlane(kmin, 8 * u), b = 6 * __builtin_amdgcn_readlane(kmax, 8 * u) + 6;
+      c_lo = min(c_lo, a); c_hi = max(c_hi, b);
+      lo[u] = b > a ? a : P - 1; hi[u] = b > a ? b : P;   // (no observation: the line-delay column alone)
+    }
+    const int nkc = max(c_hi - c_lo, 0);
     const int NCB = nkc + 1;                     // compact columns: the knot columns of the union, then the line delay
-    for (int i0 = 0; i0 < NCB; i0 += 128) {
-      double wv[8][2];
-      int col[2];
+    for (int i0 = 0; i0 < NCB; i0 += 64 * STEP_NC) {
+      double wv[8][STEP_NC];
+      int col[STEP_NC];
+      unsigned inspan = 0u;                      // bit STEP_NC u + k: column k of this lane lies in row u's span
 #pragma unroll
-      for (int k = 0; k < 2; ++k) { const int cc = min(i0 + lane + 64 * k, NCB - 1); col[k] = cc < nkc ? c_lo + cc : P - 1; }
+      for (int k = 0; k < STEP_NC; ++k) { const int cc = min(i0 + lane + 64 * k, NCB - 1); col[k] = cc < nkc ? c_lo + cc : P - 1; }
 #pragma unroll
-      for (int u = 0; u < 8; ++u)
+      for (int u = 0; u < 8; ++u) {
+        const char *row = reinterpret_cast<const char *>(Wp + (long long)min(l0 + u, L - 1) * ldw);   // (uniform)
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; k < STEP_NC; ++k) {
           // clamped, unconditional loads (a predicated load compiles to branch + load + s_waitcnt: one round trip EACH);
-          // out-of-range columns are masked through xi below, out-of-range rows are never written
-          const int l = min(l0 + u, L - 1);
-          wv[u][k] = Wp[(long long)l * ldw + col[k]];
+          // out-of-range columns are masked through xi below, out-of-span columns right here, out-of-range rows are never written
+          const int cu = col[k] == P - 1 ? col[k] : min(max(col[k], lo[u]), hi[u] - 1);
+          wv[u][k] = *reinterpret_cast<const double *>(row + 8u * (unsigned)cu);
+          inspan |= (cu == col[k] ? 1u : 0u) << (STEP_NC * u + k);
         }
+      }
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {
+      for (int k = 0; k < STEP_NC; ++k) {
         const double xi = (i0 + lane + 64 * k < NCB) ? xs[col[k]] : 0.0;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) acc8[u] += wv[u][k] * xi;
+        for (int u = 0; u < 8; ++u) acc8[u] += wv[u][k] * ((inspan >> (STEP_NC * u + k)) & 1u ? xi : 0.0);
       }
     }
     // 8 row sums over 64 lanes with 10 shuffles: each butterfly step halves the rows a lane carries (bit 5 of the lane
     // picks rows 0-3 / 4-7, bit 4 the pair, bit 3 the row), then three plain steps; row u = lane >> 3 ends up in lane 8u
-    const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+    const int ln = lane + opaque_zero();   // (the shuffles' lane addresses are formed here, per pass, instead of being held across the W loop)
+    auto shx = [&](double v, int off) {    // __shfl_xor(v, off), addressed from ln
+      const int a = (ln ^ off) << 2;
+      return __hiloint2double(__builtin_amdgcn_ds_bpermute(a, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(a, __double2loint(v)));
+    };
+    const bool b5 = ln & 32, b4 = ln & 16, b3 = ln & 8;
     double v4[4], v2[2];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) v4[q] = (b5 ? acc8[4 + q] : acc8[q]) + __shfl_xor(b5 ? acc8[q] : acc8[4 + q], 32);
+    for (int q = 0; q < 4; ++q) v4[q] = (b5 ? acc8[4 + q] : acc8[q]) + shx(b5 ? acc8[q] : acc8[4 + q], 32);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) v2[q] = (b4 ? v4[2 + q] : v4[q]) + __shfl_xor(b4 ? v4[q] : v4[2 + q], 16);
-    double v1 = (b3 ? v2[1] : v2[0]) + __shfl_xor(b3 ? v2[0] : v2[1], 8);
-    v1 += __shfl_xor(v1, 4);
-    v1 += __shfl_xor(v1, 2);
-    v1 += __shfl_xor(v1, 1);
-    if ((lane & 7) == 0 && l0 + (lane >> 3) < L) x[P + lmk] = act_l ? (-g_l - v1) * dinv_l : 0.0;
+    for (int q = 0; q < 2; ++q) v2[q] = (b4 ? v4[2 + q] : v4[q]) + shx(b4 ? v4[q] : v4[2 + q], 16);
+    double v1 = (b3 ? v2[1] : v2[0]) + shx(b3 ? v2[0] : v2[1], 8);
+    v1 += shx(v1, 4);
+    v1 += shx(v1, 2);
+    v1 += shx(v1, 1);
+    if ((ln & 7) == 0 && l0 + (ln >> 3) < L) x[P + lmk] = act_l ? (-g_l - v1) * dinv_l : 0.0;
   }
   __syncthreads();
   double mc = 0.0, gd = 0.0, dm = 0.0;   // model change; g . delta and |delta|_inf for the projected line search
@@ -1634,10 +1657,13 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
     const double *dl = d.delta + u0;
     const uint8_t *act = d.active + u0;
     double step2 = 0.0, x2 = 0.0;
-    const int nst = m.K + m.F + L + 1;
-    for (int t = tid; t < nst; t += NT) {
-      if (t < m.K) {
-        const int gk = m.knot0 + t;
+    const int nst = K + F + L + 1;
+    // (the knots OUTSIDE the loop, one per thread -- K <= 170 < NT: P = 6 K + 6 F + 1 <= 1024, ctvio.h -- and before the thread's other terms, as
+    //  the loop had them: inside it the compiler hoists the literals of so3_exp's series out of the loop and keeps them live, or spilled, across it)
+    {
+      const int t = tid;
+      if (t < K) {
+        const int gk = knot0 + t;
         const bool ar = act[6 * t] != 0, ap = act[6 * t + 3] != 0;
         const Q4 q0 = qmk(d.quat[4 * gk], d.quat[4 * gk + 1], d.quat[4 * gk + 2], d.quat[4 * gk + 3]);
         Q4 q1 = q0;
@@ -1652,16 +1678,19 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
           d.cpos[3 * gk + c] = p1;
           if (ap) { step2 += (p1 - p0) * (p1 - p0); x2 += p1 * p1; }
         }
-      } else if (t < m.K + m.F) {
-        const int f = t - m.K, gf = m.bias0 + f, u = 6 * m.K + 6 * f;
+      }
+    }
+    for (int t = tid < K ? tid + NT : tid; t < nst; t += NT) {
+      if (t < K + F) {
+        const int f = t - K, gf = bias0 + f, u = 6 * K + 6 * f;
         for (int c = 0; c < 6; ++c) {
           const bool a = act[u + c] != 0;
           const double b0 = d.bias[6 * gf + c], b1 = a ? b0 + al * dl[u + c] : b0;
           d.cbias[6 * gf + c] = b1;
           if (a) { step2 += (b1 - b0) * (b1 - b0); x2 += b1 * b1; }
         }
-      } else if (t < m.K + m.F + L) {
-        const int l = t - m.K - m.F;
+      } else if (t < K + F + L) {
+        const int l = t - K - F;
         const bool a = act[P + l] != 0;
         const double r0 = d.rho[lm0 + l], r1 = a ? r0 + al * dl[P + l] : r0;
         d.crho[lm0 + l] = r1;
@@ -1688,8 +1717,8 @@ template <int NWV> __global__ __launch_bounds__(64 * NWV) void k_step_finish(Dev
     }
   }
   // ---- knot-pair constants of the candidate (shared by all residual blocks of the linearisation that follows)
-  for (int t = tid; t < m.K - 1; t += NT) {
-    const int gk = m.knot0 + t;
+  if (tid < K - 1) {   // (K - 1 < NT)
+    const int gk = knot0 + tid;
     knot_pair_const(d.cquat + 4 * gk, d.cquat + 4 * gk + 4, d.lkd + 3 * gk, d.kjri + 9 * gk);
   }
 }
