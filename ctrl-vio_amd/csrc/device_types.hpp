@@ -200,7 +200,7 @@ struct CholTilesLds {                        // k_cholesky_tiles (a barrier per 
         bytes((size_t)(park + 12 * 64 + 2) * sizeof(double)) {}
 };
 struct CholFlowLds {                         // k_cholesky_flow (flags, three panel buffers)
-  static constexpr int NPB = 3, NFLAG = 80;  // panel buffers; ints of flags: fail, F_inv, F_row, F_park, done_E at 16 each
+  static constexpr int NPB = 3, NFLAG = 96;  // panel buffers; ints of flags: fail (and x_known behind it), F_inv, F_row, F_park, done_E, t_count at 16 each
   int Id, Li, Ls, Pn, tv, xs, flags;
   size_t bytes;
   constexpr explicit CholFlowLds(int ntr)
@@ -211,7 +211,7 @@ struct CholFlowLds {                         // k_cholesky_flow (flags, three pa
         tv(Pn + NPB * ntr * CHOL_TS),     // [16 ntr] y, then the running right-hand side of the back-substitution
         xs(tv + 16 * ntr),                // [16 ntr] solution
         flags(xs + 16 * ntr),             // int[NFLAG]
-        bytes((size_t)(flags + NFLAG / 2 + 8) * sizeof(double)) {}
+        bytes((size_t)(flags + NFLAG / 2) * sizeof(double)) {}   // (t_count took the eight spare doubles: the bytes of a launch have not moved)
 };
 static_assert(CholTilesLds(14).bytes <= CHOL_LDS_LIMIT && CholFlowLds(14).bytes <= CHOL_LDS_LIMIT, "P = 223 (14 tile rows) must fit the LDS of a CU");
 

@@ -983,14 +983,22 @@ struct CholWindow {
     return from_h && !(tiles.nz_row(a) && tiles.nz_col(b));
   }
 };
+// The activity bytes are requested (chol_active_request) and turned into masks (chol_active_masks) in two steps, so that a kernel can put its
+// tile loads between the two: the ballots are the first use of the bytes, and a wait for them waits for every load issued before it.
+__device__ __forceinline__ void chol_active_request(int (&ab)[4], const Dev &d, int u0, int P, int lane) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ab[k] = d.active[u0 + min(lane + 64 * k, P - 1)];
+}
+__device__ __forceinline__ void chol_active_masks(CholActive &act, const int (&ab)[4], int P, int lane) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) act.w[k] = __ballot(lane + 64 * k < P && ab[k] != 0);
+}
 __device__ __forceinline__ CholWindow chol_window(const Dev &d, const WinMeta &m, const Lm &lm, int lane) {
   CholWindow cw = {d.S + m.H0, d.HppS[lm.cur] + m.H0, d.rhs + m.p0, d.dd + m.u0, m.P, m.ldh, 6 * m.K, d.schur_plain_in_H != 0, {{0ull, 0ull, 0ull, 0ull}}};
   if (cw.from_h) {
-    unsigned char ab[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) ab[k] = d.active[m.u0 + min(lane + 64 * k, cw.P - 1)];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) cw.act.w[k] = __ballot(lane + 64 * k < cw.P && ab[k] != 0);
+    int ab[4];
+    chol_active_request(ab, d, m.u0, cw.P, lane);
+    chol_active_masks(cw.act, ab, cw.P, lane);
   }
   return cw;
 }
@@ -1010,12 +1018,14 @@ __device__ __forceinline__ void chol_tile_fetch(f64x4 &t, const CholWindow &cw, 
     t[r] = src[(long long)rc * cw.ldh + min(16 * b + l15, rc)];
   }
 }
-__device__ __forceinline__ void chol_tile_fixup(f64x4 &t, const CholWindow &cw, int a, int b, int q4, int l15) {
+// The two values a fix-up may need from memory, both at the tile's column col = 16 b + l15: the damping dd[col] (plain DIAGONAL tiles) and the
+// reduced rhs y[col] (tile row ip).  chol_tile_fixup takes them as arguments, so that a caller can request them with its tile loads.
+__device__ __forceinline__ int chol_fix_col(const CholWindow &cw, int b, int l15) { return min(16 * b + l15, cw.P - 1); }
+__device__ __forceinline__ void chol_tile_fixup(f64x4 &t, const CholWindow &cw, int a, int b, int q4, int l15, double dd_col, double y_col) {
   const int P = cw.P, ip = P / 16, col = 16 * b + l15;
   if (cw.plain(a, b)) {   // a tile without Schur products, straight from Hpp: damping and fixed unknowns here
     const int a_j = cw.act.bit(col);
-    double ddiag = 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window; one L2 round trip for its wave)
-    if (a == b) ddiag = cw.dd[min(col, P - 1)];
+    const double ddiag = a == b ? dd_col : 0.0;   // (a diagonal tile among them: a few bias-bias blocks per window)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 16 * a + q4 + 4 * r;
@@ -1027,13 +1037,19 @@ __device__ __forceinline__ void chol_tile_fixup(f64x4 &t, const CholWindow &cw, 
     for (int r = 0; r < 4; ++r) t[r] = (col <= 16 * a + q4 + 4 * r) ? t[r] : 0.0;
   }
   if (a == ip) {            // tile row of the rhs row P; identity beyond it
-    const double yv = cw.y[min(col, P - 1)];
+    const double yv = y_col;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 16 * ip + q4 + 4 * r;
       t[r] = row < P ? t[r] : (row == P ? (col < P ? yv : 0.0) : (row == col ? 1.0 : 0.0));
     }
   }
+}
+__device__ __forceinline__ void chol_tile_fixup(f64x4 &t, const CholWindow &cw, int a, int b, int q4, int l15) {   // the loads here: one L2 round trip each
+  double dd_col = 0.0, y_col = 0.0;
+  if (a == b && cw.plain(a, b)) dd_col = cw.dd[chol_fix_col(cw, b, l15)];
+  if (a == cw.P / 16) y_col = cw.y[chol_fix_col(cw, b, l15)];
+  chol_tile_fixup(t, cw, a, b, q4, l15, dd_col, y_col);
 }
 __device__ __forceinline__ void chol_tile_to_lds(double *blk, const f64x4 &t, int q4, int l15) {
 #pragma unroll
@@ -1095,35 +1111,47 @@ __device__ __forceinline__ void chol_last_block_x(const double *Li, const double
 // no LDS round trip on the chain); the owners of the other tiles (b, j) subtract their parts from t_j in LDS meanwhile.  Every tile has a single
 // owner -- no atomics anywhere, the summation order is fixed.  (x_b by one wave, barrier, the updates, barrier: 19.7 k of a factorisation's
 // 143 k cycles.)  Every wave of the workgroup that is still running calls this.
+// The two steps, written once for both schedules (the arithmetic, and so the bits of x, are the same whoever runs them and whenever):
+// the chain: tile (b, b - 1) = L finishes t_{b-1} and gives x_{b-1}; lk = column l15 of L_{b-1,b-1}^-1 (Li[b - 1][kk * 17 + l15])
+__device__ __forceinline__ void chol_bs_chain_step(const f64x4 &L, const double (&lk)[16], const double *tv, double *xs, int b, int q4, int l15) {
+  double xb[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) xb[r] = xs[16 * b + q4 + 4 * r];
+  const double tb = tv[16 * (b - 1) + l15];
+  double part = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) part += L[r] * xb[r];
+  const double t = tb - rowgroup_sum(part);   // t_{b-1}[l15], in every row group
+  double xa = 0.0;
+  dpp_dot16<0>(xa, t, lk);
+  if (q4 == 0) xs[16 * (b - 1) + l15] = xa;
+}
+// off the chain: tile (b, j) = L, j < b - 1: t_j -= L^T x_b
+__device__ __forceinline__ void chol_bs_off_step(const f64x4 &L, double *tv, const double *xs, int b, int j, int q4, int l15) {
+  double xb[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) xb[r] = xs[16 * b + q4 + 4 * r];
+  double part = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) part += L[r] * xb[r];
+  part += __shfl_xor(part, 16);
+  part += __shfl_xor(part, 32);
+  if (q4 == 0) tv[16 * j + l15] -= part;
+}
 __device__ __forceinline__ void chol_back_substitute(const f64x4 (&acc)[CHOL_NS], const int (&ti)[CHOL_NS], const int (&tj)[CHOL_NS], const double *Li,
                                                      double *tv, double *xs, int NTR, int q4, int l15) {
   for (int b = NTR - 1; b >= 1; --b) {
 #pragma unroll
     for (int q = 0; q < CHOL_NS; ++q) {
       if (ti[q] != b || tj[q] >= b) continue;   // tiles (b, j), j < b: t_j -= L_bj^T x_b
-      double xb[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) xb[r] = xs[16 * b + q4 + 4 * r];
       if (tj[q] == b - 1) {                     // (uniform) the chain
         const double *Lb = Li + (b - 1) * CHOL_TS;
         double lk[16];
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) lk[kk] = Lb[kk * 17 + l15];
-        const double tb = tv[16 * (b - 1) + l15];
-        double part = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
-        const double t = tb - rowgroup_sum(part);   // t_{b-1}[l15], in every row group
-        double xa = 0.0;
-        dpp_dot16<0>(xa, t, lk);
-        if (q4 == 0) xs[16 * (b - 1) + l15] = xa;
+        chol_bs_chain_step(acc[q], lk, tv, xs, b, q4, l15);
       } else {
-        double part = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part += acc[q][r] * xb[r];
-        part += __shfl_xor(part, 16);
-        part += __shfl_xor(part, 32);
-        if (q4 == 0) tv[16 * tj[q] + l15] -= part;
+        chol_bs_off_step(acc[q], tv, xs, b, tj[q], q4, l15);
       }
     }
     lds_block_sync();
@@ -1266,12 +1294,17 @@ __global__ __launch_bounds__(64 * CHOL_NW) void k_cholesky_tiles(Dev d) {
 // flag in LDS that the consumer polls (s_sleep between polls, every loop bounded -- a bound trips the window's chol_fail instead of hanging):
 //   F_inv[k]   L_kk^-1 is in Li[k]                                   chain wave   -> update waves (their L_ik of panel k)
 //   F_row[i]   = c + 1: L_ic of panel c is in Pn[c % 3][i]            whoever formed it (chain wave for i = c + 1) -> every trailing update
-//   F_park[k]  = 2: tiles (k, k - 1) and (k, k), with every update up to panel k - 2 applied, are parked in Ls[k] / Li[k]
-//                                                                      their owners -> chain wave
+//   F_park[k]  = 2: tiles (k, k - 1) and (k, k), with every update up to panel k - 2 applied, are parked in Ls[k] / Li[k] (k = 0: = 1, tile (0, 0);
+//                rows 0 and 1 are parked straight from their fix-up)    their owners -> chain wave
 //   done_E[c]  = 15: every update wave is through with panel c       update waves -> whoever overwrites that panel's buffer (panel c + 3)
-// The three panel buffers bound the skew between waves to three panels.  Tile (k, k - 1) comes back from the chain wave as L_(k,k-1) in Ls[k], where
-// its owner picks it up for the back-substitution (unchanged, one barrier per block, the chain wave gone by then).  Every tile has one owner and
-// receives its updates in panel order: the arithmetic -- and so the bitwise reproducibility of the deterministic mode -- does not depend on timing.
+//   x_known    = n: x of the last n blocks is in xs                    chain wave   -> the owners of the tiles of those rows (back-substitution)
+//   t_count[j] = n: t_j has received the tiles (b, j) of its last n rows   their owners -> the owner of the next row's tile, and the chain wave
+// The three panel buffers bound the skew between waves to three panels.  The kernel has THREE workgroup barriers: after the chain wave's
+// initialisation (with every tile load still in flight), between factorisation and back-substitution, and before x is written out.  The chain of
+// the back-substitution (t_{b-1} finished by tile (b, b - 1), x_{b-1} = L_{b-1,b-1}^-T t_{b-1}) stays on the chain wave, which reads L_(b,b-1) back from
+// Ls[b] where it left it; the update waves apply their other tiles behind it, ordered by the two counters.  Every tile has one owner and
+// receives its updates in panel order, every t_j its tiles in row order: the arithmetic -- and so the bitwise reproducibility of the deterministic
+// mode -- does not depend on timing.
 // Measured (tools/r6_chol.sh, profiles/r06_chol_flow.txt): 64 us per factorisation of one window against 70 (k_cholesky_tiles), one window's
 // solve 2.72 - 2.76 ms against 2.81; 2048 windows per launch 45.5 - 45.9 ms per solve against 45.8 - 46.0.  The chain wave still waits 1 - 6 k cycles
 // per panel for its tiles: in-order update waves with blocking waits form convoys.  Tried on the way: the chain wave alone on its SIMD (waves 4 /
@@ -1307,7 +1340,20 @@ constexpr bool chol_map_complete(const CholMap &mp) {   // every tile of every s
   return true;
 }
 static_assert(chol_map_complete(make_chol_map()), "CHOL_MAP must hold every tile once, within seven slots per update wave");
-__constant__ const CholMap CHOL_MAP = make_chol_map();
+// What the device reads: the seven slots of update wave o as ONE 64-bit word, byte q = ti << 4 | tj (0xff = empty slot) -- there is no scalar byte
+// load, and seven pairs of vector byte loads between the tile loads made every slot's tiles wait for the previous slot's.
+struct CholMapPacked { unsigned long long w[15][CHOL_NU]; };
+constexpr CholMapPacked pack_chol_map(const CholMap &mp) {
+  CholMapPacked pk{};
+  for (int n = 0; n < 15; ++n)
+    for (int o = 0; o < CHOL_NU; ++o)
+      for (int q = 0; q < CHOL_NS; ++q) {
+        const unsigned long long byte = mp.ti[n][o][q] < 0 ? 0xffull : (unsigned long long)((mp.ti[n][o][q] << 4) | mp.tj[n][o][q]);
+        pk.w[n][o] |= byte << (8 * q);
+      }
+  return pk;
+}
+__constant__ const CholMapPacked CHOL_MAP = pack_chol_map(make_chol_map());
 
 // poll an LDS flag until it reaches `target` (wave-uniform); a bound instead of a hang
 __device__ __forceinline__ void chol_wait(volatile int *f, int target, int &fail) {
@@ -1334,12 +1380,19 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   constexpr int NU = CHOL_NU, NS = CHOL_NS, NTU = 64 * NU, TS = CHOL_TS, NPB = CholFlowLds::NPB;
   const int w = blockIdx.x;
   Lm &lm = d.lm[w];
-  if (lm.status || lm.ls_active) return;
+  const WinMeta &m = d.wins[w];
+  // Everything the kernel reads from the window's two records, requested BEFORE the first wait: one scalar round trip instead of a chain of
+  // five (status -> ls_active -> P -> ..., each behind its own s_waitcnt).  The empty asm is the first use of all of them (not volatile: a
+  // volatile asm counts as a store, and every scalar load behind it would become a vector load).
+  int status = lm.status;
+  const int ls_active = lm.ls_active, cur = lm.cur;
+  const int P = m.P, K = m.K, u0 = m.u0, p0 = m.p0, ldh = m.ldh, tr0 = m.tr0;
+  const long long H0 = m.H0;
+  asm("" : "+s"(status) : "s"(ls_active), "s"(cur), "s"(P), "s"(K), "s"(u0), "s"(p0), "s"(ldh), "s"(tr0), "s"(H0));
+  if (status || ls_active) return;   // (in front of every LDS write and flag)
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const bool chain = wave == 0;
   const int uw = wave - 1;                      // update wave index 0 .. 14
-  const WinMeta &m = d.wins[w];
-  const int P = m.P;
   const int q4 = lane >> 4, l15 = lane & 15;
   const int NTR = P / 16 + 1, ip = P / 16, rp = P % 16;   // the rhs row P sits in tile row ip, local row rp
   extern __shared__ __attribute__((aligned(16))) double smt[];
@@ -1349,21 +1402,23 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   int &s_fail = fl[0];
   volatile int *F_inv = fl + 16, *F_row = fl + 32;
   int *F_park = fl + 48, *done_E = fl + 64;
+  int *x_known = fl + 1, *t_count = fl + 80;   // the back-substitution: blocks of x known (from the last one down); contributions t_j has received
   long long *dbg = (d.dbg && w == 0) ? d.dbg : nullptr;   // CTVIO_DEBUG_STAMPS: clock64 of the chain wave at its steps
   if (chain) {
     // ================================================================ the chain wave
     int dbi = 0, fail = 0;
+    CTV_STAMP(dbg, dbi, 30, lane == 0);   // kernel entry
     for (int i = lane; i < CholFlowLds::NFLAG; i += 64) fl[i] = 0;
     for (int i = lane; i < TS; i += 64) Id[i] = (i / 17 == i % 17) ? 1.0 : 0.0;
     for (int i = lane; i < 16 * NTR; i += 64) tv[i] = 0.0;
     lds_wave_sync();
-    lds_block_sync();   // tile (0, 0) is in LDS, the flags are clear
+    lds_block_sync();   // the flags are clear (the update waves arrive with their tile loads still in flight)
     CTV_STAMP(dbg, dbi, 30, lane == 0);
     for (int k = 0; k < NTR; ++k) {
       double *Dg = Li + k * TS;
+      chol_wait(reinterpret_cast<volatile int *>(F_park + k), k > 0 ? 2 : 1, fail);   // (tile (0, 0) is handed over like the rows after it)
+      if (k < 4) CTV_STAMP(dbg, dbi, 30, lane == 0);
       if (k > 0) {
-        chol_wait(reinterpret_cast<volatile int *>(F_park + k), 2, fail);
-        if (k < 4) CTV_STAMP(dbg, dbi, 30, lane == 0);
         // ---- L_(k,k-1) = A_(k,k-1) L_(k-1,k-1)^-T: both operands are in LDS in row-major form (no accumulator -> operand round trip)
         double *blk = Ls + k * TS;
         const double *Lk = Li + (k - 1) * TS;
@@ -1398,34 +1453,77 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
       CTV_STAMP(dbg, dbi, 30, lane == 0);
     }
     if (lane == 0 && fail) s_fail = 1;
+    CTV_STAMP(dbg, dbi, 30, lane == 0);
     chol_last_block_x(Li, tv, xs, NTR - 1, q4, l15);   // the back-substitution starts here
+    if (lane == 0) *x_known = 1;
     CTV_STAMP(dbg, dbi, 30, lane == 0);
     lds_block_sync();   // the factorisation is complete (the update waves arrive here when they are through)
-    return;                                      // (the update waves finish the back-substitution among themselves)
+    CTV_STAMP(dbg, dbi, 30, lane == 0);
+    // ---- the chain of the back-substitution, all of it on this wave: L_(b,b-1) from Ls (where this wave left it), L_(b-1,b-1)^-1 from Li -- both
+    // requested before the wait -- and t_{b-1} as soon as every tile (b', b - 1), b' > b, has been applied to it
+    fail = 0;
+    for (int b = NTR - 1; b >= 1; --b) {
+      const double *src = Ls + b * TS, *Lb = Li + (b - 1) * TS;
+      f64x4 L;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) L[r] = src[(q4 + 4 * r) * 17 + l15];
+      double lk[16];
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk) lk[kk] = Lb[kk * 17 + l15];
+      chol_wait(reinterpret_cast<volatile int *>(t_count + (b - 1)), NTR - 1 - b, fail);
+      chol_bs_chain_step(L, lk, tv, xs, b, q4, l15);
+      chol_post(reinterpret_cast<volatile int *>(x_known), NTR - b + 1, lane);
+    }
+    CTV_STAMP(dbg, dbi, 30, lane == 0);
+    if (lane == 0 && fail) s_fail = 1;
+    lds_block_sync();   // x is complete
+    return;
   }
   // ================================================================== update waves
   const int utid = 64 * uw + lane;
   int fail = 0;
-  const CholWindow cw = chol_window(d, m, lm, lane);
-  // ---- this wave's tiles (SGPRs) and their contents
-  int ti[NS], tj[NS], ek[NS];
+  // ---- ONE round trip for everything the wave reads from HBM: the envelope (lane i: tile row i), the activity bytes, the damping of the last
+  // diagonal tile, then per slot the tile and the one value its fix-up may need -- 1 + 4 + 1 + 7 x (4 + 1) loads per lane in flight together.
+  // No address depends on a loaded VECTOR value: the ownership of all seven slots is one 64-bit scalar load.
+  CholWindow cw = {d.S + H0, (cur ? d.HppS[1] : d.HppS[0]) + H0, d.rhs + p0, d.dd + u0, P, ldh, 6 * K, d.schur_plain_in_H != 0, {{0ull, 0ull, 0ull, 0ull}}};
+  const unsigned long long own = CHOL_MAP.w[NTR][uw];
+  int ti[NS], tj[NS], ek[NS];   // this wave's tiles (SGPRs)
+#pragma unroll
+  for (int q = 0; q < NS; ++q) {
+    const int byte = (int)(own >> (8 * q)) & 0xff;
+    ti[q] = __builtin_amdgcn_readfirstlane(byte == 0xff ? -1 : byte >> 4);
+    tj[q] = __builtin_amdgcn_readfirstlane(byte == 0xff ? 1 << 20 : byte & 15);   // (never equal to a panel, never a trailing tile: ti < tj)
+  }
+  const int env_row = d.env_tile[tr0 + min(lane, NTR - 1)];
+  int ab[4];
+  chol_active_request(ab, d, u0, P, lane);
+  const double *yy = cw.y, *ddp = cw.dd;   // (copies, as in chol_tile_fetch)
+  const double dd_ip = ddp[chol_fix_col(cw, ip, l15)];   // tile (ip, ip) can be both a plain diagonal tile and in the rhs row (P % 16 == 0)
   f64x4 acc[NS];
+  double fx[NS];                // y[col] for a tile of row ip, dd[col] for every other
 #pragma unroll
   for (int q = 0; q < NS; ++q) {
-    const int a0 = CHOL_MAP.ti[NTR][uw][q], b0 = CHOL_MAP.tj[NTR][uw][q];
-    const int a = max(a0, 0), b = max(b0, 0);
-    ti[q] = __builtin_amdgcn_readfirstlane(a0);
-    tj[q] = __builtin_amdgcn_readfirstlane(a0 >= 0 ? b0 : 1 << 20);   // (never equal to a panel, never a trailing tile: ti < tj)
-    ek[q] = chol_first_panel(d, m, a, b);
+    const int a = max(ti[q], 0), b = ti[q] < 0 ? 0 : tj[q];   // (an empty slot reads what tile (0, 0) reads, on valid addresses, and drops it)
     chol_tile_fetch(acc[q], cw, a, b, q4, l15);
+    fx[q] = (a == ip ? yy : ddp)[chol_fix_col(cw, b, l15)];
   }
+  lds_block_sync();   // the chain wave's flags, identity and tv are there -- BEFORE anybody waits for a tile (lgkmcnt only: the loads stay in flight)
 #pragma unroll
-  for (int q = 0; q < NS; ++q) {
-    if (ti[q] < 0) continue;
-    chol_tile_fixup(acc[q], cw, ti[q], tj[q], q4, l15);
-    if (ti[q] == 0) chol_tile_to_lds(Li, acc[q], q4, l15);   // tile (0, 0): to the chain wave as it is (row 1 follows in iteration 0 of the loop below)
-  }
-  lds_block_sync();
+  for (int q = 0; q < NS; ++q)   // chol_first_panel of the slot's tile
+    ek[q] = max(__builtin_amdgcn_readlane(env_row, max(ti[q], 0)), __builtin_amdgcn_readlane(env_row, ti[q] < 0 ? 0 : tj[q]));
+  chol_active_masks(cw.act, ab, P, lane);
+  // a slot's tile completed; the tiles of rows 0 and 1 -- what the chain wave needs for its first two panels -- go to it at once
+  auto finish_slot = [&](f64x4 &t, int a, int b, double fxq) {
+    if (a < 0) return;
+    chol_tile_fixup(t, cw, a, b, q4, l15, (a == ip && b == ip) ? dd_ip : fxq, fxq);
+    if (a <= 1) {   // (uniform) (0, 0) and (1, 1): Li[a]; (1, 0): Ls[1]
+      chol_tile_to_lds((a == b ? Li : Ls) + a * TS, t, q4, l15);
+      chol_count(F_park + a, lane);
+    }
+  };
+  finish_slot(acc[0], ti[0], tj[0], fx[0]);   // column 0 and tile (1, 1) are in slot 0 of their waves (column-major dealing, NTR < 15): first
+#pragma unroll
+  for (int q = 1; q < NS; ++q) finish_slot(acc[q], ti[q], tj[q], fx[q]);
   // Iteration c of an update wave: panel c - 1 applied to its NEAR trailing tiles (columns c and c + 1: the tiles whose L_ic the next panel needs, and
   // the two tiles of row c + 1 that go to the chain wave), then -- as soon as the chain wave has L_cc^-1 -- the L_ic of its tiles of column c, and
   // panel c - 1 applied to the rest, which fills the wait for L_cc^-1 when that is not there yet.
@@ -1482,7 +1580,7 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
         chol_post(F_row + ti[q], c + 1, lane);
       }
     };
-    apply_prev(0);        // (c = 0: nothing to apply -- tiles (1, 0) and (1, 1) go to the chain wave as they are)
+    if (c > 0) apply_prev(0);   // (c = 0: nothing to apply -- tiles (1, 0) and (1, 1) went to the chain wave with their fix-up)
     bool formed = false;  // the column is formed as soon as L_cc^-1 is seen -- checked before each part of the far work, which fills the wait
     auto try_form = [&](bool must) {
       if (formed) return;
@@ -1500,16 +1598,25 @@ __global__ __launch_bounds__(1024) void k_cholesky_flow(Dev d) {
   }
   if (lane == 0 && fail) s_fail = 1;
   lds_block_sync();   // the factorisation is complete; x of the last block (chain wave)
-  // the tiles (b, b - 1) come back from the chain wave as L_(b,b-1)
+  // ---- the back-substitution OFF the chain, without workgroup barriers: the owner of tile (b, j), j < b - 1, applies t_j -= L_bj^T x_b when x_b is
+  // known and t_j has received the tiles of every row above b -- t_count[j] tiles, one per row, in descending row order: the summation order of
+  // chol_back_substitute, whatever the timing.  Every tile counts, the empty ones of the envelope (exact zeros) included.  A wave walks its tiles
+  // in descending row order, so the lowest unfinished row never waits for a wave that waits for it; a wave without tiles goes straight on.
+  fail = 0;
+  for (int b = NTR - 1; b >= 2; --b) {
+    bool have_x = false;
 #pragma unroll
-  for (int q = 0; q < NS; ++q) {
-    if (ti[q] < 1 || tj[q] != ti[q] - 1) continue;
-    const double *src = Ls + ti[q] * TS;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[q][r] = src[(q4 + 4 * r) * 17 + l15];
+    for (int q = NS - 1; q >= 0; --q) {   // (a wave's tiles of one row: the highest column first -- the chain needs t_j in descending j)
+      if (ti[q] != b || tj[q] >= b - 1) continue;   // (uniform)
+      if (!have_x) { chol_wait(reinterpret_cast<volatile int *>(x_known), NTR - b, fail); have_x = true; }
+      chol_wait(reinterpret_cast<volatile int *>(t_count + tj[q]), NTR - 1 - b, fail);
+      chol_bs_off_step(acc[q], tv, xs, b, tj[q], q4, l15);
+      chol_count(t_count + tj[q], lane);
+    }
   }
-  chol_back_substitute(acc, ti, tj, Li, tv, xs, NTR, q4, l15);
-  double *x = d.delta + m.u0;
+  if (lane == 0 && fail) s_fail = 1;
+  lds_block_sync();   // x is complete (the chain wave arrives with x of block 0)
+  double *x = d.delta + u0;
   for (int i = utid; i < P; i += NTU) x[i] = xs[i];
   if (utid == 0) lm.chol_fail = s_fail;
 }
