@@ -1335,7 +1335,7 @@ class SolverImpl {
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     if (!tiles.empty())
       hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, dtiles, dsel, dy, dvar, (const PoseRec *)nullptr,
-                         (double *)nullptr);
+                         (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0);
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     if (!cwins.empty())
       hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
@@ -1415,7 +1415,8 @@ class SolverImpl {
     hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, drec, io_dev<int32_t>(io, s_stat));
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
-                       io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, drec, io_dev<double>(io, s_cov));
+                       io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, drec, io_dev<double>(io, s_cov), (const PointRec *)nullptr,
+                       (double *)nullptr, 0);
     HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
     // ---- results: the blocks as the kernel left them, the statuses in sorted order
     int32_t *hstat = io_host<int32_t>(io, s_stat);
@@ -1473,6 +1474,82 @@ class SolverImpl {
     if (const int rc = tri_timing()) return rc;
     if (depth && n) std::memcpy(depth, io_host<double>(io, s_dep), sizeof(double) * (size_t)n);
     if (flag && n) std::memcpy(flag, io_host<int32_t>(io, s_flag), sizeof(int32_t) * (size_t)n);
+    return CTVIO_OK;
+  }
+  // ctvio_landmark_points_batch / ctvio_landmark_points (single: window `only` alone): the world point of every landmark and its 3 x 3
+  // covariance.  Points only (cov9 null): k_cov_point_jac alone, nothing is linearised or factored.  Otherwise the middle of covariance(),
+  // k_cov_point_jac with the Jacobians (one record per landmark, after k_cov_prepare: it reads 1 / Hll) and k_cov_solve on tiles of kind 3,
+  // five landmarks each in the sorted order of the rows of W.  dev_, plan_ and the captured graph are not touched.
+  int landmark_points(bool single, int only, double *point3, double *cov9, int32_t *status) {
+    if (const int rc = single ? guard(only) : guard()) return rc;
+    const int nw = dev_.nwin, wbeg = single ? only : 0, wend = single ? only + 1 : nw;
+    const int l0 = single ? meta_[only].lm0 : 0, n = single ? meta_[only].L : dev_.Ltot;
+    if (n == 0) return CTVIO_OK;
+    const size_t nn = (size_t)n;
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    if (!cov9) {   // out: point3 | status (one copy)
+      CallLayout io = head_;
+      const int s_pt = io.add("point3", sizeof(double), 3 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
+      if (const int rc = reserve_call(io)) return rc;
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, 0, (PointRec *)nullptr, io_dev<double>(io, s_pt),
+                         io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_pt), io_dev<char>(io, s_pt), io.bytes() - io.off(s_pt), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      if (const int rc = tri_timing()) return rc;
+      if (point3) std::memcpy(point3, io_host<double>(io, s_pt), sizeof(double) * 3 * nn);
+      if (status) std::memcpy(status, io_host<int32_t>(io, s_stat), sizeof(int32_t) * nn);
+      return CTVIO_OK;
+    }
+    std::vector<CovTile> tiles;
+    for (int w = wbeg; w < wend; ++w)
+      for (int r = 0; r < meta_[w].L; r += LMP_PER_TILE) tiles.push_back(CovTile{w, 3, r, std::min(LMP_PER_TILE, meta_[w].L - r), 0});
+    // ---- scratch.  io: tiles (in, one staged copy); cov9 | point3 | status (out, one copy).  scr: mask, exclusions, records
+    CallLayout io = head_, scr;
+    const int s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov9", sizeof(double), 9 * nn, true),
+              s_pt = io.add("point3", sizeof(double), 3 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_rec = scr.add("records", sizeof(PointRec), (size_t)dev_.Ltot, false);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    PointRec *drec = scr.at<PointRec>(call_scr_.dev, s_rec);
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_tiles), io_host<char>(io, s_tiles), io.off(s_cov) - io.off(s_tiles), hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, 1, drec, io_dev<double>(io, s_pt), io_dev<int32_t>(io, s_stat));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+                       (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, drec,
+                       io_dev<double>(io, s_cov), l0);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // ---- results
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov9 | point3 | status)
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_point_jac and the whole call
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
+      const bool ran[3] = {true, true, true};
+      if (const int rc = cov_timing(pair, ran)) return rc;
+    }
+    // (not computable: NaN; no information on the inverse depth: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN)
+    const double *hcov = io_host<double>(io, s_cov);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    if (point3) std::memcpy(point3, io_host<double>(io, s_pt), sizeof(double) * 3 * nn);
+    size_t i = 0;
+    for (int w = wbeg; w < wend; ++w)
+      for (int l = 0; l < meta_[w].L; ++l, ++i) {
+        int st = hstat[i];
+        if (st == LMP_OK && lm[w].chol_fail != 0) st = LMP_SINGULAR;
+        double *o = cov9 + 9 * i;
+        if (st == LMP_OK) std::memcpy(o, hcov + 9 * i, sizeof(double) * 9);
+        else for (int e = 0; e < 9; ++e) o[e] = st == LMP_NO_INFO ? (e % 4 == 0 ? inf : 0.0) : nan;
+        if (status) status[i] = st;
+      }
     return CTVIO_OK;
   }
   int shift_anchor(const ctvio_triangulate_options *o, int64_t n64, const int32_t *win, const int32_t *lm, const int64_t *t_new, const int32_t *row_new,
@@ -1657,6 +1734,12 @@ int32_t ctvio_pose_covariance(ctvio_solver *s, int32_t id, int32_t n, const int6
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.pose_covariance(id, n, nullptr, t_ns, q_SI, p_SI, cov36, status);
+}
+int32_t ctvio_landmark_points_batch(ctvio_solver *s, double *point3, double *cov9, int32_t *status) {
+  CHK_S; return s->impl.landmark_points(false, 0, point3, cov9, status);
+}
+int32_t ctvio_landmark_points(ctvio_solver *s, int32_t id, double *point3, double *cov9, int32_t *status) {
+  CHK_S; return s->impl.landmark_points(true, id, point3, cov9, status);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

@@ -1,6 +1,8 @@
 // kernels_cov.hpp -- marginal covariances from the reduced system (ctvio_covariance_batch): k_cov_prepare (per-call activity mask, zero damping),
 // k_cov_solve (block forward substitution against 16 right-hand sides per workgroup), k_cov_gram (selected block of the covariance); pose
-// covariances at query times (ctvio_pose_covariance_batch): k_cov_pose_jac (one record per query), then k_cov_solve on tiles of kind 2.
+// covariances at query times (ctvio_pose_covariance_batch): k_cov_pose_jac (one record per query), then k_cov_solve on tiles of kind 2; world
+// points of the landmarks with their 3 x 3 covariances (ctvio_landmark_points_batch): k_cov_point_jac (one record per landmark), then
+// k_cov_solve on tiles of kind 3.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -9,6 +11,9 @@
 //   Sigma[i][j]     = (L^-1 e_i)^T (L^-1 e_j)                    for trajectory unknowns i, j,
 //   Sigma[P+l][P+l] = 1 / Hll_l + | L^-1 (w_l / Hll_l) |^2        for the inverse depth of landmark l (w_l: its row of W),
 //   Sigma_pose(t)   = J Sigma J^T = (L^-1 J^T)^T (L^-1 J^T)        for the 6 x P Jacobian J of the pose at time t (factors.hpp: pose_jac_T),
+//   Cov(X_l)        = (L^-1 G)^T (L^-1 G) + j_rho j_rho^T / Hll_l   for the world point X_l of landmark l: G = Jp^T - w_l j_rho^T / Hll_l (P x 3), Jp
+//                     the Jacobian of X_l against the trajectory unknowns, j_rho = dX_l / drho_l (the joint covariance of the trajectory and
+//                     rho_l is Sigma_pp, Sigma_pl = -Sigma_pp w_l / Hll_l, Sigma_ll = 1 / Hll_l + w_l^T Sigma_pp w_l / Hll_l^2),
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -18,10 +23,11 @@ namespace ctv {
 struct CovTile {
   int32_t win;
   int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll; 2: the six columns of
-                    // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5)
-  int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1: first row of W (window-local);
+                    // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5); 3: the three columns of G of up to five landmarks
+                    // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused)
+  int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
                     // kind 2: the tile's first query record
-  int32_t count;    // columns in use (<= 16); kind 2: queries (1 or 2)
+  int32_t count;    // columns in use (<= 16); kind 2: queries (1 or 2); kind 3: landmarks (<= 5)
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -101,6 +107,91 @@ __global__ __launch_bounds__(64) void k_cov_pose_jac(Dev d, int n, const PoseQue
   pose_jac_T(k.q, sc, u, ext.on != 0, qmk(ext.q[0], ext.q[1], ext.q[2], ext.q[3]), mk(ext.p[0], ext.p[1], ext.p[2]), r.jt);
 }
 
+// One landmark's world point (ctvio_landmark_points_batch) and what k_cov_point_jac makes of it.  Records are indexed by landmark through the
+// batch (lm0 + l, the caller's order).
+enum { LMP_OK = 0, LMP_SINGULAR = 1, LMP_NO_INFO = 2, LMP_NONE = 3 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
+constexpr int LMP_PER_TILE = 5;
+struct PointRec {
+  int32_t status, s, nk, pad;   // first knot of the anchor time; knots the pose depends on there (3 at u = 0, else 4)
+  double X[3], jrho[3], jld[3]; // the point, dX / drho, dX / d(line delay)
+  double jt[72];                // Jp^T, rows of knots s .. s + 3: jt[3 r + a] = dX_a / d(unknown 6 s + r) (written with the Jacobians, LMP_OK only)
+};
+
+// One lane per landmark l_begin + i < l_begin + l_count: the anchor observation (t_i, row_i, p_i) its blocks share -- read as k_triangulate
+// reads it --, the camera pose T_I(tau) (q_CI, p_CI) at tau = t_i + row_i * line delay (vis_times), X = R_C (p_i / rho) + p_C.  LMP_NONE
+// by the rules of k_shift_anchor: rho <= 0 or non-finite, no block, blocks naming several anchors, tau outside the spline.  With want_jac
+// (after k_cov_prepare: d.dinv holds 1 / Hll by row of W, 0 where Hll == 0 -> LMP_NO_INFO) the record takes j_rho = -R_C p_i / rho^2, the
+// line-delay column row_i (R_I [omega]x p_I + v) -- the formal derivative the visual factor uses (factors.hpp: vis_anchor_eval, h) -- and
+// Jp^T = ([-R_C [x_c]x, I] J_pose)^T from pose_jac_T with the extrinsic on.  The point is formed before the flag is looked at: both calls
+// give it the same bits.  point3 / status_out: [l_count], either may be null.
+__global__ __launch_bounds__(64) void k_cov_point_jac(Dev d, int l_begin, int l_count, int want_jac, PointRec *recs, double *point3, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= l_count) return;
+  const int l = l_begin + i, w = d.lm_win[l];
+  const WinMeta &m = d.wins[w];
+  const double rho = d.rho[l];
+  const int first = d.lm_vfirst[l], cnt = d.lm_vcnt[l];
+  bool ok = rho > 0.0 && isfinite(rho) && cnt > 0;
+  int a0 = m.anc0;
+  if (cnt > 0) {
+    a0 = d.v_anc[first];
+    for (int j = 1; j < cnt; ++j) ok = ok && d.v_anc[first + j] == a0;
+  }
+  const int row = cnt > 0 ? d.a_row[a0] : 0;
+  int s = 0;
+  double u = 0.0;
+  if (cnt > 0) vis_times(m, d.a_t[a0], row, d.ld[w], s, u);
+  ok = ok && s >= 0 && u >= 0.0 && s <= m.K - 4;   // (a negative time truncates towards zero: s <= 0 and u <= 0)
+  s = max(0, min(s, m.K - 4));                     // the loads stay in range either way
+  const int nk = u > 0.0 ? 4 : 3;
+  int status = ok ? LMP_OK : LMP_NONE;
+  if (ok && want_jac && d.dinv[m.lm0 + d.lm_pos[l]] == 0.0) status = LMP_NO_INFO;
+  const double zero3[3] = {0, 0, 0};
+  Knots4 k;
+  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  SegConst sc;
+  seg_const(k, sc, want_jac != 0);
+  const Q4 q_CI = qmk(m.q_CI[0], m.q_CI[1], m.q_CI[2], m.q_CI[3]);
+  const V3 p_CI = mk(m.p_CI[0], m.p_CI[1], m.p_CI[2]);
+  const double px = cnt > 0 ? d.a_obs[a0] : 0.0, py = cnt > 0 ? d.a_obs[(size_t)d.Atot + a0] : 0.0, z = 1.0 / rho;
+  const V3 x_c = mk(px * z, py * z, z);
+  double c[4];
+  basis<false, 0>(u, 1.0, c);
+  V3 pI = mk(0, 0, 0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) pI = pI + c[j] * k.p[j];
+  const Q4 qI = eval_R(k.q, sc, u);
+  const M3 RI = q2R(qI), RC = q2R(qmul(qI, q_CI));
+  const V3 X = mul(RC, x_c) + (pI + qrot(qI, p_CI));
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  if (point3) { point3[3 * i] = ok ? X.x : nan; point3[3 * i + 1] = ok ? X.y : nan; point3[3 * i + 2] = ok ? X.z : nan; }
+  if (status_out) status_out[i] = status;
+  if (!want_jac) return;
+  PointRec &r = recs[l];
+  r.status = status; r.s = s; r.nk = nk; r.pad = 0;
+  r.X[0] = X.x; r.X[1] = X.y; r.X[2] = X.z;
+  if (status != LMP_OK) return;
+  const V3 jr = (-z * z) * mul(RC, mk(px, py, 1.0));
+  r.jrho[0] = jr.x; r.jrho[1] = jr.y; r.jrho[2] = jr.z;
+  {   // the line-delay column
+    double dc[4];
+    basis<false, 1>(u, m.inv_dt, dc);
+    V3 v = mk(0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v = v + dc[j] * k.p[j];
+    const V3 p_I = qrot(q_CI, x_c) + p_CI;
+    const V3 jl = (double)row * (mul(RI, cross(eval_omega<SegConst>(sc, u, m.inv_dt), p_I)) + v);
+    r.jld[0] = jl.x; r.jld[1] = jl.y; r.jld[2] = jl.z;
+  }
+  double jp[144];
+  pose_jac_T(k.q, sc, u, true, q_CI, p_CI, jp);
+  const M3 Mx = scale(mul_hat(RC, x_c), -1.0);   // -R_C [x_c]x
+  for (int rr = 0; rr < 24; ++rr)
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      r.jt[3 * rr + a] = Mx.m[3 * a] * jp[6 * rr] + Mx.m[3 * a + 1] * jp[6 * rr + 1] + Mx.m[3 * a + 2] * jp[6 * rr + 2] + jp[6 * rr + 3 + a];
+}
+
 // Y = L^-1 B for one tile of 16 right-hand sides.  d is the covariance's copy of Dev (d.active = the per-call mask).  Four waves: wave (h, kp)
 // owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of a half are added
 // in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row, as the back-substitution of the panel
@@ -108,9 +199,14 @@ __global__ __launch_bounds__(64) void k_cov_pose_jac(Dev d, int n, const PoseQue
 // tiles of the products go to the two partial sums by their parity, so where the tile starts moves no product from one sum to the other:
 // a column's bits do not depend on the columns it shares the tile with.
 // Kind 2: sel = the caller's slot of every query record, prec = the records, pose_cov = the caller-ordered 6 x 6 blocks.
+// Kind 3: lrec = the landmark records (by landmark through the batch), lm_cov = the 3 x 3 blocks in the caller's landmark order, the block of
+// landmark lm0 + l at 9 (lm0 + l - lm_base).  Column 3 q + a of landmark q = kind 1's column (the row of W over its span, then the line-delay
+// column, times 1 / Hll) times -j_rho[a], plus row a of Jp; landmarks whose status is not LMP_OK keep zero columns and write nothing.
+// amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
+// SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill.
 constexpr int COV_NT = 256;
-__global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const PoseRec *prec, double *pose_cov) {
+__global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
+                                                      const PoseRec *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
   const WinMeta &m = d.wins[w];
@@ -139,6 +235,40 @@ __global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tile
     if (tid == 0)
       for (int qi = 0; qi < t.count; ++qi)
         if (prec[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * prec[t.first + qi].s);
+  } else if (t.kind == 3) {
+    const int q = tid >> 4, sub = tid & 15;
+    if (q < t.count) {   // -(w_l / Hll) j_rho^T: the row's planned span, then the line-delay column
+      const int row = m.lm0 + t.first + q, klo = d.lm_klo[row], khi = d.lm_khi[row];
+      const PointRec &pr = lrec[m.lm0 + d.lm_at[row]];
+      const double dv = d.dinv[row];
+      const double *Wr = d.WS[cur] + m.W0 + (long long)(t.first + q) * m.ldw;
+      if (pr.status == LMP_OK && khi >= klo && dv != 0.0) {
+        const double j0 = -pr.jrho[0], j1 = -pr.jrho[1], j2 = -pr.jrho[2];
+        const int cend = min(6 * khi + 6, P);
+        for (int c = 6 * klo + sub; c < cend; c += 16)
+          if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 3 * q] = v * j0; Ys[c * 16 + 3 * q + 1] = v * j1; Ys[c * 16 + 3 * q + 2] = v * j2; }
+        if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
+          const double v = Wr[P - 1] * dv;
+          Ys[(P - 1) * 16 + 3 * q] = v * j0; Ys[(P - 1) * 16 + 3 * q + 1] = v * j1; Ys[(P - 1) * 16 + 3 * q + 2] = v * j2;
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < 75 * t.count; e += COV_NT) {   // + Jp^T: rows 6 s .. 6 (s + nk) - 1 (r < 24), then the line-delay row (r = 24)
+      const int q = e / 75, r = (e % 75) / 3, a = e % 3;
+      const PointRec &pr = lrec[m.lm0 + d.lm_at[m.lm0 + t.first + q]];
+      if (pr.status != LMP_OK) continue;
+      const int c = r < 24 ? 6 * pr.s + r : P - 1;
+      if ((r < 6 * pr.nk || r == 24) && d.active[m.u0 + c]) Ys[c * 16 + 3 * q + a] += r < 24 ? pr.jt[3 * r + a] : pr.jld[a];
+    }
+    if (tid == 0)
+      for (int q = 0; q < t.count; ++q) {
+        const int row = m.lm0 + t.first + q;
+        const PointRec &pr = lrec[m.lm0 + d.lm_at[row]];
+        if (pr.status != LMP_OK) continue;
+        s_first = min(s_first, 6 * pr.s);
+        if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
+      }
   } else {
     const int col = tid >> 4, sub = tid & 15;
     if (col < t.count) {
@@ -224,6 +354,24 @@ __global__ __launch_bounds__(COV_NT) void k_cov_solve(Dev d, const CovTile *tile
     }
     __syncthreads();
     if (tid < 36 * t.count) pose_cov[(long long)36 * sel[t.first + tid / 36] + tid % 36] = (part[tid] + part[72 + tid]) + part[144 + tid];
+    return;
+  }
+  if (t.kind == 3) {   // point tiles: the five 3 x 3 Gram blocks; every entry four partial sums over the rows k = p mod 4, added in sequence
+    const int k0 = min(32 * b0, P);
+    constexpr int NE = 9 * LMP_PER_TILE;
+    if (tid < 4 * NE) {
+      const int p = tid / NE, e = tid % NE, ci = 3 * (e / 9) + (e % 9) / 3, cj = 3 * (e / 9) + e % 3;
+      double s = 0.0;
+      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+      part[p * NE + e] = s;
+    }
+    __syncthreads();
+    if (tid < 9 * t.count) {
+      const int q = tid / 9, a = (tid % 9) / 3, b = tid % 3, row = m.lm0 + t.first + q, l = m.lm0 + d.lm_at[row];
+      const PointRec &pr = lrec[l];
+      if (pr.status == LMP_OK)
+        lm_cov[(long long)9 * (l - lm_base) + 3 * a + b] = (((part[tid] + part[NE + tid]) + part[2 * NE + tid]) + part[3 * NE + tid]) + (pr.jrho[a] * pr.jrho[b]) * d.dinv[row];
+    }
     return;
   }
   // ---- a landmark tile: column sums of squares in a fixed order (16 strided partial sums per column, then added in sequence)

@@ -296,6 +296,25 @@ class Solver:
         capi.check(self._lib.ctvio_pose_covariance(self._h, int(wid), n, capi._p(t), capi._p(q), capi._p(p), capi._p(cov), capi._p(st)))
         return cov[:n].copy(), st[:n].copy()
 
+    def _landmark_points(self, call, L, cov):
+        pts = np.zeros((max(L, 1), 3)); c9 = np.zeros((max(L, 1), 3, 3)) if cov else None; st = np.zeros(max(L, 1), np.int32)
+        capi.check(call(capi._p(pts), capi._p(c9) if cov else None, capi._p(st)))
+        return pts[:L].copy(), (c9[:L].copy() if cov else None), st[:L].copy()
+
+    def landmark_points_batch(self, cov: bool = True):
+        """ctvio_landmark_points_batch: the world point X = R_C (p_i / rho) + p_C of every landmark of the batch at the current state (camera
+        pose at the anchor's row time) and, with cov, its 3 x 3 covariance (trajectory, inverse depth and their cross terms).  Returns (points
+        (sum L, 3), cov (sum L, 3, 3) or None, status (sum L,)) in window order, the caller's landmark order: 0 ok, 1 singular window (cov NaN),
+        2 no information on the inverse depth (+inf diagonal), 3 not computable (NaN).  cov=False: one kernel, nothing is linearised."""
+        return self._landmark_points(lambda p, c, s: self._lib.ctvio_landmark_points_batch(self._h, p, c, s), sum(w.L for w in self.windows), cov)
+
+    def landmark_points(self, wid: int, cov: bool = True):
+        """ctvio_landmark_points: the same for window wid alone (same bits as the batch entry).  Returns (points (L, 3), cov (L, 3, 3) or None,
+        status (L,))."""
+        if not 0 <= int(wid) < len(self.windows):
+            capi.check(self._lib.ctvio_landmark_points(self._h, int(wid), None, None, None))
+        return self._landmark_points(lambda p, c, s: self._lib.ctvio_landmark_points(self._h, int(wid), p, c, s), self.windows[int(wid)].L, cov)
+
     def _tri_options(self, opts):
         o = capi.TriangulateOptions()
         self._lib.ctvio_default_triangulate_options(C.byref(o))

@@ -210,7 +210,7 @@ int32_t ctvio_lm_step(ctvio_solver *s, int32_t id, double mu, double *delta, dou
  * the launch plan and the captured graph of the solve are left as they were; the kernels of the covariance use no atomics: where the linearisation
  * is order-fixed (opt.deterministic) two calls give the same bits, and the single-window entry
  * (n_sel, sel, cov, var_rho (L doubles), singular (1) of window id alone) gives the bits of the batch entry.  Pose-landmark cross terms are
- * not computed. */
+ * not returned as such; ctvio_landmark_points_batch uses them for the covariance of every landmark's world point. */
 int32_t ctvio_covariance_batch(ctvio_solver *s, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
 int32_t ctvio_covariance(ctvio_solver *s, int32_t id, int32_t n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular);
 
@@ -237,6 +237,35 @@ int32_t ctvio_pose_covariance_batch(ctvio_solver *s, int64_t n, const int32_t *w
                                     double *cov36, int32_t *status);
 int32_t ctvio_pose_covariance(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *cov36,
                               int32_t *status);
+
+/* The landmark cloud of a window with its uncertainty -- what VisualOdometry::GetLandmarksInWindow / GetMarginCloud assemble on the host
+ * (visual_odometry.cpp:310-372: Rs[i] * (point * estimated_depth) + Ps[i]) and OdometryManager::PublishCloudAndTrajectory publishes --, at the
+ * CURRENT state.  Landmark l is anchored at the observation (t_i, row_i, p_i = (x, y, 1)) that all its visual blocks share, with inverse
+ * depth rho; the point as the visual factor models it:
+ *   tau = t_i + row_i * (int64)(ld * 1e9)   (the time exactly as the factors take it),   x_c = p_i / rho,
+ *   T_C = T_I(tau) (q_CI, p_CI)  (the window's camera extrinsic),   X = R_C x_c + p_C   (world frame, metres).
+ * The reference takes the pose at the frame time t_i (per-row poses are expensive on its host): a stated difference, as for triangulateRS;
+ * ctvio_sensor_pose gives the frame-time pose to a caller who wants that cloud.
+ * cov9 = the first-order covariance of X in the world frame (dX, additive), from the same reduced system as ctvio_covariance_batch: H, the
+ * exclusions and Sigma_pp are exactly those (no damping).  With Jp (3 x P) the Jacobian of X against the trajectory unknowns under the library's
+ * retraction (R_k <- R_k exp(delta_k), p_k <- p_k + dp_k) -- the knots of tau through the camera-pose Jacobian of ctvio_pose_covariance,
+ * [-R_C [x_c]x, I] J_pose, and the line-delay column row_i (R_I(tau) [omega(tau)]x (R_CI x_c + p_CI) + v(tau)), the formal derivative the
+ * visual factor itself uses --, j_rho = dX / drho = -R_C p_i / rho^2, w_l the landmark's row of W and h_l = Hll_l:
+ *   G = Jp^T - w_l j_rho^T / h_l  (rows of excluded unknowns zero),   Cov(X) = G^T Sigma_pp G + j_rho j_rho^T / h_l,
+ * i.e. [Jp | j_rho] over the joint covariance of the trajectory and rho_l, pose-landmark cross terms included.
+ *   point3 (3 doubles per landmark), cov9 (9 per landmark, row-major, symmetric to the bit), status (1 per landmark): sum L entries (batch) /
+ *   L entries (window id), window order, the caller's landmark order (as ctvio_triangulate_batch); any of the three may be NULL.
+ *   status 0: ok;  1: the window's factorisation met a non-positive or non-finite pivot: the point is valid, the covariance NaN;  2: no
+ *   information on the inverse depth (Hll == 0 exactly): the point is valid, +inf on the diagonal and 0 elsewhere;  3: not computable -- rho <= 0
+ *   or non-finite, no visual block, blocks that name more than one anchor observation, or tau outside the spline (the rules of
+ *   ctvio_triangulate_batch): point and covariance NaN.
+ * With cov9 == NULL nothing is linearised or factored: one kernel evaluates the points, and statuses 1 and 2 cannot occur; the points have the
+ * bits of the covariance call's.  The call returns CTVIO_OK for every status, and for a batch or window with L = 0.  CTVIO_ERR_STATE before the
+ * upload; CTVIO_ERR_INVALID for a window id out of range; the handle stays usable.  The state, the launch plan and the captured graph of the
+ * solve are left as they were; no atomics: where the linearisation is order-fixed (opt.deterministic) the bits of a landmark's result depend on
+ * its window and itself alone -- the single-window entry gives the batch entry's bits, and a second call repeats them. */
+int32_t ctvio_landmark_points_batch(ctvio_solver *s, double *point3, double *cov9, int32_t *status);
+int32_t ctvio_landmark_points(ctvio_solver *s, int32_t id, double *point3, double *cov9, int32_t *status);
 
 /* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
  * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
@@ -362,6 +391,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * (linearisation, Schur complement and Cholesky included), the rest zero.
  * After a pose-covariance call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution and the 6 x 6 blocks), k_cov_pose_jac,
  * ms8[7] = the whole call on the device, the rest zero.
+ * After a landmark-points call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution and the 3 x 3 blocks), k_cov_point_jac,
+ * ms8[7] = the whole call on the device, the rest zero; points only (cov9 == NULL): ms8[0] = device time of k_cov_point_jac, ms8[7] = the whole
+ * call on the device (its copy included), the rest zero.
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

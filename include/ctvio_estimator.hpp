@@ -551,6 +551,35 @@ class TrajectoryEstimator {
     }
     return written;
   }
+  // VisualOdometry::GetLandmarksInWindow / GetMarginCloud (visual_odometry.cpp:310-372) for the landmarks of the image factors added so far, at
+  // the CURRENT parameter values (ctvio_landmark_points): points = 3 doubles per inverse-depth pointer, world frame, the camera pose taken at the
+  // anchor's row time (the reference takes the frame time: ctvio.h); cov9 (optional) = 9 per pointer, row-major, the first-order covariance of
+  // the point from the factors of Solve -- without it nothing is linearised; status (optional) = one ctvio_landmark_points status per pointer.
+  // Order: that of the inverse-depth pointers as first passed to AddImageFeatureDelayAnalytic, the order TriangulateDepths reports in (a
+  // landmark without a factor: status 3, NaN).  Returns false if any status is not 0.
+  bool GetLandmarkPoints(std::vector<double> &points, std::vector<double> *cov9 = nullptr, std::vector<int32_t> *status = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    const size_t L = (size_t)pk.w.L, n = lm_ptr_.size();
+    std::vector<double> pt(3 * L), cv(cov9 ? 9 * L : 0);
+    std::vector<int32_t> st(L, 0);
+    check(ctvio_landmark_points(s, 0, pt.data(), cov9 ? cv.data() : nullptr, st.data()));
+    points.assign(3 * n, std::nan(""));
+    if (cov9) cov9->assign(9 * n, std::nan(""));
+    if (status) status->assign(n, 3);
+    bool ok = true;
+    for (size_t l = 0; l < n; ++l) {
+      const int j = pk.lm_map[l];
+      if (j < 0) { ok = false; continue; }
+      std::copy(pt.begin() + 3 * j, pt.begin() + 3 * j + 3, points.begin() + 3 * l);
+      if (cov9) std::copy(cv.begin() + 9 * j, cv.begin() + 9 * j + 9, cov9->begin() + 9 * l);
+      if (status) (*status)[l] = st[(size_t)j];
+      ok = ok && st[(size_t)j] == 0;
+    }
+    return ok;
+  }
 
  private:
   // One packed window: only the knots the factors touch (the reference registers exactly those with Ceres,

@@ -1,0 +1,62 @@
+#!/usr/bin/env python
+"""Bit comparison of the covariance entries between two builds of the library, on one GPU.  `dump OUT.npz` runs ctvio_covariance_batch (with
+var_rho) and ctvio_pose_covariance_batch (body and camera pose) on the mixed batch of tests/test_gpu_covariance.py under deterministic = 2, at
+the initial state and after a 6-iteration solve, and ctvio_covariance with 64 scattered selections + var_rho on a solved `config1` window, with
+the library CTVIO_LIB_PATH names (default: the in-tree build), and saves every output and the solved state.  `compare A.npz B.npz` lists the
+arrays whose bits differ (exit status 1 if any).  Not a test: the second build has to come from another checkout.
+usage: python tools/covariance_bits.py dump new.npz; CTVIO_LIB_PATH=/other/libctvio.so python tools/covariance_bits.py dump old.npz;
+       python tools/covariance_bits.py compare new.npz old.npz"""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+
+
+def dump(path):
+    cv = importlib.import_module("ctrl-vio_amd")
+    import cov_helpers as ch
+    from test_gpu_covariance import DET, mixed_batch
+    from test_gpu_pose_covariance import mixed_queries
+    out = {}
+    ws, sels = mixed_batch(cv)
+    win, t = mixed_queries(ws)
+    with cv.Solver(**DET) as s:
+        s.set_windows([w.copy() for w in ws])
+        for tag in ("init", "solved"):
+            covs, vars_, sing = s.covariance_batch(sels, rho=True)
+            for i, (c, v) in enumerate(zip(covs, vars_)):
+                out[f"{tag}_cov{i}"] = c; out[f"{tag}_var{i}"] = v
+            out[f"{tag}_singular"] = sing
+            out[f"{tag}_pose"], out[f"{tag}_pose_status"] = s.pose_covariance_batch(win, t)
+            out[f"{tag}_pose_camera"], _ = s.pose_covariance_batch(win, t, ws[1].q_CI, ws[1].p_CI)
+            s.solve(6, writeback=False)
+        for i, a in enumerate(s.get_batch_state()):
+            out[f"state{i}"] = a
+    w = cv.synth.make_window("config1", seed=1000)
+    with cv.Solver() as s:
+        s.set_windows([w.copy()])
+        s.solve(15, writeback=False)
+        out["config1_cov"], out["config1_var"], _ = s.covariance(0, ch.scattered_selection(w, 64), rho=True)
+    np.savez(path, **out)
+    print(f"saved {len(out)} arrays to {path}")
+
+
+def compare(pa, pb):
+    a, b = np.load(pa), np.load(pb)
+    bad = sorted(set(a.files) ^ set(b.files)) + [k for k in a.files if k in b.files and not np.array_equal(a[k], b[k], equal_nan=True)]
+    print(f"{len(a.files)} arrays, differing: {bad}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "dump":
+        dump(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    else:
+        sys.exit(__doc__)
