@@ -1335,7 +1335,7 @@ class SolverImpl {
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     if (!tiles.empty())
       hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, dtiles, dsel, dy, dvar, (const PoseRec *)nullptr,
-                         (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0);
+                         (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     if (!cwins.empty())
       hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
@@ -1416,7 +1416,7 @@ class SolverImpl {
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
                        io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, drec, io_dev<double>(io, s_cov), (const PointRec *)nullptr,
-                       (double *)nullptr, 0);
+                       (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
     // ---- results: the blocks as the kernel left them, the statuses in sorted order
     int32_t *hstat = io_host<int32_t>(io, s_stat);
@@ -1439,6 +1439,119 @@ class SolverImpl {
       double *o = cov36 + 36 * i;
       if (st == POSE_OK) std::memcpy(o, hcov + 36 * i, sizeof(double) * 36);
       else for (int e = 0; e < 36; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 7 == 0 ? inf : 0.0) : nan;
+      if (status) status[i] = st;
+    }
+    return CTVIO_OK;
+  }
+  // ctvio_nav_state_batch / ctvio_nav_state (only >= 0: every query belongs to that window, win is not read): the navigation state (pose,
+  // world velocity, the biases of state frame[i]; frame null: the newest) at n query times and J Sigma J^T of its 15 tangent dimensions.
+  // Values only (cov225 null): k_cov_nav_jac alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable)
+  // into tiles of kind 4, one each; k_cov_nav_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the
+  // 15 x 15 blocks into the caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are not touched.
+  int nav_state(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225, int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || (only < 0 && !win) || (!state16 && !cov225 && !status))))
+      return fail(CTVIO_ERR_INVALID, "bad arguments");
+    const int n = (int)n64, nw = dev_.nwin;
+    const size_t nn = (size_t)n;
+    for (int i = 0; i < n; ++i) {
+      const int w = only >= 0 ? only : win[i];
+      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": bias state out of range");
+    }
+    if (n == 0) return CTVIO_OK;
+    // ---- queries by window; slot[r]: the caller's index of sorted query r
+    std::vector<int32_t> slot(nn);
+    for (int i = 0; i < n; ++i) slot[i] = i;
+    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
+    auto query_of = [&](int r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      const int w = win_of(r);
+      return NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(t_ns[i] - t0_[w])};
+    };
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    if (!cov225) {   // in: queries (one staged copy); out: state16 | status (one copy)
+      CallLayout io = head_;
+      const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_state = io.add("state16", sizeof(double), 16 * nn, true),
+                s_stat = io.add("status", sizeof(int32_t), nn, false);
+      if (const int rc = reserve_call(io)) return rc;
+      NavQuery *hq = io_host<NavQuery>(io, s_q);
+      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_state) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)nullptr, (NavRec *)nullptr,
+                         io_dev<double>(io, s_state), io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), io.bytes() - io.off(s_state), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      {   // device times of this call, for ctvio_last_timing: k_cov_nav_jac and the whole call
+        Timing t;
+        t.clear();
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
+        t.ms[2] = ms; t.n[2] = 1;
+        if (const int rc = publish_timing(t, 0)) return rc;
+      }
+      const double *hstate = io_host<double>(io, s_state);
+      const int32_t *hstat = io_host<int32_t>(io, s_stat);
+      for (int r = 0; r < n; ++r) {
+        const size_t i = (size_t)slot[(size_t)r];
+        if (state16) std::memcpy(state16 + 16 * i, hstate + 16 * (size_t)r, sizeof(double) * 16);
+        if (status) status[i] = hstat[r];
+      }
+      return CTVIO_OK;
+    }
+    std::vector<CovTile> tiles(nn);
+    for (int r = 0; r < n; ++r) tiles[(size_t)r] = CovTile{win_of(r), 4, r, 1, 0};
+    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); cov225 | state16 | status (out, one copy).  scr: mask, exclusions, records
+    CallLayout io = head_, scr;
+    const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), nn, false), s_cov = io.add("cov225", sizeof(double), 225 * nn, true),
+              s_state = io.add("state16", sizeof(double), 16 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_rec = scr.add("records", sizeof(NavRec), nn, false);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    NavRec *drec = scr.at<NavRec>(call_scr_.dev, s_rec);
+    NavQuery *hq = io_host<NavQuery>(io, s_q);
+    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * nn);
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_cov) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec,
+                       io_dev<double>(io, s_state), io_dev<int32_t>(io, s_stat));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles), io_dev<int32_t>(io, s_slot),
+                       (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0,
+                       drec, io_dev<double>(io, s_cov));
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // ---- results: the blocks as the kernel left them (the caller's order), the states and statuses in sorted order
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov225 | state16 | status)
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_nav_jac and the whole call
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
+      const bool ran[3] = {true, true, true};
+      if (const int rc = cov_timing(pair, ran)) return rc;
+    }
+    // (time outside the spline: NaN; an untouched knot or bias state: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad
+    // pivot: NaN)
+    const double *hcov = io_host<double>(io, s_cov), *hstate = io_host<double>(io, s_state);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      int st = hstat[r];
+      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
+      double *o = cov225 + 225 * i;
+      if (st == POSE_OK) std::memcpy(o, hcov + 225 * i, sizeof(double) * 225);
+      else for (int e = 0; e < 225; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 16 == 0 ? inf : 0.0) : nan;
+      if (state16) std::memcpy(state16 + 16 * i, hstate + 16 * (size_t)r, sizeof(double) * 16);
       if (status) status[i] = st;
     }
     return CTVIO_OK;
@@ -1524,7 +1637,7 @@ class SolverImpl {
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
                        (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, drec,
-                       io_dev<double>(io, s_cov), l0);
+                       io_dev<double>(io, s_cov), l0, (const NavRec *)nullptr, (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
     // ---- results
     Lm *lm = io_host<Lm>(io, HEAD_LM);
@@ -1740,6 +1853,16 @@ int32_t ctvio_landmark_points_batch(ctvio_solver *s, double *point3, double *cov
 }
 int32_t ctvio_landmark_points(ctvio_solver *s, int32_t id, double *point3, double *cov9, int32_t *status) {
   CHK_S; return s->impl.landmark_points(true, id, point3, cov9, status);
+}
+int32_t ctvio_nav_state_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, const int32_t *frame, double *state16,
+                              double *cov225, int32_t *status) {
+  CHK_S; return s->impl.nav_state(-1, n, win, t_ns, frame, state16, cov225, status);
+}
+int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225,
+                        int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.nav_state(id, n, nullptr, t_ns, frame, state16, cov225, status);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

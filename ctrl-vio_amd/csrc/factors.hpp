@@ -430,6 +430,15 @@ template <class SC> CTV_DI void pose_jac_T(const Q4 q[4], const SC &sc, double u
   }
 }
 
+// Jacobian of the navigation state at u (ctvio_nav_state) against the tangents of its four knots: the 24 x 6 block jt of the BODY pose as
+// pose_jac_T writes it, and cv[k] = c'_k(u) / dt, the derivative of the blending coefficients of the position spline: the world velocity is
+// v(t) = sum_k cv[k] p_k, so d(dv) / d(dp_k) = cv[k] I and the velocity does not depend on the rotations.  At u = 0 the last knot's blocks
+// and cv[3] are exact zeros (c'_3 = u^2 / 2).  The bias rows of the state's Jacobian are one-hot and need no evaluation.
+template <class SC> CTV_DI void nav_jac_T(const Q4 q[4], const SC &sc, double u, double idt, double *jt, double cv[4]) {
+  pose_jac_T(q, sc, u, false, qmk(0.0, 0.0, 0.0, 1.0), mk(0.0, 0.0, 0.0), jt);
+  basis<false, 1>(u, idt, cv);
+}
+
 // Streaming forms of the two views: the per-knot partial Jacobians are handed to `f(knot, J)` one at a time, as soon as they
 // are final, instead of being returned as four 3 x 3 matrices -- the same operations in the same order (bit-identical
 // values), but only ~5 matrices are live at any time (the array forms keep 11, i.e. ~200 fp64 registers for both ends).

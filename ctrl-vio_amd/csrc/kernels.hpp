@@ -22,6 +22,7 @@
 //   kernels_query.hpp     k_gauge_restore (double2vector), k_residual_summary, k_spline_eval (trajectory queries)
 //   kernels_cov.hpp       k_cov_prepare, k_cov_solve, k_cov_gram (marginal covariances from the factor of the reduced system)
 //                         k_cov_pose_jac (per-query pose Jacobian: pose covariances at query times through k_cov_solve)
+//                         k_cov_nav_jac (per-query navigation state and its Jacobian: 15 x 15 covariances through k_cov_solve)
 //   kernels_tri.hpp       k_triangulate (landmark depths by one-sided Jacobi, one wave per landmark), k_shift_anchor (depths re-anchored)
 #pragma once
 #include <utility>

@@ -2,7 +2,8 @@
 // k_cov_solve (block forward substitution against 16 right-hand sides per workgroup), k_cov_gram (selected block of the covariance); pose
 // covariances at query times (ctvio_pose_covariance_batch): k_cov_pose_jac (one record per query), then k_cov_solve on tiles of kind 2; world
 // points of the landmarks with their 3 x 3 covariances (ctvio_landmark_points_batch): k_cov_point_jac (one record per landmark), then
-// k_cov_solve on tiles of kind 3.
+// k_cov_solve on tiles of kind 3; navigation states (pose, velocity, biases) with their 15 x 15 covariances (ctvio_nav_state_batch):
+// k_cov_nav_jac (one record per query), then k_cov_solve on tiles of kind 4.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -14,6 +15,8 @@
 //   Cov(X_l)        = (L^-1 G)^T (L^-1 G) + j_rho j_rho^T / Hll_l   for the world point X_l of landmark l: G = Jp^T - w_l j_rho^T / Hll_l (P x 3), Jp
 //                     the Jacobian of X_l against the trajectory unknowns, j_rho = dX_l / drho_l (the joint covariance of the trajectory and
 //                     rho_l is Sigma_pp, Sigma_pl = -Sigma_pp w_l / Hll_l, Sigma_ll = 1 / Hll_l + w_l^T Sigma_pp w_l / Hll_l^2),
+//   Sigma_nav(t, f) = (L^-1 J^T)^T (L^-1 J^T)                      for the 15 x P Jacobian J of (pose, world velocity, bias state f) at time t
+//                     (factors.hpp: nav_jac_T; the bias rows are one-hot),
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -24,10 +27,11 @@ struct CovTile {
   int32_t win;
   int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll; 2: the six columns of
                     // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5); 3: the three columns of G of up to five landmarks
-                    // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused)
+                    // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused); 4: the fifteen columns of J^T of one navigation-state
+                    // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused)
   int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
-                    // kind 2: the tile's first query record
-  int32_t count;    // columns in use (<= 16); kind 2: queries (1 or 2); kind 3: landmarks (<= 5)
+                    // kind 2: the tile's first query record; kind 4: its query record
+  int32_t count;    // columns in use (<= 16); kind 2: queries (1 or 2); kind 3: landmarks (<= 5); kind 4: 1
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -105,6 +109,73 @@ __global__ __launch_bounds__(64) void k_cov_pose_jac(Dev d, int n, const PoseQue
   SegConst sc;
   seg_const(k, sc, true);
   pose_jac_T(k.q, sc, u, ext.on != 0, qmk(ext.q[0], ext.q[1], ext.q[2], ext.q[3]), mk(ext.p[0], ext.p[1], ext.p[2]), r.jt);
+}
+
+// One navigation-state query (ctvio_nav_state_batch), grouped by window on the host, and what k_cov_nav_jac makes of it.  The statuses are
+// the pose entry's (POSE_*).
+struct NavQuery {
+  int32_t win, frame;   // frame: the bias state, in [0, F) (the host has resolved "the newest")
+  long long t_rel;      // relative to the window's t0
+};
+struct NavRec {
+  int32_t status, s, nk, frame;   // first knot; knots the state depends on: 3 at u = 0 (c_3 = u^3 / 6, c'_3 = u^2 / 2), else 4
+  double cv[4];                   // c'_k(u) / dt: the velocity rows against the position unknowns of knots s .. s + 3
+  double jt[144];                 // the pose block of J^T, rows of knots s .. s + 3 (nav_jac_T; with cv written for POSE_OK only)
+};
+
+// One lane per query: segment and u by the integer-ns rule of k_spline_eval, the state -- position and orientation, world velocity (the
+// device functions of k_spline_eval), the six biases of state `frame` -- into state16 (NaN outside the spline), and with excl (after
+// k_cov_prepare; null: values only, recs is not touched) the status and the record.  A knot the state depends on, or the bias state, with
+// an unknown no factor touches (COV_UNTOUCHED) gives POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.
+// The values are formed before excl is looked at: both calls give them the same bits.
+__global__ __launch_bounds__(64) void k_cov_nav_jac(Dev d, int n, const NavQuery *qs, const uint8_t *excl, NavRec *recs, double *state16, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const NavQuery q = qs[i];
+  const WinMeta &m = d.wins[q.win];
+  const long long sl = q.t_rel / m.dt_ns;
+  const bool outside = q.t_rel < 0 || sl + 3 >= m.K;
+  const int s = outside ? 0 : (int)sl;
+  const double u = outside ? 0.0 : (double)(q.t_rel % m.dt_ns) / (double)m.dt_ns;
+  const int nk = u > 0.0 ? 4 : 3;
+  int status = outside ? POSE_OUTSIDE : POSE_OK;
+  const double zero3[3] = {0, 0, 0};
+  Knots4 k;
+  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  SegConst sc;
+  seg_const(k, sc, excl != nullptr);
+  {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double c[4], dc[4];
+    basis<false, 0>(u, 1.0, c);
+    basis<false, 1>(u, m.inv_dt, dc);
+    V3 p = mk(0, 0, 0), v = mk(0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { p = p + c[j] * k.p[j]; v = v + dc[j] * k.p[j]; }
+    const Q4 qq = eval_R(k.q, sc, u);
+    const double *bp = d.bias + 6 * (size_t)(m.bias0 + q.frame);
+    double *o = state16 + 16 * (size_t)i;
+    const double val[10] = {p.x, p.y, p.z, qq.x, qq.y, qq.z, qq.w, v.x, v.y, v.z};
+#pragma unroll
+    for (int j = 0; j < 10; ++j) o[j] = outside ? nan : val[j];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) o[10 + j] = outside ? nan : bp[j];
+  }
+  if (!excl) {
+    status_out[i] = status;
+    return;
+  }
+  if (!outside) {
+    for (int j = 6 * s; j < 6 * (s + nk); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+    for (int j = 6 * m.K + 6 * q.frame; j < 6 * m.K + 6 * q.frame + 6; ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+  }
+  NavRec &r = recs[i];
+  r.status = status; r.s = s; r.nk = nk; r.frame = q.frame;
+  status_out[i] = status;
+  if (status != POSE_OK) return;
+  nav_jac_T(k.q, sc, u, m.inv_dt, r.jt, r.cv);
 }
 
 // One landmark's world point (ctvio_landmark_points_batch) and what k_cov_point_jac makes of it.  Records are indexed by landmark through the
@@ -202,11 +273,15 @@ __global__ __launch_bounds__(64) void k_cov_point_jac(Dev d, int l_begin, int l_
 // Kind 3: lrec = the landmark records (by landmark through the batch), lm_cov = the 3 x 3 blocks in the caller's landmark order, the block of
 // landmark lm0 + l at 9 (lm0 + l - lm_base).  Column 3 q + a of landmark q = kind 1's column (the row of W over its span, then the line-delay
 // column, times 1 / Hll) times -j_rho[a], plus row a of Jp; landmarks whose status is not LMP_OK keep zero columns and write nothing.
+// Kind 4: sel = the caller's slot of every query record, nrec = the records, nav_cov = the caller-ordered 15 x 15 blocks.  One query per
+// tile: its bits depend on nothing else in the call.
 // amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
-// SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill.
+// SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
+// inlined as well.
 constexpr int COV_NT = 256;
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const PoseRec *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base) {
+                                                      const PoseRec *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
+                                                      const NavRec *nrec, double *nav_cov) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
   const WinMeta &m = d.wins[w];
@@ -235,6 +310,22 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     if (tid == 0)
       for (int qi = 0; qi < t.count; ++qi)
         if (prec[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * prec[t.first + qi].s);
+  } else if (t.kind == 4) {   // pose columns 0..5 and velocity columns 6..8 over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the
+                              // rows of bias state f, each where the unknown is in the system
+    const NavRec &nr = nrec[t.first];
+    if (nr.status == POSE_OK) {
+      if (tid < 144) {
+        const int r = tid / 6, a = tid % 6;
+        if (r < 6 * nr.nk && d.active[m.u0 + 6 * nr.s + r]) Ys[(6 * nr.s + r) * 16 + a] = nr.jt[tid];
+      } else if (tid < 156) {   // d(dv_a) / d(position a of knot s + kk) = c'_kk / dt
+        const int kk = (tid - 144) / 3, a = (tid - 144) % 3, j = 6 * (nr.s + kk) + 3 + a;
+        if (kk < nr.nk && d.active[m.u0 + j]) Ys[j * 16 + 6 + a] = nr.cv[kk];
+      } else if (tid < 162) {
+        const int a = tid - 156, j = 6 * m.K + 6 * nr.frame + a;
+        if (d.active[m.u0 + j]) Ys[j * 16 + 9 + a] = 1.0;
+      }
+      if (tid == 0) s_first = 6 * nr.s;
+    }
   } else if (t.kind == 3) {
     const int q = tid >> 4, sub = tid & 15;
     if (q < t.count) {   // -(w_l / Hll) j_rho^T: the row's planned span, then the line-delay column
@@ -354,6 +445,28 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     __syncthreads();
     if (tid < 36 * t.count) pose_cov[(long long)36 * sel[t.first + tid / 36] + tid % 36] = (part[tid] + part[72 + tid]) + part[144 + tid];
+    return;
+  }
+  if (t.kind == 4) {   // state tiles: the 120 unique entries of the 15 x 15 Gram block; every entry four partial sums over the rows k = p mod 4, added in
+                       // sequence, computed once and mirrored
+    const int k0 = min(32 * b0, P);
+    for (int x = tid; x < 480; x += COV_NT) {
+      const int p = x / 120;
+      int ci, cj;
+      tile_decode(x % 120, ci, cj);
+      double s = 0.0;
+      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+      part[x] = s;
+    }
+    __syncthreads();
+    if (tid < 120) {
+      int ci, cj;
+      tile_decode(tid, ci, cj);
+      const double v = ((part[tid] + part[120 + tid]) + part[240 + tid]) + part[360 + tid];
+      double *o = nav_cov + (long long)225 * sel[t.first];
+      o[15 * ci + cj] = v;
+      o[15 * cj + ci] = v;
+    }
     return;
   }
   if (t.kind == 3) {   // point tiles: the five 3 x 3 Gram blocks; every entry four partial sums over the rows k = p mod 4, added in sequence

@@ -315,6 +315,29 @@ class Solver:
             capi.check(self._lib.ctvio_landmark_points(self._h, int(wid), None, None, None))
         return self._landmark_points(lambda p, c, s: self._lib.ctvio_landmark_points(self._h, int(wid), p, c, s), self.windows[int(wid)].L, cov)
 
+    def _nav_state(self, call, t_ns, frame, cov, n_win=None):
+        t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        n = int(t.shape[0])
+        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
+        assert (fr is None or fr.shape[0] == n) and (n_win is None or n_win == n)
+        state = np.zeros((max(n, 1), 16)); c = np.zeros((max(n, 1), 15, 15)) if cov else None; st = np.zeros(max(n, 1), np.int32)
+        capi.check(call(n, capi._p(t), capi._p(fr), capi._p(state), capi._p(c) if cov else None, capi._p(st)))
+        return state[:n].copy(), (c[:n].copy() if cov else None), st[:n].copy()
+
+    def nav_state_batch(self, win, t_ns, frame=None, cov: bool = True):
+        """ctvio_nav_state_batch: the navigation state (px, py, pz, qx, qy, qz, qw, world velocity, bg, ba of bias state frame[i]; frame None:
+        the newest frame) at absolute time t_ns[i] of window win[i], at the current state, and with cov its 15 x 15 covariance in the tangent
+        (dtheta, dp, dv, dbg, dba) of R(t) <- R(t) exp(dtheta), the rest additive.  Returns (state (n, 16), cov (n, 15, 15) or None, status
+        (n,)): 0 ok, 1 singular window (cov NaN), 2 an untouched knot or bias state (+inf diagonal), 3 time outside the spline (NaN).
+        cov=False: one kernel, nothing is linearised."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
+        return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state_batch(self._h, C.c_int64(n), capi._p(wi), t, f, s, c, st), t_ns,
+                               frame, cov, int(wi.shape[0]))
+
+    def nav_state(self, wid: int, t_ns, frame=None, cov: bool = True):
+        """ctvio_nav_state: the same for the times t_ns of window wid alone (same bits as the batch entry)."""
+        return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state(self._h, int(wid), n, t, f, s, c, st), t_ns, frame, cov)
+
     def _tri_options(self, opts):
         o = capi.TriangulateOptions()
         self._lib.ctvio_default_triangulate_options(C.byref(o))

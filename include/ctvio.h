@@ -267,6 +267,35 @@ int32_t ctvio_pose_covariance(ctvio_solver *s, int32_t id, int32_t n, const int6
 int32_t ctvio_landmark_points_batch(ctvio_solver *s, double *point3, double *cov9, int32_t *status);
 int32_t ctvio_landmark_points(ctvio_solver *s, int32_t id, double *point3, double *cov9, int32_t *status);
 
+/* The NAVIGATION STATE at a time -- orientation, position, world velocity, gyro bias, accelerometer bias -- with its joint 15 x 15 covariance:
+ * what the reference reads after every solve to re-seed its IMU dead-reckoning (VisualOdometry::SlideWindow, visual_odometry.cpp:217-221,
+ * Trajectory::GetIMUState, trajectory.cpp:27-37) and what IMU-rate odometry, a velocity / bias gate or a downstream fuser starts from.
+ * Query i = (window win[i], absolute time t_ns[i], bias state frame[i] in [0, F)) at the CURRENT state; frame == NULL: F - 1, the newest frame,
+ * for every query.  Any number of queries, in any order, from any windows.  Segment and u by the integer-ns rule of ctvio_spline_eval; the
+ * time must lie in [t0, t0 + (K - 3) dt).  This is the BODY (IMU) state: there is no sensor extrinsic in this entry.
+ *   state16 (n x 16 doubles, or NULL): (px, py, pz, qx, qy, qz, qw) as ctvio_spline_eval's pose7, the world velocity (transVelWorld) in 7..9,
+ *   bg of bias state frame[i] in 10..12, ba in 13..15.
+ *   cov225 (n x 225 doubles, row-major 15 x 15 per query, symmetric to the bit, or NULL): J Sigma J^T in the tangent (dtheta 0..2, dp 3..5,
+ *   dv 6..8, dbg 9..11, dba 12..14), with H, the exclusions and Sigma exactly those of ctvio_covariance_batch (no damping).  R(t) <- R(t)
+ *   exp(dtheta); p, v and the biases are additive; the knots under the library's own retraction.  Rows of J: the pose rows of
+ *   ctvio_pose_covariance (body); velocity: c'_k(u) / dt I on the position unknowns of knots s .. s + 3 (knot s + 3 iff u > 0: c'_3 = u^2 / 2),
+ *   zero against rotations; bias: one-hot on unknowns 6 K + 6 f .. 6 K + 6 f + 5.  Constant unknowns contribute nothing: a locked bias gives
+ *   exact zero rows and columns, a state that depends on constant unknowns alone the exact zero matrix and status 0.
+ *   With cov225 == NULL nothing is linearised or factored: one kernel evaluates the states, and statuses 1 and 2 cannot occur.
+ *   status (n entries, or NULL) per query, in this precedence: 3 time outside the spline: state and covariance NaN;  2 a knot the state depends
+ *   on, or the selected bias state, has a non-constant unknown no factor touches: state valid, +inf on the diagonal, 0 elsewhere;  1 the
+ *   window's factorisation met a non-positive or non-finite pivot: state valid, covariance NaN;  0 ok.
+ * The call returns CTVIO_OK for every status.  n == 0 returns CTVIO_OK and launches nothing.  CTVIO_ERR_STATE before the upload;
+ * CTVIO_ERR_INVALID for a window id out of range, a frame outside [0, F), n < 0, a NULL win / t_ns with n > 0, all three outputs NULL with
+ * n > 0; the handle stays usable.  The state, the launch plan and the captured graph of the solve are left as they were; no atomics: where the
+ * linearisation is order-fixed (opt.deterministic) the bits of a query's result depend on its window, time and frame alone -- not on the entry
+ * (batch or single-window: win is window id for every query), the order of the queries, or which other queries are in the call; a second
+ * call repeats them. */
+int32_t ctvio_nav_state_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, const int32_t *frame, double *state16,
+                              double *cov225, int32_t *status);
+int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225,
+                        int32_t *status);
+
 /* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
  * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
  * a slide (feature_manager.cpp:341-381, visual_odometry.cpp:299-308). */
@@ -394,6 +423,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * After a landmark-points call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution and the 3 x 3 blocks), k_cov_point_jac,
  * ms8[7] = the whole call on the device, the rest zero; points only (cov9 == NULL): ms8[0] = device time of k_cov_point_jac, ms8[7] = the whole
  * call on the device (its copy included), the rest zero.
+ * After a navigation-state call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution and the 15 x 15 blocks), k_cov_nav_jac,
+ * ms8[7] = the whole call on the device, the rest zero; states only (cov225 == NULL): ms8[2] = device time of k_cov_nav_jac, ms8[7] = the
+ * whole call on the device (its copies included), the rest zero.
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

@@ -525,6 +525,44 @@ class TrajectoryEstimator {
     return true;
   }
 
+  // The navigation state at the times t_ns (absolute, inside the solved knots) with its 15 x 15 covariance, at the CURRENT parameter values, from
+  // the factors of Solve (ctvio_nav_state): what VisualOdometry::SlideWindow reads through Trajectory::GetIMUState to re-seed ProcessIMU
+  // (visual_odometry.cpp:217-221, 137-172), plus the uncertainty that propagation starts from.  states = one IMUState per time (body pose and
+  // world velocity); bias6 = t_ns.size() x 6, (bg, ba) of the bias state whose gyro-bias pointer, as given to the Add* calls, is bias_gyr
+  // (nullptr: the newest bias state of the window); cov225 = t_ns.size() x 225, row-major per time, in the tangent (dtheta, dp, dv, dbg, dba) of
+  // R(t) <- R(t) exp(dtheta), the rest additive.  Returns false if any status is not 0 (ctvio.h: a singular window or a time outside the
+  // spline give NaN, a knot or bias state no factor touches +inf).
+  bool GetIMUStateCovariance(const std::vector<int64_t> &t_ns, const double *bias_gyr, std::vector<IMUState> &states, std::vector<double> &bias6,
+                             std::vector<double> &cov225) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t n = t_ns.size();
+    std::vector<int32_t> frame;
+    if (bias_gyr) {
+      auto it = bias_of_.find(bias_gyr);
+      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("GetIMUStateCovariance: not a bias state of this window");
+      frame.assign(n, pk.bias_map[(size_t)it->second]);
+    }
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    std::vector<double> state16(16 * n);
+    std::vector<int32_t> status(n, 0);
+    cov225.assign(225 * n, 0.0);
+    check(ctvio_nav_state(s, 0, (int32_t)n, t_ns.data(), bias_gyr ? frame.data() : nullptr, state16.data(), cov225.data(), status.data()));
+    states.assign(n, IMUState());
+    bias6.assign(6 * n, 0.0);
+    bool ok = true;
+    for (size_t i = 0; i < n; ++i) {
+      const double *o = state16.data() + 16 * i;
+      states[i].timestamp = t_ns[i];
+      for (int c = 0; c < 3; ++c) { states[i].p[c] = o[c]; states[i].v[c] = o[7 + c]; }
+      for (int c = 0; c < 4; ++c) states[i].q[c] = o[3 + c];
+      std::copy(o + 10, o + 16, bias6.begin() + 6 * i);
+      ok = ok && status[i] == 0;
+    }
+    return ok;
+  }
+
   // FeatureManager::triangulate (feature_manager.cpp:226-274; row_times: its triangulateRS, :276-339) for the landmarks of the image factors
   // added so far, at the CURRENT parameter values (ctvio_triangulate): every inverse-depth parameter that is <= 0 (only_unset) or every one
   // receives 1 / depth in place, as the reference writes estimated_depth.  flags (optional): one ctvio_triangulate flag per inverse-depth
