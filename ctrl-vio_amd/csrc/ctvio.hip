@@ -135,7 +135,8 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_misc, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));   // (+ 2 KB of static LDS)
-    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     return CTVIO_OK;
   }
   int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
@@ -1334,7 +1335,7 @@ class SolverImpl {
     Dev c;
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     if (!tiles.empty())
-      hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, dtiles, dsel, dy, dvar, (const PoseRec *)nullptr,
+      hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, dtiles, dsel, dy, dvar, (const PoseRec *)nullptr,
                          (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     if (!cwins.empty())
@@ -1414,7 +1415,7 @@ class SolverImpl {
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, drec, io_dev<int32_t>(io, s_stat));
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+    hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
                        io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, drec, io_dev<double>(io, s_cov), (const PointRec *)nullptr,
                        (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
@@ -1526,7 +1527,7 @@ class SolverImpl {
     hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec,
                        io_dev<double>(io, s_state), io_dev<int32_t>(io, s_stat));
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles), io_dev<int32_t>(io, s_slot),
+    hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles), io_dev<int32_t>(io, s_slot),
                        (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0,
                        drec, io_dev<double>(io, s_cov));
     HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
@@ -1552,6 +1553,126 @@ class SolverImpl {
       if (st == POSE_OK) std::memcpy(o, hcov + 225 * i, sizeof(double) * 225);
       else for (int e = 0; e < 225; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 16 == 0 ? inf : 0.0) : nan;
       if (state16) std::memcpy(state16 + 16 * i, hstate + 16 * (size_t)r, sizeof(double) * 16);
+      if (status) status[i] = st;
+    }
+    return CTVIO_OK;
+  }
+  // ctvio_relative_pose_batch / ctvio_relative_pose (only >= 0: every query belongs to that window, win is not read): the pose increment
+  // T(t_a)^-1 T(t_b) of n pairs of times and J_rel Sigma J_rel^T of its six tangent dimensions.  Values only (cov36 null): k_cov_rel_jac
+  // alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a window's queries keep the caller's
+  // order) and paired into tiles of kind 5; k_cov_rel_jac writes one record per query after k_cov_prepare (it reads the exclusions),
+  // k_cov_solve the 6 x 6 blocks into the caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are
+  // not touched.
+  int relative_pose(int only, int64_t n64, const int32_t *win, const int64_t *t_a_ns, const int64_t *t_b_ns, const double *q_SI, const double *p_SI,
+                    double *rel7, double *cov36, int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_a_ns || !t_b_ns || (only < 0 && !win) || (!rel7 && !cov36 && !status))))
+      return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if ((q_SI == nullptr) != (p_SI == nullptr)) return fail(CTVIO_ERR_INVALID, "sensor extrinsic: q_SI and p_SI come together (both null: the body pose)");
+    SensorExt ext{};
+    if (q_SI)
+      if (const int rc = sensor_ext(q_SI, p_SI, ext)) return rc;
+    const int n = (int)n64, nw = dev_.nwin;
+    const size_t nn = (size_t)n;
+    if (only < 0)
+      for (int i = 0; i < n; ++i)
+        if (win[i] < 0 || win[i] >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+    if (n == 0) return CTVIO_OK;
+    // ---- queries by window; slot[r]: the caller's index of sorted query r
+    std::vector<int32_t> slot(nn);
+    for (int i = 0; i < n; ++i) slot[i] = i;
+    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
+    auto query_of = [&](int r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      const int w = win_of(r);
+      return RelQuery{w, 0, (long long)(t_a_ns[i] - t0_[w]), (long long)(t_b_ns[i] - t0_[w])};
+    };
+    if (!cov36) {   // in: queries (one staged copy); out: rel7 | status (one copy)
+      CallLayout io = head_;
+      const int s_q = io.add("queries", sizeof(RelQuery), nn, false), s_rel = io.add("rel7", sizeof(double), 7 * nn, true),
+                s_stat = io.add("status", sizeof(int32_t), nn, false);
+      if (const int rc = reserve_call(io)) return rc;
+      RelQuery *hq = io_host<RelQuery>(io, s_q);
+      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_rel) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), (const uint8_t *)nullptr, ext,
+                         (RelRec *)nullptr, io_dev<double>(io, s_rel), io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_rel), io_dev<char>(io, s_rel), io.bytes() - io.off(s_rel), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      {   // device times of this call, for ctvio_last_timing: k_cov_rel_jac and the whole call
+        Timing t;
+        t.clear();
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
+        t.ms[2] = ms; t.n[2] = 1;
+        if (const int rc = publish_timing(t, 0)) return rc;
+      }
+      const double *hrel = io_host<double>(io, s_rel);
+      const int32_t *hstat = io_host<int32_t>(io, s_stat);
+      for (int r = 0; r < n; ++r) {
+        const size_t i = (size_t)slot[(size_t)r];
+        if (rel7) std::memcpy(rel7 + 7 * i, hrel + 7 * (size_t)r, sizeof(double) * 7);
+        if (status) status[i] = hstat[r];
+      }
+      return CTVIO_OK;
+    }
+    std::vector<CovTile> tiles;
+    for (int r = 0; r < n;) {   // two per tile
+      const int cnt = (r + 1 < n && win_of(r + 1) == win_of(r)) ? 2 : 1;
+      tiles.push_back(CovTile{win_of(r), 5, r, cnt, 0});
+      r += cnt;
+    }
+    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); rel7 | cov36 | status (out, one copy).  scr: mask, exclusions, records
+    CallLayout io = head_, scr;
+    const int s_q = io.add("queries", sizeof(RelQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_rel = io.add("rel7", sizeof(double), 7 * nn, true),
+              s_cov = io.add("cov36", sizeof(double), 36 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_rec = scr.add("records", sizeof(RelRec), nn, false);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    RelRec *drec = scr.at<RelRec>(call_scr_.dev, s_rec);
+    RelQuery *hq = io_host<RelQuery>(io, s_q);
+    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_rel) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), (const uint8_t *)excl, ext, drec,
+                       io_dev<double>(io, s_rel), io_dev<int32_t>(io, s_stat));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    hipLaunchKernelGGL(k_cov_solve<true>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+                       io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, (const RelRec *)drec, io_dev<double>(io, s_cov),
+                       (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // ---- results: the blocks as the kernel left them (the caller's order), the values and statuses in sorted order
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_rel), io_dev<char>(io, s_rel), io.bytes() - io.off(s_rel), hipMemcpyDeviceToHost, stream_));   // (rel7 | cov36 | status)
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_rel_jac and the whole call
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
+      const bool ran[3] = {true, true, true};
+      if (const int rc = cov_timing(pair, ran)) return rc;
+    }
+    // (either time outside the spline: NaN; an untouched knot: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN)
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    const double *hcov = io_host<double>(io, s_cov), *hrel = io_host<double>(io, s_rel);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      int st = hstat[r];
+      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
+      double *o = cov36 + 36 * i;
+      if (st == POSE_OK) std::memcpy(o, hcov + 36 * i, sizeof(double) * 36);
+      else for (int e = 0; e < 36; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 7 == 0 ? inf : 0.0) : nan;
+      if (rel7) std::memcpy(rel7 + 7 * i, hrel + 7 * (size_t)r, sizeof(double) * 7);
       if (status) status[i] = st;
     }
     return CTVIO_OK;
@@ -1635,7 +1756,7 @@ class SolverImpl {
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, 1, drec, io_dev<double>(io, s_pt), io_dev<int32_t>(io, s_stat));
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+    hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
                        (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, drec,
                        io_dev<double>(io, s_cov), l0, (const NavRec *)nullptr, (double *)nullptr);
     HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
@@ -1863,6 +1984,16 @@ int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.nav_state(id, n, nullptr, t_ns, frame, state16, cov225, status);
+}
+int32_t ctvio_relative_pose_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_a_ns, const int64_t *t_b_ns, const double *q_SI,
+                                  const double *p_SI, double *rel7, double *cov36, int32_t *status) {
+  CHK_S; return s->impl.relative_pose(-1, n, win, t_a_ns, t_b_ns, q_SI, p_SI, rel7, cov36, status);
+}
+int32_t ctvio_relative_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_a_ns, const int64_t *t_b_ns, const double *q_SI,
+                            const double *p_SI, double *rel7, double *cov36, int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.relative_pose(id, n, nullptr, t_a_ns, t_b_ns, q_SI, p_SI, rel7, cov36, status);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

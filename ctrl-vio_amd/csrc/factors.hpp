@@ -439,6 +439,32 @@ template <class SC> CTV_DI void nav_jac_T(const Q4 q[4], const SC &sc, double u,
   basis<false, 1>(u, idt, cv);
 }
 
+// The pose increment T_ab = T_a^-1 T_b of two poses (q_a, p_a), (q_b, p_b) (ctvio_relative_pose): R_ab = R_a^T R_b, p_ab = R_a^T (p_b - p_a),
+// and its Jacobian against the knots of both poses.  jt_a, jt_b: the 24 x 6 blocks pose_jac_T wrote for the two poses; they are mapped IN
+// PLACE into the two blocks of J_rel^T, J_rel = A_a J_a + A_b J_b.  Tangent of the result (dtheta 0..2, dp 3..5): R_ab <- R_ab exp(dtheta),
+// p_ab <- p_ab + dp (dp in frame a):
+//   dtheta_ab = dtheta_b - R_ab^T dtheta_a,   dp_ab = [p_ab]x dtheta_a + R_a^T (dp_b - dp_a)
+//   A_a = [[-R_ab^T, 0], [[p_ab]x, -R_a^T]],  A_b = [[I, 0], [0, R_a^T]].
+// Rows that are exact zeros in jt_a / jt_b (the last knot at u = 0) stay exact zeros (up to the sign of a zero).  jt_a == nullptr: the value alone.
+CTV_DI void rel_pose_jac_T(Q4 q_a, V3 p_a, Q4 q_b, V3 p_b, double *jt_a, double *jt_b, Q4 &q_ab, V3 &p_ab) {
+  q_ab = qmul(qconj(q_a), q_b);
+  const M3 Ra = q2R(q_a), Rab = q2R(q_ab);
+  const V3 d = p_b - p_a;
+  p_ab = mk(Ra.m[0] * d.x + Ra.m[3] * d.y + Ra.m[6] * d.z, Ra.m[1] * d.x + Ra.m[4] * d.y + Ra.m[7] * d.z, Ra.m[2] * d.x + Ra.m[5] * d.y + Ra.m[8] * d.z);
+  if (!jt_a) return;
+  for (int r = 0; r < 24; ++r) {
+    double *ja = jt_a + 6 * r, *jb = jt_b + 6 * r;
+    const V3 th = mk(ja[0], ja[1], ja[2]), dp = mk(ja[3], ja[4], ja[5]), db = mk(jb[3], jb[4], jb[5]);
+    const V3 x = cross(p_ab, th);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      ja[a] = -(Rab.m[a] * th.x + Rab.m[3 + a] * th.y + Rab.m[6 + a] * th.z);
+      ja[3 + a] = (a == 0 ? x.x : a == 1 ? x.y : x.z) - (Ra.m[a] * dp.x + Ra.m[3 + a] * dp.y + Ra.m[6 + a] * dp.z);
+      jb[3 + a] = Ra.m[a] * db.x + Ra.m[3 + a] * db.y + Ra.m[6 + a] * db.z;
+    }
+  }
+}
+
 // Streaming forms of the two views: the per-knot partial Jacobians are handed to `f(knot, J)` one at a time, as soon as they
 // are final, instead of being returned as four 3 x 3 matrices -- the same operations in the same order (bit-identical
 // values), but only ~5 matrices are live at any time (the array forms keep 11, i.e. ~200 fp64 registers for both ends).

@@ -3,7 +3,8 @@
 // covariances at query times (ctvio_pose_covariance_batch): k_cov_pose_jac (one record per query), then k_cov_solve on tiles of kind 2; world
 // points of the landmarks with their 3 x 3 covariances (ctvio_landmark_points_batch): k_cov_point_jac (one record per landmark), then
 // k_cov_solve on tiles of kind 3; navigation states (pose, velocity, biases) with their 15 x 15 covariances (ctvio_nav_state_batch):
-// k_cov_nav_jac (one record per query), then k_cov_solve on tiles of kind 4.
+// k_cov_nav_jac (one record per query), then k_cov_solve on tiles of kind 4; pose increments between two times with their 6 x 6 covariances
+// (ctvio_relative_pose_batch): k_cov_rel_jac (one record per query), then k_cov_solve on tiles of kind 5.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -17,6 +18,8 @@
 //                     rho_l is Sigma_pp, Sigma_pl = -Sigma_pp w_l / Hll_l, Sigma_ll = 1 / Hll_l + w_l^T Sigma_pp w_l / Hll_l^2),
 //   Sigma_nav(t, f) = (L^-1 J^T)^T (L^-1 J^T)                      for the 15 x P Jacobian J of (pose, world velocity, bias state f) at time t
 //                     (factors.hpp: nav_jac_T; the bias rows are one-hot),
+//   Sigma_rel(a, b) = (L^-1 J^T)^T (L^-1 J^T)                      for the 6 x P Jacobian J = A_a J_a + A_b J_b of the increment T(t_a)^-1 T(t_b)
+//                     (factors.hpp: rel_pose_jac_T; J_a, J_b the pose Jacobians at the two times),
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -28,10 +31,11 @@ struct CovTile {
   int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll; 2: the six columns of
                     // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5); 3: the three columns of G of up to five landmarks
                     // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused); 4: the fifteen columns of J^T of one navigation-state
-                    // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused)
+                    // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 5: the six columns of
+                    // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5)
   int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
-                    // kind 2: the tile's first query record; kind 4: its query record
-  int32_t count;    // columns in use (<= 16); kind 2: queries (1 or 2); kind 3: landmarks (<= 5); kind 4: 1
+                    // kind 2 and 5: the tile's first query record; kind 4: its query record
+  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4: 1
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -178,6 +182,87 @@ __global__ __launch_bounds__(64) void k_cov_nav_jac(Dev d, int n, const NavQuery
   nav_jac_T(k.q, sc, u, m.inv_dt, r.jt, r.cv);
 }
 
+// One relative-pose query (ctvio_relative_pose_batch), grouped by window on the host, and what k_cov_rel_jac makes of it.  The statuses are
+// the pose entry's (POSE_*).
+struct RelQuery {
+  int32_t win, pad;
+  long long ta_rel, tb_rel;   // relative to the window's t0
+};
+struct RelRec {
+  int32_t status, s_a, nk_a, s_b, nk_b, pad;   // per time: first knot; knots the pose depends on (3 at u = 0, else 4)
+  double jt_a[144], jt_b[144];                 // the two blocks of J_rel^T: (A_a J_a)^T over knots s_a .. s_a + 3, (A_b J_b)^T over knots s_b .. s_b + 3
+                                               // (rel_pose_jac_T; written for POSE_OK only)
+};
+
+// The pose of one time of a relative-pose query: segment and u by the integer-ns rule of k_spline_eval, T_I(t), or T_I(t) T_SI with the
+// extrinsic; with jt the 24 x 6 block of pose_jac_T as well.  Outside the spline the loads stay in range (s = 0) and the value is not used.
+__device__ inline void rel_side(const Dev &d, const WinMeta &m, long long t_rel, const SensorExt &ext, double *jt, int &s, int &nk, bool &outside, Q4 &qo, V3 &po) {
+  const long long sl = t_rel / m.dt_ns;
+  outside = t_rel < 0 || sl + 3 >= m.K;
+  s = outside ? 0 : (int)sl;
+  const double u = outside ? 0.0 : (double)(t_rel % m.dt_ns) / (double)m.dt_ns;
+  nk = u > 0.0 ? 4 : 3;
+  const double zero3[3] = {0, 0, 0};
+  Knots4 k;
+  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  SegConst sc;
+  seg_const(k, sc, jt != nullptr);
+  double c[4];
+  basis<false, 0>(u, 1.0, c);
+  V3 p = mk(0, 0, 0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) p = p + c[j] * k.p[j];
+  const Q4 q = eval_R(k.q, sc, u);
+  const Q4 q_SI = qmk(ext.q[0], ext.q[1], ext.q[2], ext.q[3]);
+  const V3 p_SI = mk(ext.p[0], ext.p[1], ext.p[2]);
+  qo = ext.on ? qmul(q, q_SI) : q;
+  po = ext.on ? p + qrot(q, p_SI) : p;
+  if (jt) pose_jac_T(k.q, sc, u, ext.on != 0, q_SI, p_SI, jt);
+}
+
+// One lane per query: the two poses, the increment (p_ab, q_ab) into rel7 (NaN where either time is outside the spline), and with excl
+// (after k_cov_prepare; null: values only, recs is not touched) the status and the record.  A knot either pose depends on with an unknown
+// no factor touches (COV_UNTOUCHED) gives POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.  The
+// values are formed before excl is looked at, by code the Jacobians do not share: both calls give them the same bits.
+__global__ __launch_bounds__(64) void k_cov_rel_jac(Dev d, int n, const RelQuery *qs, const uint8_t *excl, SensorExt ext, RelRec *recs, double *rel7, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const RelQuery q = qs[i];
+  const WinMeta &m = d.wins[q.win];
+  int s_a, nk_a, s_b, nk_b;
+  bool out_a, out_b;
+  Q4 q_a, q_b, q_ab;
+  V3 p_a, p_b, p_ab;
+  rel_side(d, m, q.ta_rel, ext, nullptr, s_a, nk_a, out_a, q_a, p_a);
+  rel_side(d, m, q.tb_rel, ext, nullptr, s_b, nk_b, out_b, q_b, p_b);
+  const bool outside = out_a || out_b;
+  int status = outside ? POSE_OUTSIDE : POSE_OK;
+  rel_pose_jac_T(q_a, p_a, q_b, p_b, nullptr, nullptr, q_ab, p_ab);
+  if (rel7) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double val[7] = {p_ab.x, p_ab.y, p_ab.z, q_ab.x, q_ab.y, q_ab.z, q_ab.w};
+#pragma unroll
+    for (int j = 0; j < 7; ++j) rel7[7 * (size_t)i + j] = outside ? nan : val[j];
+  }
+  if (!excl) {
+    status_out[i] = status;
+    return;
+  }
+  if (!outside) {
+    for (int j = 6 * s_a; j < 6 * (s_a + nk_a); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+    for (int j = 6 * s_b; j < 6 * (s_b + nk_b); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+  }
+  RelRec &r = recs[i];
+  r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_b = s_b; r.nk_b = nk_b; r.pad = 0;
+  status_out[i] = status;
+  if (status != POSE_OK) return;
+  rel_side(d, m, q.ta_rel, ext, r.jt_a, s_a, nk_a, out_a, q_a, p_a);
+  rel_side(d, m, q.tb_rel, ext, r.jt_b, s_b, nk_b, out_b, q_b, p_b);
+  rel_pose_jac_T(q_a, p_a, q_b, p_b, r.jt_a, r.jt_b, q_ab, p_ab);
+}
+
 // One landmark's world point (ctvio_landmark_points_batch) and what k_cov_point_jac makes of it.  Records are indexed by landmark through the
 // batch (lm0 + l, the caller's order).
 enum { LMP_OK = 0, LMP_SINGULAR = 1, LMP_NO_INFO = 2, LMP_NONE = 3 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
@@ -275,12 +360,19 @@ __global__ __launch_bounds__(64) void k_cov_point_jac(Dev d, int l_begin, int l_
 // column, times 1 / Hll) times -j_rho[a], plus row a of Jp; landmarks whose status is not LMP_OK keep zero columns and write nothing.
 // Kind 4: sel = the caller's slot of every query record, nrec = the records, nav_cov = the caller-ordered 15 x 15 blocks.  One query per
 // tile: its bits depend on nothing else in the call.
+// Kind 5 (the instantiation REL = true, which holds no other kind; kinds 0 - 4 are the instantiation REL = false, whose arguments and code
+// are what they were before kind 5 existed): sel = the caller's slot of every query record, prec = the records (RelRec), pose_cov = the
+// caller-ordered 6 x 6 blocks; kind 2's epilogue.  The a-rows are stored, then after a barrier the b-rows are added: where the knot groups
+// of the two times overlap every entry is "a-term + b-term" in that order, elsewhere the one term (0.0 + b-term for a b-row).
 // amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
 // SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
 // inlined as well.
 constexpr int COV_NT = 256;
+template <bool REL> struct CovQueryRec { typedef PoseRec type; };
+template <> struct CovQueryRec<true> { typedef RelRec type; };
+template <bool REL>
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const PoseRec *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
+                                                      const typename CovQueryRec<REL>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
                                                       const NavRec *nrec, double *nav_cov) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
@@ -296,20 +388,38 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
   for (int e = tid; e < 16 * PP; e += COV_NT) Ys[e] = 0.0;
   if (tid == 0) s_first = PP;
   __syncthreads();
-  if (t.kind == 0) {
+  if constexpr (REL) {   // rows 6 s_a .. 6 (s_a + nk_a) - 1 of every query's six columns, then + rows 6 s_b .. 6 (s_b + nk_b) - 1, where the unknown is in the system
+    for (int e = tid; e < 144 * t.count; e += COV_NT) {
+      const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
+      const RelRec &rr = prec[t.first + qi];
+      if (rr.status == POSE_OK && r < 6 * rr.nk_a && d.active[m.u0 + 6 * rr.s_a + r]) Ys[(6 * rr.s_a + r) * 16 + 6 * qi + a] = rr.jt_a[6 * r + a];
+    }
+    __syncthreads();
+    for (int e = tid; e < 144 * t.count; e += COV_NT) {
+      const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
+      const RelRec &rr = prec[t.first + qi];
+      if (rr.status == POSE_OK && r < 6 * rr.nk_b && d.active[m.u0 + 6 * rr.s_b + r]) Ys[(6 * rr.s_b + r) * 16 + 6 * qi + a] += rr.jt_b[6 * r + a];
+    }
+    if (tid == 0)
+      for (int qi = 0; qi < t.count; ++qi) {
+        const RelRec &rr = prec[t.first + qi];
+        if (rr.status == POSE_OK) s_first = min(s_first, 6 * min(rr.s_a, rr.s_b));
+      }
+  } else if (t.kind == 0) {
     if (tid < t.count) {
       const int j = sel[t.first + tid];
       if (d.active[m.u0 + j]) { Ys[j * 16 + tid] = 1.0; atomicMin(&s_first, j); }   // (an excluded unknown: a zero column, finished by k_cov_gram)
     }
   } else if (t.kind == 2) {   // rows 6 s .. 6 (s + nk) - 1 of every query's six columns, where the unknown is in the system
+    const PoseRec *prec2 = (const PoseRec *)prec;   // (REL: dead code, dropped after the constant branch above)
     for (int e = tid; e < 144 * t.count; e += COV_NT) {
       const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
-      const PoseRec &pr = prec[t.first + qi];
+      const PoseRec &pr = prec2[t.first + qi];
       if (pr.status == POSE_OK && r < 6 * pr.nk && d.active[m.u0 + 6 * pr.s + r]) Ys[(6 * pr.s + r) * 16 + 6 * qi + a] = pr.jt[6 * r + a];
     }
     if (tid == 0)
       for (int qi = 0; qi < t.count; ++qi)
-        if (prec[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * prec[t.first + qi].s);
+        if (prec2[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * prec2[t.first + qi].s);
   } else if (t.kind == 4) {   // pose columns 0..5 and velocity columns 6..8 over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the
                               // rows of bias state f, each where the unknown is in the system
     const NavRec &nr = nrec[t.first];
@@ -430,12 +540,12 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     __syncthreads();
   }
-  if (t.kind == 0) {   // a selection tile: Y to the scratch, for k_cov_gram
+  if (!REL && t.kind == 0) {   // a selection tile: Y to the scratch, for k_cov_gram
     double *yo = yscr + t.yoff;
     for (int e = tid; e < 16 * P; e += COV_NT) yo[e] = Ys[e];
     return;
   }
-  if (t.kind == 2) {   // pose tiles: the two 6 x 6 Gram blocks straight from Ys; every entry three partial sums over the rows k = p mod 3, added in sequence
+  if (REL || t.kind == 2) {   // pose and relative-pose tiles: the two 6 x 6 Gram blocks straight from Ys; every entry three partial sums over the rows k = p mod 3, added in sequence
     const int k0 = min(32 * b0, P) / 3 * 3;
     if (tid < 216) {
       const int p = tid / 72, e = tid % 72, ci = 6 * (e / 36) + (e % 36) / 6, cj = 6 * (e / 36) + e % 6;

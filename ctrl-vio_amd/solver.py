@@ -338,6 +338,30 @@ class Solver:
         """ctvio_nav_state: the same for the times t_ns of window wid alone (same bits as the batch entry)."""
         return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state(self._h, int(wid), n, t, f, s, c, st), t_ns, frame, cov)
 
+    def _relative_pose(self, call, t_a, t_b, q_SI, p_SI, cov, n_win=None):
+        ta = np.ascontiguousarray(t_a, np.int64).reshape(-1); tb = np.ascontiguousarray(t_b, np.int64).reshape(-1)
+        n = int(ta.shape[0])
+        assert tb.shape[0] == n and (n_win is None or n_win == n)
+        q, p = self._extrinsic(q_SI, p_SI)
+        rel = np.zeros((max(n, 1), 7)); c = np.zeros((max(n, 1), 6, 6)) if cov else None; st = np.zeros(max(n, 1), np.int32)
+        capi.check(call(n, capi._p(ta), capi._p(tb), capi._p(q), capi._p(p), capi._p(rel), capi._p(c) if cov else None, capi._p(st)))
+        return rel[:n].copy(), (c[:n].copy() if cov else None), st[:n].copy()
+
+    def relative_pose_batch(self, win, t_a, t_b, q_SI=None, p_SI=None, cov: bool = True):
+        """ctvio_relative_pose_batch: the pose increment T(t_a[i])^-1 T(t_b[i]) of window win[i] at the current state, as (p_ab, q_ab as
+        x, y, z, w), and with cov its 6 x 6 covariance in the tangent (dtheta, dp) of R_ab <- R_ab exp(dtheta), p_ab <- p_ab + dp (dp in frame
+        a).  q_SI = (x,y,z,w), p_SI: a sensor extrinsic (None: body poses).  Returns (rel7 (n, 7), cov (n, 6, 6) or None, status (n,)): 0 ok,
+        1 singular window (cov NaN), 2 an untouched knot (+inf diagonal), 3 a time outside the spline (NaN).  cov=False: one kernel, nothing
+        is linearised."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
+        return self._relative_pose(lambda n, ta, tb, q, p, r, c, st: self._lib.ctvio_relative_pose_batch(self._h, C.c_int64(n), capi._p(wi), ta, tb, q, p, r, c, st),
+                                   t_a, t_b, q_SI, p_SI, cov, int(wi.shape[0]))
+
+    def relative_pose(self, wid: int, t_a, t_b, q_SI=None, p_SI=None, cov: bool = True):
+        """ctvio_relative_pose: the same for the pairs of times of window wid alone (same bits as the batch entry)."""
+        return self._relative_pose(lambda n, ta, tb, q, p, r, c, st: self._lib.ctvio_relative_pose(self._h, int(wid), n, ta, tb, q, p, r, c, st),
+                                   t_a, t_b, q_SI, p_SI, cov)
+
     def _tri_options(self, opts):
         o = capi.TriangulateOptions()
         self._lib.ctvio_default_triangulate_options(C.byref(o))

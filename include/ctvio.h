@@ -296,6 +296,38 @@ int32_t ctvio_nav_state_batch(ctvio_solver *s, int64_t n, const int32_t *win, co
 int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225,
                         int32_t *status);
 
+/* The POSE INCREMENT between two times, T_ab = T(t_a)^-1 T(t_b), with its 6 x 6 covariance: what a pose-graph or loop-closure back end, a
+ * keyframe-to-keyframe "between" factor, a lidar or wheel fuser or a drift gate consumes.  The entries above describe one time in the window's
+ * own gauge, which the prior on the oldest knots fixes, so their uncertainty grows along the window; the increment carries the
+ * cross-covariance of the two times and is the gauge-free quantity.
+ * Query i = (window win[i], absolute times t_a_ns[i], t_b_ns[i]) at the CURRENT state.  Any number of queries, in any order, from any windows;
+ * t_b may lie before t_a or equal it.  Segment and u of each time by the integer-ns rule of ctvio_spline_eval; each time must lie in
+ * [t0, t0 + (K - 3) dt).  q_SI == p_SI == NULL: body poses; otherwise both poses are T_I(t) T_SI, exactly as in ctvio_pose_covariance.
+ *   rel7 (n x 7 doubles, or NULL): (p_ab, q_ab as x, y, z, w) with R_ab = R_a^T R_b, p_ab = R_a^T (p_b - p_a); q_ab is a unit quaternion
+ *   whose sign is whatever the product gives: compare it as a rotation.
+ *   cov36 (n x 36 doubles, row-major 6 x 6 per query, symmetric to the bit, or NULL): J_rel Sigma J_rel^T in the tangent (dtheta 0..2, dp 3..5)
+ *   of R_ab <- R_ab exp(dtheta), p_ab <- p_ab + dp (dp in frame a), with H, the exclusions and Sigma exactly those of ctvio_covariance_batch
+ *   (no damping).  With J_a, J_b the 6 x P Jacobians of ctvio_pose_covariance at the two times (the knots under the library's own retraction):
+ *     dtheta_ab = dtheta_b - R_ab^T dtheta_a,   dp_ab = [p_ab]x dtheta_a + R_a^T (dp_b - dp_a)
+ *     J_rel = A_a J_a + A_b J_b,   A_a = [[-R_ab^T, 0], [[p_ab]x, -R_a^T]],   A_b = [[I, 0], [0, R_a^T]].
+ *   Constant unknowns contribute nothing: a pair that depends on constant knots alone gives the exact zero matrix and status 0.
+ *   With cov36 == NULL nothing is linearised or factored: one kernel evaluates the values, and statuses 1 and 2 cannot occur; the values have
+ *   the bits of the covariance call's.
+ *   status (n entries, or NULL) per query, in this precedence: 3 either time outside the spline: value and covariance NaN;  2 a knot either
+ *   pose depends on (knot s + 3 only where u > 0) has a non-constant unknown no factor touches: value valid, +inf on the diagonal, 0
+ *   elsewhere;  1 the window's factorisation met a non-positive or non-finite pivot: value valid, covariance NaN;  0 ok.
+ * The call returns CTVIO_OK for every status.  n == 0 returns CTVIO_OK and launches nothing.  CTVIO_ERR_STATE before the upload;
+ * CTVIO_ERR_INVALID for a window id out of range, n < 0, a NULL win / t_a_ns / t_b_ns with n > 0, both outputs and status NULL with n > 0,
+ * exactly one of q_SI and p_SI NULL, a zero quaternion; the handle stays usable.  The state, the launch plan and the captured graph of the
+ * solve are left as they were; no atomics: where the linearisation is order-fixed (opt.deterministic) the bits of a query's result depend on
+ * its window and its two times alone -- not on the entry (batch or single-window: win is window id for every query), the order of the
+ * queries, or which query shares its tile; a second call repeats them.
+ * ctvio_last_timing: ms8[0..2] = k_cov_prepare, k_cov_solve, k_cov_rel_jac, ms8[7] the whole call; values only: ms8[2] and ms8[7]. */
+int32_t ctvio_relative_pose_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_a_ns, const int64_t *t_b_ns,
+                                  const double *q_SI, const double *p_SI, double *rel7, double *cov36, int32_t *status);
+int32_t ctvio_relative_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_a_ns, const int64_t *t_b_ns,
+                            const double *q_SI, const double *p_SI, double *rel7, double *cov36, int32_t *status);
+
 /* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
  * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
  * a slide (feature_manager.cpp:341-381, visual_odometry.cpp:299-308). */

@@ -28,6 +28,7 @@
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "ctvio.h"
@@ -561,6 +562,29 @@ class TrajectoryEstimator {
       ok = ok && status[i] == 0;
     }
     return ok;
+  }
+
+  // The pose increments T(t_a)^-1 T(t_b) of the pairs (t_a, t_b) (absolute times, inside the solved knots; t_b may lie before t_a) with their
+  // 6 x 6 covariances, at the CURRENT parameter values, from the factors of Solve (ctvio_relative_pose): what a pose-graph back end takes as a
+  // keyframe-to-keyframe "between" factor.  rel = pairs.size() x 7, (p_ab, q_ab as x, y, z, w) with R_ab = R_a^T R_b, p_ab = R_a^T (p_b - p_a);
+  // cov36 = pairs.size() x 36, row-major per pair, in the tangent (theta0..2, p0..2) of R_ab <- R_ab exp(dtheta), p_ab <- p_ab + dp (dp in
+  // frame a).  q_SI = (x,y,z,w), p_SI: a sensor extrinsic (e.g. traj.q_CI / p_CI for camera poses; both null: body poses).  Returns false if
+  // any status is not 0 (ctvio.h: a singular window or a time outside the spline give NaN, a knot no factor touches +inf).
+  bool GetRelativePoseCovariance(const std::vector<std::pair<int64_t, int64_t>> &pairs, std::vector<double> &rel, std::vector<double> &cov36,
+                                 const double *q_SI = nullptr, const double *p_SI = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    const size_t n = pairs.size();
+    std::vector<int64_t> ta(n), tb(n);
+    for (size_t i = 0; i < n; ++i) { ta[i] = pairs[i].first; tb[i] = pairs[i].second; }
+    rel.assign(7 * n, 0.0);
+    cov36.assign(36 * n, 0.0);
+    std::vector<int32_t> status(n, 0);
+    check(ctvio_relative_pose(s, 0, (int32_t)n, ta.data(), tb.data(), q_SI, p_SI, rel.data(), cov36.data(), status.data()));
+    for (int32_t st : status) if (st != 0) return false;
+    return true;
   }
 
   // FeatureManager::triangulate (feature_manager.cpp:226-274; row_times: its triangulateRS, :276-339) for the landmarks of the image factors

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Bit comparison of the covariance entries between two builds of the library, on one GPU.  `dump OUT.npz` runs ctvio_covariance_batch (with
-var_rho) and ctvio_pose_covariance_batch (body and camera pose) on the mixed batch of tests/test_gpu_covariance.py under deterministic = 2, at
-the initial state and after a 6-iteration solve, and ctvio_covariance with 64 scattered selections + var_rho on a solved `config1` window, with
-the library CTVIO_LIB_PATH names (default: the in-tree build), and saves every output and the solved state.  `compare A.npz B.npz` lists the
+var_rho), ctvio_pose_covariance_batch (body and camera pose), ctvio_landmark_points_batch and ctvio_nav_state_batch -- the tiles of kinds 0 to
+4 of k_cov_solve -- on the mixed batch of tests/test_gpu_covariance.py under deterministic = 2, at the initial state and after a 6-iteration
+solve, and ctvio_covariance with 64 scattered selections + var_rho on a solved `config1` window, with the library CTVIO_LIB_PATH names
+(default: the in-tree build), and saves every output and the solved state.  `compare A.npz B.npz` lists the
 arrays whose bits differ (exit status 1 if any).  Not a test: the second build has to come from another checkout.
 usage: python tools/covariance_bits.py dump new.npz; CTVIO_LIB_PATH=/other/libctvio.so python tools/covariance_bits.py dump old.npz;
        python tools/covariance_bits.py compare new.npz old.npz"""
@@ -21,10 +22,12 @@ def dump(path):
     cv = importlib.import_module("ctrl-vio_amd")
     import cov_helpers as ch
     from test_gpu_covariance import DET, mixed_batch
+    from test_gpu_nav_state import mixed_queries as nav_queries
     from test_gpu_pose_covariance import mixed_queries
     out = {}
     ws, sels = mixed_batch(cv)
     win, t = mixed_queries(ws)
+    nwin, nt, nf = nav_queries(ws)
     with cv.Solver(**DET) as s:
         s.set_windows([w.copy() for w in ws])
         for tag in ("init", "solved"):
@@ -34,6 +37,8 @@ def dump(path):
             out[f"{tag}_singular"] = sing
             out[f"{tag}_pose"], out[f"{tag}_pose_status"] = s.pose_covariance_batch(win, t)
             out[f"{tag}_pose_camera"], _ = s.pose_covariance_batch(win, t, ws[1].q_CI, ws[1].p_CI)
+            out[f"{tag}_points"], out[f"{tag}_points_cov"], out[f"{tag}_points_status"] = s.landmark_points_batch()
+            out[f"{tag}_nav"], out[f"{tag}_nav_cov"], out[f"{tag}_nav_status"] = s.nav_state_batch(nwin, nt, nf)
             s.solve(6, writeback=False)
         for i, a in enumerate(s.get_batch_state()):
             out[f"state{i}"] = a
