@@ -1557,6 +1557,155 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // ctvio_imu_predict_batch / ctvio_imu_predict (only >= 0: every query belongs to that window, win is not read): the navigation state of
+  // query i at imu_t[first sample of i] (bias state frame[i]; frame null: the newest) carried through the query's n_imu[i] samples by
+  // k_imu_propagate, with its 15 x 15 covariance.  The middle is nav_state()'s: queries grouped by window (stable), k_cov_nav_jac, and with
+  // cov225 cov_factor and k_cov_solve on tiles of kind 4, whose slot is the query's first output entry, so that P_0 lands where sample 0
+  // is reported.  The samples of all queries are staged with the queries in one copy.  dev_, plan_ and the captured graph are not touched.
+  int imu_predict(int only, int64_t n64, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t, const double *imu_gyro,
+                  const double *imu_acc, const ctvio_imu_noise *noise, int last_only, double *state16, double *cov225, int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (n64 < 0 || n64 > (int64_t)1 << 30 ||
+        (n64 && (!n_imu || !imu_t || !imu_gyro || !imu_acc || !noise || (only < 0 && !win) || (!state16 && !cov225 && !status))))
+      return fail(CTVIO_ERR_INVALID, "bad arguments");
+    const int n = (int)n64, nw = dev_.nwin;
+    const size_t nn = (size_t)n;
+    if (n == 0) return CTVIO_OK;
+    {
+      const double sg[4] = {noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
+      for (double x : sg)
+        if (!(x >= 0.0) || !std::isfinite(x)) return fail(CTVIO_ERR_INVALID, "a noise sigma is negative or not finite");
+    }
+    std::vector<int64_t> first(nn + 1, 0);   // first sample of every query (the caller's order)
+    for (int i = 0; i < n; ++i) {
+      const int w = only >= 0 ? only : win[i];
+      const std::string what = "query " + std::to_string(i);
+      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, what + ": window id out of range");
+      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, what + ": bias state out of range");
+      if (n_imu[i] < 1 || n_imu[i] > 4096) return fail(CTVIO_ERR_INVALID, what + ": 1 to 4096 samples");
+      const int64_t b = first[(size_t)i], e = b + n_imu[i];
+      first[(size_t)i + 1] = e;
+      for (int64_t j = b; j < e; ++j) {
+        if (j > b && imu_t[j] <= imu_t[j - 1]) return fail(CTVIO_ERR_INVALID, what + ": sample times not strictly increasing");
+        for (int c = 0; c < 3; ++c)
+          if (!std::isfinite(imu_gyro[3 * j + c]) || !std::isfinite(imu_acc[3 * j + c])) return fail(CTVIO_ERR_INVALID, what + ": a measurement is not finite");
+      }
+    }
+    const size_t ns = (size_t)first[nn], no = last_only ? nn : ns;   // samples; output entries
+    if (ns > (size_t)1 << 30) return fail(CTVIO_ERR_INVALID, "more than 2^30 samples in one call");
+    auto entry0 = [&](size_t i) { return last_only ? (int64_t)i : first[i]; };
+    auto entries = [&](size_t i) { return last_only ? (size_t)1 : (size_t)n_imu[i]; };
+    // ---- queries by window; slot[r]: the caller's index of sorted query r
+    std::vector<int32_t> slot(nn);
+    for (int i = 0; i < n; ++i) slot[i] = i;
+    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    const bool want_cov = cov225 != nullptr;
+    // ---- scratch.  io: queries, propagation queries, sample times and measurements, entries, tiles (in, one staged copy); cov225 | state16 |
+    // status (out, one copy).  scr: mask, exclusions, records, the states at sample 0
+    CallLayout io = head_, scr;
+    const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_pq = io.add("prop", sizeof(PropQuery), nn, false),
+              s_t = io.add("imu_t", sizeof(int64_t), ns, false), s_gyro = io.add("imu_gyro", sizeof(double), 3 * ns, false),
+              s_acc = io.add("imu_acc", sizeof(double), 3 * ns, false), s_slot = io.add("entry", sizeof(int32_t), want_cov ? nn : 0, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), want_cov ? nn : 0, false),
+              s_cov = io.add("cov225", sizeof(double), want_cov ? 225 * no : 0, true), s_state = io.add("state16", sizeof(double), 16 * no, true),
+              s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, want_cov ? (size_t)dev_.Utot : 0, false), s_excl = scr.add("excl", 1, want_cov ? (size_t)dev_.Utot : 0, false),
+              s_rec = scr.add("records", sizeof(NavRec), want_cov ? nn : 0, false), s_x0 = scr.add("state0", sizeof(double), 16 * nn, true);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    NavQuery *hq = io_host<NavQuery>(io, s_q);
+    PropQuery *hp = io_host<PropQuery>(io, s_pq);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      const int w = win_of(r);
+      hq[r] = NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(imu_t[first[i]] - t0_[w])};
+      hp[r] = PropQuery{w, n_imu[i], (long long)first[i], (long long)entry0(i)};
+      if (want_cov) {
+        io_host<int32_t>(io, s_slot)[r] = (int32_t)entry0(i);
+        io_host<CovTile>(io, s_tiles)[r] = CovTile{w, 4, r, 1, 0};
+      }
+    }
+    std::memcpy(io_host<int64_t>(io, s_t), imu_t, sizeof(int64_t) * ns);
+    std::memcpy(io_host<double>(io, s_gyro), imu_gyro, sizeof(double) * 3 * ns);
+    std::memcpy(io_host<double>(io, s_acc), imu_acc, sizeof(double) * 3 * ns);
+    const ImuNoise nz{noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
+    double *x0 = scr.at<double>(call_scr_.dev, s_x0);
+    const size_t in_bytes = io.off(want_cov ? s_cov : s_state) - io.off(s_q), out0 = io.off(want_cov ? s_cov : s_state);
+    auto propagate = [&]() {
+      hipLaunchKernelGGL(k_imu_propagate, dim3(nblk(n, 4)), dim3(64), 0, stream_, dev_, n, io_dev<PropQuery>(io, s_pq), io_dev<int32_t>(io, s_stat),
+                         io_dev<long long>(io, s_t), io_dev<double>(io, s_gyro), io_dev<double>(io, s_acc), nz, last_only ? 1 : 0, (const double *)x0,
+                         io_dev<double>(io, s_state), want_cov ? io_dev<double>(io, s_cov) : (double *)nullptr);
+    };
+    Timing tm;
+    tm.clear();
+    auto elapsed = [&](int k, Ev a, Ev b) {
+      float ms = 0;
+      const hipError_t e = hipEventElapsedTime(&ms, ev_[a], ev_[b]);
+      tm.ms[k] = ms; tm.n[k] = 1;
+      return e;
+    };
+    if (!want_cov) {
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)nullptr, (NavRec *)nullptr,
+                         x0, io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      propagate();
+      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), io.bytes() - out0, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      HIPCHK(elapsed(2, EV_QUERY_BEGIN, EV_QUERY_END));
+      HIPCHK(elapsed(3, EV_QUERY_END, EV_COV_GRAM));
+    } else {
+      uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+      NavRec *drec = scr.at<NavRec>(call_scr_.dev, s_rec);
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
+      Dev c;
+      if (const int rc = cov_factor(c, mask, excl)) return rc;
+      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec, x0,
+                         io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+      hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles), io_dev<int32_t>(io, s_slot),
+                         (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0,
+                         drec, io_dev<double>(io, s_cov));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      propagate();
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - out0, hipMemcpyDeviceToHost, stream_));   // (cov225 | state16 | status)
+      HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+      if (const int rc = finish_call(io)) return rc;
+      HIPCHK(elapsed(0, EV_COV_PREPARE, EV_COV_FACTOR));
+      HIPCHK(elapsed(1, EV_COV_GRAM, EV_QUERY_BEGIN));
+      HIPCHK(elapsed(2, EV_COV_SOLVE, EV_COV_GRAM));
+      HIPCHK(elapsed(3, EV_QUERY_BEGIN, EV_QUERY_END));
+    }
+    if (const int rc = publish_timing(tm, 0)) return rc;
+    // ---- results, every entry of a query by the query's status (time outside the spline: NaN; an untouched knot or bias state: +inf on the
+    // diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN covariances)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
+    const double *hcov = want_cov ? io_host<double>(io, s_cov) : nullptr, *hstate = io_host<double>(io, s_state);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r], e0 = (size_t)entry0(i), ne = entries(i);
+      int st = hstat[r];
+      if (want_cov && st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
+      if (want_cov) {
+        double *o = cov225 + 225 * e0;
+        if (st == POSE_OK) std::memcpy(o, hcov + 225 * e0, sizeof(double) * 225 * ne);
+        else for (size_t e = 0; e < 225 * ne; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 225 % 16 == 0 ? inf : 0.0) : nan;
+      }
+      if (state16) {
+        if (st != POSE_OUTSIDE) std::memcpy(state16 + 16 * e0, hstate + 16 * e0, sizeof(double) * 16 * ne);
+        else std::fill(state16 + 16 * e0, state16 + 16 * (e0 + ne), nan);
+      }
+      if (status) status[i] = st;
+    }
+    return CTVIO_OK;
+  }
   // ctvio_relative_pose_batch / ctvio_relative_pose (only >= 0: every query belongs to that window, win is not read): the pose increment
   // T(t_a)^-1 T(t_b) of n pairs of times and J_rel Sigma J_rel^T of its six tangent dimensions.  Values only (cov36 null): k_cov_rel_jac
   // alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a window's queries keep the caller's
@@ -1984,6 +2133,22 @@ int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.nav_state(id, n, nullptr, t_ns, frame, state16, cov225, status);
+}
+void ctvio_default_imu_noise(ctvio_imu_noise *o) {
+  if (!o) return;
+  o->gyr_n = 4.0e-3; o->acc_n = 8.0e-2; o->gyr_w = 2.0e-6; o->acc_w = 4.0e-5;
+}
+int32_t ctvio_imu_predict_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t,
+                                const double *imu_gyro, const double *imu_acc, const ctvio_imu_noise *noise, int32_t last_only, double *state16,
+                                double *cov225, int32_t *status) {
+  CHK_S; return s->impl.imu_predict(-1, n, win, frame, n_imu, imu_t, imu_gyro, imu_acc, noise, last_only, state16, cov225, status);
+}
+int32_t ctvio_imu_predict(ctvio_solver *s, int32_t id, int32_t frame, int32_t m, const int64_t *imu_t, const double *imu_gyro, const double *imu_acc,
+                          const ctvio_imu_noise *noise, int32_t last_only, double *state16, double *cov225, int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  if (frame < -1) return ctv::fail(CTVIO_ERR_INVALID, "bias state out of range");
+  return s->impl.imu_predict(id, 1, nullptr, frame >= 0 ? &frame : nullptr, &m, imu_t, imu_gyro, imu_acc, noise, last_only, state16, cov225, status);
 }
 int32_t ctvio_relative_pose_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_a_ns, const int64_t *t_b_ns, const double *q_SI,
                                   const double *p_SI, double *rel7, double *cov36, int32_t *status) {

@@ -465,6 +465,48 @@ CTV_DI void rel_pose_jac_T(Q4 q_a, V3 p_a, Q4 q_b, V3 p_b, double *jt_a, double 
   }
 }
 
+// One midpoint step of the IMU dead reckoning (ctvio_imu_predict; the mean of VisualOdometry::ProcessIMU, visual_odometry.cpp:137-172) from
+// sample (w0, a0) to sample (w1, a1), dt apart, with the biases (bg, ba) held and g the window's gravity (sign as in the IMU factor):
+//   w = (w0 + w1) / 2 - bg,  R' = R Exp(w dt),  A = ((R (a0 - ba) - g) + (R' (a1 - ba) - g)) / 2,  p' = p + dt v + dt^2 A / 2,  v' = v + dt A.
+// (q, p, v) are advanced in place.  With want_jac the 3 x 3 blocks of F = d(state') / d(state) and G = d(state') / d(noise) that are not 0, I
+// or dt I, in the tangent (dtheta, dp, dv, dbg, dba) of R <- R Exp(dtheta), the rest additive, with E = Exp(w dt), J = Jr(w dt), u0 = a0 - ba,
+// u1 = a1 - ba:
+//   F[theta, theta] = E^T            F[theta, bg] = -J dt
+//   F[v, theta] = -dt (R [u0] + R' [u1] E^T) / 2     F[v, bg] = dt^2 R' [u1] J / 2     F[v, ba] = -dt (R + R') / 2
+//   F[p, .] = (dt / 2) F[v, .] in the same three columns (beside F[p, p] = I, F[p, v] = dt I: formed by the caller, not stored)
+//   G: gyro noise of either sample -F[., bg] / 2 on the rows theta, p, v; accelerometer noise of sample 0 / 1: dt R0 / 2, dt R1 / 2 on the v
+//   rows and dt / 2 times that on the p rows (R0 = R, R1 = R'); the bias walks dt I on their own rows.
+// The mean does not depend on want_jac: it is formed first, by the same operations.
+struct ImuStepJac {
+  M3 Ett, Ftg;             // F[theta, theta], F[theta, bg]
+  M3 Fvt, Fvg, Fva;        // F[v, theta], F[v, bg], F[v, ba]
+  M3 R0, R1;               // R and R'
+};
+CTV_DI void imu_step(Q4 &q, V3 &p, V3 &v, V3 bg, V3 ba, V3 g, V3 w0, V3 a0, V3 w1, V3 a1, double dt, bool want_jac, ImuStepJac &J) {
+  const V3 u0 = a0 - ba, u1 = a1 - ba;
+  const V3 phi = dt * (0.5 * (w0 + w1) - bg);
+  const Q4 e = so3_exp(phi);
+  const Q4 q1 = qmul_unit(q, e);
+  const M3 R0 = q2R(q), R1 = q2R(q1);
+  const V3 A = 0.5 * ((mul(R0, u0) - g) + (mul(R1, u1) - g));
+  p = p + dt * v + (0.5 * dt * dt) * A;
+  v = v + dt * A;
+  q = q1;
+  if (!want_jac) return;
+  const M3 E = q2R(e), Jr = so3_Jr(phi);
+  const M3 Ru0 = mul_hat(R0, u0), Ru1 = mul_hat(R1, u1);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) J.Ett.m[3 * i + j] = E.m[3 * j + i];
+  J.Ftg = scale(Jr, -dt);
+  J.Fvt = scale(add(Ru0, mulT(Ru1, E)), -0.5 * dt);
+  J.Fvg = scale(mul(Ru1, Jr), 0.5 * dt * dt);
+  J.Fva = scale(add(R0, R1), -0.5 * dt);
+  J.R0 = R0;
+  J.R1 = R1;
+}
+
 // Streaming forms of the two views: the per-knot partial Jacobians are handed to `f(knot, J)` one at a time, as soon as they
 // are final, instead of being returned as four 3 x 3 matrices -- the same operations in the same order (bit-identical
 // values), but only ~5 matrices are live at any time (the array forms keep 11, i.e. ~200 fp64 registers for both ends).

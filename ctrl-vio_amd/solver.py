@@ -362,6 +362,57 @@ class Solver:
         return self._relative_pose(lambda n, ta, tb, q, p, r, c, st: self._lib.ctvio_relative_pose(self._h, int(wid), n, ta, tb, q, p, r, c, st),
                                    t_a, t_b, q_SI, p_SI, cov)
 
+    def _imu_noise(self, noise):
+        o = capi.ImuNoise()
+        self._lib.ctvio_default_imu_noise(C.byref(o))
+        if noise is None:
+            return o
+        if isinstance(noise, dict):
+            for k, v in noise.items():
+                if not hasattr(o, k):
+                    raise KeyError(k)
+                setattr(o, k, float(v))
+            return o
+        o.gyr_n, o.acc_n, o.gyr_w, o.acc_w = (float(x) for x in noise)
+        return o
+
+    def _imu_predict(self, call, m, imu_t, gyro, acc, noise, last_only, cov):
+        """m: samples per query (n,); the concatenated samples.  Returns (state (E, 16), cov (E, 15, 15) or None, status (n,)), E = sum m, or n
+        with last_only."""
+        t = np.ascontiguousarray(imu_t, np.int64).reshape(-1)
+        g = np.ascontiguousarray(gyro, np.float64).reshape(-1, 3)
+        a = np.ascontiguousarray(acc, np.float64).reshape(-1, 3)
+        n = int(m.shape[0])
+        ns = int(t.shape[0])
+        assert g.shape[0] == ns and a.shape[0] == ns and (n == 0 or int(np.clip(m, 0, None).sum()) <= ns)
+        ne = n if last_only else ns
+        state = np.zeros((max(ne, 1), 16)); c = np.zeros((max(ne, 1), 15, 15)) if cov else None; st = np.zeros(max(n, 1), np.int32)
+        capi.check(call(capi._p(t), capi._p(g), capi._p(a), C.byref(self._imu_noise(noise)), 1 if last_only else 0, capi._p(state),
+                        capi._p(c) if cov else None, capi._p(st)))
+        return state[:ne].copy(), (c[:ne].copy() if cov else None), st[:n].copy()
+
+    def imu_predict_batch(self, win, frame, n_imu, imu_t, gyro, acc, noise=None, last_only: bool = False, cov: bool = True):
+        """ctvio_imu_predict_batch: IMU dead reckoning (midpoint rule) from the navigation state of window win[i] at the first of its n_imu[i]
+        samples, with bias state frame[i] (frame None: the newest), through the samples -- concatenated in query order: absolute times imu_t
+        (ns), gyro and acc (.., 3) -- and with cov the 15 x 15 covariance P_j = F P F^T + G Q G^T in the tangent of nav_state.  noise: (gyr_n,
+        acc_n, gyr_w, acc_w), a dict of some of them, or None for the reference's defaults.  Returns (state (E, 16), cov (E, 15, 15) or None,
+        status (n,)): E = sum n_imu entries in query then sample order (sample 0 = nav_state's output), or, last_only, one per query: its last
+        sample.  Statuses as nav_state's, per query."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
+        m = np.ascontiguousarray(n_imu, np.int32).reshape(-1)
+        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
+        assert m.shape[0] == wi.shape[0] and (fr is None or fr.shape[0] == wi.shape[0])
+        return self._imu_predict(lambda t, g, a, nz, lo, s, c, st: self._lib.ctvio_imu_predict_batch(
+            self._h, C.c_int64(int(wi.shape[0])), capi._p(wi), capi._p(fr), capi._p(m), t, g, a, nz, lo, s, c, st), m, imu_t, gyro, acc, noise,
+            last_only, cov)
+
+    def imu_predict(self, wid: int, frame, imu_t, gyro, acc, noise=None, last_only: bool = False, cov: bool = True):
+        """ctvio_imu_predict: one query of window wid (frame None or -1: the newest bias state) with len(imu_t) samples; the batch entry's bits."""
+        m = np.array([np.asarray(imu_t).reshape(-1).shape[0]], np.int32)
+        f = -1 if frame is None else int(frame)
+        return self._imu_predict(lambda t, g, a, nz, lo, s, c, st: self._lib.ctvio_imu_predict(self._h, int(wid), f, int(m[0]), t, g, a, nz, lo, s, c, st),
+                                 m, imu_t, gyro, acc, noise, last_only, cov)
+
     def _tri_options(self, opts):
         o = capi.TriangulateOptions()
         self._lib.ctvio_default_triangulate_options(C.byref(o))

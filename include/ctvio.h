@@ -328,6 +328,53 @@ int32_t ctvio_relative_pose_batch(ctvio_solver *s, int64_t n, const int32_t *win
 int32_t ctvio_relative_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_a_ns, const int64_t *t_b_ns,
                             const double *q_SI, const double *p_SI, double *rel7, double *cov36, int32_t *status);
 
+/* BETWEEN FRAMES: IMU dead reckoning from the navigation state, with its 15 x 15 covariance -- what VisualOdometry::ProcessIMU
+ * (visual_odometry.cpp:137-172) does with the state SlideWindow hands it, and where AddImageToWindow (:188-191) takes the predicted pose of
+ * the next frame from; beside the mean, the first-order covariance that IntegrationBase::midPointIntegration (integration_base.h:100-179)
+ * carries through the same recurrence (F, G, noise_covariance).
+ * Query i = (window win[i], bias state frame[i] in [0, F), m_i = n_imu[i] samples); frame == NULL: F - 1 for every query.  The samples of all
+ * queries are concatenated in query order: absolute times imu_t (ns), imu_gyro and imu_acc as 3 doubles each.  Sample 0 of a query is the
+ * measurement at the start: the state and covariance at imu_t[0] are exactly those of ctvio_nav_state_batch at (win, imu_t[0], frame) -- the same
+ * reduced system, exclusions, tangent (dtheta 0..2, dp 3..5, dv 6..8, dbg 9..11, dba 12..14) and statuses, the same bits.
+ * Sample j >= 1 is one midpoint step with dt = (imu_t[j] - imu_t[j - 1]) * 1e-9, the formulas of ProcessIMU:
+ *   w  = (w_{j-1} + w_j) / 2 - bg             R' = R Exp(w dt)
+ *   A  = ((R (a_{j-1} - ba) - g) + (R' (a_j - ba) - g)) / 2      g = the window's `gravity` (sign as in the IMU factor)
+ *   p' = p + dt v + dt^2 A / 2                v' = v + dt A      bg, ba unchanged
+ * Exp is the exact exponential; the reference's Utility::deltaQ is its first-order quaternion (1, w dt / 2), normalised later: the two agree
+ * to O(|w dt|^3) per step.
+ * Covariance: P_j = F P_{j-1} F^T + G Q G^T with F and G the EXACT Jacobians of this step map in the tangent above (R <- R Exp(dtheta), the rest
+ * additive) and additive noise per sample (n_g0, n_a0, n_g1, n_a1, n_bg, n_ba), as the reference's 18-column G has it.  With E = Exp(w dt),
+ * J = Jr(w dt), [.] the hat map, u0 = a_{j-1} - ba, u1 = a_j - ba, A_th = -(R [u0] + R' [u1] E^T) / 2, A_g = R' [u1] J dt / 2, A_a = -(R + R') / 2:
+ *   F = [ E^T          0  0     -J dt        0          ]    G (rows theta, p, v): n_g0 = n_g1 = -F[., bg] / 2;
+ *       [ dt^2 A_th/2  I  dt I  dt^2 A_g/2   dt^2 A_a/2 ]      n_a0: p dt^2 R / 4, v dt R / 2;  n_a1: p dt^2 R' / 4, v dt R' / 2;
+ *       [ dt A_th      0  I     dt A_g       dt A_a     ]      n_bg: dt I on the bg rows;  n_ba: dt I on the ba rows
+ *       [ 0 0 0 I 0 ] [ 0 0 0 0 I ]                          Q = diag(gyr_n^2, acc_n^2, gyr_n^2, acc_n^2, gyr_w^2, acc_w^2) (x) I_3
+ * The sigmas are taken as IntegrationBase takes them: per-sample standard deviations, the bias walk enters as sigma dt; the correlation of
+ * consecutive steps through their shared sample is neglected, as there.  The reference's F is the first-order form of these blocks (I - [w] dt
+ * for E^T, J = I): at 1 rad/s and 5 ms the entries differ by 2.5e-3 relative.
+ *   state16 (or NULL): as ctvio_nav_state's; the biases are those of the chosen state for every sample.   cov225 (or NULL): row-major,
+ *   symmetric to the bit.  Each holds sum m_i entries in query order, then sample order, sample 0 included; with last_only != 0 each holds n
+ *   entries, the last sample of each query.  status (or NULL): one entry per query, the precedence of ctvio_nav_state: 3 imu_t[0] outside
+ *   [t0, t0 + (K - 3) dt): states and covariances NaN;  2 an untouched non-constant unknown under the start state: states valid for every
+ *   sample, +inf on the diagonal and 0 elsewhere for every sample;  1 bad pivot in the window's factorisation: states valid, covariances NaN;
+ *   0 ok.  Constant unknowns contribute nothing to P_0.  With cov225 == NULL nothing is linearised or factored (statuses 1 and 2 cannot
+ *   occur) and the states have the bits of the covariance call's.
+ * The call returns CTVIO_OK for every status, and for n == 0, where it launches nothing.  CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID
+ * for a window id or frame out of range, n < 0, a NULL n_imu / imu_t / imu_gyro / imu_acc / noise (batch: win) with n > 0, all three outputs
+ * NULL with n > 0, m_i < 1 or m_i > 4096, sample times of a query that are not strictly increasing, a non-finite measurement, a negative or
+ * non-finite sigma; the handle stays usable.  The state, the launch plan and the captured graph of the solve are left as they were; no atomics:
+ * where the linearisation is order-fixed (opt.deterministic) the bits of a query's outputs depend on its window, frame, samples and sigmas
+ * alone -- not on the entry (batch or single), the order of the queries, which queries share a wave or a call, or last_only. */
+typedef struct ctvio_imu_noise { double gyr_n, acc_n, gyr_w, acc_w; } ctvio_imu_noise;  /* GYR_N, ACC_N, GYR_W, ACC_W */
+void ctvio_default_imu_noise(ctvio_imu_noise *o);   /* 4.0e-3, 8.0e-2, 2.0e-6, 4.0e-5: reference parameters.cpp:13-16 */
+int32_t ctvio_imu_predict_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int32_t *frame, const int32_t *n_imu,
+                                const int64_t *imu_t, const double *imu_gyro, const double *imu_acc, const ctvio_imu_noise *noise,
+                                int32_t last_only, double *state16, double *cov225, int32_t *status);
+/* One query of window id (frame -1: the newest bias state) with m samples: the same bits as the batch entry. */
+int32_t ctvio_imu_predict(ctvio_solver *s, int32_t id, int32_t frame, int32_t m, const int64_t *imu_t, const double *imu_gyro,
+                          const double *imu_acc, const ctvio_imu_noise *noise, int32_t last_only, double *state16, double *cov225,
+                          int32_t *status);
+
 /* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
  * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
  * a slide (feature_manager.cpp:341-381, visual_odometry.cpp:299-308). */
@@ -458,6 +505,8 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * After a navigation-state call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution and the 15 x 15 blocks), k_cov_nav_jac,
  * ms8[7] = the whole call on the device, the rest zero; states only (cov225 == NULL): ms8[2] = device time of k_cov_nav_jac, ms8[7] = the
  * whole call on the device (its copies included), the rest zero.
+ * After an IMU-prediction call: ms8[0..2] as after a navigation-state call, ms8[3] = device time of k_imu_propagate, ms8[7] = the whole call on
+ * the device, the rest zero; states only (cov225 == NULL): ms8[2], ms8[3] and ms8[7].
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

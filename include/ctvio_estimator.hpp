@@ -587,6 +587,46 @@ class TrajectoryEstimator {
     return true;
   }
 
+  // IMU dead reckoning between frames (ctvio_imu_predict): what VisualOdometry::ProcessIMU (visual_odometry.cpp:137-172) does with the state
+  // SlideWindow hands it, and what AddImageToWindow (:188-191) reads the next frame's predicted pose from.  samples[0] is the measurement at
+  // the start -- its timestamp must lie inside the solved knots, the newest frame time in the reference's use --, every further sample one
+  // midpoint step.  states = one IMUState per sample (samples[0]: GetIMUStateCovariance's); cov225 = samples.size() x 225, row-major per
+  // sample, the tangent of GetIMUStateCovariance, propagated as IntegrationBase::midPointIntegration propagates it, with the exact
+  // Jacobians of the step (ctvio.h).  The biases are those of the state whose gyro-bias pointer is bias_gyr (nullptr: the newest).  Returns
+  // false if the status is not 0.
+  bool PredictIMUStates(const std::vector<IMUData> &samples, const double *bias_gyr, const ctvio_imu_noise &noise, std::vector<IMUState> &states,
+                        std::vector<double> &cov225) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t m = samples.size();
+    int32_t frame = -1;
+    if (bias_gyr) {
+      auto it = bias_of_.find(bias_gyr);
+      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("PredictIMUStates: not a bias state of this window");
+      frame = pk.bias_map[(size_t)it->second];
+    }
+    std::vector<int64_t> t(m);
+    std::vector<double> gyro(3 * m), acc(3 * m);
+    for (size_t j = 0; j < m; ++j) {
+      t[j] = samples[j].timestamp;
+      for (int c = 0; c < 3; ++c) { gyro[3 * j + c] = samples[j].gyro[c]; acc[3 * j + c] = samples[j].accel[c]; }
+    }
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    std::vector<double> state16(16 * m);
+    int32_t status = 0;
+    cov225.assign(225 * m, 0.0);
+    check(ctvio_imu_predict(s, 0, frame, (int32_t)m, t.data(), gyro.data(), acc.data(), &noise, 0, state16.data(), cov225.data(), &status));
+    states.assign(m, IMUState());
+    for (size_t j = 0; j < m; ++j) {
+      const double *o = state16.data() + 16 * j;
+      states[j].timestamp = t[j];
+      for (int c = 0; c < 3; ++c) { states[j].p[c] = o[c]; states[j].v[c] = o[7 + c]; }
+      for (int c = 0; c < 4; ++c) states[j].q[c] = o[3 + c];
+    }
+    return status == 0;
+  }
+
   // FeatureManager::triangulate (feature_manager.cpp:226-274; row_times: its triangulateRS, :276-339) for the landmarks of the image factors
   // added so far, at the CURRENT parameter values (ctvio_triangulate): every inverse-depth parameter that is <= 0 (only_unset) or every one
   // receives 1 / depth in place, as the reference writes estimated_depth.  flags (optional): one ctvio_triangulate flag per inverse-depth
