@@ -168,17 +168,6 @@ CTV_DI void imu_eval_core(const Knots4 &k, const SC &sc, double u, double idt, V
   }
 }
 
-// Gyro row a on the product kernel's compact 16 columns [rot k0..k3 (12) | bg (3) | r]
-CTV_DI void imu_row_gyro2(const M3 (&Jw)[4], const double w[6], const double r[6], int a, double out[16]) {
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) out[3 * kk + b] = w[a] * Jw[kk].m[3 * a + b];
-  out[12] = out[13] = out[14] = 0.0;
-  out[12 + a] = w[a];
-  out[15] = r[a];
-}
-
 // ---- Staged form (k_imu_linearize_f64's product path: values, then the gyro Jacobians, then the accelerometer Jacobians, each stage's
 // rows consumed before the next starts, so the two 36-entry Jacobians are never live together), algebraically the same Jacobian with the rotation chain of the accelerometer
 // rows rewritten: with A_i = exp(lamR[i+1] d_i), Apost_i = (A_i .. A_2)^T and R(t)^T = Apost_0 R_0^T,
@@ -228,46 +217,78 @@ CTV_DI void imu_eval_values3(const double *gc, const SC &sc, double u, double id
   r[4] = w[4] * (a_pred.y - (acc[1] - gc[28]));
   r[5] = w[5] * (a_pred.z - (acc[2] - gc[29]));
 }
-// M (3 x 3) against the knot-pair table: J[i] -= M JrI_i^T, J[i + 1] += M JrI_i
-template <class SC> CTV_DI void imu_apply_pair(const M3 &M, const SC &sc, int i, M3 &Ji, M3 &Ji1, bool first) {
-  const M3 JrIi = sc.jri(i);
-  const M3 A = mulT(M, JrIi), B = mul(M, JrIi);
-#pragma unroll
-  for (int e = 0; e < 9; ++e) { Ji.m[e] = first ? -A.m[e] : Ji.m[e] - A.m[e]; Ji1.m[e] = B.m[e]; }
+// ---- Pair-log coordinates.  Every rotation column of a sample goes through the knot-pair table: with M_i (3 x 3) the derivative of a
+// sensor's rows with respect to the pair log d_i, knot i receives -M_i JrI_i^T and knot i + 1 receives +M_i JrI_i, so
+//   J_rot (3 x 12) = [D0 | M_0 M_1 M_2] (3 x 12) * T (12 x 12),   T = [I3 at knot 0 ; rows (i, e): -JrI_i^T at knot i, +JrI_i at knot i + 1]
+// (D0 = Apost_0 hat(b_0), the accelerometer's direct term on knot 0; zero for the gyro).  T is a constant of the group: the per-sample rows
+// are streamed in the COMPACT order [D0 3 | M_0 M_1 M_2 9 | bias 3 | r] (16 columns for either sensor), their Gram matrix G^ is accumulated
+// as it is, and the group pays T^T G^ T once (T extended by the identity on bias and residual) instead of six M JrI products per sample.
+// Entry JrI_i[a][b] lands on two places of the row-major 16 x 16 T: `plus` with its own sign, `minus` negated.
+CTV_DI void imu_pairlog_slots(int i, int a, int b, int &plus, int &minus) {
+  plus = (3 + 3 * i + a) * 16 + 3 * (i + 1) + b;
+  minus = (3 + 3 * i + b) * 16 + 3 * i + a;
 }
-template <class SC> CTV_DI void imu_jac_gyro3(const ImuMid3 &md, const SC &sc, M3 (&Jw)[4]) {
-  imu_apply_pair(scale(md.Apost[1], md.lamW[1]), sc, 0, Jw[0], Jw[1], true);
-  imu_apply_pair(add(scale(mul(mul_hat(md.Apost[1], md.om1), md.JrK[1]), md.lamR[2]), scale(md.Apost[2], md.lamW[2])), sc, 1, Jw[1], Jw[2], false);
-  M3 dod = scale(mul(mul_hat(md.Apost[2], md.om2), md.JrK[2]), md.lamR[3]);
-  dod.m[0] += md.lamW[3]; dod.m[4] += md.lamW[3]; dod.m[8] += md.lamW[3];
-  imu_apply_pair(dod, sc, 2, Jw[2], Jw[3], false);
+template <class SC> CTV_DI void imu_pairlog_T(const SC &sc, double T[256]) {
+  for (int e = 0; e < 256; ++e) T[e] = 0.0;
+  for (int k = 0; k < 16; ++k)
+    if (k < 3 || k >= 12) T[17 * k] = 1.0;
+  for (int i = 0; i < 3; ++i) {
+    const M3 J = sc.jri(i);
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        int plus, minus;
+        imu_pairlog_slots(i, a, b, plus, minus);
+        T[plus] = J.m[3 * a + b];
+        T[minus] = -J.m[3 * a + b];
+      }
+  }
 }
-// R(t)^T = Apost_0 R_0^T (gc[12..20])
-template <class SC> 
-CTV_DI void imu_jac_accel3(const ImuMid3 &md, const SC &sc, const double *gc, M3 (&Ja)[4], M3 &Rinv_g) {
+// The gyro rows' M_0, M_1, M_2
+CTV_DI void imu_pair_gyro3(const ImuMid3 &md, M3 (&M)[3]) {
+  M[0] = scale(md.Apost[1], md.lamW[1]);
+  M[1] = add(scale(mul(mul_hat(md.Apost[1], md.om1), md.JrK[1]), md.lamR[2]), scale(md.Apost[2], md.lamW[2]));
+  M[2] = scale(mul(mul_hat(md.Apost[2], md.om2), md.JrK[2]), md.lamR[3]);
+  M[2].m[0] += md.lamW[3]; M[2].m[4] += md.lamW[3]; M[2].m[8] += md.lamW[3];
+}
+// Gyro row a in the compact order: w_a [0 3 | M_0 M_1 M_2 | e_a] | r_a
+CTV_DI void imu_row_gyro_pl(const M3 (&M)[3], const double w[6], const double r[6], int a, double out[16]) {
+  out[0] = out[1] = out[2] = 0.0;
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
-      Rinv_g.m[3 * i + j] = md.Apost[0].m[3 * i] * gc[12 + j] + md.Apost[0].m[3 * i + 1] * gc[15 + j] + md.Apost[0].m[3 * i + 2] * gc[18 + j];
-  Ja[0] = mul_hat(md.Apost[0], md.b[0]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    imu_apply_pair(scale(mul(mul_hat(md.Apost[i], md.b[i]), md.JrK[i]), md.lamR[i + 1]), sc, i, Ja[i], Ja[i + 1], false);
-}
-
-// Accelerometer row a in the product kernel's two-tile order: T0 = [rot k0..k3 (12) | ba (3) | r], T1 = [pos k0..k3 (12)] (columns 28..31 unused)
-CTV_DI void imu_row_accel3(const M3 (&Ja)[4], const double lamA[4], const M3 &Rinv_g, const double w[6], const double r[6], int a, double out[28]) {
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      out[3 * kk + b] = w[3 + a] * Ja[kk].m[3 * a + b];
-      out[16 + 3 * kk + b] = w[3 + a] * lamA[kk] * Rinv_g.m[3 * a + b];
-    }
+    for (int b = 0; b < 3; ++b) out[3 + 3 * i + b] = w[a] * M[i].m[3 * a + b];
   out[12] = out[13] = out[14] = 0.0;
-  out[12 + a] = w[3 + a];
-  out[15] = r[3 + a];
+  out[12 + a] = w[a];
+  out[15] = r[a];
+}
+// The three accelerometer rows of a sample in the compact order, ROTATED INTO THE WORLD FRAME: Y = R(t) w [D0 | M_0 M_1 M_2 | I3 | r / w]
+// (3 x 16), R(t) = R_0 Apost_0^T (R_0^T: gc[12..20]).  With one weight w for the three rows (the fast body's groups) Y^T Y is the Gram matrix
+// of the unrotated rows, and the position columns w lamA_k R(t)^T of the same rows become w lamA_k I3: their product with the compact rows
+// is the lamA-weighted sum of Y over the samples.  R(t) D0 = R_0 hat(b_0) and R(t) M_0 = lamR_1 R_0 hat(b_0) Jr: no Apost_0 in either.
+CTV_DI void imu_world_accel3(const ImuMid3 &md, const double *gc, const double w[6], const double r[6], double Y[3][16]) {
+  M3 R0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R0.m[3 * i + j] = gc[12 + 3 * j + i];
+  const M3 Rs = mulT(R0, md.Apost[0]), wRs = scale(Rs, w[3]);
+  M3 blk[4];
+  blk[0] = mul_hat(R0, w[3] * md.b[0]);
+  blk[1] = mul(scale(blk[0], md.lamR[1]), md.JrK[0]);
+#pragma unroll
+  for (int i = 1; i < 3; ++i) blk[i + 1] = mul(Rs, scale(mul(mul_hat(md.Apost[i], md.b[i]), md.JrK[i]), w[3] * md.lamR[i + 1]));
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) Y[a][3 * kk + b] = blk[kk].m[3 * a + b];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) Y[a][12 + b] = wRs.m[3 * a + b];
+  }
+  // (the residual is whitened already: zero on a lane whose weights are zero, like every other column)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) Y[a][15] = Rs.m[3 * a] * r[3] + Rs.m[3 * a + 1] * r[4] + Rs.m[3 * a + 2] * r[5];
 }
 // trajectory_value_factor.h:198-245, column by column
 template <class Sink> CTV_DI void imu_emit_cols(const ImuJac &J, const double w[6], Sink &sink) {

@@ -171,7 +171,6 @@ __device__ __forceinline__ void imu_linearize_f64_body(const Dev &d, int mode, d
 //  next trip -- one ds_read2, one wait, two MFMAs, the very serialisation this removes; volatile loads become flat loads with a full wait
 //  each.  The waits carry the operand as an in/out so that the MFMA that consumes it stays behind them; a final lgkmcnt(0) leaves nothing
 //  in flight that the compiler's own wait counting does not know about.)
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void imu_chain_gyro(const double *A, int q4, int l15, int kmax, f64x4 &gacc) {
   unsigned addr = (unsigned)(size_t)(A + q4 * 17 + l15);
   double v0, v1;
@@ -187,22 +186,30 @@ __device__ __forceinline__ void imu_chain_gyro(const double *A, int q4, int l15,
   }
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v0));
 }
-__device__ __forceinline__ void imu_chain_accel(const double *A, int q4, int l15, int kmax, f64x4 &acc00, f64x4 &acc10) {
-  unsigned addr = (unsigned)(size_t)(A + q4 * 33 + l15);
-  f64x2 o0, o1;   // (lo, hi) = columns l15 and 16 + l15 of four rows
-  asm volatile("ds_read2_b64 %0, %1 offset1:16" : "=v"(o0) : "v"(addr));
+// World-frame accelerometer row b of the pass (A: [72][17], as the gyro's) with the position weights L[72][4] = w lamA_k of every sample:
+// acc00 += Y_b^T Y_b as above, and x += sum_s w lamA_k(s) Y_s[b][c] -- an M = 4 product, one v_mfma_f64_4x4x4_4b_f64 per K-step (layout,
+// tools/mfma4_layout.hip: A lane = i + 4 block + 16 k, B lane = j + 4 block + 16 k, D lane = j + 4 block + 16 i): its A operand is
+// L[sample 4 t + lane / 16][lane & 3], its B operand the very register the 16x16x4 reads, and lane l of x ends up with knot l / 16, column l & 15.
+__device__ __forceinline__ void imu_chain_world(const double *A, const double *L, int q4, int l15, int kmax, f64x4 &acc00, double &x) {
+  unsigned addr = (unsigned)(size_t)(A + q4 * 17 + l15), laddr = (unsigned)(size_t)(L + q4 * 4 + (l15 & 3));
+  double v0, v1, a0, a1;
+  asm volatile("ds_read_b64 %0, %1" : "=v"(v0) : "v"(addr));
+  asm volatile("ds_read_b64 %0, %1" : "=v"(a0) : "v"(laddr));
   for (int k0 = 0; k0 < kmax; k0 += 8) {
-    asm volatile("ds_read2_b64 %0, %1 offset0:132 offset1:148" : "=v"(o1) : "v"(addr));   // step k0 + 4 (4 rows of 33 doubles on)
-    asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(o0));
-    acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(o0[0], o0[0], acc00, 0, 0, 0);
-    acc10 = __builtin_amdgcn_mfma_f64_16x16x4f64(o0[1], o0[0], acc10, 0, 0, 0);
-    addr += 8 * 33 * 8;
-    asm volatile("ds_read2_b64 %0, %1 offset1:16" : "=v"(o0) : "v"(addr));                   // step k0 + 8
-    asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(o1));
-    acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(o1[0], o1[0], acc00, 0, 0, 0);
-    acc10 = __builtin_amdgcn_mfma_f64_16x16x4f64(o1[1], o1[0], acc10, 0, 0, 0);
+    asm volatile("ds_read_b64 %0, %1 offset:544" : "=v"(v1) : "v"(addr));          // step k0 + 4
+    asm volatile("ds_read_b64 %0, %1 offset:128" : "=v"(a1) : "v"(laddr));
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(v0), "+v"(a0));
+    acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(v0, v0, acc00, 0, 0, 0);
+    x = __builtin_amdgcn_mfma_f64_4x4x4f64(a0, v0, x, 0, 0, 0);
+    addr += 8 * 17 * 8;
+    laddr += 8 * 4 * 8;
+    asm volatile("ds_read_b64 %0, %1" : "=v"(v0) : "v"(addr));                     // step k0 + 8
+    asm volatile("ds_read_b64 %0, %1" : "=v"(a0) : "v"(laddr));
+    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(v1), "+v"(a1));
+    acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(v1, v1, acc00, 0, 0, 0);
+    x = __builtin_amdgcn_mfma_f64_4x4x4f64(a1, v1, x, 0, 0, 0);
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o0));
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v0), "+v"(a0));
 }
 
 // The fast body's groups: every knot-pair log below 0.5 rad, isotropic accelerometer weights.  Asked in two places (the fast body about its
@@ -216,11 +223,17 @@ __device__ __forceinline__ bool imu_fast_pred(const double kd[9], const double *
 }
 // ---- The product path's body for the usual group (imu_group_fast: knot-pair logs below 0.5 rad, isotropic accelerometer weights).
 // Same wave-per-group scheme and row streaming as the general body above, with
-//   * the evaluation in stages (factors.hpp, staged form): values, gyro Jacobians -> three row phases, accelerometer Jacobians -> three row
-//     phases, so the two 36-entry Jacobians are never live together; small-angle series, no branch in the loop;
-//   * global frame (the local frame of the general body is an fp32 device), Jr^-1 of the three knot pairs and their logs in SGPRs;
-//   * the accelerometer rows in two 16-column tiles T0 = [rot 12 | ba 3 | r], T1 = [pos 12]: T0^T T0 and T1^T T0 on the matrix cores,
-//     T1^T T1 = w^2 sum_s lamA_k lamA_k' I3 from ten per-lane sums (R(t)^T W^2 R(t) = w^2 I): 2 MFMAs per K-step instead of 3;
+//   * the evaluation in stages (factors.hpp, staged form): values, gyro rows -> three row phases, accelerometer rows -> three row
+//     phases, so the two sensors' 3 x 12 blocks are never live together; small-angle series, no branch in the loop;
+//   * global frame (the local frame of the general body is an fp32 device), the pair logs in SGPRs;
+//   * PAIR-LOG COORDINATES (factors.hpp): a sample's rows are streamed as w [D0 | M_0 M_1 M_2 | bias | r] -- the derivatives with respect
+//     to the three pair logs, 16 compact columns for either sensor -- and Jr^-1 of the knot pairs, a constant of the group, is applied ONCE
+//     per group in the combine stage: tile = T^T G^ T, five 16 x 16 x 16 products on the matrix cores with the accumulators as operands
+//     (20 MFMAs per ~100 samples instead of six M Jr^-1 products, ~380 fp64 instructions, per sample);
+//   * the accelerometer rows ROTATED INTO THE WORLD FRAME (isotropic weights: the Gram matrix does not change): the position columns
+//     w lamA_k R(t)^T become w lamA_k I3, so T1^T T0 is the lamA-weighted sum of the rows -- an M = 4 product, one v_mfma_f64_4x4x4 (16
+//     cycles) per K-step in place of a 16x16x4 (64 cycles), and the rows are 16 columns wide instead of 28;
+//     T1^T T1 = w^2 sum_s lamA_k lamA_k' I3 from ten per-lane sums as before;
 //   * the next pass's measurements requested before the current pass is evaluated.
 // (fp64 MFMA and fp64 VALU instructions share one datapath on gfx950 -- tools/mfma_valu_overlap.hip: one wave's MFMAs and FMAs add up,
 //  two waves on a SIMD do not overlap them either -- so the kernel's time is the SUM of its vector and matrix work: both are cut here.)
@@ -273,16 +286,13 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
   do {
   const int w = grp.win;
   const int base = grp.iabs;
-  // the group's constants: knot-pair logs and Jr^-1 (used a dozen times per pass) in scalar registers, the rest (used once or twice per
+  // the group's constants: knot-pair logs (used a dozen times per pass) in scalar registers, the rest (used once or twice per
   // pass) in LDS behind the row buffer -- [0..11] knot positions relative to knot 0, [12..20] R_0^T, [21..23] gravity, [24..29] bias,
   // [30..35] weights.  (All of them in scalar registers overflow the SGPR file: 250 v_readlane per pass to fetch them back.)
-  SegConstS sc;
+  // Jr^-1 of the three pairs stays where the prefetch left it -- lanes 9..35 of cur.pc -- until the combine stage builds T from it.
+  SegConstS sc;   // (JrI is not filled: the staged form reads the logs only)
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    sc.d[i] = mk(readlane_d(cur.pc, 3 * i), readlane_d(cur.pc, 3 * i + 1), readlane_d(cur.pc, 3 * i + 2));
-#pragma unroll
-    for (int e = 0; e < 9; ++e) sc.JrI[i].m[e] = readlane_d(cur.pc, 9 + 9 * i + e);
-  }
+  for (int i = 0; i < 3; ++i) sc.d[i] = mk(readlane_d(cur.pc, 3 * i), readlane_d(cur.pc, 3 * i + 1), readlane_d(cur.pc, 3 * i + 2));
   // ---- the window: LM state
   const int f_status = __builtin_amdgcn_readlane(cur.fl, 0), f_valid = __builtin_amdgcn_readlane(cur.fl, 1), f_iter = __builtin_amdgcn_readlane(cur.fl, 2),
             f_ls = __builtin_amdgcn_readlane(cur.fl, 3);
@@ -333,8 +343,10 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     if (lane == 0) d.imu_cost[gidx] = csum;
     break;
   }
-  f64x4 acc00 = {0.0, 0.0, 0.0, 0.0}, acc10 = {0.0, 0.0, 0.0, 0.0}, gacc = {0.0, 0.0, 0.0, 0.0};
+  f64x4 acc00 = {0.0, 0.0, 0.0, 0.0}, gacc = {0.0, 0.0, 0.0, 0.0};
+  double xpos[3] = {0.0, 0.0, 0.0};   // lane (k, c): sum_s w lamA_k(s) Y_s[b][c], b = 0..2
   double spp[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double *Lw = A + 1280;   // [72][4] behind the [72][17] rows
   for (int c0 = 0; c0 < grp.count; c0 += 64) {
     CTV_STAMP(dbg, dbi, 16, lane == 0, csum);
     const int nval = min(64, grp.count - c0);
@@ -363,13 +375,13 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     for (int i = 0; i < 6; ++i) csum += 0.5 * r[i] * r[i];   // (dead lanes: zero weights, zero residual)
     CTV_STAMP(dbg, dbi, 16, lane == 0, csum);
     {
-      M3 Jw[4];
-      imu_jac_gyro3(md, sc, Jw);
-      CTV_STAMP(dbg, dbi, 16, lane == 0, Jw[3].m[8]);
+      M3 Mw[3];
+      imu_pair_gyro3(md, Mw);
+      CTV_STAMP(dbg, dbi, 16, lane == 0, Mw[2].m[8]);
 #pragma unroll
       for (int a = 0; a < 3; ++a) {   // unrolled: the row index must be static
         double row[16];
-        imu_row_gyro2(Jw, wl, r, a, row);
+        imu_row_gyro_pl(Mw, wl, r, a, row);
         __builtin_amdgcn_wave_barrier();   // the previous phase's operand reads are complete (consumed by its MFMAs)
 #pragma unroll
         for (int c = 0; c < 16; ++c) A[lane * 17 + c] = row[c];
@@ -379,13 +391,13 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     }
     CTV_STAMP(dbg, dbi, 16, lane == 0, gacc[0]);
     {
-      M3 Ja[4], Rinv_g;
-      imu_jac_accel3(md, sc, gc, Ja, Rinv_g);
-      CTV_STAMP(dbg, dbi, 16, lane == 0, Ja[3].m[8] + Rinv_g.m[8]);
-      {
-        double la[4];
+      double Y[3][16];
+      imu_world_accel3(md, gc, wl, r, Y);
+      CTV_STAMP(dbg, dbi, 16, lane == 0, Y[2][15]);
+      double la[4];
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) la[kk] = wl[3] * md.lamA[kk];
+      for (int kk = 0; kk < 4; ++kk) la[kk] = wl[3] * md.lamA[kk];
+      {
         int e = 0;
 #pragma unroll
         for (int ka = 0; ka < 4; ++ka)
@@ -394,26 +406,32 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
       }
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        double row[28];
-        imu_row_accel3(Ja, md.lamA, Rinv_g, wl, r, a, row);
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
-        for (int c = 0; c < 28; ++c) A[lane * 33 + c] = row[c];   // (columns 28..31 feed accumulator rows nobody reads)
+        for (int c = 0; c < 16; ++c) A[lane * 17 + c] = Y[a][c];
+        if (a == 0) {   // the position weights of the pass: the same for its three row phases
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) Lw[lane * 4 + kk] = la[kk];
+        }
         lds_wave_sync();
-        imu_chain_accel(A, q4, l15, kmax, acc00, acc10);
+        imu_chain_world(A, Lw, q4, l15, kmax, acc00, xpos[a]);
       }
     }
   }
-  CTV_STAMP(dbg, dbi, 16, lane == 0, acc00[0] + acc10[0]);
+  CTV_STAMP(dbg, dbi, 16, lane == 0, acc00[0] + xpos[0]);
   // ---- combine in LDS into the full symmetric 32 x 32 tile in the local column order [rot 12 | pos 12 | bg 3 | ba 3 | r | -]
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
   for (int i = 0; i < 16; ++i) A[i * 64 + lane] = 0.0;
+  double *S = A + 1024, *Tp = A + 1792, *Xs = A + 2048;   // the sums below [11][64] + 11 | T [16][16] | the position sums [12][17]
+#pragma unroll
+  for (int i = 0; i < 4; ++i) Tp[i * 64 + lane] = 0.0;
+#pragma unroll
+  for (int b = 0; b < 3; ++b) Xs[(3 * q4 + b) * 17 + l15] = xpos[b];
   {
     // eleven sums over the 64 lanes in a fixed order -- the ten of the pos x pos block and the group's share of the cost -- through the
     // free half of the buffer: lane (e, part) adds 16 lanes' values, two butterfly steps join the four parts (one LDS round trip for all
     // of them instead of a six-step butterfly per value)
-    double *S = A + 1024;
 #pragma unroll
     for (int e = 0; e < 10; ++e) S[e * 64 + lane] = spp[e];
     S[10 * 64 + lane] = csum;
@@ -427,11 +445,42 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
     __builtin_amdgcn_wave_barrier();
     if (lane < 40 && part == 0) S[704 + e] = t;
     if (lane == 40) d.imu_cost[gidx] = t;
+    // the group's transform T (factors.hpp, pair-log coordinates): lanes 9..35 still hold Jr^-1 of the three pairs, one entry each
+    if (lane >= 9 && lane < 36) {
+      const int i = (lane - 9) / 9, ab = (lane - 9) % 9;
+      int plus, minus;
+      imu_pairlog_slots(i, ab / 3, ab % 3, plus, minus);
+      Tp[plus] = cur.pc;
+      Tp[minus] = -cur.pc;
+    }
+    if (lane < 3 || (lane >= 12 && lane < 16)) Tp[17 * lane] = 1.0;
   }
   lds_wave_sync();
   {
+    // T^T G^ T for the gyro and the accelerometer Gram matrices and (position sums) T, on the matrix cores with the accumulators as they
+    // are: K-step r pairs accumulator register r (row q4 + 4 r of G^, symmetric) with the same row of T -- no trip through LDS for G^.
+    double Tr[4], Xa[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      Tr[r] = Tp[(q4 + 4 * r) * 16 + l15];
+      Xa[r] = Xs[min(l15, 11) * 17 + q4 + 4 * r];
+      Xa[r] = l15 < 12 ? Xa[r] : 0.0;
+    }
+    f64x4 zg = {0.0, 0.0, 0.0, 0.0}, za = {0.0, 0.0, 0.0, 0.0}, hg = {0.0, 0.0, 0.0, 0.0}, ha = {0.0, 0.0, 0.0, 0.0}, hx = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      zg = __builtin_amdgcn_mfma_f64_16x16x4f64(gacc[r], Tr[r], zg, 0, 0, 0);
+      za = __builtin_amdgcn_mfma_f64_16x16x4f64(acc00[r], Tr[r], za, 0, 0, 0);
+      hx = __builtin_amdgcn_mfma_f64_16x16x4f64(Xa[r], Tr[r], hx, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      hg = __builtin_amdgcn_mfma_f64_16x16x4f64(Tr[r], zg[r], hg, 0, 0, 0);
+      ha = __builtin_amdgcn_mfma_f64_16x16x4f64(Tr[r], za[r], ha, 0, 0, 0);
+    }
     // T0 (accelerometer rows: rot 12 | ba 3 | r) and the gyro tile (rot 12 | bg 3 | r) share the accumulator layout: where neither index
-    // is a bias one the two land on the same entry and are added in registers; a bias index sends them to the ba / bg columns
+    // is a bias one the two land on the same entry and are added in registers; a bias index sends them to the ba / bg columns.
+    // (T^T (G^ T) is symmetric up to rounding only: the lower triangle is stored on both sides, so the tile stays symmetric to the bit.)
     const int c0 = l15 < 12 ? l15 : (l15 < 15 ? l15 + 15 : 30);   // T0 index -> local column (ba at 27..29)
     const int cg = l15 < 12 ? l15 : (l15 < 15 ? l15 + 12 : 30);   // gyro tile index -> local column (bg at 24..26)
     const bool cb = l15 >= 12 && l15 < 15;
@@ -440,14 +489,18 @@ __device__ __forceinline__ void imu_linearize_f64_fast(const Dev &d, int mode, d
       const int t = q4 + 4 * r;
       const int r0 = t < 12 ? t : (t < 15 ? t + 15 : 30), rg = t < 12 ? t : (t < 15 ? t + 12 : 30);
       const bool shared = !cb && !(t >= 12 && t < 15);
-      A[r0 * 32 + c0] = shared ? acc00[r] + gacc[r] : acc00[r];
-      if (!shared) A[rg * 32 + cg] = gacc[r];
-      if (t < 12) { A[(12 + t) * 32 + c0] = acc10[r]; A[c0 * 32 + 12 + t] = acc10[r]; }
+      if (t >= l15) {
+        const double v = shared ? ha[r] + hg[r] : ha[r];
+        A[r0 * 32 + c0] = v;
+        A[c0 * 32 + r0] = v;
+        if (!shared) { A[rg * 32 + cg] = hg[r]; A[cg * 32 + rg] = hg[r]; }
+      }
+      if (t < 12) { A[(12 + t) * 32 + c0] = hx[r]; A[c0 * 32 + 12 + t] = hx[r]; }
     }
     // lane (ka, kb, b) < 48 places one entry of the pos x pos block
     const int ka = lane / 12, kb = (lane / 3) & 3, b = lane % 3;
     const int hi = max(ka, kb), lo = min(ka, kb);
-    if (lane < 48) A[(12 + 3 * ka + b) * 32 + 12 + 3 * kb + b] = A[1024 + 704 + hi * (hi + 1) / 2 + lo];
+    if (lane < 48) A[(12 + 3 * ka + b) * 32 + 12 + 3 * kb + b] = S[704 + hi * (hi + 1) / 2 + lo];
   }
   lds_wave_sync();
   double *tile = d.imu_tiles + (size_t)gidx * 1024;

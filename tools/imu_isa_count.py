@@ -2,9 +2,10 @@
 """Instruction counts of k_imu_linearize_f64's pass loop (64 samples, one per lane), read off the ISA -- no GPU needed.
   python tools/imu_isa_count.py            (compiles ctrl-vio_amd/csrc/ctvio.hip to assembly first: ~20 s)
 The pass loop is the depth-2 loop of the kernel (the walk over groups is depth 1); the six MFMA chains inside it are depth-3 loops whose
-trip count is kmax / 8 (two K-steps per trip).  Everything else in the loop body runs once per pass.  Printed: static counts per category,
+trip count is kmax / 8 (two K-steps per trip).  Everything else in the loop body runs once per pass (the MFMAs of the group transform
+in the combine stage are outside it: once per group, not counted).  Printed: static counts per category,
 the dynamic counts of a full pass (kmax = 64) and of the second pass of a 100-sample group (kmax = 36), and the issue-slot model of
-DESIGN.md section 4: fp64 vector instructions at 4 cycles (16 lanes per cycle), v_mfma_f64_16x16x4 at 64 cycles, one datapath."""
+DESIGN.md section 4: fp64 vector instructions at 4 cycles (16 lanes per cycle), v_mfma_f64_16x16x4 at 64 cycles, v_mfma_f64_4x4x4 at 16 cycles, one datapath."""
 import os
 import re
 import subprocess
@@ -21,6 +22,7 @@ def cat(l):
     if not l or l.startswith((";", ".", "//")) or l.endswith(":"):
         return None
     op = l.split()[0]
+    if op.startswith("v_mfma_f64_4x4x4"): return "mfma4"
     if op.startswith("v_mfma"): return "mfma"
     if op.startswith(("v_readlane", "v_readfirstlane", "v_writelane")): return "lane"
     if op.startswith("v_accvgpr"): return "accvgpr_mov"
@@ -52,8 +54,10 @@ def main():
         m = re.search(r"s_c?branch\w* (\.LBB\d+_\d+)", l)
         if m and m.group(1) in lab and lab[m.group(1)] < n:
             loops.append((lab[m.group(1)], n))
-    cand = [(a, z) for a, z in loops if a < mf[0] and z > mf[-1]]
-    a, z = max(cand, key=lambda t: t[0])          # innermost loop around all MFMAs = the pass loop
+    # the chains = the loops with MFMAs and no loop inside them (the combine stage's MFMAs, once per group, are in straight-line code)
+    chains = [(x, y) for x, y in loops if any(x <= q <= y for q in mf) and not any((x2, y2) != (x, y) and x <= x2 and y2 <= y for x2, y2 in loops)]
+    cand = [(a, z) for a, z in loops if all(a < x and y < z for x, y in chains)]
+    a, z = max(cand, key=lambda t: t[0])          # innermost loop around all chains = the pass loop
     inner = sorted((x, y) for x, y in loops if x > a and y < z and any(x <= q <= y for q in mf))
     print(f"pass loop: lines {a}..{z} of the kernel's {len(b)}; {len(inner)} MFMA chain loops inside")
     stat, chain = Counter(), Counter()
@@ -62,7 +66,7 @@ def main():
         k = cat(b[n])
         if k:
             (chain if in_chain(n) else stat)[k] += 1
-    cats = ["valu_f64", "valu_other", "accvgpr_mov", "lane", "mfma", "lds", "vmem", "salu", "waitcnt", "nop"]
+    cats = ["valu_f64", "valu_other", "accvgpr_mov", "lane", "mfma", "mfma4", "lds", "vmem", "salu", "waitcnt", "nop"]
     print(f"{'category':14s} {'once per pass':>14s} {'per trip, all 6 chains':>24s} {'full pass (8 trips)':>20s} {'kmax = 36 (5 trips)':>20s}")
     dyn = {}
     for c in cats:
@@ -70,10 +74,10 @@ def main():
         print(f"{c:14s} {stat[c]:14d} {chain[c]:24d} {dyn[c][0]:20d} {dyn[c][1]:20d}")
     for name, idx in (("full pass", 0), ("kmax = 36", 1)):
         v = 4 * (dyn["valu_f64"][idx] + dyn["valu_other"][idx] + dyn["accvgpr_mov"][idx] + dyn["lane"][idx])
-        m = 64 * dyn["mfma"][idx]
-        print(f"issue-slot model, {name}: vector 4 x {v // 4} = {v} cycles + matrix 64 x {dyn['mfma'][idx]} = {m} cycles = {v + m} cycles on the shared fp64 datapath")
-    full = 4 * sum(dyn[c][0] for c in ("valu_f64", "valu_other", "accvgpr_mov", "lane")) + 64 * dyn["mfma"][0]
-    part = 4 * sum(dyn[c][1] for c in ("valu_f64", "valu_other", "accvgpr_mov", "lane")) + 64 * dyn["mfma"][1]
+        m = 64 * dyn["mfma"][idx] + 16 * dyn["mfma4"][idx]
+        print(f"issue-slot model, {name}: vector 4 x {v // 4} = {v} cycles + matrix 64 x {dyn['mfma'][idx]} + 16 x {dyn['mfma4'][idx]} = {m} cycles = {v + m} cycles on the shared fp64 datapath")
+    full = 4 * sum(dyn[c][0] for c in ("valu_f64", "valu_other", "accvgpr_mov", "lane")) + 64 * dyn["mfma"][0] + 16 * dyn["mfma4"][0]
+    part = 4 * sum(dyn[c][1] for c in ("valu_f64", "valu_other", "accvgpr_mov", "lane")) + 64 * dyn["mfma"][1] + 16 * dyn["mfma4"][1]
     # config 2: 2000 samples in 21 groups (20 of 100 samples: one full pass + one of 36 lanes): 2048 windows on 1024 SIMDs
     per_window = 20 * (full + part) + 1 * (full + part) * 0   # (the 21st group of a window is the same shape in the synthetic windows: 95..100 samples)
     per_window = 21 * (full + part)
