@@ -82,6 +82,10 @@ class ImuNoise(C.Structure):
     _fields_ = [("gyr_n", C.c_double), ("acc_n", C.c_double), ("gyr_w", C.c_double), ("acc_w", C.c_double)]
 
 
+class RowModel(C.Structure):
+    _fields_ = [("fy", C.c_double), ("cy", C.c_double), ("rows", C.c_int32), ("iterations", C.c_int32)]
+
+
 # every symbol include/ctvio.h declares (tests check the .so exports all of them)
 SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "ctvio_device_count", "ctvio_create",
            "ctvio_destroy", "ctvio_clear", "ctvio_add_window", "ctvio_upload", "ctvio_set_batch", "ctvio_num_windows", "ctvio_solve",
@@ -90,7 +94,7 @@ SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "
            "ctvio_shard_count", "ctvio_shards_used", "ctvio_spline_eval_batch", "ctvio_graph_captures", "ctvio_marginalize_ran_on_host",
            "ctvio_covariance_batch", "ctvio_covariance", "ctvio_pose_covariance_batch", "ctvio_pose_covariance",
            "ctvio_landmark_points_batch", "ctvio_landmark_points", "ctvio_nav_state_batch", "ctvio_nav_state",
-           "ctvio_relative_pose_batch", "ctvio_relative_pose",
+           "ctvio_relative_pose_batch", "ctvio_relative_pose", "ctvio_project_landmarks_batch", "ctvio_project_landmarks",
            "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict",
            "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
@@ -146,6 +150,8 @@ def load_library():
         lib.ctvio_nav_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5
         lib.ctvio_relative_pose_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
         lib.ctvio_relative_pose.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
+        lib.ctvio_project_landmarks_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.POINTER(RowModel)] + [C.c_void_p] * 6
+        lib.ctvio_project_landmarks.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.POINTER(RowModel)] + [C.c_void_p] * 6
         lib.ctvio_default_imu_noise.argtypes = [C.POINTER(ImuNoise)]
         lib.ctvio_default_imu_noise.restype = None
         lib.ctvio_imu_predict_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(ImuNoise), C.c_int32] + [C.c_void_p] * 3

@@ -137,6 +137,7 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_misc, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));   // (+ 2 KB of static LDS)
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     return CTVIO_OK;
   }
   int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
@@ -1826,6 +1827,139 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // ctvio_project_landmarks_batch / ctvio_project_landmarks (only >= 0: every query belongs to that window, win is not read): the predicted
+  // image point of landmark lm[i] in the camera at (t_ns[i], row[i]), its 2 x 2 covariance and the gate of a candidate point.  Values only
+  // (cov4 and chi2 null): k_cov_proj_jac alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a
+  // window's queries keep the caller's order), eight to a tile of kind 6; k_cov_proj_jac writes one record per query after k_cov_prepare (it
+  // reads the exclusions and 1 / Hll), k_cov_solve the 2 x 2 blocks and gates by record.  Around them the middle of covariance(): dev_, plan_
+  // and the captured graph are not touched.
+  int project_landmarks(int only, int64_t n64, const int32_t *win, const int32_t *lmi, const int64_t *t_ns, const int32_t *row, const ctvio_row_model *rm,
+                        const double *obs2, double *proj3, double *cov4, double *chi2, int32_t *row_out, int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (n64 < 0 || n64 > (int64_t)1 << 30 ||
+        (n64 && (!lmi || !t_ns || !row || (only < 0 && !win) || (!proj3 && !cov4 && !chi2 && !row_out && !status) || (chi2 && !obs2))))
+      return fail(CTVIO_ERR_INVALID, "bad arguments");
+    ProjRowModel prm{0.0, 0.0, 1, 0};
+    if (rm) {
+      if (rm->iterations < 1 || rm->iterations > 8 || rm->rows < 1 || !std::isfinite(rm->fy) || !std::isfinite(rm->cy))
+        return fail(CTVIO_ERR_INVALID, "row model: iterations in 1 .. 8, rows >= 1, finite fy and cy");
+      prm = ProjRowModel{rm->fy, rm->cy, rm->rows, rm->iterations};
+    }
+    const int n = (int)n64, nw = dev_.nwin;
+    const size_t nn = (size_t)n;
+    for (int i = 0; i < n; ++i) {
+      const int w = only >= 0 ? only : win[i];
+      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+      if (lmi[i] < 0 || lmi[i] >= meta_[w].L) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": landmark index out of range");
+      if (obs2 && !(std::isfinite(obs2[2 * (size_t)i]) && std::isfinite(obs2[2 * (size_t)i + 1])))
+        return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": non-finite candidate point");
+    }
+    if (n == 0) return CTVIO_OK;
+    // ---- queries by window; slot[r]: the caller's index of sorted query r
+    std::vector<int32_t> slot(nn);
+    for (int i = 0; i < n; ++i) slot[i] = i;
+    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
+    auto query_of = [&](int r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      const int w = win_of(r);
+      return ProjQuery{w, lmi[i], row[i], 0, (long long)(t_ns[i] - t0_[w]), {obs2 ? obs2[2 * i] : 0.0, obs2 ? obs2[2 * i + 1] : 0.0}};
+    };
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    if (!cov4 && !chi2) {   // in: queries (one staged copy); out: proj3 | row | status (one copy)
+      CallLayout io = head_;
+      const int s_q = io.add("queries", sizeof(ProjQuery), nn, false), s_proj = io.add("proj3", sizeof(double), 3 * nn, true),
+                s_row = io.add("row", sizeof(int32_t), nn, false), s_stat = io.add("status", sizeof(int32_t), nn, false);
+      if (const int rc = reserve_call(io)) return rc;
+      ProjQuery *hq = io_host<ProjQuery>(io, s_q);
+      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_proj) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), (const uint8_t *)nullptr, prm,
+                         (ProjRec *)nullptr, io_dev<double>(io, s_proj), io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_proj), io_dev<char>(io, s_proj), io.bytes() - io.off(s_proj), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      {   // device times of this call, for ctvio_last_timing: k_cov_proj_jac and the whole call
+        Timing t;
+        t.clear();
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
+        t.ms[2] = ms; t.n[2] = 1;
+        if (const int rc = publish_timing(t, 0)) return rc;
+      }
+      const double *hproj = io_host<double>(io, s_proj);
+      const int32_t *hrow = io_host<int32_t>(io, s_row), *hstat = io_host<int32_t>(io, s_stat);
+      for (int r = 0; r < n; ++r) {
+        const size_t i = (size_t)slot[(size_t)r];
+        if (proj3) std::memcpy(proj3 + 3 * i, hproj + 3 * (size_t)r, sizeof(double) * 3);
+        if (row_out) row_out[i] = hrow[r];
+        if (status) status[i] = hstat[r];
+      }
+      return CTVIO_OK;
+    }
+    std::vector<CovTile> tiles;
+    for (int r = 0; r < n;) {   // eight per tile
+      int cnt = 1;
+      while (cnt < PRJ_PER_TILE && r + cnt < n && win_of(r + cnt) == win_of(r)) ++cnt;
+      tiles.push_back(CovTile{win_of(r), 6, r, cnt, 0});
+      r += cnt;
+    }
+    // ---- scratch.  io: queries, tiles (in, one staged copy); proj3 | cov4 | chi2 | row | status (out, one copy).  scr: mask, exclusions, records
+    CallLayout io = head_, scr;
+    const int s_q = io.add("queries", sizeof(ProjQuery), nn, false), s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
+              s_proj = io.add("proj3", sizeof(double), 3 * nn, true), s_cov = io.add("cov4", sizeof(double), 4 * nn, true),
+              s_chi = io.add("chi2", sizeof(double), nn, true), s_row = io.add("row", sizeof(int32_t), nn, false),
+              s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_rec = scr.add("records", sizeof(ProjRec), nn, false);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    ProjRec *drec = scr.at<ProjRec>(call_scr_.dev, s_rec);
+    ProjQuery *hq = io_host<ProjQuery>(io, s_q);
+    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_proj) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), (const uint8_t *)excl, prm, drec,
+                       io_dev<double>(io, s_proj), io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    hipLaunchKernelGGL((k_cov_solve<false, true>), dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+                       (const int32_t *)nullptr, (double *)nullptr, chi2 ? io_dev<double>(io, s_chi) : (double *)nullptr, (const ProjRec *)drec,
+                       io_dev<double>(io, s_cov), (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // ---- results, all in sorted order
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_proj), io_dev<char>(io, s_proj), io.bytes() - io.off(s_proj), hipMemcpyDeviceToHost, stream_));   // (proj3 | cov4 | chi2 | row | status)
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_proj_jac and the whole call
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
+      const bool ran[3] = {true, true, true};
+      if (const int rc = cov_timing(pair, ran)) return rc;
+    }
+    // (not computable: NaN; no information: +inf on the diagonal, 0 elsewhere, chi2 0; a window whose factorisation met a bad pivot: NaN)
+    const double *hproj = io_host<double>(io, s_proj), *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
+    const int32_t *hrow = io_host<int32_t>(io, s_row), *hstat = io_host<int32_t>(io, s_stat);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      int st = hstat[r];
+      if (st == PRJ_OK && lm[win_of(r)].chol_fail != 0) st = PRJ_SINGULAR;
+      if (cov4) {
+        double *o = cov4 + 4 * i;
+        if (st == PRJ_OK) std::memcpy(o, hcov + 4 * (size_t)r, sizeof(double) * 4);
+        else for (int e = 0; e < 4; ++e) o[e] = st == PRJ_NO_INFO ? (e % 3 == 0 ? inf : 0.0) : nan;
+      }
+      if (chi2) chi2[i] = st == PRJ_OK ? hchi[r] : (st == PRJ_NO_INFO ? 0.0 : nan);
+      if (proj3) std::memcpy(proj3 + 3 * i, hproj + 3 * (size_t)r, sizeof(double) * 3);
+      if (row_out) row_out[i] = hrow[r];
+      if (status) status[i] = st;
+    }
+    return CTVIO_OK;
+  }
   // ---------------------------------------------------------------------------------------- landmark depths
   // ctvio_triangulate_batch / ctvio_triangulate (single: window `only` alone) and ctvio_shift_anchor_batch: one kernel each
   // (csrc/kernels_tri.hpp) on the current state.  dev_, plan_ and the captured graph are not touched.
@@ -2159,6 +2293,18 @@ int32_t ctvio_relative_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.relative_pose(id, n, nullptr, t_a_ns, t_b_ns, q_SI, p_SI, rel7, cov36, status);
+}
+int32_t ctvio_project_landmarks_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int32_t *lm, const int64_t *t_ns, const int32_t *row,
+                                      const ctvio_row_model *rm, const double *obs2, double *proj3, double *cov4, double *chi2, int32_t *row_out,
+                                      int32_t *status) {
+  CHK_S; return s->impl.project_landmarks(-1, n, win, lm, t_ns, row, rm, obs2, proj3, cov4, chi2, row_out, status);
+}
+int32_t ctvio_project_landmarks(ctvio_solver *s, int32_t id, int32_t n, const int32_t *lm, const int64_t *t_ns, const int32_t *row,
+                                const ctvio_row_model *rm, const double *obs2, double *proj3, double *cov4, double *chi2, int32_t *row_out,
+                                int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.project_landmarks(id, n, nullptr, lm, t_ns, row, rm, obs2, proj3, cov4, chi2, row_out, status);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

@@ -486,6 +486,71 @@ CTV_DI void rel_pose_jac_T(Q4 q_a, V3 p_a, Q4 q_b, V3 p_b, double *jt_a, double 
   }
 }
 
+// The visual factor's prediction of a landmark in the camera at a query time (ctvio_project_landmarks; ImageFeatureDelayFactor::Evaluate,
+// image_feature_factor.h:63-269, x_j): anchor camera pose (q_Ci, p_Ci), query camera pose (q_Cq, p_Cq), anchor observation (px, py, 1) and
+// inverse depth rho: X = R_Ci (p_i / rho) + p_Ci, y = R_Cq^T (X - p_Cq).  The prediction is (y.x / y.z, y.y / y.z) at depth y.z.
+CTV_DI V3 proj_point(Q4 q_Ci, V3 p_Ci, Q4 q_Cq, V3 p_Cq, double px, double py, double rho) {
+  const double z = 1.0 / rho;
+  const V3 dX = (mul(q2R(q_Ci), mk(px * z, py * z, z)) + p_Ci) - p_Cq;
+  const M3 R = q2R(q_Cq);
+  return mk(R.m[0] * dX.x + R.m[3] * dX.y + R.m[6] * dX.z, R.m[1] * dX.x + R.m[4] * dX.y + R.m[7] * dX.z, R.m[2] * dX.x + R.m[5] * dX.y + R.m[8] * dX.z);
+}
+// Its linear maps at y: Pi = (1 / y.z) [[1, 0, -y.x / y.z], [0, 1, -y.y / y.z]] (2 x 3, row-major) and M = Pi R_Cq^T, the map of a world
+// displacement of X.
+struct ProjLin { double Pi[6], M[6]; };
+CTV_DI ProjLin proj_lin(Q4 q_Cq, V3 y) {
+  ProjLin L;
+  const double iz = 1.0 / y.z;
+  L.Pi[0] = iz; L.Pi[1] = 0.0; L.Pi[2] = -(y.x * iz) * iz;
+  L.Pi[3] = 0.0; L.Pi[4] = iz; L.Pi[5] = -(y.y * iz) * iz;
+  const M3 R = q2R(q_Cq);
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) L.M[3 * a + b] = L.Pi[3 * a] * R.m[3 * b] + L.Pi[3 * a + 1] * R.m[3 * b + 1] + L.Pi[3 * a + 2] * R.m[3 * b + 2];
+  return L;
+}
+// One time's 24 x 2 block of the prediction's Jacobian, TRANSPOSED, from the 24 x 6 block jp that pose_jac_T wrote for the CAMERA pose at that
+// time (extrinsic on): jt[2 r + a] = d(proj_a) / d(unknown r of knots s .. s + 3).  Anchor time: M [-R_Ci [x_c]x, I] jp^T, x_c = p_i / rho (the
+// point Jacobian of ctvio_landmark_points, mapped by M); query time: [Pi [y]x, -M] jp^T (dy = [y]x dtheta_C - R_Cq^T dp_C).  Rows that are
+// exact zeros in jp (the last knot at u = 0) stay exact zeros (up to the sign of a zero).  jp and jt may not overlap.
+CTV_DI void proj_jac_T(const ProjLin &L, bool query, const M3 &R_Ci, V3 x_c, V3 y, const double *jp, double *jt) {
+  double B[12];
+  const M3 Hx = query ? hat(y) : scale(mul_hat(R_Ci, x_c), -1.0);
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double *T = query ? L.Pi : L.M;
+      B[6 * a + c] = T[3 * a] * Hx.m[c] + T[3 * a + 1] * Hx.m[3 + c] + T[3 * a + 2] * Hx.m[6 + c];
+      B[6 * a + 3 + c] = query ? -L.M[3 * a + c] : L.M[3 * a + c];
+    }
+  for (int r = 0; r < 24; ++r)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+      jt[2 * r + a] = ((B[6 * a] * jp[6 * r] + B[6 * a + 1] * jp[6 * r + 1]) + B[6 * a + 2] * jp[6 * r + 2]) +
+                      ((B[6 * a + 3] * jp[6 * r + 3] + B[6 * a + 4] * jp[6 * r + 4]) + B[6 * a + 5] * jp[6 * r + 5]);
+}
+// Its two remaining columns.  j = M (-R_Ci p_i / rho^2), the inverse depth; jld = the line delay, the formal derivative the factor uses, both
+// times summed: row_i M (R_Ii [omega_Ii]x (R_CI x_c + p_CI) + v_Ii) + row_q Pi ([y]x omega_C - R_Cq^T v_C) with omega_C = R_CI^T omega_Iq,
+// v_C = v_Iq + R_Iq [omega_Iq]x p_CI (omega: body rates of eval_omega, v: world velocities of the position spline).
+CTV_DI void proj_cols(const ProjLin &L, const M3 &R_Ci, double px, double py, double rho, V3 y, Q4 q_CI, V3 p_CI, double row_i, const M3 &R_Ii, V3 om_i,
+                      V3 v_i, double row_q, Q4 q_Iq, V3 om_q, V3 v_q, double j[2], double jld[2]) {
+  const double z = 1.0 / rho;
+  const V3 jr = (-z * z) * mul(R_Ci, mk(px, py, 1.0));
+  const V3 p_I = qrot(q_CI, mk(px * z, py * z, z)) + p_CI;
+  const V3 da = row_i * (mul(R_Ii, cross(om_i, p_I)) + v_i);
+  const V3 om_C = qrot(qconj(q_CI), om_q);
+  const V3 v_C = v_q + qrot(q_Iq, cross(om_q, p_CI));
+  const V3 rv = qrot(qconj(qmul(q_Iq, q_CI)), v_C);
+  const V3 dq = row_q * (cross(y, om_C) - rv);
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    j[a] = L.M[3 * a] * jr.x + L.M[3 * a + 1] * jr.y + L.M[3 * a + 2] * jr.z;
+    jld[a] = (L.M[3 * a] * da.x + L.M[3 * a + 1] * da.y + L.M[3 * a + 2] * da.z) + (L.Pi[3 * a] * dq.x + L.Pi[3 * a + 1] * dq.y + L.Pi[3 * a + 2] * dq.z);
+  }
+}
+
 // One midpoint step of the IMU dead reckoning (ctvio_imu_predict; the mean of VisualOdometry::ProcessIMU, visual_odometry.cpp:137-172) from
 // sample (w0, a0) to sample (w1, a1), dt apart, with the biases (bg, ba) held and g the window's gravity (sign as in the IMU factor):
 //   w = (w0 + w1) / 2 - bg,  R' = R Exp(w dt),  A = ((R (a0 - ba) - g) + (R' (a1 - ba) - g)) / 2,  p' = p + dt v + dt^2 A / 2,  v' = v + dt A.

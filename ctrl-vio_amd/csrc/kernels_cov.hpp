@@ -4,7 +4,9 @@
 // points of the landmarks with their 3 x 3 covariances (ctvio_landmark_points_batch): k_cov_point_jac (one record per landmark), then
 // k_cov_solve on tiles of kind 3; navigation states (pose, velocity, biases) with their 15 x 15 covariances (ctvio_nav_state_batch):
 // k_cov_nav_jac (one record per query), then k_cov_solve on tiles of kind 4; pose increments between two times with their 6 x 6 covariances
-// (ctvio_relative_pose_batch): k_cov_rel_jac (one record per query), then k_cov_solve on tiles of kind 5.
+// (ctvio_relative_pose_batch): k_cov_rel_jac (one record per query), then k_cov_solve on tiles of kind 5; predicted image points of landmarks
+// at query times with their 2 x 2 covariances and gates (ctvio_project_landmarks_batch): k_cov_proj_jac (one record per query), then
+// k_cov_solve on tiles of kind 6.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -20,6 +22,9 @@
 //                     (factors.hpp: nav_jac_T; the bias rows are one-hot),
 //   Sigma_rel(a, b) = (L^-1 J^T)^T (L^-1 J^T)                      for the 6 x P Jacobian J = A_a J_a + A_b J_b of the increment T(t_a)^-1 T(t_b)
 //                     (factors.hpp: rel_pose_jac_T; J_a, J_b the pose Jacobians at the two times),
+//   Cov(proj)       = (L^-1 G)^T (L^-1 G) + j j^T / Hll_l           for the predicted image point of landmark l at a query time: Cov(X_l)'s identity
+//                     with two columns, G = Jp^T - w_l j^T / Hll_l, Jp over the knots of the anchor time and of the query time and the line
+//                     delay (factors.hpp: proj_jac_T, proj_cols), j = d(proj) / drho_l,
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -32,10 +37,11 @@ struct CovTile {
                     // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5); 3: the three columns of G of up to five landmarks
                     // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused); 4: the fifteen columns of J^T of one navigation-state
                     // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 5: the six columns of
-                    // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5)
+                    // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5); 6: the two columns of G of up to eight
+                    // projection queries of the window (columns 2 q, 2 q + 1)
   int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
-                    // kind 2 and 5: the tile's first query record; kind 4: its query record
-  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4: 1
+                    // kind 2, 5 and 6: the tile's first query record; kind 4: its query record
+  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4: 1; kind 6: queries (<= 8)
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -348,6 +354,132 @@ __global__ __launch_bounds__(64) void k_cov_point_jac(Dev d, int l_begin, int l_
       r.jt[3 * rr + a] = Mx.m[3 * a] * jp[6 * rr] + Mx.m[3 * a + 1] * jp[6 * rr + 1] + Mx.m[3 * a + 2] * jp[6 * rr + 2] + jp[6 * rr + 3 + a];
 }
 
+// One projection query (ctvio_project_landmarks_batch), grouped by window on the host, and what k_cov_proj_jac makes of it.
+enum { PRJ_OK = 0, PRJ_SINGULAR = 1, PRJ_NO_INFO = 2, PRJ_NONE = 3 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
+constexpr int PRJ_PER_TILE = 8;
+struct ProjQuery {
+  int32_t win, lm, row, pad;   // lm: the caller's landmark index in the window; row: the image row, or the first guess of the row iteration
+  long long t_rel;             // the frame time relative to the window's t0
+  double obs[2];               // the candidate point of the gate (zeros without one)
+};
+struct ProjRowModel { double fy, cy; int32_t rows, iterations; };   // ctvio_row_model; iterations == 0: the rows are used as given
+struct ProjRec {
+  int32_t status, s_a, nk_a, s_q, nk_q, wrow;   // per time (anchor, query): first knot; knots the pose depends on (3 at u = 0, else 4); wrow: the
+                                                // landmark's sorted row of W (window-local)
+  double proj[2], obs[2];                       // the prediction as returned in proj3, the candidate point
+  double j[2], jld[2];                          // d(proj) / drho; d(proj) / d(line delay), both times summed (proj_cols)
+  double jt_a[48], jt_q[48];                    // the two 24 x 2 blocks of Jp^T over knots s_a .. s_a + 3 and s_q .. s_q + 3 (proj_jac_T)
+                                                // (j, jld, jt_a, jt_q: written for PRJ_OK only)
+};
+
+// The body pose at tau (inside the spline), the body rate and world velocity there, and the 24 x 6 block of pose_jac_T for the camera pose.
+__device__ inline void proj_side(const Dev &d, const WinMeta &m, long long tau, Q4 q_CI, V3 p_CI, double *jp, Q4 &q_I, V3 &om, V3 &v) {
+  const int s = (int)(tau / m.dt_ns);
+  const double u = (double)(tau % m.dt_ns) / (double)m.dt_ns;
+  const double zero3[3] = {0, 0, 0};
+  Knots4 k;
+  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  SegConst sc;
+  seg_const(k, sc, true);
+  q_I = eval_R(k.q, sc, u);
+  double dc[4];
+  basis<false, 1>(u, m.inv_dt, dc);
+  v = mk(0, 0, 0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v = v + dc[j] * k.p[j];
+  om = eval_omega<SegConst>(sc, u, m.inv_dt);
+  pose_jac_T(k.q, sc, u, true, q_CI, p_CI, jp);
+}
+
+// One lane per query: the anchor observation of the landmark as k_cov_point_jac reads it and the camera pose at its row time; the camera pose
+// at tau_q = t + row * line delay (integer ns, vis_times' rule) and y = R_Cq^T (X - p_Cq).  With a row model (rm.iterations > 0) the row is
+// first iterated: y at the current row, then row <- clamp(rint(fy y.y / y.z + cy), 0, rows - 1); value and Jacobian are taken at the final row.
+// PRJ_NONE: the landmark is not computable (k_cov_point_jac's rules), or at any row visited tau_q is outside the spline or y.z <= 0 or y is
+// not finite; the iteration stops there, the loads stay in range (rel_side: s = 0 outside the spline), proj3 is NaN and row_out -1.  The value
+// is formed before excl is looked at, by code the Jacobians do not share: the values-only call (excl null; recs is not touched) gives it the
+// same bits.  With excl (after k_cov_prepare) the status and the record: PRJ_NO_INFO where 1 / Hll == 0 (d.dinv) or a knot either time
+// depends on has an unknown no factor touches (COV_UNTOUCHED; decided on the exclusion flags and on u > 0, never on a Jacobian entry).  The
+// anchor block is formed in the 144-double pose buffer and stored, then the buffer is reused for the query block.
+__global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQuery *qs, const uint8_t *excl, ProjRowModel rm, ProjRec *recs, double *proj3,
+                                                     int32_t *row_out, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const ProjQuery q = qs[i];
+  const int w = q.win;
+  const WinMeta &m = d.wins[w];
+  const int l = m.lm0 + q.lm;
+  const double rho = d.rho[l];
+  const int first = d.lm_vfirst[l], cnt = d.lm_vcnt[l];
+  bool ok = rho > 0.0 && isfinite(rho) && cnt > 0;
+  int a0 = m.anc0;
+  if (cnt > 0) {
+    a0 = d.v_anc[first];
+    for (int j = 1; j < cnt; ++j) ok = ok && d.v_anc[first + j] == a0;
+  }
+  const int row_i = cnt > 0 ? d.a_row[a0] : 0;
+  const long long ld_ns = (long long)(d.ld[w] * 1e9);
+  const long long tau_i = cnt > 0 ? d.a_t[a0] + (long long)row_i * ld_ns : 0;
+  const double px = cnt > 0 ? d.a_obs[a0] : 0.0, py = cnt > 0 ? d.a_obs[(size_t)d.Atot + a0] : 0.0;
+  const Q4 q_CI = qmk(m.q_CI[0], m.q_CI[1], m.q_CI[2], m.q_CI[3]);
+  const V3 p_CI = mk(m.p_CI[0], m.p_CI[1], m.p_CI[2]);
+  SensorExt cam;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cam.q[j] = m.q_CI[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) cam.p[j] = m.p_CI[j];
+  cam.on = 1;
+  int s_a, nk_a, s_q, nk_q;
+  bool out_a, out_q;
+  Q4 q_Ci, q_Cq;
+  V3 p_Ci, p_Cq, y;
+  rel_side(d, m, tau_i, cam, nullptr, s_a, nk_a, out_a, q_Ci, p_Ci);
+  ok = ok && !out_a;
+  int row = q.row;
+  long long tau_q;
+  for (int it = 0;; ++it) {
+    tau_q = q.t_rel + (long long)row * ld_ns;
+    rel_side(d, m, tau_q, cam, nullptr, s_q, nk_q, out_q, q_Cq, p_Cq);
+    y = proj_point(q_Ci, p_Ci, q_Cq, p_Cq, px, py, rho);
+    ok = ok && !out_q && y.z > 0.0 && isfinite(y.x) && isfinite(y.y) && isfinite(y.z);
+    if (it >= rm.iterations || !ok) break;
+    row = (int)fmin(fmax(rint(rm.fy * y.y / y.z + rm.cy), 0.0), (double)(rm.rows - 1));
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double zx = y.x / y.z, zy = y.y / y.z;
+  proj3[3 * (size_t)i] = ok ? zx : nan; proj3[3 * (size_t)i + 1] = ok ? zy : nan; proj3[3 * (size_t)i + 2] = ok ? y.z : nan;
+  row_out[i] = ok ? row : -1;
+  int status = ok ? PRJ_OK : PRJ_NONE;
+  if (!excl) {
+    status_out[i] = status;
+    return;
+  }
+  const int wrow = d.lm_pos[l];
+  if (ok) {
+    if (d.dinv[m.lm0 + wrow] == 0.0) status = PRJ_NO_INFO;
+    for (int j = 6 * s_a; j < 6 * (s_a + nk_a); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
+    for (int j = 6 * s_q; j < 6 * (s_q + nk_q); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
+  }
+  ProjRec &r = recs[i];
+  r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_q = s_q; r.nk_q = nk_q; r.wrow = wrow;
+  r.proj[0] = zx; r.proj[1] = zy; r.obs[0] = q.obs[0]; r.obs[1] = q.obs[1];
+  status_out[i] = status;
+  if (status != PRJ_OK) return;
+  const double z = 1.0 / rho;
+  const V3 x_c = mk(px * z, py * z, z);
+  const M3 R_Ci = q2R(q_Ci);
+  const ProjLin L = proj_lin(q_Cq, y);
+  double jp[144];
+  Q4 q_Ii, q_Iq;
+  V3 om_i, v_i, om_q, v_q;
+  proj_side(d, m, tau_i, q_CI, p_CI, jp, q_Ii, om_i, v_i);
+  proj_jac_T(L, false, R_Ci, x_c, y, jp, r.jt_a);
+  proj_side(d, m, tau_q, q_CI, p_CI, jp, q_Iq, om_q, v_q);
+  proj_jac_T(L, true, R_Ci, x_c, y, jp, r.jt_q);
+  proj_cols(L, R_Ci, px, py, rho, y, q_CI, p_CI, (double)row_i, q2R(q_Ii), om_i, v_i, (double)row, q_Iq, om_q, v_q, r.j, r.jld);
+}
+
 // Y = L^-1 B for one tile of 16 right-hand sides.  d is the covariance's copy of Dev (d.active = the per-call mask).  Four waves: wave (h, kp)
 // owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of a half are added
 // in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row, as the back-substitution of the panel
@@ -364,15 +496,23 @@ __global__ __launch_bounds__(64) void k_cov_point_jac(Dev d, int l_begin, int l_
 // are what they were before kind 5 existed): sel = the caller's slot of every query record, prec = the records (RelRec), pose_cov = the
 // caller-ordered 6 x 6 blocks; kind 2's epilogue.  The a-rows are stored, then after a barrier the b-rows are added: where the knot groups
 // of the two times overlap every entry is "a-term + b-term" in that order, elsewhere the one term (0.0 + b-term for a b-row).
+// Kind 6 (the instantiation PROJ = true, which holds no other kind and leaves the code of the other two what it was): prec = the records
+// (ProjRec, in the order of the tiles), pose_cov = the 2 x 2 blocks and var_rho = the gates chi2 (null: not asked for), both by record.
+// Columns 2 q, 2 q + 1 of query q: kind 3's -(w_l / Hll) j^T over the span of the landmark's row of W and the line-delay column; after a
+// barrier + the anchor rows, after another + the query rows -- where the knot groups of the two times overlap every entry is "anchor term
+// + query term" in that order -- and the line-delay row.  Epilogue: the three unique entries of every 2 x 2 Gram block, four partial sums over
+// the rows k = p mod 4 added in sequence, + j j^T / Hll, mirrored; then chi2 = e^T (Cov + I / img_w^2)^-1 e, e = obs - proj, by the 2 x 2
+// Cholesky factor, from the block just written and the record's prediction.  Queries whose status is not PRJ_OK keep zero columns and write nothing.
 // amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
 // SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
 // inlined as well.
 constexpr int COV_NT = 256;
-template <bool REL> struct CovQueryRec { typedef PoseRec type; };
-template <> struct CovQueryRec<true> { typedef RelRec type; };
-template <bool REL>
+template <bool REL, bool PROJ = false> struct CovQueryRec { typedef PoseRec type; };
+template <> struct CovQueryRec<true, false> { typedef RelRec type; };
+template <> struct CovQueryRec<false, true> { typedef ProjRec type; };
+template <bool REL, bool PROJ = false>
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const typename CovQueryRec<REL>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
+                                                      const typename CovQueryRec<REL, PROJ>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
                                                       const NavRec *nrec, double *nav_cov) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
@@ -388,7 +528,47 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
   for (int e = tid; e < 16 * PP; e += COV_NT) Ys[e] = 0.0;
   if (tid == 0) s_first = PP;
   __syncthreads();
-  if constexpr (REL) {   // rows 6 s_a .. 6 (s_a + nk_a) - 1 of every query's six columns, then + rows 6 s_b .. 6 (s_b + nk_b) - 1, where the unknown is in the system
+  if constexpr (PROJ) {
+    const int q = tid >> 4, sub = tid & 15;
+    if (q < t.count) {   // -(w_l / Hll) j^T: the row's planned span, then the line-delay column
+      const ProjRec &pr = prec[t.first + q];
+      const int row = m.lm0 + pr.wrow, klo = d.lm_klo[row], khi = d.lm_khi[row];
+      const double dv = d.dinv[row];
+      const double *Wr = d.WS[cur] + m.W0 + (long long)pr.wrow * m.ldw;
+      if (pr.status == PRJ_OK && khi >= klo && dv != 0.0) {
+        const double j0 = -pr.j[0], j1 = -pr.j[1];
+        const int cend = min(6 * khi + 6, P);
+        for (int c = 6 * klo + sub; c < cend; c += 16)
+          if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 2 * q] = v * j0; Ys[c * 16 + 2 * q + 1] = v * j1; }
+        if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
+          const double v = Wr[P - 1] * dv;
+          Ys[(P - 1) * 16 + 2 * q] = v * j0; Ys[(P - 1) * 16 + 2 * q + 1] = v * j1;
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < 48 * t.count; e += COV_NT) {   // + the anchor rows 6 s_a .. 6 (s_a + nk_a) - 1
+      const int qi = e / 48, r = (e % 48) / 2, a = e % 2;
+      const ProjRec &pr = prec[t.first + qi];
+      if (pr.status == PRJ_OK && r < 6 * pr.nk_a && d.active[m.u0 + 6 * pr.s_a + r]) Ys[(6 * pr.s_a + r) * 16 + 2 * qi + a] += pr.jt_a[2 * r + a];
+    }
+    __syncthreads();
+    for (int e = tid; e < 50 * t.count; e += COV_NT) {   // + the query rows 6 s_q .. 6 (s_q + nk_q) - 1 (r < 24), then the line-delay row (r = 24)
+      const int qi = e / 50, r = (e % 50) / 2, a = e % 2;
+      const ProjRec &pr = prec[t.first + qi];
+      if (pr.status != PRJ_OK) continue;
+      const int c = r < 24 ? 6 * pr.s_q + r : P - 1;
+      if ((r < 6 * pr.nk_q || r == 24) && d.active[m.u0 + c]) Ys[c * 16 + 2 * qi + a] += r < 24 ? pr.jt_q[2 * r + a] : pr.jld[a];
+    }
+    if (tid == 0)
+      for (int qi = 0; qi < t.count; ++qi) {
+        const ProjRec &pr = prec[t.first + qi];
+        if (pr.status != PRJ_OK) continue;
+        const int row = m.lm0 + pr.wrow;
+        s_first = min(s_first, 6 * min(pr.s_a, pr.s_q));
+        if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
+      }
+  } else if constexpr (REL) {   // rows 6 s_a .. 6 (s_a + nk_a) - 1 of every query's six columns, then + rows 6 s_b .. 6 (s_b + nk_b) - 1, where the unknown is in the system
     for (int e = tid; e < 144 * t.count; e += COV_NT) {
       const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
       const RelRec &rr = prec[t.first + qi];
@@ -539,6 +719,36 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
       for (int r = 0; r < 4; ++r) Ys[(32 * b + 16 * h + q4 + 4 * r) * 16 + l15] = yv[r];
     }
     __syncthreads();
+  }
+  if constexpr (PROJ) {   // projection tiles: entries (0,0), (0,1), (1,1) of the eight 2 x 2 Gram blocks, then the gate
+    const int k0 = min(32 * b0, P);
+    constexpr int NE = 3 * PRJ_PER_TILE;
+    if (tid < 4 * NE) {
+      const int p = tid / NE, e = tid % NE, x = e % 3, ci = 2 * (e / 3) + (x == 2), cj = 2 * (e / 3) + (x != 0);
+      double s = 0.0;
+      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+      part[p * NE + e] = s;
+    }
+    __syncthreads();
+    if (tid < t.count) {
+      const ProjRec &pr = prec[t.first + tid];
+      if (pr.status == PRJ_OK) {
+        const double dv = d.dinv[m.lm0 + pr.wrow];
+        double c[3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+          c[x] = (((part[3 * tid + x] + part[NE + 3 * tid + x]) + part[2 * NE + 3 * tid + x]) + part[3 * NE + 3 * tid + x]) + (pr.j[x == 2] * pr.j[x != 0]) * dv;
+        double *o = pose_cov + (long long)4 * (t.first + tid);
+        o[0] = c[0]; o[1] = c[1]; o[2] = c[1]; o[3] = c[2];
+        if (var_rho) {
+          const double iw2 = 1.0 / (m.img_w * m.img_w), e0 = pr.obs[0] - pr.proj[0], e1 = pr.obs[1] - pr.proj[1];
+          const double l00 = sqrt(c[0] + iw2), l10 = c[1] / l00, l11 = sqrt((c[2] + iw2) - l10 * l10);
+          const double z0 = e0 / l00, z1 = (e1 - l10 * z0) / l11;
+          var_rho[t.first + tid] = z0 * z0 + z1 * z1;
+        }
+      }
+    }
+    return;
   }
   if (!REL && t.kind == 0) {   // a selection tile: Y to the scratch, for k_cov_gram
     double *yo = yscr + t.yoff;

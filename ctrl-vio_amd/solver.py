@@ -7,6 +7,7 @@ Solve(max_iterations), copy the state back -- except that many independent windo
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -361,6 +362,40 @@ class Solver:
         """ctvio_relative_pose: the same for the pairs of times of window wid alone (same bits as the batch entry)."""
         return self._relative_pose(lambda n, ta, tb, q, p, r, c, st: self._lib.ctvio_relative_pose(self._h, int(wid), n, ta, tb, q, p, r, c, st),
                                    t_a, t_b, q_SI, p_SI, cov)
+
+    def _project_landmarks(self, call, lm, t_ns, row, row_model, obs, cov, n_win=None):
+        li = np.ascontiguousarray(lm, np.int32).reshape(-1); t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        r = np.ascontiguousarray(row, np.int32).reshape(-1)
+        n = int(li.shape[0])
+        o = None if obs is None else np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+        assert t.shape[0] == n and r.shape[0] == n and (o is None or o.shape[0] == n) and (n_win is None or n_win == n)
+        if o is not None and not cov:
+            raise ValueError("obs needs cov=True: the gate is formed from the covariance")
+        rm = None
+        if row_model is not None:
+            rm = row_model if isinstance(row_model, capi.RowModel) else capi.RowModel(float(row_model[0]), float(row_model[1]), int(row_model[2]), int(row_model[3]))
+        m = max(n, 1)
+        proj = np.zeros((m, 3)); c = np.zeros((m, 2, 2)) if cov else None; chi = np.zeros(m) if o is not None else None
+        ro = np.zeros(m, np.int32); st = np.zeros(m, np.int32)
+        capi.check(call(n, capi._p(li), capi._p(t), capi._p(r), C.byref(rm) if rm is not None else None, capi._p(o) if o is not None else None,
+                        capi._p(proj), capi._p(c) if cov else None, capi._p(chi) if chi is not None else None, capi._p(ro), capi._p(st)))
+        return SimpleNamespace(proj=proj[:n].copy(), cov=c[:n].copy() if cov else None, chi2=chi[:n].copy() if chi is not None else None,
+                               row=ro[:n].copy(), status=st[:n].copy())
+
+    def project_landmarks_batch(self, win, lm, t_ns, row, cov: bool = True, obs=None, row_model=None):
+        """ctvio_project_landmarks_batch: where landmark lm[i] of window win[i] falls in the camera at frame time t_ns[i], image row row[i], at the
+        current state: proj (n, 3) = the normalised image point and the depth in the query camera; with cov the 2 x 2 covariance of the point
+        (trajectory, inverse depth and their cross terms); with obs (n, 2) the gate chi2 = e^T (Cov + I / img_w^2)^-1 e of the candidate points.
+        row_model = (fy, cy, rows, iterations) or capi.RowModel: row[i] is the first guess of a pinhole row iteration, the final row comes
+        back in .row.  Returns a namespace (proj, cov or None, chi2 or None, row, status): 0 ok, 1 singular window (cov, chi2 NaN), 2 no
+        information (+inf diagonal, chi2 0), 3 not computable (NaN, row -1).  cov=False: one kernel, nothing is linearised."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
+        return self._project_landmarks(lambda n, *a: self._lib.ctvio_project_landmarks_batch(self._h, C.c_int64(n), capi._p(wi), *a),
+                                       lm, t_ns, row, row_model, obs, cov, int(wi.shape[0]))
+
+    def project_landmarks(self, wid: int, lm, t_ns, row, cov: bool = True, obs=None, row_model=None):
+        """ctvio_project_landmarks: the same for queries of window wid alone (same bits as the batch entry)."""
+        return self._project_landmarks(lambda n, *a: self._lib.ctvio_project_landmarks(self._h, int(wid), n, *a), lm, t_ns, row, row_model, obs, cov)
 
     def _imu_noise(self, noise):
         o = capi.ImuNoise()

@@ -328,6 +328,53 @@ int32_t ctvio_relative_pose_batch(ctvio_solver *s, int64_t n, const int32_t *win
 int32_t ctvio_relative_pose(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_a_ns, const int64_t *t_b_ns,
                             const double *q_SI, const double *p_SI, double *rel7, double *cov36, int32_t *status);
 
+/* WHERE A LANDMARK FALLS IN THE CAMERA at a time, and how sure the window is: what a visual front end asks before the next solve -- the
+ * prediction seeds the tracker, the 2 x 2 covariance sizes the search window, the Mahalanobis distance of a candidate match gates it.  The
+ * value is the visual factor's own prediction (ImageFeatureDelayFactor::Evaluate, image_feature_factor.h:63-269: x_j.xy / x_j.z); the
+ * reference has no covariance for it.
+ * Query i = (window win[i], landmark lm[i] in the caller's landmark order, frame time t_ns[i], image row row[i]) at the CURRENT state.  Any
+ * number of queries, in any order, from any windows; the same landmark may be queried many times.  Landmark l is anchored as in
+ * ctvio_landmark_points: anchor observation (t_i, row_i, p_i), x_c = p_i / rho, X = R_C(tau_i) x_c + p_C(tau_i).  With
+ * tau_q = t + row * (int64)(ld * 1e9) and the window's camera extrinsic:
+ *   y = R_C(tau_q)^T (X - p_C(tau_q)),   proj3 = (y.x / y.z, y.y / y.z, y.z): the normalised image point and the depth in the query camera.
+ * For a query that coincides with a visual block (t_j, row_j), img_w (proj.xy - p_j) is that block's residual before the robust loss.
+ *   rm == NULL: row[i] is used as given.  rm != NULL (pinhole rows without distortion): row[i] is the first guess and the row is iterated
+ *   rm->iterations times (1 .. 8): one iteration evaluates y at the current row, then sets row <- clamp(lrint(fy y.y / y.z + cy), 0, rows - 1).
+ *   Value and Jacobian are taken at the final row, which goes to row_out (n entries, or NULL).  The row is treated as GIVEN in the
+ *   covariance: its own dependence on the state is of second order in ld |dy/dt|.  A caller with a distorted camera passes rows explicitly.
+ *   cov4 (n x 4 doubles, row-major 2 x 2, symmetric to the bit, or NULL): the first-order covariance of proj.xy, with H, the exclusions and
+ *   Sigma exactly those of ctvio_covariance_batch (no damping).  With Pi = (1 / y.z) [[1, 0, -z0], [0, 1, -z1]], z = proj.xy, the row Jp of
+ *   either coordinate against the trajectory unknowns (the library's retraction) is, on the knots of the anchor time, Pi R_Cq^T Jp_X with Jp_X
+ *   the point Jacobian of ctvio_landmark_points; on the knots of the query time Pi ([y]x J_theta - R_Cq^T J_p) with (J_theta, J_p) the
+ *   camera-pose Jacobian of ctvio_pose_covariance at tau_q; in the line-delay column the anchor's (Pi R_Cq^T times the line-delay column of
+ *   ctvio_landmark_points) plus row_q Pi ([y]x omega_C - R_Cq^T v_C), omega_C = R_CI^T omega_I(tau_q), v_C = v_I(tau_q) + R_I(tau_q)
+ *   [omega_I]x p_CI, the formal derivative the factor itself uses.  j = Pi R_Cq^T (-R_Ci p_i / rho^2) is the inverse-depth column.  Then
+ *     G = Jp^T - w_l j^T / h_l  (rows of excluded unknowns zero),   Cov = G^T Sigma_pp G + j j^T / h_l,
+ *   pose-landmark cross terms included.  Constant unknowns contribute nothing.
+ *   chi2 (n doubles, or NULL; requires obs2, n x 2 candidate image points): e^T (Cov + I / img_w^2)^-1 e with e = obs - proj.xy, formed on
+ *   the device from the very cov4 and proj3 bits that are returned.  The gate is meant for NEW matches: for an observation that is already a
+ *   block of the window, estimate and measurement are correlated and the sum above overstates the variance of e.
+ *   status (n entries, or NULL) per query, in this precedence: 3 not computable -- the landmark by the rules of ctvio_landmark_points status 3,
+ *   tau_q outside [t0, t0 + (K - 3) dt) at any row visited, y.z <= 0 or non-finite at any row visited: everything NaN, row_out -1;  2
+ *   Hll_l == 0, or a knot either time depends on (knot s + 3 only where u > 0) has a non-constant unknown no factor touches: value valid,
+ *   +inf on the diagonal, 0 elsewhere, chi2 = 0;  1 the window's factorisation met a bad pivot: value valid, covariance and chi2 NaN;  0 ok.
+ *   With cov4 == NULL and chi2 == NULL nothing is linearised or factored: one kernel evaluates the values, statuses 1 and 2 cannot occur, and
+ *   the values have the bits of the covariance call's.
+ * The call returns CTVIO_OK for every status.  n == 0 returns CTVIO_OK and launches nothing.  CTVIO_ERR_STATE before the upload;
+ * CTVIO_ERR_INVALID for a window id or landmark index out of range, n < 0, a NULL lm / t_ns / row (batch entry: win) with n > 0, every output
+ * NULL with n > 0, chi2 without obs2, a non-finite obs2, rm with iterations outside 1 .. 8, rows < 1 or non-finite fy / cy; the handle stays
+ * usable.  The state, the launch plan and the captured graph of the solve are left as they were; no atomics: where the linearisation is
+ * order-fixed (opt.deterministic) the bits of a query's result depend on its own arguments alone -- not on the entry (batch or single-window:
+ * win is window id for every query), the order of the queries, which queries share its tile or call, or which optional outputs were asked for.
+ * ctvio_last_timing: ms8[0..2] = k_cov_prepare, k_cov_solve, k_cov_proj_jac, ms8[7] the whole call; values only: ms8[2] and ms8[7]. */
+typedef struct ctvio_row_model { double fy, cy; int32_t rows, iterations; } ctvio_row_model;   /* 24 bytes */
+int32_t ctvio_project_landmarks_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int32_t *lm, const int64_t *t_ns, const int32_t *row,
+                                      const ctvio_row_model *rm, const double *obs2,
+                                      double *proj3, double *cov4, double *chi2, int32_t *row_out, int32_t *status);
+int32_t ctvio_project_landmarks(ctvio_solver *s, int32_t id, int32_t n, const int32_t *lm, const int64_t *t_ns, const int32_t *row,
+                                const ctvio_row_model *rm, const double *obs2,
+                                double *proj3, double *cov4, double *chi2, int32_t *row_out, int32_t *status);
+
 /* BETWEEN FRAMES: IMU dead reckoning from the navigation state, with its 15 x 15 covariance -- what VisualOdometry::ProcessIMU
  * (visual_odometry.cpp:137-172) does with the state SlideWindow hands it, and where AddImageToWindow (:188-191) takes the predicted pose of
  * the next frame from; beside the mean, the first-order covariance that IntegrationBase::midPointIntegration (integration_base.h:100-179)
@@ -507,6 +554,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * whole call on the device (its copies included), the rest zero.
  * After an IMU-prediction call: ms8[0..2] as after a navigation-state call, ms8[3] = device time of k_imu_propagate, ms8[7] = the whole call on
  * the device, the rest zero; states only (cov225 == NULL): ms8[2], ms8[3] and ms8[7].
+ * After a landmark-projection call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution, the 2 x 2 blocks and the gates),
+ * k_cov_proj_jac, ms8[7] = the whole call on the device, the rest zero; values only (cov4 == NULL and chi2 == NULL): ms8[2] = device time of
+ * k_cov_proj_jac, ms8[7] = the whole call on the device (its copies included), the rest zero.
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

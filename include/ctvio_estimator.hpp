@@ -682,6 +682,40 @@ class TrajectoryEstimator {
     }
     return ok;
   }
+  // Where landmarks fall in the camera at later times, at the CURRENT parameter values (ctvio_project_landmarks): what a front end asks before
+  // it tracks the next image.  Query i = (the inverse-depth pointer as passed to AddImageFeatureDelayAnalytic, frame time, image row).
+  // proj3 = 3 doubles per query: the normalised image point (the factor's own prediction x_j.xy / x_j.z) and the depth in the query camera;
+  // cov4 (optional) = 4 per query, the row-major 2 x 2 covariance of the point from the factors of Solve -- without it and chi2 nothing is
+  // linearised; obs2 + chi2 (optional, together): candidate image points, 2 per query, and their gates e^T (Cov + I / img_w^2)^-1 e (meant for
+  // NEW matches: ctvio.h); rm (optional): a pinhole row model, rows are then first guesses and the final rows come back in row_out (optional);
+  // status (optional) = one ctvio_project_landmarks status per query.  Returns false if any status is not 0.
+  struct ProjectionQuery { const double *inv_depth; int64_t timestamp; int32_t row; };
+  bool ProjectLandmarks(const std::vector<ProjectionQuery> &queries, std::vector<double> &proj3, std::vector<double> *cov4 = nullptr,
+                        const std::vector<double> *obs2 = nullptr, std::vector<double> *chi2 = nullptr, const ctvio_row_model *rm = nullptr,
+                        std::vector<int32_t> *row_out = nullptr, std::vector<int32_t> *status = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t n = queries.size();
+    if ((chi2 != nullptr) != (obs2 != nullptr) || (obs2 && obs2->size() != 2 * n)) throw std::invalid_argument("ProjectLandmarks: obs2 (2 per query) and chi2 come together");
+    std::vector<int32_t> lm(n), row(n), st(n, 0), ro(n, 0);
+    std::vector<int64_t> t(n);
+    for (size_t i = 0; i < n; ++i) {
+      auto it = lm_of_.find(queries[i].inv_depth);
+      if (it == lm_of_.end() || pk.lm_map[(size_t)it->second] < 0) throw std::invalid_argument("ProjectLandmarks: not a landmark of this window");
+      lm[i] = pk.lm_map[(size_t)it->second]; t[i] = queries[i].timestamp; row[i] = queries[i].row;
+    }
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    proj3.assign(3 * n, 0.0);
+    if (cov4) cov4->assign(4 * n, 0.0);
+    if (chi2) chi2->assign(n, 0.0);
+    check(ctvio_project_landmarks(s, 0, (int32_t)n, lm.data(), t.data(), row.data(), rm, obs2 ? obs2->data() : nullptr, proj3.data(),
+                                  cov4 ? cov4->data() : nullptr, chi2 ? chi2->data() : nullptr, ro.data(), st.data()));
+    if (row_out) *row_out = ro;
+    if (status) *status = st;
+    for (int32_t v : st) if (v != 0) return false;
+    return true;
+  }
 
  private:
   // One packed window: only the knots the factors touch (the reference registers exactly those with Ceres,
