@@ -95,7 +95,7 @@ SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "
            "ctvio_covariance_batch", "ctvio_covariance", "ctvio_pose_covariance_batch", "ctvio_pose_covariance",
            "ctvio_landmark_points_batch", "ctvio_landmark_points", "ctvio_nav_state_batch", "ctvio_nav_state",
            "ctvio_relative_pose_batch", "ctvio_relative_pose", "ctvio_project_landmarks_batch", "ctvio_project_landmarks",
-           "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict",
+           "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict", "ctvio_body_rates_batch", "ctvio_body_rates",
            "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
 _lib = None
@@ -148,6 +148,8 @@ def load_library():
         lib.ctvio_landmark_points.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
         lib.ctvio_nav_state_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
         lib.ctvio_nav_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+        lib.ctvio_body_rates_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 9
+        lib.ctvio_body_rates.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 8
         lib.ctvio_relative_pose_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 8
         lib.ctvio_relative_pose.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 7
         lib.ctvio_project_landmarks_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.POINTER(RowModel)] + [C.c_void_p] * 6

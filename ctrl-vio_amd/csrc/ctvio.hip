@@ -138,6 +138,7 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     return CTVIO_OK;
   }
   int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
@@ -1558,6 +1559,135 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // ctvio_body_rates_batch / ctvio_body_rates (only >= 0: every query belongs to that window, win is not read): body angular velocity,
+  // specific force and body-frame velocity at n query times, J Sigma J^T of (domega, df, dv_B, dbg, dba) with the biases of state frame[i]
+  // (frame null: the newest), and the gate of a candidate IMU sample.  Values only (cov225 and chi2 null): k_cov_rates_jac alone, nothing
+  // is linearised or factored.  Otherwise nav_state()'s middle: the queries grouped by window (stable) into tiles of kind 7, one each;
+  // k_cov_rates_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 15 x 15 blocks and the gates
+  // into the caller's slots.  dev_, plan_ and the captured graph are not touched.
+  int body_rates(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const int32_t *frame, const double *meas6, const double *noise6,
+                 double *rates9, double *cov225, double *chi2, int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || (only < 0 && !win) || (!rates9 && !cov225 && !chi2 && !status) || (chi2 && !meas6))))
+      return fail(CTVIO_ERR_INVALID, "bad arguments");
+    const int n = (int)n64, nw = dev_.nwin;
+    const size_t nn = (size_t)n;
+    if (n && noise6)
+      for (int c = 0; c < 6; ++c)
+        if (!(noise6[c] > 0.0) || !std::isfinite(noise6[c])) return fail(CTVIO_ERR_INVALID, "noise6: six positive, finite standard deviations");
+    for (int i = 0; i < n; ++i) {
+      const int w = only >= 0 ? only : win[i];
+      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": bias state out of range");
+      for (int c = 0; c < 6; ++c) {
+        if (meas6 && !std::isfinite(meas6[6 * (size_t)i + c])) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": non-finite IMU sample");
+        if (chi2 && !noise6 && !(meta_[w].imu_w[c] > 0.0))
+          return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": noise6 is null and the window's imu_w has a non-positive entry");
+      }
+    }
+    if (n == 0) return CTVIO_OK;
+    // ---- queries by window; slot[r]: the caller's index of sorted query r
+    std::vector<int32_t> slot(nn);
+    for (int i = 0; i < n; ++i) slot[i] = i;
+    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
+    auto query_of = [&](int r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      const int w = win_of(r);
+      RatesQuery q{w, frame ? frame[i] : meta_[w].F - 1, (long long)(t_ns[i] - t0_[w]), {0, 0, 0, 0, 0, 0}, {1, 1, 1, 1, 1, 1}};
+      for (int c = 0; c < 6 && chi2; ++c) { q.meas[c] = meas6[6 * i + c]; q.sig[c] = noise6 ? noise6[c] : 1.0 / meta_[w].imu_w[c]; }
+      return q;
+    };
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    if (!cov225 && !chi2) {   // in: queries (one staged copy); out: rates9 | status (one copy)
+      CallLayout io = head_;
+      const int s_q = io.add("queries", sizeof(RatesQuery), nn, false), s_val = io.add("rates9", sizeof(double), 9 * nn, true),
+                s_stat = io.add("status", sizeof(int32_t), nn, false);
+      if (const int rc = reserve_call(io)) return rc;
+      RatesQuery *hq = io_host<RatesQuery>(io, s_q);
+      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_val) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), (const uint8_t *)nullptr, (RatesRec *)nullptr,
+                         io_dev<double>(io, s_val), io_dev<int32_t>(io, s_stat));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_val), io_dev<char>(io, s_val), io.bytes() - io.off(s_val), hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      {   // device times of this call, for ctvio_last_timing: k_cov_rates_jac and the whole call
+        Timing t;
+        t.clear();
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
+        t.ms[2] = ms; t.n[2] = 1;
+        if (const int rc = publish_timing(t, 0)) return rc;
+      }
+      const double *hval = io_host<double>(io, s_val);
+      const int32_t *hstat = io_host<int32_t>(io, s_stat);
+      for (int r = 0; r < n; ++r) {
+        const size_t i = (size_t)slot[(size_t)r];
+        if (rates9) std::memcpy(rates9 + 9 * i, hval + 9 * (size_t)r, sizeof(double) * 9);
+        if (status) status[i] = hstat[r];
+      }
+      return CTVIO_OK;
+    }
+    std::vector<CovTile> tiles(nn);
+    for (int r = 0; r < n; ++r) tiles[(size_t)r] = CovTile{win_of(r), 7, r, 1, 0};
+    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); cov225 | chi2 | rates9 | status (out, one copy).  scr: mask, exclusions, records
+    CallLayout io = head_, scr;
+    const int s_q = io.add("queries", sizeof(RatesQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), nn, false), s_cov = io.add("cov225", sizeof(double), 225 * nn, true),
+              s_chi = io.add("chi2", sizeof(double), nn, true), s_val = io.add("rates9", sizeof(double), 9 * nn, true),
+              s_stat = io.add("status", sizeof(int32_t), nn, false);
+    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
+              s_rec = scr.add("records", sizeof(RatesRec), nn, false);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
+    RatesRec *drec = scr.at<RatesRec>(call_scr_.dev, s_rec);
+    RatesQuery *hq = io_host<RatesQuery>(io, s_q);
+    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
+    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * nn);
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_cov) - io.off(s_q), hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), (const uint8_t *)excl, drec,
+                       io_dev<double>(io, s_val), io_dev<int32_t>(io, s_stat));
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    hipLaunchKernelGGL((k_cov_solve<false, false, true>), dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
+                       io_dev<int32_t>(io, s_slot), (double *)nullptr, chi2 ? io_dev<double>(io, s_chi) : (double *)nullptr, (const RatesRec *)drec,
+                       io_dev<double>(io, s_cov), (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // ---- results: the blocks and gates as the kernel left them (the caller's order), the values and statuses in sorted order
+    Lm *lm = io_host<Lm>(io, HEAD_LM);
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov225 | chi2 | rates9 | status)
+    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_rates_jac and the whole call
+      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
+      const bool ran[3] = {true, true, true};
+      if (const int rc = cov_timing(pair, ran)) return rc;
+    }
+    // (time outside the spline: NaN; an untouched knot or bias state: +inf on the diagonal, 0 elsewhere, chi2 0; a window whose factorisation
+    // met a bad pivot: NaN)
+    const double *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi), *hval = io_host<double>(io, s_val);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)slot[(size_t)r];
+      int st = hstat[r];
+      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
+      if (cov225) {
+        double *o = cov225 + 225 * i;
+        if (st == POSE_OK) std::memcpy(o, hcov + 225 * i, sizeof(double) * 225);
+        else for (int e = 0; e < 225; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 16 == 0 ? inf : 0.0) : nan;
+      }
+      if (chi2) chi2[i] = st == POSE_OK ? hchi[i] : (st == POSE_UNTOUCHED ? 0.0 : nan);
+      if (rates9) std::memcpy(rates9 + 9 * i, hval + 9 * (size_t)r, sizeof(double) * 9);
+      if (status) status[i] = st;
+    }
+    return CTVIO_OK;
+  }
   // ctvio_imu_predict_batch / ctvio_imu_predict (only >= 0: every query belongs to that window, win is not read): the navigation state of
   // query i at imu_t[first sample of i] (bias state frame[i]; frame null: the newest) carried through the query's n_imu[i] samples by
   // k_imu_propagate, with its 15 x 15 covariance.  The middle is nav_state()'s: queries grouped by window (stable), k_cov_nav_jac, and with
@@ -2267,6 +2397,16 @@ int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.nav_state(id, n, nullptr, t_ns, frame, state16, cov225, status);
+}
+int32_t ctvio_body_rates_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, const int32_t *frame, const double *meas6,
+                               const double *noise6, double *rates9, double *cov225, double *chi2, int32_t *status) {
+  CHK_S; return s->impl.body_rates(-1, n, win, t_ns, frame, meas6, noise6, rates9, cov225, chi2, status);
+}
+int32_t ctvio_body_rates(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const int32_t *frame, const double *meas6,
+                         const double *noise6, double *rates9, double *cov225, double *chi2, int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.body_rates(id, n, nullptr, t_ns, frame, meas6, noise6, rates9, cov225, chi2, status);
 }
 void ctvio_default_imu_noise(ctvio_imu_noise *o) {
   if (!o) return;

@@ -460,6 +460,43 @@ template <class SC> CTV_DI void nav_jac_T(const Q4 q[4], const SC &sc, double u,
   basis<false, 1>(u, idt, cv);
 }
 
+// Jacobian of the body rates at u (ctvio_body_rates) -- body angular velocity omega, specific force f = R(t)^T (p''(t) + g), body-frame
+// velocity v_B = R(t)^T v_W(t) -- against the tangents of its four knots, TRANSPOSED: jt[(6 k + c) * 9 + a] = d(output a) / d(unknown c of
+// knot k), unknowns (rot 0..2, pos 3..5) under R_k <- R_k exp(delta_k), p_k <- p_k + dp_k, outputs (domega 0..2, df 3..5, dv_B 6..8),
+// all additive.  The omega and f rows are the IMU factor's (imu_eval_core, the general body, unit weights, zero measurement and bias,
+// global frame: Jw, Ja, lamA (x) Rinv_g); under R(t) <- R(t) exp(dtheta), v_B <- v_B + [v_B]x dtheta, so the v_B rows are [v_B]x J^Rp_k
+// (eval_Rp: the rotation rows of pose_jac_T) on the rotations and c'_k(u) / dt R(t)^T on the positions.  All 216 entries are written, each
+// once.  At u = 0 the last knot's blocks are exact zeros (up to the sign of a zero): lamR_3 = u^3 / 6, lamW_3 and c'_3 = u^2 / 2, lamA_3 = u.
+template <class SC> CTV_DI void rates_jac_T(const Knots4 &k, const SC &sc, double u, double idt, V3 gravity, double *jt) {
+  const double zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, one6[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
+  double r[6], cv[4];
+  ImuJac J;
+  imu_eval_core<SC>(k, sc, u, idt, gravity, zero6, zero6, zero6 + 3, one6, m3_id(), r, true, J);
+  M3 Jth[4];
+  eval_Rp<SC>(k.q, sc, u, Jth, true);
+  basis<false, 1>(u, idt, cv);
+  V3 v = mk(0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v = v + cv[i] * k.p[i];
+  const M3 VBx = hat(mul(J.Rinv_g, v));
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const M3 B = mul(VBx, Jth[kk]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        double *rot = jt + (6 * kk + c) * 9, *pos = jt + (6 * kk + 3 + c) * 9;
+        rot[a] = J.Jw[kk].m[3 * a + c];
+        rot[3 + a] = J.Ja[kk].m[3 * a + c];
+        rot[6 + a] = B.m[3 * a + c];
+        pos[a] = 0.0;
+        pos[3 + a] = J.lamA[kk] * J.Rinv_g.m[3 * a + c];
+        pos[6 + a] = cv[kk] * J.Rinv_g.m[3 * a + c];
+      }
+  }
+}
+
 // The pose increment T_ab = T_a^-1 T_b of two poses (q_a, p_a), (q_b, p_b) (ctvio_relative_pose): R_ab = R_a^T R_b, p_ab = R_a^T (p_b - p_a),
 // and its Jacobian against the knots of both poses.  jt_a, jt_b: the 24 x 6 blocks pose_jac_T wrote for the two poses; they are mapped IN
 // PLACE into the two blocks of J_rel^T, J_rel = A_a J_a + A_b J_b.  Tangent of the result (dtheta 0..2, dp 3..5): R_ab <- R_ab exp(dtheta),

@@ -23,6 +23,7 @@
 //   kernels_cov.hpp       k_cov_prepare, k_cov_solve, k_cov_gram (marginal covariances from the factor of the reduced system)
 //                         k_cov_pose_jac (per-query pose Jacobian: pose covariances at query times through k_cov_solve)
 //                         k_cov_nav_jac (per-query navigation state and its Jacobian: 15 x 15 covariances through k_cov_solve)
+//                         k_cov_rates_jac (per-query body rates and their Jacobian: 15 x 15 covariances and IMU gates through k_cov_solve)
 //   kernels_prop.hpp      k_imu_propagate (IMU dead reckoning from a navigation state: mean and 15 x 15 covariance, four queries per wave)
 //   kernels_tri.hpp       k_triangulate (landmark depths by one-sided Jacobi, one wave per landmark), k_shift_anchor (depths re-anchored)
 #pragma once

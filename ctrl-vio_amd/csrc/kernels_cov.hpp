@@ -6,7 +6,8 @@
 // k_cov_nav_jac (one record per query), then k_cov_solve on tiles of kind 4; pose increments between two times with their 6 x 6 covariances
 // (ctvio_relative_pose_batch): k_cov_rel_jac (one record per query), then k_cov_solve on tiles of kind 5; predicted image points of landmarks
 // at query times with their 2 x 2 covariances and gates (ctvio_project_landmarks_batch): k_cov_proj_jac (one record per query), then
-// k_cov_solve on tiles of kind 6.
+// k_cov_solve on tiles of kind 6; body rates (angular velocity, specific force, body-frame velocity) with their 15 x 15 covariances and IMU
+// gates (ctvio_body_rates_batch): k_cov_rates_jac (one record per query), then k_cov_solve on tiles of kind 7.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -25,6 +26,8 @@
 //   Cov(proj)       = (L^-1 G)^T (L^-1 G) + j j^T / Hll_l           for the predicted image point of landmark l at a query time: Cov(X_l)'s identity
 //                     with two columns, G = Jp^T - w_l j^T / Hll_l, Jp over the knots of the anchor time and of the query time and the line
 //                     delay (factors.hpp: proj_jac_T, proj_cols), j = d(proj) / drho_l,
+//   Sigma_rates(t, f) = (L^-1 J^T)^T (L^-1 J^T)                    for the 15 x P Jacobian J of (omega, specific force, body-frame velocity, bias state f)
+//                     at time t (factors.hpp: rates_jac_T; the bias rows are one-hot),
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -38,10 +41,11 @@ struct CovTile {
                     // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused); 4: the fifteen columns of J^T of one navigation-state
                     // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 5: the six columns of
                     // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5); 6: the two columns of G of up to eight
-                    // projection queries of the window (columns 2 q, 2 q + 1)
+                    // projection queries of the window (columns 2 q, 2 q + 1); 7: the fifteen columns of J^T of one body-rates query (omega
+                    // 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused)
   int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
-                    // kind 2, 5 and 6: the tile's first query record; kind 4: its query record
-  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4: 1; kind 6: queries (<= 8)
+                    // kind 2, 5 and 6: the tile's first query record; kind 4 and 7: its query record
+  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4 and 7: 1; kind 6: queries (<= 8)
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -186,6 +190,80 @@ __global__ __launch_bounds__(64) void k_cov_nav_jac(Dev d, int n, const NavQuery
   status_out[i] = status;
   if (status != POSE_OK) return;
   nav_jac_T(k.q, sc, u, m.inv_dt, r.jt, r.cv);
+}
+
+// One body-rates query (ctvio_body_rates_batch), grouped by window on the host, and what k_cov_rates_jac makes of it.  The statuses are the
+// pose entry's (POSE_*).
+struct RatesQuery {
+  int32_t win, frame;   // frame: the bias state, in [0, F) (the host has resolved "the newest")
+  long long t_rel;      // relative to the window's t0
+  double meas[6];       // the candidate IMU sample of the gate, gyro then accelerometer (zeros without one)
+  double sig[6];        // its six standard deviations (the host has resolved noise6 == NULL to 1 / imu_w; ones without a gate)
+};
+struct RatesRec {
+  int32_t status, s, nk, frame;   // first knot; knots the rates depend on: 3 at u = 0, else 4
+  double z[6];                    // the predicted reading (omega + bg_f, f + ba_f), from the bits that go to rates9
+  double meas[6], sig[6];         // the query's
+  double jt[216];                 // J^T over the knots s .. s + 3, 24 x 9 (rates_jac_T; written for POSE_OK only)
+};
+
+// One lane per query: segment and u by the integer-ns rule of k_spline_eval, the values -- omega (eval_omega), f = R(t)^T (p''(t) + g),
+// v_B = R(t)^T v_W(t) -- into rates9 (NaN outside the spline), and with excl (after k_cov_prepare; null: values only, recs is not touched)
+// the status and the record.  A knot the rates depend on, or the bias state, with an unknown no factor touches (COV_UNTOUCHED) gives
+// POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.  The values are formed before excl is looked at,
+// by code the Jacobians do not share: both calls give them the same bits.
+__global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQuery *qs, const uint8_t *excl, RatesRec *recs, double *rates9, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const RatesQuery &q = qs[i];
+  const int frame = q.frame;
+  const long long t_rel = q.t_rel;
+  const WinMeta &m = d.wins[q.win];
+  const long long sl = t_rel / m.dt_ns;
+  const bool outside = t_rel < 0 || sl + 3 >= m.K;
+  const int s = outside ? 0 : (int)sl;
+  const double u = outside ? 0.0 : (double)(t_rel % m.dt_ns) / (double)m.dt_ns;
+  const int nk = u > 0.0 ? 4 : 3;
+  int status = outside ? POSE_OUTSIDE : POSE_OK;
+  Knots4 k;
+  load_knots(d.quat, d.pos, m.knot0 + s, d.pos + 3 * (size_t)(m.knot0 + s), k);   // relative to knot s: the rates are translation invariant
+  SegConst sc;
+  seg_const(k, sc, excl != nullptr);
+  const V3 grav = mk(m.gravity[0], m.gravity[1], m.gravity[2]);
+  double val[9];
+  {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double dc[4], ddc[4];
+    basis<false, 1>(u, m.inv_dt, dc);
+    basis<false, 2>(u, m.inv_dt * m.inv_dt, ddc);
+    V3 v = mk(0, 0, 0), a = mk(0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v = v + dc[j] * k.p[j]; a = a + ddc[j] * k.p[j]; }
+    const Q4 qinv = qconj(eval_R(k.q, sc, u));
+    const V3 om = eval_omega<SegConst>(sc, u, m.inv_dt), f = qrot(qinv, a + grav), vb = qrot(qinv, v);
+    val[0] = om.x; val[1] = om.y; val[2] = om.z; val[3] = f.x; val[4] = f.y; val[5] = f.z; val[6] = vb.x; val[7] = vb.y; val[8] = vb.z;
+    double *o = rates9 + 9 * (size_t)i;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) o[j] = outside ? nan : val[j];
+  }
+  if (!excl) {
+    status_out[i] = status;
+    return;
+  }
+  if (!outside) {
+    for (int j = 6 * s; j < 6 * (s + nk); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+    for (int j = 6 * m.K + 6 * frame; j < 6 * m.K + 6 * frame + 6; ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+  }
+  RatesRec &r = recs[i];
+  r.status = status; r.s = s; r.nk = nk; r.frame = frame;
+  status_out[i] = status;
+  if (status != POSE_OK) return;
+  const double *bp = d.bias + 6 * (size_t)(m.bias0 + frame);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) { r.z[j] = val[j] + bp[j]; r.meas[j] = q.meas[j]; r.sig[j] = q.sig[j]; }
+  rates_jac_T(k, sc, u, m.inv_dt, grav, r.jt);
 }
 
 // One relative-pose query (ctvio_relative_pose_batch), grouped by window on the host, and what k_cov_rel_jac makes of it.  The statuses are
@@ -503,16 +581,45 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
 // + query term" in that order -- and the line-delay row.  Epilogue: the three unique entries of every 2 x 2 Gram block, four partial sums over
 // the rows k = p mod 4 added in sequence, + j j^T / Hll, mirrored; then chi2 = e^T (Cov + I / img_w^2)^-1 e, e = obs - proj, by the 2 x 2
 // Cholesky factor, from the block just written and the record's prediction.  Queries whose status is not PRJ_OK keep zero columns and write nothing.
+// Kind 7 (the instantiation RATES = true, which holds no other kind and leaves the code of the other three what it was): sel = the caller's
+// slot of every query record, prec = the records (RatesRec), pose_cov = the caller-ordered 15 x 15 blocks and var_rho = the gates chi2 by
+// slot (null: not asked for).  One query per tile, kind 4's prologue with nine Jacobian columns and kind 4's Gram epilogue (cov_gram15);
+// then S = A C A^T + diag(sigma^2) from the block just written -- 21 lanes, every entry ((C[a][b] + C[a][9 + b]) + C[9 + a][b]) +
+// C[9 + a][9 + b] -- and one lane's 6 x 6 Cholesky factor and forward substitution in LDS: chi2 = |L^-1 e|^2, e = meas - z.
 // amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
 // SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
 // inlined as well.
 constexpr int COV_NT = 256;
-template <bool REL, bool PROJ = false> struct CovQueryRec { typedef PoseRec type; };
-template <> struct CovQueryRec<true, false> { typedef RelRec type; };
-template <> struct CovQueryRec<false, true> { typedef ProjRec type; };
-template <bool REL, bool PROJ = false>
+template <bool REL, bool PROJ = false, bool RATES = false> struct CovQueryRec { typedef PoseRec type; };
+template <> struct CovQueryRec<true, false, false> { typedef RelRec type; };
+template <> struct CovQueryRec<false, true, false> { typedef ProjRec type; };
+template <> struct CovQueryRec<false, false, true> { typedef RatesRec type; };
+// The 120 unique entries of the 15 x 15 Gram block of a tile's columns 0..14 over the rows k0 .. P - 1 (kinds 4 and 7): every entry four
+// partial sums over the rows k = p mod 4, added in sequence, computed once and mirrored into the caller's block cov + 225 slot[0].  keep: lane
+// tid < 120 leaves its entry in part[tid] as well (entry (i >= j) at i (i + 1) / 2 + j; that lane alone has read part[tid]).
+__device__ __forceinline__ void cov_gram15(const double *Ys, double *part, int k0, int P, int tid, double *cov, const int32_t *slot, bool keep) {
+  for (int x = tid; x < 480; x += COV_NT) {
+    const int p = x / 120;
+    int ci, cj;
+    tile_decode(x % 120, ci, cj);
+    double s = 0.0;
+    for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+    part[x] = s;
+  }
+  __syncthreads();
+  if (tid < 120) {
+    int ci, cj;
+    tile_decode(tid, ci, cj);
+    const double v = ((part[tid] + part[120 + tid]) + part[240 + tid]) + part[360 + tid];
+    double *o = cov + (long long)225 * slot[0];
+    o[15 * ci + cj] = v;
+    o[15 * cj + ci] = v;
+    if (keep) part[tid] = v;
+  }
+}
+template <bool REL, bool PROJ = false, bool RATES = false>
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const typename CovQueryRec<REL, PROJ>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
+                                                      const typename CovQueryRec<REL, PROJ, RATES>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
                                                       const NavRec *nrec, double *nav_cov) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
@@ -528,7 +635,20 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
   for (int e = tid; e < 16 * PP; e += COV_NT) Ys[e] = 0.0;
   if (tid == 0) s_first = PP;
   __syncthreads();
-  if constexpr (PROJ) {
+  if constexpr (RATES) {   // the nine columns of J^T over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the rows of bias state f, each
+                           // where the unknown is in the system
+    const RatesRec &rr = prec[t.first];
+    if (rr.status == POSE_OK) {
+      if (tid < 216) {
+        const int r = tid / 9, a = tid % 9;
+        if (r < 6 * rr.nk && d.active[m.u0 + 6 * rr.s + r]) Ys[(6 * rr.s + r) * 16 + a] = rr.jt[tid];
+      } else if (tid < 222) {
+        const int a = tid - 216, j = 6 * m.K + 6 * rr.frame + a;
+        if (d.active[m.u0 + j]) Ys[j * 16 + 9 + a] = 1.0;
+      }
+      if (tid == 0) s_first = 6 * rr.s;
+    }
+  } else if constexpr (PROJ) {
     const int q = tid >> 4, sub = tid & 15;
     if (q < t.count) {   // -(w_l / Hll) j^T: the row's planned span, then the line-delay column
       const ProjRec &pr = prec[t.first + q];
@@ -720,6 +840,40 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     __syncthreads();
   }
+  if constexpr (RATES) {   // rates tiles: kind 4's 15 x 15 Gram block, then the gate of the IMU sample, one lane per tile
+    const RatesRec &rr = prec[t.first];
+    if (rr.status != POSE_OK) return;
+    cov_gram15(Ys, part, min(32 * b0, P), P, tid, pose_cov, sel + t.first, true);
+    if (!var_rho) return;
+    __syncthreads();
+    double *Sm = part + 128, *zv = Sm + 36;   // S = A C A^T + diag(sigma^2), A = [[I, 0, 0, I, 0], [0, I, 0, 0, I]]: rows a and 9 + a of C; then
+                                              // its Cholesky factor in place (lower triangle); z = L^-1 e
+    if (tid < 21) {
+      int a, b;
+      tile_decode(tid, a, b);
+      const double c = ((part[a * (a + 1) / 2 + b] + part[(9 + b) * (10 + b) / 2 + a]) + part[(9 + a) * (10 + a) / 2 + b]) + part[(9 + a) * (10 + a) / 2 + 9 + b];
+      Sm[6 * a + b] = a == b ? c + rr.sig[a] * rr.sig[a] : c;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double chi = 0.0;
+      for (int j = 0; j < 6; ++j) {   // column j of L, then z_j of L z = e
+        double dj = Sm[7 * j], ej = rr.meas[j] - rr.z[j];
+        for (int k = 0; k < j; ++k) { dj -= Sm[6 * j + k] * Sm[6 * j + k]; ej -= Sm[6 * j + k] * zv[k]; }
+        const double ljj = sqrt(dj);
+        for (int i = j + 1; i < 6; ++i) {
+          double x = Sm[6 * i + j];
+          for (int k = 0; k < j; ++k) x -= Sm[6 * i + k] * Sm[6 * j + k];
+          Sm[6 * i + j] = x / ljj;
+        }
+        const double zj = ej / ljj;
+        zv[j] = zj;
+        chi += zj * zj;
+      }
+      var_rho[sel[t.first]] = chi;
+    }
+    return;
+  }
   if constexpr (PROJ) {   // projection tiles: entries (0,0), (0,1), (1,1) of the eight 2 x 2 Gram blocks, then the gate
     const int k0 = min(32 * b0, P);
     constexpr int NE = 3 * PRJ_PER_TILE;
@@ -767,26 +921,8 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     if (tid < 36 * t.count) pose_cov[(long long)36 * sel[t.first + tid / 36] + tid % 36] = (part[tid] + part[72 + tid]) + part[144 + tid];
     return;
   }
-  if (t.kind == 4) {   // state tiles: the 120 unique entries of the 15 x 15 Gram block; every entry four partial sums over the rows k = p mod 4, added in
-                       // sequence, computed once and mirrored
-    const int k0 = min(32 * b0, P);
-    for (int x = tid; x < 480; x += COV_NT) {
-      const int p = x / 120;
-      int ci, cj;
-      tile_decode(x % 120, ci, cj);
-      double s = 0.0;
-      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
-      part[x] = s;
-    }
-    __syncthreads();
-    if (tid < 120) {
-      int ci, cj;
-      tile_decode(tid, ci, cj);
-      const double v = ((part[tid] + part[120 + tid]) + part[240 + tid]) + part[360 + tid];
-      double *o = nav_cov + (long long)225 * sel[t.first];
-      o[15 * ci + cj] = v;
-      o[15 * cj + ci] = v;
-    }
+  if (t.kind == 4) {   // state tiles: the 15 x 15 Gram block
+    cov_gram15(Ys, part, min(32 * b0, P), P, tid, nav_cov, sel + t.first, false);
     return;
   }
   if (t.kind == 3) {   // point tiles: the five 3 x 3 Gram blocks; every entry four partial sums over the rows k = p mod 4, added in sequence

@@ -339,6 +339,38 @@ class Solver:
         """ctvio_nav_state: the same for the times t_ns of window wid alone (same bits as the batch entry)."""
         return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state(self._h, int(wid), n, t, f, s, c, st), t_ns, frame, cov)
 
+    def _body_rates(self, call, t_ns, frame, meas, noise, cov, n_win=None):
+        t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        n = int(t.shape[0])
+        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
+        z = None if meas is None else np.ascontiguousarray(meas, np.float64).reshape(-1, 6)
+        sg = None if noise is None else np.ascontiguousarray(noise, np.float64).reshape(6)
+        assert (fr is None or fr.shape[0] == n) and (z is None or z.shape[0] == n) and (n_win is None or n_win == n)
+        if z is not None and not cov:
+            raise ValueError("meas needs cov=True: the gate is formed from the covariance")
+        m = max(n, 1)
+        rates = np.zeros((m, 9)); c = np.zeros((m, 15, 15)) if cov else None; chi = np.zeros(m) if z is not None else None
+        st = np.zeros(m, np.int32)
+        capi.check(call(n, capi._p(t), capi._p(fr), capi._p(z), capi._p(sg), capi._p(rates), capi._p(c) if cov else None,
+                        capi._p(chi) if chi is not None else None, capi._p(st)))
+        return rates[:n].copy(), (c[:n].copy() if cov else None), (chi[:n].copy() if chi is not None else None), st[:n].copy()
+
+    def body_rates_batch(self, win, t_ns, frame=None, cov: bool = True, meas=None, noise=None):
+        """ctvio_body_rates_batch: the body angular velocity, the specific force f = R(t)^T (p''(t) + g) and the body-frame velocity
+        v_B = R(t)^T v_W(t) at absolute time t_ns[i] of window win[i], at the current state, and with cov their 15 x 15 covariance with the
+        biases of state frame[i] (None: the newest) in the additive tangent (domega, df, dv_B, dbg, dba).  meas (n, 6): candidate IMU samples
+        (gyro, then accelerometer) for the gate chi2 = e^T (A C A^T + diag(sigma^2))^-1 e, e = meas - (omega + bg, f + ba); noise: the six
+        standard deviations (None: 1 / imu_w of the window).  Returns (rates (n, 9), cov (n, 15, 15) or None, chi2 (n,) or None, status
+        (n,)): 0 ok, 1 singular window (cov, chi2 NaN), 2 an untouched knot or bias state (+inf diagonal, chi2 0), 3 time outside the spline
+        (NaN).  cov=False: one kernel, nothing is linearised."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
+        return self._body_rates(lambda n, *a: self._lib.ctvio_body_rates_batch(self._h, C.c_int64(n), capi._p(wi), *a), t_ns, frame, meas, noise,
+                                cov, int(wi.shape[0]))
+
+    def body_rates(self, wid: int, t_ns, frame=None, cov: bool = True, meas=None, noise=None):
+        """ctvio_body_rates: the same for the times t_ns of window wid alone (same bits as the batch entry)."""
+        return self._body_rates(lambda n, *a: self._lib.ctvio_body_rates(self._h, int(wid), n, *a), t_ns, frame, meas, noise, cov)
+
     def _relative_pose(self, call, t_a, t_b, q_SI, p_SI, cov, n_win=None):
         ta = np.ascontiguousarray(t_a, np.int64).reshape(-1); tb = np.ascontiguousarray(t_b, np.int64).reshape(-1)
         n = int(ta.shape[0])

@@ -296,6 +296,50 @@ int32_t ctvio_nav_state_batch(ctvio_solver *s, int64_t n, const int32_t *win, co
 int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225,
                         int32_t *status);
 
+/* The BODY RATES at a time -- angular velocity, specific force, body-frame velocity -- with their joint covariance, and a Mahalanobis gate
+ * for an IMU sample: the twist half of an odometry message (child-frame linear and angular velocity with a 6 x 6 covariance), a rate
+ * uncertainty for a controller, and the inertial counterpart of ctvio_project_landmarks' gate.  The values are Se3Spline::rotVelBody /
+ * transAccelWorld / transVelWorld (se3_spline.h:361-389) and the prediction inside IMUFactor::Evaluate (trajectory_value_factor.h:165-171);
+ * the reference has no covariance for any of them.
+ * Query i = (window win[i], absolute time t_ns[i], bias state frame[i] in [0, F)) at the CURRENT state; frame == NULL: F - 1 for every query.
+ * Any number of queries, in any order, from any windows.  Segment and u by the integer-ns rule of ctvio_spline_eval; the time must lie in
+ * [t0, t0 + (K - 3) dt).  This is the BODY (IMU) frame: there is no sensor extrinsic in this entry, as in ctvio_nav_state (a caller maps
+ * (omega, v_B) and their joint block to another point of the body with its fixed lever arm).
+ *   rates9 (n x 9 doubles, or NULL): omega in 0..2, the body angular velocity;  f = R(t)^T (p''(t) + g) in 3..5, the specific force, g the
+ *   window's `gravity`, signed as in the IMU factor;  v_B = R(t)^T v_W(t) in 6..8, the body-frame velocity.
+ *   cov225 (n x 225 doubles, row-major 15 x 15 per query, symmetric to the bit, or NULL): J Sigma J^T in the additive tangent (domega 0..2,
+ *   df 3..5, dv_B 6..8, dbg 9..11, dba 12..14), with H, the exclusions and Sigma exactly those of ctvio_covariance_batch (no damping).  Rows of
+ *   J against the knots s .. s + 3 (knot s + 3 only where u > 0) under the library's retraction: omega and f are the IMU factor's rows
+ *   (rotations: Jw[k], Ja[k]; positions: zero, c''_k(u) / dt^2 R(t)^T);  v_B: [v_B]x J_theta,k on the rotations (J_theta,k the rotation rows
+ *   of ctvio_pose_covariance), c'_k(u) / dt R(t)^T on the positions;  bias: one-hot on unknowns 6 K + 6 f .. 6 K + 6 f + 5.  The line delay
+ *   and the inverse depths do not enter.  Constant unknowns contribute nothing: a locked bias gives exact zero rows and columns, a query that
+ *   depends on constant unknowns alone the exact zero matrix and status 0.
+ *   chi2 (n doubles, or NULL; requires meas6, n x 6: the gyro sample, then the accelerometer sample, as the IMU factor takes them): with the
+ *   predicted reading z = (omega + bg_f, f + ba_f) and e = meas - z, chi2 = e^T S^-1 e, S = A C A^T + diag(sigma_k^2),
+ *   A = [[I, 0, 0, I, 0], [0, I, 0, 0, I]], C the 15 x 15 block above: a 6 x 6 Cholesky on the device, from the very cov225 and rates9 bits
+ *   that are returned.  noise6: the six standard deviations for the whole call; NULL: sigma_k = 1 / imu_w[k] of the query's window.  The gate
+ *   is meant for NEW samples: for a sample that is already a factor of the window, estimate and measurement are correlated and S overstates
+ *   the variance of e.
+ *   status (n entries, or NULL) per query, in this precedence: 3 time outside the spline: everything NaN;  2 a knot the query depends on, or
+ *   the bias state, has a non-constant unknown no factor touches: values valid, +inf on the diagonal and 0 elsewhere, chi2 = 0;  1 the
+ *   window's factorisation met a non-positive or non-finite pivot: values valid, covariance and chi2 NaN;  0 ok.
+ *   With cov225 == NULL and chi2 == NULL nothing is linearised or factored: one kernel evaluates the values, statuses 1 and 2 cannot occur,
+ *   and the values have the bits of the covariance call's.
+ * The call returns CTVIO_OK for every status.  n == 0 returns CTVIO_OK and launches nothing.  CTVIO_ERR_STATE before the upload;
+ * CTVIO_ERR_INVALID for a window id or frame out of range, n < 0, a NULL t_ns (batch entry: win) with n > 0, every output NULL with n > 0,
+ * chi2 without meas6, a non-finite meas6, a non-positive or non-finite noise6 entry, noise6 == NULL with chi2 asked for and a queried window
+ * whose imu_w has a non-positive entry; the handle stays usable.  The state, the launch plan and the captured graph of the solve are left as
+ * they were; no atomics: where the linearisation is order-fixed (opt.deterministic) the bits of a query's outputs depend on its own arguments
+ * alone -- not on the entry (batch or single-window: win is window id for every query), the order of the queries, which queries share a
+ * call, or which optional outputs were asked for.
+ * ctvio_last_timing: ms8[0..2] = k_cov_prepare, k_cov_solve, k_cov_rates_jac, ms8[7] the whole call; values only: ms8[2] and ms8[7]. */
+int32_t ctvio_body_rates_batch(ctvio_solver *s, int64_t n, const int32_t *win, const int64_t *t_ns, const int32_t *frame,
+                               const double *meas6, const double *noise6,
+                               double *rates9, double *cov225, double *chi2, int32_t *status);
+int32_t ctvio_body_rates(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t_ns, const int32_t *frame,
+                         const double *meas6, const double *noise6,
+                         double *rates9, double *cov225, double *chi2, int32_t *status);
+
 /* The POSE INCREMENT between two times, T_ab = T(t_a)^-1 T(t_b), with its 6 x 6 covariance: what a pose-graph or loop-closure back end, a
  * keyframe-to-keyframe "between" factor, a lidar or wheel fuser or a drift gate consumes.  The entries above describe one time in the window's
  * own gauge, which the prior on the oldest knots fixes, so their uncertainty grows along the window; the increment carries the
@@ -557,6 +601,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * After a landmark-projection call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution, the 2 x 2 blocks and the gates),
  * k_cov_proj_jac, ms8[7] = the whole call on the device, the rest zero; values only (cov4 == NULL and chi2 == NULL): ms8[2] = device time of
  * k_cov_proj_jac, ms8[7] = the whole call on the device (its copies included), the rest zero.
+ * After a body-rates call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution, the 15 x 15 blocks and the gates),
+ * k_cov_rates_jac, ms8[7] = the whole call on the device, the rest zero; values only (cov225 == NULL and chi2 == NULL): ms8[2] = device time
+ * of k_cov_rates_jac, ms8[7] = the whole call on the device (its copies included), the rest zero.
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

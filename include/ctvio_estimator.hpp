@@ -564,6 +564,37 @@ class TrajectoryEstimator {
     return ok;
   }
 
+  // The body rates at the times t_ns (absolute, inside the solved knots) with their 15 x 15 covariance, at the CURRENT parameter values, from
+  // the factors of Solve (ctvio_body_rates): the twist of an odometry message and the prediction an IMU sample is gated against.  rates =
+  // t_ns.size() x 9: body angular velocity, specific force R(t)^T (p''(t) + g), body-frame velocity R(t)^T v_W(t); cov225 = t_ns.size() x 225,
+  // row-major per time, in the additive tangent (domega, df, dv_B, dbg, dba) with the bias state whose gyro-bias pointer, as given to the Add*
+  // calls, is bias_gyr (nullptr: the newest bias state of the window).  With meas6 (t_ns.size() x 6: gyro, then accelerometer) and chi2, the
+  // Mahalanobis gate of every sample against its prediction (noise6: six standard deviations; nullptr: 1 / the IMU weights of the window).
+  // Returns false if any status is not 0 (ctvio.h: a singular window or a time outside the spline give NaN, a knot or bias state no factor
+  // touches +inf).
+  bool GetBodyRatesCovariance(const std::vector<int64_t> &t_ns, const double *bias_gyr, std::vector<double> &rates, std::vector<double> &cov225,
+                              const double *meas6 = nullptr, const double *noise6 = nullptr, std::vector<double> *chi2 = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t n = t_ns.size();
+    std::vector<int32_t> frame;
+    if (bias_gyr) {
+      auto it = bias_of_.find(bias_gyr);
+      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("GetBodyRatesCovariance: not a bias state of this window");
+      frame.assign(n, pk.bias_map[(size_t)it->second]);
+    }
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    std::vector<int32_t> status(n, 0);
+    rates.assign(9 * n, 0.0);
+    cov225.assign(225 * n, 0.0);
+    if (chi2) chi2->assign(n, 0.0);
+    check(ctvio_body_rates(s, 0, (int32_t)n, t_ns.data(), bias_gyr ? frame.data() : nullptr, meas6, noise6, rates.data(), cov225.data(),
+                           chi2 ? chi2->data() : nullptr, status.data()));
+    for (int32_t st : status) if (st != 0) return false;
+    return true;
+  }
+
   // The pose increments T(t_a)^-1 T(t_b) of the pairs (t_a, t_b) (absolute times, inside the solved knots; t_b may lie before t_a) with their
   // 6 x 6 covariances, at the CURRENT parameter values, from the factors of Solve (ctvio_relative_pose): what a pose-graph back end takes as a
   // keyframe-to-keyframe "between" factor.  rel = pairs.size() x 7, (p_ab, q_ab as x, y, z, w) with R_ab = R_a^T R_b, p_ab = R_a^T (p_b - p_a);
