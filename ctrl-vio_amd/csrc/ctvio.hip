@@ -1265,6 +1265,90 @@ class SolverImpl {
     return CTVIO_OK;
   }
   size_t cov_solve_lds() const { return ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double); }   // Ys | part (k_cov_solve)
+  // k_cov_solve's arguments by name; what a call does not use stays null.  The template arguments are the kernel's (they choose the type
+  // of the query records).  sel: the selections of covariance(), the output slots of the queries elsewhere.
+  template <bool REL = false, bool PROJ = false, bool RATES = false> struct CovSolveArgs {
+    const CovTile *tiles = nullptr;
+    const int32_t *sel = nullptr;
+    double *Y = nullptr, *var_rho = nullptr;
+    double *chi2 = nullptr;                                            // the gates of the PROJ / RATES queries
+    const typename CovQueryRec<REL, PROJ, RATES>::type *qrec = nullptr;   // pose, relative-pose, projection or rates records
+    double *qcov = nullptr;
+    const PointRec *lrec = nullptr;
+    double *lm_cov = nullptr;
+    int lm_base = 0;
+    const NavRec *nrec = nullptr;
+    double *nav_cov = nullptr;
+  };
+  template <bool REL, bool PROJ, bool RATES> void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveArgs<REL, PROJ, RATES> &a) {
+    // (the PROJ / RATES instantiations have no landmark tiles: the kernel takes their gates in the position of var_rho)
+    hipLaunchKernelGGL((k_cov_solve<REL, PROJ, RATES>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a.tiles, a.sel, a.Y,
+                       PROJ || RATES ? a.chi2 : a.var_rho, a.qrec, a.qcov, a.lrec, a.lm_cov, a.lm_base, a.nrec, a.nav_cov);
+  }
+  // the device times of a call between pairs of its events (the stream is idle): ms[slot] of ctvio_last_timing, one launch each
+  struct Span { int slot; Ev begin, end; };
+  int span_timing(std::initializer_list<Span> spans) {
+    Timing t;
+    t.clear();
+    for (const Span &s : spans) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, ev_[s.begin], ev_[s.end]));
+      t.ms[s.slot] = ms; t.n[s.slot] = 1;
+    }
+    return publish_timing(t, 0);
+  }
+  // ---- the query entries (pose_covariance .. project_landmarks) share what follows.  Each validates its arguments, groups its queries by
+  // window (host_pack.hpp: QueryOrder), names its segments ONCE -- what a call without covariances does not need has no elements: io is
+  // queries | slot | tiles (in, one staged copy), then the outputs (one copy back); the device-only scratch is CovScratch --, fills the
+  // host inputs, runs run_query and scatters the mirror into the caller's arrays by status.
+  static_assert(POSE_OK == QUERY_OK && POSE_SINGULAR == QUERY_SINGULAR && POSE_UNTOUCHED == QUERY_NO_INFO, "merge_status / fill_not_ok");
+  static_assert(LMP_OK == QUERY_OK && LMP_SINGULAR == QUERY_SINGULAR && LMP_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
+  static_assert(PRJ_OK == QUERY_OK && PRJ_SINGULAR == QUERY_SINGULAR && PRJ_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
+  // the tiles of a covariance query: at most per_tile consecutive sorted queries of one window each
+  static std::vector<CovTile> query_tiles(const QueryOrder &ord, int per_tile, int kind) {
+    std::vector<CovTile> tiles;
+    ord.runs(per_tile, [&](int w, int first, int cnt) { tiles.push_back(CovTile{w, kind, first, cnt, 0}); });
+    return tiles;
+  }
+  // the tiles and (s_slot >= 0: kernels that write into the caller's slots) the sorted order into the mirror; no tiles: values only, neither
+  void stage_tiles(const CallLayout &io, int s_slot, int s_tiles, const QueryOrder &ord, const std::vector<CovTile> &tiles) {
+    if (tiles.empty()) return;
+    if (s_slot >= 0) std::memcpy(io_host<int32_t>(io, s_slot), ord.slot.data(), sizeof(int32_t) * ord.slot.size());
+    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+  }
+  // From "layout reserved, host inputs filled" to "results in the pinned mirror".  io: the segments [s_in, s_out) go to the device in one
+  // copy, [s_out, end) come back in one.  jac(excl, records) launches the entry's record kernel, solve(c, records) its k_cov_solve.
+  // scr null (values only): the record kernel alone, without exclusions and records -- nothing is linearised or factored; ms[2] is its
+  // time.  Otherwise the middle of covariance(): the record kernel runs after k_cov_prepare (it reads the exclusions), k_cov_solve on the
+  // factored copy c of Dev; ms[0] k_cov_prepare, ms[1] k_cov_solve, ms[2] the record kernel.  The window records come back with the
+  // results (Lm::chol_fail).  dev_, plan_ and the captured graph are not touched.
+  template <class Rec, class Jac, class Solve> int run_query(const CallLayout &io, int s_in, int s_out, const CovScratch *scr, Jac &&jac, Solve &&solve) {
+    const size_t in_bytes = io.off(s_out) - io.off(s_in), out_bytes = io.bytes() - io.off(s_out);
+    if (!scr) {
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      jac((const uint8_t *)nullptr, (Rec *)nullptr);
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_out), io_dev<char>(io, s_out), out_bytes, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      return span_timing({{2, EV_QUERY_BEGIN, EV_QUERY_END}});
+    }
+    uint8_t *mask = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_mask), *excl = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_excl);
+    Rec *rec = scr->lay.at<Rec>(call_scr_.dev, scr->s_rec);
+    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
+    Dev c;
+    if (const int rc = cov_factor(c, mask, excl)) return rc;
+    jac((const uint8_t *)excl, rec);
+    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+    solve(c, (const Rec *)rec);
+    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_out), io_dev<char>(io, s_out), out_bytes, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = finish_call(io)) return rc;
+    return span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_COV_SOLVE, EV_COV_GRAM}});
+  }
   // the three kernel times of a covariance call (the stream is idle): ms[i] between the events pair[i], where the kernel ran
   int cov_timing(const Ev (&pair)[3][2], const bool (&ran)[3]) {
     Timing t;
@@ -1336,9 +1420,11 @@ class SolverImpl {
       HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_sel), io_host<char>(io, s_sel), io.off(s_cov) - io.off(s_sel), hipMemcpyHostToDevice, stream_));
     Dev c;
     if (const int rc = cov_factor(c, mask, excl)) return rc;
-    if (!tiles.empty())
-      hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, dtiles, dsel, dy, dvar, (const PoseRec *)nullptr,
-                         (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
+    if (!tiles.empty()) {
+      CovSolveArgs<> a;
+      a.tiles = dtiles; a.sel = dsel; a.Y = dy; a.var_rho = dvar;
+      launch_cov_solve(c, tiles.size(), a);
+    }
     HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
     if (!cwins.empty())
       hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
@@ -1381,67 +1467,41 @@ class SolverImpl {
     SensorExt ext{};
     if (q_SI)
       if (const int rc = sensor_ext(q_SI, p_SI, ext)) return rc;
-    const int n = (int)n64, nw = dev_.nwin;
+    const int n = (int)n64;
     const size_t nn = (size_t)n;
-    if (only < 0)
-      for (int i = 0; i < n; ++i)
-        if (win[i] < 0 || win[i] >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+    const QueryOrder ord(only, n, win, dev_.nwin);
+    if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     if (n == 0) return CTVIO_OK;
-    // ---- queries by window, two per tile; slot[r]: the caller's index of sorted query r
-    std::vector<int32_t> slot(nn);
-    for (int i = 0; i < n; ++i) slot[i] = i;
-    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
-    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
-    std::vector<CovTile> tiles;
-    for (int r = 0; r < n;) {
-      const int cnt = (r + 1 < n && win_of(r + 1) == win_of(r)) ? 2 : 1;
-      tiles.push_back(CovTile{win_of(r), 2, r, cnt, 0});
-      r += cnt;
-    }
-    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); cov36 | status (out, one copy).  scr: mask, exclusions, records
-    CallLayout io = head_, scr;
+    const std::vector<CovTile> tiles = query_tiles(ord, 2, 2);
+    // ---- out: cov36 | status
+    CovScratch scr(true, (size_t)dev_.Utot, sizeof(PoseRec), nn);
+    CallLayout io = head_;
     const int s_q = io.add("queries", sizeof(PoseQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
               s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov36", sizeof(double), 36 * nn, true),
               s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_rec = scr.add("records", sizeof(PoseRec), nn, false);
-    if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-    PoseRec *drec = scr.at<PoseRec>(call_scr_.dev, s_rec);
+    if (const int rc = reserve_call(io, &scr.lay)) return rc;
     PoseQuery *hq = io_host<PoseQuery>(io, s_q);
-    for (int r = 0; r < n; ++r) hq[r] = PoseQuery{win_of(r), 0, (long long)(t_ns[slot[(size_t)r]] - t0_[win_of(r)])};
-    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
-    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_cov) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, drec, io_dev<int32_t>(io, s_stat));
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
-                       io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, drec, io_dev<double>(io, s_cov), (const PointRec *)nullptr,
-                       (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    // ---- results: the blocks as the kernel left them, the statuses in sorted order
-    int32_t *hstat = io_host<int32_t>(io, s_stat);
-    Lm *lm = io_host<Lm>(io, HEAD_LM);
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov36 | status)
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_pose_jac and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
-      const bool ran[3] = {true, true, true};
-      if (const int rc = cov_timing(pair, ran)) return rc;
-    }
-    // (time outside the spline: NaN; an untouched knot: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN)
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    for (int r = 0; r < n; ++r) hq[r] = PoseQuery{ord.win_of(r), 0, (long long)(t_ns[ord.slot[(size_t)r]] - t0_[ord.win_of(r)])};
+    stage_tiles(io, s_slot, s_tiles, ord, tiles);
+    const int rc = run_query<PoseRec>(
+        io, s_q, s_cov, &scr,
+        [&](const uint8_t *excl, PoseRec *rec) {
+          hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, rec, io_dev<int32_t>(io, s_stat));
+        },
+        [&](const Dev &c, const PoseRec *rec) {
+          CovSolveArgs<> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          launch_cov_solve(c, tiles.size(), a);
+        });
+    if (rc) return rc;
+    // ---- results: the blocks as the kernel left them (the caller's order), the statuses in sorted order (time outside the spline: NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      int st = hstat[r];
-      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
-      double *o = cov36 + 36 * i;
-      if (st == POSE_OK) std::memcpy(o, hcov + 36 * i, sizeof(double) * 36);
-      else for (int e = 0; e < 36; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 7 == 0 ? inf : 0.0) : nan;
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int st = merge_status(hstat[r], lm[ord.win_of(r)].chol_fail != 0);
+      cov_block(cov36 + 36 * i, hcov + 36 * i, 6, st);
       if (status) status[i] = st;
     }
     return CTVIO_OK;
@@ -1455,105 +1515,53 @@ class SolverImpl {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
     if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || (only < 0 && !win) || (!state16 && !cov225 && !status))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
-    const int n = (int)n64, nw = dev_.nwin;
+    const int n = (int)n64;
     const size_t nn = (size_t)n;
+    const QueryOrder ord(only, n, win, dev_.nwin);
+    if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     for (int i = 0; i < n; ++i) {
       const int w = only >= 0 ? only : win[i];
-      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
       if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": bias state out of range");
     }
     if (n == 0) return CTVIO_OK;
-    // ---- queries by window; slot[r]: the caller's index of sorted query r
-    std::vector<int32_t> slot(nn);
-    for (int i = 0; i < n; ++i) slot[i] = i;
-    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
-    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
-    auto query_of = [&](int r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      const int w = win_of(r);
-      return NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(t_ns[i] - t0_[w])};
-    };
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
-    if (!cov225) {   // in: queries (one staged copy); out: state16 | status (one copy)
-      CallLayout io = head_;
-      const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_state = io.add("state16", sizeof(double), 16 * nn, true),
-                s_stat = io.add("status", sizeof(int32_t), nn, false);
-      if (const int rc = reserve_call(io)) return rc;
-      NavQuery *hq = io_host<NavQuery>(io, s_q);
-      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_state) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)nullptr, (NavRec *)nullptr,
-                         io_dev<double>(io, s_state), io_dev<int32_t>(io, s_stat));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), io.bytes() - io.off(s_state), hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      {   // device times of this call, for ctvio_last_timing: k_cov_nav_jac and the whole call
-        Timing t;
-        t.clear();
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
-        t.ms[2] = ms; t.n[2] = 1;
-        if (const int rc = publish_timing(t, 0)) return rc;
-      }
-      const double *hstate = io_host<double>(io, s_state);
-      const int32_t *hstat = io_host<int32_t>(io, s_stat);
-      for (int r = 0; r < n; ++r) {
-        const size_t i = (size_t)slot[(size_t)r];
-        if (state16) std::memcpy(state16 + 16 * i, hstate + 16 * (size_t)r, sizeof(double) * 16);
-        if (status) status[i] = hstat[r];
-      }
-      return CTVIO_OK;
-    }
-    std::vector<CovTile> tiles(nn);
-    for (int r = 0; r < n; ++r) tiles[(size_t)r] = CovTile{win_of(r), 4, r, 1, 0};
-    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); cov225 | state16 | status (out, one copy).  scr: mask, exclusions, records
-    CallLayout io = head_, scr;
-    const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
-              s_tiles = io.add("tiles", sizeof(CovTile), nn, false), s_cov = io.add("cov225", sizeof(double), 225 * nn, true),
+    const bool want_cov = cov225 != nullptr;
+    const size_t nc = want_cov ? nn : 0;
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, 4) : std::vector<CovTile>();
+    // ---- out: cov225 | state16 | status
+    CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(NavRec), nn);
+    CallLayout io = head_;
+    const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nc, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov225", sizeof(double), 225 * nc, true),
               s_state = io.add("state16", sizeof(double), 16 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_rec = scr.add("records", sizeof(NavRec), nn, false);
-    if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-    NavRec *drec = scr.at<NavRec>(call_scr_.dev, s_rec);
+    if (const int rc = reserve_call(io, want_cov ? &scr.lay : nullptr)) return rc;
     NavQuery *hq = io_host<NavQuery>(io, s_q);
-    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
-    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * nn);
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_cov) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec,
-                       io_dev<double>(io, s_state), io_dev<int32_t>(io, s_stat));
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles), io_dev<int32_t>(io, s_slot),
-                       (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0,
-                       drec, io_dev<double>(io, s_cov));
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    // ---- results: the blocks as the kernel left them (the caller's order), the states and statuses in sorted order
-    Lm *lm = io_host<Lm>(io, HEAD_LM);
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov225 | state16 | status)
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_nav_jac and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
-      const bool ran[3] = {true, true, true};
-      if (const int rc = cov_timing(pair, ran)) return rc;
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int w = ord.win_of(r);
+      hq[r] = NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(t_ns[i] - t0_[w])};
     }
-    // (time outside the spline: NaN; an untouched knot or bias state: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad
-    // pivot: NaN)
+    stage_tiles(io, s_slot, s_tiles, ord, tiles);
+    const int rc = run_query<NavRec>(
+        io, s_q, s_cov, want_cov ? &scr : nullptr,
+        [&](const uint8_t *excl, NavRec *rec) {
+          hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), excl, rec, io_dev<double>(io, s_state),
+                             io_dev<int32_t>(io, s_stat));
+        },
+        [&](const Dev &c, const NavRec *rec) {
+          CovSolveArgs<> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.nrec = rec; a.nav_cov = io_dev<double>(io, s_cov);
+          launch_cov_solve(c, tiles.size(), a);
+        });
+    if (rc) return rc;
+    // ---- results: the blocks as the kernel left them (the caller's order), the states and statuses in sorted order (time outside the
+    // spline: NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov), *hstate = io_host<double>(io, s_state);
     const int32_t *hstat = io_host<int32_t>(io, s_stat);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      int st = hstat[r];
-      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
-      double *o = cov225 + 225 * i;
-      if (st == POSE_OK) std::memcpy(o, hcov + 225 * i, sizeof(double) * 225);
-      else for (int e = 0; e < 225; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 16 == 0 ? inf : 0.0) : nan;
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int st = want_cov ? merge_status(hstat[r], lm[ord.win_of(r)].chol_fail != 0) : hstat[r];
+      if (want_cov) cov_block(cov225 + 225 * i, hcov + 225 * i, 15, st);
       if (state16) std::memcpy(state16 + 16 * i, hstate + 16 * (size_t)r, sizeof(double) * 16);
       if (status) status[i] = st;
     }
@@ -1570,14 +1578,15 @@ class SolverImpl {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
     if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || (only < 0 && !win) || (!rates9 && !cov225 && !chi2 && !status) || (chi2 && !meas6))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
-    const int n = (int)n64, nw = dev_.nwin;
+    const int n = (int)n64;
     const size_t nn = (size_t)n;
     if (n && noise6)
       for (int c = 0; c < 6; ++c)
         if (!(noise6[c] > 0.0) || !std::isfinite(noise6[c])) return fail(CTVIO_ERR_INVALID, "noise6: six positive, finite standard deviations");
+    const QueryOrder ord(only, n, win, dev_.nwin);
+    if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     for (int i = 0; i < n; ++i) {
       const int w = only >= 0 ? only : win[i];
-      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
       if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": bias state out of range");
       for (int c = 0; c < 6; ++c) {
         if (meas6 && !std::isfinite(meas6[6 * (size_t)i + c])) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": non-finite IMU sample");
@@ -1586,103 +1595,49 @@ class SolverImpl {
       }
     }
     if (n == 0) return CTVIO_OK;
-    // ---- queries by window; slot[r]: the caller's index of sorted query r
-    std::vector<int32_t> slot(nn);
-    for (int i = 0; i < n; ++i) slot[i] = i;
-    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
-    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
-    auto query_of = [&](int r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      const int w = win_of(r);
+    const bool want_cov = cov225 || chi2;
+    const size_t nc = want_cov ? nn : 0;
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, 7) : std::vector<CovTile>();
+    // ---- out: cov225 | chi2 | rates9 | status
+    CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(RatesRec), nn);
+    CallLayout io = head_;
+    const int s_q = io.add("queries", sizeof(RatesQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nc, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov225", sizeof(double), 225 * nc, true),
+              s_chi = io.add("chi2", sizeof(double), nc, true), s_val = io.add("rates9", sizeof(double), 9 * nn, true),
+              s_stat = io.add("status", sizeof(int32_t), nn, false);
+    if (const int rc = reserve_call(io, want_cov ? &scr.lay : nullptr)) return rc;
+    RatesQuery *hq = io_host<RatesQuery>(io, s_q);
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int w = ord.win_of(r);
       RatesQuery q{w, frame ? frame[i] : meta_[w].F - 1, (long long)(t_ns[i] - t0_[w]), {0, 0, 0, 0, 0, 0}, {1, 1, 1, 1, 1, 1}};
       for (int c = 0; c < 6 && chi2; ++c) { q.meas[c] = meas6[6 * i + c]; q.sig[c] = noise6 ? noise6[c] : 1.0 / meta_[w].imu_w[c]; }
-      return q;
-    };
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
-    if (!cov225 && !chi2) {   // in: queries (one staged copy); out: rates9 | status (one copy)
-      CallLayout io = head_;
-      const int s_q = io.add("queries", sizeof(RatesQuery), nn, false), s_val = io.add("rates9", sizeof(double), 9 * nn, true),
-                s_stat = io.add("status", sizeof(int32_t), nn, false);
-      if (const int rc = reserve_call(io)) return rc;
-      RatesQuery *hq = io_host<RatesQuery>(io, s_q);
-      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_val) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), (const uint8_t *)nullptr, (RatesRec *)nullptr,
-                         io_dev<double>(io, s_val), io_dev<int32_t>(io, s_stat));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_val), io_dev<char>(io, s_val), io.bytes() - io.off(s_val), hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      {   // device times of this call, for ctvio_last_timing: k_cov_rates_jac and the whole call
-        Timing t;
-        t.clear();
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
-        t.ms[2] = ms; t.n[2] = 1;
-        if (const int rc = publish_timing(t, 0)) return rc;
-      }
-      const double *hval = io_host<double>(io, s_val);
-      const int32_t *hstat = io_host<int32_t>(io, s_stat);
-      for (int r = 0; r < n; ++r) {
-        const size_t i = (size_t)slot[(size_t)r];
-        if (rates9) std::memcpy(rates9 + 9 * i, hval + 9 * (size_t)r, sizeof(double) * 9);
-        if (status) status[i] = hstat[r];
-      }
-      return CTVIO_OK;
+      hq[r] = q;
     }
-    std::vector<CovTile> tiles(nn);
-    for (int r = 0; r < n; ++r) tiles[(size_t)r] = CovTile{win_of(r), 7, r, 1, 0};
-    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); cov225 | chi2 | rates9 | status (out, one copy).  scr: mask, exclusions, records
-    CallLayout io = head_, scr;
-    const int s_q = io.add("queries", sizeof(RatesQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
-              s_tiles = io.add("tiles", sizeof(CovTile), nn, false), s_cov = io.add("cov225", sizeof(double), 225 * nn, true),
-              s_chi = io.add("chi2", sizeof(double), nn, true), s_val = io.add("rates9", sizeof(double), 9 * nn, true),
-              s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_rec = scr.add("records", sizeof(RatesRec), nn, false);
-    if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-    RatesRec *drec = scr.at<RatesRec>(call_scr_.dev, s_rec);
-    RatesQuery *hq = io_host<RatesQuery>(io, s_q);
-    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
-    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * nn);
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_cov) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), (const uint8_t *)excl, drec,
-                       io_dev<double>(io, s_val), io_dev<int32_t>(io, s_stat));
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL((k_cov_solve<false, false, true>), dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
-                       io_dev<int32_t>(io, s_slot), (double *)nullptr, chi2 ? io_dev<double>(io, s_chi) : (double *)nullptr, (const RatesRec *)drec,
-                       io_dev<double>(io, s_cov), (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    // ---- results: the blocks and gates as the kernel left them (the caller's order), the values and statuses in sorted order
-    Lm *lm = io_host<Lm>(io, HEAD_LM);
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov225 | chi2 | rates9 | status)
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_rates_jac and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
-      const bool ran[3] = {true, true, true};
-      if (const int rc = cov_timing(pair, ran)) return rc;
-    }
-    // (time outside the spline: NaN; an untouched knot or bias state: +inf on the diagonal, 0 elsewhere, chi2 0; a window whose factorisation
-    // met a bad pivot: NaN)
+    stage_tiles(io, s_slot, s_tiles, ord, tiles);
+    const int rc = run_query<RatesRec>(
+        io, s_q, s_cov, want_cov ? &scr : nullptr,
+        [&](const uint8_t *excl, RatesRec *rec) {
+          hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), excl, rec, io_dev<double>(io, s_val),
+                             io_dev<int32_t>(io, s_stat));
+        },
+        [&](const Dev &c, const RatesRec *rec) {
+          CovSolveArgs<false, false, true> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          if (chi2) a.chi2 = io_dev<double>(io, s_chi);
+          launch_cov_solve(c, tiles.size(), a);
+        });
+    if (rc) return rc;
+    // ---- results: the blocks and gates as the kernel left them (the caller's order), the values and statuses in sorted order (time
+    // outside the spline: NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi), *hval = io_host<double>(io, s_val);
     const int32_t *hstat = io_host<int32_t>(io, s_stat);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      int st = hstat[r];
-      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
-      if (cov225) {
-        double *o = cov225 + 225 * i;
-        if (st == POSE_OK) std::memcpy(o, hcov + 225 * i, sizeof(double) * 225);
-        else for (int e = 0; e < 225; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 16 == 0 ? inf : 0.0) : nan;
-      }
-      if (chi2) chi2[i] = st == POSE_OK ? hchi[i] : (st == POSE_UNTOUCHED ? 0.0 : nan);
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int st = want_cov ? merge_status(hstat[r], lm[ord.win_of(r)].chol_fail != 0) : hstat[r];
+      if (cov225) cov_block(cov225 + 225 * i, hcov + 225 * i, 15, st);
+      if (chi2) chi2[i] = gate_value(hchi[i], st);
       if (rates9) std::memcpy(rates9 + 9 * i, hval + 9 * (size_t)r, sizeof(double) * 9);
       if (status) status[i] = st;
     }
@@ -1699,7 +1654,7 @@ class SolverImpl {
     if (n64 < 0 || n64 > (int64_t)1 << 30 ||
         (n64 && (!n_imu || !imu_t || !imu_gyro || !imu_acc || !noise || (only < 0 && !win) || (!state16 && !cov225 && !status))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
-    const int n = (int)n64, nw = dev_.nwin;
+    const int n = (int)n64;
     const size_t nn = (size_t)n;
     if (n == 0) return CTVIO_OK;
     {
@@ -1707,11 +1662,12 @@ class SolverImpl {
       for (double x : sg)
         if (!(x >= 0.0) || !std::isfinite(x)) return fail(CTVIO_ERR_INVALID, "a noise sigma is negative or not finite");
     }
+    const QueryOrder ord(only, n, win, dev_.nwin);
+    if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     std::vector<int64_t> first(nn + 1, 0);   // first sample of every query (the caller's order)
     for (int i = 0; i < n; ++i) {
       const int w = only >= 0 ? only : win[i];
       const std::string what = "query " + std::to_string(i);
-      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, what + ": window id out of range");
       if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, what + ": bias state out of range");
       if (n_imu[i] < 1 || n_imu[i] > 4096) return fail(CTVIO_ERR_INVALID, what + ": 1 to 4096 samples");
       const int64_t b = first[(size_t)i], e = b + n_imu[i];
@@ -1726,37 +1682,30 @@ class SolverImpl {
     if (ns > (size_t)1 << 30) return fail(CTVIO_ERR_INVALID, "more than 2^30 samples in one call");
     auto entry0 = [&](size_t i) { return last_only ? (int64_t)i : first[i]; };
     auto entries = [&](size_t i) { return last_only ? (size_t)1 : (size_t)n_imu[i]; };
-    // ---- queries by window; slot[r]: the caller's index of sorted query r
-    std::vector<int32_t> slot(nn);
-    for (int i = 0; i < n; ++i) slot[i] = i;
-    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
-    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
     const bool want_cov = cov225 != nullptr;
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, 4) : std::vector<CovTile>();
     // ---- scratch.  io: queries, propagation queries, sample times and measurements, entries, tiles (in, one staged copy); cov225 | state16 |
     // status (out, one copy).  scr: mask, exclusions, records, the states at sample 0
-    CallLayout io = head_, scr;
+    CovScratch cs(want_cov, (size_t)dev_.Utot, sizeof(NavRec), nn);
+    CallLayout io = head_, &scr = cs.lay;
     const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_pq = io.add("prop", sizeof(PropQuery), nn, false),
               s_t = io.add("imu_t", sizeof(int64_t), ns, false), s_gyro = io.add("imu_gyro", sizeof(double), 3 * ns, false),
               s_acc = io.add("imu_acc", sizeof(double), 3 * ns, false), s_slot = io.add("entry", sizeof(int32_t), want_cov ? nn : 0, false),
-              s_tiles = io.add("tiles", sizeof(CovTile), want_cov ? nn : 0, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
               s_cov = io.add("cov225", sizeof(double), want_cov ? 225 * no : 0, true), s_state = io.add("state16", sizeof(double), 16 * no, true),
               s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, want_cov ? (size_t)dev_.Utot : 0, false), s_excl = scr.add("excl", 1, want_cov ? (size_t)dev_.Utot : 0, false),
-              s_rec = scr.add("records", sizeof(NavRec), want_cov ? nn : 0, false), s_x0 = scr.add("state0", sizeof(double), 16 * nn, true);
+    const int s_x0 = scr.add("state0", sizeof(double), 16 * nn, true);
     if (const int rc = reserve_call(io, &scr)) return rc;
     NavQuery *hq = io_host<NavQuery>(io, s_q);
     PropQuery *hp = io_host<PropQuery>(io, s_pq);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      const int w = win_of(r);
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int w = ord.win_of(r);
       hq[r] = NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(imu_t[first[i]] - t0_[w])};
       hp[r] = PropQuery{w, n_imu[i], (long long)first[i], (long long)entry0(i)};
-      if (want_cov) {
-        io_host<int32_t>(io, s_slot)[r] = (int32_t)entry0(i);
-        io_host<CovTile>(io, s_tiles)[r] = CovTile{w, 4, r, 1, 0};
-      }
+      if (want_cov) io_host<int32_t>(io, s_slot)[r] = (int32_t)entry0(i);
     }
+    stage_tiles(io, -1, s_tiles, ord, tiles);
     std::memcpy(io_host<int64_t>(io, s_t), imu_t, sizeof(int64_t) * ns);
     std::memcpy(io_host<double>(io, s_gyro), imu_gyro, sizeof(double) * 3 * ns);
     std::memcpy(io_host<double>(io, s_acc), imu_acc, sizeof(double) * 3 * ns);
@@ -1768,14 +1717,7 @@ class SolverImpl {
                          io_dev<long long>(io, s_t), io_dev<double>(io, s_gyro), io_dev<double>(io, s_acc), nz, last_only ? 1 : 0, (const double *)x0,
                          io_dev<double>(io, s_state), want_cov ? io_dev<double>(io, s_cov) : (double *)nullptr);
     };
-    Timing tm;
-    tm.clear();
-    auto elapsed = [&](int k, Ev a, Ev b) {
-      float ms = 0;
-      const hipError_t e = hipEventElapsedTime(&ms, ev_[a], ev_[b]);
-      tm.ms[k] = ms; tm.n[k] = 1;
-      return e;
-    };
+    // (run_query's sequence with k_imu_propagate behind the record kernel or the solve, timed as ms[3])
     if (!want_cov) {
       HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
       HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
@@ -1788,50 +1730,41 @@ class SolverImpl {
       HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), io.bytes() - out0, hipMemcpyDeviceToHost, stream_));
       HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
       if (const int rc = sync_call()) return rc;
-      HIPCHK(elapsed(2, EV_QUERY_BEGIN, EV_QUERY_END));
-      HIPCHK(elapsed(3, EV_QUERY_END, EV_COV_GRAM));
+      if (const int rc = span_timing({{2, EV_QUERY_BEGIN, EV_QUERY_END}, {3, EV_QUERY_END, EV_COV_GRAM}})) return rc;
     } else {
-      uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-      NavRec *drec = scr.at<NavRec>(call_scr_.dev, s_rec);
+      uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, cs.s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, cs.s_excl);
+      NavRec *drec = scr.at<NavRec>(call_scr_.dev, cs.s_rec);
       HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
       Dev c;
       if (const int rc = cov_factor(c, mask, excl)) return rc;
       hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec, x0,
                          io_dev<int32_t>(io, s_stat));
       HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)n), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles), io_dev<int32_t>(io, s_slot),
-                         (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, (const PointRec *)nullptr, (double *)nullptr, 0,
-                         drec, io_dev<double>(io, s_cov));
+      CovSolveArgs<> a;
+      a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.nrec = drec; a.nav_cov = io_dev<double>(io, s_cov);
+      launch_cov_solve(c, tiles.size(), a);
       HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
       propagate();
       HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
       HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
       HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - out0, hipMemcpyDeviceToHost, stream_));   // (cov225 | state16 | status)
-      HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
       if (const int rc = finish_call(io)) return rc;
-      HIPCHK(elapsed(0, EV_COV_PREPARE, EV_COV_FACTOR));
-      HIPCHK(elapsed(1, EV_COV_GRAM, EV_QUERY_BEGIN));
-      HIPCHK(elapsed(2, EV_COV_SOLVE, EV_COV_GRAM));
-      HIPCHK(elapsed(3, EV_QUERY_BEGIN, EV_QUERY_END));
+      if (const int rc = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM},
+                                      {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
+        return rc;
     }
-    if (const int rc = publish_timing(tm, 0)) return rc;
-    // ---- results, every entry of a query by the query's status (time outside the spline: NaN; an untouched knot or bias state: +inf on the
-    // diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN covariances)
+    // ---- results, every entry of a query by the query's status (time outside the spline: NaN)
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
-    const double *hcov = want_cov ? io_host<double>(io, s_cov) : nullptr, *hstate = io_host<double>(io, s_state);
+    const double *hcov = io_host<double>(io, s_cov), *hstate = io_host<double>(io, s_state);
     const int32_t *hstat = io_host<int32_t>(io, s_stat);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r], e0 = (size_t)entry0(i), ne = entries(i);
-      int st = hstat[r];
-      if (want_cov && st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
-      if (want_cov) {
-        double *o = cov225 + 225 * e0;
-        if (st == POSE_OK) std::memcpy(o, hcov + 225 * e0, sizeof(double) * 225 * ne);
-        else for (size_t e = 0; e < 225 * ne; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 225 % 16 == 0 ? inf : 0.0) : nan;
-      }
+      const size_t i = (size_t)ord.slot[(size_t)r], e0 = (size_t)entry0(i), ne = entries(i);
+      const int st = want_cov ? merge_status(hstat[r], lm[ord.win_of(r)].chol_fail != 0) : hstat[r];
+      for (size_t e = e0; e < e0 + ne && want_cov; ++e) cov_block(cov225 + 225 * e, hcov + 225 * e, 15, st);
       if (state16) {
         if (st != POSE_OUTSIDE) std::memcpy(state16 + 16 * e0, hstate + 16 * e0, sizeof(double) * 16 * ne);
-        else std::fill(state16 + 16 * e0, state16 + 16 * (e0 + ne), nan);
+        else std::fill(state16 + 16 * e0, state16 + 16 * (e0 + ne), std::nan(""));
       }
       if (status) status[i] = st;
     }
@@ -1852,106 +1785,49 @@ class SolverImpl {
     SensorExt ext{};
     if (q_SI)
       if (const int rc = sensor_ext(q_SI, p_SI, ext)) return rc;
-    const int n = (int)n64, nw = dev_.nwin;
+    const int n = (int)n64;
     const size_t nn = (size_t)n;
-    if (only < 0)
-      for (int i = 0; i < n; ++i)
-        if (win[i] < 0 || win[i] >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
+    const QueryOrder ord(only, n, win, dev_.nwin);
+    if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     if (n == 0) return CTVIO_OK;
-    // ---- queries by window; slot[r]: the caller's index of sorted query r
-    std::vector<int32_t> slot(nn);
-    for (int i = 0; i < n; ++i) slot[i] = i;
-    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
-    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
-    auto query_of = [&](int r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      const int w = win_of(r);
-      return RelQuery{w, 0, (long long)(t_a_ns[i] - t0_[w]), (long long)(t_b_ns[i] - t0_[w])};
-    };
-    if (!cov36) {   // in: queries (one staged copy); out: rel7 | status (one copy)
-      CallLayout io = head_;
-      const int s_q = io.add("queries", sizeof(RelQuery), nn, false), s_rel = io.add("rel7", sizeof(double), 7 * nn, true),
-                s_stat = io.add("status", sizeof(int32_t), nn, false);
-      if (const int rc = reserve_call(io)) return rc;
-      RelQuery *hq = io_host<RelQuery>(io, s_q);
-      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_rel) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), (const uint8_t *)nullptr, ext,
-                         (RelRec *)nullptr, io_dev<double>(io, s_rel), io_dev<int32_t>(io, s_stat));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_rel), io_dev<char>(io, s_rel), io.bytes() - io.off(s_rel), hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      {   // device times of this call, for ctvio_last_timing: k_cov_rel_jac and the whole call
-        Timing t;
-        t.clear();
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
-        t.ms[2] = ms; t.n[2] = 1;
-        if (const int rc = publish_timing(t, 0)) return rc;
-      }
-      const double *hrel = io_host<double>(io, s_rel);
-      const int32_t *hstat = io_host<int32_t>(io, s_stat);
-      for (int r = 0; r < n; ++r) {
-        const size_t i = (size_t)slot[(size_t)r];
-        if (rel7) std::memcpy(rel7 + 7 * i, hrel + 7 * (size_t)r, sizeof(double) * 7);
-        if (status) status[i] = hstat[r];
-      }
-      return CTVIO_OK;
-    }
-    std::vector<CovTile> tiles;
-    for (int r = 0; r < n;) {   // two per tile
-      const int cnt = (r + 1 < n && win_of(r + 1) == win_of(r)) ? 2 : 1;
-      tiles.push_back(CovTile{win_of(r), 5, r, cnt, 0});
-      r += cnt;
-    }
-    // ---- scratch.  io: queries, slots, tiles (in, one staged copy); rel7 | cov36 | status (out, one copy).  scr: mask, exclusions, records
-    CallLayout io = head_, scr;
-    const int s_q = io.add("queries", sizeof(RelQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nn, false),
+    const bool want_cov = cov36 != nullptr;
+    const size_t nc = want_cov ? nn : 0;
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 2, 5) : std::vector<CovTile>();
+    // ---- out: rel7 | cov36 | status
+    CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(RelRec), nn);
+    CallLayout io = head_;
+    const int s_q = io.add("queries", sizeof(RelQuery), nn, false), s_slot = io.add("slot", sizeof(int32_t), nc, false),
               s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_rel = io.add("rel7", sizeof(double), 7 * nn, true),
-              s_cov = io.add("cov36", sizeof(double), 36 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_rec = scr.add("records", sizeof(RelRec), nn, false);
-    if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-    RelRec *drec = scr.at<RelRec>(call_scr_.dev, s_rec);
+              s_cov = io.add("cov36", sizeof(double), 36 * nc, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
+    if (const int rc = reserve_call(io, want_cov ? &scr.lay : nullptr)) return rc;
     RelQuery *hq = io_host<RelQuery>(io, s_q);
-    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-    std::memcpy(io_host<int32_t>(io, s_slot), slot.data(), sizeof(int32_t) * nn);
-    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_rel) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), (const uint8_t *)excl, ext, drec,
-                       io_dev<double>(io, s_rel), io_dev<int32_t>(io, s_stat));
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve<true>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
-                       io_dev<int32_t>(io, s_slot), (double *)nullptr, (double *)nullptr, (const RelRec *)drec, io_dev<double>(io, s_cov),
-                       (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    // ---- results: the blocks as the kernel left them (the caller's order), the values and statuses in sorted order
-    Lm *lm = io_host<Lm>(io, HEAD_LM);
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_rel), io_dev<char>(io, s_rel), io.bytes() - io.off(s_rel), hipMemcpyDeviceToHost, stream_));   // (rel7 | cov36 | status)
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_rel_jac and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
-      const bool ran[3] = {true, true, true};
-      if (const int rc = cov_timing(pair, ran)) return rc;
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int w = ord.win_of(r);
+      hq[r] = RelQuery{w, 0, (long long)(t_a_ns[i] - t0_[w]), (long long)(t_b_ns[i] - t0_[w])};
     }
-    // (either time outside the spline: NaN; an untouched knot: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN)
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    stage_tiles(io, s_slot, s_tiles, ord, tiles);
+    const int rc = run_query<RelRec>(
+        io, s_q, s_rel, want_cov ? &scr : nullptr,
+        [&](const uint8_t *excl, RelRec *rec) {
+          hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), excl, ext, rec, io_dev<double>(io, s_rel),
+                             io_dev<int32_t>(io, s_stat));
+        },
+        [&](const Dev &c, const RelRec *rec) {
+          CovSolveArgs<true> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          launch_cov_solve(c, tiles.size(), a);
+        });
+    if (rc) return rc;
+    // ---- results: the blocks as the kernel left them (the caller's order), the values and statuses in sorted order (either time outside
+    // the spline: NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov), *hrel = io_host<double>(io, s_rel);
     const int32_t *hstat = io_host<int32_t>(io, s_stat);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      int st = hstat[r];
-      if (st == POSE_OK && lm[win_of(r)].chol_fail != 0) st = POSE_SINGULAR;
-      double *o = cov36 + 36 * i;
-      if (st == POSE_OK) std::memcpy(o, hcov + 36 * i, sizeof(double) * 36);
-      else for (int e = 0; e < 36; ++e) o[e] = st == POSE_UNTOUCHED ? (e % 7 == 0 ? inf : 0.0) : nan;
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int st = want_cov ? merge_status(hstat[r], lm[ord.win_of(r)].chol_fail != 0) : hstat[r];
+      if (want_cov) cov_block(cov36 + 36 * i, hcov + 36 * i, 6, st);
       if (rel7) std::memcpy(rel7 + 7 * i, hrel + 7 * (size_t)r, sizeof(double) * 7);
       if (status) status[i] = st;
     }
@@ -1975,115 +1851,57 @@ class SolverImpl {
         return fail(CTVIO_ERR_INVALID, "row model: iterations in 1 .. 8, rows >= 1, finite fy and cy");
       prm = ProjRowModel{rm->fy, rm->cy, rm->rows, rm->iterations};
     }
-    const int n = (int)n64, nw = dev_.nwin;
+    const int n = (int)n64;
     const size_t nn = (size_t)n;
+    const QueryOrder ord(only, n, win, dev_.nwin);
+    if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     for (int i = 0; i < n; ++i) {
       const int w = only >= 0 ? only : win[i];
-      if (w < 0 || w >= nw) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": window id out of range");
       if (lmi[i] < 0 || lmi[i] >= meta_[w].L) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": landmark index out of range");
       if (obs2 && !(std::isfinite(obs2[2 * (size_t)i]) && std::isfinite(obs2[2 * (size_t)i + 1])))
         return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": non-finite candidate point");
     }
     if (n == 0) return CTVIO_OK;
-    // ---- queries by window; slot[r]: the caller's index of sorted query r
-    std::vector<int32_t> slot(nn);
-    for (int i = 0; i < n; ++i) slot[i] = i;
-    if (only < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
-    auto win_of = [&](int r) { return only >= 0 ? only : win[slot[(size_t)r]]; };
-    auto query_of = [&](int r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      const int w = win_of(r);
-      return ProjQuery{w, lmi[i], row[i], 0, (long long)(t_ns[i] - t0_[w]), {obs2 ? obs2[2 * i] : 0.0, obs2 ? obs2[2 * i + 1] : 0.0}};
-    };
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
-    if (!cov4 && !chi2) {   // in: queries (one staged copy); out: proj3 | row | status (one copy)
-      CallLayout io = head_;
-      const int s_q = io.add("queries", sizeof(ProjQuery), nn, false), s_proj = io.add("proj3", sizeof(double), 3 * nn, true),
-                s_row = io.add("row", sizeof(int32_t), nn, false), s_stat = io.add("status", sizeof(int32_t), nn, false);
-      if (const int rc = reserve_call(io)) return rc;
-      ProjQuery *hq = io_host<ProjQuery>(io, s_q);
-      for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_proj) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), (const uint8_t *)nullptr, prm,
-                         (ProjRec *)nullptr, io_dev<double>(io, s_proj), io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_proj), io_dev<char>(io, s_proj), io.bytes() - io.off(s_proj), hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      {   // device times of this call, for ctvio_last_timing: k_cov_proj_jac and the whole call
-        Timing t;
-        t.clear();
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
-        t.ms[2] = ms; t.n[2] = 1;
-        if (const int rc = publish_timing(t, 0)) return rc;
-      }
-      const double *hproj = io_host<double>(io, s_proj);
-      const int32_t *hrow = io_host<int32_t>(io, s_row), *hstat = io_host<int32_t>(io, s_stat);
-      for (int r = 0; r < n; ++r) {
-        const size_t i = (size_t)slot[(size_t)r];
-        if (proj3) std::memcpy(proj3 + 3 * i, hproj + 3 * (size_t)r, sizeof(double) * 3);
-        if (row_out) row_out[i] = hrow[r];
-        if (status) status[i] = hstat[r];
-      }
-      return CTVIO_OK;
-    }
-    std::vector<CovTile> tiles;
-    for (int r = 0; r < n;) {   // eight per tile
-      int cnt = 1;
-      while (cnt < PRJ_PER_TILE && r + cnt < n && win_of(r + cnt) == win_of(r)) ++cnt;
-      tiles.push_back(CovTile{win_of(r), 6, r, cnt, 0});
-      r += cnt;
-    }
-    // ---- scratch.  io: queries, tiles (in, one staged copy); proj3 | cov4 | chi2 | row | status (out, one copy).  scr: mask, exclusions, records
-    CallLayout io = head_, scr;
+    const bool want_cov = cov4 || chi2;
+    const size_t nc = want_cov ? nn : 0;
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, PRJ_PER_TILE, 6) : std::vector<CovTile>();
+    // ---- out: proj3 | cov4 | chi2 | row | status, all in sorted order (the kernels write by record: no slots)
+    CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(ProjRec), nn);
+    CallLayout io = head_;
     const int s_q = io.add("queries", sizeof(ProjQuery), nn, false), s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
-              s_proj = io.add("proj3", sizeof(double), 3 * nn, true), s_cov = io.add("cov4", sizeof(double), 4 * nn, true),
-              s_chi = io.add("chi2", sizeof(double), nn, true), s_row = io.add("row", sizeof(int32_t), nn, false),
+              s_proj = io.add("proj3", sizeof(double), 3 * nn, true), s_cov = io.add("cov4", sizeof(double), 4 * nc, true),
+              s_chi = io.add("chi2", sizeof(double), nc, true), s_row = io.add("row", sizeof(int32_t), nn, false),
               s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_rec = scr.add("records", sizeof(ProjRec), nn, false);
-    if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-    ProjRec *drec = scr.at<ProjRec>(call_scr_.dev, s_rec);
+    if (const int rc = reserve_call(io, want_cov ? &scr.lay : nullptr)) return rc;
     ProjQuery *hq = io_host<ProjQuery>(io, s_q);
-    for (int r = 0; r < n; ++r) hq[r] = query_of(r);
-    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), io.off(s_proj) - io.off(s_q), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), (const uint8_t *)excl, prm, drec,
-                       io_dev<double>(io, s_proj), io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL((k_cov_solve<false, true>), dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
-                       (const int32_t *)nullptr, (double *)nullptr, chi2 ? io_dev<double>(io, s_chi) : (double *)nullptr, (const ProjRec *)drec,
-                       io_dev<double>(io, s_cov), (const PointRec *)nullptr, (double *)nullptr, 0, (const NavRec *)nullptr, (double *)nullptr);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    // ---- results, all in sorted order
-    Lm *lm = io_host<Lm>(io, HEAD_LM);
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_proj), io_dev<char>(io, s_proj), io.bytes() - io.off(s_proj), hipMemcpyDeviceToHost, stream_));   // (proj3 | cov4 | chi2 | row | status)
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_proj_jac and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
-      const bool ran[3] = {true, true, true};
-      if (const int rc = cov_timing(pair, ran)) return rc;
+    for (int r = 0; r < n; ++r) {
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int w = ord.win_of(r);
+      hq[r] = ProjQuery{w, lmi[i], row[i], 0, (long long)(t_ns[i] - t0_[w]), {obs2 ? obs2[2 * i] : 0.0, obs2 ? obs2[2 * i + 1] : 0.0}};
     }
-    // (not computable: NaN; no information: +inf on the diagonal, 0 elsewhere, chi2 0; a window whose factorisation met a bad pivot: NaN)
+    stage_tiles(io, -1, s_tiles, ord, tiles);
+    const int rc = run_query<ProjRec>(
+        io, s_q, s_proj, want_cov ? &scr : nullptr,
+        [&](const uint8_t *excl, ProjRec *rec) {
+          hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), excl, prm, rec, io_dev<double>(io, s_proj),
+                             io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
+        },
+        [&](const Dev &c, const ProjRec *rec) {
+          CovSolveArgs<false, true> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          if (chi2) a.chi2 = io_dev<double>(io, s_chi);
+          launch_cov_solve(c, tiles.size(), a);
+        });
+    if (rc) return rc;
+    // ---- results (not computable: NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hproj = io_host<double>(io, s_proj), *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
     const int32_t *hrow = io_host<int32_t>(io, s_row), *hstat = io_host<int32_t>(io, s_stat);
     for (int r = 0; r < n; ++r) {
-      const size_t i = (size_t)slot[(size_t)r];
-      int st = hstat[r];
-      if (st == PRJ_OK && lm[win_of(r)].chol_fail != 0) st = PRJ_SINGULAR;
-      if (cov4) {
-        double *o = cov4 + 4 * i;
-        if (st == PRJ_OK) std::memcpy(o, hcov + 4 * (size_t)r, sizeof(double) * 4);
-        else for (int e = 0; e < 4; ++e) o[e] = st == PRJ_NO_INFO ? (e % 3 == 0 ? inf : 0.0) : nan;
-      }
-      if (chi2) chi2[i] = st == PRJ_OK ? hchi[r] : (st == PRJ_NO_INFO ? 0.0 : nan);
+      const size_t i = (size_t)ord.slot[(size_t)r];
+      const int st = want_cov ? merge_status(hstat[r], lm[ord.win_of(r)].chol_fail != 0) : hstat[r];
+      if (cov4) cov_block(cov4 + 4 * i, hcov + 4 * (size_t)r, 2, st);
+      if (chi2) chi2[i] = gate_value(hchi[r], st);
       if (proj3) std::memcpy(proj3 + 3 * i, hproj + 3 * (size_t)r, sizeof(double) * 3);
       if (row_out) row_out[i] = hrow[r];
       if (status) status[i] = st;
@@ -2096,14 +1914,7 @@ class SolverImpl {
   static TriOpts tri_opts(const ctvio_triangulate_options &o) {
     return TriOpts{o.row_times != 0, o.only_unset != 0, o.apply != 0, 0, o.min_depth, o.init_depth};
   }
-  int tri_timing() {   // (the stream is idle) ms[0]: the kernel between the query events, ms[7]: the whole call
-    Timing t;
-    t.clear();
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev_[EV_QUERY_BEGIN], ev_[EV_QUERY_END]));
-    t.ms[0] = ms; t.n[0] = 1;
-    return publish_timing(t, 0);
-  }
+  int tri_timing() { return span_timing({{0, EV_QUERY_BEGIN, EV_QUERY_END}}); }   // ms[0]: the kernel between the query events, ms[7]: the whole call
   int triangulate(bool single, int only, const ctvio_triangulate_options *o, double *depth, int32_t *flag) {
     if (const int rc = single ? guard(only) : guard()) return rc;
     if (!o) return fail(CTVIO_ERR_INVALID, "null options");
@@ -2133,68 +1944,47 @@ class SolverImpl {
     const int l0 = single ? meta_[only].lm0 : 0, n = single ? meta_[only].L : dev_.Ltot;
     if (n == 0) return CTVIO_OK;
     const size_t nn = (size_t)n;
-    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
-    if (!cov9) {   // out: point3 | status (one copy)
-      CallLayout io = head_;
-      const int s_pt = io.add("point3", sizeof(double), 3 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
-      if (const int rc = reserve_call(io)) return rc;
+    const bool want_cov = cov9 != nullptr;
+    std::vector<CovTile> tiles;
+    for (int w = wbeg; w < wend && want_cov; ++w)
+      for (int r = 0; r < meta_[w].L; r += LMP_PER_TILE) tiles.push_back(CovTile{w, 3, r, std::min(LMP_PER_TILE, meta_[w].L - r), 0});
+    // ---- io: tiles (in, one staged copy); cov9 | point3 | status (out, one copy).  The records: one per landmark of the batch
+    CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(PointRec), (size_t)dev_.Ltot);
+    CallLayout io = head_;
+    const int s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov9", sizeof(double), want_cov ? 9 * nn : 0, true),
+              s_pt = io.add("point3", sizeof(double), 3 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
+    if (const int rc = reserve_call(io, want_cov ? &scr.lay : nullptr)) return rc;
+    auto jac = [&](const uint8_t *, PointRec *rec) {
+      hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, rec ? 1 : 0, rec, io_dev<double>(io, s_pt), io_dev<int32_t>(io, s_stat));
+    };
+    if (!want_cov) {   // nothing goes in; the kernel's time is reported as the triangulation's is (ms[0])
       HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
       HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, 0, (PointRec *)nullptr, io_dev<double>(io, s_pt),
-                         io_dev<int32_t>(io, s_stat));
+      jac(nullptr, nullptr);
       HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
       HIPCHK(hipMemcpyAsync(io_host<char>(io, s_pt), io_dev<char>(io, s_pt), io.bytes() - io.off(s_pt), hipMemcpyDeviceToHost, stream_));
       HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
       if (const int rc = sync_call()) return rc;
       if (const int rc = tri_timing()) return rc;
-      if (point3) std::memcpy(point3, io_host<double>(io, s_pt), sizeof(double) * 3 * nn);
-      if (status) std::memcpy(status, io_host<int32_t>(io, s_stat), sizeof(int32_t) * nn);
-      return CTVIO_OK;
+    } else {
+      std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+      const int rc = run_query<PointRec>(io, s_tiles, s_cov, &scr, jac, [&](const Dev &c, const PointRec *rec) {
+        CovSolveArgs<> a;
+        a.tiles = io_dev<CovTile>(io, s_tiles); a.lrec = rec; a.lm_cov = io_dev<double>(io, s_cov); a.lm_base = l0;
+        launch_cov_solve(c, tiles.size(), a);
+      });
+      if (rc) return rc;
     }
-    std::vector<CovTile> tiles;
-    for (int w = wbeg; w < wend; ++w)
-      for (int r = 0; r < meta_[w].L; r += LMP_PER_TILE) tiles.push_back(CovTile{w, 3, r, std::min(LMP_PER_TILE, meta_[w].L - r), 0});
-    // ---- scratch.  io: tiles (in, one staged copy); cov9 | point3 | status (out, one copy).  scr: mask, exclusions, records
-    CallLayout io = head_, scr;
-    const int s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov9", sizeof(double), 9 * nn, true),
-              s_pt = io.add("point3", sizeof(double), 3 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_rec = scr.add("records", sizeof(PointRec), (size_t)dev_.Ltot, false);
-    if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
-    PointRec *drec = scr.at<PointRec>(call_scr_.dev, s_rec);
-    std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_tiles), io_host<char>(io, s_tiles), io.off(s_cov) - io.off(s_tiles), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, 1, drec, io_dev<double>(io, s_pt), io_dev<int32_t>(io, s_stat));
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    hipLaunchKernelGGL(k_cov_solve<false>, dim3((unsigned)tiles.size()), dim3(COV_NT), cov_solve_lds(), stream_, c, io_dev<CovTile>(io, s_tiles),
-                       (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (const PoseRec *)nullptr, (double *)nullptr, drec,
-                       io_dev<double>(io, s_cov), l0, (const NavRec *)nullptr, (double *)nullptr);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    // ---- results
-    Lm *lm = io_host<Lm>(io, HEAD_LM);
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));   // (cov9 | point3 | status)
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: k_cov_prepare, k_cov_solve, k_cov_point_jac and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_GRAM, EV_CALL_END}, {EV_COV_SOLVE, EV_COV_GRAM}};
-      const bool ran[3] = {true, true, true};
-      if (const int rc = cov_timing(pair, ran)) return rc;
-    }
-    // (not computable: NaN; no information on the inverse depth: +inf on the diagonal, 0 elsewhere; a window whose factorisation met a bad pivot: NaN)
+    // ---- results (not computable: NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov);
     const int32_t *hstat = io_host<int32_t>(io, s_stat);
     if (point3) std::memcpy(point3, io_host<double>(io, s_pt), sizeof(double) * 3 * nn);
     size_t i = 0;
     for (int w = wbeg; w < wend; ++w)
       for (int l = 0; l < meta_[w].L; ++l, ++i) {
-        int st = hstat[i];
-        if (st == LMP_OK && lm[w].chol_fail != 0) st = LMP_SINGULAR;
-        double *o = cov9 + 9 * i;
-        if (st == LMP_OK) std::memcpy(o, hcov + 9 * i, sizeof(double) * 9);
-        else for (int e = 0; e < 9; ++e) o[e] = st == LMP_NO_INFO ? (e % 4 == 0 ? inf : 0.0) : nan;
+        const int st = want_cov ? merge_status(hstat[i], lm[w].chol_fail != 0) : hstat[i];
+        if (want_cov) cov_block(cov9 + 9 * i, hcov + 9 * i, 3, st);
         if (status) status[i] = st;
       }
     return CTVIO_OK;

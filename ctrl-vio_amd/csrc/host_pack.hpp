@@ -11,6 +11,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <cstdint>
 #include <cstring>
@@ -497,6 +498,65 @@ class CallLayout {
   size_t bytes_ = 0, dev_bytes_ = 0;
   bool landing_ = false, reserved_ = false;
 };
+
+// The device-only scratch of a query entry that wants covariances (ctvio.hip: run_query): the call's activity mask and exclusions over the
+// batch's unknowns, then one record of rec_bytes per query.  Without covariances (want false) every segment is empty.
+struct CovScratch {
+  CallLayout lay;
+  int s_mask, s_excl, s_rec;
+  CovScratch(bool want, size_t unknowns, size_t rec_bytes, size_t nrec)
+      : s_mask(lay.add("mask", 1, want ? unknowns : 0, false)), s_excl(lay.add("excl", 1, want ? unknowns : 0, false)),
+        s_rec(lay.add("records", rec_bytes, want ? nrec : 0, false)) {}
+};
+
+// The n queries of a per-call entry grouped by window: query i belongs to window `only` (only >= 0; win is not read) or to win[i].
+// slot[r] is the caller's index of sorted query r; the sort is stable, so a window's queries keep the caller's order.
+class QueryOrder {
+ public:
+  std::vector<int32_t> slot;
+  QueryOrder(int only, int n, const int32_t *win, int nwin) : slot((size_t)std::max(n, 0)), only_(only), win_(win) {
+    std::iota(slot.begin(), slot.end(), 0);
+    if (only >= 0) return;
+    for (int i = 0; i < n && bad_ < 0; ++i)
+      if (win[i] < 0 || win[i] >= nwin) bad_ = i;
+    if (bad_ < 0) std::stable_sort(slot.begin(), slot.end(), [&](int32_t a, int32_t b) { return win[a] < win[b]; });
+  }
+  // empty, or the complaint about the first query whose window id lies outside [0, nwin): nothing below may be used then
+  std::string error() const { return bad_ < 0 ? std::string() : "query " + std::to_string(bad_) + ": window id out of range"; }
+  int win_of(int r) const { return only_ >= 0 ? only_ : win_[slot[(size_t)r]]; }
+  // the sorted queries cut into runs of at most per_tile consecutive queries of one window, in order: emit(window, first, count)
+  template <class F> void runs(int per_tile, F &&emit) const {
+    const int n = (int)slot.size();
+    for (int r = 0; r < n;) {
+      int cnt = 1;
+      while (cnt < per_tile && r + cnt < n && win_of(r + cnt) == win_of(r)) ++cnt;
+      emit(win_of(r), r, cnt);
+      r += cnt;
+    }
+  }
+
+ private:
+  int only_, bad_ = -1;
+  const int32_t *win_;
+};
+
+// The statuses a query entry reports share these values (ctvio.h; ctvio.hip asserts it of every enum of kernels_cov.hpp): 1 is the
+// host's -- the window's factorisation met a bad pivot (Lm::chol_fail) --, 2 "no information" (an untouched knot or bias state).
+enum { QUERY_OK = 0, QUERY_SINGULAR = 1, QUERY_NO_INFO = 2 };
+inline int merge_status(int st, bool chol_fail) { return st == QUERY_OK && chol_fail ? (int)QUERY_SINGULAR : st; }
+// The dim x dim covariance block (row-major) of a query whose status is not QUERY_OK: no information gives +inf on the diagonal and 0
+// elsewhere, every other status NaN.
+inline void fill_not_ok(double *o, int dim, int st) {
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int e = 0; e < dim * dim; ++e) o[e] = st == QUERY_NO_INFO ? (e % (dim + 1) == 0 ? inf : 0.0) : std::nan("");
+}
+// the caller's block o by status: the block `computed` the kernel left, or the fill
+inline void cov_block(double *o, const double *computed, int dim, int st) {
+  if (st == QUERY_OK) std::memcpy(o, computed, sizeof(double) * (size_t)dim * dim);
+  else fill_not_ok(o, dim, st);
+}
+// the caller's gate by status, likewise: no information gates nothing
+inline double gate_value(double computed, int st) { return st == QUERY_OK ? computed : (st == QUERY_NO_INFO ? 0.0 : std::nan("")); }
 
 // The input arena (pinned host mirror + device), every segment ONCE: X(element type, segment, Dev member, allocated count, filled count).
 // An empty set keeps one entry allocated.  The names stand for BatchFacts members (layout_input).  Irregular: `state` is the contiguous

@@ -76,6 +76,14 @@ std::vector<Case> cases() {
   }
   c.push_back({"mb_window_268_553", {}, {}, mb_window(268, 553), 1, 127});
   c.push_back({"mb_window_m0", {}, {}, mb_window(0, 70), 1, 127});
+  // the device-only scratch of the query entries, from the library's own CovScratch (not restated): 115 unknowns, records of 1184 bytes
+  for (size_t n : {(size_t)0, (size_t)5})
+    for (bool cov : {false, true}) {
+      const ctv::CovScratch s(cov, 115, 1184, n);
+      Case k{n ? (cov ? "query_scr_5_cov" : "query_scr_5") : (cov ? "query_scr_0_cov" : "query_scr_0"), {}, {}, {}, 1, 127};
+      for (const ctv::ArenaSeg &g : s.lay.segs()) k.scr.push_back({g.name, 1, g.bytes, g.dbl});
+      c.push_back(k);
+    }
   return c;
 }
 const std::vector<Case> g_cases = cases();
@@ -128,9 +136,77 @@ int fill_and_read(const Case &k, int which) {
     }
   return 0;
 }
+// QueryOrder over (only, n, win, nwin) cut at per_tile.  0, or the first rule broken: 1 slot is not the stable order by window; 2 a tile
+// holds two windows; 3 a count outside [1, per_tile]; 4 the tiles do not partition [0, n) in order; 5 an error where none is due
+int order_rules(int only, int n, const int32_t *win, int nwin, int per_tile) {
+  const ctv::QueryOrder ord(only, n, win, nwin);
+  if (!ord.error().empty()) return 5;
+  if ((int)ord.slot.size() != n) return 1;
+  std::vector<char> seen((size_t)n, 0);
+  for (int r = 0; r < n; ++r) {
+    const int i = ord.slot[(size_t)r];
+    if (i < 0 || i >= n || seen[(size_t)i]++) return 1;
+    if (ord.win_of(r) != (only >= 0 ? only : win[i])) return 1;
+    if (r && (ord.win_of(r - 1) > ord.win_of(r) || (ord.win_of(r - 1) == ord.win_of(r) && ord.slot[(size_t)r - 1] > i))) return 1;
+  }
+  int next = 0, bad = 0;
+  ord.runs(per_tile, [&](int w, int first, int cnt) {
+    if (first != next && !bad) bad = 4;
+    if ((cnt < 1 || cnt > per_tile || first + cnt > n) && !bad) bad = 3;
+    for (int r = first; r < first + cnt && !bad; ++r) if (ord.win_of(r) != w) bad = 2;
+    next = first + cnt;
+  });
+  return bad ? bad : (next == n ? 0 : 4);
+}
+const int32_t ORDER_WIN[11] = {2, 0, 2, 1, 2, 2, 2, 2, 2, 2, 2};
+// the cases of the issue that added QueryOrder: no query, one, a single window without a window list, the mixed list at every per_tile in use
+int order_cases() {
+  const int32_t one[1] = {1};
+  if (const int r = order_rules(-1, 0, nullptr, 3, 2)) return 10 + r;
+  if (const int r = order_rules(-1, 1, one, 3, 8)) return 20 + r;
+  if (const int r = order_rules(1, 5, nullptr, 3, 2)) return 30 + r;
+  for (int per : {1, 2, 8})
+    if (const int r = order_rules(-1, 11, ORDER_WIN, 3, per)) return 100 * per + r;
+  const int32_t out[3] = {0, 3, -1};
+  if (ctv::QueryOrder(-1, 3, out, 3).error() != "query 1: window id out of range") return 40;
+  return 0;
+}
+// fill_not_ok / cov_block / merge_status / gate_value against the literal patterns at dim 2, 3, 6, 15.  0, or 100 dim + the rule broken
+int fill_cases() {
+  for (int dim : {2, 3, 6, 15}) {
+    std::vector<double> o((size_t)dim * dim + 1), src((size_t)dim * dim, 7.0);
+    for (int st : {1, 2, 3}) {
+      std::fill(o.begin(), o.end(), -1.0);
+      ctv::cov_block(o.data(), src.data(), dim, st);
+      for (int i = 0; i < dim; ++i)
+        for (int j = 0; j < dim; ++j) {
+          const double v = o[(size_t)i * dim + j];
+          if (st == 2 ? (i == j ? !(std::isinf(v) && v > 0) : v != 0.0) : !std::isnan(v)) return 100 * dim + st;
+        }
+      if (o.back() != -1.0) return 100 * dim + 4;   // nothing past the block
+    }
+    ctv::cov_block(o.data(), src.data(), dim, 0);
+    for (int e = 0; e < dim * dim; ++e) if (o[(size_t)e] != 7.0) return 100 * dim + 5;
+  }
+  if (ctv::merge_status(0, true) != 1 || ctv::merge_status(0, false) != 0 || ctv::merge_status(2, true) != 2 || ctv::merge_status(3, true) != 3) return 6;
+  if (ctv::gate_value(5.0, 0) != 5.0 || ctv::gate_value(5.0, 2) != 0.0 || !std::isnan(ctv::gate_value(5.0, 1)) || !std::isnan(ctv::gate_value(5.0, 3))) return 7;
+  return 0;
+}
 }  // namespace
 
 extern "C" {
+int cl_order_cases() { return order_cases(); }
+int cl_fill_cases() { return fill_cases(); }
+// QueryOrder raw: slot[n]; the runs at per_tile as (window, first, count) triples in tile[3 cap]; returns the number of runs, -1 with an error
+int cl_query_order(int only, int n, const int32_t *win, int nwin, int per_tile, int32_t *slot, int cap, int32_t *tile) {
+  const ctv::QueryOrder ord(only, n, win, nwin);
+  if (!ord.error().empty()) return -1;
+  std::copy(ord.slot.begin(), ord.slot.end(), slot);
+  int nt = 0;
+  ord.runs(per_tile, [&](int w, int first, int cnt) { if (nt < cap) { tile[3 * nt] = w; tile[3 * nt + 1] = first; tile[3 * nt + 2] = cnt; } ++nt; });
+  return nt;
+}
+void cl_fill_not_ok(double *o, int dim, int st) { ctv::fill_not_ok(o, dim, st); }
 int cl_ncases() { return (int)g_cases.size(); }
 const char *cl_case_name(int c) { return g_cases[(size_t)c].name; }
 // the segments of case c in arena `which` (at most cap): names, offsets, bytes, flags; tot[0] the total, tot[1] the device's, tot[2] the head's segments
@@ -171,6 +247,8 @@ int main() {
       const int r = cl_refusals(c, which), f = cl_fill_and_read(c, which);
       if (r || f) { std::printf("%s arena %d: refusal rule %d, segment %d\n", cl_case_name(c), which, r, f); return 1; }
     }
+  if (const int r = order_cases()) { std::printf("query order: case / rule %d\n", r); return 1; }
+  if (const int r = fill_cases()) { std::printf("status fill: dim / rule %d\n", r); return 1; }
   std::printf("CALL_LAYOUT_OK %d cases\n", cl_ncases());
   return 0;
 }

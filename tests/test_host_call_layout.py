@@ -3,8 +3,10 @@
 after the one reservation of the call, typed pointers.  The cases are the entries' segment lists at the smallest interesting sizes and the
 degenerate ones (no queries, no selection with var_rho, nothing marginalised, a batch with no blocked window, a batch of only blocked ones).
 The shim also reads out the LDS layouts of the two tile Cholesky kernels (csrc/device_types.hpp: CholTilesLds, CholFlowLds).
+Beside it the host-only parts the query entries share: the order of the queries by window and its cut into tiles (QueryOrder), the
+device-only scratch (CovScratch) and the status merge and fill (merge_status, fill_not_ok, cov_block, gate_value).
 The same file is also built as a stand-alone program under AddressSanitizer + UBSan, which fills every segment of every case through its
-pointer over buffers of exactly the reserved sizes."""
+pointer over buffers of exactly the reserved sizes and runs the order and fill cases."""
 import ctypes as C
 import os
 import subprocess
@@ -49,7 +51,7 @@ def layout(cl, c, which):
 
 NAMES = ["head_only", "head_241", "linearize_tiny", "linearize_cost_only", "lm_step", "residual_summary", "gauge_two_windows", "query_none",
          "query_97_pose", "query_batch_5", "cov_tiny_20", "cov_no_selection_var_rho", "cov_nothing", "marg_no_blocked", "marg_only_blocked",
-         "marg_mixed", "mb_window_268_553", "mb_window_m0"]
+         "marg_mixed", "mb_window_268_553", "mb_window_m0", "query_scr_0", "query_scr_0_cov", "query_scr_5", "query_scr_5_cov"]
 
 
 def test_the_cases_are_the_listed_ones(cl):
@@ -94,6 +96,63 @@ def test_degenerate_cases_cost_what_they_should(cl):
     assert m[7][1] == m[8][1] == m[9][1] == m[10][1]
     b = layout(cl, NAMES.index("marg_only_blocked"), 1)
     assert [s[0] for s in b[0]] == ["mb", "rank"] and b[0][0][2] == layout(cl, NAMES.index("mb_window_268_553"), 1)[1]
+
+
+def test_query_scratch_costs_nothing_without_covariances(cl):
+    """host_pack.hpp: CovScratch, the one device-only layout of the query entries (mask | excl | records)."""
+    for case in ("query_scr_0", "query_scr_5"):
+        segs, total, _, _ = layout(cl, NAMES.index(case), 1)
+        assert [s[0] for s in segs] == ["mask", "excl", "records"] and [s[2] for s in segs] == [0, 0, 0] and total == 0
+    segs, total, _, _ = layout(cl, NAMES.index("query_scr_5_cov"), 1)
+    assert [s[2] for s in segs] == [115, 115, 5 * 1184] and [s[3] for s in segs] == [0, 0, 0] and total == 256 + 256 + 6144
+    assert [s[2] for s in layout(cl, NAMES.index("query_scr_0_cov"), 1)[0]] == [115, 115, 0]
+
+
+ORDER_WIN = [2, 0, 2, 1, 2, 2, 2, 2, 2, 2, 2]
+ORDER_CASES = [("none", -1, [], 2), ("one", -1, [1], 8), ("single_window", 1, None, 2)] + [("mixed_%d" % p, -1, ORDER_WIN, p) for p in (1, 2, 8)]
+
+
+@pytest.mark.parametrize("name,only,win,per_tile", ORDER_CASES, ids=[c[0] for c in ORDER_CASES])
+def test_query_order(cl, name, only, win, per_tile):
+    """host_pack.hpp: QueryOrder -- the stable order by window of the query entries and its cut into tiles of at most per_tile queries of
+    one window (1: nav_state / body_rates / imu_predict, 2: pose_covariance / relative_pose, 8: project_landmarks)."""
+    n = 5 if win is None else len(win)
+    w = None if win is None else np.asarray(win, np.int32)
+    wins = np.full(n, only, np.int32) if win is None else w
+    slot = np.full(max(n, 1), -7, np.int32); tile = np.zeros(3 * 16, np.int32)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    nt = cl.cl_query_order(only, n, None if w is None or n == 0 else p(w), 3, per_tile, p(slot), 16, p(tile))
+    assert 0 <= nt <= 16
+    assert slot[:n].tolist() == np.argsort(wins, kind="stable").tolist()               # the stable order
+    tiles = tile[:3 * nt].reshape(nt, 3)
+    nxt = 0
+    for tw, first, cnt in tiles.tolist():
+        assert first == nxt and 1 <= cnt <= per_tile                                    # a partition of [0, n), in order
+        assert set(wins[slot[first:first + cnt]].tolist()) == {tw}                      # one window per tile
+        nxt = first + cnt
+    assert nxt == n
+    if name.startswith("mixed"):
+        # window 0 and window 1: one query each; window 2: nine -- runs that end at the window boundary, more than 8 in one window
+        assert tiles[:2].tolist() == [[0, 0, 1], [1, 1, 1]]
+        assert tiles[2:, 2].tolist() == {1: [1] * 9, 2: [2, 2, 2, 2, 1], 8: [8, 1]}[per_tile] and set(tiles[2:, 0].tolist()) == {2}
+
+
+def test_query_order_refuses_a_window_out_of_range(cl):
+    w = np.asarray([0, 3, -1], np.int32); buf = np.zeros(48, np.int32)
+    assert cl.cl_query_order(-1, 3, w.ctypes.data_as(C.c_void_p), 3, 2, buf.ctypes.data_as(C.c_void_p), 16, buf.ctypes.data_as(C.c_void_p)) == -1
+    assert cl.cl_order_cases() == 0        # the same cases in C++ (the sanitizer program runs these), with the message of the refusal
+
+
+@pytest.mark.parametrize("dim", [2, 3, 6, 15])
+def test_status_fill(cl, dim):
+    """host_pack.hpp: fill_not_ok -- the block of a query that is not OK: no information (2) +inf on the diagonal and 0 elsewhere, else NaN."""
+    for st in (1, 2, 3):
+        o = np.full(dim * dim + 1, -1.0)
+        cl.cl_fill_not_ok(o.ctypes.data_as(C.c_void_p), dim, st)
+        want = np.diag(np.full(dim, np.inf)) if st == 2 else np.full((dim, dim), np.nan)
+        with np.errstate(invalid="ignore"):
+            assert np.array_equal(o[:-1].reshape(dim, dim), want, equal_nan=True) and o[-1] == -1.0
+    assert cl.cl_fill_cases() == 0         # cov_block, merge_status and gate_value beside it (the sanitizer program runs these too)
 
 
 @pytest.mark.parametrize("flow", [0, 1], ids=["barrier", "flow"])
