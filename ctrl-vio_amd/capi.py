@@ -96,6 +96,7 @@ SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "
            "ctvio_landmark_points_batch", "ctvio_landmark_points", "ctvio_nav_state_batch", "ctvio_nav_state",
            "ctvio_relative_pose_batch", "ctvio_relative_pose", "ctvio_project_landmarks_batch", "ctvio_project_landmarks",
            "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict", "ctvio_body_rates_batch", "ctvio_body_rates",
+           "ctvio_predict_landmarks_batch", "ctvio_predict_landmarks",
            "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
 _lib = None
@@ -158,6 +159,10 @@ def load_library():
         lib.ctvio_default_imu_noise.restype = None
         lib.ctvio_imu_predict_batch.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(ImuNoise), C.c_int32] + [C.c_void_p] * 3
         lib.ctvio_imu_predict.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.POINTER(ImuNoise), C.c_int32] + [C.c_void_p] * 3
+        lib.ctvio_predict_landmarks_batch.argtypes = ([C.c_void_p, C.c_int64] + [C.c_void_p] * 6 + [C.POINTER(ImuNoise), C.c_int64] + [C.c_void_p] * 3 +
+                                                      [C.POINTER(RowModel)] + [C.c_void_p] * 7)
+        lib.ctvio_predict_landmarks.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.POINTER(ImuNoise), C.c_int32] +
+                                                [C.c_void_p] * 2 + [C.POINTER(RowModel)] + [C.c_void_p] * 7)
         lib.ctvio_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
         lib.ctvio_default_triangulate_options.restype = None
         lib.ctvio_triangulate_batch.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p]

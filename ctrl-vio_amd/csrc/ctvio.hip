@@ -1267,12 +1267,12 @@ class SolverImpl {
   size_t cov_solve_lds() const { return ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double); }   // Ys | part (k_cov_solve)
   // k_cov_solve's arguments by name; what a call does not use stays null.  The template arguments are the kernel's (they choose the type
   // of the query records).  sel: the selections of covariance(), the output slots of the queries elsewhere.
-  template <bool REL = false, bool PROJ = false, bool RATES = false> struct CovSolveArgs {
+  template <bool REL = false, bool PROJ = false, bool RATES = false, bool PRED = false> struct CovSolveArgs {
     const CovTile *tiles = nullptr;
     const int32_t *sel = nullptr;
     double *Y = nullptr, *var_rho = nullptr;
-    double *chi2 = nullptr;                                            // the gates of the PROJ / RATES queries
-    const typename CovQueryRec<REL, PROJ, RATES>::type *qrec = nullptr;   // pose, relative-pose, projection or rates records
+    double *chi2 = nullptr;                                            // the gates of the PROJ / RATES / PRED queries
+    const typename CovQueryRec<REL, PROJ, RATES, PRED>::type *qrec = nullptr;   // pose, relative-pose, projection, rates or prediction records
     double *qcov = nullptr;
     const PointRec *lrec = nullptr;
     double *lm_cov = nullptr;
@@ -1280,10 +1280,10 @@ class SolverImpl {
     const NavRec *nrec = nullptr;
     double *nav_cov = nullptr;
   };
-  template <bool REL, bool PROJ, bool RATES> void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveArgs<REL, PROJ, RATES> &a) {
-    // (the PROJ / RATES instantiations have no landmark tiles: the kernel takes their gates in the position of var_rho)
-    hipLaunchKernelGGL((k_cov_solve<REL, PROJ, RATES>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a.tiles, a.sel, a.Y,
-                       PROJ || RATES ? a.chi2 : a.var_rho, a.qrec, a.qcov, a.lrec, a.lm_cov, a.lm_base, a.nrec, a.nav_cov);
+  template <bool REL, bool PROJ, bool RATES, bool PRED> void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveArgs<REL, PROJ, RATES, PRED> &a) {
+    // (the PROJ / RATES / PRED instantiations have no landmark tiles: the kernel takes their gates in the position of var_rho)
+    hipLaunchKernelGGL((k_cov_solve<REL, PROJ, RATES, PRED>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a.tiles, a.sel, a.Y,
+                       PROJ || RATES || PRED ? a.chi2 : a.var_rho, a.qrec, a.qcov, a.lrec, a.lm_cov, a.lm_base, a.nrec, a.nav_cov);
   }
   // the device times of a call between pairs of its events (the stream is idle): ms[slot] of ctvio_last_timing, one launch each
   struct Span { int slot; Ev begin, end; };
@@ -1908,6 +1908,173 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // ctvio_predict_landmarks_batch / ctvio_predict_landmarks (only >= 0: every prediction belongs to that window, win is not read): where
+  // landmark lm[i] falls in the camera at the IMU-predicted pose of prediction pred[i], row row[i], beyond the spline, with its 2 x 2
+  // covariance and gate.  The predictions are imu_predict()'s queries (grouped by window, stable), the points are grouped by the window of
+  // their prediction, eight to a tile of kind 8.  Sequence: staged copy, (cov_factor,) k_cov_nav_jac on the predictions' start times,
+  // k_imu_transition (end state, Phi, N), k_cov_pred_jac (value, status, record), k_cov_solve<PRED>, one copy back.  Its own sequence, as
+  // imu_predict's and for its reason: two record kernels, the transition between them and a fourth timing slot.  dev_, plan_ and the
+  // captured graph are not touched.
+  int predict_landmarks(int only, int64_t np64, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t, const double *imu_gyro,
+                        const double *imu_acc, const ctvio_imu_noise *noise, int64_t nq64, const int32_t *pred, const int32_t *lmi, const int32_t *row,
+                        const ctvio_row_model *rm, const double *obs2, double *state16, double *proj3, double *cov4, double *chi2, int32_t *row_out,
+                        int32_t *status) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (np64 < 0 || np64 > (int64_t)1 << 30 || nq64 < 0 || nq64 > (int64_t)1 << 30) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (np64 == 0 || nq64 == 0) return CTVIO_OK;
+    if (!n_imu || !imu_t || !imu_gyro || !imu_acc || !noise || (only < 0 && (!win || !pred)) || !lmi || !row || (!proj3 && !cov4 && !chi2 && !state16) ||
+        (chi2 && !obs2))
+      return fail(CTVIO_ERR_INVALID, "bad arguments");
+    ProjRowModel prm{0.0, 0.0, 1, 0};
+    if (rm) {
+      if (rm->iterations < 1 || rm->iterations > 8 || rm->rows < 1 || !std::isfinite(rm->fy) || !std::isfinite(rm->cy))
+        return fail(CTVIO_ERR_INVALID, "row model: iterations in 1 .. 8, rows >= 1, finite fy and cy");
+      prm = ProjRowModel{rm->fy, rm->cy, rm->rows, rm->iterations};
+    }
+    {
+      const double sg[4] = {noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
+      for (double x : sg)
+        if (!(x >= 0.0) || !std::isfinite(x)) return fail(CTVIO_ERR_INVALID, "a noise sigma is negative or not finite");
+    }
+    const int np = (int)np64, nq = (int)nq64;
+    const size_t npp = (size_t)np, nn = (size_t)nq;
+    const QueryOrder ordp(only, np, win, dev_.nwin);
+    if (!ordp.error().empty()) return fail(CTVIO_ERR_INVALID, "prediction: " + ordp.error());
+    std::vector<int64_t> first(npp + 1, 0);   // first sample of every prediction (the caller's order)
+    for (int i = 0; i < np; ++i) {
+      const int w = only >= 0 ? only : win[i];
+      const std::string what = "prediction " + std::to_string(i);
+      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, what + ": bias state out of range");
+      if (n_imu[i] < 1 || n_imu[i] > 4096) return fail(CTVIO_ERR_INVALID, what + ": 1 to 4096 samples");
+      const int64_t b = first[(size_t)i], e = b + n_imu[i];
+      first[(size_t)i + 1] = e;
+      for (int64_t j = b; j < e; ++j) {
+        if (j > b && imu_t[j] <= imu_t[j - 1]) return fail(CTVIO_ERR_INVALID, what + ": sample times not strictly increasing");
+        for (int c = 0; c < 3; ++c)
+          if (!std::isfinite(imu_gyro[3 * j + c]) || !std::isfinite(imu_acc[3 * j + c])) return fail(CTVIO_ERR_INVALID, what + ": a measurement is not finite");
+      }
+    }
+    const size_t ns = (size_t)first[npp];
+    if (ns > (size_t)1 << 30) return fail(CTVIO_ERR_INVALID, "more than 2^30 samples in one call");
+    std::vector<int32_t> pwin(nn), rank(npp);   // the window of every point; the sorted position of every prediction
+    for (int r = 0; r < np; ++r) rank[(size_t)ordp.slot[(size_t)r]] = r;
+    for (int i = 0; i < nq; ++i) {
+      const std::string what = "point " + std::to_string(i);
+      if (pred && (pred[i] < 0 || pred[i] >= np)) return fail(CTVIO_ERR_INVALID, what + ": prediction index out of range");
+      const int w = only >= 0 ? only : win[pred[i]];
+      pwin[(size_t)i] = w;
+      if (lmi[i] < 0 || lmi[i] >= meta_[w].L) return fail(CTVIO_ERR_INVALID, what + ": landmark index out of range");
+      if (obs2 && !(std::isfinite(obs2[2 * (size_t)i]) && std::isfinite(obs2[2 * (size_t)i + 1]))) return fail(CTVIO_ERR_INVALID, what + ": non-finite candidate point");
+    }
+    const QueryOrder ordq(only, nq, pwin.data(), dev_.nwin);
+    const bool want_cov = cov4 || chi2;
+    const size_t nc = want_cov ? nn : 0;
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ordq, PRJ_PER_TILE, 8) : std::vector<CovTile>();
+    // ---- io: start-time queries, propagation queries, samples, points, tiles (in, one staged copy); state16 | proj3 | cov4 | chi2 | row |
+    // status | the predictions' statuses (out, one copy).  scr: mask, exclusions, point records; start records, start states, Phi | N
+    CovScratch cs(want_cov, (size_t)dev_.Utot, sizeof(PredRec), nn);
+    CallLayout io = head_, &scr = cs.lay;
+    const int s_q = io.add("queries", sizeof(NavQuery), npp, false), s_pq = io.add("prop", sizeof(PropQuery), npp, false),
+              s_t = io.add("imu_t", sizeof(int64_t), ns, false), s_gyro = io.add("imu_gyro", sizeof(double), 3 * ns, false),
+              s_acc = io.add("imu_acc", sizeof(double), 3 * ns, false), s_pts = io.add("points", sizeof(PredPoint), nn, false),
+              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_state = io.add("state16", sizeof(double), 16 * npp, true),
+              s_proj = io.add("proj3", sizeof(double), 3 * nn, true), s_cov = io.add("cov4", sizeof(double), 4 * nc, true),
+              s_chi = io.add("chi2", sizeof(double), nc, true), s_row = io.add("row", sizeof(int32_t), nn, false),
+              s_stat = io.add("status", sizeof(int32_t), nn, false), s_pstat = io.add("pred_status", sizeof(int32_t), npp, false);
+    const int s_nrec = scr.add("start_records", sizeof(NavRec), want_cov ? npp : 0, false), s_x0 = scr.add("state0", sizeof(double), 16 * npp, true),
+              s_tr = scr.add("transition", sizeof(double), want_cov ? TRN_OUT * npp : 0, true);
+    if (const int rc = reserve_call(io, &scr)) return rc;
+    NavQuery *hq = io_host<NavQuery>(io, s_q);
+    PropQuery *hp = io_host<PropQuery>(io, s_pq);
+    for (int r = 0; r < np; ++r) {
+      const size_t i = (size_t)ordp.slot[(size_t)r];
+      const int w = ordp.win_of(r);
+      hq[r] = NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(imu_t[first[i]] - t0_[w])};
+      hp[r] = PropQuery{w, n_imu[i], (long long)first[i], (long long)r};
+    }
+    PredPoint *hpt = io_host<PredPoint>(io, s_pts);
+    for (int r = 0; r < nq; ++r) {
+      const size_t i = (size_t)ordq.slot[(size_t)r], pi = pred ? (size_t)pred[i] : 0;   // (pred null: the single-window entry's one prediction)
+      hpt[r] = PredPoint{ordq.win_of(r), rank[pi], lmi[i], row[i], (long long)(first[pi + 1] - 1), {obs2 ? obs2[2 * i] : 0.0, obs2 ? obs2[2 * i + 1] : 0.0}};
+    }
+    stage_tiles(io, -1, s_tiles, ordq, tiles);
+    std::memcpy(io_host<int64_t>(io, s_t), imu_t, sizeof(int64_t) * ns);
+    std::memcpy(io_host<double>(io, s_gyro), imu_gyro, sizeof(double) * 3 * ns);
+    std::memcpy(io_host<double>(io, s_acc), imu_acc, sizeof(double) * 3 * ns);
+    const ImuNoise nz{noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
+    double *x0 = scr.at<double>(call_scr_.dev, s_x0), *tr = scr.at<double>(call_scr_.dev, s_tr);
+    NavRec *nrec = scr.at<NavRec>(call_scr_.dev, s_nrec);
+    const size_t in_bytes = io.off(s_state) - io.off(s_q), out_bytes = io.bytes() - io.off(s_state);
+    auto start_states = [&](const uint8_t *excl) {
+      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(np, 64)), dim3(64), 0, stream_, dev_, np, io_dev<NavQuery>(io, s_q), excl, nrec, x0, io_dev<int32_t>(io, s_pstat));
+    };
+    auto transition = [&]() {
+      hipLaunchKernelGGL(k_imu_transition, dim3(nblk(np, 4)), dim3(64), 0, stream_, dev_, np, io_dev<PropQuery>(io, s_pq), io_dev<int32_t>(io, s_pstat),
+                         io_dev<long long>(io, s_t), io_dev<double>(io, s_gyro), io_dev<double>(io, s_acc), nz, want_cov ? 1 : 0, (const double *)x0,
+                         io_dev<double>(io, s_state), tr);
+    };
+    auto records = [&](const uint8_t *excl, PredRec *rec) {
+      hipLaunchKernelGGL(k_cov_pred_jac, dim3(nblk(nq, 64)), dim3(64), 0, stream_, dev_, nq, io_dev<PredPoint>(io, s_pts), excl, prm, io_dev<int32_t>(io, s_pstat),
+                         io_dev<double>(io, s_state), io_dev<double>(io, s_gyro), (const NavRec *)nrec, (const double *)tr, rec, io_dev<double>(io, s_proj),
+                         io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
+    };
+    if (!want_cov) {
+      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
+      start_states(nullptr);
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      transition();
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      records(nullptr, nullptr);
+      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), out_bytes, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      if (const int rc = sync_call()) return rc;
+      if (const int rc = span_timing({{2, EV_QUERY_END, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}})) return rc;
+    } else {
+      uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, cs.s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, cs.s_excl);
+      PredRec *drec = scr.at<PredRec>(call_scr_.dev, cs.s_rec);
+      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
+      Dev c;
+      if (const int rc = cov_factor(c, mask, excl)) return rc;
+      start_states(excl);
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
+      transition();
+      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
+      records(excl, drec);
+      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
+      CovSolveArgs<false, false, false, true> a;
+      a.tiles = io_dev<CovTile>(io, s_tiles); a.qrec = drec; a.qcov = io_dev<double>(io, s_cov);
+      if (chi2) a.chi2 = io_dev<double>(io, s_chi);
+      launch_cov_solve(c, tiles.size(), a);
+      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), out_bytes, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
+      if (const int rc = finish_call(io)) return rc;
+      if (const int rc = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_QUERY_END, EV_COV_GRAM},
+                                      {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
+        return rc;
+    }
+    // ---- results (not computable: NaN; a start time outside the spline: its state NaN)
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
+    const double *hstate = io_host<double>(io, s_state), *hproj = io_host<double>(io, s_proj), *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
+    const int32_t *hrow = io_host<int32_t>(io, s_row), *hstat = io_host<int32_t>(io, s_stat), *hps = io_host<int32_t>(io, s_pstat);
+    for (int r = 0; r < np && state16; ++r) {
+      double *o = state16 + 16 * (size_t)ordp.slot[(size_t)r];
+      if (hps[r] != POSE_OUTSIDE) std::memcpy(o, hstate + 16 * (size_t)r, sizeof(double) * 16);
+      else std::fill(o, o + 16, std::nan(""));
+    }
+    for (int r = 0; r < nq; ++r) {
+      const size_t i = (size_t)ordq.slot[(size_t)r];
+      const int st = want_cov ? merge_status(hstat[r], lm[ordq.win_of(r)].chol_fail != 0) : hstat[r];
+      if (cov4) cov_block(cov4 + 4 * i, hcov + 4 * (size_t)r, 2, st);
+      if (chi2) chi2[i] = gate_value(hchi[r], st);
+      if (proj3) std::memcpy(proj3 + 3 * i, hproj + 3 * (size_t)r, sizeof(double) * 3);
+      if (row_out) row_out[i] = hrow[r];
+      if (status) status[i] = st;
+    }
+    return CTVIO_OK;
+  }
   // ---------------------------------------------------------------------------------------- landmark depths
   // ctvio_triangulate_batch / ctvio_triangulate (single: window `only` alone) and ctvio_shift_anchor_batch: one kernel each
   // (csrc/kernels_tri.hpp) on the current state.  dev_, plan_ and the captured graph are not touched.
@@ -2235,6 +2402,22 @@ int32_t ctvio_project_landmarks(ctvio_solver *s, int32_t id, int32_t n, const in
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.project_landmarks(id, n, nullptr, lm, t_ns, row, rm, obs2, proj3, cov4, chi2, row_out, status);
+}
+int32_t ctvio_predict_landmarks_batch(ctvio_solver *s, int64_t n_pred, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t,
+                                      const double *imu_gyro, const double *imu_acc, const ctvio_imu_noise *noise, int64_t n_pts, const int32_t *pred,
+                                      const int32_t *lm, const int32_t *row, const ctvio_row_model *rm, const double *obs2, double *state16, double *proj3,
+                                      double *cov4, double *chi2, int32_t *row_out, int32_t *status) {
+  CHK_S;
+  return s->impl.predict_landmarks(-1, n_pred, win, frame, n_imu, imu_t, imu_gyro, imu_acc, noise, n_pts, pred, lm, row, rm, obs2, state16, proj3, cov4, chi2,
+                                   row_out, status);
+}
+int32_t ctvio_predict_landmarks(ctvio_solver *s, int32_t id, int32_t frame, int32_t m, const int64_t *imu_t, const double *imu_gyro, const double *imu_acc,
+                                const ctvio_imu_noise *noise, int32_t n_pts, const int32_t *lm, const int32_t *row, const ctvio_row_model *rm,
+                                const double *obs2, double *state16, double *proj3, double *cov4, double *chi2, int32_t *row_out, int32_t *status) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.predict_landmarks(id, 1, nullptr, frame >= 0 ? &frame : nullptr, &m, imu_t, imu_gyro, imu_acc, noise, n_pts, nullptr, lm, row, rm, obs2, state16,
+                                   proj3, cov4, chi2, row_out, status);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

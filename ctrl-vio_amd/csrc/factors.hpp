@@ -630,6 +630,56 @@ CTV_DI void imu_step(Q4 &q, V3 &p, V3 &v, V3 bg, V3 ba, V3 g, V3 w0, V3 a0, V3 w
   J.R1 = R1;
 }
 
+// A landmark seen from an IMU-PREDICTED pose beyond the spline (ctvio_predict_landmarks).  The end state (q, p, v) of the dead reckoning and
+// the last body rate w_e = gyro - bg are carried over the read-out of image row `row` at a constant rate, delta = row * line delay:
+//   R_I(tau) = R Exp(w_e delta),   p_I(tau) = p + delta v                                                       (pred_row_pose)
+// and the camera pose is T_I(tau) (q_CI, p_CI).  In the tangent of ctvio_imu_predict (dtheta, dp, dv, dbg, dba) the body pose at tau moves by
+//   B (6 x 15) = [[E^T, 0, 0, -delta Jr(w_e delta), 0], [0, I, delta I, 0, 0]],  E = Exp(w_e delta)   (pred_B: the blocks E^T and -delta Jr),
+// the camera pose by C_ext = [[R_CI^T, 0], [-R_I(tau) [p_CI]x, I]] times that (pred_Cext: the blocks R_CI^T and -R_I(tau) [p_CI]x, the
+// tangent map of pose_jac_T's extrinsic), and with dy = [y]x dtheta_C - R_C^T dp_C the image point by
+//   A (2 x 15, row-major) = Pi [[y]x, -R_C^T] C_ext B                                                           (pred_A).
+// delta = 0 gives E = Jr = I exactly and exact zeros in the velocity and gyro-bias columns.
+CTV_DI void pred_row_pose(Q4 q, V3 p, V3 v, V3 w_e, double delta, Q4 &q_I, V3 &p_I) {
+  q_I = qmul_unit(q, so3_exp(delta * w_e));
+  p_I = p + delta * v;
+}
+CTV_DI void pred_B(V3 w_e, double delta, M3 &Et, M3 &Bg) {
+  const M3 E = q2R(so3_exp(delta * w_e));
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Et.m[3 * i + j] = E.m[3 * j + i];
+  Bg = scale(so3_Jr(delta * w_e), -delta);
+}
+CTV_DI void pred_Cext(Q4 q_CI, V3 p_CI, Q4 q_I, M3 &Rt, M3 &X) {
+  const M3 R = q2R(q_CI);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rt.m[3 * i + j] = R.m[3 * j + i];
+  X = scale(mul_hat(q2R(q_I), p_CI), -1.0);
+}
+CTV_DI void pred_A(const ProjLin &L, V3 y, const M3 &Rt, const M3 &X, const M3 &Et, const M3 &Bg, double delta, double A[30]) {
+  const M3 Hy = hat(y);
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    double h[3], dth[3];   // row a of Pi [y]x, then of D_theta = Pi [y]x R_CI^T - M X (the camera-pose row against dtheta_I)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) h[c] = L.Pi[3 * a] * Hy.m[c] + L.Pi[3 * a + 1] * Hy.m[3 + c] + L.Pi[3 * a + 2] * Hy.m[6 + c];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      dth[c] = (h[0] * Rt.m[c] + h[1] * Rt.m[3 + c] + h[2] * Rt.m[6 + c]) - (L.M[3 * a] * X.m[c] + L.M[3 * a + 1] * X.m[3 + c] + L.M[3 * a + 2] * X.m[6 + c]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      A[15 * a + c] = dth[0] * Et.m[c] + dth[1] * Et.m[3 + c] + dth[2] * Et.m[6 + c];
+      A[15 * a + 3 + c] = -L.M[3 * a + c];
+      A[15 * a + 6 + c] = -(delta * L.M[3 * a + c]);
+      A[15 * a + 9 + c] = dth[0] * Bg.m[c] + dth[1] * Bg.m[3 + c] + dth[2] * Bg.m[6 + c];
+      A[15 * a + 12 + c] = 0.0;
+    }
+  }
+}
+
 // Streaming forms of the two views: the per-knot partial Jacobians are handed to `f(knot, J)` one at a time, as soon as they
 // are final, instead of being returned as four 3 x 3 matrices -- the same operations in the same order (bit-identical
 // values), but only ~5 matrices are live at any time (the array forms keep 11, i.e. ~200 fp64 registers for both ends).

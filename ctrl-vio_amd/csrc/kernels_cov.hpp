@@ -7,7 +7,9 @@
 // (ctvio_relative_pose_batch): k_cov_rel_jac (one record per query), then k_cov_solve on tiles of kind 5; predicted image points of landmarks
 // at query times with their 2 x 2 covariances and gates (ctvio_project_landmarks_batch): k_cov_proj_jac (one record per query), then
 // k_cov_solve on tiles of kind 6; body rates (angular velocity, specific force, body-frame velocity) with their 15 x 15 covariances and IMU
-// gates (ctvio_body_rates_batch): k_cov_rates_jac (one record per query), then k_cov_solve on tiles of kind 7.
+// gates (ctvio_body_rates_batch): k_cov_rates_jac (one record per query), then k_cov_solve on tiles of kind 7; image points of landmarks seen
+// from IMU-predicted poses beyond the spline (ctvio_predict_landmarks_batch): k_cov_nav_jac on the predictions' start times, k_imu_transition
+// (kernels_prop.hpp), k_cov_pred_jac (one record per point), then k_cov_solve on tiles of kind 8.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 // With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
@@ -28,6 +30,10 @@
 //                     delay (factors.hpp: proj_jac_T, proj_cols), j = d(proj) / drho_l,
 //   Sigma_rates(t, f) = (L^-1 J^T)^T (L^-1 J^T)                    for the 15 x P Jacobian J of (omega, specific force, body-frame velocity, bias state f)
 //                     at time t (factors.hpp: rates_jac_T; the bias rows are one-hot),
+//   Cov(pred)       = (L^-1 G)^T (L^-1 G) + j j^T / Hll_l + A N A^T  for the image point of landmark l seen from an IMU-predicted pose beyond the
+//                     spline: Cov(proj)'s identity with Jp over the knots of the anchor time, the knots of the prediction's start time and its
+//                     bias state (A Phi J_nav: the image point's row A pulled back through the propagation's transition Phi) and the line
+//                     delay (factors.hpp: pred_A), plus the propagation's process noise N through A,
 // so everything is a forward substitution Y = L^-1 B against many right-hand sides, 16 per workgroup, with Y resident in LDS.
 #pragma once
 
@@ -42,10 +48,11 @@ struct CovTile {
                     // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 5: the six columns of
                     // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5); 6: the two columns of G of up to eight
                     // projection queries of the window (columns 2 q, 2 q + 1); 7: the fifteen columns of J^T of one body-rates query (omega
-                    // 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused)
+                    // 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 8: the two
+                    // columns of G of up to eight points of ctvio_predict_landmarks_batch (columns 2 q, 2 q + 1)
   int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
-                    // kind 2, 5 and 6: the tile's first query record; kind 4 and 7: its query record
-  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4 and 7: 1; kind 6: queries (<= 8)
+                    // kind 2, 5, 6 and 8: the tile's first query record; kind 4 and 7: its query record
+  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4 and 7: 1; kind 6 and 8: queries (<= 8)
   long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -558,6 +565,163 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
   proj_cols(L, R_Ci, px, py, rho, y, q_CI, p_CI, (double)row_i, q2R(q_Ii), om_i, v_i, (double)row, q_Iq, om_q, v_q, r.j, r.jld);
 }
 
+// One point of ctvio_predict_landmarks_batch -- a landmark seen from an IMU-predicted pose beyond the spline --, grouped by window on the host,
+// and what k_cov_pred_jac makes of it.  The statuses are the projection entry's (PRJ_*).
+struct PredPoint {
+  int32_t win, pred, lm, row;   // pred: the point's prediction, in the sorted order of the predictions; lm: the caller's landmark index in the window;
+                                // row: the image row, or the first guess of the row iteration
+  long long last;               // the last sample of the prediction in the concatenated sample arrays (its gyro reading gives w_e)
+  double obs[2];                // the candidate point of the gate (zeros without one)
+};
+constexpr int TRN_OUT = 450;   // doubles k_imu_transition (kernels_prop.hpp) leaves per prediction: Phi (225, row-major) | N (225)
+struct PredRec {
+  int32_t status, s_a, nk_a, s_q, nk_q, wrow;   // ProjRec's, the "query time" being the prediction's start time imu_t[0]
+  int32_t frame, pad;                           // the prediction's bias state
+  double proj[2], obs[2];                       // the prediction as returned in proj3, the candidate point
+  double j[2], jld[2];                          // d(proj) / drho; d(proj) / d(line delay): the anchor's term + the read-out term (proj_cols)
+  double jt_a[48], jt_q[48];                    // Jp^T: the anchor block (proj_jac_T) over knots s_a .. s_a + 3; (A Phi J_nav)^T over knots s_q .. s_q + 3
+  double jb[12];                                // (A Phi)[:, 9:15]^T: the rows of the six bias unknowns of state `frame`
+  double ana[3];                                // A N A^T: entries (0,0), (0,1), (1,1)
+                                                // (j .. ana: written for PRJ_OK only)
+};
+
+// One lane per point.  pstat / xe / nrec / trans: per prediction, the status k_cov_nav_jac gave its start time, the end state k_imu_transition
+// left (untouched for POSE_OUTSIDE), the start state's record and Phi | N.  The anchor is read as k_cov_proj_jac reads it; the body pose at
+// the row time is pred_row_pose(end state, w_e = gyro[last] - bg, delta = (double)(row * ld_ns) * 1e-9), the camera pose that times (q_CI, p_CI),
+// y = R_C^T (X - p_C); with a row model the row is iterated first, exactly as there.  PRJ_NONE: the start time is outside the spline, the
+// landmark is not computable, or y.z <= 0 or y is not finite at any row visited: proj3 NaN, row_out -1.  The value is formed before excl is
+// looked at, by code the Jacobians do not share: the values-only call (excl null; recs, nrec, trans are not touched) gives it the same bits.
+// With excl (after k_cov_prepare): PRJ_NO_INFO where 1 / Hll == 0, an anchor knot has an unknown no factor touches, or the start state's
+// record says so (POSE_UNTOUCHED: its knots, knot s + 3 only where u > 0, and the bias state); otherwise the record: the anchor block and the
+// columns j, jld as k_cov_proj_jac forms them (the read-out term of jld with omega = w_e, v = the end velocity, R_I(tau)), A (pred_A),
+// M = A Phi, the start block M[:, 0:9] J_nav^T from the NavRec (pose rows jt, velocity rows cv), the bias rows M[:, 9:15] and A N A^T.
+__global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoint *qs, const uint8_t *excl, ProjRowModel rm, const int32_t *pstat, const double *xe,
+                                                     const double *gyro, const NavRec *nrec, const double *trans, PredRec *recs, double *proj3,
+                                                     int32_t *row_out, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PredPoint q = qs[i];
+  const int w = q.win;
+  const WinMeta &m = d.wins[w];
+  const int l = m.lm0 + q.lm;
+  const double rho = d.rho[l];
+  const int first = d.lm_vfirst[l], cnt = d.lm_vcnt[l];
+  bool ok = rho > 0.0 && isfinite(rho) && cnt > 0 && pstat[q.pred] != POSE_OUTSIDE;
+  int a0 = m.anc0;
+  if (cnt > 0) {
+    a0 = d.v_anc[first];
+    for (int j = 1; j < cnt; ++j) ok = ok && d.v_anc[first + j] == a0;
+  }
+  const int row_i = cnt > 0 ? d.a_row[a0] : 0;
+  const long long ld_ns = (long long)(d.ld[w] * 1e9);
+  const long long tau_i = cnt > 0 ? d.a_t[a0] + (long long)row_i * ld_ns : 0;
+  const double px = cnt > 0 ? d.a_obs[a0] : 0.0, py = cnt > 0 ? d.a_obs[(size_t)d.Atot + a0] : 0.0;
+  const Q4 q_CI = qmk(m.q_CI[0], m.q_CI[1], m.q_CI[2], m.q_CI[3]);
+  const V3 p_CI = mk(m.p_CI[0], m.p_CI[1], m.p_CI[2]);
+  SensorExt cam;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) cam.q[j] = m.q_CI[j];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) cam.p[j] = m.p_CI[j];
+  cam.on = 1;
+  int s_a, nk_a;
+  bool out_a;
+  Q4 q_Ci;
+  V3 p_Ci;
+  rel_side(d, m, tau_i, cam, nullptr, s_a, nk_a, out_a, q_Ci, p_Ci);
+  ok = ok && !out_a;
+  // the end state and the last body rate
+  const double *x = xe + 16 * (size_t)q.pred, *gl = gyro + 3 * q.last;
+  const V3 p_e = mk(x[0], x[1], x[2]), v_e = mk(x[7], x[8], x[9]);
+  const Q4 q_e = qmk(x[3], x[4], x[5], x[6]);
+  const V3 w_e = mk(gl[0] - x[10], gl[1] - x[11], gl[2] - x[12]);
+  int row = q.row;
+  double delta;
+  Q4 q_I, q_C;
+  V3 p_I, p_C, y;
+  for (int it = 0;; ++it) {
+    delta = (double)((long long)row * ld_ns) * 1e-9;
+    pred_row_pose(q_e, p_e, v_e, w_e, delta, q_I, p_I);
+    q_C = qmul(q_I, q_CI);
+    p_C = p_I + qrot(q_I, p_CI);
+    y = proj_point(q_Ci, p_Ci, q_C, p_C, px, py, rho);
+    ok = ok && y.z > 0.0 && isfinite(y.x) && isfinite(y.y) && isfinite(y.z);
+    if (it >= rm.iterations || !ok) break;
+    row = (int)fmin(fmax(rint(rm.fy * y.y / y.z + rm.cy), 0.0), (double)(rm.rows - 1));
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double zx = y.x / y.z, zy = y.y / y.z;
+  proj3[3 * (size_t)i] = ok ? zx : nan; proj3[3 * (size_t)i + 1] = ok ? zy : nan; proj3[3 * (size_t)i + 2] = ok ? y.z : nan;
+  row_out[i] = ok ? row : -1;
+  int status = ok ? PRJ_OK : PRJ_NONE;
+  if (!excl) {
+    status_out[i] = status;
+    return;
+  }
+  const int wrow = d.lm_pos[l];
+  const NavRec &nr = nrec[q.pred];
+  if (ok) {
+    if (d.dinv[m.lm0 + wrow] == 0.0) status = PRJ_NO_INFO;
+    for (int j = 6 * s_a; j < 6 * (s_a + nk_a); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
+    if (nr.status != POSE_OK) status = PRJ_NO_INFO;
+  }
+  PredRec &r = recs[i];
+  r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_q = ok ? nr.s : 0; r.nk_q = ok ? nr.nk : 3; r.wrow = wrow; r.frame = ok ? nr.frame : 0; r.pad = 0;
+  r.proj[0] = zx; r.proj[1] = zy; r.obs[0] = q.obs[0]; r.obs[1] = q.obs[1];
+  status_out[i] = status;
+  if (status != PRJ_OK) return;
+  const double z = 1.0 / rho;
+  const V3 x_c = mk(px * z, py * z, z);
+  const M3 R_Ci = q2R(q_Ci);
+  const ProjLin L = proj_lin(q_C, y);
+  {   // the anchor block and the two columns
+    double jp[144];
+    Q4 q_Ii;
+    V3 om_i, v_i;
+    proj_side(d, m, tau_i, q_CI, p_CI, jp, q_Ii, om_i, v_i);
+    proj_jac_T(L, false, R_Ci, x_c, y, jp, r.jt_a);
+    proj_cols(L, R_Ci, px, py, rho, y, q_CI, p_CI, (double)row_i, q2R(q_Ii), om_i, v_i, (double)row, q_I, w_e, v_e, r.j, r.jld);
+  }
+  double A[30], M[30];
+  {
+    M3 Et, Bg, Rt, X;
+    pred_B(w_e, delta, Et, Bg);
+    pred_Cext(q_CI, p_CI, q_I, Rt, X);
+    pred_A(L, y, Rt, X, Et, Bg, delta, A);
+  }
+  const double *Phi = trans + (size_t)TRN_OUT * q.pred, *N = Phi + 225;
+  double T[30];   // A N, then A N A^T
+#pragma unroll
+  for (int c = 0; c < 15; ++c) {
+    double m0 = 0.0, m1 = 0.0, t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+      const double ph = Phi[15 * k + c], nn = N[15 * k + c];
+      m0 += A[k] * ph; m1 += A[15 + k] * ph;
+      t0 += A[k] * nn; t1 += A[15 + k] * nn;
+    }
+    M[c] = m0; M[15 + c] = m1; T[c] = t0; T[15 + c] = t1;
+  }
+  double a00 = 0.0, a01 = 0.0, a11 = 0.0;
+#pragma unroll
+  for (int c = 0; c < 15; ++c) { a00 += T[c] * A[c]; a01 += T[c] * A[15 + c]; a11 += T[15 + c] * A[15 + c]; }
+  r.ana[0] = a00; r.ana[1] = a01; r.ana[2] = a11;
+  for (int rr = 0; rr < 24; ++rr) {   // (A Phi J_nav)^T over the knots of the start time: the pose rows, and on position unknowns the velocity rows
+    const double *jr = nr.jt + 6 * rr;
+    const int b = rr % 6 - 3;
+    const double cvk = nr.cv[rr / 6];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      double s = ((M[15 * a] * jr[0] + M[15 * a + 1] * jr[1]) + M[15 * a + 2] * jr[2]) + ((M[15 * a + 3] * jr[3] + M[15 * a + 4] * jr[4]) + M[15 * a + 5] * jr[5]);
+      if (b >= 0) s += (b == 0 ? M[15 * a + 6] : b == 1 ? M[15 * a + 7] : M[15 * a + 8]) * cvk;
+      r.jt_q[2 * rr + a] = s;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) { r.jb[2 * c] = M[9 + c]; r.jb[2 * c + 1] = M[24 + c]; }
+}
+
 // Y = L^-1 B for one tile of 16 right-hand sides.  d is the covariance's copy of Dev (d.active = the per-call mask).  Four waves: wave (h, kp)
 // owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of a half are added
 // in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row, as the back-substitution of the panel
@@ -586,14 +750,20 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
 // slot (null: not asked for).  One query per tile, kind 4's prologue with nine Jacobian columns and kind 4's Gram epilogue (cov_gram15);
 // then S = A C A^T + diag(sigma^2) from the block just written -- 21 lanes, every entry ((C[a][b] + C[a][9 + b]) + C[9 + a][b]) +
 // C[9 + a][9 + b] -- and one lane's 6 x 6 Cholesky factor and forward substitution in LDS: chi2 = |L^-1 e|^2, e = meas - z.
+// Kind 8 (the instantiation PRED = true, which holds no other kind and leaves the code of the other four what it was): prec = the records
+// (PredRec, in the order of the tiles), pose_cov = the 2 x 2 blocks and var_rho = the gates chi2 (null: not asked for), both by record.
+// Prologue: kind 6's, the "query rows" being (A Phi J_nav)^T over the knots of the prediction's start time -- where they overlap the anchor's
+// every entry is "anchor term + start term" in that order --, then the line-delay row and the six rows (A Phi)[:, 9:15]^T of the bias state.
+// Epilogue: kind 6's Gram entries, + j j^T / Hll, + A N A^T (the record's three entries) before mirroring; then kind 6's gate.
 // amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
 // SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
 // inlined as well.
 constexpr int COV_NT = 256;
-template <bool REL, bool PROJ = false, bool RATES = false> struct CovQueryRec { typedef PoseRec type; };
-template <> struct CovQueryRec<true, false, false> { typedef RelRec type; };
-template <> struct CovQueryRec<false, true, false> { typedef ProjRec type; };
-template <> struct CovQueryRec<false, false, true> { typedef RatesRec type; };
+template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false> struct CovQueryRec { typedef PoseRec type; };
+template <> struct CovQueryRec<true, false, false, false> { typedef RelRec type; };
+template <> struct CovQueryRec<false, true, false, false> { typedef ProjRec type; };
+template <> struct CovQueryRec<false, false, true, false> { typedef RatesRec type; };
+template <> struct CovQueryRec<false, false, false, true> { typedef PredRec type; };
 // The 120 unique entries of the 15 x 15 Gram block of a tile's columns 0..14 over the rows k0 .. P - 1 (kinds 4 and 7): every entry four
 // partial sums over the rows k = p mod 4, added in sequence, computed once and mirrored into the caller's block cov + 225 slot[0].  keep: lane
 // tid < 120 leaves its entry in part[tid] as well (entry (i >= j) at i (i + 1) / 2 + j; that lane alone has read part[tid]).
@@ -617,9 +787,9 @@ __device__ __forceinline__ void cov_gram15(const double *Ys, double *part, int k
     if (keep) part[tid] = v;
   }
 }
-template <bool REL, bool PROJ = false, bool RATES = false>
+template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false>
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const typename CovQueryRec<REL, PROJ, RATES>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
+                                                      const typename CovQueryRec<REL, PROJ, RATES, PRED>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
                                                       const NavRec *nrec, double *nav_cov) {
   const CovTile t = tiles[blockIdx.x];
   const int w = t.win;
@@ -635,7 +805,48 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
   for (int e = tid; e < 16 * PP; e += COV_NT) Ys[e] = 0.0;
   if (tid == 0) s_first = PP;
   __syncthreads();
-  if constexpr (RATES) {   // the nine columns of J^T over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the rows of bias state f, each
+  if constexpr (PRED) {
+    const int q = tid >> 4, sub = tid & 15;
+    if (q < t.count) {   // -(w_l / Hll) j^T: the row's planned span, then the line-delay column (kind 6's)
+      const PredRec &pr = prec[t.first + q];
+      const int row = m.lm0 + pr.wrow, klo = d.lm_klo[row], khi = d.lm_khi[row];
+      const double dv = d.dinv[row];
+      const double *Wr = d.WS[cur] + m.W0 + (long long)pr.wrow * m.ldw;
+      if (pr.status == PRJ_OK && khi >= klo && dv != 0.0) {
+        const double j0 = -pr.j[0], j1 = -pr.j[1];
+        const int cend = min(6 * khi + 6, P);
+        for (int c = 6 * klo + sub; c < cend; c += 16)
+          if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 2 * q] = v * j0; Ys[c * 16 + 2 * q + 1] = v * j1; }
+        if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
+          const double v = Wr[P - 1] * dv;
+          Ys[(P - 1) * 16 + 2 * q] = v * j0; Ys[(P - 1) * 16 + 2 * q + 1] = v * j1;
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < 48 * t.count; e += COV_NT) {   // + the anchor rows 6 s_a .. 6 (s_a + nk_a) - 1
+      const int qi = e / 48, r = (e % 48) / 2, a = e % 2;
+      const PredRec &pr = prec[t.first + qi];
+      if (pr.status == PRJ_OK && r < 6 * pr.nk_a && d.active[m.u0 + 6 * pr.s_a + r]) Ys[(6 * pr.s_a + r) * 16 + 2 * qi + a] += pr.jt_a[2 * r + a];
+    }
+    __syncthreads();
+    for (int e = tid; e < 62 * t.count; e += COV_NT) {   // + the rows of the start time 6 s_q .. 6 (s_q + nk_q) - 1 (r < 24), the line-delay row (r = 24),
+                                                         // the six rows of bias state `frame` (r = 25 .. 30)
+      const int qi = e / 62, r = (e % 62) / 2, a = e % 2;
+      const PredRec &pr = prec[t.first + qi];
+      if (pr.status != PRJ_OK) continue;
+      const int c = r < 24 ? 6 * pr.s_q + r : (r == 24 ? P - 1 : 6 * m.K + 6 * pr.frame + (r - 25));
+      if ((r < 6 * pr.nk_q || r >= 24) && d.active[m.u0 + c]) Ys[c * 16 + 2 * qi + a] += r < 24 ? pr.jt_q[2 * r + a] : (r == 24 ? pr.jld[a] : pr.jb[2 * (r - 25) + a]);
+    }
+    if (tid == 0)
+      for (int qi = 0; qi < t.count; ++qi) {
+        const PredRec &pr = prec[t.first + qi];
+        if (pr.status != PRJ_OK) continue;
+        const int row = m.lm0 + pr.wrow;
+        s_first = min(s_first, 6 * min(pr.s_a, pr.s_q));
+        if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
+      }
+  } else if constexpr (RATES) {   // the nine columns of J^T over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the rows of bias state f, each
                            // where the unknown is in the system
     const RatesRec &rr = prec[t.first];
     if (rr.status == POSE_OK) {
@@ -839,6 +1050,36 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
       for (int r = 0; r < 4; ++r) Ys[(32 * b + 16 * h + q4 + 4 * r) * 16 + l15] = yv[r];
     }
     __syncthreads();
+  }
+  if constexpr (PRED) {   // prediction tiles: kind 6's Gram epilogue, + A N A^T on the three unique entries, mirrored; then the gate
+    const int k0 = min(32 * b0, P);
+    constexpr int NE = 3 * PRJ_PER_TILE;
+    if (tid < 4 * NE) {
+      const int p = tid / NE, e = tid % NE, x = e % 3, ci = 2 * (e / 3) + (x == 2), cj = 2 * (e / 3) + (x != 0);
+      double s = 0.0;
+      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+      part[p * NE + e] = s;
+    }
+    __syncthreads();
+    if (tid < t.count) {
+      const PredRec &pr = prec[t.first + tid];
+      if (pr.status == PRJ_OK) {
+        const double dv = d.dinv[m.lm0 + pr.wrow];
+        double c[3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+          c[x] = ((((part[3 * tid + x] + part[NE + 3 * tid + x]) + part[2 * NE + 3 * tid + x]) + part[3 * NE + 3 * tid + x]) + (pr.j[x == 2] * pr.j[x != 0]) * dv) + pr.ana[x];
+        double *o = pose_cov + (long long)4 * (t.first + tid);
+        o[0] = c[0]; o[1] = c[1]; o[2] = c[1]; o[3] = c[2];
+        if (var_rho) {
+          const double iw2 = 1.0 / (m.img_w * m.img_w), e0 = pr.obs[0] - pr.proj[0], e1 = pr.obs[1] - pr.proj[1];
+          const double l00 = sqrt(c[0] + iw2), l10 = c[1] / l00, l11 = sqrt((c[2] + iw2) - l10 * l10);
+          const double z0 = e0 / l00, z1 = (e1 - l10 * z0) / l11;
+          var_rho[t.first + tid] = z0 * z0 + z1 * z1;
+        }
+      }
+    }
+    return;
   }
   if constexpr (RATES) {   // rates tiles: kind 4's 15 x 15 Gram block, then the gate of the IMU sample, one lane per tile
     const RatesRec &rr = prec[t.first];

@@ -480,6 +480,55 @@ class Solver:
         return self._imu_predict(lambda t, g, a, nz, lo, s, c, st: self._lib.ctvio_imu_predict(self._h, int(wid), f, int(m[0]), t, g, a, nz, lo, s, c, st),
                                  m, imu_t, gyro, acc, noise, last_only, cov)
 
+    def _predict_landmarks(self, call, n_pred, imu_t, gyro, acc, noise, lm, row, row_model, obs, cov, n_pts_expected=None):
+        t = np.ascontiguousarray(imu_t, np.int64).reshape(-1)
+        g = np.ascontiguousarray(gyro, np.float64).reshape(-1, 3)
+        a = np.ascontiguousarray(acc, np.float64).reshape(-1, 3)
+        li = np.ascontiguousarray(lm, np.int32).reshape(-1); r = np.ascontiguousarray(row, np.int32).reshape(-1)
+        n = int(li.shape[0])
+        o = None if obs is None else np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+        assert g.shape[0] == t.shape[0] and a.shape[0] == t.shape[0] and r.shape[0] == n and (o is None or o.shape[0] == n)
+        assert n_pts_expected is None or n_pts_expected == n
+        if o is not None and not cov:
+            raise ValueError("obs needs cov=True: the gate is formed from the covariance")
+        rm = None
+        if row_model is not None:
+            rm = row_model if isinstance(row_model, capi.RowModel) else capi.RowModel(float(row_model[0]), float(row_model[1]), int(row_model[2]), int(row_model[3]))
+        m = max(n, 1)
+        state = np.zeros((max(n_pred, 1), 16)); proj = np.zeros((m, 3)); c = np.zeros((m, 2, 2)) if cov else None
+        chi = np.zeros(m) if o is not None else None
+        ro = np.zeros(m, np.int32); st = np.zeros(m, np.int32)
+        capi.check(call(capi._p(t), capi._p(g), capi._p(a), C.byref(self._imu_noise(noise)), n, capi._p(li), capi._p(r),
+                        C.byref(rm) if rm is not None else None, capi._p(o) if o is not None else None, capi._p(state), capi._p(proj),
+                        capi._p(c) if cov else None, capi._p(chi) if chi is not None else None, capi._p(ro), capi._p(st)))
+        return SimpleNamespace(state=state[:n_pred].copy(), proj=proj[:n].copy(), cov=c[:n].copy() if cov else None,
+                               chi2=chi[:n].copy() if chi is not None else None, row=ro[:n].copy(), status=st[:n].copy())
+
+    def predict_landmarks_batch(self, win, frame, n_imu, imu_t, gyro, acc, pred, lm, row, noise=None, cov: bool = True, obs=None, row_model=None):
+        """ctvio_predict_landmarks_batch: where landmarks fall in the camera at IMU-predicted poses BEYOND the spline.  Predictions are the queries
+        of imu_predict_batch (win, frame or None, n_imu, the concatenated samples); point i = (prediction pred[i], landmark lm[i] of that
+        prediction's window, image row row[i]).  Returns a namespace like project_landmarks' (proj (n, 3), cov (n, 2, 2) or None, chi2 or None,
+        row, status) plus state (n_pred, 16): the end state of every prediction (imu_predict's with last_only).  The covariance carries the
+        window's uncertainty through the propagation (cross terms with the landmark included) plus the IMU process noise.  cov=False: values
+        only, nothing is linearised."""
+        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
+        m = np.ascontiguousarray(n_imu, np.int32).reshape(-1)
+        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
+        pi = np.ascontiguousarray(pred, np.int32).reshape(-1)
+        assert m.shape[0] == wi.shape[0] and (fr is None or fr.shape[0] == wi.shape[0])
+        npred = int(wi.shape[0])
+        return self._predict_landmarks(lambda t, g, a, nz, n, li, r, *rest: self._lib.ctvio_predict_landmarks_batch(
+            self._h, C.c_int64(npred), capi._p(wi), capi._p(fr), capi._p(m), t, g, a, nz, C.c_int64(n), capi._p(pi), li, r, *rest),
+            npred, imu_t, gyro, acc, noise, lm, row, row_model, obs, cov, int(pi.shape[0]))
+
+    def predict_landmarks(self, wid: int, frame, imu_t, gyro, acc, lm, row, noise=None, cov: bool = True, obs=None, row_model=None):
+        """ctvio_predict_landmarks: one prediction of window wid (frame None or -1: the newest bias state) with len(imu_t) samples and every
+        point under it; the batch entry's bits."""
+        m = int(np.asarray(imu_t).reshape(-1).shape[0])
+        f = -1 if frame is None else int(frame)
+        return self._predict_landmarks(lambda t, g, a, nz, n, li, r, *rest: self._lib.ctvio_predict_landmarks(
+            self._h, int(wid), f, m, t, g, a, nz, n, li, r, *rest), 1, imu_t, gyro, acc, noise, lm, row, row_model, obs, cov)
+
     def _tri_options(self, opts):
         o = capi.TriangulateOptions()
         self._lib.ctvio_default_triangulate_options(C.byref(o))

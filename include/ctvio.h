@@ -466,6 +466,60 @@ int32_t ctvio_imu_predict(ctvio_solver *s, int32_t id, int32_t frame, int32_t m,
                           const double *imu_acc, const ctvio_imu_noise *noise, int32_t last_only, double *state16, double *cov225,
                           int32_t *status);
 
+/* WHERE A LANDMARK FALLS IN THE NEXT IMAGE: ctvio_project_landmarks at an IMU-PREDICTED pose beyond the end of the spline.  A window's spline
+ * ends shortly after its newest frame, so the one frame a tracker needs seeding for -- the next one -- lies outside ctvio_project_landmarks'
+ * range; ctvio_imu_predict carries the state there but stops at the state, and the covariance of an image point needs the cross-covariance
+ * of the propagated pose and the landmark (shared anchor knots, line delay, inverse depth), which no entry returns.  This entry composes
+ * the two on the device.  The reference predicts the pose the same way (VisualOdometry::ProcessIMU) and has no covariance for the point.
+ * PREDICTIONS (n_pred) are exactly the queries of ctvio_imu_predict_batch: prediction k = (window win[k], bias state frame[k], frame == NULL:
+ * F - 1, n_imu[k] samples), the samples concatenated in prediction order, the same refusals.  POINTS (n_pts): point i = (prediction pred[i],
+ * landmark lm[i] in the caller's landmark order of that prediction's window, image row row[i]); many points normally share a prediction.
+ * End state: (R, p, v, bg, ba) at t_e = imu_t[m - 1] is ctvio_imu_predict's with last_only, the same bits; state16 (n_pred x 16, or NULL)
+ * returns it (NaN where imu_t[0] is outside the spline).  w_e = the last sample's gyro reading - bg (m = 1: sample 0).
+ * Pose at the row time -- a STATED MODEL, a constant-rate extrapolation over the read-out, the acceleration term a delta^2 / 2 neglected:
+ *   delta = (double)(row * (int64)(ld * 1e9)) * 1e-9,   R_I(tau) = R Exp(w_e delta),   p_I(tau) = p + delta v,   T_C = T_I(tau) (q_CI, p_CI).
+ * Value: X the world point of ctvio_landmark_points (same anchor rules), y = R_C^T (X - p_C), proj3 = (y.x / y.z, y.y / y.z, y.z).
+ *   rm: the row iteration of ctvio_project_landmarks (1 .. 8 iterations; value and Jacobian at the final row, returned in row_out).
+ *   cov4 (n_pts x 4, row-major 2 x 2, symmetric to the bit, or NULL): with Pi as in ctvio_project_landmarks, E = Exp(w_e delta),
+ *     B (6 x 15) = [[E^T, 0, 0, -delta Jr(w_e delta), 0], [0, I, delta I, 0, 0]]   (the body pose at tau against the tangent of ctvio_imu_predict),
+ *     C_ext = the body -> camera tangent map of ctvio_pose_covariance (dtheta_C = R_CI^T dtheta_I, dp_C = dp_I - R_I(tau) [p_CI]x dtheta_I),
+ *     A (2 x 15) = Pi [[y]x, -R_C^T] C_ext B,   Phi = F_{m-1} ... F_1 the product of ctvio_imu_predict's exact step Jacobians (m = 1: I),
+ *     J_nav = the 15 rows of ctvio_nav_state at (imu_t[0], frame),   Jp = A Phi J_nav + Pi R_C^T Jp_X,
+ *   Jp_X the point Jacobian of ctvio_landmark_points with its line-delay column; the line-delay column additionally gets
+ *   row Pi ([y]x R_CI^T w_e - R_C^T (v + R_I(tau) [w_e]x p_CI)), the formal derivative of the read-out;  j = Pi R_C^T (-R_Ci p_i / rho^2).  Then
+ *     G = Jp^T - w_l j^T / h_l  (rows of excluded unknowns zero),   Cov = G^T Sigma_pp G + j j^T / h_l + A N A^T,
+ *   H, the exclusions and Sigma_pp exactly those of ctvio_covariance_batch; N the process noise of the propagation, N_j = F N_{j-1} F^T +
+ *   G Q G^T from N_0 = 0 (ctvio_imu_predict's recurrence with a zero start).  Cross terms between the propagated pose and the landmark are
+ *   included; the row is treated as given; constant unknowns contribute nothing.
+ *   chi2 (n_pts doubles, or NULL; requires obs2, n_pts x 2): e^T (Cov + I / img_w^2)^-1 e, e = obs - proj.xy, formed on the device from the
+ *   very bits that are returned, as in ctvio_project_landmarks.
+ *   status (n_pts entries, or NULL) per point, in this precedence: 3 imu_t[0] of its prediction outside [t0, t0 + (K - 3) dt), the landmark
+ *   not computable (ctvio_landmark_points status 3), y.z <= 0 or non-finite at any row visited: everything NaN, row_out -1;  2 Hll_l == 0, or
+ *   a non-constant unknown no factor touches under the anchor knots, the knots of imu_t[0] (knot s + 3 only where u > 0) or the chosen bias
+ *   state: value valid, +inf on the diagonal, 0 elsewhere, chi2 = 0;  1 bad pivot in the window's factorisation: value valid, covariance and
+ *   chi2 NaN;  0 ok.  With cov4 == NULL and chi2 == NULL nothing is linearised or factored, statuses 1 and 2 cannot occur, and the values
+ *   have the bits of the covariance call's.
+ * The single-window entry is one prediction of window id (frame -1: the newest bias state) with every point under it: the batch entry's bits.
+ * The call returns CTVIO_OK for every status, and for n_pred == 0 or n_pts == 0, where it launches nothing.  CTVIO_ERR_STATE before the
+ * upload; CTVIO_ERR_INVALID for every refusal of ctvio_imu_predict_batch (window id or frame out of range, a count < 0, NULL sample arrays or
+ * noise, m outside 1 .. 4096, sample times not strictly increasing, a non-finite measurement, a negative or non-finite sigma), pred[i] outside
+ * [0, n_pred), a landmark index out of range for its prediction's window, a NULL pred / lm / row, all of proj3 / cov4 / chi2 / state16 NULL,
+ * chi2 without obs2, a non-finite obs2, a bad rm; the handle stays usable.  The state, the launch plan and the captured graph of the solve are
+ * left as they were; no atomics: where the linearisation is order-fixed (opt.deterministic) the bits of a point depend on its own arguments
+ * and its prediction's samples alone -- not on the entry, the order of points or predictions, which points share a tile or call, or which
+ * optional outputs were asked for.
+ * ctvio_last_timing: ms8[0..2] = k_cov_prepare, k_cov_solve, k_cov_pred_jac, ms8[3] = k_imu_transition, ms8[7] the whole call; values only:
+ * ms8[2], ms8[3] and ms8[7]. */
+int32_t ctvio_predict_landmarks_batch(ctvio_solver *s, int64_t n_pred, const int32_t *win, const int32_t *frame, const int32_t *n_imu,
+                                      const int64_t *imu_t, const double *imu_gyro, const double *imu_acc, const ctvio_imu_noise *noise,
+                                      int64_t n_pts, const int32_t *pred, const int32_t *lm, const int32_t *row, const ctvio_row_model *rm,
+                                      const double *obs2, double *state16, double *proj3, double *cov4, double *chi2, int32_t *row_out,
+                                      int32_t *status);
+int32_t ctvio_predict_landmarks(ctvio_solver *s, int32_t id, int32_t frame, int32_t m, const int64_t *imu_t, const double *imu_gyro,
+                                const double *imu_acc, const ctvio_imu_noise *noise, int32_t n_pts, const int32_t *lm, const int32_t *row,
+                                const ctvio_row_model *rm, const double *obs2, double *state16, double *proj3, double *cov4, double *chi2,
+                                int32_t *row_out, int32_t *status);
+
 /* Landmark depths on the device, at the CURRENT state: what FeatureManager::triangulate gives a window to start from (called from
  * VisualOdometry::AddImageToWindow, visual_odometry.cpp:174-193; feature_manager.cpp:226-274) and what removeBackShiftDepth does to them after
  * a slide (feature_manager.cpp:341-381, visual_odometry.cpp:299-308). */
@@ -604,6 +658,9 @@ int32_t ctvio_set_profiling(ctvio_solver *s, int32_t on);
  * After a body-rates call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution, the 15 x 15 blocks and the gates),
  * k_cov_rates_jac, ms8[7] = the whole call on the device, the rest zero; values only (cov225 == NULL and chi2 == NULL): ms8[2] = device time
  * of k_cov_rates_jac, ms8[7] = the whole call on the device (its copies included), the rest zero.
+ * After a landmark-prediction call: ms8[0..2] = device time of k_cov_prepare, k_cov_solve (substitution, the 2 x 2 blocks and the gates),
+ * k_cov_pred_jac, ms8[3] = device time of k_imu_transition, ms8[7] = the whole call on the device, the rest zero; values only (cov4 == NULL
+ * and chi2 == NULL): ms8[2], ms8[3] and ms8[7].
  * After a triangulation or anchor-shift call: ms8[0] = device time of k_triangulate / k_shift_anchor, ms8[7] = the whole call on the device
  * (its copies included), the rest zero. */
 int32_t ctvio_last_timing(ctvio_solver *s, double *ms8, int32_t *launches8);

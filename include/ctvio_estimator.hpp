@@ -747,6 +747,57 @@ class TrajectoryEstimator {
     for (int32_t v : st) if (v != 0) return false;
     return true;
   }
+  // Where landmarks fall in the NEXT image, beyond the solved knots (ctvio_predict_landmarks): PredictIMUStates' dead reckoning through
+  // `samples` (samples[0] inside the solved knots, the newest frame time in the reference's use; bias_gyr as there) composed with
+  // ProjectLandmarks at the predicted pose.  Point i = (the inverse-depth pointer, image row).  end (optional): the predicted state at the last
+  // sample; proj3, cov4, obs2 + chi2, rm, row_out, status: as in ProjectLandmarks -- the covariance carries the window's uncertainty through the
+  // propagation, the cross terms with the landmark and the IMU process noise.  Returns false if any status is not 0.
+  struct PredictionPoint { const double *inv_depth; int32_t row; };
+  bool PredictLandmarks(const std::vector<IMUData> &samples, const double *bias_gyr, const ctvio_imu_noise &noise, const std::vector<PredictionPoint> &points,
+                        std::vector<double> &proj3, std::vector<double> *cov4 = nullptr, const std::vector<double> *obs2 = nullptr,
+                        std::vector<double> *chi2 = nullptr, const ctvio_row_model *rm = nullptr, std::vector<int32_t> *row_out = nullptr,
+                        std::vector<int32_t> *status = nullptr, IMUState *end = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t m = samples.size(), n = points.size();
+    if ((chi2 != nullptr) != (obs2 != nullptr) || (obs2 && obs2->size() != 2 * n)) throw std::invalid_argument("PredictLandmarks: obs2 (2 per point) and chi2 come together");
+    int32_t frame = -1;
+    if (bias_gyr) {
+      auto it = bias_of_.find(bias_gyr);
+      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("PredictLandmarks: not a bias state of this window");
+      frame = pk.bias_map[(size_t)it->second];
+    }
+    std::vector<int64_t> t(m);
+    std::vector<double> gyro(3 * m), acc(3 * m);
+    for (size_t j = 0; j < m; ++j) {
+      t[j] = samples[j].timestamp;
+      for (int c = 0; c < 3; ++c) { gyro[3 * j + c] = samples[j].gyro[c]; acc[3 * j + c] = samples[j].accel[c]; }
+    }
+    std::vector<int32_t> lm(n), row(n), st(n, 0), ro(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      auto it = lm_of_.find(points[i].inv_depth);
+      if (it == lm_of_.end() || pk.lm_map[(size_t)it->second] < 0) throw std::invalid_argument("PredictLandmarks: not a landmark of this window");
+      lm[i] = pk.lm_map[(size_t)it->second]; row[i] = points[i].row;
+    }
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    double state16[16] = {0};
+    proj3.assign(3 * n, 0.0);
+    if (cov4) cov4->assign(4 * n, 0.0);
+    if (chi2) chi2->assign(n, 0.0);
+    check(ctvio_predict_landmarks(s, 0, frame, (int32_t)m, t.data(), gyro.data(), acc.data(), &noise, (int32_t)n, lm.data(), row.data(), rm,
+                                  obs2 ? obs2->data() : nullptr, state16, proj3.data(), cov4 ? cov4->data() : nullptr, chi2 ? chi2->data() : nullptr,
+                                  ro.data(), st.data()));
+    if (end && m) {
+      end->timestamp = t[m - 1];
+      for (int c = 0; c < 3; ++c) { end->p[c] = state16[c]; end->v[c] = state16[7 + c]; }
+      for (int c = 0; c < 4; ++c) end->q[c] = state16[3 + c];
+    }
+    if (row_out) *row_out = ro;
+    if (status) *status = st;
+    for (int32_t v : st) if (v != 0) return false;
+    return true;
+  }
 
  private:
   // One packed window: only the knots the factors touch (the reference registers exactly those with Ceres,
