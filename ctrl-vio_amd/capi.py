@@ -86,6 +86,10 @@ class RowModel(C.Structure):
     _fields_ = [("fy", C.c_double), ("cy", C.c_double), ("rows", C.c_int32), ("iterations", C.c_int32)]
 
 
+class GateOptions(C.Structure):
+    _fields_ = [("min_redundancy", C.c_double)]
+
+
 # every symbol include/ctvio.h declares (tests check the .so exports all of them)
 SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "ctvio_device_count", "ctvio_create",
            "ctvio_destroy", "ctvio_clear", "ctvio_add_window", "ctvio_upload", "ctvio_set_batch", "ctvio_num_windows", "ctvio_solve",
@@ -97,6 +101,7 @@ SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "
            "ctvio_relative_pose_batch", "ctvio_relative_pose", "ctvio_project_landmarks_batch", "ctvio_project_landmarks",
            "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict", "ctvio_body_rates_batch", "ctvio_body_rates",
            "ctvio_predict_landmarks_batch", "ctvio_predict_landmarks",
+           "ctvio_default_gate_options", "ctvio_visual_gate_batch", "ctvio_visual_gate",
            "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
 _lib = None
@@ -163,6 +168,10 @@ def load_library():
                                                       [C.POINTER(RowModel)] + [C.c_void_p] * 7)
         lib.ctvio_predict_landmarks.argtypes = ([C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.POINTER(ImuNoise), C.c_int32] +
                                                 [C.c_void_p] * 2 + [C.POINTER(RowModel)] + [C.c_void_p] * 7)
+        lib.ctvio_default_gate_options.argtypes = [C.POINTER(GateOptions)]
+        lib.ctvio_default_gate_options.restype = None
+        lib.ctvio_visual_gate_batch.argtypes = [C.c_void_p, C.POINTER(GateOptions)] + [C.c_void_p] * 9
+        lib.ctvio_visual_gate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GateOptions)] + [C.c_void_p] * 9
         lib.ctvio_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
         lib.ctvio_default_triangulate_options.restype = None
         lib.ctvio_triangulate_batch.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p]

@@ -59,6 +59,7 @@ struct DebugSwitches {
   int marg_host = 0;         // CTVIO_MARG_HOST=1        ctvio_marginalize on the host factorisation
   int marg_blocked = 0;      // CTVIO_MARG_BLOCKED=1     ctvio_marginalize_batch: every window through the blocked path (csrc/marg_blocked.hpp)
   int shard_oversubscribe = 0;   // CTVIO_SHARD_OVERSUBSCRIBE=1  TEST ONLY: more shards than devices (ctvio_shards_used)
+  int gate_slice = 0;        // CTVIO_GATE_SLICE=n       TEST ONLY: ctvio_visual_gate_batch slices its windows at n block slots (host_pack.hpp: GATE_SLICE_SLOTS)
   int poison = 0;            // CTVIO_POISON=1/2         TEST ONLY: reused double scratch starts as quiet NaN / 2.6e151 at every use; the
                              //                          upload checks that the packer writes every staged byte (host_pack.hpp: check_staging)
 };
@@ -68,7 +69,8 @@ static DebugSwitches read_debug_switches() {
       {"CTVIO_DEBUG_STAMPS", &g.stamps}, {"CTVIO_SPLIT_LINEARIZE", &g.split_linearize},
       {"CTVIO_SCHUR_COPY_PLAIN", &g.schur_copy_plain}, {"CTVIO_CHOL_TILES", &g.chol_tiles}, {"CTVIO_CHOL_COMPACT", &g.chol_compact}, {"CTVIO_DENSE", &g.dense},
       {"CTVIO_SCHUR_TILE2", &g.schur_tile2}, {"CTVIO_MARG_DEBUG", &g.marg_debug}, {"CTVIO_MARG_HOST", &g.marg_host},
-      {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}, {"CTVIO_POISON", &g.poison}};
+      {"CTVIO_MARG_BLOCKED", &g.marg_blocked}, {"CTVIO_SHARD_OVERSUBSCRIBE", &g.shard_oversubscribe}, {"CTVIO_POISON", &g.poison},
+      {"CTVIO_GATE_SLICE", &g.gate_slice}};
   for (const auto &t : tab)
     if (const char *e = std::getenv(t.name)) *t.dst = (e[0] == '\0') ? 1 : std::atoi(e);   // (set but empty counts as 1)
   return g;
@@ -139,6 +141,7 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     return CTVIO_OK;
   }
   int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
@@ -235,6 +238,12 @@ class SolverImpl {
     }
     const InputPtrs hp = lay.at(in_.host), dp = lay.at(in_.dev);
     h_lm_pos_ = hp.lm_pos; h_ld_ = StatePtrs(hp.state, b).ld;
+    // the block slot of every caller's block (visual_gate: the upload sorts the blocks landmark-major), window after window
+    gate_voff_.assign((size_t)nw + 1, 0);
+    for (int wi = 0; wi < nw; ++wi) gate_voff_[(size_t)wi + 1] = gate_voff_[(size_t)wi] + (size_t)meta_[wi].V;
+    gate_slot_.resize(gate_voff_[(size_t)nw]);
+    for (int wi = 0; wi < nw; ++wi)
+      for (int v = 0; v < meta_[wi].V; ++v) gate_slot_[gate_voff_[(size_t)wi] + (size_t)v] = meta_[wi].vis0 + tmp[wi].vpos[(size_t)v];
     // ---- device pointers of the input arena
     Dev &d = dev_;
     std::memset(&d, 0, sizeof d);
@@ -1267,23 +1276,25 @@ class SolverImpl {
   size_t cov_solve_lds() const { return ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double); }   // Ys | part (k_cov_solve)
   // k_cov_solve's arguments by name; what a call does not use stays null.  The template arguments are the kernel's (they choose the type
   // of the query records).  sel: the selections of covariance(), the output slots of the queries elsewhere.
-  template <bool REL = false, bool PROJ = false, bool RATES = false, bool PRED = false> struct CovSolveArgs {
+  template <bool REL = false, bool PROJ = false, bool RATES = false, bool PRED = false, bool GATE = false> struct CovSolveArgs {
     const CovTile *tiles = nullptr;
     const int32_t *sel = nullptr;
     double *Y = nullptr, *var_rho = nullptr;
     double *chi2 = nullptr;                                            // the gates of the PROJ / RATES / PRED queries
-    const typename CovQueryRec<REL, PROJ, RATES, PRED>::type *qrec = nullptr;   // pose, relative-pose, projection, rates or prediction records
+    const typename CovQueryRec<REL, PROJ, RATES, PRED, GATE>::type *qrec = nullptr;   // pose, relative-pose, projection, rates, prediction or block records
     double *qcov = nullptr;
     const PointRec *lrec = nullptr;
     double *lm_cov = nullptr;
     int lm_base = 0;
     const NavRec *nrec = nullptr;
     double *nav_cov = nullptr;
+    GateOut gate{};   // GATE: the outputs by block slot; lm_base is the slice's first slot
   };
-  template <bool REL, bool PROJ, bool RATES, bool PRED> void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveArgs<REL, PROJ, RATES, PRED> &a) {
+  template <bool REL, bool PROJ, bool RATES, bool PRED, bool GATE>
+  void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveArgs<REL, PROJ, RATES, PRED, GATE> &a) {
     // (the PROJ / RATES / PRED instantiations have no landmark tiles: the kernel takes their gates in the position of var_rho)
-    hipLaunchKernelGGL((k_cov_solve<REL, PROJ, RATES, PRED>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a.tiles, a.sel, a.Y,
-                       PROJ || RATES || PRED ? a.chi2 : a.var_rho, a.qrec, a.qcov, a.lrec, a.lm_cov, a.lm_base, a.nrec, a.nav_cov);
+    hipLaunchKernelGGL((k_cov_solve<REL, PROJ, RATES, PRED, GATE>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a.tiles, a.sel, a.Y,
+                       PROJ || RATES || PRED ? a.chi2 : a.var_rho, a.qrec, a.qcov, a.lrec, a.lm_cov, a.lm_base, a.nrec, a.nav_cov, a.gate);
   }
   // the device times of a call between pairs of its events (the stream is idle): ms[slot] of ctvio_last_timing, one launch each
   struct Span { int slot; Ev begin, end; };
@@ -1326,7 +1337,7 @@ class SolverImpl {
     const size_t in_bytes = io.off(s_out) - io.off(s_in), out_bytes = io.bytes() - io.off(s_out);
     if (!scr) {
       HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
+      if (in_bytes) HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
       HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
       jac((const uint8_t *)nullptr, (Rec *)nullptr);
       HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
@@ -1337,7 +1348,7 @@ class SolverImpl {
     }
     uint8_t *mask = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_mask), *excl = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_excl);
     Rec *rec = scr->lay.at<Rec>(call_scr_.dev, scr->s_rec);
-    HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
+    if (in_bytes) HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
     Dev c;
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     jac((const uint8_t *)excl, rec);
@@ -1908,6 +1919,109 @@ class SolverImpl {
     }
     return CTVIO_OK;
   }
+  // ctvio_visual_gate_batch / ctvio_visual_gate (only >= 0: that window alone): the leave-one-out test of every visual block of the windows
+  // themselves.  No inputs: k_cov_gate_jac reads the block slots the upload holds and writes by slot; the host scatters into the caller's
+  // block order (gate_slot_).  Values only (redundancy, cov4, chi2 and lm_stats3 null): k_cov_gate_jac alone (and k_cov_gate_reduce for
+  // lm_count), nothing is linearised or factored.  Otherwise run_query: one factorisation, then per slice of windows (plan_gate_slices: the
+  // record scratch is bounded) k_cov_gate_jac and k_cov_solve on tiles of kind 9 -- the first slice's record kernel where run_query times
+  // it (ms[2]), the later slices' inside ms[1] --, then k_cov_gate_reduce (ms[3]).  dev_, plan_ and the captured graph are not touched.
+  int visual_gate(int only, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *red, double *cov4, double *chi2, int32_t *status,
+                  double *lm_stats3, int32_t *lm_count) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (!o) return fail(CTVIO_ERR_INVALID, "null options");
+    if (!(o->min_redundancy > 0.0 && o->min_redundancy < 1.0)) return fail(CTVIO_ERR_INVALID, "min_redundancy outside (0, 1)");
+    const int wbeg = only >= 0 ? only : 0, wend = only >= 0 ? only + 1 : dev_.nwin;
+    const int s0 = meta_[wbeg].vis0, nslot = meta_[wend - 1].vis0 + meta_[wend - 1].Vp - s0, l0 = meta_[wbeg].lm0;
+    const size_t v0 = gate_voff_[(size_t)wbeg], V = gate_voff_[(size_t)wend] - v0;
+    size_t L = 0;
+    for (int w = wbeg; w < wend; ++w) L += (size_t)meta_[w].L;
+    if (V && !res2 && !weight && !depth && !red && !cov4 && !chi2 && !status && !lm_stats3 && !lm_count) return fail(CTVIO_ERR_INVALID, "every output is null");
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    if (V == 0) {   // (nothing is launched; a landmark without blocks: count 0 and (NaN, 0, +inf))
+      for (size_t l = 0; l < L; ++l) {
+        if (lm_count) lm_count[l] = 0;
+        if (lm_stats3) { lm_stats3[3 * l] = nan; lm_stats3[3 * l + 1] = 0.0; lm_stats3[3 * l + 2] = inf; }
+      }
+      return CTVIO_OK;
+    }
+    const bool full = red || cov4 || chi2 || lm_stats3, want_lm = lm_stats3 || lm_count;
+    std::vector<int32_t> wslots((size_t)dev_.nwin);
+    for (int w = 0; w < dev_.nwin; ++w) wslots[(size_t)w] = meta_[w].Vp;
+    const std::vector<GateSlice> slices = plan_gate_slices(wslots.data(), wbeg, wend, dbg_.gate_slice > 0 ? (size_t)dbg_.gate_slice : GATE_SLICE_SLOTS);
+    size_t nrec = 0;
+    for (const GateSlice &sl : slices) nrec = std::max(nrec, (size_t)sl.slots);
+    // ---- out, by block slot: res2 | weight | depth | redundancy | cov4 | chi2 | status, then by landmark: lm_stats3 | lm_count; no inputs
+    const size_t ns = (size_t)nslot, nf = full ? ns : 0, nl = want_lm ? L : 0;
+    CovScratch scr(full, (size_t)dev_.Utot, sizeof(GateRec), nrec);
+    const int s_en = scr.lay.add("enorm", sizeof(double), lm_stats3 ? ns : 0, true);
+    CallLayout io = head_;
+    const int s_res = io.add("res2", sizeof(double), 2 * ns, true), s_wgt = io.add("weight", sizeof(double), ns, true),
+              s_dep = io.add("depth", sizeof(double), ns, true), s_red = io.add("redundancy", sizeof(double), nf, true),
+              s_cov = io.add("cov4", sizeof(double), 4 * nf, true), s_chi = io.add("chi2", sizeof(double), nf, true),
+              s_stat = io.add("status", sizeof(int32_t), ns, false), s_lms = io.add("lm_stats3", sizeof(double), lm_stats3 ? 3 * L : 0, true),
+              s_lmc = io.add("lm_count", sizeof(int32_t), nl, false);
+    if (const int rc = reserve_call(io, full ? &scr.lay : nullptr)) return rc;
+    GateOut out{io_dev<double>(io, s_res), io_dev<double>(io, s_wgt), io_dev<double>(io, s_dep), lm_stats3 ? scr.lay.at<double>(call_scr_.dev, s_en) : nullptr,
+                full ? io_dev<double>(io, s_red) : nullptr, full ? io_dev<double>(io, s_cov) : nullptr, full ? io_dev<double>(io, s_chi) : nullptr,
+                io_dev<int32_t>(io, s_stat), s0, 0, o->min_redundancy};
+    auto slot_range = [&](const GateSlice &sl, int &first, int &n) { first = meta_[sl.wbeg].vis0; n = (int)sl.slots; };
+    auto reduce = [&]() {
+      if (want_lm)
+        hipLaunchKernelGGL(k_cov_gate_reduce, dim3(nblk((int)L, 64)), dim3(64), 0, stream_, dev_, l0, (int)L, out, full ? 1 : 0,
+                           lm_stats3 ? io_dev<double>(io, s_lms) : nullptr, io_dev<int32_t>(io, s_lmc));
+    };
+    hipError_t ev_err = hipSuccess;
+    const int rc = run_query<GateRec>(
+        io, s_res, s_res, full ? &scr : nullptr,
+        [&](const uint8_t *excl, GateRec *rec) {
+          int first = s0, n = nslot;
+          if (excl) slot_range(slices[0], first, n);
+          if (n) hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, excl, rec, out);
+          if (!excl) reduce();
+        },
+        [&](const Dev &c, const GateRec *rec) {
+          for (size_t si = 0; si < slices.size(); ++si) {
+            int first, n;
+            slot_range(slices[si], first, n);
+            if (!n) continue;
+            if (si) hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, scr.lay.at<uint8_t>(call_scr_.dev, scr.s_excl), const_cast<GateRec *>(rec), out);
+            CovSolveArgs<false, false, false, false, true> a;
+            a.qrec = rec; a.lm_base = first; a.gate = out; a.gate.nslot = n;
+            launch_cov_solve(c, (size_t)nblk(n, PRJ_PER_TILE), a);
+          }
+          ev_err = hipEventRecord(ev_[EV_QUERY_BEGIN], stream_);
+          reduce();
+          if (ev_err == hipSuccess) ev_err = hipEventRecord(ev_[EV_QUERY_END], stream_);
+        });
+    if (rc) return rc;
+    HIPCHK(ev_err);
+    if (full)
+      if (const int rc2 = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
+        return rc2;
+    // ---- results, in the caller's block order.  Precedence 3, 2, 1 (the window's factorisation failed), 4, 0.
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
+    const double *hres = io_host<double>(io, s_res), *hwgt = io_host<double>(io, s_wgt), *hdep = io_host<double>(io, s_dep), *hred = io_host<double>(io, s_red),
+                 *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    for (int w = wbeg; w < wend; ++w) {
+      const bool bad = full && lm[w].chol_fail != 0;
+      for (size_t b = gate_voff_[(size_t)w]; b < gate_voff_[(size_t)w + 1]; ++b) {
+        const size_t i = b - v0, k = (size_t)(gate_slot_[b] - s0);
+        int st = hstat[k];
+        if (bad && (st == PRJ_OK || st == GATE_WEAK)) st = PRJ_SINGULAR;
+        if (res2) { res2[2 * i] = hres[2 * k]; res2[2 * i + 1] = hres[2 * k + 1]; }
+        if (weight) weight[i] = hwgt[k];
+        if (depth) depth[i] = hdep[k];
+        if (red) red[i] = st == PRJ_OK || st == GATE_WEAK ? hred[k] : (st == PRJ_NO_INFO ? 0.0 : nan);
+        if (cov4) cov_block(cov4 + 4 * i, hcov + 4 * k, 2, st == GATE_WEAK ? (int)QUERY_NO_INFO : st);
+        if (chi2) chi2[i] = gate_value(hchi[k], st == GATE_WEAK ? (int)QUERY_NO_INFO : st);
+        if (status) status[i] = st;
+      }
+    }
+    if (lm_stats3) std::memcpy(lm_stats3, io_host<double>(io, s_lms), sizeof(double) * 3 * L);
+    if (lm_count) std::memcpy(lm_count, io_host<int32_t>(io, s_lmc), sizeof(int32_t) * L);
+    return CTVIO_OK;
+  }
   // ctvio_predict_landmarks_batch / ctvio_predict_landmarks (only >= 0: every prediction belongs to that window, win is not read): where
   // landmark lm[i] falls in the camera at the IMU-predicted pose of prediction pred[i], row row[i], beyond the spline, with its 2 x 2
   // covariance and gate.  The predictions are imu_predict()'s queries (grouped by window, stable), the points are grouped by the window of
@@ -2239,6 +2353,8 @@ class SolverImpl {
   LaunchPlan graph_plan_;
   bool snap_valid_ = false;
   const double *h_ld_ = nullptr;        // the line delays as uploaded (same arena)
+  std::vector<int32_t> gate_slot_;   // [sum V] the absolute block slot of every caller's block, window after window (gate_voff_: nwin + 1 offsets)
+  std::vector<size_t> gate_voff_;
   const int32_t *h_lm_pos_ = nullptr;   // host mirror of Dev::lm_pos (inside in_.host: valid while the batch is uploaded)
 };
 
@@ -2418,6 +2534,20 @@ int32_t ctvio_predict_landmarks(ctvio_solver *s, int32_t id, int32_t frame, int3
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.predict_landmarks(id, 1, nullptr, frame >= 0 ? &frame : nullptr, &m, imu_t, imu_gyro, imu_acc, noise, n_pts, nullptr, lm, row, rm, obs2, state16,
                                    proj3, cov4, chi2, row_out, status);
+}
+void ctvio_default_gate_options(ctvio_gate_options *o) {
+  if (!o) return;
+  o->min_redundancy = 0.01;
+}
+int32_t ctvio_visual_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *redundancy, double *cov4,
+                                double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count) {
+  CHK_S; return s->impl.visual_gate(-1, o, res2, weight, depth, redundancy, cov4, chi2, status, lm_stats3, lm_count);
+}
+int32_t ctvio_visual_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *redundancy, double *cov4,
+                          double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.visual_gate(id, o, res2, weight, depth, redundancy, cov4, chi2, status, lm_stats3, lm_count);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

@@ -558,6 +558,26 @@ inline void cov_block(double *o, const double *computed, int dim, int st) {
 // the caller's gate by status, likewise: no information gates nothing
 inline double gate_value(double computed, int st) { return st == QUERY_OK ? computed : (st == QUERY_NO_INFO ? 0.0 : std::nan("")); }
 
+// ctvio_visual_gate_batch writes one record per block slot (kernels_cov.hpp: GateRec, about 0.9 KB) and a large batch holds 10^6 of them, so
+// the records of a call live in a scratch of bounded size and the windows are walked in slices.  GATE_SLICE_SLOTS: 65536 slots, 57 MB of
+// records -- 8192 tiles of k_cov_solve per slice, four times what the 256 CUs of an MI355X hold at eight workgroups each, so a slice still
+// fills the device and its two launches (a few microseconds) are noise against the substitution; and small against HBM, which the
+// batch's normal equations already share.
+constexpr size_t GATE_SLICE_SLOTS = 65536;
+struct GateSlice { int32_t wbeg, wend; int64_t slots; };   // windows [wbeg, wend) and their block slots (padding included)
+// The slices of windows [wbeg, wend) with slots[w] block slots each: consecutive whole windows, as many as stay within `budget` slots; a
+// window beyond the budget is alone in its slice; a window without slots rides with its predecessor (with its successor at the very
+// beginning).  Every window is in exactly one slice, in order; no slice is empty of windows.
+inline std::vector<GateSlice> plan_gate_slices(const int32_t *slots, int wbeg, int wend, size_t budget) {
+  std::vector<GateSlice> out;
+  for (int w = wbeg; w < wend; ++w) {
+    const int64_t n = slots[w];
+    if (out.empty() || (n > 0 && out.back().slots > 0 && (size_t)(out.back().slots + n) > budget)) out.push_back(GateSlice{w, w + 1, n});
+    else { out.back().wend = w + 1; out.back().slots += n; }
+  }
+  return out;
+}
+
 // The input arena (pinned host mirror + device), every segment ONCE: X(element type, segment, Dev member, allocated count, filled count).
 // An empty set keeps one entry allocated.  The names stand for BatchFacts members (layout_input).  Irregular: `state` is the contiguous
 // block quat | pos | bias | rho | ld (StatePtrs); vrow / vrow_off hold one unused entry unless the row walk is uploaded, and Dev gets null.

@@ -49,7 +49,8 @@ struct CovTile {
                     // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5); 6: the two columns of G of up to eight
                     // projection queries of the window (columns 2 q, 2 q + 1); 7: the fifteen columns of J^T of one body-rates query (omega
                     // 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 8: the two
-                    // columns of G of up to eight points of ctvio_predict_landmarks_batch (columns 2 q, 2 q + 1)
+                    // columns of G of up to eight points of ctvio_predict_landmarks_batch (columns 2 q, 2 q + 1); 9: kind 6's columns for eight
+                    // consecutive block slots of the window (ctvio_visual_gate_batch; built in the kernel, not listed)
   int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
                     // kind 2, 5, 6 and 8: the tile's first query record; kind 4 and 7: its query record
   int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4 and 7: 1; kind 6 and 8: queries (<= 8)
@@ -485,11 +486,8 @@ __device__ inline void proj_side(const Dev &d, const WinMeta &m, long long tau, 
 // same bits.  With excl (after k_cov_prepare) the status and the record: PRJ_NO_INFO where 1 / Hll == 0 (d.dinv) or a knot either time
 // depends on has an unknown no factor touches (COV_UNTOUCHED; decided on the exclusion flags and on u > 0, never on a Jacobian entry).  The
 // anchor block is formed in the 144-double pose buffer and stored, then the buffer is reused for the query block.
-__global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQuery *qs, const uint8_t *excl, ProjRowModel rm, ProjRec *recs, double *proj3,
-                                                     int32_t *row_out, int32_t *status_out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const ProjQuery q = qs[i];
+// (The lane's work is proj_query, shared with k_cov_gate_jac: out3 = the query's proj3, the return value its status; r is written with excl only.)
+__device__ __forceinline__ int proj_query(const Dev &d, const ProjQuery &q, const uint8_t *excl, const ProjRowModel &rm, ProjRec *rp, double *out3, int &row_o) {
   const int w = q.win;
   const WinMeta &m = d.wins[w];
   const int l = m.lm0 + q.lm;
@@ -531,13 +529,10 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
   }
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const double zx = y.x / y.z, zy = y.y / y.z;
-  proj3[3 * (size_t)i] = ok ? zx : nan; proj3[3 * (size_t)i + 1] = ok ? zy : nan; proj3[3 * (size_t)i + 2] = ok ? y.z : nan;
-  row_out[i] = ok ? row : -1;
+  out3[0] = ok ? zx : nan; out3[1] = ok ? zy : nan; out3[2] = ok ? y.z : nan;
+  row_o = ok ? row : -1;
   int status = ok ? PRJ_OK : PRJ_NONE;
-  if (!excl) {
-    status_out[i] = status;
-    return;
-  }
+  if (!excl) return status;
   const int wrow = d.lm_pos[l];
   if (ok) {
     if (d.dinv[m.lm0 + wrow] == 0.0) status = PRJ_NO_INFO;
@@ -546,11 +541,10 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
     for (int j = 6 * s_q; j < 6 * (s_q + nk_q); ++j)
       if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
   }
-  ProjRec &r = recs[i];
+  ProjRec &r = *rp;
   r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_q = s_q; r.nk_q = nk_q; r.wrow = wrow;
   r.proj[0] = zx; r.proj[1] = zy; r.obs[0] = q.obs[0]; r.obs[1] = q.obs[1];
-  status_out[i] = status;
-  if (status != PRJ_OK) return;
+  if (status != PRJ_OK) return status;
   const double z = 1.0 / rho;
   const V3 x_c = mk(px * z, py * z, z);
   const M3 R_Ci = q2R(q_Ci);
@@ -563,6 +557,106 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
   proj_side(d, m, tau_q, q_CI, p_CI, jp, q_Iq, om_q, v_q);
   proj_jac_T(L, true, R_Ci, x_c, y, jp, r.jt_q);
   proj_cols(L, R_Ci, px, py, rho, y, q_CI, p_CI, (double)row_i, q2R(q_Ii), om_i, v_i, (double)row, q_Iq, om_q, v_q, r.j, r.jld);
+  return status;
+}
+__global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQuery *qs, const uint8_t *excl, ProjRowModel rm, ProjRec *recs, double *proj3,
+                                                     int32_t *row_out, int32_t *status_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double o[3];
+  int row;
+  const int status = proj_query(d, qs[i], excl, rm, excl ? recs + i : nullptr, o, row);
+  proj3[3 * (size_t)i] = o[0]; proj3[3 * (size_t)i + 1] = o[1]; proj3[3 * (size_t)i + 2] = o[2];
+  row_out[i] = row;
+  status_out[i] = status;
+}
+
+// One visual block of the window itself (ctvio_visual_gate_batch) and what k_cov_gate_jac makes of it: the projection record of the query
+// (landmark, t_j, row_j) with obs = p_j, the whitened residual before the loss r = img_w (proj - p_j), the loss weight rho'(|r|^2) and the
+// corrector S (symmetric 2 x 2: entries (0,0), (0,1), (1,1)) as vis_block_eval (factors.hpp) applies it to the block's Jacobian rows:
+// S = sqrt(rho') (I - alpha r r^T / s) with Ceres' rule alpha = 0 where s == 0 or rho'' <= 0 -- which the Cauchy loss always meets, so that
+// S = sqrt(rho') I here; the general form is kept so that the epilogue does not depend on the loss.
+enum { GATE_WEAK = 4 };   // ctvio.h: redundancy < min_redundancy (the statuses below it are PRJ_*)
+struct GateRec : ProjRec {
+  double r[2], weight, S[3];
+};
+// What the gate's kernels write per block slot (absolute slot - slot0; null: not asked for) and the threshold of GATE_WEAK.
+struct GateOut {
+  double *res2, *weight, *depth, *enorm;   // enorm: |res2| / img_w = |proj - p_j|, the unwhitened reprojection error (for the landmark mean)
+  double *red, *cov4, *chi2;
+  int32_t *status;
+  int32_t slot0, nslot;   // the outputs' first slot; the slots of the slice k_cov_solve runs over (from its lm_base on)
+  double min_red;
+};
+// One lane per block slot e = first + i of the slice (records by i, outputs by e - slot0).  A padding slot (v_win < 0) gets a PRJ_NONE
+// record and nothing else.  The value comes from proj_query, so it has the bits of the values-only call (excl null: no records).
+__global__ __launch_bounds__(64) void k_cov_gate_jac(Dev d, int first, int n, const uint8_t *excl, GateRec *recs, GateOut o) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int e = first + i, w = d.v_win[e];
+  if (w < 0) {
+    if (excl) { recs[i].status = PRJ_NONE; recs[i].wrow = 0; }
+    return;
+  }
+  const WinMeta &m = d.wins[w];
+  const double pjx = d.v_obs[e], pjy = d.v_obs[(size_t)d.Vtot + e], ca = d.v_cauchy[e];
+  const ProjQuery q{w, d.v_lm[e], d.v_rowj[e], 0, (long long)d.v_tj[e], {pjx, pjy}};
+  const ProjRowModel rm{0.0, 0.0, 1, 0};
+  double p3[3];
+  int row;
+  const int status = proj_query(d, q, excl, rm, excl ? recs + i : nullptr, p3, row);
+  // (a status-3 block: p3 is NaN and so is everything below)
+  const double ex = p3[0] - pjx, ey = p3[1] - pjy, r0 = m.img_w * ex, r1 = m.img_w * ey;
+  const double s = r0 * r0 + r1 * r1;
+  double wgt = 1.0, sq = 1.0, asq = 0.0;
+  if (ca > 0.0) {
+    const double cc = 1.0 / (ca * ca), inv = 1.0 / (1.0 + s * cc), rho2 = -cc * inv * inv;
+    wgt = inv;
+    sq = sqrt(inv);
+    if (!(s == 0.0 || rho2 <= 0.0)) asq = (1.0 - sqrt(fmax(0.0, 1.0 + 2.0 * s * rho2 / inv))) / s;
+  }
+  if (status == PRJ_NONE) wgt = p3[0];   // (NaN, also without a loss)
+  const size_t k = (size_t)(e - o.slot0);
+  if (o.res2) { o.res2[2 * k] = r0; o.res2[2 * k + 1] = r1; }
+  if (o.weight) o.weight[k] = wgt;
+  if (o.depth) o.depth[k] = p3[2];
+  // (from the residual as returned, every operation rounded once: the landmark mean can be re-derived from res2 to the summation order)
+  if (o.enorm) o.enorm[k] = __ddiv_rn(__dsqrt_rn(__dadd_rn(__dmul_rn(r0, r0), __dmul_rn(r1, r1))), m.img_w);
+  o.status[k] = status;
+  if (!excl) return;
+  GateRec &g = recs[i];
+  g.r[0] = r0; g.r[1] = r1; g.weight = wgt;
+  g.S[0] = sq * (1.0 - asq * r0 * r0); g.S[1] = sq * (-asq * r0 * r1); g.S[2] = sq * (1.0 - asq * r1 * r1);
+}
+
+// One lane per landmark of windows wbeg .. (the caller's order; outputs by landmark - lm_base): over its blocks lm_vfirst .. + lm_vcnt in
+// slot order -- the upload's packed order, so the bits are the window's -- the count of the blocks whose status is not 3, the mean of their
+// |proj - p_j|, the largest chi2 of its status-0 blocks (0: none) and the smallest redundancy of its blocks of status 0 or 4 (+inf: none).
+// A window whose factorisation failed (chol_fail; full: the call factored) has neither.  stats3 null: the count alone.
+__global__ __launch_bounds__(64) void k_cov_gate_reduce(Dev d, int lm_base, int n, GateOut o, int full, double *stats3, int32_t *count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int l = lm_base + i, first = d.lm_vfirst[l], cnt = d.lm_vcnt[l];
+  const bool bad = full && d.lm[d.lm_win[l]].chol_fail != 0;
+  int c = 0;
+  double sum = 0.0, cmax = 0.0, rmin = __builtin_inf();
+  for (int j = 0; j < cnt; ++j) {
+    const size_t k = (size_t)(first + j - o.slot0);
+    const int st = o.status[k];
+    if (st == PRJ_NONE) continue;
+    ++c;
+    if (!stats3) continue;
+    sum = __dadd_rn(sum, o.enorm[k]);
+    if (bad) continue;
+    if (st == PRJ_OK) cmax = fmax(cmax, o.chi2[k]);
+    if (st == PRJ_OK || st == GATE_WEAK) rmin = fmin(rmin, o.red[k]);
+  }
+  count[i] = c;
+  if (stats3) {
+    stats3[3 * (size_t)i] = c ? sum / (double)c : __longlong_as_double(0x7ff8000000000000ll);
+    stats3[3 * (size_t)i + 1] = cmax;
+    stats3[3 * (size_t)i + 2] = rmin;
+  }
 }
 
 // One point of ctvio_predict_landmarks_batch -- a landmark seen from an IMU-predicted pose beyond the spline --, grouped by window on the host,
@@ -755,15 +849,22 @@ __global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoi
 // Prologue: kind 6's, the "query rows" being (A Phi J_nav)^T over the knots of the prediction's start time -- where they overlap the anchor's
 // every entry is "anchor term + start term" in that order --, then the line-delay row and the six rows (A Phi)[:, 9:15]^T of the bias state.
 // Epilogue: kind 6's Gram entries, + j j^T / Hll, + A N A^T (the record's three entries) before mirroring; then kind 6's gate.
+// Kind 9 (the instantiation GATE = true, which holds no other kind and leaves the code of the other five what it was): the visual blocks of
+// the windows themselves (ctvio_visual_gate_batch).  No tile list: tile b is the eight block slots lm_base + 8 b .. + 7 of the slice, prec =
+// their records (GateRec, by slot of the slice; a padding slot's says PRJ_NONE), gate = the outputs by absolute slot.  Kind 6's prologue and
+// Gram entries, whitened: Cw = img_w^2 C.  Then, with the record's corrector S: T = Cw S, A = S T, redundancy = lambda_min(I - A) in closed
+// form; below gate.min_red the status becomes GATE_WEAK, else C_loo = Cw + T (I - A)^-1 T^T (three unique entries, mirrored) and
+// chi2 = r^T (C_loo + I)^-1 r by the 2 x 2 Cholesky factor from the values just written.
 // amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
 // SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
 // inlined as well.
 constexpr int COV_NT = 256;
-template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false> struct CovQueryRec { typedef PoseRec type; };
-template <> struct CovQueryRec<true, false, false, false> { typedef RelRec type; };
-template <> struct CovQueryRec<false, true, false, false> { typedef ProjRec type; };
-template <> struct CovQueryRec<false, false, true, false> { typedef RatesRec type; };
-template <> struct CovQueryRec<false, false, false, true> { typedef PredRec type; };
+template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false, bool GATE = false> struct CovQueryRec { typedef PoseRec type; };
+template <> struct CovQueryRec<true, false, false, false, false> { typedef RelRec type; };
+template <> struct CovQueryRec<false, true, false, false, false> { typedef ProjRec type; };
+template <> struct CovQueryRec<false, false, true, false, false> { typedef RatesRec type; };
+template <> struct CovQueryRec<false, false, false, true, false> { typedef PredRec type; };
+template <> struct CovQueryRec<false, false, false, false, true> { typedef GateRec type; };
 // The 120 unique entries of the 15 x 15 Gram block of a tile's columns 0..14 over the rows k0 .. P - 1 (kinds 4 and 7): every entry four
 // partial sums over the rows k = p mod 4, added in sequence, computed once and mirrored into the caller's block cov + 225 slot[0].  keep: lane
 // tid < 120 leaves its entry in part[tid] as well (entry (i >= j) at i (i + 1) / 2 + j; that lane alone has read part[tid]).
@@ -787,11 +888,13 @@ __device__ __forceinline__ void cov_gram15(const double *Ys, double *part, int k
     if (keep) part[tid] = v;
   }
 }
-template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false>
+template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false, bool GATE = false>
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const typename CovQueryRec<REL, PROJ, RATES, PRED>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
-                                                      const NavRec *nrec, double *nav_cov) {
-  const CovTile t = tiles[blockIdx.x];
+                                                      const typename CovQueryRec<REL, PROJ, RATES, PRED, GATE>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
+                                                      const NavRec *nrec, double *nav_cov, GateOut gate) {
+  // (GATE: no tile list -- tile b is the block slots lm_base + 8 b .. + 7, which lie in one window: a window's slots start on a group of 64)
+  const CovTile t = GATE ? CovTile{d.vb_win[(lm_base + PRJ_PER_TILE * (int)blockIdx.x) / 64], 9, PRJ_PER_TILE * (int)blockIdx.x, min(PRJ_PER_TILE, gate.nslot - PRJ_PER_TILE * (int)blockIdx.x), 0}
+                         : tiles[blockIdx.x];
   const int w = t.win;
   const WinMeta &m = d.wins[w];
   const int P = m.P, ldh = m.ldh, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -859,7 +962,7 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
       }
       if (tid == 0) s_first = 6 * rr.s;
     }
-  } else if constexpr (PROJ) {
+  } else if constexpr (PROJ || GATE) {
     const int q = tid >> 4, sub = tid & 15;
     if (q < t.count) {   // -(w_l / Hll) j^T: the row's planned span, then the line-delay column
       const ProjRec &pr = prec[t.first + q];
@@ -1112,6 +1215,49 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         chi += zj * zj;
       }
       var_rho[sel[t.first]] = chi;
+    }
+    return;
+  }
+  if constexpr (GATE) {   // block tiles: kind 6's Gram entries, then the leave-one-out epilogue of ctvio_visual_gate_batch, one lane per block
+    const int k0 = min(32 * b0, P);
+    constexpr int NE = 3 * PRJ_PER_TILE;
+    if (tid < 4 * NE) {
+      const int p = tid / NE, e = tid % NE, x = e % 3, ci = 2 * (e / 3) + (x == 2), cj = 2 * (e / 3) + (x != 0);
+      double s = 0.0;
+      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+      part[p * NE + e] = s;
+    }
+    __syncthreads();
+    if (tid < t.count) {
+      const GateRec &pr = prec[t.first + tid];
+      if (pr.status == PRJ_OK) {
+        const double dv = d.dinv[m.lm0 + pr.wrow], w2 = m.img_w * m.img_w;
+        double c[3];   // Cw = img_w^2 C
+#pragma unroll
+        for (int x = 0; x < 3; ++x)
+          c[x] = w2 * ((((part[3 * tid + x] + part[NE + 3 * tid + x]) + part[2 * NE + 3 * tid + x]) + part[3 * NE + 3 * tid + x]) + (pr.j[x == 2] * pr.j[x != 0]) * dv);
+        const double s00 = pr.S[0], s01 = pr.S[1], s11 = pr.S[2];
+        // T = Cw S, A = S T, M = I - A
+        const double t00 = c[0] * s00 + c[1] * s01, t01 = c[0] * s01 + c[1] * s11, t10 = c[1] * s00 + c[2] * s01, t11 = c[1] * s01 + c[2] * s11;
+        const double m00 = 1.0 - (s00 * t00 + s01 * t10), m01 = -(s00 * t01 + s01 * t11), m11 = 1.0 - (s01 * t01 + s11 * t11);
+        const double hd = 0.5 * (m00 - m11), red = 0.5 * (m00 + m11) - sqrt(hd * hd + m01 * m01);
+        const size_t k = (size_t)(lm_base + t.first + tid - gate.slot0);
+        if (gate.red) gate.red[k] = red;
+        if (!(red >= gate.min_red)) {
+          gate.status[k] = GATE_WEAK;   // (cov4 and chi2 are the host's fill)
+        } else {
+          // C_loo = Cw + T M^-1 T^T: U = T M^-1, the three unique entries of U T^T
+          const double idet = 1.0 / (m00 * m11 - m01 * m01);
+          const double u00 = (t00 * m11 - t01 * m01) * idet, u01 = (t01 * m00 - t00 * m01) * idet, u10 = (t10 * m11 - t11 * m01) * idet, u11 = (t11 * m00 - t10 * m01) * idet;
+          const double l0 = c[0] + (u00 * t00 + u01 * t01), l1 = c[1] + (u00 * t10 + u01 * t11), l2 = c[2] + (u10 * t10 + u11 * t11);
+          if (gate.cov4) { double *o = gate.cov4 + 4 * k; o[0] = l0; o[1] = l1; o[2] = l1; o[3] = l2; }
+          if (gate.chi2) {   // r^T (C_loo + I)^-1 r by the 2 x 2 Cholesky factor, from the values just written
+            const double f00 = sqrt(l0 + 1.0), f10 = l1 / f00, f11 = sqrt((l2 + 1.0) - f10 * f10);
+            const double z0 = pr.r[0] / f00, z1 = (pr.r[1] - f10 * z0) / f11;
+            gate.chi2[k] = z0 * z0 + z1 * z1;
+          }
+        }
+      }
     }
     return;
   }

@@ -429,6 +429,35 @@ class Solver:
         """ctvio_project_landmarks: the same for queries of window wid alone (same bits as the batch entry)."""
         return self._project_landmarks(lambda n, *a: self._lib.ctvio_project_landmarks(self._h, int(wid), n, *a), lm, t_ns, row, row_model, obs, cov)
 
+    def _visual_gate(self, call, wids, cov, min_redundancy):
+        o = capi.GateOptions()
+        self._lib.ctvio_default_gate_options(C.byref(o))
+        if min_redundancy is not None:
+            o.min_redundancy = float(min_redundancy)
+        V = sum(int(self.windows[w].V) for w in wids); L = sum(int(self.windows[w].L) for w in wids)
+        m, ml = max(V, 1), max(L, 1)
+        res = np.zeros((m, 2)); wgt = np.zeros(m); dep = np.zeros(m); st = np.zeros(m, np.int32); cnt = np.zeros(ml, np.int32)
+        red = np.zeros(m) if cov else None; c = np.zeros((m, 2, 2)) if cov else None; chi = np.zeros(m) if cov else None
+        lms = np.zeros((ml, 3)) if cov else None
+        opt = lambda a: capi._p(a) if a is not None else None
+        capi.check(call(C.byref(o), capi._p(res), capi._p(wgt), capi._p(dep), opt(red), opt(c), opt(chi), capi._p(st), opt(lms), capi._p(cnt)))
+        cut = lambda a, n: a[:n].copy() if a is not None else None
+        return SimpleNamespace(res=cut(res, V), weight=cut(wgt, V), depth=cut(dep, V), redundancy=cut(red, V), cov=cut(c, V), chi2=cut(chi, V),
+                               status=cut(st, V), lm_stats=cut(lms, L), lm_count=cut(cnt, L))
+
+    def visual_gate_batch(self, cov: bool = True, min_redundancy=None):
+        """ctvio_visual_gate_batch: the leave-one-out test of every visual block of the uploaded windows at the current state, window after
+        window in the caller's block order.  Returns a namespace: res (V, 2) the whitened residual before the loss, weight the loss weight
+        rho', depth, redundancy = lambda_min(I - A), cov (V, 2, 2) the whitened leave-one-out prediction covariance, chi2 = r^T (cov + I)^-1 r
+        (2 degrees of freedom), status (0 ok, 1 singular window, 2 no information, 3 not computable, 4 redundancy < min_redundancy),
+        lm_stats (L, 3) = (mean |proj - p_j|, largest chi2, smallest redundancy) and lm_count per landmark.  cov=False: values only
+        (redundancy, cov, chi2 and lm_stats None), nothing is linearised or factored."""
+        return self._visual_gate(lambda *a: self._lib.ctvio_visual_gate_batch(self._h, *a), range(len(self.windows)), cov, min_redundancy)
+
+    def visual_gate(self, wid: int, cov: bool = True, min_redundancy=None):
+        """ctvio_visual_gate: the same for window wid alone (same bits as the batch entry)."""
+        return self._visual_gate(lambda *a: self._lib.ctvio_visual_gate(self._h, int(wid), *a), [int(wid)], cov, min_redundancy)
+
     def _imu_noise(self, noise):
         o = capi.ImuNoise()
         self._lib.ctvio_default_imu_noise(C.byref(o))

@@ -419,6 +419,52 @@ int32_t ctvio_project_landmarks(ctvio_solver *s, int32_t id, int32_t n, const in
                                 const ctvio_row_model *rm, const double *obs2,
                                 double *proj3, double *cov4, double *chi2, int32_t *row_out, int32_t *status);
 
+/* AFTER THE SOLVE, WHICH OBSERVATIONS ARE OUTLIERS: the leave-one-out (deleted) innovation test of every visual block of the windows
+ * themselves.  ctvio_project_landmarks' gate is for NEW matches; an observation that is already a block of the window is correlated with the
+ * estimate.  Here the block's own information is taken out of the normal matrix, the observation is predicted from everything else, and the
+ * residual is gated against that prediction's covariance plus the measurement noise -- a 2 x 2 Woodbury correction per block on top of Sigma
+ * of the full system, no second factorisation, and well defined under the Cauchy loss.
+ * There are no query inputs: the blocks are the window's own, as uploaded.  Per-block outputs hold sum V entries (batch) or V entries
+ * (single window), window after window and in the CALLER'S block order (ctvio_window.v_*); per-landmark outputs sum L or L entries in the
+ * caller's landmark order.  Any output may be NULL.  Per block b = (l, t_j, row_j, p_j) at the CURRENT state, a_b = v_cauchy[b] (else
+ * cauchy_a; <= 0: no loss):
+ *   (proj.xy, depth) = ctvio_project_landmarks' proj3 for the query (l, t_j, row_j) with rm == NULL;
+ *   res2 (x 2) = r = img_w (proj.xy - p_j), the factor's whitened residual before the loss; s = |r|^2;
+ *   weight = rho'(s) = 1 / (1 + s / a_b^2), 1 without a loss;
+ *   corrector S, as the linearisation applies it to the block's Jacobian rows (Ceres' Corrector): S = sqrt(rho') (I - alpha r r^T / s),
+ *   alpha = 1 - sqrt(max(0, 1 + 2 s rho'' / rho')), rho'' = -(1 / a_b^2) / (1 + s / a_b^2)^2, with Corrector's rule alpha = 0 where s == 0 or
+ *   rho'' <= 0 -- which the Cauchy loss always meets, so that S = sqrt(rho') I; S = I without a loss;
+ *   Cw = img_w^2 C with C ctvio_project_landmarks' cov4 of that query (H, the exclusions and Sigma exactly those of ctvio_covariance_batch,
+ *   pose-landmark cross terms included, no damping; constant unknowns contribute nothing);
+ *   A = S Cw S (A <= I: the block's own J~^T J~ is part of H), redundancy = lambda_min(I - A) in closed form;
+ *   cov4 (x 4, row-major 2 x 2, whitened, symmetric to the bit) = C_loo = Cw + Cw S (I - A)^-1 S Cw = J (H - J~_b^T J~_b)^-1 J^T (Woodbury);
+ *   chi2 = r^T (C_loo + I)^-1 r, 2 degrees of freedom, formed on the device from the very res2 / cov4 bits that are returned.
+ *   status, in this precedence: 3 not computable (ctvio_project_landmarks' status 3): everything NaN;  2 Hll_l == 0 or an untouched
+ *   non-constant unknown under either time: values valid, redundancy 0, cov4 +inf on the diagonal and 0 elsewhere, chi2 = 0;  1 bad pivot in
+ *   the window's factorisation: values valid, redundancy / cov4 / chi2 NaN;  4 redundancy < opt->min_redundancy -- the rest of the window
+ *   cannot predict this observation, e.g. the only block of a landmark with a free depth: values and redundancy valid, cov4 +inf on the
+ *   diagonal and 0 elsewhere, chi2 = 0;  0 ok.
+ * Per landmark, over its blocks with status other than 3, in the library's packed block order (fixed by the upload): lm_count their number;
+ * lm_stats3[0] the mean of |proj.xy - p_j| (unwhitened: what VINS-style outliersRejection thresholds), [1] the largest chi2 over its
+ * status-0 blocks (0: none), [2] the smallest redundancy over its blocks of status 0 or 4 (+inf: none).  No blocks: 0 and (NaN, 0, +inf).
+ * With redundancy, cov4, chi2 and lm_stats3 all NULL nothing is linearised or factored: statuses 1, 2 and 4 cannot occur and the values have
+ * the bits of the covariance call's.
+ * Returns CTVIO_OK for every status, and for V = 0 or L = 0 (nothing is launched).  CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID for
+ * a window id out of range, NULL options, min_redundancy outside (0, 1) or non-finite, every output NULL with V > 0; the handle stays
+ * usable.  The state, the launch plan and the captured graph of the solve are left as they were; no atomics: where the linearisation is
+ * order-fixed (opt.deterministic) the bits of a block's and a landmark's outputs depend on the window alone -- not on the entry, on which
+ * outputs were asked for, or on how the call was sliced (large batches are walked in slices of windows so that the per-block scratch stays
+ * bounded; the factorisation happens once) -- and a second call repeats them.
+ * ctvio_last_timing: ms8[0..2] = k_cov_prepare, k_cov_solve, k_cov_gate_jac (a call of several slices: the first slice's record kernel; the
+ * later ones run between the slices' k_cov_solve and count in ms8[1]), ms8[3] the landmark reduction, ms8[7] the whole call; values only:
+ * ms8[2] (both kernels) and ms8[7]. */
+typedef struct ctvio_gate_options { double min_redundancy; } ctvio_gate_options;   /* 8 bytes */
+void ctvio_default_gate_options(ctvio_gate_options *o);                             /* 0.01 */
+int32_t ctvio_visual_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *redundancy,
+                                double *cov4, double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count);
+int32_t ctvio_visual_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *redundancy,
+                          double *cov4, double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count);
+
 /* BETWEEN FRAMES: IMU dead reckoning from the navigation state, with its 15 x 15 covariance -- what VisualOdometry::ProcessIMU
  * (visual_odometry.cpp:137-172) does with the state SlideWindow hands it, and where AddImageToWindow (:188-191) takes the predicted pose of
  * the next frame from; beside the mean, the first-order covariance that IntegrationBase::midPointIntegration (integration_base.h:100-179)
@@ -680,7 +726,8 @@ int32_t ctvio_graph_captures(const ctvio_solver *s);
  *   CTVIO_POISON=1|2 (test only: reused double scratch starts as quiet NaN / 2.6e151 at every upload and call, and ctvio_upload /
  *     ctvio_set_batch fail with CTVIO_ERR_INTERNAL if the packer leaves a staged input byte unwritten)
  *   CTVIO_CHOL_COMPACT=1|n (test only: every batch the panel Cholesky factors takes its slot-indexed variant, which otherwise runs only for
- *     windows beyond 591 unknowns; 1 = as many LDS slots as the batch needs, n >= 2 = at most n, the tiles beyond overflow to S) */
+ *     windows beyond 591 unknowns; 1 = as many LDS slots as the batch needs, n >= 2 = at most n, the tiles beyond overflow to S)
+ *   CTVIO_GATE_SLICE=n (test only: ctvio_visual_gate_batch walks its windows in slices of at most n block slots instead of 65536) */
 
 #ifdef __cplusplus
 }

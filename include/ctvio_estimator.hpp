@@ -747,6 +747,48 @@ class TrajectoryEstimator {
     for (int32_t v : st) if (v != 0) return false;
     return true;
   }
+  // After Solve, which observations are outliers (ctvio_visual_gate): the leave-one-out innovation test of every image factor added so far,
+  // at the CURRENT parameter values.  blocks: per factor, in the order of the AddImageFeatureDelayAnalytic calls -- res2 (2 per factor, the
+  // whitened residual before the loss), weight (the loss weight rho'), depth, and with with_cov redundancy, cov4 (4 per factor, the whitened
+  // leave-one-out prediction covariance), chi2 (2 degrees of freedom) -- and one ctvio_visual_gate status per factor.  landmarks (optional):
+  // keyed by the inverse-depth pointer -- the number of its computable factors, their mean unwhitened reprojection error (what
+  // outliersRejection thresholds), and with with_cov the largest chi2 and the smallest redundancy.  Without with_cov nothing is linearised.
+  // Returns false if any status is not 0.
+  struct VisualGate {
+    std::vector<double> res2, weight, depth, redundancy, cov4, chi2;
+    std::vector<int32_t> status;
+  };
+  struct LandmarkGate { int32_t count; double mean_error, max_chi2, min_redundancy; };
+  bool GateVisualBlocks(VisualGate &blocks, std::map<const double *, LandmarkGate> *landmarks = nullptr, double min_redundancy = 0.01,
+                        bool with_cov = true) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t V = (size_t)pk.w.V, L = (size_t)pk.w.L;
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_gate_options o;
+    ctvio_default_gate_options(&o);
+    o.min_redundancy = min_redundancy;
+    blocks.res2.assign(2 * V, 0.0); blocks.weight.assign(V, 0.0); blocks.depth.assign(V, 0.0); blocks.status.assign(V, 0);
+    blocks.redundancy.assign(with_cov ? V : 0, 0.0); blocks.cov4.assign(with_cov ? 4 * V : 0, 0.0); blocks.chi2.assign(with_cov ? V : 0, 0.0);
+    std::vector<double> lms(with_cov && landmarks ? 3 * L : 0);
+    std::vector<int32_t> lmc(landmarks ? L : 0);
+    check(ctvio_visual_gate(s, 0, &o, blocks.res2.data(), blocks.weight.data(), blocks.depth.data(), with_cov ? blocks.redundancy.data() : nullptr,
+                            with_cov ? blocks.cov4.data() : nullptr, with_cov ? blocks.chi2.data() : nullptr, blocks.status.data(),
+                            lms.empty() ? nullptr : lms.data(), lmc.empty() ? nullptr : lmc.data()));
+    if (landmarks) {
+      landmarks->clear();
+      for (size_t l = 0; l < lm_ptr_.size(); ++l) {
+        const int j = pk.lm_map[l];
+        if (j < 0) continue;
+        LandmarkGate g{lmc[(size_t)j], std::nan(""), std::nan(""), std::nan("")};
+        if (!lms.empty()) { g.mean_error = lms[3 * (size_t)j]; g.max_chi2 = lms[3 * (size_t)j + 1]; g.min_redundancy = lms[3 * (size_t)j + 2]; }
+        (*landmarks)[lm_ptr_[l]] = g;
+      }
+    }
+    for (int32_t v : blocks.status) if (v != 0) return false;
+    return true;
+  }
   // Where landmarks fall in the NEXT image, beyond the solved knots (ctvio_predict_landmarks): PredictIMUStates' dead reckoning through
   // `samples` (samples[0] inside the solved knots, the newest frame time in the reference's use; bias_gyr as there) composed with
   // ProjectLandmarks at the predicted pose.  Point i = (the inverse-depth pointer, image row).  end (optional): the predicted state at the last
