@@ -137,11 +137,12 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 14>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_schur_window_f64<5, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_misc, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));   // (+ 2 KB of static LDS)
-    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<false, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_BASE>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_REL>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_PROJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_RATES>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_GATE>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    // (no attribute for k_cov_solve<COV_PRED>: its launches are limited to the default dynamic-LDS size)
     return CTVIO_OK;
   }
   int bind() { HIPCHK(hipSetDevice(opt_.device)); return CTVIO_OK; }
@@ -1274,37 +1275,18 @@ class SolverImpl {
     return CTVIO_OK;
   }
   size_t cov_solve_lds() const { return ((size_t)16 * 32 * ((dev_.maxP + 31) / 32) + 512) * sizeof(double); }   // Ys | part (k_cov_solve)
-  // k_cov_solve's arguments by name; what a call does not use stays null.  The template arguments are the kernel's (they choose the type
-  // of the query records).  sel: the selections of covariance(), the output slots of the queries elsewhere.
-  template <bool REL = false, bool PROJ = false, bool RATES = false, bool PRED = false, bool GATE = false> struct CovSolveArgs {
-    const CovTile *tiles = nullptr;
-    const int32_t *sel = nullptr;
-    double *Y = nullptr, *var_rho = nullptr;
-    double *chi2 = nullptr;                                            // the gates of the PROJ / RATES / PRED queries
-    const typename CovQueryRec<REL, PROJ, RATES, PRED, GATE>::type *qrec = nullptr;   // pose, relative-pose, projection, rates, prediction or block records
-    double *qcov = nullptr;
-    const PointRec *lrec = nullptr;
-    double *lm_cov = nullptr;
-    int lm_base = 0;
-    const NavRec *nrec = nullptr;
-    double *nav_cov = nullptr;
-    GateOut gate{};   // GATE: the outputs by block slot; lm_base is the slice's first slot
-  };
-  template <bool REL, bool PROJ, bool RATES, bool PRED, bool GATE>
-  void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveArgs<REL, PROJ, RATES, PRED, GATE> &a) {
-    // (the PROJ / RATES / PRED instantiations have no landmark tiles: the kernel takes their gates in the position of var_rho)
-    hipLaunchKernelGGL((k_cov_solve<REL, PROJ, RATES, PRED, GATE>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a.tiles, a.sel, a.Y,
-                       PROJ || RATES || PRED ? a.chi2 : a.var_rho, a.qrec, a.qcov, a.lrec, a.lm_cov, a.lm_base, a.nrec, a.nav_cov, a.gate);
+  template <CovInst I> void launch_cov_solve(const Dev &c, size_t ntiles, const CovSolveIO<I> &a) {
+    hipLaunchKernelGGL((k_cov_solve<I>), dim3((unsigned)ntiles), dim3(COV_NT), cov_solve_lds(), stream_, c, a);
   }
-  // the device times of a call between pairs of its events (the stream is idle): ms[slot] of ctvio_last_timing, one launch each
-  struct Span { int slot; Ev begin, end; };
+  // the device times of a call between pairs of its events (the stream is idle): ms[slot] of ctvio_last_timing, one launch each where it ran
+  struct Span { int slot; Ev begin, end; bool ran = true; };
   int span_timing(std::initializer_list<Span> spans) {
     Timing t;
     t.clear();
     for (const Span &s : spans) {
       float ms = 0;
       HIPCHK(hipEventElapsedTime(&ms, ev_[s.begin], ev_[s.end]));
-      t.ms[s.slot] = ms; t.n[s.slot] = 1;
+      t.ms[s.slot] = ms; t.n[s.slot] = s.ran ? 1 : 0;
     }
     return publish_timing(t, 0);
   }
@@ -1316,7 +1298,7 @@ class SolverImpl {
   static_assert(LMP_OK == QUERY_OK && LMP_SINGULAR == QUERY_SINGULAR && LMP_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
   static_assert(PRJ_OK == QUERY_OK && PRJ_SINGULAR == QUERY_SINGULAR && PRJ_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
   // the tiles of a covariance query: at most per_tile consecutive sorted queries of one window each
-  static std::vector<CovTile> query_tiles(const QueryOrder &ord, int per_tile, int kind) {
+  static std::vector<CovTile> query_tiles(const QueryOrder &ord, int per_tile, CovKind kind) {
     std::vector<CovTile> tiles;
     ord.runs(per_tile, [&](int w, int first, int cnt) { tiles.push_back(CovTile{w, kind, first, cnt, 0}); });
     return tiles;
@@ -1360,17 +1342,6 @@ class SolverImpl {
     if (const int rc = finish_call(io)) return rc;
     return span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_COV_SOLVE, EV_COV_GRAM}});
   }
-  // the three kernel times of a covariance call (the stream is idle): ms[i] between the events pair[i], where the kernel ran
-  int cov_timing(const Ev (&pair)[3][2], const bool (&ran)[3]) {
-    Timing t;
-    t.clear();
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0;
-      HIPCHK(hipEventElapsedTime(&ms, ev_[pair[i][0]], ev_[pair[i][1]]));
-      t.ms[i] = ms; t.n[i] = ran[i] ? 1 : 0;
-    }
-    return publish_timing(t, 0);
-  }
   int covariance(int only, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
     if (const int rc = guard()) return rc;
     const int nw = dev_.nwin;
@@ -1399,12 +1370,12 @@ class SolverImpl {
           CovWin cw{w, ns, (int32_t)nsel_tot, 0, (long long)ycount, (long long)ncov};
           cwins.push_back(cw);
           for (int t = 0; 16 * t < ns; ++t) {
-            tiles.push_back(CovTile{w, 0, (int32_t)nsel_tot + 16 * t, std::min(16, ns - 16 * t), (long long)ycount});
+            tiles.push_back(CovTile{w, TILE_SEL, (int32_t)nsel_tot + 16 * t, std::min(16, ns - 16 * t), (long long)ycount});
             ycount += (size_t)16 * m.P;
           }
         }
         if (var_rho)
-          for (int r = 0; r < m.L; r += 16) tiles.push_back(CovTile{w, 1, r, std::min(16, m.L - r), 0});
+          for (int r = 0; r < m.L; r += 16) tiles.push_back(CovTile{w, TILE_RHO, r, std::min(16, m.L - r), 0});
         nsel_tot += (size_t)ns; ncov += (size_t)ns * ns;
       }
     }
@@ -1432,7 +1403,7 @@ class SolverImpl {
     Dev c;
     if (const int rc = cov_factor(c, mask, excl)) return rc;
     if (!tiles.empty()) {
-      CovSolveArgs<> a;
+      CovSolveIO<COV_BASE> a;
       a.tiles = dtiles; a.sel = dsel; a.Y = dy; a.var_rho = dvar;
       launch_cov_solve(c, tiles.size(), a);
     }
@@ -1444,11 +1415,9 @@ class SolverImpl {
     if (ncov + nvar) HIPCHK(hipMemcpyAsync((void *)hcov, dcov, io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
     if (const int rc = finish_call(io)) return rc;
-    {   // device times of this call, for ctvio_last_timing: the three covariance kernels and the whole call
-      const Ev pair[3][2] = {{EV_COV_PREPARE, EV_COV_FACTOR}, {EV_COV_SOLVE, EV_COV_GRAM}, {EV_COV_GRAM, EV_CALL_END}};
-      const bool ran[3] = {true, !tiles.empty(), !cwins.empty()};
-      if (const int rc = cov_timing(pair, ran)) return rc;
-    }
+    // device times of this call, for ctvio_last_timing: the three covariance kernels and the whole call
+    if (const int rc = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_SOLVE, EV_COV_GRAM, !tiles.empty()}, {2, EV_COV_GRAM, EV_CALL_END, !cwins.empty()}}))
+      return rc;
     // (a window whose factorisation met a non-positive or non-finite pivot: its outputs are NaN)
     const double nan = std::nan("");
     size_t oc = 0, ov = 0;
@@ -1468,7 +1437,7 @@ class SolverImpl {
   }
   // ctvio_pose_covariance_batch / ctvio_pose_covariance (only >= 0: every query belongs to that window, win is not read): J Sigma J^T of the
   // pose at n query times.  The queries are grouped by window (stable: a window's queries keep the caller's order) and paired into tiles of
-  // kind 2; k_cov_pose_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 6 x 6 blocks into the
+  // kind TILE_POSE; k_cov_pose_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 6 x 6 blocks into the
   // caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are not touched.
   int pose_covariance(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *cov36,
                       int32_t *status) {
@@ -1483,7 +1452,7 @@ class SolverImpl {
     const QueryOrder ord(only, n, win, dev_.nwin);
     if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
     if (n == 0) return CTVIO_OK;
-    const std::vector<CovTile> tiles = query_tiles(ord, 2, 2);
+    const std::vector<CovTile> tiles = query_tiles(ord, 2, TILE_POSE);
     // ---- out: cov36 | status
     CovScratch scr(true, (size_t)dev_.Utot, sizeof(PoseRec), nn);
     CallLayout io = head_;
@@ -1500,8 +1469,8 @@ class SolverImpl {
           hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, rec, io_dev<int32_t>(io, s_stat));
         },
         [&](const Dev &c, const PoseRec *rec) {
-          CovSolveArgs<> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          CovSolveIO<COV_BASE> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
           launch_cov_solve(c, tiles.size(), a);
         });
     if (rc) return rc;
@@ -1520,7 +1489,7 @@ class SolverImpl {
   // ctvio_nav_state_batch / ctvio_nav_state (only >= 0: every query belongs to that window, win is not read): the navigation state (pose,
   // world velocity, the biases of state frame[i]; frame null: the newest) at n query times and J Sigma J^T of its 15 tangent dimensions.
   // Values only (cov225 null): k_cov_nav_jac alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable)
-  // into tiles of kind 4, one each; k_cov_nav_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the
+  // into tiles of kind TILE_NAV, one each; k_cov_nav_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the
   // 15 x 15 blocks into the caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are not touched.
   int nav_state(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225, int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
@@ -1537,7 +1506,7 @@ class SolverImpl {
     if (n == 0) return CTVIO_OK;
     const bool want_cov = cov225 != nullptr;
     const size_t nc = want_cov ? nn : 0;
-    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, 4) : std::vector<CovTile>();
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, TILE_NAV) : std::vector<CovTile>();
     // ---- out: cov225 | state16 | status
     CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(NavRec), nn);
     CallLayout io = head_;
@@ -1559,8 +1528,8 @@ class SolverImpl {
                              io_dev<int32_t>(io, s_stat));
         },
         [&](const Dev &c, const NavRec *rec) {
-          CovSolveArgs<> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.nrec = rec; a.nav_cov = io_dev<double>(io, s_cov);
+          CovSolveIO<COV_BASE> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.nrec = rec; a.nav_cov = io_dev<double>(io, s_cov);
           launch_cov_solve(c, tiles.size(), a);
         });
     if (rc) return rc;
@@ -1581,7 +1550,7 @@ class SolverImpl {
   // ctvio_body_rates_batch / ctvio_body_rates (only >= 0: every query belongs to that window, win is not read): body angular velocity,
   // specific force and body-frame velocity at n query times, J Sigma J^T of (domega, df, dv_B, dbg, dba) with the biases of state frame[i]
   // (frame null: the newest), and the gate of a candidate IMU sample.  Values only (cov225 and chi2 null): k_cov_rates_jac alone, nothing
-  // is linearised or factored.  Otherwise nav_state()'s middle: the queries grouped by window (stable) into tiles of kind 7, one each;
+  // is linearised or factored.  Otherwise nav_state()'s middle: the queries grouped by window (stable) into tiles of kind TILE_RATES, one each;
   // k_cov_rates_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 15 x 15 blocks and the gates
   // into the caller's slots.  dev_, plan_ and the captured graph are not touched.
   int body_rates(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const int32_t *frame, const double *meas6, const double *noise6,
@@ -1608,7 +1577,7 @@ class SolverImpl {
     if (n == 0) return CTVIO_OK;
     const bool want_cov = cov225 || chi2;
     const size_t nc = want_cov ? nn : 0;
-    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, 7) : std::vector<CovTile>();
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, TILE_RATES) : std::vector<CovTile>();
     // ---- out: cov225 | chi2 | rates9 | status
     CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(RatesRec), nn);
     CallLayout io = head_;
@@ -1633,8 +1602,8 @@ class SolverImpl {
                              io_dev<int32_t>(io, s_stat));
         },
         [&](const Dev &c, const RatesRec *rec) {
-          CovSolveArgs<false, false, true> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          CovSolveIO<COV_RATES> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
           if (chi2) a.chi2 = io_dev<double>(io, s_chi);
           launch_cov_solve(c, tiles.size(), a);
         });
@@ -1657,7 +1626,7 @@ class SolverImpl {
   // ctvio_imu_predict_batch / ctvio_imu_predict (only >= 0: every query belongs to that window, win is not read): the navigation state of
   // query i at imu_t[first sample of i] (bias state frame[i]; frame null: the newest) carried through the query's n_imu[i] samples by
   // k_imu_propagate, with its 15 x 15 covariance.  The middle is nav_state()'s: queries grouped by window (stable), k_cov_nav_jac, and with
-  // cov225 cov_factor and k_cov_solve on tiles of kind 4, whose slot is the query's first output entry, so that P_0 lands where sample 0
+  // cov225 cov_factor and k_cov_solve on TILE_NAV tiles, whose slot is the query's first output entry, so that P_0 lands where sample 0
   // is reported.  The samples of all queries are staged with the queries in one copy.  dev_, plan_ and the captured graph are not touched.
   int imu_predict(int only, int64_t n64, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t, const double *imu_gyro,
                   const double *imu_acc, const ctvio_imu_noise *noise, int last_only, double *state16, double *cov225, int32_t *status) {
@@ -1694,7 +1663,7 @@ class SolverImpl {
     auto entry0 = [&](size_t i) { return last_only ? (int64_t)i : first[i]; };
     auto entries = [&](size_t i) { return last_only ? (size_t)1 : (size_t)n_imu[i]; };
     const bool want_cov = cov225 != nullptr;
-    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, 4) : std::vector<CovTile>();
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 1, TILE_NAV) : std::vector<CovTile>();
     // ---- scratch.  io: queries, propagation queries, sample times and measurements, entries, tiles (in, one staged copy); cov225 | state16 |
     // status (out, one copy).  scr: mask, exclusions, records, the states at sample 0
     CovScratch cs(want_cov, (size_t)dev_.Utot, sizeof(NavRec), nn);
@@ -1751,8 +1720,8 @@ class SolverImpl {
       hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec, x0,
                          io_dev<int32_t>(io, s_stat));
       HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      CovSolveArgs<> a;
-      a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.nrec = drec; a.nav_cov = io_dev<double>(io, s_cov);
+      CovSolveIO<COV_BASE> a;
+      a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.nrec = drec; a.nav_cov = io_dev<double>(io, s_cov);
       launch_cov_solve(c, tiles.size(), a);
       HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
       propagate();
@@ -1784,7 +1753,7 @@ class SolverImpl {
   // ctvio_relative_pose_batch / ctvio_relative_pose (only >= 0: every query belongs to that window, win is not read): the pose increment
   // T(t_a)^-1 T(t_b) of n pairs of times and J_rel Sigma J_rel^T of its six tangent dimensions.  Values only (cov36 null): k_cov_rel_jac
   // alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a window's queries keep the caller's
-  // order) and paired into tiles of kind 5; k_cov_rel_jac writes one record per query after k_cov_prepare (it reads the exclusions),
+  // order) and paired into tiles of kind TILE_REL; k_cov_rel_jac writes one record per query after k_cov_prepare (it reads the exclusions),
   // k_cov_solve the 6 x 6 blocks into the caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are
   // not touched.
   int relative_pose(int only, int64_t n64, const int32_t *win, const int64_t *t_a_ns, const int64_t *t_b_ns, const double *q_SI, const double *p_SI,
@@ -1803,7 +1772,7 @@ class SolverImpl {
     if (n == 0) return CTVIO_OK;
     const bool want_cov = cov36 != nullptr;
     const size_t nc = want_cov ? nn : 0;
-    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 2, 5) : std::vector<CovTile>();
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, 2, TILE_REL) : std::vector<CovTile>();
     // ---- out: rel7 | cov36 | status
     CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(RelRec), nn);
     CallLayout io = head_;
@@ -1825,8 +1794,8 @@ class SolverImpl {
                              io_dev<int32_t>(io, s_stat));
         },
         [&](const Dev &c, const RelRec *rec) {
-          CovSolveArgs<true> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.sel = io_dev<int32_t>(io, s_slot); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          CovSolveIO<COV_REL> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
           launch_cov_solve(c, tiles.size(), a);
         });
     if (rc) return rc;
@@ -1847,7 +1816,7 @@ class SolverImpl {
   // ctvio_project_landmarks_batch / ctvio_project_landmarks (only >= 0: every query belongs to that window, win is not read): the predicted
   // image point of landmark lm[i] in the camera at (t_ns[i], row[i]), its 2 x 2 covariance and the gate of a candidate point.  Values only
   // (cov4 and chi2 null): k_cov_proj_jac alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a
-  // window's queries keep the caller's order), eight to a tile of kind 6; k_cov_proj_jac writes one record per query after k_cov_prepare (it
+  // window's queries keep the caller's order), eight to a tile of kind TILE_PROJ; k_cov_proj_jac writes one record per query after k_cov_prepare (it
   // reads the exclusions and 1 / Hll), k_cov_solve the 2 x 2 blocks and gates by record.  Around them the middle of covariance(): dev_, plan_
   // and the captured graph are not touched.
   int project_landmarks(int only, int64_t n64, const int32_t *win, const int32_t *lmi, const int64_t *t_ns, const int32_t *row, const ctvio_row_model *rm,
@@ -1875,7 +1844,7 @@ class SolverImpl {
     if (n == 0) return CTVIO_OK;
     const bool want_cov = cov4 || chi2;
     const size_t nc = want_cov ? nn : 0;
-    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, PRJ_PER_TILE, 6) : std::vector<CovTile>();
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ord, PRJ_PER_TILE, TILE_PROJ) : std::vector<CovTile>();
     // ---- out: proj3 | cov4 | chi2 | row | status, all in sorted order (the kernels write by record: no slots)
     CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(ProjRec), nn);
     CallLayout io = head_;
@@ -1898,8 +1867,8 @@ class SolverImpl {
                              io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
         },
         [&](const Dev &c, const ProjRec *rec) {
-          CovSolveArgs<false, true> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.qrec = rec; a.qcov = io_dev<double>(io, s_cov);
+          CovSolveIO<COV_PROJ> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
           if (chi2) a.chi2 = io_dev<double>(io, s_chi);
           launch_cov_solve(c, tiles.size(), a);
         });
@@ -1923,7 +1892,7 @@ class SolverImpl {
   // themselves.  No inputs: k_cov_gate_jac reads the block slots the upload holds and writes by slot; the host scatters into the caller's
   // block order (gate_slot_).  Values only (redundancy, cov4, chi2 and lm_stats3 null): k_cov_gate_jac alone (and k_cov_gate_reduce for
   // lm_count), nothing is linearised or factored.  Otherwise run_query: one factorisation, then per slice of windows (plan_gate_slices: the
-  // record scratch is bounded) k_cov_gate_jac and k_cov_solve on tiles of kind 9 -- the first slice's record kernel where run_query times
+  // record scratch is bounded) k_cov_gate_jac and k_cov_solve<COV_GATE> (kind TILE_GATE) -- the first slice's record kernel where run_query times
   // it (ms[2]), the later slices' inside ms[1] --, then k_cov_gate_reduce (ms[3]).  dev_, plan_ and the captured graph are not touched.
   int visual_gate(int only, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *red, double *cov4, double *chi2, int32_t *status,
                   double *lm_stats3, int32_t *lm_count) {
@@ -1985,8 +1954,8 @@ class SolverImpl {
             slot_range(slices[si], first, n);
             if (!n) continue;
             if (si) hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, scr.lay.at<uint8_t>(call_scr_.dev, scr.s_excl), const_cast<GateRec *>(rec), out);
-            CovSolveArgs<false, false, false, false, true> a;
-            a.qrec = rec; a.lm_base = first; a.gate = out; a.gate.nslot = n;
+            CovSolveIO<COV_GATE> a;
+            a.rec = rec; a.slot_base = first; a.gate = out; a.gate.nslot = n;
             launch_cov_solve(c, (size_t)nblk(n, PRJ_PER_TILE), a);
           }
           ev_err = hipEventRecord(ev_[EV_QUERY_BEGIN], stream_);
@@ -2025,8 +1994,8 @@ class SolverImpl {
   // ctvio_predict_landmarks_batch / ctvio_predict_landmarks (only >= 0: every prediction belongs to that window, win is not read): where
   // landmark lm[i] falls in the camera at the IMU-predicted pose of prediction pred[i], row row[i], beyond the spline, with its 2 x 2
   // covariance and gate.  The predictions are imu_predict()'s queries (grouped by window, stable), the points are grouped by the window of
-  // their prediction, eight to a tile of kind 8.  Sequence: staged copy, (cov_factor,) k_cov_nav_jac on the predictions' start times,
-  // k_imu_transition (end state, Phi, N), k_cov_pred_jac (value, status, record), k_cov_solve<PRED>, one copy back.  Its own sequence, as
+  // their prediction, eight to a tile of kind TILE_PRED.  Sequence: staged copy, (cov_factor,) k_cov_nav_jac on the predictions' start times,
+  // k_imu_transition (end state, Phi, N), k_cov_pred_jac (value, status, record), k_cov_solve<COV_PRED>, one copy back.  Its own sequence, as
   // imu_predict's and for its reason: two record kernels, the transition between them and a fourth timing slot.  dev_, plan_ and the
   // captured graph are not touched.
   int predict_landmarks(int only, int64_t np64, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t, const double *imu_gyro,
@@ -2083,7 +2052,7 @@ class SolverImpl {
     const QueryOrder ordq(only, nq, pwin.data(), dev_.nwin);
     const bool want_cov = cov4 || chi2;
     const size_t nc = want_cov ? nn : 0;
-    const std::vector<CovTile> tiles = want_cov ? query_tiles(ordq, PRJ_PER_TILE, 8) : std::vector<CovTile>();
+    const std::vector<CovTile> tiles = want_cov ? query_tiles(ordq, PRJ_PER_TILE, TILE_PRED) : std::vector<CovTile>();
     // ---- io: start-time queries, propagation queries, samples, points, tiles (in, one staged copy); state16 | proj3 | cov4 | chi2 | row |
     // status | the predictions' statuses (out, one copy).  scr: mask, exclusions, point records; start records, start states, Phi | N
     CovScratch cs(want_cov, (size_t)dev_.Utot, sizeof(PredRec), nn);
@@ -2157,8 +2126,8 @@ class SolverImpl {
       HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
       records(excl, drec);
       HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      CovSolveArgs<false, false, false, true> a;
-      a.tiles = io_dev<CovTile>(io, s_tiles); a.qrec = drec; a.qcov = io_dev<double>(io, s_cov);
+      CovSolveIO<COV_PRED> a;
+      a.tiles = io_dev<CovTile>(io, s_tiles); a.rec = drec; a.blocks = io_dev<double>(io, s_cov);
       if (chi2) a.chi2 = io_dev<double>(io, s_chi);
       launch_cov_solve(c, tiles.size(), a);
       HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
@@ -2217,7 +2186,7 @@ class SolverImpl {
   }
   // ctvio_landmark_points_batch / ctvio_landmark_points (single: window `only` alone): the world point of every landmark and its 3 x 3
   // covariance.  Points only (cov9 null): k_cov_point_jac alone, nothing is linearised or factored.  Otherwise the middle of covariance(),
-  // k_cov_point_jac with the Jacobians (one record per landmark, after k_cov_prepare: it reads 1 / Hll) and k_cov_solve on tiles of kind 3,
+  // k_cov_point_jac with the Jacobians (one record per landmark, after k_cov_prepare: it reads 1 / Hll) and k_cov_solve on tiles of kind TILE_POINT,
   // five landmarks each in the sorted order of the rows of W.  dev_, plan_ and the captured graph are not touched.
   int landmark_points(bool single, int only, double *point3, double *cov9, int32_t *status) {
     if (const int rc = single ? guard(only) : guard()) return rc;
@@ -2228,7 +2197,7 @@ class SolverImpl {
     const bool want_cov = cov9 != nullptr;
     std::vector<CovTile> tiles;
     for (int w = wbeg; w < wend && want_cov; ++w)
-      for (int r = 0; r < meta_[w].L; r += LMP_PER_TILE) tiles.push_back(CovTile{w, 3, r, std::min(LMP_PER_TILE, meta_[w].L - r), 0});
+      for (int r = 0; r < meta_[w].L; r += LMP_PER_TILE) tiles.push_back(CovTile{w, TILE_POINT, r, std::min(LMP_PER_TILE, meta_[w].L - r), 0});
     // ---- io: tiles (in, one staged copy); cov9 | point3 | status (out, one copy).  The records: one per landmark of the batch
     CovScratch scr(want_cov, (size_t)dev_.Utot, sizeof(PointRec), (size_t)dev_.Ltot);
     CallLayout io = head_;
@@ -2250,7 +2219,7 @@ class SolverImpl {
     } else {
       std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
       const int rc = run_query<PointRec>(io, s_tiles, s_cov, &scr, jac, [&](const Dev &c, const PointRec *rec) {
-        CovSolveArgs<> a;
+        CovSolveIO<COV_BASE> a;
         a.tiles = io_dev<CovTile>(io, s_tiles); a.lrec = rec; a.lm_cov = io_dev<double>(io, s_cov); a.lm_base = l0;
         launch_cov_solve(c, tiles.size(), a);
       });

@@ -20,10 +20,10 @@
 //                         (chol_*) with the flow form and differs only in scheduling; k_cholesky_solve =
 //                         panel kernel for P > 223), k_step_finish (back-substitution, candidate x (+) alpha delta, its knot-pair table)
 //   kernels_query.hpp     k_gauge_restore (double2vector), k_residual_summary, k_spline_eval (trajectory queries)
-//   kernels_cov.hpp       k_cov_prepare, k_cov_solve, k_cov_gram (marginal covariances from the factor of the reduced system)
-//                         k_cov_pose_jac (per-query pose Jacobian: pose covariances at query times through k_cov_solve)
-//                         k_cov_nav_jac (per-query navigation state and its Jacobian: 15 x 15 covariances through k_cov_solve)
-//                         k_cov_rates_jac (per-query body rates and their Jacobian: 15 x 15 covariances and IMU gates through k_cov_solve)
+//   kernels_cov.hpp       k_cov_prepare, k_cov_solve<CovInst> (cov_prologue, cov_forward_subst, cov_epilogue over CovSolveIO), k_cov_gram (marginal
+//                         covariances from the factor of the reduced system); the record kernels that feed k_cov_solve, one record per query:
+//                         k_cov_pose_jac, k_cov_point_jac, k_cov_nav_jac, k_cov_rel_jac, k_cov_proj_jac, k_cov_rates_jac, k_cov_pred_jac,
+//                         k_cov_gate_jac (+ k_cov_gate_reduce: per-landmark statistics of the visual gate)
 //   kernels_prop.hpp      k_imu_propagate (IMU dead reckoning from a navigation state: mean and 15 x 15 covariance, four queries per wave)
 //   kernels_tri.hpp       k_triangulate (landmark depths by one-sided Jacobi, one wave per landmark), k_shift_anchor (depths re-anchored)
 #pragma once

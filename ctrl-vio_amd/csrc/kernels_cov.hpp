@@ -1,35 +1,31 @@
-// kernels_cov.hpp -- marginal covariances from the reduced system (ctvio_covariance_batch): k_cov_prepare (per-call activity mask, zero damping),
-// k_cov_solve (block forward substitution against 16 right-hand sides per workgroup), k_cov_gram (selected block of the covariance); pose
-// covariances at query times (ctvio_pose_covariance_batch): k_cov_pose_jac (one record per query), then k_cov_solve on tiles of kind 2; world
-// points of the landmarks with their 3 x 3 covariances (ctvio_landmark_points_batch): k_cov_point_jac (one record per landmark), then
-// k_cov_solve on tiles of kind 3; navigation states (pose, velocity, biases) with their 15 x 15 covariances (ctvio_nav_state_batch):
-// k_cov_nav_jac (one record per query), then k_cov_solve on tiles of kind 4; pose increments between two times with their 6 x 6 covariances
-// (ctvio_relative_pose_batch): k_cov_rel_jac (one record per query), then k_cov_solve on tiles of kind 5; predicted image points of landmarks
-// at query times with their 2 x 2 covariances and gates (ctvio_project_landmarks_batch): k_cov_proj_jac (one record per query), then
-// k_cov_solve on tiles of kind 6; body rates (angular velocity, specific force, body-frame velocity) with their 15 x 15 covariances and IMU
-// gates (ctvio_body_rates_batch): k_cov_rates_jac (one record per query), then k_cov_solve on tiles of kind 7; image points of landmarks seen
-// from IMU-predicted poses beyond the spline (ctvio_predict_landmarks_batch): k_cov_nav_jac on the predictions' start times, k_imu_transition
-// (kernels_prop.hpp), k_cov_pred_jac (one record per point), then k_cov_solve on tiles of kind 8.
-// Part of kernels.hpp (included from there, in order; not a stand-alone header).
-//
-// With H the normal matrix of the window at its current state (no LM damping) and the excluded unknowns -- constant ones, and those no factor
-// touches (H_jj == 0) -- removed, the reduced system S = Hpp - W Hll^-1 W^T = L L^T is factored by the panel kernel (k_cholesky_solve: L21 in S,
-// the inverses of the 32 x 32 diagonal blocks in Dev::chol_inv).  Then
+// kernels_cov.hpp -- covariances from the reduced system.  k_cov_prepare (per-call activity mask, zero damping), then one record kernel per
+// entry and k_cov_solve (block forward substitution against 16 right-hand sides per workgroup, and the tile's covariance blocks):
+//   ctvio_covariance_batch          selected block, var(rho)           k_cov_solve<COV_BASE> on TILE_SEL / TILE_RHO, k_cov_gram
+//   ctvio_pose_covariance_batch     6 x 6 at query times               k_cov_pose_jac, k_cov_solve<COV_BASE> on TILE_POSE
+//   ctvio_landmark_points_batch     world points, 3 x 3                k_cov_point_jac, k_cov_solve<COV_BASE> on TILE_POINT
+//   ctvio_nav_state_batch           pose, velocity, biases, 15 x 15    k_cov_nav_jac, k_cov_solve<COV_BASE> on TILE_NAV (also ctvio_imu_predict_batch)
+//   ctvio_relative_pose_batch       pose increments, 6 x 6             k_cov_rel_jac, k_cov_solve<COV_REL>
+//   ctvio_project_landmarks_batch   image points, 2 x 2, gates         k_cov_proj_jac, k_cov_solve<COV_PROJ>
+//   ctvio_body_rates_batch          body rates, 15 x 15, IMU gates     k_cov_rates_jac, k_cov_solve<COV_RATES>
+//   ctvio_predict_landmarks_batch   points from IMU-predicted poses    k_cov_nav_jac, k_imu_transition (kernels_prop.hpp), k_cov_pred_jac, k_cov_solve<COV_PRED>
+//   ctvio_visual_gate_batch         leave-one-out test of the blocks   k_cov_gate_jac, k_cov_solve<COV_GATE>, k_cov_gate_reduce
+// Part of kernels.hpp (included from there, in order; not a stand-alone header).  With H the normal matrix of the window at its current
+// state (no LM damping) and the excluded unknowns -- constant ones, and those no factor touches (H_jj == 0) -- removed, the reduced system
+// S = Hpp - W Hll^-1 W^T = L L^T is factored by the panel kernel (k_cholesky_solve: L21 in S, the inverses of the 32 x 32 diagonal blocks in
+// Dev::chol_inv).  Then
 //   Sigma[i][j]     = (L^-1 e_i)^T (L^-1 e_j)                    for trajectory unknowns i, j,
 //   Sigma[P+l][P+l] = 1 / Hll_l + | L^-1 (w_l / Hll_l) |^2        for the inverse depth of landmark l (w_l: its row of W),
 //   Sigma_pose(t)   = J Sigma J^T = (L^-1 J^T)^T (L^-1 J^T)        for the 6 x P Jacobian J of the pose at time t (factors.hpp: pose_jac_T),
 //   Cov(X_l)        = (L^-1 G)^T (L^-1 G) + j_rho j_rho^T / Hll_l   for the world point X_l of landmark l: G = Jp^T - w_l j_rho^T / Hll_l (P x 3), Jp
 //                     the Jacobian of X_l against the trajectory unknowns, j_rho = dX_l / drho_l (the joint covariance of the trajectory and
 //                     rho_l is Sigma_pp, Sigma_pl = -Sigma_pp w_l / Hll_l, Sigma_ll = 1 / Hll_l + w_l^T Sigma_pp w_l / Hll_l^2),
-//   Sigma_nav(t, f) = (L^-1 J^T)^T (L^-1 J^T)                      for the 15 x P Jacobian J of (pose, world velocity, bias state f) at time t
-//                     (factors.hpp: nav_jac_T; the bias rows are one-hot),
+//   Sigma_nav(t, f) = (L^-1 J^T)^T (L^-1 J^T)                      for the 15 x P Jacobian J of (pose, world velocity, bias state f) at t (nav_jac_T),
 //   Sigma_rel(a, b) = (L^-1 J^T)^T (L^-1 J^T)                      for the 6 x P Jacobian J = A_a J_a + A_b J_b of the increment T(t_a)^-1 T(t_b)
 //                     (factors.hpp: rel_pose_jac_T; J_a, J_b the pose Jacobians at the two times),
 //   Cov(proj)       = (L^-1 G)^T (L^-1 G) + j j^T / Hll_l           for the predicted image point of landmark l at a query time: Cov(X_l)'s identity
 //                     with two columns, G = Jp^T - w_l j^T / Hll_l, Jp over the knots of the anchor time and of the query time and the line
 //                     delay (factors.hpp: proj_jac_T, proj_cols), j = d(proj) / drho_l,
-//   Sigma_rates(t, f) = (L^-1 J^T)^T (L^-1 J^T)                    for the 15 x P Jacobian J of (omega, specific force, body-frame velocity, bias state f)
-//                     at time t (factors.hpp: rates_jac_T; the bias rows are one-hot),
+//   Sigma_rates(t, f) = (L^-1 J^T)^T (L^-1 J^T)   for the 15 x P Jacobian J of (omega, specific force, body-frame velocity, bias state f) at t (rates_jac_T),
 //   Cov(pred)       = (L^-1 G)^T (L^-1 G) + j j^T / Hll_l + A N A^T  for the image point of landmark l seen from an IMU-predicted pose beyond the
 //                     spline: Cov(proj)'s identity with Jp over the knots of the anchor time, the knots of the prediction's start time and its
 //                     bias state (A Phi J_nav: the image point's row A pulled back through the propagation's transition Phi) and the line
@@ -40,21 +36,27 @@
 namespace ctv {
 
 // One right-hand-side tile: 16 columns of one window.
+enum CovKind : int32_t {
+  TILE_SEL = 0,     // one-hot columns of selected unknowns
+  TILE_RHO = 1,     // rows of W (sorted landmark order) scaled by 1 / Hll
+  TILE_POSE = 2,    // the six columns of J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5)
+  TILE_POINT = 3,   // the three columns of G of up to five landmarks (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused)
+  TILE_NAV = 4,     // the fifteen columns of J^T of one navigation-state query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias
+                    // 12..14, column 15 unused)
+  TILE_REL = 5,     // the six columns of J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5)
+  TILE_PROJ = 6,    // the two columns of G of up to eight projection queries of the window (columns 2 q, 2 q + 1)
+  TILE_RATES = 7,   // the fifteen columns of J^T of one body-rates query (omega 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias
+                    // 9..11, accelerometer bias 12..14, column 15 unused)
+  TILE_PRED = 8,    // the two columns of G of up to eight points of ctvio_predict_landmarks_batch (columns 2 q, 2 q + 1)
+  TILE_GATE = 9     // TILE_PROJ's columns for eight consecutive block slots of the window (ctvio_visual_gate_batch; built in the kernel, not listed)
+};
 struct CovTile {
   int32_t win;
-  int32_t kind;     // 0: one-hot columns of selected unknowns; 1: rows of W (sorted landmark order) scaled by 1 / Hll; 2: the six columns of
-                    // J^T of one or two pose queries of the window (columns 6 q .. 6 q + 5); 3: the three columns of G of up to five landmarks
-                    // (sorted landmark order, columns 3 q .. 3 q + 2, column 15 unused); 4: the fifteen columns of J^T of one navigation-state
-                    // query (pose 0..5, velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 5: the six columns of
-                    // J_rel^T of one or two relative-pose queries of the window (columns 6 q .. 6 q + 5); 6: the two columns of G of up to eight
-                    // projection queries of the window (columns 2 q, 2 q + 1); 7: the fifteen columns of J^T of one body-rates query (omega
-                    // 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias 9..11, accelerometer bias 12..14, column 15 unused); 8: the two
-                    // columns of G of up to eight points of ctvio_predict_landmarks_batch (columns 2 q, 2 q + 1); 9: kind 6's columns for eight
-                    // consecutive block slots of the window (ctvio_visual_gate_batch; built in the kernel, not listed)
-  int32_t first;    // kind 0: offset of the tile's first entry in the concatenated selection; kind 1 and 3: first row of W (window-local);
-                    // kind 2, 5, 6 and 8: the tile's first query record; kind 4 and 7: its query record
-  int32_t count;    // columns in use (<= 16); kind 2 and 5: queries (1 or 2); kind 3: landmarks (<= 5); kind 4 and 7: 1; kind 6 and 8: queries (<= 8)
-  long long yoff;   // kind 0: where the tile's Y ([P][16] doubles) goes in the scratch
+  CovKind kind;
+  int32_t first;    // SEL: offset of the tile's first entry in the concatenated selection; RHO and POINT: first row of W (window-local);
+                    // POSE, REL, PROJ, PRED and GATE: the tile's first query record; NAV and RATES: its query record
+  int32_t count;    // columns in use (<= 16); POSE and REL: queries (1 or 2); POINT: landmarks (<= 5); NAV and RATES: 1; PROJ, PRED and GATE: queries (<= 8)
+  long long yoff;   // SEL: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
 struct CovWin {
@@ -585,7 +587,7 @@ struct GateOut {
   double *res2, *weight, *depth, *enorm;   // enorm: |res2| / img_w = |proj - p_j|, the unwhitened reprojection error (for the landmark mean)
   double *red, *cov4, *chi2;
   int32_t *status;
-  int32_t slot0, nslot;   // the outputs' first slot; the slots of the slice k_cov_solve runs over (from its lm_base on)
+  int32_t slot0, nslot;   // the outputs' first slot; the slots of the slice k_cov_solve runs over (from CovSolveIO::slot_base on)
   double min_red;
 };
 // One lane per block slot e = first + i of the slice (records by i, outputs by e - slot0).  A padding slot (v_win < 0) gets a PRJ_NONE
@@ -816,58 +818,122 @@ __global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoi
   for (int c = 0; c < 6; ++c) { r.jb[2 * c] = M[9 + c]; r.jb[2 * c + 1] = M[24 + c]; }
 }
 
-// Y = L^-1 B for one tile of 16 right-hand sides.  d is the covariance's copy of Dev (d.active = the per-call mask).  Four waves: wave (h, kp)
-// owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of a half are added
-// in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row, as the back-substitution of the panel
-// kernel reads it); L_bb^-1 from Dev::chol_inv.  The substitution starts at the first block in which the tile is non-zero; the 16-column
-// tiles of the products go to the two partial sums by their parity, so where the tile starts moves no product from one sum to the other:
-// a column's bits do not depend on the columns it shares the tile with.
-// Kind 2: sel = the caller's slot of every query record, prec = the records, pose_cov = the caller-ordered 6 x 6 blocks.
-// Kind 3: lrec = the landmark records (by landmark through the batch), lm_cov = the 3 x 3 blocks in the caller's landmark order, the block of
-// landmark lm0 + l at 9 (lm0 + l - lm_base).  Column 3 q + a of landmark q = kind 1's column (the row of W over its span, then the line-delay
-// column, times 1 / Hll) times -j_rho[a], plus row a of Jp; landmarks whose status is not LMP_OK keep zero columns and write nothing.
-// Kind 4: sel = the caller's slot of every query record, nrec = the records, nav_cov = the caller-ordered 15 x 15 blocks.  One query per
-// tile: its bits depend on nothing else in the call.
-// Kind 5 (the instantiation REL = true, which holds no other kind; kinds 0 - 4 are the instantiation REL = false, whose arguments and code
-// are what they were before kind 5 existed): sel = the caller's slot of every query record, prec = the records (RelRec), pose_cov = the
-// caller-ordered 6 x 6 blocks; kind 2's epilogue.  The a-rows are stored, then after a barrier the b-rows are added: where the knot groups
-// of the two times overlap every entry is "a-term + b-term" in that order, elsewhere the one term (0.0 + b-term for a b-row).
-// Kind 6 (the instantiation PROJ = true, which holds no other kind and leaves the code of the other two what it was): prec = the records
-// (ProjRec, in the order of the tiles), pose_cov = the 2 x 2 blocks and var_rho = the gates chi2 (null: not asked for), both by record.
-// Columns 2 q, 2 q + 1 of query q: kind 3's -(w_l / Hll) j^T over the span of the landmark's row of W and the line-delay column; after a
-// barrier + the anchor rows, after another + the query rows -- where the knot groups of the two times overlap every entry is "anchor term
-// + query term" in that order -- and the line-delay row.  Epilogue: the three unique entries of every 2 x 2 Gram block, four partial sums over
-// the rows k = p mod 4 added in sequence, + j j^T / Hll, mirrored; then chi2 = e^T (Cov + I / img_w^2)^-1 e, e = obs - proj, by the 2 x 2
-// Cholesky factor, from the block just written and the record's prediction.  Queries whose status is not PRJ_OK keep zero columns and write nothing.
-// Kind 7 (the instantiation RATES = true, which holds no other kind and leaves the code of the other three what it was): sel = the caller's
-// slot of every query record, prec = the records (RatesRec), pose_cov = the caller-ordered 15 x 15 blocks and var_rho = the gates chi2 by
-// slot (null: not asked for).  One query per tile, kind 4's prologue with nine Jacobian columns and kind 4's Gram epilogue (cov_gram15);
-// then S = A C A^T + diag(sigma^2) from the block just written -- 21 lanes, every entry ((C[a][b] + C[a][9 + b]) + C[9 + a][b]) +
-// C[9 + a][9 + b] -- and one lane's 6 x 6 Cholesky factor and forward substitution in LDS: chi2 = |L^-1 e|^2, e = meas - z.
-// Kind 8 (the instantiation PRED = true, which holds no other kind and leaves the code of the other four what it was): prec = the records
-// (PredRec, in the order of the tiles), pose_cov = the 2 x 2 blocks and var_rho = the gates chi2 (null: not asked for), both by record.
-// Prologue: kind 6's, the "query rows" being (A Phi J_nav)^T over the knots of the prediction's start time -- where they overlap the anchor's
-// every entry is "anchor term + start term" in that order --, then the line-delay row and the six rows (A Phi)[:, 9:15]^T of the bias state.
-// Epilogue: kind 6's Gram entries, + j j^T / Hll, + A N A^T (the record's three entries) before mirroring; then kind 6's gate.
-// Kind 9 (the instantiation GATE = true, which holds no other kind and leaves the code of the other five what it was): the visual blocks of
-// the windows themselves (ctvio_visual_gate_batch).  No tile list: tile b is the eight block slots lm_base + 8 b .. + 7 of the slice, prec =
-// their records (GateRec, by slot of the slice; a padding slot's says PRJ_NONE), gate = the outputs by absolute slot.  Kind 6's prologue and
-// Gram entries, whitened: Cw = img_w^2 C.  Then, with the record's corrector S: T = Cw S, A = S T, redundancy = lambda_min(I - A) in closed
-// form; below gate.min_red the status becomes GATE_WEAK, else C_loo = Cw + T (I - A)^-1 T^T (three unique entries, mirrored) and
-// chi2 = r^T (C_loo + I)^-1 r by the 2 x 2 Cholesky factor from the values just written.
-// amdgpu_waves_per_eu: with the prologues and epilogues of four kinds inlined the allocator otherwise settles at 58 VGPRs + 8 AGPRs, one wave per
-// SIMD short of the eight that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill -- with kind 4's
-// inlined as well.
+// ---- k_cov_solve<I>: one workgroup per tile fills the tile's 16 right-hand sides in LDS (cov_prologue), substitutes Y = L^-1 B in place
+// (cov_forward_subst) and reduces Y to the tile's outputs (cov_epilogue); COV_BASE's two stages stand in the kernel itself.  d is the call's
+// copy of Dev (d.active = the per-call mask).  Records whose status is not OK keep zero columns and write nothing.  The substitution: wave
+// (h, kp) of four owns the 16-row half h of the current 32-row block and every second 16-column tile of its products; the two partial sums of
+// a half are added in a fixed order.  L_bc is read from S inside the envelope only (columns >= 16 env_first of the tile row), L_bb^-1 from
+// Dev::chol_inv.  It starts at the first block in which the tile is non-zero (the prologue leaves that row in LDS); the tiles of the products
+// go to the two partial sums by their parity, so where the tile starts moves no product from one sum to the other: a column's bits do not
+// depend on its tile partners.  Every epilogue sums over the rows from that block on: strided partial sums, added in sequence.
+// kind: records | columns, in the order they are written | epilogue -> outputs
+// TILE_SEL: io.sel from t.first | one-hot, one per selected unknown (an excluded one: zero) | Y -> io.Y + t.yoff, for k_cov_gram
+// TILE_RHO: rows t.first .. of W | its row of W over the planned span, then the line-delay column, times 1 / Hll | 16 partial sums, + 1 / Hll -> io.var_rho
+// TILE_POSE: io.rec (PoseRec) from t.first | 6 q + a: J^T over the rows of knots s .. s + nk - 1 | cov_gram6: 3 partial sums -> io.blocks by io.slot
+// TILE_POINT: io.lrec by landmark | 3 q + a: TILE_RHO's times -j_rho[a]; barrier; + Jp^T, line-delay row | 3 x 3 Gram, + j_rho j_rho^T / Hll -> io.lm_cov
+// TILE_NAV: io.nrec[t.first] | 0..5 pose, 6..8 velocity (c' / dt on positions), 9..14 one-hot bias | cov_gram15 -> io.nav_cov by io.slot
+// TILE_REL: io.rec (RelRec) from t.first | 6 q + a: the a-rows; barrier; + the b-rows (overlap: a-term + b-term, elsewhere the one term) | TILE_POSE's
+// TILE_PROJ: io.rec (ProjRec) from t.first | 2 q + a: TILE_RHO's column times -j[a]; barrier; + anchor rows; barrier; + query rows and the line-delay
+//   row (overlap: anchor term + query term) | cov_gram2: 4 partial sums, + j j^T / Hll, mirrored -> io.blocks by record; cov_gate2(I / img_w^2) on
+//   obs - proj from the block just written -> io.chi2 by record
+// TILE_RATES: io.rec[t.first] (RatesRec) | 0..8 J^T over the knot rows, 9..14 one-hot bias | cov_gram15 -> io.blocks by io.slot; S = A C A^T +
+//   diag(sigma^2), every entry ((C[a][b] + C[a][9 + b]) + C[9 + a][b]) + C[9 + a][9 + b], 6 x 6 Cholesky by one lane -> io.chi2 by io.slot
+// TILE_PRED: io.rec (PredRec) from t.first | TILE_PROJ's, the query rows being (A Phi J_nav)^T over the knots of the start time, then the six rows
+//   (A Phi)[:, 9:15]^T of the bias state | TILE_PROJ's, + A N A^T (the record's) before mirroring
+// TILE_GATE: io.rec (GateRec) by slot of the slice; no tile list: tile b is the slots io.slot_base + 8 b .. + 7 (one window: a window's slots
+//   start on a group of 64) | TILE_PROJ's | Cw = img_w^2 (cov_gram2); T = Cw S, A = S T, redundancy = lambda_min(I - A) -> gate.red; below
+//   gate.min_red GATE_WEAK, else C_loo = Cw + T (I - A)^-1 T^T -> gate.cov4, cov_gate2(I) on r -> gate.chi2; all by absolute slot - gate.slot0
 constexpr int COV_NT = 256;
-template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false, bool GATE = false> struct CovQueryRec { typedef PoseRec type; };
-template <> struct CovQueryRec<true, false, false, false, false> { typedef RelRec type; };
-template <> struct CovQueryRec<false, true, false, false, false> { typedef ProjRec type; };
-template <> struct CovQueryRec<false, false, true, false, false> { typedef RatesRec type; };
-template <> struct CovQueryRec<false, false, false, true, false> { typedef PredRec type; };
-template <> struct CovQueryRec<false, false, false, false, true> { typedef GateRec type; };
-// The 120 unique entries of the 15 x 15 Gram block of a tile's columns 0..14 over the rows k0 .. P - 1 (kinds 4 and 7): every entry four
-// partial sums over the rows k = p mod 4, added in sequence, computed once and mirrored into the caller's block cov + 225 slot[0].  keep: lane
-// tid < 120 leaves its entry in part[tid] as well (entry (i >= j) at i (i + 1) / 2 + j; that lane alone has read part[tid]).
+enum CovInst { COV_BASE, COV_REL, COV_PROJ, COV_RATES, COV_PRED, COV_GATE };   // COV_BASE: TILE_SEL .. TILE_NAV by t.kind; the others: their one kind
+template <CovInst I> struct CovQueryRec { typedef PoseRec type; };
+template <> struct CovQueryRec<COV_REL> { typedef RelRec type; };     template <> struct CovQueryRec<COV_PROJ> { typedef ProjRec type; };
+template <> struct CovQueryRec<COV_RATES> { typedef RatesRec type; }; template <> struct CovQueryRec<COV_PRED> { typedef PredRec type; };
+template <> struct CovQueryRec<COV_GATE> { typedef GateRec type; };
+// k_cov_solve's arguments; what a call does not use stays null.
+template <CovInst I> struct CovSolveIO {
+  const CovTile *tiles = nullptr;
+  const int32_t *sel = nullptr;                          // TILE_SEL: the concatenated selections
+  const int32_t *slot = nullptr;                         // the caller's slot of every query record
+  const typename CovQueryRec<I>::type *rec = nullptr;    // the query records
+  double *blocks = nullptr;                              // their 6 x 6, 2 x 2 or 15 x 15 covariances
+  double *chi2 = nullptr;                                // their gates (null: not asked for)
+  double *Y = nullptr, *var_rho = nullptr;               // TILE_SEL, TILE_RHO
+  const PointRec *lrec = nullptr;                        // TILE_POINT: the records by landmark through the batch,
+  double *lm_cov = nullptr; int lm_base = 0;             // the 3 x 3 blocks from landmark lm_base on
+  const NavRec *nrec = nullptr; double *nav_cov = nullptr;   // TILE_NAV
+  GateOut gate{}; int slot_base = 0;                     // TILE_GATE: the outputs, and the slice's first slot
+};
+// What the stages of one workgroup share.  (The dynamic LDS is named, not carried: a pointer through the struct costs two VGPRs.)
+extern __shared__ __attribute__((aligned(16))) double cov_lds[];   // Ys | part (the launch's cov_solve_lds bytes)
+struct CovCtx {
+  const Dev &d; const CovTile t; const WinMeta &m;   // (t: a copy made field by field; a reference to the kernel's tile costs COV_BASE two VGPRs)
+  int P, ldh, cur, tid, wave;   // wave: uniform (read from the first lane)
+  int *first;                   // LDS: the first row in which the tile is non-zero (PP: a tile of zero columns)
+  __device__ double *Ys() const { return cov_lds; }                                  // [PP][16] the right-hand sides, block by block replaced by Y
+  __device__ double *part() const { return cov_lds + 16 * 32 * ((P + 31) / 32); }   // [512] partial sums handed between waves
+};
+
+// Columns col0, col0 + 1 of one landmark of a TILE_PROJ / TILE_PRED / TILE_GATE record, sixteen lanes (sub) each: its row wrow of W over the
+// planned span, then the line-delay column, times 1 / Hll and -mult[a].  live: the record is OK (mult is read only then).  (COV_BASE's
+// ladders keep their own one- and three-column loops.)
+__device__ __forceinline__ void cov_wrow_cols(const CovCtx &x, int wrow, int col0, int sub, bool live, const double *mult) {
+  const Dev &d = x.d; const WinMeta &m = x.m;
+  const int P = x.P, row = m.lm0 + wrow, klo = d.lm_klo[row], khi = d.lm_khi[row];
+  const double dv = d.dinv[row];
+  const double *Wr = d.WS[x.cur] + m.W0 + (long long)wrow * m.ldw;
+  if (!(live && khi >= klo && dv != 0.0)) return;
+  const double j0 = -mult[0], j1 = -mult[1];
+  const int cend = min(6 * khi + 6, P);
+  auto put = [&](int c) {
+    if (!d.active[m.u0 + c]) return;
+    const double v = Wr[c] * dv;
+    x.Ys()[c * 16 + col0] = v * j0; x.Ys()[c * 16 + col0 + 1] = v * j1;
+  };
+  for (int c = 6 * klo + sub; c < cend; c += 16) put(c);
+  if (sub == 0 && cend <= P - 1) put(P - 1);
+}
+// One lane's scan over the tile's OK records: a record that starts at knot s and whose landmark is row `row` of W.
+__device__ __forceinline__ void cov_span_first(const CovCtx &x, int row, int s) {
+  *x.first = min(*x.first, 6 * s);
+  if (x.d.lm_khi[row] >= x.d.lm_klo[row]) *x.first = min(*x.first, 6 * x.d.lm_klo[row]);
+}
+
+// ---- TILE_POSE and TILE_REL (ctvio_pose_covariance_batch, ctvio_relative_pose_batch)
+__device__ __forceinline__ void cov_rel_prologue(const CovCtx &x, const RelRec *rec) {
+  const CovTile &t = x.t;
+  for (int e = x.tid; e < 144 * t.count; e += COV_NT) {
+    const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
+    const RelRec &rr = rec[t.first + qi];
+    if (rr.status == POSE_OK && r < 6 * rr.nk_a && x.d.active[x.m.u0 + 6 * rr.s_a + r]) x.Ys()[(6 * rr.s_a + r) * 16 + 6 * qi + a] = rr.jt_a[6 * r + a];
+  }
+  __syncthreads();
+  for (int e = x.tid; e < 144 * t.count; e += COV_NT) {
+    const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
+    const RelRec &rr = rec[t.first + qi];
+    if (rr.status == POSE_OK && r < 6 * rr.nk_b && x.d.active[x.m.u0 + 6 * rr.s_b + r]) x.Ys()[(6 * rr.s_b + r) * 16 + 6 * qi + a] += rr.jt_b[6 * r + a];
+  }
+  if (x.tid == 0)
+    for (int qi = 0; qi < t.count; ++qi) {
+      const RelRec &rr = rec[t.first + qi];
+      if (rr.status == POSE_OK) *x.first = min(*x.first, 6 * min(rr.s_a, rr.s_b));
+    }
+}
+// the two 6 x 6 Gram blocks straight from Ys; every entry three partial sums over the rows k = p mod 3, added in sequence
+__device__ __forceinline__ void cov_gram6(const CovCtx &x, int b0, const int32_t *slot, double *blocks) {
+  const int P = x.P, tid = x.tid, k0 = min(32 * b0, P) / 3 * 3;
+  if (tid < 216) {
+    const int p = tid / 72, e = tid % 72, ci = 6 * (e / 36) + (e % 36) / 6, cj = 6 * (e / 36) + e % 6;
+    double s = 0.0;
+    for (int k = k0 + p; k < P; k += 3) s += x.Ys()[k * 16 + ci] * x.Ys()[k * 16 + cj];
+    x.part()[p * 72 + e] = s;
+  }
+  __syncthreads();
+  if (tid < 36 * x.t.count) blocks[(long long)36 * slot[x.t.first + tid / 36] + tid % 36] = (x.part()[tid] + x.part()[72 + tid]) + x.part()[144 + tid];
+}
+
+// ---- TILE_NAV and TILE_RATES (ctvio_nav_state_batch, ctvio_imu_predict_batch, ctvio_body_rates_batch): one query per tile.  The 120 unique
+// entries of the 15 x 15 Gram block of columns 0..14 over the rows k0 .. P - 1: four partial sums over the rows k = p mod 4 each, added in
+// sequence, mirrored into cov + 225 slot[0].  keep: lane tid < 120 leaves its entry (i >= j) in part[i (i + 1) / 2 + j] (it alone has read it).
 __device__ __forceinline__ void cov_gram15(const double *Ys, double *part, int k0, int P, int tid, double *cov, const int32_t *slot, bool keep) {
   for (int x = tid; x < 480; x += COV_NT) {
     const int p = x / 120;
@@ -888,221 +954,189 @@ __device__ __forceinline__ void cov_gram15(const double *Ys, double *part, int k
     if (keep) part[tid] = v;
   }
 }
-template <bool REL, bool PROJ = false, bool RATES = false, bool PRED = false, bool GATE = false>
-__global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, const CovTile *tiles, const int32_t *sel, double *yscr, double *var_rho,
-                                                      const typename CovQueryRec<REL, PROJ, RATES, PRED, GATE>::type *prec, double *pose_cov, const PointRec *lrec, double *lm_cov, int lm_base,
-                                                      const NavRec *nrec, double *nav_cov, GateOut gate) {
-  // (GATE: no tile list -- tile b is the block slots lm_base + 8 b .. + 7, which lie in one window: a window's slots start on a group of 64)
-  const CovTile t = GATE ? CovTile{d.vb_win[(lm_base + PRJ_PER_TILE * (int)blockIdx.x) / 64], 9, PRJ_PER_TILE * (int)blockIdx.x, min(PRJ_PER_TILE, gate.nslot - PRJ_PER_TILE * (int)blockIdx.x), 0}
-                         : tiles[blockIdx.x];
-  const int w = t.win;
-  const WinMeta &m = d.wins[w];
-  const int P = m.P, ldh = m.ldh, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int q4 = lane >> 4, l15 = lane & 15;
-  const int nblk = (P + 31) / 32, PP = 32 * nblk;
-  const int cur = d.lm[w].cur;
-  extern __shared__ __attribute__((aligned(16))) double smcov[];
-  double *Ys = smcov;              // [PP][16] the right-hand sides, block by block replaced by Y
-  double *part = Ys + 16 * PP;   // [512] partial sums handed between waves
-  __shared__ int s_first;
-  for (int e = tid; e < 16 * PP; e += COV_NT) Ys[e] = 0.0;
-  if (tid == 0) s_first = PP;
+__device__ __forceinline__ void cov_rates_prologue(const CovCtx &x, const RatesRec &rr) {
+  const Dev &d = x.d; const WinMeta &m = x.m;
+  const int tid = x.tid;
+  if (rr.status == POSE_OK) {
+    if (tid < 216) {
+      const int r = tid / 9, a = tid % 9;
+      if (r < 6 * rr.nk && d.active[m.u0 + 6 * rr.s + r]) x.Ys()[(6 * rr.s + r) * 16 + a] = rr.jt[tid];
+    } else if (tid < 222) {
+      const int a = tid - 216, j = 6 * m.K + 6 * rr.frame + a;
+      if (d.active[m.u0 + j]) x.Ys()[j * 16 + 9 + a] = 1.0;
+    }
+    if (tid == 0) *x.first = 6 * rr.s;
+  }
+}
+// TILE_NAV's Gram block, then the gate of the IMU sample: 21 lanes form S from the block just written, one lane factors it in LDS
+__device__ __forceinline__ void cov_rates_epilogue(const CovCtx &x, int b0, const RatesRec &rr, const int32_t *slot, double *blocks, double *chi2) {
+  const int tid = x.tid;
+  double *part = x.part();
+  if (rr.status != POSE_OK) return;
+  cov_gram15(x.Ys(), part, min(32 * b0, x.P), x.P, tid, blocks, slot, true);
+  if (!chi2) return;
   __syncthreads();
-  if constexpr (PRED) {
-    const int q = tid >> 4, sub = tid & 15;
-    if (q < t.count) {   // -(w_l / Hll) j^T: the row's planned span, then the line-delay column (kind 6's)
-      const PredRec &pr = prec[t.first + q];
-      const int row = m.lm0 + pr.wrow, klo = d.lm_klo[row], khi = d.lm_khi[row];
-      const double dv = d.dinv[row];
-      const double *Wr = d.WS[cur] + m.W0 + (long long)pr.wrow * m.ldw;
-      if (pr.status == PRJ_OK && khi >= klo && dv != 0.0) {
-        const double j0 = -pr.j[0], j1 = -pr.j[1];
-        const int cend = min(6 * khi + 6, P);
-        for (int c = 6 * klo + sub; c < cend; c += 16)
-          if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 2 * q] = v * j0; Ys[c * 16 + 2 * q + 1] = v * j1; }
-        if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
-          const double v = Wr[P - 1] * dv;
-          Ys[(P - 1) * 16 + 2 * q] = v * j0; Ys[(P - 1) * 16 + 2 * q + 1] = v * j1;
-        }
+  double *Sm = part + 128, *zv = Sm + 36;   // S = A C A^T + diag(sigma^2), A = [[I, 0, 0, I, 0], [0, I, 0, 0, I]]: rows a and 9 + a of C; then
+                                            // its Cholesky factor in place (lower triangle); z = L^-1 e
+  if (tid < 21) {
+    int a, b;
+    tile_decode(tid, a, b);
+    const double c = ((part[a * (a + 1) / 2 + b] + part[(9 + b) * (10 + b) / 2 + a]) + part[(9 + a) * (10 + a) / 2 + b]) + part[(9 + a) * (10 + a) / 2 + 9 + b];
+    Sm[6 * a + b] = a == b ? c + rr.sig[a] * rr.sig[a] : c;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double chi = 0.0;
+    for (int j = 0; j < 6; ++j) {   // column j of L, then z_j of L z = e
+      double dj = Sm[7 * j], ej = rr.meas[j] - rr.z[j];
+      for (int k = 0; k < j; ++k) { dj -= Sm[6 * j + k] * Sm[6 * j + k]; ej -= Sm[6 * j + k] * zv[k]; }
+      const double ljj = sqrt(dj);
+      for (int i = j + 1; i < 6; ++i) {
+        double v = Sm[6 * i + j];
+        for (int k = 0; k < j; ++k) v -= Sm[6 * i + k] * Sm[6 * j + k];
+        Sm[6 * i + j] = v / ljj;
       }
+      const double zj = ej / ljj;
+      zv[j] = zj;
+      chi += zj * zj;
     }
-    __syncthreads();
-    for (int e = tid; e < 48 * t.count; e += COV_NT) {   // + the anchor rows 6 s_a .. 6 (s_a + nk_a) - 1
-      const int qi = e / 48, r = (e % 48) / 2, a = e % 2;
-      const PredRec &pr = prec[t.first + qi];
-      if (pr.status == PRJ_OK && r < 6 * pr.nk_a && d.active[m.u0 + 6 * pr.s_a + r]) Ys[(6 * pr.s_a + r) * 16 + 2 * qi + a] += pr.jt_a[2 * r + a];
-    }
-    __syncthreads();
+    chi2[slot[0]] = chi;
+  }
+}
+
+// ---- TILE_PROJ, TILE_PRED and TILE_GATE (ctvio_project_landmarks_batch, ctvio_predict_landmarks_batch, ctvio_visual_gate_batch)
+// + the anchor rows 6 s_a .. 6 (s_a + nk_a) - 1 of every query's two columns
+template <class Rec> __device__ __forceinline__ void cov_anchor_rows(const CovCtx &x, const Rec *rec) {
+  for (int e = x.tid; e < 48 * x.t.count; e += COV_NT) {
+    const int qi = e / 48, r = (e % 48) / 2, a = e % 2;
+    const Rec &pr = rec[x.t.first + qi];
+    if (pr.status == PRJ_OK && r < 6 * pr.nk_a && x.d.active[x.m.u0 + 6 * pr.s_a + r]) x.Ys()[(6 * pr.s_a + r) * 16 + 2 * qi + a] += pr.jt_a[2 * r + a];
+  }
+}
+template <CovInst I, class Rec> __device__ __forceinline__ void cov_proj_prologue(const CovCtx &x, const Rec *rec) {
+  const Dev &d = x.d; const WinMeta &m = x.m; const CovTile &t = x.t;
+  const int P = x.P, tid = x.tid, q = tid >> 4, sub = tid & 15;
+  if (q < t.count) {
+    const Rec &pr = rec[t.first + q];
+    cov_wrow_cols(x, pr.wrow, 2 * q, sub, pr.status == PRJ_OK, pr.j);
+  }
+  __syncthreads();
+  cov_anchor_rows(x, rec);
+  __syncthreads();
+  if constexpr (I == COV_PRED) {
     for (int e = tid; e < 62 * t.count; e += COV_NT) {   // + the rows of the start time 6 s_q .. 6 (s_q + nk_q) - 1 (r < 24), the line-delay row (r = 24),
                                                          // the six rows of bias state `frame` (r = 25 .. 30)
       const int qi = e / 62, r = (e % 62) / 2, a = e % 2;
-      const PredRec &pr = prec[t.first + qi];
+      const Rec &pr = rec[t.first + qi];
       if (pr.status != PRJ_OK) continue;
       const int c = r < 24 ? 6 * pr.s_q + r : (r == 24 ? P - 1 : 6 * m.K + 6 * pr.frame + (r - 25));
-      if ((r < 6 * pr.nk_q || r >= 24) && d.active[m.u0 + c]) Ys[c * 16 + 2 * qi + a] += r < 24 ? pr.jt_q[2 * r + a] : (r == 24 ? pr.jld[a] : pr.jb[2 * (r - 25) + a]);
+      if ((r < 6 * pr.nk_q || r >= 24) && d.active[m.u0 + c]) x.Ys()[c * 16 + 2 * qi + a] += r < 24 ? pr.jt_q[2 * r + a] : (r == 24 ? pr.jld[a] : pr.jb[2 * (r - 25) + a]);
     }
-    if (tid == 0)
-      for (int qi = 0; qi < t.count; ++qi) {
-        const PredRec &pr = prec[t.first + qi];
-        if (pr.status != PRJ_OK) continue;
-        const int row = m.lm0 + pr.wrow;
-        s_first = min(s_first, 6 * min(pr.s_a, pr.s_q));
-        if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
-      }
-  } else if constexpr (RATES) {   // the nine columns of J^T over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the rows of bias state f, each
-                           // where the unknown is in the system
-    const RatesRec &rr = prec[t.first];
-    if (rr.status == POSE_OK) {
-      if (tid < 216) {
-        const int r = tid / 9, a = tid % 9;
-        if (r < 6 * rr.nk && d.active[m.u0 + 6 * rr.s + r]) Ys[(6 * rr.s + r) * 16 + a] = rr.jt[tid];
-      } else if (tid < 222) {
-        const int a = tid - 216, j = 6 * m.K + 6 * rr.frame + a;
-        if (d.active[m.u0 + j]) Ys[j * 16 + 9 + a] = 1.0;
-      }
-      if (tid == 0) s_first = 6 * rr.s;
-    }
-  } else if constexpr (PROJ || GATE) {
-    const int q = tid >> 4, sub = tid & 15;
-    if (q < t.count) {   // -(w_l / Hll) j^T: the row's planned span, then the line-delay column
-      const ProjRec &pr = prec[t.first + q];
-      const int row = m.lm0 + pr.wrow, klo = d.lm_klo[row], khi = d.lm_khi[row];
-      const double dv = d.dinv[row];
-      const double *Wr = d.WS[cur] + m.W0 + (long long)pr.wrow * m.ldw;
-      if (pr.status == PRJ_OK && khi >= klo && dv != 0.0) {
-        const double j0 = -pr.j[0], j1 = -pr.j[1];
-        const int cend = min(6 * khi + 6, P);
-        for (int c = 6 * klo + sub; c < cend; c += 16)
-          if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 2 * q] = v * j0; Ys[c * 16 + 2 * q + 1] = v * j1; }
-        if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
-          const double v = Wr[P - 1] * dv;
-          Ys[(P - 1) * 16 + 2 * q] = v * j0; Ys[(P - 1) * 16 + 2 * q + 1] = v * j1;
-        }
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < 48 * t.count; e += COV_NT) {   // + the anchor rows 6 s_a .. 6 (s_a + nk_a) - 1
-      const int qi = e / 48, r = (e % 48) / 2, a = e % 2;
-      const ProjRec &pr = prec[t.first + qi];
-      if (pr.status == PRJ_OK && r < 6 * pr.nk_a && d.active[m.u0 + 6 * pr.s_a + r]) Ys[(6 * pr.s_a + r) * 16 + 2 * qi + a] += pr.jt_a[2 * r + a];
-    }
-    __syncthreads();
+  } else {
     for (int e = tid; e < 50 * t.count; e += COV_NT) {   // + the query rows 6 s_q .. 6 (s_q + nk_q) - 1 (r < 24), then the line-delay row (r = 24)
       const int qi = e / 50, r = (e % 50) / 2, a = e % 2;
-      const ProjRec &pr = prec[t.first + qi];
+      const Rec &pr = rec[t.first + qi];
       if (pr.status != PRJ_OK) continue;
       const int c = r < 24 ? 6 * pr.s_q + r : P - 1;
-      if ((r < 6 * pr.nk_q || r == 24) && d.active[m.u0 + c]) Ys[c * 16 + 2 * qi + a] += r < 24 ? pr.jt_q[2 * r + a] : pr.jld[a];
+      if ((r < 6 * pr.nk_q || r == 24) && d.active[m.u0 + c]) x.Ys()[c * 16 + 2 * qi + a] += r < 24 ? pr.jt_q[2 * r + a] : pr.jld[a];
     }
-    if (tid == 0)
-      for (int qi = 0; qi < t.count; ++qi) {
-        const ProjRec &pr = prec[t.first + qi];
-        if (pr.status != PRJ_OK) continue;
-        const int row = m.lm0 + pr.wrow;
-        s_first = min(s_first, 6 * min(pr.s_a, pr.s_q));
-        if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
+  }
+  if (tid == 0)
+    for (int qi = 0; qi < t.count; ++qi) {
+      const Rec &pr = rec[t.first + qi];
+      if (pr.status == PRJ_OK) cov_span_first(x, m.lm0 + pr.wrow, min(pr.s_a, pr.s_q));
+    }
+}
+// Entries (0,0), (0,1), (1,1) of the eight 2 x 2 Gram blocks into part: four partial sums over the rows k = p mod 4 each (cov_gram2 adds them).
+__device__ __forceinline__ void cov_gram2_partials(const CovCtx &x, int b0) {
+  const int P = x.P, tid = x.tid, k0 = min(32 * b0, P);
+  constexpr int NE = 3 * PRJ_PER_TILE;
+  if (tid < 4 * NE) {
+    const int p = tid / NE, e = tid % NE, v = e % 3, ci = 2 * (e / 3) + (v == 2), cj = 2 * (e / 3) + (v != 0);
+    double s = 0.0;
+    for (int k = k0 + p; k < P; k += 4) s += x.Ys()[k * 16 + ci] * x.Ys()[k * 16 + cj];
+    x.part()[p * NE + e] = s;
+  }
+  __syncthreads();
+}
+// entry v of query q: the partial sums in sequence, + j j^T / Hll
+__device__ __forceinline__ double cov_gram2(const double *part, int q, int v, const double *j, double dv) {
+  constexpr int NE = 3 * PRJ_PER_TILE;
+  return (((part[3 * q + v] + part[NE + 3 * q + v]) + part[2 * NE + 3 * q + v]) + part[3 * NE + 3 * q + v]) + (j[v == 2] * j[v != 0]) * dv;
+}
+// e^T (C + s I)^-1 e by the 2 x 2 Cholesky factor; c: entries (0,0), (0,1), (1,1)
+__device__ __forceinline__ double cov_gate2(double c0, double c1, double c2, double s, double e0, double e1) {
+  const double l00 = sqrt(c0 + s), l10 = c1 / l00, l11 = sqrt((c2 + s) - l10 * l10);
+  const double z0 = e0 / l00, z1 = (e1 - l10 * z0) / l11;
+  return z0 * z0 + z1 * z1;
+}
+// TILE_PROJ and TILE_PRED: the blocks by record, then the gate from the block just written and the record's prediction
+template <CovInst I, class Rec> __device__ __forceinline__ void cov_proj_epilogue(const CovCtx &x, int b0, const Rec *rec, double *blocks, double *chi2) {
+  const WinMeta &m = x.m; const CovTile &t = x.t;
+  const int tid = x.tid;
+  cov_gram2_partials(x, b0);
+  if (tid < t.count) {
+    const Rec &pr = rec[t.first + tid];
+    if (pr.status == PRJ_OK) {
+      const double dv = x.d.dinv[m.lm0 + pr.wrow];
+      double c[3];
+#pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        c[v] = cov_gram2(x.part(), tid, v, pr.j, dv);
+        if constexpr (I == COV_PRED) c[v] = c[v] + pr.ana[v];
       }
-  } else if constexpr (REL) {   // rows 6 s_a .. 6 (s_a + nk_a) - 1 of every query's six columns, then + rows 6 s_b .. 6 (s_b + nk_b) - 1, where the unknown is in the system
-    for (int e = tid; e < 144 * t.count; e += COV_NT) {
-      const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
-      const RelRec &rr = prec[t.first + qi];
-      if (rr.status == POSE_OK && r < 6 * rr.nk_a && d.active[m.u0 + 6 * rr.s_a + r]) Ys[(6 * rr.s_a + r) * 16 + 6 * qi + a] = rr.jt_a[6 * r + a];
+      double *o = blocks + (long long)4 * (t.first + tid);
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[1]; o[3] = c[2];
+      if (chi2) chi2[t.first + tid] = cov_gate2(c[0], c[1], c[2], 1.0 / (m.img_w * m.img_w), pr.obs[0] - pr.proj[0], pr.obs[1] - pr.proj[1]);
     }
-    __syncthreads();
-    for (int e = tid; e < 144 * t.count; e += COV_NT) {
-      const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
-      const RelRec &rr = prec[t.first + qi];
-      if (rr.status == POSE_OK && r < 6 * rr.nk_b && d.active[m.u0 + 6 * rr.s_b + r]) Ys[(6 * rr.s_b + r) * 16 + 6 * qi + a] += rr.jt_b[6 * r + a];
-    }
-    if (tid == 0)
-      for (int qi = 0; qi < t.count; ++qi) {
-        const RelRec &rr = prec[t.first + qi];
-        if (rr.status == POSE_OK) s_first = min(s_first, 6 * min(rr.s_a, rr.s_b));
-      }
-  } else if (t.kind == 0) {
-    if (tid < t.count) {
-      const int j = sel[t.first + tid];
-      if (d.active[m.u0 + j]) { Ys[j * 16 + tid] = 1.0; atomicMin(&s_first, j); }   // (an excluded unknown: a zero column, finished by k_cov_gram)
-    }
-  } else if (t.kind == 2) {   // rows 6 s .. 6 (s + nk) - 1 of every query's six columns, where the unknown is in the system
-    const PoseRec *prec2 = (const PoseRec *)prec;   // (REL: dead code, dropped after the constant branch above)
-    for (int e = tid; e < 144 * t.count; e += COV_NT) {
-      const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
-      const PoseRec &pr = prec2[t.first + qi];
-      if (pr.status == POSE_OK && r < 6 * pr.nk && d.active[m.u0 + 6 * pr.s + r]) Ys[(6 * pr.s + r) * 16 + 6 * qi + a] = pr.jt[6 * r + a];
-    }
-    if (tid == 0)
-      for (int qi = 0; qi < t.count; ++qi)
-        if (prec2[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * prec2[t.first + qi].s);
-  } else if (t.kind == 4) {   // pose columns 0..5 and velocity columns 6..8 over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the
-                              // rows of bias state f, each where the unknown is in the system
-    const NavRec &nr = nrec[t.first];
-    if (nr.status == POSE_OK) {
-      if (tid < 144) {
-        const int r = tid / 6, a = tid % 6;
-        if (r < 6 * nr.nk && d.active[m.u0 + 6 * nr.s + r]) Ys[(6 * nr.s + r) * 16 + a] = nr.jt[tid];
-      } else if (tid < 156) {   // d(dv_a) / d(position a of knot s + kk) = c'_kk / dt
-        const int kk = (tid - 144) / 3, a = (tid - 144) % 3, j = 6 * (nr.s + kk) + 3 + a;
-        if (kk < nr.nk && d.active[m.u0 + j]) Ys[j * 16 + 6 + a] = nr.cv[kk];
-      } else if (tid < 162) {
-        const int a = tid - 156, j = 6 * m.K + 6 * nr.frame + a;
-        if (d.active[m.u0 + j]) Ys[j * 16 + 9 + a] = 1.0;
-      }
-      if (tid == 0) s_first = 6 * nr.s;
-    }
-  } else if (t.kind == 3) {
-    const int q = tid >> 4, sub = tid & 15;
-    if (q < t.count) {   // -(w_l / Hll) j_rho^T: the row's planned span, then the line-delay column
-      const int row = m.lm0 + t.first + q, klo = d.lm_klo[row], khi = d.lm_khi[row];
-      const PointRec &pr = lrec[m.lm0 + d.lm_at[row]];
-      const double dv = d.dinv[row];
-      const double *Wr = d.WS[cur] + m.W0 + (long long)(t.first + q) * m.ldw;
-      if (pr.status == LMP_OK && khi >= klo && dv != 0.0) {
-        const double j0 = -pr.jrho[0], j1 = -pr.jrho[1], j2 = -pr.jrho[2];
-        const int cend = min(6 * khi + 6, P);
-        for (int c = 6 * klo + sub; c < cend; c += 16)
-          if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 3 * q] = v * j0; Ys[c * 16 + 3 * q + 1] = v * j1; Ys[c * 16 + 3 * q + 2] = v * j2; }
-        if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
-          const double v = Wr[P - 1] * dv;
-          Ys[(P - 1) * 16 + 3 * q] = v * j0; Ys[(P - 1) * 16 + 3 * q + 1] = v * j1; Ys[(P - 1) * 16 + 3 * q + 2] = v * j2;
-        }
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < 75 * t.count; e += COV_NT) {   // + Jp^T: rows 6 s .. 6 (s + nk) - 1 (r < 24), then the line-delay row (r = 24)
-      const int q = e / 75, r = (e % 75) / 3, a = e % 3;
-      const PointRec &pr = lrec[m.lm0 + d.lm_at[m.lm0 + t.first + q]];
-      if (pr.status != LMP_OK) continue;
-      const int c = r < 24 ? 6 * pr.s + r : P - 1;
-      if ((r < 6 * pr.nk || r == 24) && d.active[m.u0 + c]) Ys[c * 16 + 3 * q + a] += r < 24 ? pr.jt[3 * r + a] : pr.jld[a];
-    }
-    if (tid == 0)
-      for (int q = 0; q < t.count; ++q) {
-        const int row = m.lm0 + t.first + q;
-        const PointRec &pr = lrec[m.lm0 + d.lm_at[row]];
-        if (pr.status != LMP_OK) continue;
-        s_first = min(s_first, 6 * pr.s);
-        if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
-      }
-  } else {
-    const int col = tid >> 4, sub = tid & 15;
-    if (col < t.count) {
-      const int row = m.lm0 + t.first + col, klo = d.lm_klo[row], khi = d.lm_khi[row];
-      const double dv = d.dinv[row];
-      const double *Wr = d.WS[cur] + m.W0 + (long long)(t.first + col) * m.ldw;
-      if (khi >= klo && dv != 0.0) {   // the row's planned span, then the line-delay column
-        const int cend = min(6 * khi + 6, P);
-        for (int c = 6 * klo + sub; c < cend; c += 16)
-          if (d.active[m.u0 + c]) Ys[c * 16 + col] = Wr[c] * dv;
-        if (sub == 0) {
-          if (cend <= P - 1 && d.active[m.u0 + P - 1]) Ys[(P - 1) * 16 + col] = Wr[P - 1] * dv;
-          atomicMin(&s_first, 6 * klo);
-        }
+  }
+}
+// TILE_GATE: the leave-one-out epilogue, one lane per block
+__device__ __forceinline__ void cov_gate_epilogue(const CovCtx &x, int b0, const GateRec *rec, const GateOut &gate, int slot_base) {
+  const WinMeta &m = x.m; const CovTile &t = x.t;
+  const int tid = x.tid;
+  cov_gram2_partials(x, b0);
+  if (tid < t.count) {
+    const GateRec &pr = rec[t.first + tid];
+    if (pr.status == PRJ_OK) {
+      const double dv = x.d.dinv[m.lm0 + pr.wrow], w2 = m.img_w * m.img_w;
+      double c[3];   // Cw = img_w^2 C
+#pragma unroll
+      for (int v = 0; v < 3; ++v) c[v] = w2 * cov_gram2(x.part(), tid, v, pr.j, dv);
+      const double s00 = pr.S[0], s01 = pr.S[1], s11 = pr.S[2];
+      // T = Cw S, A = S T, M = I - A
+      const double t00 = c[0] * s00 + c[1] * s01, t01 = c[0] * s01 + c[1] * s11, t10 = c[1] * s00 + c[2] * s01, t11 = c[1] * s01 + c[2] * s11;
+      const double m00 = 1.0 - (s00 * t00 + s01 * t10), m01 = -(s00 * t01 + s01 * t11), m11 = 1.0 - (s01 * t01 + s11 * t11);
+      const double hd = 0.5 * (m00 - m11), red = 0.5 * (m00 + m11) - sqrt(hd * hd + m01 * m01);
+      const size_t k = (size_t)(slot_base + t.first + tid - gate.slot0);
+      if (gate.red) gate.red[k] = red;
+      if (!(red >= gate.min_red)) {
+        gate.status[k] = GATE_WEAK;   // (cov4 and chi2 are the host's fill)
+      } else {
+        // C_loo = Cw + T M^-1 T^T: U = T M^-1, the three unique entries of U T^T
+        const double idet = 1.0 / (m00 * m11 - m01 * m01);
+        const double u00 = (t00 * m11 - t01 * m01) * idet, u01 = (t01 * m00 - t00 * m01) * idet, u10 = (t10 * m11 - t11 * m01) * idet, u11 = (t11 * m00 - t10 * m01) * idet;
+        const double l0 = c[0] + (u00 * t00 + u01 * t01), l1 = c[1] + (u00 * t10 + u01 * t11), l2 = c[2] + (u10 * t10 + u11 * t11);
+        if (gate.cov4) { double *o = gate.cov4 + 4 * k; o[0] = l0; o[1] = l1; o[2] = l1; o[3] = l2; }
+        if (gate.chi2) gate.chi2[k] = cov_gate2(l0, l1, l2, 1.0, pr.r[0], pr.r[1]);   // from the values just written
       }
     }
   }
+}
+
+// ---- the three stages
+template <CovInst I> __device__ __forceinline__ void cov_prologue(const CovCtx &x, const CovSolveIO<I> &io) {
+  if constexpr (I == COV_REL) cov_rel_prologue(x, io.rec);
+  else if constexpr (I == COV_RATES) cov_rates_prologue(x, io.rec[x.t.first]);
+  else cov_proj_prologue<I>(x, io.rec);   // COV_PROJ, COV_PRED, COV_GATE
+}
+// Y = L^-1 B in place, from the block of the tile's first non-zero row on; returns that block (nblk for a tile of zero columns).
+__device__ __forceinline__ int cov_forward_subst(const CovCtx &x) {
+  const Dev &d = x.d; const WinMeta &m = x.m;
+  const int w = x.t.win, P = x.P, ldh = x.ldh, nblk = (P + 31) / 32, wave = x.wave, lane = x.tid & 63, q4 = lane >> 4, l15 = lane & 15;
+  double *Ys = x.Ys(), *part = x.part();
   __syncthreads();
-  const int b0 = s_first / 32;   // (PP / 32 = nblk for a tile of zero columns: nothing to substitute)
+  const int b0 = *x.first / 32;
   const double *S = d.S + m.H0;
   const int32_t *ef = d.env_first + m.tr0;
   const int h = wave & 1, kp = wave >> 1;
@@ -1154,197 +1188,159 @@ __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     __syncthreads();
   }
-  if constexpr (PRED) {   // prediction tiles: kind 6's Gram epilogue, + A N A^T on the three unique entries, mirrored; then the gate
-    const int k0 = min(32 * b0, P);
-    constexpr int NE = 3 * PRJ_PER_TILE;
-    if (tid < 4 * NE) {
-      const int p = tid / NE, e = tid % NE, x = e % 3, ci = 2 * (e / 3) + (x == 2), cj = 2 * (e / 3) + (x != 0);
-      double s = 0.0;
-      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
-      part[p * NE + e] = s;
-    }
-    __syncthreads();
-    if (tid < t.count) {
-      const PredRec &pr = prec[t.first + tid];
-      if (pr.status == PRJ_OK) {
-        const double dv = d.dinv[m.lm0 + pr.wrow];
-        double c[3];
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-          c[x] = ((((part[3 * tid + x] + part[NE + 3 * tid + x]) + part[2 * NE + 3 * tid + x]) + part[3 * NE + 3 * tid + x]) + (pr.j[x == 2] * pr.j[x != 0]) * dv) + pr.ana[x];
-        double *o = pose_cov + (long long)4 * (t.first + tid);
-        o[0] = c[0]; o[1] = c[1]; o[2] = c[1]; o[3] = c[2];
-        if (var_rho) {
-          const double iw2 = 1.0 / (m.img_w * m.img_w), e0 = pr.obs[0] - pr.proj[0], e1 = pr.obs[1] - pr.proj[1];
-          const double l00 = sqrt(c[0] + iw2), l10 = c[1] / l00, l11 = sqrt((c[2] + iw2) - l10 * l10);
-          const double z0 = e0 / l00, z1 = (e1 - l10 * z0) / l11;
-          var_rho[t.first + tid] = z0 * z0 + z1 * z1;
+  return b0;
+}
+template <CovInst I> __device__ __forceinline__ void cov_epilogue(const CovCtx &x, const CovSolveIO<I> &io, int b0) {
+  if constexpr (I == COV_PRED || I == COV_PROJ) cov_proj_epilogue<I>(x, b0, io.rec, io.blocks, io.chi2);
+  else if constexpr (I == COV_RATES) cov_rates_epilogue(x, b0, io.rec[x.t.first], io.slot + x.t.first, io.blocks, io.chi2);
+  else if constexpr (I == COV_GATE) cov_gate_epilogue(x, b0, io.rec, io.gate, io.slot_base);
+  else cov_gram6(x, b0, io.slot, io.blocks);   // COV_REL
+}
+// amdgpu_waves_per_eu: with the stages of five kinds in it COV_BASE otherwise settles at 58 VGPRs + 8 AGPRs, one wave per SIMD short of the eight
+// that the LDS of a tile allows up to P = 128; held to eight it uses 60 VGPRs, no AGPRs, no spill.
+template <CovInst I>
+__global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, CovSolveIO<I> io) {
+  const int g0 = PRJ_PER_TILE * (int)blockIdx.x;   // (COV_GATE: the tile's first slot in the slice)
+  const CovTile t = I == COV_GATE ? CovTile{d.vb_win[(io.slot_base + g0) / 64], TILE_GATE, g0, min(PRJ_PER_TILE, io.gate.nslot - g0), 0} : io.tiles[blockIdx.x];
+  const WinMeta &m = d.wins[t.win];
+  const int P = m.P, tid = threadIdx.x, PP = 32 * ((P + 31) / 32);
+  __shared__ int s_first;
+  const CovCtx x{d, CovTile{t.win, t.kind, t.first, t.count, t.yoff}, m, P, m.ldh, d.lm[t.win].cur, tid, __builtin_amdgcn_readfirstlane(tid >> 6), &s_first};
+  for (int e = tid; e < 16 * PP; e += COV_NT) cov_lds[e] = 0.0;
+  if (tid == 0) s_first = PP;
+  __syncthreads();
+  const int cur = x.cur;   // (COV_BASE's stages stand here, in the kernel: see DESIGN.md on their register count.  Ys and part are x's: the helpers the
+                           // ladders call -- cov_forward_subst, cov_gram6, cov_gram15 -- read the same LDS through x)
+  double *Ys = x.Ys(), *part = x.part();
+  if constexpr (I == COV_BASE) {   // the five kinds of ctvio_covariance, pose_covariance, nav_state and landmark_points, by t.kind
+    if (t.kind == TILE_SEL) {
+      if (tid < t.count) {
+        const int j = io.sel[t.first + tid];
+        if (d.active[m.u0 + j]) { Ys[j * 16 + tid] = 1.0; atomicMin(&s_first, j); }   // (an excluded unknown: a zero column, finished by k_cov_gram)
+      }
+    } else if (t.kind == TILE_POSE) {   // rows 6 s .. 6 (s + nk) - 1 of every query's six columns, where the unknown is in the system
+      for (int e = tid; e < 144 * t.count; e += COV_NT) {
+        const int qi = e / 144, r = (e % 144) / 6, a = e % 6;
+        const PoseRec &pr = io.rec[t.first + qi];
+        if (pr.status == POSE_OK && r < 6 * pr.nk && d.active[m.u0 + 6 * pr.s + r]) Ys[(6 * pr.s + r) * 16 + 6 * qi + a] = pr.jt[6 * r + a];
+      }
+      if (tid == 0)
+        for (int qi = 0; qi < t.count; ++qi)
+          if (io.rec[t.first + qi].status == POSE_OK) s_first = min(s_first, 6 * io.rec[t.first + qi].s);
+    } else if (t.kind == TILE_NAV) {   // pose columns 0..5 and velocity columns 6..8 over rows 6 s .. 6 (s + nk) - 1, one-hot bias columns 9..14 over the
+                                // rows of bias state f, each where the unknown is in the system
+      const NavRec &nr = io.nrec[t.first];
+      if (nr.status == POSE_OK) {
+        if (tid < 144) {
+          const int r = tid / 6, a = tid % 6;
+          if (r < 6 * nr.nk && d.active[m.u0 + 6 * nr.s + r]) Ys[(6 * nr.s + r) * 16 + a] = nr.jt[tid];
+        } else if (tid < 156) {   // d(dv_a) / d(position a of knot s + kk) = c'_kk / dt
+          const int kk = (tid - 144) / 3, a = (tid - 144) % 3, j = 6 * (nr.s + kk) + 3 + a;
+          if (kk < nr.nk && d.active[m.u0 + j]) Ys[j * 16 + 6 + a] = nr.cv[kk];
+        } else if (tid < 162) {
+          const int a = tid - 156, j = 6 * m.K + 6 * nr.frame + a;
+          if (d.active[m.u0 + j]) Ys[j * 16 + 9 + a] = 1.0;
+        }
+        if (tid == 0) s_first = 6 * nr.s;
+      }
+    } else if (t.kind == TILE_POINT) {
+      const int q = tid >> 4, sub = tid & 15;
+      if (q < t.count) {   // -(w_l / Hll) j_rho^T: the row's planned span, then the line-delay column
+        const int row = m.lm0 + t.first + q, klo = d.lm_klo[row], khi = d.lm_khi[row];
+        const PointRec &pr = io.lrec[m.lm0 + d.lm_at[row]];
+        const double dv = d.dinv[row];
+        const double *Wr = d.WS[cur] + m.W0 + (long long)(t.first + q) * m.ldw;
+        if (pr.status == LMP_OK && khi >= klo && dv != 0.0) {
+          const double j0 = -pr.jrho[0], j1 = -pr.jrho[1], j2 = -pr.jrho[2];
+          const int cend = min(6 * khi + 6, P);
+          for (int c = 6 * klo + sub; c < cend; c += 16)
+            if (d.active[m.u0 + c]) { const double v = Wr[c] * dv; Ys[c * 16 + 3 * q] = v * j0; Ys[c * 16 + 3 * q + 1] = v * j1; Ys[c * 16 + 3 * q + 2] = v * j2; }
+          if (sub == 0 && cend <= P - 1 && d.active[m.u0 + P - 1]) {
+            const double v = Wr[P - 1] * dv;
+            Ys[(P - 1) * 16 + 3 * q] = v * j0; Ys[(P - 1) * 16 + 3 * q + 1] = v * j1; Ys[(P - 1) * 16 + 3 * q + 2] = v * j2;
+          }
         }
       }
-    }
-    return;
-  }
-  if constexpr (RATES) {   // rates tiles: kind 4's 15 x 15 Gram block, then the gate of the IMU sample, one lane per tile
-    const RatesRec &rr = prec[t.first];
-    if (rr.status != POSE_OK) return;
-    cov_gram15(Ys, part, min(32 * b0, P), P, tid, pose_cov, sel + t.first, true);
-    if (!var_rho) return;
-    __syncthreads();
-    double *Sm = part + 128, *zv = Sm + 36;   // S = A C A^T + diag(sigma^2), A = [[I, 0, 0, I, 0], [0, I, 0, 0, I]]: rows a and 9 + a of C; then
-                                              // its Cholesky factor in place (lower triangle); z = L^-1 e
-    if (tid < 21) {
-      int a, b;
-      tile_decode(tid, a, b);
-      const double c = ((part[a * (a + 1) / 2 + b] + part[(9 + b) * (10 + b) / 2 + a]) + part[(9 + a) * (10 + a) / 2 + b]) + part[(9 + a) * (10 + a) / 2 + 9 + b];
-      Sm[6 * a + b] = a == b ? c + rr.sig[a] * rr.sig[a] : c;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double chi = 0.0;
-      for (int j = 0; j < 6; ++j) {   // column j of L, then z_j of L z = e
-        double dj = Sm[7 * j], ej = rr.meas[j] - rr.z[j];
-        for (int k = 0; k < j; ++k) { dj -= Sm[6 * j + k] * Sm[6 * j + k]; ej -= Sm[6 * j + k] * zv[k]; }
-        const double ljj = sqrt(dj);
-        for (int i = j + 1; i < 6; ++i) {
-          double x = Sm[6 * i + j];
-          for (int k = 0; k < j; ++k) x -= Sm[6 * i + k] * Sm[6 * j + k];
-          Sm[6 * i + j] = x / ljj;
-        }
-        const double zj = ej / ljj;
-        zv[j] = zj;
-        chi += zj * zj;
+      __syncthreads();
+      for (int e = tid; e < 75 * t.count; e += COV_NT) {   // + Jp^T: rows 6 s .. 6 (s + nk) - 1 (r < 24), then the line-delay row (r = 24)
+        const int q = e / 75, r = (e % 75) / 3, a = e % 3;
+        const PointRec &pr = io.lrec[m.lm0 + d.lm_at[m.lm0 + t.first + q]];
+        if (pr.status != LMP_OK) continue;
+        const int c = r < 24 ? 6 * pr.s + r : P - 1;
+        if ((r < 6 * pr.nk || r == 24) && d.active[m.u0 + c]) Ys[c * 16 + 3 * q + a] += r < 24 ? pr.jt[3 * r + a] : pr.jld[a];
       }
-      var_rho[sel[t.first]] = chi;
-    }
-    return;
-  }
-  if constexpr (GATE) {   // block tiles: kind 6's Gram entries, then the leave-one-out epilogue of ctvio_visual_gate_batch, one lane per block
-    const int k0 = min(32 * b0, P);
-    constexpr int NE = 3 * PRJ_PER_TILE;
-    if (tid < 4 * NE) {
-      const int p = tid / NE, e = tid % NE, x = e % 3, ci = 2 * (e / 3) + (x == 2), cj = 2 * (e / 3) + (x != 0);
-      double s = 0.0;
-      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
-      part[p * NE + e] = s;
-    }
-    __syncthreads();
-    if (tid < t.count) {
-      const GateRec &pr = prec[t.first + tid];
-      if (pr.status == PRJ_OK) {
-        const double dv = d.dinv[m.lm0 + pr.wrow], w2 = m.img_w * m.img_w;
-        double c[3];   // Cw = img_w^2 C
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-          c[x] = w2 * ((((part[3 * tid + x] + part[NE + 3 * tid + x]) + part[2 * NE + 3 * tid + x]) + part[3 * NE + 3 * tid + x]) + (pr.j[x == 2] * pr.j[x != 0]) * dv);
-        const double s00 = pr.S[0], s01 = pr.S[1], s11 = pr.S[2];
-        // T = Cw S, A = S T, M = I - A
-        const double t00 = c[0] * s00 + c[1] * s01, t01 = c[0] * s01 + c[1] * s11, t10 = c[1] * s00 + c[2] * s01, t11 = c[1] * s01 + c[2] * s11;
-        const double m00 = 1.0 - (s00 * t00 + s01 * t10), m01 = -(s00 * t01 + s01 * t11), m11 = 1.0 - (s01 * t01 + s11 * t11);
-        const double hd = 0.5 * (m00 - m11), red = 0.5 * (m00 + m11) - sqrt(hd * hd + m01 * m01);
-        const size_t k = (size_t)(lm_base + t.first + tid - gate.slot0);
-        if (gate.red) gate.red[k] = red;
-        if (!(red >= gate.min_red)) {
-          gate.status[k] = GATE_WEAK;   // (cov4 and chi2 are the host's fill)
-        } else {
-          // C_loo = Cw + T M^-1 T^T: U = T M^-1, the three unique entries of U T^T
-          const double idet = 1.0 / (m00 * m11 - m01 * m01);
-          const double u00 = (t00 * m11 - t01 * m01) * idet, u01 = (t01 * m00 - t00 * m01) * idet, u10 = (t10 * m11 - t11 * m01) * idet, u11 = (t11 * m00 - t10 * m01) * idet;
-          const double l0 = c[0] + (u00 * t00 + u01 * t01), l1 = c[1] + (u00 * t10 + u01 * t11), l2 = c[2] + (u10 * t10 + u11 * t11);
-          if (gate.cov4) { double *o = gate.cov4 + 4 * k; o[0] = l0; o[1] = l1; o[2] = l1; o[3] = l2; }
-          if (gate.chi2) {   // r^T (C_loo + I)^-1 r by the 2 x 2 Cholesky factor, from the values just written
-            const double f00 = sqrt(l0 + 1.0), f10 = l1 / f00, f11 = sqrt((l2 + 1.0) - f10 * f10);
-            const double z0 = pr.r[0] / f00, z1 = (pr.r[1] - f10 * z0) / f11;
-            gate.chi2[k] = z0 * z0 + z1 * z1;
+      if (tid == 0)
+        for (int q = 0; q < t.count; ++q) {
+          const int row = m.lm0 + t.first + q;
+          const PointRec &pr = io.lrec[m.lm0 + d.lm_at[row]];
+          if (pr.status != LMP_OK) continue;
+          s_first = min(s_first, 6 * pr.s);
+          if (d.lm_khi[row] >= d.lm_klo[row]) s_first = min(s_first, 6 * d.lm_klo[row]);
+        }
+    } else {
+      const int col = tid >> 4, sub = tid & 15;
+      if (col < t.count) {
+        const int row = m.lm0 + t.first + col, klo = d.lm_klo[row], khi = d.lm_khi[row];
+        const double dv = d.dinv[row];
+        const double *Wr = d.WS[cur] + m.W0 + (long long)(t.first + col) * m.ldw;
+        if (khi >= klo && dv != 0.0) {   // the row's planned span, then the line-delay column
+          const int cend = min(6 * khi + 6, P);
+          for (int c = 6 * klo + sub; c < cend; c += 16)
+            if (d.active[m.u0 + c]) Ys[c * 16 + col] = Wr[c] * dv;
+          if (sub == 0) {
+            if (cend <= P - 1 && d.active[m.u0 + P - 1]) Ys[(P - 1) * 16 + col] = Wr[P - 1] * dv;
+            atomicMin(&s_first, 6 * klo);
           }
         }
       }
     }
-    return;
-  }
-  if constexpr (PROJ) {   // projection tiles: entries (0,0), (0,1), (1,1) of the eight 2 x 2 Gram blocks, then the gate
-    const int k0 = min(32 * b0, P);
-    constexpr int NE = 3 * PRJ_PER_TILE;
-    if (tid < 4 * NE) {
-      const int p = tid / NE, e = tid % NE, x = e % 3, ci = 2 * (e / 3) + (x == 2), cj = 2 * (e / 3) + (x != 0);
+  } else cov_prologue<I>(x, io);
+  const int b0 = cov_forward_subst(x);
+  if constexpr (I == COV_BASE) {
+    if (t.kind == TILE_SEL) {   // a selection tile: Y to the scratch, for k_cov_gram
+      double *yo = io.Y + t.yoff;
+      for (int e = tid; e < 16 * P; e += COV_NT) yo[e] = Ys[e];
+      return;
+    }
+    if (t.kind == TILE_POSE) { cov_gram6(x, b0, io.slot, io.blocks); return; }
+    if (t.kind == TILE_NAV) {   // state tiles: the 15 x 15 Gram block
+      cov_gram15(Ys, part, min(32 * b0, P), P, tid, io.nav_cov, io.slot + t.first, false);
+      return;
+    }
+    if (t.kind == TILE_POINT) {   // point tiles: the five 3 x 3 Gram blocks; every entry four partial sums over the rows k = p mod 4, added in sequence
+      const int k0 = min(32 * b0, P);
+      constexpr int NE = 9 * LMP_PER_TILE;
+      if (tid < 4 * NE) {
+        const int p = tid / NE, e = tid % NE, ci = 3 * (e / 9) + (e % 9) / 3, cj = 3 * (e / 9) + e % 3;
+        double s = 0.0;
+        for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
+        part[p * NE + e] = s;
+      }
+      __syncthreads();
+      if (tid < 9 * t.count) {
+        const int q = tid / 9, a = (tid % 9) / 3, b = tid % 3, row = m.lm0 + t.first + q, l = m.lm0 + d.lm_at[row];
+        const PointRec &pr = io.lrec[l];
+        if (pr.status == LMP_OK)
+          io.lm_cov[(long long)9 * (l - io.lm_base) + 3 * a + b] = (((part[tid] + part[NE + tid]) + part[2 * NE + tid]) + part[3 * NE + tid]) + (pr.jrho[a] * pr.jrho[b]) * d.dinv[row];
+      }
+      return;
+    }
+    // ---- a landmark tile: column sums of squares in a fixed order (16 strided partial sums per column, then added in sequence)
+    {
+      const int col = tid & 15, p = tid >> 4;
       double s = 0.0;
-      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
-      part[p * NE + e] = s;
+      for (int k = min(32 * b0, P) + p; k < P; k += 16) { const double v = Ys[k * 16 + col]; s += v * v; }
+      part[p * 16 + col] = s;
     }
     __syncthreads();
     if (tid < t.count) {
-      const ProjRec &pr = prec[t.first + tid];
-      if (pr.status == PRJ_OK) {
-        const double dv = d.dinv[m.lm0 + pr.wrow];
-        double c[3];
-#pragma unroll
-        for (int x = 0; x < 3; ++x)
-          c[x] = (((part[3 * tid + x] + part[NE + 3 * tid + x]) + part[2 * NE + 3 * tid + x]) + part[3 * NE + 3 * tid + x]) + (pr.j[x == 2] * pr.j[x != 0]) * dv;
-        double *o = pose_cov + (long long)4 * (t.first + tid);
-        o[0] = c[0]; o[1] = c[1]; o[2] = c[1]; o[3] = c[2];
-        if (var_rho) {
-          const double iw2 = 1.0 / (m.img_w * m.img_w), e0 = pr.obs[0] - pr.proj[0], e1 = pr.obs[1] - pr.proj[1];
-          const double l00 = sqrt(c[0] + iw2), l10 = c[1] / l00, l11 = sqrt((c[2] + iw2) - l10 * l10);
-          const double z0 = e0 / l00, z1 = (e1 - l10 * z0) / l11;
-          var_rho[t.first + tid] = z0 * z0 + z1 * z1;
-        }
-      }
+      double tot = 0.0;
+      for (int p = 0; p < 16; ++p) tot += part[p * 16 + tid];
+      const int row = m.lm0 + t.first + tid, l = d.lm_at[row];
+      const double dv = d.dinv[row];
+      io.var_rho[m.lm0 + l] = dv == 0.0 ? __builtin_inf() : dv + tot;   // (Hll = 0: no information)
     }
-    return;
-  }
-  if (!REL && t.kind == 0) {   // a selection tile: Y to the scratch, for k_cov_gram
-    double *yo = yscr + t.yoff;
-    for (int e = tid; e < 16 * P; e += COV_NT) yo[e] = Ys[e];
-    return;
-  }
-  if (REL || t.kind == 2) {   // pose and relative-pose tiles: the two 6 x 6 Gram blocks straight from Ys; every entry three partial sums over the rows k = p mod 3, added in sequence
-    const int k0 = min(32 * b0, P) / 3 * 3;
-    if (tid < 216) {
-      const int p = tid / 72, e = tid % 72, ci = 6 * (e / 36) + (e % 36) / 6, cj = 6 * (e / 36) + e % 6;
-      double s = 0.0;
-      for (int k = k0 + p; k < P; k += 3) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
-      part[p * 72 + e] = s;
-    }
-    __syncthreads();
-    if (tid < 36 * t.count) pose_cov[(long long)36 * sel[t.first + tid / 36] + tid % 36] = (part[tid] + part[72 + tid]) + part[144 + tid];
-    return;
-  }
-  if (t.kind == 4) {   // state tiles: the 15 x 15 Gram block
-    cov_gram15(Ys, part, min(32 * b0, P), P, tid, nav_cov, sel + t.first, false);
-    return;
-  }
-  if (t.kind == 3) {   // point tiles: the five 3 x 3 Gram blocks; every entry four partial sums over the rows k = p mod 4, added in sequence
-    const int k0 = min(32 * b0, P);
-    constexpr int NE = 9 * LMP_PER_TILE;
-    if (tid < 4 * NE) {
-      const int p = tid / NE, e = tid % NE, ci = 3 * (e / 9) + (e % 9) / 3, cj = 3 * (e / 9) + e % 3;
-      double s = 0.0;
-      for (int k = k0 + p; k < P; k += 4) s += Ys[k * 16 + ci] * Ys[k * 16 + cj];
-      part[p * NE + e] = s;
-    }
-    __syncthreads();
-    if (tid < 9 * t.count) {
-      const int q = tid / 9, a = (tid % 9) / 3, b = tid % 3, row = m.lm0 + t.first + q, l = m.lm0 + d.lm_at[row];
-      const PointRec &pr = lrec[l];
-      if (pr.status == LMP_OK)
-        lm_cov[(long long)9 * (l - lm_base) + 3 * a + b] = (((part[tid] + part[NE + tid]) + part[2 * NE + tid]) + part[3 * NE + tid]) + (pr.jrho[a] * pr.jrho[b]) * d.dinv[row];
-    }
-    return;
-  }
-  // ---- a landmark tile: column sums of squares in a fixed order (16 strided partial sums per column, then added in sequence)
-  {
-    const int col = tid & 15, p = tid >> 4;
-    double s = 0.0;
-    for (int k = min(32 * b0, P) + p; k < P; k += 16) { const double v = Ys[k * 16 + col]; s += v * v; }
-    part[p * 16 + col] = s;
-  }
-  __syncthreads();
-  if (tid < t.count) {
-    double tot = 0.0;
-    for (int p = 0; p < 16; ++p) tot += part[p * 16 + tid];
-    const int row = m.lm0 + t.first + tid, l = d.lm_at[row];
-    const double dv = d.dinv[row];
-    var_rho[m.lm0 + l] = dv == 0.0 ? __builtin_inf() : dv + tot;   // (Hll = 0: no information)
-  }
+  } else cov_epilogue<I>(x, io, b0);
 }
 
 // cov[i][j] = Y_i^T Y_j over the pairs of selection tiles of a window (grid: pair, window with a selection); one entry per thread, summed over

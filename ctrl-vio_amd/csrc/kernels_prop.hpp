@@ -1,6 +1,6 @@
 // kernels_prop.hpp -- IMU dead reckoning past the end of the solve (ctvio_imu_predict_batch): k_imu_propagate carries the navigation state of
 // every query, and with it the 15 x 15 covariance, through the query's IMU samples by the midpoint rule (factors.hpp: imu_step).  It runs
-// after k_cov_nav_jac (+ k_cov_solve on tiles of kind 4) have left every query's state, status and covariance block on the device.
+// after k_cov_nav_jac (+ k_cov_solve on TILE_NAV tiles) have left every query's state, status and covariance block on the device.
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).
 //
 //   P_j = F P_{j-1} F^T + G Q G^T,   Q = diag(gyr_n^2, acc_n^2, gyr_n^2, acc_n^2, gyr_w^2, acc_w^2) (x) I_3,

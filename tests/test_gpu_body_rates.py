@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_body_rates_batch / ctvio_body_rates (csrc/kernels_cov.hpp: k_cov_rates_jac, k_cov_solve tiles of kind 7) against the
+"""GPU (-m gpu): ctvio_body_rates_batch / ctvio_body_rates (csrc/kernels_cov.hpp: k_cov_rates_jac, k_cov_solve tiles of kind TILE_RATES) against the
 NumPy reference: cov_helpers.cov_reference on the DEVICE's own ctvio_linearize output of the same state with all P unknowns selected (as
 tests/test_gpu_nav_state.py, and for its reason), mapped through the NumPy Jacobian of tests/rates_helpers.py.
 

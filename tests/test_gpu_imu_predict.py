@@ -1,5 +1,5 @@
 """GPU (-m gpu): ctvio_imu_predict_batch / ctvio_imu_predict (csrc/kernels_prop.hpp: k_imu_propagate after k_cov_nav_jac and k_cov_solve's tiles
-of kind 4) against the NumPy recurrence of tests/imuprop_helpers.py STARTED FROM THE DEVICE'S OWN ctvio_nav_state output for (window, imu_t[0],
+of kind TILE_NAV) against the NumPy recurrence of tests/imuprop_helpers.py STARTED FROM THE DEVICE'S OWN ctvio_nav_state output for (window, imu_t[0],
 frame): nav_state is held to the oracle by tests/test_gpu_nav_state.py, so this isolates the new kernel.
 
 The samples are drawn here (seeded default_rng): 200 Hz from the window's newest frame time with one 7 ms gap, gyro N(0, 0.5), acc R_0^T g +

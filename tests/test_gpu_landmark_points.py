@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_landmark_points_batch / ctvio_landmark_points (csrc/kernels_cov.hpp: k_cov_point_jac, k_cov_solve tiles of kind 3) against
+"""GPU (-m gpu): ctvio_landmark_points_batch / ctvio_landmark_points (csrc/kernels_cov.hpp: k_cov_point_jac, k_cov_solve tiles of kind TILE_POINT) against
 the NumPy reference of tests/lmpoint_helpers.py: the joint covariance of (trajectory, inverse depths) by the Jacobi-scaled inverse of the
 un-eliminated system, formed from the DEVICE's own ctvio_linearize output of the same state (as tests/test_gpu_covariance.py, and for its
 reason), mapped through the NumPy Jacobian [Jp | j_rho].

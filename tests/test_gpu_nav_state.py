@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_nav_state_batch / ctvio_nav_state (csrc/kernels_cov.hpp: k_cov_nav_jac, k_cov_solve tiles of kind 4) against the NumPy
+"""GPU (-m gpu): ctvio_nav_state_batch / ctvio_nav_state (csrc/kernels_cov.hpp: k_cov_nav_jac, k_cov_solve tiles of kind TILE_NAV) against the NumPy
 reference: cov_helpers.cov_reference on the DEVICE's own ctvio_linearize output of the same state with all P unknowns selected (as
 tests/test_gpu_pose_covariance.py, and for its reason), mapped through the NumPy Jacobian of tests/navstate_helpers.py.
 

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_pose_covariance_batch / ctvio_pose_covariance (csrc/kernels_cov.hpp: k_cov_pose_jac, k_cov_solve tiles of kind 2) against
+"""GPU (-m gpu): ctvio_pose_covariance_batch / ctvio_pose_covariance (csrc/kernels_cov.hpp: k_cov_pose_jac, k_cov_solve tiles of kind TILE_POSE) against
 the NumPy reference: cov_helpers.cov_reference on the DEVICE's own ctvio_linearize output of the same state with all P unknowns selected (as
 tests/test_gpu_covariance.py, and for its reason), mapped through the NumPy Jacobian of tests/posecov_helpers.py.
 

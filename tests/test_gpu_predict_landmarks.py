@@ -1,5 +1,5 @@
 """GPU (-m gpu): ctvio_predict_landmarks_batch / ctvio_predict_landmarks (csrc/kernels_prop.hpp: k_imu_transition; csrc/kernels_cov.hpp:
-k_cov_pred_jac, k_cov_solve tiles of kind 8) against the NumPy reference of tests/predproj_helpers.py.  The joint covariance of (trajectory,
+k_cov_pred_jac, k_cov_solve tiles of kind TILE_PRED) against the NumPy reference of tests/predproj_helpers.py.  The joint covariance of (trajectory,
 inverse depths) is formed from the DEVICE's own ctvio_linearize output of the same state (tests/test_gpu_landmark_points.device_reference, for
 the reason given there).  Samples are drawn as tests/test_gpu_imu_predict.draw draws them: 200 Hz from the newest frame time, one 7 ms gap.
 

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_project_landmarks_batch / ctvio_project_landmarks (csrc/kernels_cov.hpp: k_cov_proj_jac, k_cov_solve tiles of kind 6) against
+"""GPU (-m gpu): ctvio_project_landmarks_batch / ctvio_project_landmarks (csrc/kernels_cov.hpp: k_cov_proj_jac, k_cov_solve tiles of kind TILE_PROJ) against
 the NumPy reference of tests/projection_helpers.py: the joint covariance of (trajectory, inverse depths) by the Jacobi-scaled inverse of the
 un-eliminated system, formed from the DEVICE's own ctvio_linearize output of the same state (as tests/test_gpu_landmark_points.py, and for its
 reason), mapped through the NumPy Jacobian [Jp | j].

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_relative_pose_batch / ctvio_relative_pose (csrc/kernels_cov.hpp: k_cov_rel_jac, k_cov_solve tiles of kind 5) against the
+"""GPU (-m gpu): ctvio_relative_pose_batch / ctvio_relative_pose (csrc/kernels_cov.hpp: k_cov_rel_jac, k_cov_solve tiles of kind TILE_REL) against the
 NumPy reference: cov_helpers.cov_reference on the DEVICE's own ctvio_linearize output of the same state with all P unknowns selected (as
 tests/test_gpu_pose_covariance.py, and for its reason), mapped through the NumPy J_rel of tests/relpose_helpers.py.
 

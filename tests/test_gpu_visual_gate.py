@@ -1,4 +1,4 @@
-"""GPU (-m gpu): ctvio_visual_gate_batch / ctvio_visual_gate (csrc/kernels_cov.hpp: k_cov_gate_jac, k_cov_solve tiles of kind 9,
+"""GPU (-m gpu): ctvio_visual_gate_batch / ctvio_visual_gate (csrc/kernels_cov.hpp: k_cov_gate_jac, k_cov_solve tiles of kind TILE_GATE,
 k_cov_gate_reduce) against the NumPy reference of tests/visgate_helpers.py on the DEVICE's own ctvio_linearize output of the same state (as
 tests/test_gpu_project_landmarks.py, and for its reason).
 

@@ -1,9 +1,11 @@
 #!/usr/bin/env python
-"""Bit comparison of the covariance entries between two builds of the library, on one GPU.  `dump OUT.npz` runs ctvio_covariance_batch (with
-var_rho), ctvio_pose_covariance_batch (body and camera pose), ctvio_landmark_points_batch and ctvio_nav_state_batch -- the tiles of kinds 0 to
-4 of k_cov_solve -- on the mixed batch of tests/test_gpu_covariance.py under deterministic = 2, at the initial state and after a 6-iteration
-solve, and ctvio_covariance with 64 scattered selections + var_rho on a solved `config1` window, with the library CTVIO_LIB_PATH names
-(default: the in-tree build), and saves every output and the solved state.  `compare A.npz B.npz` lists the
+"""Bit comparison of the covariance entries between two builds of the library, on one GPU.  `dump OUT.npz` runs every entry that goes through
+k_cov_solve -- ctvio_covariance_batch (with var_rho), ctvio_pose_covariance_batch (body and camera pose), ctvio_landmark_points_batch,
+ctvio_nav_state_batch, ctvio_relative_pose_batch, ctvio_project_landmarks_batch, ctvio_body_rates_batch, ctvio_imu_predict_batch,
+ctvio_predict_landmarks_batch and ctvio_visual_gate_batch, each with every optional output (gates, row model) -- on the mixed batch of
+tests/test_gpu_covariance.py under deterministic = 2, at the initial state and after a 6-iteration solve, and on a solved `config1` window
+(ctvio_covariance with 64 scattered selections + var_rho there), with the library CTVIO_LIB_PATH names (default: the in-tree build), and
+saves every output and the solved state.  The query sets are those of the entries' own GPU tests.  `compare A.npz B.npz` lists the
 arrays whose bits differ (exit status 1 if any).  Not a test: the second build has to come from another checkout.
 usage: python tools/covariance_bits.py dump new.npz; CTVIO_LIB_PATH=/other/libctvio.so python tools/covariance_bits.py dump old.npz;
        python tools/covariance_bits.py compare new.npz old.npz"""
@@ -16,6 +18,41 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
     sys.path.insert(0, p)
+
+
+def put(out, tag, res):
+    """the arrays of an entry's result: a tuple, or a namespace"""
+    items = vars(res).items() if hasattr(res, "__dict__") else enumerate(res)
+    for k, v in items:
+        if isinstance(v, np.ndarray):
+            out[f"{tag}_{k}"] = v
+
+
+def query_entries(out, tag, s, ws):
+    """relative_pose, project_landmarks, body_rates, imu_predict, predict_landmarks and visual_gate on the windows ws as uploaded to s"""
+    import test_gpu_imu_predict as ti
+    import test_gpu_predict_landmarks as tl
+    import test_gpu_project_landmarks as tp
+    from test_gpu_nav_state import mixed_queries as nav_queries
+    from test_gpu_relative_pose import mixed_queries as rel_queries
+    put(out, f"{tag}_rel", s.relative_pose_batch(*rel_queries(ws)))
+    put(out, f"{tag}_rel_camera", s.relative_pose_batch(*rel_queries(ws), ws[-1].q_CI, ws[-1].p_CI))
+    win, Q = tp.mixed_queries(ws)
+    obs = np.stack([0.01 * np.cos(np.arange(len(Q))), 0.01 * np.sin(np.arange(len(Q)))], 1)
+    put(out, f"{tag}_proj", s.project_landmarks_batch(win, *tp.cols(Q), obs=obs))
+    put(out, f"{tag}_proj_rows", s.project_landmarks_batch(win, *tp.cols(Q), obs=obs, row_model=(400.0, 240.0, 480, 3)))
+    nwin, nt, nf = nav_queries(ws)
+    meas = np.tile(np.array([0.1, -0.2, 0.3, 0.5, -0.4, 9.6]), (len(nwin), 1))
+    put(out, f"{tag}_rates", s.body_rates_batch(nwin, nt, nf, meas=meas))
+    pw, fr, ms, sam = ti.mixed_queries(ws)
+    put(out, f"{tag}_imu", s.imu_predict_batch(pw, fr, ms, *ti.cat(sam, range(len(pw)))))
+    preds = [([0, w.F - 1, w.F // 2, w.F - 1][i % 4],) + tl.draw(w, [21, 5, 21, 1][i % 4], 600 + i) for i, w in enumerate(ws)]
+    pts = [(i, l, (53 * l + 7) % 480) for i, w in enumerate(ws) for l in range(w.L)]
+    pobs = np.stack([0.01 * np.sin(np.arange(len(pts))), 0.01 * np.cos(np.arange(len(pts)))], 1)
+    put(out, f"{tag}_pred", tl.batch_call(s, list(range(len(ws))), preds, pts, obs=pobs))
+    put(out, f"{tag}_pred_rows", tl.batch_call(s, list(range(len(ws))), preds, pts, obs=pobs, row_model=(400.0, 240.0, 480, 3)))
+    put(out, f"{tag}_gate", s.visual_gate_batch())
+    put(out, f"{tag}_gate_strict", s.visual_gate_batch(min_redundancy=0.5))
 
 
 def dump(path):
@@ -39,6 +76,7 @@ def dump(path):
             out[f"{tag}_pose_camera"], _ = s.pose_covariance_batch(win, t, ws[1].q_CI, ws[1].p_CI)
             out[f"{tag}_points"], out[f"{tag}_points_cov"], out[f"{tag}_points_status"] = s.landmark_points_batch()
             out[f"{tag}_nav"], out[f"{tag}_nav_cov"], out[f"{tag}_nav_status"] = s.nav_state_batch(nwin, nt, nf)
+            query_entries(out, tag, s, ws)
             s.solve(6, writeback=False)
         for i, a in enumerate(s.get_batch_state()):
             out[f"state{i}"] = a
@@ -47,6 +85,7 @@ def dump(path):
         s.set_windows([w.copy()])
         s.solve(15, writeback=False)
         out["config1_cov"], out["config1_var"], _ = s.covariance(0, ch.scattered_selection(w, 64), rho=True)
+        query_entries(out, "config1", s, [w])
     np.savez(path, **out)
     print(f"saved {len(out)} arrays to {path}")
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two device assembly files (the `*-gfx950.s` that `hipcc -save-temps` leaves):
-    isa_diff.py <parent.s> <branch.s>
+    isa_diff.py <parent.s> <branch.s> [old=new ...]
+Every `old=new` is a substring rename applied to the parent's text before the comparison, so that a kernel whose mangled name changed (new
+template parameters, a new argument list) is compared with its successor instead of being reported GONE / NEW.
 A kernel runs from its `_Z...:` label to its `.Lfunc_end`; comment text after `;`, empty lines and the `.loc` / `.file` /
 `.cfi` / `.p2align` lines are dropped, and the function's index in its local labels (`.LBB34_10`: it shifts when a kernel elsewhere in the file
 changes its name or place) is taken out; the remaining lines are compared.  Exit status 1 if any kernel differs."""
@@ -11,9 +13,11 @@ DROP = re.compile(r"\s*\.(loc|file|cfi\w*|p2align)\b")
 LABEL = re.compile(r"\.L([A-Za-z]+)\d+_")
 
 
-def kernels(path):
+def kernels(path, renames=()):
     out, name, funcs = {}, None, set()
     for line in open(path):
+        for old, new in renames:
+            line = line.replace(old, new)
         f = re.match(r"\s*\.type\s+(_Z\w+),@function", line)
         if f:
             funcs.add(f.group(1))
@@ -32,8 +36,8 @@ def kernels(path):
     return out
 
 
-def main(parent, branch):
-    a, b = kernels(parent), kernels(branch)
+def main(parent, branch, *renames):
+    a, b = kernels(parent, [r.split("=", 1) for r in renames]), kernels(branch)
     changed = [k for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
     for k in changed:
         print(f"DIFF  {k}: {len(a.get(k, []))} -> {len(b.get(k, []))} lines" if k in a and k in b
@@ -43,4 +47,4 @@ def main(parent, branch):
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    sys.exit(main(*sys.argv[1:]))

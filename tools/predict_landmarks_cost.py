@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Device times (ctvio_last_timing, the library's HIP events) of ctvio_predict_landmarks_batch beside ctvio_project_landmarks_batch on the same
 handle, on one GPU: one prediction of 21 samples per window from its newest frame time and every landmark of the window under it at one row
-(tiles of kind 8: 8 points each), against the projection of every landmark into the newest frame (tiles of kind 6).  Three batches: the mixed
+(TILE_PRED tiles: 8 points each), against the projection of every landmark into the newest frame (TILE_PROJ tiles).  Three batches: the mixed
 batch of the tests (4 windows, solved 6 iterations, order-fixed), `config1` seed 1000 solved 15 iterations, and --windows config-2 windows
 (P 211, L 200) solved 15 iterations.  After a warm-up the calls alternate; the median of the repetitions is printed, one JSON line per batch.
 Not a test.

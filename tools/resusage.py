@@ -12,7 +12,7 @@ for line in err.splitlines():
     m = re.search(r"remark: [^:]*:?\s*(Function Name|Name): (\S+)", line) or re.search(r"(Function Name|Name): (\S+)", line)
     if m:
         name = subprocess.run(["c++filt", m.group(2)], capture_output=True, text=True).stdout.strip()
-        cur = {"name": re.sub(r"ctv::|\(.*", "", name)}
+        cur = {"name": re.sub(r"ctv::|\(ctv::CovInst\)|\(.*", "", name)}   # (an enum template argument prints as a cast)
         rows.append(cur)
         continue
     m = re.search(r"\s(SGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)

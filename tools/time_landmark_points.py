@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Device times (ctvio_last_timing, the library's HIP events) of three calls on 256 config-2 windows (P 211, L 200) solved 15 iterations, one
-handle, on one GPU: ctvio_landmark_points_batch with covariances (tiles of kind 3: ceil(L / 5) per window), the same points only (one
-kernel, nothing linearised) and ctvio_covariance_batch with var_rho and no selection (tiles of kind 1: ceil(L / 16) per window).  After a
+handle, on one GPU: ctvio_landmark_points_batch with covariances (TILE_POINT tiles: ceil(L / 5) per window), the same points only (one
+kernel, nothing linearised) and ctvio_covariance_batch with var_rho and no selection (TILE_RHO tiles: ceil(L / 16) per window).  After a
 warm-up of every call the three are timed in turn; the median of the repetitions is printed as one JSON line.  Not a test.
 usage: python tools/time_landmark_points.py [--windows N] [--reps N]"""
 import argparse

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Device times (ctvio_last_timing, the library's HIP events) of ctvio_project_landmarks_batch beside ctvio_landmark_points_batch on the same
-handle, on one GPU: one covariance call that projects every landmark once into the newest frame of its window (tiles of kind 6: 8 queries
-each) against the landmark cloud with covariances (tiles of kind 3: 5 landmarks each).  Three batches: the mixed batch of the tests (4
+handle, on one GPU: one covariance call that projects every landmark once into the newest frame of its window (TILE_PROJ tiles: 8 queries
+each) against the landmark cloud with covariances (TILE_POINT tiles: 5 landmarks each).  Three batches: the mixed batch of the tests (4
 windows, solved 6 iterations, order-fixed), `config1` seed 1000 solved 15 iterations, and --windows config-2 windows (P 211, L 200) solved 15
 iterations.  After a warm-up the two calls alternate; the median of the repetitions is printed, one JSON line per batch.  Not a test.
 usage: python tools/time_project_landmarks.py [--windows N] [--reps N]"""
