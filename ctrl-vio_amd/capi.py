@@ -101,7 +101,7 @@ SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "
            "ctvio_relative_pose_batch", "ctvio_relative_pose", "ctvio_project_landmarks_batch", "ctvio_project_landmarks",
            "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict", "ctvio_body_rates_batch", "ctvio_body_rates",
            "ctvio_predict_landmarks_batch", "ctvio_predict_landmarks",
-           "ctvio_default_gate_options", "ctvio_visual_gate_batch", "ctvio_visual_gate",
+           "ctvio_default_gate_options", "ctvio_visual_gate_batch", "ctvio_visual_gate", "ctvio_imu_gate_batch", "ctvio_imu_gate",
            "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
 _lib = None
@@ -172,6 +172,8 @@ def load_library():
         lib.ctvio_default_gate_options.restype = None
         lib.ctvio_visual_gate_batch.argtypes = [C.c_void_p, C.POINTER(GateOptions)] + [C.c_void_p] * 9
         lib.ctvio_visual_gate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GateOptions)] + [C.c_void_p] * 9
+        lib.ctvio_imu_gate_batch.argtypes = [C.c_void_p, C.POINTER(GateOptions)] + [C.c_void_p] * 6
+        lib.ctvio_imu_gate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GateOptions)] + [C.c_void_p] * 6
         lib.ctvio_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
         lib.ctvio_default_triangulate_options.restype = None
         lib.ctvio_triangulate_batch.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p]

@@ -59,7 +59,8 @@ struct DebugSwitches {
   int marg_host = 0;         // CTVIO_MARG_HOST=1        ctvio_marginalize on the host factorisation
   int marg_blocked = 0;      // CTVIO_MARG_BLOCKED=1     ctvio_marginalize_batch: every window through the blocked path (csrc/marg_blocked.hpp)
   int shard_oversubscribe = 0;   // CTVIO_SHARD_OVERSUBSCRIBE=1  TEST ONLY: more shards than devices (ctvio_shards_used)
-  int gate_slice = 0;        // CTVIO_GATE_SLICE=n       TEST ONLY: ctvio_visual_gate_batch slices its windows at n block slots (host_pack.hpp: GATE_SLICE_SLOTS)
+  int gate_slice = 0;        // CTVIO_GATE_SLICE=n       TEST ONLY: ctvio_visual_gate_batch slices its windows at n block slots (host_pack.hpp: GATE_SLICE_SLOTS),
+                             //                          ctvio_imu_gate_batch at n samples (IMU_GATE_SLICE_SAMPLES)
   int poison = 0;            // CTVIO_POISON=1/2         TEST ONLY: reused double scratch starts as quiet NaN / 2.6e151 at every use; the
                              //                          upload checks that the packer writes every staged byte (host_pack.hpp: check_staging)
 };
@@ -142,6 +143,7 @@ class SolverImpl {
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_PROJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_RATES>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_GATE>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    HIPCHK(hipFuncSetAttribute((const void *)k_cov_solve<COV_IMUGATE>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     // (no attribute for k_cov_solve<COV_PRED>: its launches are limited to the default dynamic-LDS size)
     return CTVIO_OK;
   }
@@ -245,6 +247,11 @@ class SolverImpl {
     gate_slot_.resize(gate_voff_[(size_t)nw]);
     for (int wi = 0; wi < nw; ++wi)
       for (int v = 0; v < meta_[wi].V; ++v) gate_slot_[gate_voff_[(size_t)wi] + (size_t)v] = meta_[wi].vis0 + tmp[wi].vpos[(size_t)v];
+    // the packed slot of every caller's IMU sample (imu_gate: the upload sorts the samples by segment and bias state), window after window
+    imu_moff_.assign((size_t)nw + 1, 0);
+    for (int wi = 0; wi < nw; ++wi) imu_moff_[(size_t)wi + 1] = imu_moff_[(size_t)wi] + (size_t)meta_[wi].M;
+    imu_slot_.resize(imu_moff_[(size_t)nw]);
+    for (int wi = 0; wi < nw; ++wi) imu_slot_map(tmp[wi].iorder.data(), meta_[wi].M, meta_[wi].imu0, imu_slot_.data() + imu_moff_[(size_t)wi]);
     // ---- device pointers of the input arena
     Dev &d = dev_;
     std::memset(&d, 0, sizeof d);
@@ -1297,6 +1304,7 @@ class SolverImpl {
   static_assert(POSE_OK == QUERY_OK && POSE_SINGULAR == QUERY_SINGULAR && POSE_UNTOUCHED == QUERY_NO_INFO, "merge_status / fill_not_ok");
   static_assert(LMP_OK == QUERY_OK && LMP_SINGULAR == QUERY_SINGULAR && LMP_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
   static_assert(PRJ_OK == QUERY_OK && PRJ_SINGULAR == QUERY_SINGULAR && PRJ_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
+  static_assert(IMUG_OK == QUERY_OK && IMUG_SINGULAR == QUERY_SINGULAR && IMUG_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
   // the tiles of a covariance query: at most per_tile consecutive sorted queries of one window each
   static std::vector<CovTile> query_tiles(const QueryOrder &ord, int per_tile, CovKind kind) {
     std::vector<CovTile> tiles;
@@ -1991,6 +1999,105 @@ class SolverImpl {
     if (lm_count) std::memcpy(lm_count, io_host<int32_t>(io, s_lmc), sizeof(int32_t) * L);
     return CTVIO_OK;
   }
+  // ctvio_imu_gate_batch / ctvio_imu_gate (only >= 0: that window alone): the leave-one-out test of every IMU sample of the windows
+  // themselves.  No inputs but the tile descriptors (one per window and slice): k_cov_imugate_jac reads the packed samples the upload holds
+  // and writes by slot; the host scatters into the caller's sample order (imu_slot_).  Values only (redundancy, cov36, chi2 and
+  // frame_stats4 null): k_cov_imugate_jac alone, nothing is linearised or factored.  Otherwise run_query: one factorisation, then per slice
+  // of windows (plan_gate_slices on the sample counts: the record scratch is bounded) k_cov_imugate_jac and k_cov_solve<COV_IMUGATE> -- the
+  // first slice's record kernel where run_query times it (ms[2]), the later slices' inside ms[1] --, then k_cov_imugate_reduce (ms[3]).
+  // dev_, plan_ and the captured graph are not touched.
+  int imu_gate(int only, const ctvio_gate_options *o, double *res6, double *red, double *cov36, double *chi2, int32_t *status, double *frame_stats4) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (!o) return fail(CTVIO_ERR_INVALID, "null options");
+    if (!(o->min_redundancy > 0.0 && o->min_redundancy < 1.0)) return fail(CTVIO_ERR_INVALID, "min_redundancy outside (0, 1)");
+    const int wbeg = only >= 0 ? only : 0, wend = only >= 0 ? only + 1 : dev_.nwin;
+    const int s0 = meta_[wbeg].imu0, f0 = meta_[wbeg].bias0;
+    const size_t m0 = imu_moff_[(size_t)wbeg], M = imu_moff_[(size_t)wend] - m0;
+    size_t F = 0;
+    for (int w = wbeg; w < wend; ++w) F += (size_t)meta_[w].F;
+    if (M && !res6 && !red && !cov36 && !chi2 && !status && !frame_stats4) return fail(CTVIO_ERR_INVALID, "every output is null");
+    const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
+    if (M == 0) {   // (nothing is launched; a bias state without samples: (0, NaN, 0, +inf))
+      for (size_t f = 0; f < F && frame_stats4; ++f) { frame_stats4[4 * f] = 0.0; frame_stats4[4 * f + 1] = nan; frame_stats4[4 * f + 2] = 0.0; frame_stats4[4 * f + 3] = inf; }
+      return CTVIO_OK;
+    }
+    const bool full = red || cov36 || chi2 || frame_stats4;
+    std::vector<int32_t> wsamples((size_t)dev_.nwin);
+    for (int w = 0; w < dev_.nwin; ++w) wsamples[(size_t)w] = meta_[w].M;
+    const std::vector<GateSlice> slices = plan_gate_slices(wsamples.data(), wbeg, wend, dbg_.gate_slice > 0 ? (size_t)dbg_.gate_slice : IMU_GATE_SLICE_SAMPLES);
+    size_t nrec = 0, ndesc = 0;
+    for (const GateSlice &sl : slices) { nrec = std::max(nrec, (size_t)sl.slots); ndesc += (size_t)(sl.wend - sl.wbeg) + 1; }
+    // ---- in: the tile descriptors of every slice; out, by packed sample slot: res6 | redundancy | cov36 | chi2 | status, then by bias state:
+    // frame_stats4 (the reduction reads redundancy and chi2, so they exist whenever the call factors)
+    const size_t nf = full ? M : 0;
+    CovScratch scr(full, (size_t)dev_.Utot, sizeof(ImuGateRec), nrec);
+    CallLayout io = head_;
+    const int s_desc = io.add("wtile", sizeof(int32_t), full ? ndesc : 0, false), s_res = io.add("res6", sizeof(double), 6 * M, true),
+              s_red = io.add("redundancy", sizeof(double), nf, true), s_cov = io.add("cov36", sizeof(double), cov36 ? 36 * M : 0, true),
+              s_chi = io.add("chi2", sizeof(double), nf, true), s_stat = io.add("status", sizeof(int32_t), M, false),
+              s_fs = io.add("frame_stats4", sizeof(double), frame_stats4 ? 4 * F : 0, true);
+    if (const int rc = reserve_call(io, full ? &scr.lay : nullptr)) return rc;
+    std::vector<size_t> desc0;   // every slice's first descriptor
+    if (full) {
+      int32_t *hd = io_host<int32_t>(io, s_desc);
+      size_t at = 0;
+      for (const GateSlice &sl : slices) {
+        const std::vector<int32_t> first = plan_imugate_tiles(wsamples.data(), sl.wbeg, sl.wend, IMUG_PER_TILE);
+        std::memcpy(hd + at, first.data(), sizeof(int32_t) * first.size());
+        desc0.push_back(at);
+        at += first.size();
+      }
+    }
+    const ImuGateOut out{io_dev<double>(io, s_res), full ? io_dev<double>(io, s_red) : nullptr, cov36 ? io_dev<double>(io, s_cov) : nullptr,
+                         full ? io_dev<double>(io, s_chi) : nullptr, io_dev<int32_t>(io, s_stat), s0, 0, o->min_redundancy};
+    hipError_t ev_err = hipSuccess;
+    const int rc = run_query<ImuGateRec>(
+        io, s_desc, s_res, full ? &scr : nullptr,
+        [&](const uint8_t *excl, ImuGateRec *rec) {
+          const int n = excl ? (int)slices[0].slots : (int)M;
+          if (n) hipLaunchKernelGGL(k_cov_imugate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, s0, n, excl, rec, out);
+        },
+        [&](const Dev &c, const ImuGateRec *rec) {
+          for (size_t si = 0; si < slices.size(); ++si) {
+            const GateSlice &sl = slices[si];
+            const int first = meta_[sl.wbeg].imu0, n = (int)sl.slots;
+            if (!n) continue;
+            if (si) hipLaunchKernelGGL(k_cov_imugate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, scr.lay.at<uint8_t>(call_scr_.dev, scr.s_excl), const_cast<ImuGateRec *>(rec), out);
+            CovSolveIO<COV_IMUGATE> a;
+            a.rec = rec; a.slot_base = first; a.igate = out;
+            a.wtile = io_dev<int32_t>(io, s_desc) + desc0[si]; a.wt_n = sl.wend - sl.wbeg; a.wt_w0 = sl.wbeg;
+            launch_cov_solve(c, (size_t)io_host<int32_t>(io, s_desc)[desc0[si] + (size_t)a.wt_n], a);
+          }
+          ev_err = hipEventRecord(ev_[EV_QUERY_BEGIN], stream_);
+          if (frame_stats4)
+            hipLaunchKernelGGL(k_cov_imugate_reduce, dim3(nblk((int)F, 64)), dim3(64), 0, stream_, dev_, f0, (int)F, out, io_dev<double>(io, s_fs));
+          if (ev_err == hipSuccess) ev_err = hipEventRecord(ev_[EV_QUERY_END], stream_);
+        });
+    if (rc) return rc;
+    HIPCHK(ev_err);
+    if (full)
+      if (const int rc2 = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
+        return rc2;
+    // ---- results, in the caller's sample order.  Precedence 2, 1 (the window's factorisation failed), 4, 0.
+    const Lm *lm = io_host<Lm>(io, HEAD_LM);
+    const double *hres = io_host<double>(io, s_res), *hred = io_host<double>(io, s_red), *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
+    const int32_t *hstat = io_host<int32_t>(io, s_stat);
+    for (int w = wbeg; w < wend; ++w) {
+      const bool bad = full && lm[w].chol_fail != 0;
+      for (size_t b = imu_moff_[(size_t)w]; b < imu_moff_[(size_t)w + 1]; ++b) {
+        const size_t i = b - m0, k = (size_t)(imu_slot_[b] - s0);
+        int st = hstat[k];
+        if (bad && (st == IMUG_OK || st == IMUG_WEAK)) st = IMUG_SINGULAR;
+        if (res6) std::memcpy(res6 + 6 * i, hres + 6 * k, sizeof(double) * 6);
+        if (red) red[i] = st == IMUG_OK || st == IMUG_WEAK ? hred[k] : (st == IMUG_NO_INFO ? 0.0 : nan);
+        if (cov36) cov_block(cov36 + 36 * i, hcov + 36 * k, 6, st == IMUG_WEAK ? (int)QUERY_NO_INFO : st);
+        if (chi2) chi2[i] = gate_value(hchi[k], st == IMUG_WEAK ? (int)QUERY_NO_INFO : st);
+        if (status) status[i] = st;
+      }
+    }
+    if (frame_stats4) std::memcpy(frame_stats4, io_host<double>(io, s_fs), sizeof(double) * 4 * F);
+    return CTVIO_OK;
+  }
   // ctvio_predict_landmarks_batch / ctvio_predict_landmarks (only >= 0: every prediction belongs to that window, win is not read): where
   // landmark lm[i] falls in the camera at the IMU-predicted pose of prediction pred[i], row row[i], beyond the spline, with its 2 x 2
   // covariance and gate.  The predictions are imu_predict()'s queries (grouped by window, stable), the points are grouped by the window of
@@ -2324,6 +2431,8 @@ class SolverImpl {
   const double *h_ld_ = nullptr;        // the line delays as uploaded (same arena)
   std::vector<int32_t> gate_slot_;   // [sum V] the absolute block slot of every caller's block, window after window (gate_voff_: nwin + 1 offsets)
   std::vector<size_t> gate_voff_;
+  std::vector<int32_t> imu_slot_;    // [sum M] the absolute packed slot of every caller's IMU sample, window after window (imu_moff_: nwin + 1 offsets)
+  std::vector<size_t> imu_moff_;
   const int32_t *h_lm_pos_ = nullptr;   // host mirror of Dev::lm_pos (inside in_.host: valid while the batch is uploaded)
 };
 
@@ -2517,6 +2626,16 @@ int32_t ctvio_visual_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options 
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.visual_gate(id, o, res2, weight, depth, redundancy, cov4, chi2, status, lm_stats3, lm_count);
+}
+int32_t ctvio_imu_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, double *res6, double *redundancy, double *cov36, double *chi2, int32_t *status,
+                             double *frame_stats4) {
+  CHK_S; return s->impl.imu_gate(-1, o, res6, redundancy, cov36, chi2, status, frame_stats4);
+}
+int32_t ctvio_imu_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options *o, double *res6, double *redundancy, double *cov36, double *chi2, int32_t *status,
+                       double *frame_stats4) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.imu_gate(id, o, res6, redundancy, cov36, chi2, status, frame_stats4);
 }
 void ctvio_default_triangulate_options(ctvio_triangulate_options *o) {
   if (!o) return;

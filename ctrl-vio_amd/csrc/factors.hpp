@@ -467,7 +467,9 @@ template <class SC> CTV_DI void nav_jac_T(const Q4 q[4], const SC &sc, double u,
 // global frame: Jw, Ja, lamA (x) Rinv_g); under R(t) <- R(t) exp(dtheta), v_B <- v_B + [v_B]x dtheta, so the v_B rows are [v_B]x J^Rp_k
 // (eval_Rp: the rotation rows of pose_jac_T) on the rotations and c'_k(u) / dt R(t)^T on the positions.  All 216 entries are written, each
 // once.  At u = 0 the last knot's blocks are exact zeros (up to the sign of a zero): lamR_3 = u^3 / 6, lamW_3 and c'_3 = u^2 / 2, lamA_3 = u.
-template <class SC> CTV_DI void rates_jac_T(const Knots4 &k, const SC &sc, double u, double idt, V3 gravity, double *jt) {
+// NC = 6 (ctvio_imu_gate): the omega and f columns alone, jt[(6 k + c) * 6 + a], the same entries with the same bits.
+template <class SC, int NC = 9> CTV_DI void rates_jac_T(const Knots4 &k, const SC &sc, double u, double idt, V3 gravity, double *jt) {
+  static_assert(NC == 9 || NC == 6, "rates_jac_T: 9 columns, or 6 without v_B");
   const double zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, one6[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
   double r[6], cv[4];
   ImuJac J;
@@ -486,13 +488,15 @@ template <class SC> CTV_DI void rates_jac_T(const Knots4 &k, const SC &sc, doubl
     for (int c = 0; c < 3; ++c)
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
-        double *rot = jt + (6 * kk + c) * 9, *pos = jt + (6 * kk + 3 + c) * 9;
+        double *rot = jt + (6 * kk + c) * NC, *pos = jt + (6 * kk + 3 + c) * NC;
         rot[a] = J.Jw[kk].m[3 * a + c];
         rot[3 + a] = J.Ja[kk].m[3 * a + c];
-        rot[6 + a] = B.m[3 * a + c];
         pos[a] = 0.0;
         pos[3 + a] = J.lamA[kk] * J.Rinv_g.m[3 * a + c];
-        pos[6 + a] = cv[kk] * J.Rinv_g.m[3 * a + c];
+        if (NC == 9) {
+          rot[6 + a] = B.m[3 * a + c];
+          pos[6 + a] = cv[kk] * J.Rinv_g.m[3 * a + c];
+        }
       }
   }
 }

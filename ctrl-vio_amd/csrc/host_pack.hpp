@@ -578,6 +578,25 @@ inline std::vector<GateSlice> plan_gate_slices(const int32_t *slots, int wbeg, i
   return out;
 }
 
+// ctvio_imu_gate_batch walks its windows in the same slices, counted in packed IMU samples (slots[w] = M_w; nothing pads them).  One record
+// per sample (kernels_cov.hpp: ImuGateRec): 16 bytes of header, the 6 doubles of the residual and the 24 x 6 Jacobian block, 1216 bytes.
+// IMU_GATE_SLICE_SAMPLES: 49152 samples x 1216 B = 59.8 MB of records, within the 64 MB the visual gate's records were held to -- 24576
+// tiles of two samples per slice, twelve times what the 256 CUs of an MI355X hold at eight workgroups each.
+constexpr size_t IMU_GATE_SLICE_SAMPLES = 49152;
+// The absolute packed slot of every sample of a window in the caller's order: the upload sorts the samples by (segment, bias state)
+// (PackTmp::iorder[i] = the caller's sample in packed position i), the slots of the window start at imu0.
+inline void imu_slot_map(const int32_t *iorder, int M, int32_t imu0, int32_t *slot) {
+  for (int i = 0; i < M; ++i) slot[iorder[i]] = imu0 + i;
+}
+// The tile descriptors of one slice: the first tile of every window [wbeg, wend) when each window's samples[w] packed samples are cut into
+// tiles of per_tile consecutive ones that never straddle a window, and behind them the slice's tile count.  A window without samples has no
+// tile: its entry equals its successor's.
+inline std::vector<int32_t> plan_imugate_tiles(const int32_t *samples, int wbeg, int wend, int per_tile) {
+  std::vector<int32_t> first((size_t)(wend - wbeg) + 1, 0);
+  for (int w = wbeg; w < wend; ++w) first[(size_t)(w - wbeg) + 1] = first[(size_t)(w - wbeg)] + (samples[w] + per_tile - 1) / per_tile;
+  return first;
+}
+
 // The input arena (pinned host mirror + device), every segment ONCE: X(element type, segment, Dev member, allocated count, filled count).
 // An empty set keeps one entry allocated.  The names stand for BatchFacts members (layout_input).  Irregular: `state` is the contiguous
 // block quat | pos | bias | rho | ld (StatePtrs); vrow / vrow_off hold one unused entry unless the row walk is uploaded, and Dev gets null.

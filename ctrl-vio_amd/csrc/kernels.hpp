@@ -31,6 +31,7 @@
 
 #include "device_types.hpp"
 #include "factors.hpp"
+#include "imugate6.hpp"
 
 namespace ctv {
 

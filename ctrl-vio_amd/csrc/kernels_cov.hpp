@@ -9,6 +9,7 @@
 //   ctvio_body_rates_batch          body rates, 15 x 15, IMU gates     k_cov_rates_jac, k_cov_solve<COV_RATES>
 //   ctvio_predict_landmarks_batch   points from IMU-predicted poses    k_cov_nav_jac, k_imu_transition (kernels_prop.hpp), k_cov_pred_jac, k_cov_solve<COV_PRED>
 //   ctvio_visual_gate_batch         leave-one-out test of the blocks   k_cov_gate_jac, k_cov_solve<COV_GATE>, k_cov_gate_reduce
+//   ctvio_imu_gate_batch            leave-one-out test of the samples  k_cov_imugate_jac, k_cov_solve<COV_IMUGATE>, k_cov_imugate_reduce
 // Part of kernels.hpp (included from there, in order; not a stand-alone header).  With H the normal matrix of the window at its current
 // state (no LM damping) and the excluded unknowns -- constant ones, and those no factor touches (H_jj == 0) -- removed, the reduced system
 // S = Hpp - W Hll^-1 W^T = L L^T is factored by the panel kernel (k_cholesky_solve: L21 in S, the inverses of the 32 x 32 diagonal blocks in
@@ -48,14 +49,16 @@ enum CovKind : int32_t {
   TILE_RATES = 7,   // the fifteen columns of J^T of one body-rates query (omega 0..2, specific force 3..5, body-frame velocity 6..8, gyro bias
                     // 9..11, accelerometer bias 12..14, column 15 unused)
   TILE_PRED = 8,    // the two columns of G of up to eight points of ctvio_predict_landmarks_batch (columns 2 q, 2 q + 1)
-  TILE_GATE = 9     // TILE_PROJ's columns for eight consecutive block slots of the window (ctvio_visual_gate_batch; built in the kernel, not listed)
+  TILE_GATE = 9,    // TILE_PROJ's columns for eight consecutive block slots of the window (ctvio_visual_gate_batch; built in the kernel, not listed)
+  TILE_IMUGATE = 10 // the six columns of imu_w (.) J^T of one or two consecutive packed IMU samples of the window (columns 6 q .. 6 q + 5;
+                    // ctvio_imu_gate_batch; built in the kernel from one descriptor per window, not listed)
 };
 struct CovTile {
   int32_t win;
   CovKind kind;
   int32_t first;    // SEL: offset of the tile's first entry in the concatenated selection; RHO and POINT: first row of W (window-local);
-                    // POSE, REL, PROJ, PRED and GATE: the tile's first query record; NAV and RATES: its query record
-  int32_t count;    // columns in use (<= 16); POSE and REL: queries (1 or 2); POINT: landmarks (<= 5); NAV and RATES: 1; PROJ, PRED and GATE: queries (<= 8)
+                    // POSE, REL, PROJ, PRED, GATE and IMUGATE: the tile's first query record; NAV and RATES: its query record
+  int32_t count;    // columns in use (<= 16); POSE, REL and IMUGATE: queries (1 or 2); POINT: landmarks (<= 5); NAV and RATES: 1; PROJ, PRED and GATE: queries (<= 8)
   long long yoff;   // SEL: where the tile's Y ([P][16] doubles) goes in the scratch
 };
 // One window with a selection (k_cov_gram).
@@ -222,6 +225,22 @@ struct RatesRec {
 // the status and the record.  A knot the rates depend on, or the bias state, with an unknown no factor touches (COV_UNTOUCHED) gives
 // POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.  The values are formed before excl is looked at,
 // by code the Jacobians do not share: both calls give them the same bits.
+// (The values are rates_values, shared with k_cov_imugate_jac: segment s and u in, the knots relative to knot s, the segment's constants --
+// with want_jac those the Jacobian needs as well --, gravity and val = (omega, f, v_B) out.)
+__device__ __forceinline__ void rates_values(const Dev &d, const WinMeta &m, int s, double u, bool want_jac, Knots4 &k, SegConst &sc, V3 &grav, double *val) {
+  load_knots(d.quat, d.pos, m.knot0 + s, d.pos + 3 * (size_t)(m.knot0 + s), k);   // relative to knot s: the rates are translation invariant
+  seg_const(k, sc, want_jac);
+  grav = mk(m.gravity[0], m.gravity[1], m.gravity[2]);
+  double dc[4], ddc[4];
+  basis<false, 1>(u, m.inv_dt, dc);
+  basis<false, 2>(u, m.inv_dt * m.inv_dt, ddc);
+  V3 v = mk(0, 0, 0), a = mk(0, 0, 0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { v = v + dc[j] * k.p[j]; a = a + ddc[j] * k.p[j]; }
+  const Q4 qinv = qconj(eval_R(k.q, sc, u));
+  const V3 om = eval_omega<SegConst>(sc, u, m.inv_dt), f = qrot(qinv, a + grav), vb = qrot(qinv, v);
+  val[0] = om.x; val[1] = om.y; val[2] = om.z; val[3] = f.x; val[4] = f.y; val[5] = f.z; val[6] = vb.x; val[7] = vb.y; val[8] = vb.z;
+}
 __global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQuery *qs, const uint8_t *excl, RatesRec *recs, double *rates9, int32_t *status_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -236,22 +255,12 @@ __global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQ
   const int nk = u > 0.0 ? 4 : 3;
   int status = outside ? POSE_OUTSIDE : POSE_OK;
   Knots4 k;
-  load_knots(d.quat, d.pos, m.knot0 + s, d.pos + 3 * (size_t)(m.knot0 + s), k);   // relative to knot s: the rates are translation invariant
   SegConst sc;
-  seg_const(k, sc, excl != nullptr);
-  const V3 grav = mk(m.gravity[0], m.gravity[1], m.gravity[2]);
+  V3 grav;
   double val[9];
+  rates_values(d, m, s, u, excl != nullptr, k, sc, grav, val);
   {
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    double dc[4], ddc[4];
-    basis<false, 1>(u, m.inv_dt, dc);
-    basis<false, 2>(u, m.inv_dt * m.inv_dt, ddc);
-    V3 v = mk(0, 0, 0), a = mk(0, 0, 0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v = v + dc[j] * k.p[j]; a = a + ddc[j] * k.p[j]; }
-    const Q4 qinv = qconj(eval_R(k.q, sc, u));
-    const V3 om = eval_omega<SegConst>(sc, u, m.inv_dt), f = qrot(qinv, a + grav), vb = qrot(qinv, v);
-    val[0] = om.x; val[1] = om.y; val[2] = om.z; val[3] = f.x; val[4] = f.y; val[5] = f.z; val[6] = vb.x; val[7] = vb.y; val[8] = vb.z;
     double *o = rates9 + 9 * (size_t)i;
 #pragma unroll
     for (int j = 0; j < 9; ++j) o[j] = outside ? nan : val[j];
@@ -274,6 +283,94 @@ __global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQ
 #pragma unroll
   for (int j = 0; j < 6; ++j) { r.z[j] = val[j] + bp[j]; r.meas[j] = q.meas[j]; r.sig[j] = q.sig[j]; }
   rates_jac_T(k, sc, u, m.inv_dt, grav, r.jt);
+}
+
+// One IMU sample of the window itself (ctvio_imu_gate_batch) and what k_cov_imugate_jac makes of it.  The statuses: 2 as POSE_UNTOUCHED,
+// 4 the epilogue's (redundancy < min_redundancy); 3 cannot occur, the upload refuses IMU times outside the spline.
+enum { IMUG_OK = 0, IMUG_SINGULAR = 1, IMUG_NO_INFO = 2, IMUG_WEAK = 4 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
+constexpr int IMUG_PER_TILE = 2;
+struct ImuGateRec {
+  int32_t status, s, nk, frame;   // first knot; knots the sample depends on: 3 at u = 0, else 4; its bias state
+  double r[6];                    // the whitened residual, the bits that go to res6
+  double jt[144];                 // the omega and f columns of J^T over the knots s .. s + 3, 24 x 6, unweighted (rates_jac_T<.., 6>; IMUG_OK only)
+};
+// What the gate's kernels write per packed sample slot (absolute slot - slot0; null: not asked for) and the threshold of IMUG_WEAK.
+struct ImuGateOut {
+  double *res6, *red, *cov36, *chi2;
+  int32_t *status;
+  int32_t slot0, pad;
+  double min_red;
+};
+// One lane per packed sample slot e = first + i of the slice (records by i, outputs by e - slot0): segment and bias state of the sample's
+// group, u = imu_u (the host's integer-ns rule, the one k_cov_rates_jac applies to a query time), z = rates_values + bias, and
+// r = imu_w (z - meas), every operation rounded once, so that the residual can be re-derived from ctvio_body_rates' values to the bit.
+// With excl (after k_cov_prepare; null: values only, recs is not touched) the status -- a knot the sample depends on, or its bias state,
+// with an unknown no factor touches gives IMUG_NO_INFO: decided on the exclusion flags and on u > 0 -- and the record.  The values are
+// formed before excl is looked at: both calls give them the same bits.
+__global__ __launch_bounds__(64) void k_cov_imugate_jac(Dev d, int first, int n, const uint8_t *excl, ImuGateRec *recs, ImuGateOut o) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int e = first + i;
+  const ImuGroup &g = d.groups[d.imu_grp[e]];
+  const WinMeta &m = d.wins[g.win];
+  const int s = g.s, frame = g.bias;
+  const double u = d.imu_u[e];
+  const int nk = u > 0.0 ? 4 : 3;
+  Knots4 k;
+  SegConst sc;
+  V3 grav;
+  double val[9], r[6];
+  rates_values(d, m, s, u, excl != nullptr, k, sc, grav, val);
+  const double *bp = d.bias + 6 * (size_t)(m.bias0 + frame);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) r[j] = __dmul_rn(m.imu_w[j], __dsub_rn(__dadd_rn(val[j], bp[j]), d.imu_meas[(size_t)j * d.Mtot + e]));
+  const size_t ko = (size_t)(e - o.slot0);
+  if (o.res6) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) o.res6[6 * ko + j] = r[j];
+  }
+  int status = IMUG_OK;
+  if (excl) {
+    for (int j = 6 * s; j < 6 * (s + nk); ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = IMUG_NO_INFO;
+    for (int j = 6 * m.K + 6 * frame; j < 6 * m.K + 6 * frame + 6; ++j)
+      if (excl[m.u0 + j] == COV_UNTOUCHED) status = IMUG_NO_INFO;
+  }
+  o.status[ko] = status;
+  if (!excl) return;
+  ImuGateRec &rc = recs[i];
+  rc.status = status; rc.s = s; rc.nk = nk; rc.frame = frame;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) rc.r[j] = r[j];
+  if (status != IMUG_OK) return;
+  rates_jac_T<SegConst, 6>(k, sc, u, m.inv_dt, grav, rc.jt);
+}
+
+// One lane per bias state f_base + i (absolute; outputs by i): over the IMU groups that name it (Dev::bgl, group order) and their samples in
+// slot order -- the upload's packed order, so the bits are the window's -- the number of status-0 samples, the mean of their chi2 (NaN:
+// none), the largest chi2 (0: none) and the smallest redundancy over status 0 or 4 (+inf: none).  A window whose factorisation failed
+// (chol_fail) has none of them.
+__global__ __launch_bounds__(64) void k_cov_imugate_reduce(Dev d, int f_base, int n, ImuGateOut o, double *stats4) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int fa = f_base + i, w = d.bias_win[fa];
+  const bool bad = d.lm[w].chol_fail != 0;
+  const int32_t *off = d.bgl_off + fa + w;   // (window w's F + 1 offsets start at bias0 + w)
+  int c = 0;
+  double sum = 0.0, cmax = 0.0, rmin = __builtin_inf();
+  for (int gi = off[0]; gi < off[1] && !bad; ++gi) {
+    const ImuGroup &g = d.groups[d.bgl[gi]];
+    for (int j = 0; j < g.count; ++j) {
+      const size_t k = (size_t)(g.iabs + j - o.slot0);
+      const int st = o.status[k];
+      if (st == IMUG_OK) { ++c; sum = __dadd_rn(sum, o.chi2[k]); cmax = fmax(cmax, o.chi2[k]); }
+      if (st == IMUG_OK || st == IMUG_WEAK) rmin = fmin(rmin, o.red[k]);
+    }
+  }
+  stats4[4 * (size_t)i] = (double)c;
+  stats4[4 * (size_t)i + 1] = c ? sum / (double)c : __longlong_as_double(0x7ff8000000000000ll);
+  stats4[4 * (size_t)i + 2] = cmax;
+  stats4[4 * (size_t)i + 3] = rmin;
 }
 
 // One relative-pose query (ctvio_relative_pose_batch), grouped by window on the host, and what k_cov_rel_jac makes of it.  The statuses are
@@ -843,12 +940,18 @@ __global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoi
 // TILE_GATE: io.rec (GateRec) by slot of the slice; no tile list: tile b is the slots io.slot_base + 8 b .. + 7 (one window: a window's slots
 //   start on a group of 64) | TILE_PROJ's | Cw = img_w^2 (cov_gram2); T = Cw S, A = S T, redundancy = lambda_min(I - A) -> gate.red; below
 //   gate.min_red GATE_WEAK, else C_loo = Cw + T (I - A)^-1 T^T -> gate.cov4, cov_gate2(I) on r -> gate.chi2; all by absolute slot - gate.slot0
+// TILE_IMUGATE: io.rec (ImuGateRec) by packed sample slot of the slice; no tile list: io.wtile holds the first tile of every window of the
+//   slice (one more entry: the tile count), tile b belongs to the last window whose first tile is <= b and is that window's samples
+//   2 (b - first tile), + 1 | 6 q + a: imu_w[a] times column a of J^T over the knot rows, imu_w[a] at the bias unknown a of state `frame` |
+//   the 21 unique entries of A per sample: four partial sums over the rows k = p mod 4, added in sequence; then lane 0 of wave q runs
+//   imugate6 (imugate6.hpp) for sample q in LDS: redundancy -> igate.red; below igate.min_red IMUG_WEAK, else chi2 and M^-1 - I -> igate.chi2,
+//   igate.cov36; all by absolute slot - igate.slot0
 constexpr int COV_NT = 256;
-enum CovInst { COV_BASE, COV_REL, COV_PROJ, COV_RATES, COV_PRED, COV_GATE };   // COV_BASE: TILE_SEL .. TILE_NAV by t.kind; the others: their one kind
+enum CovInst { COV_BASE, COV_REL, COV_PROJ, COV_RATES, COV_PRED, COV_GATE, COV_IMUGATE };   // COV_BASE: TILE_SEL .. TILE_NAV by t.kind; the others: their one kind
 template <CovInst I> struct CovQueryRec { typedef PoseRec type; };
 template <> struct CovQueryRec<COV_REL> { typedef RelRec type; };     template <> struct CovQueryRec<COV_PROJ> { typedef ProjRec type; };
 template <> struct CovQueryRec<COV_RATES> { typedef RatesRec type; }; template <> struct CovQueryRec<COV_PRED> { typedef PredRec type; };
-template <> struct CovQueryRec<COV_GATE> { typedef GateRec type; };
+template <> struct CovQueryRec<COV_GATE> { typedef GateRec type; };   template <> struct CovQueryRec<COV_IMUGATE> { typedef ImuGateRec type; };
 // k_cov_solve's arguments; what a call does not use stays null.
 template <CovInst I> struct CovSolveIO {
   const CovTile *tiles = nullptr;
@@ -861,8 +964,22 @@ template <CovInst I> struct CovSolveIO {
   const PointRec *lrec = nullptr;                        // TILE_POINT: the records by landmark through the batch,
   double *lm_cov = nullptr; int lm_base = 0;             // the 3 x 3 blocks from landmark lm_base on
   const NavRec *nrec = nullptr; double *nav_cov = nullptr;   // TILE_NAV
-  GateOut gate{}; int slot_base = 0;                     // TILE_GATE: the outputs, and the slice's first slot
+  GateOut gate{}; int slot_base = 0;                     // TILE_GATE: the outputs, and the slice's first slot (TILE_IMUGATE: its first sample slot)
+  ImuGateOut igate{};                                    // TILE_IMUGATE: the outputs,
+  const int32_t *wtile = nullptr; int wt_n = 0, wt_w0 = 0;   // the first tile of the slice's windows wt_w0 .. wt_w0 + wt_n - 1, then the tile count
 };
+// TILE_IMUGATE's tile b: the window by bisection over the slice's descriptors (wtile[lo] <= b < wtile[hi] throughout; a window without
+// samples shares its first tile with its successor and is never chosen), then the window's samples 2 lt, 2 lt + 1.
+template <CovInst I> __device__ __forceinline__ CovTile cov_imugate_tile(const Dev &d, const CovSolveIO<I> &io, int b) {
+  int lo = 0, hi = io.wt_n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (io.wtile[mid] <= b) lo = mid; else hi = mid;
+  }
+  const WinMeta &m = d.wins[io.wt_w0 + lo];
+  const int lt = b - io.wtile[lo];
+  return CovTile{io.wt_w0 + lo, TILE_IMUGATE, m.imu0 + IMUG_PER_TILE * lt - io.slot_base, min(IMUG_PER_TILE, m.M - IMUG_PER_TILE * lt), 0};
+}
 // What the stages of one workgroup share.  (The dynamic LDS is named, not carried: a pointer through the struct costs two VGPRs.)
 extern __shared__ __attribute__((aligned(16))) double cov_lds[];   // Ys | part (the launch's cov_solve_lds bytes)
 struct CovCtx {
@@ -1004,6 +1121,58 @@ __device__ __forceinline__ void cov_rates_epilogue(const CovCtx &x, int b0, cons
   }
 }
 
+// ---- TILE_IMUGATE (ctvio_imu_gate_batch): one or two samples per tile, six columns each
+__device__ __forceinline__ void cov_imugate_prologue(const CovCtx &x, const ImuGateRec *rec) {
+  const Dev &d = x.d; const WinMeta &m = x.m; const CovTile &t = x.t;
+  for (int e = x.tid; e < 150 * t.count; e += COV_NT) {   // the knot rows (f < 144), then the six bias rows
+    const int qi = e / 150, f = e % 150;
+    const ImuGateRec &rr = rec[t.first + qi];
+    if (rr.status != IMUG_OK) continue;
+    if (f < 144) {
+      const int r = f / 6, a = f % 6;
+      if (r < 6 * rr.nk && d.active[m.u0 + 6 * rr.s + r]) x.Ys()[(6 * rr.s + r) * 16 + 6 * qi + a] = m.imu_w[a] * rr.jt[f];
+    } else {
+      const int a = f - 144, j = 6 * m.K + 6 * rr.frame + a;
+      if (d.active[m.u0 + j]) x.Ys()[j * 16 + 6 * qi + a] = m.imu_w[a];
+    }
+  }
+  if (x.tid == 0)
+    for (int qi = 0; qi < t.count; ++qi)
+      if (rec[t.first + qi].status == IMUG_OK) *x.first = min(*x.first, 6 * rec[t.first + qi].s);
+}
+// part: [4][42] partial sums | [2][21] A | [2][IMUGATE6_WORK] the work areas of the two lanes.  The two samples' 6 x 6 steps run in lane 0
+// of waves 0 and 1: two wave instructions never share an LDS cycle, so the layout of the work areas needs no padding against each other,
+// and the rest of the part buffer is free by then.
+static_assert(168 + 42 + IMUG_PER_TILE * IMUGATE6_WORK <= 512, "cov_imugate_epilogue: the part buffer");
+__device__ __forceinline__ void cov_imugate_epilogue(const CovCtx &x, int b0, const ImuGateRec *rec, const ImuGateOut &g, int slot_base) {
+  const CovTile &t = x.t;
+  const int P = x.P, tid = x.tid, k0 = min(32 * b0, P);
+  double *part = x.part();
+  if (tid < 168) {
+    const int p = tid / 42, e = tid % 42, c0 = 6 * (e / 21);
+    int ci, cj;
+    tile_decode(e % 21, ci, cj);
+    double s = 0.0;
+    for (int k = k0 + p; k < P; k += 4) s += x.Ys()[k * 16 + c0 + ci] * x.Ys()[k * 16 + c0 + cj];
+    part[p * 42 + e] = s;
+  }
+  __syncthreads();
+  if (tid < 42) part[168 + tid] = ((part[tid] + part[42 + tid]) + part[84 + tid]) + part[126 + tid];
+  __syncthreads();
+  const int q = x.wave;
+  if ((tid & 63) == 0 && q < t.count) {
+    const ImuGateRec &rr = rec[t.first + q];
+    if (rr.status == IMUG_OK) {
+      const size_t k = (size_t)(slot_base + t.first + q - g.slot0);
+      double red, chi;
+      imugate6(part + 168 + 21 * q, rr.r, g.cov36 != nullptr, part + 210 + IMUGATE6_WORK * q, red, chi, g.cov36 ? g.cov36 + 36 * k : nullptr);
+      if (g.red) g.red[k] = red;
+      if (!(red >= g.min_red)) g.status[k] = IMUG_WEAK;   // (cov36 and chi2 are the host's fill)
+      else if (g.chi2) g.chi2[k] = chi;
+    }
+  }
+}
+
 // ---- TILE_PROJ, TILE_PRED and TILE_GATE (ctvio_project_landmarks_batch, ctvio_predict_landmarks_batch, ctvio_visual_gate_batch)
 // + the anchor rows 6 s_a .. 6 (s_a + nk_a) - 1 of every query's two columns
 template <class Rec> __device__ __forceinline__ void cov_anchor_rows(const CovCtx &x, const Rec *rec) {
@@ -1128,6 +1297,7 @@ __device__ __forceinline__ void cov_gate_epilogue(const CovCtx &x, int b0, const
 template <CovInst I> __device__ __forceinline__ void cov_prologue(const CovCtx &x, const CovSolveIO<I> &io) {
   if constexpr (I == COV_REL) cov_rel_prologue(x, io.rec);
   else if constexpr (I == COV_RATES) cov_rates_prologue(x, io.rec[x.t.first]);
+  else if constexpr (I == COV_IMUGATE) cov_imugate_prologue(x, io.rec);
   else cov_proj_prologue<I>(x, io.rec);   // COV_PROJ, COV_PRED, COV_GATE
 }
 // Y = L^-1 B in place, from the block of the tile's first non-zero row on; returns that block (nblk for a tile of zero columns).
@@ -1194,6 +1364,7 @@ template <CovInst I> __device__ __forceinline__ void cov_epilogue(const CovCtx &
   if constexpr (I == COV_PRED || I == COV_PROJ) cov_proj_epilogue<I>(x, b0, io.rec, io.blocks, io.chi2);
   else if constexpr (I == COV_RATES) cov_rates_epilogue(x, b0, io.rec[x.t.first], io.slot + x.t.first, io.blocks, io.chi2);
   else if constexpr (I == COV_GATE) cov_gate_epilogue(x, b0, io.rec, io.gate, io.slot_base);
+  else if constexpr (I == COV_IMUGATE) cov_imugate_epilogue(x, b0, io.rec, io.igate, io.slot_base);
   else cov_gram6(x, b0, io.slot, io.blocks);   // COV_REL
 }
 // amdgpu_waves_per_eu: with the stages of five kinds in it COV_BASE otherwise settles at 58 VGPRs + 8 AGPRs, one wave per SIMD short of the eight
@@ -1201,7 +1372,9 @@ template <CovInst I> __device__ __forceinline__ void cov_epilogue(const CovCtx &
 template <CovInst I>
 __global__ __launch_bounds__(COV_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_cov_solve(Dev d, CovSolveIO<I> io) {
   const int g0 = PRJ_PER_TILE * (int)blockIdx.x;   // (COV_GATE: the tile's first slot in the slice)
-  const CovTile t = I == COV_GATE ? CovTile{d.vb_win[(io.slot_base + g0) / 64], TILE_GATE, g0, min(PRJ_PER_TILE, io.gate.nslot - g0), 0} : io.tiles[blockIdx.x];
+  const CovTile t = I == COV_GATE      ? CovTile{d.vb_win[(io.slot_base + g0) / 64], TILE_GATE, g0, min(PRJ_PER_TILE, io.gate.nslot - g0), 0}
+                    : I == COV_IMUGATE ? cov_imugate_tile(d, io, (int)blockIdx.x)
+                                       : io.tiles[blockIdx.x];
   const WinMeta &m = d.wins[t.win];
   const int P = m.P, tid = threadIdx.x, PP = 32 * ((P + 31) / 32);
   __shared__ int s_first;

@@ -458,6 +458,34 @@ class Solver:
         """ctvio_visual_gate: the same for window wid alone (same bits as the batch entry)."""
         return self._visual_gate(lambda *a: self._lib.ctvio_visual_gate(self._h, int(wid), *a), [int(wid)], cov, min_redundancy)
 
+    def _imu_gate(self, call, wids, cov, min_redundancy):
+        o = capi.GateOptions()
+        self._lib.ctvio_default_gate_options(C.byref(o))
+        if min_redundancy is not None:
+            o.min_redundancy = float(min_redundancy)
+        M = sum(int(self.windows[w].M) for w in wids); F = sum(int(self.windows[w].F) for w in wids)
+        m = max(M, 1)
+        res = np.zeros((m, 6)); st = np.zeros(m, np.int32)
+        red = np.zeros(m) if cov else None; c = np.zeros((m, 6, 6)) if cov else None; chi = np.zeros(m) if cov else None
+        fs = np.zeros((max(F, 1), 4)) if cov else None
+        opt = lambda a: capi._p(a) if a is not None else None
+        capi.check(call(C.byref(o), capi._p(res), opt(red), opt(c), opt(chi), capi._p(st), opt(fs)))
+        cut = lambda a, n: a[:n].copy() if a is not None else None
+        return SimpleNamespace(res=cut(res, M), redundancy=cut(red, M), cov=cut(c, M), chi2=cut(chi, M), status=cut(st, M), frame_stats=cut(fs, F))
+
+    def imu_gate_batch(self, cov: bool = True, min_redundancy=None):
+        """ctvio_imu_gate_batch: the leave-one-out test of every IMU sample of the uploaded windows at the current state, window after window
+        in the caller's sample order.  Returns a namespace: res (M, 6) the whitened residual, redundancy = lambda_min(I - A), cov (M, 6, 6) the
+        whitened leave-one-out prediction covariance (I - A)^-1 - I, chi2 = r^T (I - A)^-1 r (6 degrees of freedom), status (0 ok, 1 singular
+        window, 2 no information, 4 redundancy < min_redundancy) and frame_stats (F, 4) = (status-0 samples, their mean chi2, largest chi2,
+        smallest redundancy) per bias state.  cov=False: values only (redundancy, cov, chi2 and frame_stats None), nothing is linearised or
+        factored."""
+        return self._imu_gate(lambda *a: self._lib.ctvio_imu_gate_batch(self._h, *a), range(len(self.windows)), cov, min_redundancy)
+
+    def imu_gate(self, wid: int, cov: bool = True, min_redundancy=None):
+        """ctvio_imu_gate: the same for window wid alone (same bits as the batch entry)."""
+        return self._imu_gate(lambda *a: self._lib.ctvio_imu_gate(self._h, int(wid), *a), [int(wid)], cov, min_redundancy)
+
     def _imu_noise(self, noise):
         o = capi.ImuNoise()
         self._lib.ctvio_default_imu_noise(C.byref(o))

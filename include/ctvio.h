@@ -319,7 +319,7 @@ int32_t ctvio_nav_state(ctvio_solver *s, int32_t id, int32_t n, const int64_t *t
  *   A = [[I, 0, 0, I, 0], [0, I, 0, 0, I]], C the 15 x 15 block above: a 6 x 6 Cholesky on the device, from the very cov225 and rates9 bits
  *   that are returned.  noise6: the six standard deviations for the whole call; NULL: sigma_k = 1 / imu_w[k] of the query's window.  The gate
  *   is meant for NEW samples: for a sample that is already a factor of the window, estimate and measurement are correlated and S overstates
- *   the variance of e.
+ *   the variance of e.  The samples of the window itself are tested by ctvio_imu_gate_batch, below.
  *   status (n entries, or NULL) per query, in this precedence: 3 time outside the spline: everything NaN;  2 a knot the query depends on, or
  *   the bias state, has a non-constant unknown no factor touches: values valid, +inf on the diagonal and 0 elsewhere, chi2 = 0;  1 the
  *   window's factorisation met a non-positive or non-finite pivot: values valid, covariance and chi2 NaN;  0 ok.
@@ -464,6 +464,53 @@ int32_t ctvio_visual_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, do
                                 double *cov4, double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count);
 int32_t ctvio_visual_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *redundancy,
                           double *cov4, double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count);
+
+/* AFTER THE SOLVE, WHICH IMU SAMPLES ARE OUTLIERS: the leave-one-out (deleted) residual test of every IMU sample of the windows themselves.
+ * The IMU factor carries no robust loss, so a saturated, dropped or mis-timed sample pulls the spline at full weight; ctvio_body_rates' gate is
+ * for NEW samples.  Here the sample's own information is taken out of the normal matrix -- a 6 x 6 Woodbury correction per sample on top of
+ * Sigma of the full system, no second factorisation.
+ * There are no query inputs: the samples are the window's own, as uploaded.  Per-sample outputs hold sum M entries (batch) or M entries
+ * (single window), window after window and in the CALLER'S sample order (ctvio_window.imu_*); frame_stats4 holds sum F or F entries of four
+ * doubles, one per bias state.  Any output may be NULL.  Per sample m = (t, bias state b, gyro, acc) at the CURRENT state, w = imu_w:
+ *   z = (omega(t) + bg_b, f(t) + ba_b): ctvio_body_rates' rates9[0..5] at (t, b) plus the bias -- the same segment / u rule and the same code,
+ *   so the same bits;
+ *   res6 (x 6) = r = w (.) (z - meas), the factor's own whitened residual, every operation rounded once;
+ *   J (6 x P) = w (.) the omega and f rows of ctvio_body_rates' Jacobian plus its one-hot bias rows; knot s + 3 enters only where u > 0, rows
+ *   of excluded unknowns are zero, constant unknowns contribute nothing;
+ *   A = J Sigma J^T (H, the exclusions and Sigma exactly those of ctvio_covariance_batch, no damping).  A <= I: the sample's own J^T J is
+ *   part of H.  There is no loss and so no corrector: S = I;
+ *   redundancy = lambda_min(I - A);
+ *   cov36 (x 36, row-major 6 x 6, whitened, symmetric to the bit) = C_loo = (I - A)^-1 - I = J (H - J^T J)^-1 J^T (Woodbury with S = I);
+ *   chi2 = r^T (I - A)^-1 r, 6 degrees of freedom (16.81 is the 99 % point), formed on the device from the very res6 bits that are returned.
+ *   It equals r_loo^T (C_loo + I)^-1 r_loo with r_loo = (I - A)^-1 r, the first-order residual of the sample against the estimate re-solved
+ *   without it, and is also the test of the post-fit residual against its own covariance Cov(r) = I - A.  Under the model its mean over the
+ *   samples of a window is 6: a check of the tuning of imu_w.
+ *   THIS IS NOT ctvio_visual_gate's chi2: that one gates the POST-FIT residual r against C_loo + I, which with S = I reads r^T (I - A) r and
+ *   is smaller by up to (1 - lambda)^2 (5.67 against 6.23 on the config1 fixture).
+ *   status, in this precedence: 2 a non-constant unknown under the sample's knots or its bias state is touched by no factor (possible only
+ *   with zero weights): values valid, redundancy 0, cov36 +inf on the diagonal and 0 elsewhere, chi2 = 0;  1 bad pivot in the window's
+ *   factorisation: values valid, redundancy / cov36 / chi2 NaN;  4 redundancy < opt->min_redundancy -- the rest of the window cannot predict
+ *   this sample: values and redundancy valid, cov36 +inf on the diagonal and 0 elsewhere, chi2 = 0;  0 ok.  Status 3 cannot occur: the upload
+ *   refuses IMU times outside the spline.  A sample that depends on constant unknowns alone: A = 0, redundancy 1, a zero cov36,
+ *   chi2 = |r|^2, status 0.
+ * Per bias state, over the samples naming it, in the library's packed sample order (fixed by the upload): frame_stats4[0] the number of
+ * its status-0 samples, [1] their mean chi2 (NaN: none), [2] their largest chi2 (0: none), [3] the smallest redundancy over status 0 or 4
+ * (+inf: none).
+ * With redundancy, cov36, chi2 and frame_stats4 all NULL nothing is linearised or factored: one kernel writes res6 and status (all 0), with
+ * the bits of the full call's.
+ * Returns CTVIO_OK for every status, and for M = 0 (nothing is launched).  CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID for a window
+ * id out of range, NULL options, min_redundancy outside (0, 1) or non-finite, every output NULL with M > 0; the handle stays usable.  The
+ * state, the launch plan and the captured graph of the solve are left as they were; no atomics: where the linearisation is order-fixed
+ * (opt.deterministic) the bits of a sample's and a bias state's outputs depend on the window alone -- not on the entry, on which outputs
+ * were asked for, or on how the call was sliced (large batches are walked in slices of windows so that the per-sample scratch stays bounded;
+ * the factorisation happens once) -- and a second call repeats them.
+ * ctvio_last_timing: ms8[0..2] = k_cov_prepare, k_cov_solve, k_cov_imugate_jac (a call of several slices: the first slice's record kernel;
+ * the later ones run between the slices' k_cov_solve and count in ms8[1]), ms8[3] the bias-state reduction, ms8[7] the whole call; values
+ * only: ms8[2] and ms8[7]. */
+int32_t ctvio_imu_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, double *res6, double *redundancy, double *cov36, double *chi2,
+                             int32_t *status, double *frame_stats4);
+int32_t ctvio_imu_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options *o, double *res6, double *redundancy, double *cov36, double *chi2,
+                       int32_t *status, double *frame_stats4);
 
 /* BETWEEN FRAMES: IMU dead reckoning from the navigation state, with its 15 x 15 covariance -- what VisualOdometry::ProcessIMU
  * (visual_odometry.cpp:137-172) does with the state SlideWindow hands it, and where AddImageToWindow (:188-191) takes the predicted pose of
@@ -727,7 +774,8 @@ int32_t ctvio_graph_captures(const ctvio_solver *s);
  *     ctvio_set_batch fail with CTVIO_ERR_INTERNAL if the packer leaves a staged input byte unwritten)
  *   CTVIO_CHOL_COMPACT=1|n (test only: every batch the panel Cholesky factors takes its slot-indexed variant, which otherwise runs only for
  *     windows beyond 591 unknowns; 1 = as many LDS slots as the batch needs, n >= 2 = at most n, the tiles beyond overflow to S)
- *   CTVIO_GATE_SLICE=n (test only: ctvio_visual_gate_batch walks its windows in slices of at most n block slots instead of 65536) */
+ *   CTVIO_GATE_SLICE=n (test only: ctvio_visual_gate_batch walks its windows in slices of at most n block slots instead of 65536, and
+ *     ctvio_imu_gate_batch in slices of at most n IMU samples instead of 49152) */
 
 #ifdef __cplusplus
 }

@@ -789,6 +789,43 @@ class TrajectoryEstimator {
     for (int32_t v : blocks.status) if (v != 0) return false;
     return true;
   }
+  // After Solve, which IMU samples are outliers (ctvio_imu_gate): the leave-one-out test of every IMU factor added so far, at the CURRENT
+  // parameter values -- the IMU factor carries no robust loss, so a saturated or mis-timed sample pulls the spline at full weight.
+  // samples: per factor, in the order of the AddIMUMeasurementAnalytic calls -- res6 (6 per factor, the whitened residual), redundancy,
+  // chi2 = r^T (I - A)^-1 r (6 degrees of freedom; 16.81 is the 99 % point), with with_cov cov36 (36 per factor, the whitened leave-one-out
+  // prediction covariance) -- and one ctvio_imu_gate status per factor.  frames (optional): keyed by the gyro-bias pointer -- the number of
+  // its status-0 samples, their mean and largest chi2 (the mean is 6 under the model: a check of the IMU weights) and the smallest
+  // redundancy.  Returns false if any status is not 0.
+  struct IMUGate {
+    std::vector<double> res6, redundancy, cov36, chi2;
+    std::vector<int32_t> status;
+  };
+  struct FrameGate { int32_t count; double mean_chi2, max_chi2, min_redundancy; };
+  bool GateIMUSamples(IMUGate &samples, std::map<const double *, FrameGate> *frames = nullptr, double min_redundancy = 0.01, bool with_cov = false) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    const size_t M = (size_t)pk.w.M, F = (size_t)pk.w.F;
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_gate_options o;
+    ctvio_default_gate_options(&o);
+    o.min_redundancy = min_redundancy;
+    samples.res6.assign(6 * M, 0.0); samples.redundancy.assign(M, 0.0); samples.chi2.assign(M, 0.0); samples.status.assign(M, 0);
+    samples.cov36.assign(with_cov ? 36 * M : 0, 0.0);
+    std::vector<double> fs(frames ? 4 * F : 0);
+    check(ctvio_imu_gate(s, 0, &o, samples.res6.data(), samples.redundancy.data(), with_cov ? samples.cov36.data() : nullptr, samples.chi2.data(),
+                         samples.status.data(), fs.empty() ? nullptr : fs.data()));
+    if (frames) {
+      frames->clear();
+      for (size_t f = 0; f < bias_ptr_.size(); ++f) {
+        const int j = pk.bias_map[f];
+        if (j < 0) continue;
+        (*frames)[bias_ptr_[f].first] = FrameGate{(int32_t)fs[4 * (size_t)j], fs[4 * (size_t)j + 1], fs[4 * (size_t)j + 2], fs[4 * (size_t)j + 3]};
+      }
+    }
+    for (int32_t v : samples.status) if (v != 0) return false;
+    return true;
+  }
   // Where landmarks fall in the NEXT image, beyond the solved knots (ctvio_predict_landmarks): PredictIMUStates' dead reckoning through
   // `samples` (samples[0] inside the solved knots, the newest frame time in the reference's use; bias_gyr as there) composed with
   // ProjectLandmarks at the predicted pose.  Point i = (the inverse-depth pointer, image row).  end (optional): the predicted state at the last
