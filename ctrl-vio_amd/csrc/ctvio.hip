@@ -1217,7 +1217,7 @@ class SolverImpl {
   int spline_eval_batch(int64_t n64, const int32_t *win, const int64_t *t_ns, double *pose7, double *vel3, double *omega3, double *acc3,
                         double *kernel_ms) {
     if (const int rc = guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || !win))) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (!check_count(n64) || (n64 && (!t_ns || !win))) return fail(CTVIO_ERR_INVALID, "bad arguments");
     if (kernel_ms) *kernel_ms = 0.0;
     return spline_query(0, win, (int)n64, t_ns, pose7, vel3, omega3, acc3, SensorExt{}, kernel_ms);
   }
@@ -1261,10 +1261,10 @@ class SolverImpl {
   // ---------------------------------------------------------------------------------------- marginal covariances
   // ctvio_covariance_batch / ctvio_covariance (only >= 0: that window alone, n_sel / sel / outputs are its own).  The normal equations of the
   // current state (as ctvio_linearize forms them), then Schur complement and panel Cholesky on a COPY of Dev -- per-call activity mask, zero
-  // damping, every tile of S written -- and the kernels of csrc/kernels_cov.hpp.  dev_, plan_ and the captured graph are not touched; the panel
+  // damping, every tile of S written -- and the kernels of csrc/kernels_cov.hpp, in run_query's sequence (below; always full).  The panel
   // kernel launches from the plan like the solve's (launch_chol_panel).  The scratch follows the call's selections, not the upload.
   static constexpr int COV_MAX_SEL = 64;
-  // The shared middle of covariance() and pose_covariance(): the normal equations at the current state, then the factor of the undamped
+  // What every full call of run_query starts with: the normal equations at the current state, then the factor of the undamped
   // reduced system on c, the call's copy of Dev.  Records EV_CALL_BEGIN .. EV_COV_SOLVE; the stream is left ready for k_cov_solve.
   int cov_factor(Dev &c, uint8_t *mask, uint8_t *excl) {
     set_params(1);
@@ -1287,7 +1287,8 @@ class SolverImpl {
   }
   // the device times of a call between pairs of its events (the stream is idle): ms[slot] of ctvio_last_timing, one launch each where it ran
   struct Span { int slot; Ev begin, end; bool ran = true; };
-  int span_timing(std::initializer_list<Span> spans) {
+  typedef std::initializer_list<Span> Spans;
+  int span_timing(Spans spans) {
     Timing t;
     t.clear();
     for (const Span &s : spans) {
@@ -1297,14 +1298,16 @@ class SolverImpl {
     }
     return publish_timing(t, 0);
   }
-  // ---- the query entries (pose_covariance .. project_landmarks) share what follows.  Each validates its arguments, groups its queries by
-  // window (host_pack.hpp: QueryOrder), names its segments ONCE -- what a call without covariances does not need has no elements: io is
-  // queries | slot | tiles (in, one staged copy), then the outputs (one copy back); the device-only scratch is CovScratch --, fills the
-  // host inputs, runs run_query and scatters the mirror into the caller's arrays by status.
+  // ---- the entries that factor (covariance .. imu_gate, landmark_points) share what follows.  Each validates its arguments, groups its
+  // queries by window (host_pack.hpp: QueryOrder), names its segments ONCE -- what a call without covariances does not need has no elements:
+  // io is its inputs (one staged copy), then the outputs (one copy back); the device-only scratch is CovScratch --, fills the host inputs,
+  // runs run_query and scatters the mirror into the caller's arrays by status.
   static_assert(POSE_OK == QUERY_OK && POSE_SINGULAR == QUERY_SINGULAR && POSE_UNTOUCHED == QUERY_NO_INFO, "merge_status / fill_not_ok");
   static_assert(LMP_OK == QUERY_OK && LMP_SINGULAR == QUERY_SINGULAR && LMP_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
   static_assert(PRJ_OK == QUERY_OK && PRJ_SINGULAR == QUERY_SINGULAR && PRJ_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
   static_assert(IMUG_OK == QUERY_OK && IMUG_SINGULAR == QUERY_SINGULAR && IMUG_NO_INFO == QUERY_NO_INFO, "merge_status / fill_not_ok");
+  static_assert(GATE_WEAK == IMUG_WEAK, "gate_scatter: one set of codes for the two gates");
+  static constexpr GateCodes GATE_CODES{QUERY_OK, GATE_WEAK, QUERY_SINGULAR, QUERY_NO_INFO};
   // the tiles of a covariance query: at most per_tile consecutive sorted queries of one window each
   static std::vector<CovTile> query_tiles(const QueryOrder &ord, int per_tile, CovKind kind) {
     std::vector<CovTile> tiles;
@@ -1317,38 +1320,102 @@ class SolverImpl {
     if (s_slot >= 0) std::memcpy(io_host<int32_t>(io, s_slot), ord.slot.data(), sizeof(int32_t) * ord.slot.size());
     std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
   }
-  // From "layout reserved, host inputs filled" to "results in the pinned mirror".  io: the segments [s_in, s_out) go to the device in one
-  // copy, [s_out, end) come back in one.  jac(excl, records) launches the entry's record kernel, solve(c, records) its k_cov_solve.
-  // scr null (values only): the record kernel alone, without exclusions and records -- nothing is linearised or factored; ms[2] is its
-  // time.  Otherwise the middle of covariance(): the record kernel runs after k_cov_prepare (it reads the exclusions), k_cov_solve on the
-  // factored copy c of Dev; ms[0] k_cov_prepare, ms[1] k_cov_solve, ms[2] the record kernel.  The window records come back with the
-  // results (Lm::chol_fail).  dev_, plan_ and the captured graph are not touched.
-  template <class Rec, class Jac, class Solve> int run_query(const CallLayout &io, int s_in, int s_out, const CovScratch *scr, Jac &&jac, Solve &&solve) {
-    const size_t in_bytes = io.off(s_out) - io.off(s_in), out_bytes = io.bytes() - io.off(s_out);
-    if (!scr) {
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      if (in_bytes) HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      jac((const uint8_t *)nullptr, (Rec *)nullptr);
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_out), io_dev<char>(io, s_out), out_bytes, hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      return span_timing({{2, EV_QUERY_BEGIN, EV_QUERY_END}});
-    }
-    uint8_t *mask = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_mask), *excl = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_excl);
-    Rec *rec = scr->lay.at<Rec>(call_scr_.dev, scr->s_rec);
-    if (in_bytes) HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
+  // What an entry's launches see of the run (run_query).  excl: the exclusions k_cov_prepare left -- null in a values-only call: nothing
+  // was factored and there are no records --; rec<Rec>(): the record scratch; c: the factored copy of Dev that k_cov_solve runs on.
+  // mark(e) records event e behind what has been launched so far; the first failure is kept and becomes the run's.
+  struct QueryRun {
+    SolverImpl &self;
+    const uint8_t *excl;
+    void *records;
     Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    jac((const uint8_t *)excl, rec);
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    solve(c, (const Rec *)rec);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-    HIPCHK(hipMemcpyAsync(io_host<char>(io, s_out), io_dev<char>(io, s_out), out_bytes, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    return span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_COV_SOLVE, EV_COV_GRAM}});
+    hipError_t err;
+    template <class Rec> Rec *rec() const { return static_cast<Rec *>(records); }
+    void mark(Ev e) {
+      const hipError_t r = hipEventRecord(self.ev_[e], self.stream_);
+      if (err == hipSuccess) err = r;
+    }
+  };
+  // THE run sequence, from "layout reserved, host inputs filled" to "results in the pinned mirror, timing published".  io: the segments
+  // [s_in, s_out) go to the device in one copy, [s_out, end) come back in one.  launches(x) queues the entry's kernels in stream order and
+  // marks the events its span tables name.
+  //   scr null (values only; nothing is linearised or factored): EV_CALL_BEGIN, the copy in, EV_COV_SOLVE where the values table starts
+  //     a span there, launches, the copy back, EV_CALL_END, sync_call, span_timing(values).
+  //   otherwise: the copy in, cov_factor on the call's copy of Dev (EV_CALL_BEGIN .. EV_COV_SOLVE), launches, EV_CALL_END, the copy back
+  //     and the window records (Lm::chol_fail), finish_call, span_timing(full).
+  // So a span from EV_COV_SOLVE starts in front of the entry's first launch either way; ms[0] of a full table is k_cov_prepare (span_prepare()).
+  // dev_, plan_ and the captured graph are not touched.
+  static Span span_prepare() { return {0, EV_COV_PREPARE, EV_COV_FACTOR}; }
+  template <class Launches> int run_query(const CallLayout &io, int s_in, int s_out, const CovScratch *scr, Spans values, Spans full, Launches &&launches) {
+    const size_t in_bytes = io.off(s_out) - io.off(s_in), out_bytes = io.bytes() - io.off(s_out);
+    QueryRun x{*this, nullptr, nullptr, Dev{}, hipSuccess};
+    if (!scr) HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
+    if (in_bytes) HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_in), io_host<char>(io, s_in), in_bytes, hipMemcpyHostToDevice, stream_));
+    if (scr) {
+      x.excl = scr->lay.at<uint8_t>(call_scr_.dev, scr->s_excl);
+      x.records = scr->lay.at<char>(call_scr_.dev, scr->s_rec);
+      if (const int rc = cov_factor(x.c, scr->lay.at<uint8_t>(call_scr_.dev, scr->s_mask), scr->lay.at<uint8_t>(call_scr_.dev, scr->s_excl))) return rc;
+    } else if (std::any_of(values.begin(), values.end(), [](const Span &s) { return s.begin == EV_COV_SOLVE; })) {
+      HIPCHK(hipEventRecord(ev_[EV_COV_SOLVE], stream_));   // (an event costs a few microseconds of the call: none that no span reads)
+    }
+    launches(x);
+    HIPCHK(x.err);
+    if (scr) HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    if (out_bytes) HIPCHK(hipMemcpyAsync(io_host<char>(io, s_out), io_dev<char>(io, s_out), out_bytes, hipMemcpyDeviceToHost, stream_));
+    if (scr) HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
+    else HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    if (const int rc = scr ? finish_call(io) : sync_call()) return rc;
+    return span_timing(scr ? full : values);
+  }
+  // The usual launches: jac(x), the entry's record kernel -- after k_cov_prepare in a full call: it reads the exclusions --, then
+  // solve(x), its k_cov_solve.  ms[1] k_cov_solve, ms[2] the record kernel (values only: ms[values_slot]).
+  template <class Jac, class Solve>
+  int run_query(const CallLayout &io, int s_in, int s_out, const CovScratch *scr, Jac &&jac, Solve &&solve, int values_slot = 2) {
+    return run_query(io, s_in, s_out, scr, {{values_slot, EV_COV_SOLVE, EV_COV_GRAM}}, {span_prepare(), {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_COV_SOLVE, EV_COV_GRAM}},
+                     [&](QueryRun &x) {
+                       jac(x);
+                       x.mark(EV_COV_GRAM);
+                       if (x.excl) solve(x);
+                     });
+  }
+  // The windows [wbeg, wend) of a leave-one-out gate cut into slices of at most `budget` slots (plan_gate_slices; CTVIO_GATE_SLICE
+  // overrides the budget), window w holding meta_[w].*count of them: the record scratch is bounded by nrec, the largest slice.
+  struct GateSlices {
+    std::vector<int32_t> counts;   // by window, the whole batch
+    std::vector<GateSlice> slices;
+    size_t nrec = 0;
+  };
+  GateSlices gate_slices(int32_t WinMeta::*count, int wbeg, int wend, size_t budget) const {
+    GateSlices g;
+    for (const WinMeta &m : meta_) g.counts.push_back(m.*count);
+    g.slices = plan_gate_slices(g.counts.data(), wbeg, wend, dbg_.gate_slice > 0 ? (size_t)dbg_.gate_slice : budget);
+    for (const GateSlice &sl : g.slices) g.nrec = std::max(g.nrec, (size_t)sl.slots);
+    return g;
+  }
+  // run_query for a gate; slot0: the WinMeta member that holds a window's first slot.  Values only: record(x, s0, nall) over every slot at
+  // once and reduce(x), both in ms[2].  Otherwise one factorisation, then per slice record(x, first slot, slots) and solve(x, slice,
+  // first slot, slots) -- the first slice's record kernel is the timed one (ms[2]), the later slices' fall inside ms[1] --, then
+  // reduce(x) (ms[3]).
+  template <class Record, class Solve, class Reduce>
+  int run_gate(const CallLayout &io, int s_in, int s_out, const CovScratch *scr, const GateSlices &gs, int32_t WinMeta::*slot0, int s0, int nall, Record &&record,
+               Solve &&solve, Reduce &&reduce) {
+    return run_query(io, s_in, s_out, scr, {{2, EV_COV_SOLVE, EV_COV_GRAM}},
+                     {span_prepare(), {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}, [&](QueryRun &x) {
+                       if (!x.excl) {
+                         if (nall) record(x, s0, nall);
+                         reduce(x);
+                         x.mark(EV_COV_GRAM);
+                         return;
+                       }
+                       for (size_t si = 0; si < gs.slices.size(); ++si) {
+                         const int first = meta_[gs.slices[si].wbeg].*slot0, n = (int)gs.slices[si].slots;
+                         if (n) record(x, first, n);
+                         if (si == 0) x.mark(EV_COV_GRAM);
+                         if (n) solve(x, si, first, n);
+                       }
+                       x.mark(EV_QUERY_BEGIN);
+                       reduce(x);
+                       x.mark(EV_QUERY_END);
+                     });
   }
   int covariance(int only, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
     if (const int rc = guard()) return rc;
@@ -1387,16 +1454,16 @@ class SolverImpl {
         nsel_tot += (size_t)ns; ncov += (size_t)ns * ns;
       }
     }
-    // ---- scratch.  io: selections, tiles, windows (in, one staged copy); cov | var_rho (Ltot, batch order) (out, one copy).  scr: mask, exclusions, Y
+    // ---- scratch.  io: selections, tiles, windows (in, one staged copy); cov | var_rho (Ltot, batch order) (out, one copy).  scr: mask,
+    // exclusions, no records, Y
     const size_t nvar = var_rho ? (size_t)dev_.Ltot : 0;
-    CallLayout io = head_, scr;
+    CovScratch cs(true, (size_t)dev_.Utot, 0, 0);
+    CallLayout io = head_, &scr = cs.lay;
     const int s_sel = io.add("sel", sizeof(int32_t), nsel_tot, false), s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
               s_wins = io.add("wins", sizeof(CovWin), cwins.size(), false), s_cov = io.add("cov", sizeof(double), ncov, true),
               s_var = io.add("var_rho", sizeof(double), nvar, true);
-    const int s_mask = scr.add("mask", 1, (size_t)dev_.Utot, false), s_excl = scr.add("excl", 1, (size_t)dev_.Utot, false),
-              s_y = scr.add("Y", sizeof(double), ycount, true);
+    const int s_y = scr.add("Y", sizeof(double), ycount, true);
     if (const int rc = reserve_call(io, &scr)) return rc;
-    uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, s_excl);
     double *dy = scr.at<double>(call_scr_.dev, s_y), *dcov = io_dev<double>(io, s_cov), *dvar = io_dev<double>(io, s_var);
     const int32_t *dsel = io_dev<int32_t>(io, s_sel);
     const CovTile *dtiles = io_dev<CovTile>(io, s_tiles);
@@ -1406,26 +1473,20 @@ class SolverImpl {
     if (nsel_tot) std::memcpy(io_host<int32_t>(io, s_sel), sel, sizeof(int32_t) * nsel_tot);
     if (!tiles.empty()) std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
     if (!cwins.empty()) std::memcpy(io_host<CovWin>(io, s_wins), cwins.data(), sizeof(CovWin) * cwins.size());
-    if (io.off(s_cov) > io.off(s_sel))
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_sel), io_host<char>(io, s_sel), io.off(s_cov) - io.off(s_sel), hipMemcpyHostToDevice, stream_));
-    Dev c;
-    if (const int rc = cov_factor(c, mask, excl)) return rc;
-    if (!tiles.empty()) {
-      CovSolveIO<COV_BASE> a;
-      a.tiles = dtiles; a.sel = dsel; a.Y = dy; a.var_rho = dvar;
-      launch_cov_solve(c, tiles.size(), a);
-    }
-    HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-    if (!cwins.empty())
-      hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, c, dwins, dsel, excl, dy, dcov);
-    HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
+    // the run sequence with k_cov_solve (ms[1]) and k_cov_gram (ms[2]) for launches, each where the call has work for it
+    const int rc = run_query(io, s_sel, s_cov, &cs, {}, {span_prepare(), {1, EV_COV_SOLVE, EV_COV_GRAM, !tiles.empty()}, {2, EV_COV_GRAM, EV_CALL_END, !cwins.empty()}},
+                             [&](QueryRun &x) {
+                               if (!tiles.empty()) {
+                                 CovSolveIO<COV_BASE> a;
+                                 a.tiles = dtiles; a.sel = dsel; a.Y = dy; a.var_rho = dvar;
+                                 launch_cov_solve(x.c, tiles.size(), a);
+                               }
+                               x.mark(EV_COV_GRAM);
+                               if (!cwins.empty())
+                                 hipLaunchKernelGGL(k_cov_gram, dim3(10, (unsigned)cwins.size()), dim3(256), 0, stream_, x.c, dwins, dsel, x.excl, dy, dcov);
+                             });
+    if (rc) return rc;
     // ---- results
-    if (ncov + nvar) HIPCHK(hipMemcpyAsync((void *)hcov, dcov, io.bytes() - io.off(s_cov), hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(lm, dev_.lm, sizeof(Lm) * nw, hipMemcpyDeviceToHost, stream_));
-    if (const int rc = finish_call(io)) return rc;
-    // device times of this call, for ctvio_last_timing: the three covariance kernels and the whole call
-    if (const int rc = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_SOLVE, EV_COV_GRAM, !tiles.empty()}, {2, EV_COV_GRAM, EV_CALL_END, !cwins.empty()}}))
-      return rc;
     // (a window whose factorisation met a non-positive or non-finite pivot: its outputs are NaN)
     const double nan = std::nan("");
     size_t oc = 0, ov = 0;
@@ -1446,11 +1507,11 @@ class SolverImpl {
   // ctvio_pose_covariance_batch / ctvio_pose_covariance (only >= 0: every query belongs to that window, win is not read): J Sigma J^T of the
   // pose at n query times.  The queries are grouped by window (stable: a window's queries keep the caller's order) and paired into tiles of
   // kind TILE_POSE; k_cov_pose_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 6 x 6 blocks into the
-  // caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are not touched.
+  // caller's slots (run_query, always full).
   int pose_covariance(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const double *q_SI, const double *p_SI, double *cov36,
                       int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || !cov36 || (only < 0 && !win)))) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (!check_count(n64) || (n64 && (!t_ns || !cov36 || (only < 0 && !win)))) return fail(CTVIO_ERR_INVALID, "bad arguments");
     if ((q_SI == nullptr) != (p_SI == nullptr)) return fail(CTVIO_ERR_INVALID, "sensor extrinsic: q_SI and p_SI come together (both null: the body pose)");
     SensorExt ext{};
     if (q_SI)
@@ -1471,15 +1532,16 @@ class SolverImpl {
     PoseQuery *hq = io_host<PoseQuery>(io, s_q);
     for (int r = 0; r < n; ++r) hq[r] = PoseQuery{ord.win_of(r), 0, (long long)(t_ns[ord.slot[(size_t)r]] - t0_[ord.win_of(r)])};
     stage_tiles(io, s_slot, s_tiles, ord, tiles);
-    const int rc = run_query<PoseRec>(
+    const int rc = run_query(
         io, s_q, s_cov, &scr,
-        [&](const uint8_t *excl, PoseRec *rec) {
-          hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), excl, ext, rec, io_dev<int32_t>(io, s_stat));
+        [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_pose_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<PoseQuery>(io, s_q), x.excl, ext, x.rec<PoseRec>(),
+                             io_dev<int32_t>(io, s_stat));
         },
-        [&](const Dev &c, const PoseRec *rec) {
+        [&](QueryRun &x) {
           CovSolveIO<COV_BASE> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
-          launch_cov_solve(c, tiles.size(), a);
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = x.rec<PoseRec>(); a.blocks = io_dev<double>(io, s_cov);
+          launch_cov_solve(x.c, tiles.size(), a);
         });
     if (rc) return rc;
     // ---- results: the blocks as the kernel left them (the caller's order), the statuses in sorted order (time outside the spline: NaN)
@@ -1498,18 +1560,19 @@ class SolverImpl {
   // world velocity, the biases of state frame[i]; frame null: the newest) at n query times and J Sigma J^T of its 15 tangent dimensions.
   // Values only (cov225 null): k_cov_nav_jac alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable)
   // into tiles of kind TILE_NAV, one each; k_cov_nav_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the
-  // 15 x 15 blocks into the caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are not touched.
+  // 15 x 15 blocks into the caller's slots (run_query).
   int nav_state(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const int32_t *frame, double *state16, double *cov225, int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || (only < 0 && !win) || (!state16 && !cov225 && !status))))
+    if (!check_count(n64) || (n64 && (!t_ns || (only < 0 && !win) || (!state16 && !cov225 && !status))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
     const int n = (int)n64;
     const size_t nn = (size_t)n;
     const QueryOrder ord(only, n, win, dev_.nwin);
     if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
+    std::string err;
     for (int i = 0; i < n; ++i) {
       const int w = only >= 0 ? only : win[i];
-      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": bias state out of range");
+      if (!check_frame(frame, i, meta_[w].F, "query", err)) return fail(CTVIO_ERR_INVALID, err);
     }
     if (n == 0) return CTVIO_OK;
     const bool want_cov = cov225 != nullptr;
@@ -1529,16 +1592,16 @@ class SolverImpl {
       hq[r] = NavQuery{w, frame ? frame[i] : meta_[w].F - 1, (long long)(t_ns[i] - t0_[w])};
     }
     stage_tiles(io, s_slot, s_tiles, ord, tiles);
-    const int rc = run_query<NavRec>(
+    const int rc = run_query(
         io, s_q, s_cov, want_cov ? &scr : nullptr,
-        [&](const uint8_t *excl, NavRec *rec) {
-          hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), excl, rec, io_dev<double>(io, s_state),
-                             io_dev<int32_t>(io, s_stat));
+        [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), x.excl, x.rec<NavRec>(),
+                             io_dev<double>(io, s_state), io_dev<int32_t>(io, s_stat));
         },
-        [&](const Dev &c, const NavRec *rec) {
+        [&](QueryRun &x) {
           CovSolveIO<COV_BASE> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.nrec = rec; a.nav_cov = io_dev<double>(io, s_cov);
-          launch_cov_solve(c, tiles.size(), a);
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.nrec = x.rec<NavRec>(); a.nav_cov = io_dev<double>(io, s_cov);
+          launch_cov_solve(x.c, tiles.size(), a);
         });
     if (rc) return rc;
     // ---- results: the blocks as the kernel left them (the caller's order), the states and statuses in sorted order (time outside the
@@ -1558,13 +1621,13 @@ class SolverImpl {
   // ctvio_body_rates_batch / ctvio_body_rates (only >= 0: every query belongs to that window, win is not read): body angular velocity,
   // specific force and body-frame velocity at n query times, J Sigma J^T of (domega, df, dv_B, dbg, dba) with the biases of state frame[i]
   // (frame null: the newest), and the gate of a candidate IMU sample.  Values only (cov225 and chi2 null): k_cov_rates_jac alone, nothing
-  // is linearised or factored.  Otherwise nav_state()'s middle: the queries grouped by window (stable) into tiles of kind TILE_RATES, one each;
+  // is linearised or factored.  Otherwise the queries are grouped by window (stable) into tiles of kind TILE_RATES, one each;
   // k_cov_rates_jac writes one record per query after k_cov_prepare (it reads the exclusions), k_cov_solve the 15 x 15 blocks and the gates
-  // into the caller's slots.  dev_, plan_ and the captured graph are not touched.
+  // into the caller's slots (run_query).
   int body_rates(int only, int64_t n64, const int32_t *win, const int64_t *t_ns, const int32_t *frame, const double *meas6, const double *noise6,
                  double *rates9, double *cov225, double *chi2, int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_ns || (only < 0 && !win) || (!rates9 && !cov225 && !chi2 && !status) || (chi2 && !meas6))))
+    if (!check_count(n64) || (n64 && (!t_ns || (only < 0 && !win) || (!rates9 && !cov225 && !chi2 && !status) || (chi2 && !meas6))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
     const int n = (int)n64;
     const size_t nn = (size_t)n;
@@ -1573,9 +1636,10 @@ class SolverImpl {
         if (!(noise6[c] > 0.0) || !std::isfinite(noise6[c])) return fail(CTVIO_ERR_INVALID, "noise6: six positive, finite standard deviations");
     const QueryOrder ord(only, n, win, dev_.nwin);
     if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
+    std::string err;
     for (int i = 0; i < n; ++i) {
       const int w = only >= 0 ? only : win[i];
-      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": bias state out of range");
+      if (!check_frame(frame, i, meta_[w].F, "query", err)) return fail(CTVIO_ERR_INVALID, err);
       for (int c = 0; c < 6; ++c) {
         if (meas6 && !std::isfinite(meas6[6 * (size_t)i + c])) return fail(CTVIO_ERR_INVALID, "query " + std::to_string(i) + ": non-finite IMU sample");
         if (chi2 && !noise6 && !(meta_[w].imu_w[c] > 0.0))
@@ -1603,17 +1667,17 @@ class SolverImpl {
       hq[r] = q;
     }
     stage_tiles(io, s_slot, s_tiles, ord, tiles);
-    const int rc = run_query<RatesRec>(
+    const int rc = run_query(
         io, s_q, s_cov, want_cov ? &scr : nullptr,
-        [&](const uint8_t *excl, RatesRec *rec) {
-          hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), excl, rec, io_dev<double>(io, s_val),
-                             io_dev<int32_t>(io, s_stat));
+        [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_rates_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RatesQuery>(io, s_q), x.excl, x.rec<RatesRec>(),
+                             io_dev<double>(io, s_val), io_dev<int32_t>(io, s_stat));
         },
-        [&](const Dev &c, const RatesRec *rec) {
+        [&](QueryRun &x) {
           CovSolveIO<COV_RATES> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = x.rec<RatesRec>(); a.blocks = io_dev<double>(io, s_cov);
           if (chi2) a.chi2 = io_dev<double>(io, s_chi);
-          launch_cov_solve(c, tiles.size(), a);
+          launch_cov_solve(x.c, tiles.size(), a);
         });
     if (rc) return rc;
     // ---- results: the blocks and gates as the kernel left them (the caller's order), the values and statuses in sorted order (time
@@ -1633,41 +1697,25 @@ class SolverImpl {
   }
   // ctvio_imu_predict_batch / ctvio_imu_predict (only >= 0: every query belongs to that window, win is not read): the navigation state of
   // query i at imu_t[first sample of i] (bias state frame[i]; frame null: the newest) carried through the query's n_imu[i] samples by
-  // k_imu_propagate, with its 15 x 15 covariance.  The middle is nav_state()'s: queries grouped by window (stable), k_cov_nav_jac, and with
-  // cov225 cov_factor and k_cov_solve on TILE_NAV tiles, whose slot is the query's first output entry, so that P_0 lands where sample 0
-  // is reported.  The samples of all queries are staged with the queries in one copy.  dev_, plan_ and the captured graph are not touched.
+  // k_imu_propagate, with its 15 x 15 covariance.  nav_state()'s launches -- queries grouped by window (stable), k_cov_nav_jac, and with
+  // cov225 k_cov_solve on TILE_NAV tiles, whose slot is the query's first output entry, so that P_0 lands where sample 0 is reported --,
+  // then k_imu_propagate (run_query with a fourth timing slot).  The samples of all queries (ImuSamples) are staged with the queries in one copy.
   int imu_predict(int only, int64_t n64, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t, const double *imu_gyro,
                   const double *imu_acc, const ctvio_imu_noise *noise, int last_only, double *state16, double *cov225, int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 ||
+    if (!check_count(n64) ||
         (n64 && (!n_imu || !imu_t || !imu_gyro || !imu_acc || !noise || (only < 0 && !win) || (!state16 && !cov225 && !status))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
     const int n = (int)n64;
     const size_t nn = (size_t)n;
     if (n == 0) return CTVIO_OK;
-    {
-      const double sg[4] = {noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
-      for (double x : sg)
-        if (!(x >= 0.0) || !std::isfinite(x)) return fail(CTVIO_ERR_INVALID, "a noise sigma is negative or not finite");
-    }
+    ImuSamples sam;
+    if (!sam.noise(*noise)) return fail(CTVIO_ERR_INVALID, sam.error);
     const QueryOrder ord(only, n, win, dev_.nwin);
     if (!ord.error().empty()) return fail(CTVIO_ERR_INVALID, ord.error());
-    std::vector<int64_t> first(nn + 1, 0);   // first sample of every query (the caller's order)
-    for (int i = 0; i < n; ++i) {
-      const int w = only >= 0 ? only : win[i];
-      const std::string what = "query " + std::to_string(i);
-      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, what + ": bias state out of range");
-      if (n_imu[i] < 1 || n_imu[i] > 4096) return fail(CTVIO_ERR_INVALID, what + ": 1 to 4096 samples");
-      const int64_t b = first[(size_t)i], e = b + n_imu[i];
-      first[(size_t)i + 1] = e;
-      for (int64_t j = b; j < e; ++j) {
-        if (j > b && imu_t[j] <= imu_t[j - 1]) return fail(CTVIO_ERR_INVALID, what + ": sample times not strictly increasing");
-        for (int c = 0; c < 3; ++c)
-          if (!std::isfinite(imu_gyro[3 * j + c]) || !std::isfinite(imu_acc[3 * j + c])) return fail(CTVIO_ERR_INVALID, what + ": a measurement is not finite");
-      }
-    }
-    const size_t ns = (size_t)first[nn], no = last_only ? nn : ns;   // samples; output entries
-    if (ns > (size_t)1 << 30) return fail(CTVIO_ERR_INVALID, "more than 2^30 samples in one call");
+    if (!sam.streams("query", only, n, win, frame, meta_.data(), n_imu, imu_t, imu_gyro, imu_acc)) return fail(CTVIO_ERR_INVALID, sam.error);
+    const std::vector<int64_t> &first = sam.first;   // first sample of every query (the caller's order)
+    const size_t ns = sam.ns, no = last_only ? nn : ns;   // samples; output entries
     auto entry0 = [&](size_t i) { return last_only ? (int64_t)i : first[i]; };
     auto entries = [&](size_t i) { return last_only ? (size_t)1 : (size_t)n_imu[i]; };
     const bool want_cov = cov225 != nullptr;
@@ -1676,10 +1724,9 @@ class SolverImpl {
     // status (out, one copy).  scr: mask, exclusions, records, the states at sample 0
     CovScratch cs(want_cov, (size_t)dev_.Utot, sizeof(NavRec), nn);
     CallLayout io = head_, &scr = cs.lay;
-    const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_pq = io.add("prop", sizeof(PropQuery), nn, false),
-              s_t = io.add("imu_t", sizeof(int64_t), ns, false), s_gyro = io.add("imu_gyro", sizeof(double), 3 * ns, false),
-              s_acc = io.add("imu_acc", sizeof(double), 3 * ns, false), s_slot = io.add("entry", sizeof(int32_t), want_cov ? nn : 0, false),
-              s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
+    const int s_q = io.add("queries", sizeof(NavQuery), nn, false), s_pq = io.add("prop", sizeof(PropQuery), nn, false);
+    sam.add(io);
+    const int s_slot = io.add("entry", sizeof(int32_t), want_cov ? nn : 0, false), s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false),
               s_cov = io.add("cov225", sizeof(double), want_cov ? 225 * no : 0, true), s_state = io.add("state16", sizeof(double), 16 * no, true),
               s_stat = io.add("status", sizeof(int32_t), nn, false);
     const int s_x0 = scr.add("state0", sizeof(double), 16 * nn, true);
@@ -1694,54 +1741,28 @@ class SolverImpl {
       if (want_cov) io_host<int32_t>(io, s_slot)[r] = (int32_t)entry0(i);
     }
     stage_tiles(io, -1, s_tiles, ord, tiles);
-    std::memcpy(io_host<int64_t>(io, s_t), imu_t, sizeof(int64_t) * ns);
-    std::memcpy(io_host<double>(io, s_gyro), imu_gyro, sizeof(double) * 3 * ns);
-    std::memcpy(io_host<double>(io, s_acc), imu_acc, sizeof(double) * 3 * ns);
+    sam.stage(io, call_io_.host);
     const ImuNoise nz{noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
     double *x0 = scr.at<double>(call_scr_.dev, s_x0);
-    const size_t in_bytes = io.off(want_cov ? s_cov : s_state) - io.off(s_q), out0 = io.off(want_cov ? s_cov : s_state);
-    auto propagate = [&]() {
-      hipLaunchKernelGGL(k_imu_propagate, dim3(nblk(n, 4)), dim3(64), 0, stream_, dev_, n, io_dev<PropQuery>(io, s_pq), io_dev<int32_t>(io, s_stat),
-                         io_dev<long long>(io, s_t), io_dev<double>(io, s_gyro), io_dev<double>(io, s_acc), nz, last_only ? 1 : 0, (const double *)x0,
-                         io_dev<double>(io, s_state), want_cov ? io_dev<double>(io, s_cov) : (double *)nullptr);
-    };
-    // (run_query's sequence with k_imu_propagate behind the record kernel or the solve, timed as ms[3])
-    if (!want_cov) {
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)nullptr, (NavRec *)nullptr,
-                         x0, io_dev<int32_t>(io, s_stat));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      propagate();
-      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), io.bytes() - out0, hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      if (const int rc = span_timing({{2, EV_QUERY_BEGIN, EV_QUERY_END}, {3, EV_QUERY_END, EV_COV_GRAM}})) return rc;
-    } else {
-      uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, cs.s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, cs.s_excl);
-      NavRec *drec = scr.at<NavRec>(call_scr_.dev, cs.s_rec);
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
-      Dev c;
-      if (const int rc = cov_factor(c, mask, excl)) return rc;
-      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), (const uint8_t *)excl, drec, x0,
-                         io_dev<int32_t>(io, s_stat));
-      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      CovSolveIO<COV_BASE> a;
-      a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.nrec = drec; a.nav_cov = io_dev<double>(io, s_cov);
-      launch_cov_solve(c, tiles.size(), a);
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      propagate();
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_cov), io_dev<char>(io, s_cov), io.bytes() - out0, hipMemcpyDeviceToHost, stream_));   // (cov225 | state16 | status)
-      HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
-      if (const int rc = finish_call(io)) return rc;
-      if (const int rc = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM},
-                                      {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
-        return rc;
-    }
+    // the launches: k_cov_nav_jac (ms[2]), with cov225 k_cov_solve (ms[1]), then k_imu_propagate (ms[3]) behind whichever came last
+    const int rc = run_query(
+        io, s_q, s_cov, want_cov ? &cs : nullptr, {{2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_COV_GRAM, EV_QUERY_END}},
+        {span_prepare(), {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}, [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<NavQuery>(io, s_q), x.excl, x.rec<NavRec>(), x0,
+                             io_dev<int32_t>(io, s_stat));
+          x.mark(EV_COV_GRAM);
+          if (x.excl) {
+            CovSolveIO<COV_BASE> a;
+            a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.nrec = x.rec<NavRec>(); a.nav_cov = io_dev<double>(io, s_cov);
+            launch_cov_solve(x.c, tiles.size(), a);
+            x.mark(EV_QUERY_BEGIN);
+          }
+          hipLaunchKernelGGL(k_imu_propagate, dim3(nblk(n, 4)), dim3(64), 0, stream_, dev_, n, io_dev<PropQuery>(io, s_pq), io_dev<int32_t>(io, s_stat),
+                             io_dev<long long>(io, sam.s_t), io_dev<double>(io, sam.s_gyro), io_dev<double>(io, sam.s_acc), nz, last_only ? 1 : 0, (const double *)x0,
+                             io_dev<double>(io, s_state), want_cov ? io_dev<double>(io, s_cov) : (double *)nullptr);
+          x.mark(EV_QUERY_END);
+        });
+    if (rc) return rc;
     // ---- results, every entry of a query by the query's status (time outside the spline: NaN)
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov), *hstate = io_host<double>(io, s_state);
@@ -1762,12 +1783,11 @@ class SolverImpl {
   // T(t_a)^-1 T(t_b) of n pairs of times and J_rel Sigma J_rel^T of its six tangent dimensions.  Values only (cov36 null): k_cov_rel_jac
   // alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a window's queries keep the caller's
   // order) and paired into tiles of kind TILE_REL; k_cov_rel_jac writes one record per query after k_cov_prepare (it reads the exclusions),
-  // k_cov_solve the 6 x 6 blocks into the caller's slots.  Around them the middle of covariance(): dev_, plan_ and the captured graph are
-  // not touched.
+  // k_cov_solve the 6 x 6 blocks into the caller's slots (run_query).
   int relative_pose(int only, int64_t n64, const int32_t *win, const int64_t *t_a_ns, const int64_t *t_b_ns, const double *q_SI, const double *p_SI,
                     double *rel7, double *cov36, int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!t_a_ns || !t_b_ns || (only < 0 && !win) || (!rel7 && !cov36 && !status))))
+    if (!check_count(n64) || (n64 && (!t_a_ns || !t_b_ns || (only < 0 && !win) || (!rel7 && !cov36 && !status))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
     if ((q_SI == nullptr) != (p_SI == nullptr)) return fail(CTVIO_ERR_INVALID, "sensor extrinsic: q_SI and p_SI come together (both null: the body pose)");
     SensorExt ext{};
@@ -1795,16 +1815,16 @@ class SolverImpl {
       hq[r] = RelQuery{w, 0, (long long)(t_a_ns[i] - t0_[w]), (long long)(t_b_ns[i] - t0_[w])};
     }
     stage_tiles(io, s_slot, s_tiles, ord, tiles);
-    const int rc = run_query<RelRec>(
+    const int rc = run_query(
         io, s_q, s_rel, want_cov ? &scr : nullptr,
-        [&](const uint8_t *excl, RelRec *rec) {
-          hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), excl, ext, rec, io_dev<double>(io, s_rel),
-                             io_dev<int32_t>(io, s_stat));
+        [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_rel_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<RelQuery>(io, s_q), x.excl, ext, x.rec<RelRec>(),
+                             io_dev<double>(io, s_rel), io_dev<int32_t>(io, s_stat));
         },
-        [&](const Dev &c, const RelRec *rec) {
+        [&](QueryRun &x) {
           CovSolveIO<COV_REL> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
-          launch_cov_solve(c, tiles.size(), a);
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.slot = io_dev<int32_t>(io, s_slot); a.rec = x.rec<RelRec>(); a.blocks = io_dev<double>(io, s_cov);
+          launch_cov_solve(x.c, tiles.size(), a);
         });
     if (rc) return rc;
     // ---- results: the blocks as the kernel left them (the caller's order), the values and statuses in sorted order (either time outside
@@ -1825,12 +1845,11 @@ class SolverImpl {
   // image point of landmark lm[i] in the camera at (t_ns[i], row[i]), its 2 x 2 covariance and the gate of a candidate point.  Values only
   // (cov4 and chi2 null): k_cov_proj_jac alone, nothing is linearised or factored.  Otherwise the queries are grouped by window (stable: a
   // window's queries keep the caller's order), eight to a tile of kind TILE_PROJ; k_cov_proj_jac writes one record per query after k_cov_prepare (it
-  // reads the exclusions and 1 / Hll), k_cov_solve the 2 x 2 blocks and gates by record.  Around them the middle of covariance(): dev_, plan_
-  // and the captured graph are not touched.
+  // reads the exclusions and 1 / Hll), k_cov_solve the 2 x 2 blocks and gates by record (run_query).
   int project_landmarks(int only, int64_t n64, const int32_t *win, const int32_t *lmi, const int64_t *t_ns, const int32_t *row, const ctvio_row_model *rm,
                         const double *obs2, double *proj3, double *cov4, double *chi2, int32_t *row_out, int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (n64 < 0 || n64 > (int64_t)1 << 30 ||
+    if (!check_count(n64) ||
         (n64 && (!lmi || !t_ns || !row || (only < 0 && !win) || (!proj3 && !cov4 && !chi2 && !row_out && !status) || (chi2 && !obs2))))
       return fail(CTVIO_ERR_INVALID, "bad arguments");
     ProjRowModel prm{0.0, 0.0, 1, 0};
@@ -1868,17 +1887,17 @@ class SolverImpl {
       hq[r] = ProjQuery{w, lmi[i], row[i], 0, (long long)(t_ns[i] - t0_[w]), {obs2 ? obs2[2 * i] : 0.0, obs2 ? obs2[2 * i + 1] : 0.0}};
     }
     stage_tiles(io, -1, s_tiles, ord, tiles);
-    const int rc = run_query<ProjRec>(
+    const int rc = run_query(
         io, s_q, s_proj, want_cov ? &scr : nullptr,
-        [&](const uint8_t *excl, ProjRec *rec) {
-          hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), excl, prm, rec, io_dev<double>(io, s_proj),
-                             io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
+        [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_proj_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, n, io_dev<ProjQuery>(io, s_q), x.excl, prm, x.rec<ProjRec>(),
+                             io_dev<double>(io, s_proj), io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
         },
-        [&](const Dev &c, const ProjRec *rec) {
+        [&](QueryRun &x) {
           CovSolveIO<COV_PROJ> a;
-          a.tiles = io_dev<CovTile>(io, s_tiles); a.rec = rec; a.blocks = io_dev<double>(io, s_cov);
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.rec = x.rec<ProjRec>(); a.blocks = io_dev<double>(io, s_cov);
           if (chi2) a.chi2 = io_dev<double>(io, s_chi);
-          launch_cov_solve(c, tiles.size(), a);
+          launch_cov_solve(x.c, tiles.size(), a);
         });
     if (rc) return rc;
     // ---- results (not computable: NaN)
@@ -1899,9 +1918,8 @@ class SolverImpl {
   // ctvio_visual_gate_batch / ctvio_visual_gate (only >= 0: that window alone): the leave-one-out test of every visual block of the windows
   // themselves.  No inputs: k_cov_gate_jac reads the block slots the upload holds and writes by slot; the host scatters into the caller's
   // block order (gate_slot_).  Values only (redundancy, cov4, chi2 and lm_stats3 null): k_cov_gate_jac alone (and k_cov_gate_reduce for
-  // lm_count), nothing is linearised or factored.  Otherwise run_query: one factorisation, then per slice of windows (plan_gate_slices: the
-  // record scratch is bounded) k_cov_gate_jac and k_cov_solve<COV_GATE> (kind TILE_GATE) -- the first slice's record kernel where run_query times
-  // it (ms[2]), the later slices' inside ms[1] --, then k_cov_gate_reduce (ms[3]).  dev_, plan_ and the captured graph are not touched.
+  // lm_count), nothing is linearised or factored.  Otherwise run_gate: per slice of windows k_cov_gate_jac and k_cov_solve<COV_GATE> (kind
+  // TILE_GATE), then k_cov_gate_reduce.
   int visual_gate(int only, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *red, double *cov4, double *chi2, int32_t *status,
                   double *lm_stats3, int32_t *lm_count) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
@@ -1922,14 +1940,10 @@ class SolverImpl {
       return CTVIO_OK;
     }
     const bool full = red || cov4 || chi2 || lm_stats3, want_lm = lm_stats3 || lm_count;
-    std::vector<int32_t> wslots((size_t)dev_.nwin);
-    for (int w = 0; w < dev_.nwin; ++w) wslots[(size_t)w] = meta_[w].Vp;
-    const std::vector<GateSlice> slices = plan_gate_slices(wslots.data(), wbeg, wend, dbg_.gate_slice > 0 ? (size_t)dbg_.gate_slice : GATE_SLICE_SLOTS);
-    size_t nrec = 0;
-    for (const GateSlice &sl : slices) nrec = std::max(nrec, (size_t)sl.slots);
+    const GateSlices gs = gate_slices(&WinMeta::Vp, wbeg, wend, GATE_SLICE_SLOTS);
     // ---- out, by block slot: res2 | weight | depth | redundancy | cov4 | chi2 | status, then by landmark: lm_stats3 | lm_count; no inputs
     const size_t ns = (size_t)nslot, nf = full ? ns : 0, nl = want_lm ? L : 0;
-    CovScratch scr(full, (size_t)dev_.Utot, sizeof(GateRec), nrec);
+    CovScratch scr(full, (size_t)dev_.Utot, sizeof(GateRec), gs.nrec);
     const int s_en = scr.lay.add("enorm", sizeof(double), lm_stats3 ? ns : 0, true);
     CallLayout io = head_;
     const int s_res = io.add("res2", sizeof(double), 2 * ns, true), s_wgt = io.add("weight", sizeof(double), ns, true),
@@ -1941,40 +1955,22 @@ class SolverImpl {
     GateOut out{io_dev<double>(io, s_res), io_dev<double>(io, s_wgt), io_dev<double>(io, s_dep), lm_stats3 ? scr.lay.at<double>(call_scr_.dev, s_en) : nullptr,
                 full ? io_dev<double>(io, s_red) : nullptr, full ? io_dev<double>(io, s_cov) : nullptr, full ? io_dev<double>(io, s_chi) : nullptr,
                 io_dev<int32_t>(io, s_stat), s0, 0, o->min_redundancy};
-    auto slot_range = [&](const GateSlice &sl, int &first, int &n) { first = meta_[sl.wbeg].vis0; n = (int)sl.slots; };
-    auto reduce = [&]() {
-      if (want_lm)
-        hipLaunchKernelGGL(k_cov_gate_reduce, dim3(nblk((int)L, 64)), dim3(64), 0, stream_, dev_, l0, (int)L, out, full ? 1 : 0,
-                           lm_stats3 ? io_dev<double>(io, s_lms) : nullptr, io_dev<int32_t>(io, s_lmc));
-    };
-    hipError_t ev_err = hipSuccess;
-    const int rc = run_query<GateRec>(
-        io, s_res, s_res, full ? &scr : nullptr,
-        [&](const uint8_t *excl, GateRec *rec) {
-          int first = s0, n = nslot;
-          if (excl) slot_range(slices[0], first, n);
-          if (n) hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, excl, rec, out);
-          if (!excl) reduce();
+    const int rc = run_gate(
+        io, s_res, s_res, full ? &scr : nullptr, gs, &WinMeta::vis0, s0, nslot,
+        [&](QueryRun &x, int first, int n) {
+          hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, x.excl, x.rec<GateRec>(), out);
         },
-        [&](const Dev &c, const GateRec *rec) {
-          for (size_t si = 0; si < slices.size(); ++si) {
-            int first, n;
-            slot_range(slices[si], first, n);
-            if (!n) continue;
-            if (si) hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, scr.lay.at<uint8_t>(call_scr_.dev, scr.s_excl), const_cast<GateRec *>(rec), out);
-            CovSolveIO<COV_GATE> a;
-            a.rec = rec; a.slot_base = first; a.gate = out; a.gate.nslot = n;
-            launch_cov_solve(c, (size_t)nblk(n, PRJ_PER_TILE), a);
-          }
-          ev_err = hipEventRecord(ev_[EV_QUERY_BEGIN], stream_);
-          reduce();
-          if (ev_err == hipSuccess) ev_err = hipEventRecord(ev_[EV_QUERY_END], stream_);
+        [&](QueryRun &x, size_t, int first, int n) {
+          CovSolveIO<COV_GATE> a;
+          a.rec = x.rec<GateRec>(); a.slot_base = first; a.gate = out; a.gate.nslot = n;
+          launch_cov_solve(x.c, (size_t)nblk(n, PRJ_PER_TILE), a);
+        },
+        [&](QueryRun &) {
+          if (want_lm)
+            hipLaunchKernelGGL(k_cov_gate_reduce, dim3(nblk((int)L, 64)), dim3(64), 0, stream_, dev_, l0, (int)L, out, full ? 1 : 0,
+                               lm_stats3 ? io_dev<double>(io, s_lms) : nullptr, io_dev<int32_t>(io, s_lmc));
         });
     if (rc) return rc;
-    HIPCHK(ev_err);
-    if (full)
-      if (const int rc2 = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
-        return rc2;
     // ---- results, in the caller's block order.  Precedence 3, 2, 1 (the window's factorisation failed), 4, 0.
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hres = io_host<double>(io, s_res), *hwgt = io_host<double>(io, s_wgt), *hdep = io_host<double>(io, s_dep), *hred = io_host<double>(io, s_red),
@@ -1984,14 +1980,11 @@ class SolverImpl {
       const bool bad = full && lm[w].chol_fail != 0;
       for (size_t b = gate_voff_[(size_t)w]; b < gate_voff_[(size_t)w + 1]; ++b) {
         const size_t i = b - v0, k = (size_t)(gate_slot_[b] - s0);
-        int st = hstat[k];
-        if (bad && (st == PRJ_OK || st == GATE_WEAK)) st = PRJ_SINGULAR;
+        const int st = gate_scatter(GATE_CODES, hstat[k], bad, 2, hred + k, hcov + 4 * k, hchi + k, red ? red + i : nullptr, cov4 ? cov4 + 4 * i : nullptr,
+                                    chi2 ? chi2 + i : nullptr);
         if (res2) { res2[2 * i] = hres[2 * k]; res2[2 * i + 1] = hres[2 * k + 1]; }
         if (weight) weight[i] = hwgt[k];
         if (depth) depth[i] = hdep[k];
-        if (red) red[i] = st == PRJ_OK || st == GATE_WEAK ? hred[k] : (st == PRJ_NO_INFO ? 0.0 : nan);
-        if (cov4) cov_block(cov4 + 4 * i, hcov + 4 * k, 2, st == GATE_WEAK ? (int)QUERY_NO_INFO : st);
-        if (chi2) chi2[i] = gate_value(hchi[k], st == GATE_WEAK ? (int)QUERY_NO_INFO : st);
         if (status) status[i] = st;
       }
     }
@@ -2002,10 +1995,8 @@ class SolverImpl {
   // ctvio_imu_gate_batch / ctvio_imu_gate (only >= 0: that window alone): the leave-one-out test of every IMU sample of the windows
   // themselves.  No inputs but the tile descriptors (one per window and slice): k_cov_imugate_jac reads the packed samples the upload holds
   // and writes by slot; the host scatters into the caller's sample order (imu_slot_).  Values only (redundancy, cov36, chi2 and
-  // frame_stats4 null): k_cov_imugate_jac alone, nothing is linearised or factored.  Otherwise run_query: one factorisation, then per slice
-  // of windows (plan_gate_slices on the sample counts: the record scratch is bounded) k_cov_imugate_jac and k_cov_solve<COV_IMUGATE> -- the
-  // first slice's record kernel where run_query times it (ms[2]), the later slices' inside ms[1] --, then k_cov_imugate_reduce (ms[3]).
-  // dev_, plan_ and the captured graph are not touched.
+  // frame_stats4 null): k_cov_imugate_jac alone, nothing is linearised or factored.  Otherwise run_gate on the sample counts: per slice of
+  // windows k_cov_imugate_jac and k_cov_solve<COV_IMUGATE>, then k_cov_imugate_reduce.
   int imu_gate(int only, const ctvio_gate_options *o, double *res6, double *red, double *cov36, double *chi2, int32_t *status, double *frame_stats4) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
     if (!o) return fail(CTVIO_ERR_INVALID, "null options");
@@ -2022,15 +2013,13 @@ class SolverImpl {
       return CTVIO_OK;
     }
     const bool full = red || cov36 || chi2 || frame_stats4;
-    std::vector<int32_t> wsamples((size_t)dev_.nwin);
-    for (int w = 0; w < dev_.nwin; ++w) wsamples[(size_t)w] = meta_[w].M;
-    const std::vector<GateSlice> slices = plan_gate_slices(wsamples.data(), wbeg, wend, dbg_.gate_slice > 0 ? (size_t)dbg_.gate_slice : IMU_GATE_SLICE_SAMPLES);
-    size_t nrec = 0, ndesc = 0;
-    for (const GateSlice &sl : slices) { nrec = std::max(nrec, (size_t)sl.slots); ndesc += (size_t)(sl.wend - sl.wbeg) + 1; }
+    const GateSlices gs = gate_slices(&WinMeta::M, wbeg, wend, IMU_GATE_SLICE_SAMPLES);
+    size_t ndesc = 0;
+    for (const GateSlice &sl : gs.slices) ndesc += (size_t)(sl.wend - sl.wbeg) + 1;
     // ---- in: the tile descriptors of every slice; out, by packed sample slot: res6 | redundancy | cov36 | chi2 | status, then by bias state:
     // frame_stats4 (the reduction reads redundancy and chi2, so they exist whenever the call factors)
     const size_t nf = full ? M : 0;
-    CovScratch scr(full, (size_t)dev_.Utot, sizeof(ImuGateRec), nrec);
+    CovScratch scr(full, (size_t)dev_.Utot, sizeof(ImuGateRec), gs.nrec);
     CallLayout io = head_;
     const int s_desc = io.add("wtile", sizeof(int32_t), full ? ndesc : 0, false), s_res = io.add("res6", sizeof(double), 6 * M, true),
               s_red = io.add("redundancy", sizeof(double), nf, true), s_cov = io.add("cov36", sizeof(double), cov36 ? 36 * M : 0, true),
@@ -2041,8 +2030,8 @@ class SolverImpl {
     if (full) {
       int32_t *hd = io_host<int32_t>(io, s_desc);
       size_t at = 0;
-      for (const GateSlice &sl : slices) {
-        const std::vector<int32_t> first = plan_imugate_tiles(wsamples.data(), sl.wbeg, sl.wend, IMUG_PER_TILE);
+      for (const GateSlice &sl : gs.slices) {
+        const std::vector<int32_t> first = plan_imugate_tiles(gs.counts.data(), sl.wbeg, sl.wend, IMUG_PER_TILE);
         std::memcpy(hd + at, first.data(), sizeof(int32_t) * first.size());
         desc0.push_back(at);
         at += first.size();
@@ -2050,34 +2039,23 @@ class SolverImpl {
     }
     const ImuGateOut out{io_dev<double>(io, s_res), full ? io_dev<double>(io, s_red) : nullptr, cov36 ? io_dev<double>(io, s_cov) : nullptr,
                          full ? io_dev<double>(io, s_chi) : nullptr, io_dev<int32_t>(io, s_stat), s0, 0, o->min_redundancy};
-    hipError_t ev_err = hipSuccess;
-    const int rc = run_query<ImuGateRec>(
-        io, s_desc, s_res, full ? &scr : nullptr,
-        [&](const uint8_t *excl, ImuGateRec *rec) {
-          const int n = excl ? (int)slices[0].slots : (int)M;
-          if (n) hipLaunchKernelGGL(k_cov_imugate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, s0, n, excl, rec, out);
+    const int rc = run_gate(
+        io, s_desc, s_res, full ? &scr : nullptr, gs, &WinMeta::imu0, s0, (int)M,
+        [&](QueryRun &x, int first, int n) {
+          hipLaunchKernelGGL(k_cov_imugate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, x.excl, x.rec<ImuGateRec>(), out);
         },
-        [&](const Dev &c, const ImuGateRec *rec) {
-          for (size_t si = 0; si < slices.size(); ++si) {
-            const GateSlice &sl = slices[si];
-            const int first = meta_[sl.wbeg].imu0, n = (int)sl.slots;
-            if (!n) continue;
-            if (si) hipLaunchKernelGGL(k_cov_imugate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, scr.lay.at<uint8_t>(call_scr_.dev, scr.s_excl), const_cast<ImuGateRec *>(rec), out);
-            CovSolveIO<COV_IMUGATE> a;
-            a.rec = rec; a.slot_base = first; a.igate = out;
-            a.wtile = io_dev<int32_t>(io, s_desc) + desc0[si]; a.wt_n = sl.wend - sl.wbeg; a.wt_w0 = sl.wbeg;
-            launch_cov_solve(c, (size_t)io_host<int32_t>(io, s_desc)[desc0[si] + (size_t)a.wt_n], a);
-          }
-          ev_err = hipEventRecord(ev_[EV_QUERY_BEGIN], stream_);
+        [&](QueryRun &x, size_t si, int first, int) {
+          const GateSlice &sl = gs.slices[si];
+          CovSolveIO<COV_IMUGATE> a;
+          a.rec = x.rec<ImuGateRec>(); a.slot_base = first; a.igate = out;
+          a.wtile = io_dev<int32_t>(io, s_desc) + desc0[si]; a.wt_n = sl.wend - sl.wbeg; a.wt_w0 = sl.wbeg;
+          launch_cov_solve(x.c, (size_t)io_host<int32_t>(io, s_desc)[desc0[si] + (size_t)a.wt_n], a);
+        },
+        [&](QueryRun &) {
           if (frame_stats4)
             hipLaunchKernelGGL(k_cov_imugate_reduce, dim3(nblk((int)F, 64)), dim3(64), 0, stream_, dev_, f0, (int)F, out, io_dev<double>(io, s_fs));
-          if (ev_err == hipSuccess) ev_err = hipEventRecord(ev_[EV_QUERY_END], stream_);
         });
     if (rc) return rc;
-    HIPCHK(ev_err);
-    if (full)
-      if (const int rc2 = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
-        return rc2;
     // ---- results, in the caller's sample order.  Precedence 2, 1 (the window's factorisation failed), 4, 0.
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hres = io_host<double>(io, s_res), *hred = io_host<double>(io, s_red), *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
@@ -2086,12 +2064,9 @@ class SolverImpl {
       const bool bad = full && lm[w].chol_fail != 0;
       for (size_t b = imu_moff_[(size_t)w]; b < imu_moff_[(size_t)w + 1]; ++b) {
         const size_t i = b - m0, k = (size_t)(imu_slot_[b] - s0);
-        int st = hstat[k];
-        if (bad && (st == IMUG_OK || st == IMUG_WEAK)) st = IMUG_SINGULAR;
+        const int st = gate_scatter(GATE_CODES, hstat[k], bad, 6, hred + k, hcov + 36 * k, hchi + k, red ? red + i : nullptr, cov36 ? cov36 + 36 * i : nullptr,
+                                    chi2 ? chi2 + i : nullptr);
         if (res6) std::memcpy(res6 + 6 * i, hres + 6 * k, sizeof(double) * 6);
-        if (red) red[i] = st == IMUG_OK || st == IMUG_WEAK ? hred[k] : (st == IMUG_NO_INFO ? 0.0 : nan);
-        if (cov36) cov_block(cov36 + 36 * i, hcov + 36 * k, 6, st == IMUG_WEAK ? (int)QUERY_NO_INFO : st);
-        if (chi2) chi2[i] = gate_value(hchi[k], st == IMUG_WEAK ? (int)QUERY_NO_INFO : st);
         if (status) status[i] = st;
       }
     }
@@ -2101,16 +2076,14 @@ class SolverImpl {
   // ctvio_predict_landmarks_batch / ctvio_predict_landmarks (only >= 0: every prediction belongs to that window, win is not read): where
   // landmark lm[i] falls in the camera at the IMU-predicted pose of prediction pred[i], row row[i], beyond the spline, with its 2 x 2
   // covariance and gate.  The predictions are imu_predict()'s queries (grouped by window, stable), the points are grouped by the window of
-  // their prediction, eight to a tile of kind TILE_PRED.  Sequence: staged copy, (cov_factor,) k_cov_nav_jac on the predictions' start times,
-  // k_imu_transition (end state, Phi, N), k_cov_pred_jac (value, status, record), k_cov_solve<COV_PRED>, one copy back.  Its own sequence, as
-  // imu_predict's and for its reason: two record kernels, the transition between them and a fourth timing slot.  dev_, plan_ and the
-  // captured graph are not touched.
+  // their prediction, eight to a tile of kind TILE_PRED.  The launches of its run_query: k_cov_nav_jac on the predictions' start times,
+  // k_imu_transition (end state, Phi, N), k_cov_pred_jac (value, status, record), k_cov_solve<COV_PRED>; a fourth timing slot.
   int predict_landmarks(int only, int64_t np64, const int32_t *win, const int32_t *frame, const int32_t *n_imu, const int64_t *imu_t, const double *imu_gyro,
                         const double *imu_acc, const ctvio_imu_noise *noise, int64_t nq64, const int32_t *pred, const int32_t *lmi, const int32_t *row,
                         const ctvio_row_model *rm, const double *obs2, double *state16, double *proj3, double *cov4, double *chi2, int32_t *row_out,
                         int32_t *status) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
-    if (np64 < 0 || np64 > (int64_t)1 << 30 || nq64 < 0 || nq64 > (int64_t)1 << 30) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (!check_count(np64) || !check_count(nq64)) return fail(CTVIO_ERR_INVALID, "bad arguments");
     if (np64 == 0 || nq64 == 0) return CTVIO_OK;
     if (!n_imu || !imu_t || !imu_gyro || !imu_acc || !noise || (only < 0 && (!win || !pred)) || !lmi || !row || (!proj3 && !cov4 && !chi2 && !state16) ||
         (chi2 && !obs2))
@@ -2121,31 +2094,14 @@ class SolverImpl {
         return fail(CTVIO_ERR_INVALID, "row model: iterations in 1 .. 8, rows >= 1, finite fy and cy");
       prm = ProjRowModel{rm->fy, rm->cy, rm->rows, rm->iterations};
     }
-    {
-      const double sg[4] = {noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
-      for (double x : sg)
-        if (!(x >= 0.0) || !std::isfinite(x)) return fail(CTVIO_ERR_INVALID, "a noise sigma is negative or not finite");
-    }
+    ImuSamples sam;
+    if (!sam.noise(*noise)) return fail(CTVIO_ERR_INVALID, sam.error);
     const int np = (int)np64, nq = (int)nq64;
     const size_t npp = (size_t)np, nn = (size_t)nq;
     const QueryOrder ordp(only, np, win, dev_.nwin);
     if (!ordp.error().empty()) return fail(CTVIO_ERR_INVALID, "prediction: " + ordp.error());
-    std::vector<int64_t> first(npp + 1, 0);   // first sample of every prediction (the caller's order)
-    for (int i = 0; i < np; ++i) {
-      const int w = only >= 0 ? only : win[i];
-      const std::string what = "prediction " + std::to_string(i);
-      if (frame && (frame[i] < 0 || frame[i] >= meta_[w].F)) return fail(CTVIO_ERR_INVALID, what + ": bias state out of range");
-      if (n_imu[i] < 1 || n_imu[i] > 4096) return fail(CTVIO_ERR_INVALID, what + ": 1 to 4096 samples");
-      const int64_t b = first[(size_t)i], e = b + n_imu[i];
-      first[(size_t)i + 1] = e;
-      for (int64_t j = b; j < e; ++j) {
-        if (j > b && imu_t[j] <= imu_t[j - 1]) return fail(CTVIO_ERR_INVALID, what + ": sample times not strictly increasing");
-        for (int c = 0; c < 3; ++c)
-          if (!std::isfinite(imu_gyro[3 * j + c]) || !std::isfinite(imu_acc[3 * j + c])) return fail(CTVIO_ERR_INVALID, what + ": a measurement is not finite");
-      }
-    }
-    const size_t ns = (size_t)first[npp];
-    if (ns > (size_t)1 << 30) return fail(CTVIO_ERR_INVALID, "more than 2^30 samples in one call");
+    if (!sam.streams("prediction", only, np, win, frame, meta_.data(), n_imu, imu_t, imu_gyro, imu_acc)) return fail(CTVIO_ERR_INVALID, sam.error);
+    const std::vector<int64_t> &first = sam.first;   // first sample of every prediction (the caller's order)
     std::vector<int32_t> pwin(nn), rank(npp);   // the window of every point; the sorted position of every prediction
     for (int r = 0; r < np; ++r) rank[(size_t)ordp.slot[(size_t)r]] = r;
     for (int i = 0; i < nq; ++i) {
@@ -2164,9 +2120,9 @@ class SolverImpl {
     // status | the predictions' statuses (out, one copy).  scr: mask, exclusions, point records; start records, start states, Phi | N
     CovScratch cs(want_cov, (size_t)dev_.Utot, sizeof(PredRec), nn);
     CallLayout io = head_, &scr = cs.lay;
-    const int s_q = io.add("queries", sizeof(NavQuery), npp, false), s_pq = io.add("prop", sizeof(PropQuery), npp, false),
-              s_t = io.add("imu_t", sizeof(int64_t), ns, false), s_gyro = io.add("imu_gyro", sizeof(double), 3 * ns, false),
-              s_acc = io.add("imu_acc", sizeof(double), 3 * ns, false), s_pts = io.add("points", sizeof(PredPoint), nn, false),
+    const int s_q = io.add("queries", sizeof(NavQuery), npp, false), s_pq = io.add("prop", sizeof(PropQuery), npp, false);
+    sam.add(io);
+    const int s_pts = io.add("points", sizeof(PredPoint), nn, false),
               s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_state = io.add("state16", sizeof(double), 16 * npp, true),
               s_proj = io.add("proj3", sizeof(double), 3 * nn, true), s_cov = io.add("cov4", sizeof(double), 4 * nc, true),
               s_chi = io.add("chi2", sizeof(double), nc, true), s_row = io.add("row", sizeof(int32_t), nn, false),
@@ -2188,63 +2144,31 @@ class SolverImpl {
       hpt[r] = PredPoint{ordq.win_of(r), rank[pi], lmi[i], row[i], (long long)(first[pi + 1] - 1), {obs2 ? obs2[2 * i] : 0.0, obs2 ? obs2[2 * i + 1] : 0.0}};
     }
     stage_tiles(io, -1, s_tiles, ordq, tiles);
-    std::memcpy(io_host<int64_t>(io, s_t), imu_t, sizeof(int64_t) * ns);
-    std::memcpy(io_host<double>(io, s_gyro), imu_gyro, sizeof(double) * 3 * ns);
-    std::memcpy(io_host<double>(io, s_acc), imu_acc, sizeof(double) * 3 * ns);
+    sam.stage(io, call_io_.host);
     const ImuNoise nz{noise->gyr_n, noise->acc_n, noise->gyr_w, noise->acc_w};
     double *x0 = scr.at<double>(call_scr_.dev, s_x0), *tr = scr.at<double>(call_scr_.dev, s_tr);
     NavRec *nrec = scr.at<NavRec>(call_scr_.dev, s_nrec);
-    const size_t in_bytes = io.off(s_state) - io.off(s_q), out_bytes = io.bytes() - io.off(s_state);
-    auto start_states = [&](const uint8_t *excl) {
-      hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(np, 64)), dim3(64), 0, stream_, dev_, np, io_dev<NavQuery>(io, s_q), excl, nrec, x0, io_dev<int32_t>(io, s_pstat));
-    };
-    auto transition = [&]() {
-      hipLaunchKernelGGL(k_imu_transition, dim3(nblk(np, 4)), dim3(64), 0, stream_, dev_, np, io_dev<PropQuery>(io, s_pq), io_dev<int32_t>(io, s_pstat),
-                         io_dev<long long>(io, s_t), io_dev<double>(io, s_gyro), io_dev<double>(io, s_acc), nz, want_cov ? 1 : 0, (const double *)x0,
-                         io_dev<double>(io, s_state), tr);
-    };
-    auto records = [&](const uint8_t *excl, PredRec *rec) {
-      hipLaunchKernelGGL(k_cov_pred_jac, dim3(nblk(nq, 64)), dim3(64), 0, stream_, dev_, nq, io_dev<PredPoint>(io, s_pts), excl, prm, io_dev<int32_t>(io, s_pstat),
-                         io_dev<double>(io, s_state), io_dev<double>(io, s_gyro), (const NavRec *)nrec, (const double *)tr, rec, io_dev<double>(io, s_proj),
-                         io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
-    };
-    if (!want_cov) {
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
-      start_states(nullptr);
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      transition();
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      records(nullptr, nullptr);
-      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), out_bytes, hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      if (const int rc = span_timing({{2, EV_QUERY_END, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}})) return rc;
-    } else {
-      uint8_t *mask = scr.at<uint8_t>(call_scr_.dev, cs.s_mask), *excl = scr.at<uint8_t>(call_scr_.dev, cs.s_excl);
-      PredRec *drec = scr.at<PredRec>(call_scr_.dev, cs.s_rec);
-      HIPCHK(hipMemcpyAsync(io_dev<char>(io, s_q), io_host<char>(io, s_q), in_bytes, hipMemcpyHostToDevice, stream_));
-      Dev c;
-      if (const int rc = cov_factor(c, mask, excl)) return rc;
-      start_states(excl);
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      transition();
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      records(excl, drec);
-      HIPCHK(hipEventRecord(ev_[EV_COV_GRAM], stream_));
-      CovSolveIO<COV_PRED> a;
-      a.tiles = io_dev<CovTile>(io, s_tiles); a.rec = drec; a.blocks = io_dev<double>(io, s_cov);
-      if (chi2) a.chi2 = io_dev<double>(io, s_chi);
-      launch_cov_solve(c, tiles.size(), a);
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_state), io_dev<char>(io, s_state), out_bytes, hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipMemcpyAsync(io_host<Lm>(io, HEAD_LM), dev_.lm, sizeof(Lm) * dev_.nwin, hipMemcpyDeviceToHost, stream_));
-      if (const int rc = finish_call(io)) return rc;
-      if (const int rc = span_timing({{0, EV_COV_PREPARE, EV_COV_FACTOR}, {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_QUERY_END, EV_COV_GRAM},
-                                      {3, EV_QUERY_BEGIN, EV_QUERY_END}}))
-        return rc;
-    }
+    // the launches: k_cov_nav_jac on the start times (untimed), k_imu_transition (ms[3]), k_cov_pred_jac (ms[2]), with covariances k_cov_solve (ms[1])
+    const int rc = run_query(
+        io, s_q, s_state, want_cov ? &cs : nullptr, {{2, EV_QUERY_END, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}},
+        {span_prepare(), {1, EV_COV_GRAM, EV_CALL_END}, {2, EV_QUERY_END, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}, [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_nav_jac, dim3(nblk(np, 64)), dim3(64), 0, stream_, dev_, np, io_dev<NavQuery>(io, s_q), x.excl, nrec, x0, io_dev<int32_t>(io, s_pstat));
+          x.mark(EV_QUERY_BEGIN);
+          hipLaunchKernelGGL(k_imu_transition, dim3(nblk(np, 4)), dim3(64), 0, stream_, dev_, np, io_dev<PropQuery>(io, s_pq), io_dev<int32_t>(io, s_pstat),
+                             io_dev<long long>(io, sam.s_t), io_dev<double>(io, sam.s_gyro), io_dev<double>(io, sam.s_acc), nz, want_cov ? 1 : 0, (const double *)x0,
+                             io_dev<double>(io, s_state), tr);
+          x.mark(EV_QUERY_END);
+          hipLaunchKernelGGL(k_cov_pred_jac, dim3(nblk(nq, 64)), dim3(64), 0, stream_, dev_, nq, io_dev<PredPoint>(io, s_pts), x.excl, prm, io_dev<int32_t>(io, s_pstat),
+                             io_dev<double>(io, s_state), io_dev<double>(io, sam.s_gyro), (const NavRec *)nrec, (const double *)tr, x.rec<PredRec>(),
+                             io_dev<double>(io, s_proj), io_dev<int32_t>(io, s_row), io_dev<int32_t>(io, s_stat));
+          x.mark(EV_COV_GRAM);
+          if (!x.excl) return;
+          CovSolveIO<COV_PRED> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.rec = x.rec<PredRec>(); a.blocks = io_dev<double>(io, s_cov);
+          if (chi2) a.chi2 = io_dev<double>(io, s_chi);
+          launch_cov_solve(x.c, tiles.size(), a);
+        });
+    if (rc) return rc;
     // ---- results (not computable: NaN; a start time outside the spline: its state NaN)
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hstate = io_host<double>(io, s_state), *hproj = io_host<double>(io, s_proj), *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
@@ -2292,9 +2216,9 @@ class SolverImpl {
     return CTVIO_OK;
   }
   // ctvio_landmark_points_batch / ctvio_landmark_points (single: window `only` alone): the world point of every landmark and its 3 x 3
-  // covariance.  Points only (cov9 null): k_cov_point_jac alone, nothing is linearised or factored.  Otherwise the middle of covariance(),
-  // k_cov_point_jac with the Jacobians (one record per landmark, after k_cov_prepare: it reads 1 / Hll) and k_cov_solve on tiles of kind TILE_POINT,
-  // five landmarks each in the sorted order of the rows of W.  dev_, plan_ and the captured graph are not touched.
+  // covariance.  Points only (cov9 null): k_cov_point_jac alone, nothing is linearised or factored.  Otherwise k_cov_point_jac with the
+  // Jacobians (one record per landmark, after k_cov_prepare: it reads 1 / Hll) and k_cov_solve on tiles of kind TILE_POINT, five landmarks
+  // each in the sorted order of the rows of W (run_query).
   int landmark_points(bool single, int only, double *point3, double *cov9, int32_t *status) {
     if (const int rc = single ? guard(only) : guard()) return rc;
     const int nw = dev_.nwin, wbeg = single ? only : 0, wend = single ? only + 1 : nw;
@@ -2311,27 +2235,21 @@ class SolverImpl {
     const int s_tiles = io.add("tiles", sizeof(CovTile), tiles.size(), false), s_cov = io.add("cov9", sizeof(double), want_cov ? 9 * nn : 0, true),
               s_pt = io.add("point3", sizeof(double), 3 * nn, true), s_stat = io.add("status", sizeof(int32_t), nn, false);
     if (const int rc = reserve_call(io, want_cov ? &scr.lay : nullptr)) return rc;
-    auto jac = [&](const uint8_t *, PointRec *rec) {
-      hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, rec ? 1 : 0, rec, io_dev<double>(io, s_pt), io_dev<int32_t>(io, s_stat));
-    };
-    if (!want_cov) {   // nothing goes in; the kernel's time is reported as the triangulation's is (ms[0])
-      HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], stream_));
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_BEGIN], stream_));
-      jac(nullptr, nullptr);
-      HIPCHK(hipEventRecord(ev_[EV_QUERY_END], stream_));
-      HIPCHK(hipMemcpyAsync(io_host<char>(io, s_pt), io_dev<char>(io, s_pt), io.bytes() - io.off(s_pt), hipMemcpyDeviceToHost, stream_));
-      HIPCHK(hipEventRecord(ev_[EV_CALL_END], stream_));
-      if (const int rc = sync_call()) return rc;
-      if (const int rc = tri_timing()) return rc;
-    } else {
-      std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
-      const int rc = run_query<PointRec>(io, s_tiles, s_cov, &scr, jac, [&](const Dev &c, const PointRec *rec) {
-        CovSolveIO<COV_BASE> a;
-        a.tiles = io_dev<CovTile>(io, s_tiles); a.lrec = rec; a.lm_cov = io_dev<double>(io, s_cov); a.lm_base = l0;
-        launch_cov_solve(c, tiles.size(), a);
-      });
-      if (rc) return rc;
-    }
+    if (want_cov) std::memcpy(io_host<CovTile>(io, s_tiles), tiles.data(), sizeof(CovTile) * tiles.size());
+    // (points only: nothing goes in, and the kernel's time is reported as the triangulation's is, ms[0])
+    const int rc = run_query(
+        io, s_tiles, s_cov, want_cov ? &scr : nullptr,
+        [&](QueryRun &x) {
+          hipLaunchKernelGGL(k_cov_point_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, l0, n, x.excl ? 1 : 0, x.rec<PointRec>(), io_dev<double>(io, s_pt),
+                             io_dev<int32_t>(io, s_stat));
+        },
+        [&](QueryRun &x) {
+          CovSolveIO<COV_BASE> a;
+          a.tiles = io_dev<CovTile>(io, s_tiles); a.lrec = x.rec<PointRec>(); a.lm_cov = io_dev<double>(io, s_cov); a.lm_base = l0;
+          launch_cov_solve(x.c, tiles.size(), a);
+        },
+        0);
+    if (rc) return rc;
     // ---- results (not computable: NaN)
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hcov = io_host<double>(io, s_cov);
@@ -2350,7 +2268,7 @@ class SolverImpl {
                    double *depth_new, int32_t *flag) {
     if (const int rc = guard()) return rc;
     if (!o) return fail(CTVIO_ERR_INVALID, "null options");
-    if (n64 < 0 || n64 > (int64_t)1 << 30 || (n64 && (!win || !lm || !t_new))) return fail(CTVIO_ERR_INVALID, "bad arguments");
+    if (!check_count(n64) || (n64 && (!win || !lm || !t_new))) return fail(CTVIO_ERR_INVALID, "bad arguments");
     if (!row_new && o->row_times) return fail(CTVIO_ERR_INVALID, "row_new may be null only with row_times = 0");
     const int n = (int)n64;
     const size_t nn = (size_t)n;

@@ -558,6 +558,84 @@ inline void cov_block(double *o, const double *computed, int dim, int st) {
 // the caller's gate by status, likewise: no information gates nothing
 inline double gate_value(double computed, int st) { return st == QUERY_OK ? computed : (st == QUERY_NO_INFO ? 0.0 : std::nan("")); }
 
+// The statuses of a leave-one-out gate (ctvio_visual_gate_batch, ctvio_imu_gate_batch): ok, singular and no_info are QUERY_*'s (ctvio.hip
+// asserts it), weak is "redundancy < min_redundancy".
+struct GateCodes { int ok, weak, singular, no_info; };
+// One block or sample of a gate by status, into the caller's entries (null: not asked for; the computed values are read only where one
+// is).  st: what the kernels left; bad: the window's factorisation failed (Lm::chol_fail), which turns ok and weak into singular and lets
+// every other status stand.  The redundancy is the computed one for ok and weak, 0 without information, NaN otherwise; the dim x dim block
+// and the gate are cov_block's and gate_value's with weak counted as no information.  Returns the status to report.
+inline int gate_scatter(const GateCodes &c, int st, bool bad, int dim, const double *computed_red, const double *computed_cov, const double *computed_chi2,
+                        double *red, double *cov, double *chi2) {
+  if (bad && (st == c.ok || st == c.weak)) st = c.singular;
+  const int as = st == c.weak ? c.no_info : st;
+  if (red) *red = st == c.ok || st == c.weak ? *computed_red : (st == c.no_info ? 0.0 : std::nan(""));
+  if (cov) cov_block(cov, computed_cov, dim, as);
+  if (chi2) *chi2 = gate_value(*computed_chi2, as);
+  return st;
+}
+
+// The 2^30 bound every per-call entry puts on a count of queries.
+inline bool check_count(int64_t n64) { return n64 >= 0 && n64 <= (int64_t)1 << 30; }
+// Whether the bias state of query i (frame null: the newest, always there) lies in [0, F) of its window; otherwise err is the complaint,
+// `what` being "query" or "prediction".
+inline bool check_frame(const int32_t *frame, int64_t i, int F, const char *what, std::string &err) {
+  if (!frame || (frame[i] >= 0 && frame[i] < F)) return true;
+  err = std::string(what) + " " + std::to_string(i) + ": bias state out of range";
+  return false;
+}
+
+// The IMU sample streams of ctvio_imu_predict_batch and ctvio_predict_landmarks_batch: query i (the caller's order) owns n_imu[i]
+// consecutive samples of imu_t / imu_gyro / imu_acc.  noise() and streams() validate -- false: `error` says why --, then add() names the
+// three io segments (among the call's inputs) and stage() fills them.
+struct ImuSamples {
+  std::vector<int64_t> first;   // the first sample of every query, and behind them ns, the number of samples
+  size_t ns = 0;
+  int s_t = -1, s_gyro = -1, s_acc = -1;
+  std::string error;
+  bool noise(const ctvio_imu_noise &nz) {
+    for (double x : {nz.gyr_n, nz.acc_n, nz.gyr_w, nz.acc_w})
+      if (!(x >= 0.0) || !std::isfinite(x)) { error = "a noise sigma is negative or not finite"; return false; }
+    return true;
+  }
+  // per query, in this order: the bias state (check_frame against meta[window].F), 1 to 4096 samples, strictly increasing times, finite
+  // measurements; then at most 2^30 samples in the call.  what: "query" or "prediction".
+  bool streams(const char *what, int only, int n, const int32_t *win, const int32_t *frame, const WinMeta *meta, const int32_t *n_imu, const int64_t *imu_t,
+               const double *imu_gyro, const double *imu_acc) {
+    first.assign((size_t)n + 1, 0);
+    t_ = imu_t; gyro_ = imu_gyro; acc_ = imu_acc;
+    for (int i = 0; i < n; ++i) {
+      if (!check_frame(frame, i, meta[only >= 0 ? only : win[i]].F, what, error)) return false;
+      const std::string q = std::string(what) + " " + std::to_string(i);
+      if (n_imu[i] < 1 || n_imu[i] > 4096) { error = q + ": 1 to 4096 samples"; return false; }
+      const int64_t b = first[(size_t)i], e = b + n_imu[i];
+      first[(size_t)i + 1] = e;
+      for (int64_t j = b; j < e; ++j) {
+        if (j > b && imu_t[j] <= imu_t[j - 1]) { error = q + ": sample times not strictly increasing"; return false; }
+        for (int c = 0; c < 3; ++c)
+          if (!std::isfinite(imu_gyro[3 * j + c]) || !std::isfinite(imu_acc[3 * j + c])) { error = q + ": a measurement is not finite"; return false; }
+      }
+    }
+    ns = (size_t)first[(size_t)n];
+    if (ns > (size_t)1 << 30) { error = "more than 2^30 samples in one call"; return false; }
+    return true;
+  }
+  void add(CallLayout &io) {
+    s_t = io.add("imu_t", sizeof(int64_t), ns, false);
+    s_gyro = io.add("imu_gyro", sizeof(double), 3 * ns, false);
+    s_acc = io.add("imu_acc", sizeof(double), 3 * ns, false);
+  }
+  void stage(const CallLayout &io, char *host) const {
+    std::memcpy(io.at<int64_t>(host, s_t), t_, sizeof(int64_t) * ns);
+    std::memcpy(io.at<double>(host, s_gyro), gyro_, sizeof(double) * 3 * ns);
+    std::memcpy(io.at<double>(host, s_acc), acc_, sizeof(double) * 3 * ns);
+  }
+
+ private:
+  const int64_t *t_ = nullptr;
+  const double *gyro_ = nullptr, *acc_ = nullptr;
+};
+
 // ctvio_visual_gate_batch writes one record per block slot (kernels_cov.hpp: GateRec, about 0.9 KB) and a large batch holds 10^6 of them, so
 // the records of a call live in a scratch of bounded size and the windows are walked in slices.  GATE_SLICE_SLOTS: 65536 slots, 57 MB of
 // records -- 8192 tiles of k_cov_solve per slice, four times what the 256 CUs of an MI355X hold at eight workgroups each, so a slice still

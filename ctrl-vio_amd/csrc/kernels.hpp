@@ -65,6 +65,9 @@ __device__ __forceinline__ double readlane_d(double x, int lane) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// the quiet NaN the kernels report for a value that does not exist
+__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
 // the sum of a value over the four 16-lane row groups of the wave, in every lane (the tree of two __shfl_xor steps, without the LDS crossbar)
 __device__ __forceinline__ double rowgroup_sum(double p) {
   unsigned lo = (unsigned)__double2loint(p), hi = (unsigned)__double2hiint(p);

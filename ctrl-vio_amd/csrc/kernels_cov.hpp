@@ -98,44 +98,75 @@ __global__ __launch_bounds__(256) void k_cov_prepare(Dev d, uint8_t *mask, uint8
   }
 }
 
+// ---- what the record kernels (k_cov_*_jac) share
+// The segment of a time t_rel (relative to the window's t0) by the integer-ns rule of k_spline_eval (reference spline_segment.h:83-85):
+// first knot s = t_rel / dt_ns, u = (t_rel % dt_ns) / dt_ns from one remainder and one division, and nk, the knots a value at t_rel depends
+// on: 3 at u = 0 (the last blending weights are multiples of u), else 4.  Outside the spline (t_rel < 0 or s + 3 >= K) s = 0 and u = 0: the
+// loads stay in range and the value is not used.
+struct CovSeg { int s, nk; double u; bool outside; };
+__device__ __forceinline__ CovSeg cov_segment(const WinMeta &m, long long t_rel) {
+  const long long sl = t_rel / m.dt_ns;
+  CovSeg g;
+  g.outside = t_rel < 0 || sl + 3 >= m.K;
+  g.s = g.outside ? 0 : (int)sl;
+  g.u = g.outside ? 0.0 : (double)(t_rel % m.dt_ns) / (double)m.dt_ns;
+  g.nk = g.u > 0.0 ? 4 : 3;
+  return g;
+}
+// Whether one of the knots s .. s + nk - 1, or the bias state `frame`, has an unknown that no factor touches (k_cov_prepare: COV_UNTOUCHED
+// on any of its six unknowns).  Decided on the exclusion flags and on u > 0 (nk), never on a Jacobian entry.  The caller names the status:
+// POSE_UNTOUCHED, IMUG_NO_INFO or PRJ_NO_INFO.  Several tests are joined with |, not ||: every flag is loaded, no load waits for a result.
+__device__ __forceinline__ bool cov_untouched(const uint8_t *excl, const WinMeta &m, int j0, int n) {
+  bool hit = false;
+  for (int j = j0; j < j0 + n; ++j)
+    if (excl[m.u0 + j] == COV_UNTOUCHED) hit = true;
+  return hit;
+}
+__device__ __forceinline__ bool cov_untouched_knots(const uint8_t *excl, const WinMeta &m, int s, int nk) { return cov_untouched(excl, m, 6 * s, 6 * nk); }
+__device__ __forceinline__ bool cov_untouched_bias(const uint8_t *excl, const WinMeta &m, int frame) { return cov_untouched(excl, m, 6 * (m.K + frame), 6); }
+// What the records of the one-sided entries begin with (k_cov_solve reads it under these names): first knot, knots the value depends on
+// (cov_segment), the bias state -- 0 where the entry has none (PoseRec, PointRec).  The two-sided records (RelRec, ProjRec, GateRec,
+// PredRec) have headers of their own.  CTV_REC_LAYOUT: a record is laid out as k_cov_solve reads it -- the header at offset 0, jt where it
+// has always been (offsetof through the base is well defined for these plain structs; the compiler's remark about it is silenced).
+struct CovRecHead { int32_t status, s, nk, frame; };
+__device__ __forceinline__ void cov_rec_head(CovRecHead &r, int status, int s, int nk, int frame) { r.status = status; r.s = s; r.nk = nk; r.frame = frame; }
+#define CTV_REC_LAYOUT(Rec, jt_off, bytes)                                                                                                            \
+  _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winvalid-offsetof\"")                                                         \
+  static_assert(sizeof(CovRecHead) == 16 && sizeof(Rec) == (bytes) && __builtin_offsetof(Rec, status) == 0 && __builtin_offsetof(Rec, frame) == 12 && \
+                __builtin_offsetof(Rec, jt) == (jt_off), #Rec ": the layout k_cov_solve reads");                                                      \
+  _Pragma("clang diagnostic pop") static_assert(true, "")
+
 // One pose query (ctvio_pose_covariance_batch), grouped by window on the host, and what k_cov_pose_jac makes of it.
 enum { POSE_OK = 0, POSE_SINGULAR = 1, POSE_UNTOUCHED = 2, POSE_OUTSIDE = 3 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
 struct PoseQuery {
   int32_t win, pad;
   long long t_rel;   // relative to the window's t0
 };
-struct PoseRec {
-  int32_t status, s, nk, pad;   // first knot; knots the pose depends on: 3 at u = 0 (the last blending weights are u^3 / 6), else 4
-  double jt[144];               // J^T, rows of knots s .. s + 3 (pose_jac_T; written for POSE_OK only)
+struct PoseRec : CovRecHead {
+  double jt[144];   // J^T, rows of knots s .. s + 3 (pose_jac_T; written for POSE_OK only)
 };
+CTV_REC_LAYOUT(PoseRec, 16, 16 + 8 * 144);
 
-// One lane per query: segment and u by the integer-ns rule of k_spline_eval, the status, and J^T at the current state.  A knot the pose
-// depends on that no factor touches (k_cov_prepare: COV_UNTOUCHED on any of its six unknowns) gives POSE_UNTOUCHED: decided on the
-// exclusion flags and on u > 0, never on a Jacobian entry.
+// One lane per query: the segment (cov_segment), the status, and J^T at the current state.  A knot the pose depends on that no factor
+// touches gives POSE_UNTOUCHED (cov_untouched_knots).
 __global__ __launch_bounds__(64) void k_cov_pose_jac(Dev d, int n, const PoseQuery *qs, const uint8_t *excl, SensorExt ext, PoseRec *recs, int32_t *status_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const PoseQuery q = qs[i];
   const WinMeta &m = d.wins[q.win];
-  const long long sl = q.t_rel / m.dt_ns;
-  const bool outside = q.t_rel < 0 || sl + 3 >= m.K;
-  const int s = outside ? 0 : (int)sl;
-  const double u = (double)(q.t_rel % m.dt_ns) / (double)m.dt_ns;
-  const int nk = u > 0.0 ? 4 : 3;
-  int status = outside ? POSE_OUTSIDE : POSE_OK;
-  if (!outside)
-    for (int j = 6 * s; j < 6 * (s + nk); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
+  const CovSeg g = cov_segment(m, q.t_rel);
+  int status = g.outside ? POSE_OUTSIDE : POSE_OK;
+  if (!g.outside && cov_untouched_knots(excl, m, g.s, g.nk)) status = POSE_UNTOUCHED;
   PoseRec &r = recs[i];
-  r.status = status; r.s = s; r.nk = nk; r.pad = 0;
+  cov_rec_head(r, status, g.s, g.nk, 0);
   status_out[i] = status;
   if (status != POSE_OK) return;
   const double zero3[3] = {0, 0, 0};
   Knots4 k;
-  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  load_knots(d.quat, d.pos, m.knot0 + g.s, zero3, k);
   SegConst sc;
   seg_const(k, sc, true);
-  pose_jac_T(k.q, sc, u, ext.on != 0, qmk(ext.q[0], ext.q[1], ext.q[2], ext.q[3]), mk(ext.p[0], ext.p[1], ext.p[2]), r.jt);
+  pose_jac_T(k.q, sc, g.u, ext.on != 0, qmk(ext.q[0], ext.q[1], ext.q[2], ext.q[3]), mk(ext.p[0], ext.p[1], ext.p[2]), r.jt);
 }
 
 // One navigation-state query (ctvio_nav_state_batch), grouped by window on the host, and what k_cov_nav_jac makes of it.  The statuses are
@@ -144,35 +175,32 @@ struct NavQuery {
   int32_t win, frame;   // frame: the bias state, in [0, F) (the host has resolved "the newest")
   long long t_rel;      // relative to the window's t0
 };
-struct NavRec {
-  int32_t status, s, nk, frame;   // first knot; knots the state depends on: 3 at u = 0 (c_3 = u^3 / 6, c'_3 = u^2 / 2), else 4
-  double cv[4];                   // c'_k(u) / dt: the velocity rows against the position unknowns of knots s .. s + 3
-  double jt[144];                 // the pose block of J^T, rows of knots s .. s + 3 (nav_jac_T; with cv written for POSE_OK only)
+struct NavRec : CovRecHead {
+  double cv[4];     // c'_k(u) / dt: the velocity rows against the position unknowns of knots s .. s + 3
+  double jt[144];   // the pose block of J^T, rows of knots s .. s + 3 (nav_jac_T; with cv written for POSE_OK only)
 };
+CTV_REC_LAYOUT(NavRec, 48, 48 + 8 * 144);
 
-// One lane per query: segment and u by the integer-ns rule of k_spline_eval, the state -- position and orientation, world velocity (the
-// device functions of k_spline_eval), the six biases of state `frame` -- into state16 (NaN outside the spline), and with excl (after
-// k_cov_prepare; null: values only, recs is not touched) the status and the record.  A knot the state depends on, or the bias state, with
-// an unknown no factor touches (COV_UNTOUCHED) gives POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.
-// The values are formed before excl is looked at: both calls give them the same bits.
+// One lane per query: the segment (cov_segment), the state -- position and orientation, world velocity (the device functions of
+// k_spline_eval), the six biases of state `frame` -- into state16 (NaN outside the spline), and with excl (after k_cov_prepare; null: values
+// only, recs is not touched) the status and the record.  A knot the state depends on, or the bias state, that no factor touches gives
+// POSE_UNTOUCHED (cov_untouched_knots, cov_untouched_bias).  The values are formed before excl is looked at: both calls give them the same bits.
 __global__ __launch_bounds__(64) void k_cov_nav_jac(Dev d, int n, const NavQuery *qs, const uint8_t *excl, NavRec *recs, double *state16, int32_t *status_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const NavQuery q = qs[i];
   const WinMeta &m = d.wins[q.win];
-  const long long sl = q.t_rel / m.dt_ns;
-  const bool outside = q.t_rel < 0 || sl + 3 >= m.K;
-  const int s = outside ? 0 : (int)sl;
-  const double u = outside ? 0.0 : (double)(q.t_rel % m.dt_ns) / (double)m.dt_ns;
-  const int nk = u > 0.0 ? 4 : 3;
+  const CovSeg g = cov_segment(m, q.t_rel);
+  const double u = g.u;
+  const bool outside = g.outside;
   int status = outside ? POSE_OUTSIDE : POSE_OK;
   const double zero3[3] = {0, 0, 0};
   Knots4 k;
-  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  load_knots(d.quat, d.pos, m.knot0 + g.s, zero3, k);
   SegConst sc;
   seg_const(k, sc, excl != nullptr);
   {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = qnan();
     double c[4], dc[4];
     basis<false, 0>(u, 1.0, c);
     basis<false, 1>(u, m.inv_dt, dc);
@@ -192,14 +220,9 @@ __global__ __launch_bounds__(64) void k_cov_nav_jac(Dev d, int n, const NavQuery
     status_out[i] = status;
     return;
   }
-  if (!outside) {
-    for (int j = 6 * s; j < 6 * (s + nk); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
-    for (int j = 6 * m.K + 6 * q.frame; j < 6 * m.K + 6 * q.frame + 6; ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
-  }
+  if (!outside && (cov_untouched_knots(excl, m, g.s, g.nk) | cov_untouched_bias(excl, m, q.frame))) status = POSE_UNTOUCHED;
   NavRec &r = recs[i];
-  r.status = status; r.s = s; r.nk = nk; r.frame = q.frame;
+  cov_rec_head(r, status, g.s, g.nk, q.frame);
   status_out[i] = status;
   if (status != POSE_OK) return;
   nav_jac_T(k.q, sc, u, m.inv_dt, r.jt, r.cv);
@@ -213,18 +236,17 @@ struct RatesQuery {
   double meas[6];       // the candidate IMU sample of the gate, gyro then accelerometer (zeros without one)
   double sig[6];        // its six standard deviations (the host has resolved noise6 == NULL to 1 / imu_w; ones without a gate)
 };
-struct RatesRec {
-  int32_t status, s, nk, frame;   // first knot; knots the rates depend on: 3 at u = 0, else 4
-  double z[6];                    // the predicted reading (omega + bg_f, f + ba_f), from the bits that go to rates9
-  double meas[6], sig[6];         // the query's
-  double jt[216];                 // J^T over the knots s .. s + 3, 24 x 9 (rates_jac_T; written for POSE_OK only)
+struct RatesRec : CovRecHead {
+  double z[6];              // the predicted reading (omega + bg_f, f + ba_f), from the bits that go to rates9
+  double meas[6], sig[6];   // the query's
+  double jt[216];           // J^T over the knots s .. s + 3, 24 x 9 (rates_jac_T; written for POSE_OK only)
 };
+CTV_REC_LAYOUT(RatesRec, 160, 160 + 8 * 216);
 
-// One lane per query: segment and u by the integer-ns rule of k_spline_eval, the values -- omega (eval_omega), f = R(t)^T (p''(t) + g),
-// v_B = R(t)^T v_W(t) -- into rates9 (NaN outside the spline), and with excl (after k_cov_prepare; null: values only, recs is not touched)
-// the status and the record.  A knot the rates depend on, or the bias state, with an unknown no factor touches (COV_UNTOUCHED) gives
-// POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.  The values are formed before excl is looked at,
-// by code the Jacobians do not share: both calls give them the same bits.
+// One lane per query: the segment (cov_segment), the values -- omega (eval_omega), f = R(t)^T (p''(t) + g), v_B = R(t)^T v_W(t) -- into
+// rates9 (NaN outside the spline), and with excl (after k_cov_prepare; null: values only, recs is not touched) the status and the record.
+// A knot the rates depend on, or the bias state, that no factor touches gives POSE_UNTOUCHED (cov_untouched_knots, cov_untouched_bias).
+// The values are formed before excl is looked at, by code the Jacobians do not share: both calls give them the same bits.
 // (The values are rates_values, shared with k_cov_imugate_jac: segment s and u in, the knots relative to knot s, the segment's constants --
 // with want_jac those the Jacobian needs as well --, gravity and val = (omega, f, v_B) out.)
 __device__ __forceinline__ void rates_values(const Dev &d, const WinMeta &m, int s, double u, bool want_jac, Knots4 &k, SegConst &sc, V3 &grav, double *val) {
@@ -246,21 +268,18 @@ __global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQ
   if (i >= n) return;
   const RatesQuery &q = qs[i];
   const int frame = q.frame;
-  const long long t_rel = q.t_rel;
   const WinMeta &m = d.wins[q.win];
-  const long long sl = t_rel / m.dt_ns;
-  const bool outside = t_rel < 0 || sl + 3 >= m.K;
-  const int s = outside ? 0 : (int)sl;
-  const double u = outside ? 0.0 : (double)(t_rel % m.dt_ns) / (double)m.dt_ns;
-  const int nk = u > 0.0 ? 4 : 3;
+  const CovSeg g = cov_segment(m, q.t_rel);
+  const double u = g.u;
+  const bool outside = g.outside;
   int status = outside ? POSE_OUTSIDE : POSE_OK;
   Knots4 k;
   SegConst sc;
   V3 grav;
   double val[9];
-  rates_values(d, m, s, u, excl != nullptr, k, sc, grav, val);
+  rates_values(d, m, g.s, u, excl != nullptr, k, sc, grav, val);
   {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = qnan();
     double *o = rates9 + 9 * (size_t)i;
 #pragma unroll
     for (int j = 0; j < 9; ++j) o[j] = outside ? nan : val[j];
@@ -269,14 +288,9 @@ __global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQ
     status_out[i] = status;
     return;
   }
-  if (!outside) {
-    for (int j = 6 * s; j < 6 * (s + nk); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
-    for (int j = 6 * m.K + 6 * frame; j < 6 * m.K + 6 * frame + 6; ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
-  }
+  if (!outside && (cov_untouched_knots(excl, m, g.s, g.nk) | cov_untouched_bias(excl, m, frame))) status = POSE_UNTOUCHED;
   RatesRec &r = recs[i];
-  r.status = status; r.s = s; r.nk = nk; r.frame = frame;
+  cov_rec_head(r, status, g.s, g.nk, frame);
   status_out[i] = status;
   if (status != POSE_OK) return;
   const double *bp = d.bias + 6 * (size_t)(m.bias0 + frame);
@@ -289,11 +303,11 @@ __global__ __launch_bounds__(64) void k_cov_rates_jac(Dev d, int n, const RatesQ
 // 4 the epilogue's (redundancy < min_redundancy); 3 cannot occur, the upload refuses IMU times outside the spline.
 enum { IMUG_OK = 0, IMUG_SINGULAR = 1, IMUG_NO_INFO = 2, IMUG_WEAK = 4 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
 constexpr int IMUG_PER_TILE = 2;
-struct ImuGateRec {
-  int32_t status, s, nk, frame;   // first knot; knots the sample depends on: 3 at u = 0, else 4; its bias state
-  double r[6];                    // the whitened residual, the bits that go to res6
-  double jt[144];                 // the omega and f columns of J^T over the knots s .. s + 3, 24 x 6, unweighted (rates_jac_T<.., 6>; IMUG_OK only)
+struct ImuGateRec : CovRecHead {
+  double r[6];      // the whitened residual, the bits that go to res6
+  double jt[144];   // the omega and f columns of J^T over the knots s .. s + 3, 24 x 6, unweighted (rates_jac_T<.., 6>; IMUG_OK only)
 };
+CTV_REC_LAYOUT(ImuGateRec, 64, 64 + 8 * 144);
 // What the gate's kernels write per packed sample slot (absolute slot - slot0; null: not asked for) and the threshold of IMUG_WEAK.
 struct ImuGateOut {
   double *res6, *red, *cov36, *chi2;
@@ -305,8 +319,8 @@ struct ImuGateOut {
 // group, u = imu_u (the host's integer-ns rule, the one k_cov_rates_jac applies to a query time), z = rates_values + bias, and
 // r = imu_w (z - meas), every operation rounded once, so that the residual can be re-derived from ctvio_body_rates' values to the bit.
 // With excl (after k_cov_prepare; null: values only, recs is not touched) the status -- a knot the sample depends on, or its bias state,
-// with an unknown no factor touches gives IMUG_NO_INFO: decided on the exclusion flags and on u > 0 -- and the record.  The values are
-// formed before excl is looked at: both calls give them the same bits.
+// that no factor touches gives IMUG_NO_INFO (cov_untouched_knots, cov_untouched_bias) -- and the record.  The values are formed before
+// excl is looked at: both calls give them the same bits.
 __global__ __launch_bounds__(64) void k_cov_imugate_jac(Dev d, int first, int n, const uint8_t *excl, ImuGateRec *recs, ImuGateOut o) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -330,16 +344,11 @@ __global__ __launch_bounds__(64) void k_cov_imugate_jac(Dev d, int first, int n,
     for (int j = 0; j < 6; ++j) o.res6[6 * ko + j] = r[j];
   }
   int status = IMUG_OK;
-  if (excl) {
-    for (int j = 6 * s; j < 6 * (s + nk); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = IMUG_NO_INFO;
-    for (int j = 6 * m.K + 6 * frame; j < 6 * m.K + 6 * frame + 6; ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = IMUG_NO_INFO;
-  }
+  if (excl && (cov_untouched_knots(excl, m, s, nk) | cov_untouched_bias(excl, m, frame))) status = IMUG_NO_INFO;
   o.status[ko] = status;
   if (!excl) return;
   ImuGateRec &rc = recs[i];
-  rc.status = status; rc.s = s; rc.nk = nk; rc.frame = frame;
+  cov_rec_head(rc, status, s, nk, frame);
 #pragma unroll
   for (int j = 0; j < 6; ++j) rc.r[j] = r[j];
   if (status != IMUG_OK) return;
@@ -368,7 +377,7 @@ __global__ __launch_bounds__(64) void k_cov_imugate_reduce(Dev d, int f_base, in
     }
   }
   stats4[4 * (size_t)i] = (double)c;
-  stats4[4 * (size_t)i + 1] = c ? sum / (double)c : __longlong_as_double(0x7ff8000000000000ll);
+  stats4[4 * (size_t)i + 1] = c ? sum / (double)c : qnan();
   stats4[4 * (size_t)i + 2] = cmax;
   stats4[4 * (size_t)i + 3] = rmin;
 }
@@ -385,14 +394,12 @@ struct RelRec {
                                                // (rel_pose_jac_T; written for POSE_OK only)
 };
 
-// The pose of one time of a relative-pose query: segment and u by the integer-ns rule of k_spline_eval, T_I(t), or T_I(t) T_SI with the
-// extrinsic; with jt the 24 x 6 block of pose_jac_T as well.  Outside the spline the loads stay in range (s = 0) and the value is not used.
+// The pose of one time of a relative-pose query: the segment (cov_segment), T_I(t), or T_I(t) T_SI with the extrinsic; with jt the 24 x 6
+// block of pose_jac_T as well.
 __device__ inline void rel_side(const Dev &d, const WinMeta &m, long long t_rel, const SensorExt &ext, double *jt, int &s, int &nk, bool &outside, Q4 &qo, V3 &po) {
-  const long long sl = t_rel / m.dt_ns;
-  outside = t_rel < 0 || sl + 3 >= m.K;
-  s = outside ? 0 : (int)sl;
-  const double u = outside ? 0.0 : (double)(t_rel % m.dt_ns) / (double)m.dt_ns;
-  nk = u > 0.0 ? 4 : 3;
+  const CovSeg g = cov_segment(m, t_rel);
+  s = g.s; nk = g.nk; outside = g.outside;
+  const double u = g.u;
   const double zero3[3] = {0, 0, 0};
   Knots4 k;
   load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
@@ -412,9 +419,9 @@ __device__ inline void rel_side(const Dev &d, const WinMeta &m, long long t_rel,
 }
 
 // One lane per query: the two poses, the increment (p_ab, q_ab) into rel7 (NaN where either time is outside the spline), and with excl
-// (after k_cov_prepare; null: values only, recs is not touched) the status and the record.  A knot either pose depends on with an unknown
-// no factor touches (COV_UNTOUCHED) gives POSE_UNTOUCHED: decided on the exclusion flags and on u > 0, never on a Jacobian entry.  The
-// values are formed before excl is looked at, by code the Jacobians do not share: both calls give them the same bits.
+// (after k_cov_prepare; null: values only, recs is not touched) the status and the record.  A knot either pose depends on that no factor
+// touches gives POSE_UNTOUCHED (cov_untouched_knots).  The values are formed before excl is looked at, by code the Jacobians do not
+// share: both calls give them the same bits.
 __global__ __launch_bounds__(64) void k_cov_rel_jac(Dev d, int n, const RelQuery *qs, const uint8_t *excl, SensorExt ext, RelRec *recs, double *rel7, int32_t *status_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -430,7 +437,7 @@ __global__ __launch_bounds__(64) void k_cov_rel_jac(Dev d, int n, const RelQuery
   int status = outside ? POSE_OUTSIDE : POSE_OK;
   rel_pose_jac_T(q_a, p_a, q_b, p_b, nullptr, nullptr, q_ab, p_ab);
   if (rel7) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = qnan();
     const double val[7] = {p_ab.x, p_ab.y, p_ab.z, q_ab.x, q_ab.y, q_ab.z, q_ab.w};
 #pragma unroll
     for (int j = 0; j < 7; ++j) rel7[7 * (size_t)i + j] = outside ? nan : val[j];
@@ -439,12 +446,7 @@ __global__ __launch_bounds__(64) void k_cov_rel_jac(Dev d, int n, const RelQuery
     status_out[i] = status;
     return;
   }
-  if (!outside) {
-    for (int j = 6 * s_a; j < 6 * (s_a + nk_a); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
-    for (int j = 6 * s_b; j < 6 * (s_b + nk_b); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = POSE_UNTOUCHED;
-  }
+  if (!outside && (cov_untouched_knots(excl, m, s_a, nk_a) | cov_untouched_knots(excl, m, s_b, nk_b))) status = POSE_UNTOUCHED;
   RelRec &r = recs[i];
   r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_b = s_b; r.nk_b = nk_b; r.pad = 0;
   status_out[i] = status;
@@ -458,11 +460,11 @@ __global__ __launch_bounds__(64) void k_cov_rel_jac(Dev d, int n, const RelQuery
 // batch (lm0 + l, the caller's order).
 enum { LMP_OK = 0, LMP_SINGULAR = 1, LMP_NO_INFO = 2, LMP_NONE = 3 };   // the statuses of ctvio.h (1 is the host's: Lm::chol_fail)
 constexpr int LMP_PER_TILE = 5;
-struct PointRec {
-  int32_t status, s, nk, pad;   // first knot of the anchor time; knots the pose depends on there (3 at u = 0, else 4)
-  double X[3], jrho[3], jld[3]; // the point, dX / drho, dX / d(line delay)
-  double jt[72];                // Jp^T, rows of knots s .. s + 3: jt[3 r + a] = dX_a / d(unknown 6 s + r) (written with the Jacobians, LMP_OK only)
+struct PointRec : CovRecHead {    // (s, nk: of the anchor time)
+  double X[3], jrho[3], jld[3];   // the point, dX / drho, dX / d(line delay)
+  double jt[72];                  // Jp^T, rows of knots s .. s + 3: jt[3 r + a] = dX_a / d(unknown 6 s + r) (written with the Jacobians, LMP_OK only)
 };
+CTV_REC_LAYOUT(PointRec, 88, 88 + 8 * 72);
 
 // One lane per landmark l_begin + i < l_begin + l_count: the anchor observation (t_i, row_i, p_i) its blocks share -- read as k_triangulate
 // reads it --, the camera pose T_I(tau) (q_CI, p_CI) at tau = t_i + row_i * line delay (vis_times), X = R_C (p_i / rho) + p_C.  LMP_NONE
@@ -510,12 +512,12 @@ __global__ __launch_bounds__(64) void k_cov_point_jac(Dev d, int l_begin, int l_
   const Q4 qI = eval_R(k.q, sc, u);
   const M3 RI = q2R(qI), RC = q2R(qmul(qI, q_CI));
   const V3 X = mul(RC, x_c) + (pI + qrot(qI, p_CI));
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = qnan();
   if (point3) { point3[3 * i] = ok ? X.x : nan; point3[3 * i + 1] = ok ? X.y : nan; point3[3 * i + 2] = ok ? X.z : nan; }
   if (status_out) status_out[i] = status;
   if (!want_jac) return;
   PointRec &r = recs[l];
-  r.status = status; r.s = s; r.nk = nk; r.pad = 0;
+  cov_rec_head(r, status, s, nk, 0);
   r.X[0] = X.x; r.X[1] = X.y; r.X[2] = X.z;
   if (status != LMP_OK) return;
   const V3 jr = (-z * z) * mul(RC, mk(px, py, 1.0));
@@ -557,13 +559,14 @@ struct ProjRec {
                                                 // (j, jld, jt_a, jt_q: written for PRJ_OK only)
 };
 
-// The body pose at tau (inside the spline), the body rate and world velocity there, and the 24 x 6 block of pose_jac_T for the camera pose.
+// The body pose at tau (inside the spline, as the caller has established: of cov_segment only s and u are used), the body rate and world
+// velocity there, and the 24 x 6 block of pose_jac_T for the camera pose.
 __device__ inline void proj_side(const Dev &d, const WinMeta &m, long long tau, Q4 q_CI, V3 p_CI, double *jp, Q4 &q_I, V3 &om, V3 &v) {
-  const int s = (int)(tau / m.dt_ns);
-  const double u = (double)(tau % m.dt_ns) / (double)m.dt_ns;
+  const CovSeg g = cov_segment(m, tau);
+  const double u = g.u;
   const double zero3[3] = {0, 0, 0};
   Knots4 k;
-  load_knots(d.quat, d.pos, m.knot0 + s, zero3, k);
+  load_knots(d.quat, d.pos, m.knot0 + g.s, zero3, k);
   SegConst sc;
   seg_const(k, sc, true);
   q_I = eval_R(k.q, sc, u);
@@ -583,8 +586,8 @@ __device__ inline void proj_side(const Dev &d, const WinMeta &m, long long tau, 
 // not finite; the iteration stops there, the loads stay in range (rel_side: s = 0 outside the spline), proj3 is NaN and row_out -1.  The value
 // is formed before excl is looked at, by code the Jacobians do not share: the values-only call (excl null; recs is not touched) gives it the
 // same bits.  With excl (after k_cov_prepare) the status and the record: PRJ_NO_INFO where 1 / Hll == 0 (d.dinv) or a knot either time
-// depends on has an unknown no factor touches (COV_UNTOUCHED; decided on the exclusion flags and on u > 0, never on a Jacobian entry).  The
-// anchor block is formed in the 144-double pose buffer and stored, then the buffer is reused for the query block.
+// depends on is one no factor touches (cov_untouched_knots).  The anchor block is formed in the 144-double pose buffer and stored, then
+// the buffer is reused for the query block.
 // (The lane's work is proj_query, shared with k_cov_gate_jac: out3 = the query's proj3, the return value its status; r is written with excl only.)
 __device__ __forceinline__ int proj_query(const Dev &d, const ProjQuery &q, const uint8_t *excl, const ProjRowModel &rm, ProjRec *rp, double *out3, int &row_o) {
   const int w = q.win;
@@ -626,7 +629,7 @@ __device__ __forceinline__ int proj_query(const Dev &d, const ProjQuery &q, cons
     if (it >= rm.iterations || !ok) break;
     row = (int)fmin(fmax(rint(rm.fy * y.y / y.z + rm.cy), 0.0), (double)(rm.rows - 1));
   }
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = qnan();
   const double zx = y.x / y.z, zy = y.y / y.z;
   out3[0] = ok ? zx : nan; out3[1] = ok ? zy : nan; out3[2] = ok ? y.z : nan;
   row_o = ok ? row : -1;
@@ -634,11 +637,7 @@ __device__ __forceinline__ int proj_query(const Dev &d, const ProjQuery &q, cons
   if (!excl) return status;
   const int wrow = d.lm_pos[l];
   if (ok) {
-    if (d.dinv[m.lm0 + wrow] == 0.0) status = PRJ_NO_INFO;
-    for (int j = 6 * s_a; j < 6 * (s_a + nk_a); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
-    for (int j = 6 * s_q; j < 6 * (s_q + nk_q); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
+    if ((d.dinv[m.lm0 + wrow] == 0.0) | cov_untouched_knots(excl, m, s_a, nk_a) | cov_untouched_knots(excl, m, s_q, nk_q)) status = PRJ_NO_INFO;
   }
   ProjRec &r = *rp;
   r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_q = s_q; r.nk_q = nk_q; r.wrow = wrow;
@@ -752,7 +751,7 @@ __global__ __launch_bounds__(64) void k_cov_gate_reduce(Dev d, int lm_base, int 
   }
   count[i] = c;
   if (stats3) {
-    stats3[3 * (size_t)i] = c ? sum / (double)c : __longlong_as_double(0x7ff8000000000000ll);
+    stats3[3 * (size_t)i] = c ? sum / (double)c : qnan();
     stats3[3 * (size_t)i + 1] = cmax;
     stats3[3 * (size_t)i + 2] = rmin;
   }
@@ -784,8 +783,8 @@ struct PredRec {
 // y = R_C^T (X - p_C); with a row model the row is iterated first, exactly as there.  PRJ_NONE: the start time is outside the spline, the
 // landmark is not computable, or y.z <= 0 or y is not finite at any row visited: proj3 NaN, row_out -1.  The value is formed before excl is
 // looked at, by code the Jacobians do not share: the values-only call (excl null; recs, nrec, trans are not touched) gives it the same bits.
-// With excl (after k_cov_prepare): PRJ_NO_INFO where 1 / Hll == 0, an anchor knot has an unknown no factor touches, or the start state's
-// record says so (POSE_UNTOUCHED: its knots, knot s + 3 only where u > 0, and the bias state); otherwise the record: the anchor block and the
+// With excl (after k_cov_prepare): PRJ_NO_INFO where 1 / Hll == 0, an anchor knot is one no factor touches (cov_untouched_knots), or the
+// start state's record says so (POSE_UNTOUCHED: its knots, knot s + 3 only where u > 0, and the bias state); otherwise the record: the anchor block and the
 // columns j, jld as k_cov_proj_jac forms them (the read-out term of jld with omega = w_e, v = the end velocity, R_I(tau)), A (pred_A),
 // M = A Phi, the start block M[:, 0:9] J_nav^T from the NavRec (pose rows jt, velocity rows cv), the bias rows M[:, 9:15] and A N A^T.
 __global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoint *qs, const uint8_t *excl, ProjRowModel rm, const int32_t *pstat, const double *xe,
@@ -842,7 +841,7 @@ __global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoi
     if (it >= rm.iterations || !ok) break;
     row = (int)fmin(fmax(rint(rm.fy * y.y / y.z + rm.cy), 0.0), (double)(rm.rows - 1));
   }
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double nan = qnan();
   const double zx = y.x / y.z, zy = y.y / y.z;
   proj3[3 * (size_t)i] = ok ? zx : nan; proj3[3 * (size_t)i + 1] = ok ? zy : nan; proj3[3 * (size_t)i + 2] = ok ? y.z : nan;
   row_out[i] = ok ? row : -1;
@@ -854,10 +853,7 @@ __global__ __launch_bounds__(64) void k_cov_pred_jac(Dev d, int n, const PredPoi
   const int wrow = d.lm_pos[l];
   const NavRec &nr = nrec[q.pred];
   if (ok) {
-    if (d.dinv[m.lm0 + wrow] == 0.0) status = PRJ_NO_INFO;
-    for (int j = 6 * s_a; j < 6 * (s_a + nk_a); ++j)
-      if (excl[m.u0 + j] == COV_UNTOUCHED) status = PRJ_NO_INFO;
-    if (nr.status != POSE_OK) status = PRJ_NO_INFO;
+    if ((d.dinv[m.lm0 + wrow] == 0.0) | cov_untouched_knots(excl, m, s_a, nk_a) | (nr.status != POSE_OK)) status = PRJ_NO_INFO;
   }
   PredRec &r = recs[i];
   r.status = status; r.s_a = s_a; r.nk_a = nk_a; r.s_q = ok ? nr.s : 0; r.nk_q = ok ? nr.nk : 3; r.wrow = wrow; r.frame = ok ? nr.frame : 0; r.pad = 0;

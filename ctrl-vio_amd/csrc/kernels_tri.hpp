@@ -174,7 +174,7 @@ __global__ void k_shift_anchor(Dev d, int n, const int32_t *win, const int32_t *
     for (int j = 1; j < cnt; ++j) ok = ok && d.v_anc[first + j] == a0;
   }
   int fl = TRI_NONE;
-  double dep = __longlong_as_double(0x7ff8000000000000ll);
+  double dep = qnan();
   if (ok) {
     const bool row_times = o.row_times != 0;
     const double ld = d.ld[w];
