@@ -15,6 +15,47 @@ from . import capi
 from .window import Window
 
 
+def _arr(a, dtype, cols=None):
+    """None stays None; anything else becomes a contiguous array of dtype, flat or with `cols` columns."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype)
+    return a.reshape(-1) if cols is None else a.reshape(-1, cols)
+
+
+_ptr = capi._p   # None (and an empty array) -> NULL
+
+
+def _out(n, *shape, dtype=float, want=True):
+    """The output array of n records, never empty (the entries take no NULL for a required output); want=False: None."""
+    return np.zeros((max(n, 1),) + shape, dtype) if want else None
+
+
+def _cut(a, n):
+    return a[:n].copy() if a is not None else None
+
+
+def _row_model(rm):
+    """(fy, cy, rows, iterations) or capi.RowModel or None -> the pointer argument."""
+    if rm is None:
+        return None
+    return C.byref(rm if isinstance(rm, capi.RowModel) else capi.RowModel(float(rm[0]), float(rm[1]), int(rm[2]), int(rm[3])))
+
+
+def _gate_options(lib, min_redundancy):
+    o = capi.GateOptions()
+    lib.ctvio_default_gate_options(C.byref(o))
+    if min_redundancy is not None:
+        o.min_redundancy = float(min_redundancy)
+    return o
+
+
+def _imu_samples(imu_t, gyro, acc):
+    t, g, a = _arr(imu_t, np.int64), _arr(gyro, np.float64, 3), _arr(acc, np.float64, 3)
+    assert g.shape[0] == t.shape[0] and a.shape[0] == t.shape[0]
+    return t, g, a
+
+
 class Solver:
     """One handle = one HIP stream + the HBM buffers of a batch of windows."""
 
@@ -243,14 +284,14 @@ class Solver:
         (trajectory unknowns in [0, P), at most 64, may be empty).  Returns (list of n x n arrays in the order of each selection,
         list of per-landmark inverse-depth variances or None, singular flags (n windows))."""
         assert len(sels) == len(self.windows)
-        sels = [np.ascontiguousarray(s, np.int32).reshape(-1) for s in sels]
+        sels = [_arr(s, np.int32) for s in sels]
         ns = np.array([s.shape[0] for s in sels], np.int32)
-        sel = np.ascontiguousarray(np.concatenate(sels) if len(sels) else np.zeros(0, np.int32), np.int32)
-        cov = np.zeros(max(int((ns.astype(np.int64) ** 2).sum()), 1))
+        sel = _arr(np.concatenate(sels) if len(sels) else np.zeros(0, np.int32), np.int32)
+        cov = _out(int((ns.astype(np.int64) ** 2).sum()))
         Ls = [w.L for w in self.windows]
-        var = np.zeros(max(sum(Ls), 1)) if rho else None
+        var = _out(sum(Ls), want=rho)
         sing = np.zeros(len(sels), np.int32)
-        capi.check(self._lib.ctvio_covariance_batch(self._h, capi._p(ns), capi._p(sel), capi._p(cov), capi._p(var) if rho else None, capi._p(sing)))
+        capi.check(self._lib.ctvio_covariance_batch(self._h, _ptr(ns), _ptr(sel), _ptr(cov), _ptr(var), _ptr(sing)))
         covs, vars_, oc, ov = [], [], 0, 0
         for n, L in zip(ns, Ls):
             n = int(n)
@@ -262,11 +303,11 @@ class Solver:
     def covariance(self, wid: int, sel, rho: bool = False):
         """ctvio_covariance: the same for window wid alone (same bits as the batch entry).  Returns (n x n array, inverse-depth
         variances (L,) or None, singular flag)."""
-        sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+        sel = _arr(sel, np.int32)
         n, L = int(sel.shape[0]), self.windows[wid].L
-        cov = np.zeros(max(n * n, 1)); var = np.zeros(max(L, 1)) if rho else None; sing = np.zeros(1, np.int32)
-        capi.check(self._lib.ctvio_covariance(self._h, int(wid), n, capi._p(sel), capi._p(cov), capi._p(var) if rho else None, capi._p(sing)))
-        return cov[:n * n].reshape(n, n).copy(), (var[:L].copy() if rho else None), int(sing[0])
+        cov = _out(n * n); var = _out(L, want=rho); sing = np.zeros(1, np.int32)
+        capi.check(self._lib.ctvio_covariance(self._h, int(wid), n, _ptr(sel), _ptr(cov), _ptr(var), _ptr(sing)))
+        return cov[:n * n].reshape(n, n).copy(), _cut(var, L), int(sing[0])
 
     @staticmethod
     def _extrinsic(q_SI, p_SI):
@@ -280,27 +321,27 @@ class Solver:
         """ctvio_pose_covariance_batch: the 6 x 6 covariance of the pose at absolute time t_ns[i] of window win[i], at the current state, in the
         tangent (theta, p) of R(t) <- R(t) exp(dtheta), p(t) <- p(t) + dp.  q_SI = (x,y,z,w), p_SI: a sensor extrinsic (None: the body pose).
         Returns (cov (n, 6, 6), status (n,)): 0 ok, 1 singular window (NaN), 2 an untouched knot (+inf diagonal), 3 time outside the spline (NaN)."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1); t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        wi = _arr(win, np.int32); t = _arr(t_ns, np.int64)
         n = int(t.shape[0])
         assert wi.shape[0] == n
         q, p = self._extrinsic(q_SI, p_SI)
-        cov = np.zeros((max(n, 1), 6, 6)); st = np.zeros(max(n, 1), np.int32)
-        capi.check(self._lib.ctvio_pose_covariance_batch(self._h, C.c_int64(n), capi._p(wi), capi._p(t), capi._p(q), capi._p(p), capi._p(cov), capi._p(st)))
-        return cov[:n].copy(), st[:n].copy()
+        cov = _out(n, 6, 6); st = _out(n, dtype=np.int32)
+        capi.check(self._lib.ctvio_pose_covariance_batch(self._h, C.c_int64(n), _ptr(wi), _ptr(t), _ptr(q), _ptr(p), _ptr(cov), _ptr(st)))
+        return _cut(cov, n), _cut(st, n)
 
     def pose_covariance(self, wid: int, t_ns, q_SI=None, p_SI=None):
         """ctvio_pose_covariance: the same for the times t_ns of window wid alone (same bits as the batch entry)."""
-        t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        t = _arr(t_ns, np.int64)
         n = int(t.shape[0])
         q, p = self._extrinsic(q_SI, p_SI)
-        cov = np.zeros((max(n, 1), 6, 6)); st = np.zeros(max(n, 1), np.int32)
-        capi.check(self._lib.ctvio_pose_covariance(self._h, int(wid), n, capi._p(t), capi._p(q), capi._p(p), capi._p(cov), capi._p(st)))
-        return cov[:n].copy(), st[:n].copy()
+        cov = _out(n, 6, 6); st = _out(n, dtype=np.int32)
+        capi.check(self._lib.ctvio_pose_covariance(self._h, int(wid), n, _ptr(t), _ptr(q), _ptr(p), _ptr(cov), _ptr(st)))
+        return _cut(cov, n), _cut(st, n)
 
     def _landmark_points(self, call, L, cov):
-        pts = np.zeros((max(L, 1), 3)); c9 = np.zeros((max(L, 1), 3, 3)) if cov else None; st = np.zeros(max(L, 1), np.int32)
-        capi.check(call(capi._p(pts), capi._p(c9) if cov else None, capi._p(st)))
-        return pts[:L].copy(), (c9[:L].copy() if cov else None), st[:L].copy()
+        pts = _out(L, 3); c9 = _out(L, 3, 3, want=cov); st = _out(L, dtype=np.int32)
+        capi.check(call(_ptr(pts), _ptr(c9), _ptr(st)))
+        return _cut(pts, L), _cut(c9, L), _cut(st, L)
 
     def landmark_points_batch(self, cov: bool = True):
         """ctvio_landmark_points_batch: the world point X = R_C (p_i / rho) + p_C of every landmark of the batch at the current state (camera
@@ -317,13 +358,12 @@ class Solver:
         return self._landmark_points(lambda p, c, s: self._lib.ctvio_landmark_points(self._h, int(wid), p, c, s), self.windows[int(wid)].L, cov)
 
     def _nav_state(self, call, t_ns, frame, cov, n_win=None):
-        t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        t = _arr(t_ns, np.int64); fr = _arr(frame, np.int32)
         n = int(t.shape[0])
-        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
         assert (fr is None or fr.shape[0] == n) and (n_win is None or n_win == n)
-        state = np.zeros((max(n, 1), 16)); c = np.zeros((max(n, 1), 15, 15)) if cov else None; st = np.zeros(max(n, 1), np.int32)
-        capi.check(call(n, capi._p(t), capi._p(fr), capi._p(state), capi._p(c) if cov else None, capi._p(st)))
-        return state[:n].copy(), (c[:n].copy() if cov else None), st[:n].copy()
+        state = _out(n, 16); c = _out(n, 15, 15, want=cov); st = _out(n, dtype=np.int32)
+        capi.check(call(n, _ptr(t), _ptr(fr), _ptr(state), _ptr(c), _ptr(st)))
+        return _cut(state, n), _cut(c, n), _cut(st, n)
 
     def nav_state_batch(self, win, t_ns, frame=None, cov: bool = True):
         """ctvio_nav_state_batch: the navigation state (px, py, pz, qx, qy, qz, qw, world velocity, bg, ba of bias state frame[i]; frame None:
@@ -331,8 +371,8 @@ class Solver:
         (dtheta, dp, dv, dbg, dba) of R(t) <- R(t) exp(dtheta), the rest additive.  Returns (state (n, 16), cov (n, 15, 15) or None, status
         (n,)): 0 ok, 1 singular window (cov NaN), 2 an untouched knot or bias state (+inf diagonal), 3 time outside the spline (NaN).
         cov=False: one kernel, nothing is linearised."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
-        return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state_batch(self._h, C.c_int64(n), capi._p(wi), t, f, s, c, st), t_ns,
+        wi = _arr(win, np.int32)
+        return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state_batch(self._h, C.c_int64(n), _ptr(wi), t, f, s, c, st), t_ns,
                                frame, cov, int(wi.shape[0]))
 
     def nav_state(self, wid: int, t_ns, frame=None, cov: bool = True):
@@ -340,20 +380,15 @@ class Solver:
         return self._nav_state(lambda n, t, f, s, c, st: self._lib.ctvio_nav_state(self._h, int(wid), n, t, f, s, c, st), t_ns, frame, cov)
 
     def _body_rates(self, call, t_ns, frame, meas, noise, cov, n_win=None):
-        t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
+        t = _arr(t_ns, np.int64); fr = _arr(frame, np.int32); z = _arr(meas, np.float64, 6)
         n = int(t.shape[0])
-        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
-        z = None if meas is None else np.ascontiguousarray(meas, np.float64).reshape(-1, 6)
-        sg = None if noise is None else np.ascontiguousarray(noise, np.float64).reshape(6)
+        sg = None if noise is None else _arr(noise, np.float64).reshape(6)
         assert (fr is None or fr.shape[0] == n) and (z is None or z.shape[0] == n) and (n_win is None or n_win == n)
         if z is not None and not cov:
             raise ValueError("meas needs cov=True: the gate is formed from the covariance")
-        m = max(n, 1)
-        rates = np.zeros((m, 9)); c = np.zeros((m, 15, 15)) if cov else None; chi = np.zeros(m) if z is not None else None
-        st = np.zeros(m, np.int32)
-        capi.check(call(n, capi._p(t), capi._p(fr), capi._p(z), capi._p(sg), capi._p(rates), capi._p(c) if cov else None,
-                        capi._p(chi) if chi is not None else None, capi._p(st)))
-        return rates[:n].copy(), (c[:n].copy() if cov else None), (chi[:n].copy() if chi is not None else None), st[:n].copy()
+        rates = _out(n, 9); c = _out(n, 15, 15, want=cov); chi = _out(n, want=z is not None); st = _out(n, dtype=np.int32)
+        capi.check(call(n, _ptr(t), _ptr(fr), _ptr(z), _ptr(sg), _ptr(rates), _ptr(c), _ptr(chi), _ptr(st)))
+        return _cut(rates, n), _cut(c, n), _cut(chi, n), _cut(st, n)
 
     def body_rates_batch(self, win, t_ns, frame=None, cov: bool = True, meas=None, noise=None):
         """ctvio_body_rates_batch: the body angular velocity, the specific force f = R(t)^T (p''(t) + g) and the body-frame velocity
@@ -363,8 +398,8 @@ class Solver:
         standard deviations (None: 1 / imu_w of the window).  Returns (rates (n, 9), cov (n, 15, 15) or None, chi2 (n,) or None, status
         (n,)): 0 ok, 1 singular window (cov, chi2 NaN), 2 an untouched knot or bias state (+inf diagonal, chi2 0), 3 time outside the spline
         (NaN).  cov=False: one kernel, nothing is linearised."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
-        return self._body_rates(lambda n, *a: self._lib.ctvio_body_rates_batch(self._h, C.c_int64(n), capi._p(wi), *a), t_ns, frame, meas, noise,
+        wi = _arr(win, np.int32)
+        return self._body_rates(lambda n, *a: self._lib.ctvio_body_rates_batch(self._h, C.c_int64(n), _ptr(wi), *a), t_ns, frame, meas, noise,
                                 cov, int(wi.shape[0]))
 
     def body_rates(self, wid: int, t_ns, frame=None, cov: bool = True, meas=None, noise=None):
@@ -372,13 +407,13 @@ class Solver:
         return self._body_rates(lambda n, *a: self._lib.ctvio_body_rates(self._h, int(wid), n, *a), t_ns, frame, meas, noise, cov)
 
     def _relative_pose(self, call, t_a, t_b, q_SI, p_SI, cov, n_win=None):
-        ta = np.ascontiguousarray(t_a, np.int64).reshape(-1); tb = np.ascontiguousarray(t_b, np.int64).reshape(-1)
+        ta = _arr(t_a, np.int64); tb = _arr(t_b, np.int64)
         n = int(ta.shape[0])
         assert tb.shape[0] == n and (n_win is None or n_win == n)
         q, p = self._extrinsic(q_SI, p_SI)
-        rel = np.zeros((max(n, 1), 7)); c = np.zeros((max(n, 1), 6, 6)) if cov else None; st = np.zeros(max(n, 1), np.int32)
-        capi.check(call(n, capi._p(ta), capi._p(tb), capi._p(q), capi._p(p), capi._p(rel), capi._p(c) if cov else None, capi._p(st)))
-        return rel[:n].copy(), (c[:n].copy() if cov else None), st[:n].copy()
+        rel = _out(n, 7); c = _out(n, 6, 6, want=cov); st = _out(n, dtype=np.int32)
+        capi.check(call(n, _ptr(ta), _ptr(tb), _ptr(q), _ptr(p), _ptr(rel), _ptr(c), _ptr(st)))
+        return _cut(rel, n), _cut(c, n), _cut(st, n)
 
     def relative_pose_batch(self, win, t_a, t_b, q_SI=None, p_SI=None, cov: bool = True):
         """ctvio_relative_pose_batch: the pose increment T(t_a[i])^-1 T(t_b[i]) of window win[i] at the current state, as (p_ab, q_ab as
@@ -386,8 +421,8 @@ class Solver:
         a).  q_SI = (x,y,z,w), p_SI: a sensor extrinsic (None: body poses).  Returns (rel7 (n, 7), cov (n, 6, 6) or None, status (n,)): 0 ok,
         1 singular window (cov NaN), 2 an untouched knot (+inf diagonal), 3 a time outside the spline (NaN).  cov=False: one kernel, nothing
         is linearised."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
-        return self._relative_pose(lambda n, ta, tb, q, p, r, c, st: self._lib.ctvio_relative_pose_batch(self._h, C.c_int64(n), capi._p(wi), ta, tb, q, p, r, c, st),
+        wi = _arr(win, np.int32)
+        return self._relative_pose(lambda n, ta, tb, q, p, r, c, st: self._lib.ctvio_relative_pose_batch(self._h, C.c_int64(n), _ptr(wi), ta, tb, q, p, r, c, st),
                                    t_a, t_b, q_SI, p_SI, cov, int(wi.shape[0]))
 
     def relative_pose(self, wid: int, t_a, t_b, q_SI=None, p_SI=None, cov: bool = True):
@@ -396,23 +431,15 @@ class Solver:
                                    t_a, t_b, q_SI, p_SI, cov)
 
     def _project_landmarks(self, call, lm, t_ns, row, row_model, obs, cov, n_win=None):
-        li = np.ascontiguousarray(lm, np.int32).reshape(-1); t = np.ascontiguousarray(t_ns, np.int64).reshape(-1)
-        r = np.ascontiguousarray(row, np.int32).reshape(-1)
+        li = _arr(lm, np.int32); t = _arr(t_ns, np.int64); r = _arr(row, np.int32); o = _arr(obs, np.float64, 2)
         n = int(li.shape[0])
-        o = None if obs is None else np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
         assert t.shape[0] == n and r.shape[0] == n and (o is None or o.shape[0] == n) and (n_win is None or n_win == n)
         if o is not None and not cov:
             raise ValueError("obs needs cov=True: the gate is formed from the covariance")
-        rm = None
-        if row_model is not None:
-            rm = row_model if isinstance(row_model, capi.RowModel) else capi.RowModel(float(row_model[0]), float(row_model[1]), int(row_model[2]), int(row_model[3]))
-        m = max(n, 1)
-        proj = np.zeros((m, 3)); c = np.zeros((m, 2, 2)) if cov else None; chi = np.zeros(m) if o is not None else None
-        ro = np.zeros(m, np.int32); st = np.zeros(m, np.int32)
-        capi.check(call(n, capi._p(li), capi._p(t), capi._p(r), C.byref(rm) if rm is not None else None, capi._p(o) if o is not None else None,
-                        capi._p(proj), capi._p(c) if cov else None, capi._p(chi) if chi is not None else None, capi._p(ro), capi._p(st)))
-        return SimpleNamespace(proj=proj[:n].copy(), cov=c[:n].copy() if cov else None, chi2=chi[:n].copy() if chi is not None else None,
-                               row=ro[:n].copy(), status=st[:n].copy())
+        proj = _out(n, 3); c = _out(n, 2, 2, want=cov); chi = _out(n, want=o is not None)
+        ro = _out(n, dtype=np.int32); st = _out(n, dtype=np.int32)
+        capi.check(call(n, _ptr(li), _ptr(t), _ptr(r), _row_model(row_model), _ptr(o), _ptr(proj), _ptr(c), _ptr(chi), _ptr(ro), _ptr(st)))
+        return SimpleNamespace(proj=_cut(proj, n), cov=_cut(c, n), chi2=_cut(chi, n), row=_cut(ro, n), status=_cut(st, n))
 
     def project_landmarks_batch(self, win, lm, t_ns, row, cov: bool = True, obs=None, row_model=None):
         """ctvio_project_landmarks_batch: where landmark lm[i] of window win[i] falls in the camera at frame time t_ns[i], image row row[i], at the
@@ -421,8 +448,8 @@ class Solver:
         row_model = (fy, cy, rows, iterations) or capi.RowModel: row[i] is the first guess of a pinhole row iteration, the final row comes
         back in .row.  Returns a namespace (proj, cov or None, chi2 or None, row, status): 0 ok, 1 singular window (cov, chi2 NaN), 2 no
         information (+inf diagonal, chi2 0), 3 not computable (NaN, row -1).  cov=False: one kernel, nothing is linearised."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
-        return self._project_landmarks(lambda n, *a: self._lib.ctvio_project_landmarks_batch(self._h, C.c_int64(n), capi._p(wi), *a),
+        wi = _arr(win, np.int32)
+        return self._project_landmarks(lambda n, *a: self._lib.ctvio_project_landmarks_batch(self._h, C.c_int64(n), _ptr(wi), *a),
                                        lm, t_ns, row, row_model, obs, cov, int(wi.shape[0]))
 
     def project_landmarks(self, wid: int, lm, t_ns, row, cov: bool = True, obs=None, row_model=None):
@@ -430,20 +457,13 @@ class Solver:
         return self._project_landmarks(lambda n, *a: self._lib.ctvio_project_landmarks(self._h, int(wid), n, *a), lm, t_ns, row, row_model, obs, cov)
 
     def _visual_gate(self, call, wids, cov, min_redundancy):
-        o = capi.GateOptions()
-        self._lib.ctvio_default_gate_options(C.byref(o))
-        if min_redundancy is not None:
-            o.min_redundancy = float(min_redundancy)
+        o = _gate_options(self._lib, min_redundancy)
         V = sum(int(self.windows[w].V) for w in wids); L = sum(int(self.windows[w].L) for w in wids)
-        m, ml = max(V, 1), max(L, 1)
-        res = np.zeros((m, 2)); wgt = np.zeros(m); dep = np.zeros(m); st = np.zeros(m, np.int32); cnt = np.zeros(ml, np.int32)
-        red = np.zeros(m) if cov else None; c = np.zeros((m, 2, 2)) if cov else None; chi = np.zeros(m) if cov else None
-        lms = np.zeros((ml, 3)) if cov else None
-        opt = lambda a: capi._p(a) if a is not None else None
-        capi.check(call(C.byref(o), capi._p(res), capi._p(wgt), capi._p(dep), opt(red), opt(c), opt(chi), capi._p(st), opt(lms), capi._p(cnt)))
-        cut = lambda a, n: a[:n].copy() if a is not None else None
-        return SimpleNamespace(res=cut(res, V), weight=cut(wgt, V), depth=cut(dep, V), redundancy=cut(red, V), cov=cut(c, V), chi2=cut(chi, V),
-                               status=cut(st, V), lm_stats=cut(lms, L), lm_count=cut(cnt, L))
+        res = _out(V, 2); wgt = _out(V); dep = _out(V); st = _out(V, dtype=np.int32); cnt = _out(L, dtype=np.int32)
+        red = _out(V, want=cov); c = _out(V, 2, 2, want=cov); chi = _out(V, want=cov); lms = _out(L, 3, want=cov)
+        capi.check(call(C.byref(o), _ptr(res), _ptr(wgt), _ptr(dep), _ptr(red), _ptr(c), _ptr(chi), _ptr(st), _ptr(lms), _ptr(cnt)))
+        return SimpleNamespace(res=_cut(res, V), weight=_cut(wgt, V), depth=_cut(dep, V), redundancy=_cut(red, V), cov=_cut(c, V), chi2=_cut(chi, V),
+                               status=_cut(st, V), lm_stats=_cut(lms, L), lm_count=_cut(cnt, L))
 
     def visual_gate_batch(self, cov: bool = True, min_redundancy=None):
         """ctvio_visual_gate_batch: the leave-one-out test of every visual block of the uploaded windows at the current state, window after
@@ -459,19 +479,12 @@ class Solver:
         return self._visual_gate(lambda *a: self._lib.ctvio_visual_gate(self._h, int(wid), *a), [int(wid)], cov, min_redundancy)
 
     def _imu_gate(self, call, wids, cov, min_redundancy):
-        o = capi.GateOptions()
-        self._lib.ctvio_default_gate_options(C.byref(o))
-        if min_redundancy is not None:
-            o.min_redundancy = float(min_redundancy)
+        o = _gate_options(self._lib, min_redundancy)
         M = sum(int(self.windows[w].M) for w in wids); F = sum(int(self.windows[w].F) for w in wids)
-        m = max(M, 1)
-        res = np.zeros((m, 6)); st = np.zeros(m, np.int32)
-        red = np.zeros(m) if cov else None; c = np.zeros((m, 6, 6)) if cov else None; chi = np.zeros(m) if cov else None
-        fs = np.zeros((max(F, 1), 4)) if cov else None
-        opt = lambda a: capi._p(a) if a is not None else None
-        capi.check(call(C.byref(o), capi._p(res), opt(red), opt(c), opt(chi), capi._p(st), opt(fs)))
-        cut = lambda a, n: a[:n].copy() if a is not None else None
-        return SimpleNamespace(res=cut(res, M), redundancy=cut(red, M), cov=cut(c, M), chi2=cut(chi, M), status=cut(st, M), frame_stats=cut(fs, F))
+        res = _out(M, 6); st = _out(M, dtype=np.int32)
+        red = _out(M, want=cov); c = _out(M, 6, 6, want=cov); chi = _out(M, want=cov); fs = _out(F, 4, want=cov)
+        capi.check(call(C.byref(o), _ptr(res), _ptr(red), _ptr(c), _ptr(chi), _ptr(st), _ptr(fs)))
+        return SimpleNamespace(res=_cut(res, M), redundancy=_cut(red, M), cov=_cut(c, M), chi2=_cut(chi, M), status=_cut(st, M), frame_stats=_cut(fs, F))
 
     def imu_gate_batch(self, cov: bool = True, min_redundancy=None):
         """ctvio_imu_gate_batch: the leave-one-out test of every IMU sample of the uploaded windows at the current state, window after window
@@ -503,17 +516,14 @@ class Solver:
     def _imu_predict(self, call, m, imu_t, gyro, acc, noise, last_only, cov):
         """m: samples per query (n,); the concatenated samples.  Returns (state (E, 16), cov (E, 15, 15) or None, status (n,)), E = sum m, or n
         with last_only."""
-        t = np.ascontiguousarray(imu_t, np.int64).reshape(-1)
-        g = np.ascontiguousarray(gyro, np.float64).reshape(-1, 3)
-        a = np.ascontiguousarray(acc, np.float64).reshape(-1, 3)
+        t, g, a = _imu_samples(imu_t, gyro, acc)
         n = int(m.shape[0])
         ns = int(t.shape[0])
-        assert g.shape[0] == ns and a.shape[0] == ns and (n == 0 or int(np.clip(m, 0, None).sum()) <= ns)
+        assert n == 0 or int(np.clip(m, 0, None).sum()) <= ns
         ne = n if last_only else ns
-        state = np.zeros((max(ne, 1), 16)); c = np.zeros((max(ne, 1), 15, 15)) if cov else None; st = np.zeros(max(n, 1), np.int32)
-        capi.check(call(capi._p(t), capi._p(g), capi._p(a), C.byref(self._imu_noise(noise)), 1 if last_only else 0, capi._p(state),
-                        capi._p(c) if cov else None, capi._p(st)))
-        return state[:ne].copy(), (c[:ne].copy() if cov else None), st[:n].copy()
+        state = _out(ne, 16); c = _out(ne, 15, 15, want=cov); st = _out(n, dtype=np.int32)
+        capi.check(call(_ptr(t), _ptr(g), _ptr(a), C.byref(self._imu_noise(noise)), 1 if last_only else 0, _ptr(state), _ptr(c), _ptr(st)))
+        return _cut(state, ne), _cut(c, ne), _cut(st, n)
 
     def imu_predict_batch(self, win, frame, n_imu, imu_t, gyro, acc, noise=None, last_only: bool = False, cov: bool = True):
         """ctvio_imu_predict_batch: IMU dead reckoning (midpoint rule) from the navigation state of window win[i] at the first of its n_imu[i]
@@ -522,12 +532,11 @@ class Solver:
         acc_n, gyr_w, acc_w), a dict of some of them, or None for the reference's defaults.  Returns (state (E, 16), cov (E, 15, 15) or None,
         status (n,)): E = sum n_imu entries in query then sample order (sample 0 = nav_state's output), or, last_only, one per query: its last
         sample.  Statuses as nav_state's, per query."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
-        m = np.ascontiguousarray(n_imu, np.int32).reshape(-1)
-        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
+        wi = _arr(win, np.int32)
+        m = _arr(n_imu, np.int32); fr = _arr(frame, np.int32)
         assert m.shape[0] == wi.shape[0] and (fr is None or fr.shape[0] == wi.shape[0])
         return self._imu_predict(lambda t, g, a, nz, lo, s, c, st: self._lib.ctvio_imu_predict_batch(
-            self._h, C.c_int64(int(wi.shape[0])), capi._p(wi), capi._p(fr), capi._p(m), t, g, a, nz, lo, s, c, st), m, imu_t, gyro, acc, noise,
+            self._h, C.c_int64(int(wi.shape[0])), _ptr(wi), _ptr(fr), _ptr(m), t, g, a, nz, lo, s, c, st), m, imu_t, gyro, acc, noise,
             last_only, cov)
 
     def imu_predict(self, wid: int, frame, imu_t, gyro, acc, noise=None, last_only: bool = False, cov: bool = True):
@@ -538,28 +547,18 @@ class Solver:
                                  m, imu_t, gyro, acc, noise, last_only, cov)
 
     def _predict_landmarks(self, call, n_pred, imu_t, gyro, acc, noise, lm, row, row_model, obs, cov, n_pts_expected=None):
-        t = np.ascontiguousarray(imu_t, np.int64).reshape(-1)
-        g = np.ascontiguousarray(gyro, np.float64).reshape(-1, 3)
-        a = np.ascontiguousarray(acc, np.float64).reshape(-1, 3)
-        li = np.ascontiguousarray(lm, np.int32).reshape(-1); r = np.ascontiguousarray(row, np.int32).reshape(-1)
+        t, g, a = _imu_samples(imu_t, gyro, acc)
+        li = _arr(lm, np.int32); r = _arr(row, np.int32); o = _arr(obs, np.float64, 2)
         n = int(li.shape[0])
-        o = None if obs is None else np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
-        assert g.shape[0] == t.shape[0] and a.shape[0] == t.shape[0] and r.shape[0] == n and (o is None or o.shape[0] == n)
+        assert r.shape[0] == n and (o is None or o.shape[0] == n)
         assert n_pts_expected is None or n_pts_expected == n
         if o is not None and not cov:
             raise ValueError("obs needs cov=True: the gate is formed from the covariance")
-        rm = None
-        if row_model is not None:
-            rm = row_model if isinstance(row_model, capi.RowModel) else capi.RowModel(float(row_model[0]), float(row_model[1]), int(row_model[2]), int(row_model[3]))
-        m = max(n, 1)
-        state = np.zeros((max(n_pred, 1), 16)); proj = np.zeros((m, 3)); c = np.zeros((m, 2, 2)) if cov else None
-        chi = np.zeros(m) if o is not None else None
-        ro = np.zeros(m, np.int32); st = np.zeros(m, np.int32)
-        capi.check(call(capi._p(t), capi._p(g), capi._p(a), C.byref(self._imu_noise(noise)), n, capi._p(li), capi._p(r),
-                        C.byref(rm) if rm is not None else None, capi._p(o) if o is not None else None, capi._p(state), capi._p(proj),
-                        capi._p(c) if cov else None, capi._p(chi) if chi is not None else None, capi._p(ro), capi._p(st)))
-        return SimpleNamespace(state=state[:n_pred].copy(), proj=proj[:n].copy(), cov=c[:n].copy() if cov else None,
-                               chi2=chi[:n].copy() if chi is not None else None, row=ro[:n].copy(), status=st[:n].copy())
+        state = _out(n_pred, 16); proj = _out(n, 3); c = _out(n, 2, 2, want=cov); chi = _out(n, want=o is not None)
+        ro = _out(n, dtype=np.int32); st = _out(n, dtype=np.int32)
+        capi.check(call(_ptr(t), _ptr(g), _ptr(a), C.byref(self._imu_noise(noise)), n, _ptr(li), _ptr(r), _row_model(row_model), _ptr(o),
+                        _ptr(state), _ptr(proj), _ptr(c), _ptr(chi), _ptr(ro), _ptr(st)))
+        return SimpleNamespace(state=_cut(state, n_pred), proj=_cut(proj, n), cov=_cut(c, n), chi2=_cut(chi, n), row=_cut(ro, n), status=_cut(st, n))
 
     def predict_landmarks_batch(self, win, frame, n_imu, imu_t, gyro, acc, pred, lm, row, noise=None, cov: bool = True, obs=None, row_model=None):
         """ctvio_predict_landmarks_batch: where landmarks fall in the camera at IMU-predicted poses BEYOND the spline.  Predictions are the queries
@@ -568,14 +567,13 @@ class Solver:
         row, status) plus state (n_pred, 16): the end state of every prediction (imu_predict's with last_only).  The covariance carries the
         window's uncertainty through the propagation (cross terms with the landmark included) plus the IMU process noise.  cov=False: values
         only, nothing is linearised."""
-        wi = np.ascontiguousarray(win, np.int32).reshape(-1)
-        m = np.ascontiguousarray(n_imu, np.int32).reshape(-1)
-        fr = None if frame is None else np.ascontiguousarray(frame, np.int32).reshape(-1)
-        pi = np.ascontiguousarray(pred, np.int32).reshape(-1)
+        wi = _arr(win, np.int32)
+        m = _arr(n_imu, np.int32); fr = _arr(frame, np.int32)
+        pi = _arr(pred, np.int32)
         assert m.shape[0] == wi.shape[0] and (fr is None or fr.shape[0] == wi.shape[0])
         npred = int(wi.shape[0])
         return self._predict_landmarks(lambda t, g, a, nz, n, li, r, *rest: self._lib.ctvio_predict_landmarks_batch(
-            self._h, C.c_int64(npred), capi._p(wi), capi._p(fr), capi._p(m), t, g, a, nz, C.c_int64(n), capi._p(pi), li, r, *rest),
+            self._h, C.c_int64(npred), _ptr(wi), _ptr(fr), _ptr(m), t, g, a, nz, C.c_int64(n), _ptr(pi), li, r, *rest),
             npred, imu_t, gyro, acc, noise, lm, row, row_model, obs, cov, int(pi.shape[0]))
 
     def predict_landmarks(self, wid: int, frame, imu_t, gyro, acc, lm, row, noise=None, cov: bool = True, obs=None, row_model=None):

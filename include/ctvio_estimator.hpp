@@ -443,8 +443,7 @@ class TrajectoryEstimator {
   ResidualSummary GetResidualSummary(const std::string &descri = "") {
     Packed pk;
     pack(pk, false, /*all_factors=*/true);
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     std::vector<double> sums((size_t)14 + pk.w.pn);
     int32_t cnt[4];
     check(ctvio_residual_summary(s, 0, sums.data(), cnt));
@@ -493,8 +492,7 @@ class TrajectoryEstimator {
     }
     if (!lms.empty() && !sel.empty())
       throw std::invalid_argument("covariance between an inverse depth and a trajectory block is not computed: ask for the depths in a list of their own");
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     int32_t singular = 0;
     if (!lms.empty()) {
       std::vector<double> var((size_t)L);
@@ -516,14 +514,12 @@ class TrajectoryEstimator {
   bool GetPoseCovariance(const std::vector<int64_t> &t_ns, std::vector<double> &cov36, const double *q_SI = nullptr, const double *p_SI = nullptr) {
     Packed pk;
     pack(pk, /*marg_only=*/false);
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     const size_t n = t_ns.size();
     cov36.assign(36 * n, 0.0);
     std::vector<int32_t> status(n, 0);
     check(ctvio_pose_covariance(s, 0, (int32_t)n, t_ns.data(), q_SI, p_SI, cov36.data(), status.data()));
-    for (int32_t st : status) if (st != 0) return false;
-    return true;
+    return all_ok(status);
   }
 
   // The navigation state at the times t_ns (absolute, inside the solved knots) with its 15 x 15 covariance, at the CURRENT parameter values, from
@@ -538,30 +534,20 @@ class TrajectoryEstimator {
     Packed pk;
     pack(pk, /*marg_only=*/false);
     const size_t n = t_ns.size();
-    std::vector<int32_t> frame;
-    if (bias_gyr) {
-      auto it = bias_of_.find(bias_gyr);
-      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("GetIMUStateCovariance: not a bias state of this window");
-      frame.assign(n, pk.bias_map[(size_t)it->second]);
-    }
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    const std::vector<int32_t> frame(n, frame_of(pk, bias_gyr, "GetIMUStateCovariance"));
+    ctvio_solver *s = upload(pk);
     std::vector<double> state16(16 * n);
     std::vector<int32_t> status(n, 0);
     cov225.assign(225 * n, 0.0);
     check(ctvio_nav_state(s, 0, (int32_t)n, t_ns.data(), bias_gyr ? frame.data() : nullptr, state16.data(), cov225.data(), status.data()));
     states.assign(n, IMUState());
     bias6.assign(6 * n, 0.0);
-    bool ok = true;
     for (size_t i = 0; i < n; ++i) {
       const double *o = state16.data() + 16 * i;
-      states[i].timestamp = t_ns[i];
-      for (int c = 0; c < 3; ++c) { states[i].p[c] = o[c]; states[i].v[c] = o[7 + c]; }
-      for (int c = 0; c < 4; ++c) states[i].q[c] = o[3 + c];
+      to_imu_state(o, t_ns[i], states[i]);
       std::copy(o + 10, o + 16, bias6.begin() + 6 * i);
-      ok = ok && status[i] == 0;
     }
-    return ok;
+    return all_ok(status);
   }
 
   // The body rates at the times t_ns (absolute, inside the solved knots) with their 15 x 15 covariance, at the CURRENT parameter values, from
@@ -577,22 +563,15 @@ class TrajectoryEstimator {
     Packed pk;
     pack(pk, /*marg_only=*/false);
     const size_t n = t_ns.size();
-    std::vector<int32_t> frame;
-    if (bias_gyr) {
-      auto it = bias_of_.find(bias_gyr);
-      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("GetBodyRatesCovariance: not a bias state of this window");
-      frame.assign(n, pk.bias_map[(size_t)it->second]);
-    }
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    const std::vector<int32_t> frame(n, frame_of(pk, bias_gyr, "GetBodyRatesCovariance"));
+    ctvio_solver *s = upload(pk);
     std::vector<int32_t> status(n, 0);
     rates.assign(9 * n, 0.0);
     cov225.assign(225 * n, 0.0);
     if (chi2) chi2->assign(n, 0.0);
     check(ctvio_body_rates(s, 0, (int32_t)n, t_ns.data(), bias_gyr ? frame.data() : nullptr, meas6, noise6, rates.data(), cov225.data(),
                            chi2 ? chi2->data() : nullptr, status.data()));
-    for (int32_t st : status) if (st != 0) return false;
-    return true;
+    return all_ok(status);
   }
 
   // The pose increments T(t_a)^-1 T(t_b) of the pairs (t_a, t_b) (absolute times, inside the solved knots; t_b may lie before t_a) with their
@@ -605,8 +584,7 @@ class TrajectoryEstimator {
                                  const double *q_SI = nullptr, const double *p_SI = nullptr) {
     Packed pk;
     pack(pk, /*marg_only=*/false);
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     const size_t n = pairs.size();
     std::vector<int64_t> ta(n), tb(n);
     for (size_t i = 0; i < n; ++i) { ta[i] = pairs[i].first; tb[i] = pairs[i].second; }
@@ -614,8 +592,7 @@ class TrajectoryEstimator {
     cov36.assign(36 * n, 0.0);
     std::vector<int32_t> status(n, 0);
     check(ctvio_relative_pose(s, 0, (int32_t)n, ta.data(), tb.data(), q_SI, p_SI, rel.data(), cov36.data(), status.data()));
-    for (int32_t st : status) if (st != 0) return false;
-    return true;
+    return all_ok(status);
   }
 
   // IMU dead reckoning between frames (ctvio_imu_predict): what VisualOdometry::ProcessIMU (visual_odometry.cpp:137-172) does with the state
@@ -630,31 +607,15 @@ class TrajectoryEstimator {
     Packed pk;
     pack(pk, /*marg_only=*/false);
     const size_t m = samples.size();
-    int32_t frame = -1;
-    if (bias_gyr) {
-      auto it = bias_of_.find(bias_gyr);
-      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("PredictIMUStates: not a bias state of this window");
-      frame = pk.bias_map[(size_t)it->second];
-    }
-    std::vector<int64_t> t(m);
-    std::vector<double> gyro(3 * m), acc(3 * m);
-    for (size_t j = 0; j < m; ++j) {
-      t[j] = samples[j].timestamp;
-      for (int c = 0; c < 3; ++c) { gyro[3 * j + c] = samples[j].gyro[c]; acc[3 * j + c] = samples[j].accel[c]; }
-    }
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    const int32_t frame = frame_of(pk, bias_gyr, "PredictIMUStates");
+    const SampleArrays a(samples);
+    ctvio_solver *s = upload(pk);
     std::vector<double> state16(16 * m);
     int32_t status = 0;
     cov225.assign(225 * m, 0.0);
-    check(ctvio_imu_predict(s, 0, frame, (int32_t)m, t.data(), gyro.data(), acc.data(), &noise, 0, state16.data(), cov225.data(), &status));
+    check(ctvio_imu_predict(s, 0, frame, (int32_t)m, a.t.data(), a.gyro.data(), a.acc.data(), &noise, 0, state16.data(), cov225.data(), &status));
     states.assign(m, IMUState());
-    for (size_t j = 0; j < m; ++j) {
-      const double *o = state16.data() + 16 * j;
-      states[j].timestamp = t[j];
-      for (int c = 0; c < 3; ++c) { states[j].p[c] = o[c]; states[j].v[c] = o[7 + c]; }
-      for (int c = 0; c < 4; ++c) states[j].q[c] = o[3 + c];
-    }
+    for (size_t j = 0; j < m; ++j) to_imu_state(state16.data() + 16 * j, a.t[j], states[j]);
     return status == 0;
   }
 
@@ -666,8 +627,7 @@ class TrajectoryEstimator {
   int TriangulateDepths(bool row_times = true, bool only_unset = true, std::vector<int32_t> *flags = nullptr) {
     Packed pk;
     pack(pk, /*marg_only=*/false);
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     ctvio_triangulate_options o;
     ctvio_default_triangulate_options(&o);
     o.row_times = row_times ? 1 : 0; o.only_unset = only_unset ? 1 : 0; o.apply = 0;
@@ -693,8 +653,7 @@ class TrajectoryEstimator {
   bool GetLandmarkPoints(std::vector<double> &points, std::vector<double> *cov9 = nullptr, std::vector<int32_t> *status = nullptr) {
     Packed pk;
     pack(pk, /*marg_only=*/false);
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     const size_t L = (size_t)pk.w.L, n = lm_ptr_.size();
     std::vector<double> pt(3 * L), cv(cov9 ? 9 * L : 0);
     std::vector<int32_t> st(L, 0);
@@ -731,12 +690,9 @@ class TrajectoryEstimator {
     std::vector<int32_t> lm(n), row(n), st(n, 0), ro(n, 0);
     std::vector<int64_t> t(n);
     for (size_t i = 0; i < n; ++i) {
-      auto it = lm_of_.find(queries[i].inv_depth);
-      if (it == lm_of_.end() || pk.lm_map[(size_t)it->second] < 0) throw std::invalid_argument("ProjectLandmarks: not a landmark of this window");
-      lm[i] = pk.lm_map[(size_t)it->second]; t[i] = queries[i].timestamp; row[i] = queries[i].row;
+      lm[i] = landmark_of(pk, queries[i].inv_depth, "ProjectLandmarks"); t[i] = queries[i].timestamp; row[i] = queries[i].row;
     }
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     proj3.assign(3 * n, 0.0);
     if (cov4) cov4->assign(4 * n, 0.0);
     if (chi2) chi2->assign(n, 0.0);
@@ -744,8 +700,7 @@ class TrajectoryEstimator {
                                   cov4 ? cov4->data() : nullptr, chi2 ? chi2->data() : nullptr, ro.data(), st.data()));
     if (row_out) *row_out = ro;
     if (status) *status = st;
-    for (int32_t v : st) if (v != 0) return false;
-    return true;
+    return all_ok(st);
   }
   // After Solve, which observations are outliers (ctvio_visual_gate): the leave-one-out innovation test of every image factor added so far,
   // at the CURRENT parameter values.  blocks: per factor, in the order of the AddImageFeatureDelayAnalytic calls -- res2 (2 per factor, the
@@ -764,8 +719,7 @@ class TrajectoryEstimator {
     Packed pk;
     pack(pk, /*marg_only=*/false);
     const size_t V = (size_t)pk.w.V, L = (size_t)pk.w.L;
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     ctvio_gate_options o;
     ctvio_default_gate_options(&o);
     o.min_redundancy = min_redundancy;
@@ -786,8 +740,7 @@ class TrajectoryEstimator {
         (*landmarks)[lm_ptr_[l]] = g;
       }
     }
-    for (int32_t v : blocks.status) if (v != 0) return false;
-    return true;
+    return all_ok(blocks.status);
   }
   // After Solve, which IMU samples are outliers (ctvio_imu_gate): the leave-one-out test of every IMU factor added so far, at the CURRENT
   // parameter values -- the IMU factor carries no robust loss, so a saturated or mis-timed sample pulls the spline at full weight.
@@ -805,8 +758,7 @@ class TrajectoryEstimator {
     Packed pk;
     pack(pk, /*marg_only=*/false);
     const size_t M = (size_t)pk.w.M, F = (size_t)pk.w.F;
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    ctvio_solver *s = upload(pk);
     ctvio_gate_options o;
     ctvio_default_gate_options(&o);
     o.min_redundancy = min_redundancy;
@@ -823,8 +775,7 @@ class TrajectoryEstimator {
         (*frames)[bias_ptr_[f].first] = FrameGate{(int32_t)fs[4 * (size_t)j], fs[4 * (size_t)j + 1], fs[4 * (size_t)j + 2], fs[4 * (size_t)j + 3]};
       }
     }
-    for (int32_t v : samples.status) if (v != 0) return false;
-    return true;
+    return all_ok(samples.status);
   }
   // Where landmarks fall in the NEXT image, beyond the solved knots (ctvio_predict_landmarks): PredictIMUStates' dead reckoning through
   // `samples` (samples[0] inside the solved knots, the newest frame time in the reference's use; bias_gyr as there) composed with
@@ -840,42 +791,22 @@ class TrajectoryEstimator {
     pack(pk, /*marg_only=*/false);
     const size_t m = samples.size(), n = points.size();
     if ((chi2 != nullptr) != (obs2 != nullptr) || (obs2 && obs2->size() != 2 * n)) throw std::invalid_argument("PredictLandmarks: obs2 (2 per point) and chi2 come together");
-    int32_t frame = -1;
-    if (bias_gyr) {
-      auto it = bias_of_.find(bias_gyr);
-      if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument("PredictLandmarks: not a bias state of this window");
-      frame = pk.bias_map[(size_t)it->second];
-    }
-    std::vector<int64_t> t(m);
-    std::vector<double> gyro(3 * m), acc(3 * m);
-    for (size_t j = 0; j < m; ++j) {
-      t[j] = samples[j].timestamp;
-      for (int c = 0; c < 3; ++c) { gyro[3 * j + c] = samples[j].gyro[c]; acc[3 * j + c] = samples[j].accel[c]; }
-    }
+    const int32_t frame = frame_of(pk, bias_gyr, "PredictLandmarks");
+    const SampleArrays a(samples);
     std::vector<int32_t> lm(n), row(n), st(n, 0), ro(n, 0);
-    for (size_t i = 0; i < n; ++i) {
-      auto it = lm_of_.find(points[i].inv_depth);
-      if (it == lm_of_.end() || pk.lm_map[(size_t)it->second] < 0) throw std::invalid_argument("PredictLandmarks: not a landmark of this window");
-      lm[i] = pk.lm_map[(size_t)it->second]; row[i] = points[i].row;
-    }
-    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
-    check(ctvio_set_batch(s, 1, &pk.w));
+    for (size_t i = 0; i < n; ++i) { lm[i] = landmark_of(pk, points[i].inv_depth, "PredictLandmarks"); row[i] = points[i].row; }
+    ctvio_solver *s = upload(pk);
     double state16[16] = {0};
     proj3.assign(3 * n, 0.0);
     if (cov4) cov4->assign(4 * n, 0.0);
     if (chi2) chi2->assign(n, 0.0);
-    check(ctvio_predict_landmarks(s, 0, frame, (int32_t)m, t.data(), gyro.data(), acc.data(), &noise, (int32_t)n, lm.data(), row.data(), rm,
+    check(ctvio_predict_landmarks(s, 0, frame, (int32_t)m, a.t.data(), a.gyro.data(), a.acc.data(), &noise, (int32_t)n, lm.data(), row.data(), rm,
                                   obs2 ? obs2->data() : nullptr, state16, proj3.data(), cov4 ? cov4->data() : nullptr, chi2 ? chi2->data() : nullptr,
                                   ro.data(), st.data()));
-    if (end && m) {
-      end->timestamp = t[m - 1];
-      for (int c = 0; c < 3; ++c) { end->p[c] = state16[c]; end->v[c] = state16[7 + c]; }
-      for (int c = 0; c < 4; ++c) end->q[c] = state16[3 + c];
-    }
+    if (end && m) to_imu_state(state16, a.t[m - 1], *end);
     if (row_out) *row_out = ro;
     if (status) *status = st;
-    for (int32_t v : st) if (v != 0) return false;
-    return true;
+    return all_ok(st);
   }
 
  private:
@@ -892,6 +823,44 @@ class TrajectoryEstimator {
   };
   static void check(int rc) {
     if (rc) throw std::runtime_error(std::string(ctvio_status_string(rc)) + ": " + ctvio_last_error());
+  }
+  // the cached handle with pk as its one-window batch; callers run every argument check that can throw before it
+  ctvio_solver *upload(const Packed &pk) {
+    ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
+    check(ctvio_set_batch(s, 1, &pk.w));
+    return s;
+  }
+  // gyro-bias pointer as given to the Add* calls -> bias index in the window (nullptr: -1, the entries' "newest")
+  int frame_of(const Packed &pk, const double *bias_gyr, const char *who) const {
+    if (!bias_gyr) return -1;
+    auto it = bias_of_.find(bias_gyr);
+    if (it == bias_of_.end() || pk.bias_map[(size_t)it->second] < 0) throw std::invalid_argument(std::string(who) + ": not a bias state of this window");
+    return pk.bias_map[(size_t)it->second];
+  }
+  // inverse-depth pointer as given to AddImageFeatureDelayAnalytic -> landmark index in the window
+  int landmark_of(const Packed &pk, const double *inv_depth, const char *who) const {
+    auto it = lm_of_.find(inv_depth);
+    if (it == lm_of_.end() || pk.lm_map[(size_t)it->second] < 0) throw std::invalid_argument(std::string(who) + ": not a landmark of this window");
+    return pk.lm_map[(size_t)it->second];
+  }
+  struct SampleArrays {   // IMU samples as the entries take them
+    std::vector<int64_t> t;
+    std::vector<double> gyro, acc;
+    explicit SampleArrays(const std::vector<IMUData> &samples) : t(samples.size()), gyro(3 * samples.size()), acc(3 * samples.size()) {
+      for (size_t j = 0; j < samples.size(); ++j) {
+        t[j] = samples[j].timestamp;
+        for (int c = 0; c < 3; ++c) { gyro[3 * j + c] = samples[j].gyro[c]; acc[3 * j + c] = samples[j].accel[c]; }
+      }
+    }
+  };
+  static void to_imu_state(const double *state16, int64_t t, IMUState &st) {   // state16: p, q (x, y, z, w), v, bg, ba
+    st.timestamp = t;
+    for (int c = 0; c < 3; ++c) { st.p[c] = state16[c]; st.v[c] = state16[7 + c]; }
+    for (int c = 0; c < 4; ++c) st.q[c] = state16[3 + c];
+  }
+  static bool all_ok(const std::vector<int32_t> &status) {
+    for (int32_t v : status) if (v != 0) return false;
+    return true;
   }
   // AddControlPoints (trajectory_estimator.cpp:114-141) for knots k0..k1
   void touch(int k0, int k1) {

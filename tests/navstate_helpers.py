@@ -93,7 +93,7 @@ def entry_errors(c, r):
     c, r = np.asarray(c, float), np.asarray(r, float)
     d = np.diag(r)
     live = d > 0
-    e = np.zeros((15, 15))
+    e = np.zeros(r.shape)
     sd = np.sqrt(np.where(live, d, 1.0))
     e[np.ix_(live, live)] = (np.abs(c - r) / np.outer(sd, sd))[np.ix_(live, live)]
     dead = ~(live[:, None] & live[None, :])

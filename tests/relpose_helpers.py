@@ -76,15 +76,4 @@ def entry_bounds(tol, g):
     return tol * np.sqrt(np.outer(g, g))
 
 
-def entry_errors(c, r):
-    """|c_ab - r_ab| / sqrt(r_aa r_bb) entry by entry; rows whose reference diagonal is zero (constant unknowns alone) must be exact zeros in c and
-    count as error 0 / inf."""
-    c, r = np.asarray(c, float), np.asarray(r, float)
-    d = np.diag(r)
-    live = d > 0
-    e = np.zeros((6, 6))
-    sd = np.sqrt(np.where(live, d, 1.0))
-    e[np.ix_(live, live)] = (np.abs(c - r) / np.outer(sd, sd))[np.ix_(live, live)]
-    dead = ~(live[:, None] & live[None, :])
-    e[dead & (c != 0.0)] = np.inf
-    return e
+entry_errors = nh.entry_errors

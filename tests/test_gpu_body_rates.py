@@ -34,7 +34,6 @@ seed 1003 after solve(15): kappa_s 4.47e9, 4 kappa_s 2^-53 = 2.0e-6; g omega 26 
 the cap at the solved state too), g v_B 5 .. 56; largest bound among the capped entries 2.9e-4; worst error / bound 0.068 (1.3e-7 at 2.0e-6).
 `tiny` with locked biases: kappa_s 4.2e4, every bound below 5e-8, worst error / bound 0.034."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -42,21 +41,14 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import DET, device_reference  # noqa: E402,F401
 
 OFF = ~np.eye(15, dtype=bool)
 TINY_QUERIES = ((0, 0.0), (1, 0.9), (5, 0.37), (7, 0.999), (8, 0.0), (8, 0.5))
 TINY_F_CAPPED = (0, 1)                                  # the `tiny` queries whose f rows are held to the cap (see above)
 C1_QUERIES = ((0, 0.0), (0, 0.37), (1, 0.9), (2, 0.25), (3, 0.0), (3, 0.37))
-DET = dict(deterministic=2)
-
-
-def device_reference(s, wid, w):
-    """cov_reference over all P unknowns of window wid on the device's own linearisation at its current state."""
-    import cov_helpers as ch
-    H, W, Hll, _, _ = s.linearize(wid)
-    return ch.cov_reference(H, W, Hll, ~ch.constant_mask(w), range(w.P))
 
 
 def check(w, ref, times, frames, rates, cov, st, what, f_capped=(), expect=None):
@@ -109,7 +101,7 @@ def check(w, ref, times, frames, rates, cov, st, what, f_capped=(), expect=None)
 
 
 def same(a, b):
-    return all((x is None and y is None) or np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
+    return qh.same_bits(tuple(a), tuple(b))
 
 
 def test_tiny_initial_state(cv):
@@ -139,14 +131,10 @@ def config1_solved(cv):
     """`config1` seed 1003 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference, the
     queries, the covariance call's outputs)."""
     import rates_helpers as rh
-    w = cv.synth.make_window("config1", seed=1003)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        times = np.array([rh.time_of(b[0], sg, u) for sg, u in C1_QUERIES], np.int64)
+    for s, w in qh.solved_window(cv, "config1", 1003, 15):
+        times = np.array([rh.time_of(w, sg, u) for sg, u in C1_QUERIES], np.int64)
         frames = np.array([i % w.F for i in range(len(times))], np.int32)
-        yield s, b[0], device_reference(s, 0, b[0]), times, frames, s.body_rates(0, times, frames)
+        yield s, w, device_reference(s, 0, w), times, frames, s.body_rates(0, times, frames)
 
 
 def test_config1_solved_against_reference(config1_solved):
@@ -272,27 +260,12 @@ def test_leaves_the_solve_alone(cv):
     import rates_helpers as rh
     w = cv.synth.make_window("config1", seed=1003)
     times = [rh.time_of(w, sg, u) for sg, u in C1_QUERIES]
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
+
+    def calls(s, b):
         o1 = s.body_rates(0, times, meas=np.ones((len(times), 6)))
         assert not o1[3].any() and np.isfinite(o1[1]).all() and np.isfinite(o1[2]).all()
         s.body_rates(0, times, cov=False)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver() as fs:
-        fb = [w.copy()]
-        fs.set_windows(fb)
-        fs.solve(6, writeback=False)
-        smf = fs.solve(6)
-    assert sm == smf
-    for a in ("quat", "pos", "bias", "rho"):
-        assert np.array_equal(getattr(b[0], a), getattr(fb[0], a)), a
-    assert b[0].ld == fb[0].ld
+    qh.check_leaves_the_solve_alone(cv, [w], calls, solver_kw={})
 
 
 def test_refusals_leave_the_handle_usable(cv):
@@ -360,36 +333,16 @@ def test_refusals_leave_the_handle_usable(cv):
         assert single(0, 1, p(t), None, p(z), None, p(x), p(cov), p(chi), p(st)) == 1
         assert single(0, 1, p(t), None, p(z), p(sg), p(x), p(cov), p(chi), p(st)) == 0 and np.isfinite(chi[0])
         assert single(0, 1, p(t), None, None, None, p(x), p(cov), None, p(st)) == 0
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_body_rates_matches_python(cv, tmp_path):
     """tests/body_rates_demo.cpp through the C++ adaptor: the rates, covariances, twists and the gated sample equal the Python call on the same
     window at the demo's solved state, bit for bit."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "body_rates_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "body_rates_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
     K, F, L = w0.K, w0.F, w0.L
     n, g = 4, w0.M // 4
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(n), str(g)], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("body_rates_demo", tmp_path), w0, tmp_path, 15, n, g)
     assert rest[0] == 1 and rest[1] == n
     r_cpp, c_cpp = rest[2:2 + 9 * n].reshape(n, 9), rest[2 + 9 * n:2 + 234 * n].reshape(n, 15, 15)
     tw = rest[2 + 234 * n:2 + 276 * n].reshape(n, 42)

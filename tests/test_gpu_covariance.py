@@ -4,7 +4,6 @@ is held to the oracle's at 1e-10 elsewhere; kappa_s x 1e-10 would be O(1)).  Tol
 helper, on max |Sigma_a - Sigma_b| / sqrt(Sigma_ii Sigma_jj) over the finite selected pairs and on the relative error of var_rho.  The smallest
 modelling error this must catch -- leftover LM damping at radius 1e4 -- moves Sigma by about 1e-4."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,8 +11,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import DET, same_bits  # noqa: E402,F401  (the other entries' tests take both from here)
 
 
 def reference(s, wid, w, sel):
@@ -123,10 +123,7 @@ def mixed_batch(cv):
     return ws, sels
 
 
-# The bit-for-bit comparisons need a linearisation that is itself repeatable: by default a batch with a window beyond the LDS-resident Hessian
-# (the P = 301 and K = 27 windows here) assembles its normal equations with floating-point atomics, and two runs differ at 1e-13 before any
-# kernel of the covariance starts.  deterministic = 2 fixes the order for every batch; cases 1, 2, 3 and 5 run the default mode.
-DET = dict(deterministic=2)
+# The bit-for-bit comparisons run with query_harness.DET (order-fixed linearisation, and why); cases 1, 2, 3 and 5 run the default mode.
 
 
 def run_mixed(cv, ws, sels):
@@ -167,11 +164,6 @@ def test_mixed_batch_other_factorisations(cv, mixed, monkeypatch, env):
         monkeypatch.setenv(k, v)
     ws, sels, refs, _ = mixed
     check_mixed(ws, sels, refs, run_mixed(cv, ws, sels), str(env))
-
-
-def same_bits(a, b):
-    return (all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a[0], b[0])) and all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a[1], b[1]))
-            and np.array_equal(a[2], b[2]))
 
 
 def test_mixed_batch_poisoned_scratch_same_bits(cv, mixed, monkeypatch):
@@ -251,36 +243,16 @@ def test_refusals_leave_the_handle_usable(cv):
                 s.covariance_batch([bad])
         cov, var, sing = s.covariance(0, [], rho=False)
         assert cov.shape == (0, 0) and var is None and sing == 0
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_covariance_matches_python(cv, tmp_path):
     """Case 8: tests/covariance_demo.cpp through the C++ adaptor: the covariance of the newest touched knot and the last bias state equals
     the Python call on the same window to 1e-12 relative."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "covariance_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "covariance_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
     K, F, L = w0.K, w0.F, w0.L
     knot = K - 2
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(knot)], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("covariance_demo", tmp_path), w0, tmp_path, 15, knot)
     assert rest[0] == 1 and rest[1] == 12
     cov_cpp = rest[2:2 + 144].reshape(12, 12)
     ok2, v0, v1, refused = rest[146:150]

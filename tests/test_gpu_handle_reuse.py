@@ -24,8 +24,6 @@ import marg_blocked_helpers as mb
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @contextlib.contextmanager
@@ -372,11 +370,9 @@ def test_cpp_adaptor_under_poison(cv, tmp_path):
     residual summary of the three slide windows) writes the same bytes with the switch off and with either pattern -- each run a fresh
     process under its own time limit."""
     import slide_helpers as sh
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "slide_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "slide_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
-    _dump(sh.make_world(), str(tmp_path / "world.txt"))
+    import query_harness as qh
+    exe = qh.build_demo("slide_demo", tmp_path)
+    qh._dump(sh.make_world(), str(tmp_path / "world.txt"))
     outs = []
     for pattern in (None, 1, 2):
         env = {k: v for k, v in os.environ.items() if k != "CTVIO_POISON"}

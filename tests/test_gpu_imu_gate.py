@@ -19,17 +19,13 @@ import pytest
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import DET, device_joint_reference as device_reference  # noqa: E402,F401
 
 EPS = 2.0 ** -53
-DET = dict(deterministic=2)
 FIELDS = ("res", "redundancy", "cov", "chi2", "status", "frame_stats")
 VALUES = ("res",)
 IMU_ARRAYS = ("imu_t", "imu_gyro", "imu_acc", "imu_bias")
-
-
-def device_reference(s, wid, w):
-    from test_gpu_landmark_points import device_reference as dr
-    return dr(s, wid, w)
 
 
 def references(w, ref, min_red=0.01):
@@ -38,7 +34,7 @@ def references(w, ref, min_red=0.01):
 
 
 def same(a, b, fields=FIELDS):
-    return all(np.array_equal(getattr(a, f), getattr(b, f), equal_nan=True) for f in fields)
+    return qh.same_bits(a, b, fields)
 
 
 def take(o, ms, fs):
@@ -239,11 +235,8 @@ def test_leaves_the_solve_alone(cv, golden_dir):
     imu_w (rates9[:6] + bias - meas) from ctvio_body_rates at the sample times, to the bit; the per-component sum of |res6| is
     ctvio_residual_summary's IMU sum within M 2^-52 relative."""
     ws = mixed_windows(cv, golden_dir)[:2]
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
+
+    def calls(s, b):
         o1 = s.imu_gate_batch()
         ms, launches = s.last_timing()
         assert launches[:4].tolist() == [1, 1, 1, 1] and ms[7] >= ms[1] > 0 and ms[2] > 0 and ms[3] > 0
@@ -251,8 +244,9 @@ def test_leaves_the_solve_alone(cv, golden_dir):
         ms, launches = s.last_timing()
         assert launches[:4].tolist() == [0, 0, 1, 0] and ms[7] >= ms[2] > 0
         assert same(o1, o2, VALUES)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
+        return o1
+
+    def cross_checks(s, b, o1):
         s.writeback_all()
         m0 = 0
         for i, w in enumerate(b):
@@ -266,17 +260,7 @@ def test_leaves_the_solve_alone(cv, golden_dir):
             print(f"window {i}: sum |res6| against the residual summary: {np.abs(mine - sums) / sums} of M 2^-52 = {w.M * 2.0 ** -52:.3g}")
             assert cnt == w.M and (np.abs(mine - sums) <= w.M * 2.0 ** -52 * sums).all(), (i, mine, sums)
             m0 += w.M
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as f:
-        fb = [w.copy() for w in ws]
-        f.set_windows(fb)
-        f.solve(6, writeback=False)
-        smf = f.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
+    qh.check_leaves_the_solve_alone(cv, ws, calls, compare_ld=False, then=cross_checks)
 
 
 def test_callers_sample_order(cv, golden_dir):

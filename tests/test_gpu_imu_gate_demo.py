@@ -3,26 +3,21 @@ reading of one IMU sample by 0.04 rad/s (10 sigma at imu_w = 250), solves the wi
 has the largest chi2 of its window, beyond the 99 % point of chi-square with 6 degrees of freedom (the demo's own exit status), and its bias
 state reports it; per-factor results come in the order of the AddIMUMeasurementAnalytic calls, per-frame results keyed by the gyro-bias
 pointer."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 def test_corrupted_sample_has_the_largest_chi2(cv, tmp_path):
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "imu_gate_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "imu_gate_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
+    import query_harness as qh
+    exe = qh.build_demo("imu_gate_demo", tmp_path)
     w0 = cv.synth.make_window("config1", seed=1003)
     M, F, bad = w0.M, w0.F, 250
     assert M == 500 and abs(w0.imu_w[0] - 250.0) < 1e-9
-    _dump(w0, str(tmp_path / "in.txt"))
+    qh._dump(w0, str(tmp_path / "in.txt"))
     p = subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(bad), "0.04"], capture_output=True, text=True, timeout=120)
     print(p.stdout[-400:])
     assert p.returncode == 0, (p.returncode, p.stdout[-400:], p.stderr[-2000:])

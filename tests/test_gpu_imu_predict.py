@@ -10,7 +10,6 @@ np.longdouble on those inputs (the recurrence's own rounding), 64 for the device
 asserts that this bound is below 1e-10 and prints it: a wrong block is at least 1e-5 (J = I alone is 2.5e-3 at these rates).  States:
 positions and velocities to 1e-12 max(1, |x|), rotations to 1e-12 rad, biases equal to the bit -- the tolerances of test_gpu_nav_state.py."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,8 +17,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
 
 FRAME_DT = 100_000_000      # synth.py: frame_dt_ns of every configuration used here
 OFF = ~np.eye(15, dtype=bool)
@@ -226,37 +225,19 @@ def test_mixed_batch_bits(cv):
 def test_leaves_the_solve_alone(cv):
     """Case 6: state bits, graph captures and a following solve are unchanged by the call; ctvio_covariance_batch on the same handle gives
     identical bits before and after it; last_timing reports one launch in each of the slots 0..3."""
-    from test_gpu_covariance import DET, mixed_batch, same_bits
+    from test_gpu_covariance import mixed_batch
     ws, sels = mixed_batch(cv)
     win, fr, ms, sam = mixed_queries(ws)
     args = (win, fr, ms) + cat(sam, range(len(win)))
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
-        before = s.covariance_batch(sels, rho=True)
+
+    def calls(s, b):
         o1 = s.imu_predict_batch(*args)
         assert np.isfinite(o1[1][np.repeat(o1[2] == 0, ms)]).all() and np.isfinite(o1[0]).all()
         ms8, launches = s.last_timing()
         assert launches[:4].tolist() == [1, 1, 1, 1] and ms8[7] >= ms8[3] > 0 and (ms8[:3] > 0).all() and not ms8[4:7].any()
         s.imu_predict_batch(*args, cov=False)
         s.imu_predict_batch(*args, last_only=True)
-        assert same_bits(s.covariance_batch(sels, rho=True), before)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as fs:
-        fb = [w.copy() for w in ws]
-        fs.set_windows(fb)
-        fs.solve(6, writeback=False)
-        smf = fs.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls, sels)
 
 
 def test_refusals_leave_the_handle_usable(cv):
@@ -316,41 +297,21 @@ def test_refusals_leave_the_handle_usable(cv):
         assert batch(x=None, c=None) == 0 and st[0] == 0
         zero = cv.capi.ImuNoise(0.0, 0.0, 0.0, 0.0)
         assert batch(nz=zero) == 0                                                 # sigma 0 is allowed
-        bl = [w.copy()]
-        s.set_windows(bl)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(bl[0].pos, fb[0].pos) and np.array_equal(bl[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_predict_matches_python(cv, tmp_path):
     """Case 8: tests/imu_predict_demo.cpp through the C++ adaptor: the states and covariances of 11 samples from the newest frame time, with the
     newest bias state and with bias state 1, equal the Python call on the same window at the demo's solved state, bit for bit."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "imu_predict_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "imu_predict_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
     K, F, L = w0.K, w0.F, w0.L
     m = 11
     t, gyro, acc = draw(w0, m, 1005)
-    _dump(w0, str(tmp_path / "in.txt"))
     with open(tmp_path / "samples.txt", "w") as fh:
         fh.write(f"{m}\n")
         for j in range(m):
             fh.write(f"{int(t[j])} " + " ".join(repr(float(v)) for v in np.concatenate([gyro[j], acc[j]])) + "\n")
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(tmp_path / "samples.txt")], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("imu_predict_demo", tmp_path), w0, tmp_path, 15, str(tmp_path / "samples.txt"))
     got = []
     for _ in range(2):
         assert rest[0] == 1 and rest[1] == m

@@ -7,7 +7,6 @@ Tolerance of the covariances everywhere: cov_helpers.bound(kappa_s) * g on cov_h
 of [Jp | j_rho] over the joint covariance; every check asserts that its bound stays below 1e-4.  Points: the sensor-pose test's rtol 1e-12 and
 atol 1e-11, the atol times max(1, the window's largest depth in metres) -- a rotation error acts at the lever arm of the depth."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,18 +14,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import device_joint_reference as device_reference  # noqa: E402,F401
 
 OFF = ~np.eye(3, dtype=bool)
-
-
-def device_reference(s, wid, w):
-    """lmpoint_helpers.joint_reference of window wid on the device's own linearisation at its current state."""
-    import cov_helpers as ch
-    import lmpoint_helpers as lh
-    H, W, Hll, _, _ = s.linearize(wid)
-    return lh.joint_reference(H, W, Hll, ~ch.constant_mask(w))
 
 
 def check(w, ref, pts, cov, st, what, only=None):
@@ -75,12 +67,8 @@ def test_tiny_initial_state(cv):
 @pytest.fixture(scope="module")
 def config1_solved(cv):
     """`config1` seed 1000 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference)."""
-    w = cv.synth.make_window("config1", seed=1000)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        yield s, b[0], device_reference(s, 0, b[0])
+    for s, w in qh.solved_window(cv, "config1", 1000, 15):
+        yield s, w, device_reference(s, 0, w)
 
 
 def test_config1_solved(config1_solved):
@@ -238,15 +226,11 @@ def test_cross_check_against_the_entries_that_exist(config1_solved):
 def test_leaves_the_solve_alone(cv, mixed):
     """Case 7: state bits, graph captures and a following solve are unchanged by the calls; ctvio_covariance_batch on the same handle gives
     identical bits before and after them; the timing slots of both calls; the points-only call's points have the covariance call's bits."""
-    from test_gpu_covariance import DET, mixed_batch, same_bits
+    from test_gpu_covariance import mixed_batch
     ws, _, _ = mixed
     _, sels = mixed_batch(cv)
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
-        before = s.covariance_batch(sels, rho=True)
+
+    def calls(s, b):
         p1, c1, s1 = s.landmark_points_batch()
         assert np.isfinite(c1[s1 == 0]).all() and np.isfinite(p1[s1 != 3]).all()
         ms, launches = s.last_timing()
@@ -255,21 +239,7 @@ def test_leaves_the_solve_alone(cv, mixed):
         ms, launches = s.last_timing()
         assert launches[:3].tolist() == [1, 0, 0] and ms[7] >= ms[0] > 0
         assert c2 is None and np.array_equal(p2, p1) and np.array_equal(s2, s1)
-        assert same_bits(s.covariance_batch(sels, rho=True), before)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as f:
-        fb = [w.copy() for w in ws]
-        f.set_windows(fb)
-        f.solve(6, writeback=False)
-        smf = f.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls, sels)
 
 
 def test_refusals_leave_the_handle_usable(cv):
@@ -296,37 +266,17 @@ def test_refusals_leave_the_handle_usable(cv):
         assert lib.ctvio_landmark_points_batch(h, p(pts), None, p(st)) == 0                   # points only
         p1, c1, s1 = s.landmark_points(0)
         assert not s1.any() and np.array_equal(c1.ravel(), cov) and np.array_equal(p1.ravel(), pts) and not st.any()
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_landmark_points_matches_python(cv, tmp_path):
     """Case 9: tests/landmark_points_demo.cpp through the C++ adaptor: points, covariances and statuses equal the Python call on the same window
     at the demo's solved state, bit for bit; entry i of the adaptor is the i-th landmark in the order of first appearance among the blocks."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "landmark_points_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "landmark_points_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
-    K, F, L = w0.K, w0.F, w0.L
+    L = w0.L
     order = list(dict.fromkeys(int(l) for l in w0.v_lm))
     assert sorted(order) == list(range(L))
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15"], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("landmark_points_demo", tmp_path), w0, tmp_path, 15)
     assert rest[0] == 1 and rest[1] == L
     pts_cpp = rest[2:2 + 3 * L].reshape(L, 3)
     cov_cpp = rest[2 + 3 * L:2 + 12 * L].reshape(L, 3, 3)

@@ -9,7 +9,6 @@ Sigma becomes at most tol s_a s_b in Pi_ab).  The velocity rows cancel between n
 among pose and bias rows -- the size of the leftover-damping error the covariance tests exist to catch -- and below 1e-3 for entries that
 involve a velocity row, whose own errors (a wrong derivative coefficient, a missing 1 / dt, a knot offset) are O(1)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,18 +16,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 FRAME_DT = 100_000_000      # synth.py: frame_dt_ns of every configuration used here
 OFF = ~np.eye(15, dtype=bool)
-
-
-def device_reference(s, wid, w):
-    """cov_reference over all P unknowns of window wid on the device's own linearisation at its current state."""
-    import cov_helpers as ch
-    H, W, Hll, _, _ = s.linearize(wid)
-    return ch.cov_reference(H, W, Hll, ~ch.constant_mask(w), range(w.P))
 
 
 def check(w, ref, times, frames, state, cov, st, what, expect=None):
@@ -86,9 +77,10 @@ def test_tiny_initial_state(cv):
     times = [nh.time_of(w, s, u) for s, u in ((0, 0.0), (1, 0.9), (5, 0.37), (7, 0.999), (8, 0.0), (8, 0.5))]
     times += [w.t0_ns - 1, w.t0_ns + (w.K - 3) * w.dt_ns]           # before t0; the end of the spline
     frames = [i % w.F for i in range(len(times))]
+    import query_harness as qh
     with cv.Solver() as s:
         s.set_windows([w.copy()])
-        ref = device_reference(s, 0, w)
+        ref = qh.device_reference(s, 0, w)
         state, cov, st = s.nav_state(0, times, frames)
         state_n, cov_n, st_n = s.nav_state(0, times)
         state_l, cov_l, st_l = s.nav_state(0, times, [w.F - 1] * len(times))
@@ -106,12 +98,9 @@ def test_tiny_initial_state(cv):
 @pytest.fixture(scope="module")
 def config1_solved(cv):
     """`config1` seed 1000 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference)."""
-    w = cv.synth.make_window("config1", seed=1000)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        yield s, b[0], device_reference(s, 0, b[0])
+    import query_harness as qh
+    for s, w in qh.solved_window(cv, "config1", 1000, 15):
+        yield s, w, qh.device_reference(s, 0, w)
 
 
 def test_config1_solved_frames(config1_solved):
@@ -140,9 +129,10 @@ def test_constants(cv):
     w.normalize()
     times = [nh.time_of(w, 0, 0.0), nh.time_of(w, 1, 0.5)]
     frames = [1, 2]
+    import query_harness as qh
     with cv.Solver() as s:
         s.set_windows([w.copy()])
-        ref = device_reference(s, 0, w)
+        ref = qh.device_reference(s, 0, w)
         state, cov, st = s.nav_state(0, times, frames)
     assert st.tolist() == [0, 0]
     assert not cov[0][:12].any() and not cov[0][:, :12].any() and (np.diag(cov[0])[12:] > 0).all()
@@ -173,12 +163,13 @@ def mixed(cv):
     """The four windows of test_gpu_covariance's mixed batch (`tiny`, `config1`, the F = 16 window on the envelope panel path, the IMU-only
     predict window with locked biases and L = 0), order-fixed linearisation; the queries, the device references and the plain call's outputs --
     computed once."""
+    import query_harness as qh
     from test_gpu_covariance import DET, mixed_batch
     ws, _ = mixed_batch(cv)
     win, t, f = mixed_queries(ws)
     with cv.Solver(**DET) as s:
         s.set_windows([w.copy() for w in ws])
-        refs = [device_reference(s, i, w) for i, w in enumerate(ws)]
+        refs = [qh.device_reference(s, i, w) for i, w in enumerate(ws)]
         out = s.nav_state_batch(win, t, f)
     return ws, win, t, f, refs, out
 
@@ -194,20 +185,11 @@ def test_mixed_batch_against_reference(mixed):
 def test_mixed_batch_bits(cv, mixed):
     """Case 4: the bits of a query depend on its window, time and frame alone: the single-window entry, a second call, the reversed order, and
     calls with other counts per window give the batch call's bits."""
-    from test_gpu_covariance import DET
+    import query_harness as qh
     ws, win, t, f, _, out = mixed
-    same = lambda a, b: all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-    with cv.Solver(**DET) as s:
+    with cv.Solver(**qh.DET) as s:
         s.set_windows([w.copy() for w in ws])
-        for i in range(len(ws)):
-            idx = np.nonzero(win == i)[0]
-            assert same(s.nav_state(i, t[idx], f[idx]), [o[idx] for o in out]), i
-        assert same(s.nav_state_batch(win, t, f), out)
-        rev = s.nav_state_batch(win[::-1].copy(), t[::-1].copy(), f[::-1].copy())
-        assert same([o[::-1] for o in rev], out)
-        n = len(ws)
-        for keep in (np.arange(n), np.arange(2 * n), np.r_[np.arange(n), np.arange(2 * n, 3 * n)]):    # 1 / 2 / the outer 2 of the 3 per window
-            assert same(s.nav_state_batch(win[keep].copy(), t[keep].copy(), f[keep].copy()), [o[keep] for o in out]), keep
+        qh.check_batch_bits(s.nav_state, s.nav_state_batch, win, (t, f), out, len(ws))
 
 
 def test_cross_checks(config1_solved):
@@ -251,40 +233,24 @@ def test_cross_checks(config1_solved):
 def test_leaves_the_solve_alone(cv, mixed):
     """Case 6: state bits, graph captures and a following solve are unchanged by the call; ctvio_covariance_batch on the same handle gives
     identical bits before and after it; last_timing reports one launch of each of the three kernels."""
-    from test_gpu_covariance import DET, mixed_batch, same_bits
+    import query_harness as qh
+    from test_gpu_covariance import mixed_batch
     ws, win, t, f, _, _ = mixed
     _, sels = mixed_batch(cv)
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
-        before = s.covariance_batch(sels, rho=True)
+
+    def calls(s, b):
         o1 = s.nav_state_batch(win, t, f)
         assert np.isfinite(o1[1][o1[2] == 0]).all() and np.isfinite(o1[0]).all()
         ms, launches = s.last_timing()
         assert launches[:3].tolist() == [1, 1, 1] and ms[7] >= ms[1] > 0 and not ms[3:7].any()
         s.nav_state_batch(win, t, cov=False)
-        assert same_bits(s.covariance_batch(sels, rho=True), before)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as fs:
-        fb = [w.copy() for w in ws]
-        fs.set_windows(fb)
-        fs.solve(6, writeback=False)
-        smf = fs.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls, sels)
 
 
 def test_refusals_leave_the_handle_usable(cv):
     """Case 7: CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID for a window id out of range, a frame outside [0, F), a negative n, a NULL win
     / t_ns with n > 0, all three outputs NULL with n > 0; n == 0 is fine; the handle solves afterwards like a fresh one."""
+    import query_harness as qh
     p = cv.capi._p
     w = cv.synth.make_window("tiny", seed=7)
     t = np.array([w.t0_ns + 1], np.int64); win = np.zeros(1, np.int32); fr = np.zeros(1, np.int32)
@@ -323,36 +289,17 @@ def test_refusals_leave_the_handle_usable(cv):
         assert lib.ctvio_nav_state(h, 0, 1, p(t), None, p(x), None, None) == 0
         assert np.array_equal(x, x1[0])
         assert lib.ctvio_nav_state(h, 0, 1, p(t), None, None, None, p(st)) == 0 and st[0] == 0
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_nav_state_matches_python(cv, tmp_path):
     """Case 8: tests/nav_state_demo.cpp through the C++ adaptor: the states and covariances at five times, with the newest bias state and with
     bias state 1, equal the Python call on the same window at the demo's solved state, bit for bit."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "nav_state_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "nav_state_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
+    import query_harness as qh
     w0 = cv.synth.make_window("config1", seed=1005)
-    K, F, L = w0.K, w0.F, w0.L
+    K, F = w0.K, w0.F
     n = 5
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(n)], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("nav_state_demo", tmp_path), w0, tmp_path, 15, n)
     got = []
     for _ in range(2):
         assert rest[0] == 1 and rest[1] == n

@@ -7,7 +7,6 @@ tests' own bound and g = max_a (sum_k |J_ak| sqrt(Sigma_kk))^2 / Pi_aa the ampli
 entry of Sigma becomes at most tol s_a s_b in Pi).  Every check asserts that its bound stays below 1e-4, the size of the smallest modelling error
 the covariance tests are built to catch (leftover damping at radius 1e4)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,17 +14,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import device_reference  # noqa: E402,F401
 
 FRAME_DT = 100_000_000      # synth.py: frame_dt_ns of every configuration used here
-
-
-def device_reference(s, wid, w):
-    """cov_reference over all P unknowns of window wid on the device's own linearisation at its current state."""
-    import cov_helpers as ch
-    H, W, Hll, _, _ = s.linearize(wid)
-    return ch.cov_reference(H, W, Hll, ~ch.constant_mask(w), range(w.P))
 
 
 def check(w, ref, times, cov, st, ext, what, expect=None):
@@ -85,12 +78,8 @@ def test_tiny_initial_state(cv):
 @pytest.fixture(scope="module")
 def config1_solved(cv):
     """`config1` seed 1000 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference)."""
-    w = cv.synth.make_window("config1", seed=1000)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        yield s, b[0], device_reference(s, 0, b[0])
+    for s, w in qh.solved_window(cv, "config1", 1000, 15):
+        yield s, w, device_reference(s, 0, w)
 
 
 def config1_times(w):
@@ -169,23 +158,10 @@ def test_mixed_batch_against_reference(mixed):
 def test_mixed_batch_bits(cv, mixed):
     """Case 4: the bits of a query depend on its window and time alone: the single-window entry, a second call, the reversed order, and calls
     with other counts per window (other tile partners) give the batch call's bits."""
-    from test_gpu_covariance import DET
-    ws, win, t, _, (cov, st) = mixed
-    same = lambda a, b: np.array_equal(a, b, equal_nan=True)
-    with cv.Solver(**DET) as s:
+    ws, win, t, _, out = mixed
+    with cv.Solver(**qh.DET) as s:
         s.set_windows([w.copy() for w in ws])
-        for i in range(len(ws)):
-            idx = np.nonzero(win == i)[0]
-            c1, s1 = s.pose_covariance(i, t[idx])
-            assert same(c1, cov[idx]) and np.array_equal(s1, st[idx]), i
-        c2, s2 = s.pose_covariance_batch(win, t)
-        assert same(c2, cov) and np.array_equal(s2, st)
-        cr, sr = s.pose_covariance_batch(win[::-1].copy(), t[::-1].copy())
-        assert same(cr[::-1], cov) and np.array_equal(sr[::-1], st)
-        n = len(ws)
-        for keep in (np.arange(n), np.arange(2 * n), np.r_[np.arange(n), np.arange(2 * n, 3 * n)]):    # 1 / 2 / the outer 2 of the 3 per window
-            ck, sk = s.pose_covariance_batch(win[keep].copy(), t[keep].copy())
-            assert same(ck, cov[keep]) and np.array_equal(sk, st[keep]), keep
+        qh.check_batch_bits(s.pose_covariance, s.pose_covariance_batch, win, (t,), out, len(ws))
 
 
 def test_cross_check_against_the_selected_block(config1_solved):
@@ -209,35 +185,17 @@ def test_cross_check_against_the_selected_block(config1_solved):
 def test_leaves_the_solve_alone(cv, mixed):
     """Case 6: state bits, graph captures and a following solve are unchanged by the call; ctvio_covariance_batch on the same handle gives
     identical bits before and after it."""
-    from test_gpu_covariance import DET, mixed_batch, same_bits
+    from test_gpu_covariance import mixed_batch
     ws, win, t, _, _ = mixed
     _, sels = mixed_batch(cv)
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
-        before = s.covariance_batch(sels, rho=True)
+
+    def calls(s, b):
         o1 = s.pose_covariance_batch(win, t)
         o2 = s.pose_covariance_batch(win, t, ws[1].q_CI, ws[1].p_CI)
         assert np.isfinite(o1[0][o1[1] == 0]).all() and np.isfinite(o2[0][o2[1] == 0]).all()
         ms, launches = s.last_timing()
         assert launches[:3].tolist() == [1, 1, 1] and ms[7] >= ms[1] > 0
-        assert same_bits(s.covariance_batch(sels, rho=True), before)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as f:
-        fb = [w.copy() for w in ws]
-        f.set_windows(fb)
-        f.solve(6, writeback=False)
-        smf = f.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls, sels)
 
 
 def test_refusals_leave_the_handle_usable(cv):
@@ -274,36 +232,16 @@ def test_refusals_leave_the_handle_usable(cv):
         assert lib.ctvio_pose_covariance(h, 0, 1, p(t), p(q), p(pp), p(cov), None) == 0          # status may be NULL
         c1, s1 = s.pose_covariance(0, t)
         assert s1[0] == 0 and np.array_equal(c1[0].ravel(), cov)                                   # (identity extrinsic: the body pose's bits)
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_pose_covariance_matches_python(cv, tmp_path):
     """Case 8: tests/pose_covariance_demo.cpp through the C++ adaptor: the body and camera pose covariances at five times equal the Python
     call on the same window at the demo's solved state, bit for bit."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "pose_covariance_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "pose_covariance_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
     K, F, L = w0.K, w0.F, w0.L
     n = 5
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(n)], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("pose_covariance_demo", tmp_path), w0, tmp_path, 15, n)
     assert rest[0] == 1 and rest[1] == n
     body_cpp = rest[2:2 + 36 * n].reshape(n, 6, 6)
     rest = rest[2 + 36 * n:]

@@ -17,17 +17,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import device_joint_reference as device_reference  # noqa: E402,F401
 
 EPS = 2.0 ** -53
 ROW_MODEL = (460.0, 240.0, 480, 3)
 FIELDS = ("state", "proj", "cov", "chi2", "row", "status")
-
-
-def device_reference(s, wid, w):
-    from test_gpu_landmark_points import device_reference as dr
-    return dr(s, wid, w)
 
 
 def draw(w, m, seed, t_start=None):
@@ -119,7 +115,7 @@ def take(out, idx):
 
 
 def same(a, b, fields=FIELDS):
-    return all((getattr(a, f) is None and getattr(b, f) is None) or np.array_equal(getattr(a, f), getattr(b, f), equal_nan=True) for f in fields)
+    return qh.same_bits(a, b, fields)
 
 
 def batch_call(s, win, preds, pts, **kw):
@@ -173,12 +169,8 @@ def test_tiny_initial_state(cv):
 def config1_solved(cv):
     """`config1` seed 1000 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference, one
     21-sample prediction from the newest frame time)."""
-    w = cv.synth.make_window("config1", seed=1000)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        yield s, b[0], device_reference(s, 0, b[0]), (None,) + draw(w, 21, 1000)
+    for s, w in qh.solved_window(cv, "config1", 1000, 15):
+        yield s, w, device_reference(s, 0, w), (None,) + draw(w, 21, 1000)
 
 
 def test_config1_solved(config1_solved):
@@ -378,13 +370,9 @@ def test_mixed_batch_bits(cv, mixed, monkeypatch):
 
 def test_leaves_the_solve_alone(cv, mixed):
     """Case 5: state bits, graph captures and a following solve are unchanged by the calls; the timing slots of both calls."""
-    from test_gpu_covariance import DET
     ws, win, preds, pts, R, obs, out = mixed
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
+
+    def calls(s, b):
         o1 = batch_call(s, win, preds, pts, obs=obs)
         assert np.isfinite(o1.cov[o1.status == 0]).all() and np.isfinite(o1.proj[o1.status != 3]).all()
         ms, launches = s.last_timing()
@@ -393,20 +381,7 @@ def test_leaves_the_solve_alone(cv, mixed):
         ms, launches = s.last_timing()
         assert launches[:4].tolist() == [0, 0, 1, 1] and ms[7] >= ms[2] > 0 and ms[3] > 0
         assert np.array_equal(o2.proj, o1.proj, equal_nan=True) and np.array_equal(o2.row, o1.row) and np.array_equal(o2.state, o1.state)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as f:
-        fb = [w.copy() for w in ws]
-        f.set_windows(fb)
-        f.solve(6, writeback=False)
-        smf = f.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls)
 
 
 def test_refusals_leave_the_handle_usable(cv):

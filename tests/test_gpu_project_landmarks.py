@@ -8,7 +8,6 @@ symmetric to the bit with a positive diagonal and cov_metric <= 4 kappa_s 2^-53 
 covariance, the bound itself below 1e-2; chi2 against the extended-precision value from the returned proj3 / cov4 / obs2 at relative
 16 kappa_2(Cov + I / img_w^2) 2^-53."""
 import os
-import subprocess
 import sys
 from types import SimpleNamespace
 
@@ -17,8 +16,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import device_joint_reference as device_reference  # noqa: E402,F401
 
 EPS = 2.0 ** -53
 ROW_MODEL = (460.0, 240.0, 480, 3)
@@ -28,11 +28,6 @@ ROW_MODEL = (460.0, 240.0, 480, 3)
 # Such a query is recognised on the REFERENCE (its covariance below CANCELLED times the size it would have without cancellation) and the
 # device's block is held to the same ceiling instead of the relative bound; only the fix_ld variant may contain any.
 CANCELLED = 1e-18
-
-
-def device_reference(s, wid, w):
-    from test_gpu_landmark_points import device_reference as dr
-    return dr(s, wid, w)
 
 
 def frames_of(w):
@@ -150,14 +145,10 @@ def config1_queries(w):
 def config1_solved(cv):
     """`config1` seed 1000 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference, the
     queries, their references)."""
-    w = cv.synth.make_window("config1", seed=1000)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        ref = device_reference(s, 0, b[0])
-        Q = config1_queries(b[0])
-        yield s, b[0], ref, Q, references(b[0], ref, Q)
+    for s, w in qh.solved_window(cv, "config1", 1000, 15):
+        ref = device_reference(s, 0, w)
+        Q = config1_queries(w)
+        yield s, w, ref, Q, references(w, ref, Q)
 
 
 def test_config1_solved(config1_solved):
@@ -280,7 +271,7 @@ def take(out, idx):
 
 
 def same(a, b):
-    return all(np.array_equal(getattr(a, f), getattr(b, f), equal_nan=True) for f in ("proj", "cov", "chi2", "row", "status"))
+    return qh.same_bits(a, b, ("proj", "cov", "chi2", "row", "status"))
 
 
 def test_mixed_batch_against_reference(mixed):
@@ -346,16 +337,12 @@ def test_row_model(cv, config1_solved):
 def test_leaves_the_solve_alone(cv, mixed):
     """State bits, graph captures and a following solve are unchanged by the calls; ctvio_covariance_batch on the same handle gives identical bits
     before and after them; the timing slots of both calls."""
-    from test_gpu_covariance import DET, mixed_batch, same_bits
+    from test_gpu_covariance import mixed_batch
     ws, win, Q, R, obs, out = mixed
     _, sels = mixed_batch(cv)
     l, t, row = cols(Q)
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
-        before = s.covariance_batch(sels, rho=True)
+
+    def calls(s, b):
         o1 = s.project_landmarks_batch(win, l, t, row, obs=obs)
         assert np.isfinite(o1.cov[o1.status == 0]).all() and np.isfinite(o1.proj[o1.status != 3]).all()
         ms, launches = s.last_timing()
@@ -364,21 +351,7 @@ def test_leaves_the_solve_alone(cv, mixed):
         ms, launches = s.last_timing()
         assert launches[:3].tolist() == [0, 0, 1] and ms[7] >= ms[2] > 0
         assert np.array_equal(o2.proj, o1.proj, equal_nan=True) and np.array_equal(o2.row, o1.row)
-        assert same_bits(s.covariance_batch(sels, rho=True), before)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as f:
-        fb = [w.copy() for w in ws]
-        f.set_windows(fb)
-        f.solve(6, writeback=False)
-        smf = f.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls, sels)
 
 
 def test_refusals_leave_the_handle_usable(cv):
@@ -427,35 +400,15 @@ def test_refusals_leave_the_handle_usable(cv):
         o = s.project_landmarks(0, lm, t, row, obs=obs, row_model=rm)
         assert np.array_equal(o.proj, proj) and np.array_equal(o.cov.ravel(), cov.ravel()) and np.array_equal(o.chi2, chi)
         assert np.array_equal(o.row, ro) and np.array_equal(o.status, st)
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_project_landmarks_matches_python(cv, tmp_path):
     """tests/project_landmarks_demo.cpp through the C++ adaptor: predictions, covariances, gates and statuses of every block's own observation
     equal the Python call on the same window at the demo's solved state, bit for bit."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "project_landmarks_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "project_landmarks_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
     K, F, L, V = w0.K, w0.F, w0.L, w0.V
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15"], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("project_landmarks_demo", tmp_path), w0, tmp_path, 15)
     assert rest[0] == 1 and rest[1] == V
     proj_cpp = rest[2:2 + 3 * V].reshape(V, 3)
     cov_cpp = rest[2 + 3 * V:2 + 7 * V].reshape(V, 2, 2)

@@ -11,7 +11,6 @@ R_ab for R_ab^T, the wrong frame for dp, a missing overlap sum.
 Measured on an MI355X over cases 1 to 5: worst error 1.1e-6 at its bound 1.8e-5 (`tiny`, initial state); largest bound 6.1e-4 (DESIGN.md
 section 6 has every case)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,19 +18,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import device_reference  # noqa: E402,F401
 
 FRAME_DT = 100_000_000      # synth.py: frame_dt_ns of every configuration used here
 EXT = (np.array([0.1, -0.2, 0.3, 0.9]) / np.linalg.norm([0.1, -0.2, 0.3, 0.9]), np.array([0.05, -0.02, 0.1]))
 BODY = (None, None)
-
-
-def device_reference(s, wid, w):
-    """cov_reference over all P unknowns of window wid on the device's own linearisation at its current state."""
-    import cov_helpers as ch
-    H, W, Hll, _, _ = s.linearize(wid)
-    return ch.cov_reference(H, W, Hll, ~ch.constant_mask(w), range(w.P))
 
 
 def check(w, ref, pairs, ext, rel, cov, st, what, expect=None):
@@ -109,12 +102,8 @@ def test_tiny_initial_state(cv):
 @pytest.fixture(scope="module")
 def config1_solved(cv):
     """`config1` seed 1000 after a 15-iteration solve on an open handle: (solver, the window at the solved state, the device reference)."""
-    w = cv.synth.make_window("config1", seed=1000)
-    with cv.Solver() as s:
-        b = [w.copy()]
-        s.set_windows(b)
-        s.solve(15)
-        yield s, b[0], device_reference(s, 0, b[0])
+    for s, w in qh.solved_window(cv, "config1", 1000, 15):
+        yield s, w, device_reference(s, 0, w)
 
 
 def test_config1_solved_frame_pairs(config1_solved):
@@ -191,20 +180,10 @@ def test_mixed_batch_against_reference(mixed):
 def test_mixed_batch_bits(cv, mixed):
     """Case 4: the bits of a query depend on its window and its two times alone: the single-window entry, a second call, the reversed order, and
     calls with other counts per window (another tile partner, or none) give the batch call's bits."""
-    from test_gpu_covariance import DET
     ws, win, ta, tb, _, out = mixed
-    same = lambda a, b: all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-    with cv.Solver(**DET) as s:
+    with cv.Solver(**qh.DET) as s:
         s.set_windows([w.copy() for w in ws])
-        for i in range(len(ws)):
-            idx = np.nonzero(win == i)[0]
-            assert same(s.relative_pose(i, ta[idx], tb[idx]), [o[idx] for o in out]), i
-        assert same(s.relative_pose_batch(win, ta, tb), out)
-        rev = s.relative_pose_batch(win[::-1].copy(), ta[::-1].copy(), tb[::-1].copy())
-        assert same([o[::-1] for o in rev], out)
-        n = len(ws)
-        for keep in (np.arange(n), np.arange(2 * n), np.r_[np.arange(n), np.arange(2 * n, 3 * n)]):    # 1 / 2 / the outer 2 of the 3 per window
-            assert same(s.relative_pose_batch(win[keep].copy(), ta[keep].copy(), tb[keep].copy()), [o[keep] for o in out]), keep
+        qh.check_batch_bits(s.relative_pose, s.relative_pose_batch, win, (ta, tb), out, len(ws))
 
 
 def test_cross_checks(config1_solved):
@@ -252,35 +231,17 @@ def test_cross_checks(config1_solved):
 def test_leaves_the_solve_alone(cv, mixed):
     """Case 6: state bits, graph captures and a following solve are unchanged by the call; ctvio_covariance_batch on the same handle gives
     identical bits before and after it; last_timing reports one launch of each of the three kernels."""
-    from test_gpu_covariance import DET, mixed_batch, same_bits
+    from test_gpu_covariance import mixed_batch
     ws, win, ta, tb, _, _ = mixed
     _, sels = mixed_batch(cv)
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
-        before = s.covariance_batch(sels, rho=True)
+
+    def calls(s, b):
         o1 = s.relative_pose_batch(win, ta, tb)
         assert np.isfinite(o1[1][o1[2] == 0]).all() and np.isfinite(o1[0]).all()
         ms, launches = s.last_timing()
         assert launches[:3].tolist() == [1, 1, 1] and ms[7] >= ms[1] > 0 and not ms[3:7].any()
         s.relative_pose_batch(win, ta, tb, cov=False)
-        assert same_bits(s.covariance_batch(sels, rho=True), before)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as fs:
-        fb = [w.copy() for w in ws]
-        fs.set_windows(fb)
-        fs.solve(6, writeback=False)
-        smf = fs.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
-        assert x.ld == y.ld
+    qh.check_leaves_the_solve_alone(cv, ws, calls, sels)
 
 
 def test_refusals_leave_the_handle_usable(cv):
@@ -328,36 +289,16 @@ def test_refusals_leave_the_handle_usable(cv):
         assert lib.ctvio_relative_pose(h, 0, 1, p(ta), p(tb), None, None, p(x), None, None) == 0
         assert np.array_equal(x, x1[0])
         assert lib.ctvio_relative_pose(h, 0, 1, p(ta), p(tb), None, None, None, None, p(st)) == 0 and st[0] == 0
-        b = [w.copy()]
-        s.set_windows(b)
-        sm = s.solve(15)[0]
-    with cv.Solver() as f:
-        fb = [w.copy()]
-        f.set_windows(fb)
-        assert f.solve(15)[0] == sm
-    assert np.array_equal(b[0].pos, fb[0].pos) and np.array_equal(b[0].quat, fb[0].quat)
+        qh.check_usable_after(cv, w, s)
 
 
 def test_adaptor_relative_pose_matches_python(cv, tmp_path):
     """Case 8: tests/relative_pose_demo.cpp through the C++ adaptor: the increments and covariances of five pairs, body and camera, equal the
     Python call on the same window at the demo's solved state, bit for bit."""
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "relative_pose_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "relative_pose_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
     w0 = cv.synth.make_window("config1", seed=1005)
     K, F, L = w0.K, w0.F, w0.L
     n = 5
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(n)], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
-    kn = arr[:7 * K].reshape(K, 7)
-    wa = w0.copy()
-    wa.quat, wa.pos = kn[:, :4].copy(), kn[:, 4:].copy()
-    wa.bias = arr[7 * K:7 * K + 6 * F].reshape(F, 6).copy()
-    wa.rho = arr[7 * K + 6 * F:7 * K + 6 * F + L].copy()
-    wa.ld = float(arr[7 * K + 6 * F + L])
-    rest = arr[7 * K + 6 * F + L + 3:]
+    wa, rest = qh.run_demo(qh.build_demo("relative_pose_demo", tmp_path), w0, tmp_path, 15, n)
     got = []
     for _ in range(2):
         assert rest[0] == 1 and rest[1] == n

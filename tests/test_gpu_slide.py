@@ -11,7 +11,6 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 
@@ -38,11 +37,9 @@ def test_three_windows_through_the_c_abi(cv, slide_reference):
 
 def test_three_windows_through_the_cpp_adaptor(cv, slide_reference, tmp_path):
     sh, world, st_o, rec_o = slide_reference
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "slide_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "slide_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
-    _dump(world, str(tmp_path / "world.txt"))
+    import query_harness as qh
+    exe = qh.build_demo("slide_demo", tmp_path)
+    qh._dump(world, str(tmp_path / "world.txt"))
     out = subprocess.check_output([exe, str(tmp_path / "world.txt"), str(tmp_path / "out.txt")], text=True)
     assert out.count("ctvio: iterations") == 3 and "ResidualSummary" in out and "- Image: num =" in out, out
     for k, r in enumerate(rec_o[:-1]):

@@ -10,7 +10,6 @@ itself below 1e-2; redundancy within visgate_helpers.redundancy_bound; chi2 agai
 at relative 16 kappa_2(C_loo + I) 2^-53.  Per landmark: the count, the mean against the NumPy sum of the returned per-block values within
 lm_count 2^-52 relative, max and min bit-equal to the extremes of the returned per-block arrays."""
 import os
-import subprocess
 import sys
 from types import SimpleNamespace
 
@@ -19,18 +18,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import query_harness as qh  # noqa: E402
+from query_harness import DET, device_joint_reference as device_reference  # noqa: E402,F401
 
 EPS = 2.0 ** -53
-DET = dict(deterministic=2)
 FIELDS = ("res", "weight", "depth", "redundancy", "cov", "chi2", "status", "lm_stats", "lm_count")
 VALUES = ("res", "weight", "depth", "lm_count")
-
-
-def device_reference(s, wid, w):
-    from test_gpu_landmark_points import device_reference as dr
-    return dr(s, wid, w)
 
 
 def references(w, ref, min_red=0.01):
@@ -39,7 +33,7 @@ def references(w, ref, min_red=0.01):
 
 
 def same(a, b, fields=FIELDS):
-    return all(np.array_equal(getattr(a, f), getattr(b, f), equal_nan=True) for f in fields)
+    return qh.same_bits(a, b, fields)
 
 
 def take(o, vs, ls):
@@ -251,11 +245,8 @@ def test_leaves_the_solve_alone(cv, golden_dir):
     ctvio_project_landmarks of the blocks' own (l, t_j, row_j) within the value bound."""
     import projection_helpers as pr
     ws = mixed_windows(cv, golden_dir)[:2]
-    with cv.Solver(**DET) as s:
-        b = [w.copy() for w in ws]
-        s.set_windows(b)
-        s.solve(6, writeback=False)
-        cap, state = s.graph_captures, s.get_batch_state()
+
+    def calls(s, b):
         o1 = s.visual_gate_batch()
         ms, launches = s.last_timing()
         assert launches[:4].tolist() == [1, 1, 1, 1] and ms[7] >= ms[1] > 0 and ms[2] > 0 and ms[3] > 0
@@ -263,8 +254,9 @@ def test_leaves_the_solve_alone(cv, golden_dir):
         ms, launches = s.last_timing()
         assert launches[:4].tolist() == [0, 0, 1, 0] and ms[7] >= ms[2] > 0
         assert same(o1, o2, VALUES)
-        assert s.graph_captures == cap
-        assert all(np.array_equal(x, y) for x, y in zip(state, s.get_batch_state()))
+        return o1
+
+    def cross_checks(s, b, o1):
         s.writeback_all()
         v0 = 0
         for i, w in enumerate(b):
@@ -273,17 +265,7 @@ def test_leaves_the_solve_alone(cv, golden_dir):
                 txy, _ = pr.value_atol(w, pl.proj[v])
                 assert (np.abs(o1.res[v0 + v] - w.img_w * (pl.proj[v, :2] - w.v_pj[v])) <= w.img_w * txy).all(), (i, v)
             v0 += w.V
-        sm = s.solve(6)
-        assert s.graph_captures == cap
-    with cv.Solver(**DET) as f:
-        fb = [w.copy() for w in ws]
-        f.set_windows(fb)
-        f.solve(6, writeback=False)
-        smf = f.solve(6)
-    assert sm == smf
-    for x, y in zip(b, fb):
-        for a in ("quat", "pos", "bias", "rho"):
-            assert np.array_equal(getattr(x, a), getattr(y, a)), a
+    qh.check_leaves_the_solve_alone(cv, ws, calls, compare_ld=False, then=cross_checks)
 
 
 def test_callers_block_order(cv, golden_dir):

@@ -2,23 +2,16 @@
 moves one observation by 30 pixel-equivalents (a wrong match), solves again and runs the leave-one-out test: that block has the largest chi2
 of its window, far beyond the 99.9 % point of chi-square with 2 degrees of freedom, and its landmark reports it; per-factor results come in
 the order of the AddImageFeatureDelayAnalytic calls, per-landmark results keyed by the inverse-depth pointer."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 PIXEL = 1.0 / 460.0      # one pixel in normalised image units at the focal length the row model of the other demos uses
 
 
 def test_perturbed_observation_has_the_largest_chi2(cv, tmp_path):
-    from test_gpu_adaptor import _dump
-    exe = str(tmp_path / "visual_gate_demo")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(HERE, "visual_gate_demo.cpp"),
-                           "-L", os.path.join(ROOT, "ctrl-vio_amd"), "-lctvio", "-Wl,-rpath," + os.path.join(ROOT, "ctrl-vio_amd"), "-o", exe])
+    import query_harness as qh
     w0 = cv.synth.make_window("config1", seed=1005)
     L, V = w0.L, w0.V
     counts = np.bincount(w0.v_lm, minlength=L)
@@ -26,9 +19,7 @@ def test_perturbed_observation_has_the_largest_chi2(cv, tmp_path):
     assert counts[l_bad] >= 4
     vs = np.nonzero(w0.v_lm == l_bad)[0]
     bad = int(vs[len(vs) // 2])
-    _dump(w0, str(tmp_path / "in.txt"))
-    subprocess.run([exe, str(tmp_path / "in.txt"), str(tmp_path / "out.txt"), "15", str(bad), repr(30 * PIXEL)], check=True, timeout=120)
-    arr = np.array(open(tmp_path / "out.txt").read().split(), float)
+    _, arr = qh.run_demo(qh.build_demo("visual_gate_demo", tmp_path), w0, tmp_path, 15, bad, repr(30 * PIXEL), state=False)
     assert arr[1] == V
     chi2 = arr[2:2 + V]; status = arr[2 + V:2 + 2 * V]; res = arr[2 + 2 * V:2 + 4 * V].reshape(V, 2)
     rest = arr[2 + 4 * V:]
