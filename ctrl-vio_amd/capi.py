@@ -90,6 +90,11 @@ class GateOptions(C.Structure):
     _fields_ = [("min_redundancy", C.c_double)]
 
 
+class CullOptions(C.Structure):
+    _fields_ = [("min_redundancy", C.c_double), ("chi2_max", C.c_double), ("mean_error_max", C.c_double),
+                ("worst_only", C.c_int32), ("drop_uncomputable", C.c_int32)]
+
+
 # every symbol include/ctvio.h declares (tests check the .so exports all of them)
 SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "ctvio_device_count", "ctvio_create",
            "ctvio_destroy", "ctvio_clear", "ctvio_add_window", "ctvio_upload", "ctvio_set_batch", "ctvio_num_windows", "ctvio_solve",
@@ -102,6 +107,8 @@ SYMBOLS = ["ctvio_default_options", "ctvio_status_string", "ctvio_last_error", "
            "ctvio_default_imu_noise", "ctvio_imu_predict_batch", "ctvio_imu_predict", "ctvio_body_rates_batch", "ctvio_body_rates",
            "ctvio_predict_landmarks_batch", "ctvio_predict_landmarks",
            "ctvio_default_gate_options", "ctvio_visual_gate_batch", "ctvio_visual_gate", "ctvio_imu_gate_batch", "ctvio_imu_gate",
+           "ctvio_set_visual_active_batch", "ctvio_set_visual_active", "ctvio_get_visual_active_batch", "ctvio_get_visual_active",
+           "ctvio_default_cull_options", "ctvio_cull_visual_batch", "ctvio_cull_visual",
            "ctvio_default_triangulate_options", "ctvio_triangulate_batch", "ctvio_triangulate", "ctvio_shift_anchor_batch"]
 
 _lib = None
@@ -174,6 +181,14 @@ def load_library():
         lib.ctvio_visual_gate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GateOptions)] + [C.c_void_p] * 9
         lib.ctvio_imu_gate_batch.argtypes = [C.c_void_p, C.POINTER(GateOptions)] + [C.c_void_p] * 6
         lib.ctvio_imu_gate.argtypes = [C.c_void_p, C.c_int32, C.POINTER(GateOptions)] + [C.c_void_p] * 6
+        lib.ctvio_set_visual_active_batch.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ctvio_set_visual_active.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        lib.ctvio_get_visual_active_batch.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ctvio_get_visual_active.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        lib.ctvio_default_cull_options.argtypes = [C.POINTER(CullOptions)]
+        lib.ctvio_default_cull_options.restype = None
+        lib.ctvio_cull_visual_batch.argtypes = [C.c_void_p, C.POINTER(CullOptions), C.c_void_p, C.c_void_p]
+        lib.ctvio_cull_visual.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CullOptions), C.c_void_p, C.c_void_p]
         lib.ctvio_default_triangulate_options.argtypes = [C.POINTER(TriangulateOptions)]
         lib.ctvio_default_triangulate_options.restype = None
         lib.ctvio_triangulate_batch.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.c_void_p, C.c_void_p]

@@ -1164,13 +1164,13 @@ class SolverImpl {
     const WinMeta &m = meta_[id];
     const size_t n = (size_t)14 + m.pn;
     CallLayout io = head_;
-    const int s_out = io.add("sums", sizeof(double), n, true);
+    const int s_out = io.add("sums", sizeof(double), n + 1, true);   // (+ the number of active visual blocks)
     if (const int rc = reserve_call(io)) return rc;
     hipLaunchKernelGGL(k_residual_summary, dim3(1), dim3(256), (size_t)(14 + 2 * m.pn) * sizeof(double), stream_, dev_, id, io_dev<double>(io, s_out));
-    HIPCHK(hipMemcpyAsync(io_host<double>(io, s_out), io_dev<double>(io, s_out), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(io_host<double>(io, s_out), io_dev<double>(io, s_out), sizeof(double) * (n + 1), hipMemcpyDeviceToHost, stream_));
     if (const int rc = sync_call()) return rc;
     std::memcpy(sums, io_host<double>(io, s_out), sizeof(double) * n);
-    if (counts4) { counts4[0] = m.M; counts4[1] = m.NB; counts4[2] = m.V; counts4[3] = m.pn > 0 ? 1 : 0; }
+    if (counts4) { counts4[0] = m.M; counts4[1] = m.NB; counts4[2] = (int32_t)io_host<double>(io, s_out)[n]; counts4[3] = m.pn > 0 ? 1 : 0; }
     return CTVIO_OK;
   }
   int gauge_restore(int n, const int32_t *ids, const int32_t *knot, const double *q0, const double *t0) {
@@ -1394,12 +1394,16 @@ class SolverImpl {
   // run_query for a gate; slot0: the WinMeta member that holds a window's first slot.  Values only: record(x, s0, nall) over every slot at
   // once and reduce(x), both in ms[2].  Otherwise one factorisation, then per slice record(x, first slot, slots) and solve(x, slice,
   // first slot, slots) -- the first slice's record kernel is the timed one (ms[2]), the later slices' fall inside ms[1] --, then
-  // reduce(x) (ms[3]).
-  template <class Record, class Solve, class Reduce>
+  // reduce(x) (ms[3]) and, in a full call that acts on the results (act: ctvio_cull_visual), act(x) behind it (ms[4]).
+  struct NoAct { void operator()(QueryRun &) const {} };
+  template <class Record, class Solve, class Reduce, class Act = NoAct>
   int run_gate(const CallLayout &io, int s_in, int s_out, const CovScratch *scr, const GateSlices &gs, int32_t WinMeta::*slot0, int s0, int nall, Record &&record,
-               Solve &&solve, Reduce &&reduce) {
-    return run_query(io, s_in, s_out, scr, {{2, EV_COV_SOLVE, EV_COV_GRAM}},
-                     {span_prepare(), {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}}, [&](QueryRun &x) {
+               Solve &&solve, Reduce &&reduce, Act &&act = Act()) {
+    constexpr bool acts = !std::is_same<typename std::decay<Act>::type, NoAct>::value;
+    const Spans full = {span_prepare(), {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END}};
+    const Spans full_act = {span_prepare(), {1, EV_COV_GRAM, EV_QUERY_BEGIN}, {2, EV_COV_SOLVE, EV_COV_GRAM}, {3, EV_QUERY_BEGIN, EV_QUERY_END},
+                            {4, EV_QUERY_END, EV_CALL_END}};   // (run_query marks EV_CALL_END right behind the launches of a full call)
+    return run_query(io, s_in, s_out, scr, {{2, EV_COV_SOLVE, EV_COV_GRAM}}, acts ? full_act : full, [&](QueryRun &x) {
                        if (!x.excl) {
                          if (nall) record(x, s0, nall);
                          reduce(x);
@@ -1415,6 +1419,7 @@ class SolverImpl {
                        x.mark(EV_QUERY_BEGIN);
                        reduce(x);
                        x.mark(EV_QUERY_END);
+                       act(x);
                      });
   }
   int covariance(int only, const int32_t *n_sel, const int32_t *sel, double *cov, double *var_rho, int32_t *singular) {
@@ -1920,8 +1925,12 @@ class SolverImpl {
   // block order (gate_slot_).  Values only (redundancy, cov4, chi2 and lm_stats3 null): k_cov_gate_jac alone (and k_cov_gate_reduce for
   // lm_count), nothing is linearised or factored.  Otherwise run_gate: per slice of windows k_cov_gate_jac and k_cov_solve<COV_GATE> (kind
   // TILE_GATE), then k_cov_gate_reduce.
+  // ctvio_cull_visual_batch / ctvio_cull_visual are the same call with `cull`: always full, every gate output stays on the device, and
+  // k_vis_cull behind the reduction decides on them and updates Dev::v_on; what comes back is culled | flags by slot.
+  static constexpr GateCodes VIS_GATE_CODES{QUERY_OK, GATE_WEAK, QUERY_SINGULAR, QUERY_NO_INFO, GATE_INACTIVE};
+  struct CullCall { CullRules rules; int32_t *n_culled; uint8_t *active; };
   int visual_gate(int only, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *red, double *cov4, double *chi2, int32_t *status,
-                  double *lm_stats3, int32_t *lm_count) {
+                  double *lm_stats3, int32_t *lm_count, const CullCall *cull = nullptr) {
     if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
     if (!o) return fail(CTVIO_ERR_INVALID, "null options");
     if (!(o->min_redundancy > 0.0 && o->min_redundancy < 1.0)) return fail(CTVIO_ERR_INVALID, "min_redundancy outside (0, 1)");
@@ -1930,48 +1939,69 @@ class SolverImpl {
     const size_t v0 = gate_voff_[(size_t)wbeg], V = gate_voff_[(size_t)wend] - v0;
     size_t L = 0;
     for (int w = wbeg; w < wend; ++w) L += (size_t)meta_[w].L;
-    if (V && !res2 && !weight && !depth && !red && !cov4 && !chi2 && !status && !lm_stats3 && !lm_count) return fail(CTVIO_ERR_INVALID, "every output is null");
+    if (V && !cull && !res2 && !weight && !depth && !red && !cov4 && !chi2 && !status && !lm_stats3 && !lm_count) return fail(CTVIO_ERR_INVALID, "every output is null");
     const double nan = std::nan(""), inf = std::numeric_limits<double>::infinity();
     if (V == 0) {   // (nothing is launched; a landmark without blocks: count 0 and (NaN, 0, +inf))
       for (size_t l = 0; l < L; ++l) {
         if (lm_count) lm_count[l] = 0;
         if (lm_stats3) { lm_stats3[3 * l] = nan; lm_stats3[3 * l + 1] = 0.0; lm_stats3[3 * l + 2] = inf; }
       }
+      if (cull && cull->n_culled) std::fill(cull->n_culled, cull->n_culled + (wend - wbeg), 0);
       return CTVIO_OK;
     }
-    const bool full = red || cov4 || chi2 || lm_stats3, want_lm = lm_stats3 || lm_count;
+    const bool full = cull || red || cov4 || chi2 || lm_stats3, want_lm = cull || lm_stats3 || lm_count, want_stats = cull || lm_stats3;
     const GateSlices gs = gate_slices(&WinMeta::Vp, wbeg, wend, GATE_SLICE_SLOTS);
     // ---- out, by block slot: res2 | weight | depth | redundancy | cov4 | chi2 | status, then by landmark: lm_stats3 | lm_count; no inputs
     const size_t ns = (size_t)nslot, nf = full ? ns : 0, nl = want_lm ? L : 0;
     CovScratch scr(full, (size_t)dev_.Utot, sizeof(GateRec), gs.nrec);
-    const int s_en = scr.lay.add("enorm", sizeof(double), lm_stats3 ? ns : 0, true);
+    const int s_en = scr.lay.add("enorm", sizeof(double), want_stats ? ns : 0, true);
     CallLayout io = head_;
     const int s_res = io.add("res2", sizeof(double), 2 * ns, true), s_wgt = io.add("weight", sizeof(double), ns, true),
               s_dep = io.add("depth", sizeof(double), ns, true), s_red = io.add("redundancy", sizeof(double), nf, true),
               s_cov = io.add("cov4", sizeof(double), 4 * nf, true), s_chi = io.add("chi2", sizeof(double), nf, true),
-              s_stat = io.add("status", sizeof(int32_t), ns, false), s_lms = io.add("lm_stats3", sizeof(double), lm_stats3 ? 3 * L : 0, true),
-              s_lmc = io.add("lm_count", sizeof(int32_t), nl, false);
+              s_stat = io.add("status", sizeof(int32_t), ns, false), s_lms = io.add("lm_stats3", sizeof(double), want_stats ? 3 * L : 0, true),
+              s_lmc = io.add("lm_count", sizeof(int32_t), nl, false), s_cul = io.add("culled", 1, cull ? ns : 0, false),
+              s_flg = io.add("flags", 1, cull ? ns : 0, false);
     if (const int rc = reserve_call(io, full ? &scr.lay : nullptr)) return rc;
-    GateOut out{io_dev<double>(io, s_res), io_dev<double>(io, s_wgt), io_dev<double>(io, s_dep), lm_stats3 ? scr.lay.at<double>(call_scr_.dev, s_en) : nullptr,
+    GateOut out{io_dev<double>(io, s_res), io_dev<double>(io, s_wgt), io_dev<double>(io, s_dep), want_stats ? scr.lay.at<double>(call_scr_.dev, s_en) : nullptr,
                 full ? io_dev<double>(io, s_red) : nullptr, full ? io_dev<double>(io, s_cov) : nullptr, full ? io_dev<double>(io, s_chi) : nullptr,
                 io_dev<int32_t>(io, s_stat), s0, 0, o->min_redundancy};
-    const int rc = run_gate(
-        io, s_res, s_res, full ? &scr : nullptr, gs, &WinMeta::vis0, s0, nslot,
-        [&](QueryRun &x, int first, int n) {
-          hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, x.excl, x.rec<GateRec>(), out);
-        },
-        [&](QueryRun &x, size_t, int first, int n) {
-          CovSolveIO<COV_GATE> a;
-          a.rec = x.rec<GateRec>(); a.slot_base = first; a.gate = out; a.gate.nslot = n;
-          launch_cov_solve(x.c, (size_t)nblk(n, PRJ_PER_TILE), a);
-        },
-        [&](QueryRun &) {
-          if (want_lm)
-            hipLaunchKernelGGL(k_cov_gate_reduce, dim3(nblk((int)L, 64)), dim3(64), 0, stream_, dev_, l0, (int)L, out, full ? 1 : 0,
-                               lm_stats3 ? io_dev<double>(io, s_lms) : nullptr, io_dev<int32_t>(io, s_lmc));
-        });
+    const auto record = [&](QueryRun &x, int first, int n) {
+      hipLaunchKernelGGL(k_cov_gate_jac, dim3(nblk(n, 64)), dim3(64), 0, stream_, dev_, first, n, x.excl, x.rec<GateRec>(), out);
+    };
+    const auto solve = [&](QueryRun &x, size_t, int first, int n) {
+      CovSolveIO<COV_GATE> a;
+      a.rec = x.rec<GateRec>(); a.slot_base = first; a.gate = out; a.gate.nslot = n;
+      launch_cov_solve(x.c, (size_t)nblk(n, PRJ_PER_TILE), a);
+    };
+    const auto reduce = [&](QueryRun &) {
+      if (want_lm && L)
+        hipLaunchKernelGGL(k_cov_gate_reduce, dim3(nblk((int)L, 64)), dim3(64), 0, stream_, dev_, l0, (int)L, out, full ? 1 : 0,
+                           want_stats ? io_dev<double>(io, s_lms) : nullptr, io_dev<int32_t>(io, s_lmc));
+    };
+    if (cull) {
+      // (no inputs; culled | flags come back)
+      const int rc = run_gate(io, s_cul, s_cul, &scr, gs, &WinMeta::vis0, s0, nslot, record, solve, reduce, [&](QueryRun &) {
+        if (L)
+          hipLaunchKernelGGL(k_vis_cull, dim3(nblk((int)L, 64)), dim3(64), 0, stream_, dev_, l0, (int)L, out, cull->rules, io_dev<double>(io, s_lms),
+                             io_dev<int32_t>(io, s_lmc), io_dev<uint8_t>(io, s_cul), io_dev<uint8_t>(io, s_flg));
+      });
+      if (rc) return rc;
+      const uint8_t *hcul = io_host<uint8_t>(io, s_cul), *hflg = io_host<uint8_t>(io, s_flg);
+      for (int w = wbeg; w < wend; ++w) {
+        int32_t nc = 0;
+        for (size_t b = gate_voff_[(size_t)w]; b < gate_voff_[(size_t)w + 1]; ++b) {
+          const size_t k = (size_t)(gate_slot_[b] - s0);
+          nc += hcul[k];
+          if (cull->active) cull->active[b - v0] = hflg[k];
+        }
+        if (cull->n_culled) cull->n_culled[w - wbeg] = nc;
+      }
+      return CTVIO_OK;
+    }
+    const int rc = run_gate(io, s_res, s_res, full ? &scr : nullptr, gs, &WinMeta::vis0, s0, nslot, record, solve, reduce);
     if (rc) return rc;
-    // ---- results, in the caller's block order.  Precedence 3, 2, 1 (the window's factorisation failed), 4, 0.
+    // ---- results, in the caller's block order.  Precedence 3, 2, 1 (the window's factorisation failed), 5 (inactive), 4, 0.
     const Lm *lm = io_host<Lm>(io, HEAD_LM);
     const double *hres = io_host<double>(io, s_res), *hwgt = io_host<double>(io, s_wgt), *hdep = io_host<double>(io, s_dep), *hred = io_host<double>(io, s_red),
                  *hcov = io_host<double>(io, s_cov), *hchi = io_host<double>(io, s_chi);
@@ -1980,7 +2010,7 @@ class SolverImpl {
       const bool bad = full && lm[w].chol_fail != 0;
       for (size_t b = gate_voff_[(size_t)w]; b < gate_voff_[(size_t)w + 1]; ++b) {
         const size_t i = b - v0, k = (size_t)(gate_slot_[b] - s0);
-        const int st = gate_scatter(GATE_CODES, hstat[k], bad, 2, hred + k, hcov + 4 * k, hchi + k, red ? red + i : nullptr, cov4 ? cov4 + 4 * i : nullptr,
+        const int st = gate_scatter(VIS_GATE_CODES, hstat[k], bad, 2, hred + k, hcov + 4 * k, hchi + k, red ? red + i : nullptr, cov4 ? cov4 + 4 * i : nullptr,
                                     chi2 ? chi2 + i : nullptr);
         if (res2) { res2[2 * i] = hres[2 * k]; res2[2 * i + 1] = hres[2 * k + 1]; }
         if (weight) weight[i] = hwgt[k];
@@ -1990,6 +2020,47 @@ class SolverImpl {
     }
     if (lm_stats3) std::memcpy(lm_stats3, io_host<double>(io, s_lms), sizeof(double) * 3 * L);
     if (lm_count) std::memcpy(lm_count, io_host<int32_t>(io, s_lmc), sizeof(int32_t) * L);
+    return CTVIO_OK;
+  }
+  int cull_visual(int only, const ctvio_cull_options *o, int32_t *n_culled, uint8_t *active) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    if (!o) return fail(CTVIO_ERR_INVALID, "null options");
+    const ctvio_gate_options g{o->min_redundancy};
+    const CullCall c{CullRules{o->chi2_max, o->mean_error_max, o->worst_only, o->drop_uncomputable}, n_culled, active};
+    return visual_gate(only, &g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &c);
+  }
+  // ctvio_set_visual_active* / ctvio_get_visual_active* (only >= 0: that window alone): Dev::v_on of the windows' slots (padding included:
+  // nobody reads a padding slot's flag) in ONE copy, the caller's block order by gate_slot_.  Nothing else of the handle moves.
+  int set_visual_active(int only, const uint8_t *active) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    const int wbeg = only >= 0 ? only : 0, wend = only >= 0 ? only + 1 : dev_.nwin;
+    const int s0 = meta_[wbeg].vis0, nslot = meta_[wend - 1].vis0 + meta_[wend - 1].Vp - s0;
+    const size_t v0 = gate_voff_[(size_t)wbeg];
+    if (nslot == 0) return CTVIO_OK;
+    CallLayout io = head_;
+    const int s_f = io.add("flags", 1, (size_t)nslot, false);
+    if (const int rc = reserve_call(io)) return rc;
+    uint8_t *h = io_host<uint8_t>(io, s_f);
+    std::memset(h, 1, (size_t)nslot);
+    if (active)
+      for (size_t b = v0; b < gate_voff_[(size_t)wend]; ++b) h[gate_slot_[b] - s0] = active[b - v0] ? 1 : 0;
+    HIPCHK(hipMemcpyAsync(dev_.v_on + s0, h, (size_t)nslot, hipMemcpyHostToDevice, stream_));
+    return sync_call();
+  }
+  int get_visual_active(int only, uint8_t *active) {
+    if (const int rc = only >= 0 ? guard(only) : guard()) return rc;
+    const int wbeg = only >= 0 ? only : 0, wend = only >= 0 ? only + 1 : dev_.nwin;
+    const int s0 = meta_[wbeg].vis0, nslot = meta_[wend - 1].vis0 + meta_[wend - 1].Vp - s0;
+    const size_t v0 = gate_voff_[(size_t)wbeg], V = gate_voff_[(size_t)wend] - v0;
+    if (V == 0) return CTVIO_OK;
+    if (!active) return fail(CTVIO_ERR_INVALID, "null output");
+    CallLayout io = head_;
+    const int s_f = io.add("flags", 1, (size_t)nslot, false);
+    if (const int rc = reserve_call(io)) return rc;
+    uint8_t *h = io_host<uint8_t>(io, s_f);
+    HIPCHK(hipMemcpyAsync(h, dev_.v_on + s0, (size_t)nslot, hipMemcpyDeviceToHost, stream_));
+    if (const int rc = sync_call()) return rc;
+    for (size_t b = v0; b < v0 + V; ++b) active[b - v0] = h[gate_slot_[b] - s0] ? 1 : 0;
     return CTVIO_OK;
   }
   // ctvio_imu_gate_batch / ctvio_imu_gate (only >= 0: that window alone): the leave-one-out test of every IMU sample of the windows
@@ -2544,6 +2615,34 @@ int32_t ctvio_visual_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options 
   CHK_S;
   if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
   return s->impl.visual_gate(id, o, res2, weight, depth, redundancy, cov4, chi2, status, lm_stats3, lm_count);
+}
+int32_t ctvio_set_visual_active_batch(ctvio_solver *s, const uint8_t *active) { CHK_S; return s->impl.set_visual_active(-1, active); }
+int32_t ctvio_set_visual_active(ctvio_solver *s, int32_t id, const uint8_t *active) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.set_visual_active(id, active);
+}
+int32_t ctvio_get_visual_active_batch(ctvio_solver *s, uint8_t *active) { CHK_S; return s->impl.get_visual_active(-1, active); }
+int32_t ctvio_get_visual_active(ctvio_solver *s, int32_t id, uint8_t *active) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.get_visual_active(id, active);
+}
+void ctvio_default_cull_options(ctvio_cull_options *o) {
+  if (!o) return;
+  o->min_redundancy = 0.01;
+  o->chi2_max = 9.21;
+  o->mean_error_max = 0.0;
+  o->worst_only = 0;
+  o->drop_uncomputable = 1;
+}
+int32_t ctvio_cull_visual_batch(ctvio_solver *s, const ctvio_cull_options *o, int32_t *n_culled, uint8_t *active) {
+  CHK_S; return s->impl.cull_visual(-1, o, n_culled, active);
+}
+int32_t ctvio_cull_visual(ctvio_solver *s, int32_t id, const ctvio_cull_options *o, int32_t *n_culled, uint8_t *active) {
+  CHK_S;
+  if (id < 0) return ctv::fail(CTVIO_ERR_INVALID, "window id out of range");
+  return s->impl.cull_visual(id, o, n_culled, active);
 }
 int32_t ctvio_imu_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, double *res6, double *redundancy, double *cov36, double *chi2, int32_t *status,
                              double *frame_stats4) {

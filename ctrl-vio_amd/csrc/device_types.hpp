@@ -116,6 +116,9 @@ struct Dev {
   const double *v_obs;        // [2][Vtot] pjx, pjy
   const double *v_cauchy; // [Vtot] width a of the block's ceres::CauchyLoss(a) (<= 0: no loss): the reference picks it per residual
                          // block (trajectory_estimator.cpp:320-323: 1 when the feature is being marginalised, else 2)
+  uint8_t *v_on;         // [Vtot] 1: the block slot is an ACTIVE factor (ctvio.h: ctvio_set_visual_active; every slot after an upload).  An inactive slot keeps
+                         // its place in the wave's landmark / anchor lane structure (it is NOT a padding slot) and emits a zero record, residual and cost.
+                         // Written by ctvio_set_visual_active* and k_vis_cull only; read from memory on every pass (graph replay included).
   double *Jt;                 // robust-corrected block records, block-major [Vtot][VT_ROWS] (factors.hpp VB_*: rotation columns of the j end,
                          // inverse-depth and line-delay columns, residual, A~ (2 x 3) and the j end's blending coefficients -- the i-end
                          // columns are A~ times the anchor record and are rebuilt by the assembly): the assembly gathers the blocks of an

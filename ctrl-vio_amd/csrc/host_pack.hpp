@@ -560,16 +560,16 @@ inline double gate_value(double computed, int st) { return st == QUERY_OK ? comp
 
 // The statuses of a leave-one-out gate (ctvio_visual_gate_batch, ctvio_imu_gate_batch): ok, singular and no_info are QUERY_*'s (ctvio.hip
 // asserts it), weak is "redundancy < min_redundancy".
-struct GateCodes { int ok, weak, singular, no_info; };
+struct GateCodes { int ok, weak, singular, no_info, inactive = -1; };   // inactive (the visual gate alone): an ok block that is switched off -- values as for ok
 // One block or sample of a gate by status, into the caller's entries (null: not asked for; the computed values are read only where one
 // is).  st: what the kernels left; bad: the window's factorisation failed (Lm::chol_fail), which turns ok and weak into singular and lets
 // every other status stand.  The redundancy is the computed one for ok and weak, 0 without information, NaN otherwise; the dim x dim block
 // and the gate are cov_block's and gate_value's with weak counted as no information.  Returns the status to report.
 inline int gate_scatter(const GateCodes &c, int st, bool bad, int dim, const double *computed_red, const double *computed_cov, const double *computed_chi2,
                         double *red, double *cov, double *chi2) {
-  if (bad && (st == c.ok || st == c.weak)) st = c.singular;
-  const int as = st == c.weak ? c.no_info : st;
-  if (red) *red = st == c.ok || st == c.weak ? *computed_red : (st == c.no_info ? 0.0 : std::nan(""));
+  if (bad && (st == c.ok || st == c.weak || st == c.inactive)) st = c.singular;
+  const int as = st == c.weak ? c.no_info : (st == c.inactive ? c.ok : st);
+  if (red) *red = st == c.ok || st == c.weak || st == c.inactive ? *computed_red : (st == c.no_info ? 0.0 : std::nan(""));
   if (cov) cov_block(cov, computed_cov, dim, as);
   if (chi2) *chi2 = gate_value(*computed_chi2, as);
   return st;
@@ -686,7 +686,7 @@ inline std::vector<int32_t> plan_imugate_tiles(const int32_t *samples, int wbeg,
   X(double, imu_u, imu_u, Mt, M0) X(double, imu_meas, imu_meas, 6 * Mt, 6 * M0)                        \
   X(int32_t, v_win, v_win, Vt, V0) X(int32_t, v_lm, v_lm, Vt, V0) X(int32_t, v_anc, v_anc, Vt, V0) X(int32_t, v_rowj, v_rowj, Vt, V0) \
   X(int64_t, v_tj, v_tj, Vt, V0) X(double, v_obs, v_obs, 2 * Vt, 2 * V0)                               \
-  X(double, v_cauchy, v_cauchy, Vt, V0) X(int32_t, vb_win, vb_win, Vt / 64 + 1, V0 / 64)               \
+  X(double, v_cauchy, v_cauchy, Vt, V0) X(uint8_t, v_on, v_on, Vt, V0) X(int32_t, vb_win, vb_win, Vt / 64 + 1, V0 / 64) \
   X(int32_t, a_win, a_win, At, A0) X(int32_t, a_lm, a_lm, At, A0) X(int32_t, a_row, a_row, At, A0)     \
   X(int64_t, a_t, a_t, At, A0) X(double, a_obs, a_obs, 2 * At, 2 * A0)                                 \
   X(VisItem, vitems, vitems, std::max<size_t>(I0, 1), I0) X(int32_t, vblk, vblk, Vt, V0) X(int32_t, vblk_anc, vblk_anc, Vt, V0) \
@@ -862,6 +862,7 @@ inline void fill_window(const ctvio_window &w, int wi, const WinMeta &m, const P
   for (int i = 0; i < m.Vp; ++i) {
     const int v = t.lord[i];
     const size_t e = (size_t)m.vis0 + i;
+    h.v_on[e] = 1;   // (every block is active after an upload; a padding slot's flag is never read)
     if (v < 0) {
       h.v_win[e] = -1; h.v_lm[e] = 0; h.v_anc[e] = m.anc0; h.v_tj[e] = 0; h.v_rowj[e] = 0; h.v_cauchy[e] = 0.0;
       for (int c = 0; c < 2; ++c) h.v_obs[(size_t)c * Vt + e] = 0.0;

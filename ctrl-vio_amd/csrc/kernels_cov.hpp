@@ -674,7 +674,7 @@ __global__ __launch_bounds__(64) void k_cov_proj_jac(Dev d, int n, const ProjQue
 // corrector S (symmetric 2 x 2: entries (0,0), (0,1), (1,1)) as vis_block_eval (factors.hpp) applies it to the block's Jacobian rows:
 // S = sqrt(rho') (I - alpha r r^T / s) with Ceres' rule alpha = 0 where s == 0 or rho'' <= 0 -- which the Cauchy loss always meets, so that
 // S = sqrt(rho') I here; the general form is kept so that the epilogue does not depend on the loss.
-enum { GATE_WEAK = 4 };   // ctvio.h: redundancy < min_redundancy (the statuses below it are PRJ_*)
+enum { GATE_WEAK = 4, GATE_INACTIVE = 5 };   // ctvio.h: redundancy < min_redundancy; an inactive block that is otherwise ok (the statuses below them are PRJ_*)
 struct GateRec : ProjRec {
   double r[2], weight, S[3];
 };
@@ -686,6 +686,13 @@ struct GateOut {
   int32_t slot0, nslot;   // the outputs' first slot; the slots of the slice k_cov_solve runs over (from CovSolveIO::slot_base on)
   double min_red;
 };
+// |r| / img_w with every operation rounded once.  (The __d*_rn intrinsics are plain operators here and contract into an fma like any
+// others: a landmark with a single counted block then missed "re-derivable from res2" by an ulp.  The pragma is what keeps them apart.)
+__device__ __forceinline__ double gate_enorm(double r0, double r1, double img_w) {
+#pragma clang fp contract(off)
+  const double a = r0 * r0, b = r1 * r1, s = a + b;
+  return sqrt(s) / img_w;
+}
 // One lane per block slot e = first + i of the slice (records by i, outputs by e - slot0).  A padding slot (v_win < 0) gets a PRJ_NONE
 // record and nothing else.  The value comes from proj_query, so it has the bits of the values-only call (excl null: no records).
 __global__ __launch_bounds__(64) void k_cov_gate_jac(Dev d, int first, int n, const uint8_t *excl, GateRec *recs, GateOut o) {
@@ -714,13 +721,20 @@ __global__ __launch_bounds__(64) void k_cov_gate_jac(Dev d, int first, int n, co
     if (!(s == 0.0 || rho2 <= 0.0)) asq = (1.0 - sqrt(fmax(0.0, 1.0 + 2.0 * s * rho2 / inv))) / s;
   }
   if (status == PRJ_NONE) wgt = p3[0];   // (NaN, also without a loss)
+  // An inactive block (Dev::v_on) is not in H: nothing is taken out -- weight 0 and S = 0, with which the epilogue's formulas give
+  // redundancy 1, C_loo = Cw and chi2 = r^T (Cw + I)^-1 r -- and GATE_INACTIVE stands where PRJ_OK would.
+  const bool act = d.v_on[e] != 0;
+  if (!act) {
+    if (status != PRJ_NONE) wgt = 0.0;
+    sq = 0.0;
+  }
   const size_t k = (size_t)(e - o.slot0);
   if (o.res2) { o.res2[2 * k] = r0; o.res2[2 * k + 1] = r1; }
   if (o.weight) o.weight[k] = wgt;
   if (o.depth) o.depth[k] = p3[2];
   // (from the residual as returned, every operation rounded once: the landmark mean can be re-derived from res2 to the summation order)
-  if (o.enorm) o.enorm[k] = __ddiv_rn(__dsqrt_rn(__dadd_rn(__dmul_rn(r0, r0), __dmul_rn(r1, r1))), m.img_w);
-  o.status[k] = status;
+  if (o.enorm) o.enorm[k] = gate_enorm(r0, r1, m.img_w);
+  o.status[k] = !act && status == PRJ_OK ? GATE_INACTIVE : status;
   if (!excl) return;
   GateRec &g = recs[i];
   g.r[0] = r0; g.r[1] = r1; g.weight = wgt;
@@ -741,7 +755,7 @@ __global__ __launch_bounds__(64) void k_cov_gate_reduce(Dev d, int lm_base, int 
   for (int j = 0; j < cnt; ++j) {
     const size_t k = (size_t)(first + j - o.slot0);
     const int st = o.status[k];
-    if (st == PRJ_NONE) continue;
+    if (st == PRJ_NONE || !d.v_on[first + j]) continue;   // (the landmark's statistics run over its ACTIVE blocks)
     ++c;
     if (!stats3) continue;
     sum = __dadd_rn(sum, o.enorm[k]);
@@ -754,6 +768,45 @@ __global__ __launch_bounds__(64) void k_cov_gate_reduce(Dev d, int lm_base, int 
     stats3[3 * (size_t)i] = c ? sum / (double)c : qnan();
     stats3[3 * (size_t)i + 1] = cmax;
     stats3[3 * (size_t)i + 2] = rmin;
+  }
+}
+
+// ctvio_cull_visual_batch: the decision on the gate's device outputs and the flag update.  One lane per landmark (as k_cov_gate_reduce, after
+// it and after the last slice's k_cov_solve), over its slots in slot order; no atomics.  A window whose factorisation failed (chol_fail)
+// is left alone.  Rules (ctvio.h): an active PRJ_OK block with chi2 > chi2_max goes (worst_only: the landmark's largest such chi2 alone,
+// the first in slot order on a tie); every active PRJ_OK block of a landmark with count > 0 and mean error > mean_max goes; an active
+// PRJ_NONE block goes with drop_unc.  Singular / no-information / weak blocks and inactive ones are never touched.  Per slot (absolute
+// slot - o.slot0): culled = switched off by this launch, flags = Dev::v_on after it.
+struct CullRules { double chi2_max, mean_max; int32_t worst_only, drop_unc; };
+__global__ __launch_bounds__(64) void k_vis_cull(Dev d, int lm_base, int n, GateOut o, CullRules a, const double *stats3, const int32_t *count, uint8_t *culled,
+                                                 uint8_t *flags) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int l = lm_base + i, first = d.lm_vfirst[l], cnt = d.lm_vcnt[l];
+  const bool bad = d.lm[d.lm_win[l]].chol_fail != 0;
+  const bool by_chi2 = !bad && a.chi2_max > 0.0, by_mean = !bad && a.mean_max > 0.0 && count[i] > 0 && stats3[3 * (size_t)i] > a.mean_max;
+  int worst = -1;
+  double cw = 0.0;
+  if (by_chi2 && a.worst_only)
+    for (int j = 0; j < cnt; ++j) {
+      const size_t k = (size_t)(first + j - o.slot0);
+      if (!d.v_on[first + j] || o.status[k] != PRJ_OK) continue;
+      const double c = o.chi2[k];
+      if (c > a.chi2_max && (worst < 0 || c > cw)) { worst = j; cw = c; }
+    }
+  for (int j = 0; j < cnt; ++j) {
+    const int e = first + j;
+    const size_t k = (size_t)(e - o.slot0);
+    const bool on = d.v_on[e] != 0;
+    const int st = o.status[k];
+    bool off = false;
+    if (on && !bad) {
+      if (st == PRJ_OK) off = by_mean || (by_chi2 && o.chi2[k] > a.chi2_max && (!a.worst_only || j == worst));
+      else if (st == PRJ_NONE) off = a.drop_unc != 0;
+    }
+    if (off) d.v_on[e] = 0;
+    culled[k] = off ? 1 : 0;
+    flags[k] = on && !off ? 1 : 0;
   }
 }
 

@@ -66,9 +66,12 @@ __global__ void k_gauge_restore(Dev d, int n, const int32_t *ids, const int32_t 
 // ------------------------------------------------------------------------------------------------ residual summary
 // ResidualSummary::AddResidualInfo (reference trajectory_estimator.cpp:36-67): per factor type, the sum of |r_i| of every
 // residual component over all blocks (the cost functions' raw whitened residuals: no robust loss) and the block count.
-// Diagnostic entry (fp64 evaluation, one workgroup per call): out = [imu 6 | bias 6 | image 2 | prior pn].
+// Diagnostic entry (fp64 evaluation, one workgroup per call): out = [imu 6 | bias 6 | image 2 | prior pn | number of active visual blocks].
+// The image sums run over the ACTIVE block slots (Dev::v_on).
 __global__ __launch_bounds__(256) void k_residual_summary(Dev d, int w, double *out) {
   const WinMeta &m = d.wins[w];
+  __shared__ int n_on;
+  if (threadIdx.x == 0) n_on = 0;
   extern __shared__ __attribute__((aligned(16))) double smr[];   // [14 + pn] sums, then [pn] dx
   const int tid = threadIdx.x, n = m.pn;
   double *sums = smr, *dx = smr + 14 + n;
@@ -99,7 +102,8 @@ __global__ __launch_bounds__(256) void k_residual_summary(Dev d, int w, double *
   }
   for (int i = tid; i < m.Vp; i += 256) {
     const int v = m.vis0 + i;
-    if (d.v_win[v] < 0) continue;   // padding slot
+    if (d.v_win[v] < 0 || !d.v_on[v]) continue;   // padding slot, inactive block
+    atomicAdd(&n_on, 1);
     // raw residual at the current state: anchor value and block value evaluated here, pair constants straight from the knots
     // (independent of the tables and of the records the solver keeps)
     const int a = d.v_anc[v];
@@ -155,6 +159,7 @@ __global__ __launch_bounds__(256) void k_residual_summary(Dev d, int w, double *
   }
   __syncthreads();
   for (int i = tid; i < 14 + n; i += 256) out[i] = sums[i];
+  if (tid == 0) out[14 + n] = (double)n_on;
 }
 
 // ------------------------------------------------------------------------------------------------ trajectory query

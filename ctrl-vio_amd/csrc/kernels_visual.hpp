@@ -121,7 +121,13 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
   if (!lin_run(lmw, mode)) return;               // (wave-uniform: nothing of this window is evaluated on this pass)
   const bool jac = !lin_cost_only(lmw, mode, d.prm);
   const int tgw = lin_target(lmw, mode);
-  if (v < d.Vtot && d.v_win[v] >= 0) {           // (padding slots carry window -1)
+  // The slot's flag (Dev::v_on) is requested together with its window word: one wait for both, no round trip of its own.  An INACTIVE slot
+  // is not a padding slot: it keeps its lane among its landmark's and anchor's lanes (a gap would make a second head lane that stores the
+  // same row of W; a landmark without a live lane would keep a stale row), is not evaluated, and emits a zero record, residual and cost.
+  int vwin = -1;
+  bool act = false;
+  if (v < d.Vtot) { vwin = d.v_win[v]; act = d.v_on[v] != 0; }
+  if (vwin >= 0) {                               // (padding slots carry window -1)
     {
       int sj;
       double uj;
@@ -135,7 +141,7 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
       double dmax = 0.0;
 #pragma unroll
       for (int i = 0; i < 3; ++i) dmax = fmax(dmax, dot(scj.d[i], scj.d[i]));
-      const bool small = __ballot(dmax >= 0.25) == 0ull;
+      const bool small = __ballot(act && dmax >= 0.25) == 0ull;
       const double *qj = quat + 4 * (m.knot0 + sj), *pj = pos + 3 * (m.knot0 + sj);
       const Q4 q0 = qmk(qj[0], qj[1], qj[2], qj[3]);
       V3 p[4];
@@ -159,15 +165,19 @@ __device__ __forceinline__ void vis_eval_body(const Dev &d, int mode, unsigned c
         on = true;
         my_lm = d.v_lm[v];
         my_anc = anc;
-        if (small) c = vis_block_eval<true>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, true, sink);
-        else c = vis_block_eval<false>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, true, sink);
-        sink.put(VB_RES, r[0]); sink.put(VB_RES + 1, r[1]);
+        if (!act) {
+          for (int e = 0; e < VT_ROWS; ++e) sink.put(e, 0.0);
+        } else {
+          if (small) c = vis_block_eval<true>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, true, sink);
+          else c = vis_block_eval<false>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, true, sink);
+          sink.put(VB_RES, r[0]); sink.put(VB_RES + 1, r[1]);
+        }
         d.vsj[v] = sj;
         ksj = sj;
       } else {
         VisNullSink nsink;
         costed = true;
-        c = vis_block_eval<false>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, false, nsink);
+        if (act) c = vis_block_eval<false>(rec, q0, p, scj, uj, m.inv_dt, RCIT, p_CI, m.img_w, ca, pjx, pjy, (double)rowj, r, false, nsink);
       }
     }
   }

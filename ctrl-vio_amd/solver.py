@@ -478,6 +478,48 @@ class Solver:
         """ctvio_visual_gate: the same for window wid alone (same bits as the batch entry)."""
         return self._visual_gate(lambda *a: self._lib.ctvio_visual_gate(self._h, int(wid), *a), [int(wid)], cov, min_redundancy)
 
+    def _block_count(self, wid):
+        return sum(int(w.V) for w in self.windows) if wid is None else int(self.windows[int(wid)].V)
+
+    def set_visual_active(self, active, wid=None):
+        """ctvio_set_visual_active(_batch): switch visual blocks on (non-zero) and off (0), one entry per block in the caller's block order --
+        of window wid, or of every window one after the other.  None: every block active.  An inactive block is not a factor of the window;
+        the slot order, the sparsity plan and the captured graph stay the upload's."""
+        a = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, dtype=np.uint8)
+        if a is not None and a.shape != (self._block_count(wid),):
+            raise ValueError("active: one entry per visual block")
+        if wid is None:
+            capi.check(self._lib.ctvio_set_visual_active_batch(self._h, _ptr(a) if a is not None else None))
+        else:
+            capi.check(self._lib.ctvio_set_visual_active(self._h, int(wid), _ptr(a) if a is not None else None))
+
+    def visual_active(self, wid=None):
+        """ctvio_get_visual_active(_batch): the flags as a uint8 array (1 active, 0 inactive), the caller's block order."""
+        a = np.zeros(max(self._block_count(wid), 1), dtype=np.uint8)
+        if wid is None:
+            capi.check(self._lib.ctvio_get_visual_active_batch(self._h, _ptr(a)))
+        else:
+            capi.check(self._lib.ctvio_get_visual_active(self._h, int(wid), _ptr(a)))
+        return a[:self._block_count(wid)]
+
+    def cull_visual(self, wid=None, **options):
+        """ctvio_cull_visual(_batch): gate, decision and flag update on the device at the current state.  options: the fields of
+        ctvio_cull_options (min_redundancy, chi2_max, mean_error_max, worst_only, drop_uncomputable) over its defaults.  Returns a namespace:
+        n_culled (blocks switched off by this call, per window) and active (the flags after the call)."""
+        o = capi.CullOptions()
+        self._lib.ctvio_default_cull_options(C.byref(o))
+        for k, v in options.items():
+            if k not in dict(capi.CullOptions._fields_):
+                raise TypeError(f"unknown cull option {k!r}")
+            setattr(o, k, v)
+        nw = len(self.windows) if wid is None else 1
+        nc = np.zeros(nw, dtype=np.int32); a = np.zeros(max(self._block_count(wid), 1), dtype=np.uint8)
+        if wid is None:
+            capi.check(self._lib.ctvio_cull_visual_batch(self._h, C.byref(o), _ptr(nc), _ptr(a)))
+        else:
+            capi.check(self._lib.ctvio_cull_visual(self._h, int(wid), C.byref(o), _ptr(nc), _ptr(a)))
+        return SimpleNamespace(n_culled=nc, active=a[:self._block_count(wid)])
+
     def _imu_gate(self, call, wids, cov, min_redundancy):
         o = _gate_options(self._lib, min_redundancy)
         M = sum(int(self.windows[w].M) for w in wids); F = sum(int(self.windows[w].F) for w in wids)

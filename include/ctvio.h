@@ -465,6 +465,59 @@ int32_t ctvio_visual_gate_batch(ctvio_solver *s, const ctvio_gate_options *o, do
 int32_t ctvio_visual_gate(ctvio_solver *s, int32_t id, const ctvio_gate_options *o, double *res2, double *weight, double *depth, double *redundancy,
                           double *cov4, double *chi2, int32_t *status, double *lm_stats3, int32_t *lm_count);
 
+/* ACTING ON THE GATE: every visual block of an uploaded batch is ACTIVE or INACTIVE.  ctvio_upload, ctvio_set_batch and ctvio_clear make
+ * every block active; ctvio_set_state and ctvio_snapshot_state / ctvio_restore_state leave the flags alone (they are not state).  The flags
+ * live in device memory and are read on every pass, so changing them moves neither the launch plan nor the captured graph
+ * (ctvio_graph_captures).
+ * An inactive block is NOT A FACTOR of the window: it contributes exactly 0.0 to the cost, to Hpp, W, Hll and g and to the block records
+ * the assembly reads, on every linearisation path (LDS-resident and wide windows, deterministic 1 and 2, use_mfma 1 and 2, cost-only passes
+ * and candidate evaluation, graph replay and profiled launches) -- also where its own projection is not finite (the block is not evaluated
+ * at all; its anchor's record still is, which needs no more than a finite non-zero inverse depth).  ctvio_solve, ctvio_linearize,
+ * ctvio_cost, ctvio_lm_step, ctvio_marginalize(_batch) and every covariance-family entry see the window without it.  A landmark whose
+ * blocks are all inactive has Hll == 0 and gets the existing "no information" statuses; a knot that inactive blocks alone touch is
+ * "untouched" by the existing rule.  ctvio_residual_summary's image sums and counts4[2] cover the active blocks.
+ * THE STRUCTURE STAYS THE UPLOAD'S: the slot order, the sparsity plan (a superset of any subset of the blocks), the landmark spans, the
+ * anchor of a landmark, ctvio_triangulate* and ctvio_shift_anchor_batch do not look at the flags.
+ * ctvio_visual_gate(_batch) on an inactive block is the RE-ADMISSION test: its information is not in H, so nothing is taken out (S = 0,
+ * weight = 0), and the formulas above give redundancy = 1, cov4 = Cw and chi2 = r^T (Cw + I)^-1 r -- ctvio_project_landmarks' new-match
+ * gate, whitened.  Where its status would be 0 it is 5 (inactive); the precedence is 3, 2, 1, 5, 4, 0.  lm_count and lm_stats3 run over the
+ * active blocks only.  With every block active the gate computes what it computed before there were flags; one output is formed more
+ * strictly than it used to be: lm_stats3[0] now rounds every operation of |proj.xy - p_j| once, as its definition above says (the earlier
+ * build fused a product into the sum), and may differ from that build in the last place.
+ * active: one byte per block in the CALLER'S block order (ctvio_window.v_*), non-zero = active; sum V entries (batch) / V (window id).
+ * set: NULL makes every block active.  get: 1 / 0.  CTVIO_OK also for V = 0; CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID for a
+ * window id out of range or a NULL output. */
+int32_t ctvio_set_visual_active_batch(ctvio_solver *s, const uint8_t *active);
+int32_t ctvio_set_visual_active(ctvio_solver *s, int32_t id, const uint8_t *active);
+int32_t ctvio_get_visual_active_batch(ctvio_solver *s, uint8_t *active);
+int32_t ctvio_get_visual_active(ctvio_solver *s, int32_t id, uint8_t *active);
+
+/* CULL: gate + decision + flag update, all on the device, at the CURRENT state and the current flags.  The rules are written in terms of
+ * what ctvio_visual_gate_batch with the same min_redundancy returns at this state and these flags, and are applied to those very bits
+ * (k_vis_cull reads the gate's device outputs), so that on an order-fixed linearisation the result does not depend on the entry or on how
+ * the call was sliced.
+ *   block rule: an active block of status 0 with chi2 > chi2_max is switched off; with worst_only only the landmark's worst such block
+ *     (largest chi2, first in the packed block order on a tie) -- Baarda-style data snooping, one deletion per re-solve;
+ *   landmark rule: every active status-0 block of a landmark with lm_count > 0 and lm_stats3[0] > mean_error_max is switched off;
+ *   drop_uncomputable: an active block of status 3 is switched off (the counterpart of setDepth's failure flag + removeFailures).
+ * Never touched: blocks of status 1, 2 or 4 (4: the rest of the window cannot check the block) and blocks that are already inactive -- the
+ * cull never re-admits; a caller re-admits with ctvio_set_visual_active from the gate's status-5 results.  A window whose factorisation
+ * failed is left alone entirely (n_culled = 0).
+ * n_culled: blocks switched off by THIS call per window (n windows / 1); active: the flags after the call, as ctvio_get_visual_active*;
+ * either may be NULL.  CTVIO_OK also for V = 0 (nothing is launched); CTVIO_ERR_STATE before the upload; CTVIO_ERR_INVALID for a window id
+ * out of range, NULL options or min_redundancy outside (0, 1); the handle stays usable.  The state, the launch plan and the captured
+ * graph are left as they were.  ctvio_last_timing: as after a full ctvio_visual_gate call, and ms8[4] = k_vis_cull. */
+typedef struct ctvio_cull_options {
+  double min_redundancy;     /* the gate's; 0.01 */
+  double chi2_max;           /* 9.21 (99 % point, 2 dof); <= 0: block rule off */
+  double mean_error_max;     /* landmark rule on lm_stats3[0] (unwhitened mean |proj - p_j|); <= 0 (default): off */
+  int32_t worst_only;        /* 0 (default); 1: the block rule takes at most one block per landmark and call */
+  int32_t drop_uncomputable; /* 1 (default) */
+} ctvio_cull_options;        /* 32 bytes */
+void ctvio_default_cull_options(ctvio_cull_options *o);
+int32_t ctvio_cull_visual_batch(ctvio_solver *s, const ctvio_cull_options *o, int32_t *n_culled, uint8_t *active);
+int32_t ctvio_cull_visual(ctvio_solver *s, int32_t id, const ctvio_cull_options *o, int32_t *n_culled, uint8_t *active);
+
 /* AFTER THE SOLVE, WHICH IMU SAMPLES ARE OUTLIERS: the leave-one-out (deleted) residual test of every IMU sample of the windows themselves.
  * The IMU factor carries no robust loss, so a saturated, dropped or mis-timed sample pulls the spline at full weight; ctvio_body_rates' gate is
  * for NEW samples.  Here the sample's own information is taken out of the normal matrix -- a 6 x 6 Woodbury correction per sample on top of

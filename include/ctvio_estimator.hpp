@@ -339,17 +339,29 @@ class TrajectoryEstimator {
     check(ctvio_set_batch(s, 1, &pk.w));
     SolveSummary sum;
     check(ctvio_solve(s, max_iterations, &sum.s));
-    double ld = traj_->line_delay;
-    check(ctvio_get_state(s, 0, pk.quat.data(), pk.pos.data(), pk.bias.data(), pk.rho.data(), &ld));
-    // results back in place, like Ceres writing through the double* (trajectory_manager.cpp:457-463)
-    for (int k = 0; k < pk.w.K; ++k) {
-      for (int c = 0; c < 4; ++c) traj_->so3_[pk.kmin + k][c] = pk.quat[4 * k + c];
-      for (int c = 0; c < 3; ++c) traj_->pos_[pk.kmin + k][c] = pk.pos[3 * k + c];
+    write_back(s, pk);
+    return sum;
+  }
+  // Solve -> drop the outliers -> solve again, on ONE upload (ctvio_cull_visual): `rounds` x (solve, cull at the solved state), then a final
+  // solve; the image factors the culls switched off take no part in the following solves.  culled (optional): those factors, in the order of
+  // the AddImageFeatureDelayAnalytic calls.  The estimator's factor lists are not changed: a later Solve sees every factor again, and it is
+  // the caller who erases the features (removeFailures / outliersRejection).  Returns the summary of the final solve.
+  SolveSummary SolveWithCulling(int max_iterations, const ctvio_cull_options &cull_options, int rounds = 1, std::vector<int> *culled = nullptr) {
+    Packed pk;
+    pack(pk, /*marg_only=*/false);
+    ctvio_solver *s = upload(pk);
+    SolveSummary sum;
+    std::vector<uint8_t> active((size_t)pk.w.V, 1);
+    for (int r = 0; r < rounds; ++r) {
+      check(ctvio_solve(s, max_iterations, &sum.s));
+      check(ctvio_cull_visual(s, 0, &cull_options, nullptr, active.empty() ? nullptr : active.data()));
     }
-    for (int f = 0; f < pk.w.F; ++f)
-      for (int c = 0; c < 3; ++c) { bias_ptr_[f].first[c] = pk.bias[6 * f + c]; bias_ptr_[f].second[c] = pk.bias[6 * f + 3 + c]; }
-    for (int l = 0; l < pk.w.L; ++l) *lm_ptr_[l] = pk.rho[l];
-    traj_->line_delay = ld;
+    check(ctvio_solve(s, max_iterations, &sum.s));
+    write_back(s, pk);
+    if (culled) {
+      culled->clear();
+      for (size_t v = 0; v < active.size(); ++v) if (!active[v]) culled->push_back((int)v);
+    }
     return sum;
   }
 
@@ -829,6 +841,19 @@ class TrajectoryEstimator {
     ctvio_solver *s = SolverCache::get(opt_.device, opt_.precision);
     check(ctvio_set_batch(s, 1, &pk.w));
     return s;
+  }
+  // the handle's state of window 0 back in place, like Ceres writing through the double* (trajectory_manager.cpp:457-463)
+  void write_back(ctvio_solver *s, Packed &pk) {
+    double ld = traj_->line_delay;
+    check(ctvio_get_state(s, 0, pk.quat.data(), pk.pos.data(), pk.bias.data(), pk.rho.data(), &ld));
+    for (int k = 0; k < pk.w.K; ++k) {
+      for (int c = 0; c < 4; ++c) traj_->so3_[pk.kmin + k][c] = pk.quat[4 * k + c];
+      for (int c = 0; c < 3; ++c) traj_->pos_[pk.kmin + k][c] = pk.pos[3 * k + c];
+    }
+    for (int f = 0; f < pk.w.F; ++f)
+      for (int c = 0; c < 3; ++c) { bias_ptr_[f].first[c] = pk.bias[6 * f + c]; bias_ptr_[f].second[c] = pk.bias[6 * f + 3 + c]; }
+    for (int l = 0; l < pk.w.L; ++l) *lm_ptr_[l] = pk.rho[l];
+    traj_->line_delay = ld;
   }
   // gyro-bias pointer as given to the Add* calls -> bias index in the window (nullptr: -1, the entries' "newest")
   int frame_of(const Packed &pk, const double *bias_gyr, const char *who) const {
