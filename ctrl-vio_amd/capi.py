@@ -21,13 +21,19 @@ FP64 = 1   # the only precision (ctvio.h: the mixed fp32 mode was removed)
 TERMINATION = {0: "max-iterations", 1: "gradient-tolerance", 2: "parameter-tolerance", 3: "function-tolerance", 4: "min-radius", 5: "failure"}
 
 
+def hipcc_command(out: str, src: str) -> list:
+    """The one hipcc line for device code of this project: libctvio.so and the test-only probe of the device math (tests/devprobe.py)
+    are built with it, so a flag change reaches both."""
+    return ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize",
+            "-o", out, src]
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc cross-compiles for gfx950 without a GPU; the .so is kept in-tree so it ships with the repo snapshot."""
     deps = SRC + [HDR]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(f) for f in deps):
         return LIB_PATH
-    cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize",
-           "-o", LIB_PATH, SRC[0]]
+    cmd = hipcc_command(LIB_PATH, SRC[0])
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)

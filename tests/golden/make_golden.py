@@ -2,6 +2,7 @@
 
 Run ONLY in the build container:  python tests/golden/make_golden.py   (all the small fixtures), and
     python tests/golden/make_golden.py bench_fd | bench_lm                (the fixtures at the benchmarked sizes: minutes each)
+    python tests/golden/make_golden.py lie                                (lie_edge_grid.npz: needs mpmath; seconds)
 Source of truth = oracle/np_oracle.py (independent NumPy/SciPy restatement: residuals by a
 different code path, Jacobians by central finite differences, minimiser = scipy trf).  The
 fixtures pin oracle/ctvo.c (tests/test_oracle_golden.py) and, through it, the HIP path.
@@ -121,7 +122,20 @@ def bench_size_lm():
                                        "num_line_search_reduced", "final_cost", "final_radius")})
 
 
+def lie_fixture():
+    """(g) the Lie primitives of so3.hpp on an edge grid (tests/lie_fixture.py): inputs, and outputs from mpmath at 50 digits rounded once to
+    fp64.  Both builds of the header (g++ for the host, hipcc for gfx950) are checked against it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import lie_fixture as lf
+    inp = lf.inputs()          # (the knot spacings come from the generator: lie_fixture.knot_spacings)
+    exp = lf.expected_values(inp)
+    np.savez_compressed(lf.PATH, **inp, **exp)
+    print("lie_edge_grid:", {k: v.shape for k, v in {**inp, **exp}.items()})
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "lie":
+        return lie_fixture()
     if len(sys.argv) > 1 and sys.argv[1] == "lm":
         return lm_fixtures()
     if len(sys.argv) > 1 and sys.argv[1] == "bench_fd":

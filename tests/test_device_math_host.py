@@ -2,7 +2,7 @@
 only (tests/host_math_check.cpp) and compared block by block with the fp64 oracle (fp64 like the kernels: agreement to rounding)."""
 import ctypes as C
 import os
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -12,13 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 @pytest.fixture(scope="module")
 def hm():
-    out = os.path.join(HERE, "_build", "libhostmath.so")
-    src = os.path.join(HERE, "host_math_check.cpp")
-    hdrs = [os.path.join(HERE, "..", "ctrl-vio_amd", "csrc", f) for f in ("so3.hpp", "factors.hpp")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    lib = C.CDLL(out)
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import devprobe
+    lib = devprobe.host_lib("libhostmath.so", "host_math_check.cpp")          # one build rule for every host check
     lib.hm_visual_eval.restype = C.c_double
     return lib
 
@@ -91,6 +88,35 @@ def test_visual_block_matches_oracle(cv, oracle, hm, small):
         colscale = np.maximum(np.abs(Jc).max(0), 1e-3 * np.abs(Jc).max())
         assert (np.abs(J - Jc) / colscale).max() <= rtol
         assert cost == pytest.approx(cost0, rel=1e-10, abs=1e-12)
+
+
+def test_lie_primitives_match_high_precision_fixture():
+    """The g++ build of so3.hpp against tests/golden/lie_edge_grid.npz (mpmath at 50 digits; tests/lie_fixture.py has the grid, the bounds --
+    those of test_lie_primitives below -- and why angles near pi are not in it).  tests/test_gpu_device_math.py runs the same check on the
+    gfx950 build.  Measured: every output within 1e-2 of its bound (a few 1e-16)."""
+    import sys
+    sys.path.insert(0, HERE)
+    import devprobe
+    import lie_fixture
+    lie_fixture.check(lie_fixture.load(), devprobe.Host(), "host")
+
+
+def test_lie_fixture_regenerates():
+    """The committed expected values are what tests/lie_fixture.py computes today from the committed inputs (to the bit), and the inputs
+    are the ones it builds."""
+    mp = pytest.importorskip("mpmath")
+    import sys
+    sys.path.insert(0, HERE)
+    import lie_fixture
+    fx = lie_fixture.load()
+    inp = lie_fixture.inputs()
+    for k, a in inp.items():
+        np.testing.assert_array_equal(fx[k], a, err_msg=k)
+    again = lie_fixture.expected_values({k: fx[k] for k in inp})
+    assert set(again) == set(lie_fixture.EXPECTED)
+    for k, a in again.items():
+        np.testing.assert_array_equal(fx[k], a, err_msg=k)
+    assert mp.mp.dps == lie_fixture.DIGITS
 
 
 def test_lie_primitives(oracle, hm):

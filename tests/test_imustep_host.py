@@ -3,7 +3,6 @@ the test only (tests/host_imustep_check.cpp) and compared with the NumPy restate
 of tests/test_navjac_host.py for fp64 device math -- including w = 0 exactly and |w dt| = 1e-9, the small-angle branches."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,13 +14,10 @@ sys.path.insert(0, HERE)
 
 @pytest.fixture(scope="module")
 def hs():
-    out = os.path.join(HERE, "_build", "libhostimustep.so")
-    src = os.path.join(HERE, "host_imustep_check.cpp")
-    hdrs = [os.path.join(HERE, "..", "ctrl-vio_amd", "csrc", f) for f in ("so3.hpp", "factors.hpp")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    lib = C.CDLL(out)
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import devprobe
+    lib = devprobe.host_lib("libhostimustep.so", "host_imustep_check.cpp")          # one build rule for every host check
     lib.hm_imu_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
     lib.hm_imu_step.restype = None
     return lib

@@ -3,7 +3,6 @@ end state to the image point, compiled with g++ for the test only (tests/host_pr
 (tests/predproj_helpers.py) at rtol 1e-11, the bound of tests/test_projjac_host.py."""
 import ctypes as C
 import os
-import subprocess
 import sys
 from types import SimpleNamespace
 
@@ -19,13 +18,10 @@ CASES = [(1.0, 0.0), (1.0, 1e-9), (0.7, 0.036), (25.0, 0.036)]
 
 @pytest.fixture(scope="module")
 def hp():
-    out = os.path.join(HERE, "_build", "libhostpredjac.so")
-    src = os.path.join(HERE, "host_predjac_check.cpp")
-    hdrs = [os.path.join(HERE, "..", "ctrl-vio_amd", "csrc", f) for f in ("so3.hpp", "factors.hpp")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    lib = C.CDLL(out)
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import devprobe
+    lib = devprobe.host_lib("libhostpredjac.so", "host_predjac_check.cpp")          # one build rule for every host check
     lib.hm_pred_jac.argtypes = [C.c_void_p] * 4 + [C.c_double] + [C.c_void_p] * 8
     lib.hm_pred_jac.restype = None
     return lib

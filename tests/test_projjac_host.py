@@ -3,7 +3,6 @@ compiled with g++ for the test only (tests/host_projjac_check.cpp) and compared 
 rtol 1e-11, the bound of tests/test_posejac_host.py and the convention of tests/test_device_math_host.py for fp64 device math."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,13 +18,10 @@ CASES = [((2, 0.3, 120), (4, 0.75, 300)), ((4, 0.0, 0), (3, 0.6, 17)), ((1, 0.9,
 
 @pytest.fixture(scope="module")
 def hp():
-    out = os.path.join(HERE, "_build", "libhostprojjac.so")
-    src = os.path.join(HERE, "host_projjac_check.cpp")
-    hdrs = [os.path.join(HERE, "..", "ctrl-vio_amd", "csrc", f) for f in ("so3.hpp", "factors.hpp")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    lib = C.CDLL(out)
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import devprobe
+    lib = devprobe.host_lib("libhostprojjac.so", "host_projjac_check.cpp")          # one build rule for every host check
     lib.hm_proj_jac.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 7
     lib.hm_proj_jac.restype = None
     return lib

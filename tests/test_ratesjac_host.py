@@ -3,7 +3,6 @@
 tests/test_device_math_host.py for fp64 device math."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,13 +14,10 @@ sys.path.insert(0, HERE)
 
 @pytest.fixture(scope="module")
 def hr():
-    out = os.path.join(HERE, "_build", "libhostrates.so")
-    src = os.path.join(HERE, "host_rates_check.cpp")
-    hdrs = [os.path.join(HERE, "..", "ctrl-vio_amd", "csrc", f) for f in ("so3.hpp", "factors.hpp")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    return C.CDLL(out)
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import devprobe
+    return devprobe.host_lib("libhostrates.so", "host_rates_check.cpp")          # one build rule for every host check
 
 
 def _p(a):

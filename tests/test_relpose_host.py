@@ -3,7 +3,6 @@ only (tests/host_relpose_check.cpp) and compared with the NumPy restatement (tes
 tests/test_navjac_host.py and the convention of tests/test_device_math_host.py for fp64 device math."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -19,13 +18,10 @@ PAIRS = [((2, 0.3), (4, 0.75)), ((1, 0.9), (9, 0.37)), ((5, 0.37), (5, 0.87)), (
 
 @pytest.fixture(scope="module")
 def hr():
-    out = os.path.join(HERE, "_build", "libhostrelpose.so")
-    src = os.path.join(HERE, "host_relpose_check.cpp")
-    hdrs = [os.path.join(HERE, "..", "ctrl-vio_amd", "csrc", f) for f in ("so3.hpp", "factors.hpp")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
-    lib = C.CDLL(out)
+    if HERE not in sys.path:
+        sys.path.insert(0, HERE)
+    import devprobe
+    lib = devprobe.host_lib("libhostrelpose.so", "host_relpose_check.cpp")          # one build rule for every host check
     lib.hm_rel_pose_jac.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 5
     lib.hm_rel_pose_jac.restype = None
     return lib
